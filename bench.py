@@ -9,9 +9,12 @@ A step = one pass of the compress path (candidates -> walk -> entropy -> frame a
 64 KiB chunks, level 3); the Silesia corpus is not available offline, so the chunks come from the synthetic
 Zipf-token log stream of SURVEY.md 8(d) unless --corpus PATH is given.  Chunks shard across ranks with no
 data-path collective (weak scaling: every GPU gets its own --chunks chunks).
-Rank 0 prints one JSON line.  The same line carries "decode" (BASELINE config 4 shape: many ~32 KiB frames, the one path the
-reference implements itself), "ratio_by_class" (HIP encoder vs upstream libzstd on the mixed corpus of tests/_corpus.py) and
-"libzstd_yardstick" (upstream libzstd on the host cores: NOT the reference, which has no encoder and cannot run here).
+Rank 0 prints one JSON line.  A plain run does only what that line's headline needs: set up, warm up, time the --steps steps, write
+the last timed step's output if --dump-outputs is given, print.  With --full the same line also carries the per-kernel times (a second
+pass of the steps), "sustained", the oracle check of the timed output, "cpu_baseline", "decode" (BASELINE config 4 shape: many ~32 KiB
+frames, the one path the reference implements itself), "throughput_by_class", "ratio_by_class" (HIP encoder vs upstream libzstd on the
+mixed corpus of tests/_corpus.py) and "libzstd_yardstick" (upstream libzstd on the host cores: NOT the reference, which has no encoder
+and cannot run here); with more than one rank also "io_inclusive".
 
 --gpus N without a torch.distributed environment (no WORLD_SIZE) starts the N ranks itself, before anything touches the GPU.
 """
@@ -324,6 +327,28 @@ def decode_leg(bc, args, rank, world, distributed, barrier, torch, dist):
     return out
 
 
+DUMP_FRAME_BYTES = 32 << 20      # budget of the frame sample in float32; the sizes of every chunk come on top
+
+
+def dump_outputs(out_dir, d_dst, doffs, d_sizes, bound):
+    """What a caller of the compress path receives from the last timed step, so that two builds compare output for output:
+    compressed_sizes.npy   float64 (chunks,): every chunk's frame size
+    compressed_frames.npy  float32 (k, bound): the frames of k chunks drawn with a fixed seed (as many as fit in DUMP_FRAME_BYTES),
+                           byte values, zero past each frame's size"""
+    n = len(doffs)
+    csz = d_sizes.cpu().numpy().astype(np.uint32)
+    assert (csz < 0xFFFFFF88).all(), "a chunk failed to compress"
+    k = min(n, DUMP_FRAME_BYTES // (4 * bound))
+    pick = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    frames = np.zeros((k, bound), dtype=np.float32)
+    for row, i in enumerate(pick):
+        o, s = int(doffs[i]), int(csz[i])
+        frames[row, :s] = d_dst[o:o + s].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "compressed_sizes.npy"), csz.astype(np.float64))
+    np.save(os.path.join(out_dir, "compressed_frames.npy"), frames)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -335,20 +360,23 @@ def main():
     ap.add_argument("--corpus", type=str, default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--with-io", action="store_true", help="with --force-dist on one GPU: also time the job that starts and ends on rank 0: scatter shards, compress, pack, "
-                    "gather frames (SURVEY 8e steps 1-4); with more than one rank that leg always runs; reported as io_inclusive, never as value")
+                    "gather frames (SURVEY 8e steps 1-4); with --full and more than one rank that leg always runs; reported as io_inclusive, never as value")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even for one rank: exercises the N > 1 code path on a 1-GPU box")
-    ap.add_argument("--decode-frames", type=int, default=57344, help="frames of --decode-frame-size bytes decoded per step of the decode leg (0: no decode leg)")
+    ap.add_argument("--decode-frames", type=int, default=57344, help="with --full: frames of --decode-frame-size bytes decoded per step of the decode leg (0: no decode leg)")
     ap.add_argument("--decode-frame-size", type=int, default=32768)
-    ap.add_argument("--no-extras", action="store_true", help="skip ratio_by_class and libzstd_yardstick")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip sustained, throughput_by_class, ratio_by_class, libzstd_yardstick and the decode leg's extras")
     ap.add_argument("--class-bytes", type=int, default=64 << 20, help="distinct bytes per data class of throughput_by_class")
     ap.add_argument("--dry-run-gloo", action="store_true", help="CPU rehearsal of the launch path: gloo process group, no GPU work; prints the ranks that ran")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: per-kernel times, sustained clocks, oracle check, CPU baselines, the decode leg, "
+                    "per-class throughput and ratio, libzstd yardsticks, io_inclusive with more than one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="rank 0 writes what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
 
     rank = int(os.environ.get("RANK", "0")); local_rank = int(os.environ.get("LOCAL_RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     class_data, class_gen_s = (None, 0.0)
-    if rank == 0 and not args.no_extras and not args.dry_run_gloo:
+    if rank == 0 and args.full and not args.no_extras and not args.dry_run_gloo:
         class_data, class_gen_s = class_corpus(args)          # (a pool of forked processes: before torch / HIP are initialised)
     import torch
     assert world == args.gpus or (args.gpus == 1 and args.force_dist), f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU"
@@ -413,16 +441,21 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     ktimes = bc.kernel_times()
-    # every kernel's time: the same steps once more with events around every launch (ten event records a step cost ~2 % of it: not in the timed region)
-    bc.enable_timing(True)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    ktimes_all = bc.kernel_times()
     bc.enable_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_dst, doffs, d_sizes, bound)
+    ktimes_all = None
+    if args.full:
+        # every kernel's time: the same steps once more with events around every launch (ten event records a step cost ~2 % of it: not in the timed region)
+        bc.enable_timing(True)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        ktimes_all = bc.kernel_times()
+        bc.enable_timing(False)
     # sustained clocks: the same step back to back for >= 2 s, outside the headline's timed region
     sustained = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         t1 = time.perf_counter(); k = 0
         while time.perf_counter() - t1 < 2.0:
             for _ in range(50):
@@ -438,9 +471,9 @@ def main():
         elapsed = float(t.item())
 
     io_inclusive = None
-    if distributed and (world > 1 or args.with_io):
-        # the whole job from rank 0's input to rank 0's frames; inputs and outputs stay in HBM (no PCIe leg).  Default whenever there is
-        # more than one rank: this is the path north_star names (RCCL scatter of input shards, gather of frames)
+    if distributed and ((args.full and world > 1) or args.with_io):
+        # the whole job from rank 0's input to rank 0's frames; inputs and outputs stay in HBM (no PCIe leg).  Default under --full whenever
+        # there is more than one rank: this is the path of SURVEY 8e (RCCL scatter of input shards, gather of frames)
         all_sizes = np.full(n * world, cs, dtype=np.uint32)
         g_src = torch.cat([d_src] * world) if rank == 0 else None          # root holds world x the per-GPU batch
         d_packed = torch.empty(n * stride, dtype=torch.uint8, device="cuda")
@@ -469,7 +502,7 @@ def main():
                             "note": "rank 0 input -> scatter (grouped send/recv) -> compress -> pack -> all-gather sizes -> gather frames to rank 0; device memory only; "
                                     "a sample of every rank's frames decoded on rank 0 with oracle D after the timed region"}
 
-    decode = decode_leg(bc, args, rank, world, distributed, barrier, torch, dist if distributed else None) if args.decode_frames else None
+    decode = decode_leg(bc, args, rank, world, distributed, barrier, torch, dist if distributed else None) if (args.full and args.decode_frames) else None
 
     csz = d_sizes.cpu().numpy().astype(np.uint32)
     assert (csz < 0xFFFFFF88).all(), "a chunk failed to compress"
@@ -505,11 +538,26 @@ def main():
                 traffic_note = "no traffic file: %s" % type(e).__name__
             roofline = {"bound": "hbm", "kernel": name, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "algorithmic_bytes_per_launch": int(per_launch_bytes),
-                        "avg_launch_ms": round(avg * 1e3, 4),
-                        "kernels_ms_per_step": {k: round(v[0] / args.steps * 1e3, 4) for k, v in ktimes_all.items()},
-                        "kernels_ms_per_step_note": "second pass of the same steps with events around every launch; avg_launch_ms is from the timed region"}
+                        "avg_launch_ms": round(avg * 1e3, 4)}
+            if ktimes_all is not None:
+                roofline["kernels_ms_per_step"] = {k: round(v[0] / args.steps * 1e3, 4) for k, v in ktimes_all.items()}
+                roofline["kernels_ms_per_step_note"] = "second pass of the same steps with events around every launch; avg_launch_ms is from the timed region"
             if traffic_note:
                 roofline["traffic_note"] = traffic_note
+        ratio = total_in / total_out
+        # BASELINE.json's metric at its own configuration; other levels / chunk sizes (development runs) are labelled as what they are
+        metric = "GiB/s compress @ level 3, 64 KiB chunks" if (args.level == 3 and cs == 65536) else f"GiB/s compress @ level {args.level}, {cs // 1024} KiB chunks"
+        out = {"metric": metric, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world,
+               "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "host_issue_ms_per_step": round(issued / args.steps * 1e3, 3), "higher_is_better": True,
+               "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": data_label, "ranks": world,
+               "config": {"workload": f"{n} independent {cs} B chunks per GPU per step, level {args.level}, BASELINE config[1] shape "
+                                      f"(Silesia unavailable offline -> Zipf-token log stream, SURVEY 8d)", "chunks_per_gpu": n,
+                          "chunk_bytes": cs, "level": args.level, "parallelism": f"chunks sharded over {world} GPU(s), no collective in the data path"},
+               "ratio": round(ratio, 4), "hbm_read_roofline_frac": round(total_in * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 5),
+               "roofline": roofline, "datagen_s": round(gen_s, 2), "library": bc.L.zsmi_versionString().decode()}
+        if not args.full:
+            print(json.dumps(out))
+    if rank == 0 and args.full:
         # exactness spot check of the timed output + ratio yardstick
         import _oracle as O
         sample = list(range(0, n, max(1, n // 16)))[:16]
@@ -518,7 +566,6 @@ def main():
             f = dst_host[int(doffs[i]):int(doffs[i]) + int(csz[i])].tobytes()
             c = host[i * cs:(i + 1) * cs].tobytes()
             assert O.decompress(f, len(c)) == c, "timed output must decode under the restated reference decoder"
-        ratio = total_in / total_out
         ratio_vs_zstd = None
         if O.libzstd():
             z = sum(len(O.zstd_compress(host[i * cs:(i + 1) * cs].tobytes(), args.level)) for i in sample)
@@ -536,18 +583,8 @@ def main():
                 dt = d if dt is None else min(dt, d)
             cpu = {"value": round(m * cs / dt / (1 << 30), 4), "unit": "GiB/s", "cores": cores, "kind": "port",
                    "sample": f"{m} x {cs} B chunks of the same batch, oracle E (scalar statement of the HIP encoder), one thread per core"}
-        # BASELINE.json's metric at its own configuration; other levels / chunk sizes (development runs) are labelled as what they are
-        metric = "GiB/s compress @ level 3, 64 KiB chunks" if (args.level == 3 and cs == 65536) else f"GiB/s compress @ level {args.level}, {cs // 1024} KiB chunks"
-        out = {"metric": metric, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "host_issue_ms_per_step": round(issued / args.steps * 1e3, 3), "higher_is_better": True,
-               "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": data_label, "ranks": world,
-               "config": {"workload": f"{n} independent {cs} B chunks per GPU per step, level {args.level}, BASELINE config[1] shape "
-                                      f"(Silesia unavailable offline -> Zipf-token log stream, SURVEY 8d)", "chunks_per_gpu": n,
-                          "chunk_bytes": cs, "level": args.level, "parallelism": f"chunks sharded over {world} GPU(s), no collective in the data path"},
-               "ratio": round(ratio, 4), "ratio_vs_libzstd_same_level": ratio_vs_zstd,
-               "hbm_read_roofline_frac": round(total_in * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 5),
-               "roofline": roofline, "cpu_baseline": cpu, "datagen_s": round(gen_s, 2),
-               "library": bc.L.zsmi_versionString().decode()}
+        out["ratio_vs_libzstd_same_level"] = ratio_vs_zstd
+        out["cpu_baseline"] = cpu
         if sustained:
             out["sustained"] = sustained
         if decode:

@@ -1,6 +1,8 @@
 import re, csv, glob, collections, sys, os
 tag = sys.argv[1]
 root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+if len(sys.argv) > 2:                   # the directory the passes wrote to, when not the default
+    root = sys.argv[2]
 res = collections.defaultdict(dict)
 for d in "abcdef":
     fs = glob.glob(f"{root}/pmc_{tag}_{d}/*/*_counter_collection.csv")
