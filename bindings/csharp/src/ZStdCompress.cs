@@ -12,6 +12,8 @@ namespace EPAM.Deltix.ZStd
         [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
         static extern UIntPtr zsmi_compressBound(UIntPtr srcSize);
         [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
+        static extern UIntPtr zsmi_compress_usingDict(void* dst, UIntPtr dstCapacity, void* src, UIntPtr srcSize, void* dict, UIntPtr dictSize, int level);
+        [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
         static extern IntPtr zsmi_getErrorName(UIntPtr code);
 
         public const int DefaultLevel = 3;
@@ -25,6 +27,14 @@ namespace EPAM.Deltix.ZStd
             if (dstCapacity > (uint)dst.Length || srcSize > (uint)src.Length) throw new ArgumentOutOfRangeException();
             fixed (byte* d = dst, s = src)
                 return unchecked((uint)(ulong)zsmi_compress(d, (UIntPtr)dstCapacity, s, (UIntPtr)srcSize, compressionLevel));
+        }
+        // the same with a dictionary (raw content or formatted, as ZStdDecompress's usingDict decode takes it); null / empty = Compress
+        public static uint CompressUsingDict(byte[] dst, uint dstCapacity, byte[] src, uint srcSize, byte[] dict, int compressionLevel = DefaultLevel)
+        {
+            if (dst == null || src == null) throw new ArgumentNullException(dst == null ? nameof(dst) : nameof(src));
+            if (dstCapacity > (uint)dst.Length || srcSize > (uint)src.Length) throw new ArgumentOutOfRangeException();
+            fixed (byte* d = dst, s = src, dc = dict)
+                return unchecked((uint)(ulong)zsmi_compress_usingDict(d, (UIntPtr)dstCapacity, s, (UIntPtr)srcSize, dc, (UIntPtr)(uint)(dict?.Length ?? 0), compressionLevel));
         }
         public static uint Compress(byte[] dst, byte[] src, int compressionLevel = DefaultLevel) => Compress(dst, (uint)dst.Length, src, (uint)src.Length, compressionLevel);
 

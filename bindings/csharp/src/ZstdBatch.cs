@@ -12,6 +12,10 @@ namespace EPAM.Deltix.ZStd
         [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
         static extern int zsmi_compressBatchHost(IntPtr ctx, void* src, ulong* srcOffsets, uint* srcSizes, uint n, void* dst, ulong* dstOffsets, uint* dstSizes, int level);
         [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
+        static extern int zsmi_compressBatchHost_usingDict(IntPtr ctx, void* src, ulong* srcOffsets, uint* srcSizes, uint n, void* dst, ulong* dstOffsets, uint* dstSizes, int level, void* dict, UIntPtr dictSize);
+        [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
+        static extern int zsmi_compressBatchDevice_usingDict(IntPtr ctx, void* dSrc, ulong* srcOffsets, uint* srcSizes, uint n, void* dDst, ulong* dstOffsets, uint* dDstSizes, int level, void* dDict, UIntPtr dictSize);
+        [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
         static extern int zsmi_decompressBatchHost(IntPtr ctx, void* src, ulong* srcOffsets, uint* srcSizes, uint n, void* dst, ulong* dstOffsets, uint* dstCaps, uint* dstSizes);
 
         IntPtr ctx;
@@ -27,6 +31,12 @@ namespace EPAM.Deltix.ZStd
         {
             fixed (byte* s = src, d = dst) fixed (ulong* so = srcOffsets, dof = dstOffsets) fixed (uint* ss = srcSizes, ds = dstSizes)
             { int rc = zsmi_compressBatchHost(ctx, s, so, ss, (uint)srcSizes.Length, d, dof, ds, level); if (rc != 0) throw new InvalidOperationException("zsmi error " + rc); }
+        }
+        // one dictionary for every chunk (raw content or formatted; null / empty = Compress)
+        public void CompressUsingDict(byte[] src, ulong[] srcOffsets, uint[] srcSizes, byte[] dst, ulong[] dstOffsets, uint[] dstSizes, byte[] dict, int level = 3)
+        {
+            fixed (byte* s = src, d = dst, dc = dict) fixed (ulong* so = srcOffsets, dof = dstOffsets) fixed (uint* ss = srcSizes, ds = dstSizes)
+            { int rc = zsmi_compressBatchHost_usingDict(ctx, s, so, ss, (uint)srcSizes.Length, d, dof, ds, level, dc, (UIntPtr)(uint)(dict?.Length ?? 0)); if (rc != 0) throw new InvalidOperationException("zsmi error " + rc); }
         }
         public void Decompress(byte[] src, ulong[] srcOffsets, uint[] srcSizes, byte[] dst, ulong[] dstOffsets, uint[] dstCaps, uint[] dstSizes)
         {

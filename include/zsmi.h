@@ -69,6 +69,13 @@ unsigned long long zsmi_getDecompressedSize(const void *src, size_t srcSize);
  * One frame for the whole input.  level <= 2: fast parameters, level >= 3: default parameters. */
 size_t zsmi_compress(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level);
 
+/* replaces: ZSTD_compress_usingDict(cctx, dst, dstCapacity, src, srcSize, dict, dictSize, level) (no cctx, as zsmi_compress)
+ * One frame for the whole input, to be decoded with the same dictionary (zsmi_decompress_usingDict).  dict: raw content, or a formatted
+ * dictionary (magic 0xEC30A437): its ID goes into the frame header, its recent offsets start the first block; its entropy tables are not
+ * used.  Matches reach into the last 64 KiB of the content for inputs of <= 64 KiB (longer inputs: none).  NULL / 0 = zsmi_compress, byte
+ * for byte.  Errors: dictionary_corrupted (30) for a formatted dictionary the decoder would refuse, before anything runs on the device. */
+size_t zsmi_compress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level);
+
 /* replaces: commented macro ZSTD_COMPRESSBOUND  csharp/src/ZStd.cs:144-145 (plus this codec's per-64 KiB block headers) */
 size_t zsmi_compressBound(size_t srcSize);
 
@@ -93,6 +100,13 @@ int zsmi_sync(zsmi_ctx *ctx);
 int zsmi_compressBatchDevice(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                              uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level);
 
+/* The same with one dictionary for every chunk of the call (dDict: device memory; rules as zsmi_compress_usingDict: chunks of <= 64 KiB
+ * may match into the last 64 KiB of its content).  The dictionary is read back and parsed on the host first: the call waits for the
+ * context's stream once.  NULL / 0 = zsmi_compressBatchDevice. */
+int zsmi_compressBatchDevice_usingDict(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                       uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
+                                       const void *dDict, size_t dictSize);
+
 /* Asynchronous on the context's stream.  Each frame i = src[srcOffsets[i] .. +srcSizes[i]) may hold several
  * concatenated / skippable frames (same rules as zsmi_decompress); dstCaps[i] is the room at dstOffsets[i]. */
 int zsmi_decompressBatchDevice(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
@@ -108,6 +122,9 @@ int zsmi_decompressBatchDevice_usingDict(zsmi_ctx *ctx, const void *dSrc, const 
 /* Host-buffer forms: stage through device memory, run the device form, copy back, synchronise. */
 int zsmi_compressBatchHost(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                            uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level);
+int zsmi_compressBatchHost_usingDict(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                     uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
+                                     const void *dict, size_t dictSize);
 int zsmi_decompressBatchHost(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                              uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps,
                              uint32_t *dstSizes);

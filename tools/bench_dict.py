@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""GPU box: compression with a dictionary against compression without one (device-resident, per-call wall time, like tools/bench_sizes.py).
+One JSON line per (class, chunk size, level): GiB/s and ratio with and without the dictionary (the class's 64 KiB trained dictionary of
+tests/golden/libzstd_fixtures_dict_compress.npz), and our compressed size over libzstd's with the trained dictionary and with its content
+alone (the first 64 chunks; absent without libzstd).  --kernels: per-kernel times of one dictionary call (zsmi_enableKernelTiming)."""
+import argparse, ctypes, json, os, sys, time
+import numpy as np, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _data as D, _oracle as O, _corpus as C
+from zstandard_amd import BatchCodec, _lib
+
+FIXC = os.path.join(ROOT, "tests", "golden", "libzstd_fixtures_dict_compress.npz")
+
+
+def class_bytes(cls, n):
+    if cls == "zipf":
+        return D.zipf_log(n).tobytes()
+    return getattr(C, cls)(n)[:n]
+
+
+def zstd_sizes(chunks, dic, level):
+    Z = O.libzstd()
+    if not Z:
+        return None
+    sz, vp, cp = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_char_p
+    Z.ZSTD_createCCtx.restype = vp
+    Z.ZSTD_compress_usingDict.restype = sz; Z.ZSTD_compress_usingDict.argtypes = [vp, vp, sz, cp, sz, cp, sz, ctypes.c_int]
+    cctx = Z.ZSTD_createCCtx(); total = 0
+    for c in chunks:
+        cap = Z.ZSTD_compressBound(len(c)); out = ctypes.create_string_buffer(cap)
+        r = Z.ZSTD_compress_usingDict(cctx, out, cap, c, len(c), dic, len(dic), level); assert not Z.ZSTD_isError(r)
+        total += r
+    return total
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bytes", type=int, default=64 << 20, help="input bytes per class")
+    ap.add_argument("--classes", default="zipf,json_records,xml_records,csv_records,binary_table")
+    ap.add_argument("--chunks", default="1024,4096,16384,65536")
+    ap.add_argument("--levels", default="3")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--kernels", action="store_true")
+    a = ap.parse_args()
+    fix = np.load(FIXC)
+    dev = torch.device("cuda:0")
+    bc = BatchCodec(device=0)
+    Z = _lib.lib()
+    for cls in a.classes.split(","):
+        data = class_bytes(cls, a.bytes)
+        dsrc = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).to(dev)
+        dic = fix["trained_" + cls].tobytes()
+        content = dic[dic.find(bytes([1, 0, 0, 0, 4, 0, 0, 0, 8, 0, 0, 0]), 8) + 12:]
+        ddict = torch.from_numpy(np.frombuffer(dic, dtype=np.uint8).copy()).to(dev)
+        for cs in [int(x) for x in a.chunks.split(",")]:
+            n = len(data) // cs
+            off = np.arange(n, dtype=np.uint64) * cs; sz = np.full(n, cs, dtype=np.uint32)
+            bound = int(Z.zsmi_compressBound(cs)); doff = np.arange(n, dtype=np.uint64) * bound
+            ddst = torch.empty(n * bound, dtype=torch.uint8, device=dev); dsz = torch.empty(n, dtype=torch.int32, device=dev)
+            for lvl in [int(x) for x in a.levels.split(",")]:
+                rec = {"class": cls, "chunk": cs, "level": lvl, "chunks": n}
+                for tag, dp, dn in (("plain", 0, 0), ("dict", ddict.data_ptr(), len(dic))):
+                    run = lambda: bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), lvl, dp, dn)
+                    for _ in range(2):
+                        run()
+                    bc.sync(); t0 = time.perf_counter()
+                    for _ in range(a.steps):
+                        run()
+                    bc.sync(); dt = (time.perf_counter() - t0) / a.steps
+                    sizes = dsz.cpu().numpy().view(np.uint32)
+                    assert (sizes < 0xFFFFFF88).all()
+                    host = ddst[:min(n, 64) * bound].cpu().numpy()
+                    for i in (0, min(n, 64) - 1):                     # spot check under oracle D
+                        f = host[int(doff[i]):int(doff[i]) + int(sizes[i])].tobytes()
+                        c = data[i * cs:(i + 1) * cs]
+                        assert (O.decompress_using_dict(f, cs, dic) if dn else O.decompress(f, cs)) == c
+                    rec["gib_s_" + tag] = round(n * cs / dt / 2**30, 2)
+                    rec["ratio_" + tag] = round(n * cs / float(sizes.sum()), 4)
+                    if dn:
+                        k = min(n, 64); ours = float(sizes[:k].sum())
+                        chunks = [data[i * cs:(i + 1) * cs] for i in range(k)]
+                        zt, zc = zstd_sizes(chunks, dic, lvl), zstd_sizes(chunks, content, lvl)
+                        if zt:
+                            rec["vs_libzstd_trained"] = round(ours / zt, 4); rec["vs_libzstd_content"] = round(ours / zc, 4)
+                        if a.kernels:
+                            bc.enable_timing(True); run(); bc.sync()
+                            rec["kernels_ms"] = {k2: round(v[0] * 1e3, 3) for k2, v in bc.kernel_times().items()}
+                            bc.enable_timing(False)
+                rec["dict_over_plain"] = round(rec["gib_s_dict"] / rec["gib_s_plain"], 3)
+                print(json.dumps(rec), flush=True)
+            del ddst, dsz
+
+
+if __name__ == "__main__":
+    main()

@@ -83,6 +83,7 @@ def lib():
     L.zsmi_compressBound.restype = sz; L.zsmi_compressBound.argtypes = [sz]
     L.zsmi_getDecompressedSize.restype = ctypes.c_ulonglong; L.zsmi_getDecompressedSize.argtypes = [vp, sz]
     L.zsmi_compress.restype = sz; L.zsmi_compress.argtypes = [vp, sz, vp, sz, i32]
+    L.zsmi_compress_usingDict.restype = sz; L.zsmi_compress_usingDict.argtypes = [vp, sz, vp, sz, vp, sz, i32]
     L.zsmi_decompress.restype = sz; L.zsmi_decompress.argtypes = [vp, sz, vp, sz]
     L.zsmi_decompress_usingDict.restype = sz; L.zsmi_decompress_usingDict.argtypes = [vp, sz, vp, sz, vp, sz]
     L.zsmi_createCtx.restype = vp; L.zsmi_createCtx.argtypes = [i32, vp]
@@ -91,6 +92,8 @@ def lib():
     L.zsmi_compressBatchDevice.restype = i32; L.zsmi_compressBatchDevice.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32]
     L.zsmi_decompressBatchDevice.restype = i32; L.zsmi_decompressBatchDevice.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_compressBatchHost.restype = i32; L.zsmi_compressBatchHost.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32]
+    L.zsmi_compressBatchDevice_usingDict.restype = i32; L.zsmi_compressBatchDevice_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32, vp, sz]
+    L.zsmi_compressBatchHost_usingDict.restype = i32; L.zsmi_compressBatchHost_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32, vp, sz]
     L.zsmi_decompressBatchHost.restype = i32; L.zsmi_decompressBatchHost.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_decompressBatchHost_usingDict.restype = i32; L.zsmi_decompressBatchHost_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
     L.zsmi_decompressBatchDevice_usingDict.restype = i32; L.zsmi_decompressBatchDevice_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
@@ -109,4 +112,5 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_compress", "zsmi_compressBound", "zsmi_createCtx", "zsmi_freeCtx", "zsmi_sync",
            "zsmi_compressBatchDevice", "zsmi_decompressBatchDevice", "zsmi_compressBatchHost", "zsmi_decompressBatchHost",
            "zsmi_decompress_usingDict", "zsmi_decompressBatchDevice_usingDict", "zsmi_decompressBatchHost_usingDict",
+           "zsmi_compress_usingDict", "zsmi_compressBatchDevice_usingDict", "zsmi_compressBatchHost_usingDict",
            "zsmi_packFramesDevice", "zsmi_enableKernelTiming", "zsmi_getKernelTimes", "zsmi_versionString", "zsmi_decodeScratchBytes", "zsmi_shutdown"]

@@ -76,10 +76,12 @@ class ZstdDecompressor:
 
 
 class ZstdCompressor:
-    """One frame per call; level <= 2 fast parameters, level >= 3 default parameters."""
+    """One frame per call; level <= 2 fast parameters, level >= 3 default parameters.  dictionary: raw content or a formatted
+    dictionary (ZSTD_compress_usingDict); the frames decode with the same dictionary (zsmi_decompress_usingDict)."""
 
-    def __init__(self, level=3):
+    def __init__(self, level=3, dictionary=None):
         self.level = level
+        self.dictionary = bytes(dictionary) if dictionary else b""
 
     @staticmethod
     def compressBound(n: int) -> int:
@@ -90,7 +92,10 @@ class ZstdCompressor:
         s, sn = _buf(src)
         cap = L.zsmi_compressBound(sn)
         out = ctypes.create_string_buffer(cap)
-        r = L.zsmi_compress(out, cap, s, sn, self.level)
+        if self.dictionary:
+            r = L.zsmi_compress_usingDict(out, cap, s, sn, self.dictionary, len(self.dictionary), self.level)
+        else:
+            r = L.zsmi_compress(out, cap, s, sn, self.level)
         if L.zsmi_isError(r):
             raise RuntimeError(L.zsmi_getErrorName(r).decode())
         return out.raw[:r]
@@ -126,9 +131,17 @@ class BatchCodec:
     def _p(a):
         return a.ctypes.data_as(ctypes.c_void_p)
 
-    def compress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, d_dst_sizes_ptr, level=3):
+    def compress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, d_dst_sizes_ptr, level=3, d_dict_ptr=0, dict_size=0):
+        """d_dict_ptr / dict_size: one dictionary (device memory) for every chunk of the call (zsmi_compressBatchDevice_usingDict)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        if d_dict_ptr and dict_size:
+            rc = self.L.zsmi_compressBatchDevice_usingDict(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
+                                                           ctypes.c_void_p(d_dst_ptr), self._p(do), ctypes.c_void_p(d_dst_sizes_ptr), level,
+                                                           ctypes.c_void_p(d_dict_ptr), dict_size)
+            if rc:
+                raise RuntimeError(f"zsmi_compressBatchDevice_usingDict: error {rc}")
+            return
         rc = self.L.zsmi_compressBatchDevice(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
                                              ctypes.c_void_p(d_dst_ptr), self._p(do), ctypes.c_void_p(d_dst_sizes_ptr), level)
         if rc:
@@ -150,8 +163,9 @@ class BatchCodec:
         if rc:
             raise RuntimeError(f"zsmi_packFramesDevice: error {rc}")
 
-    def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3):
-        """returns (arena uint8, dst_offsets uint64, dst_sizes uint32)"""
+    def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b""):
+        """returns (arena uint8, dst_offsets uint64, dst_sizes uint32).  dictionary: one for every chunk (raw content or a formatted
+        dictionary; zsmi_compressBatchHost_usingDict)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         n = len(ss)
         bounds = np.array([self.L.zsmi_compressBound(int(s)) for s in ss], dtype=np.uint64) if n < 4096 else \
@@ -161,6 +175,13 @@ class BatchCodec:
             do[1:] = np.cumsum(bounds)[:-1]
         arena = np.zeros(int(bounds.sum()), dtype=np.uint8)
         dsz = np.zeros(n, dtype=np.uint32)
+        if dictionary:
+            dbuf = np.frombuffer(bytes(dictionary), dtype=np.uint8)
+            rc = self.L.zsmi_compressBatchHost_usingDict(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), level,
+                                                         self._p(dbuf), len(dbuf))
+            if rc:
+                raise RuntimeError(f"zsmi_compressBatchHost_usingDict: error {rc}")
+            return arena, do, dsz
         rc = self.L.zsmi_compressBatchHost(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), level)
         if rc:
             raise RuntimeError(f"zsmi_compressBatchHost: error {rc}")

@@ -667,15 +667,19 @@ __device__ __forceinline__ void loadRangesWave(const ZsRangeHdr *hdr, uint32_t *
 struct ZsChunkDesc { uint64_t srcOff; uint64_t dstOff; uint32_t size; uint32_t firstBlock; uint32_t nBlocks; uint32_t pad; };
 
 // frame header of a chunk (magic + FHD + FCS, single segment); returns its size.  One thread writes it.
-__device__ __forceinline__ uint32_t zs_frame_header(uint8_t *out, uint32_t size, bool writer)
+// dictID != 0 (dictionary calls): the dictionary ID field between FHD and FCS, in 1, 2 or 4 bytes (the fewest that hold it, as libzstd)
+__device__ __forceinline__ uint32_t zs_frame_header(uint8_t *out, uint32_t size, bool writer, uint32_t dictID = 0)
 {
+    const uint32_t didCode = (dictID != 0) + (dictID >= 256) + (dictID >= 65536), didSize = didCode == 3 ? 4 : didCode;
     if (writer) {
         out[0] = 0x28; out[1] = 0xB5; out[2] = 0x2F; out[3] = 0xFD;
-        if (size < 256) { out[4] = 0x20; out[5] = (uint8_t)size; }
-        else if (size < 65536 + 256) { out[4] = 0x60; const uint32_t v = size - 256; out[5] = (uint8_t)v; out[6] = (uint8_t)(v >> 8); }
-        else { out[4] = 0xA0; out[5] = (uint8_t)size; out[6] = (uint8_t)(size >> 8); out[7] = (uint8_t)(size >> 16); out[8] = (uint8_t)(size >> 24); }
+        for (uint32_t k = 0; k < didSize; k++) out[5 + k] = (uint8_t)(dictID >> (8 * k));
+        uint8_t *f = out + didSize;
+        if (size < 256) { out[4] = 0x20 | didCode; f[5] = (uint8_t)size; }
+        else if (size < 65536 + 256) { out[4] = 0x60 | didCode; const uint32_t v = size - 256; f[5] = (uint8_t)v; f[6] = (uint8_t)(v >> 8); }
+        else { out[4] = 0xA0 | didCode; f[5] = (uint8_t)size; f[6] = (uint8_t)(size >> 8); f[7] = (uint8_t)(size >> 16); f[8] = (uint8_t)(size >> 24); }
     }
-    return (size < 256) ? 6 : (size < 65536 + 256 ? 7 : 9);
+    return ((size < 256) ? 6 : (size < 65536 + 256 ? 7 : 9)) + didSize;
 }
 // one block into its frame at out + pos (all threads of the workgroup); returns the bytes written.  A block is emitted compressed
 // iff both sections exist and literal section + sequence section < block size (else raw; RLE if flagged).
@@ -710,12 +714,14 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
 // literal gather + histogram (wavefront w takes ranges w and w+4), Huffman lengths by package-merge (256 threads),
 // table description (one lane), the 4 Huffman streams (one wavefront each)  -> litSec[], meta.{type, rleByte, litSecSize}
 // ---------------------------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG)
-k_encode_literals(const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks,
-                  const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll,
-                  uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, uint8_t *__restrict__ litSecAll,
-                  ZsBlockMeta *__restrict__ metas, int stopAt,
-                  const ZsChunkDesc *__restrict__ chunks, const uint8_t *__restrict__ seqSecAll, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes)
+// (k_encode_literals_dict: the same for a dictionary call, whose frame headers carry the dictionary's ID)
+#define ZS_LIT_PARAMS const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, \
+                      const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
+                      uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, uint8_t *__restrict__ litSecAll, \
+                      ZsBlockMeta *__restrict__ metas, int stopAt, \
+                      const ZsChunkDesc *__restrict__ chunks, const uint8_t *__restrict__ seqSecAll, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes
+#define ZS_LIT_ARGS src, blocks, seqAll, hdrAll, litsAll, streamAll, litSecAll, metas, stopAt, chunks, seqSecAll, dst, dstSizes
+__device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t dictID)
 {
     __shared__ K3Lds L;
     const uint32_t blk = blockIdx.x;
@@ -731,7 +737,7 @@ k_encode_literals(const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict
     // slot holds zsmi_compressBound(n) >= n + 27 bytes, the section never more than n + 3), every other block's in the section buffer
     const bool solo = bd.firstInChunk && bd.lastInChunk && !ZS_STOPPED;
     uint8_t *payload = litSecAll + (size_t)blk * ZS_LITSEC_STRIDE;
-    if (solo) { const ZsChunkDesc cd0 = chunks[bd.chunk]; payload = dst + cd0.dstOff + zs_frame_header(nullptr, cd0.size, false) + 3; }
+    if (solo) { const ZsChunkDesc cd0 = chunks[bd.chunk]; payload = dst + cd0.dstOff + zs_frame_header(nullptr, cd0.size, false, dictID) + 3; }
     const uint32_t cap = n + 512;
 
     // The block's literal side is done: its meta goes out; a chunk of ONE block is assembled right here (the sequences kernel ran before this
@@ -743,7 +749,7 @@ k_encode_literals(const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict
             ZsBlockMeta m_ = metas[blk]; m_.type = (tp); m_.rleByte = (rb); m_.litSecSize = (lsz); \
             const ZsChunkDesc cd_ = chunks[bd.chunk]; \
             uint8_t *out_ = dst + cd_.dstOff; \
-            uint32_t pos_ = zs_frame_header(out_, cd_.size, tid == 0); \
+            uint32_t pos_ = zs_frame_header(out_, cd_.size, tid == 0, dictID); \
             pos_ += zs_emit_block(out_, pos_, s, n, 1u, m_, payload, seqSecAll + (size_t)blk * ZS_SEQSEC_STRIDE, tid, 256); \
             if (tid == 0) dstSizes[bd.chunk] = pos_; \
         } \
@@ -1109,6 +1115,8 @@ k_encode_literals(const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict
     FINISH(2, litSecSize, 0);
     #undef FINISH
 }
+extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS) { encode_literals_block(ZS_LIT_ARGS, 0u); }
+extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals_dict(ZS_LIT_PARAMS, uint32_t dictID) { encode_literals_block(ZS_LIT_ARGS, dictID); }
 
 // ---------------------------------------------------------------------------------------------
 // k_encode_sequences : one wavefront per block.  Repcodes (parallel: two last-index scans), code
@@ -1216,11 +1224,13 @@ __device__ static void buildCTableWave(SeqLds &L, FseCT &ct, const int16_t *norm
 #define ZS_CHAIN_MINSEG 4u         // shortest segment, in blocks of 16 steps
 #endif
 static_assert(3u * ZS_CHAIN_CODES <= ZS_BLOCK_MAX + 64u && 3u * 2u * ZS_CHAIN_CODES <= 4u * ZS_STREAM_STRIDE && ZS_CHAIN_CODES == ZS_WALK_RANGES * ZS_SEQ_PER_RANGE, "the chain scratch fits the buffers it borrows");
+// reps: the recent offsets a chunk's first block starts from ({1, 4, 8}; a formatted dictionary's own in k_encode_sequences_dict)
+#define ZS_SEQ_PARAMS const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
+                      uint8_t *__restrict__ seqSecAll, ZsBlockMeta *__restrict__ metas, int stopAt, uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, \
+                      uint2 *__restrict__ packRecAll
+#define ZS_SEQ_ARGS blocks, nBlocks, seqAll, hdrAll, seqSecAll, metas, stopAt, litsAll, streamAll, packRecAll
 template <int G>
-__global__ void __launch_bounds__(64 * G)
-k_encode_sequences(const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll,
-                   uint8_t *__restrict__ seqSecAll, ZsBlockMeta *__restrict__ metas, int stopAt, uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll,
-                   uint2 *__restrict__ packRecAll)
+__device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint32_t rep0, const uint32_t rep1, const uint32_t rep2)
 {
     __shared__ SeqLds LS[G];
     const uint32_t wave = threadIdx.x >> 6;
@@ -1269,7 +1279,7 @@ k_encode_sequences(const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, con
         //   whose offset differed from its rep1: two "last index below me" scans per 64 sequences. ----
         {
             uint32_t cPrev, cA, cB;                       // carried: previous offset (= rep0), rep1, rep2
-            if (bd.firstInChunk) { cPrev = 1; cA = 4; cB = 8; } else { cPrev = 0xFFFFFFF1u; cA = 0xFFFFFFF2u; cB = 0xFFFFFFF3u; }
+            if (bd.firstInChunk) { cPrev = rep0; cA = rep1; cB = rep2; } else { cPrev = 0xFFFFFFF1u; cA = 0xFFFFFFF2u; cB = 0xFFFFFFF3u; }
             // sequences are taken 64 at a time in block order, whatever walk range they belong to; the records of the next 64 are
             // loaded while these are worked on (their addresses depend on nothing that is carried)
             auto locate = [&](uint32_t g, uint32_t &kOut, uint32_t &rrOut) -> const ZsSeqRec * {
@@ -1622,6 +1632,10 @@ k_encode_sequences(const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, con
     }
     if (lane == 0 && exists) { metas[blk].seqSecSize = result; metas[blk].seqHdrSize = (secHdr == 0xFFFFFFFFu) ? result : secHdr; metas[blk].seqGap = secGap; }
 }
+template <int G>
+__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS) { encode_sequences_block<G>(ZS_SEQ_ARGS, 1u, 4u, 8u); }
+template <int G>
+__global__ void __launch_bounds__(64 * G) k_encode_sequences_dict(ZS_SEQ_PARAMS, uint4 reps) { encode_sequences_block<G>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z); }
 
 // ---------------------------------------------------------------------------------------------
 // k_assemble_frames : one workgroup per chunk.  frame = magic + FHD + FCS (single segment)
@@ -1629,16 +1643,17 @@ k_encode_sequences(const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, con
 // iff both sections exist and literal section + sequence section < block size (else raw; RLE if flagged).
 // ---------------------------------------------------------------------------------------------
 
-extern "C" __global__ void __launch_bounds__(256)
-k_assemble_frames(const uint8_t *__restrict__ src, const ZsChunkDesc *__restrict__ chunks, const ZsBlockDesc *__restrict__ blocks,
-                  const ZsBlockMeta *__restrict__ metas, const uint8_t *__restrict__ litSecAll, const uint8_t *__restrict__ seqSecAll,
-                  uint32_t blockBase, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes, uint32_t chunkBase)
+#define ZS_ASM_PARAMS const uint8_t *__restrict__ src, const ZsChunkDesc *__restrict__ chunks, const ZsBlockDesc *__restrict__ blocks, \
+                      const ZsBlockMeta *__restrict__ metas, const uint8_t *__restrict__ litSecAll, const uint8_t *__restrict__ seqSecAll, \
+                      uint32_t blockBase, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes, uint32_t chunkBase
+#define ZS_ASM_ARGS src, chunks, blocks, metas, litSecAll, seqSecAll, blockBase, dst, dstSizes, chunkBase
+__device__ __forceinline__ void assemble_frame(ZS_ASM_PARAMS, uint32_t dictID)
 {
     const ZsChunkDesc cd = chunks[chunkBase + blockIdx.x];
     if (cd.nBlocks <= 1) return;                               // one-block chunks were assembled by the literals kernel
     uint8_t *out = dst + cd.dstOff;
     const uint32_t tid = threadIdx.x;
-    uint32_t pos = zs_frame_header(out, cd.size, tid == 0);
+    uint32_t pos = zs_frame_header(out, cd.size, tid == 0, dictID);
     for (uint32_t b = 0; b < cd.nBlocks; b++) {
         const uint32_t gb = cd.firstBlock + b;             // global block index
         const uint32_t lb = gb - blockBase;                // index inside this sub-batch's scratch
@@ -1648,3 +1663,5 @@ k_assemble_frames(const uint8_t *__restrict__ src, const ZsChunkDesc *__restrict
     }
     if (tid == 0) dstSizes[chunkBase + blockIdx.x] = pos;
 }
+extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAMS) { assemble_frame(ZS_ASM_ARGS, 0u); }
+extern "C" __global__ void __launch_bounds__(256) k_assemble_frames_dict(ZS_ASM_PARAMS, uint32_t dictID) { assemble_frame(ZS_ASM_ARGS, dictID); }

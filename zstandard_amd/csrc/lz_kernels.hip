@@ -69,11 +69,17 @@ __device__ __forceinline__ uint32_t zs_hash_short(uint32_t lo, uint32_t hi) { re
 __device__ __forceinline__ uint32_t zs_hash_long(uint32_t lo, uint32_t hi)
 { return __umul24(lo, 0x9E3779u) + __umul24(__builtin_amdgcn_alignbit(hi, lo, 24), 0x85EBCBu) + __umul24(hi >> 16, 0xC2B2AFu); }
 
-template <int TLOG, int NT>
+// PFX (dictionary calls, TLOG = ZS_TABLE_LOG_BIG): a PREFIXED unit.  Its positions are virtual: [0, pfx) the dictionary's last pfx bytes,
+// [pfx, pfx + n) the chunk.  The owners start from the table images k_lz_dict_tables made of the dictionary part (instead of empty tables)
+// and insert the chunk's positions as pfx + p; so a distance may reach into the dictionary (up to pfx + n - 1 < 2^17: distHi).  Everything
+// else - dist[], candCount, the runs - counts chunk positions only.
+template <int TLOG, int NT, bool PFX = false>
 __global__ void __launch_bounds__(64 * ZS_CAND_WAVES(NT))
 k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units, uint32_t block0,
-                uint16_t *__restrict__ distAll, uint8_t *__restrict__ distHiAll, uint32_t *__restrict__ candCount)
+                uint16_t *__restrict__ distAll, uint8_t *__restrict__ distHiAll, uint32_t *__restrict__ candCount,
+                const uint32_t *__restrict__ dictImg = nullptr, uint32_t pfx = 0)
 {
+    static_assert(!PFX || TLOG == ZS_TABLE_LOG_BIG, "a prefixed unit spans up to 128 KiB of positions");
     extern __shared__ __attribute__((aligned(16))) uint32_t candLds[];
     constexpr bool BIG = TLOG > ZS_TABLE_LOG_SMALL;
     constexpr uint32_t G = ZS_CAND_GOF(TLOG), GP = G * 64u, H = G / NT;  // H: steps of a group a hasher merges and stores
@@ -178,7 +184,12 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
 
     if (wave < NT) {
         // ---------------- owner ----------------
-        {   // clears its own table (its LDS instructions execute in order: no barrier needed before it uses it)
+        if constexpr (PFX) {   // loads the dictionary's image of its table (same order argument as the clear below)
+            uint4 *t4 = reinterpret_cast<uint4 *>(T);
+            const uint4 *img4 = reinterpret_cast<const uint4 *>(dictImg + ((size_t)tab << TLOG));
+            #pragma unroll 8
+            for (uint32_t i = lane; i < (1u << TLOG) / 4; i += 64) t4[i] = img4[i];
+        } else {   // clears its own table (its LDS instructions execute in order: no barrier needed before it uses it)
             uint4 *t4 = reinterpret_cast<uint4 *>(T);
             const uint4 e = make_uint4(ZS_SLOT_EMPTY, ZS_SLOT_EMPTY, ZS_SLOT_EMPTY, ZS_SLOT_EMPTY);
             #pragma unroll 8
@@ -188,7 +199,7 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
         __syncthreads();                                                 // interval 0: the hashers fill group 0
         for (uint32_t i = 1; i <= nGroups; i++) {
             uint32_t *ob = opnd + ((size_t)ringSlot * NT + tab) * GR + lane;
-            const uint32_t base = (i - 1) * GP + lane;
+            const uint32_t base = (i - 1) * GP + lane + (PFX ? pfx : 0u);   // (virtual position of a prefixed unit)
             uint32_t op[G], entry[G], old[G];
             #pragma unroll
             for (uint32_t u = 0; u < G; u++) op[u] = ob[u * ROW];
@@ -314,6 +325,38 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
         }
     };
     if (tab == 0) run(std::false_type{}); else run(std::true_type{});
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_lz_dict_tables<NT> : the candidate tables of a dictionary call's prefix, once per call.  Workgroup t builds table t (0 short, 1 long:
+// NT == 2) over the positions [0, pfx - 7) of the dictionary's last pfx bytes, in the 2^ZS_TABLE_LOG_BIG-slot layout of k_lz_candidates:
+// what its owner wavefront would hold after inserting them one after the other - every slot the LAST position that hashed to it (an LDS
+// atomicMax of (position + 1) << 15 | tag), then written out as tag << 17 | position.  Every prefixed unit of the call loads the image
+// instead of hashing the same pfx bytes again ("Dictionary prefix").  (The last 7 positions of the prefix would hash bytes of
+// the chunk: they are left out, as the unit's own last 7 positions are.)
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(1024)
+k_lz_dict_tables(const uint8_t *__restrict__ pre, uint32_t pfx, uint32_t *__restrict__ img)
+{
+    constexpr int TLOG = ZS_TABLE_LOG_BIG;
+    __shared__ uint32_t T[1u << TLOG];
+    const uint32_t tab = blockIdx.x, tid = threadIdx.x;
+    for (uint32_t i = tid; i < (1u << TLOG); i += 1024) T[i] = 0;
+    __syncthreads();
+    const uint32_t hashable = pfx >= 8 ? pfx - 7 : 0;
+    for (uint32_t p = tid; p < hashable; p += 1024) {
+        const uint64_t v = zs_load64(pre + p);
+        const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+        const uint32_t h = tab ? zs_hash_long(lo, hi) : zs_hash_short(lo, hi);
+        const uint32_t r = __builtin_amdgcn_alignbit(h, h, 32 - TLOG);
+        atomicMax(&T[r & ((1u << TLOG) - 1u)], ((p + 1u) << 15) | (r >> 17));
+    }
+    __syncthreads();
+    uint32_t *out = img + ((size_t)tab << TLOG);
+    for (uint32_t i = tid; i < (1u << TLOG); i += 1024) {
+        const uint32_t k = T[i];
+        out[i] = k ? (((k & 0x7FFFu) << 17) | ((k >> 15) - 1u)) : ZS_SLOT_EMPTY;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -459,12 +502,19 @@ __device__ __forceinline__ uint32_t zs_nonzero8(const uint4 d)
 #else
 #define WPROF_STAMP(k)
 #endif
-template <int LPW, int WGRP, int LOOK, int REPWIN, bool BIG, int NT>
+// PFX (dictionary calls, with BIG: 128 KiB of staged source): a prefixed unit (k_lz_candidates) - the dictionary's last pfx bytes are staged
+// in front of the chunk, at LDS positions [0, pfx), the chunk at [pfx, pfx + n).  Every other position of the walk - ranges, records, limits,
+// anchors - is a chunk position p (LDS position p + pfx): no match starts in front of the chunk, a match's source may lie in the dictionary
+// or straddle its end.
+#define ZS_WALK_KERNEL_PFX(LOOK, REPW, WLOG) k_lz_walk<ZS_WALK_LPW(WLOG), ZS_WALK_WGRP(WLOG), LOOK, REPW, true, ZS_WALK_THREADS(false, WLOG), true>
+template <int LPW, int WGRP, int LOOK, int REPWIN, bool BIG, int NT, bool PFX = false>
 __global__ void __launch_bounds__(NT, BIG ? 1 : ZS_WALK_MINW)
 k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units, uint32_t block0,
           const uint16_t *__restrict__ distAll, const uint8_t *__restrict__ distHiAll,
-          uint2 *__restrict__ recAll, uint32_t junkSlot, uint4 *__restrict__ resAll, int rangeLogArg, const uint32_t *__restrict__ candCount)
+          uint2 *__restrict__ recAll, uint32_t junkSlot, uint4 *__restrict__ resAll, int rangeLogArg, const uint32_t *__restrict__ candCount,
+          const uint8_t *__restrict__ pre = nullptr, uint32_t pfx = 0)
 {
+    static_assert(!PFX || BIG, "a prefixed unit is staged in the 128 KiB layout");
     constexpr uint32_t CAP = BIG ? ZS_UNIT_MAX : ZS_BLOCK_MAX;                  // unit capacity in bytes
     constexpr uint32_t CPL = LOOK / LPW, RPL = REPWIN / LPW, GPL = WGRP / LPW;   // candidates / recent-offset positions / groups of distances per lane and step
     static_assert((LPW == 1 || LPW == 2 || LPW == 4) && WGRP % LPW == 0 && LOOK % LPW == 0 && REPWIN % LPW == 0 && CPL >= 1 && RPL >= 1 && LOOK <= 8 && REPWIN <= 8, "a walker's lanes share the groups and candidates evenly");
@@ -472,11 +522,13 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     extern __shared__ __attribute__((aligned(16))) uint8_t walkLds[];
     // LDS: exchange buffer (the low addresses: the LDS-DMA's base register is not known to reach beyond 64 KiB), front pad, source, tail pad, results, queue, xhi
     constexpr uint32_t SRC = CAP / 8 + 16 + ZS_WALK_FRONT;                       // LDS address of source byte 0
-    // LDS address of source position p (p may be a little negative: row -1 = the front pad)
-    auto lpos = [](uint32_t p) { return SRC + p + (uint32_t)__mul24((int)p >> 8, (int)ZS_WALK_SKEW); };
-    // 16 source bytes at position i (a multiple of 16) into the skewed copy, and into the row before's tail where they are a row's head
+    // LDS address of staged position v (v may be a little negative: row -1 = the front pad); of source position p (a prefixed unit: v = p + pfx)
+    auto lposv = [](uint32_t v) { return SRC + v + (uint32_t)__mul24((int)v >> 8, (int)ZS_WALK_SKEW); };
+    const uint32_t vb = PFX ? pfx : 0u;
+    auto lpos = [&](uint32_t p) { return lposv(p + vb); };
+    // 16 source bytes at staged position i (a multiple of 16) into the skewed copy, and into the row before's tail where they are a row's head
     auto stage16 = [&](uint32_t i, const uint4 v) {
-        uint8_t *d = walkLds + lpos(i);
+        uint8_t *d = walkLds + lposv(i);
         *reinterpret_cast<uint2 *>(d) = make_uint2(v.x, v.y); *reinterpret_cast<uint2 *>(d + 8) = make_uint2(v.z, v.w);
         const uint32_t o = i & 255u;
         if (o == 0) { *reinterpret_cast<uint2 *>(d - ZS_WALK_SKEW) = make_uint2(v.x, v.y); *reinterpret_cast<uint2 *>(d - ZS_WALK_SKEW + 8) = make_uint2(v.z, v.w); }
@@ -515,7 +567,29 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     if (tid < (ZS_WALK_FRONT - ZS_WALK_SKEW) / 4) reinterpret_cast<uint32_t *>(walkLds + SRC - ZS_WALK_FRONT)[tid] = 0;
     if (tid == 0) { queue[0] = 0; queue[1] = 0; }
     __syncthreads();
-    {
+    if constexpr (PFX) {
+        // the dictionary's tail and the chunk, 16 staged bytes a thread and round: a piece wholly in one of them is one load, the (at most two)
+        // pieces across the seam or the end byte by byte.  mixed as below: the chunk's bytes against its first (ragged or short chunks: 1)
+        const uint32_t end = pfx + n, splat = (n ? (uint32_t)s[0] : 0u) * 0x01010101u;
+        for (uint32_t i = tid * 16; i < end + ZS_WALK_TAIL && i + 16 <= CAP + ZS_WALK_TAIL; i += NT * 16) {
+            uint4 w = make_uint4(0, 0, 0, 0);
+            if (i + 16 <= pfx) __builtin_memcpy(&w, pre + i, 16);
+            else if (i >= pfx && i + 16 <= end) {
+                __builtin_memcpy(&w, s + (i - pfx), 16);
+                mixed |= (w.x ^ splat) | (w.y ^ splat) | (w.z ^ splat) | (w.w ^ splat);
+            } else if (i < end) {
+                uint8_t b[16];
+                for (uint32_t k = 0; k < 16; k++) {
+                    const uint32_t v = i + k;
+                    b[k] = v < pfx ? pre[v] : (v < end ? s[v - pfx] : (uint8_t)0);
+                    if (v >= pfx && v < end && b[k] != (uint8_t)splat) mixed = 1;
+                }
+                __builtin_memcpy(&w, b, 16);
+            }
+            stage16(i, w);
+        }
+        if ((n & 15u) != 0 || n < 16) mixed = 1;
+    } else {
         // whole 16-byte pieces: the loads of a thread are issued together (a load behind a branch, followed by its LDS
         // store, would wait out one memory round trip per piece); then the partial piece and the zero tail
         constexpr uint32_t PER = (CAP / 16 + NT - 1) / NT;                       // pieces per thread
@@ -623,7 +697,7 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
             // ---- recent offsets: the walker's lanes try RPL positions each ----
             uint32_t rm0 = 0, rm1 = 0;                                           // bit i: rep0 / rep1 repeats 4 bytes at ip + i
             {
-                const bool t0 = active && rep0 != 0 && ip >= rep0, t1 = active && rep1 != 0 && ip >= rep1;
+                const bool t0 = active && rep0 != 0 && ip + vb >= rep0, t1 = active && rep1 != 0 && ip + vb >= rep1;
                 const uint32_t p0 = ip + sub * RPL;
                 constexpr int SP = (RPL + 3 + 3) / 4;                            // dwords that hold RPL + 3 bytes
                 uint32_t a[SP] = {}, b[SP] = {}, c[SP] = {};
@@ -717,7 +791,7 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
                 const uint32_t xb = a[0] ^ b[0], x0 = a[1] ^ b[1], x1 = a[2] ^ b[2];
                 const uint32_t f0 = x0 ? (uint32_t)__builtin_ctz(x0) : 32u, f1 = x1 ? (uint32_t)__builtin_ctz(x1) : 32u;
                 const uint32_t fwd = min(((x0 ? f0 : 32u + f1)) >> 3, limit - q);
-                const uint32_t maxBack = min(min(q - anchor, q - off[c]), ZS_BCAP);
+                const uint32_t maxBack = min(min(q - anchor, q + vb - off[c]), ZS_BCAP);
                 const uint32_t back = min(xb ? ((uint32_t)__builtin_clz(xb) >> 3) : 4u, maxBack);
                 if (have[c] && fwd >= (isRep[c] ? ZS_REPMIN : ZS_MINMATCH)) {
                     const int gain = (int)(4u * fwd + 8u * back) - (isRep[c] ? 0 : (int)zs_highbit(off[c] + 1)) - 5 * (int)idx[c];

@@ -137,6 +137,10 @@ struct zsmi_ctx {
     uint32_t planSmall = 0, planBig = 0;
     std::vector<uint64_t> planKey;       // copy of (srcOffsets, srcSizes, dstOffsets) the device-side plan was built from
     uint64_t planBlocks = 0; uint32_t planMaxChunkBlocks = 1;
+    // dictionary calls: their own unit list for the plan (built on the first such call), the prefix's candidate-table images
+    PinBuf hUnitsDict; DevBuf dUnitsDict, dDictImg;
+    std::vector<uint32_t> wholeBefore, tailBefore;
+    uint32_t planDictWhole = 0; bool planDict = false;
     // decompress workspace
     DevBuf dItems, dLitScratch, dFastDesc, dHufTabs, dSeqTabs, dSeqOut, dSeqLists;     // decode: items, literal scratch, fast-path tables and sequences, the blocks of each table class
     bool decodeFast = true;              // ZSMI_DEC_FAST=0: general kernel only
@@ -200,6 +204,11 @@ extern "C" zsmi_ctx *zsmi_createCtx(int device, void *hipStream)
         ok &= walkOk((const void *)ZS_WALK_KERNEL(4, 8, false, 9), ZS_WALK_LDS(ZS_BLOCK_MAX)) && walkOk((const void *)ZS_WALK_KERNEL(4, 8, true, 9), ZS_WALK_LDS(ZS_UNIT_MAX));
         ok &= walkOk((const void *)ZS_WALK_KERNEL(4, 4, false, 8), ZS_WALK_LDS(ZS_BLOCK_MAX)) && walkOk((const void *)ZS_WALK_KERNEL(4, 4, true, 8), ZS_WALK_LDS(ZS_UNIT_MAX));
         ok &= walkOk((const void *)ZS_WALK_KERNEL(8, 8, false, 8), ZS_WALK_LDS(ZS_BLOCK_MAX)) && walkOk((const void *)ZS_WALK_KERNEL(8, 8, true, 8), ZS_WALK_LDS(ZS_UNIT_MAX));
+        // dictionary calls: prefixed units (the 128 KiB shapes)
+        ok &= hipFuncSetAttribute((const void *)k_lz_candidates<ZS_TABLE_LOG_BIG, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZS_CAND_LDS(ZS_TABLE_LOG_BIG, 1)) == hipSuccess;
+        ok &= hipFuncSetAttribute((const void *)k_lz_candidates<ZS_TABLE_LOG_BIG, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZS_CAND_LDS(ZS_TABLE_LOG_BIG, 2)) == hipSuccess;
+        ok &= walkOk((const void *)ZS_WALK_KERNEL_PFX(4, 8, 9), ZS_WALK_LDS(ZS_UNIT_MAX)) && walkOk((const void *)ZS_WALK_KERNEL_PFX(4, 4, 8), ZS_WALK_LDS(ZS_UNIT_MAX)) &&
+              walkOk((const void *)ZS_WALK_KERNEL_PFX(8, 8, 8), ZS_WALK_LDS(ZS_UNIT_MAX));
         if (!ok) { (void)hipGetLastError(); if (c->ownStream) (void)hipStreamDestroy(c->stream); delete c; return nullptr; }
     }
     if (const char *e = getenv("ZSMI_BLOCKS_IN_FLIGHT")) { long v = atol(e); if (v >= 64) c->maxBlocksInFlight = (uint32_t)v; }
@@ -228,7 +237,7 @@ extern "C" void zsmi_freeCtx(zsmi_ctx *c)
 {
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : { &c->dBlocks, &c->dChunks, &c->dUnits, &c->dItems, &c->dPoolLit, &c->dLitScratch, &c->dFastDesc, &c->dHufTabs, &c->dSeqTabs, &c->dSeqOut, &c->dSeqLists, &c->sSrc, &c->sDst, &c->sSizes, &c->sDict, &c->sPack, &c->sPackOff }) b->release();
+    for (DevBuf *b : { &c->dBlocks, &c->dChunks, &c->dUnits, &c->dItems, &c->dPoolLit, &c->dLitScratch, &c->dFastDesc, &c->dHufTabs, &c->dSeqTabs, &c->dSeqOut, &c->dSeqLists, &c->sSrc, &c->sDst, &c->sSizes, &c->sDict, &c->sPack, &c->sPackOff, &c->dUnitsDict, &c->dDictImg }) b->release();
     for (int i = 0; i < zsmi_ctx::kMaxLanes; i++) {
         zsmi_ctx::Scratch &L = c->lanes[i];
         if (L.stream) (void)hipStreamSynchronize(L.stream);
@@ -238,7 +247,7 @@ extern "C" void zsmi_freeCtx(zsmi_ctx *c)
     }
     if (c->evStart) (void)hipEventDestroy(c->evStart);
     for (int i = 0; i < 2; i++) if (c->hItemsEv[i]) (void)hipEventDestroy(c->hItemsEv[i]);
-    for (PinBuf *b : { &c->hBlocks, &c->hChunks, &c->hUnits, &c->hItems2[0], &c->hItems2[1], &c->hPack }) b->release();
+    for (PinBuf *b : { &c->hBlocks, &c->hChunks, &c->hUnits, &c->hItems2[0], &c->hItems2[1], &c->hPack, &c->hUnitsDict }) b->release();
     for (auto &tl : c->launches) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->eventPool) (void)hipEventDestroy(e);
     if (c->ownStream) (void)hipStreamDestroy(c->stream);
@@ -276,10 +285,192 @@ extern "C" int zsmi_getKernelTimes(zsmi_ctx *c, zsmi_kernel_time *out, int maxEn
 }
 
 // ---------------------------------------------------------------------------------------------
+// dictionaries for the compressor: what a usingDict DECODE of the frames will load (ZSTD_decompress_insertDictionary :2452-2475).
+// A formatted dictionary (magic 0xEC30A437, >= 8 bytes) gives the frames its ID and their first blocks its recent offsets; its entropy
+// section is parsed only to find where the content starts and to refuse, with dictionary_corrupted, exactly what LoadEntropy
+// (:2378-2450) refuses (its checks restated on the host: readNCount, the Huffman weights and their FSE header, the recent offsets).
+// Any other bytes are raw content: offsets {1, 4, 8}, no ID.  The encoder uses none of the dictionary's tables.
+// ---------------------------------------------------------------------------------------------
+struct ZsCompressDict { uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 }; };
+namespace hdict {
+static uint32_t hb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
+static const size_t kErr = ~(size_t)0;
+// EntropyCommon.cs:79-188 (FSE_readNCount): bytes read or kErr
+static size_t readNCount(int16_t *norm, uint32_t *maxSV, uint32_t *tableLog, const uint8_t *istart, size_t hbSize)
+{
+    const uint8_t *const iend = istart + hbSize;
+    const uint8_t *ip = istart;
+    if (hbSize < 4) return kErr;
+    uint32_t bitStream = h_rd32(ip), charnum = 0;
+    int nbBits = (int)(bitStream & 0xF) + 5, remaining, threshold, bitCount, previous0 = 0;
+    if (nbBits > 15) return kErr;
+    bitStream >>= 4; bitCount = 4;
+    *tableLog = (uint32_t)nbBits;
+    remaining = (1 << nbBits) + 1; threshold = 1 << nbBits; nbBits++;
+    while ((remaining > 1) & (charnum <= *maxSV)) {
+        if (previous0) {
+            uint32_t n0 = charnum;
+            while ((bitStream & 0xFFFF) == 0xFFFF) {
+                n0 += 24;
+                if (ip < iend - 5) { ip += 2; bitStream = h_rd32(ip) >> bitCount; }
+                else { bitStream >>= 16; bitCount += 16; }
+            }
+            while ((bitStream & 3) == 3) { n0 += 3; bitStream >>= 2; bitCount += 2; }
+            n0 += bitStream & 3; bitCount += 2;
+            if (n0 > *maxSV) return kErr;
+            while (charnum < n0) norm[charnum++] = 0;
+            if ((ip <= iend - 7) || (ip + (bitCount >> 3) <= iend - 4)) { ip += bitCount >> 3; bitCount &= 7; bitStream = h_rd32(ip) >> bitCount; }
+            else bitStream >>= 2;
+        }
+        const int max = (2 * threshold - 1) - remaining;
+        int count;
+        if ((bitStream & (uint32_t)(threshold - 1)) < (uint32_t)max) { count = (int)(bitStream & (uint32_t)(threshold - 1)); bitCount += nbBits - 1; }
+        else { count = (int)(bitStream & (uint32_t)(2 * threshold - 1)); if (count >= threshold) count -= max; bitCount += nbBits; }
+        count--;
+        remaining -= count < 0 ? -count : count;
+        norm[charnum++] = (int16_t)count;
+        previous0 = !count;
+        while (remaining < threshold) { nbBits--; threshold >>= 1; }
+        if ((ip <= iend - 7) || (ip + (bitCount >> 3) <= iend - 4)) { ip += bitCount >> 3; bitCount &= 7; }
+        else { bitCount -= (int)(8 * (iend - 4 - ip)); ip = iend - 4; }
+        bitStream = h_rd32(ip) >> (bitCount & 31);
+    }
+    if (remaining != 1 || bitCount > 32) return kErr;
+    *maxSV = charnum - 1;
+    ip += (bitCount + 7) >> 3;
+    return (size_t)(ip - istart);
+}
+// BitStream.cs:322-494: the backward bit reader, 32-bit container
+struct Bits { uint32_t c = 0, used = 0; const uint8_t *ptr = nullptr, *start = nullptr, *limit = nullptr; };
+static bool bitInit(Bits &b, const uint8_t *src, size_t n)
+{
+    if (n < 1) return false;
+    b.start = src; b.limit = src + 4;
+    const uint8_t last = src[n - 1];
+    if (last == 0) return false;
+    b.used = 8 - hb(last);
+    if (n >= 4) { b.ptr = src + n - 4; b.c = h_rd32(b.ptr); }
+    else {
+        b.ptr = src; b.c = src[0];
+        if (n >= 3) b.c += (uint32_t)src[2] << 16;
+        if (n >= 2) b.c += (uint32_t)src[1] << 8;
+        b.used += (uint32_t)(4 - n) * 8;
+    }
+    return true;
+}
+static uint32_t bitRead(Bits &b, uint32_t n) { const uint32_t v = ((b.c << (b.used & 31)) >> 1) >> ((31 - n) & 31); b.used += n; return v; }
+enum { B_unfinished, B_end, B_completed, B_overflow };
+static int bitReload(Bits &b)
+{
+    if (b.used > 32) return B_overflow;
+    if (b.ptr >= b.limit) { b.ptr -= b.used >> 3; b.used &= 7; b.c = h_rd32(b.ptr); return B_unfinished; }
+    if (b.ptr == b.start) return b.used < 32 ? B_end : B_completed;
+    uint32_t nb = b.used >> 3; int r = B_unfinished;
+    if (b.ptr - nb < b.start) { nb = (uint32_t)(b.ptr - b.start); r = B_end; }
+    b.ptr -= nb; b.used -= nb * 8; b.c = h_rd32(b.ptr);
+    return r;
+}
+// FseDecompress.cs:111-332 for the Huffman weights (tableLog <= 6): the weights decoded, or kErr
+static size_t fseWeights(uint8_t *dst, size_t cap, const uint8_t *src, size_t n)
+{
+    int16_t norm[256]; uint32_t maxSV = 255, tableLog;
+    const size_t nc = readNCount(norm, &maxSV, &tableLog, src, n);
+    if (nc == kErr || tableLog > 6) return kErr;
+    src += nc; n -= nc;
+    struct Cell { uint16_t next; uint8_t sym, bits; } cells[64];
+    uint16_t symNext[256];
+    const uint32_t size = 1u << tableLog, mask = size - 1, step = (size >> 1) + (size >> 3) + 3;
+    uint32_t high = size - 1, pos = 0;
+    for (uint32_t s = 0; s <= maxSV; s++) { if (norm[s] == -1) { cells[high--].sym = (uint8_t)s; symNext[s] = 1; } else symNext[s] = (uint16_t)norm[s]; }
+    for (uint32_t s = 0; s <= maxSV; s++)
+        for (int i = 0; i < norm[s]; i++) { cells[pos].sym = (uint8_t)s; pos = (pos + step) & mask; while (pos > high) pos = (pos + step) & mask; }
+    if (pos != 0) return kErr;
+    for (uint32_t u = 0; u < size; u++) { const uint32_t ns = symNext[cells[u].sym]++; cells[u].bits = (uint8_t)(tableLog - hb(ns)); cells[u].next = (uint16_t)((ns << cells[u].bits) - size); }
+    Bits b;
+    if (!bitInit(b, src, n)) return kErr;
+    uint32_t s1 = bitRead(b, tableLog); bitReload(b);
+    uint32_t s2 = bitRead(b, tableLog); bitReload(b);
+    auto sym = [&](uint32_t &st) { const Cell c = cells[st]; st = c.next + bitRead(b, c.bits); return c.sym; };
+    uint8_t *op = dst, *const omax = dst + cap;
+    for (; (bitReload(b) == B_unfinished) & (op < omax - 3); op += 4) {
+        op[0] = sym(s1); op[1] = sym(s2);
+        if (bitReload(b) > B_unfinished) { op += 2; break; }
+        op[2] = sym(s1); op[3] = sym(s2);
+    }
+    for (;;) {
+        if (op > omax - 2) return kErr;
+        *op++ = sym(s1);
+        if (bitReload(b) == B_overflow) { *op++ = sym(s2); break; }
+        if (op > omax - 2) return kErr;
+        *op++ = sym(s2);
+        if (bitReload(b) == B_overflow) { *op++ = sym(s1); break; }
+    }
+    return (size_t)(op - dst);
+}
+// EntropyCommon.cs:198-269 (HUF_readStats) with the table-log limit of HUF_readDTableX4: bytes of the table description, or kErr
+static size_t hufTable(const uint8_t *ip, size_t n)
+{
+    uint8_t w[256]; size_t iSize, oSize;
+    if (!n) return kErr;
+    iSize = ip[0];
+    if (iSize >= 128) {
+        oSize = iSize - 127; iSize = (oSize + 1) / 2;
+        if (iSize + 1 > n || oSize >= 256) return kErr;
+        for (uint32_t k = 0; k < oSize; k += 2) { w[k] = ip[1 + k / 2] >> 4; w[k + 1] = ip[1 + k / 2] & 15; }
+    } else {
+        if (iSize + 1 > n) return kErr;
+        oSize = fseWeights(w, 255, ip + 1, iSize);
+        if (oSize == kErr) return kErr;
+    }
+    uint32_t rank[13] = {}, total = 0;
+    for (size_t k = 0; k < oSize; k++) { if (w[k] >= 12) return kErr; rank[w[k]]++; total += (1u << w[k]) >> 1; }
+    if (total == 0) return kErr;
+    const uint32_t tableLog = hb(total) + 1;
+    if (tableLog > 12) return kErr;
+    const uint32_t rest = (1u << tableLog) - total;
+    if ((1u << hb(rest)) != rest) return kErr;
+    rank[hb(rest) + 1]++;
+    if (rank[1] < 2 || (rank[1] & 1)) return kErr;
+    return iSize + 1;
+}
+}
+// 0, or ZSMI_error_dictionary_corrupted
+static int parseCompressDict(const uint8_t *d, size_t size, ZsCompressDict &out)
+{
+    out = ZsCompressDict();
+    if (size >= 8 && h_rd32(d) == 0xEC30A437u) {
+        out.dictID = h_rd32(d + 4);
+        if (size <= 8) return ZSMI_error_dictionary_corrupted;
+        const uint8_t *p = d + 8, *const end = d + size;
+        const size_t hs = hdict::hufTable(p, (size_t)(end - p));
+        if (hs == hdict::kErr) return ZSMI_error_dictionary_corrupted;
+        p += hs;
+        const uint32_t maxes[3] = { 31, 52, 35 }, logs[3] = { 8, 9, 9 };     // offsets, match lengths, literal lengths
+        for (int t = 0; t < 3; t++) {
+            int16_t norm[256]; uint32_t mx = maxes[t], lg;
+            const size_t h = hdict::readNCount(norm, &mx, &lg, p, (size_t)(end - p));
+            if (h == hdict::kErr || mx > maxes[t] || lg > logs[t]) return ZSMI_error_dictionary_corrupted;
+            p += h;
+        }
+        if (p + 12 > end) return ZSMI_error_dictionary_corrupted;
+        const size_t contentSize = (size_t)(end - (p + 12));
+        for (int i = 0; i < 3; i++) { const uint32_t r = h_rd32(p + 4 * i); if (r == 0 || r >= contentSize) return ZSMI_error_dictionary_corrupted; out.rep[i] = r; }
+        p += 12;
+        out.contentOff = (uint32_t)(p - d);
+    }
+    out.contentSize = (uint32_t)(size - out.contentOff);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // compress
 // ---------------------------------------------------------------------------------------------
-extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                        uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level)
+// dict (dictionary calls): parsed on the host (parseCompressDict), dDict its bytes in device memory.  Chunks of <= 64 KiB are PREFIXED
+// units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the last <= 64 KiB of the content); the units of longer chunks are
+// parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
+static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                   uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
+                                   const uint8_t *dDict, const ZsCompressDict *dict)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
@@ -342,8 +533,36 @@ extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uin
         if (hipMemcpyAsync(c->dChunks.p, hc0, sizeof(ZsChunkDesc) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         if (hipMemcpyAsync(c->dBlocks.p, hb, sizeof(ZsBlockDesc) * nBlocks, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         c->planKey.swap(key); c->planBlocks = nBlocks; c->planMaxChunkBlocks = maxChunkBlocks;
+        c->planDict = false;
     }
     const ZsChunkDesc *hc = (const ZsChunkDesc *)c->hChunks.p;
+    // dictionary calls: the units again, in a list of their own - [chunks of <= 64 KiB, one unit each (prefixed)][the other small units]
+    // (wholeBefore / tailBefore: per chunk, as smallBefore), built once per plan; the prefix's table images, once per call
+    const uint32_t pfx = dict ? std::min<uint32_t>(dict->contentSize, ZS_BLOCK_MAX) : 0u;
+    const uint8_t *dPre = dict ? dDict + dict->contentOff + dict->contentSize - pfx : nullptr;
+    if (dict) {
+        if (!c->planDict) {
+            c->wholeBefore.assign((size_t)n + 1, 0); c->tailBefore.assign((size_t)n + 1, 0);
+            uint32_t nWhole = 0, nTail = 0;
+            for (uint32_t i = 0; i < n; i++) {
+                c->wholeBefore[i] = nWhole; c->tailBefore[i] = nTail;
+                if (srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX) nWhole++;
+                else if (srcSizes[i] > ZS_BLOCK_MAX && ((srcSizes[i] - 1) % ZS_UNIT_MAX) < ZS_BLOCK_MAX) nTail++;      // its last unit is one block
+            }
+            c->wholeBefore[n] = nWhole; c->tailBefore[n] = nTail;
+            if (!c->hUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1)) || !c->dUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1))) return ZSMI_error_memory_allocation;
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;         // (the pinned list may still feed a previous copy)
+            ZsUnitDesc *hu = (ZsUnitDesc *)c->hUnitsDict.p;
+            const ZsUnitDesc *all = (const ZsUnitDesc *)c->hUnits.p;
+            uint32_t iw = 0, it = nWhole;
+            for (uint32_t i = 0; i < n; i++)                                     // the small units are in chunk order: a chunk's is its whole or its tail
+                for (uint32_t k = c->smallBefore[i]; k < c->smallBefore[i + 1]; k++) hu[srcSizes[i] <= ZS_BLOCK_MAX ? iw++ : it++] = all[k];
+            if (nWhole + nTail && hipMemcpyAsync(c->dUnitsDict.p, hu, sizeof(ZsUnitDesc) * (nWhole + nTail), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+            c->planDictWhole = nWhole; c->planDict = true;
+        }
+        if (!c->dDictImg.reserve((size_t)2 << (ZS_TABLE_LOG_BIG + 2))) return ZSMI_error_memory_allocation;
+        LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(useLong ? 2 : 1), dim3(1024), 0, dPre, pfx, (uint32_t *)c->dDictImg.p);
+    }
     // sub-batches of whole chunks, dealt round-robin to the internal streams; each stream owns a scratch set
     const int nLanes = (int)std::min<uint64_t>((uint64_t)c->nLanes, std::max<uint64_t>(1, nBlocks / 256));
     uint32_t cap = (uint32_t)std::min<uint64_t>((nBlocks + nLanes - 1) / nLanes, std::max<uint32_t>(64, c->maxBlocksInFlight / (uint32_t)nLanes));
@@ -376,18 +595,47 @@ extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uin
         const ZsUnitDesc *dUS = (const ZsUnitDesc *)c->dUnits.p + s0, *dUB = (const ZsUnitDesc *)c->dUnits.p + c->planSmall + b0;
         #define CAND_LAUNCH(name, TL, NT, cnt, du) LAUNCH_ON(c, st, name, (k_lz_candidates<TL, NT>), dim3(cnt), dim3(64 * ZS_CAND_WAVES(NT)), ZS_CAND_LDS(TL, NT), (const uint8_t *)dSrc, du, block0, \
                           (uint16_t *)L.dDist.p, (uint8_t *)L.dDistHi.p, (uint32_t *)L.dCand.p)
-        if (ns) { if (useLong) CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 2, ns, dUS); else CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 1, ns, dUS); }
+        if (dict) {
+            // prefixed units, then the other small ones from the dictionary call's own list
+            const uint32_t w0 = c->wholeBefore[chunk0], nw = c->wholeBefore[chunk1] - w0, t0 = c->tailBefore[chunk0], nt = c->tailBefore[chunk1] - t0;
+            const ZsUnitDesc *dUW = (const ZsUnitDesc *)c->dUnitsDict.p + w0, *dUT = (const ZsUnitDesc *)c->dUnitsDict.p + c->planDictWhole + t0;
+            #define CAND_PFX_LAUNCH(NT) LAUNCH_ON(c, st, "k_lz_candidates_dict", (k_lz_candidates<ZS_TABLE_LOG_BIG, NT, true>), dim3(nw), dim3(64 * ZS_CAND_WAVES(NT)), ZS_CAND_LDS(ZS_TABLE_LOG_BIG, NT), \
+                              (const uint8_t *)dSrc, dUW, block0, (uint16_t *)L.dDist.p, (uint8_t *)L.dDistHi.p, (uint32_t *)L.dCand.p, (const uint32_t *)c->dDictImg.p, pfx)
+            if (nw) { if (useLong) CAND_PFX_LAUNCH(2); else CAND_PFX_LAUNCH(1); }
+            #undef CAND_PFX_LAUNCH
+            if (nt) { if (useLong) CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 2, nt, dUT); else CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 1, nt, dUT); }
+        } else if (ns) { if (useLong) CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 2, ns, dUS); else CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 1, ns, dUS); }
         if (nbig) { if (useLong) CAND_LAUNCH("k_lz_candidates_big", ZS_TABLE_LOG_BIG, 2, nbig, dUB); else CAND_LAUNCH("k_lz_candidates_big", ZS_TABLE_LOG_BIG, 1, nbig, dUB); }
         #undef CAND_LAUNCH
         #define WALK_LAUNCH(name, LOOK, REPW, BIG, WLOG, cnt, du) LAUNCH_ON(c, st, name, (ZS_WALK_KERNEL(LOOK, REPW, BIG, WLOG)), dim3(cnt), dim3(ZS_WALK_THREADS(BIG, WLOG)), ZS_WALK_LDS((BIG) ? ZS_UNIT_MAX : ZS_BLOCK_MAX), \
                           (const uint8_t *)dSrc, du, block0, (const uint16_t *)L.dDist.p, (const uint8_t *)L.dDistHi.p, (uint2 *)L.dRecs.p, cap * (ZS_BLOCK_MAX / 4), (uint4 *)L.dRes.p, WLOG, (const uint32_t *)L.dCand.p)
-        if (ns) { if (level <= 2) WALK_LAUNCH("k_lz_walk", 4, 8, false, 9, ns, dUS); else if (level == 3) WALK_LAUNCH("k_lz_walk", 4, 4, false, 8, ns, dUS); else WALK_LAUNCH("k_lz_walk", 8, 8, false, 8, ns, dUS); }
+        if (dict) {
+            const uint32_t w0 = c->wholeBefore[chunk0], nw = c->wholeBefore[chunk1] - w0, t0 = c->tailBefore[chunk0], nt = c->tailBefore[chunk1] - t0;
+            const ZsUnitDesc *dUW = (const ZsUnitDesc *)c->dUnitsDict.p + w0, *dUT = (const ZsUnitDesc *)c->dUnitsDict.p + c->planDictWhole + t0;
+            #define WALK_PFX_LAUNCH(LOOK, REPW, WLOG) LAUNCH_ON(c, st, "k_lz_walk_dict", (ZS_WALK_KERNEL_PFX(LOOK, REPW, WLOG)), dim3(nw), dim3(ZS_WALK_THREADS(false, WLOG)), ZS_WALK_LDS(ZS_UNIT_MAX), \
+                              (const uint8_t *)dSrc, dUW, block0, (const uint16_t *)L.dDist.p, (const uint8_t *)L.dDistHi.p, (uint2 *)L.dRecs.p, cap * (ZS_BLOCK_MAX / 4), (uint4 *)L.dRes.p, WLOG, (const uint32_t *)L.dCand.p, dPre, pfx)
+            if (nw) { if (level <= 2) WALK_PFX_LAUNCH(4, 8, 9); else if (level == 3) WALK_PFX_LAUNCH(4, 4, 8); else WALK_PFX_LAUNCH(8, 8, 8); }
+            #undef WALK_PFX_LAUNCH
+            if (nt) { if (level <= 2) WALK_LAUNCH("k_lz_walk", 4, 8, false, 9, nt, dUT); else if (level == 3) WALK_LAUNCH("k_lz_walk", 4, 4, false, 8, nt, dUT); else WALK_LAUNCH("k_lz_walk", 8, 8, false, 8, nt, dUT); }
+        } else if (ns) { if (level <= 2) WALK_LAUNCH("k_lz_walk", 4, 8, false, 9, ns, dUS); else if (level == 3) WALK_LAUNCH("k_lz_walk", 4, 4, false, 8, ns, dUS); else WALK_LAUNCH("k_lz_walk", 8, 8, false, 8, ns, dUS); }
         if (nbig) { if (level <= 2) WALK_LAUNCH("k_lz_walk_big", 4, 8, true, 9, nbig, dUB); else if (level == 3) WALK_LAUNCH("k_lz_walk_big", 4, 4, true, 8, nbig, dUB); else WALK_LAUNCH("k_lz_walk_big", 8, 8, true, 8, nbig, dUB); }
         #undef WALK_LAUNCH
         LAUNCH_ON(c, st, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, (const uint2 *)L.dRecs.p, (const uint4 *)L.dRes.p, (ZsSeqRec *)L.dSeqs.p, (ZsRangeHdr *)L.dHdrs.p, walkLog);
         if (c->stopAfterWalk) { chunk0 = chunk1; continue; }
         // sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and reads the sequence
         // sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)
+        if (dict) {
+            LAUNCH_ON(c, st, "k_encode_sequences", (k_encode_sequences_dict<ZS_SEQ_GROUP>), dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)L.dSeqs.p, (const ZsRangeHdr *)L.dHdrs.p,
+                      (uint8_t *)L.dSeqSec.p, (ZsBlockMeta *)L.dMetas.p, c->stopSeq, (uint8_t *)L.dLits.p, (uint8_t *)L.dStreams.p, (uint2 *)L.dDist.p, make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u));
+            LAUNCH_ON(c, st, "k_encode_literals", k_encode_literals_dict, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)L.dSeqs.p, (const ZsRangeHdr *)L.dHdrs.p,
+                      (uint8_t *)L.dLits.p, (uint8_t *)L.dStreams.p, (uint8_t *)L.dLitSec.p, (ZsBlockMeta *)L.dMetas.p, c->stopLit,
+                      (const ZsChunkDesc *)c->dChunks.p, (const uint8_t *)L.dSeqSec.p, (uint8_t *)dDst, dDstSizes, dict->dictID);
+            if (maxChunkBlocks > 1)
+                LAUNCH_ON(c, st, "k_assemble_frames", k_assemble_frames_dict, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, (const ZsChunkDesc *)c->dChunks.p,
+                          (const ZsBlockDesc *)c->dBlocks.p, (const ZsBlockMeta *)L.dMetas.p, (const uint8_t *)L.dLitSec.p, (const uint8_t *)L.dSeqSec.p, block0, (uint8_t *)dDst, dDstSizes, chunk0, dict->dictID);
+            chunk0 = chunk1;
+            continue;
+        }
         LAUNCH_ON(c, st, "k_encode_sequences", (k_encode_sequences<ZS_SEQ_GROUP>), dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)L.dSeqs.p, (const ZsRangeHdr *)L.dHdrs.p,
                   (uint8_t *)L.dSeqSec.p, (ZsBlockMeta *)L.dMetas.p, c->stopSeq, (uint8_t *)L.dLits.p, (uint8_t *)L.dStreams.p, (uint2 *)L.dDist.p);
         LAUNCH_ON(c, st, "k_encode_literals", k_encode_literals, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)L.dSeqs.p, (const ZsRangeHdr *)L.dHdrs.p,
@@ -403,6 +651,28 @@ extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uin
         if (hipStreamWaitEvent(c->stream, c->lanes[i].done, 0) != hipSuccess) return ZSMI_error_GENERIC;
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                        uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level)
+{
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, nullptr);
+}
+// dDict: device memory.  Its bytes are read back to the host to be parsed (a formatted dictionary's ID, recent offsets and content
+// offset): the call waits for the context's stream once.
+extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                  uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
+                                                  const void *dDict, size_t dictSize)
+{
+    if (!dDict || dictSize == 0) return zsmi_compressBatchDevice(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level);
+    if (!c) return ZSMI_error_init_missing;
+    if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    std::vector<uint8_t> h(dictSize);
+    if (hipMemcpyAsync(h.data(), dDict, dictSize, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    ZsCompressDict d;
+    if (const int e = parseCompressDict(h.data(), dictSize, d)) return e;
+    if (n == 0) return 0;
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, (const uint8_t *)dDict, &d);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -663,11 +933,22 @@ static int copyBack(zsmi_ctx *c, const uint8_t *dBase, const uint64_t *dof, uint
     }
     return 0;
 }
-extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                      uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level)
+static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                 uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level, const void *dict, size_t dictSize)
 {
     if (!c) return ZSMI_error_init_missing;
+    ZsCompressDict dc;
+    const bool useDict = dict != nullptr && dictSize != 0;
+    if (useDict) {
+        if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
+        if (const int e = parseCompressDict((const uint8_t *)dict, dictSize, dc)) return e;
+    }
     if (n == 0) return 0;
+    if (useDict) {
+        if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+        if (!c->sDict.reserve(dictSize + 64)) return ZSMI_error_memory_allocation;
+        if (hipMemcpyAsync(c->sDict.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    }
     uint64_t slo, shi, dlo, dhi;
     spanOf(srcOffsets, srcSizes, nullptr, n, slo, shi);
     std::vector<uint32_t> bounds(n);
@@ -678,11 +959,22 @@ extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64
     for (uint32_t i = 0; i < n; i++) { so[i] = srcOffsets[i] - slo; dof[i] = dstOffsets[i] - dlo; }
     if (shi > slo && hipMemcpyAsync(c->sSrc.p, (const uint8_t *)src + slo, shi - slo, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     uint32_t *dSizes = (uint32_t *)((uint8_t *)c->sSizes.p + sizeof(uint64_t) * n);
-    const int rc = zsmi_compressBatchDevice(c, c->sSrc.p, so.data(), srcSizes, n, c->sDst.p, dof.data(), dSizes, level);
+    const int rc = compressBatchDeviceImpl(c, c->sSrc.p, so.data(), srcSizes, n, c->sDst.p, dof.data(), dSizes, level, useDict ? (const uint8_t *)c->sDict.p : nullptr, useDict ? &dc : nullptr);
     if (rc) return rc;
     if (hipMemcpyAsync(dstSizes, dSizes, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     return copyBack(c, (const uint8_t *)c->sDst.p, dof.data(), (uint8_t *)dst, dstOffsets, dstSizes, n);
+}
+extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                      uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level)
+{
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, 0);
+}
+extern "C" int zsmi_compressBatchHost_usingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
+                                                const void *dict, size_t dictSize)
+{
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict, dictSize);
 }
 static int decompressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
@@ -785,6 +1077,10 @@ extern "C" size_t zsmi_decodeScratchBytes(zsmi_ctx *c)
 
 extern "C" size_t zsmi_compress(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level)
 {
+    return zsmi_compress_usingDict(dst, dstCapacity, src, srcSize, nullptr, 0, level);
+}
+extern "C" size_t zsmi_compress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level)
+{
     if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
     Borrowed b; zsmi_ctx *c = b.c;
     if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
@@ -793,7 +1089,7 @@ extern "C" size_t zsmi_compress(void *dst, size_t dstCapacity, const void *src, 
     uint8_t *out = (uint8_t *)dst;
     if (dstCapacity < bound) { tmp.resize(bound); out = tmp.data(); }     // compress into a bound-sized buffer, then check the fit
     const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
-    const int rc = zsmi_compressBatchHost(c, src, &so, &ss, 1, out, &dof, &ds, level);
+    const int rc = zsmi_compressBatchHost_usingDict(c, src, &so, &ss, 1, out, &dof, &ds, level, dict, dictSize);
     if (rc) return ZSMI_ERR(rc);
     if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
     if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
