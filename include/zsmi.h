@@ -145,8 +145,8 @@ typedef struct { char name[48]; double seconds; uint32_t launches; } zsmi_kernel
 int zsmi_enableKernelTiming(zsmi_ctx *ctx, int on);
 int zsmi_getKernelTimes(zsmi_ctx *ctx, zsmi_kernel_time *out, int maxEntries);
 
-/* device scratch the context holds for decoding after the last zsmi_decompressBatch* call (bytes): sized by that call's items in flight and
- * its largest capacity; a later, smaller call gives most of it back */
+/* device memory the context's decode buffers hold (bytes): the capacities of its scratch buffers, each with its reserve slack (1/8 + 4 KiB).
+ * A call grows them to its items in flight and largest capacity; a later, much smaller call gives most of it back */
 size_t zsmi_decodeScratchBytes(zsmi_ctx *ctx);
 
 /* Releases the per-device contexts the one-shot calls (zsmi_compress / zsmi_decompress*) keep.  For embedders that unload the library: nothing

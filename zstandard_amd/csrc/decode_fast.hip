@@ -748,7 +748,7 @@ k_dec_sequences(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict_
 // chain whatever the call's size (0.46 + 0.49 ms at 8192 frames of 32 KiB, the CUs at two wavefronts each), and the Huffman and the sequence
 // streams do not depend on each other - side by side they take the longer chain's time.  (Two streams for the same: 0.4 ms SLOWER, the
 // cross-stream waits cost more than the overlap brought.)  The grid is the four grids one behind the other; the LDS is the largest of the four
-// images (45 KiB: fewer workgroups a CU than the Huffman kernel's 30 KiB allows, which is why large calls keep the separate launches).
+// images (37376 B: fewer workgroups a CU than the Huffman kernel's 30 KiB allows, which is why large calls keep the separate launches).
 __global__ void __launch_bounds__(64)
 k_dec_entropy(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
               const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, const uint8_t *__restrict__ seqTabs, ZsFastSeq *__restrict__ seqOutAll,

@@ -91,30 +91,27 @@ extern "C" unsigned long long zsmi_getDecompressedSize(const void *srcv, size_t 
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
-struct DevBuf {
+// A buffer that grows by 1/8 + 4 KiB beyond the request; device or pinned host memory.  The context owns its buffers: they go with it.
+static hipError_t devAlloc(void **p, size_t n) { return hipMalloc(p, n); }
+static hipError_t pinAlloc(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+template <hipError_t (*Alloc)(void **, size_t), hipError_t (*Free)(void *)>
+struct Buf {
     void *p = nullptr; size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
     bool reserve(size_t n) {
         if (n <= cap) return true;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
+        release();
         size_t want = n + (n >> 3) + 4096;
-        if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return false; }
+        if (Alloc(&p, want) != hipSuccess) { p = nullptr; return false; }
         cap = want; return true;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() { if (p) (void)Free(p); p = nullptr; cap = 0; }
 };
-struct PinBuf {
-    void *p = nullptr; size_t cap = 0;
-    bool reserve(size_t n) {
-        if (n <= cap) return true;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        size_t want = n + (n >> 3) + 4096;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-        cap = want; return true;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
+typedef Buf<devAlloc, hipFree> DevBuf;
+typedef Buf<pinAlloc, hipHostFree> PinBuf;
 
 struct TimedLaunch { const char *name; hipEvent_t a, b; };
 
@@ -123,15 +120,20 @@ struct zsmi_ctx {
     hipStream_t stream = nullptr;
     bool ownStream = false;
     uint32_t maxBlocksInFlight = 16384;   // ZSMI_BLOCKS_IN_FLIGHT: 64 KiB blocks per sub-batch (scratch ~0.6 MiB a block, reserved for what a call needs); 2 GiB of 128 KiB chunks: 8192: 86.5, 16384: 88.2, 32768: 89.4 GiB/s
-    // compress workspace: plan (shared) + one scratch set per internal stream ("lane")
+    // compress workspace: the plan and the scratch of a sub-batch
     DevBuf dBlocks, dChunks, dUnits;     // dUnits: small units (<= 64 KiB) first, then big ones, each in chunk order
-    struct Scratch { DevBuf dDist, dDistHi, dCand, dRecs, dRes, dSeqs, dHdrs, dLits, dStreams, dLitSec, dSeqSec, dMetas; hipStream_t stream = nullptr; hipEvent_t done = nullptr; };
-    static const int kMaxLanes = 8;
-    Scratch lanes[kMaxLanes];
-    int nLanes = 1;
+    struct Scratch {
+        DevBuf dDist, dDistHi, dCand, dRecs, dRes, dSeqs, dHdrs, dLits, dStreams, dLitSec, dSeqSec, dMetas;
+        bool reserve(uint32_t cap) {           // cap: blocks of a sub-batch
+            return dDist.reserve((size_t)cap * ZS_BLOCK_MAX * 2 + 256) && dDistHi.reserve((size_t)cap * (ZS_BLOCK_MAX / 8) + 256) && dCand.reserve((size_t)cap * 2 * sizeof(uint32_t) + 64) &&
+                   dRecs.reserve(((size_t)cap * (ZS_BLOCK_MAX / 4) + 64) * sizeof(uint2)) && dRes.reserve((size_t)cap * ZS_RES_PER_BLOCK * sizeof(uint4) + ((size_t)8 << 20)) &&
+                   dSeqs.reserve((size_t)cap * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE * sizeof(ZsSeqRec)) && dHdrs.reserve((size_t)cap * ZS_WALK_RANGES * sizeof(ZsRangeHdr)) &&
+                   dLits.reserve((size_t)cap * (ZS_BLOCK_MAX + 64)) && dStreams.reserve((size_t)cap * 4 * ZS_STREAM_STRIDE) && dLitSec.reserve((size_t)cap * ZS_LITSEC_STRIDE) &&
+                   dSeqSec.reserve((size_t)cap * ZS_SEQSEC_STRIDE) && dMetas.reserve((size_t)cap * sizeof(ZsBlockMeta));
+        }
+    } scratch;
     int stopAfterWalk = 0;                 // ZSMI_STOP_AFTER_WALK (debug-hooks build, tools/walk_check.py): the entropy kernels are not launched
     int stopLit = 0, stopSeq = 0;          // timing aids of a -DZSMI_DEBUG_HOOKS build (ZSMI_STOP_LIT / ZSMI_STOP_SEQ): end a kernel after a stage; always 0 in the product
-    hipEvent_t evStart = nullptr;
     PinBuf hBlocks, hChunks, hUnits;
     std::vector<uint32_t> smallBefore, bigBefore;   // per chunk (n + 1 entries): small / big units in front of it
     uint32_t planSmall = 0, planBig = 0;
@@ -149,13 +151,8 @@ struct zsmi_ctx {
                                          // last round is mostly tail, so big launches pay (16384 frames of 32 KiB: 82 GiB/s, 57344: 104 GiB/s)
     PinBuf hItems2[2]; hipEvent_t hItemsEv[2] = { nullptr, nullptr }; bool hItemsBusy[2] = { false, false }; uint32_t decodeCalls = 0;    // the decode item list: two pinned buffers taken in turn
     DevBuf dPoolLit;                         // the general decode kernel's literal buffers: one per wavefront of its pool
-    uint32_t seqLog9Group = 0;               // experiment: force the 2.5 KiB sequence-table class to 16 or 4 items a wavefront (ZSMI_SEQ_LOG9_G; 0: the heuristic)
-    uint32_t decodeFuseBelow = 0;            // ZSMI_DEC_FUSE_BELOW given: (item, block) pairs of a call up to which the entropy kernels are one launch (0: never) - instead of the rule below
-    bool decodeFuseSet = false;
-    int execWaves = 0;                       // ZSMI_EXEC_WAVES=7 / 8: force the execute kernel's form for one-block items (0: by the call's size, below)
     uint32_t cus = 256;                      // compute units of the device (rounds of workgroups a launch takes)
     uint32_t decodePool = 3072;              // wavefronts of that pool (ZSMI_DEC_POOL): the chip holds 10 a CU x 256
-    size_t lastDecodeScratch = 0;            // bytes of scratch the last decode call needed (INTEGRATION.md states them)
     // staging for host-buffer calls
     DevBuf sSrc, sDst, sSizes, sDict, sPack, sPackOff;
     PinBuf hPack;
@@ -180,6 +177,30 @@ static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz
     } while (0)
 #define LAUNCH(ctx, name, kernel, grid, block, lds, ...) LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, lds, __VA_ARGS__)
 
+// ---- the LZ kernels of a level: k_lz_candidates and k_lz_walk for small units (<= 64 KiB), big units and a dictionary call's prefixed units ----
+// level <= 2: short table only ("fast"), walk ranges of 512 bytes; level >= 3: short + long table ("double"), ranges of 256 bytes;
+// level >= 4 scores 8 candidates a step instead of 4 (paramsForLevel in oracle/zso_encoder.c)
+typedef void (*CandFn)(const uint8_t *, const ZsUnitDesc *, uint32_t, uint16_t *, uint8_t *, uint32_t *, const uint32_t *, uint32_t);
+typedef void (*WalkFn)(const uint8_t *, const ZsUnitDesc *, uint32_t, const uint16_t *, const uint8_t *, uint2 *, uint32_t, uint4 *, int,
+                       const uint32_t *, const uint8_t *, uint32_t);
+template <class Fn> struct LzKernel { const char *name; Fn fn; uint32_t threads; size_t lds; };
+enum { kUnitsPfx, kUnitsSmall, kUnitsBig };       // (the order the kernels are launched in)
+struct LzShape { LzKernel<CandFn> cand[3]; LzKernel<WalkFn> walk[3]; int walkLog; bool useLong; };
+#define ZS_CAND_SHAPES(NT) { { "k_lz_candidates_dict", k_lz_candidates<ZS_TABLE_LOG_BIG, NT, true>, 64 * ZS_CAND_WAVES(NT), ZS_CAND_LDS(ZS_TABLE_LOG_BIG, NT) }, \
+                             { "k_lz_candidates", k_lz_candidates<ZS_TABLE_LOG_SMALL, NT>, 64 * ZS_CAND_WAVES(NT), ZS_CAND_LDS(ZS_TABLE_LOG_SMALL, NT) }, \
+                             { "k_lz_candidates_big", k_lz_candidates<ZS_TABLE_LOG_BIG, NT>, 64 * ZS_CAND_WAVES(NT), ZS_CAND_LDS(ZS_TABLE_LOG_BIG, NT) } }
+#define ZS_WALK_SHAPES(LOOK, REPW, WLOG) { { "k_lz_walk_dict", ZS_WALK_KERNEL_PFX(LOOK, REPW, WLOG), ZS_WALK_THREADS(false, WLOG), ZS_WALK_LDS(ZS_UNIT_MAX) }, \
+                                           { "k_lz_walk", ZS_WALK_KERNEL(LOOK, REPW, false, WLOG), ZS_WALK_THREADS(false, WLOG), ZS_WALK_LDS(ZS_BLOCK_MAX) }, \
+                                           { "k_lz_walk_big", ZS_WALK_KERNEL(LOOK, REPW, true, WLOG), ZS_WALK_THREADS(true, WLOG), ZS_WALK_LDS(ZS_UNIT_MAX) } }
+static const LzShape kLzShapes[3] = {
+    { ZS_CAND_SHAPES(1), ZS_WALK_SHAPES(4, 8, 9), 9, false },     // level <= 2
+    { ZS_CAND_SHAPES(2), ZS_WALK_SHAPES(4, 4, 8), 8, true },      // level 3
+    { ZS_CAND_SHAPES(2), ZS_WALK_SHAPES(8, 8, 8), 8, true },      // level >= 4
+};
+#undef ZS_CAND_SHAPES
+#undef ZS_WALK_SHAPES
+static const LzShape &lzShape(int level) { return kLzShapes[level <= 2 ? 0 : (level == 3 ? 1 : 2)]; }
+
 extern "C" zsmi_ctx *zsmi_createCtx(int device, void *hipStream)
 {
     int count = 0;
@@ -189,33 +210,20 @@ extern "C" zsmi_ctx *zsmi_createCtx(int device, void *hipStream)
     else { c->device = device; if (hipSetDevice(device) != hipSuccess) { delete c; return nullptr; } }
     if (hipStream) { c->stream = (hipStream_t)hipStream; c->ownStream = false; }
     else { if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return nullptr; } c->ownStream = true; }
-    // dynamic LDS beyond the 64 KiB default
-    {   // dynamic LDS beyond the 64 KiB default: refused requests fail here, not at the first launch
-        bool ok = true;
-        ok &= hipFuncSetAttribute((const void *)k_lz_candidates<ZS_TABLE_LOG_SMALL, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZS_CAND_LDS(ZS_TABLE_LOG_SMALL, 1)) == hipSuccess;
-        ok &= hipFuncSetAttribute((const void *)k_lz_candidates<ZS_TABLE_LOG_SMALL, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZS_CAND_LDS(ZS_TABLE_LOG_SMALL, 2)) == hipSuccess;
-        ok &= hipFuncSetAttribute((const void *)k_lz_candidates<ZS_TABLE_LOG_BIG, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZS_CAND_LDS(ZS_TABLE_LOG_BIG, 1)) == hipSuccess;
-        ok &= hipFuncSetAttribute((const void *)k_lz_candidates<ZS_TABLE_LOG_BIG, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZS_CAND_LDS(ZS_TABLE_LOG_BIG, 2)) == hipSuccess;
-        // k_lz_walk addresses its (dynamic) LDS from 0: that holds as long as the kernel has no static LDS in front of it
-        auto walkOk = [](const void *fn, size_t lds) {
+    bool ok = true;
+    // dynamic LDS beyond the 64 KiB default: refused requests fail here, not at the first launch.  k_lz_walk addresses its (dynamic) LDS
+    // from 0: that holds as long as the kernel has no static LDS in front of it
+    for (const LzShape &s : kLzShapes)
+        for (int k = 0; k < 3; k++) {
             hipFuncAttributes fa;
-            return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess && hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.sharedSizeBytes == 0;
-        };
-        ok &= walkOk((const void *)ZS_WALK_KERNEL(4, 8, false, 9), ZS_WALK_LDS(ZS_BLOCK_MAX)) && walkOk((const void *)ZS_WALK_KERNEL(4, 8, true, 9), ZS_WALK_LDS(ZS_UNIT_MAX));
-        ok &= walkOk((const void *)ZS_WALK_KERNEL(4, 4, false, 8), ZS_WALK_LDS(ZS_BLOCK_MAX)) && walkOk((const void *)ZS_WALK_KERNEL(4, 4, true, 8), ZS_WALK_LDS(ZS_UNIT_MAX));
-        ok &= walkOk((const void *)ZS_WALK_KERNEL(8, 8, false, 8), ZS_WALK_LDS(ZS_BLOCK_MAX)) && walkOk((const void *)ZS_WALK_KERNEL(8, 8, true, 8), ZS_WALK_LDS(ZS_UNIT_MAX));
-        // dictionary calls: prefixed units (the 128 KiB shapes)
-        ok &= hipFuncSetAttribute((const void *)k_lz_candidates<ZS_TABLE_LOG_BIG, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZS_CAND_LDS(ZS_TABLE_LOG_BIG, 1)) == hipSuccess;
-        ok &= hipFuncSetAttribute((const void *)k_lz_candidates<ZS_TABLE_LOG_BIG, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZS_CAND_LDS(ZS_TABLE_LOG_BIG, 2)) == hipSuccess;
-        ok &= walkOk((const void *)ZS_WALK_KERNEL_PFX(4, 8, 9), ZS_WALK_LDS(ZS_UNIT_MAX)) && walkOk((const void *)ZS_WALK_KERNEL_PFX(4, 4, 8), ZS_WALK_LDS(ZS_UNIT_MAX)) &&
-              walkOk((const void *)ZS_WALK_KERNEL_PFX(8, 8, 8), ZS_WALK_LDS(ZS_UNIT_MAX));
-        if (!ok) { (void)hipGetLastError(); if (c->ownStream) (void)hipStreamDestroy(c->stream); delete c; return nullptr; }
-    }
+            ok &= hipFuncSetAttribute((const void *)s.cand[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.cand[k].lds) == hipSuccess;
+            ok &= hipFuncSetAttribute((const void *)s.walk[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.walk[k].lds) == hipSuccess &&
+                  hipFuncGetAttributes(&fa, (const void *)s.walk[k].fn) == hipSuccess && fa.sharedSizeBytes == 0;
+        }
+    for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->hItemsEv[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); zsmi_freeCtx(c); return nullptr; }
     if (const char *e = getenv("ZSMI_BLOCKS_IN_FLIGHT")) { long v = atol(e); if (v >= 64) c->maxBlocksInFlight = (uint32_t)v; }
     if (const char *e = getenv("ZSMI_DEC_FAST")) c->decodeFast = atoi(e) != 0;
-    if (const char *e = getenv("ZSMI_SEQ_LOG9_G")) c->seqLog9Group = (uint32_t)atol(e);
-    if (const char *e = getenv("ZSMI_DEC_FUSE_BELOW")) { c->decodeFuseBelow = (uint32_t)atol(e); c->decodeFuseSet = true; }
-    if (const char *e = getenv("ZSMI_EXEC_WAVES")) c->execWaves = atoi(e);
     { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0) c->cus = (uint32_t)v; }
     if (const char *e = getenv("ZSMI_DEC_POOL")) { long v = atol(e); if (v >= 2 && v <= (1 << 20)) c->decodePool = (uint32_t)v; }
     if (const char *e = getenv("ZSMI_ITEMS_IN_FLIGHT")) { long v = atol(e); if (v >= 64 && v <= (1 << 20)) c->maxItemsInFlight = (uint32_t)v; }
@@ -224,36 +232,18 @@ extern "C" zsmi_ctx *zsmi_createCtx(int device, void *hipStream)
     if (const char *e = getenv("ZSMI_STOP_AFTER_WALK")) c->stopAfterWalk = atoi(e);
     if (const char *e = getenv("ZSMI_STOP_SEQ")) c->stopSeq = atoi(e);
 #endif
-    if (const char *e = getenv("ZSMI_LANES")) { long v = atol(e); if (v >= 1 && v <= zsmi_ctx::kMaxLanes) c->nLanes = (int)v; }
-    // sub-batches of one call run on internal streams so that the latency-bound kernels of different sub-batches overlap
-    for (int i = 0; i < c->nLanes; i++) {
-        if (hipStreamCreateWithFlags(&c->lanes[i].stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&c->lanes[i].done, hipEventDisableTiming) != hipSuccess) { c->nLanes = i; break; }
-    }
-    if (c->nLanes == 0 || hipEventCreateWithFlags(&c->evStart, hipEventDisableTiming) != hipSuccess) { zsmi_freeCtx(c); return nullptr; }
     return c;
 }
 extern "C" void zsmi_freeCtx(zsmi_ctx *c)
 {
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : { &c->dBlocks, &c->dChunks, &c->dUnits, &c->dItems, &c->dPoolLit, &c->dLitScratch, &c->dFastDesc, &c->dHufTabs, &c->dSeqTabs, &c->dSeqOut, &c->dSeqLists, &c->sSrc, &c->sDst, &c->sSizes, &c->sDict, &c->sPack, &c->sPackOff, &c->dUnitsDict, &c->dDictImg }) b->release();
-    for (int i = 0; i < zsmi_ctx::kMaxLanes; i++) {
-        zsmi_ctx::Scratch &L = c->lanes[i];
-        if (L.stream) (void)hipStreamSynchronize(L.stream);
-        for (DevBuf *b : { &L.dDist, &L.dDistHi, &L.dCand, &L.dRecs, &L.dRes, &L.dSeqs, &L.dHdrs, &L.dLits, &L.dStreams, &L.dLitSec, &L.dSeqSec, &L.dMetas }) b->release();
-        if (L.done) (void)hipEventDestroy(L.done);
-        if (L.stream) (void)hipStreamDestroy(L.stream);
-    }
-    if (c->evStart) (void)hipEventDestroy(c->evStart);
     for (int i = 0; i < 2; i++) if (c->hItemsEv[i]) (void)hipEventDestroy(c->hItemsEv[i]);
-    for (PinBuf *b : { &c->hBlocks, &c->hChunks, &c->hUnits, &c->hItems2[0], &c->hItems2[1], &c->hPack, &c->hUnitsDict }) b->release();
     for (auto &tl : c->launches) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->eventPool) (void)hipEventDestroy(e);
     if (c->ownStream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                    // (and with it every buffer the context holds)
 }
-extern "C" void zsmi_freeCtx(zsmi_ctx *c);
 extern "C" int zsmi_sync(zsmi_ctx *c)
 {
     if (!c) return ZSMI_error_init_missing;
@@ -465,31 +455,18 @@ static int parseCompressDict(const uint8_t *d, size_t size, ZsCompressDict &out)
 // ---------------------------------------------------------------------------------------------
 // compress
 // ---------------------------------------------------------------------------------------------
-// dict (dictionary calls): parsed on the host (parseCompressDict), dDict its bytes in device memory.  Chunks of <= 64 KiB are PREFIXED
-// units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the last <= 64 KiB of the content); the units of longer chunks are
-// parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
-static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                   uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const uint8_t *dDict, const ZsCompressDict *dict)
+// The plan of a call: chunks -> blocks (ZsChunkDesc, ZsBlockDesc) and LZ units, built on the host and copied to the device.  It is reused
+// while the chunk layout repeats (steady-state batches; compared in place: such a call allocates and copies nothing).  A dictionary call
+// adds a unit list of its own, once per plan.
+static int buildPlan(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict)
 {
-    if (!c) return ZSMI_error_init_missing;
-    if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    // level <= 2: short table only ("fast"), walk ranges of 512 bytes; level >= 3: short + long table ("double"), ranges of 256 bytes;
-    // level >= 4 scores 8 candidates a step instead of 4 (paramsForLevel in oracle/zso_encoder.c)
-    const bool useLong = level >= 3;
-    const int walkLog = level <= 2 ? 9 : 8;
-    // plan: chunks -> blocks.  The device-side plan is reused when the chunk layout repeats (steady-state batches).
-    // (compared in place: a call of a repeating layout allocates and copies nothing)
     bool samePlan = c->planKey.size() == (size_t)n * 3 + 1 && c->planKey[0] == n;
     for (uint32_t i = 0; samePlan && i < n; i++) samePlan = c->planKey[1 + i] == srcOffsets[i] && c->planKey[1 + n + i] == dstOffsets[i] && c->planKey[1 + 2 * (size_t)n + i] == srcSizes[i];
-    uint64_t nBlocks; uint32_t maxChunkBlocks;
-    if (samePlan) { nBlocks = c->planBlocks; maxChunkBlocks = c->planMaxChunkBlocks; }
-    else {
+    if (!samePlan) {
         std::vector<uint64_t> key((size_t)n * 3 + 1);
         key[0] = n;
         for (uint32_t i = 0; i < n; i++) { key[1 + i] = srcOffsets[i]; key[1 + n + i] = dstOffsets[i]; key[1 + 2 * (size_t)n + i] = srcSizes[i]; }
-        nBlocks = 0;
+        uint64_t nBlocks = 0;
         for (uint32_t i = 0; i < n; i++) nBlocks += srcSizes[i] ? (srcSizes[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX : 1;
         if (nBlocks > 0x7FFFFFFFull) return ZSMI_error_srcSize_wrong;
         if (!c->hChunks.reserve(sizeof(ZsChunkDesc) * n) || !c->hBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
@@ -498,7 +475,7 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
         // the pinned plan buffers may still feed a previous asynchronous copy
         if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         ZsChunkDesc *hc0 = (ZsChunkDesc *)c->hChunks.p; ZsBlockDesc *hb = (ZsBlockDesc *)c->hBlocks.p;
-        uint32_t b = 0; maxChunkBlocks = 1;
+        uint32_t b = 0, maxChunkBlocks = 1;
         for (uint32_t i = 0; i < n; i++) {
             const uint32_t nb = srcSizes[i] ? (srcSizes[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX : 1;
             hc0[i].srcOff = srcOffsets[i]; hc0[i].dstOff = dstOffsets[i]; hc0[i].size = srcSizes[i]; hc0[i].firstBlock = b; hc0[i].nBlocks = nb; hc0[i].pad = 0;
@@ -518,137 +495,135 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
             for (uint64_t o = 0; o < srcSizes[i]; o += ZS_UNIT_MAX) { if ((uint64_t)srcSizes[i] - o > ZS_BLOCK_MAX) nBig++; else nSmall++; }
         }
         c->smallBefore[n] = nSmall; c->bigBefore[n] = nBig;
-        {
-            ZsUnitDesc *hu = (ZsUnitDesc *)c->hUnits.p;
-            uint32_t is = 0, ib = nSmall;
-            for (uint32_t i = 0; i < n; i++)
-                for (uint64_t o = 0; o < srcSizes[i]; o += ZS_UNIT_MAX) {
-                    const uint64_t left = (uint64_t)srcSizes[i] - o;
-                    ZsUnitDesc &u = hu[left > ZS_BLOCK_MAX ? ib++ : is++];
-                    u.srcOff = srcOffsets[i] + o; u.size = (uint32_t)(left < ZS_UNIT_MAX ? left : ZS_UNIT_MAX); u.firstBlock = hc0[i].firstBlock + (uint32_t)(o / ZS_BLOCK_MAX);
-                }
-            if (nSmall + nBig && hipMemcpyAsync(c->dUnits.p, hu, sizeof(ZsUnitDesc) * (nSmall + nBig), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        }
+        ZsUnitDesc *hu = (ZsUnitDesc *)c->hUnits.p;
+        uint32_t is = 0, ib = nSmall;
+        for (uint32_t i = 0; i < n; i++)
+            for (uint64_t o = 0; o < srcSizes[i]; o += ZS_UNIT_MAX) {
+                const uint64_t left = (uint64_t)srcSizes[i] - o;
+                ZsUnitDesc &u = hu[left > ZS_BLOCK_MAX ? ib++ : is++];
+                u.srcOff = srcOffsets[i] + o; u.size = (uint32_t)(left < ZS_UNIT_MAX ? left : ZS_UNIT_MAX); u.firstBlock = hc0[i].firstBlock + (uint32_t)(o / ZS_BLOCK_MAX);
+            }
+        if (nSmall + nBig && hipMemcpyAsync(c->dUnits.p, hu, sizeof(ZsUnitDesc) * (nSmall + nBig), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         c->planSmall = nSmall; c->planBig = nBig;
         if (hipMemcpyAsync(c->dChunks.p, hc0, sizeof(ZsChunkDesc) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         if (hipMemcpyAsync(c->dBlocks.p, hb, sizeof(ZsBlockDesc) * nBlocks, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         c->planKey.swap(key); c->planBlocks = nBlocks; c->planMaxChunkBlocks = maxChunkBlocks;
         c->planDict = false;
     }
+    // dictionary calls: the small units again, in a list of their own - [chunks of <= 64 KiB, one unit each (prefixed)][the other small
+    // units: tails of longer chunks] (wholeBefore / tailBefore: per chunk, as smallBefore)
+    if (dict && !c->planDict) {
+        c->wholeBefore.assign((size_t)n + 1, 0); c->tailBefore.assign((size_t)n + 1, 0);
+        uint32_t nWhole = 0, nTail = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            c->wholeBefore[i] = nWhole; c->tailBefore[i] = nTail;
+            if (srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX) nWhole++;
+            else if (srcSizes[i] > ZS_BLOCK_MAX && ((srcSizes[i] - 1) % ZS_UNIT_MAX) < ZS_BLOCK_MAX) nTail++;      // its last unit is one block
+        }
+        c->wholeBefore[n] = nWhole; c->tailBefore[n] = nTail;
+        if (!c->hUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1)) || !c->dUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1))) return ZSMI_error_memory_allocation;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;         // (the pinned list may still feed a previous copy)
+        ZsUnitDesc *hu = (ZsUnitDesc *)c->hUnitsDict.p;
+        const ZsUnitDesc *all = (const ZsUnitDesc *)c->hUnits.p;
+        uint32_t iw = 0, it = nWhole;
+        for (uint32_t i = 0; i < n; i++)                                     // the small units are in chunk order: a chunk's is its whole or its tail
+            for (uint32_t k = c->smallBefore[i]; k < c->smallBefore[i + 1]; k++) hu[srcSizes[i] <= ZS_BLOCK_MAX ? iw++ : it++] = all[k];
+        if (nWhole + nTail && hipMemcpyAsync(c->dUnitsDict.p, hu, sizeof(ZsUnitDesc) * (nWhole + nTail), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        c->planDictWhole = nWhole; c->planDict = true;
+    }
+    return 0;
+}
+// dict (dictionary calls): parsed on the host (parseCompressDict), dDict its bytes in device memory.  Chunks of <= 64 KiB are PREFIXED
+// units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the last <= 64 KiB of the content); the units of longer chunks are
+// parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
+// A call without a dictionary is one with no prefixed units.
+static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                   uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
+                                   const uint8_t *dDict, const ZsCompressDict *dict)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (n == 0) return 0;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    const LzShape &shape = lzShape(level);
+    if (const int e = buildPlan(c, srcOffsets, srcSizes, n, dstOffsets, dict != nullptr)) return e;
+    const uint64_t nBlocks = c->planBlocks;
+    const uint32_t maxChunkBlocks = c->planMaxChunkBlocks;
     const ZsChunkDesc *hc = (const ZsChunkDesc *)c->hChunks.p;
-    // dictionary calls: the units again, in a list of their own - [chunks of <= 64 KiB, one unit each (prefixed)][the other small units]
-    // (wholeBefore / tailBefore: per chunk, as smallBefore), built once per plan; the prefix's table images, once per call
+    // the prefix: the dictionary content's last <= 64 KiB, and its candidate-table images (once per call)
     const uint32_t pfx = dict ? std::min<uint32_t>(dict->contentSize, ZS_BLOCK_MAX) : 0u;
     const uint8_t *dPre = dict ? dDict + dict->contentOff + dict->contentSize - pfx : nullptr;
     if (dict) {
-        if (!c->planDict) {
-            c->wholeBefore.assign((size_t)n + 1, 0); c->tailBefore.assign((size_t)n + 1, 0);
-            uint32_t nWhole = 0, nTail = 0;
-            for (uint32_t i = 0; i < n; i++) {
-                c->wholeBefore[i] = nWhole; c->tailBefore[i] = nTail;
-                if (srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX) nWhole++;
-                else if (srcSizes[i] > ZS_BLOCK_MAX && ((srcSizes[i] - 1) % ZS_UNIT_MAX) < ZS_BLOCK_MAX) nTail++;      // its last unit is one block
-            }
-            c->wholeBefore[n] = nWhole; c->tailBefore[n] = nTail;
-            if (!c->hUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1)) || !c->dUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1))) return ZSMI_error_memory_allocation;
-            if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;         // (the pinned list may still feed a previous copy)
-            ZsUnitDesc *hu = (ZsUnitDesc *)c->hUnitsDict.p;
-            const ZsUnitDesc *all = (const ZsUnitDesc *)c->hUnits.p;
-            uint32_t iw = 0, it = nWhole;
-            for (uint32_t i = 0; i < n; i++)                                     // the small units are in chunk order: a chunk's is its whole or its tail
-                for (uint32_t k = c->smallBefore[i]; k < c->smallBefore[i + 1]; k++) hu[srcSizes[i] <= ZS_BLOCK_MAX ? iw++ : it++] = all[k];
-            if (nWhole + nTail && hipMemcpyAsync(c->dUnitsDict.p, hu, sizeof(ZsUnitDesc) * (nWhole + nTail), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-            c->planDictWhole = nWhole; c->planDict = true;
-        }
         if (!c->dDictImg.reserve((size_t)2 << (ZS_TABLE_LOG_BIG + 2))) return ZSMI_error_memory_allocation;
-        LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(useLong ? 2 : 1), dim3(1024), 0, dPre, pfx, (uint32_t *)c->dDictImg.p);
+        LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(shape.useLong ? 2 : 1), dim3(1024), 0, dPre, pfx, (uint32_t *)c->dDictImg.p);
     }
-    // sub-batches of whole chunks, dealt round-robin to the internal streams; each stream owns a scratch set
-    const int nLanes = (int)std::min<uint64_t>((uint64_t)c->nLanes, std::max<uint64_t>(1, nBlocks / 256));
-    uint32_t cap = (uint32_t)std::min<uint64_t>((nBlocks + nLanes - 1) / nLanes, std::max<uint32_t>(64, c->maxBlocksInFlight / (uint32_t)nLanes));
+    // sub-batches of whole chunks, one after the other through one scratch set.  Every kernel goes to the caller's stream: a stream of
+    // the context's own costs two queue crossings a call (~0.01 - 0.09 ms each: a bench line of 126 GiB/s where the kernels added up to 137).
+    uint32_t cap = (uint32_t)std::min<uint64_t>(nBlocks, std::max<uint32_t>(64, c->maxBlocksInFlight));
     if (cap < maxChunkBlocks) cap = maxChunkBlocks;
-    for (int i = 0; i < nLanes; i++) {
-        zsmi_ctx::Scratch &L = c->lanes[i];
-        if (!L.dDist.reserve((size_t)cap * ZS_BLOCK_MAX * 2 + 256) || !L.dDistHi.reserve((size_t)cap * (ZS_BLOCK_MAX / 8) + 256) || !L.dCand.reserve((size_t)cap * 2 * sizeof(uint32_t) + 64) || !L.dRecs.reserve(((size_t)cap * (ZS_BLOCK_MAX / 4) + 64) * sizeof(uint2)) || !L.dRes.reserve((size_t)cap * ZS_RES_PER_BLOCK * sizeof(uint4) + ((size_t)8 << 20)) || !L.dSeqs.reserve((size_t)cap * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE * sizeof(ZsSeqRec)) ||
-            !L.dHdrs.reserve((size_t)cap * ZS_WALK_RANGES * sizeof(ZsRangeHdr)) || !L.dLits.reserve((size_t)cap * (ZS_BLOCK_MAX + 64)) ||
-            !L.dStreams.reserve((size_t)cap * 4 * ZS_STREAM_STRIDE) || !L.dLitSec.reserve((size_t)cap * ZS_LITSEC_STRIDE) ||
-            !L.dSeqSec.reserve((size_t)cap * ZS_SEQSEC_STRIDE) || !L.dMetas.reserve((size_t)cap * sizeof(ZsBlockMeta))) return ZSMI_error_memory_allocation;
-    }
-    // One lane (the default): its kernels go to the caller's stream itself.  (Through a stream of the lane's own - an event from the caller's
-    // stream in front, one back behind - every call crossed from one hardware queue to another twice: ~0.01 ms a crossing on most boxes of
-    // the pool, ~0.09 on some - a bench line of 126 GiB/s where the same binary's kernels added up to 137.)
-    const bool direct = nLanes == 1;
-    if (!direct) {
-        if (hipEventRecord(c->evStart, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        for (int i = 0; i < nLanes; i++) if (hipStreamWaitEvent(c->lanes[i].stream, c->evStart, 0) != hipSuccess) return ZSMI_error_GENERIC;
-    }
-    uint32_t chunk0 = 0; int turn = 0;
-    while (chunk0 < n) {
-        uint32_t chunk1 = chunk0, nb = 0;
-        while (chunk1 < n && (nb == 0 || nb + hc[chunk1].nBlocks <= cap)) { nb += hc[chunk1].nBlocks; chunk1++; }
+    zsmi_ctx::Scratch &S = c->scratch;
+    if (!S.reserve(cap)) return ZSMI_error_memory_allocation;
+    for (uint32_t chunk0 = 0, chunk1; chunk0 < n; chunk0 = chunk1) {
+        uint32_t nb = 0;
+        for (chunk1 = chunk0; chunk1 < n && (nb == 0 || nb + hc[chunk1].nBlocks <= cap); chunk1++) nb += hc[chunk1].nBlocks;
         const uint32_t block0 = hc[chunk0].firstBlock;
         const ZsBlockDesc *dB = (const ZsBlockDesc *)c->dBlocks.p + block0;
-        zsmi_ctx::Scratch &L = c->lanes[turn % nLanes]; turn++;
-        hipStream_t st = direct ? c->stream : L.stream;
-        // match search per LZ unit: small units (one block) and big units (two blocks) have their own kernel shapes
-        const uint32_t s0 = c->smallBefore[chunk0], ns = c->smallBefore[chunk1] - s0, b0 = c->bigBefore[chunk0], nbig = c->bigBefore[chunk1] - b0;
-        const ZsUnitDesc *dUS = (const ZsUnitDesc *)c->dUnits.p + s0, *dUB = (const ZsUnitDesc *)c->dUnits.p + c->planSmall + b0;
-        #define CAND_LAUNCH(name, TL, NT, cnt, du) LAUNCH_ON(c, st, name, (k_lz_candidates<TL, NT>), dim3(cnt), dim3(64 * ZS_CAND_WAVES(NT)), ZS_CAND_LDS(TL, NT), (const uint8_t *)dSrc, du, block0, \
-                          (uint16_t *)L.dDist.p, (uint8_t *)L.dDistHi.p, (uint32_t *)L.dCand.p)
+        // the sub-batch's LZ units by kernel shape: prefixed, small (a dictionary call: the tails in its own list), big
+        struct { const ZsUnitDesc *d; uint32_t n; } units[3];
+        const uint32_t b0 = c->bigBefore[chunk0];
+        units[kUnitsBig] = { (const ZsUnitDesc *)c->dUnits.p + c->planSmall + b0, c->bigBefore[chunk1] - b0 };
         if (dict) {
-            // prefixed units, then the other small ones from the dictionary call's own list
-            const uint32_t w0 = c->wholeBefore[chunk0], nw = c->wholeBefore[chunk1] - w0, t0 = c->tailBefore[chunk0], nt = c->tailBefore[chunk1] - t0;
-            const ZsUnitDesc *dUW = (const ZsUnitDesc *)c->dUnitsDict.p + w0, *dUT = (const ZsUnitDesc *)c->dUnitsDict.p + c->planDictWhole + t0;
-            #define CAND_PFX_LAUNCH(NT) LAUNCH_ON(c, st, "k_lz_candidates_dict", (k_lz_candidates<ZS_TABLE_LOG_BIG, NT, true>), dim3(nw), dim3(64 * ZS_CAND_WAVES(NT)), ZS_CAND_LDS(ZS_TABLE_LOG_BIG, NT), \
-                              (const uint8_t *)dSrc, dUW, block0, (uint16_t *)L.dDist.p, (uint8_t *)L.dDistHi.p, (uint32_t *)L.dCand.p, (const uint32_t *)c->dDictImg.p, pfx)
-            if (nw) { if (useLong) CAND_PFX_LAUNCH(2); else CAND_PFX_LAUNCH(1); }
-            #undef CAND_PFX_LAUNCH
-            if (nt) { if (useLong) CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 2, nt, dUT); else CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 1, nt, dUT); }
-        } else if (ns) { if (useLong) CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 2, ns, dUS); else CAND_LAUNCH("k_lz_candidates", ZS_TABLE_LOG_SMALL, 1, ns, dUS); }
-        if (nbig) { if (useLong) CAND_LAUNCH("k_lz_candidates_big", ZS_TABLE_LOG_BIG, 2, nbig, dUB); else CAND_LAUNCH("k_lz_candidates_big", ZS_TABLE_LOG_BIG, 1, nbig, dUB); }
-        #undef CAND_LAUNCH
-        #define WALK_LAUNCH(name, LOOK, REPW, BIG, WLOG, cnt, du) LAUNCH_ON(c, st, name, (ZS_WALK_KERNEL(LOOK, REPW, BIG, WLOG)), dim3(cnt), dim3(ZS_WALK_THREADS(BIG, WLOG)), ZS_WALK_LDS((BIG) ? ZS_UNIT_MAX : ZS_BLOCK_MAX), \
-                          (const uint8_t *)dSrc, du, block0, (const uint16_t *)L.dDist.p, (const uint8_t *)L.dDistHi.p, (uint2 *)L.dRecs.p, cap * (ZS_BLOCK_MAX / 4), (uint4 *)L.dRes.p, WLOG, (const uint32_t *)L.dCand.p)
-        if (dict) {
-            const uint32_t w0 = c->wholeBefore[chunk0], nw = c->wholeBefore[chunk1] - w0, t0 = c->tailBefore[chunk0], nt = c->tailBefore[chunk1] - t0;
-            const ZsUnitDesc *dUW = (const ZsUnitDesc *)c->dUnitsDict.p + w0, *dUT = (const ZsUnitDesc *)c->dUnitsDict.p + c->planDictWhole + t0;
-            #define WALK_PFX_LAUNCH(LOOK, REPW, WLOG) LAUNCH_ON(c, st, "k_lz_walk_dict", (ZS_WALK_KERNEL_PFX(LOOK, REPW, WLOG)), dim3(nw), dim3(ZS_WALK_THREADS(false, WLOG)), ZS_WALK_LDS(ZS_UNIT_MAX), \
-                              (const uint8_t *)dSrc, dUW, block0, (const uint16_t *)L.dDist.p, (const uint8_t *)L.dDistHi.p, (uint2 *)L.dRecs.p, cap * (ZS_BLOCK_MAX / 4), (uint4 *)L.dRes.p, WLOG, (const uint32_t *)L.dCand.p, dPre, pfx)
-            if (nw) { if (level <= 2) WALK_PFX_LAUNCH(4, 8, 9); else if (level == 3) WALK_PFX_LAUNCH(4, 4, 8); else WALK_PFX_LAUNCH(8, 8, 8); }
-            #undef WALK_PFX_LAUNCH
-            if (nt) { if (level <= 2) WALK_LAUNCH("k_lz_walk", 4, 8, false, 9, nt, dUT); else if (level == 3) WALK_LAUNCH("k_lz_walk", 4, 4, false, 8, nt, dUT); else WALK_LAUNCH("k_lz_walk", 8, 8, false, 8, nt, dUT); }
-        } else if (ns) { if (level <= 2) WALK_LAUNCH("k_lz_walk", 4, 8, false, 9, ns, dUS); else if (level == 3) WALK_LAUNCH("k_lz_walk", 4, 4, false, 8, ns, dUS); else WALK_LAUNCH("k_lz_walk", 8, 8, false, 8, ns, dUS); }
-        if (nbig) { if (level <= 2) WALK_LAUNCH("k_lz_walk_big", 4, 8, true, 9, nbig, dUB); else if (level == 3) WALK_LAUNCH("k_lz_walk_big", 4, 4, true, 8, nbig, dUB); else WALK_LAUNCH("k_lz_walk_big", 8, 8, true, 8, nbig, dUB); }
-        #undef WALK_LAUNCH
-        LAUNCH_ON(c, st, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, (const uint2 *)L.dRecs.p, (const uint4 *)L.dRes.p, (ZsSeqRec *)L.dSeqs.p, (ZsRangeHdr *)L.dHdrs.p, walkLog);
-        if (c->stopAfterWalk) { chunk0 = chunk1; continue; }
-        // sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and reads the sequence
-        // sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)
-        if (dict) {
-            LAUNCH_ON(c, st, "k_encode_sequences", (k_encode_sequences_dict<ZS_SEQ_GROUP>), dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)L.dSeqs.p, (const ZsRangeHdr *)L.dHdrs.p,
-                      (uint8_t *)L.dSeqSec.p, (ZsBlockMeta *)L.dMetas.p, c->stopSeq, (uint8_t *)L.dLits.p, (uint8_t *)L.dStreams.p, (uint2 *)L.dDist.p, make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u));
-            LAUNCH_ON(c, st, "k_encode_literals", k_encode_literals_dict, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)L.dSeqs.p, (const ZsRangeHdr *)L.dHdrs.p,
-                      (uint8_t *)L.dLits.p, (uint8_t *)L.dStreams.p, (uint8_t *)L.dLitSec.p, (ZsBlockMeta *)L.dMetas.p, c->stopLit,
-                      (const ZsChunkDesc *)c->dChunks.p, (const uint8_t *)L.dSeqSec.p, (uint8_t *)dDst, dDstSizes, dict->dictID);
-            if (maxChunkBlocks > 1)
-                LAUNCH_ON(c, st, "k_assemble_frames", k_assemble_frames_dict, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, (const ZsChunkDesc *)c->dChunks.p,
-                          (const ZsBlockDesc *)c->dBlocks.p, (const ZsBlockMeta *)L.dMetas.p, (const uint8_t *)L.dLitSec.p, (const uint8_t *)L.dSeqSec.p, block0, (uint8_t *)dDst, dDstSizes, chunk0, dict->dictID);
-            chunk0 = chunk1;
-            continue;
+            const uint32_t w0 = c->wholeBefore[chunk0], t0 = c->tailBefore[chunk0];
+            units[kUnitsPfx] = { (const ZsUnitDesc *)c->dUnitsDict.p + w0, c->wholeBefore[chunk1] - w0 };
+            units[kUnitsSmall] = { (const ZsUnitDesc *)c->dUnitsDict.p + c->planDictWhole + t0, c->tailBefore[chunk1] - t0 };
+        } else {
+            const uint32_t s0 = c->smallBefore[chunk0];
+            units[kUnitsPfx] = { nullptr, 0 };
+            units[kUnitsSmall] = { (const ZsUnitDesc *)c->dUnits.p + s0, c->smallBefore[chunk1] - s0 };
         }
-        LAUNCH_ON(c, st, "k_encode_sequences", (k_encode_sequences<ZS_SEQ_GROUP>), dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)L.dSeqs.p, (const ZsRangeHdr *)L.dHdrs.p,
-                  (uint8_t *)L.dSeqSec.p, (ZsBlockMeta *)L.dMetas.p, c->stopSeq, (uint8_t *)L.dLits.p, (uint8_t *)L.dStreams.p, (uint2 *)L.dDist.p);
-        LAUNCH_ON(c, st, "k_encode_literals", k_encode_literals, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)L.dSeqs.p, (const ZsRangeHdr *)L.dHdrs.p,
-                  (uint8_t *)L.dLits.p, (uint8_t *)L.dStreams.p, (uint8_t *)L.dLitSec.p, (ZsBlockMeta *)L.dMetas.p, c->stopLit,
-                  (const ZsChunkDesc *)c->dChunks.p, (const uint8_t *)L.dSeqSec.p, (uint8_t *)dDst, dDstSizes);
-        if (maxChunkBlocks > 1)                    // chunks of several blocks
-            LAUNCH_ON(c, st, "k_assemble_frames", k_assemble_frames, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, (const ZsChunkDesc *)c->dChunks.p,
-                      (const ZsBlockDesc *)c->dBlocks.p, (const ZsBlockMeta *)L.dMetas.p, (const uint8_t *)L.dLitSec.p, (const uint8_t *)L.dSeqSec.p, block0, (uint8_t *)dDst, dDstSizes, chunk0);
-        chunk0 = chunk1;
-    }
-    for (int i = 0; !direct && i < nLanes; i++) {
-        if (hipEventRecord(c->lanes[i].done, c->lanes[i].stream) != hipSuccess) return ZSMI_error_GENERIC;
-        if (hipStreamWaitEvent(c->stream, c->lanes[i].done, 0) != hipSuccess) return ZSMI_error_GENERIC;
+        for (int k = 0; k < 3; k++) {
+            const LzKernel<CandFn> &K = shape.cand[k];
+            const bool p = k == kUnitsPfx;
+            if (units[k].n)
+                LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, (uint16_t *)S.dDist.p,
+                       (uint8_t *)S.dDistHi.p, (uint32_t *)S.dCand.p, p ? (const uint32_t *)c->dDictImg.p : nullptr, p ? pfx : 0u);
+        }
+        for (int k = 0; k < 3; k++) {
+            const LzKernel<WalkFn> &K = shape.walk[k];
+            const bool p = k == kUnitsPfx;
+            if (units[k].n)
+                LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, (const uint16_t *)S.dDist.p,
+                       (const uint8_t *)S.dDistHi.p, (uint2 *)S.dRecs.p, cap * (ZS_BLOCK_MAX / 4), (uint4 *)S.dRes.p, shape.walkLog, (const uint32_t *)S.dCand.p,
+                       p ? dPre : nullptr, p ? pfx : 0u);
+        }
+        LAUNCH(c, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, (const uint2 *)S.dRecs.p, (const uint4 *)S.dRes.p, (ZsSeqRec *)S.dSeqs.p, (ZsRangeHdr *)S.dHdrs.p, shape.walkLog);
+        if (c->stopAfterWalk) continue;
+        // sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and reads the sequence
+        // sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  A dictionary call's kernels
+        // take its recent offsets and its ID besides.
+        auto sequences = [&](auto kernel, auto... dictArgs) {
+            LAUNCH(c, "k_encode_sequences", kernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)S.dSeqs.p,
+                   (const ZsRangeHdr *)S.dHdrs.p, (uint8_t *)S.dSeqSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopSeq, (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p,
+                   (uint2 *)S.dDist.p, dictArgs...);
+        };
+        auto literals = [&](auto kernel, auto... dictArgs) {
+            LAUNCH(c, "k_encode_literals", kernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p, (const ZsRangeHdr *)S.dHdrs.p,
+                   (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p, (uint8_t *)S.dLitSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopLit,
+                   (const ZsChunkDesc *)c->dChunks.p, (const uint8_t *)S.dSeqSec.p, (uint8_t *)dDst, dDstSizes, dictArgs...);
+        };
+        auto assemble = [&](auto kernel, auto... dictArgs) {     // chunks of several blocks
+            LAUNCH(c, "k_assemble_frames", kernel, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, (const ZsChunkDesc *)c->dChunks.p,
+                   (const ZsBlockDesc *)c->dBlocks.p, (const ZsBlockMeta *)S.dMetas.p, (const uint8_t *)S.dLitSec.p, (const uint8_t *)S.dSeqSec.p, block0,
+                   (uint8_t *)dDst, dDstSizes, chunk0, dictArgs...);
+        };
+        if (dict) {
+            sequences(k_encode_sequences_dict<ZS_SEQ_GROUP>, make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u));
+            literals(k_encode_literals_dict, dict->dictID);
+            if (maxChunkBlocks > 1) assemble(k_assemble_frames_dict, dict->dictID);
+        } else {
+            sequences(k_encode_sequences<ZS_SEQ_GROUP>);
+            literals(k_encode_literals);
+            if (maxChunkBlocks > 1) assemble(k_assemble_frames);
+        }
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
@@ -694,8 +669,7 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
     ZsDecItem *hi = (ZsDecItem *)hItems.p;
     for (uint32_t i = 0; i < n; i++) { hi[i].srcOff = srcOffsets[i]; hi[i].dstOff = dstOffsets[i]; hi[i].srcSize = srcSizes[i]; hi[i].dstCap = dstCaps[i]; }
     if (hipMemcpyAsync(c->dItems.p, hi, sizeof(ZsDecItem) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (!c->hItemsEv[hb] && hipEventCreateWithFlags(&c->hItemsEv[hb], hipEventDisableTiming) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipEventRecord(c->hItemsEv[hb], c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipEventRecord(c->hItemsEv[hb], c->stream) != hipSuccess) { (void)hipStreamSynchronize(c->stream); return ZSMI_error_GENERIC; }   // (the buffer is idle after that)
     c->hItemsBusy[hb] = true;
     const bool useDict = dDict != nullptr && dictSize != 0;
     const bool fast = c->decodeFast && !useDict;                  // frames that name a dictionary go to the general kernel
@@ -749,7 +723,6 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
                      !fitBuf(c->dHufTabs, (size_t)cap * maxBlocks * ZS_FAST_HUFTAB_BYTES) || !fitBuf(c->dSeqTabs, (size_t)cap * maxBlocks * ZS_FAST_SEQTAB_BYTES) ||
                      !fitBuf(c->dSeqOut, (size_t)cap * maxBlocks * seqCap * sizeof(ZsFastSeq)) || !fitBuf(c->dSeqLists, (8 + 2 * (size_t)cap * maxBlocks + cap) * sizeof(uint32_t)))) return ZSMI_error_memory_allocation;
         if (!fast && !c->dSeqLists.reserve(8 * sizeof(uint32_t))) return ZSMI_error_memory_allocation;
-        c->lastDecodeScratch = (fast ? (size_t)cap * perItem : 0) + poolBytes;
     }
     for (uint32_t i0 = 0; i0 < n; i0 += cap) {
         const uint32_t cnt = std::min(cap, n - i0);
@@ -771,9 +744,8 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
                 // the 37 KiB image and a round is 2 CUs' worth of Huffman AND sequence groups (8192 items on 256 CUs, ~0.48 ms); apart, 5 workgroups of 30 KiB and
                 // a round of each kind is 20480 items (~0.55 ms, twice).  The fewer round-milliseconds win - measured over 8192 .. 65536 frames of 32 KiB: fused
                 // below 20480 items except right at it, at 22528 .. 32768 (4.42 against 4.64 ms at 28672) and 49152; apart at 20480, 36864 .. 45056, 53248 .. 61440.
-                bool fuse;
-                if (c->decodeFuseSet) fuse = vcnt <= c->decodeFuseBelow;
-                else { const uint32_t perF = 32u * c->cus, perS = 80u * c->cus; fuse = ((vcnt + perF - 1) / perF) * 48u < 2u * ((vcnt + perS - 1) / perS) * 55u; }
+                const uint32_t perF = 32u * c->cus, perS = 80u * c->cus;
+                const bool fuse = ((vcnt + perF - 1) / perF) * 48u < 2u * ((vcnt + perS - 1) / perS) * 55u;
                 if (fuse && mb == 1) {
                     // a round of workgroups or less of one-block items: the four entropy launches as one (k_dec_entropy), the 2.5 KiB sequence class at 4 items a wavefront as below
                     // (items of several blocks - 128 KiB frames: 64 KiB blocks, the 2.5 KiB table class at 16 a wavefront - keep the separate launches: 8192 two-block frames of text
@@ -790,24 +762,17 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
                     // wavefront's instructions are what the kernel costs: 57344 frames of Python sources 4.00 -> 3.78 ms, of a binary table 4.99 -> 4.00), 4 a wavefront
                     // when it is a fraction of it (libzstd's 32 KiB frames: 9 % of the blocks; fewer, emptier wavefronts finish sooner: 3.8 vs 5.2 ms) or the call is small.
                     // Both shapes are launched; each looks at the list's length and leaves at once when the other one serves it.
-                    const uint32_t many = c->seqLog9Group == 16 ? 0u : (c->seqLog9Group == 4 ? 0xFFFFFFFFu : ZS_FAST_SEQGROUP_MANY);
-                    LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, ZS_FAST_SEQGROUP>), dim3(((cnt + ZS_FAST_SEQGROUP - 1) / ZS_FAST_SEQGROUP) * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dSeqTabs.p, (ZsFastSeq *)c->dSeqOut.p, mb, cap, (const uint32_t *)dLists, seqCap, many, 0xFFFFFFFFu);
-                    LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, 4u>), dim3(((cnt + 3) / 4) * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dSeqTabs.p, (ZsFastSeq *)c->dSeqOut.p, mb, cap, (const uint32_t *)dLists, seqCap, 0u, many);
+                    LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, ZS_FAST_SEQGROUP>), dim3(((cnt + ZS_FAST_SEQGROUP - 1) / ZS_FAST_SEQGROUP) * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dSeqTabs.p, (ZsFastSeq *)c->dSeqOut.p, mb, cap, (const uint32_t *)dLists, seqCap, ZS_FAST_SEQGROUP_MANY, 0xFFFFFFFFu);
+                    LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, 4u>), dim3(((cnt + 3) / 4) * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dSeqTabs.p, (ZsFastSeq *)c->dSeqOut.p, mb, cap, (const uint32_t *)dLists, seqCap, 0u, ZS_FAST_SEQGROUP_MANY);
                 }
             }
             // one-block items: 7 wavefronts a SIMD (decode_fast.hip) - but a call that fits ONE round of wavefronts at 8 a SIMD and not at 7 (7169 .. 8192 items on 256 CUs)
             // takes the 8 form: a round of it is ~12 % longer (64 VGPRs: more spills), one round instead of two is not (8192 frames: execute 0.67 -> 0.59 ms; at every
             // other size measured, 4096 .. 57344, the 7 form is as fast or faster)
             const bool oneRoundAt8 = cnt > 7u * 4u * c->cus && cnt <= 8u * 4u * c->cus;
-            if (maxBlocks == 1 && (c->execWaves == 8 || (c->execWaves == 0 && oneRoundAt8)))
-                LAUNCH(c, "k_dec_execute", (k_dec_execute<4, 8>), dim3((cnt + 3) / 4), dim3(256), 0, (const uint8_t *)dSrc, dI, cnt, dD, (ZsFastSeq *)c->dSeqOut.p,
-                       (uint8_t *)c->dLitScratch.p, (uint8_t *)dDst, dDstSizes + i0, cap, descSlots, litStride, seqCap);
-            else if (maxBlocks == 1)
-                LAUNCH(c, "k_dec_execute", (k_dec_execute<4, 7>), dim3((cnt + 3) / 4), dim3(256), 0, (const uint8_t *)dSrc, dI, cnt, dD, (ZsFastSeq *)c->dSeqOut.p,
-                       (uint8_t *)c->dLitScratch.p, (uint8_t *)dDst, dDstSizes + i0, cap, descSlots, litStride, seqCap);
-            else
-                LAUNCH(c, "k_dec_execute", (k_dec_execute<4, 6>), dim3((cnt + 3) / 4), dim3(256), 0, (const uint8_t *)dSrc, dI, cnt, dD, (ZsFastSeq *)c->dSeqOut.p,
-                       (uint8_t *)c->dLitScratch.p, (uint8_t *)dDst, dDstSizes + i0, cap, descSlots, litStride, seqCap);
+            const auto execute = maxBlocks > 1 ? k_dec_execute<4, 6> : (oneRoundAt8 ? k_dec_execute<4, 8> : k_dec_execute<4, 7>);
+            LAUNCH(c, "k_dec_execute", execute, dim3((cnt + 3) / 4), dim3(256), 0, (const uint8_t *)dSrc, dI, cnt, dD, (ZsFastSeq *)c->dSeqOut.p,
+                   (uint8_t *)c->dLitScratch.p, (uint8_t *)dDst, dDstSizes + i0, cap, descSlots, litStride, seqCap);
             LAUNCH(c, "k_dec_checksum", k_dec_checksum, dim3((cnt + 15) / 16), dim3(64), 0, dI, cnt, (const ZsFastDesc *)dD, (const uint8_t *)dDst, dDstSizes + i0);
             doneFlags = &dD->fast;
         }
@@ -884,12 +849,12 @@ extern "C" int zsmi_packFramesDevice(zsmi_ctx *c, const void *dFrames, const uin
 // ---------------------------------------------------------------------------------------------
 // host-buffer forms
 // ---------------------------------------------------------------------------------------------
-static bool spanOf(const uint64_t *off, const uint32_t *sz, const uint32_t *caps, uint32_t n, uint64_t &lo, uint64_t &hi)
+// [lo, hi): the bytes items of len[i] bytes at off[i] span
+static void spanOf(const uint64_t *off, const uint32_t *len, uint32_t n, uint64_t &lo, uint64_t &hi)
 {
     lo = ~0ull; hi = 0;
-    for (uint32_t i = 0; i < n; i++) { const uint64_t a = off[i], b = off[i] + (caps ? caps[i] : sz[i]); if (a < lo) lo = a; if (b > hi) hi = b; }
+    for (uint32_t i = 0; i < n; i++) { const uint64_t a = off[i], b = off[i] + len[i]; if (a < lo) lo = a; if (b > hi) hi = b; }
     if (lo == ~0ull) { lo = 0; hi = 0; }
-    return true;
 }
 // Results of a host-buffer call go back to the caller's buffer: items that sit back to back are one transfer; a scattered batch (compressed
 // frames in bound-sized slots) is packed on the device, crosses PCIe once into pinned memory and is placed from there (a transfer per item costs
@@ -933,6 +898,29 @@ static int copyBack(zsmi_ctx *c, const uint8_t *dBase, const uint64_t *dof, uint
     }
     return 0;
 }
+// A host-buffer call through the context's staging buffers: the dictionary (if any) and the span of the sources go to the device, run() is
+// the device form with the offsets rebased to the spans (dstLen[i]: the bytes item i may write), then the sizes and the results come back.
+template <class Run>
+static int staged(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, void *dst, const uint64_t *dstOffsets,
+                  const uint32_t *dstLen, uint32_t *dstSizes, const void *dict, size_t dictSize, Run run)
+{
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (dict) {
+        if (!c->sDict.reserve(dictSize + 64)) return ZSMI_error_memory_allocation;
+        if (hipMemcpyAsync(c->sDict.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    }
+    uint64_t slo, shi, dlo, dhi;
+    spanOf(srcOffsets, srcSizes, n, slo, shi);
+    spanOf(dstOffsets, dstLen, n, dlo, dhi);
+    if (!c->sSrc.reserve(shi - slo + 64) || !c->sDst.reserve(dhi - dlo + 64) || !c->sSizes.reserve(sizeof(uint32_t) * n)) return ZSMI_error_memory_allocation;
+    std::vector<uint64_t> so(n), dof(n);
+    for (uint32_t i = 0; i < n; i++) { so[i] = srcOffsets[i] - slo; dof[i] = dstOffsets[i] - dlo; }
+    if (shi > slo && hipMemcpyAsync(c->sSrc.p, (const uint8_t *)src + slo, shi - slo, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int rc = run(so.data(), dof.data(), (uint32_t *)c->sSizes.p)) return rc;
+    if (hipMemcpyAsync(dstSizes, c->sSizes.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    return copyBack(c, (const uint8_t *)c->sDst.p, dof.data(), (uint8_t *)dst, dstOffsets, dstSizes, n);
+}
 static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                  uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level, const void *dict, size_t dictSize)
 {
@@ -944,26 +932,13 @@ static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *s
         if (const int e = parseCompressDict((const uint8_t *)dict, dictSize, dc)) return e;
     }
     if (n == 0) return 0;
-    if (useDict) {
-        if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-        if (!c->sDict.reserve(dictSize + 64)) return ZSMI_error_memory_allocation;
-        if (hipMemcpyAsync(c->sDict.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    }
-    uint64_t slo, shi, dlo, dhi;
-    spanOf(srcOffsets, srcSizes, nullptr, n, slo, shi);
     std::vector<uint32_t> bounds(n);
     for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
-    spanOf(dstOffsets, nullptr, bounds.data(), n, dlo, dhi);
-    if (!c->sSrc.reserve(shi - slo + 64) || !c->sDst.reserve(dhi - dlo + 64) || !c->sSizes.reserve(sizeof(uint32_t) * n + sizeof(uint64_t) * n)) return ZSMI_error_memory_allocation;
-    std::vector<uint64_t> so(n), dof(n);
-    for (uint32_t i = 0; i < n; i++) { so[i] = srcOffsets[i] - slo; dof[i] = dstOffsets[i] - dlo; }
-    if (shi > slo && hipMemcpyAsync(c->sSrc.p, (const uint8_t *)src + slo, shi - slo, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    uint32_t *dSizes = (uint32_t *)((uint8_t *)c->sSizes.p + sizeof(uint64_t) * n);
-    const int rc = compressBatchDeviceImpl(c, c->sSrc.p, so.data(), srcSizes, n, c->sDst.p, dof.data(), dSizes, level, useDict ? (const uint8_t *)c->sDict.p : nullptr, useDict ? &dc : nullptr);
-    if (rc) return rc;
-    if (hipMemcpyAsync(dstSizes, dSizes, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    return copyBack(c, (const uint8_t *)c->sDst.p, dof.data(), (uint8_t *)dst, dstOffsets, dstSizes, n);
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes, useDict ? dict : nullptr, dictSize,
+                  [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
+                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, useDict ? (const uint8_t *)c->sDict.p : nullptr,
+                                                     useDict ? &dc : nullptr);
+                  });
 }
 extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                       uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level)
@@ -984,23 +959,11 @@ static int decompressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t 
     if (n == 0) return 0;
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
     const bool useDict = dict != nullptr && dictSize != 0;
-    if (useDict) {
-        if (!c->sDict.reserve(dictSize + 64)) return ZSMI_error_memory_allocation;
-        if (hipMemcpyAsync(c->sDict.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    }
-    uint64_t slo, shi, dlo, dhi;
-    spanOf(srcOffsets, srcSizes, nullptr, n, slo, shi);
-    spanOf(dstOffsets, nullptr, dstCaps, n, dlo, dhi);
-    if (!c->sSrc.reserve(shi - slo + 64) || !c->sDst.reserve(dhi - dlo + 64) || !c->sSizes.reserve(sizeof(uint32_t) * n)) return ZSMI_error_memory_allocation;
-    std::vector<uint64_t> so(n), dof(n);
-    for (uint32_t i = 0; i < n; i++) { so[i] = srcOffsets[i] - slo; dof[i] = dstOffsets[i] - dlo; }
-    if (shi > slo && hipMemcpyAsync(c->sSrc.p, (const uint8_t *)src + slo, shi - slo, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    const int rc = decompressBatchDeviceImpl(c, c->sSrc.p, so.data(), srcSizes, n, c->sDst.p, dof.data(), dstCaps, (uint32_t *)c->sSizes.p,
-                                             useDict ? c->sDict.p : nullptr, useDict ? (uint32_t)dictSize : 0u);
-    if (rc) return rc;
-    if (hipMemcpyAsync(dstSizes, c->sSizes.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    return copyBack(c, (const uint8_t *)c->sDst.p, dof.data(), (uint8_t *)dst, dstOffsets, dstSizes, n);
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, useDict ? dict : nullptr, dictSize,
+                  [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
+                      return decompressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dstCaps, dSizes, useDict ? c->sDict.p : nullptr,
+                                                       useDict ? (uint32_t)dictSize : 0u);
+                  });
 }
 
 extern "C" int zsmi_decompressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
@@ -1098,15 +1061,7 @@ extern "C" size_t zsmi_compress_usingDict(void *dst, size_t dstCapacity, const v
 }
 extern "C" size_t zsmi_decompress(void *dst, size_t dstCapacity, const void *src, size_t srcSize)
 {
-    if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
-    Borrowed b; zsmi_ctx *c = b.c;
-    if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
-    const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
-    const uint32_t cap = (uint32_t)std::min<size_t>(dstCapacity, 0xFFFFFF00u);
-    const int rc = zsmi_decompressBatchHost(c, src, &so, &ss, 1, dst, &dof, &cap, &ds);
-    if (rc) return ZSMI_ERR(rc);
-    if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
-    return ds;
+    return zsmi_decompress_usingDict(dst, dstCapacity, src, srcSize, nullptr, 0);
 }
 
 extern "C" size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize)
@@ -1135,8 +1090,8 @@ extern "C" int zsmi_dbg_copyScratch(zsmi_ctx *c, int which, void *hostDst, size_
 {
     if (!c) return -1;
     (void)hipStreamSynchronize(c->stream);
-    zsmi_ctx::Scratch &L0 = c->lanes[0];
-    DevBuf *b = which == 0 ? &L0.dDist : which == 1 ? &L0.dSeqs : which == 2 ? &L0.dHdrs : which == 4 ? &L0.dDistHi : which == 7 ? &L0.dRecs : which == 8 ? &L0.dRes : which == 5 ? &c->dLitScratch : which == 9 ? &c->dHufTabs : which == 10 ? &c->dFastDesc : &L0.dMetas;
+    zsmi_ctx::Scratch &S = c->scratch;
+    DevBuf *b = which == 0 ? &S.dDist : which == 1 ? &S.dSeqs : which == 2 ? &S.dHdrs : which == 4 ? &S.dDistHi : which == 7 ? &S.dRecs : which == 8 ? &S.dRes : which == 5 ? &c->dLitScratch : which == 9 ? &c->dHufTabs : which == 10 ? &c->dFastDesc : &S.dMetas;
     if (bytes > b->cap) return -2;
     return hipMemcpy(hostDst, b->p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }
