@@ -29,8 +29,33 @@ static int loadLibzstd(void)
     return state == 1;
 }
 
+/* a dictionary as zsmi_compress_usingDict reads it: oracle D's parse (content, ID, recent offsets); the prefix is the content's last
+ * min(content, 64 KiB) bytes */
+typedef struct { const uint8_t *pre; uint32_t pfx, dictID, rep[3]; } EDict;
+static size_t loadDict(EDict *e, const void *dict, size_t dictSize)
+{
+    size_t contentOff = 0, content;
+    if (dictSize > 0xFFFFFFFFu || zso_isError(zso_dictParams(dict, dictSize, &contentOff, &e->dictID, e->rep)))
+        return (size_t)0 - (size_t)ZSO_dictionary_corrupted;
+    content = dictSize - contentOff;
+    e->pfx = (uint32_t)(content < 65536 ? content : 65536);
+    e->pre = (const uint8_t *)dict + dictSize - e->pfx;
+    return 0;
+}
+
+size_t zso_compress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level)
+{
+    EDict e;
+    size_t r;
+    if (!dict || !dictSize) return zso_compress(dst, dstCapacity, src, srcSize, level);
+    r = loadDict(&e, dict, dictSize);
+    if (zso_isError(r)) return r;
+    return zso_compressFrame(dst, dstCapacity, src, srcSize, level, e.pre, e.pfx, e.dictID, e.rep);
+}
+
 typedef struct {
     int compress, level, useLibzstd;
+    const EDict *dict;
     uint8_t *dst; const uint64_t *dstOffsets; const uint32_t *dstCaps; uint32_t *dstSizes;
     const uint8_t *src; const uint64_t *srcOffsets; const uint32_t *srcSizes;
     uint32_t begin, end; int failed;
@@ -50,7 +75,9 @@ static void *worker(void *arg)
         }
         if (j->compress) {
             size_t const cap = zso_compressBound(j->srcSizes[i]);
-            r = zso_compress(j->dst + j->dstOffsets[i], cap, j->src + j->srcOffsets[i], j->srcSizes[i], j->level);
+            const EDict *e = j->dict;
+            r = e ? zso_compressFrame(j->dst + j->dstOffsets[i], cap, j->src + j->srcOffsets[i], j->srcSizes[i], j->level, e->pre, e->pfx, e->dictID, e->rep)
+                  : zso_compress(j->dst + j->dstOffsets[i], cap, j->src + j->srcOffsets[i], j->srcSizes[i], j->level);
         } else {
             r = zso_decompress(j->dst + j->dstOffsets[i], j->dstCaps[i], j->src + j->srcOffsets[i], j->srcSizes[i]);
         }
@@ -83,7 +110,21 @@ int zso_compressBatch(void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes,
                       const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                       uint32_t n, int level, int nThreads)
 {
-    Job j = { 1, level, 0, (uint8_t *)dst, dstOffsets, NULL, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
+    Job j = { 1, level, 0, NULL, (uint8_t *)dst, dstOffsets, NULL, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
+    return run(j, n, nThreads);
+}
+
+/* one dictionary for every chunk, parsed once: a dictionary oracle D refuses gives -30 before any chunk is compressed */
+int zso_compressBatch_usingDict(void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes,
+                                const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                uint32_t n, int level, int nThreads, const void *dict, size_t dictSize)
+{
+    Job j = { 1, level, 0, NULL, (uint8_t *)dst, dstOffsets, NULL, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
+    EDict e;
+    if (dict && dictSize) {
+        if (zso_isError(loadDict(&e, dict, dictSize))) return -ZSO_dictionary_corrupted;
+        j.dict = &e;
+    }
     return run(j, n, nThreads);
 }
 
@@ -91,7 +132,7 @@ int zso_decompressBatch(void *dst, const uint64_t *dstOffsets, const uint32_t *d
                         const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                         uint32_t n, int nThreads)
 {
-    Job j = { 0, 0, 0, (uint8_t *)dst, dstOffsets, dstCaps, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
+    Job j = { 0, 0, 0, NULL, (uint8_t *)dst, dstOffsets, dstCaps, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
     return run(j, n, nThreads);
 }
 
@@ -100,7 +141,7 @@ int zso_libzstdCompressBatch(void *dst, const uint64_t *dstOffsets, uint32_t *ds
                              const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                              uint32_t n, int level, int nThreads)
 {
-    Job j = { 1, level, 1, (uint8_t *)dst, dstOffsets, NULL, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
+    Job j = { 1, level, 1, NULL, (uint8_t *)dst, dstOffsets, NULL, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
     if (!loadLibzstd()) return -2;
     return run(j, n, nThreads);
 }
@@ -108,7 +149,7 @@ int zso_libzstdDecompressBatch(void *dst, const uint64_t *dstOffsets, const uint
                                const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                uint32_t n, int nThreads)
 {
-    Job j = { 0, 0, 1, (uint8_t *)dst, dstOffsets, dstCaps, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
+    Job j = { 0, 0, 1, NULL, (uint8_t *)dst, dstOffsets, dstCaps, dstSizes, (const uint8_t *)src, srcOffsets, srcSizes, 0, 0, 0 };
     if (!loadLibzstd()) return -2;
     return run(j, n, nThreads);
 }

@@ -1359,6 +1359,23 @@ static size_t insertDictionary(DCtx *d, const void *dict, size_t dictSize)
     return 0;
 }
 
+/* what a usingDict decode loads from a dictionary (dictSize > 0), for oracle E: where its content starts, its ID, the recent offsets the
+ * first block starts from.  0, or ERR(dictionary_corrupted) for a dictionary the decode would refuse */
+size_t zso_dictParams(const void *dict, size_t dictSize, size_t *contentOff, uint32_t *dictID, uint32_t rep[3])
+{
+    DCtx *d = (DCtx *)malloc(sizeof(DCtx));
+    size_t r;
+    if (!d) return ERR(ZSO_memory_allocation);
+    decompressBegin(d);
+    r = insertDictionary(d, dict, dictSize);
+    if (!zso_isError(r)) {
+        *contentOff = (size_t)(d->dictContent - (const BYTE *)dict); *dictID = d->dictIDLoaded;
+        rep[0] = d->rep[0]; rep[1] = d->rep[1]; rep[2] = d->rep[2];
+    }
+    free(d);
+    return r;
+}
+
 /* ZSTD_decompress_usingDict :2162-2167 -> DecompressMultiFrame :2096-2160, with a fresh context per call (:2174-2180).
  * dict == NULL / dictSize == 0: the reference's public Decompress */
 size_t zso_decompress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize)

@@ -518,6 +518,7 @@ typedef struct {
     BYTE llCode[BLOCK_MAX / 3 + 8], mlCode[BLOCK_MAX / 3 + 8], ofCode[BLOCK_MAX / 3 + 8];
     U32 ofValue[BLOCK_MAX / 3 + 8];           /* offset field value: 1..3 repcode, else offset+3 */
     BYTE tmp[BLOCK_MAX + 1024];
+    BYTE unitBytes[2 * BLOCK_MAX];            /* a prefixed unit: the prefix, then the chunk */
     int matchless;                            /* the unit's candidates are too few to be worth a parse: its blocks get no sequences */
 } Work;
 
@@ -542,29 +543,36 @@ static U32 mul24(U32 a, U32 b) { return (a & 0xFFFFFFu) * (b & 0xFFFFFFu); }
 static U32 hashShort(const BYTE *p) { U32 const lo = rd32(p), hi = rd32(p + 4); return mul24(lo, 0x9E3779u) + mul24((lo >> 16) | (hi << 16), 0x85EBCBu); }
 static U32 hashLong(const BYTE *p) { U32 const lo = rd32(p), hi = rd32(p + 4); return mul24(lo, 0x9E3779u) + mul24((lo >> 24) | (hi << 8), 0x85EBCBu) + mul24(hi >> 16, 0xC2B2AFu); }
 static U32 tableLogFor(U32 unitN) { return unitN > BLOCK_MAX ? MAX_TABLE_LOG : MAX_TABLE_LOG - 1; }
-static void findCandidates(Work *w, const BYTE *src, U32 n, const EParams *prm)
+/* PREFIXED units (dictionary calls, zso_compress_usingDict): pfx > 0 bytes of dictionary content lie in front of src (a chunk of
+ * <= 64 KiB), and the unit's positions are virtual: [0, pfx) the prefix, [pfx, pfx + n) the chunk.  The tables have 2^14 slots whatever
+ * pfx is, and start from the state after inserting the prefix's positions [0, pfx - 7) in order (the last 7 would hash bytes of the
+ * chunk: left out, as a unit's own last 7 are); then only the chunk's positions are inserted, as pfx + p, so a distance may reach into
+ * the prefix.  dist[], the matchless count and everything after count chunk positions.  pfx = 0: a plain unit. */
+static void slotInsert(U32 *tab, U32 tlog, U32 h, U32 v, U32 *d)
 {
-    U32 const tlog = tableLogFor(n);
+    U32 const e = (((h >> (32 - tlog - 15)) & 0x7FFFu) << 17) | v;
+    U32 const o = tab[h >> (32 - tlog)];
+    tab[h >> (32 - tlog)] = e;
+    if (o != SLOT_EMPTY && ((o ^ e) >> 17) == 0) *d = v - (o & 0x1FFFFu);
+}
+static void findCandidates(Work *w, const BYTE *src, U32 n, const EParams *prm, U32 pfx)
+{
+    U32 const tlog = pfx ? MAX_TABLE_LOG : tableLogFor(n);
     U32 p, found = 0;
     memset(w->dist, 0, n * sizeof(U32));
     w->matchless = 0;
     if (n < 8) return;
     memset(w->tabS, 0xFF, sizeof(U32) << tlog);
     if (prm->useLong) memset(w->tabL, 0xFF, sizeof(U32) << tlog);
+    for (p = 0; p + 8 <= pfx; p++) {                                /* the prefix: table state only (k_lz_dict_tables) */
+        U32 none = 0;
+        slotInsert(w->tabS, tlog, hashShort(src - pfx + p), p, &none);
+        if (prm->useLong) slotInsert(w->tabL, tlog, hashLong(src - pfx + p), p, &none);
+    }
     for (p = 0; p + 8 <= n; p++) {
-        U32 const hs = hashShort(src + p);
-        U32 const es = (((hs >> (32 - tlog - 15)) & 0x7FFFu) << 17) | p;
-        U32 const os = w->tabS[hs >> (32 - tlog)];
         U32 d = 0;
-        w->tabS[hs >> (32 - tlog)] = es;
-        if (os != SLOT_EMPTY && ((os ^ es) >> 17) == 0) d = p - (os & 0x1FFFFu);
-        if (prm->useLong) {
-            U32 const hl = hashLong(src + p);
-            U32 const el = (((hl >> (32 - tlog - 15)) & 0x7FFFu) << 17) | p;
-            U32 const ol = w->tabL[hl >> (32 - tlog)];
-            w->tabL[hl >> (32 - tlog)] = el;
-            if (ol != SLOT_EMPTY && ((ol ^ el) >> 17) == 0) d = p - (ol & 0x1FFFFu);
-        }
+        slotInsert(w->tabS, tlog, hashShort(src + p), pfx + p, &d);
+        if (prm->useLong) slotInsert(w->tabL, tlog, hashLong(src + p), pfx + p, &d);   /* the long table's distance wins */
         w->dist[p] = d;
         found += d != 0;
     }
@@ -586,12 +594,16 @@ static U32 matchLen(const BYTE *src, U32 a, U32 b, U32 limit)   /* common prefix
  * tried, and only while ip lies at least that offset inside the unit) or stage 1 left a distance.  The first LOOK such
  * positions are scored: forward match length (the score counts at most FCAP bytes), backward extension into the
  * pending literals (at most BCAP bytes), offset cost (none for a recent offset), literals skipped.  The best one (the
- * earliest among equals) becomes a sequence with its full forward length. */
+ * earliest among equals) becomes a sequence with its full forward length.
+ * A prefixed unit (pfx > 0): every position here is a chunk position p (byte src[p], virtual position pfx + p); a recent offset is tried
+ * only where pfx + p >= offset, a backward extension stops at the anchor and at virtual position 0, a match source may straddle the
+ * prefix's end. */
 #define FCAP 8u
 #define BCAP 4u
 #define REPMIN 4u
-static U32 walkRange(Work *w, const BYTE *src, U32 n, U32 start, U32 end, U32 limit, const EParams *prm, ASeq *out)
+static U32 walkRange(Work *w, const BYTE *src, U32 n, U32 start, U32 end, U32 limit, const EParams *prm, U32 pfx, ASeq *out)
 {
+    const BYTE *const v = src - pfx;                           /* the unit's bytes by virtual position */
     U32 ip = start, anchor = start, nseq = 0, rep0 = 0, rep1 = 0;
     U32 const hashable = (n >= 8) ? n - 7 : 0;
     U32 const look = (U32)prm->look, repWin = (U32)prm->repWin, window = 8u * (U32)prm->windowGroups;
@@ -599,19 +611,19 @@ static U32 walkRange(Work *w, const BYTE *src, U32 n, U32 start, U32 end, U32 li
     while (ip < scanEnd) {
         int bestGain = 0, have = 0; U32 bestQ = 0, bestFwd = 0, bestBack = 0, bestOff = 0, q, seen = 0;
         U32 const wend = ((ip & ~7u) + window < scanEnd) ? (ip & ~7u) + window : scanEnd;   /* windowGroups aligned groups of 8 positions */
-        int const try0 = rep0 && ip >= rep0, try1 = rep1 && ip >= rep1;
+        int const try0 = rep0 && ip + pfx >= rep0, try1 = rep1 && ip + pfx >= rep1;
         for (q = ip; q < wend && seen < look; q++) {
             U32 off = 0, fwd, back = 0; int isRep = 0, gain;
             if (q < ip + repWin && q + 4 <= limit) {
-                if (try0 && rd32(src + q) == rd32(src + q - rep0)) { off = rep0; isRep = 1; }
-                else if (try1 && rd32(src + q) == rd32(src + q - rep1)) { off = rep1; isRep = 1; }
+                if (try0 && rd32(src + q) == rd32(v + pfx + q - rep0)) { off = rep0; isRep = 1; }
+                else if (try1 && rd32(src + q) == rd32(v + pfx + q - rep1)) { off = rep1; isRep = 1; }
             }
             if (!off) off = w->dist[q];
             if (!off) continue;
             seen++;
-            fwd = matchLen(src, q, q - off, limit);
+            fwd = matchLen(v, pfx + q, pfx + q - off, pfx + limit);
             if (fwd < (isRep ? REPMIN : MINMATCH)) continue;
-            while (back < BCAP && q - back > anchor && q - off - back > 0 && src[q - back - 1] == src[q - off - back - 1]) back++;
+            while (back < BCAP && q - back > anchor && pfx + q - off - back > 0 && v[pfx + q - back - 1] == v[pfx + q - off - back - 1]) back++;
             gain = (int)((fwd > FCAP ? FCAP : fwd) + back) * 4 - (isRep ? 0 : (int)highbit32(off + 1)) - 4 * ((int)(q - back) - (int)ip) - (int)(q - ip);
             if (!have || gain > bestGain) { have = 1; bestGain = gain; bestQ = q; bestFwd = fwd; bestBack = back; bestOff = off; }
         }
@@ -632,7 +644,7 @@ static U32 walkRange(Work *w, const BYTE *src, U32 n, U32 start, U32 end, U32 li
  * Every decision follows from the ranges' last match ends and last offsets alone, so the GPU decides all ranges at once
  * (k_lz_walk: a scan of the ends, one lane per range, a second scan for the joined lengths).
  * Leaves w->seqs / w->lits; returns the number of sequences. */
-static U32 parseBlock(Work *w, const BYTE *src, U32 unitN, U32 blockOff, U32 n, const EParams *prm, U32 *nlitOut)
+static U32 parseBlock(Work *w, const BYTE *src, U32 unitN, U32 blockOff, U32 n, const EParams *prm, U32 pfx, U32 *nlitOut)
 {
     U32 nseq = 0, nlit = 0;
     U32 const WS = 1u << prm->walkLog;
@@ -644,7 +656,7 @@ static U32 parseBlock(Work *w, const BYTE *src, U32 unitN, U32 blockOff, U32 n, 
         U32 const start = blockOff + (r << prm->walkLog);
         U32 const end = (start + WS < blockEnd) ? start + WS : blockEnd;
         U32 const limit = (end + CROSS_MAX < blockEnd) ? end + CROSS_MAX : blockEnd;
-        w->rangeN[r] = w->matchless ? 0 : walkRange(w, src, unitN, start, end, limit, prm, w->rangeSeq + ((start - blockOff) >> 2));
+        w->rangeN[r] = w->matchless ? 0 : walkRange(w, src, unitN, start, end, limit, prm, pfx, w->rangeSeq + ((start - blockOff) >> 2));
     }
     for (r = 0; r < nRanges; r++) {
         ASeq *const rs = w->rangeSeq + (r << (prm->walkLog - 2));
@@ -676,28 +688,29 @@ static U32 parseBlock(Work *w, const BYTE *src, U32 unitN, U32 blockOff, U32 n, 
  *  one block -> compressed block payload (without the 3-byte block header)
  *  returns payload size, or 0 if the block should be stored raw
  * ======================================================================= */
-/* src / unitN: the LZ unit (findCandidates has run on it); the block is src[blockOff .. blockOff + n) */
-static size_t encodeParsed(Work *w, BYTE *dst, size_t cap, U32 nseq, U32 nlit, int firstBlock);
-static size_t compressBlock(Work *w, BYTE *dst, size_t cap, const BYTE *src, U32 unitN, U32 blockOff, U32 n, const EParams *prm, int firstBlock)
+/* src / unitN: the LZ unit (findCandidates has run on it, with pfx bytes of prefix in front of src); the block is src[blockOff .. blockOff + n).
+ * firstRep: the recent offsets the chunk's first block starts from, NULL for the blocks after it */
+static size_t encodeParsed(Work *w, BYTE *dst, size_t cap, U32 nseq, U32 nlit, const U32 *firstRep);
+static size_t compressBlock(Work *w, BYTE *dst, size_t cap, const BYTE *src, U32 unitN, U32 blockOff, U32 n, const EParams *prm, U32 pfx, const U32 *firstRep)
 {
     U32 nseq, nlit = 0;
     if (n < 16) return 0;
-    nseq = parseBlock(w, src, unitN, blockOff, n, prm, &nlit);
-    return encodeParsed(w, dst, cap, nseq, nlit, firstBlock);
+    nseq = parseBlock(w, src, unitN, blockOff, n, prm, pfx, &nlit);
+    return encodeParsed(w, dst, cap, nseq, nlit, firstRep);
 }
 
 /* stages 3b-6 for one block whose sequences (w->seqs) and literals (w->lits) are in place */
 U32 g_lastNseq;   /* development aid (tools/lab): sequences of the last block encoded */
-static size_t encodeParsed(Work *w, BYTE *dst, size_t cap, U32 nseq, U32 nlit, int firstBlock)
+static size_t encodeParsed(Work *w, BYTE *dst, size_t cap, U32 nseq, U32 nlit, const U32 *firstRep)
 {
     g_lastNseq = nseq;
     {
         /* stage 3b: offsets -> offset field values through the 3-entry recent-offset list
-         * (inverse of ZStdDecompress.cs:1509-1530).  Blocks after the first start from an unknown
-         * history: sentinels that never equal a real offset (< 131072). */
+         * (inverse of ZStdDecompress.cs:1509-1530).  A chunk's first block starts from {1, 4, 8}, or from a dictionary's
+         * recent offsets; blocks after the first start from an unknown history: sentinels that never equal a real offset (< 131072). */
         U32 rep[3];
         U32 i;
-        if (firstBlock) { rep[0] = 1; rep[1] = 4; rep[2] = 8; } else { rep[0] = 0xFFFFFFF1u; rep[1] = 0xFFFFFFF2u; rep[2] = 0xFFFFFFF3u; }
+        if (firstRep) { rep[0] = firstRep[0]; rep[1] = firstRep[1]; rep[2] = firstRep[2]; } else { rep[0] = 0xFFFFFFF1u; rep[1] = 0xFFFFFFF2u; rep[2] = 0xFFFFFFF3u; }
         for (i = 0; i < nseq; i++) {
             U32 const off = w->seqs[i].offset, ll = w->seqs[i].litLength;
             U32 val;
@@ -812,34 +825,48 @@ size_t zso_compressBound(size_t srcSize)
     return srcSize + (srcSize >> 8) + ((srcSize < (128u << 10)) ? (((128u << 10) - srcSize) >> 11) : 0) + 3 * (srcSize / BLOCK_MAX + 1) + 18;
 }
 
-/* frame = magic + FHD + FCS (single segment) + blocks   (inverse of ZStdDecompress.cs:421-499, 2008-2091) */
-size_t zso_compress(void *dstv, size_t dstCapacity, const void *srcv, size_t srcSize, int level)
+/* frame = magic + FHD + dictionary ID (0, 1, 2 or 4 bytes) + FCS (single segment) + blocks   (inverse of ZStdDecompress.cs:421-499, 2008-2091).
+ * A dictionary gives the frame (zso_compress_usingDict, zso_batch.c): pre[0 .. pfx), the content's last pfx <= 64 KiB bytes, as the prefix of
+ * a chunk of <= 64 KiB; the ID for the header (none if 0); the first block's recent offsets.  Without one: pfx 0, ID 0, rep NULL ({1, 4, 8}). */
+static const U32 kRepStart[3] = { 1, 4, 8 };
+size_t zso_compressFrame(void *dstv, size_t dstCapacity, const void *srcv, size_t srcSize, int level,
+                         const void *pre, uint32_t pfxSize, uint32_t dictID, const uint32_t *rep)
 {
     BYTE *const dst = (BYTE *)dstv;
-    const BYTE *const src = (const BYTE *)srcv;
+    const BYTE *src = (const BYTE *)srcv;
     BYTE *op = dst;
     BYTE *const oend = dst + dstCapacity;
     EParams const prm = paramsForLevel(level);
+    U32 const didCode = (dictID != 0) + (dictID >= 256) + (dictID >= 65536), didSize = didCode == 3 ? 4 : didCode;
+    U32 const pfx = (srcSize <= BLOCK_MAX) ? pfxSize : 0;             /* a chunk of <= 64 KiB is one prefixed unit, a longer one is parsed as without */
     Work *w;
     size_t pos = 0;
     if (srcSize > 0xFFFFFFFFu) return ERR(ZSO_srcSize_wrong);
-    if (dstCapacity < 4 + 1 + 4 + 3) return ERR(ZSO_dstSize_tooSmall);
+    if (dstCapacity < 4 + 1 + didSize + 4 + 3) return ERR(ZSO_dstSize_tooSmall);
     wr32(op, 0xFD2FB528u); op += 4;
-    if (srcSize < 256) { *op++ = 0x20; *op++ = (BYTE)srcSize; }
-    else if (srcSize < 65536 + 256) { *op++ = 0x60; wr16(op, (U32)srcSize - 256); op += 2; }
-    else { *op++ = 0xA0; wr32(op, (U32)srcSize); op += 4; }
+    op[0] = (BYTE)((srcSize < 256 ? 0x20 : (srcSize < 65536 + 256 ? 0x60 : 0xA0)) | didCode);
+    { U32 k; for (k = 0; k < didSize; k++) op[1 + k] = (BYTE)(dictID >> (8 * k)); }
+    op += 1 + didSize;
+    if (srcSize < 256) { *op++ = (BYTE)srcSize; }
+    else if (srcSize < 65536 + 256) { wr16(op, (U32)srcSize - 256); op += 2; }
+    else { wr32(op, (U32)srcSize); op += 4; }
     {
         static __thread Work *tls_work;          /* one workspace per thread, kept for the thread's life */
         if (!tls_work) tls_work = (Work *)malloc(sizeof(Work));
         w = tls_work;
     }
     if (!w) return ERR(ZSO_memory_allocation);
+    if (pfx) {                                   /* the unit's bytes by virtual position: prefix, then the chunk */
+        memcpy(w->unitBytes, pre, pfx);
+        memcpy(w->unitBytes + pfx, src, srcSize);
+        src = w->unitBytes + pfx;
+    }
     do {
         U32 const n = (U32)((srcSize - pos < BLOCK_MAX) ? srcSize - pos : BLOCK_MAX);
         int const last = (pos + n == srcSize);
         size_t const unitPos = pos & ~(size_t)(UNIT_MAX - 1);             /* units are cut every 128 KiB of the chunk */
         U32 const unitN = (U32)((srcSize - unitPos < UNIT_MAX) ? srcSize - unitPos : UNIT_MAX);
-        if (pos == unitPos && n) findCandidates(w, src + unitPos, unitN, &prm);
+        if (pos == unitPos && n) findCandidates(w, src + unitPos, unitN, &prm, pfx);
         size_t csize = 0;
         U32 i, same = n > 0;
         if ((size_t)(oend - op) < 3 + 1) return ERR(ZSO_dstSize_tooSmall);
@@ -849,7 +876,8 @@ size_t zso_compress(void *dstv, size_t dstCapacity, const void *srcv, size_t src
         } else {
             /* the payload is built in scratch of n + 512 bytes; it is used iff it is smaller than n
              * (anything that would not fit the scratch is larger than n anyway) */
-            if (n) csize = compressBlock(w, w->tmp, n + 512, src + unitPos, unitN, (U32)(pos - unitPos), n, &prm, pos == 0);
+            if (n) csize = compressBlock(w, w->tmp, n + 512, src + unitPos, unitN, (U32)(pos - unitPos), n, &prm, pfx,
+                                         pos == 0 ? (rep ? rep : kRepStart) : NULL);
             if (csize && csize < n && (size_t)(oend - op) >= 3 + csize) { wr24(op, (U32)last + (2u << 1) + ((U32)csize << 3)); memcpy(op + 3, w->tmp, csize); op += 3 + csize; }
             else {                                                   /* raw block (ZStdDecompress.cs:662-667) */
                 if ((size_t)(oend - op) < 3 + (size_t)n) return ERR(ZSO_dstSize_tooSmall);
@@ -861,6 +889,11 @@ size_t zso_compress(void *dstv, size_t dstCapacity, const void *srcv, size_t src
     return (size_t)(op - dst);
 }
 
+size_t zso_compress(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level)
+{
+    return zso_compressFrame(dst, dstCapacity, src, srcSize, level, NULL, 0, 0, NULL);
+}
+
 /* ---- test hooks: intermediate results of stages 1 and 2 for one LZ unit (n <= 131072), so the HIP
  *      kernels can be checked stage by stage ---- */
 int zso_debugCandidates(uint32_t *distOut, const void *src, uint32_t n, int level)
@@ -868,7 +901,7 @@ int zso_debugCandidates(uint32_t *distOut, const void *src, uint32_t n, int leve
     EParams const prm = paramsForLevel(level);
     Work *w = (Work *)malloc(sizeof(Work));
     if (!w || n > UNIT_MAX) { free(w); return -1; }
-    findCandidates(w, (const BYTE *)src, n, &prm);
+    findCandidates(w, (const BYTE *)src, n, &prm, 0);
     memcpy(distOut, w->dist, n * sizeof(U32));
     free(w);
     return 0;
@@ -881,11 +914,11 @@ int zso_debugWalk(uint32_t *seqOut, uint32_t *nseqOut, const void *src, uint32_t
     Work *w = (Work *)malloc(sizeof(Work));
     U32 blockOff, b = 0, o = 0;
     if (!w || n > UNIT_MAX) { free(w); return -1; }
-    findCandidates(w, (const BYTE *)src, n, &prm);
+    findCandidates(w, (const BYTE *)src, n, &prm, 0);
     for (blockOff = 0; blockOff < n; blockOff += BLOCK_MAX, b++) {
         U32 const bn = (n - blockOff < BLOCK_MAX) ? n - blockOff : BLOCK_MAX;
         U32 nlit = 0, k, pos = 0;
-        U32 const ns = (bn < 16) ? 0 : parseBlock(w, (const BYTE *)src, n, blockOff, bn, &prm, &nlit);
+        U32 const ns = (bn < 16) ? 0 : parseBlock(w, (const BYTE *)src, n, blockOff, bn, &prm, 0, &nlit);
         for (k = 0; k < ns; k++) {
             pos += w->seqs[k].litLength;
             seqOut[o++] = pos; seqOut[o++] = w->seqs[k].matchLength; seqOut[o++] = w->seqs[k].offset;

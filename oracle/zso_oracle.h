@@ -36,10 +36,23 @@ void zso_statsGet(uint32_t *out32);   /* 32 counters, see zso_decoder.c */
 /* oracle E : scalar CPU statement of this repo's block encoder (the algorithm the HIP kernels run) */
 size_t zso_compressBound(size_t srcSize);
 size_t zso_compress(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level);
-/* multi-threaded drivers used only by bench.py's cpu_baseline leg: n independent chunks */
+/* the frame writer behind both: pre[0 .. pfx) the prefix of chunks of <= 64 KiB, dictID for the header (0: no field), rep the first
+ * block's recent offsets (NULL: {1, 4, 8}) */
+size_t zso_compressFrame(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level,
+                         const void *pre, uint32_t pfx, uint32_t dictID, const uint32_t *rep);
+/* with a dictionary (what zsmi_compress_usingDict does): raw-content or formatted; NULL / 0 bytes = zso_compress.
+ * A dictionary oracle D refuses gives dictionary_corrupted (30). */
+size_t zso_compress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level);
+/* oracle D's dictionary parse (insertDictionary): content offset, ID (0 for raw content), first block's recent offsets */
+size_t zso_dictParams(const void *dict, size_t dictSize, size_t *contentOff, uint32_t *dictID, uint32_t rep[3]);
+/* multi-threaded drivers used by bench.py's cpu_baseline leg and tests: n independent chunks */
 int zso_compressBatch(void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes,
                       const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                       uint32_t n, int level, int nThreads);
+/* the same with one dictionary for every chunk (zso_compress_usingDict) */
+int zso_compressBatch_usingDict(void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes,
+                                const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                uint32_t n, int level, int nThreads, const void *dict, size_t dictSize);
 int zso_decompressBatch(void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
                         const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                         uint32_t n, int nThreads);

@@ -33,6 +33,9 @@ def lib():
         L.zso_statsGet.argtypes = [vp]
         L.zso_compressBatch.restype = ctypes.c_int
         L.zso_compressBatch.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_int]
+        L.zso_compress_usingDict.restype = sz; L.zso_compress_usingDict.argtypes = [vp, sz, vp, sz, ctypes.c_char_p, sz, ctypes.c_int]
+        L.zso_compressBatch_usingDict.restype = ctypes.c_int
+        L.zso_compressBatch_usingDict.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz]
         L.zso_decompressBatch.restype = ctypes.c_int
         L.zso_decompressBatch.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_int]
         _lib = L
@@ -78,6 +81,29 @@ def compress(data: bytes, level=3) -> bytes:
     return out.raw[:r]
 
 
+def compress_using_dict(data: bytes, dictionary, level=3) -> bytes:
+    """oracle E with a dictionary (zso_compress_usingDict: what zsmi_compress_usingDict does); None / b"" = compress()"""
+    L = lib()
+    cap = L.zso_compressBound(len(data))
+    out = ctypes.create_string_buffer(cap)
+    r = L.zso_compress_usingDict(out, cap, data, len(data), dictionary, len(dictionary) if dictionary else 0, level)
+    if L.zso_isError(r):
+        raise OracleError(L.zso_errorCode(r))
+    return out.raw[:r]
+
+
+def dict_params(dictionary: bytes):
+    """oracle D's parse of a dictionary (zso_dictParams): (content offset, ID, recent offsets); OracleError(30) if D refuses it"""
+    L = lib()
+    L.zso_dictParams.restype = ctypes.c_size_t
+    L.zso_dictParams.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    off, did, reps = ctypes.c_size_t(), ctypes.c_uint32(), (ctypes.c_uint32 * 3)()
+    r = L.zso_dictParams(dictionary, len(dictionary), ctypes.byref(off), ctypes.byref(did), reps)
+    if L.zso_isError(r):
+        raise OracleError(L.zso_errorCode(r))
+    return off.value, did.value, tuple(reps)
+
+
 def decode_stats(frame: bytes, capacity: int):
     L = lib()
     L.zso_statsReset()
@@ -87,8 +113,8 @@ def decode_stats(frame: bytes, capacity: int):
     return out, st
 
 
-def compress_batch(src: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, level=3, threads=1):
-    """src uint8 array; returns (arena, dst_offsets, dst_sizes)"""
+def compress_batch(src: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, level=3, threads=1, dictionary=None):
+    """src uint8 array; returns (arena, dst_offsets, dst_sizes).  dictionary: one for every chunk (zso_compressBatch_usingDict)"""
     L = lib()
     n = len(sizes)
     bounds = np.array([L.zso_compressBound(int(s)) for s in np.unique(sizes)])
@@ -99,12 +125,21 @@ def compress_batch(src: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, leve
     arena = np.empty(int(caps.sum()), dtype=np.uint8)
     dsz = np.zeros(n, dtype=np.uint32)
     vp = ctypes.c_void_p
-    rc = L.zso_compressBatch(arena.ctypes.data_as(vp), doff.ctypes.data_as(vp), dsz.ctypes.data_as(vp),
-                             src.ctypes.data_as(vp), offsets.astype(np.uint64).ctypes.data_as(vp),
-                             sizes.astype(np.uint32).ctypes.data_as(vp), n, level, threads)
+    args = (arena.ctypes.data_as(vp), doff.ctypes.data_as(vp), dsz.ctypes.data_as(vp),
+            src.ctypes.data_as(vp), offsets.astype(np.uint64).ctypes.data_as(vp),
+            sizes.astype(np.uint32).ctypes.data_as(vp), n, level, threads)
+    if dictionary:
+        rc = L.zso_compressBatch_usingDict(*args, bytes(dictionary), len(dictionary))
+    else:
+        rc = L.zso_compressBatch(*args)
     if rc:
-        raise OracleError(-1)
+        raise OracleError(-rc if rc < 0 else -1)
     return arena, doff, dsz
+
+
+def compress_batch_using_dict(src: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, dictionary, level=3, threads=1):
+    """oracle E's batch form with one dictionary for every chunk; a dictionary oracle D refuses raises OracleError(30)"""
+    return compress_batch(src, offsets, sizes, level, threads, dictionary)
 
 
 # ---- optional yardstick: upstream libzstd (independent implementation, NOT the reference) ----

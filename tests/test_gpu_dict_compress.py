@@ -1,82 +1,24 @@
-"""Compression with a dictionary on the GPU (zsmi_compress_usingDict, zsmi_compressBatch{Host,Device}_usingDict): the frames must
-decode to their input with the same dictionary under oracle D, under the library's own decoder and under upstream libzstd; the
-dictionary must really be used (ratio, dictID, recent offsets); corrupted dictionaries are refused as oracle D refuses them; no
-dictionary gives exactly the frames of the calls without one.  Fixtures: tests/golden/libzstd_fixtures_dict.npz (an 8 KiB trained
-dictionary) and tests/golden/libzstd_fixtures_dict_compress.npz (64 KiB dictionaries trained per record class)."""
+"""Compression with a dictionary on the GPU (zsmi_compress_usingDict, zsmi_compressBatch{Host,Device}_usingDict).  Every frame must
+equal oracle E's (zso_compress_usingDict, the scalar statement of the prefixed units, the dictionary's recent offsets and its ID) byte
+for byte: at levels 1 - 4 and above, for raw, tiny, trained, re-offset and re-numbered dictionaries, chunk sizes around every limit
+and contents aimed at the prefix rules, across plan reuse, through device pointers and in sub-batches.  The frames must also decode to
+their input with the same dictionary under oracle D, under the library's own decoder and under upstream libzstd; the dictionary must
+really be used (ratio, dictID, recent offsets); corrupted dictionaries are refused as oracle D refuses them; no dictionary gives exactly
+the frames of the calls without one.  Dictionaries and chunks: tests/_dicts.py."""
 import ctypes, os, subprocess, sys
 import numpy as np
 import pytest
 import _oracle as O
 import _data as D
 import _corpus as C
+import _dicts as X
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR = 0xFFFFFF88
-FIX = np.load(os.path.join(D.GOLDEN, "libzstd_fixtures_dict.npz"))
-FIXC = np.load(os.path.join(D.GOLDEN, "libzstd_fixtures_dict_compress.npz"))
-TRAINED8K = FIX["trained_small_l3_dict"].tobytes()
-RECORD_CLASSES = ["json_records", "xml_records", "zipf", "csv_records", "binary_table"]
-
-
-def trained(cls):
-    return FIXC["trained_" + cls].tobytes()
-
-
-def content_of(dic):
-    """the content part of a ZDICT-trained dictionary: what follows its recent offsets, which ZDICT leaves at {1, 4, 8}
-    (libzstd's ZDICT_getDictHeaderSize agrees where it is exported)"""
-    at = dic.find(bytes([1, 0, 0, 0, 4, 0, 0, 0, 8, 0, 0, 0]), 8)
-    assert at > 8
-    return dic[at + 12:]
-
-
-_data_cache = {}
-
-
-def class_data(cls, n=1 << 19):
-    if (cls, n) not in _data_cache:
-        if cls == "zipf":
-            b = D.zipf_log(n, seed_lo=0x77).tobytes()
-        elif cls == "repetitive":
-            b = C.repetitive(n)
-        else:
-            b = getattr(C, cls)(n)
-        _data_cache[(cls, n)] = b[:n]
-    return _data_cache[(cls, n)]
-
-
-# ---- upstream libzstd with dictionaries (optional yardstick) ----
-_Z = None
-
-
-def _zstd():
-    global _Z
-    if _Z is None:
-        Z = O.libzstd()
-        if Z:
-            sz, vp, cp = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_char_p
-            Z.ZSTD_createCCtx.restype = vp; Z.ZSTD_createDCtx.restype = vp
-            Z.ZSTD_compress_usingDict.restype = sz; Z.ZSTD_compress_usingDict.argtypes = [vp, vp, sz, cp, sz, cp, sz, ctypes.c_int]
-            Z.ZSTD_decompress_usingDict.restype = sz; Z.ZSTD_decompress_usingDict.argtypes = [vp, vp, sz, cp, sz, cp, sz]
-            Z.cctx = Z.ZSTD_createCCtx(); Z.dctx = Z.ZSTD_createDCtx()
-        _Z = Z or False
-    return _Z or None
-
-
-def zstd_compress_dict(data, dic, level):
-    Z = _zstd()
-    cap = Z.ZSTD_compressBound(len(data)); out = ctypes.create_string_buffer(cap)
-    r = Z.ZSTD_compress_usingDict(Z.cctx, out, cap, data, len(data), dic, len(dic), level)
-    assert not Z.ZSTD_isError(r)
-    return out.raw[:r]
-
-
-def zstd_decompress_dict(frame, cap, dic):
-    Z = _zstd()
-    out = ctypes.create_string_buffer(max(cap, 1))
-    r = Z.ZSTD_decompress_usingDict(Z.dctx, out, cap, frame, len(frame), dic, len(dic))
-    return None if Z.ZSTD_isError(r) else out.raw[:r]
+FIX, FIXC, TRAINED8K, RECORD_CLASSES = X.FIX, X.FIXC, X.TRAINED8K, X.RECORD_CLASSES
+trained, content_of, class_data, with_reps, bad_dictionaries = X.trained, X.content_of, X.class_data, X.with_reps, X.bad_dictionaries
+_zstd, zstd_compress_dict, zstd_decompress_dict = X.zstd, X.zstd_compress_dict, X.zstd_decompress_dict
 
 
 @pytest.fixture(scope="module")
@@ -138,6 +80,54 @@ def test_round_trip(codec, level):
         assert_round_trip(codec, frames, chunks, dic)
 
 
+# ------------------------------------------------------------------ byte for byte: oracle E
+def assert_matches_oracle(codec, chunks, level, dic, what):
+    """the HIP frames of one batch call (BatchCodec.compress_host) against oracle E's batch form, frame by frame"""
+    frames = compress_many(codec, chunks, level, dic)
+    expect = X.oracle_frames(chunks, level, dic)
+    for i, (f, e) in enumerate(zip(frames, expect)):
+        assert f == e, (what, level, i, len(chunks[i]), len(f), len(e), X.first_difference(f, e))
+    return frames
+
+
+@pytest.mark.parametrize("level", [1, 2, 3, 4, 7])
+def test_frames_match_oracle(codec, level):
+    """levels 1 - 4 and 7 (every row of the LZ shape table and the level-to-class mapping) x every dictionary kind
+    (tests/_dicts.py: raw content of 1 - 100 000 bytes, the trained ones, other recent offsets) x chunk sizes 0 .. 200 KiB around every
+    limit, every corpus class and the prefix-rule contents; the frames also decode under oracle D"""
+    for name, dic in X.identity_dictionaries().items():
+        chunks = X.prefix_chunks(dic)
+        frames = assert_matches_oracle(codec, chunks, level, dic, name)
+        for i, (f, c) in enumerate(zip(frames, chunks)):
+            assert O.decompress_using_dict(f, len(c), dic) == c, (name, i)
+
+
+def test_dictionary_ids_match_oracle(codec):
+    """the 8 KiB trained dictionary with IDs 0, 1, 255, 256, 65535, 65536 and 0xFFFFFFFF: every header field size"""
+    chunks = X.prefix_chunks(X.TRAINED8K, (0, 1, 17, 255, 4096, 65535, 65536, 65537, 65791, 65792, 131073))
+    for did, dic in X.id_dictionaries().items():
+        for level in (1, 3):
+            frames = assert_matches_oracle(codec, chunks, level, dic, did)
+            size = 0 if did == 0 else (1 if did < 256 else (2 if did < 65536 else 4))
+            assert all(f[4] & 3 == (3 if size == 4 else size) and int.from_bytes(f[5:5 + size], "little") == did for f in frames)
+
+
+def test_plan_reuse_matches_oracle(codec):
+    """one chunk layout called again and again on one context: no dictionary, dictionary A, dictionary B with another prefix length,
+    no dictionary again, A again - buildPlan's cached plan and its dictionary unit list, the table images rebuilt every call"""
+    a, b = X.identity_dictionaries()["trained64k_zipf"], X.identity_dictionaries()["raw6000"]
+    chunks = X.prefix_chunks(X.identity_dictionaries()["raw65536"])
+    for level in (3, 1):
+        for name, dic in (("none", b""), ("A", a), ("B", b), ("none", b""), ("A", a)):
+            if dic:
+                assert_matches_oracle(codec, chunks, level, dic, name)
+            else:
+                frames = compress_many(codec, chunks, level)
+                src, offs, sizes = X.batch(chunks)
+                ea, eo, es = O.compress_batch(src, offs, sizes, level, 8)
+                assert frames == [ea[int(eo[i]):int(eo[i]) + int(es[i])].tobytes() for i in range(len(chunks))], (name, level)
+
+
 # ------------------------------------------------------------------ the dictionary is used
 def test_trained_dictionary_shrinks_small_chunks(codec):
     for cls in ("json_records", "xml_records", "zipf"):
@@ -180,12 +170,6 @@ def test_frames_need_their_dictionary(codec):
     assert bad > 0
 
 
-def with_reps(dic, reps):
-    content = content_of(dic)
-    at = len(dic) - len(content) - 12
-    return dic[:at] + b"".join(r.to_bytes(4, "little") for r in reps) + content
-
-
 def test_first_block_starts_from_the_dictionarys_recent_offsets(codec):
     """a dictionary whose recent offsets are not {1, 4, 8}: chunks whose first sequences repeat at offsets 1, 4 and 8 decode right only if
     the encoder's repcodes start from the dictionary's offsets"""
@@ -207,13 +191,6 @@ def test_first_block_starts_from_the_dictionarys_recent_offsets(codec):
 
 
 # ------------------------------------------------------------------ errors
-def bad_dictionaries():
-    dic = TRAINED8K
-    rep0 = with_reps(dic, (0, 4, 8))
-    past = with_reps(dic, (1, len(content_of(dic)), 8))
-    return [dic[:9], dic[:40], dic[:120], rep0, past]
-
-
 def test_corrupted_dictionaries_are_refused(codec):
     L = codec.L
     data = class_data("json_records")[:4096]
@@ -251,12 +228,14 @@ def test_no_dictionary_is_the_plain_call(codec):
             r = L.zsmi_compress_usingDict(out, len(out), c, len(c), None, 0, level)
             assert out.raw[:r] == f
             assert ZstdCompressor(level, dictionary=b"").compress(c) == f
+        for c in chunks:                                                  # oracle E: the same holds for the scalar statement
+            assert O.compress_using_dict(c, None, level) == O.compress_using_dict(c, b"", level) == O.compress(c, level)
     dic = trained("json_records")
     c = class_data("json_records")[:3000]
     out = ctypes.create_string_buffer(L.zsmi_compressBound(len(c)))
     r = L.zsmi_compress_usingDict(out, len(out), c, len(c), dic, len(dic), 3)
     assert not L.zsmi_isError(r) and ZstdCompressor(3, dictionary=dic).compress(c) == out.raw[:r]
-    assert out.raw[:r] == compress_many(codec, [c], 3, dic)[0]
+    assert out.raw[:r] == compress_many(codec, [c], 3, dic)[0] == O.compress_using_dict(c, dic, 3)
     assert O.decompress_using_dict(out.raw[:r], len(c), dic) == c
 
 
@@ -303,9 +282,11 @@ for name, dic in (("trained", FIXC["trained_json_records"].tobytes()), ("raw", d
             inside[int(do[i]):int(do[i]) + int(sz[i])] = True
         bad = np.flatnonzero(~inside & (host != CANARY))
         assert bad.size == 0, (name, level, "written outside the frames", bad[:10].tolist())
+        ea, eo, es = O.compress_batch_using_dict(src_np, so, sizes, dic, level, 8)
         for i in range(len(sizes)):
             f = host[int(do[i]):int(do[i]) + int(sz[i])].tobytes(); c = src_np[int(so[i]):int(so[i]) + int(sizes[i])].tobytes()
             assert O.decompress_using_dict(f, len(c), dic) == c, (name, level, i)
+            assert f == ea[int(eo[i]):int(eo[i]) + int(es[i])].tobytes(), ("oracle E", name, level, i)
         # the host form gives the same frames
         arena, hdo, hsz = bc.compress_host(src_np, so, sizes, level, dic)
         assert (hsz == sz).all() and all(arena[int(hdo[i]):int(hdo[i]) + int(hsz[i])].tobytes() == host[int(do[i]):int(do[i]) + int(sz[i])].tobytes() for i in range(len(sizes)))
@@ -331,7 +312,7 @@ print("CHILD-OK")
 
 def test_device_calls_stay_in_bounds_and_refuse_bad_dictionaries():
     """zsmi_compressBatchDevice_usingDict: canary-filled output, ragged chunks around the 64 KiB limit; every frame within
-    zsmi_compressBound and nothing written outside the frames; frames equal to the host form's and decode under oracle D; a NULL /
+    zsmi_compressBound and nothing written outside the frames; frames equal to the host form's and oracle E's and decode under oracle D; a NULL /
     0-byte dictionary is the plain call; corrupted dictionaries return 30"""
     extra = ",".join(d.hex() for d in bad_dictionaries()[3:])
     r = subprocess.run([sys.executable, "-c", _DEVICE_CHILD, ROOT, extra], capture_output=True, text=True, timeout=600)
@@ -357,9 +338,11 @@ for level in (3, 1):
     arena, do, dsz = bc.compress_host(data, offs, sizes, level, dic)
     assert (dsz < ERR).all()
     frames = [arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes() for i in range(len(sizes))]
+    ea, eo, es = O.compress_batch_using_dict(data, offs, sizes, dic, level, 8)
     for i, f in enumerate(frames):
         c = data[int(offs[i]):int(offs[i]) + int(sizes[i])].tobytes()
         assert O.decompress_using_dict(f, len(c), dic) == c, (level, i)
+        assert f == ea[int(eo[i]):int(eo[i]) + int(es[i])].tobytes(), ("oracle E", level, i)
     fo = np.zeros(len(sizes), dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
     out, oo, osz = bc.decompress_host(np.frombuffer(b"".join(frames), dtype=np.uint8), fo, dsz, np.maximum(sizes, 1), dic)
     assert (osz == sizes).all()
@@ -369,7 +352,7 @@ print("CHILD-OK")
 
 def test_sub_batches_with_a_dictionary():
     """ZSMI_BLOCKS_IN_FLIGHT=64 in a child process: a mixed batch (prefixed units, tails of long chunks, big units) is cut in many
-    sub-batches; every frame round-trips"""
+    sub-batches; every frame equals oracle E's and round-trips"""
     env = dict(os.environ, ZSMI_BLOCKS_IN_FLIGHT="64")
     r = subprocess.run([sys.executable, "-c", _SUB_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "CHILD-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])

@@ -1,6 +1,7 @@
 """The oracle (restated decoder incl. both Huffman decoders, scalar encoder) under AddressSanitizer + UBSan on the CPU
 (GPU sanitizers are not available on this pool): mixed inputs and corpus classes at two levels, every frame decoded back,
-plus six randomly damaged copies of each frame through the decoder's error paths."""
+plus six randomly damaged copies of each frame through the decoder's error paths; then compression with raw, tiny, formatted and
+> 64 KiB dictionaries, each frame decoded back with its dictionary and three damaged copies through the decoder."""
 import os, subprocess, sys
 import pytest
 

@@ -8,8 +8,8 @@ int main(int argc, char **argv)
     Work *w = malloc(sizeof(Work)); EParams prm = paramsForLevel(3);
     U32 hist[64] = {0}; double sum = 0; U32 cnt = 0, worst = 0, nover = 0;
     for (size_t pos = 0; pos + 65536 <= n && pos < (8u << 20); pos += 65536) {
-        findCandidates(w, buf + pos, 65536, &prm);
-        compressBlock(w, w->tmp, 65536 + 512, buf + pos, 65536, 0, 65536, &prm, 1);
+        findCandidates(w, buf + pos, 65536, &prm, 0);
+        compressBlock(w, w->tmp, 65536 + 512, buf + pos, 65536, 0, 65536, &prm, 0, kRepStart);
         /* recover nseq: count until seqs matchLength 0? use codes arrays: recompute nseq by re-parsing is heavy; use a global */
         extern U32 g_lastNseq; U32 nseq = g_lastNseq;
         for (int t = 0; t < 3; t++) {

@@ -89,7 +89,7 @@ static void simUnit(Work *w, const BYTE *src, U32 n, const EParams *prm)
     U32 const WPW = 64u / (U32)LPW;                       /* walkers per wavefront */
     U32 const look = (U32)prm->look, repWin = (U32)prm->repWin, CPL = look / (U32)LPW, RPL = repWin / (U32)LPW;
     U32 const hashable = (n >= 8) ? n - 7 : 0;
-    findCandidates(w, src, n, prm);
+    findCandidates(w, src, n, prm, 0);
     for (U32 r0 = 0; r0 < nRanges; r0 += WPW) {
         Walker wk[32];
         U32 nw = (nRanges - r0 < WPW) ? nRanges - r0 : WPW, k;

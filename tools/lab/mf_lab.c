@@ -52,7 +52,7 @@ static void labCandidates(Work *w, const BYTE *src, U32 n, const EParams *prm)
     U32 p, base;
     if (!distS) { distS = malloc(4 * UNIT_MAX); distL = malloc(4 * UNIT_MAX); tabS = malloc(4u << LBITS); tabL = malloc(4u << LBITS); }
     memset(distS, 0, 4 * n); memset(distL, 0, 4 * n);
-    if (!P.ideal) { findCandidates(w, src, n, prm); memcpy(distS, w->dist, 4 * n); }
+    if (!P.ideal) { findCandidates(w, src, n, prm, 0); memcpy(distS, w->dist, 4 * n); }
     if (n < 16) return;
     memset(tabS, 0xFF, 4u << LBITS); memset(tabL, 0xFF, 4u << LBITS);
     for (base = 0; base + 8 <= n; base += 64) {
@@ -162,7 +162,7 @@ static size_t labBlock(Work *w, BYTE *dst, size_t cap, const BYTE *src, U32 unit
         }
     }
     memcpy(w->lits + nlit, src + reach, blockEnd - reach); nlit += blockEnd - reach;
-    return encodeParsed(w, dst, cap, nseq, nlit, firstBlock);
+    return encodeParsed(w, dst, cap, nseq, nlit, firstBlock ? kRepStart : NULL);
 }
 
 size_t lab_compress(void *dstv, size_t dstCapacity, const void *srcv, size_t srcSize, int level)

@@ -201,7 +201,7 @@ static size_t wlBlock(Work *w, BYTE *dst, size_t cap, const BYTE *src, U32 unitN
         memcpy(w->lits + nlit, src + pos, blockEnd - pos); nlit += blockEnd - pos;
     }
     S.kept += nseq;
-    return encodeParsed(w, dst, cap, nseq, nlit, firstBlock);
+    return encodeParsed(w, dst, cap, nseq, nlit, firstBlock ? kRepStart : NULL);
 }
 
 size_t wl_compress(void *dstv, size_t dstCapacity, const void *srcv, size_t srcSize, int level)
