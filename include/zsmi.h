@@ -33,7 +33,9 @@ enum {
     ZSMI_error_tableLog_tooLarge = 44, ZSMI_error_maxSymbolValue_tooLarge = 46,
     ZSMI_error_maxSymbolValue_tooSmall = 48, ZSMI_error_stage_wrong = 60, ZSMI_error_init_missing = 62,
     ZSMI_error_memory_allocation = 64, ZSMI_error_workSpace_tooSmall = 66,
-    ZSMI_error_dstSize_tooSmall = 70, ZSMI_error_srcSize_wrong = 72, ZSMI_error_maxCode = 120
+    ZSMI_error_dstSize_tooSmall = 70, ZSMI_error_srcSize_wrong = 72,
+    ZSMI_error_frameIndex_tooLarge = 100, ZSMI_error_seekableIO = 102,       /* ZStdErrors.cs:87-88: the seekable format's codes */
+    ZSMI_error_maxCode = 120
 };
 
 /* replaces: internal ZStdErrors.IsError (ZStdErrors.cs:95-98) */
@@ -136,6 +138,45 @@ int zsmi_decompressBatchHost_usingDict(zsmi_ctx *ctx, const void *src, const uin
  * dPackedOffsets[n+1] (device, uint64) receives the running offsets.  Asynchronous. */
 int zsmi_packFramesDevice(zsmi_ctx *ctx, const void *dFrames, const uint64_t *dstOffsets, const uint32_t *dSizes,
                           uint32_t n, void *dPacked, uint64_t *dPackedOffsets);
+
+/* ------------------------------------------------------------------------------------------
+ * Seekable archives (zstd's seekable format): independent frames, then a seek table in a skippable frame
+ *   Skippable magic 0x184D2A5E | Frame_Size | n entries {Compressed_Size, Decompressed_Size[, Checksum]} | n | descriptor | 0x8F92EAB1
+ * Any zstd decoder reads an archive as concatenated frames (zsmi_decompress included).  Frame i holds src[i F, min((i + 1) F, srcSize)),
+ * compressed exactly as chunk i of zsmi_compressBatchDevice at the same level.  frameSize F: 0 = 64 KiB, else 1 .. 1 GiB
+ * (parameter_outOfBound otherwise); more than 0x8000000 frames: frameIndex_tooLarge.  checksumFlag: each entry carries the low 32 bits of
+ * XXH64 (seed 0) of the frame's content.  An empty input is an archive of 0 frames (the 17-byte table alone).
+ * Reading checks the table before anything runs on the device: prefix_unknown (a magic is wrong), corruption_detected (reserved descriptor
+ * bits, Frame_Size against n, compressed sizes that do not add up to the bytes in front of the table, a Compressed_Size of 0, a
+ * Decompressed_Size over 1 GiB), frameIndex_tooLarge (more than 0x8000000 frames), parameter_outOfBound (offset past the content).
+ * Only the frames that overlap the range are decoded; the first failing one in content order decides the result: its decoder error,
+ * corruption_detected when its size is not its entry's, checksum_wrong when its checksum is not.
+ * ------------------------------------------------------------------------------------------ */
+/* room zsmi_compressSeekable* need: the frames' compress bounds plus the table (an error code for parameters they refuse) */
+size_t zsmi_seekableBound(unsigned long long srcSize, uint32_t frameSize, int checksumFlag);
+/* one-shot, host buffers (inputs over 4 GiB too).  Returns the archive's size or an error code */
+size_t zsmi_compressSeekable(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level, uint32_t frameSize, int checksumFlag);
+/* Device buffers, asynchronous on the context's stream.  Parameters and dstCapacity >= zsmi_seekableBound(...) are checked on the host first;
+ * on failure nothing is queued and the code is returned.  *dArchiveSize (device memory) receives the archive's size, or (uint64_t)-code
+ * if a frame failed.  The frames are compressed into context staging of about one bound of the input, then packed into dDst.
+ * Writes only inside [dDst, dDst + dstCapacity). */
+int zsmi_compressSeekableDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, void *dDst, uint64_t dstCapacity,
+                                uint64_t *dArchiveSize, int level, uint32_t frameSize, int checksumFlag);
+/* content bytes [offset, offset + dstCapacity), clipped at the content's end (offset == content size reads 0 bytes).  Only the compressed
+ * bytes of the frames that overlap the range go to the device.  Returns the bytes written or an error code. */
+size_t zsmi_decompressSeekable(void *dst, size_t dstCapacity, const void *src, size_t srcSize, unsigned long long offset);
+/* Device buffers.  Reads back the table (the call waits for the context's stream), checks it, then queues the decode of the frames that
+ * overlap [offset, offset + length) (clipped at the content's end) and returns; *written (host) receives the bytes the range holds,
+ * *dStatus (device) 0 or the first failing frame's code.  Frames wholly inside the range decode straight into dDst, a partial first or
+ * last frame into context scratch.  Writes only inside [dDst, dDst + *written). */
+int zsmi_decompressSeekableDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, uint64_t offset, uint64_t length,
+                                  void *dDst, uint64_t *written, uint32_t *dStatus);
+/* host only: the table at the archive's end (errors as above) */
+size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
+size_t zsmi_seekableContentSize(const void *src, size_t srcSize);
+/* frame index's place: compressed offset and size, content offset and size.  Returns 0 or an error code value */
+int zsmi_seekableFrameInfo(const void *src, size_t srcSize, uint32_t index, uint64_t *cOffset, uint64_t *dOffset,
+                           uint32_t *cSize, uint32_t *dSize);
 
 /* ---- measurement hooks (bench.py): HIP-event timing of the kernels launched on the context's stream by the
  *      last batch call; one entry per kernel name, seconds are summed over launches.  Returns entries written.

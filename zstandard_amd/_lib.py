@@ -102,6 +102,15 @@ def lib():
     L.zsmi_getKernelTimes.restype = i32; L.zsmi_getKernelTimes.argtypes = [vp, ctypes.POINTER(KernelTime), i32]
     L.zsmi_decodeScratchBytes.restype = sz; L.zsmi_decodeScratchBytes.argtypes = [vp]
     L.zsmi_shutdown.restype = None; L.zsmi_shutdown.argtypes = []
+    u64, ull, pu64 = ctypes.c_uint64, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_uint64)
+    L.zsmi_seekableBound.restype = sz; L.zsmi_seekableBound.argtypes = [ull, u32, i32]
+    L.zsmi_compressSeekable.restype = sz; L.zsmi_compressSeekable.argtypes = [vp, sz, vp, sz, i32, u32, i32]
+    L.zsmi_compressSeekableDevice.restype = i32; L.zsmi_compressSeekableDevice.argtypes = [vp, vp, u64, vp, u64, vp, i32, u32, i32]
+    L.zsmi_decompressSeekable.restype = sz; L.zsmi_decompressSeekable.argtypes = [vp, sz, vp, sz, ull]
+    L.zsmi_decompressSeekableDevice.restype = i32; L.zsmi_decompressSeekableDevice.argtypes = [vp, vp, u64, u64, u64, vp, pu64, vp]
+    L.zsmi_seekableNumFrames.restype = sz; L.zsmi_seekableNumFrames.argtypes = [vp, sz]
+    L.zsmi_seekableContentSize.restype = sz; L.zsmi_seekableContentSize.argtypes = [vp, sz]
+    L.zsmi_seekableFrameInfo.restype = i32; L.zsmi_seekableFrameInfo.argtypes = [vp, sz, u32, pu64, pu64, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     if DEBUG or hasattr(L, "zsmi_dbg_copyScratch"):            # (a variant build named by ZSMI_LIB_FILE may carry the hooks too)
         L.zsmi_dbg_copyScratch.restype = i32; L.zsmi_dbg_copyScratch.argtypes = [vp, i32, vp, sz]
     _lib = L
@@ -113,4 +122,6 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_compressBatchDevice", "zsmi_decompressBatchDevice", "zsmi_compressBatchHost", "zsmi_decompressBatchHost",
            "zsmi_decompress_usingDict", "zsmi_decompressBatchDevice_usingDict", "zsmi_decompressBatchHost_usingDict",
            "zsmi_compress_usingDict", "zsmi_compressBatchDevice_usingDict", "zsmi_compressBatchHost_usingDict",
-           "zsmi_packFramesDevice", "zsmi_enableKernelTiming", "zsmi_getKernelTimes", "zsmi_versionString", "zsmi_decodeScratchBytes", "zsmi_shutdown"]
+           "zsmi_packFramesDevice", "zsmi_enableKernelTiming", "zsmi_getKernelTimes", "zsmi_versionString", "zsmi_decodeScratchBytes", "zsmi_shutdown",
+           "zsmi_seekableBound", "zsmi_compressSeekable", "zsmi_compressSeekableDevice", "zsmi_decompressSeekable", "zsmi_decompressSeekableDevice",
+           "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo"]

@@ -5,6 +5,8 @@
   ZstdDecompressor    Java class java/src/main/java/com/epam/deltix/zstd/ZstdDecompressor.java:18-34: raises RuntimeError
                       like Util.java:32-40.
   ZstdCompressor      the compressor the reference lacks (north_star), same calling conventions.
+  SeekableArchive     random access into a seekable archive (zstd's seekable format: independent frames + a seek table), made by
+                      ZstdCompressor.compress_seekable or BatchCodec.compress_seekable_device.
   BatchCodec          the batch hot path on device memory (torch tensors are only a handle to device memory here).
 
 Everything computes on the GPU through libzsmi.so; nothing here falls back to a CPU codec.
@@ -14,6 +16,17 @@ import numpy as np
 from . import _lib
 
 ERROR_MAX = 0xFFFFFF88          # ZStdErrors.cs:95-98 : IsError(c) = c > (uint)-120
+
+
+def _raise_if_error(L, r):
+    """r: a size_t result; an error code raises RuntimeError with its name"""
+    if L.zsmi_isError(r):
+        raise RuntimeError(L.zsmi_getErrorName(r).decode())
+    return int(r)
+
+
+def _error_name(L, code: int) -> str:
+    return L.zsmi_getErrorName((1 << 64) - code).decode()
 
 
 def _buf(b):
@@ -100,6 +113,50 @@ class ZstdCompressor:
             raise RuntimeError(L.zsmi_getErrorName(r).decode())
         return out.raw[:r]
 
+    def compress_seekable(self, src, frame_size=0, checksum=True) -> bytes:
+        """a seekable archive: frame i holds src[i * frame_size, (i + 1) * frame_size) (frame_size 0: 64 KiB), each compressed as
+        compress() would compress that slice, then the seek table (checksum: each entry carries the low 32 bits of the slice's XXH64).
+        Any zstd decoder reads it as concatenated frames; SeekableArchive reads ranges of it."""
+        L = _lib.lib()
+        if self.dictionary:
+            raise RuntimeError(_error_name(L, 40))                     # parameter_unsupported: no dictionaries in seekable archives
+        s, sn = _buf(src)
+        cap = _raise_if_error(L, L.zsmi_seekableBound(sn, frame_size, int(bool(checksum))))
+        out = ctypes.create_string_buffer(cap)
+        r = _raise_if_error(L, L.zsmi_compressSeekable(out, cap, s, sn, self.level, frame_size, int(bool(checksum))))
+        return out.raw[:r]
+
+
+class SeekableArchive:
+    """A seekable archive in host memory.  The table is checked when the object is made (RuntimeError with the error's name, as every
+    read); read() decodes on the GPU only the frames that overlap the range."""
+
+    def __init__(self, archive):
+        self.L = _lib.lib()
+        self.archive = bytes(archive)
+        self.num_frames = _raise_if_error(self.L, self.L.zsmi_seekableNumFrames(self.archive, len(self.archive)))
+        self.content_size = _raise_if_error(self.L, self.L.zsmi_seekableContentSize(self.archive, len(self.archive)))
+
+    def frame_info(self, index):
+        """(compressed offset, content offset, compressed size, content size) of frame `index`"""
+        co, do, cs, ds = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+        if index < 0:
+            index += self.num_frames
+        index = index if 0 <= index <= 0xFFFFFFFF else 0xFFFFFFFF          # (out of range either way: frameIndex_tooLarge)
+        rc = self.L.zsmi_seekableFrameInfo(self.archive, len(self.archive), index, ctypes.byref(co),
+                                           ctypes.byref(do), ctypes.byref(cs), ctypes.byref(ds))
+        if rc:
+            raise RuntimeError(_error_name(self.L, rc))
+        return co.value, do.value, cs.value, ds.value
+
+    def read(self, offset=0, length=None) -> bytes:
+        """content bytes [offset, offset + length), clipped at the content's end (length None: to the end)"""
+        if length is None:
+            length = max(self.content_size - offset, 0)
+        out = ctypes.create_string_buffer(max(length, 1))
+        r = _raise_if_error(self.L, self.L.zsmi_decompressSeekable(out, length, self.archive, len(self.archive), offset))
+        return out.raw[:r]
+
 
 class BatchCodec:
     """n independent chunks <-> n frames on one GPU.  Arrays of offsets/sizes live on the host (numpy);
@@ -162,6 +219,28 @@ class BatchCodec:
                                           ctypes.c_void_p(d_packed_ptr), ctypes.c_void_p(d_packed_offsets_ptr))
         if rc:
             raise RuntimeError(f"zsmi_packFramesDevice: error {rc}")
+
+    def seekable_bound(self, src_size, frame_size=0, checksum=True) -> int:
+        return _raise_if_error(self.L, self.L.zsmi_seekableBound(src_size, frame_size, int(bool(checksum))))
+
+    def compress_seekable_device(self, d_src_ptr, src_size, d_dst_ptr, dst_capacity, d_archive_size_ptr, level=3, frame_size=0, checksum=True):
+        """a seekable archive of d_src[0, src_size) at d_dst (asynchronous); *d_archive_size_ptr (device uint64) receives its size, or
+        (uint64)-code if a frame failed.  dst_capacity must be at least seekable_bound(src_size, frame_size, checksum)."""
+        rc = self.L.zsmi_compressSeekableDevice(self.ctx, ctypes.c_void_p(d_src_ptr), src_size, ctypes.c_void_p(d_dst_ptr), dst_capacity,
+                                                ctypes.c_void_p(d_archive_size_ptr), level, frame_size, int(bool(checksum)))
+        if rc:
+            raise RuntimeError(f"zsmi_compressSeekableDevice: {_error_name(self.L, rc)}")
+
+    def decompress_seekable_device(self, d_src_ptr, src_size, offset, length, d_dst_ptr, d_status_ptr) -> int:
+        """content bytes [offset, offset + length) of the archive at d_src into d_dst; returns how many (the range clipped at the content's
+        end).  The table is read and checked at once (RuntimeError); the frames decode asynchronously, *d_status_ptr (device uint32)
+        receives 0 or the first failing frame's code."""
+        written = ctypes.c_uint64(0)
+        rc = self.L.zsmi_decompressSeekableDevice(self.ctx, ctypes.c_void_p(d_src_ptr), src_size, offset, length, ctypes.c_void_p(d_dst_ptr),
+                                                  ctypes.byref(written), ctypes.c_void_p(d_status_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_decompressSeekableDevice: {_error_name(self.L, rc)}")
+        return written.value
 
     def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b""):
         """returns (arena uint8, dst_offsets uint64, dst_sizes uint32).  dictionary: one for every chunk (raw content or a formatted

@@ -754,6 +754,9 @@ __device__ static uint64_t xxh64(const uint8_t *p, uint64_t len)
 // The same by FOUR lanes (a quad of the wavefront, r = lane & 3): the stripe loop is four independent accumulators, lane r runs the r-th (the 8 bytes at 8 r of
 // every 32-byte stripe), the quad's first lane merges them and finishes the tail.  Every lane of the quad must call; the result is valid in its first lane.
 // (k_dec_checksum hashed an item's whole output on one lane: 1 MiB frames are 32768 dependent rounds there.)
+// AHEAD > 1: the stripe loop loads AHEAD stripes before it folds them in (AHEAD loads a lane in flight instead of one dependent load a stripe:
+// k_seek_hash, whose quads are few and long).  AHEAD = 1 is the plain loop the decode kernels use.
+template <int AHEAD = 1>
 __device__ __forceinline__ uint64_t xxh64_quad(const uint8_t *p, uint64_t len)
 {
     const uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL, P3 = 1609587929392839161ULL, P4 = 9650029242287828579ULL, P5 = 2870177450012600261ULL;
@@ -764,7 +767,18 @@ __device__ __forceinline__ uint64_t xxh64_quad(const uint8_t *p, uint64_t len)
     if (stripes) {
         uint64_t v = r == 0 ? P1 + P2 : (r == 1 ? P2 : (r == 2 ? 0ull : 0ull - P1));
         const uint8_t *q = p + 8u * r;
-        for (uint64_t i = 0; i < stripes; i++) { XXR(v, zs_load64(q)); q += 32; }
+        uint64_t i = 0;
+        if constexpr (AHEAD > 1) {
+            for (; i + AHEAD <= stripes; i += AHEAD) {
+                uint64_t in[AHEAD];
+                #pragma unroll
+                for (int k = 0; k < AHEAD; k++) in[k] = zs_load64(q + 32 * k);
+                #pragma unroll
+                for (int k = 0; k < AHEAD; k++) XXR(v, in[k]);
+                q += 32 * AHEAD;
+            }
+        }
+        for (; i < stripes; i++) { XXR(v, zs_load64(q)); q += 32; }
         const int base = zs_lane() & ~3;
         uint64_t vv[4];
         #pragma unroll

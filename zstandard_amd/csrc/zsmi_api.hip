@@ -46,6 +46,8 @@ extern "C" const char *zsmi_getErrorName(size_t code)
     case ZSMI_error_workSpace_tooSmall: return "workSpace buffer is not large enough";
     case ZSMI_error_dstSize_tooSmall: return "Destination buffer is too small";
     case ZSMI_error_srcSize_wrong: return "Src size is incorrect";
+    case ZSMI_error_frameIndex_tooLarge: return "Frame index is too large";
+    case ZSMI_error_seekableIO: return "An I/O error occurred when reading/seeking";
     default: return "Unspecified error code";
     }
 }
@@ -156,6 +158,10 @@ struct zsmi_ctx {
     // staging for host-buffer calls
     DevBuf sSrc, sDst, sSizes, sDict, sPack, sPackOff;
     PinBuf hPack;
+    // seekable archives (seekable.hip): compressed frames at bound spacing before they are packed, per-frame words (sizes, hashes, offsets,
+    // the error word), a partial first / last frame's decoded bytes, the verify list
+    DevBuf dSeekStage, dSeekMeta, dSeekDec;
+    PinBuf hSeek;
     // timing
     int timing = 0;                      // 1: events around every launch; 2: only around the dominant kernels (k_lz_walk*, k_dec_execute)
     std::vector<TimedLaunch> launches;
@@ -1076,6 +1082,8 @@ extern "C" size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const
     if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
     return ds;
 }
+
+#include "seekable.hip"
 
 #ifdef ZSMI_DEBUG_HOOKS
 // ---- test hook (not in include/zsmi.h): copy a scratch buffer of the last compress sub-batch to the host.
