@@ -178,6 +178,43 @@ size_t zsmi_seekableContentSize(const void *src, size_t srcSize);
 int zsmi_seekableFrameInfo(const void *src, size_t srcSize, uint32_t index, uint64_t *cOffset, uint64_t *dOffset,
                            uint32_t *cSize, uint32_t *dSize);
 
+/* ------------------------------------------------------------------------------------------
+ * Dictionary training (zstd's fastCover trainer and ZDICT_finalizeDictionary, on the GPU).  The result is a formatted dictionary
+ * (magic 0xEC30A437 | dictID | Huffman description | OF, ML, LL NCounts | recent offsets 1, 4, 8 | content) that this library, oracle D and
+ * upstream libzstd load.  Parameters as zdict.h of zstd 1.4.x; ZDICT_DICTSIZE_MIN = 256, ZDICT_CONTENTSIZE_MIN = 128.
+ * Errors (nothing is written): dictCapacity < 256: dstSize_tooSmall; no samples, total sample bytes below 8 or of 4 GiB or more, a content
+ * below 128 bytes: srcSize_wrong; d other than 6 / 8, k < d, k > dictCapacity or k > 65536, f outside 12..26, accel > 1, splitPoint outside
+ * (0, 1]: parameter_outOfBound.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    unsigned k;          /* segment size; 0 = search (with steps) */
+    unsigned d;          /* d-mer size, 6 or 8; 0 = search both (8 in zsmi_trainFromBuffer) */
+    unsigned f;          /* log2 of the frequency table, 12..26; 0 = 20 */
+    unsigned steps;      /* k candidates tried when searching: k = 50, 50 + s, ... <= 2000, s = max(1950 / steps, 1); 0 = 40 (4 in zsmi_trainFromBuffer) */
+    unsigned accel;      /* 0 or 1 (others: parameter_outOfBound) */
+    double   splitPoint; /* share of samples trained on while searching; 0 = 0.75; 1.0 = train and score on all */
+    int      level;      /* compression level used to score candidates and gather the entropy statistics; 0 = 3 */
+    unsigned dictID;     /* 0 = derived from the content as ZDICT does: XXH64(content) % ((1u<<31) - 32768) + 32768 */
+} zsmi_fastCoverParams;
+
+/* replaces: ZDICT_trainFromBuffer (fastCover, d = 8, steps = 4, split 0.75, level 3).  Returns the dictionary's size or an error code */
+size_t zsmi_trainFromBuffer(void *dictBuffer, size_t dictCapacity, const void *samplesBuffer, const size_t *samplesSizes, unsigned nbSamples);
+/* replaces: ZDICT_optimizeTrainFromBuffer_fastCover / ZDICT_trainFromBuffer_fastCover: k and d given = no search (trained on all samples);
+ * otherwise each candidate (k, d) is trained on the first splitPoint share of the samples and scored by the size of the rest compressed by
+ * this library at `level` with the candidate as raw content (ties: smaller k, then smaller d).  The chosen k, d are written back */
+size_t zsmi_trainFromBuffer_fastCover(void *dictBuffer, size_t dictCapacity, const void *samplesBuffer, const size_t *samplesSizes,
+                                      unsigned nbSamples, zsmi_fastCoverParams *params);
+/* the same with the samples in device memory (host offsets / sizes, as the batch calls); the dictionary comes back to the host buffer
+ * dictBuffer, its size to *dictSize; the call waits for the context's stream.  Returns 0 or an error code value */
+int zsmi_trainFromDevice(zsmi_ctx *ctx, const void *dSamples, const uint64_t *sampleOffsets, const uint32_t *sampleSizes, uint32_t nbSamples,
+                         void *dictBuffer, size_t dictCapacity, zsmi_fastCoverParams *params, size_t *dictSize);
+/* replaces: ZDICT_finalizeDictionary: entropy tables from compressing the samples with `content` as raw content at `level` (0 = 3; every
+ * count starts at 1), header, recent offsets {1, 4, 8}; the content's front is cut when header + content exceed dstCapacity */
+size_t zsmi_finalizeDictionary(void *dst, size_t dstCapacity, const void *content, size_t contentSize, const void *samplesBuffer,
+                               const size_t *samplesSizes, unsigned nbSamples, int level, unsigned dictID);
+/* replaces: ZDICT_getDictID / ZSTD_getDictID_fromDict: host only, 0 for raw content or a buffer too short */
+unsigned zsmi_getDictID(const void *dict, size_t dictSize);
+
 /* ---- measurement hooks (bench.py): HIP-event timing of the kernels launched on the context's stream by the
  *      last batch call; one entry per kernel name, seconds are summed over launches.  Returns entries written.
  *      on = 1: events around every launch; on = 2: only around the dominant kernel of each direction (k_lz_walk*, k_dec_execute):

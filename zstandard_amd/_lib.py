@@ -64,6 +64,11 @@ def build(force=False):
 _lib = None
 
 
+class FastCoverParams(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_uint), ("d", ctypes.c_uint), ("f", ctypes.c_uint), ("steps", ctypes.c_uint), ("accel", ctypes.c_uint),
+                ("splitPoint", ctypes.c_double), ("level", ctypes.c_int), ("dictID", ctypes.c_uint)]
+
+
 class KernelTime(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("seconds", ctypes.c_double), ("launches", ctypes.c_uint32)]
 
@@ -111,6 +116,12 @@ def lib():
     L.zsmi_seekableNumFrames.restype = sz; L.zsmi_seekableNumFrames.argtypes = [vp, sz]
     L.zsmi_seekableContentSize.restype = sz; L.zsmi_seekableContentSize.argtypes = [vp, sz]
     L.zsmi_seekableFrameInfo.restype = i32; L.zsmi_seekableFrameInfo.argtypes = [vp, sz, u32, pu64, pu64, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
+    L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
+    L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
+    L.zsmi_trainFromDevice.restype = i32; L.zsmi_trainFromDevice.argtypes = [vp, vp, vp, vp, u32, vp, sz, pfc, psz]
+    L.zsmi_finalizeDictionary.restype = sz; L.zsmi_finalizeDictionary.argtypes = [vp, sz, vp, sz, vp, psz, ctypes.c_uint, i32, ctypes.c_uint]
+    L.zsmi_getDictID.restype = ctypes.c_uint; L.zsmi_getDictID.argtypes = [vp, sz]
     if DEBUG or hasattr(L, "zsmi_dbg_copyScratch"):            # (a variant build named by ZSMI_LIB_FILE may carry the hooks too)
         L.zsmi_dbg_copyScratch.restype = i32; L.zsmi_dbg_copyScratch.argtypes = [vp, i32, vp, sz]
     _lib = L
@@ -124,4 +135,5 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_compress_usingDict", "zsmi_compressBatchDevice_usingDict", "zsmi_compressBatchHost_usingDict",
            "zsmi_packFramesDevice", "zsmi_enableKernelTiming", "zsmi_getKernelTimes", "zsmi_versionString", "zsmi_decodeScratchBytes", "zsmi_shutdown",
            "zsmi_seekableBound", "zsmi_compressSeekable", "zsmi_compressSeekableDevice", "zsmi_decompressSeekable", "zsmi_decompressSeekableDevice",
-           "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo"]
+           "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo",
+           "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID"]

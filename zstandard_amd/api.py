@@ -8,6 +8,8 @@
   SeekableArchive     random access into a seekable archive (zstd's seekable format: independent frames + a seek table), made by
                       ZstdCompressor.compress_seekable or BatchCodec.compress_seekable_device.
   BatchCodec          the batch hot path on device memory (torch tensors are only a handle to device memory here).
+  train_dictionary, finalize_dictionary, get_dict_id
+                      zstd dictionaries made on the GPU (fastCover and ZDICT_finalizeDictionary; zdict.h's parameters).
 
 Everything computes on the GPU through libzsmi.so; nothing here falls back to a CPU codec.
 """
@@ -158,6 +160,53 @@ class SeekableArchive:
         return out.raw[:r]
 
 
+def _samples(samples):
+    """a list of bytes-likes, or (buffer, sizes) -> (contiguous uint8 array, size_t array)"""
+    if isinstance(samples, tuple):
+        buf, sizes = samples
+        buf = np.frombuffer(bytes(buf), dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, dtype=np.uint8)
+        sizes = np.ascontiguousarray(sizes, dtype=np.uintp)
+    else:
+        parts = [bytes(x) for x in samples]
+        buf = np.frombuffer(b"".join(parts) or b"\0", dtype=np.uint8)
+        sizes = np.array([len(x) for x in parts], dtype=np.uintp)
+    return buf, sizes
+
+
+def _params(k, d, f, steps, split_point, level, dict_id, accel):
+    return _lib.FastCoverParams(k=k, d=d, f=f, steps=steps, accel=accel, splitPoint=split_point, level=level, dictID=dict_id)
+
+
+def train_dictionary(samples, capacity=65536, k=0, d=0, level=3, dict_id=0, f=0, steps=0, split_point=0.0, accel=0, return_params=False):
+    """A zstd dictionary trained on the GPU (zsmi_trainFromBuffer_fastCover).  samples: a list of bytes-likes or (buffer, sizes).  k = 0 or
+    d = 0 searches (steps k values in [50, 2000], d in {6, 8} when d = 0), scoring on the samples behind the split_point share.  Returns the
+    dictionary, or (dictionary, k, d) with return_params."""
+    L = _lib.lib()
+    buf, sizes = _samples(samples)
+    p = _params(k, d, f, steps, split_point, level, dict_id, accel)
+    out = ctypes.create_string_buffer(max(int(capacity), 1))
+    r = _raise_if_error(L, L.zsmi_trainFromBuffer_fastCover(out, capacity, buf.ctypes.data_as(ctypes.c_void_p),
+                                                            sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), len(sizes), ctypes.byref(p)))
+    return (out.raw[:r], p.k, p.d) if return_params else out.raw[:r]
+
+
+def finalize_dictionary(content, samples, capacity, level=3, dict_id=0) -> bytes:
+    """ZDICT_finalizeDictionary on the GPU: entropy tables from the samples compressed with `content`, the header, recent offsets {1, 4, 8}"""
+    L = _lib.lib()
+    buf, sizes = _samples(samples)
+    content = bytes(content)
+    out = ctypes.create_string_buffer(max(int(capacity), 1))
+    r = _raise_if_error(L, L.zsmi_finalizeDictionary(out, capacity, content, len(content), buf.ctypes.data_as(ctypes.c_void_p),
+                                                     sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), len(sizes), level, dict_id))
+    return out.raw[:r]
+
+
+def get_dict_id(dic) -> int:
+    """the ID of a formatted dictionary; 0 for raw content (host only)"""
+    dic = bytes(dic)
+    return int(_lib.lib().zsmi_getDictID(dic, len(dic)))
+
+
 class BatchCodec:
     """n independent chunks <-> n frames on one GPU.  Arrays of offsets/sizes live on the host (numpy);
     data lives on the device.  `stream` is a raw hipStream_t handle (e.g. torch.cuda.current_stream().cuda_stream)."""
@@ -286,6 +335,17 @@ class BatchCodec:
         if rc:
             raise RuntimeError(f"zsmi_decompressBatchHost: error {rc}")
         return arena, do, dsz
+
+    def train_device(self, d_samples_ptr, offsets, sizes, capacity=65536, k=0, d=0, level=3, dict_id=0, f=0, steps=0, split_point=0.0, accel=0):
+        """a dictionary trained on samples in device memory (zsmi_trainFromDevice; host offsets / sizes).  Returns (dictionary, k, d)"""
+        so = np.ascontiguousarray(offsets, dtype=np.uint64); ss = np.ascontiguousarray(sizes, dtype=np.uint32)
+        p = _params(k, d, f, steps, split_point, level, dict_id, accel)
+        out = ctypes.create_string_buffer(max(int(capacity), 1))
+        size = ctypes.c_size_t(0)
+        rc = self.L.zsmi_trainFromDevice(self.ctx, ctypes.c_void_p(d_samples_ptr), self._p(so), self._p(ss), len(ss), out, capacity, ctypes.byref(p), ctypes.byref(size))
+        if rc:
+            raise RuntimeError(f"zsmi_trainFromDevice: {_error_name(self.L, rc)}")
+        return out.raw[:size.value], p.k, p.d
 
     def kernel_times(self):
         out = (_lib.KernelTime * 16)()

@@ -1,0 +1,557 @@
+// dict_train.hip -- dictionary training on the GPU: zstd's fastCover trainer and ZDICT_finalizeDictionary (included from zsmi_api.hip after the
+// one-shot calls).
+//
+//   frequencies  k_train_freq:    every d-mer of the training samples hashed to f bits (zstd's 6- / 8-byte multiplicative hash); the d-mers that
+//                                 lie inside their sample (8 bytes readable) are counted into a 2^f table by integer atomics (order-independent)
+//   links        radix sort of (hash << 32 | position), k_train_links: per position the distance to the previous and the next position of the
+//                                 same hash (capped at 65535 = none within reach)
+//   segments     k_train_select:  one workgroup a candidate (k, d); epochs one after the other inside it.  An epoch scores every window end e at
+//                                 once: score(e) - score(e - 1) depends only on the d-mer entering (e - 1) and the one leaving (e - L - 1) and on
+//                                 whether their hash occurs again inside the window, so the scores are a prefix sum of per-position deltas and the
+//                                 segment is the first argmax.  Its d-mers' frequencies are zeroed on the device and its bytes fill the content from
+//                                 the end.  Only the content's start (one word a candidate) is read back.
+//   search       each candidate's content is a raw dictionary for the batch compressor over the held-out samples; the smallest total wins
+//   finalize     the samples compressed with the content (compressBatchDeviceImpl with a stats pointer): k_train_stats counts literal bytes and
+//                                 LL / OF / ML codes; k_train_id hashes the content (XXH64) into the dictionary ID; k_train_tables builds the
+//                                 Huffman description and the three NCounts with the encoder's routines and assembles the dictionary.
+static const uint32_t kTrainDefaultF = 20, kTrainMinF = 12, kTrainMaxF = 26;
+static const uint32_t kTrainDictSizeMin = 256, kTrainContentMin = 128;       // ZDICT_DICTSIZE_MIN, ZDICT_CONTENTSIZE_MIN
+static const uint32_t kTrainMaxZeroRun = 10;                                 // epochs in a row without a segment end the content (zstd >= 1.4.5)
+static const uint32_t kTrainThreads = 1024, kTrainPerThread = 8;            // k_train_select: window ends a thread scores per tile
+static const uint32_t kTrainStatWords = 448;                                // literal bytes [0, 256), LL codes [256, 320), OF [320, 384), ML [384, 448)
+
+struct ZsTrainCand { uint32_t k, d, pad0, pad1; uint32_t *freq; uint8_t *content; };
+
+__device__ __forceinline__ uint32_t train_hash(const uint8_t *p, uint32_t d, uint32_t f)
+{
+    const uint64_t v = zs_load64(p);
+    if (d == 6) return (uint32_t)(((v << 16) * 227718039650203ull) >> (64 - f));      // ZSTD_hash6Ptr
+    return (uint32_t)((v * 0xCF1BBCDCB7A56463ull) >> (64 - f));                          // ZSTD_hash8Ptr
+}
+
+// one thread a d-mer start p < nbDmers: its hash (info.x), its sort key, and its count if its 8 bytes lie inside its sample (ends: the training
+// samples' end offsets)
+__global__ void k_train_freq(const uint8_t *__restrict__ samples, uint32_t nbDmers, uint32_t d, uint32_t f, const uint64_t *__restrict__ ends, uint32_t nTrain,
+                             uint2 *__restrict__ info, uint64_t *__restrict__ keys, uint32_t *__restrict__ freq)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nbDmers) return;
+    const uint32_t h = train_hash(samples + p, d, f);
+    info[p] = make_uint2(h, 0u);
+    keys[p] = ((uint64_t)h << 32) | p;
+    uint32_t lo = 0, hi = nTrain;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (ends[mid] <= p) lo = mid + 1; else hi = mid; }
+    if (lo < nTrain && (uint64_t)p + 8 <= ends[lo]) atomicAdd(&freq[h], 1u);
+}
+
+// sorted keys -> per position: distance to the previous (low 16 bits) and the next (high 16 bits) position of the same hash; 65535 = none nearer
+__global__ void k_train_links(const uint64_t *__restrict__ sorted, uint32_t n, uint2 *__restrict__ info)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t key = sorted[i];
+    const uint32_t h = (uint32_t)(key >> 32), p = (uint32_t)key;
+    uint32_t dp = 65535u, dn = 65535u;
+    if (i > 0) { const uint64_t o = sorted[i - 1]; if ((uint32_t)(o >> 32) == h) dp = min(p - (uint32_t)o, 65535u); }
+    if (i + 1 < n) { const uint64_t o = sorted[i + 1]; if ((uint32_t)(o >> 32) == h) dn = min((uint32_t)o - p, 65535u); }
+    info[p].y = dp | (dn << 16);
+}
+
+// exclusive prefix sum of one int64 a thread over the workgroup (kTrainThreads); *total: the sum of all
+__device__ __forceinline__ int64_t train_block_scan(int64_t v, int64_t *lds, int64_t &total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    int64_t x = v;
+    #pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) { const int64_t y = __shfl_up(x, o); if (lane >= o) x += y; }
+    if (lane == 63) lds[wave] = x;
+    __syncthreads();
+    if (wave == 0) {
+        int64_t w = lane < kTrainThreads / 64 ? lds[lane] : 0;
+        #pragma unroll
+        for (uint32_t o = 1; o < kTrainThreads / 64; o <<= 1) { const int64_t y = __shfl_up(w, o); if (lane >= o) w += y; }
+        if (lane < kTrainThreads / 64) lds[16 + lane] = w;
+    }
+    __syncthreads();
+    const int64_t before = wave ? lds[16 + wave - 1] : 0;
+    total = lds[16 + kTrainThreads / 64 - 1];
+    __syncthreads();
+    return before + x - v;
+}
+__device__ __forceinline__ bool train_better(int64_t s, uint32_t e, int64_t bs, uint32_t be) { return s > bs || (s == bs && e < be); }
+
+// one workgroup a candidate: the whole epoch loop of FASTCOVER_buildDictionary.  Epochs: num = max(1, cap / k / 4), size = nbDmers / num, and at
+// least 10 k d-mers an epoch (then num = nbDmers / size); they are visited in turn until the content is full or kTrainMaxZeroRun epochs in a row
+// have no segment of positive score.  The window of end e holds the d-mers [max(eb, e - L), e), L = k - d + 1; its score is the summed frequency
+// of its distinct hashes.  tails[c]: where the candidate's content starts in its buffer of cap bytes.
+__global__ void __launch_bounds__(kTrainThreads) k_train_select(const uint2 *__restrict__ info6, const uint2 *__restrict__ info8, const uint8_t *__restrict__ samples,
+                                                                uint32_t nbDmers, uint32_t cap, const ZsTrainCand *__restrict__ cands, uint32_t *__restrict__ tails)
+{
+    __shared__ int64_t scan[32];
+    __shared__ int64_t redS[16];
+    __shared__ uint32_t redE[16], seg[2];
+    const ZsTrainCand C = cands[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t k = C.k, d = C.d, L = k - d + 1;
+    const uint2 *info = d == 6 ? info6 : info8;
+    uint32_t *freq = C.freq;
+    uint8_t *content = C.content;
+    uint32_t num = max(1u, cap / k / 4u), size = nbDmers / num;
+    if ((uint64_t)size < 10ull * k) { size = (uint32_t)min<uint64_t>(10ull * k, nbDmers); num = nbDmers / size; }
+    uint32_t tail = cap, zeroRun = 0;
+    for (uint32_t epoch = 0; tail > 0; epoch = (epoch + 1) % num) {
+        const uint64_t eb = (uint64_t)epoch * size, ee = eb + size;
+        int64_t carry = 0, best = 0;
+        uint32_t bestE = 0xFFFFFFFFu;
+        for (uint64_t base = eb + 1; base <= ee; base += kTrainThreads * kTrainPerThread) {
+            int64_t part[kTrainPerThread], run = 0;
+            #pragma unroll
+            for (uint32_t v = 0; v < kTrainPerThread; v++) {
+                const uint64_t e = base + tid * kTrainPerThread + v;
+                int64_t x = 0;
+                if (e <= ee) {
+                    const uint64_t j = e - 1, be = e >= eb + L ? e - L : eb;
+                    const uint2 a = info[j];
+                    if ((a.y & 0xFFFFu) > j - be) x += freq[a.x];                   // entering: no earlier occurrence inside the window
+                    if (e >= eb + L + 1) {
+                        const uint2 q = info[e - L - 1];
+                        if ((q.y >> 16) >= L) x -= freq[q.x];                        // leaving: no later occurrence inside the window
+                    }
+                }
+                run += x; part[v] = run;
+            }
+            int64_t total;
+            const int64_t before = train_block_scan(run, scan, total);
+            #pragma unroll
+            for (uint32_t v = 0; v < kTrainPerThread; v++) {
+                const uint64_t e = base + tid * kTrainPerThread + v;
+                const int64_t s = carry + before + part[v];
+                if (e <= ee && s > best) { best = s; bestE = (uint32_t)e; }
+            }
+            carry += total;
+        }
+        // first window end of the largest score
+        #pragma unroll
+        for (uint32_t o = 32; o >= 1; o >>= 1) {
+            const int64_t s = __shfl_xor(best, o); const uint32_t e = (uint32_t)__shfl_xor((int)bestE, o);
+            if (train_better(s, e, best, bestE)) { best = s; bestE = e; }
+        }
+        if (lane == 0) { redS[wave] = best; redE[wave] = bestE; }
+        __syncthreads();
+        if (tid == 0) {
+            for (uint32_t w = 1; w < kTrainThreads / 64; w++) if (train_better(redS[w], redE[w], redS[0], redE[0])) { redS[0] = redS[w]; redE[0] = redE[w]; }
+            seg[0] = 0xFFFFFFFFu; seg[1] = 0;
+        }
+        __syncthreads();
+        best = redS[0]; bestE = redE[0];
+        __syncthreads();
+        if (best <= 0) { if (++zeroRun >= kTrainMaxZeroRun) break; continue; }
+        zeroRun = 0;
+        // the segment without its zero-frequency head and tail, then its d-mers' frequencies zeroed
+        const uint32_t sb = bestE >= eb + L ? bestE - L : (uint32_t)eb;
+        for (uint32_t p = sb + tid; p < bestE; p += kTrainThreads)
+            if (freq[info[p].x]) { atomicMin(&seg[0], p); atomicMax(&seg[1], p + 1); }
+        __syncthreads();
+        const uint32_t nb = seg[0], ne = seg[1];
+        for (uint32_t p = nb + tid; p < ne; p += kTrainThreads) freq[info[p].x] = 0;
+        const uint32_t segSize = min(ne - nb + d - 1, tail);
+        __syncthreads();
+        if (segSize < d) break;
+        tail -= segSize;
+        for (uint32_t i = tid; i < segSize; i += kTrainThreads) content[tail + i] = samples[nb + i];
+        __syncthreads();
+    }
+    if (tid == 0) tails[blockIdx.x] = tail;
+}
+
+// finalize statistics of one compressed sub-batch, between k_encode_sequences and k_encode_literals: the codes the sequences kernel left in the
+// block's literal buffer (LL, OF with the recent-offset codes applied, ML; ZS_CHAIN_CODES apart), and the literal bytes - every block byte no match
+// of the block's records covers.  One workgroup a block, counts added to stats[kTrainStatWords].
+__global__ void __launch_bounds__(256) k_train_stats(const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, const ZsSeqRec *__restrict__ seqAll,
+                                                     const ZsRangeHdr *__restrict__ hdrAll, const uint8_t *__restrict__ litsAll, uint32_t *__restrict__ stats)
+{
+    __shared__ uint32_t cov[ZS_BLOCK_MAX / 32], hist[kTrainStatWords], rstart[ZS_WALK_RANGES + 1];
+    const uint32_t blk = blockIdx.x, tid = threadIdx.x;
+    const ZsBlockDesc bd = blocks[blk];
+    const uint32_t n = bd.size;
+    for (uint32_t i = tid; i < ZS_BLOCK_MAX / 32; i += 256) cov[i] = 0;
+    for (uint32_t i = tid; i < kTrainStatWords; i += 256) hist[i] = 0;
+    const ZsRangeHdr *hdr = hdrAll + (size_t)blk * ZS_WALK_RANGES;
+    if (tid == 0) { uint32_t s = 0; for (uint32_t r = 0; r < ZS_WALK_RANGES; r++) { rstart[r] = s; s += n >= 16 ? hdr[r].nseq : 0u; } rstart[ZS_WALK_RANGES] = s; }
+    __syncthreads();
+    const uint32_t nseq = rstart[ZS_WALK_RANGES];
+    const ZsSeqRec *seqBase = seqAll + (size_t)blk * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE;
+    const uint8_t *codes = litsAll + (size_t)blk * (ZS_BLOCK_MAX + 64);
+    for (uint32_t g = tid; g < nseq; g += 256) {
+        uint32_t r = 0;
+        for (uint32_t st = ZS_WALK_RANGES / 2; st >= 1; st >>= 1) if (g >= rstart[r + st]) r += st;
+        const ZsSeqRec rec = seqBase[(size_t)r * ZS_SEQ_PER_RANGE + hdr[r].first + (g - rstart[r])];
+        const uint32_t pos = zs_rec_pos(rec.y), end = min(pos + zs_rec_ml(rec.x), n);
+        for (uint32_t b = pos; b < end;) {                                  // the match's bytes in the coverage bitmap
+            const uint32_t w = b >> 5, lo = b & 31u, cnt = min(32u - lo, end - b);
+            atomicOr(&cov[w], (cnt == 32u ? 0xFFFFFFFFu : ((1u << cnt) - 1u)) << lo);
+            b += cnt;
+        }
+        atomicAdd(&hist[256 + codes[g]], 1u);
+        atomicAdd(&hist[320 + codes[ZS_CHAIN_CODES + g]], 1u);
+        atomicAdd(&hist[384 + codes[2u * ZS_CHAIN_CODES + g]], 1u);
+    }
+    __syncthreads();
+    const uint8_t *s = src + bd.srcOff;
+    for (uint32_t b = tid; b < n; b += 256) if (!((cov[b >> 5] >> (b & 31u)) & 1u)) atomicAdd(&hist[s[b]], 1u);
+    __syncthreads();
+    for (uint32_t i = tid; i < kTrainStatWords; i += 256) if (hist[i]) atomicAdd(&stats[i], hist[i]);
+}
+
+// the dictionary ID: the caller's, or XXH64(content) % ((1 << 31) - 32768) + 32768 as ZDICT derives it
+__global__ void __launch_bounds__(64) k_train_id(const uint8_t *__restrict__ content, uint32_t size, uint32_t given, uint32_t *__restrict__ id)
+{
+    const uint64_t h = xxh64_quad<16>(content, size);                  // (every lane of a quad calls)
+    if (threadIdx.x == 0) *id = given ? given : (uint32_t)(h % 2147450880ull) + 32768u;
+}
+
+// counts + 1 (every symbol representable), halved until their sum is below `limit`, never below 1
+__device__ static uint32_t train_scaled(const uint32_t *raw, uint32_t n, uint32_t *out, uint64_t limit)
+{
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < n; s++) total += (uint64_t)raw[s] + 1;
+    uint32_t shift = 0;
+    while ((total >> shift) >= limit) shift++;
+    uint32_t sum = 0;
+    for (uint32_t s = 0; s < n; s++) { out[s] = max(1u, (uint32_t)(((uint64_t)raw[s] + 1) >> shift)); sum += out[s]; }
+    return sum;
+}
+
+// one workgroup of 256: the entropy section (Huffman description of <= 11 bits, NCounts OF 8 / ML 9 / LL 9), the recent offsets {1, 4, 8},
+// then the content behind it, cut at its front to fit cap.  hdr: 1 KiB of scratch.  result[0]: the dictionary's size, 0 if it cannot be made.
+__global__ void __launch_bounds__(256) k_train_tables(const uint32_t *__restrict__ stats, const uint8_t *__restrict__ content, uint32_t contentSize, uint32_t cap,
+                                                      const uint32_t *__restrict__ dictID, uint8_t *__restrict__ hdr, uint8_t *__restrict__ out, uint32_t *__restrict__ result)
+{
+    __shared__ K3Lds L;
+    __shared__ uint32_t cnt[64], misc[4];
+    __shared__ int16_t norm[64];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t hcap = 1024;
+    if (tid == 0) { misc[0] = 0; misc[1] = 0; train_scaled(stats, 256, L.count, 1u << 23); }   // (package-merge keys are count << 8 | symbol)
+    __syncthreads();
+    const uint32_t lit = L.count[tid];
+    for (uint32_t maxBits = ZS_HUF_MAXBITS; maxBits >= 8; maxBits--) {     // a description over 127 bytes: flatter codes
+        L.count[tid] = lit;
+        __syncthreads();
+        const uint32_t tableLog = huffLengths(L, 255, maxBits);
+        huffCodesAndWeights(L, 255, tableLog);
+        if (wave == 0) { const uint32_t hs = writeHuffHeaderWave(L, hdr + 8, 256, 255, tableLog); if (lane == 0) misc[0] = hs; }
+        __syncthreads();
+        if (misc[0]) break;
+        __syncthreads();
+    }
+    if (tid == 0 && misc[0]) {
+        uint32_t pos = 8 + misc[0];
+        const uint32_t ofMax = zs_highbit(contentSize + (128u << 10));
+        const uint32_t maxes[3] = { min(ofMax, (uint32_t)MaxOff), MaxML, MaxLL }, logs[3] = { 8, 9, 9 }, base[3] = { 320, 384, 256 };
+        bool ok = true;
+        for (uint32_t t = 0; t < 3 && ok; t++) {
+            const uint32_t total = train_scaled(stats + base[t], maxes[t] + 1, cnt, 1u << 30);
+            normalizeCounts(norm, logs[t], cnt, total, maxes[t]);
+            const uint32_t w = writeNCount(hdr + pos, hcap - pos, norm, maxes[t], logs[t]);
+            ok = w != 0; pos += w;
+        }
+        ok = ok && pos + 12 <= hcap;
+        const uint32_t id = *dictID, words[5] = { 0xEC30A437u, id, 1u, 4u, 8u };
+        for (uint32_t i = 0; i < 2; i++) zs_store32(hdr + 4 * i, words[i]);
+        if (ok) for (uint32_t i = 0; i < 3; i++) zs_store32(hdr + pos + 4 * i, words[2 + i]);
+        pos += 12;
+        misc[1] = (ok && pos <= hcap && pos < cap) ? pos : 0u;
+    }
+    __syncthreads();
+    const uint32_t hs = misc[1];
+    if (!hs) { if (tid == 0) *result = 0; return; }
+    const uint32_t keep = min(contentSize, cap - hs);
+    for (uint32_t i = tid; i < hs; i += 256) out[i] = hdr[i];
+    zs_block_copy(out + hs, content + (contentSize - keep), keep, tid, 256);
+    if (tid == 0) *result = hs + keep;
+}
+
+// samples at scattered offsets -> back to back (one workgroup a sample)
+__global__ void k_train_gather(const uint8_t *__restrict__ src, const uint64_t *__restrict__ offs /* [0, n): from, [n, 2n): to */, const uint32_t *__restrict__ sizes,
+                               uint32_t n, uint8_t *__restrict__ dst)
+{
+    const uint32_t i = blockIdx.x;
+    zs_block_copy(dst + offs[n + i], src + offs[i], sizes[i], threadIdx.x, blockDim.x);
+}
+
+// ---- host ----
+extern "C" unsigned zsmi_getDictID(const void *dict, size_t dictSize)
+{
+    const uint8_t *d = (const uint8_t *)dict;
+    if (!d || dictSize < 8 || h_rd32(d) != 0xEC30A437u) return 0;
+    return h_rd32(d + 4);
+}
+
+namespace {
+struct TrainPlan {
+    uint32_t f = kTrainDefaultF, steps = 40;
+    int level = 3;
+    double split = 0.75;
+    std::vector<std::pair<uint32_t, uint32_t>> cands;          // (k, d)
+    bool search = false;
+};
+}
+
+// the parameters the trainer runs with, or an error code; total: the samples' bytes
+static int trainParams(const zsmi_fastCoverParams *p, size_t cap, uint64_t total, uint32_t nb, TrainPlan &t)
+{
+    if (cap < kTrainDictSizeMin) return ZSMI_error_dstSize_tooSmall;
+    if (!p) return ZSMI_error_GENERIC;
+    if (p->d != 0 && p->d != 6 && p->d != 8) return ZSMI_error_parameter_outOfBound;
+    if (p->f != 0 && (p->f < kTrainMinF || p->f > kTrainMaxF)) return ZSMI_error_parameter_outOfBound;
+    if (p->accel > 1) return ZSMI_error_parameter_outOfBound;
+    if (!(p->splitPoint == 0.0 || (p->splitPoint > 0.0 && p->splitPoint <= 1.0))) return ZSMI_error_parameter_outOfBound;
+    if (p->k != 0 && (p->k < (p->d ? p->d : 8u) || p->k > cap || p->k > 65536u)) return ZSMI_error_parameter_outOfBound;
+    if (nb == 0 || total < 8 || total >= (1ull << 32)) return ZSMI_error_srcSize_wrong;
+    t.f = p->f ? p->f : kTrainDefaultF;
+    t.steps = p->steps ? p->steps : 40;
+    t.split = p->splitPoint > 0.0 ? p->splitPoint : 0.75;
+    t.level = p->level ? p->level : 3;
+    t.search = p->k == 0 || p->d == 0;
+    std::vector<uint32_t> ds, ks;
+    if (p->d) ds.push_back(p->d); else { ds.push_back(6); ds.push_back(8); }
+    if (p->k) ks.push_back(p->k);
+    else {
+        const uint32_t step = std::max<uint32_t>((2000 - 50) / t.steps, 1);             // ZDICT_optimizeTrainFromBuffer_fastCover's k range
+        for (uint32_t k = 50; k <= 2000; k += step) if (k <= cap) ks.push_back(k);
+    }
+    for (uint32_t d : ds) for (uint32_t k : ks) if (k >= d) t.cands.push_back({ k, d });
+    if (t.cands.empty()) return ZSMI_error_parameter_outOfBound;
+    return 0;
+}
+
+static int trainLaunchSort(zsmi_ctx *c, uint32_t n, uint32_t f)
+{
+    size_t tmp = 0;
+    if (hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n, 0, 32 + (int)f, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (!c->dTrSortTmp.reserve(tmp)) return ZSMI_error_memory_allocation;
+    TimedLaunch tl{ "radix_sort", nullptr, nullptr };
+    if (c->timing == 1) { tl.a = getEvent(c); tl.b = getEvent(c); (void)hipEventRecord(tl.a, c->stream); }
+    if (hipcub::DeviceRadixSort::SortKeys(c->dTrSortTmp.p, tmp, (const uint64_t *)c->dTrKeys.p, (uint64_t *)c->dTrKeysOut.p, (int)n, 0, 32 + (int)f, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (c->timing == 1) { (void)hipEventRecord(tl.b, c->stream); c->launches.push_back(tl); }
+    return 0;
+}
+
+// content (device, contentSize bytes) + the samples (device, back to back at offs / sizes) -> a formatted dictionary at dOut (device, cap bytes);
+// *dResult (device): its size or 0.  Asynchronous.
+static int finalizeQueue(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uint64_t> &offs, const std::vector<uint32_t> &sizes, const uint8_t *dContent,
+                         uint32_t contentSize, uint32_t cap, int level, uint32_t dictID, uint8_t *dOut, uint32_t *dResult)
+{
+    const uint32_t n = (uint32_t)sizes.size();
+    std::vector<uint64_t> dof(n);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; i++) { dof[i] = at; at += zsmi_compressBound(sizes[i]); }
+    if (!c->dTrArena.reserve(at + 64) || !c->dTrMisc.reserve(sizeof(uint32_t) * (kTrainStatWords + 8) + 1024) || !c->dTrSizes.reserve(sizeof(uint32_t) * n + 64)) return ZSMI_error_memory_allocation;
+    uint32_t *dStats = (uint32_t *)c->dTrMisc.p, *dId = dStats + kTrainStatWords;
+    uint8_t *dHdr = (uint8_t *)(dId + 8);
+    if (hipMemsetAsync(dStats, 0, sizeof(uint32_t) * kTrainStatWords, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    ZsCompressDict dict; dict.contentSize = contentSize;
+    if (const int e = compressBatchDeviceImpl(c, dSamples, offs.data(), sizes.data(), n, c->dTrArena.p, dof.data(), (uint32_t *)c->dTrSizes.p, level, dContent, &dict, dStats)) return e;
+    LAUNCH(c, "k_train_id", k_train_id, dim3(1), dim3(64), 0, dContent, contentSize, dictID, dId);
+    LAUNCH(c, "k_train_tables", k_train_tables, dim3(1), dim3(256), 0, (const uint32_t *)dStats, dContent, contentSize, cap, (const uint32_t *)dId, dHdr, dOut, dResult);
+    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+
+// samples back to back in device memory (sizes on the host) -> the dictionary in hostDict; the chosen k, d go back into *params
+static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uint32_t> &sizes, void *hostDict, size_t cap, zsmi_fastCoverParams *params, size_t *dictSize)
+{
+    const uint32_t n = (uint32_t)sizes.size();
+    uint64_t total = 0;
+    for (uint32_t s : sizes) total += s;
+    TrainPlan t;
+    if (const int e = trainParams(params, cap, total, n, t)) return e;
+    if (!hostDict) return ZSMI_error_GENERIC;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    const uint32_t cap32 = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu - 4096);
+    // training share: the first split of the samples while searching (at least one, and at least 8 bytes), all of them otherwise
+    uint32_t nTrain = n;
+    if (t.search && t.split < 1.0) nTrain = std::max<uint32_t>(1, (uint32_t)(n * t.split));
+    uint64_t trainBytes = 0;
+    for (uint32_t i = 0; i < nTrain; i++) trainBytes += sizes[i];
+    if (trainBytes < 8) { nTrain = n; trainBytes = total; }
+    const uint32_t nbDmers = (uint32_t)(trainBytes - 7);
+    std::vector<uint64_t> offs(n), ends(nTrain);
+    { uint64_t at = 0; for (uint32_t i = 0; i < n; i++) { offs[i] = at; at += sizes[i]; if (i < nTrain) ends[i] = at; } }
+    // d-mer hashes, counts and links, once per d
+    const size_t table = (size_t)4 << t.f;
+    bool needD[2] = { false, false };
+    for (auto &kd : t.cands) needD[kd.second == 8] = true;
+    if (!c->dTrKeys.reserve((size_t)8 * nbDmers) || !c->dTrKeysOut.reserve((size_t)8 * nbDmers) || !c->dTrEnds.reserve(8 * (size_t)nTrain) || !c->dTrFreqBase.reserve(2 * table)) return ZSMI_error_memory_allocation;
+    for (int w = 0; w < 2; w++) if (needD[w] && !c->dTrInfo[w].reserve((size_t)8 * nbDmers)) return ZSMI_error_memory_allocation;
+    if (hipMemcpyAsync(c->dTrEnds.p, ends.data(), 8 * (size_t)nTrain, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipMemsetAsync(c->dTrFreqBase.p, 0, 2 * table, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    for (int w = 0; w < 2; w++) {
+        if (!needD[w]) continue;
+        uint32_t *freqBase = (uint32_t *)((uint8_t *)c->dTrFreqBase.p + w * table);
+        LAUNCH(c, "k_train_freq", k_train_freq, dim3((nbDmers + 255) / 256), dim3(256), 0, dSamples, nbDmers, w ? 8u : 6u, t.f, (const uint64_t *)c->dTrEnds.p, nTrain,
+               (uint2 *)c->dTrInfo[w].p, (uint64_t *)c->dTrKeys.p, freqBase);
+        if (const int e = trainLaunchSort(c, nbDmers, t.f)) return e;
+        LAUNCH(c, "k_train_links", k_train_links, dim3((nbDmers + 255) / 256), dim3(256), 0, (const uint64_t *)c->dTrKeysOut.p, nbDmers, (uint2 *)c->dTrInfo[w].p);
+    }
+    // the candidates, in groups whose frequency tables fit 2 GiB
+    const uint32_t nc = (uint32_t)t.cands.size();
+    const uint32_t group = (uint32_t)std::max<size_t>(1, std::min<size_t>(nc, ((size_t)2 << 30) / table));
+    if (!c->dTrFreq.reserve(table * group) || !c->dTrContent.reserve((size_t)cap32 * nc) || !c->dTrCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc) ||
+        !c->hTrCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc)) return ZSMI_error_memory_allocation;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;          // (the pinned candidate list may feed an earlier copy)
+    ZsTrainCand *hc = (ZsTrainCand *)c->hTrCand.p;
+    uint32_t *dTails = (uint32_t *)((ZsTrainCand *)c->dTrCand.p + nc);
+    for (uint32_t i = 0; i < nc; i++) {
+        hc[i].k = t.cands[i].first; hc[i].d = t.cands[i].second; hc[i].pad0 = hc[i].pad1 = 0;
+        hc[i].freq = (uint32_t *)((uint8_t *)c->dTrFreq.p + table * (i % group));
+        hc[i].content = (uint8_t *)c->dTrContent.p + (size_t)cap32 * i;
+    }
+    if (hipMemcpyAsync(c->dTrCand.p, hc, sizeof(ZsTrainCand) * nc, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    for (uint32_t g0 = 0; g0 < nc; g0 += group) {
+        const uint32_t g1 = std::min(nc, g0 + group);
+        for (uint32_t i = g0; i < g1; i++)
+            if (hipMemcpyAsync(hc[i].freq, (uint8_t *)c->dTrFreqBase.p + (hc[i].d == 8) * table, table, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        LAUNCH(c, "k_train_select", k_train_select, dim3(g1 - g0), dim3(kTrainThreads), 0, (const uint2 *)c->dTrInfo[0].p, (const uint2 *)c->dTrInfo[1].p, dSamples, nbDmers, cap32,
+               (const ZsTrainCand *)c->dTrCand.p + g0, dTails + g0);
+    }
+    uint32_t *hTails = (uint32_t *)(hc + nc);
+    if (hipMemcpyAsync(hTails, dTails, sizeof(uint32_t) * nc, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    uint32_t win = 0;
+    if (nc > 1) {
+        // each candidate as raw content for the held-out samples (the samples behind the training share; all of them if there are none)
+        const uint32_t t0 = nTrain < n ? nTrain : 0, nt = n - t0;
+        std::vector<uint64_t> so(offs.begin() + t0, offs.end()), dof(nt);
+        std::vector<uint32_t> ss(sizes.begin() + t0, sizes.end());
+        uint64_t at = 0;
+        for (uint32_t i = 0; i < nt; i++) { dof[i] = at; at += zsmi_compressBound(ss[i]); }
+        if (!c->dTrArena.reserve(at + 64) || !c->dTrSizes.reserve(sizeof(uint32_t) * (size_t)nt * nc + 64)) return ZSMI_error_memory_allocation;
+        for (uint32_t i = 0; i < nc; i++) {
+            ZsCompressDict dict; dict.contentSize = cap32 - hTails[i];
+            uint32_t *dSizes = (uint32_t *)c->dTrSizes.p + (size_t)nt * i;
+            if (const int e = compressBatchDeviceImpl(c, dSamples, so.data(), ss.data(), nt, c->dTrArena.p, dof.data(), dSizes, t.level,
+                                                      dict.contentSize ? hc[i].content + hTails[i] : nullptr, dict.contentSize ? &dict : nullptr)) return e;
+        }
+        std::vector<uint32_t> hs((size_t)nt * nc);
+        if (hipMemcpyAsync(hs.data(), c->dTrSizes.p, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        uint64_t bestTotal = ~0ull;
+        for (uint32_t i = 0; i < nc; i++) {
+            uint64_t sum = 0;
+            for (uint32_t j = 0; j < nt; j++) { const uint32_t v = hs[(size_t)nt * i + j]; if (v > 0xFFFFFF88u) return 0u - v; sum += v; }
+            const bool better = sum < bestTotal || (sum == bestTotal && (hc[i].k < hc[win].k || (hc[i].k == hc[win].k && hc[i].d < hc[win].d)));
+            if (better) { bestTotal = sum; win = i; }
+        }
+    }
+    params->k = hc[win].k; params->d = hc[win].d;
+    const uint32_t contentSize = cap32 - hTails[win];
+    if (contentSize < kTrainContentMin) return ZSMI_error_srcSize_wrong;
+    if (!c->dTrOut.reserve(cap32 + 64)) return ZSMI_error_memory_allocation;
+    uint32_t *dResult = dTails + win;                                       // (its tail is read already)
+    if (const int e = finalizeQueue(c, dSamples, offs, sizes, hc[win].content + hTails[win], contentSize, cap32, t.level, params->dictID, (uint8_t *)c->dTrOut.p, dResult)) return e;
+    uint32_t size = 0;
+    if (hipMemcpyAsync(&size, dResult, sizeof size, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (!size) return ZSMI_error_dstSize_tooSmall;
+    if (hipMemcpy(hostDict, c->dTrOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_error_GENERIC;
+    *dictSize = size;
+    return 0;
+}
+
+// host samples -> the context's device copy
+static int trainStageHost(zsmi_ctx *c, const void *samples, const size_t *samplesSizes, unsigned nb, std::vector<uint32_t> &sizes)
+{
+    uint64_t total = 0;
+    sizes.resize(nb);
+    for (unsigned i = 0; i < nb; i++) { if (samplesSizes[i] > 0xFFFFFFFFull) return ZSMI_error_srcSize_wrong; sizes[i] = (uint32_t)samplesSizes[i]; total += samplesSizes[i]; }
+    if (total >= (1ull << 32)) return ZSMI_error_srcSize_wrong;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (!c->dTrSamples.reserve(total + 64)) return ZSMI_error_memory_allocation;
+    if (hipMemsetAsync((uint8_t *)c->dTrSamples.p + total, 0, 64, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    return hipMemcpyAsync(c->dTrSamples.p, samples, total, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+
+extern "C" size_t zsmi_trainFromBuffer_fastCover(void *dictBuffer, size_t dictCapacity, const void *samplesBuffer, const size_t *samplesSizes,
+                                                 unsigned nbSamples, zsmi_fastCoverParams *params)
+{
+    uint64_t total = 0;
+    for (unsigned i = 0; i < nbSamples; i++) total += samplesSizes[i];
+    { TrainPlan t; if (const int e = trainParams(params, dictCapacity, total, nbSamples, t)) return ZSMI_ERR(e); }
+    Borrowed b; zsmi_ctx *c = b.c;
+    if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
+    std::vector<uint32_t> sizes;
+    if (const int e = trainStageHost(c, samplesBuffer, samplesSizes, nbSamples, sizes)) return ZSMI_ERR(e);
+    std::vector<uint8_t> tmp(dictCapacity);                                  // nothing reaches the caller's buffer unless the call succeeds
+    zsmi_fastCoverParams p = *params;
+    size_t size = 0;
+    if (const int e = trainImpl(c, (const uint8_t *)c->dTrSamples.p, sizes, tmp.data(), dictCapacity, &p, &size)) return ZSMI_ERR(e);
+    memcpy(dictBuffer, tmp.data(), size);
+    params->k = p.k; params->d = p.d;
+    return size;
+}
+
+extern "C" size_t zsmi_trainFromBuffer(void *dictBuffer, size_t dictCapacity, const void *samplesBuffer, const size_t *samplesSizes, unsigned nbSamples)
+{
+    zsmi_fastCoverParams p;
+    memset(&p, 0, sizeof p);
+    p.d = 8; p.steps = 4; p.splitPoint = 0.75; p.level = 3;
+    return zsmi_trainFromBuffer_fastCover(dictBuffer, dictCapacity, samplesBuffer, samplesSizes, nbSamples, &p);
+}
+
+extern "C" int zsmi_trainFromDevice(zsmi_ctx *c, const void *dSamples, const uint64_t *sampleOffsets, const uint32_t *sampleSizes, uint32_t nbSamples,
+                                    void *dictBuffer, size_t dictCapacity, zsmi_fastCoverParams *params, size_t *dictSize)
+{
+    if (!c) return ZSMI_error_init_missing;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nbSamples; i++) total += sampleSizes[i];
+    { TrainPlan t; if (const int e = trainParams(params, dictCapacity, total, nbSamples, t)) return e; }
+    if (!dictSize || !dSamples) return ZSMI_error_GENERIC;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    // the samples back to back in the context's buffer (one gather launch)
+    if (!c->dTrSamples.reserve(total + 64) || !c->dTrGather.reserve(sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples) ||
+        !c->hTrCand.reserve(sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples)) return ZSMI_error_memory_allocation;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    uint64_t *ho = (uint64_t *)c->hTrCand.p;
+    uint32_t *hs = (uint32_t *)(ho + 2 * (size_t)nbSamples);
+    std::vector<uint32_t> sizes(sampleSizes, sampleSizes + nbSamples);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < nbSamples; i++) { ho[i] = sampleOffsets[i]; ho[nbSamples + i] = at; hs[i] = sampleSizes[i]; at += sampleSizes[i]; }
+    if (hipMemcpyAsync(c->dTrGather.p, ho, sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipMemsetAsync((uint8_t *)c->dTrSamples.p + total, 0, 64, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    LAUNCH(c, "k_train_gather", k_train_gather, dim3(nbSamples), dim3(256), 0, (const uint8_t *)dSamples, (const uint64_t *)c->dTrGather.p,
+           (const uint32_t *)((const uint64_t *)c->dTrGather.p + 2 * (size_t)nbSamples), nbSamples, (uint8_t *)c->dTrSamples.p);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;      // (the pinned offsets are reused below)
+    std::vector<uint8_t> tmp(dictCapacity);
+    zsmi_fastCoverParams p = *params;
+    size_t size = 0;
+    if (const int e = trainImpl(c, (const uint8_t *)c->dTrSamples.p, sizes, tmp.data(), dictCapacity, &p, &size)) return e;
+    memcpy(dictBuffer, tmp.data(), size);
+    params->k = p.k; params->d = p.d;
+    *dictSize = size;
+    return 0;
+}
+
+extern "C" size_t zsmi_finalizeDictionary(void *dst, size_t dstCapacity, const void *content, size_t contentSize, const void *samplesBuffer,
+                                          const size_t *samplesSizes, unsigned nbSamples, int level, unsigned dictID)
+{
+    if (dstCapacity < kTrainDictSizeMin) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
+    if (!content || contentSize < kTrainContentMin || contentSize > 0xFFFFFFFFull - (128u << 10) || nbSamples == 0) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
+    uint64_t total = 0;
+    for (unsigned i = 0; i < nbSamples; i++) total += samplesSizes[i];
+    if (total >= (1ull << 32)) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
+    Borrowed b; zsmi_ctx *c = b.c;
+    if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
+    std::vector<uint32_t> sizes;
+    if (const int e = trainStageHost(c, samplesBuffer, samplesSizes, nbSamples, sizes)) return ZSMI_ERR(e);
+    const uint32_t cap32 = (uint32_t)std::min<size_t>(dstCapacity, 0xFFFFFFFFu - 4096);
+    if (!c->dTrContent.reserve(contentSize) || !c->dTrOut.reserve((size_t)cap32 + 64) || !c->dTrCand.reserve(64)) return ZSMI_ERR(ZSMI_error_memory_allocation);
+    if (hipMemcpyAsync(c->dTrContent.p, content, contentSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    std::vector<uint64_t> offs(nbSamples);
+    { uint64_t at = 0; for (unsigned i = 0; i < nbSamples; i++) { offs[i] = at; at += sizes[i]; } }
+    uint32_t *dResult = (uint32_t *)c->dTrCand.p;
+    if (const int e = finalizeQueue(c, (const uint8_t *)c->dTrSamples.p, offs, sizes, (const uint8_t *)c->dTrContent.p, (uint32_t)contentSize, cap32, level ? level : 3, dictID,
+                                    (uint8_t *)c->dTrOut.p, dResult)) return ZSMI_ERR(e);
+    uint32_t size = 0;
+    if (hipMemcpyAsync(&size, dResult, sizeof size, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (!size) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
+    if (hipMemcpy(dst, c->dTrOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    return size;
+}

@@ -3,6 +3,7 @@
 // in this library: every compress/decompress call launches the gfx950 kernels or fails.
 //
 // Single translation unit: the kernel sources are included so that launches and kernels share one code object.
+#include <hipcub/hipcub.hpp>            // (dict_train.hip: the radix sort of its d-mer keys)
 #include "lz_kernels.hip"
 #include "entropy_kernels.hip"
 #include "decode_kernels.hip"
@@ -162,6 +163,10 @@ struct zsmi_ctx {
     // the error word), a partial first / last frame's decoded bytes, the verify list
     DevBuf dSeekStage, dSeekMeta, dSeekDec;
     PinBuf hSeek;
+    // dictionary training (dict_train.hip): the samples back to back, sort keys, per-position hash / links (d = 6, 8), base and per-candidate
+    // frequency tables, candidate contents and list, compressed sizes and frames of the scoring / statistics calls, stats + header scratch, the result
+    DevBuf dTrSamples, dTrGather, dTrEnds, dTrKeys, dTrKeysOut, dTrSortTmp, dTrInfo[2], dTrFreqBase, dTrFreq, dTrContent, dTrCand, dTrArena, dTrSizes, dTrMisc, dTrOut;
+    PinBuf hTrCand;
     // timing
     int timing = 0;                      // 1: events around every launch; 2: only around the dominant kernels (k_lz_walk*, k_dec_execute)
     std::vector<TimedLaunch> launches;
@@ -539,13 +544,16 @@ static int buildPlan(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *sr
     }
     return 0;
 }
+// finalize statistics of a sub-batch (dict_train.hip); launched only when a call asks for them
+__global__ void k_train_stats(const uint8_t *src, const ZsBlockDesc *blocks, const ZsSeqRec *seqAll, const ZsRangeHdr *hdrAll, const uint8_t *litsAll, uint32_t *stats);
 // dict (dictionary calls): parsed on the host (parseCompressDict), dDict its bytes in device memory.  Chunks of <= 64 KiB are PREFIXED
 // units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the last <= 64 KiB of the content); the units of longer chunks are
 // parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
-// A call without a dictionary is one with no prefixed units.
+// A call without a dictionary is one with no prefixed units.  dStats (the dictionary trainer's finalize; nullptr on every other path): device
+// counters of the literal bytes and LL / OF / ML codes, added to by k_train_stats after each sub-batch's sequences kernel.
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const uint8_t *dDict, const ZsCompressDict *dict)
+                                   const uint8_t *dDict, const ZsCompressDict *dict, uint32_t *dStats = nullptr)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
@@ -621,12 +629,18 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
                    (const ZsBlockDesc *)c->dBlocks.p, (const ZsBlockMeta *)S.dMetas.p, (const uint8_t *)S.dLitSec.p, (const uint8_t *)S.dSeqSec.p, block0,
                    (uint8_t *)dDst, dDstSizes, chunk0, dictArgs...);
         };
+        auto stats = [&]() {                                    // (the codes it reads are in the literal buffers until the literals kernel)
+            if (dStats) LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p,
+                               (const ZsRangeHdr *)S.dHdrs.p, (const uint8_t *)S.dLits.p, dStats);
+        };
         if (dict) {
             sequences(k_encode_sequences_dict<ZS_SEQ_GROUP>, make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u));
+            stats();
             literals(k_encode_literals_dict, dict->dictID);
             if (maxChunkBlocks > 1) assemble(k_assemble_frames_dict, dict->dictID);
         } else {
             sequences(k_encode_sequences<ZS_SEQ_GROUP>);
+            stats();
             literals(k_encode_literals);
             if (maxChunkBlocks > 1) assemble(k_assemble_frames);
         }
@@ -1084,6 +1098,7 @@ extern "C" size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const
 }
 
 #include "seekable.hip"
+#include "dict_train.hip"
 
 #ifdef ZSMI_DEBUG_HOOKS
 // ---- test hook (not in include/zsmi.h): copy a scratch buffer of the last compress sub-batch to the host.
