@@ -61,15 +61,6 @@ struct ZsFastDesc {                               // per item, global memory, wr
 typedef uint64_t ZsFastSeq;
 __device__ __forceinline__ ZsFastSeq zs_fastseq(uint32_t bitPos, uint32_t symLL, uint32_t symML, uint32_t symOF)
 { return (uint64_t)(bitPos | (symLL << 20) | (symML << 26)) | ((uint64_t)symOF << 32); }
-// (the 16-bit cell format: zs_fastcell in decode_kernels.hip.)  The extra bits of a code come from the code by arithmetic
-// (LL_bits / ML_bits, ZStdInternal.cs:158,173).
-__device__ __forceinline__ void zs_fastcell_open(uint32_t c, uint32_t &next, uint32_t &nb, uint32_t &sym)
-{
-    const uint32_t p = c >> 6, hb = 31u - (uint32_t)__builtin_clz(p | 1u);
-    nb = 9u - hb; next = (p ^ (1u << hb)) << nb; sym = c & 63u;
-}
-__device__ __forceinline__ uint32_t zs_llExtraBits(uint32_t s) { return s < 16 ? 0u : (s <= 19 ? 1u : (s <= 21 ? 2u : (s <= 23 ? 3u : (s == 24 ? 4u : s - 19)))); }
-__device__ __forceinline__ uint32_t zs_mlExtraBits(uint32_t s) { return s < 32 ? 0u : (s <= 35 ? 1u : (s <= 37 ? 2u : (s <= 39 ? 3u : (s <= 41 ? 4u : (s == 42 ? 5u : s - 36))))); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_dec_prep

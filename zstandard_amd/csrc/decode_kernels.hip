@@ -109,45 +109,6 @@ __device__ __forceinline__ uint32_t rd16(const uint8_t *p) { return (uint32_t)p[
 __device__ __forceinline__ uint32_t rd24(const uint8_t *p) { return rd16(p) | ((uint32_t)p[2] << 16); }
 __device__ __forceinline__ uint32_t rd32(const uint8_t *p) { return zs_load32(p); }
 
-// ---- backward bit reader (BitStream.cs:322-494).  64-bit container here; the reference's 32-bit reload
-//      points only decide where a damaged stream is rejected, the bits read are the same. ----
-struct BitR { const uint8_t *start; uint32_t size; int64_t bitPos; /* number of unread bits below the cursor */ uint32_t err;
-              uint64_t cont; int64_t contLo; /* cont = stream bits [contLo, contLo + 64) */ };
-__device__ __forceinline__ void br_fill(BitR &b)
-{
-    // 8 bytes whose top byte holds the bit just below the cursor (or the first 8 bytes of the stream)
-    int64_t b0 = 0;
-    if (b.size >= 8) {
-        b0 = ((b.bitPos - 1) >> 3) - 7; if (b0 < 0) b0 = 0;
-        if (b0 > (int64_t)b.size - 8) b0 = (int64_t)b.size - 8;
-        b.cont = zs_load64(b.start + b0);
-    } else {
-        uint64_t w = 0;
-        for (uint32_t k = 0; k < b.size; k++) w |= (uint64_t)b.start[k] << (8 * k);
-        b.cont = w;
-    }
-    b.contLo = 8 * b0;
-}
-__device__ __forceinline__ void br_init(BitR &b, const uint8_t *src, uint32_t size)
-{
-    b.start = src; b.size = size; b.err = 0; b.bitPos = 0; b.cont = 0; b.contLo = 0;
-    if (size == 0) { b.err = 1; return; }
-    const uint32_t last = src[size - 1];
-    if (last == 0) { b.err = 1; return; }
-    b.bitPos = (int64_t)size * 8 - (int64_t)(8 - zs_highbit(last));      // bits below the end mark
-    br_fill(b);
-}
-// next n bits (n <= 32) below the cursor, most significant first; bits below the stream start read as 0
-__device__ __forceinline__ uint32_t br_look(BitR &b, uint32_t n)
-{
-    if (n == 0 || b.bitPos <= 0) return 0;
-    int64_t rel = b.bitPos - (int64_t)n - b.contLo;       // position of the lowest wanted bit inside cont
-    if (rel < 0 && b.contLo > 0) { br_fill(b); rel = b.bitPos - (int64_t)n - b.contLo; }
-    const uint64_t v = (rel >= 0) ? (b.cont >> (uint32_t)rel) : ((rel <= -64) ? 0ull : (b.cont << (uint32_t)(-rel)));
-    return (uint32_t)(v & ((n >= 32) ? 0xFFFFFFFFull : ((1ull << n) - 1)));
-}
-__device__ __forceinline__ uint32_t br_read(BitR &b, uint32_t n) { const uint32_t v = br_look(b, n); b.bitPos -= n; return v; }
-
 // ---- a header region staged in LDS (all lanes load 4 bytes each: 256 bytes, zero beyond the region), read by the serial
 //      parsers below, which run on one lane: a global load inside them is a memory round trip per few bits.
 //      (Keeping the window in registers and reading it with v_readlane inside the one-lane branch is NOT safe: register
@@ -726,32 +687,9 @@ __device__ __forceinline__ bool hufDecodeStreams(DLds &L, uint32_t nStreams, uin
     return !__ballot(bad);
 }
 
-// XXH64 seed 0 (XxHash.cs:896-1161), single lane
 __device__ static uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-__device__ static uint64_t xxh64(const uint8_t *p, uint64_t len)
-{
-    const uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL, P3 = 1609587929392839161ULL, P4 = 9650029242287828579ULL, P5 = 2870177450012600261ULL;
-    const uint8_t *const bEnd = p + len; uint64_t h64;
-    #define XXR(acc, in) { acc += (in) * P2; acc = rotl64(acc, 31); acc *= P1; }
-    if (len >= 32) {
-        const uint8_t *const limit = bEnd - 32;
-        uint64_t v1 = P1 + P2, v2 = P2, v3 = 0, v4 = 0 - P1;
-        do { XXR(v1, zs_load64(p)); p += 8; XXR(v2, zs_load64(p)); p += 8; XXR(v3, zs_load64(p)); p += 8; XXR(v4, zs_load64(p)); p += 8; } while (p <= limit);
-        h64 = rotl64(v1, 1) + rotl64(v2, 7) + rotl64(v3, 12) + rotl64(v4, 18);
-        #define XXM(v) { uint64_t t_ = 0; XXR(t_, v); h64 ^= t_; h64 = h64 * P1 + P4; }
-        XXM(v1); XXM(v2); XXM(v3); XXM(v4);
-        #undef XXM
-    } else h64 = P5;
-    h64 += len;
-    while (p + 8 <= bEnd) { uint64_t k1 = 0; XXR(k1, zs_load64(p)); h64 ^= k1; h64 = rotl64(h64, 27) * P1 + P4; p += 8; }
-    if (p + 4 <= bEnd) { h64 ^= (uint64_t)zs_load32(p) * P1; h64 = rotl64(h64, 23) * P2 + P3; p += 4; }
-    while (p < bEnd) { h64 ^= (*p) * P5; h64 = rotl64(h64, 11) * P1; p++; }
-    #undef XXR
-    h64 ^= h64 >> 33; h64 *= P2; h64 ^= h64 >> 29; h64 *= P3; h64 ^= h64 >> 32;
-    return h64;
-}
 
-// The same by FOUR lanes (a quad of the wavefront, r = lane & 3): the stripe loop is four independent accumulators, lane r runs the r-th (the 8 bytes at 8 r of
+// XXH64 seed 0 (XxHash.cs:896-1161) by FOUR lanes (a quad of the wavefront, r = lane & 3): the stripe loop is four independent accumulators, lane r runs the r-th (the 8 bytes at 8 r of
 // every 32-byte stripe), the quad's first lane merges them and finishes the tail.  Every lane of the quad must call; the result is valid in its first lane.
 // (k_dec_checksum hashed an item's whole output on one lane: 1 MiB frames are 32768 dependent rounds there.)
 // AHEAD > 1: the stripe loop loads AHEAD stripes before it folds them in (AHEAD loads a lane in flight instead of one dependent load a stripe:

@@ -198,13 +198,6 @@ __device__ __forceinline__ void zs_block_copy(uint8_t *__restrict__ d, const uin
     }
     for (uint32_t j = (n16 << 4) + tid; j < n; j += nthreads) d[j] = s[j];
 }
-// the same for one wavefront inside a kernel short of registers: one 16-byte piece a lane and round
-__device__ __forceinline__ void zs_wave_copy(uint8_t *__restrict__ d, const uint8_t *__restrict__ s, uint32_t n, uint32_t lane)
-{
-    const uint32_t n16 = n >> 4;
-    for (uint32_t i = lane; i < n16; i += 64) { const uint64_t a = zs_load64(s + 16 * i), b = zs_load64(s + 16 * i + 8); zs_store64(d + 16 * i, a); zs_store64(d + 16 * i + 8, b); }
-    for (uint32_t j = (n16 << 4) + lane; j < n; j += 64) d[j] = s[j];
-}
 
 struct BitSink {
     uint32_t *out32;
@@ -263,22 +256,6 @@ __device__ __forceinline__ uint32_t sink_close(BitSink &b)
 // ---------------------------------------------------------------------------------------------
 // lane-0 sequential pieces (small tables; scalar statement in oracle/zso_encoder.c)
 // ---------------------------------------------------------------------------------------------
-struct BitW { uint64_t acc; uint32_t nbits; uint8_t *ptr, *start, *end; int overflow; };
-__device__ static void bw_init(BitW &b, uint8_t *dst, uint32_t cap) { b.acc = 0; b.nbits = 0; b.ptr = b.start = dst; b.end = dst + cap; b.overflow = 0; }
-__device__ static void bw_add(BitW &b, uint32_t value, uint32_t nb)
-{
-    if (!nb) return;
-    b.acc |= (uint64_t)(value & ((nb >= 32) ? 0xFFFFFFFFu : ((1u << nb) - 1))) << b.nbits;
-    b.nbits += nb;
-    while (b.nbits >= 8) { if (b.ptr < b.end) *b.ptr++ = (uint8_t)b.acc; else b.overflow = 1; b.acc >>= 8; b.nbits -= 8; }
-}
-__device__ static uint32_t bw_close(BitW &b)
-{
-    bw_add(b, 1, 1);
-    if (b.nbits) { if (b.ptr < b.end) *b.ptr++ = (uint8_t)b.acc; else b.overflow = 1; b.nbits = 0; }
-    return b.overflow ? 0u : (uint32_t)(b.ptr - b.start);
-}
-
 __device__ static void normalizeCounts(int16_t *norm, uint32_t tableLog, const uint32_t *count, uint32_t total, uint32_t maxSym)
 {
     const uint32_t tableSize = 1u << tableLog;

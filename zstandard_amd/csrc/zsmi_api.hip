@@ -117,6 +117,7 @@ typedef Buf<devAlloc, hipFree> DevBuf;
 typedef Buf<pinAlloc, hipHostFree> PinBuf;
 
 struct TimedLaunch { const char *name; hipEvent_t a, b; };
+struct DecodePlan;
 
 struct zsmi_ctx {
     int device = 0;
@@ -146,16 +147,24 @@ struct zsmi_ctx {
     PinBuf hUnitsDict; DevBuf dUnitsDict, dDictImg;
     std::vector<uint32_t> wholeBefore, tailBefore;
     uint32_t planDictWhole = 0; bool planDict = false;
-    // decompress workspace
-    DevBuf dItems, dLitScratch, dFastDesc, dHufTabs, dSeqTabs, dSeqOut, dSeqLists;     // decode: items, literal scratch, fast-path tables and sequences, the blocks of each table class
+    // decompress workspace: the item list (on the host: two pinned buffers taken in turn) and the scratch of a sub-batch, whose sizes for a
+    // call's plan are stated once, in the decompress section (DecodeScratch::each)
+    DevBuf dItems;
+    PinBuf hItems2[2]; hipEvent_t hItemsEv[2] = { nullptr, nullptr }; bool hItemsBusy[2] = { false, false }; uint32_t decodeCalls = 0;
+    struct DecodeScratch {
+        DevBuf dPoolLit;                                                 // the general kernel's literal buffers: one per wavefront of its pool
+        DevBuf dLitScratch, dFastDesc, dHufTabs, dSeqTabs, dSeqOut;      // the fast path's block slots: literals, descriptors, tables, sequences
+        DevBuf dSeqLists;                                                // the general kernel's queue, the blocks of each table class, the items left (DecLists)
+        template <class F> void each(const DecodePlan &p, F f);
+        size_t held();
+        bool reserve(const DecodePlan &p);
+    } dec;
     bool decodeFast = true;              // ZSMI_DEC_FAST=0: general kernel only
-    uint32_t maxItemsInFlight = 65536;   // ZSMI_ITEMS_IN_FLIGHT: items per decode launch (scratch: ~263 KiB per item and block slot, one slot unless an item can hold two 64 KiB blocks; cut down to half the free device memory).
+    uint32_t maxItemsInFlight = 65536;   // ZSMI_ITEMS_IN_FLIGHT: items per decode launch (cut down when the scratch does not fit: planDecode).
                                          // Every decode kernel is a long dependent chain per item: a launch is one to three rounds of workgroups and its
                                          // last round is mostly tail, so big launches pay (16384 frames of 32 KiB: 82 GiB/s, 57344: 104 GiB/s)
-    PinBuf hItems2[2]; hipEvent_t hItemsEv[2] = { nullptr, nullptr }; bool hItemsBusy[2] = { false, false }; uint32_t decodeCalls = 0;    // the decode item list: two pinned buffers taken in turn
-    DevBuf dPoolLit;                         // the general decode kernel's literal buffers: one per wavefront of its pool
     uint32_t cus = 256;                      // compute units of the device (rounds of workgroups a launch takes)
-    uint32_t decodePool = 3072;              // wavefronts of that pool (ZSMI_DEC_POOL): the chip holds 10 a CU x 256
+    uint32_t decodePool = 3072;              // wavefronts of the general decode kernel's pool (ZSMI_DEC_POOL): the chip holds 10 a CU x 256
     // staging for host-buffer calls
     DevBuf sSrc, sDst, sSizes, sDict, sPack, sPackOff;
     PinBuf hPack;
@@ -673,15 +682,121 @@ extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc,
 // ---------------------------------------------------------------------------------------------
 // decompress
 // ---------------------------------------------------------------------------------------------
-static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                     uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
-                                     const void *dDict, uint32_t dictSize)
+// A call runs in sub-batches of `cap` items, one after the other through one scratch set.  The fast path (decode_fast.hip: items that are one
+// frame of up to ZS_FAST_MAXBLOCKS blocks) runs k_dec_prep -> entropy stage -> k_dec_execute -> k_dec_checksum -> k_dec_collect; then the general
+// kernel (decode_kernels.hip) takes what the fast path left, or every item when it does not run.
+//
+// Scratch.  The general kernel's wavefronts form a POOL with a literal buffer each (ZS_DEC_LITBUF = 128 KiB + 64; as many as the chip holds at once),
+// whatever the call's size.  The fast path keeps per-block scratch in slot = block index * cap + item, sized by the CALL'S LARGEST CAPACITY:
+//   literal bytes a slot:  min(capacity, 128 KiB) + 64        (a block regenerates no more than its item may hold)
+//   sequences a slot:      min(capacity, 128 KiB) / 3 + 64    (a sequence copies >= 3 bytes), 8 bytes each
+//   + Huffman table 4 KiB + sequence tables 2.5 KiB + a descriptor                     -> 32 KiB items: ~125 KiB an item (round 3: 263 KiB whatever the capacity)
+// A block that wants more than its slot holds cannot fit its item's capacity: k_dec_prep leaves it to the general kernel, which reports it.
+struct DecodePlan {
+    bool fast;                                        // the fast path runs: not under ZSMI_DEC_FAST=0, not for a dictionary call (frames that name one go to the general kernel)
+    uint32_t maxBlocks, descSlots;                    // block slots an item; descriptors an item (>= 2)
+    uint32_t blockCap, litStride, litCap, seqCap;     // a slot: the bytes its block may regenerate, its literal stride and bytes, its sequences
+    uint32_t pool, cap;                               // wavefronts of the general kernel's pool (whole workgroups); items in flight
+};
+// dSeqLists, in 32-bit words (slots = cap * maxBlocks; "-": unused):
+//   [queue][left count][-][-][class count 0][class count 1][class list 0: slots][class list 1: slots][-][-][left list: cap]
+// k_dec_prep, k_dec_sequences and k_dec_entropy are handed the words from kClassCounts on and index them themselves (decode_fast.hip: k_dec_prep's
+// seqLists[cls] and seqLists[2 + cls * cap * maxBlocks + at]; zs_dec_sequences_body's seqLists[LOG9 ? 1 : 0] and seqLists + 2 + (LOG9 ? cap * nBlk : 0)).
+// k_dec_collect fills the left list and its count; k_decode_frames takes the queue, the count and the list (decode_kernels.hip).  Without the fast
+// path only the queue and the left count are used.
+struct DecLists {
+    static constexpr size_t kQueue = 0, kLeftCount = 1, kClassCounts = 4, kClassLists = kClassCounts + 2;   // (the fast path zeroes every word in front of kClassLists)
+    static size_t leftList(size_t slots) { return kClassLists + 2 * slots + 2; }
+};
+// Every decode scratch buffer and its bytes for a plan: the one statement of the sizes, which the budget (planDecode), the reservation and
+// zsmi_decodeScratchBytes go through.  0: a buffer the plan does not use (the fast path's, on a call without it), left as it is.
+template <class F>
+void zsmi_ctx::DecodeScratch::each(const DecodePlan &p, F f)
 {
-    if (!c) return ZSMI_error_init_missing;
-    if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    // the item list travels through one of two pinned buffers: a call waits only for the copy that last read the buffer it is about to fill
-    // (two calls back), not for the device to finish the call before it (round 3 began every call with hipStreamSynchronize)
+    const size_t items = p.fast ? p.cap : 0, slots = items * p.maxBlocks;
+    f(dPoolLit, (size_t)p.pool * ZS_DEC_LITBUF);
+    f(dLitScratch, slots * p.litStride);
+    f(dFastDesc, items * p.descSlots * sizeof(ZsFastDesc));
+    f(dHufTabs, slots * ZS_FAST_HUFTAB_BYTES);
+    f(dSeqTabs, slots * ZS_FAST_SEQTAB_BYTES);
+    f(dSeqOut, slots * p.seqCap * sizeof(ZsFastSeq));
+    f(dSeqLists, (DecLists::leftList(slots) + items) * sizeof(uint32_t));
+}
+size_t zsmi_ctx::DecodeScratch::held() { size_t s = 0; each(DecodePlan(), [&](DevBuf &b, size_t) { s += b.cap; }); return s; }
+// give back what an earlier, larger call left behind: a buffer more than twice (and 256 MiB) beyond this call's need is released first
+bool zsmi_ctx::DecodeScratch::reserve(const DecodePlan &p)
+{
+    bool ok = true;
+    each(p, [&](DevBuf &b, size_t need) { if (ok && need) { if (b.cap > 2 * need + ((size_t)256 << 20)) b.release(); ok = b.reserve(need); } });
+    return ok;
+}
+
+// The plan of a call.  Block slots per item: 1; 2 when some item can hold more than one 64 KiB block; up to ZS_FAST_MAXBLOCKS when at least a
+// quarter of the call's items can hold more than two (a call of large frames; a few large frames among many small ones go to the general kernel,
+// so the small ones do not pay for slots and launches they do not use).
+// The budget: a call whose buffers all fit asks the runtime nothing (the one-shot path).  When any buffer must grow, the scratch gets half of the
+// free device memory and of what the context holds: first the slots per item go back to 2 and 1, then the items in flight are cut down (never
+// below one sub-batch of 64, never above n).
+static DecodePlan planDecode(zsmi_ctx *c, const uint32_t *dstCaps, uint32_t n, bool useDict)
+{
+    DecodePlan p;
+    p.fast = c->decodeFast && !useDict; p.maxBlocks = 1;
+    uint32_t bigItems = 0, needBlocks = 1, maxCapBytes = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t nb = (uint32_t)(((uint64_t)dstCaps[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX);
+        maxCapBytes = std::max(maxCapBytes, dstCaps[i]);
+        if (nb > 1) p.maxBlocks = 2;
+        if (nb > 2) { bigItems++; needBlocks = std::max(needBlocks, std::min<uint32_t>(nb, ZS_FAST_MAXBLOCKS)); }
+    }
+    if (bigItems && (uint64_t)bigItems * 4 >= n) p.maxBlocks = needBlocks;
+    p.descSlots = std::max(2u, p.maxBlocks);
+    p.blockCap = std::min<uint32_t>(std::max<uint32_t>(maxCapBytes, 64u), 1u << 17);
+    p.litStride = ((p.blockCap + 63u) & ~63u) + 64u; p.litCap = p.litStride - 64u;
+    p.seqCap = std::min<uint32_t>(ZS_FAST_MAXSEQ, ((p.blockCap / 3u + 64u) & ~63u));
+    p.pool = std::min<uint32_t>(std::max<uint32_t>(n, 1u), c->decodePool);
+    p.pool = ((p.pool + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP) * ZS_DEC_GROUP;
+    p.cap = std::min<uint32_t>(n, c->maxItemsInFlight);
+    zsmi_ctx::DecodeScratch &S = c->dec;
+    bool grow = false;
+    S.each(p, [&](DevBuf &b, size_t need) { grow |= need > b.cap; });
+    size_t freeB = 0, totalB = 0;
+    if (p.fast && grow && hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+        const size_t budget = (freeB + S.held()) / 2;                 // (what the context holds already counts as available)
+        auto bytesAt = [&](uint32_t items) { DecodePlan q = p; q.cap = items; size_t s = 0; S.each(q, [&](DevBuf &, size_t need) { s += need; }); return s; };
+        while (p.maxBlocks > 1 && bytesAt(std::min(p.cap, 64u)) > budget) { p.maxBlocks = p.maxBlocks > 2 ? 2 : 1; p.descSlots = std::max(2u, p.maxBlocks); }
+        const size_t fixed = bytesAt(0), perItem = bytesAt(1) - fixed;      // (the bytes grow linearly with the items)
+        if (bytesAt(p.cap) > budget)
+            p.cap = (uint32_t)std::min<size_t>(p.cap, std::max<size_t>(std::min(64u, n), budget > fixed ? (budget - fixed) / perItem : 0));
+    }
+    return p;
+}
+
+// The launch shapes of a sub-batch of cnt items, chosen by its size
+struct DecodeShape { bool fused; uint32_t executeWaves, poolWgs; };     // executeWaves: k_dec_execute<4, 6, 7 or 8>
+static DecodeShape decodeShape(const DecodePlan &p, uint32_t cnt, uint32_t cus)
+{
+    DecodeShape s;
+    // One launch for the four entropy kernels, or one each?  Both are rounds of workgroups of an item's chain each: fused, a CU holds 4 workgroups of
+    // the 37 KiB image and a round is 2 CUs' worth of Huffman AND sequence groups (8192 items on 256 CUs, ~0.48 ms); apart, 5 workgroups of 30 KiB and
+    // a round of each kind is 20480 items (~0.55 ms, twice).  The fewer round-milliseconds win - measured over 8192 .. 65536 frames of 32 KiB: fused
+    // below 20480 items except right at it, at 22528 .. 32768 (4.42 against 4.64 ms at 28672) and 49152; apart at 20480, 36864 .. 45056, 53248 .. 61440.
+    // Items of several blocks (128 KiB frames: 64 KiB blocks, the 2.5 KiB table class at 16 a wavefront) keep the separate launches: 8192 two-block
+    // frames of text decoded at 100 GiB/s fused against 135 apart.
+    const uint32_t vcnt = cnt * p.maxBlocks, perF = 32u * cus, perS = 80u * cus;     // (item, block) pairs: what a launch's rounds of workgroups count
+    s.fused = p.maxBlocks == 1 && ((vcnt + perF - 1) / perF) * 48u < 2u * ((vcnt + perS - 1) / perS) * 55u;
+    // one-block items: 7 wavefronts a SIMD (decode_fast.hip) - but a call that fits ONE round of wavefronts at 8 a SIMD and not at 7 (7169 .. 8192 items on 256 CUs)
+    // takes the 8 form: a round of it is ~12 % longer (64 VGPRs: more spills), one round instead of two is not (8192 frames: execute 0.67 -> 0.59 ms; at every
+    // other size measured, 4096 .. 57344, the 7 form is as fast or faster)
+    const bool oneRoundAt8 = cnt > 7u * 4u * cus && cnt <= 8u * 4u * cus;
+    s.executeWaves = p.maxBlocks > 1 ? 6 : (oneRoundAt8 ? 8 : 7);
+    s.poolWgs = std::min<uint32_t>((cnt + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP, p.pool / ZS_DEC_GROUP);      // (a workgroup takes ZS_DEC_GROUP items)
+    return s;
+}
+
+// the item list travels through one of two pinned buffers: a call waits only for the copy that last read the buffer it is about to fill
+// (two calls back), not for the device to finish the call before it (round 3 began every call with hipStreamSynchronize)
+static int uploadDecodeItems(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, const uint32_t *dstCaps)
+{
     const int hb = (int)(c->decodeCalls++ & 1u);
     PinBuf &hItems = c->hItems2[hb];
     if (c->hItemsBusy[hb]) { if (hipEventSynchronize(c->hItemsEv[hb]) != hipSuccess) return ZSMI_error_GENERIC; c->hItemsBusy[hb] = false; }
@@ -691,125 +806,71 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
     if (hipMemcpyAsync(c->dItems.p, hi, sizeof(ZsDecItem) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     if (hipEventRecord(c->hItemsEv[hb], c->stream) != hipSuccess) { (void)hipStreamSynchronize(c->stream); return ZSMI_error_GENERIC; }   // (the buffer is idle after that)
     c->hItemsBusy[hb] = true;
+    return 0;
+}
+
+static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                     uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
+                                     const void *dDict, uint32_t dictSize)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (n == 0) return 0;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = uploadDecodeItems(c, srcOffsets, srcSizes, n, dstOffsets, dstCaps)) return e;
     const bool useDict = dDict != nullptr && dictSize != 0;
-    const bool fast = c->decodeFast && !useDict;                  // frames that name a dictionary go to the general kernel
-    // Scratch.  The general kernel's wavefronts form a POOL with a literal buffer each (ZS_DEC_LITBUF = 128 KiB + 64; as many as the chip holds at once),
-    // whatever the call's size.  The fast path keeps per-block scratch in slot = block index * cap + item, sized by the CALL'S LARGEST CAPACITY:
-    //   literal bytes a slot:  min(capacity, 128 KiB) + 64        (a block regenerates no more than its item may hold)
-    //   sequences a slot:      min(capacity, 128 KiB) / 3 + 64    (a sequence copies >= 3 bytes), 8 bytes each
-    //   + Huffman table 4 KiB + sequence tables 2.5 KiB + a descriptor                     -> 32 KiB items: ~125 KiB an item (round 3: 263 KiB whatever the capacity)
-    // A block that wants more than its slot holds cannot fit its item's capacity: k_dec_prep leaves it to the general kernel, which reports it.
-    // Block slots per item: 1; 2 when some item can hold more than one 64 KiB block; up to ZS_FAST_MAXBLOCKS when at least a quarter of the
-    // call's items can hold more than two (a call of large frames; a few large frames among many small ones go to the general kernel, so the
-    // small ones do not pay for slots and launches they do not use).  If the scratch does not fit half of the free device memory, first the
-    // slots per item go back to 2 and 1, then the items in flight are cut down (never below one sub-batch of 64, never above n).
-    uint32_t maxBlocks = 1, bigItems = 0, needBlocks = 1, maxCapBytes = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t nb = (uint32_t)(((uint64_t)dstCaps[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX);
-        maxCapBytes = std::max(maxCapBytes, dstCaps[i]);
-        if (nb > 1) maxBlocks = 2;
-        if (nb > 2) { bigItems++; needBlocks = std::max(needBlocks, std::min<uint32_t>(nb, ZS_FAST_MAXBLOCKS)); }
-    }
-    if (bigItems && (uint64_t)bigItems * 4 >= n) maxBlocks = needBlocks;
-    const uint32_t blockCap = std::min<uint32_t>(std::max<uint32_t>(maxCapBytes, 64u), 1u << 17);
-    const uint32_t litStride = ((blockCap + 63u) & ~63u) + 64u, litCap = litStride - 64u;
-    const uint32_t seqCap = std::min<uint32_t>(ZS_FAST_MAXSEQ, ((blockCap / 3u + 64u) & ~63u));
-    uint32_t pool = std::min<uint32_t>(std::max<uint32_t>(n, 1u), c->decodePool);
-    pool = ((pool + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP) * ZS_DEC_GROUP;
-    uint32_t cap = std::min<uint32_t>(n, c->maxItemsInFlight);
-    uint32_t descSlots = std::max(2u, maxBlocks);
-    auto perItemBytes = [&](uint32_t mb) { return (size_t)std::max(2u, mb) * sizeof(ZsFastDesc) + (size_t)mb * ((size_t)litStride + ZS_FAST_HUFTAB_BYTES + ZS_FAST_SEQTAB_BYTES + (size_t)seqCap * sizeof(ZsFastSeq) + 2 * sizeof(uint32_t)) + sizeof(uint32_t); };
-    size_t perItem = fast ? perItemBytes(maxBlocks) : 0;
-    const size_t poolBytes = (size_t)pool * ZS_DEC_LITBUF;
-    {
-        const size_t have = c->dLitScratch.cap + c->dFastDesc.cap + c->dHufTabs.cap + c->dSeqTabs.cap + c->dSeqOut.cap + c->dPoolLit.cap;     // what the context holds already counts as available
-        const size_t need = (size_t)cap * perItem + poolBytes;
-        if (need > have) {                                           // (a call the buffers already hold asks the runtime nothing: the one-shot path)
-            size_t freeB = 0, totalB = 0;
-            if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-                const size_t budget = (freeB + have) / 2;
-                while (fast && maxBlocks > 1 && (size_t)std::min<uint32_t>(cap, 64u) * perItemBytes(maxBlocks) + poolBytes > budget) { maxBlocks = maxBlocks > 2 ? 2 : 1; }
-                descSlots = std::max(2u, maxBlocks); perItem = fast ? perItemBytes(maxBlocks) : 0;
-                if (perItem && (size_t)cap * perItem + poolBytes > budget) {
-                    const size_t fit = budget > poolBytes ? (budget - poolBytes) / perItem : 0;
-                    cap = (uint32_t)std::min<size_t>(cap, std::max<size_t>(std::min<uint32_t>(64u, n), fit));
-                }
-            }
-        }
-        // give back what an earlier, larger call left behind: a buffer more than twice (and 256 MiB) beyond this call's need is released first
-        auto fitBuf = [&](DevBuf &b, size_t want) { if (b.cap > 2 * want + ((size_t)256 << 20)) b.release(); return b.reserve(want); };
-        if (!fitBuf(c->dPoolLit, poolBytes)) return ZSMI_error_memory_allocation;
-        if (fast && (!fitBuf(c->dLitScratch, (size_t)cap * maxBlocks * litStride) || !fitBuf(c->dFastDesc, (size_t)cap * descSlots * sizeof(ZsFastDesc)) ||
-                     !fitBuf(c->dHufTabs, (size_t)cap * maxBlocks * ZS_FAST_HUFTAB_BYTES) || !fitBuf(c->dSeqTabs, (size_t)cap * maxBlocks * ZS_FAST_SEQTAB_BYTES) ||
-                     !fitBuf(c->dSeqOut, (size_t)cap * maxBlocks * seqCap * sizeof(ZsFastSeq)) || !fitBuf(c->dSeqLists, (8 + 2 * (size_t)cap * maxBlocks + cap) * sizeof(uint32_t)))) return ZSMI_error_memory_allocation;
-        if (!fast && !c->dSeqLists.reserve(8 * sizeof(uint32_t))) return ZSMI_error_memory_allocation;
-    }
-    for (uint32_t i0 = 0; i0 < n; i0 += cap) {
-        const uint32_t cnt = std::min(cap, n - i0);
+    const DecodePlan p = planDecode(c, dstCaps, n, useDict);
+    zsmi_ctx::DecodeScratch &S = c->dec;
+    if (!S.reserve(p)) return ZSMI_error_memory_allocation;
+    const uint8_t *src = (const uint8_t *)dSrc;
+    const uint32_t mb = p.maxBlocks;
+    ZsFastDesc *dD = (ZsFastDesc *)S.dFastDesc.p;
+    uint32_t *lists = (uint32_t *)S.dSeqLists.p, *classes = lists + DecLists::kClassCounts, *leftCount = lists + DecLists::kLeftCount;
+    for (uint32_t i0 = 0; i0 < n; i0 += p.cap) {
+        const uint32_t cnt = std::min(p.cap, n - i0);
         const ZsDecItem *dI = (const ZsDecItem *)c->dItems.p + i0;
-        const uint32_t *doneFlags = nullptr;
-        if (fast) {
-            // items that are one frame with one compressed block: entropy decoding lane-parallel across 16 items per wavefront
-            // (decode_fast.hip); whatever those kernels do not take or reject is left to the general kernel below
-            ZsFastDesc *dD = (ZsFastDesc *)c->dFastDesc.p;
-            const uint32_t groups = (cnt + ZS_FAST_GROUP - 1) / ZS_FAST_GROUP;
-            uint32_t *dLists = (uint32_t *)c->dSeqLists.p + 4;            // [0], [1]: blocks listed per sequence-table class; then the two lists.  (In front of them: the general kernel's queue)
-            if (hipMemsetAsync(c->dSeqLists.p, 0, 6 * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-            LAUNCH(c, "k_dec_prep", (k_dec_prep<ZS_DEC_GROUP>), dim3((cnt + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP), dim3(64 * ZS_DEC_GROUP), 0, (const uint8_t *)dSrc, dI, cnt, dD,
-                   (uint8_t *)c->dHufTabs.p, (uint8_t *)c->dSeqTabs.p, cap, maxBlocks, dLists, litCap, seqCap);
-            {   // every block index of the items in one launch per kernel class (the grid: maxBlocks runs of the items' groups; a wavefront whose items
-                // have no such block leaves at once)
-                const uint32_t mb = maxBlocks, vcnt = cnt * mb;                 // (item, block) pairs: what a launch's rounds of workgroups count
-                // One launch for the four entropy kernels, or one each?  Both are rounds of workgroups of an item's chain each: fused, a CU holds 4 workgroups of
-                // the 37 KiB image and a round is 2 CUs' worth of Huffman AND sequence groups (8192 items on 256 CUs, ~0.48 ms); apart, 5 workgroups of 30 KiB and
-                // a round of each kind is 20480 items (~0.55 ms, twice).  The fewer round-milliseconds win - measured over 8192 .. 65536 frames of 32 KiB: fused
-                // below 20480 items except right at it, at 22528 .. 32768 (4.42 against 4.64 ms at 28672) and 49152; apart at 20480, 36864 .. 45056, 53248 .. 61440.
-                const uint32_t perF = 32u * c->cus, perS = 80u * c->cus;
-                const bool fuse = ((vcnt + perF - 1) / perF) * 48u < 2u * ((vcnt + perS - 1) / perS) * 55u;
-                if (fuse && mb == 1) {
-                    // a round of workgroups or less of one-block items: the four entropy launches as one (k_dec_entropy), the 2.5 KiB sequence class at 4 items a wavefront as below
-                    // (items of several blocks - 128 KiB frames: 64 KiB blocks, the 2.5 KiB table class at 16 a wavefront - keep the separate launches: 8192 two-block frames of text
-                    //  decoded at 100 GiB/s fused against 135 apart)
-                    const uint32_t gH0 = groups * mb, gH1 = ((cnt + 7) / 8) * mb, gS0 = ((cnt + ZS_FAST_SEQGROUP_SMALL - 1) / ZS_FAST_SEQGROUP_SMALL) * mb, gS1 = ((cnt + 3) / 4) * mb;
-                    LAUNCH(c, "k_dec_entropy", k_dec_entropy, dim3(gH0 + gH1 + gS0 + gS1), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dHufTabs.p, (uint8_t *)c->dLitScratch.p,
-                           (const uint8_t *)c->dSeqTabs.p, (ZsFastSeq *)c->dSeqOut.p, mb, cap, (const uint32_t *)dLists, litStride, seqCap, gH0, gH1, gS0);
-                } else {
-                    LAUNCH(c, "k_dec_huffman", (k_dec_huffman<false, ZS_FAST_GROUP>), dim3(groups * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dHufTabs.p, (uint8_t *)c->dLitScratch.p, mb, cap, litStride);
-                    LAUNCH(c, "k_dec_huffman", (k_dec_huffman<true, 8u>), dim3(((cnt + 7) / 8) * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dHufTabs.p, (uint8_t *)c->dLitScratch.p, mb, cap, litStride);
-                    LAUNCH(c, "k_dec_sequences", (k_dec_sequences<false, ZS_FAST_SEQGROUP_SMALL>), dim3(((cnt + ZS_FAST_SEQGROUP_SMALL - 1) / ZS_FAST_SEQGROUP_SMALL) * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dSeqTabs.p, (ZsFastSeq *)c->dSeqOut.p, mb, cap, (const uint32_t *)dLists, seqCap, 0u, 0xFFFFFFFFu);
-                    // the 2.5 KiB table class (blocks of > 2048 sequences: sources, tables, binaries at 32 KiB; the 64 KiB blocks of 128 KiB frames).  How many blocks of a call
-                    // are in it only the device knows (k_dec_prep's list), and it decides the shape: 16 items a wavefront when the class holds most of a large call (the
-                    // wavefront's instructions are what the kernel costs: 57344 frames of Python sources 4.00 -> 3.78 ms, of a binary table 4.99 -> 4.00), 4 a wavefront
-                    // when it is a fraction of it (libzstd's 32 KiB frames: 9 % of the blocks; fewer, emptier wavefronts finish sooner: 3.8 vs 5.2 ms) or the call is small.
-                    // Both shapes are launched; each looks at the list's length and leaves at once when the other one serves it.
-                    LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, ZS_FAST_SEQGROUP>), dim3(((cnt + ZS_FAST_SEQGROUP - 1) / ZS_FAST_SEQGROUP) * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dSeqTabs.p, (ZsFastSeq *)c->dSeqOut.p, mb, cap, (const uint32_t *)dLists, seqCap, ZS_FAST_SEQGROUP_MANY, 0xFFFFFFFFu);
-                    LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, 4u>), dim3(((cnt + 3) / 4) * mb), dim3(64), 0, (const uint8_t *)dSrc, dI, cnt, dD, (const uint8_t *)c->dSeqTabs.p, (ZsFastSeq *)c->dSeqOut.p, mb, cap, (const uint32_t *)dLists, seqCap, 0u, ZS_FAST_SEQGROUP_MANY);
-                }
+        const DecodeShape shape = decodeShape(p, cnt, c->cus);
+        uint32_t *left = nullptr;
+        if (p.fast) {
+            // items that are one frame of up to mb blocks: entropy decoding lane-parallel across 16 items per wavefront (decode_fast.hip); whatever
+            // those kernels do not take or reject is left to the general kernel below
+            if (hipMemsetAsync(lists, 0, DecLists::kClassLists * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+            LAUNCH(c, "k_dec_prep", (k_dec_prep<ZS_DEC_GROUP>), dim3((cnt + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, dD,
+                   (uint8_t *)S.dHufTabs.p, (uint8_t *)S.dSeqTabs.p, p.cap, mb, classes, p.litCap, p.seqCap);
+            // every block index of the items in one launch per kernel class (the grid: mb runs of the items' groups; a wavefront whose items have no such
+            // block leaves at once)
+            const uint32_t gH0 = ((cnt + ZS_FAST_GROUP - 1) / ZS_FAST_GROUP) * mb, gH1 = ((cnt + 7) / 8) * mb;
+            const uint32_t gS0 = ((cnt + ZS_FAST_SEQGROUP_SMALL - 1) / ZS_FAST_SEQGROUP_SMALL) * mb, gS1 = ((cnt + 3) / 4) * mb;
+            if (shape.fused) {
+                // the four entropy launches as one (k_dec_entropy), the 2.5 KiB sequence class at 4 items a wavefront as below
+                LAUNCH(c, "k_dec_entropy", k_dec_entropy, dim3(gH0 + gH1 + gS0 + gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p,
+                       (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.litStride, p.seqCap, gH0, gH1, gS0);
+            } else {
+                LAUNCH(c, "k_dec_huffman", (k_dec_huffman<false, ZS_FAST_GROUP>), dim3(gH0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride);
+                LAUNCH(c, "k_dec_huffman", (k_dec_huffman<true, 8u>), dim3(gH1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride);
+                LAUNCH(c, "k_dec_sequences", (k_dec_sequences<false, ZS_FAST_SEQGROUP_SMALL>), dim3(gS0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
+                       mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, 0xFFFFFFFFu);
+                // the 2.5 KiB table class (blocks of > 2048 sequences: sources, tables, binaries at 32 KiB; the 64 KiB blocks of 128 KiB frames).  How many blocks of a call
+                // are in it only the device knows (k_dec_prep's list), and it decides the shape: 16 items a wavefront when the class holds most of a large call (the
+                // wavefront's instructions are what the kernel costs: 57344 frames of Python sources 4.00 -> 3.78 ms, of a binary table 4.99 -> 4.00), 4 a wavefront
+                // when it is a fraction of it (libzstd's 32 KiB frames: 9 % of the blocks; fewer, emptier wavefronts finish sooner: 3.8 vs 5.2 ms) or the call is small.
+                // Both shapes are launched; each looks at the list's length and leaves at once when the other one serves it.
+                LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, ZS_FAST_SEQGROUP>), dim3(((cnt + ZS_FAST_SEQGROUP - 1) / ZS_FAST_SEQGROUP) * mb), dim3(64), 0, src, dI, cnt, dD,
+                       (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.seqCap, ZS_FAST_SEQGROUP_MANY, 0xFFFFFFFFu);
+                LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, 4u>), dim3(gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
+                       mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, ZS_FAST_SEQGROUP_MANY);
             }
-            // one-block items: 7 wavefronts a SIMD (decode_fast.hip) - but a call that fits ONE round of wavefronts at 8 a SIMD and not at 7 (7169 .. 8192 items on 256 CUs)
-            // takes the 8 form: a round of it is ~12 % longer (64 VGPRs: more spills), one round instead of two is not (8192 frames: execute 0.67 -> 0.59 ms; at every
-            // other size measured, 4096 .. 57344, the 7 form is as fast or faster)
-            const bool oneRoundAt8 = cnt > 7u * 4u * c->cus && cnt <= 8u * 4u * c->cus;
-            const auto execute = maxBlocks > 1 ? k_dec_execute<4, 6> : (oneRoundAt8 ? k_dec_execute<4, 8> : k_dec_execute<4, 7>);
-            LAUNCH(c, "k_dec_execute", execute, dim3((cnt + 3) / 4), dim3(256), 0, (const uint8_t *)dSrc, dI, cnt, dD, (ZsFastSeq *)c->dSeqOut.p,
-                   (uint8_t *)c->dLitScratch.p, (uint8_t *)dDst, dDstSizes + i0, cap, descSlots, litStride, seqCap);
+            const auto execute = shape.executeWaves == 6 ? k_dec_execute<4, 6> : (shape.executeWaves == 8 ? k_dec_execute<4, 8> : k_dec_execute<4, 7>);
+            LAUNCH(c, "k_dec_execute", execute, dim3((cnt + 3) / 4), dim3(256), 0, src, dI, cnt, dD, (ZsFastSeq *)S.dSeqOut.p,
+                   (uint8_t *)S.dLitScratch.p, (uint8_t *)dDst, dDstSizes + i0, p.cap, p.descSlots, p.litStride, p.seqCap);
             LAUNCH(c, "k_dec_checksum", k_dec_checksum, dim3((cnt + 15) / 16), dim3(64), 0, dI, cnt, (const ZsFastDesc *)dD, (const uint8_t *)dDst, dDstSizes + i0);
-            doneFlags = &dD->fast;
-        }
+            // the items the fast path did not finish, listed for the general kernel
+            left = lists + DecLists::leftList((size_t)p.cap * mb);
+            LAUNCH(c, "k_dec_collect", k_dec_collect, dim3((cnt + 255) / 256), dim3(256), 0, &dD->fast, (uint32_t)(sizeof(ZsFastDesc) / sizeof(uint32_t)), cnt, left, leftCount);
+        } else if (hipMemsetAsync(lists, 0, (DecLists::kLeftCount + 1) * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         // the general kernel: a pool of wavefronts over a queue - of every item, or (behind the fast path) of the list of the items it left
-        uint32_t *dQueue = (uint32_t *)c->dSeqLists.p, *dLeftCount = dQueue + 1, *dLeft = nullptr;
-        if (!fast && hipMemsetAsync(dQueue, 0, 2 * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        if (doneFlags) {
-            dLeft = dQueue + 8 + 2 * (size_t)cap * maxBlocks;
-            LAUNCH(c, "k_dec_collect", k_dec_collect, dim3((cnt + 255) / 256), dim3(256), 0, doneFlags, (uint32_t)(sizeof(ZsFastDesc) / sizeof(uint32_t)), cnt, dLeft, dLeftCount);
-        }
-        const uint32_t poolWgs = std::min<uint32_t>((cnt + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP, pool / ZS_DEC_GROUP);
-        if (useDict)
-            LAUNCH(c, "k_decode_frames_dict", (k_decode_frames<ZS_DEC_GROUP, true>), dim3(poolWgs), dim3(64 * ZS_DEC_GROUP), 0, (const uint8_t *)dSrc,
-                   dI, cnt, (uint8_t *)dDst, dDstSizes + i0, (uint8_t *)c->dPoolLit.p, (const uint32_t *)dLeft, (const uint32_t *)dLeftCount, (const uint8_t *)dDict, dictSize, dQueue);
-        else
-            LAUNCH(c, "k_decode_frames", (k_decode_frames<ZS_DEC_GROUP, false>), dim3(poolWgs), dim3(64 * ZS_DEC_GROUP), 0, (const uint8_t *)dSrc,
-                   dI, cnt, (uint8_t *)dDst, dDstSizes + i0, (uint8_t *)c->dPoolLit.p, (const uint32_t *)dLeft, (const uint32_t *)dLeftCount, (const uint8_t *)nullptr, 0u, dQueue);
+        LAUNCH(c, useDict ? "k_decode_frames_dict" : "k_decode_frames", useDict ? (k_decode_frames<ZS_DEC_GROUP, true>) : (k_decode_frames<ZS_DEC_GROUP, false>),
+               dim3(shape.poolWgs), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, (uint8_t *)dDst, dDstSizes + i0, (uint8_t *)S.dPoolLit.p, (const uint32_t *)left,
+               (const uint32_t *)leftCount, useDict ? (const uint8_t *)dDict : nullptr, useDict ? dictSize : 0u, lists + DecLists::kQueue);
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
@@ -1055,7 +1116,7 @@ extern "C" void zsmi_shutdown(void) { g_pool.drain(); }
 extern "C" size_t zsmi_decodeScratchBytes(zsmi_ctx *c)
 {
     if (!c) return 0;
-    return c->dPoolLit.cap + c->dLitScratch.cap + c->dFastDesc.cap + c->dHufTabs.cap + c->dSeqTabs.cap + c->dSeqOut.cap + c->dSeqLists.cap;
+    return c->dec.held();
 }
 
 extern "C" size_t zsmi_compress(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level)
@@ -1114,7 +1175,7 @@ extern "C" int zsmi_dbg_copyScratch(zsmi_ctx *c, int which, void *hostDst, size_
     if (!c) return -1;
     (void)hipStreamSynchronize(c->stream);
     zsmi_ctx::Scratch &S = c->scratch;
-    DevBuf *b = which == 0 ? &S.dDist : which == 1 ? &S.dSeqs : which == 2 ? &S.dHdrs : which == 4 ? &S.dDistHi : which == 7 ? &S.dRecs : which == 8 ? &S.dRes : which == 5 ? &c->dLitScratch : which == 9 ? &c->dHufTabs : which == 10 ? &c->dFastDesc : &S.dMetas;
+    DevBuf *b = which == 0 ? &S.dDist : which == 1 ? &S.dSeqs : which == 2 ? &S.dHdrs : which == 4 ? &S.dDistHi : which == 7 ? &S.dRecs : which == 8 ? &S.dRes : which == 5 ? &c->dec.dLitScratch : which == 9 ? &c->dec.dHufTabs : which == 10 ? &c->dec.dFastDesc : &S.dMetas;
     if (bytes > b->cap) return -2;
     return hipMemcpy(hostDst, b->p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }

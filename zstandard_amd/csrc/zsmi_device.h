@@ -47,8 +47,6 @@ struct ZsUnitDesc {
 struct ZsSeqRec { uint32_t x, y; };
 __device__ __forceinline__ uint32_t zs_rec_ll(uint32_t x) { return x & 0x7FFu; }
 __device__ __forceinline__ uint32_t zs_rec_ml(uint32_t x) { return (x >> 11) & 0x1FFFFu; }
-__device__ __forceinline__ uint32_t zs_rec_rep(uint32_t x) { return (x >> 29) & 3u; }
-__device__ __forceinline__ uint32_t zs_rec_with_rep(uint32_t x, uint32_t rep) { return (x & 0x1FFFFFFFu) | (rep << 29); }
 __device__ __forceinline__ uint32_t zs_rec_off(uint32_t x, uint32_t y) { return (y & 0xFFFFu) | (((x >> 28) & 1u) << 16); }
 __device__ __forceinline__ uint32_t zs_rec_pos(uint32_t y) { return y >> 16; }
 __device__ __forceinline__ uint32_t zs_rec_x(uint32_t ll, uint32_t ml, uint32_t off) { return ll | (ml << 11) | ((off >> 16) << 28); }
