@@ -1,10 +1,11 @@
 #!/bin/bash
 # Development aid: builds kernel-shape variants of the library as zstandard_amd/lib/var_<name>.so (they travel to the GPU box);
 # usage: tools/build_variants.sh name1:"-DX=1 -DY=2" name2:"..."   (tools/variants.sh benches them there)
+# The compile command is zstandard_amd/_lib.py's own: ZSMI_LIB_FILE names the output, ZSMI_HIPCC_FLAGS the variant's flags (part of its fingerprint).
 rm -f zstandard_amd/lib/var_*.so
 for spec in "$@"; do
     name=${spec%%:*}; flags=${spec#*:}
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC $flags -o zstandard_amd/lib/var_${name}.so zstandard_amd/csrc/zsmi_api.hip 2>&1 | grep -v 'warning: argument unused' &
+    ZSMI_LIB_FILE=$PWD/zstandard_amd/lib/var_${name}.so ZSMI_HIPCC_FLAGS="$flags" python3 -c "from zstandard_amd import _lib; _lib.build(force=True)" 2>&1 | grep -v 'warning: argument unused' &
     if (( $(jobs -r | wc -l) >= 4 )); then wait -n; fi
 done
 wait

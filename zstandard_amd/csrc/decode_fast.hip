@@ -18,8 +18,11 @@
 // kernel (k_decode_frames, same reference semantics and error codes) decodes it afterwards from scratch.  So the fast
 // path only ever has to be right about VALID frames; the error behaviour stays that of decode_kernels.hip.
 //
-// Reference functions restated: see decode_kernels.hip (same helpers: readHufTable, seqHeaders, execTile, BitC readers).
+// Reference functions restated: see decode_kernels.hip, whose routines this path shares: the error codes and isErr, ZsDecItem, DLds and the
+// constant tables, readNCount, buildSeqTableWave, readHufTableT, BitC and its readers, hufDecodeStreams, seqHeadersT, execTileT.
 #include "zsmi_device.h"
+#include "zsmi_wave.h"
+#include "decode_kernels.hip"
 
 #define ZS_FAST_HUFLOG   11u                      // Huffman tables the fast kernel holds: 2^11 entries per item
 #define ZS_FAST_MAXSEQ   16384u                   // sequences per block the fast path buffers (8 bytes each)

@@ -13,7 +13,10 @@
 // Work split inside the wavefront: headers and FSE/Huffman table parsing on lane 0 (small, serial),
 // Huffman streams on lanes 0..3 (one stream each), sequence decoding on lane 0 in tiles of 64,
 // literal and match copies by all 64 lanes.
+#ifndef ZSMI_DECODE_KERNELS_HIP         // (decode_fast.hip and seekable.hip include this file too)
+#define ZSMI_DECODE_KERNELS_HIP
 #include "zsmi_device.h"
+#include "zsmi_wave.h"
 
 // -DZS_DEC_PROFILE: cycles per phase of each item, left in the 64 spare bytes behind its literal scratch
 // (0 literals incl. Huffman table, 1 sequence tables, 2 sequence decoding, 3 sequence execution, 4 checksum, 5 whole item)
@@ -24,11 +27,6 @@
 #define PROF_T0() do {} while (0)
 #define PROF_ADD(k) do {} while (0)
 #endif
-// Synchronisation inside one item is wavefront-local.  wave_sync() orders LDS traffic between the lanes (LDS instructions of
-// a wavefront execute in issue order).  Bytes handed from lane to lane through GLOBAL memory additionally need the stores to
-// have completed before the loads are issued (loads and stores of a wavefront may complete out of order with respect to
-// each other): wave_mem_sync() waits for the outstanding vector-memory operations of the wavefront.
-__device__ __forceinline__ void wave_mem_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
 #ifdef ZS_DEC_ERRLINE                     // debugging aid: an error result carries the source line that raised it
 #define ZE(code) (0xFF000000u | (uint32_t)__LINE__)
 #else
@@ -104,10 +102,6 @@ struct DLds {
 #define PPROF(L, k) do { } while (0)
 #endif
 __device__ __forceinline__ uint32_t ofBaseOf(uint32_t sym) { return sym == 0 ? 0u : (sym == 1 ? 1u : ((1u << sym) - 3u)); }   // OF_base :1088
-
-__device__ __forceinline__ uint32_t rd16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t rd24(const uint8_t *p) { return rd16(p) | ((uint32_t)p[2] << 16); }
-__device__ __forceinline__ uint32_t rd32(const uint8_t *p) { return zs_load32(p); }
 
 // ---- a header region staged in LDS (all lanes load 4 bytes each: 256 bytes, zero beyond the region), read by the serial
 //      parsers below, which run on one lane: a global load inside them is a memory round trip per few bits.
@@ -685,54 +679,6 @@ __device__ __forceinline__ bool hufDecodeStreams(DLds &L, uint32_t nStreams, uin
     bool bad = mine && b.bitPos != 0;                  // EndOfDStream (BitStream.cs:494): every bit consumed, none over-read
     if (useX4 && __ballot(bad)) { if (bad) bad = !hufX4TailAccepts(L.huf, dtLog, src, size, n, out); }
     return !__ballot(bad);
-}
-
-__device__ static uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-
-// XXH64 seed 0 (XxHash.cs:896-1161) by FOUR lanes (a quad of the wavefront, r = lane & 3): the stripe loop is four independent accumulators, lane r runs the r-th (the 8 bytes at 8 r of
-// every 32-byte stripe), the quad's first lane merges them and finishes the tail.  Every lane of the quad must call; the result is valid in its first lane.
-// (k_dec_checksum hashed an item's whole output on one lane: 1 MiB frames are 32768 dependent rounds there.)
-// AHEAD > 1: the stripe loop loads AHEAD stripes before it folds them in (AHEAD loads a lane in flight instead of one dependent load a stripe:
-// k_seek_hash, whose quads are few and long).  AHEAD = 1 is the plain loop the decode kernels use.
-template <int AHEAD = 1>
-__device__ __forceinline__ uint64_t xxh64_quad(const uint8_t *p, uint64_t len)
-{
-    const uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL, P3 = 1609587929392839161ULL, P4 = 9650029242287828579ULL, P5 = 2870177450012600261ULL;
-    const uint32_t r = (uint32_t)zs_lane() & 3u;
-    const uint8_t *const bEnd = p + len; uint64_t h64 = P5;
-    #define XXR(acc, in) { acc += (in) * P2; acc = rotl64(acc, 31); acc *= P1; }
-    const uint64_t stripes = len >> 5;
-    if (stripes) {
-        uint64_t v = r == 0 ? P1 + P2 : (r == 1 ? P2 : (r == 2 ? 0ull : 0ull - P1));
-        const uint8_t *q = p + 8u * r;
-        uint64_t i = 0;
-        if constexpr (AHEAD > 1) {
-            for (; i + AHEAD <= stripes; i += AHEAD) {
-                uint64_t in[AHEAD];
-                #pragma unroll
-                for (int k = 0; k < AHEAD; k++) in[k] = zs_load64(q + 32 * k);
-                #pragma unroll
-                for (int k = 0; k < AHEAD; k++) XXR(v, in[k]);
-                q += 32 * AHEAD;
-            }
-        }
-        for (; i < stripes; i++) { XXR(v, zs_load64(q)); q += 32; }
-        const int base = zs_lane() & ~3;
-        uint64_t vv[4];
-        #pragma unroll
-        for (int k = 0; k < 4; k++) vv[k] = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), base + k) << 32) | (uint32_t)__shfl((int)(uint32_t)v, base + k);
-        h64 = rotl64(vv[0], 1) + rotl64(vv[1], 7) + rotl64(vv[2], 12) + rotl64(vv[3], 18);
-        #pragma unroll
-        for (int k = 0; k < 4; k++) { uint64_t t_ = 0; XXR(t_, vv[k]); h64 ^= t_; h64 = h64 * P1 + P4; }
-        p += stripes << 5;
-    }
-    h64 += len;
-    while (p + 8 <= bEnd) { uint64_t k1 = 0; XXR(k1, zs_load64(p)); h64 ^= k1; h64 = rotl64(h64, 27) * P1 + P4; p += 8; }
-    if (p + 4 <= bEnd) { h64 ^= (uint64_t)zs_load32(p) * P1; h64 = rotl64(h64, 23) * P2 + P3; p += 4; }
-    while (p < bEnd) { h64 ^= (*p) * P5; h64 = rotl64(h64, 11) * P1; p++; }
-    #undef XXR
-    h64 ^= h64 >> 33; h64 *= P2; h64 ^= h64 >> 29; h64 *= P3; h64 ^= h64 >> 32;
-    return h64;
 }
 
 struct DState { uint32_t rep[3]; uint32_t litEntropy, fseEntropy; uint32_t llRepeatOk; uint32_t hufX4; };   // hufX4: the reference built the current Huffman table for its double-symbol decoder
@@ -1330,3 +1276,5 @@ k_decode_frames(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict_
         wave_mem_sync();                                                        // the buffer and the LDS image are the next item's
     }
 }
+
+#endif

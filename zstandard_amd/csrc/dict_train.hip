@@ -1,5 +1,5 @@
-// dict_train.hip -- dictionary training on the GPU: zstd's fastCover trainer and ZDICT_finalizeDictionary (included from zsmi_api.hip after the
-// one-shot calls).
+// dict_train.hip -- dictionary training on the GPU: zstd's fastCover trainer and ZDICT_finalizeDictionary, over the batch compressor of
+// zsmi_api.hip (zsmi_ctx.h declares it).
 //
 //   frequencies  k_train_freq:    every d-mer of the training samples hashed to f bits (zstd's 6- / 8-byte multiplicative hash); the d-mers that
 //                                 lie inside their sample (8 bytes readable) are counted into a 2^f table by integer atomics (order-independent)
@@ -11,14 +11,20 @@
 //                                 segment is the first argmax.  Its d-mers' frequencies are zeroed on the device and its bytes fill the content from
 //                                 the end.  Only the content's start (one word a candidate) is read back.
 //   search       each candidate's content is a raw dictionary for the batch compressor over the held-out samples; the smallest total wins
-//   finalize     the samples compressed with the content (compressBatchDeviceImpl with a stats pointer): k_train_stats counts literal bytes and
+//   finalize     the samples compressed with the content (compressBatchDeviceImpl with a stats pointer): k_train_stats (entropy_kernels.hip) counts literal bytes and
 //                                 LL / OF / ML codes; k_train_id hashes the content (XXH64) into the dictionary ID; k_train_tables builds the
 //                                 Huffman description and the three NCounts with the encoder's routines and assembles the dictionary.
+#include <hipcub/hipcub.hpp>      // the radix sort of the d-mer keys
+#include "zsmi_wave.h"            // zs_block_copy, xxh64_quad
+#include "entropy_kernels.hip"    // k_train_stats and kTrainStatWords; the encoder's routines k_train_tables builds with (K3Lds, huffLengths,
+                                  // huffCodesAndWeights, writeHuffHeaderWave, normalizeCounts, writeNCount)
+#include "zsmi_ctx.h"
+#include <algorithm>
+
 static const uint32_t kTrainDefaultF = 20, kTrainMinF = 12, kTrainMaxF = 26;
 static const uint32_t kTrainDictSizeMin = 256, kTrainContentMin = 128;       // ZDICT_DICTSIZE_MIN, ZDICT_CONTENTSIZE_MIN
 static const uint32_t kTrainMaxZeroRun = 10;                                 // epochs in a row without a segment end the content (zstd >= 1.4.5)
 static const uint32_t kTrainThreads = 1024, kTrainPerThread = 8;            // k_train_select: window ends a thread scores per tile
-static const uint32_t kTrainStatWords = 448;                                // literal bytes [0, 256), LL codes [256, 320), OF [320, 384), ML [384, 448)
 
 struct ZsTrainCand { uint32_t k, d, pad0, pad1; uint32_t *freq; uint8_t *content; };
 
@@ -164,45 +170,6 @@ __global__ void __launch_bounds__(kTrainThreads) k_train_select(const uint2 *__r
     if (tid == 0) tails[blockIdx.x] = tail;
 }
 
-// finalize statistics of one compressed sub-batch, between k_encode_sequences and k_encode_literals: the codes the sequences kernel left in the
-// block's literal buffer (LL, OF with the recent-offset codes applied, ML; ZS_CHAIN_CODES apart), and the literal bytes - every block byte no match
-// of the block's records covers.  One workgroup a block, counts added to stats[kTrainStatWords].
-__global__ void __launch_bounds__(256) k_train_stats(const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, const ZsSeqRec *__restrict__ seqAll,
-                                                     const ZsRangeHdr *__restrict__ hdrAll, const uint8_t *__restrict__ litsAll, uint32_t *__restrict__ stats)
-{
-    __shared__ uint32_t cov[ZS_BLOCK_MAX / 32], hist[kTrainStatWords], rstart[ZS_WALK_RANGES + 1];
-    const uint32_t blk = blockIdx.x, tid = threadIdx.x;
-    const ZsBlockDesc bd = blocks[blk];
-    const uint32_t n = bd.size;
-    for (uint32_t i = tid; i < ZS_BLOCK_MAX / 32; i += 256) cov[i] = 0;
-    for (uint32_t i = tid; i < kTrainStatWords; i += 256) hist[i] = 0;
-    const ZsRangeHdr *hdr = hdrAll + (size_t)blk * ZS_WALK_RANGES;
-    if (tid == 0) { uint32_t s = 0; for (uint32_t r = 0; r < ZS_WALK_RANGES; r++) { rstart[r] = s; s += n >= 16 ? hdr[r].nseq : 0u; } rstart[ZS_WALK_RANGES] = s; }
-    __syncthreads();
-    const uint32_t nseq = rstart[ZS_WALK_RANGES];
-    const ZsSeqRec *seqBase = seqAll + (size_t)blk * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE;
-    const uint8_t *codes = litsAll + (size_t)blk * (ZS_BLOCK_MAX + 64);
-    for (uint32_t g = tid; g < nseq; g += 256) {
-        uint32_t r = 0;
-        for (uint32_t st = ZS_WALK_RANGES / 2; st >= 1; st >>= 1) if (g >= rstart[r + st]) r += st;
-        const ZsSeqRec rec = seqBase[(size_t)r * ZS_SEQ_PER_RANGE + hdr[r].first + (g - rstart[r])];
-        const uint32_t pos = zs_rec_pos(rec.y), end = min(pos + zs_rec_ml(rec.x), n);
-        for (uint32_t b = pos; b < end;) {                                  // the match's bytes in the coverage bitmap
-            const uint32_t w = b >> 5, lo = b & 31u, cnt = min(32u - lo, end - b);
-            atomicOr(&cov[w], (cnt == 32u ? 0xFFFFFFFFu : ((1u << cnt) - 1u)) << lo);
-            b += cnt;
-        }
-        atomicAdd(&hist[256 + codes[g]], 1u);
-        atomicAdd(&hist[320 + codes[ZS_CHAIN_CODES + g]], 1u);
-        atomicAdd(&hist[384 + codes[2u * ZS_CHAIN_CODES + g]], 1u);
-    }
-    __syncthreads();
-    const uint8_t *s = src + bd.srcOff;
-    for (uint32_t b = tid; b < n; b += 256) if (!((cov[b >> 5] >> (b & 31u)) & 1u)) atomicAdd(&hist[s[b]], 1u);
-    __syncthreads();
-    for (uint32_t i = tid; i < kTrainStatWords; i += 256) if (hist[i]) atomicAdd(&stats[i], hist[i]);
-}
-
 // the dictionary ID: the caller's, or XXH64(content) % ((1 << 31) - 32768) + 32768 as ZDICT derives it
 __global__ void __launch_bounds__(64) k_train_id(const uint8_t *__restrict__ content, uint32_t size, uint32_t given, uint32_t *__restrict__ id)
 {
@@ -330,10 +297,10 @@ static int trainLaunchSort(zsmi_ctx *c, uint32_t n, uint32_t f)
 {
     size_t tmp = 0;
     if (hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n, 0, 32 + (int)f, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (!c->dTrSortTmp.reserve(tmp)) return ZSMI_error_memory_allocation;
+    if (!c->train.dSortTmp.reserve(tmp)) return ZSMI_error_memory_allocation;
     TimedLaunch tl{ "radix_sort", nullptr, nullptr };
     if (c->timing == 1) { tl.a = getEvent(c); tl.b = getEvent(c); (void)hipEventRecord(tl.a, c->stream); }
-    if (hipcub::DeviceRadixSort::SortKeys(c->dTrSortTmp.p, tmp, (const uint64_t *)c->dTrKeys.p, (uint64_t *)c->dTrKeysOut.p, (int)n, 0, 32 + (int)f, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipcub::DeviceRadixSort::SortKeys(c->train.dSortTmp.p, tmp, (const uint64_t *)c->train.dKeys.p, (uint64_t *)c->train.dKeysOut.p, (int)n, 0, 32 + (int)f, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     if (c->timing == 1) { (void)hipEventRecord(tl.b, c->stream); c->launches.push_back(tl); }
     return 0;
 }
@@ -347,12 +314,12 @@ static int finalizeQueue(zsmi_ctx *c, const uint8_t *dSamples, const std::vector
     std::vector<uint64_t> dof(n);
     uint64_t at = 0;
     for (uint32_t i = 0; i < n; i++) { dof[i] = at; at += zsmi_compressBound(sizes[i]); }
-    if (!c->dTrArena.reserve(at + 64) || !c->dTrMisc.reserve(sizeof(uint32_t) * (kTrainStatWords + 8) + 1024) || !c->dTrSizes.reserve(sizeof(uint32_t) * n + 64)) return ZSMI_error_memory_allocation;
-    uint32_t *dStats = (uint32_t *)c->dTrMisc.p, *dId = dStats + kTrainStatWords;
+    if (!c->train.dArena.reserve(at + 64) || !c->train.dMisc.reserve(sizeof(uint32_t) * (kTrainStatWords + 8) + 1024) || !c->train.dSizes.reserve(sizeof(uint32_t) * n + 64)) return ZSMI_error_memory_allocation;
+    uint32_t *dStats = (uint32_t *)c->train.dMisc.p, *dId = dStats + kTrainStatWords;
     uint8_t *dHdr = (uint8_t *)(dId + 8);
     if (hipMemsetAsync(dStats, 0, sizeof(uint32_t) * kTrainStatWords, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     ZsCompressDict dict; dict.contentSize = contentSize;
-    if (const int e = compressBatchDeviceImpl(c, dSamples, offs.data(), sizes.data(), n, c->dTrArena.p, dof.data(), (uint32_t *)c->dTrSizes.p, level, dContent, &dict, dStats)) return e;
+    if (const int e = compressBatchDeviceImpl(c, dSamples, offs.data(), sizes.data(), n, c->train.dArena.p, dof.data(), (uint32_t *)c->train.dSizes.p, level, dContent, &dict, dStats)) return e;
     LAUNCH(c, "k_train_id", k_train_id, dim3(1), dim3(64), 0, dContent, contentSize, dictID, dId);
     LAUNCH(c, "k_train_tables", k_train_tables, dim3(1), dim3(256), 0, (const uint32_t *)dStats, dContent, contentSize, cap, (const uint32_t *)dId, dHdr, dOut, dResult);
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
@@ -382,38 +349,38 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
     const size_t table = (size_t)4 << t.f;
     bool needD[2] = { false, false };
     for (auto &kd : t.cands) needD[kd.second == 8] = true;
-    if (!c->dTrKeys.reserve((size_t)8 * nbDmers) || !c->dTrKeysOut.reserve((size_t)8 * nbDmers) || !c->dTrEnds.reserve(8 * (size_t)nTrain) || !c->dTrFreqBase.reserve(2 * table)) return ZSMI_error_memory_allocation;
-    for (int w = 0; w < 2; w++) if (needD[w] && !c->dTrInfo[w].reserve((size_t)8 * nbDmers)) return ZSMI_error_memory_allocation;
-    if (hipMemcpyAsync(c->dTrEnds.p, ends.data(), 8 * (size_t)nTrain, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipMemsetAsync(c->dTrFreqBase.p, 0, 2 * table, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (!c->train.dKeys.reserve((size_t)8 * nbDmers) || !c->train.dKeysOut.reserve((size_t)8 * nbDmers) || !c->train.dEnds.reserve(8 * (size_t)nTrain) || !c->train.dFreqBase.reserve(2 * table)) return ZSMI_error_memory_allocation;
+    for (int w = 0; w < 2; w++) if (needD[w] && !c->train.dInfo[w].reserve((size_t)8 * nbDmers)) return ZSMI_error_memory_allocation;
+    if (hipMemcpyAsync(c->train.dEnds.p, ends.data(), 8 * (size_t)nTrain, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipMemsetAsync(c->train.dFreqBase.p, 0, 2 * table, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     for (int w = 0; w < 2; w++) {
         if (!needD[w]) continue;
-        uint32_t *freqBase = (uint32_t *)((uint8_t *)c->dTrFreqBase.p + w * table);
-        LAUNCH(c, "k_train_freq", k_train_freq, dim3((nbDmers + 255) / 256), dim3(256), 0, dSamples, nbDmers, w ? 8u : 6u, t.f, (const uint64_t *)c->dTrEnds.p, nTrain,
-               (uint2 *)c->dTrInfo[w].p, (uint64_t *)c->dTrKeys.p, freqBase);
+        uint32_t *freqBase = (uint32_t *)((uint8_t *)c->train.dFreqBase.p + w * table);
+        LAUNCH(c, "k_train_freq", k_train_freq, dim3((nbDmers + 255) / 256), dim3(256), 0, dSamples, nbDmers, w ? 8u : 6u, t.f, (const uint64_t *)c->train.dEnds.p, nTrain,
+               (uint2 *)c->train.dInfo[w].p, (uint64_t *)c->train.dKeys.p, freqBase);
         if (const int e = trainLaunchSort(c, nbDmers, t.f)) return e;
-        LAUNCH(c, "k_train_links", k_train_links, dim3((nbDmers + 255) / 256), dim3(256), 0, (const uint64_t *)c->dTrKeysOut.p, nbDmers, (uint2 *)c->dTrInfo[w].p);
+        LAUNCH(c, "k_train_links", k_train_links, dim3((nbDmers + 255) / 256), dim3(256), 0, (const uint64_t *)c->train.dKeysOut.p, nbDmers, (uint2 *)c->train.dInfo[w].p);
     }
     // the candidates, in groups whose frequency tables fit 2 GiB
     const uint32_t nc = (uint32_t)t.cands.size();
     const uint32_t group = (uint32_t)std::max<size_t>(1, std::min<size_t>(nc, ((size_t)2 << 30) / table));
-    if (!c->dTrFreq.reserve(table * group) || !c->dTrContent.reserve((size_t)cap32 * nc) || !c->dTrCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc) ||
-        !c->hTrCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc)) return ZSMI_error_memory_allocation;
+    if (!c->train.dFreq.reserve(table * group) || !c->train.dContent.reserve((size_t)cap32 * nc) || !c->train.dCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc) ||
+        !c->train.hCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc)) return ZSMI_error_memory_allocation;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;          // (the pinned candidate list may feed an earlier copy)
-    ZsTrainCand *hc = (ZsTrainCand *)c->hTrCand.p;
-    uint32_t *dTails = (uint32_t *)((ZsTrainCand *)c->dTrCand.p + nc);
+    ZsTrainCand *hc = (ZsTrainCand *)c->train.hCand.p;
+    uint32_t *dTails = (uint32_t *)((ZsTrainCand *)c->train.dCand.p + nc);
     for (uint32_t i = 0; i < nc; i++) {
         hc[i].k = t.cands[i].first; hc[i].d = t.cands[i].second; hc[i].pad0 = hc[i].pad1 = 0;
-        hc[i].freq = (uint32_t *)((uint8_t *)c->dTrFreq.p + table * (i % group));
-        hc[i].content = (uint8_t *)c->dTrContent.p + (size_t)cap32 * i;
+        hc[i].freq = (uint32_t *)((uint8_t *)c->train.dFreq.p + table * (i % group));
+        hc[i].content = (uint8_t *)c->train.dContent.p + (size_t)cap32 * i;
     }
-    if (hipMemcpyAsync(c->dTrCand.p, hc, sizeof(ZsTrainCand) * nc, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipMemcpyAsync(c->train.dCand.p, hc, sizeof(ZsTrainCand) * nc, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     for (uint32_t g0 = 0; g0 < nc; g0 += group) {
         const uint32_t g1 = std::min(nc, g0 + group);
         for (uint32_t i = g0; i < g1; i++)
-            if (hipMemcpyAsync(hc[i].freq, (uint8_t *)c->dTrFreqBase.p + (hc[i].d == 8) * table, table, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        LAUNCH(c, "k_train_select", k_train_select, dim3(g1 - g0), dim3(kTrainThreads), 0, (const uint2 *)c->dTrInfo[0].p, (const uint2 *)c->dTrInfo[1].p, dSamples, nbDmers, cap32,
-               (const ZsTrainCand *)c->dTrCand.p + g0, dTails + g0);
+            if (hipMemcpyAsync(hc[i].freq, (uint8_t *)c->train.dFreqBase.p + (hc[i].d == 8) * table, table, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        LAUNCH(c, "k_train_select", k_train_select, dim3(g1 - g0), dim3(kTrainThreads), 0, (const uint2 *)c->train.dInfo[0].p, (const uint2 *)c->train.dInfo[1].p, dSamples, nbDmers, cap32,
+               (const ZsTrainCand *)c->train.dCand.p + g0, dTails + g0);
     }
     uint32_t *hTails = (uint32_t *)(hc + nc);
     if (hipMemcpyAsync(hTails, dTails, sizeof(uint32_t) * nc, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
@@ -425,15 +392,15 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
         std::vector<uint32_t> ss(sizes.begin() + t0, sizes.end());
         uint64_t at = 0;
         for (uint32_t i = 0; i < nt; i++) { dof[i] = at; at += zsmi_compressBound(ss[i]); }
-        if (!c->dTrArena.reserve(at + 64) || !c->dTrSizes.reserve(sizeof(uint32_t) * (size_t)nt * nc + 64)) return ZSMI_error_memory_allocation;
+        if (!c->train.dArena.reserve(at + 64) || !c->train.dSizes.reserve(sizeof(uint32_t) * (size_t)nt * nc + 64)) return ZSMI_error_memory_allocation;
         for (uint32_t i = 0; i < nc; i++) {
             ZsCompressDict dict; dict.contentSize = cap32 - hTails[i];
-            uint32_t *dSizes = (uint32_t *)c->dTrSizes.p + (size_t)nt * i;
-            if (const int e = compressBatchDeviceImpl(c, dSamples, so.data(), ss.data(), nt, c->dTrArena.p, dof.data(), dSizes, t.level,
+            uint32_t *dSizes = (uint32_t *)c->train.dSizes.p + (size_t)nt * i;
+            if (const int e = compressBatchDeviceImpl(c, dSamples, so.data(), ss.data(), nt, c->train.dArena.p, dof.data(), dSizes, t.level,
                                                       dict.contentSize ? hc[i].content + hTails[i] : nullptr, dict.contentSize ? &dict : nullptr)) return e;
         }
         std::vector<uint32_t> hs((size_t)nt * nc);
-        if (hipMemcpyAsync(hs.data(), c->dTrSizes.p, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        if (hipMemcpyAsync(hs.data(), c->train.dSizes.p, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         uint64_t bestTotal = ~0ull;
         for (uint32_t i = 0; i < nc; i++) {
             uint64_t sum = 0;
@@ -445,13 +412,13 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
     params->k = hc[win].k; params->d = hc[win].d;
     const uint32_t contentSize = cap32 - hTails[win];
     if (contentSize < kTrainContentMin) return ZSMI_error_srcSize_wrong;
-    if (!c->dTrOut.reserve(cap32 + 64)) return ZSMI_error_memory_allocation;
+    if (!c->train.dOut.reserve(cap32 + 64)) return ZSMI_error_memory_allocation;
     uint32_t *dResult = dTails + win;                                       // (its tail is read already)
-    if (const int e = finalizeQueue(c, dSamples, offs, sizes, hc[win].content + hTails[win], contentSize, cap32, t.level, params->dictID, (uint8_t *)c->dTrOut.p, dResult)) return e;
+    if (const int e = finalizeQueue(c, dSamples, offs, sizes, hc[win].content + hTails[win], contentSize, cap32, t.level, params->dictID, (uint8_t *)c->train.dOut.p, dResult)) return e;
     uint32_t size = 0;
     if (hipMemcpyAsync(&size, dResult, sizeof size, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     if (!size) return ZSMI_error_dstSize_tooSmall;
-    if (hipMemcpy(hostDict, c->dTrOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipMemcpy(hostDict, c->train.dOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_error_GENERIC;
     *dictSize = size;
     return 0;
 }
@@ -464,9 +431,9 @@ static int trainStageHost(zsmi_ctx *c, const void *samples, const size_t *sample
     for (unsigned i = 0; i < nb; i++) { if (samplesSizes[i] > 0xFFFFFFFFull) return ZSMI_error_srcSize_wrong; sizes[i] = (uint32_t)samplesSizes[i]; total += samplesSizes[i]; }
     if (total >= (1ull << 32)) return ZSMI_error_srcSize_wrong;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    if (!c->dTrSamples.reserve(total + 64)) return ZSMI_error_memory_allocation;
-    if (hipMemsetAsync((uint8_t *)c->dTrSamples.p + total, 0, 64, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    return hipMemcpyAsync(c->dTrSamples.p, samples, total, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    if (!c->train.dSamples.reserve(total + 64)) return ZSMI_error_memory_allocation;
+    if (hipMemsetAsync((uint8_t *)c->train.dSamples.p + total, 0, 64, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    return hipMemcpyAsync(c->train.dSamples.p, samples, total, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
 
 extern "C" size_t zsmi_trainFromBuffer_fastCover(void *dictBuffer, size_t dictCapacity, const void *samplesBuffer, const size_t *samplesSizes,
@@ -482,7 +449,7 @@ extern "C" size_t zsmi_trainFromBuffer_fastCover(void *dictBuffer, size_t dictCa
     std::vector<uint8_t> tmp(dictCapacity);                                  // nothing reaches the caller's buffer unless the call succeeds
     zsmi_fastCoverParams p = *params;
     size_t size = 0;
-    if (const int e = trainImpl(c, (const uint8_t *)c->dTrSamples.p, sizes, tmp.data(), dictCapacity, &p, &size)) return ZSMI_ERR(e);
+    if (const int e = trainImpl(c, (const uint8_t *)c->train.dSamples.p, sizes, tmp.data(), dictCapacity, &p, &size)) return ZSMI_ERR(e);
     memcpy(dictBuffer, tmp.data(), size);
     params->k = p.k; params->d = p.d;
     return size;
@@ -506,23 +473,23 @@ extern "C" int zsmi_trainFromDevice(zsmi_ctx *c, const void *dSamples, const uin
     if (!dictSize || !dSamples) return ZSMI_error_GENERIC;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
     // the samples back to back in the context's buffer (one gather launch)
-    if (!c->dTrSamples.reserve(total + 64) || !c->dTrGather.reserve(sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples) ||
-        !c->hTrCand.reserve(sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples)) return ZSMI_error_memory_allocation;
+    if (!c->train.dSamples.reserve(total + 64) || !c->train.dGather.reserve(sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples) ||
+        !c->train.hCand.reserve(sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples)) return ZSMI_error_memory_allocation;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    uint64_t *ho = (uint64_t *)c->hTrCand.p;
+    uint64_t *ho = (uint64_t *)c->train.hCand.p;
     uint32_t *hs = (uint32_t *)(ho + 2 * (size_t)nbSamples);
     std::vector<uint32_t> sizes(sampleSizes, sampleSizes + nbSamples);
     uint64_t at = 0;
     for (uint32_t i = 0; i < nbSamples; i++) { ho[i] = sampleOffsets[i]; ho[nbSamples + i] = at; hs[i] = sampleSizes[i]; at += sampleSizes[i]; }
-    if (hipMemcpyAsync(c->dTrGather.p, ho, sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipMemsetAsync((uint8_t *)c->dTrSamples.p + total, 0, 64, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    LAUNCH(c, "k_train_gather", k_train_gather, dim3(nbSamples), dim3(256), 0, (const uint8_t *)dSamples, (const uint64_t *)c->dTrGather.p,
-           (const uint32_t *)((const uint64_t *)c->dTrGather.p + 2 * (size_t)nbSamples), nbSamples, (uint8_t *)c->dTrSamples.p);
+    if (hipMemcpyAsync(c->train.dGather.p, ho, sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipMemsetAsync((uint8_t *)c->train.dSamples.p + total, 0, 64, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    LAUNCH(c, "k_train_gather", k_train_gather, dim3(nbSamples), dim3(256), 0, (const uint8_t *)dSamples, (const uint64_t *)c->train.dGather.p,
+           (const uint32_t *)((const uint64_t *)c->train.dGather.p + 2 * (size_t)nbSamples), nbSamples, (uint8_t *)c->train.dSamples.p);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;      // (the pinned offsets are reused below)
     std::vector<uint8_t> tmp(dictCapacity);
     zsmi_fastCoverParams p = *params;
     size_t size = 0;
-    if (const int e = trainImpl(c, (const uint8_t *)c->dTrSamples.p, sizes, tmp.data(), dictCapacity, &p, &size)) return e;
+    if (const int e = trainImpl(c, (const uint8_t *)c->train.dSamples.p, sizes, tmp.data(), dictCapacity, &p, &size)) return e;
     memcpy(dictBuffer, tmp.data(), size);
     params->k = p.k; params->d = p.d;
     *dictSize = size;
@@ -542,16 +509,16 @@ extern "C" size_t zsmi_finalizeDictionary(void *dst, size_t dstCapacity, const v
     std::vector<uint32_t> sizes;
     if (const int e = trainStageHost(c, samplesBuffer, samplesSizes, nbSamples, sizes)) return ZSMI_ERR(e);
     const uint32_t cap32 = (uint32_t)std::min<size_t>(dstCapacity, 0xFFFFFFFFu - 4096);
-    if (!c->dTrContent.reserve(contentSize) || !c->dTrOut.reserve((size_t)cap32 + 64) || !c->dTrCand.reserve(64)) return ZSMI_ERR(ZSMI_error_memory_allocation);
-    if (hipMemcpyAsync(c->dTrContent.p, content, contentSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (!c->train.dContent.reserve(contentSize) || !c->train.dOut.reserve((size_t)cap32 + 64) || !c->train.dCand.reserve(64)) return ZSMI_ERR(ZSMI_error_memory_allocation);
+    if (hipMemcpyAsync(c->train.dContent.p, content, contentSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
     std::vector<uint64_t> offs(nbSamples);
     { uint64_t at = 0; for (unsigned i = 0; i < nbSamples; i++) { offs[i] = at; at += sizes[i]; } }
-    uint32_t *dResult = (uint32_t *)c->dTrCand.p;
-    if (const int e = finalizeQueue(c, (const uint8_t *)c->dTrSamples.p, offs, sizes, (const uint8_t *)c->dTrContent.p, (uint32_t)contentSize, cap32, level ? level : 3, dictID,
-                                    (uint8_t *)c->dTrOut.p, dResult)) return ZSMI_ERR(e);
+    uint32_t *dResult = (uint32_t *)c->train.dCand.p;
+    if (const int e = finalizeQueue(c, (const uint8_t *)c->train.dSamples.p, offs, sizes, (const uint8_t *)c->train.dContent.p, (uint32_t)contentSize, cap32, level ? level : 3, dictID,
+                                    (uint8_t *)c->train.dOut.p, dResult)) return ZSMI_ERR(e);
     uint32_t size = 0;
     if (hipMemcpyAsync(&size, dResult, sizeof size, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
     if (!size) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
-    if (hipMemcpy(dst, c->dTrOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (hipMemcpy(dst, c->train.dOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
     return size;
 }

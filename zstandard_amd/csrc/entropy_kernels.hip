@@ -3,13 +3,18 @@
 //   k_encode_literals   (1 block, 4 wavefronts per workgroup)    -> literals section: gather, Huffman lengths / codes / description / streams;
 //                                                                    writes the frame of a one-block chunk as its workgroup finishes
 //   k_assemble_frames   (1 chunk per workgroup)                  -> frames of chunks of several blocks
+//   k_train_stats       (1 block per workgroup)                  -> the dictionary trainer's finalize: counts of what the sequences kernel coded
+//   k_pack_offsets, k_pack_copy                                  -> frames in bound-sized slots packed back to back
 // Scalar statement of the same algorithm: oracle/zso_encoder.c (compressBlock and below); the two
 // must agree bit for bit.  Every piece is the format-inverse of a function of the reference decoder:
 //   literals section        <-> DecodeLiteralsBlock            csharp/src/ZStdDecompress.cs:683-821
 //   Huffman table / streams <-> ReadStats, HUF_readDTableX2,   EntropyCommon.cs:198-269, HufDecompress.cs:117-358
 //   sequences header/tables <-> DecodeSeqHeaders, BuildFSETable ZStdDecompress.cs:958-1180, EntropyCommon.cs:79-188
 //   sequences bitstream     <-> DecodeSequence, decompressSequences_body  ZStdDecompress.cs:1473-1608
+#ifndef ZSMI_ENTROPY_KERNELS_HIP        // (dict_train.hip and seekable.hip include this file too)
+#define ZSMI_ENTROPY_KERNELS_HIP
 #include "zsmi_device.h"
+#include "zsmi_wave.h"
 // timing aids of the development tools (tools/time_kernels.py): end a kernel after a stage.  Compiled in only with
 // -DZSMI_DEBUG_HOOKS (the library the product ships ignores the stopAt argument).
 #ifdef ZSMI_DEBUG_HOOKS
@@ -146,59 +151,8 @@ struct SeqLds {                      // sequences kernel.  Kept under 10 KiB: 16
     uint8_t  rngFirst[ZS_WALK_RANGES];   // index of a range's first record that counts (after the walk kernel's stitch)
 };
 
-// ---------------------------------------------------------------------------------------------
-// wave helpers
-// ---------------------------------------------------------------------------------------------
-// Cross-lane moves by data-parallel primitives (DPP): vector-ALU operand modifiers, no LDS round trip (a __shfl is a
-// ds_bpermute: ~100 cycles of latency each, six in a row for a scan).  Control codes (gfx9): row_shr:n = 0x110 + n
-// (zero fill with bound_ctrl), row_bcast15 = 0x142 (lane 15 of a row to the next row), row_bcast31 = 0x143.
-#define ZS_DPP(old, v, ctrl, rowMask, boundCtrl) ((uint32_t)__builtin_amdgcn_update_dpp((int)(old), (int)(v), (ctrl), (rowMask), 0xF, (boundCtrl)))
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    v += ZS_DPP(0, v, 0x111, 0xF, true);
-    v += ZS_DPP(0, v, 0x112, 0xF, true);
-    v += ZS_DPP(0, v, 0x114, 0xF, true);
-    v += ZS_DPP(0, v, 0x118, 0xF, true);            // inclusive within each row of 16
-    v += ZS_DPP(0, v, 0x142, 0xA, false);           // rows 1, 3 += total of the row before
-    v += ZS_DPP(0, v, 0x143, 0xC, false);           // rows 2, 3 += total of rows 0..1
-    return v;
-}
-// value of lane l, l the same for the whole wavefront
-__device__ __forceinline__ uint32_t wave_get(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane(l)); }
-__device__ __forceinline__ uint32_t wave_last(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_last(wave_incl_scan(v)); }
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-    v = max(v, ZS_DPP(0, v, 0x111, 0xF, true));
-    v = max(v, ZS_DPP(0, v, 0x112, 0xF, true));
-    v = max(v, ZS_DPP(0, v, 0x114, 0xF, true));
-    v = max(v, ZS_DPP(0, v, 0x118, 0xF, true));
-    v = max(v, ZS_DPP(0, v, 0x142, 0xA, false));
-    v = max(v, ZS_DPP(0, v, 0x143, 0xC, false));
-    return wave_last(v);
-}
-
-// ordering point between LDS accesses of different lanes of ONE wavefront: LDS instructions of a wave execute in issue
-// order, so only the compiler has to be kept from moving them across
-__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-
 // Wave-cooperative forward bit writer.  Each put() appends, lane 0 first, up to 96 bits per lane.
 // out32 must be 4-byte aligned; bits are packed little-endian (bit k of the stream = bit k%8 of byte k/8).
-// a workgroup copies n bytes: 16-byte pieces (two unaligned 8-byte accesses), four pieces a thread in flight, then the tail.
-// (A byte a thread and iteration was 100 dependent load -> store rounds per section.)
-__device__ __forceinline__ void zs_block_copy(uint8_t *__restrict__ d, const uint8_t *__restrict__ s, uint32_t n, uint32_t tid, uint32_t nthreads)
-{
-    const uint32_t n16 = n >> 4;
-    for (uint32_t i = tid; i < n16; i += 4 * nthreads) {
-        uint64_t a[4], b[4];
-        #pragma unroll
-        for (uint32_t k = 0; k < 4; k++) { const uint32_t idx = min(i + k * nthreads, n16 - 1); a[k] = zs_load64(s + 16 * idx); b[k] = zs_load64(s + 16 * idx + 8); }
-        #pragma unroll
-        for (uint32_t k = 0; k < 4; k++) { const uint32_t idx = i + k * nthreads; if (idx < n16) { zs_store64(d + 16 * idx, a[k]); zs_store64(d + 16 * idx + 8, b[k]); } }
-    }
-    for (uint32_t j = (n16 << 4) + tid; j < n; j += nthreads) d[j] = s[j];
-}
-
 struct BitSink {
     uint32_t *out32;
     uint32_t *tile;       // LDS, >= 200 words
@@ -1642,3 +1596,71 @@ __device__ __forceinline__ void assemble_frame(ZS_ASM_PARAMS, uint32_t dictID)
 }
 extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAMS) { assemble_frame(ZS_ASM_ARGS, 0u); }
 extern "C" __global__ void __launch_bounds__(256) k_assemble_frames_dict(ZS_ASM_PARAMS, uint32_t dictID) { assemble_frame(ZS_ASM_ARGS, dictID); }
+
+static const uint32_t kTrainStatWords = 448;                                // literal bytes [0, 256), LL codes [256, 320), OF [320, 384), ML [384, 448)
+// finalize statistics of one compressed sub-batch, between k_encode_sequences and k_encode_literals: the codes the sequences kernel left in the
+// block's literal buffer (LL, OF with the recent-offset codes applied, ML; ZS_CHAIN_CODES apart), and the literal bytes - every block byte no match
+// of the block's records covers.  One workgroup a block, counts added to stats[kTrainStatWords].
+__global__ void __launch_bounds__(256) k_train_stats(const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, const ZsSeqRec *__restrict__ seqAll,
+                                                     const ZsRangeHdr *__restrict__ hdrAll, const uint8_t *__restrict__ litsAll, uint32_t *__restrict__ stats)
+{
+    __shared__ uint32_t cov[ZS_BLOCK_MAX / 32], hist[kTrainStatWords], rstart[ZS_WALK_RANGES + 1];
+    const uint32_t blk = blockIdx.x, tid = threadIdx.x;
+    const ZsBlockDesc bd = blocks[blk];
+    const uint32_t n = bd.size;
+    for (uint32_t i = tid; i < ZS_BLOCK_MAX / 32; i += 256) cov[i] = 0;
+    for (uint32_t i = tid; i < kTrainStatWords; i += 256) hist[i] = 0;
+    const ZsRangeHdr *hdr = hdrAll + (size_t)blk * ZS_WALK_RANGES;
+    if (tid == 0) { uint32_t s = 0; for (uint32_t r = 0; r < ZS_WALK_RANGES; r++) { rstart[r] = s; s += n >= 16 ? hdr[r].nseq : 0u; } rstart[ZS_WALK_RANGES] = s; }
+    __syncthreads();
+    const uint32_t nseq = rstart[ZS_WALK_RANGES];
+    const ZsSeqRec *seqBase = seqAll + (size_t)blk * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE;
+    const uint8_t *codes = litsAll + (size_t)blk * (ZS_BLOCK_MAX + 64);
+    for (uint32_t g = tid; g < nseq; g += 256) {
+        uint32_t r = 0;
+        for (uint32_t st = ZS_WALK_RANGES / 2; st >= 1; st >>= 1) if (g >= rstart[r + st]) r += st;
+        const ZsSeqRec rec = seqBase[(size_t)r * ZS_SEQ_PER_RANGE + hdr[r].first + (g - rstart[r])];
+        const uint32_t pos = zs_rec_pos(rec.y), end = min(pos + zs_rec_ml(rec.x), n);
+        for (uint32_t b = pos; b < end;) {                                  // the match's bytes in the coverage bitmap
+            const uint32_t w = b >> 5, lo = b & 31u, cnt = min(32u - lo, end - b);
+            atomicOr(&cov[w], (cnt == 32u ? 0xFFFFFFFFu : ((1u << cnt) - 1u)) << lo);
+            b += cnt;
+        }
+        atomicAdd(&hist[256 + codes[g]], 1u);
+        atomicAdd(&hist[320 + codes[ZS_CHAIN_CODES + g]], 1u);
+        atomicAdd(&hist[384 + codes[2u * ZS_CHAIN_CODES + g]], 1u);
+    }
+    __syncthreads();
+    const uint8_t *s = src + bd.srcOff;
+    for (uint32_t b = tid; b < n; b += 256) if (!((cov[b >> 5] >> (b & 31u)) & 1u)) atomicAdd(&hist[s[b]], 1u);
+    __syncthreads();
+    for (uint32_t i = tid; i < kTrainStatWords; i += 256) if (hist[i]) atomicAdd(&stats[i], hist[i]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// pack frames: compressed frames in bound-sized slots -> back to back
+// ---------------------------------------------------------------------------------------------
+__global__ void k_pack_offsets(const uint32_t *sizes, uint32_t n, uint64_t *offsets)
+{
+    // single workgroup exclusive scan over n sizes (errors count as 0 bytes)
+    __shared__ uint64_t part[1024];
+    const uint32_t tid = threadIdx.x, per = (n + blockDim.x - 1) / blockDim.x;
+    const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
+    uint64_t s = 0;
+    for (uint32_t i = lo; i < hi; i++) { const uint32_t v = sizes[i]; s += (v > 0xFFFFFF88u) ? 0 : v; }
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) { uint64_t run = 0; for (uint32_t t = 0; t < blockDim.x; t++) { const uint64_t v = part[t]; part[t] = run; run += v; } offsets[n] = run; }
+    __syncthreads();
+    uint64_t run = part[tid];
+    for (uint32_t i = lo; i < hi; i++) { offsets[i] = run; const uint32_t v = sizes[i]; run += (v > 0xFFFFFF88u) ? 0 : v; }
+}
+__global__ void k_pack_copy(const uint8_t *frames, const uint64_t *srcOffsets, const uint32_t *sizes, const uint64_t *packedOffsets, uint8_t *packed)
+{
+    const uint32_t i = blockIdx.x;
+    const uint32_t sz = sizes[i] > 0xFFFFFF88u ? 0 : sizes[i];
+    const uint8_t *s = frames + srcOffsets[i]; uint8_t *d = packed + packedOffsets[i];
+    zs_block_copy(d, s, sz, threadIdx.x, blockDim.x);
+}
+
+#endif

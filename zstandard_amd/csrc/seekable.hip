@@ -1,4 +1,4 @@
-// seekable.hip -- zstd's seekable format over the batch paths (included from zsmi_api.hip after the one-shot calls).
+// seekable.hip -- zstd's seekable format over the batch paths of zsmi_api.hip (zsmi_ctx.h declares them).
 //
 //   archive    = frame_0 .. frame_{n-1} | seek table
 //   seek table = 0x184D2A5E | Frame_Size | entry_0 .. entry_{n-1} | Number_Of_Frames | Seek_Table_Descriptor | 0x8F92EAB1   (little-endian)
@@ -11,6 +11,10 @@
 // Decompressed_Size as capacity - the ones wholly inside the range decode straight into dDst, a partial first / last one into context scratch
 // and is copied in slices - then k_seek_verify checks every decoded frame's size and checksum against its entry.
 
+#include "zsmi_wave.h"            // zs_block_copy, xxh64_quad
+#include "entropy_kernels.hip"    // k_pack_offsets
+#include "decode_kernels.hip"     // the decoder's error codes (E_*)
+#include "zsmi_ctx.h"
 #include <algorithm>
 
 static const uint32_t kSeekSkippableMagic = 0x184D2A5Eu, kSeekableMagic = 0x8F92EAB1u;
@@ -197,20 +201,20 @@ static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize,
     const uint64_t stride = zsmi_compressBound(F);
     // per-frame words: sizes [n], hashes [n], then (8-aligned) packed offsets [n + 1] and the error word
     const size_t words = 2 * (size_t)n * sizeof(uint32_t);
-    if (!c->dSeekMeta.reserve(words + ((size_t)n + 2) * sizeof(uint64_t))) return ZSMI_error_memory_allocation;
-    uint32_t *dSizes = (uint32_t *)c->dSeekMeta.p, *dHash = dSizes + n;
-    uint64_t *dPacked = (uint64_t *)((uint8_t *)c->dSeekMeta.p + words);
+    if (!c->seek.dMeta.reserve(words + ((size_t)n + 2) * sizeof(uint64_t))) return ZSMI_error_memory_allocation;
+    uint32_t *dSizes = (uint32_t *)c->seek.dMeta.p, *dHash = dSizes + n;
+    uint64_t *dPacked = (uint64_t *)((uint8_t *)c->seek.dMeta.p + words);
     unsigned long long *dErr = (unsigned long long *)(dPacked + n + 1);
     if (n) {
-        if (!c->dSeekStage.reserve((n - 1) * stride + zsmi_compressBound(srcSize - (n64 - 1) * F))) return ZSMI_error_memory_allocation;
+        if (!c->seek.dStage.reserve((n - 1) * stride + zsmi_compressBound(srcSize - (n64 - 1) * F))) return ZSMI_error_memory_allocation;
         std::vector<uint64_t> so(n), dof(n);
         std::vector<uint32_t> ss(n);
         for (uint32_t i = 0; i < n; i++) { so[i] = (uint64_t)i * F; ss[i] = (uint32_t)std::min<uint64_t>(F, srcSize - so[i]); dof[i] = (uint64_t)i * stride; }
-        if (const int e = compressBatchDeviceImpl(c, dSrc, so.data(), ss.data(), n, c->dSeekStage.p, dof.data(), dSizes, level, nullptr, nullptr)) return e;
+        if (const int e = compressBatchDeviceImpl(c, dSrc, so.data(), ss.data(), n, c->seek.dStage.p, dof.data(), dSizes, level, nullptr, nullptr)) return e;
         if (checksumFlag) LAUNCH(c, "k_seek_hash", k_seek_hash, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, srcSize, F, n, dHash);
     }
     LAUNCH(c, "k_pack_offsets", k_pack_offsets, dim3(1), dim3(1024), 0, (const uint32_t *)dSizes, n, dPacked);
-    if (n) LAUNCH(c, "k_seek_pack", k_seek_pack, dim3(n), dim3(256), 0, (const uint8_t *)c->dSeekStage.p, stride, (const uint32_t *)dSizes, (const uint64_t *)dPacked, (uint8_t *)dDst);
+    if (n) LAUNCH(c, "k_seek_pack", k_seek_pack, dim3(n), dim3(256), 0, (const uint8_t *)c->seek.dStage.p, stride, (const uint32_t *)dSizes, (const uint64_t *)dPacked, (uint8_t *)dDst);
     if (hipMemsetAsync(dErr, 0xFF, sizeof(*dErr), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     LAUNCH(c, "k_seek_table", k_seek_table, dim3(std::max<uint32_t>(1, (n + 255) / 256)), dim3(256), 0, (const uint32_t *)dSizes, (const uint64_t *)dPacked,
            (const uint32_t *)dHash, srcSize, F, n, checksumFlag ? 1 : 0, (uint8_t *)dDst, dErr);
@@ -252,7 +256,7 @@ static void seekSpan(const SeekTable &t, uint64_t a, uint64_t b, uint32_t &first
     last = (uint32_t)(std::lower_bound(t.dOff.begin(), t.dOff.end(), b) - t.dOff.begin()) - 1;
 }
 // Queue the decode of [a, b) on the context's stream.  Frame i's compressed bytes are at dFrames + t.cOff[i] - base.  The context must be idle
-// on the host side (hSeek is refilled): the callers have waited for its stream.
+// on the host side (seek.hItems is refilled): the callers have waited for its stream.
 static int seekReadQueue(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames, uint64_t base, uint64_t a, uint64_t b, uint8_t *dDst, uint32_t *dStatus)
 {
     if (hipMemsetAsync(dStatus, 0, sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
@@ -265,11 +269,11 @@ static int seekReadQueue(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames
     const uint32_t in0 = partFirst ? 1 : 0, in1 = partLast ? m - 1 : m;
     // status words: [m] for the span in content order, [2] behind them for the partial frames' decode call; (8-aligned) the error word; the verify list
     const size_t words = (((size_t)m + 3) & ~(size_t)1) * sizeof(uint32_t);
-    if (!c->dSeekMeta.reserve(words + sizeof(uint64_t) + (size_t)m * sizeof(ZsSeekItem)) || !c->hSeek.reserve((size_t)m * sizeof(ZsSeekItem))) return ZSMI_error_memory_allocation;
-    uint32_t *dSt = (uint32_t *)c->dSeekMeta.p;
-    unsigned long long *dErr = (unsigned long long *)((uint8_t *)c->dSeekMeta.p + words);
+    if (!c->seek.dMeta.reserve(words + sizeof(uint64_t) + (size_t)m * sizeof(ZsSeekItem)) || !c->seek.hItems.reserve((size_t)m * sizeof(ZsSeekItem))) return ZSMI_error_memory_allocation;
+    uint32_t *dSt = (uint32_t *)c->seek.dMeta.p;
+    unsigned long long *dErr = (unsigned long long *)((uint8_t *)c->seek.dMeta.p + words);
     ZsSeekItem *dItems = (ZsSeekItem *)(dErr + 1);
-    ZsSeekItem *hi = (ZsSeekItem *)c->hSeek.p;
+    ZsSeekItem *hi = (ZsSeekItem *)c->seek.hItems.p;
     std::vector<uint64_t> so, dof; std::vector<uint32_t> ss, caps;
     auto item = [&](uint32_t k, uint8_t *dBase, uint64_t at, uint32_t slot) {
         const uint32_t i = first + k;
@@ -285,8 +289,8 @@ static int seekReadQueue(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames
         if (partFirst) parts[np++] = 0;
         if (partLast) parts[np++] = m - 1;
         const uint64_t partBytes = (uint64_t)t.dSize[first + parts[0]] + (np > 1 ? t.dSize[first + parts[1]] : 0u);
-        if (!c->dSeekDec.reserve(partBytes + 64)) return ZSMI_error_memory_allocation;
-        uint8_t *dS = (uint8_t *)c->dSeekDec.p;
+        if (!c->seek.dDec.reserve(partBytes + 64)) return ZSMI_error_memory_allocation;
+        uint8_t *dS = (uint8_t *)c->seek.dDec.p;
         so.clear(); dof.clear(); ss.clear(); caps.clear();
         ZsSeekSlices sl = {};
         uint64_t pos = 0;

@@ -2,13 +2,17 @@
 // workspaces, block planning, kernel launches, staging for host-buffer calls.  No CPU codec path exists
 // in this library: every compress/decompress call launches the gfx950 kernels or fails.
 //
-// Single translation unit: the kernel sources are included so that launches and kernels share one code object.
-#include <hipcub/hipcub.hpp>            // (dict_train.hip: the radix sort of its d-mer keys)
-#include "lz_kernels.hip"
-#include "entropy_kernels.hip"
-#include "decode_kernels.hip"
-#include "decode_fast.hip"
-#include "../../include/zsmi.h"
+// Single translation unit: the kernel sources are included so that launches and kernels share one code object.  Every file includes what
+// it uses; the list is the library's table of contents.
+#include "zsmi_device.h"          // format constants, block / unit / sequence records, unaligned loads and stores
+#include "zsmi_wave.h"            // device primitives of more than one kernel file: wave_*, zs_block_copy, rd16/24/32, xxh64_quad
+#include "lz_kernels.hip"         // encoder, LZ stage: k_lz_candidates, k_lz_walk, k_lz_stitch, k_lz_dict_tables
+#include "entropy_kernels.hip"    // encoder, entropy stage: k_encode_sequences, k_encode_literals, k_assemble_frames; k_train_stats, k_pack_*
+#include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares
+#include "decode_fast.hip"        // fast decode path: k_dec_prep, k_dec_huffman, k_dec_sequences, k_dec_entropy, k_dec_execute, k_dec_checksum, k_dec_collect
+#include "zsmi_ctx.h"             // host: zsmi_ctx and its buffers, LAUNCH, the batch entry points the features call
+#include "seekable.hip"           // feature: seekable archives (kernels and host)
+#include "dict_train.hip"         // feature: dictionary training and finalize (kernels and host)
 
 #include <cstdio>
 #include <cstdlib>
@@ -18,8 +22,6 @@
 #include <mutex>
 #include <string>
 #include <vector>
-
-#define ZSMI_ERR(code) ((size_t)0 - (size_t)(code))
 
 extern "C" unsigned zsmi_isError(size_t code) { return code > ZSMI_ERR(ZSMI_error_maxCode); }     // ZStdErrors.cs:95-98
 extern "C" unsigned zsmi_getErrorCode(size_t code) { return zsmi_isError(code) ? (unsigned)(0 - code) : 0; }
@@ -65,7 +67,6 @@ extern "C" size_t zsmi_compressBound(size_t srcSize)
 }
 
 // ---- host-only frame header parse: ZStdDecompress.cs:421-499, 518-532, 617-622 ----
-static uint32_t h_rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 extern "C" unsigned long long zsmi_getDecompressedSize(const void *srcv, size_t srcSize)
 {
     const uint8_t *src = (const uint8_t *)srcv;
@@ -90,112 +91,6 @@ extern "C" unsigned long long zsmi_getDecompressedSize(const void *srcv, size_t 
     }
     return (fcs >= 0xFFFFFFFFFFFFFFFEull) ? 0 : fcs;
 }
-
-// ---------------------------------------------------------------------------------------------
-// context
-// ---------------------------------------------------------------------------------------------
-// A buffer that grows by 1/8 + 4 KiB beyond the request; device or pinned host memory.  The context owns its buffers: they go with it.
-static hipError_t devAlloc(void **p, size_t n) { return hipMalloc(p, n); }
-static hipError_t pinAlloc(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
-template <hipError_t (*Alloc)(void **, size_t), hipError_t (*Free)(void *)>
-struct Buf {
-    void *p = nullptr; size_t cap = 0;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { release(); }
-    bool reserve(size_t n) {
-        if (n <= cap) return true;
-        release();
-        size_t want = n + (n >> 3) + 4096;
-        if (Alloc(&p, want) != hipSuccess) { p = nullptr; return false; }
-        cap = want; return true;
-    }
-    void release() { if (p) (void)Free(p); p = nullptr; cap = 0; }
-};
-typedef Buf<devAlloc, hipFree> DevBuf;
-typedef Buf<pinAlloc, hipHostFree> PinBuf;
-
-struct TimedLaunch { const char *name; hipEvent_t a, b; };
-struct DecodePlan;
-
-struct zsmi_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
-    uint32_t maxBlocksInFlight = 16384;   // ZSMI_BLOCKS_IN_FLIGHT: 64 KiB blocks per sub-batch (scratch ~0.6 MiB a block, reserved for what a call needs); 2 GiB of 128 KiB chunks: 8192: 86.5, 16384: 88.2, 32768: 89.4 GiB/s
-    // compress workspace: the plan and the scratch of a sub-batch
-    DevBuf dBlocks, dChunks, dUnits;     // dUnits: small units (<= 64 KiB) first, then big ones, each in chunk order
-    struct Scratch {
-        DevBuf dDist, dDistHi, dCand, dRecs, dRes, dSeqs, dHdrs, dLits, dStreams, dLitSec, dSeqSec, dMetas;
-        bool reserve(uint32_t cap) {           // cap: blocks of a sub-batch
-            return dDist.reserve((size_t)cap * ZS_BLOCK_MAX * 2 + 256) && dDistHi.reserve((size_t)cap * (ZS_BLOCK_MAX / 8) + 256) && dCand.reserve((size_t)cap * 2 * sizeof(uint32_t) + 64) &&
-                   dRecs.reserve(((size_t)cap * (ZS_BLOCK_MAX / 4) + 64) * sizeof(uint2)) && dRes.reserve((size_t)cap * ZS_RES_PER_BLOCK * sizeof(uint4) + ((size_t)8 << 20)) &&
-                   dSeqs.reserve((size_t)cap * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE * sizeof(ZsSeqRec)) && dHdrs.reserve((size_t)cap * ZS_WALK_RANGES * sizeof(ZsRangeHdr)) &&
-                   dLits.reserve((size_t)cap * (ZS_BLOCK_MAX + 64)) && dStreams.reserve((size_t)cap * 4 * ZS_STREAM_STRIDE) && dLitSec.reserve((size_t)cap * ZS_LITSEC_STRIDE) &&
-                   dSeqSec.reserve((size_t)cap * ZS_SEQSEC_STRIDE) && dMetas.reserve((size_t)cap * sizeof(ZsBlockMeta));
-        }
-    } scratch;
-    int stopAfterWalk = 0;                 // ZSMI_STOP_AFTER_WALK (debug-hooks build, tools/walk_check.py): the entropy kernels are not launched
-    int stopLit = 0, stopSeq = 0;          // timing aids of a -DZSMI_DEBUG_HOOKS build (ZSMI_STOP_LIT / ZSMI_STOP_SEQ): end a kernel after a stage; always 0 in the product
-    PinBuf hBlocks, hChunks, hUnits;
-    std::vector<uint32_t> smallBefore, bigBefore;   // per chunk (n + 1 entries): small / big units in front of it
-    uint32_t planSmall = 0, planBig = 0;
-    std::vector<uint64_t> planKey;       // copy of (srcOffsets, srcSizes, dstOffsets) the device-side plan was built from
-    uint64_t planBlocks = 0; uint32_t planMaxChunkBlocks = 1;
-    // dictionary calls: their own unit list for the plan (built on the first such call), the prefix's candidate-table images
-    PinBuf hUnitsDict; DevBuf dUnitsDict, dDictImg;
-    std::vector<uint32_t> wholeBefore, tailBefore;
-    uint32_t planDictWhole = 0; bool planDict = false;
-    // decompress workspace: the item list (on the host: two pinned buffers taken in turn) and the scratch of a sub-batch, whose sizes for a
-    // call's plan are stated once, in the decompress section (DecodeScratch::each)
-    DevBuf dItems;
-    PinBuf hItems2[2]; hipEvent_t hItemsEv[2] = { nullptr, nullptr }; bool hItemsBusy[2] = { false, false }; uint32_t decodeCalls = 0;
-    struct DecodeScratch {
-        DevBuf dPoolLit;                                                 // the general kernel's literal buffers: one per wavefront of its pool
-        DevBuf dLitScratch, dFastDesc, dHufTabs, dSeqTabs, dSeqOut;      // the fast path's block slots: literals, descriptors, tables, sequences
-        DevBuf dSeqLists;                                                // the general kernel's queue, the blocks of each table class, the items left (DecLists)
-        template <class F> void each(const DecodePlan &p, F f);
-        size_t held();
-        bool reserve(const DecodePlan &p);
-    } dec;
-    bool decodeFast = true;              // ZSMI_DEC_FAST=0: general kernel only
-    uint32_t maxItemsInFlight = 65536;   // ZSMI_ITEMS_IN_FLIGHT: items per decode launch (cut down when the scratch does not fit: planDecode).
-                                         // Every decode kernel is a long dependent chain per item: a launch is one to three rounds of workgroups and its
-                                         // last round is mostly tail, so big launches pay (16384 frames of 32 KiB: 82 GiB/s, 57344: 104 GiB/s)
-    uint32_t cus = 256;                      // compute units of the device (rounds of workgroups a launch takes)
-    uint32_t decodePool = 3072;              // wavefronts of the general decode kernel's pool (ZSMI_DEC_POOL): the chip holds 10 a CU x 256
-    // staging for host-buffer calls
-    DevBuf sSrc, sDst, sSizes, sDict, sPack, sPackOff;
-    PinBuf hPack;
-    // seekable archives (seekable.hip): compressed frames at bound spacing before they are packed, per-frame words (sizes, hashes, offsets,
-    // the error word), a partial first / last frame's decoded bytes, the verify list
-    DevBuf dSeekStage, dSeekMeta, dSeekDec;
-    PinBuf hSeek;
-    // dictionary training (dict_train.hip): the samples back to back, sort keys, per-position hash / links (d = 6, 8), base and per-candidate
-    // frequency tables, candidate contents and list, compressed sizes and frames of the scoring / statistics calls, stats + header scratch, the result
-    DevBuf dTrSamples, dTrGather, dTrEnds, dTrKeys, dTrKeysOut, dTrSortTmp, dTrInfo[2], dTrFreqBase, dTrFreq, dTrContent, dTrCand, dTrArena, dTrSizes, dTrMisc, dTrOut;
-    PinBuf hTrCand;
-    // timing
-    int timing = 0;                      // 1: events around every launch; 2: only around the dominant kernels (k_lz_walk*, k_dec_execute)
-    std::vector<TimedLaunch> launches;
-    std::vector<hipEvent_t> eventPool;
-};
-
-static hipEvent_t getEvent(zsmi_ctx *c)
-{
-    if (!c->eventPool.empty()) { hipEvent_t e = c->eventPool.back(); c->eventPool.pop_back(); return e; }
-    hipEvent_t e; (void)hipEventCreate(&e); return e;
-}
-static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz_walk", 9) == 0 || strncmp(name, "k_dec_execute", 13) == 0; }
-#define LAUNCH_ON(ctx, strm, name, kernel, grid, block, lds, ...) do { \
-        TimedLaunch tl_{name, nullptr, nullptr}; \
-        const bool timed_ = (ctx)->timing == 1 || ((ctx)->timing == 2 && dominantKernel(name)); \
-        if (timed_) { tl_.a = getEvent(ctx); tl_.b = getEvent(ctx); (void)hipEventRecord(tl_.a, (strm)); } \
-        hipLaunchKernelGGL(kernel, grid, block, lds, (strm), __VA_ARGS__); \
-        if (timed_) { (void)hipEventRecord(tl_.b, (strm)); (ctx)->launches.push_back(tl_); } \
-    } while (0)
-#define LAUNCH(ctx, name, kernel, grid, block, lds, ...) LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, lds, __VA_ARGS__)
 
 // ---- the LZ kernels of a level: k_lz_candidates and k_lz_walk for small units (<= 64 KiB), big units and a dictionary call's prefixed units ----
 // level <= 2: short table only ("fast"), walk ranges of 512 bytes; level >= 3: short + long table ("double"), ranges of 256 bytes;
@@ -301,7 +196,6 @@ extern "C" int zsmi_getKernelTimes(zsmi_ctx *c, zsmi_kernel_time *out, int maxEn
 // (:2378-2450) refuses (its checks restated on the host: readNCount, the Huffman weights and their FSE header, the recent offsets).
 // Any other bytes are raw content: offsets {1, 4, 8}, no ID.  The encoder uses none of the dictionary's tables.
 // ---------------------------------------------------------------------------------------------
-struct ZsCompressDict { uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 }; };
 namespace hdict {
 static uint32_t hb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
 static const size_t kErr = ~(size_t)0;
@@ -475,6 +369,15 @@ static int parseCompressDict(const uint8_t *d, size_t size, ZsCompressDict &out)
 // ---------------------------------------------------------------------------------------------
 // compress
 // ---------------------------------------------------------------------------------------------
+// the scratch of a sub-batch of cap blocks
+bool zsmi_ctx::Scratch::reserve(uint32_t cap)
+{
+    return dDist.reserve((size_t)cap * ZS_BLOCK_MAX * 2 + 256) && dDistHi.reserve((size_t)cap * (ZS_BLOCK_MAX / 8) + 256) && dCand.reserve((size_t)cap * 2 * sizeof(uint32_t) + 64) &&
+           dRecs.reserve(((size_t)cap * (ZS_BLOCK_MAX / 4) + 64) * sizeof(uint2)) && dRes.reserve((size_t)cap * ZS_RES_PER_BLOCK * sizeof(uint4) + ((size_t)8 << 20)) &&
+           dSeqs.reserve((size_t)cap * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE * sizeof(ZsSeqRec)) && dHdrs.reserve((size_t)cap * ZS_WALK_RANGES * sizeof(ZsRangeHdr)) &&
+           dLits.reserve((size_t)cap * (ZS_BLOCK_MAX + 64)) && dStreams.reserve((size_t)cap * 4 * ZS_STREAM_STRIDE) && dLitSec.reserve((size_t)cap * ZS_LITSEC_STRIDE) &&
+           dSeqSec.reserve((size_t)cap * ZS_SEQSEC_STRIDE) && dMetas.reserve((size_t)cap * sizeof(ZsBlockMeta));
+}
 // The plan of a call: chunks -> blocks (ZsChunkDesc, ZsBlockDesc) and LZ units, built on the host and copied to the device.  It is reused
 // while the chunk layout repeats (steady-state batches; compared in place: such a call allocates and copies nothing).  A dictionary call
 // adds a unit list of its own, once per plan.
@@ -553,8 +456,6 @@ static int buildPlan(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *sr
     }
     return 0;
 }
-// finalize statistics of a sub-batch (dict_train.hip); launched only when a call asks for them
-__global__ void k_train_stats(const uint8_t *src, const ZsBlockDesc *blocks, const ZsSeqRec *seqAll, const ZsRangeHdr *hdrAll, const uint8_t *litsAll, uint32_t *stats);
 // dict (dictionary calls): parsed on the host (parseCompressDict), dDict its bytes in device memory.  Chunks of <= 64 KiB are PREFIXED
 // units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the last <= 64 KiB of the content); the units of longer chunks are
 // parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
@@ -562,7 +463,7 @@ __global__ void k_train_stats(const uint8_t *src, const ZsBlockDesc *blocks, con
 // counters of the literal bytes and LL / OF / ML codes, added to by k_train_stats after each sub-batch's sequences kernel.
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const uint8_t *dDict, const ZsCompressDict *dict, uint32_t *dStats = nullptr)
+                                   const uint8_t *dDict, const ZsCompressDict *dict, uint32_t *dStats)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
@@ -893,28 +794,6 @@ extern "C" int zsmi_decompressBatchDevice_usingDict(zsmi_ctx *c, const void *dSr
 // ---------------------------------------------------------------------------------------------
 // pack frames
 // ---------------------------------------------------------------------------------------------
-__global__ void k_pack_offsets(const uint32_t *sizes, uint32_t n, uint64_t *offsets)
-{
-    // single workgroup exclusive scan over n sizes (errors count as 0 bytes)
-    __shared__ uint64_t part[1024];
-    const uint32_t tid = threadIdx.x, per = (n + blockDim.x - 1) / blockDim.x;
-    const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
-    uint64_t s = 0;
-    for (uint32_t i = lo; i < hi; i++) { const uint32_t v = sizes[i]; s += (v > 0xFFFFFF88u) ? 0 : v; }
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) { uint64_t run = 0; for (uint32_t t = 0; t < blockDim.x; t++) { const uint64_t v = part[t]; part[t] = run; run += v; } offsets[n] = run; }
-    __syncthreads();
-    uint64_t run = part[tid];
-    for (uint32_t i = lo; i < hi; i++) { offsets[i] = run; const uint32_t v = sizes[i]; run += (v > 0xFFFFFF88u) ? 0 : v; }
-}
-__global__ void k_pack_copy(const uint8_t *frames, const uint64_t *srcOffsets, const uint32_t *sizes, const uint64_t *packedOffsets, uint8_t *packed)
-{
-    const uint32_t i = blockIdx.x;
-    const uint32_t sz = sizes[i] > 0xFFFFFF88u ? 0 : sizes[i];
-    const uint8_t *s = frames + srcOffsets[i]; uint8_t *d = packed + packedOffsets[i];
-    zs_block_copy(d, s, sz, threadIdx.x, blockDim.x);
-}
 extern "C" int zsmi_packFramesDevice(zsmi_ctx *c, const void *dFrames, const uint64_t *dstOffsets, const uint32_t *dSizes,
                                      uint32_t n, void *dPacked, uint64_t *dPackedOffsets)
 {
@@ -1105,12 +984,9 @@ struct OneShotPool {
     }
 };
 OneShotPool &g_pool = *new OneShotPool();                  // (never destroyed: see above)
-struct Borrowed {
-    zsmi_ctx *c;
-    Borrowed() : c(g_pool.acquire()) {}
-    ~Borrowed() { if (c) g_pool.release(c); }
-};
 }
+Borrowed::Borrowed() : c(g_pool.acquire()) {}
+Borrowed::~Borrowed() { if (c) g_pool.release(c); }
 
 extern "C" void zsmi_shutdown(void) { g_pool.drain(); }
 extern "C" size_t zsmi_decodeScratchBytes(zsmi_ctx *c)
@@ -1157,9 +1033,6 @@ extern "C" size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const
     if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
     return ds;
 }
-
-#include "seekable.hip"
-#include "dict_train.hip"
 
 #ifdef ZSMI_DEBUG_HOOKS
 // ---- test hook (not in include/zsmi.h): copy a scratch buffer of the last compress sub-batch to the host.

@@ -1,0 +1,124 @@
+// Host side that zsmi_api.hip and the feature files (seekable.hip, dict_train.hip) share: the context with its buffers, the timed launch,
+// and the batch entry points the features are built on (defined in zsmi_api.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/zsmi.h"
+
+#include <cstring>
+#include <vector>
+
+#define ZSMI_ERR(code) ((size_t)0 - (size_t)(code))
+
+static uint32_t h_rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+// ---------------------------------------------------------------------------------------------
+// context
+// ---------------------------------------------------------------------------------------------
+// A buffer that grows by 1/8 + 4 KiB beyond the request; device or pinned host memory.  The context owns its buffers: they go with it.
+static hipError_t devAlloc(void **p, size_t n) { return hipMalloc(p, n); }
+static hipError_t pinAlloc(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+template <hipError_t (*Alloc)(void **, size_t), hipError_t (*Free)(void *)>
+struct Buf {
+    void *p = nullptr; size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
+    bool reserve(size_t n) {
+        if (n <= cap) return true;
+        release();
+        size_t want = n + (n >> 3) + 4096;
+        if (Alloc(&p, want) != hipSuccess) { p = nullptr; return false; }
+        cap = want; return true;
+    }
+    void release() { if (p) (void)Free(p); p = nullptr; cap = 0; }
+};
+typedef Buf<devAlloc, hipFree> DevBuf;
+typedef Buf<pinAlloc, hipHostFree> PinBuf;
+
+struct TimedLaunch { const char *name; hipEvent_t a, b; };
+struct DecodePlan;
+
+struct zsmi_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool ownStream = false;
+    uint32_t maxBlocksInFlight = 16384;   // ZSMI_BLOCKS_IN_FLIGHT: 64 KiB blocks per sub-batch (scratch ~0.6 MiB a block, reserved for what a call needs); 2 GiB of 128 KiB chunks: 8192: 86.5, 16384: 88.2, 32768: 89.4 GiB/s
+    // compress workspace: the plan and the scratch of a sub-batch (its sizes: the compress section of zsmi_api.hip)
+    DevBuf dBlocks, dChunks, dUnits;     // dUnits: small units (<= 64 KiB) first, then big ones, each in chunk order
+    struct Scratch {
+        DevBuf dDist, dDistHi, dCand, dRecs, dRes, dSeqs, dHdrs, dLits, dStreams, dLitSec, dSeqSec, dMetas;
+        bool reserve(uint32_t cap);            // cap: blocks of a sub-batch
+    } scratch;
+    int stopAfterWalk = 0;                 // ZSMI_STOP_AFTER_WALK (debug-hooks build, tools/walk_check.py): the entropy kernels are not launched
+    int stopLit = 0, stopSeq = 0;          // timing aids of a -DZSMI_DEBUG_HOOKS build (ZSMI_STOP_LIT / ZSMI_STOP_SEQ): end a kernel after a stage; always 0 in the product
+    PinBuf hBlocks, hChunks, hUnits;
+    std::vector<uint32_t> smallBefore, bigBefore;   // per chunk (n + 1 entries): small / big units in front of it
+    uint32_t planSmall = 0, planBig = 0;
+    std::vector<uint64_t> planKey;       // copy of (srcOffsets, srcSizes, dstOffsets) the device-side plan was built from
+    uint64_t planBlocks = 0; uint32_t planMaxChunkBlocks = 1;
+    // dictionary calls: their own unit list for the plan (built on the first such call), the prefix's candidate-table images
+    PinBuf hUnitsDict; DevBuf dUnitsDict, dDictImg;
+    std::vector<uint32_t> wholeBefore, tailBefore;
+    uint32_t planDictWhole = 0; bool planDict = false;
+    // decompress workspace: the item list (on the host: two pinned buffers taken in turn) and the scratch of a sub-batch, whose sizes for a
+    // call's plan are stated once, in the decompress section (DecodeScratch::each)
+    DevBuf dItems;
+    PinBuf hItems2[2]; hipEvent_t hItemsEv[2] = { nullptr, nullptr }; bool hItemsBusy[2] = { false, false }; uint32_t decodeCalls = 0;
+    struct DecodeScratch {
+        DevBuf dPoolLit;                                                 // the general kernel's literal buffers: one per wavefront of its pool
+        DevBuf dLitScratch, dFastDesc, dHufTabs, dSeqTabs, dSeqOut;      // the fast path's block slots: literals, descriptors, tables, sequences
+        DevBuf dSeqLists;                                                // the general kernel's queue, the blocks of each table class, the items left (DecLists)
+        template <class F> void each(const DecodePlan &p, F f);
+        size_t held();
+        bool reserve(const DecodePlan &p);
+    } dec;
+    bool decodeFast = true;              // ZSMI_DEC_FAST=0: general kernel only
+    uint32_t maxItemsInFlight = 65536;   // ZSMI_ITEMS_IN_FLIGHT: items per decode launch (cut down when the scratch does not fit: planDecode).
+                                         // Every decode kernel is a long dependent chain per item: a launch is one to three rounds of workgroups and its
+                                         // last round is mostly tail, so big launches pay (16384 frames of 32 KiB: 82 GiB/s, 57344: 104 GiB/s)
+    uint32_t cus = 256;                      // compute units of the device (rounds of workgroups a launch takes)
+    uint32_t decodePool = 3072;              // wavefronts of the general decode kernel's pool (ZSMI_DEC_POOL): the chip holds 10 a CU x 256
+    // staging for host-buffer calls
+    DevBuf sSrc, sDst, sSizes, sDict, sPack, sPackOff;
+    PinBuf hPack;
+    // seekable archives (seekable.hip): compressed frames at bound spacing before they are packed, per-frame words (sizes, hashes, offsets,
+    // the error word), a partial first / last frame's decoded bytes, the verify list
+    struct SeekScratch { DevBuf dStage, dMeta, dDec; PinBuf hItems; } seek;
+    // dictionary training (dict_train.hip): the samples back to back, sort keys, per-position hash / links (d = 6, 8), base and per-candidate
+    // frequency tables, candidate contents and list, compressed sizes and frames of the scoring / statistics calls, stats + header scratch, the result
+    struct TrainScratch {
+        DevBuf dSamples, dGather, dEnds, dKeys, dKeysOut, dSortTmp, dInfo[2], dFreqBase, dFreq, dContent, dCand, dArena, dSizes, dMisc, dOut;
+        PinBuf hCand;
+    } train;
+    // timing
+    int timing = 0;                      // 1: events around every launch; 2: only around the dominant kernels (k_lz_walk*, k_dec_execute)
+    std::vector<TimedLaunch> launches;
+    std::vector<hipEvent_t> eventPool;
+};
+
+static hipEvent_t getEvent(zsmi_ctx *c)
+{
+    if (!c->eventPool.empty()) { hipEvent_t e = c->eventPool.back(); c->eventPool.pop_back(); return e; }
+    hipEvent_t e; (void)hipEventCreate(&e); return e;
+}
+static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz_walk", 9) == 0 || strncmp(name, "k_dec_execute", 13) == 0; }
+#define LAUNCH_ON(ctx, strm, name, kernel, grid, block, lds, ...) do { \
+        TimedLaunch tl_{name, nullptr, nullptr}; \
+        const bool timed_ = (ctx)->timing == 1 || ((ctx)->timing == 2 && dominantKernel(name)); \
+        if (timed_) { tl_.a = getEvent(ctx); tl_.b = getEvent(ctx); (void)hipEventRecord(tl_.a, (strm)); } \
+        hipLaunchKernelGGL(kernel, grid, block, lds, (strm), __VA_ARGS__); \
+        if (timed_) { (void)hipEventRecord(tl_.b, (strm)); (ctx)->launches.push_back(tl_); } \
+    } while (0)
+#define LAUNCH(ctx, name, kernel, grid, block, lds, ...) LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, lds, __VA_ARGS__)
+
+// ---- the batch calls in device memory (zsmi_api.hip: the compress and the decompress section state their arguments) ----
+struct ZsCompressDict { uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 }; };
+static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                   uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
+                                   const uint8_t *dDict, const ZsCompressDict *dict, uint32_t *dStats = nullptr);
+static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                     uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
+                                     const void *dDict, uint32_t dictSize);
+// a context of the one-shot pool (zsmi_api.hip), given back when the handle goes
+namespace { struct Borrowed { zsmi_ctx *c; Borrowed(); ~Borrowed(); }; }
