@@ -5,7 +5,7 @@ ZsBlockMeta.pad[0] >> 16 and K | Sb << 8 | nseq << 16 in pad[1]): ZSMI_LIB_FILE=
 import os, sys, ctypes
 os.environ["ZSMI_DEBUG_LIB"] = "1"
 import numpy as np, torch
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _data as D
 from zstandard_amd import BatchCodec, _lib

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
-"""Development aid (GPU box, library built with -DZS_DEC_PROFILE): cycles per decoder phase, averaged over the frames."""
+"""Development aid (GPU box): cycles per phase of the general decode kernel (k_decode_frames), averaged over the last frame of each wavefront of
+its pool.  Needs a library built with -DZSMI_DEBUG_HOOKS -DZS_DEC_PROFILE (tools/build_variants.sh decprof:"-DZSMI_DEBUG_HOOKS -DZS_DEC_PROFILE"):
+ZSMI_LIB_FILE=$PWD/zstandard_amd/lib/var_decprof.so python tools/dec_profile.py"""
 import os; os.environ["ZSMI_DEBUG_LIB"] = "1"          # the library built with -DZSMI_DEBUG_HOOKS (zstandard_amd/_lib.py)
+pool = 256                                             # every frame to the general kernel, whose pool is small enough that each wavefront takes frames
+os.environ["ZSMI_DEC_FAST"] = "0"; os.environ["ZSMI_DEC_POOL"] = str(pool)
 import sys, os, ctypes
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,9 +21,9 @@ fo = np.zeros(n, dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1
 out, oo, osz = bc.decompress_host(frames, fo, dsz, sizes)
 assert (osz == cs).all() and (out[:n * cs] == host).all()
 stride = (1 << 17) + 64
-buf = np.zeros(n * stride, dtype=np.uint8)
-rc = Z.zsmi_dbg_copyScratch(bc.ctx, 5, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n * stride)); assert rc == 0, rc
-prof = np.stack([buf[i * stride + (1 << 17): i * stride + (1 << 17) + 64].view(np.uint64) for i in range(n)])
+buf = np.zeros(pool * stride, dtype=np.uint8)             # the pool's literal buffers: a wavefront's counts sit in the 64 spare bytes behind its own
+rc = Z.zsmi_dbg_copyScratch(bc.ctx, 5, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(pool * stride)); assert rc == 0, rc
+prof = np.stack([buf[i * stride + (1 << 17): i * stride + (1 << 17) + 64].view(np.uint64) for i in range(pool)])
 names = ["literals", "seq tables", "seq decode", "seq execute", "checksum", "whole item", "  huf table", "  huf symbol loops"]
 m = prof.mean(axis=0)
 for k, nm in enumerate(names):

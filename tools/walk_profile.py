@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Development aid (GPU box, library built with -DZSMI_DEBUG_HOOKS -DZS_WALK_PROFILE): where k_lz_walk's wavefronts spend their time,
-from s_memtime stamps per wavefront (tools/build_variants.sh prof:"-DZSMI_DEBUG_HOOKS -DZS_WALK_PROFILE ..." ; ZSMI_LIB_FILE=... ZSMI_DEBUG_LIB=1)."""
+from s_memtime stamps per wavefront: tools/build_variants.sh walkprof:"-DZSMI_DEBUG_HOOKS -DZS_WALK_PROFILE", then
+ZSMI_LIB_FILE=$PWD/zstandard_amd/lib/var_walkprof.so python tools/walk_profile.py (tools/README.md, "Diagnostic builds")."""
 import os; os.environ["ZSMI_DEBUG_LIB"] = "1"
 import sys, ctypes
 import numpy as np, torch

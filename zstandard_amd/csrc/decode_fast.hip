@@ -31,8 +31,8 @@
 #define ZS_FAST_HUFWIN   128u                     // bytes of each Huffman stream staged in LDS at a time
 #endif
 #ifndef ZS_FAST_SEQWIN
-#define ZS_FAST_SEQWIN   256u
-#endif                     // bytes of each sequence bitstream staged in LDS at a time
+#define ZS_FAST_SEQWIN   256u                     // bytes of each sequence bitstream staged in LDS at a time
+#endif
 #define ZS_FAST_GROUP    16u                      // items per wavefront of the Huffman kernel (4 lanes each)
 #ifndef ZS_FAST_SEQGROUP
 #define ZS_FAST_SEQGROUP 16u                      // items per wavefront of the sequences kernel (2.5 KiB of tables each); 16384 two-block frames of 128 KiB: 2: 10.4 ms, 4: 8.5, 8: 8.2, 16: 7.0 (round 1, with the carried bit container: 4 was best)

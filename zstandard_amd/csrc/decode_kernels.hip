@@ -393,27 +393,6 @@ __device__ __forceinline__ uint32_t readHufTableT(DLds &L, const uint8_t *src, u
         if (TO_GLOBAL && wgt[c]) { sStart[myRank] = (uint16_t)myStart; sEntry[myRank] = (uint16_t)((64 * c + lane) | ((tableLog + 1 - wgt[c]) << 8)); }
     }
     wave_sync();
-#ifdef ZS_DEC_ERRLINE
-    {   // debugging aid: the serial statement (old code) must agree on every derived value
-        uint32_t mism = 0;
-        if (lane == 0) {
-            uint32_t rk[16]; for (int i = 0; i < 16; i++) rk[i] = 0;
-            uint32_t wt = 0;
-            for (uint32_t n = 0; n < oSize; n++) { rk[L.u.tb.weights[n]]++; wt += (1u << L.u.tb.weights[n]) >> 1; }
-            const uint32_t tl = zs_highbit(wt) + 1;
-            const uint32_t rs = (1u << tl) - wt, lw = zs_highbit(rs) + 1;
-            if (tl != tableLog) mism = 0x810000u | tl;
-            else if (lw != lastWeight || L.u.tb.weights[oSize] != lw) mism = 0x820000u | (lastWeight << 12) | ((uint32_t)L.u.tb.weights[oSize] << 8) | (oSize & 0xFFu);
-            else {
-                rk[lw]++;
-                uint32_t next = 0; for (uint32_t n = 1; n < tl + 1; n++) { const uint32_t cur = next; next += rk[n] << (n - 1); rk[n] = cur; }
-                for (uint32_t n = 0; n < nbSymbols && !mism; n++) { const uint32_t w = L.u.tb.weights[n]; if (w) { if (rk[w] != L.u.tb.symStart[n]) mism = 0x830000u | n; rk[w] += (1u << w) >> 1; } }
-            }
-        }
-        mism = wave_get(mism, 0);
-        if (mism) return 0xFF000000u | mism;
-    }
-#endif
     PPROF(L, 5);
     if (!TO_GLOBAL)
     for (uint32_t n = 0; n < nbSymbols; n++) {            // uniform loop; lanes fill one symbol's cells together

@@ -111,12 +111,6 @@ struct FseCT {                       // encoding table of one symbol type
 #ifndef ZS_LIT_MINWG
 #define ZS_LIT_MINWG 8
 #endif
-#ifndef ZS_LIT_BITMAP
-#define ZS_LIT_BITMAP 1             // literal gather as a stream compaction of the block (0: sequence by sequence)
-#endif
-#ifndef ZS_LIT_TILES
-#define ZS_LIT_TILES 2               // tiles of 64 sequences the literal gather keeps in flight per wavefront
-#endif
 struct K3Lds {                       // literals kernel
     uint32_t count[256];             // literal histogram
     uint8_t  nbBits[256];
@@ -642,7 +636,7 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
 
 // ---------------------------------------------------------------------------------------------
 // k_encode_literals : one workgroup of 4 wavefronts per block.  Block type (raw for tiny blocks, RLE block),
-// literal gather + histogram (wavefront w takes ranges w and w+4), Huffman lengths by package-merge (256 threads),
+// literal gather (a stream compaction of the block) + histogram, Huffman lengths by package-merge (256 threads),
 // table description (one lane), the 4 Huffman streams (one wavefront each)  -> litSec[], meta.{type, rleByte, litSecSize}
 // ---------------------------------------------------------------------------------------------
 // (k_encode_literals_dict: the same for a dictionary call, whose frame headers carry the dictionary's ID)
@@ -703,28 +697,19 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     if (n < 16) FINISH(0, 0, 0);
 
     if (wave == 0) loadRangesWave(hdr, L.rngN, L.rngCarry, nullptr, L.litBase, L.rngFirst, &L.misc[1], &L.misc[2]);
-#if !ZS_LIT_BITMAP
-    #pragma unroll
-    for (uint32_t k = 0; k < 8; k++) L.u.hist[k][tid] = 0;
-#endif
     __syncthreads();
-    const uint32_t lastLits = L.misc[1];
     const uint32_t nlit = L.misc[2];
 
-    // ---- literals: gather into lits[], histogram.  Range r's own literals start at litBase[r]; the first sequence of a
-    //      range also takes the literals carried over from the ranges before it (they sit right in front). ----
-    // The wavefront's tiles (64 sequences of one of its ranges) are taken ZS_LIT_TILES at a time: the record loads of all of
-    // them are issued together, then their source loads, then the stores.  A tile alone is two dependent memory round
-    // trips, and the loop was bound by exactly that latency.
+    // ---- literals: gather into lits[], histogram ----
     uint32_t *hist = L.u.hist[lane & 7u];                                  // this lane's private histogram
     // a block without a match (a matchless unit: noise, packed data) has its literals where they are: no gather, the source is read in its place
     const bool ungathered = nlit == n;
     const uint8_t *litp = ungathered ? s : lits;
-#if ZS_LIT_BITMAP
     // The literals of a block are its bytes outside every match, in order.  So: a bit per byte, toggled at every match start and
     // end (LDS atomics, lane = sequence); a prefix xor turns the toggles into "inside a match"; the rest is a stream compaction of
     // the source, 16 bytes a lane and round, every lane busy with contiguous, coalesced bytes.  (Taking the literal runs sequence by
-    // sequence - a run of ~3 bytes per lane, its own load and store pieces - was ~300 instructions per 64 sequences, issue-bound.)
+    // sequence - a run of ~3 bytes per lane, its own load and store pieces - was ~300 instructions per 64 sequences, issue-bound; that
+    // form is gone, and with it the only reader of rngCarry, litBase and misc[1], which loadRangesWave still fills.)
     if (!ungathered) {
         uint32_t *T = L.u.gm.T;
         for (uint32_t i = tid; i < 2052; i += 256) T[i] = 0;
@@ -852,90 +837,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
         if (k > 2) atomicAdd(&hist[(w >> 16) & 0xFFu], 1u);
         if (k > 3) atomicAdd(&hist[w >> 24], 1u);
     }
-    (void)lastLits;
     __syncthreads();
-#else
-    {
-        constexpr uint32_t GT = ZS_LIT_TILES;
-        auto rangeN = [&](uint32_t r) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)L.rngN[r]); };
-        uint32_t r = wave, base = 0, done = 0;                               // next tile: range, first sequence (wavefront-uniform)
-        while (r < ZS_WALK_RANGES && rangeN(r) == 0) r += 4;
-        while (r < ZS_WALK_RANGES) {
-            uint32_t tr[GT], tb[GT];                                          // the tiles of this round; tr == ZS_WALK_RANGES: none
-            uint2 rec[GT];                                                    // records as raw words: ll, ml | off, flags
-            #pragma unroll
-            for (uint32_t g = 0; g < GT; g++) {                               // stage 1: the records
-                tr[g] = r; tb[g] = base;
-                rec[g] = make_uint2(0, 0);
-                if (r < ZS_WALK_RANGES) {
-                    const uint32_t ns = rangeN(r), k = base + lane;
-                    if (k < ns) rec[g] = *reinterpret_cast<const uint2 *>(seqBase + (size_t)r * ZS_SEQ_PER_RANGE + L.rngFirst[r] + k);
-                    base += 64;
-                    if (base >= ns) { base = 0; r += 4; while (r < ZS_WALK_RANGES && rangeN(r) == 0) r += 4; }
-                }
-            }
-            uint32_t ll[GT], dstOff[GT], srcPos[GT];
-            uint64_t w0[GT], w1[GT];
-            #pragma unroll
-            for (uint32_t g = 0; g < GT; g++) {                               // stage 2: places in the literal buffer, source loads
-                ll[g] = 0; dstOff[g] = 0; srcPos[g] = 0; w0[g] = 0; w1[g] = 0;
-                if (tr[g] < ZS_WALK_RANGES) {
-                    const uint32_t k = tb[g] + lane;
-                    uint32_t l = (k < rangeN(tr[g])) ? zs_rec_ll(rec[g].x) : 0u;
-                    if (k == 0) l += L.rngCarry[tr[g]];
-                    if (tb[g] == 0) done = L.litBase[tr[g]] - L.rngCarry[tr[g]];
-                    const uint32_t incl = wave_incl_scan(l);
-                    ll[g] = l; dstOff[g] = done + incl - l; srcPos[g] = zs_rec_pos(rec[g].y) - l;
-                    done += wave_last(incl);
-                    // short runs by their own lane (one round of loads), long runs by the whole wavefront
-                    if (l && l <= 16) {
-                        const uint32_t endPos = srcPos[g] + l, skip = 16 - l;
-                        if (endPos >= 16) { w0[g] = zs_load64(s + endPos - 16); w1[g] = zs_load64(s + endPos - 8); }
-                        else for (uint32_t j = 0; j < l; j++) { const uint64_t c = s[srcPos[g] + j]; const uint32_t bi = skip + j; if (bi < 8) w0[g] |= c << (8 * bi); else w1[g] |= c << (8 * (bi - 8)); }
-                    }
-                }
-            }
-            #pragma unroll
-            for (uint32_t g = 0; g < GT; g++) {                               // stage 3: the stores and the histogram
-                if (tr[g] >= ZS_WALK_RANGES) continue;
-                const uint32_t l = ll[g];
-                if (l && l <= 16) {
-                    // the run sits right-aligned in the 16-byte window (w0, w1): it leaves in at most five unaligned stores, biggest
-                    // piece first from its end, and is counted a window word at a time (a loop over its bytes cost the vector ALU
-                    // ~200 instructions a tile at a third of the lanes).  Counting in a pass of its own over the gathered buffer
-                    // (every lane busy) was slower: 0.50 vs 0.48 ms for the kernel
-                    uint8_t *dp = lits + dstOff[g];
-                    uint64_t t1 = w1[g];
-                    if (l == 16) { zs_store64(dp, w0[g]); zs_store64(dp + 8, t1); }
-                    else {
-                        if (l & 8) { zs_store64(dp + l - 8, t1); t1 = w0[g]; }                   // what is left ends at the top of t1
-                        if (l & 4) { zs_store32(dp + (l & 7) - 4, (uint32_t)(t1 >> 32)); t1 <<= 32; }
-                        if (l & 2) { zs_store16(dp + (l & 3) - 2, (uint16_t)(t1 >> 48)); t1 <<= 16; }
-                        if (l & 1) dp[0] = (uint8_t)(t1 >> 56);
-                    }
-                }
-                {
-                    const uint32_t first = (l && l <= 16) ? 16 - l : 16;        // window bytes [first, 16) are literals
-                    const uint32_t wd[4] = { (uint32_t)w0[g], (uint32_t)(w0[g] >> 32), (uint32_t)w1[g], (uint32_t)(w1[g] >> 32) };
-                    #pragma unroll
-                    for (uint32_t i = 0; i < 4; i++) {
-                        if (!__any(first < 4 * i + 4)) continue;
-                        #pragma unroll
-                        for (uint32_t bb = 0; bb < 4; bb++) if (4 * i + bb >= first) atomicAdd(&hist[(wd[i] >> (8 * bb)) & 0xFFu], 1u);
-                    }
-                }
-                uint64_t longm = __ballot(l > 16);
-                while (longm) {
-                    const int t = __builtin_ctzll(longm); longm &= longm - 1;
-                    const uint32_t l2 = wave_get(l, t), d2 = wave_get(dstOff[g], t), s2 = wave_get(srcPos[g], t);
-                    for (uint32_t j = lane; j < l2; j += 64) { const uint8_t c = s[s2 + j]; lits[d2 + j] = c; atomicAdd(&hist[c], 1u); }
-                }
-            }
-        }
-    }
-    for (uint32_t j = tid; j < lastLits; j += 256) { const uint8_t c = s[n - lastLits + j]; lits[nlit - lastLits + j] = c; atomicAdd(&hist[c], 1u); }
-    __syncthreads();
-#endif
     {
         uint32_t c = 0;
         #pragma unroll

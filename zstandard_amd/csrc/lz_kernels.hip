@@ -32,7 +32,7 @@
 // One barrier per interval.  The operand ring holds 3 groups per table; a step's 64 words are ZS_CAND_ROW = 65 words apart, which
 // spreads both the hashers' writes (8 consecutive positions a lane) and the owners' reads (64 consecutive) over all banks and keeps
 // every address of the form base + constant.
-// Runs of one byte (round 4, ZS_CAND_RUNS): zeros in a binary or a line of blanks give consecutive positions the SAME operand - up to 64 lanes
+// Runs of one byte (round 4): zeros in a binary or a line of blanks give consecutive positions the SAME operand - up to 64 lanes
 // of one exchange on one slot, which the LDS serves one after the other (repetitive class: 1.33 ms against 0.46).  What such a run's lanes
 // get is known without asking: every lane but the run's first the entry of the lane below, distance 1, and the slot keeps the run's last
 // entry.  The hasher sees the runs in its bytes (a lane whose G positions + 7 bytes are one byte, and the lanes next to it): it MARKS the
@@ -54,9 +54,6 @@
 #define ZS_CAND_GOF(TLOG) ((TLOG) > ZS_TABLE_LOG_SMALL ? ZS_CAND_G_BIG : ZS_CAND_G)
 #ifndef ZS_CAND_DEPTH
 #define ZS_CAND_DEPTH 2            // a register set holds the source loads of this many groups (two sets: 2 .. 4 groups in flight; 4: 0.64 vs 0.52 ms, the unrolled body grows)
-#endif
-#ifndef ZS_CAND_RUNS
-#define ZS_CAND_RUNS 1             // runs of one byte: the inner positions' exchanges are kept off the run's slot (below); 0: every position exchanges there
 #endif
 #define ZS_CAND_WAVES(NT) (3 * (NT))
 #define ZS_CAND_ROW 65u            // words per step in the operand ring (64 + 1 of padding)
@@ -93,7 +90,7 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
     uint32_t *opnd = candLds + ((size_t)NT << TLOG);                     // [3][NT][GP]
     constexpr uint32_t ROW = ZS_CAND_ROW, GR = G * ROW;                  // words of a group in the ring, per table
     constexpr uint32_t RING = 3u * NT * GR;
-    uint64_t *runMarks = reinterpret_cast<uint64_t *>(opnd + RING + NT * 64u);   // [3][16]: per group in the ring and step, the marked positions (ZS_CAND_RUNS; both tables' hashers see the same: table 0's writes)
+    uint64_t *runMarks = reinterpret_cast<uint64_t *>(opnd + RING + NT * 64u);   // [3][16]: per group in the ring and step, the marked positions (both tables' hashers see the same: table 0's writes)
     uint32_t *runFlag = opnd + RING + NT * 64u + 3u * 16u * 2u;           // [3][2]: the group has marked positions, a word a merger (set by table 0's hasher, cleared by the merger)
     const ZsUnitDesc ud = units[blockIdx.x];
     const uint8_t *s = src + ud.srcOff;
@@ -165,7 +162,6 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
         for (uint32_t i = 2; i <= nGroups + 1; i++) {
             uint32_t mS[H], mL[H];
             mergeRead(i - 2, mS, mL);
-#if ZS_CAND_RUNS
             if (__builtin_amdgcn_readfirstlane((int)runFlag[((i - 2) % 3u) * 2u + tab])) {
                 if (lane == 0) runFlag[((i - 2) % 3u) * 2u + tab] = 0;
                 #pragma unroll
@@ -174,7 +170,6 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
                     if ((marks >> lane) & 1ull) { if (NT > 1) mL[uu] = 1u; else mS[uu] = 1u; }
                 }
             }
-#endif
             mergeStore(i - 2, mS, mL);
             __syncthreads();
         }
@@ -266,7 +261,6 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
                     const uint32_t r = __builtin_amdgcn_alignbit(h, h, 32 - TLOG);
                     ob[u] = (WHOLE || pbase + u < hashable) ? (r & (0xFFFE0000u | ((1u << TLOG) - 1u))) : ((r & 0xFFFE0000u) | (dummyBase + l0 + u));
                 }
-#if ZS_CAND_RUNS
                 // flat: the lane's bytes (its G positions and the 7 behind) are one byte - its positions but the first hash what the position
                 // below them hashes; the first too if the lane below is flat with the same byte (and belongs to the same step of 64 positions).
                 // Groups with such lanes (rare on ordinary data: this wavefront's instructions are the kernel's time as much as the owner's)
@@ -303,7 +297,6 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
                         else reinterpret_cast<uint16_t *>(runMarks + ringSlot * 16u)[lane] = (uint16_t)bits;
                     }
                 }
-#endif
             }
             __syncthreads();
         };
@@ -311,9 +304,7 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
             if (i > nGroups + 1) return;
             if ((i + 1) * GP + 8u <= n) iter(std::true_type{}, i, w); else iter(std::false_type{}, i, w);
         };
-#if ZS_CAND_RUNS
         if (!LONG && lane < 6u) runFlag[lane] = 0;                         // (this wavefront's LDS instructions execute in order; the mergers read after two barriers)
-#endif
         loadM(0, bufA);
         for (uint32_t g0 = 0; g0 <= nGroups + 1; g0 += 2 * M) {
             loadM(g0 + M, bufB);
@@ -382,9 +373,6 @@ k_lz_dict_tables(const uint8_t *__restrict__ pre, uint32_t pfx, uint32_t *__rest
 // Last, the records that count are packed, 1 KiB of source (an OUTPUT RANGE = 1024 / R walk ranges) at a time, into the layout the
 // entropy kernels read: seqAll[block][64 output ranges][256 records] + hdrAll (nseq, trailing, litSum, first = 0).
 // ---------------------------------------------------------------------------------------------
-#ifndef ZS_WALK_MASK
-#define ZS_WALK_MASK 2             // lanes without a candidate, walkers at rest: 0 read along, 1 masked out of the LDS reads (branches), 2 read their own exchange slot (no branch, no conflict)
-#endif
 #ifndef ZS_WALK_MINW
 #define ZS_WALK_MINW 1             // waves per SIMD the small-unit kernel is compiled for (register budget)
 #endif
@@ -702,10 +690,11 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
                 constexpr int SP = (RPL + 3 + 3) / 4;                            // dwords that hold RPL + 3 bytes
                 uint32_t a[SP] = {}, b[SP] = {}, c[SP] = {};
                 // (lanes with nothing to try stay out of the source's banks - an LDS instruction costs what its busiest bank takes, and walkers at rest
-                // all sit at a range end, the same bank - : ZS_WALK_MASK 1 by the exec mask (branches around the reads), 2 by reading their own
-                // slot of the exchange buffer instead (no branch: the reads of a step stay one batch))
-                if (ZS_WALK_MASK != 1 || t0 || t1) {
-                    const bool tr = ZS_WALK_MASK != 2 || t0 || t1;
+                // all sit at a range end, the same bank - : they read their own slot of the exchange buffer instead (no branch, no conflict: the
+                // reads of a step stay one batch.  Masking them out by branches around the reads gave each candidate's reads an LDS round trip of
+                // their own: walk 0.567 -> 0.549 ms without the branches))
+                {
+                    const bool tr = t0 || t1;
                     lds_span<SP>(tr ? lpos(p0) : safeAddr, a);
                     lds_span<SP>(tr ? lpos(t0 ? p0 - rep0 : p0) : safeAddr, b);
                     lds_span<SP>(tr ? lpos(t1 ? p0 - rep1 : p0) : safeAddr, c);
@@ -774,16 +763,12 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
                 const uint32_t q = ip + idx[c];
                 #pragma unroll
                 for (int k = 0; k < 3; k++) { sa[c][k] = 0; sb[c][k] = 0; }
-                if (ZS_WALK_MASK != 1 || have[c]) {
-                    const bool tr = ZS_WALK_MASK != 2 || have[c];
-                    lds_span<3>(tr ? lpos(q - 4) : safeAddr, sa[c]);
-                    lds_span<3>(tr ? lpos(q - off[c] - 4) : safeAddr, sb[c]);
-                }
+                const bool tr = have[c];
+                lds_span<3>(tr ? lpos(q - 4) : safeAddr, sa[c]);
+                lds_span<3>(tr ? lpos(q - off[c] - 4) : safeAddr, sb[c]);
             }
-            if (ZS_WALK_MASK != 1) {
-                #pragma unroll
-                for (uint32_t c = 0; c < CPL; c++) asm volatile("" : "+v"(sa[c][0]), "+v"(sa[c][1]), "+v"(sa[c][2]), "+v"(sb[c][0]), "+v"(sb[c][1]), "+v"(sb[c][2]));
-            }
+            #pragma unroll
+            for (uint32_t c = 0; c < CPL; c++) asm volatile("" : "+v"(sa[c][0]), "+v"(sa[c][1]), "+v"(sa[c][2]), "+v"(sb[c][0]), "+v"(sb[c][1]), "+v"(sb[c][2]));
             #pragma unroll
             for (uint32_t c = 0; c < CPL; c++) {
                 const uint32_t q = ip + idx[c];

@@ -1048,7 +1048,7 @@ extern "C" int zsmi_dbg_copyScratch(zsmi_ctx *c, int which, void *hostDst, size_
     if (!c) return -1;
     (void)hipStreamSynchronize(c->stream);
     zsmi_ctx::Scratch &S = c->scratch;
-    DevBuf *b = which == 0 ? &S.dDist : which == 1 ? &S.dSeqs : which == 2 ? &S.dHdrs : which == 4 ? &S.dDistHi : which == 7 ? &S.dRecs : which == 8 ? &S.dRes : which == 5 ? &c->dec.dLitScratch : which == 9 ? &c->dec.dHufTabs : which == 10 ? &c->dec.dFastDesc : &S.dMetas;
+    DevBuf *b = which == 0 ? &S.dDist : which == 1 ? &S.dSeqs : which == 2 ? &S.dHdrs : which == 4 ? &S.dDistHi : which == 7 ? &S.dRecs : which == 8 ? &S.dRes : which == 5 ? &c->dec.dPoolLit : which == 9 ? &c->dec.dHufTabs : which == 10 ? &c->dec.dFastDesc : &S.dMetas;
     if (bytes > b->cap) return -2;
     return hipMemcpy(hostDst, b->p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }
