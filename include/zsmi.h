@@ -109,6 +109,30 @@ int zsmi_compressBatchDevice_usingDict(zsmi_ctx *ctx, const void *dSrc, const ui
                                        uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
                                        const void *dDict, size_t dictSize);
 
+/* ------------------------------------------------------------------------------------------
+ * Digested dictionaries (ZSTD_createCDict / ZSTD_compress_usingCDict): a dictionary parsed, checked and laid out in device memory once,
+ * then used by many calls.  Unlike the _usingDict calls, a call with a formatted CDict also uses the dictionary's entropy tables: the
+ * first block of a frame may carry Treeless literals and Repeat_Mode sequence tables where those come out smaller, so its frames are
+ * not byte for byte the _usingDict frames (with raw content they are).  They decode with the same dictionary.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zsmi_cdict zsmi_cdict;
+/* dict: raw content or a formatted dictionary (host memory), parsed and checked as zsmi_compress_usingDict does (dictionary_corrupted
+ * before anything runs).  The level is bound here.  Builds the device image on ctx's device and stream and waits for it, once.  NULL on
+ * failure, with the code in *err if err != NULL.  A CDict is read-only after creation: any context of the same device may use it (a
+ * context of another device: parameter_unsupported).  It must outlive the work queued with it: free it after zsmi_sync. */
+zsmi_cdict *zsmi_createCDict(zsmi_ctx *ctx, const void *dict, size_t dictSize, int level, int *err);
+void zsmi_freeCDict(zsmi_cdict *cd);                   /* NULL: nothing */
+unsigned zsmi_getDictID_fromCDict(const zsmi_cdict *cd);   /* 0: raw content, or NULL */
+size_t zsmi_sizeofCDict(const zsmi_cdict *cd);         /* device bytes held */
+/* zsmi_compressBatchDevice with a digested dictionary for every chunk.  Queues its work and returns: no device-to-host copy, no wait for
+ * the stream.  cd == NULL: zsmi_compressBatchDevice at level 3. */
+int zsmi_compressBatchDevice_usingCDict(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                        uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, const zsmi_cdict *cd);
+/* the host-buffer form, and the one-shot form (which runs on the current device) */
+int zsmi_compressBatchHost_usingCDict(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                      uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, const zsmi_cdict *cd);
+size_t zsmi_compress_usingCDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd);
+
 /* Asynchronous on the context's stream.  Each frame i = src[srcOffsets[i] .. +srcSizes[i]) may hold several
  * concatenated / skippable frames (same rules as zsmi_decompress); dstCaps[i] is the room at dstOffsets[i]. */
 int zsmi_decompressBatchDevice(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,

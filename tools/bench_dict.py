@@ -2,13 +2,17 @@
 """GPU box: compression with a dictionary against compression without one (device-resident, per-call wall time, like tools/bench_sizes.py).
 One JSON line per (class, chunk size, level): GiB/s and ratio with and without the dictionary (the class's 64 KiB trained dictionary of
 tests/golden/libzstd_fixtures_dict_compress.npz), and our compressed size over libzstd's with the trained dictionary and with its content
-alone (the first 64 chunks; absent without libzstd).  --kernels: per-kernel times of one dictionary call (zsmi_enableKernelTiming)."""
+alone (the first 64 chunks; absent without libzstd).  The same call with the dictionary digested once (CompressionDict,
+zsmi_compressBatchDevice_usingCDict) is measured next to it in the same process: gib_s_cdict, ratio_cdict, vs_libzstd_trained_cdict, and
+gap_closed = the share of the _usingDict call's excess over libzstd that the CDict call removes.  Every rate is the median of --repeats
+timings of --steps calls; spread_* is (max - min) / median of those timings.  --kernels: per-kernel times of one call of each dictionary
+form (zsmi_enableKernelTiming)."""
 import argparse, ctypes, json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _data as D, _oracle as O, _corpus as C
-from zstandard_amd import BatchCodec, _lib
+from zstandard_amd import BatchCodec, CompressionDict, _lib
 
 FIXC = os.path.join(ROOT, "tests", "golden", "libzstd_fixtures_dict_compress.npz")
 
@@ -41,6 +45,7 @@ def main():
     ap.add_argument("--chunks", default="1024,4096,16384,65536")
     ap.add_argument("--levels", default="3")
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--kernels", action="store_true")
     a = ap.parse_args()
     fix = np.load(FIXC)
@@ -60,14 +65,19 @@ def main():
             ddst = torch.empty(n * bound, dtype=torch.uint8, device=dev); dsz = torch.empty(n, dtype=torch.int32, device=dev)
             for lvl in [int(x) for x in a.levels.split(",")]:
                 rec = {"class": cls, "chunk": cs, "level": lvl, "chunks": n}
-                for tag, dp, dn in (("plain", 0, 0), ("dict", ddict.data_ptr(), len(dic))):
-                    run = lambda: bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), lvl, dp, dn)
+                cdict = CompressionDict(bc, dic, lvl)
+                for tag, dp, dn, cd in (("plain", 0, 0, None), ("dict", ddict.data_ptr(), len(dic), None), ("cdict", 0, len(dic), cdict)):
+                    run = lambda: bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), lvl, dp, dn if dp else 0, cdict=cd)
                     for _ in range(2):
                         run()
-                    bc.sync(); t0 = time.perf_counter()
-                    for _ in range(a.steps):
-                        run()
-                    bc.sync(); dt = (time.perf_counter() - t0) / a.steps
+                    times = []
+                    for _ in range(a.repeats):
+                        bc.sync(); t0 = time.perf_counter()
+                        for _ in range(a.steps):
+                            run()
+                        bc.sync(); times.append((time.perf_counter() - t0) / a.steps)
+                    dt = float(np.median(times))
+                    rec["spread_" + tag] = round((max(times) - min(times)) / dt, 3)
                     sizes = dsz.cpu().numpy().view(np.uint32)
                     assert (sizes < 0xFFFFFF88).all()
                     host = ddst[:min(n, 64) * bound].cpu().numpy()
@@ -80,14 +90,21 @@ def main():
                     if dn:
                         k = min(n, 64); ours = float(sizes[:k].sum())
                         chunks = [data[i * cs:(i + 1) * cs] for i in range(k)]
-                        zt, zc = zstd_sizes(chunks, dic, lvl), zstd_sizes(chunks, content, lvl)
-                        if zt:
-                            rec["vs_libzstd_trained"] = round(ours / zt, 4); rec["vs_libzstd_content"] = round(ours / zc, 4)
+                        if cd is None:
+                            zt, zc = zstd_sizes(chunks, dic, lvl), zstd_sizes(chunks, content, lvl)
+                            if zt:
+                                rec["vs_libzstd_trained"] = round(ours / zt, 4); rec["vs_libzstd_content"] = round(ours / zc, 4)
+                        elif zt:
+                            rec["vs_libzstd_trained_cdict"] = round(ours / zt, 4)
+                            gap = rec["vs_libzstd_trained"] - 1.0
+                            rec["gap_closed"] = round((rec["vs_libzstd_trained"] - rec["vs_libzstd_trained_cdict"]) / gap, 3) if gap > 0 else None
                         if a.kernels:
                             bc.enable_timing(True); run(); bc.sync()
-                            rec["kernels_ms"] = {k2: round(v[0] * 1e3, 3) for k2, v in bc.kernel_times().items()}
+                            rec["kernels_ms" + ("_cdict" if cd else "")] = {k2: round(v[0] * 1e3, 3) for k2, v in bc.kernel_times().items()}
                             bc.enable_timing(False)
+                bc.sync(); cdict.close()
                 rec["dict_over_plain"] = round(rec["gib_s_dict"] / rec["gib_s_plain"], 3)
+                rec["cdict_over_dict"] = round(rec["gib_s_cdict"] / rec["gib_s_dict"], 3)
                 print(json.dumps(rec), flush=True)
             del ddst, dsz
 

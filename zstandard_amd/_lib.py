@@ -99,6 +99,13 @@ def lib():
     L.zsmi_compressBatchHost.restype = i32; L.zsmi_compressBatchHost.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32]
     L.zsmi_compressBatchDevice_usingDict.restype = i32; L.zsmi_compressBatchDevice_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32, vp, sz]
     L.zsmi_compressBatchHost_usingDict.restype = i32; L.zsmi_compressBatchHost_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32, vp, sz]
+    L.zsmi_createCDict.restype = vp; L.zsmi_createCDict.argtypes = [vp, vp, sz, i32, ctypes.POINTER(i32)]
+    L.zsmi_freeCDict.restype = None; L.zsmi_freeCDict.argtypes = [vp]
+    L.zsmi_getDictID_fromCDict.restype = ctypes.c_uint; L.zsmi_getDictID_fromCDict.argtypes = [vp]
+    L.zsmi_sizeofCDict.restype = sz; L.zsmi_sizeofCDict.argtypes = [vp]
+    L.zsmi_compressBatchDevice_usingCDict.restype = i32; L.zsmi_compressBatchDevice_usingCDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.zsmi_compressBatchHost_usingCDict.restype = i32; L.zsmi_compressBatchHost_usingCDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.zsmi_compress_usingCDict.restype = sz; L.zsmi_compress_usingCDict.argtypes = [vp, sz, vp, sz, vp]
     L.zsmi_decompressBatchHost.restype = i32; L.zsmi_decompressBatchHost.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_decompressBatchHost_usingDict.restype = i32; L.zsmi_decompressBatchHost_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
     L.zsmi_decompressBatchDevice_usingDict.restype = i32; L.zsmi_decompressBatchDevice_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
@@ -133,6 +140,8 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_compressBatchDevice", "zsmi_decompressBatchDevice", "zsmi_compressBatchHost", "zsmi_decompressBatchHost",
            "zsmi_decompress_usingDict", "zsmi_decompressBatchDevice_usingDict", "zsmi_decompressBatchHost_usingDict",
            "zsmi_compress_usingDict", "zsmi_compressBatchDevice_usingDict", "zsmi_compressBatchHost_usingDict",
+           "zsmi_createCDict", "zsmi_freeCDict", "zsmi_getDictID_fromCDict", "zsmi_sizeofCDict",
+           "zsmi_compressBatchDevice_usingCDict", "zsmi_compressBatchHost_usingCDict", "zsmi_compress_usingCDict",
            "zsmi_packFramesDevice", "zsmi_enableKernelTiming", "zsmi_getKernelTimes", "zsmi_versionString", "zsmi_decodeScratchBytes", "zsmi_shutdown",
            "zsmi_seekableBound", "zsmi_compressSeekable", "zsmi_compressSeekableDevice", "zsmi_decompressSeekable", "zsmi_decompressSeekableDevice",
            "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo",

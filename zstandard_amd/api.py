@@ -8,6 +8,8 @@
   SeekableArchive     random access into a seekable archive (zstd's seekable format: independent frames + a seek table), made by
                       ZstdCompressor.compress_seekable or BatchCodec.compress_seekable_device.
   BatchCodec          the batch hot path on device memory (torch tensors are only a handle to device memory here).
+  CompressionDict     a digested dictionary (zsmi_createCDict): parsed and laid out on the device once, used by many calls; with a
+                      formatted dictionary its entropy tables code the first block of a frame where that is smaller.
   train_dictionary, finalize_dictionary, get_dict_id
                       zstd dictionaries made on the GPU (fastCover and ZDICT_finalizeDictionary; zdict.h's parameters).
 
@@ -90,13 +92,49 @@ class ZstdDecompressor:
         return int(L.zsmi_getDecompressedSize(src, len(src)))
 
 
+class CompressionDict:
+    """A digested dictionary (ZSTD_createCDict): `dictionary` (raw content or a formatted dictionary) parsed, checked and laid out in the
+    device memory of `codec`'s device once, with the level bound.  Any BatchCodec of that device may use it (cdict=); it must stay open
+    until the work queued with it is done (BatchCodec.sync)."""
+
+    def __init__(self, codec, dictionary, level=3):
+        self.L = codec.L
+        self.level = level
+        err = ctypes.c_int(0)
+        dic = bytes(dictionary)
+        self.handle = self.L.zsmi_createCDict(codec.ctx, dic, len(dic), level, ctypes.byref(err))
+        if not self.handle:
+            raise RuntimeError(f"zsmi_createCDict: error {err.value} ({_error_name(self.L, err.value)})")
+
+    @property
+    def dict_id(self) -> int:
+        return int(self.L.zsmi_getDictID_fromCDict(self.handle))
+
+    @property
+    def device_bytes(self) -> int:
+        return int(self.L.zsmi_sizeofCDict(self.handle))
+
+    def close(self):
+        if self.handle:
+            self.L.zsmi_freeCDict(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ZstdCompressor:
     """One frame per call; level <= 2 fast parameters, level >= 3 default parameters.  dictionary: raw content or a formatted
-    dictionary (ZSTD_compress_usingDict); the frames decode with the same dictionary (zsmi_decompress_usingDict)."""
+    dictionary (ZSTD_compress_usingDict), or a CompressionDict (ZSTD_compress_usingCDict: its level holds); the frames decode with the
+    same dictionary (zsmi_decompress_usingDict)."""
 
     def __init__(self, level=3, dictionary=None):
         self.level = level
-        self.dictionary = bytes(dictionary) if dictionary else b""
+        self.cdict = dictionary if isinstance(dictionary, CompressionDict) else None
+        self.dictionary = bytes(dictionary) if dictionary and not self.cdict else b""
 
     @staticmethod
     def compressBound(n: int) -> int:
@@ -107,7 +145,9 @@ class ZstdCompressor:
         s, sn = _buf(src)
         cap = L.zsmi_compressBound(sn)
         out = ctypes.create_string_buffer(cap)
-        if self.dictionary:
+        if self.cdict:
+            r = L.zsmi_compress_usingCDict(out, cap, s, sn, self.cdict.handle)
+        elif self.dictionary:
             r = L.zsmi_compress_usingDict(out, cap, s, sn, self.dictionary, len(self.dictionary), self.level)
         else:
             r = L.zsmi_compress(out, cap, s, sn, self.level)
@@ -120,7 +160,7 @@ class ZstdCompressor:
         compress() would compress that slice, then the seek table (checksum: each entry carries the low 32 bits of the slice's XXH64).
         Any zstd decoder reads it as concatenated frames; SeekableArchive reads ranges of it."""
         L = _lib.lib()
-        if self.dictionary:
+        if self.dictionary or self.cdict:
             raise RuntimeError(_error_name(L, 40))                     # parameter_unsupported: no dictionaries in seekable archives
         s, sn = _buf(src)
         cap = _raise_if_error(L, L.zsmi_seekableBound(sn, frame_size, int(bool(checksum))))
@@ -237,10 +277,17 @@ class BatchCodec:
     def _p(a):
         return a.ctypes.data_as(ctypes.c_void_p)
 
-    def compress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, d_dst_sizes_ptr, level=3, d_dict_ptr=0, dict_size=0):
-        """d_dict_ptr / dict_size: one dictionary (device memory) for every chunk of the call (zsmi_compressBatchDevice_usingDict)"""
+    def compress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, d_dst_sizes_ptr, level=3, d_dict_ptr=0, dict_size=0, cdict=None):
+        """d_dict_ptr / dict_size: one dictionary (device memory) for every chunk of the call (zsmi_compressBatchDevice_usingDict).
+        cdict: a CompressionDict instead (zsmi_compressBatchDevice_usingCDict: its level holds; queued without a wait)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        if cdict is not None:
+            rc = self.L.zsmi_compressBatchDevice_usingCDict(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
+                                                            ctypes.c_void_p(d_dst_ptr), self._p(do), ctypes.c_void_p(d_dst_sizes_ptr), cdict.handle)
+            if rc:
+                raise RuntimeError(f"zsmi_compressBatchDevice_usingCDict: error {rc}")
+            return
         if d_dict_ptr and dict_size:
             rc = self.L.zsmi_compressBatchDevice_usingDict(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
                                                            ctypes.c_void_p(d_dst_ptr), self._p(do), ctypes.c_void_p(d_dst_sizes_ptr), level,
@@ -291,9 +338,9 @@ class BatchCodec:
             raise RuntimeError(f"zsmi_decompressSeekableDevice: {_error_name(self.L, rc)}")
         return written.value
 
-    def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b""):
+    def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b"", cdict=None):
         """returns (arena uint8, dst_offsets uint64, dst_sizes uint32).  dictionary: one for every chunk (raw content or a formatted
-        dictionary; zsmi_compressBatchHost_usingDict)"""
+        dictionary; zsmi_compressBatchHost_usingDict).  cdict: a CompressionDict instead (zsmi_compressBatchHost_usingCDict: its level holds)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         n = len(ss)
         bounds = np.array([self.L.zsmi_compressBound(int(s)) for s in ss], dtype=np.uint64) if n < 4096 else \
@@ -303,6 +350,11 @@ class BatchCodec:
             do[1:] = np.cumsum(bounds)[:-1]
         arena = np.zeros(int(bounds.sum()), dtype=np.uint8)
         dsz = np.zeros(n, dtype=np.uint32)
+        if cdict is not None:
+            rc = self.L.zsmi_compressBatchHost_usingCDict(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), cdict.handle)
+            if rc:
+                raise RuntimeError(f"zsmi_compressBatchHost_usingCDict: error {rc}")
+            return arena, do, dsz
         if dictionary:
             dbuf = np.frombuffer(bytes(dictionary), dtype=np.uint8)
             rc = self.L.zsmi_compressBatchHost_usingDict(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), level,

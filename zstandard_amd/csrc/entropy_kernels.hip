@@ -4,6 +4,7 @@
 //                                                                    writes the frame of a one-block chunk as its workgroup finishes
 //   k_assemble_frames   (1 chunk per workgroup)                  -> frames of chunks of several blocks
 //   k_train_stats       (1 block per workgroup)                  -> the dictionary trainer's finalize: counts of what the sequences kernel coded
+//   k_cdict_tables      (one workgroup)                          -> a digested dictionary's entropy tables in encoder form (ZsCDictTables)
 //   k_pack_offsets, k_pack_copy                                  -> frames in bound-sized slots packed back to back
 // Scalar statement of the same algorithm: oracle/zso_encoder.c (compressBlock and below); the two
 // must agree bit for bit.  Every piece is the format-inverse of a function of the reference decoder:
@@ -106,6 +107,27 @@ struct FseCT {                       // encoding table of one symbol type
     uint32_t tableLog;
     uint32_t rle;
 };
+// A digested dictionary (zsmi_cdict): the entropy tables of a formatted dictionary as the decoder loads them (parsed on the host), and
+// their encoder form (k_cdict_tables), which the _cdict kernels read for a frame's first block: Repeat_Mode sequences, Treeless literals.
+#define ZS_COST_NONE 0xFFFFu         // a symbol the table cannot code (probability 0)
+struct ZsCDictEntropy {              // kernel argument of k_cdict_tables
+    uint8_t weights[256]; uint32_t nWeights, hufLog;           // Huffman weights, the implied last one included
+    int16_t norm[3][64]; uint32_t maxSym[3], tableLog[3];      // normalised counts of LL, OF, ML (-1: low probability)
+};
+struct ZsCDictTables {
+    FseCT ct[3];                     // LL, OF, ML
+    uint16_t cost[3][64];            // bits to code symbol s under ct[t], in 1/256 bit (fseSymbolCost); ZS_COST_NONE
+    uint32_t hufCodeNb[256];         // code | length << 16, as K3Lds::codeNb; 0: the byte has no code
+    uint32_t hufLog;                 // 0: no Huffman table to code with (codes longer than ZS_HUF_MAXBITS are not used)
+};
+// bits a symbol of normalised count nv >= 1 costs in a table of 2^tableLog cells, in 1/256 bit: exact where nv is a power of two, linear
+// between two of them (the state's low bits are maxBitsOut or maxBitsOut - 1 by where the state lies)
+__device__ __forceinline__ uint32_t fseSymbolCost(uint32_t nv, uint32_t tableLog)
+{
+    nv = max(nv, 1u);
+    const uint32_t maxBitsOut = nv > 1 ? tableLog - zs_highbit(nv - 1) : tableLog;
+    return maxBitsOut * 256u - ((((nv << maxBitsOut) - (1u << tableLog)) << 8) >> tableLog);
+}
 // workgroups per CU the literals kernel is compiled for: 8 caps it at 64 VGPRs, so the 16 blocks a CU gets per 4096-block
 // batch run in two full rounds (measured alone: 0.89 ms uncapped (88 VGPRs, 5 per CU), 0.74 at 6, 0.57 at 8 despite spills)
 #ifndef ZS_LIT_MINWG
@@ -639,14 +661,17 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
 // literal gather (a stream compaction of the block) + histogram, Huffman lengths by package-merge (256 threads),
 // table description (one lane), the 4 Huffman streams (one wavefront each)  -> litSec[], meta.{type, rleByte, litSecSize}
 // ---------------------------------------------------------------------------------------------
-// (k_encode_literals_dict: the same for a dictionary call, whose frame headers carry the dictionary's ID)
+// (k_encode_literals_dict: the same for a dictionary call, whose frame headers carry the dictionary's ID; k_encode_literals_cdict: with a
+//  digested dictionary's Huffman codes besides - CD: the first block of a frame is coded as Treeless literals (type 3) iff every literal byte
+//  has a code and that section is strictly smaller than the one the rules below produce)
 #define ZS_LIT_PARAMS const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, \
                       const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
                       uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, uint8_t *__restrict__ litSecAll, \
                       ZsBlockMeta *__restrict__ metas, int stopAt, \
                       const ZsChunkDesc *__restrict__ chunks, const uint8_t *__restrict__ seqSecAll, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes
 #define ZS_LIT_ARGS src, blocks, seqAll, hdrAll, litsAll, streamAll, litSecAll, metas, stopAt, chunks, seqSecAll, dst, dstSizes
-__device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t dictID)
+template <bool CD>
+__device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictTables *__restrict__ cdt)
 {
     __shared__ K3Lds L;
     const uint32_t blk = blockIdx.x;
@@ -877,6 +902,33 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
         litSecSize = (nlit < 32) ? 2 : (nlit < 4096 ? 3 : 4);
         done = true;
     }
+    // CD, a frame's first block: the size of the section as Treeless literals, exact - the histogram says whether every byte has a code, a pass
+    // over the literals gives each stream its bits (a stream: its bits and the end mark, in whole bytes).  0: not to be had, or not smaller
+    // than the literals themselves
+    uint32_t tlSize = 0;
+    if constexpr (CD) {
+        const uint32_t lhSize = 3 + (nlit >= 1024) + (nlit >= 16384);
+        const bool single = nlit < 256;
+        if (!done && bd.firstInChunk && nlit > 0 && !ZS_STOPPED && cdt->hufLog) {
+            const uint32_t cn = cdt->hufCodeNb[tid];
+            L.nbBits[tid] = (uint8_t)(cn >> 16);                         // (free until the code lengths are made)
+            if (__syncthreads_and(L.count[tid] == 0 || (cn >> 16) != 0)) {
+                const uint32_t seg = (nlit + 3) / 4;
+                const uint32_t from = single ? 0u : wave * seg, len = single ? (wave == 0 ? nlit : 0u) : ((wave < 3) ? seg : nlit - 3 * seg);
+                uint32_t bits = 0;
+                for (uint32_t j = 4 * lane; j < len; j += 256) {
+                    if (j + 4 <= len) { const uint32_t w = zs_load32(litp + from + j); bits += L.nbBits[w & 0xFFu] + L.nbBits[(w >> 8) & 0xFFu] + L.nbBits[(w >> 16) & 0xFFu] + L.nbBits[w >> 24]; }
+                    else for (uint32_t q = j; q < len; q++) bits += L.nbBits[litp[from + q]];
+                }
+                bits = wave_sum(bits);
+                if (lane == 0) L.misc[8 + wave] = (bits + 8u) >> 3;
+                __syncthreads();
+                const uint32_t csz = single ? L.misc[8] : 6u + L.misc[8] + L.misc[9] + L.misc[10] + L.misc[11];
+                if (lhSize + csz <= cap && csz + lhSize < nlit + (3 - (nlit < 32) - (nlit < 4096)) && (single || csz >= 10)) tlSize = lhSize + csz;
+            }
+            __syncthreads();
+        }
+    }
     if (!done && nlit >= 64 && !flatCounts) {
         const uint32_t tableLog = huffLengths(L, maxSym, ZS_HUF_MAXBITS);
         if (ZS_STOP_AT(2)) FINISH(0, 0, 0);    // stop after the code lengths
@@ -894,7 +946,11 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
         }
         const uint32_t codeBits = L.misc[12] + L.misc[13] + L.misc[14] + L.misc[15];
         const bool hopeless = lhSize + 1u + (single ? 0u : 6u) + (codeBits >> 3) >= nlit + (3 - (nlit < 32) - (nlit < 4096));
-        if (!hopeless) {
+        // CD: a section of this block's own code holds at least its header, a description of two bytes and the code's bits; where the Treeless
+        // section is smaller than that, it is smaller than whatever would be made here
+        bool beaten = false;
+        if constexpr (CD) beaten = tlSize && tlSize < lhSize + 2u + (single ? 0u : 6u) + (codeBits >> 3);
+        if (!hopeless && !beaten) {
         huffCodesAndWeights(L, maxSym, tableLog);
         if (wave == 0) { const uint32_t hs_ = writeHuffHeaderWave(L, payload + lhSize, cap - lhSize, maxSym, tableLog); if (lane == 0) L.misc[0] = hs_; }
         __syncthreads();
@@ -935,6 +991,47 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
         }
         }
     }
+    if constexpr (CD) {
+        if (tlSize && (!done || tlSize < litSecSize)) {                // (no section of its own: raw literals, larger by tlSize's making)
+            // the streams under the dictionary's codes, as the section above lays them out, behind no description
+            const uint32_t lhSize = 3 + (nlit >= 1024) + (nlit >= 16384);
+            const bool single = nlit < 256;
+            L.codeNb[tid] = cdt->hufCodeNb[tid];
+            done = false;
+            __syncthreads();
+            const uint32_t seg = (nlit + 3) / 4;
+            if (single) { if (wave == 0) { const uint32_t z = huffEncodeStream(L, L.u.tile[0], streams, litp, 0, nlit); if (lane == 0) L.misc[8] = z; } }
+            else {
+                const uint32_t len = (wave < 3) ? seg : nlit - 3 * seg;
+                const uint32_t z = huffEncodeStream(L, L.u.tile[wave], streams + wave * ZS_STREAM_STRIDE, litp, wave * seg, len);
+                if (lane == 0) L.misc[8 + wave] = z;
+            }
+            __syncthreads();
+            const uint32_t ssz0 = L.misc[8], ssz1 = single ? 0 : L.misc[9], ssz2 = single ? 0 : L.misc[10], ssz3 = single ? 0 : L.misc[11];
+            const bool ok = single || (ssz0 <= 65535 && ssz1 <= 65535 && ssz2 <= 65535 && ssz3 <= 65535);
+            const uint32_t csz = (single ? ssz0 : 6 + ssz0 + ssz1 + ssz2 + ssz3);
+            if (ok && lhSize + csz <= cap && csz + lhSize < nlit + (3 - (nlit < 32) - (nlit < 4096)) && (single || csz >= 10)) {
+                uint8_t *op = payload + lhSize;
+                if (!single) {
+                    if (tid == 0) { op[0] = (uint8_t)ssz0; op[1] = (uint8_t)(ssz0 >> 8); op[2] = (uint8_t)ssz1; op[3] = (uint8_t)(ssz1 >> 8); op[4] = (uint8_t)ssz2; op[5] = (uint8_t)(ssz2 >> 8); }
+                    op += 6;
+                }
+                const uint32_t ssz[4] = { ssz0, ssz1, ssz2, ssz3 };
+                for (uint32_t k = 0; k < (single ? 1u : 4u); k++) {
+                    const uint8_t *from = streams + k * ZS_STREAM_STRIDE;
+                    zs_block_copy(op, from, ssz[k], tid, 256);
+                    op += ssz[k];
+                }
+                if (tid == 0) {
+                    if (lhSize == 3) { const uint32_t h = 3 + ((single ? 0u : 1u) << 2) + (nlit << 4) + (csz << 14); payload[0] = (uint8_t)h; payload[1] = (uint8_t)(h >> 8); payload[2] = (uint8_t)(h >> 16); }
+                    else if (lhSize == 4) { const uint32_t h = 3 + (2 << 2) + (nlit << 4) + (csz << 18); payload[0] = (uint8_t)h; payload[1] = (uint8_t)(h >> 8); payload[2] = (uint8_t)(h >> 16); payload[3] = (uint8_t)(h >> 24); }
+                    else { const uint32_t h = 3 + (3 << 2) + (nlit << 4) + (csz << 22); payload[0] = (uint8_t)h; payload[1] = (uint8_t)(h >> 8); payload[2] = (uint8_t)(h >> 16); payload[3] = (uint8_t)(h >> 24); payload[4] = (uint8_t)(csz >> 10); }
+                }
+                litSecSize = lhSize + csz;
+                done = true;
+            }
+        }
+    }
     if (!done) {
         const uint32_t lh = 1 + (nlit > 31) + (nlit > 4095);
         if (tid == 0) {
@@ -948,8 +1045,9 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     FINISH(2, litSecSize, 0);
     #undef FINISH
 }
-extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS) { encode_literals_block(ZS_LIT_ARGS, 0u); }
-extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals_dict(ZS_LIT_PARAMS, uint32_t dictID) { encode_literals_block(ZS_LIT_ARGS, dictID); }
+extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS) { encode_literals_block<false>(ZS_LIT_ARGS, 0u, nullptr); }
+extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals_dict(ZS_LIT_PARAMS, uint32_t dictID) { encode_literals_block<false>(ZS_LIT_ARGS, dictID, nullptr); }
+extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals_cdict(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictTables *__restrict__ cdt) { encode_literals_block<true>(ZS_LIT_ARGS, dictID, cdt); }
 
 // ---------------------------------------------------------------------------------------------
 // k_encode_sequences : one wavefront per block.  Repcodes (parallel: two last-index scans), code
@@ -1062,8 +1160,12 @@ static_assert(3u * ZS_CHAIN_CODES <= ZS_BLOCK_MAX + 64u && 3u * 2u * ZS_CHAIN_CO
                       uint8_t *__restrict__ seqSecAll, ZsBlockMeta *__restrict__ metas, int stopAt, uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, \
                       uint2 *__restrict__ packRecAll
 #define ZS_SEQ_ARGS blocks, nBlocks, seqAll, hdrAll, seqSecAll, metas, stopAt, litsAll, streamAll, packRecAll
-template <int G>
-__device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint32_t rep0, const uint32_t rep1, const uint32_t rep2)
+// CD (k_encode_sequences_cdict: a digested dictionary's tables in cdt): for the first block of a frame each of LL / OF / ML is coded in
+// Repeat_Mode (3) with the dictionary's table iff that table codes every code present and its estimate, the sum of count x cost, is strictly
+// below the estimate of what the rules below pick: RLE one byte, the predefined table its own sum of count x cost, a new table its
+// description's bytes plus that sum over its normalised counts (in 1/256 bit throughout)
+template <int G, bool CD>
+__device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint32_t rep0, const uint32_t rep1, const uint32_t rep2, const ZsCDictTables *__restrict__ cdt)
 {
     __shared__ SeqLds LS[G];
     const uint32_t wave = threadIdx.x >> 6;
@@ -1196,6 +1298,15 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
         uint32_t pos = hdrBytes + 1;                        // after nbSeq and the modes byte
         uint32_t modeByte = 0;
         bool fail = false;
+        // (CD) the dictionary's table t beats an estimate of est: it is loaded in place of the one that would be built
+        auto repeatBeats = [&](uint32_t t, uint32_t c, uint32_t est) -> bool {
+            const uint32_t dc = cdt->cost[t][lane];
+            if (__any(c != 0 && dc == ZS_COST_NONE)) return false;
+            if (wave_sum(c * dc) >= est) return false;
+            const uint32_t *from = reinterpret_cast<const uint32_t *>(&cdt->ct[t]); uint32_t *to = reinterpret_cast<uint32_t *>(&L.ct[t]);
+            for (uint32_t i = lane; i < sizeof(FseCT) / 4; i += 64) to[i] = from[i];
+            return true;
+        };
         #pragma unroll 1
         for (uint32_t t = 0; t < 3; t++) {
             const uint32_t *count = L.count + 64 * t;
@@ -1211,11 +1322,21 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
             if (largest == nseq) {
                 mode = 1;
                 if (pos >= cap) { fail = true; break; }
+                if constexpr (CD) { if (bd.firstInChunk && repeatBeats(t, c, 8u * 256u)) mode = 3; }
+                if (mode == 1) {
                 if (lane == 0) { out[pos] = (uint8_t)maxSym; ct.rle = 1; ct.tableLog = 0; }
                 pos += 1;
+                }
             } else if (nseq < 64 && maxSym <= defMax) {
                 mode = 0;
-                if (lane == 0) {
+                if constexpr (CD) {
+                    if (bd.firstInChunk) {
+                        const int16_t *defNorm = t == 0 ? c_LL_defaultNorm : (t == 1 ? c_OF_defaultNorm : c_ML_defaultNorm);
+                        const int nv = lane <= defMax ? defNorm[lane] : 1;
+                        if (repeatBeats(t, c, wave_sum(c * fseSymbolCost((uint32_t)(nv < 0 ? 1 : nv), defLog)))) mode = 3;
+                    }
+                }
+                if (mode == 0 && lane == 0) {
                     const int16_t *defNorm = t == 0 ? c_LL_defaultNorm : (t == 1 ? c_OF_defaultNorm : c_ML_defaultNorm);
                     for (uint32_t i = 0; i <= defMax; i++) L.norm[i] = defNorm[i];
                     buildCTable(ct, L.u.build.tableSymbol, L.u.build.cumul, L.norm, defMax, defLog);
@@ -1232,9 +1353,14 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
                 wave_sync();
                 const uint32_t h = L.misc[0];
                 if (!h) { fail = true; break; }
-                pos += h;
                 mode = 2;
+                if constexpr (CD) {
+                    if (bd.firstInChunk && repeatBeats(t, c, h * 8u * 256u + wave_sum(c ? c * fseSymbolCost((uint32_t)L.norm[lane], tableLog) : 0u))) mode = 3;
+                }
+                if (mode == 2) {
+                pos += h;
                 buildCTableWave(L, ct, L.norm, maxSym, tableLog);
+                }
             }
             modeByte |= mode << (6 - 2 * t);
             wave_sync();
@@ -1466,9 +1592,11 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
     if (lane == 0 && exists) { metas[blk].seqSecSize = result; metas[blk].seqHdrSize = (secHdr == 0xFFFFFFFFu) ? result : secHdr; metas[blk].seqGap = secGap; }
 }
 template <int G>
-__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS) { encode_sequences_block<G>(ZS_SEQ_ARGS, 1u, 4u, 8u); }
+__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS) { encode_sequences_block<G, false>(ZS_SEQ_ARGS, 1u, 4u, 8u, nullptr); }
 template <int G>
-__global__ void __launch_bounds__(64 * G) k_encode_sequences_dict(ZS_SEQ_PARAMS, uint4 reps) { encode_sequences_block<G>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z); }
+__global__ void __launch_bounds__(64 * G) k_encode_sequences_dict(ZS_SEQ_PARAMS, uint4 reps) { encode_sequences_block<G, false>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, nullptr); }
+template <int G>
+__global__ void __launch_bounds__(64 * G) k_encode_sequences_cdict(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictTables *__restrict__ cdt) { encode_sequences_block<G, true>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, cdt); }
 
 // ---------------------------------------------------------------------------------------------
 // k_assemble_frames : one workgroup per chunk.  frame = magic + FHD + FCS (single segment)
@@ -1537,6 +1665,34 @@ __global__ void __launch_bounds__(256) k_train_stats(const uint8_t *__restrict__
     for (uint32_t b = tid; b < n; b += 256) if (!((cov[b >> 5] >> (b & 31u)) & 1u)) atomicAdd(&hist[s[b]], 1u);
     __syncthreads();
     for (uint32_t i = tid; i < kTrainStatWords; i += 256) if (hist[i]) atomicAdd(&stats[i], hist[i]);
+}
+
+// A digested dictionary's entropy tables in encoder form, once per dictionary, by the encoder's own routines: the Huffman codes in the decoder's
+// order from the weights (huffCodesAndWeights), the three encoding tables by the lane-0 buildCTable (a trained dictionary's counts hold -1
+// entries, which buildCTableWave does not take), and the cost of every symbol.  One workgroup of 256 threads; wavefront t < 3 makes table t.
+__global__ void __launch_bounds__(256) k_cdict_tables(const ZsCDictEntropy e, ZsCDictTables *__restrict__ out)
+{
+    __shared__ K3Lds L;
+    __shared__ struct { FseCT ct; int16_t norm[64]; uint8_t tableSymbol[512]; uint32_t cumul[66]; } F[3];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const bool huf = e.hufLog != 0 && e.hufLog <= ZS_HUF_MAXBITS;
+    const uint32_t w = (huf && tid < e.nWeights) ? e.weights[tid] : 0u;
+    L.nbBits[tid] = (uint8_t)(w ? e.hufLog + 1 - w : 0u);
+    __syncthreads();
+    if (huf) huffCodesAndWeights(L, 255, e.hufLog);
+    out->hufCodeNb[tid] = w ? L.codeNb[tid] : 0u;
+    if (tid == 0) out->hufLog = huf ? e.hufLog : 0u;
+    if (wave < 3) {
+        const uint32_t maxSym = e.maxSym[wave], tableLog = e.tableLog[wave];
+        const int nv = lane <= maxSym ? e.norm[wave][lane] : 0;
+        F[wave].norm[lane] = (int16_t)nv;
+        wave_sync();
+        if (lane == 0) buildCTable(F[wave].ct, F[wave].tableSymbol, F[wave].cumul, F[wave].norm, maxSym, tableLog);
+        wave_sync();
+        const uint32_t *from = reinterpret_cast<const uint32_t *>(&F[wave].ct); uint32_t *to = reinterpret_cast<uint32_t *>(&out->ct[wave]);
+        for (uint32_t i = lane; i < sizeof(FseCT) / 4; i += 64) to[i] = from[i];
+        out->cost[wave][lane] = (uint16_t)(nv == 0 ? ZS_COST_NONE : fseSymbolCost((uint32_t)(nv < 0 ? 1 : nv), tableLog));
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -194,7 +194,8 @@ extern "C" int zsmi_getKernelTimes(zsmi_ctx *c, zsmi_kernel_time *out, int maxEn
 // A formatted dictionary (magic 0xEC30A437, >= 8 bytes) gives the frames its ID and their first blocks its recent offsets; its entropy
 // section is parsed only to find where the content starts and to refuse, with dictionary_corrupted, exactly what LoadEntropy
 // (:2378-2450) refuses (its checks restated on the host: readNCount, the Huffman weights and their FSE header, the recent offsets).
-// Any other bytes are raw content: offsets {1, 4, 8}, no ID.  The encoder uses none of the dictionary's tables.
+// Any other bytes are raw content: offsets {1, 4, 8}, no ID.  The _usingDict calls use none of the dictionary's tables; a digested
+// dictionary (zsmi_createCDict) takes them from the same parse (ZsCDictEntropy).
 // ---------------------------------------------------------------------------------------------
 namespace hdict {
 static uint32_t hb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
@@ -311,8 +312,9 @@ static size_t fseWeights(uint8_t *dst, size_t cap, const uint8_t *src, size_t n)
     }
     return (size_t)(op - dst);
 }
-// EntropyCommon.cs:198-269 (HUF_readStats) with the table-log limit of HUF_readDTableX4: bytes of the table description, or kErr
-static size_t hufTable(const uint8_t *ip, size_t n)
+// EntropyCommon.cs:198-269 (HUF_readStats) with the table-log limit of HUF_readDTableX4: bytes of the table description, or kErr.
+// ent: receives the weights (the implied last one included) and the table log
+static size_t hufTable(const uint8_t *ip, size_t n, ZsCDictEntropy *ent = nullptr)
 {
     uint8_t w[256]; size_t iSize, oSize;
     if (!n) return kErr;
@@ -335,18 +337,19 @@ static size_t hufTable(const uint8_t *ip, size_t n)
     if ((1u << hb(rest)) != rest) return kErr;
     rank[hb(rest) + 1]++;
     if (rank[1] < 2 || (rank[1] & 1)) return kErr;
+    if (ent) { memcpy(ent->weights, w, oSize); ent->weights[oSize] = (uint8_t)(hb(rest) + 1); ent->nWeights = (uint32_t)oSize + 1; ent->hufLog = tableLog; }
     return iSize + 1;
 }
 }
 // 0, or ZSMI_error_dictionary_corrupted
-static int parseCompressDict(const uint8_t *d, size_t size, ZsCompressDict &out)
+static int parseCompressDict(const uint8_t *d, size_t size, ZsCompressDict &out, ZsCDictEntropy *ent = nullptr)
 {
     out = ZsCompressDict();
     if (size >= 8 && h_rd32(d) == 0xEC30A437u) {
         out.dictID = h_rd32(d + 4);
         if (size <= 8) return ZSMI_error_dictionary_corrupted;
         const uint8_t *p = d + 8, *const end = d + size;
-        const size_t hs = hdict::hufTable(p, (size_t)(end - p));
+        const size_t hs = hdict::hufTable(p, (size_t)(end - p), ent);
         if (hs == hdict::kErr) return ZSMI_error_dictionary_corrupted;
         p += hs;
         const uint32_t maxes[3] = { 31, 52, 35 }, logs[3] = { 8, 9, 9 };     // offsets, match lengths, literal lengths
@@ -354,6 +357,7 @@ static int parseCompressDict(const uint8_t *d, size_t size, ZsCompressDict &out)
             int16_t norm[256]; uint32_t mx = maxes[t], lg;
             const size_t h = hdict::readNCount(norm, &mx, &lg, p, (size_t)(end - p));
             if (h == hdict::kErr || mx > maxes[t] || lg > logs[t]) return ZSMI_error_dictionary_corrupted;
+            if (ent) { const int k = t == 0 ? 1 : (t == 1 ? 2 : 0); memcpy(ent->norm[k], norm, sizeof(int16_t) * (mx + 1)); ent->maxSym[k] = mx; ent->tableLog[k] = lg; }     // (the encoder's order: LL, OF, ML)
             p += h;
         }
         if (p + 12 > end) return ZSMI_error_dictionary_corrupted;
@@ -456,6 +460,7 @@ static int buildPlan(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *sr
     }
     return 0;
 }
+static const size_t kDictImgBytes = (size_t)2 << (ZS_TABLE_LOG_BIG + 2);      // k_lz_dict_tables' images: the short table's and the long table's
 // dict (dictionary calls): parsed on the host (parseCompressDict), dDict its bytes in device memory.  Chunks of <= 64 KiB are PREFIXED
 // units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the last <= 64 KiB of the content); the units of longer chunks are
 // parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
@@ -476,9 +481,11 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
     // the prefix: the dictionary content's last <= 64 KiB, and its candidate-table images (once per call)
     const uint32_t pfx = dict ? std::min<uint32_t>(dict->contentSize, ZS_BLOCK_MAX) : 0u;
     const uint8_t *dPre = dict ? dDict + dict->contentOff + dict->contentSize - pfx : nullptr;
-    if (dict) {
-        if (!c->dDictImg.reserve((size_t)2 << (ZS_TABLE_LOG_BIG + 2))) return ZSMI_error_memory_allocation;
+    const uint32_t *dImg = dict ? dict->dImg : nullptr;                  // (a digested dictionary brings its images along)
+    if (dict && !dImg) {
+        if (!c->dDictImg.reserve(kDictImgBytes)) return ZSMI_error_memory_allocation;
         LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(shape.useLong ? 2 : 1), dim3(1024), 0, dPre, pfx, (uint32_t *)c->dDictImg.p);
+        dImg = (const uint32_t *)c->dDictImg.p;
     }
     // sub-batches of whole chunks, one after the other through one scratch set.  Every kernel goes to the caller's stream: a stream of
     // the context's own costs two queue crossings a call (~0.01 - 0.09 ms each: a bench line of 126 GiB/s where the kernels added up to 137).
@@ -509,7 +516,7 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
             const bool p = k == kUnitsPfx;
             if (units[k].n)
                 LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, (uint16_t *)S.dDist.p,
-                       (uint8_t *)S.dDistHi.p, (uint32_t *)S.dCand.p, p ? (const uint32_t *)c->dDictImg.p : nullptr, p ? pfx : 0u);
+                       (uint8_t *)S.dDistHi.p, (uint32_t *)S.dCand.p, p ? dImg : nullptr, p ? pfx : 0u);
         }
         for (int k = 0; k < 3; k++) {
             const LzKernel<WalkFn> &K = shape.walk[k];
@@ -543,7 +550,12 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
             if (dStats) LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p,
                                (const ZsRangeHdr *)S.dHdrs.p, (const uint8_t *)S.dLits.p, dStats);
         };
-        if (dict) {
+        if (dict && dict->dTables) {                            // a digested, formatted dictionary: its tables may code a frame's first block
+            sequences(k_encode_sequences_cdict<ZS_SEQ_GROUP>, make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u), dict->dTables);
+            stats();
+            literals(k_encode_literals_cdict, dict->dictID, dict->dTables);
+            if (maxChunkBlocks > 1) assemble(k_assemble_frames_dict, dict->dictID);
+        } else if (dict) {
             sequences(k_encode_sequences_dict<ZS_SEQ_GROUP>, make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u));
             stats();
             literals(k_encode_literals_dict, dict->dictID);
@@ -578,6 +590,64 @@ extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc,
     if (const int e = parseCompressDict(h.data(), dictSize, d)) return e;
     if (n == 0) return 0;
     return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, (const uint8_t *)dDict, &d);
+}
+
+// ---- digested dictionaries (ZSTD_createCDict / ZSTD_compress_usingCDict): parsed once, everything a call needs kept in device memory - the
+// bytes, the prefix's candidate-table images for the bound level's LZ shape, and for a formatted dictionary its entropy tables in encoder
+// form (k_cdict_tables).  Read-only after creation: any context of the same device may use it, from any thread. ----
+struct zsmi_cdict {
+    int device = 0, level = 3;
+    bool empty = false;                  // no bytes: its calls are the plain calls at its level
+    ZsCompressDict d;                    // (dImg, dTables: into the buffers below)
+    DevBuf dBytes, dImg, dTables;
+};
+extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t dictSize, int level, int *err)
+{
+    int code = 0;
+    zsmi_cdict *cd = nullptr;
+    do {
+        if (!c) { code = ZSMI_error_init_missing; break; }
+        if (dictSize > 0xFFFFFFFFull) { code = ZSMI_error_dictionary_corrupted; break; }
+        cd = new zsmi_cdict();
+        cd->device = c->device; cd->level = level;
+        if (!dict || dictSize == 0) { cd->empty = true; break; }
+        ZsCDictEntropy ent; memset(&ent, 0, sizeof ent);
+        if ((code = parseCompressDict((const uint8_t *)dict, dictSize, cd->d, &ent))) break;
+        const bool formatted = cd->d.contentOff != 0;
+        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        if (!cd->dBytes.reserve(dictSize + 64) || !cd->dImg.reserve(kDictImgBytes) || (formatted && !cd->dTables.reserve(sizeof(ZsCDictTables)))) { code = ZSMI_error_memory_allocation; break; }
+        if (hipMemcpyAsync(cd->dBytes.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        const uint32_t pfx = std::min<uint32_t>(cd->d.contentSize, ZS_BLOCK_MAX);
+        LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(lzShape(level).useLong ? 2 : 1), dim3(1024), 0,
+               (const uint8_t *)cd->dBytes.p + cd->d.contentOff + cd->d.contentSize - pfx, pfx, (uint32_t *)cd->dImg.p);
+        cd->d.dImg = (const uint32_t *)cd->dImg.p;
+        if (formatted) {
+            LAUNCH(c, "k_cdict_tables", k_cdict_tables, dim3(1), dim3(256), 0, ent, (ZsCDictTables *)cd->dTables.p);
+            cd->d.dTables = (const ZsCDictTables *)cd->dTables.p;
+        }
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
+    } while (0);
+    if (code) { delete cd; cd = nullptr; }
+    if (err) *err = code;
+    return cd;
+}
+extern "C" void zsmi_freeCDict(zsmi_cdict *cd) { delete cd; }
+extern "C" unsigned zsmi_getDictID_fromCDict(const zsmi_cdict *cd) { return cd ? cd->d.dictID : 0; }
+extern "C" size_t zsmi_sizeofCDict(const zsmi_cdict *cd) { return cd ? cd->dBytes.cap + cd->dImg.cap + cd->dTables.cap : 0; }
+// 0: the call may go on; cd != nullptr
+static int checkCDict(const zsmi_ctx *c, const zsmi_cdict *cd)
+{
+    if (!c) return ZSMI_error_init_missing;
+    return cd->device == c->device ? 0 : ZSMI_error_parameter_unsupported;
+}
+// queues the work and returns: nothing is read back, nothing waited for (the dictionary call's parse, wait and table build were done at creation)
+extern "C" int zsmi_compressBatchDevice_usingCDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                   uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, const zsmi_cdict *cd)
+{
+    if (!cd) return zsmi_compressBatchDevice(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, 3);
+    if (const int e = checkCDict(c, cd)) return e;
+    if (cd->empty) return zsmi_compressBatchDevice(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, cd->level);
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, cd->level, (const uint8_t *)cd->dBytes.p, &cd->d);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -911,6 +981,20 @@ extern "C" int zsmi_compressBatchHost_usingDict(zsmi_ctx *c, const void *src, co
 {
     return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict, dictSize);
 }
+extern "C" int zsmi_compressBatchHost_usingCDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                 uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, const zsmi_cdict *cd)
+{
+    if (!cd) return zsmi_compressBatchHost(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, 3);
+    if (const int e = checkCDict(c, cd)) return e;
+    if (cd->empty) return zsmi_compressBatchHost(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, cd->level);
+    if (n == 0) return 0;
+    std::vector<uint32_t> bounds(n);
+    for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes, nullptr, 0,
+                  [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
+                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, cd->level, (const uint8_t *)cd->dBytes.p, &cd->d);
+                  });
+}
 static int decompressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
                                    const void *dict, size_t dictSize)
@@ -1010,6 +1094,25 @@ extern "C" size_t zsmi_compress_usingDict(void *dst, size_t dstCapacity, const v
     if (dstCapacity < bound) { tmp.resize(bound); out = tmp.data(); }     // compress into a bound-sized buffer, then check the fit
     const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
     const int rc = zsmi_compressBatchHost_usingDict(c, src, &so, &ss, 1, out, &dof, &ds, level, dict, dictSize);
+    if (rc) return ZSMI_ERR(rc);
+    if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
+    if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
+    if (out != dst) memcpy(dst, out, ds);
+    return ds;
+}
+// (the borrowed context is one of the current device: a dictionary digested on another device is parameter_unsupported)
+extern "C" size_t zsmi_compress_usingCDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd)
+{
+    if (!cd) return zsmi_compress(dst, dstCapacity, src, srcSize, 3);
+    if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
+    Borrowed b; zsmi_ctx *c = b.c;
+    if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
+    const size_t bound = zsmi_compressBound(srcSize);
+    std::vector<uint8_t> tmp;
+    uint8_t *out = (uint8_t *)dst;
+    if (dstCapacity < bound) { tmp.resize(bound); out = tmp.data(); }     // compress into a bound-sized buffer, then check the fit
+    const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
+    const int rc = zsmi_compressBatchHost_usingCDict(c, src, &so, &ss, 1, out, &dof, &ds, cd);
     if (rc) return ZSMI_ERR(rc);
     if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
     if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);

@@ -113,7 +113,10 @@ static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz
 #define LAUNCH(ctx, name, kernel, grid, block, lds, ...) LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, lds, __VA_ARGS__)
 
 // ---- the batch calls in device memory (zsmi_api.hip: the compress and the decompress section state their arguments) ----
-struct ZsCompressDict { uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 }; };
+// dImg, dTables: a digested dictionary's (zsmi_cdict) - the prefix's candidate-table images, built once and not by the call, and the
+// dictionary's entropy tables in encoder form (nullptr: raw content, none)
+struct ZsCDictTables;
+struct ZsCompressDict { uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 }; const uint32_t *dImg = nullptr; const ZsCDictTables *dTables = nullptr; };
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
                                    const uint8_t *dDict, const ZsCompressDict *dict, uint32_t *dStats = nullptr);
