@@ -114,7 +114,7 @@ def test_dictionary_ids_match_oracle(codec):
 
 def test_plan_reuse_matches_oracle(codec):
     """one chunk layout called again and again on one context: no dictionary, dictionary A, dictionary B with another prefix length,
-    no dictionary again, A again - buildPlan's cached plan and its dictionary unit list, the table images rebuilt every call"""
+    no dictionary again, A again - the cached CompressPlan and its dictionary unit list, the table images rebuilt every call"""
     a, b = X.identity_dictionaries()["trained64k_zipf"], X.identity_dictionaries()["raw6000"]
     chunks = X.prefix_chunks(X.identity_dictionaries()["raw65536"])
     for level in (3, 1):

@@ -33,6 +33,12 @@ def _error_name(L, code: int) -> str:
     return L.zsmi_getErrorName((1 << 64) - code).decode()
 
 
+def _check(rc, name):
+    """rc: the int result of the C function `name`; non-zero raises RuntimeError"""
+    if rc:
+        raise RuntimeError(f"{name}: error {rc}")
+
+
 def _buf(b):
     """bytes-like -> (ctypes pointer/obj, length)"""
     if isinstance(b, np.ndarray):
@@ -145,12 +151,10 @@ class ZstdCompressor:
         s, sn = _buf(src)
         cap = L.zsmi_compressBound(sn)
         out = ctypes.create_string_buffer(cap)
-        if self.cdict:
-            r = L.zsmi_compress_usingCDict(out, cap, s, sn, self.cdict.handle)
-        elif self.dictionary:
-            r = L.zsmi_compress_usingDict(out, cap, s, sn, self.dictionary, len(self.dictionary), self.level)
-        else:
-            r = L.zsmi_compress(out, cap, s, sn, self.level)
+        call = (L.zsmi_compress_usingCDict, self.cdict.handle) if self.cdict else \
+               (L.zsmi_compress_usingDict, self.dictionary, len(self.dictionary), self.level) if self.dictionary else \
+               (L.zsmi_compress, self.level)
+        r = call[0](out, cap, s, sn, *call[1:])
         if L.zsmi_isError(r):
             raise RuntimeError(L.zsmi_getErrorName(r).decode())
         return out.raw[:r]
@@ -277,44 +281,35 @@ class BatchCodec:
     def _p(a):
         return a.ctypes.data_as(ctypes.c_void_p)
 
+    @staticmethod
+    def _compress_form(name, level, dict_ptr, dict_size, cdict):
+        """the C function of a batch compress call and its arguments behind the common ones: a CompressionDict comes first, then a dictionary"""
+        if cdict is not None:
+            return name + "_usingCDict", (cdict.handle,)
+        if dict_size:
+            return name + "_usingDict", (level, dict_ptr, dict_size)
+        return name, (level,)
+
     def compress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, d_dst_sizes_ptr, level=3, d_dict_ptr=0, dict_size=0, cdict=None):
         """d_dict_ptr / dict_size: one dictionary (device memory) for every chunk of the call (zsmi_compressBatchDevice_usingDict).
         cdict: a CompressionDict instead (zsmi_compressBatchDevice_usingCDict: its level holds; queued without a wait)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
-        if cdict is not None:
-            rc = self.L.zsmi_compressBatchDevice_usingCDict(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
-                                                            ctypes.c_void_p(d_dst_ptr), self._p(do), ctypes.c_void_p(d_dst_sizes_ptr), cdict.handle)
-            if rc:
-                raise RuntimeError(f"zsmi_compressBatchDevice_usingCDict: error {rc}")
-            return
-        if d_dict_ptr and dict_size:
-            rc = self.L.zsmi_compressBatchDevice_usingDict(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
-                                                           ctypes.c_void_p(d_dst_ptr), self._p(do), ctypes.c_void_p(d_dst_sizes_ptr), level,
-                                                           ctypes.c_void_p(d_dict_ptr), dict_size)
-            if rc:
-                raise RuntimeError(f"zsmi_compressBatchDevice_usingDict: error {rc}")
-            return
-        rc = self.L.zsmi_compressBatchDevice(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
-                                             ctypes.c_void_p(d_dst_ptr), self._p(do), ctypes.c_void_p(d_dst_sizes_ptr), level)
-        if rc:
-            raise RuntimeError(f"zsmi_compressBatchDevice: error {rc}")
+        name, tail = self._compress_form("zsmi_compressBatchDevice", level, ctypes.c_void_p(d_dict_ptr), d_dict_ptr and dict_size, cdict)
+        _check(getattr(self.L, name)(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss), ctypes.c_void_p(d_dst_ptr), self._p(do),
+                                     ctypes.c_void_p(d_dst_sizes_ptr), *tail), name)
 
     def decompress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, dst_caps, d_dst_sizes_ptr):
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64); dc = np.ascontiguousarray(dst_caps, dtype=np.uint32)
-        rc = self.L.zsmi_decompressBatchDevice(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
-                                               ctypes.c_void_p(d_dst_ptr), self._p(do), self._p(dc), ctypes.c_void_p(d_dst_sizes_ptr))
-        if rc:
-            raise RuntimeError(f"zsmi_decompressBatchDevice: error {rc}")
+        _check(self.L.zsmi_decompressBatchDevice(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
+                                                 ctypes.c_void_p(d_dst_ptr), self._p(do), self._p(dc), ctypes.c_void_p(d_dst_sizes_ptr)), "zsmi_decompressBatchDevice")
 
     def pack_device(self, d_frames_ptr, dst_offsets, d_sizes_ptr, n, d_packed_ptr, d_packed_offsets_ptr):
         """frames sitting at dst_offsets (sizes on the device) -> one contiguous run at d_packed; d_packed_offsets[n + 1] (device, uint64)"""
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
-        rc = self.L.zsmi_packFramesDevice(self.ctx, ctypes.c_void_p(d_frames_ptr), self._p(do), ctypes.c_void_p(d_sizes_ptr), n,
-                                          ctypes.c_void_p(d_packed_ptr), ctypes.c_void_p(d_packed_offsets_ptr))
-        if rc:
-            raise RuntimeError(f"zsmi_packFramesDevice: error {rc}")
+        _check(self.L.zsmi_packFramesDevice(self.ctx, ctypes.c_void_p(d_frames_ptr), self._p(do), ctypes.c_void_p(d_sizes_ptr), n,
+                                            ctypes.c_void_p(d_packed_ptr), ctypes.c_void_p(d_packed_offsets_ptr)), "zsmi_packFramesDevice")
 
     def seekable_bound(self, src_size, frame_size=0, checksum=True) -> int:
         return _raise_if_error(self.L, self.L.zsmi_seekableBound(src_size, frame_size, int(bool(checksum))))
@@ -350,21 +345,9 @@ class BatchCodec:
             do[1:] = np.cumsum(bounds)[:-1]
         arena = np.zeros(int(bounds.sum()), dtype=np.uint8)
         dsz = np.zeros(n, dtype=np.uint32)
-        if cdict is not None:
-            rc = self.L.zsmi_compressBatchHost_usingCDict(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), cdict.handle)
-            if rc:
-                raise RuntimeError(f"zsmi_compressBatchHost_usingCDict: error {rc}")
-            return arena, do, dsz
-        if dictionary:
-            dbuf = np.frombuffer(bytes(dictionary), dtype=np.uint8)
-            rc = self.L.zsmi_compressBatchHost_usingDict(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), level,
-                                                         self._p(dbuf), len(dbuf))
-            if rc:
-                raise RuntimeError(f"zsmi_compressBatchHost_usingDict: error {rc}")
-            return arena, do, dsz
-        rc = self.L.zsmi_compressBatchHost(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), level)
-        if rc:
-            raise RuntimeError(f"zsmi_compressBatchHost: error {rc}")
+        dbuf = np.frombuffer(bytes(dictionary or b""), dtype=np.uint8)
+        name, tail = self._compress_form("zsmi_compressBatchHost", level, self._p(dbuf), len(dbuf), cdict)
+        _check(getattr(self.L, name)(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), *tail), name)
         return arena, do, dsz
 
     def decompress_host(self, src: np.ndarray, src_offsets, src_sizes, dst_caps, dictionary: bytes = b""):
@@ -384,8 +367,7 @@ class BatchCodec:
                                                            self._p(dbuf), len(dbuf))
         else:
             rc = self.L.zsmi_decompressBatchHost(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dc), self._p(dsz))
-        if rc:
-            raise RuntimeError(f"zsmi_decompressBatchHost: error {rc}")
+        _check(rc, "zsmi_decompressBatchHost")
         return arena, do, dsz
 
     def train_device(self, d_samples_ptr, offsets, sizes, capacity=65536, k=0, d=0, level=3, dict_id=0, f=0, steps=0, split_point=0.0, accel=0):

@@ -210,7 +210,7 @@ static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize,
         std::vector<uint64_t> so(n), dof(n);
         std::vector<uint32_t> ss(n);
         for (uint32_t i = 0; i < n; i++) { so[i] = (uint64_t)i * F; ss[i] = (uint32_t)std::min<uint64_t>(F, srcSize - so[i]); dof[i] = (uint64_t)i * stride; }
-        if (const int e = compressBatchDeviceImpl(c, dSrc, so.data(), ss.data(), n, c->seek.dStage.p, dof.data(), dSizes, level, nullptr, nullptr)) return e;
+        if (const int e = compressBatchDeviceImpl(c, dSrc, so.data(), ss.data(), n, c->seek.dStage.p, dof.data(), dSizes, level, nullptr)) return e;
         if (checksumFlag) LAUNCH(c, "k_seek_hash", k_seek_hash, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, srcSize, F, n, dHash);
     }
     LAUNCH(c, "k_pack_offsets", k_pack_offsets, dim3(1), dim3(1024), 0, (const uint32_t *)dSizes, n, dPacked);

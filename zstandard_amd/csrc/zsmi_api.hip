@@ -21,6 +21,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 extern "C" unsigned zsmi_isError(size_t code) { return code > ZSMI_ERR(ZSMI_error_maxCode); }     // ZStdErrors.cs:95-98
@@ -385,24 +386,24 @@ bool zsmi_ctx::Scratch::reserve(uint32_t cap)
 // The plan of a call: chunks -> blocks (ZsChunkDesc, ZsBlockDesc) and LZ units, built on the host and copied to the device.  It is reused
 // while the chunk layout repeats (steady-state batches; compared in place: such a call allocates and copies nothing).  A dictionary call
 // adds a unit list of its own, once per plan.
-static int buildPlan(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict)
+int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict)
 {
-    bool samePlan = c->planKey.size() == (size_t)n * 3 + 1 && c->planKey[0] == n;
-    for (uint32_t i = 0; samePlan && i < n; i++) samePlan = c->planKey[1 + i] == srcOffsets[i] && c->planKey[1 + n + i] == dstOffsets[i] && c->planKey[1 + 2 * (size_t)n + i] == srcSizes[i];
-    if (!samePlan) {
-        std::vector<uint64_t> key((size_t)n * 3 + 1);
-        key[0] = n;
-        for (uint32_t i = 0; i < n; i++) { key[1 + i] = srcOffsets[i]; key[1 + n + i] = dstOffsets[i]; key[1 + 2 * (size_t)n + i] = srcSizes[i]; }
+    bool same = key.size() == (size_t)n * 3 + 1 && key[0] == n;
+    for (uint32_t i = 0; same && i < n; i++) same = key[1 + i] == srcOffsets[i] && key[1 + n + i] == dstOffsets[i] && key[1 + 2 * (size_t)n + i] == srcSizes[i];
+    if (!same) {
+        std::vector<uint64_t> newKey((size_t)n * 3 + 1);
+        newKey[0] = n;
+        for (uint32_t i = 0; i < n; i++) { newKey[1 + i] = srcOffsets[i]; newKey[1 + n + i] = dstOffsets[i]; newKey[1 + 2 * (size_t)n + i] = srcSizes[i]; }
         uint64_t nBlocks = 0;
         for (uint32_t i = 0; i < n; i++) nBlocks += srcSizes[i] ? (srcSizes[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX : 1;
         if (nBlocks > 0x7FFFFFFFull) return ZSMI_error_srcSize_wrong;
-        if (!c->hChunks.reserve(sizeof(ZsChunkDesc) * n) || !c->hBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
-        if (!c->dChunks.reserve(sizeof(ZsChunkDesc) * n) || !c->dBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
-        if (!c->hUnits.reserve(sizeof(ZsUnitDesc) * nBlocks) || !c->dUnits.reserve(sizeof(ZsUnitDesc) * nBlocks)) return ZSMI_error_memory_allocation;
+        if (!hChunks.reserve(sizeof(ZsChunkDesc) * n) || !hBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
+        if (!dChunks.reserve(sizeof(ZsChunkDesc) * n) || !dBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
+        if (!hUnits.reserve(sizeof(ZsUnitDesc) * nBlocks) || !dUnits.reserve(sizeof(ZsUnitDesc) * nBlocks)) return ZSMI_error_memory_allocation;
         // the pinned plan buffers may still feed a previous asynchronous copy
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        ZsChunkDesc *hc0 = (ZsChunkDesc *)c->hChunks.p; ZsBlockDesc *hb = (ZsBlockDesc *)c->hBlocks.p;
-        uint32_t b = 0, maxChunkBlocks = 1;
+        if (hipStreamSynchronize(stream) != hipSuccess) return ZSMI_error_GENERIC;
+        ZsChunkDesc *hc0 = (ZsChunkDesc *)hChunks.p; ZsBlockDesc *hb = (ZsBlockDesc *)hBlocks.p;
+        uint32_t b = 0, maxNb = 1;
         for (uint32_t i = 0; i < n; i++) {
             const uint32_t nb = srcSizes[i] ? (srcSizes[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX : 1;
             hc0[i].srcOff = srcOffsets[i]; hc0[i].dstOff = dstOffsets[i]; hc0[i].size = srcSizes[i]; hc0[i].firstBlock = b; hc0[i].nBlocks = nb; hc0[i].pad = 0;
@@ -412,17 +413,17 @@ static int buildPlan(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *sr
                 hb[b].size = (uint32_t)(left < ZS_BLOCK_MAX ? left : ZS_BLOCK_MAX);
                 hb[b].chunk = i; hb[b].firstInChunk = (k == 0); hb[b].lastInChunk = (k + 1 == nb);
             }
-            if (nb > maxChunkBlocks) maxChunkBlocks = nb;
+            if (nb > maxNb) maxNb = nb;
         }
         // LZ units: every 128 KiB of a chunk (two blocks); a unit of <= 64 KiB goes to the small-unit kernels
-        c->smallBefore.assign((size_t)n + 1, 0); c->bigBefore.assign((size_t)n + 1, 0);
+        small.before.assign((size_t)n + 1, 0); big.before.assign((size_t)n + 1, 0);
         uint32_t nSmall = 0, nBig = 0;
         for (uint32_t i = 0; i < n; i++) {
-            c->smallBefore[i] = nSmall; c->bigBefore[i] = nBig;
+            small.before[i] = nSmall; big.before[i] = nBig;
             for (uint64_t o = 0; o < srcSizes[i]; o += ZS_UNIT_MAX) { if ((uint64_t)srcSizes[i] - o > ZS_BLOCK_MAX) nBig++; else nSmall++; }
         }
-        c->smallBefore[n] = nSmall; c->bigBefore[n] = nBig;
-        ZsUnitDesc *hu = (ZsUnitDesc *)c->hUnits.p;
+        small.before[n] = nSmall; big.before[n] = nBig;
+        ZsUnitDesc *hu = (ZsUnitDesc *)hUnits.p;
         uint32_t is = 0, ib = nSmall;
         for (uint32_t i = 0; i < n; i++)
             for (uint64_t o = 0; o < srcSizes[i]; o += ZS_UNIT_MAX) {
@@ -430,93 +431,110 @@ static int buildPlan(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *sr
                 ZsUnitDesc &u = hu[left > ZS_BLOCK_MAX ? ib++ : is++];
                 u.srcOff = srcOffsets[i] + o; u.size = (uint32_t)(left < ZS_UNIT_MAX ? left : ZS_UNIT_MAX); u.firstBlock = hc0[i].firstBlock + (uint32_t)(o / ZS_BLOCK_MAX);
             }
-        if (nSmall + nBig && hipMemcpyAsync(c->dUnits.p, hu, sizeof(ZsUnitDesc) * (nSmall + nBig), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        c->planSmall = nSmall; c->planBig = nBig;
-        if (hipMemcpyAsync(c->dChunks.p, hc0, sizeof(ZsChunkDesc) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        if (hipMemcpyAsync(c->dBlocks.p, hb, sizeof(ZsBlockDesc) * nBlocks, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        c->planKey.swap(key); c->planBlocks = nBlocks; c->planMaxChunkBlocks = maxChunkBlocks;
-        c->planDict = false;
+        if (nSmall + nBig && hipMemcpyAsync(dUnits.p, hu, sizeof(ZsUnitDesc) * (nSmall + nBig), hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
+        small.base = 0; big.base = nSmall;
+        if (hipMemcpyAsync(dChunks.p, hc0, sizeof(ZsChunkDesc) * n, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
+        if (hipMemcpyAsync(dBlocks.p, hb, sizeof(ZsBlockDesc) * nBlocks, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
+        key.swap(newKey); blocks = nBlocks; maxChunkBlocks = maxNb;
+        hasDictList = false;
     }
     // dictionary calls: the small units again, in a list of their own - [chunks of <= 64 KiB, one unit each (prefixed)][the other small
-    // units: tails of longer chunks] (wholeBefore / tailBefore: per chunk, as smallBefore)
-    if (dict && !c->planDict) {
-        c->wholeBefore.assign((size_t)n + 1, 0); c->tailBefore.assign((size_t)n + 1, 0);
+    // units: tails of longer chunks]
+    if (dict && !hasDictList) {
+        whole.before.assign((size_t)n + 1, 0); tail.before.assign((size_t)n + 1, 0);
         uint32_t nWhole = 0, nTail = 0;
         for (uint32_t i = 0; i < n; i++) {
-            c->wholeBefore[i] = nWhole; c->tailBefore[i] = nTail;
+            whole.before[i] = nWhole; tail.before[i] = nTail;
             if (srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX) nWhole++;
             else if (srcSizes[i] > ZS_BLOCK_MAX && ((srcSizes[i] - 1) % ZS_UNIT_MAX) < ZS_BLOCK_MAX) nTail++;      // its last unit is one block
         }
-        c->wholeBefore[n] = nWhole; c->tailBefore[n] = nTail;
-        if (!c->hUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1)) || !c->dUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1))) return ZSMI_error_memory_allocation;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;         // (the pinned list may still feed a previous copy)
-        ZsUnitDesc *hu = (ZsUnitDesc *)c->hUnitsDict.p;
-        const ZsUnitDesc *all = (const ZsUnitDesc *)c->hUnits.p;
+        whole.before[n] = nWhole; tail.before[n] = nTail;
+        if (!hUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1)) || !dUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1))) return ZSMI_error_memory_allocation;
+        if (hipStreamSynchronize(stream) != hipSuccess) return ZSMI_error_GENERIC;         // (the pinned list may still feed a previous copy)
+        ZsUnitDesc *hu = (ZsUnitDesc *)hUnitsDict.p;
+        const ZsUnitDesc *all = (const ZsUnitDesc *)hUnits.p;
         uint32_t iw = 0, it = nWhole;
         for (uint32_t i = 0; i < n; i++)                                     // the small units are in chunk order: a chunk's is its whole or its tail
-            for (uint32_t k = c->smallBefore[i]; k < c->smallBefore[i + 1]; k++) hu[srcSizes[i] <= ZS_BLOCK_MAX ? iw++ : it++] = all[k];
-        if (nWhole + nTail && hipMemcpyAsync(c->dUnitsDict.p, hu, sizeof(ZsUnitDesc) * (nWhole + nTail), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        c->planDictWhole = nWhole; c->planDict = true;
+            for (uint32_t k = small.before[i]; k < small.before[i + 1]; k++) hu[srcSizes[i] <= ZS_BLOCK_MAX ? iw++ : it++] = all[k];
+        if (nWhole + nTail && hipMemcpyAsync(dUnitsDict.p, hu, sizeof(ZsUnitDesc) * (nWhole + nTail), hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
+        whole.base = 0; tail.base = nWhole; hasDictList = true;
     }
     return 0;
 }
-static const size_t kDictImgBytes = (size_t)2 << (ZS_TABLE_LOG_BIG + 2);      // k_lz_dict_tables' images: the short table's and the long table's
-// dict (dictionary calls): parsed on the host (parseCompressDict), dDict its bytes in device memory.  Chunks of <= 64 KiB are PREFIXED
-// units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the last <= 64 KiB of the content); the units of longer chunks are
-// parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
+CompressPlan::Cut CompressPlan::cut(uint32_t chunk0, uint32_t cap) const
+{
+    const ZsChunkDesc *hc = (const ZsChunkDesc *)hChunks.p;
+    Cut s = { chunk0, 0, hc[chunk0].firstBlock };
+    for (; s.chunk1 < key[0] && (s.nb == 0 || s.nb + hc[s.chunk1].nBlocks <= cap); s.chunk1++) s.nb += hc[s.chunk1].nBlocks;
+    return s;
+}
+// the sub-batch's LZ units of a kernel shape: prefixed (dictionary calls only), small (a dictionary call: the tails in its own list), big
+CompressPlan::Units CompressPlan::units(int kind, bool dict, uint32_t chunk0, uint32_t chunk1) const
+{
+    if (kind == kUnitsPfx && !dict) return { nullptr, 0 };
+    const bool ownList = dict && kind != kUnitsBig;
+    const Run &r = kind == kUnitsBig ? big : (!dict ? small : (kind == kUnitsPfx ? whole : tail));
+    return { (const ZsUnitDesc *)(ownList ? dUnitsDict : dUnits).p + r.base + r.before[chunk0], r.before[chunk1] - r.before[chunk0] };
+}
+
+// the prefix: the dictionary content's last <= 64 KiB, where a prefixed unit's matches may reach
+struct DictPrefix { const uint8_t *d; uint32_t size; };
+static DictPrefix dictPrefix(const ZsCompressDict &d)
+{
+    const uint32_t size = std::min<uint32_t>(d.contentSize, ZS_BLOCK_MAX);
+    return { d.dBytes + d.contentOff + d.contentSize - size, size };
+}
+// the prefix's candidate-table images for a level's LZ shape (the short table's and the long table's), into dImg
+static const size_t kDictImgBytes = (size_t)2 << (ZS_TABLE_LOG_BIG + 2);
+static void launchDictTables(zsmi_ctx *c, const ZsCompressDict &d, int level, void *dImg)
+{
+    const DictPrefix pre = dictPrefix(d);
+    LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(lzShape(level).useLong ? 2 : 1), dim3(1024), 0, pre.d, pre.size, (uint32_t *)dImg);
+}
+// The launch sequence of a call, over the plan's sub-batches.  dict: nullptr, or the call's dictionary, in one of three kinds -
+//   content only, or parsed from a formatted dictionary (the _usingDict calls, the trainer): the table images are built here, every call;
+//   digested, raw content (dImg): it brings its images along;
+//   digested, formatted (dImg and dTables): besides, its entropy tables may code a frame's first block.
+// Chunks of <= 64 KiB are PREFIXED units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the prefix); the units of longer
+// chunks are parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
 // A call without a dictionary is one with no prefixed units.  dStats (the dictionary trainer's finalize; nullptr on every other path): device
 // counters of the literal bytes and LL / OF / ML codes, added to by k_train_stats after each sub-batch's sequences kernel.
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const uint8_t *dDict, const ZsCompressDict *dict, uint32_t *dStats)
+                                   const ZsCompressDict *dict, uint32_t *dStats)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
     const LzShape &shape = lzShape(level);
-    if (const int e = buildPlan(c, srcOffsets, srcSizes, n, dstOffsets, dict != nullptr)) return e;
-    const uint64_t nBlocks = c->planBlocks;
-    const uint32_t maxChunkBlocks = c->planMaxChunkBlocks;
-    const ZsChunkDesc *hc = (const ZsChunkDesc *)c->hChunks.p;
-    // the prefix: the dictionary content's last <= 64 KiB, and its candidate-table images (once per call)
-    const uint32_t pfx = dict ? std::min<uint32_t>(dict->contentSize, ZS_BLOCK_MAX) : 0u;
-    const uint8_t *dPre = dict ? dDict + dict->contentOff + dict->contentSize - pfx : nullptr;
-    const uint32_t *dImg = dict ? dict->dImg : nullptr;                  // (a digested dictionary brings its images along)
+    CompressPlan &P = c->plan;
+    if (const int e = P.build(c->stream, srcOffsets, srcSizes, n, dstOffsets, dict != nullptr)) return e;
+    const DictPrefix pre = dict ? dictPrefix(*dict) : DictPrefix{ nullptr, 0u };
+    const uint32_t *dImg = dict ? dict->dImg : nullptr;
     if (dict && !dImg) {
         if (!c->dDictImg.reserve(kDictImgBytes)) return ZSMI_error_memory_allocation;
-        LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(shape.useLong ? 2 : 1), dim3(1024), 0, dPre, pfx, (uint32_t *)c->dDictImg.p);
+        launchDictTables(c, *dict, level, c->dDictImg.p);
         dImg = (const uint32_t *)c->dDictImg.p;
     }
     // sub-batches of whole chunks, one after the other through one scratch set.  Every kernel goes to the caller's stream: a stream of
     // the context's own costs two queue crossings a call (~0.01 - 0.09 ms each: a bench line of 126 GiB/s where the kernels added up to 137).
-    uint32_t cap = (uint32_t)std::min<uint64_t>(nBlocks, std::max<uint32_t>(64, c->maxBlocksInFlight));
-    if (cap < maxChunkBlocks) cap = maxChunkBlocks;
+    const uint32_t cap = std::max<uint32_t>((uint32_t)std::min<uint64_t>(P.blocks, std::max<uint32_t>(64, c->maxBlocksInFlight)), P.maxChunkBlocks);
     zsmi_ctx::Scratch &S = c->scratch;
     if (!S.reserve(cap)) return ZSMI_error_memory_allocation;
+    const ZsChunkDesc *dChunks = (const ZsChunkDesc *)P.dChunks.p;
     for (uint32_t chunk0 = 0, chunk1; chunk0 < n; chunk0 = chunk1) {
-        uint32_t nb = 0;
-        for (chunk1 = chunk0; chunk1 < n && (nb == 0 || nb + hc[chunk1].nBlocks <= cap); chunk1++) nb += hc[chunk1].nBlocks;
-        const uint32_t block0 = hc[chunk0].firstBlock;
-        const ZsBlockDesc *dB = (const ZsBlockDesc *)c->dBlocks.p + block0;
-        // the sub-batch's LZ units by kernel shape: prefixed, small (a dictionary call: the tails in its own list), big
-        struct { const ZsUnitDesc *d; uint32_t n; } units[3];
-        const uint32_t b0 = c->bigBefore[chunk0];
-        units[kUnitsBig] = { (const ZsUnitDesc *)c->dUnits.p + c->planSmall + b0, c->bigBefore[chunk1] - b0 };
-        if (dict) {
-            const uint32_t w0 = c->wholeBefore[chunk0], t0 = c->tailBefore[chunk0];
-            units[kUnitsPfx] = { (const ZsUnitDesc *)c->dUnitsDict.p + w0, c->wholeBefore[chunk1] - w0 };
-            units[kUnitsSmall] = { (const ZsUnitDesc *)c->dUnitsDict.p + c->planDictWhole + t0, c->tailBefore[chunk1] - t0 };
-        } else {
-            const uint32_t s0 = c->smallBefore[chunk0];
-            units[kUnitsPfx] = { nullptr, 0 };
-            units[kUnitsSmall] = { (const ZsUnitDesc *)c->dUnits.p + s0, c->smallBefore[chunk1] - s0 };
-        }
+        const CompressPlan::Cut sub = P.cut(chunk0, cap);
+        const uint32_t nb = sub.nb, block0 = sub.block0;
+        chunk1 = sub.chunk1;
+        const ZsBlockDesc *dB = (const ZsBlockDesc *)P.dBlocks.p + block0;
+        CompressPlan::Units units[3];
+        for (int k = 0; k < 3; k++) units[k] = P.units(k, dict != nullptr, chunk0, chunk1);
         for (int k = 0; k < 3; k++) {
             const LzKernel<CandFn> &K = shape.cand[k];
             const bool p = k == kUnitsPfx;
             if (units[k].n)
                 LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, (uint16_t *)S.dDist.p,
-                       (uint8_t *)S.dDistHi.p, (uint32_t *)S.dCand.p, p ? dImg : nullptr, p ? pfx : 0u);
+                       (uint8_t *)S.dDistHi.p, (uint32_t *)S.dCand.p, p ? dImg : nullptr, p ? pre.size : 0u);
         }
         for (int k = 0; k < 3; k++) {
             const LzKernel<WalkFn> &K = shape.walk[k];
@@ -524,55 +542,44 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
             if (units[k].n)
                 LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, (const uint16_t *)S.dDist.p,
                        (const uint8_t *)S.dDistHi.p, (uint2 *)S.dRecs.p, cap * (ZS_BLOCK_MAX / 4), (uint4 *)S.dRes.p, shape.walkLog, (const uint32_t *)S.dCand.p,
-                       p ? dPre : nullptr, p ? pfx : 0u);
+                       p ? pre.d : nullptr, p ? pre.size : 0u);
         }
         LAUNCH(c, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, (const uint2 *)S.dRecs.p, (const uint4 *)S.dRes.p, (ZsSeqRec *)S.dSeqs.p, (ZsRangeHdr *)S.dHdrs.p, shape.walkLog);
         if (c->stopAfterWalk) continue;
-        // sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and reads the sequence
-        // sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  A dictionary call's kernels
-        // take its recent offsets and its ID besides.
-        auto sequences = [&](auto kernel, auto... dictArgs) {
-            LAUNCH(c, "k_encode_sequences", kernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)S.dSeqs.p,
-                   (const ZsRangeHdr *)S.dHdrs.p, (uint8_t *)S.dSeqSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopSeq, (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p,
-                   (uint2 *)S.dDist.p, dictArgs...);
+        // The entropy stage.  Sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and
+        // reads the sequence sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  A
+        // dictionary's kind chooses the kernels and what they take besides (tuples): its recent offsets, its ID, a digested one's tables.
+        auto entropy = [&](auto seqKernel, auto seqDict, auto litKernel, auto litDict, auto asmKernel, auto asmDict) {
+            std::apply([&](auto... a) {
+                LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)S.dSeqs.p,
+                       (const ZsRangeHdr *)S.dHdrs.p, (uint8_t *)S.dSeqSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopSeq, (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p,
+                       (uint2 *)S.dDist.p, a...); }, seqDict);
+            if (dStats)                                              // (the codes it reads are in the literal buffers until the literals kernel)
+                LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p,
+                       (const ZsRangeHdr *)S.dHdrs.p, (const uint8_t *)S.dLits.p, dStats);
+            std::apply([&](auto... a) {
+                LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p, (const ZsRangeHdr *)S.dHdrs.p,
+                       (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p, (uint8_t *)S.dLitSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopLit,
+                       dChunks, (const uint8_t *)S.dSeqSec.p, (uint8_t *)dDst, dDstSizes, a...); }, litDict);
+            if (P.maxChunkBlocks > 1)                                // chunks of several blocks
+                std::apply([&](auto... a) {
+                    LAUNCH(c, "k_assemble_frames", asmKernel, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, dChunks,
+                           (const ZsBlockDesc *)P.dBlocks.p, (const ZsBlockMeta *)S.dMetas.p, (const uint8_t *)S.dLitSec.p, (const uint8_t *)S.dSeqSec.p, block0,
+                           (uint8_t *)dDst, dDstSizes, chunk0, a...); }, asmDict);
         };
-        auto literals = [&](auto kernel, auto... dictArgs) {
-            LAUNCH(c, "k_encode_literals", kernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p, (const ZsRangeHdr *)S.dHdrs.p,
-                   (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p, (uint8_t *)S.dLitSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopLit,
-                   (const ZsChunkDesc *)c->dChunks.p, (const uint8_t *)S.dSeqSec.p, (uint8_t *)dDst, dDstSizes, dictArgs...);
-        };
-        auto assemble = [&](auto kernel, auto... dictArgs) {     // chunks of several blocks
-            LAUNCH(c, "k_assemble_frames", kernel, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, (const ZsChunkDesc *)c->dChunks.p,
-                   (const ZsBlockDesc *)c->dBlocks.p, (const ZsBlockMeta *)S.dMetas.p, (const uint8_t *)S.dLitSec.p, (const uint8_t *)S.dSeqSec.p, block0,
-                   (uint8_t *)dDst, dDstSizes, chunk0, dictArgs...);
-        };
-        auto stats = [&]() {                                    // (the codes it reads are in the literal buffers until the literals kernel)
-            if (dStats) LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p,
-                               (const ZsRangeHdr *)S.dHdrs.p, (const uint8_t *)S.dLits.p, dStats);
-        };
-        if (dict && dict->dTables) {                            // a digested, formatted dictionary: its tables may code a frame's first block
-            sequences(k_encode_sequences_cdict<ZS_SEQ_GROUP>, make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u), dict->dTables);
-            stats();
-            literals(k_encode_literals_cdict, dict->dictID, dict->dTables);
-            if (maxChunkBlocks > 1) assemble(k_assemble_frames_dict, dict->dictID);
-        } else if (dict) {
-            sequences(k_encode_sequences_dict<ZS_SEQ_GROUP>, make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u));
-            stats();
-            literals(k_encode_literals_dict, dict->dictID);
-            if (maxChunkBlocks > 1) assemble(k_assemble_frames_dict, dict->dictID);
-        } else {
-            sequences(k_encode_sequences<ZS_SEQ_GROUP>);
-            stats();
-            literals(k_encode_literals);
-            if (maxChunkBlocks > 1) assemble(k_assemble_frames);
-        }
+        using std::make_tuple;
+        const uint4 rep = dict ? make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u) : uint4();
+        if (dict && dict->dTables) entropy(k_encode_sequences_cdict<ZS_SEQ_GROUP>, make_tuple(rep, dict->dTables), k_encode_literals_cdict, make_tuple(dict->dictID, dict->dTables),
+                                           k_assemble_frames_dict, make_tuple(dict->dictID));
+        else if (dict) entropy(k_encode_sequences_dict<ZS_SEQ_GROUP>, make_tuple(rep), k_encode_literals_dict, make_tuple(dict->dictID), k_assemble_frames_dict, make_tuple(dict->dictID));
+        else entropy(k_encode_sequences<ZS_SEQ_GROUP>, make_tuple(), k_encode_literals, make_tuple(), k_assemble_frames, make_tuple());
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
 extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                         uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level)
 {
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, nullptr);
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr);
 }
 // dDict: device memory.  Its bytes are read back to the host to be parsed (a formatted dictionary's ID, recent offsets and content
 // offset): the call waits for the context's stream once.
@@ -588,8 +595,8 @@ extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc,
     if (hipMemcpyAsync(h.data(), dDict, dictSize, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     ZsCompressDict d;
     if (const int e = parseCompressDict(h.data(), dictSize, d)) return e;
-    if (n == 0) return 0;
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, (const uint8_t *)dDict, &d);
+    d.dBytes = (const uint8_t *)dDict;
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &d);
 }
 
 // ---- digested dictionaries (ZSTD_createCDict / ZSTD_compress_usingCDict): parsed once, everything a call needs kept in device memory - the
@@ -598,7 +605,7 @@ extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc,
 struct zsmi_cdict {
     int device = 0, level = 3;
     bool empty = false;                  // no bytes: its calls are the plain calls at its level
-    ZsCompressDict d;                    // (dImg, dTables: into the buffers below)
+    ZsCompressDict d;                    // (dBytes, dImg, dTables: into the buffers below)
     DevBuf dBytes, dImg, dTables;
 };
 extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t dictSize, int level, int *err)
@@ -617,9 +624,8 @@ extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t di
         if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
         if (!cd->dBytes.reserve(dictSize + 64) || !cd->dImg.reserve(kDictImgBytes) || (formatted && !cd->dTables.reserve(sizeof(ZsCDictTables)))) { code = ZSMI_error_memory_allocation; break; }
         if (hipMemcpyAsync(cd->dBytes.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        const uint32_t pfx = std::min<uint32_t>(cd->d.contentSize, ZS_BLOCK_MAX);
-        LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(lzShape(level).useLong ? 2 : 1), dim3(1024), 0,
-               (const uint8_t *)cd->dBytes.p + cd->d.contentOff + cd->d.contentSize - pfx, pfx, (uint32_t *)cd->dImg.p);
+        cd->d.dBytes = (const uint8_t *)cd->dBytes.p;
+        launchDictTables(c, cd->d, level, cd->dImg.p);
         cd->d.dImg = (const uint32_t *)cd->dImg.p;
         if (formatted) {
             LAUNCH(c, "k_cdict_tables", k_cdict_tables, dim3(1), dim3(256), 0, ent, (ZsCDictTables *)cd->dTables.p);
@@ -634,9 +640,12 @@ extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t di
 extern "C" void zsmi_freeCDict(zsmi_cdict *cd) { delete cd; }
 extern "C" unsigned zsmi_getDictID_fromCDict(const zsmi_cdict *cd) { return cd ? cd->d.dictID : 0; }
 extern "C" size_t zsmi_sizeofCDict(const zsmi_cdict *cd) { return cd ? cd->dBytes.cap + cd->dImg.cap + cd->dTables.cap : 0; }
-// 0: the call may go on; cd != nullptr
-static int checkCDict(const zsmi_ctx *c, const zsmi_cdict *cd)
+// What a zsmi_cdict * argument asks of a call on context c - 0, with level and dict set: compress at `level`, plainly (dict nullptr: a null
+// cdict at level 3, one without bytes at its own) or with the descriptor; or the error (a dictionary digested on another device: parameter_unsupported)
+static int resolveCDict(const zsmi_ctx *c, const zsmi_cdict *cd, int &level, const ZsCompressDict *&dict)
 {
+    level = cd ? cd->level : 3; dict = cd && !cd->empty ? &cd->d : nullptr;
+    if (!cd) return 0;
     if (!c) return ZSMI_error_init_missing;
     return cd->device == c->device ? 0 : ZSMI_error_parameter_unsupported;
 }
@@ -644,10 +653,9 @@ static int checkCDict(const zsmi_ctx *c, const zsmi_cdict *cd)
 extern "C" int zsmi_compressBatchDevice_usingCDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, const zsmi_cdict *cd)
 {
-    if (!cd) return zsmi_compressBatchDevice(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, 3);
-    if (const int e = checkCDict(c, cd)) return e;
-    if (cd->empty) return zsmi_compressBatchDevice(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, cd->level);
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, cd->level, (const uint8_t *)cd->dBytes.p, &cd->d);
+    int level; const ZsCompressDict *dict;
+    if (const int e = resolveCDict(c, cd, level, dict)) return e;
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, dict);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -951,49 +959,43 @@ static int staged(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, cons
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     return copyBack(c, (const uint8_t *)c->sDst.p, dof.data(), (uint8_t *)dst, dstOffsets, dstSizes, n);
 }
-static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                 uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level, const void *dict, size_t dictSize)
+// dict: the call's dictionary, or nullptr.  hostDict (the _usingDict form): its bytes, which this call stages; dict's other members come from their parse
+static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, void *dst, const uint64_t *dstOffsets,
+                                 uint32_t *dstSizes, int level, const ZsCompressDict *dict, const void *hostDict = nullptr, size_t hostDictSize = 0)
 {
     if (!c) return ZSMI_error_init_missing;
-    ZsCompressDict dc;
-    const bool useDict = dict != nullptr && dictSize != 0;
-    if (useDict) {
-        if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-        if (const int e = parseCompressDict((const uint8_t *)dict, dictSize, dc)) return e;
-    }
     if (n == 0) return 0;
     std::vector<uint32_t> bounds(n);
     for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
-    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes, useDict ? dict : nullptr, dictSize,
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes, hostDict, hostDictSize,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, useDict ? (const uint8_t *)c->sDict.p : nullptr,
-                                                     useDict ? &dc : nullptr);
+                      ZsCompressDict d = dict ? *dict : ZsCompressDict();
+                      if (hostDict) d.dBytes = (const uint8_t *)c->sDict.p;
+                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict ? &d : nullptr);
                   });
 }
 extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                       uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level)
 {
-    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, 0);
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr);
 }
 extern "C" int zsmi_compressBatchHost_usingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                 uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
                                                 const void *dict, size_t dictSize)
 {
-    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict, dictSize);
+    if (!dict || dictSize == 0) return zsmi_compressBatchHost(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level);
+    if (!c) return ZSMI_error_init_missing;
+    if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
+    ZsCompressDict d;
+    if (const int e = parseCompressDict((const uint8_t *)dict, dictSize, d)) return e;
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, &d, dict, dictSize);
 }
 extern "C" int zsmi_compressBatchHost_usingCDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                  uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, const zsmi_cdict *cd)
 {
-    if (!cd) return zsmi_compressBatchHost(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, 3);
-    if (const int e = checkCDict(c, cd)) return e;
-    if (cd->empty) return zsmi_compressBatchHost(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, cd->level);
-    if (n == 0) return 0;
-    std::vector<uint32_t> bounds(n);
-    for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
-    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes, nullptr, 0,
-                  [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, cd->level, (const uint8_t *)cd->dBytes.p, &cd->d);
-                  });
+    int level; const ZsCompressDict *dict;
+    if (const int e = resolveCDict(c, cd, level, dict)) return e;
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict);
 }
 static int decompressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
@@ -1079,45 +1081,37 @@ extern "C" size_t zsmi_decodeScratchBytes(zsmi_ctx *c)
     return c->dec.held();
 }
 
+// one frame through a borrowed context: with the digested dictionary cd, or at `level` with the dictionary's bytes (or with none)
+static size_t compressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level, const void *dict, size_t dictSize, const zsmi_cdict *cd)
+{
+    if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
+    Borrowed b; zsmi_ctx *c = b.c;
+    if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
+    const size_t bound = zsmi_compressBound(srcSize);
+    std::vector<uint8_t> tmp;
+    uint8_t *out = (uint8_t *)dst;
+    if (dstCapacity < bound) { tmp.resize(bound); out = tmp.data(); }     // compress into a bound-sized buffer, then check the fit
+    const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
+    const int rc = cd ? zsmi_compressBatchHost_usingCDict(c, src, &so, &ss, 1, out, &dof, &ds, cd)
+                      : zsmi_compressBatchHost_usingDict(c, src, &so, &ss, 1, out, &dof, &ds, level, dict, dictSize);
+    if (rc) return ZSMI_ERR(rc);
+    if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
+    if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
+    if (out != dst) memcpy(dst, out, ds);
+    return ds;
+}
 extern "C" size_t zsmi_compress(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level)
 {
-    return zsmi_compress_usingDict(dst, dstCapacity, src, srcSize, nullptr, 0, level);
+    return compressOneShot(dst, dstCapacity, src, srcSize, level, nullptr, 0, nullptr);
 }
 extern "C" size_t zsmi_compress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level)
 {
-    if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
-    Borrowed b; zsmi_ctx *c = b.c;
-    if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
-    const size_t bound = zsmi_compressBound(srcSize);
-    std::vector<uint8_t> tmp;
-    uint8_t *out = (uint8_t *)dst;
-    if (dstCapacity < bound) { tmp.resize(bound); out = tmp.data(); }     // compress into a bound-sized buffer, then check the fit
-    const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
-    const int rc = zsmi_compressBatchHost_usingDict(c, src, &so, &ss, 1, out, &dof, &ds, level, dict, dictSize);
-    if (rc) return ZSMI_ERR(rc);
-    if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
-    if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
-    if (out != dst) memcpy(dst, out, ds);
-    return ds;
+    return compressOneShot(dst, dstCapacity, src, srcSize, level, dict, dictSize, nullptr);
 }
-// (the borrowed context is one of the current device: a dictionary digested on another device is parameter_unsupported)
+// a null cd: the plain call at level 3.  (The borrowed context is one of the current device: a dictionary digested on another device is parameter_unsupported)
 extern "C" size_t zsmi_compress_usingCDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd)
 {
-    if (!cd) return zsmi_compress(dst, dstCapacity, src, srcSize, 3);
-    if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
-    Borrowed b; zsmi_ctx *c = b.c;
-    if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
-    const size_t bound = zsmi_compressBound(srcSize);
-    std::vector<uint8_t> tmp;
-    uint8_t *out = (uint8_t *)dst;
-    if (dstCapacity < bound) { tmp.resize(bound); out = tmp.data(); }     // compress into a bound-sized buffer, then check the fit
-    const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
-    const int rc = zsmi_compressBatchHost_usingCDict(c, src, &so, &ss, 1, out, &dof, &ds, cd);
-    if (rc) return ZSMI_ERR(rc);
-    if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
-    if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
-    if (out != dst) memcpy(dst, out, ds);
-    return ds;
+    return compressOneShot(dst, dstCapacity, src, srcSize, 3, nullptr, 0, cd);
 }
 extern "C" size_t zsmi_decompress(void *dst, size_t dstCapacity, const void *src, size_t srcSize)
 {

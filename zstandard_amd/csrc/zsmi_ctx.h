@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/zsmi.h"
+#include "zsmi_device.h"
 
 #include <cstring>
 #include <vector>
@@ -39,28 +40,41 @@ typedef Buf<pinAlloc, hipHostFree> PinBuf;
 struct TimedLaunch { const char *name; hipEvent_t a, b; };
 struct DecodePlan;
 
+// The plan of a compress call (built in the compress section of zsmi_api.hip): chunks -> blocks and LZ units, on the host and in device
+// memory.  Everything here is valid together, for the layout `key` states; the dictionary list only while hasDictList.
+struct CompressPlan {
+    std::vector<uint64_t> key;           // n, then the srcOffsets, dstOffsets and srcSizes the plan was built from
+    uint64_t blocks = 0; uint32_t maxChunkBlocks = 1;
+    PinBuf hBlocks, hChunks, hUnits, hUnitsDict;
+    DevBuf dBlocks, dChunks, dUnits, dUnitsDict;
+    // A run of units in chunk order inside one of the two device lists: before[i] (n + 1 entries) units of the run belong to chunks in
+    // front of chunk i; the run starts at unit `base` of its list.
+    //   dUnits:     [small: units of <= 64 KiB][big]
+    //   dUnitsDict: [whole: chunks of <= 64 KiB, one prefixed unit each][tail: the other small units] - dictionary calls; built on the first of a plan
+    struct Run { std::vector<uint32_t> before; uint32_t base = 0; } small, big, whole, tail;
+    bool hasDictList = false;
+    struct Units { const ZsUnitDesc *d; uint32_t n; };
+    struct Cut { uint32_t chunk1, nb, block0; };
+
+    int build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict);
+    Cut cut(uint32_t chunk0, uint32_t cap) const;                                      // the sub-batch of whole chunks from chunk0: at most cap blocks (one chunk at least)
+    Units units(int kind, bool dict, uint32_t chunk0, uint32_t chunk1) const;          // kind: kUnitsPfx, kUnitsSmall, kUnitsBig
+};
+
 struct zsmi_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool ownStream = false;
     uint32_t maxBlocksInFlight = 16384;   // ZSMI_BLOCKS_IN_FLIGHT: 64 KiB blocks per sub-batch (scratch ~0.6 MiB a block, reserved for what a call needs); 2 GiB of 128 KiB chunks: 8192: 86.5, 16384: 88.2, 32768: 89.4 GiB/s
-    // compress workspace: the plan and the scratch of a sub-batch (its sizes: the compress section of zsmi_api.hip)
-    DevBuf dBlocks, dChunks, dUnits;     // dUnits: small units (<= 64 KiB) first, then big ones, each in chunk order
+    // compress workspace: the plan of the call's layout and the scratch of a sub-batch (its sizes: the compress section of zsmi_api.hip)
+    CompressPlan plan;
     struct Scratch {
         DevBuf dDist, dDistHi, dCand, dRecs, dRes, dSeqs, dHdrs, dLits, dStreams, dLitSec, dSeqSec, dMetas;
         bool reserve(uint32_t cap);            // cap: blocks of a sub-batch
     } scratch;
+    DevBuf dDictImg;                       // a _usingDict call's candidate-table images of the prefix (a digested dictionary holds its own)
     int stopAfterWalk = 0;                 // ZSMI_STOP_AFTER_WALK (debug-hooks build, tools/walk_check.py): the entropy kernels are not launched
     int stopLit = 0, stopSeq = 0;          // timing aids of a -DZSMI_DEBUG_HOOKS build (ZSMI_STOP_LIT / ZSMI_STOP_SEQ): end a kernel after a stage; always 0 in the product
-    PinBuf hBlocks, hChunks, hUnits;
-    std::vector<uint32_t> smallBefore, bigBefore;   // per chunk (n + 1 entries): small / big units in front of it
-    uint32_t planSmall = 0, planBig = 0;
-    std::vector<uint64_t> planKey;       // copy of (srcOffsets, srcSizes, dstOffsets) the device-side plan was built from
-    uint64_t planBlocks = 0; uint32_t planMaxChunkBlocks = 1;
-    // dictionary calls: their own unit list for the plan (built on the first such call), the prefix's candidate-table images
-    PinBuf hUnitsDict; DevBuf dUnitsDict, dDictImg;
-    std::vector<uint32_t> wholeBefore, tailBefore;
-    uint32_t planDictWhole = 0; bool planDict = false;
     // decompress workspace: the item list (on the host: two pinned buffers taken in turn) and the scratch of a sub-batch, whose sizes for a
     // call's plan are stated once, in the decompress section (DecodeScratch::each)
     DevBuf dItems;
@@ -113,13 +127,18 @@ static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz
 #define LAUNCH(ctx, name, kernel, grid, block, lds, ...) LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, lds, __VA_ARGS__)
 
 // ---- the batch calls in device memory (zsmi_api.hip: the compress and the decompress section state their arguments) ----
-// dImg, dTables: a digested dictionary's (zsmi_cdict) - the prefix's candidate-table images, built once and not by the call, and the
-// dictionary's entropy tables in encoder form (nullptr: raw content, none)
+// A dictionary as the compress launch sequence takes it (nullptr: none).  dBytes: its bytes in device memory; contentOff .. rep: what
+// parseCompressDict found in them (raw content: all of it, no ID, offsets {1, 4, 8}).  dImg, dTables: a digested dictionary's (zsmi_cdict) - the
+// prefix's candidate-table images, built once and not by the call, and a formatted one's entropy tables in encoder form.
 struct ZsCDictTables;
-struct ZsCompressDict { uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 }; const uint32_t *dImg = nullptr; const ZsCDictTables *dTables = nullptr; };
+struct ZsCompressDict {
+    const uint8_t *dBytes = nullptr;
+    uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 };
+    const uint32_t *dImg = nullptr; const ZsCDictTables *dTables = nullptr;
+};
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const uint8_t *dDict, const ZsCompressDict *dict, uint32_t *dStats = nullptr);
+                                   const ZsCompressDict *dict, uint32_t *dStats = nullptr);
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                      const void *dDict, uint32_t dictSize);
