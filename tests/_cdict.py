@@ -1,6 +1,7 @@
 """What the digested-dictionary tests share (tests/test_gpu_cdict.py) with the generator of their libzstd fixture
 (tests/golden/gen_fixtures_cdict_sizes.py): the chunks of the size test, and a parser of a frame's block structure."""
 import _dicts as X
+import _framewriter as W
 
 SIZE_CHUNKS = (1024, 4096, 16384, 65536)
 SIZE_BYTES = 256 * 1024
@@ -15,44 +16,10 @@ def size_chunks(cls, cs):
 def blocks_of(frame):
     """[(block type, literals type or None, sequence modes byte or None)] of a single-segment frame as this library writes them.  The
     modes byte is None where the block has no sequences.  RFC 8878 3.1.1.1 - 3.1.1.3."""
-    assert frame[:4] == b"\x28\xb5\x2f\xfd"
-    fhd = frame[4]
-    assert fhd & 0x20, "single segment"
-    did = (0, 1, 2, 4)[fhd & 3]
-    fcs = (1, 2, 4, 8)[fhd >> 6]
-    pos = 5 + did + fcs
-    out = []
-    while True:
-        h = int.from_bytes(frame[pos:pos + 3], "little"); pos += 3
-        last, btype, bsize = h & 1, (h >> 1) & 3, h >> 3
-        if btype == 2:
-            b = frame[pos:pos + bsize]
-            lt, sf = b[0] & 3, (b[0] >> 2) & 3
-            if lt < 2:                                       # raw, RLE
-                lh = (1, 2, 1, 3)[sf]
-                regen = (b[0] >> 3) if lh == 1 else (int.from_bytes(b[:lh], "little") >> 4)
-                lsz = lh + (regen if lt == 0 else 1)
-            else:                                            # compressed, treeless
-                lh = (3, 3, 4, 5)[sf]
-                bits = (10, 10, 14, 18)[sf]
-                v = int.from_bytes(b[:lh], "little")
-                lsz = lh + ((v >> (4 + bits)) & ((1 << bits) - 1))
-            q = lsz
-            nseq = b[q]; q += 1
-            if nseq >= 128:
-                if nseq == 255:
-                    nseq = b[q] + (b[q + 1] << 8) + 0x7F00; q += 2
-                else:
-                    nseq = ((nseq - 128) << 8) + b[q]; q += 1
-            out.append((2, lt, b[q] if nseq else None))
-            pos += bsize
-        else:
-            out.append((btype, None, None))
-            pos += 1 if btype == 1 else bsize
-        if last:
-            break
-    assert pos == len(frame), (pos, len(frame))
-    return out
+    assert W.frame_header(frame).single, "single segment"
+    found = list(W.blocks(frame))
+    assert found[-1].end == len(frame), (found[-1].end, len(frame))
+    return [(b.type, b.lit_type, b.modes) if b.type == 2 else (b.type, None, None) for b in found]
 
 
 def uses_dictionary_tables(block):

@@ -156,21 +156,3 @@ def zstd_decompress_dict(frame, cap, dic):
     out = ctypes.create_string_buffer(max(cap, 1))
     r = Z.ZSTD_decompress_usingDict(Z.dctx, out, cap, frame, len(frame), dic, len(dic))
     return None if Z.ZSTD_isError(r) else out.raw[:r]
-
-
-def batch(chunks):
-    """(src, offsets, sizes) of chunks laid back to back"""
-    sizes = np.array([len(c) for c in chunks], dtype=np.uint32)
-    offs = np.zeros(len(chunks), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-    return np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8), offs, sizes
-
-
-def oracle_frames(chunks, level, dic, threads=8):
-    """oracle E's frames for a batch with one dictionary, through its batch form"""
-    src, offs, sizes = batch(chunks)
-    a, o, s = O.compress_batch_using_dict(src, offs, sizes, dic, level, threads)
-    return [a[int(o[i]):int(o[i]) + int(s[i])].tobytes() for i in range(len(chunks))]
-
-
-def first_difference(a, b):
-    return next((k for k in range(min(len(a), len(b))) if a[k] != b[k]), min(len(a), len(b)))

@@ -6,6 +6,7 @@ FSE and Huffman streams are written by inverting the spec's DECODING tables (RFC
 successor state is known, take the state that decodes that symbol and whose [baseline, baseline + 2^nbBits) range covers the successor.
 No encoder heuristics; numpy-free plain Python.  Section references below are to RFC 8878."""
 import struct
+from types import SimpleNamespace
 
 MAGIC = 0xFD2FB528
 MASK64 = (1 << 64) - 1
@@ -167,6 +168,41 @@ def ncount(norm, al):
             nb -= 1; threshold >>= 1
     assert remaining == 1 and s == len(norm), "counts must end at the last symbol"
     return acc.to_bytes((nbits + 7) // 8, "little")
+
+
+def read_ncount(b, pos, max_symbol):
+    """the inverse of ncount (FSE_readNCount) on the description at b[pos:]: (normalised counts, accuracy log, position behind the
+    description).  Counts are read up to symbol max_symbol; a run of zeros may not lead past the symbol behind it."""
+    bits, at = int.from_bytes(b[pos:pos + 256], "little"), 0
+
+    def take(n, keep=False):
+        nonlocal at
+        v = (bits >> at) & ((1 << n) - 1)
+        at += 0 if keep else n
+        return v
+    al = take(4) + 5
+    remaining, threshold, nb = (1 << al) + 1, 1 << al, al + 1
+    norm, prev0 = [], False
+    while remaining > 1 and len(norm) <= max_symbol:
+        if prev0:
+            while take(2, keep=True) == 3:               # (the writer's 16 set bits for 24 zeros are eight of these)
+                norm += [0] * 3; at += 2
+            norm += [0] * take(2)
+            assert len(norm) <= max_symbol + 1
+        mx = (2 * threshold - 1) - remaining
+        if take(nb - 1, keep=True) < mx:
+            c = take(nb - 1)
+        else:
+            c = take(nb)
+            if c >= threshold:
+                c -= mx
+        c -= 1
+        remaining -= abs(c)
+        norm.append(c); prev0 = c == 0
+        while remaining < threshold:
+            nb -= 1; threshold >>= 1
+    assert remaining == 1
+    return norm, al, pos + (at + 7) // 8
 
 
 def normalize(hist, al, cap=None):
@@ -523,3 +559,58 @@ def frame(blocks, fcs="auto", fcs_bytes=None, single=True, window=None, dict_id=
 def skippable(payload, nibble=0, size=None):
     """§3.1.2 skippable frame: magic 0x184D2A50 + nibble, a 4-byte size (default: the payload's), the payload"""
     return struct.pack("<II", 0x184D2A50 + nibble, len(payload) if size is None else size) + bytes(payload)
+
+
+# ---------------------------------------------------------------- reading a frame's structure back (§3.1.1)
+def frame_header(frame):
+    """the fields of the header of the frame at frame[0:]: single (segment), dict_desc (the dictionary-ID field's size code), dict_id,
+    window (bytes; -1 for a single-segment frame), content_size (None if not stated), checksum (flag), reserved (bit), end (position
+    of the first block)"""
+    assert frame[:4] == MAGIC.to_bytes(4, "little")
+    fhd = frame[4]
+    h = SimpleNamespace(single=(fhd >> 5) & 1, dict_desc=fhd & 3, checksum=(fhd >> 2) & 1, reserved=(fhd >> 3) & 1, window=-1)
+    pos = 5
+    if not h.single:
+        base = 1 << (10 + (frame[pos] >> 3)); h.window = base + (base // 8) * (frame[pos] & 7); pos += 1
+    did = (0, 1, 2, 4)[h.dict_desc]
+    h.dict_id = int.from_bytes(frame[pos:pos + did], "little"); pos += did
+    fcs = (h.single, 2, 4, 8)[fhd >> 6]
+    h.content_size = int.from_bytes(frame[pos:pos + fcs], "little") + (256 if fcs == 2 else 0) if fcs else None
+    h.end = pos + fcs
+    return h
+
+
+def blocks(frame):
+    """yields, for every block of the frame at frame[0:]: type (0 raw, 1 RLE, 2 compressed), size (the header's Block_Size), last, pos and
+    end (of the block's bytes in the frame).  A compressed block also has lit_type, size_format, regen and csize (its literals' regenerated
+    and stored sizes: stored is regen for raw, 1 for RLE literals), lit_header (bytes), huf_pos (where a Huffman description starts, for
+    lit_type 2; else None), seq_pos (of the sequences section), nseq, modes (the byte; None where nseq is 0) and tables_pos (behind the
+    modes byte: the first table description, or the bit stream).  Nothing beyond what locates these fields is checked."""
+    pos = frame_header(frame).end
+    last = 0
+    while not last:
+        h = int.from_bytes(frame[pos:pos + 3], "little"); pos += 3
+        last = h & 1
+        b = SimpleNamespace(type=(h >> 1) & 3, size=h >> 3, last=last, pos=pos)
+        b.end = pos + (1 if b.type == 1 else b.size)
+        if b.type == 2:
+            b.lit_type, b.size_format = frame[pos] & 3, (frame[pos] >> 2) & 3
+            if b.lit_type < 2:                                              # raw, RLE: 5, 12 or 20 bits of size
+                b.lit_header = (1, 2, 1, 3)[b.size_format]
+                b.regen = int.from_bytes(frame[pos:pos + b.lit_header], "little") >> (3 if b.lit_header == 1 else 4)
+                b.csize = b.regen if b.lit_type == 0 else 1
+            else:                                                           # compressed, treeless: two sizes of 10, 10, 14 or 18 bits
+                b.lit_header, nbits = ((3, 10), (3, 10), (4, 14), (5, 18))[b.size_format]
+                v = int.from_bytes(frame[pos:pos + b.lit_header], "little") >> 4
+                b.regen, b.csize = v & ((1 << nbits) - 1), v >> nbits
+            b.huf_pos = pos + b.lit_header if b.lit_type == 2 else None
+            q = b.seq_pos = pos + b.lit_header + b.csize
+            b.nseq = frame[q]; q += 1
+            if b.nseq == 255:
+                b.nseq = int.from_bytes(frame[q:q + 2], "little") + 0x7F00; q += 2
+            elif b.nseq >= 128:
+                b.nseq = ((b.nseq - 128) << 8) + frame[q]; q += 1
+            b.modes = frame[q] if b.nseq else None
+            b.tables_pos = q + (1 if b.nseq else 0)
+        yield b
+        pos = b.end

@@ -1,0 +1,38 @@
+"""The HIP runtime through ctypes, for tests that hand the library device pointers without torch: hip_of() and a canary-padded buffer."""
+import ctypes
+
+CANARY = 0xA5
+PAD = 4096
+
+
+def hip_of():
+    """the HIP runtime libzsmi.so is linked against (by its soname: the copy already loaded with it)"""
+    from zstandard_amd import _lib
+    _lib.lib()
+    H = ctypes.CDLL("libamdhip64.so.7")
+    H.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+    H.hipFree.argtypes = [ctypes.c_void_p]
+    H.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    H.hipMemset.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]
+    return H
+
+
+class Dev:
+    """device buffer of n bytes + PAD canary bytes on each side; .p is the first byte after the front canary"""
+
+    def __init__(self, H, n, fill=b""):
+        self.H, self.n = H, n
+        self.base = ctypes.c_void_p()
+        assert H.hipMalloc(ctypes.byref(self.base), n + 2 * PAD) == 0
+        assert H.hipMemset(self.base, CANARY, n + 2 * PAD) == 0
+        self.p = self.base.value + PAD
+        if fill:
+            assert H.hipMemcpy(ctypes.c_void_p(self.p), fill, len(fill), 1) == 0
+
+    def all(self) -> bytes:
+        out = ctypes.create_string_buffer(self.n + 2 * PAD)
+        assert self.H.hipMemcpy(out, self.base, self.n + 2 * PAD, 2) == 0
+        return out.raw
+
+    def free(self):
+        self.H.hipFree(self.base)

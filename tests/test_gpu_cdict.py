@@ -3,19 +3,18 @@ the _usingDict frames byte for byte (and so oracle E's).  With a formatted dicti
 dictionary's own entropy tables - Treeless literals (type 3), Repeat_Mode (3) sequence tables - where that is smaller: every frame must
 decode to its input with the dictionary under oracle D, the library's decoder and upstream libzstd; a frame that uses neither is the
 _usingDict frame; no later block uses them; the batch never grows and shrinks at 1 KiB; symbols the dictionary cannot code are never
-coded with it.  Dictionaries and chunks: tests/_dicts.py; frame structure: tests/_cdict.py."""
-import ctypes, os, subprocess, sys
+coded with it.  Dictionaries and chunks: tests/_dicts.py; batches and round trips: tests/_batch.py; frame structure: tests/_cdict.py."""
+import ctypes, os
 import numpy as np
 import pytest
 import _oracle as O
 import _data as D
 import _dicts as X
+import _batch as B
 import _cdict as K
 import _framewriter as W
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR = 0xFFFFFF88
 SIZES_FIX = os.path.join(D.GOLDEN, "libzstd_fixtures_cdict_sizes.npz")
 
 
@@ -23,40 +22,6 @@ SIZES_FIX = os.path.join(D.GOLDEN, "libzstd_fixtures_cdict_sizes.npz")
 def codec():
     from zstandard_amd import BatchCodec
     return BatchCodec(0)
-
-
-def frames_of(res, n):
-    arena, do, dsz = res
-    assert (dsz <= ERR).all()
-    return [arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes() for i in range(n)]
-
-
-def compress_cdict(codec, chunks, cd):
-    src, offs, sizes = X.batch(chunks)
-    return frames_of(codec.compress_host(src, offs, sizes, cdict=cd), len(chunks))
-
-
-def compress_dict(codec, chunks, level, dic=b""):
-    src, offs, sizes = X.batch(chunks)
-    return frames_of(codec.compress_host(src, offs, sizes, level, dic), len(chunks))
-
-
-def decode_many(codec, frames, caps, dic):
-    src, offs, sizes = X.batch(frames)
-    out, oo, osz = codec.decompress_host(src, offs, sizes, np.maximum(np.array(caps, dtype=np.uint32), 1), dic)
-    return [(int(osz[i]), out[int(oo[i]):int(oo[i]) + (int(osz[i]) if osz[i] <= ERR else 0)].tobytes()) for i in range(len(frames))]
-
-
-def assert_round_trip(codec, frames, chunks, dic, what=""):
-    bound = codec.L.zsmi_compressBound
-    for i, (f, c) in enumerate(zip(frames, chunks)):
-        assert len(f) <= bound(len(c)), (what, i)
-        assert O.decompress_using_dict(f, len(c), dic) == c, (what, "oracle D", i, len(c))
-    for i, ((sz, got), c) in enumerate(zip(decode_many(codec, frames, [len(c) for c in chunks], dic), chunks)):
-        assert sz == len(c) and got == c, (what, "zsmi_decompressBatchHost_usingDict", i, len(c), hex(sz))
-    if X.zstd():
-        for i, (f, c) in enumerate(zip(frames, chunks)):
-            assert X.zstd_decompress_dict(f, len(c), dic) == c, (what, "libzstd", i, len(c))
 
 
 def assert_structure(frames, plain, what=""):
@@ -68,7 +33,7 @@ def assert_structure(frames, plain, what=""):
         if K.uses_dictionary_tables(blocks[0]):
             used += 1
         else:
-            assert f == p, (what, i, len(f), len(p), X.first_difference(f, p))
+            assert f == p, (what, i, len(f), len(p), B.first_difference(f, p))
     return used
 
 
@@ -86,10 +51,10 @@ def test_raw_content_frames_equal_usingdict(codec, level):
         chunks = X.prefix_chunks(dic)
         cd = CompressionDict(codec, dic, level)
         assert cd.dict_id == 0 and cd.device_bytes >= len(dic)
-        frames = compress_cdict(codec, chunks, cd)
+        frames = B.compress_many(codec, chunks, cdict=cd)
         cd.close()
-        plain = compress_dict(codec, chunks, level, dic)
-        expect = X.oracle_frames(chunks, level, dic)
+        plain = B.compress_many(codec, chunks, level, dic)
+        expect = B.oracle_frames(chunks, level, dic)
         for i, (f, p, e) in enumerate(zip(frames, plain, expect)):
             assert f == p == e, (name, level, i, len(chunks[i]), len(f), len(p), len(e))
 
@@ -103,14 +68,14 @@ def test_formatted_dictionaries_round_trip(codec, level):
         chunks = X.prefix_chunks(dic)
         cd = CompressionDict(codec, dic, level)
         assert cd.dict_id == int.from_bytes(dic[4:8], "little")
-        frames = compress_cdict(codec, chunks, cd)
+        frames = B.compress_many(codec, chunks, cdict=cd)
         cd.close()
-        assert_round_trip(codec, frames, chunks, dic, name)
+        B.assert_round_trip(codec, frames, chunks, dic, name)
         cd_id = int.from_bytes(dic[4:8], "little")
         for f in frames:
             code = f[4] & 3
             assert code and int.from_bytes(f[5:5 + (4 if code == 3 else code)], "little") == cd_id
-        used += assert_structure(frames, compress_dict(codec, chunks, level, dic), name)
+        used += assert_structure(frames, B.compress_many(codec, chunks, level, dic), name)
     assert used > 0
 
 
@@ -120,13 +85,13 @@ def test_small_records_use_the_dictionarys_tables(codec):
     for cls in X.RECORD_CLASSES:
         dic, chunks = X.trained(cls), K.size_chunks(cls, 1024)
         cd = CompressionDict(codec, dic, 3)
-        frames = compress_cdict(codec, chunks, cd)
+        frames = B.compress_many(codec, chunks, cdict=cd)
         cd.close()
         first = [K.blocks_of(f)[0] for f in frames]
         assert any(b[1] == 3 for b in first), (cls, "no treeless literals")
         assert any(b[2] is not None and any(((b[2] >> s) & 3) == 3 for s in (6, 4, 2)) for b in first), (cls, "no repeat mode")
-        assert_structure(frames, compress_dict(codec, chunks, 3, dic), cls)
-        assert_round_trip(codec, frames, chunks, dic, cls)
+        assert_structure(frames, B.compress_many(codec, chunks, 3, dic), cls)
+        B.assert_round_trip(codec, frames, chunks, dic, cls)
 
 
 # ------------------------------------------------------------------ 4. size
@@ -142,8 +107,8 @@ def test_sizes_against_usingdict_and_libzstd(codec):
         cd = CompressionDict(codec, dic, 3)
         for cs in K.SIZE_CHUNKS:
             chunks = K.size_chunks(cls, cs)
-            a = compress_cdict(codec, chunks, cd)
-            b = compress_dict(codec, chunks, 3, dic)
+            a = B.compress_many(codec, chunks, cdict=cd)
+            b = B.compress_many(codec, chunks, 3, dic)
             ta, tb, tz = sum(map(len, a)), sum(map(len, b)), int(fix[f"{cls}_{cs}"])
             table[(cls, cs)] = (tb, ta, tz, round(tb / tz, 4), round(ta / tz, 4))
             grow = max(len(x) - len(y) for x, y in zip(a, b))
@@ -188,10 +153,10 @@ def test_symbols_the_dictionary_cannot_code(codec):
     chunks = covered + foreign + far
     for level in (1, 3):
         cd = CompressionDict(codec, dic, level)
-        frames = compress_cdict(codec, chunks, cd)
+        frames = B.compress_many(codec, chunks, cdict=cd)
         cd.close()
-        assert_round_trip(codec, frames, chunks, dic, "narrow")
-        assert_structure(frames, compress_dict(codec, chunks, level, dic), "narrow")
+        B.assert_round_trip(codec, frames, chunks, dic, "narrow")
+        assert_structure(frames, B.compress_many(codec, chunks, level, dic), "narrow")
         for f, c in zip(frames[len(covered):len(covered) + 4], foreign[:4]):              # bytes without a code: never treeless
             b0 = K.blocks_of(f)[0]
             assert b0[1] != 3, b0
@@ -209,23 +174,21 @@ def test_one_cdict_many_calls_and_two_in_alternation(codec):
     first = {}
     for rnd in range(2):
         for k, chunks in enumerate(layouts):
-            plain = compress_dict(codec, chunks, 3)
-            ud = compress_dict(codec, chunks, 3, da)
-            fa = compress_cdict(codec, chunks, ca)
-            fb = compress_cdict(codec, chunks, cb)
-            fa2 = compress_cdict(codec, chunks, ca)
+            plain = B.compress_many(codec, chunks, 3)
+            ud = B.compress_many(codec, chunks, 3, da)
+            fa = B.compress_many(codec, chunks, cdict=ca)
+            fb = B.compress_many(codec, chunks, cdict=cb)
+            fa2 = B.compress_many(codec, chunks, cdict=ca)
             assert fa == fa2
-            assert compress_dict(codec, chunks, 3) == plain and compress_dict(codec, chunks, 3, da) == ud      # the older calls: unchanged
+            assert B.compress_many(codec, chunks, 3) == plain and B.compress_many(codec, chunks, 3, da) == ud      # the older calls: unchanged
             if rnd == 0:
                 first[k] = (plain, ud, fa, fb)
-                src, offs, sizes = X.batch(chunks)
-                ea, eo, es = O.compress_batch(src, offs, sizes, 3, 8)
-                assert plain == [ea[int(eo[i]):int(eo[i]) + int(es[i])].tobytes() for i in range(len(chunks))]
-                assert ud == X.oracle_frames(chunks, 3, da)
-                assert_round_trip(codec, fa, chunks, da, "A")
-                assert_round_trip(codec, fb, chunks, db, "B")
+                assert plain == B.oracle_frames(chunks, 3)
+                assert ud == B.oracle_frames(chunks, 3, da)
+                B.assert_round_trip(codec, fa, chunks, da, "A")
+                B.assert_round_trip(codec, fb, chunks, db, "B")
                 assert_structure(fa, ud, "A")
-                assert_structure(fb, compress_dict(codec, chunks, 1, db), "B")
+                assert_structure(fb, B.compress_many(codec, chunks, 1, db), "B")
             else:
                 assert first[k] == (plain, ud, fa, fb)
     ca.close(); cb.close()
@@ -249,7 +212,7 @@ def test_one_shot_null_and_compressor_forms(codec):
     cd = CompressionDict(codec, dic, 3)
     data = X.class_data("xml_records")
     chunks = [data[:1024], data[2000:2000 + 4096], b"", b"q", data[10000:10000 + 70000]]
-    batch = compress_cdict(codec, chunks, cd)
+    batch = B.compress_many(codec, chunks, cdict=cd)
     for c, f in zip(chunks, batch):
         out = ctypes.create_string_buffer(L.zsmi_compressBound(len(c)))
         r = L.zsmi_compress_usingCDict(out, len(out), c, len(c), cd.handle)
@@ -259,8 +222,8 @@ def test_one_shot_null_and_compressor_forms(codec):
         assert out.raw[:r] == O.compress(c, 3)
     small = ctypes.create_string_buffer(8)
     assert L.zsmi_getErrorCode(L.zsmi_compress_usingCDict(small, 8, chunks[1], len(chunks[1]), cd.handle)) == 70
-    src, offs, sizes = X.batch(chunks)
-    assert frames_of(codec.compress_host(src, offs, sizes, cdict=None), len(chunks)) == compress_dict(codec, chunks, 3)
+    src, offs, sizes = B.batch(chunks)
+    assert B.frames_of(codec.compress_host(src, offs, sizes, cdict=None), len(chunks)) == B.compress_many(codec, chunks, 3)
     cd.close()
 
 
@@ -269,57 +232,44 @@ import sys, os, ctypes
 import torch
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import numpy as np
-import _oracle as O, _dicts as X, _cdict as K
+import _oracle as O, _dicts as X, _cdict as K, _batch as B
 from zstandard_amd import BatchCodec, CompressionDict
-CANARY = 0xA5
 bc = BatchCodec(0)
 L = bc.L
 dic = X.trained("json_records")
 data = X.class_data("json_records", 3 << 20)
 rng = np.random.default_rng(4)
 sizes = np.concatenate([rng.integers(0, 70000, 40), [1024] * 40, [65536, 65537, 131072, 131073, 200000, 1, 0, 17]]).astype(np.uint32)
-so = np.zeros(len(sizes), dtype=np.uint64); so[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
 assert int(sizes.sum()) <= len(data)
 src_np = np.frombuffer(data[:int(sizes.sum())], dtype=np.uint8)
-bounds = np.array([L.zsmi_compressBound(int(s)) for s in sizes], dtype=np.uint64)
-gaps = rng.integers(0, 300, len(sizes)).astype(np.uint64) * (np.arange(len(sizes)) % 2)
-do = np.zeros(len(sizes), dtype=np.uint64)
-pos = 0
-for i in range(len(sizes)):
-    pos += int(gaps[i]); do[i] = pos; pos += int(bounds[i])
-total = pos + 4096
+so, do, bounds, total = B.ragged_device_layout(L, sizes, rng)
+chunks = B.cut(src_np, so, sizes)
 src = torch.from_numpy(src_np.copy()).cuda()
 for level in (1, 3, 4):
     cd = CompressionDict(bc, dic, level)
-    dst = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda")
+    dst = torch.full((total,), B.CANARY, dtype=torch.uint8, device="cuda")
     dsz = torch.zeros(len(sizes), dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     bc.compress_device(src.data_ptr(), so, sizes, dst.data_ptr(), do, dsz.data_ptr(), cdict=cd)
     bc.sync()
     host = dst.cpu().numpy(); sz = dsz.cpu().numpy().view(np.uint32)
-    inside = np.zeros(total, dtype=bool)
-    for i in range(len(sizes)):
-        assert sz[i] <= bounds[i], (level, i)
-        inside[int(do[i]):int(do[i]) + int(sz[i])] = True
-    bad = np.flatnonzero(~inside & (host != CANARY))
-    assert bad.size == 0, (level, "written outside the frames", bad[:10].tolist())
-    arena, hdo, hsz = bc.compress_host(src_np, so, sizes, cdict=cd)
-    ua, uo, us = bc.compress_host(src_np, so, sizes, level, dic)
+    B.assert_only_frames_written(host, do, sz, bounds, B.CANARY, level)
+    host_form = B.cut(*bc.compress_host(src_np, so, sizes, cdict=cd))
+    using_dict = B.cut(*bc.compress_host(src_np, so, sizes, level, dic))
     used = 0
-    for i in range(len(sizes)):
-        f = host[int(do[i]):int(do[i]) + int(sz[i])].tobytes(); c = src_np[int(so[i]):int(so[i]) + int(sizes[i])].tobytes()
+    for i, (f, c) in enumerate(zip(B.cut(host, do, sz), chunks)):
         assert O.decompress_using_dict(f, len(c), dic) == c, (level, i)
-        assert f == arena[int(hdo[i]):int(hdo[i]) + int(hsz[i])].tobytes(), ("host form", level, i)
+        assert f == host_form[i], ("host form", level, i)
         blocks = K.blocks_of(f)
         assert not any(K.uses_dictionary_tables(b) for b in blocks[1:]), (level, i)
         if K.uses_dictionary_tables(blocks[0]):
             used += 1
         else:
-            assert f == ua[int(uo[i]):int(uo[i]) + int(us[i])].tobytes(), ("usingDict", level, i)
+            assert f == using_dict[i], ("usingDict", level, i)
     assert used > 0
     cd.close()
 # a context of another device is refused where there is one; NULL is the plain call at level 3
-dst0 = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda"); dst1 = dst0.clone()
+dst0 = torch.full((total,), B.CANARY, dtype=torch.uint8, device="cuda"); dst1 = dst0.clone()
 s0 = torch.zeros(len(sizes), dtype=torch.int32, device="cuda"); s1 = s0.clone()
 bc.compress_device(src.data_ptr(), so, sizes, dst0.data_ptr(), do, s0.data_ptr(), 3)
 p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
@@ -334,40 +284,36 @@ print("CHILD-OK")
 def test_device_pointer_form_stays_in_bounds():
     """zsmi_compressBatchDevice_usingCDict: canary-filled output, ragged chunks around the 64 KiB limit and over it; every frame within
     zsmi_compressBound, nothing written outside the frames; the frames of the host form; they decode under oracle D"""
-    r = subprocess.run([sys.executable, "-c", _DEVICE_CHILD, ROOT], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CHILD-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    B.run_child("-c", _DEVICE_CHILD, B.ROOT)
 
 
 _SUB_CHILD = r'''
 import sys, os
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import numpy as np
-import _oracle as O, _data as D, _dicts as X, _cdict as K
+import _oracle as O, _data as D, _dicts as X, _cdict as K, _batch as B
 from zstandard_amd import BatchCodec, CompressionDict
-ERR = 0xFFFFFF88
 dic = X.trained("zipf")
 bc = BatchCodec()
 data = D.zipf_log(16 << 20, seed_lo=4343)
 rng = np.random.default_rng(22)
 sizes = np.concatenate([rng.integers(0, 190000, 120), [65536] * 40, [1024] * 60, [131072] * 6]).astype(np.uint32)
 rng.shuffle(sizes)
-offs = np.zeros(len(sizes), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
+offs = B.layout(sizes)
+chunks = B.cut(data, offs, sizes)
 for level in (3, 1):
     cd = CompressionDict(bc, dic, level)
-    arena, do, dsz = bc.compress_host(data, offs, sizes, cdict=cd)
-    assert (dsz < ERR).all()
-    ua, uo, us = bc.compress_host(data, offs, sizes, level, dic)
+    frames = B.frames_of(bc.compress_host(data, offs, sizes, cdict=cd))
+    using_dict = B.cut(*bc.compress_host(data, offs, sizes, level, dic))
     used = 0
-    for i in range(len(sizes)):
-        f = arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes()
-        c = data[int(offs[i]):int(offs[i]) + int(sizes[i])].tobytes()
+    for i, (f, c) in enumerate(zip(frames, chunks)):
         assert O.decompress_using_dict(f, len(c), dic) == c, (level, i)
         blocks = K.blocks_of(f)
         assert not any(K.uses_dictionary_tables(b) for b in blocks[1:]), (level, i)
         if K.uses_dictionary_tables(blocks[0]):
             used += 1
         else:
-            assert f == ua[int(uo[i]):int(uo[i]) + int(us[i])].tobytes(), (level, i)
+            assert f == using_dict[i], (level, i)
     assert used > 0
     cd.close()
 print("CHILD-OK")
@@ -377,5 +323,4 @@ print("CHILD-OK")
 def test_sub_batches_with_a_cdict():
     """ZSMI_BLOCKS_IN_FLIGHT=64 in a child process: a mixed batch is cut in many sub-batches"""
     env = dict(os.environ, ZSMI_BLOCKS_IN_FLIGHT="64")
-    r = subprocess.run([sys.executable, "-c", _SUB_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CHILD-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    B.run_child("-c", _SUB_CHILD, B.ROOT, env=env)

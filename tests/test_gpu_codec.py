@@ -4,17 +4,15 @@
            (b) be byte-identical to oracle E (the scalar statement of the same algorithm),
            (c) decode under upstream libzstd when present, (d) keep the stated ratio tolerance.
 Run with -m gpu on an MI355X."""
-import ctypes, os, sys
+import json, os, sys
 import numpy as np
 import pytest
 import _oracle as O
 import _data as D
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _batch as B
+from _batch import ERR, ROOT
 
 pytestmark = pytest.mark.gpu
-
-ERR = 0xFFFFFF88
 
 
 @pytest.fixture(scope="module")
@@ -23,30 +21,6 @@ def codec():
     bc = BatchCodec()
     yield bc
     bc.close()
-
-
-def _u8(b):
-    return np.frombuffer(b, dtype=np.uint8) if len(b) else np.zeros(1, dtype=np.uint8)
-
-
-def _compress_many(codec, chunks, level=3):
-    src = np.concatenate([_u8(c)[:len(c)] for c in chunks] + [np.zeros(1, np.uint8)])
-    sizes = np.array([len(c) for c in chunks], dtype=np.uint32)
-    offs = np.zeros(len(chunks), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-    arena, do, dsz = codec.compress_host(src, offs, sizes, level)
-    out = []
-    for i in range(len(chunks)):
-        assert dsz[i] < ERR, (i, hex(int(dsz[i])))
-        out.append(arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes())
-    return out
-
-
-def _decompress_many(codec, frames, caps):
-    src = np.concatenate([_u8(f)[:len(f)] for f in frames] + [np.zeros(1, np.uint8)])
-    sizes = np.array([len(f) for f in frames], dtype=np.uint32)
-    offs = np.zeros(len(frames), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-    arena, do, dsz = codec.decompress_host(src, offs, sizes, np.array(caps, dtype=np.uint32))
-    return [(int(dsz[i]), arena[int(do[i]):int(do[i]) + (int(dsz[i]) if dsz[i] < ERR else 0)].tobytes()) for i in range(len(frames))]
 
 
 # ------------------------------------------------------------------ decode
@@ -69,7 +43,7 @@ def test_decode_reference_golden_vectors(codec):
 def test_decode_libzstd_fixtures(codec):
     fx = D.fixtures()
     names = sorted(fx)
-    res = _decompress_many(codec, [fx[k][0] for k in names], [max(len(fx[k][1]), 1) for k in names])
+    res = B.decode_many(codec, [fx[k][0] for k in names], [max(len(fx[k][1]), 1) for k in names])
     for k, (sz, got) in zip(names, res):
         assert sz == len(fx[k][1]), (k, hex(sz))
         assert got == fx[k][1], k
@@ -88,7 +62,7 @@ def test_decode_errors_match_oracle(codec):
     for pos in (20, 100, 200, 300, 470):
         b = bytearray(cs); b[pos] ^= 0x55
         cases.append((bytes(b), 3409, None))
-    res = _decompress_many(codec, [c[0] for c in cases], [max(c[1], 1) for c in cases])
+    res = B.decode_many(codec, [c[0] for c in cases], [max(c[1], 1) for c in cases])
     for (fr, cap, code), (sz, _) in zip(cases, res):
         assert sz > ERR, "must be an error"
         try:
@@ -113,7 +87,7 @@ def test_decode_damaged_own_frames_match_oracle(codec):
         for _ in range(40):
             b = bytearray(f); pos = int(rng.integers(0, len(f))); b[pos] ^= int(rng.integers(1, 256))
             frames.append(bytes(b)); caps.append(len(c))
-    res = _decompress_many(codec, frames, caps)
+    res = B.decode_many(codec, frames, caps)
     nerr = 0
     for fr, cap, (sz, got) in zip(frames, caps, res):
         try:
@@ -134,7 +108,7 @@ def test_decode_damaged_own_frames_match_oracle(codec):
 def test_decode_truncations(codec):
     frame, want = D.fixtures()["small_text_l3"]
     frames = [frame[:c] for c in range(1, len(frame))]
-    res = _decompress_many(codec, frames, [len(want)] * len(frames))
+    res = B.decode_many(codec, frames, [len(want)] * len(frames))
     for c, (sz, _) in enumerate(res, start=1):
         assert sz > ERR, c
 
@@ -146,7 +120,7 @@ INPUTS = D.mixed_inputs()
 @pytest.mark.parametrize("level", [1, 3])
 def test_encode_roundtrip_and_bit_exact_vs_oracle(codec, level):
     names = sorted(INPUTS)
-    frames = _compress_many(codec, [INPUTS[k] for k in names], level)
+    frames = B.compress_many(codec, [INPUTS[k] for k in names], level)
     for k, f in zip(names, frames):
         data = INPUTS[k]
         assert O.lib().zso_getDecompressedSize(f, len(f)) == len(data), k
@@ -155,7 +129,7 @@ def test_encode_roundtrip_and_bit_exact_vs_oracle(codec, level):
         if O.libzstd():
             assert O.zstd_decompress(f, len(data)) == data, k
     # and through this codec's own decoder
-    res = _decompress_many(codec, frames, [max(len(INPUTS[k]), 1) for k in names])
+    res = B.decode_many(codec, frames, [max(len(INPUTS[k]), 1) for k in names])
     for k, (sz, got) in zip(names, res):
         assert sz == len(INPUTS[k]) and got == INPUTS[k], k
 
@@ -186,7 +160,7 @@ def test_encode_batch_64k_chunks_log(codec):
         assert (arena[int(do[i]):int(do[i]) + int(dsz[i])] == ea[int(eo[i]):int(eo[i]) + int(es[i])]).all(), i
     # decode all with this codec and compare with the input
     frames = np.concatenate([arena[int(do[i]):int(do[i]) + int(dsz[i])] for i in range(n)])
-    fo = np.zeros(n, dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
+    fo = B.layout(dsz)
     out, oo, osz = codec.decompress_host(frames, fo, dsz, sizes)
     assert (osz == cs).all()
     assert (out[:n * cs] == data[:n * cs]).all()
@@ -216,7 +190,7 @@ def test_encode_batch_128k_chunks_log(codec, level):
         out, st = O.decode_stats(f, cs)
         assert out == data[i * cs:(i + 1) * cs].tobytes()
     frames = np.concatenate([arena[int(do[i]):int(do[i]) + int(dsz[i])] for i in range(n)])
-    fo = np.zeros(n, dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
+    fo = B.layout(dsz)
     out, oo, osz = codec.decompress_host(frames, fo, dsz, sizes)
     assert (osz == cs).all() and (out[:n * cs] == data[:n * cs]).all()
     if O.libzstd():
@@ -229,12 +203,10 @@ def test_encode_128k_chunks_and_ragged(codec):
     data = D.zipf_log(3 << 20, seed_lo=77)
     rng = np.random.default_rng(5)
     sizes = np.concatenate([np.full(8, 131072), rng.integers(0, 200000, 12)]).astype(np.uint32)
-    offs = np.zeros(len(sizes), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
+    offs = B.layout(sizes)
     assert int(offs[-1]) + int(sizes[-1]) <= len(data)
     arena, do, dsz = codec.compress_host(data, offs, sizes, 3)
-    for i in range(len(sizes)):
-        f = arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes()
-        c = data[int(offs[i]):int(offs[i]) + int(sizes[i])].tobytes()
+    for f, c in zip(B.cut(arena, do, dsz), B.cut(data, offs, sizes)):
         assert O.decompress(f, len(c)) == c
         assert f == O.compress(c, 3)
 
@@ -244,7 +216,7 @@ def test_many_tiny_and_odd_chunks(codec):
     data = D.zipf_log(6 << 20, seed_lo=99)
     rng = np.random.default_rng(11)
     sizes = np.concatenate([rng.integers(0, 3000, 3000), [255, 256, 257, 65535, 65536, 65537, 65791, 65792, 131071, 131072, 131073, 262144, 0, 1, 15, 16, 17]]).astype(np.uint32)
-    offs = np.zeros(len(sizes), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
+    offs = B.layout(sizes)
     assert int(offs[-1]) + int(sizes[-1]) <= len(data)
     arena, do, dsz = codec.compress_host(data, offs, sizes, 3)
     assert (dsz < ERR).all()
@@ -253,7 +225,7 @@ def test_many_tiny_and_odd_chunks(codec):
     bad = [i for i in range(len(sizes)) if not (arena[int(do[i]):int(do[i]) + int(dsz[i])] == ea[int(eo[i]):int(eo[i]) + int(es[i])]).all()]
     assert not bad, bad[:5]
     frames = np.concatenate([arena[int(do[i]):int(do[i]) + int(dsz[i])] for i in range(len(sizes))])
-    fo = np.zeros(len(sizes), dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
+    fo = B.layout(dsz)
     out, oo, osz = codec.decompress_host(frames, fo, dsz, np.maximum(sizes, 1))
     assert (osz == sizes).all()
     for i in range(len(sizes)):
@@ -281,9 +253,7 @@ def test_pack_frames_device():
     """zsmi_packFramesDevice: frames left at their worst-case offsets by the batch compressor end up back to back, in order
     (ragged sizes, so that every copy alignment occurs).  Device buffers come from torch, which has to be loaded before
     libzsmi.so in its process: the check runs as a script of its own (tools/pack_check.py)."""
-    import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pack_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    B.run_child(os.path.join(ROOT, "tools", "pack_check.py"), timeout=300, marker=None)
 
 
 def test_checksummed_one_block_frames(codec):
@@ -298,7 +268,7 @@ def test_checksummed_one_block_frames(codec):
     frames = [zstd_compress_checked(c, 3 + (i % 5)) for i, c in enumerate(chunks)]
     assert all((f[4] >> 2) & 1 for f in frames)                                     # the checksum flag is set
     bad_sum = [bytes(f[:-1]) + bytes([f[-1] ^ 0x40]) for f in frames[:4]]            # stored checksum damaged
-    res = _decompress_many(codec, frames + bad_sum, [len(c) for c in chunks] + [len(c) for c in chunks[:4]])
+    res = B.decode_many(codec, frames + bad_sum, [len(c) for c in chunks] + [len(c) for c in chunks[:4]])
     for (sz, got), c in zip(res[:len(frames)], chunks):
         assert sz == len(c) and got == c
     for (sz, _), f, c in zip(res[len(frames):], bad_sum, chunks):
@@ -317,13 +287,11 @@ def test_mixed_corpus_matches_oracle_and_ratio(codec, cs, level):
     worst = {}
     for name, data in C.corpus(1 << 20).items():
         chunks = [data[i:i + cs] for i in range(0, len(data), cs)]
-        frames = _compress_many(codec, chunks, level)
-        ea, eo, es = O.compress_batch(np.frombuffer(data, dtype=np.uint8), np.arange(0, len(data), cs, dtype=np.uint64),
-                                      np.array([len(c) for c in chunks], dtype=np.uint32), level, 8)
-        for i, (f, c) in enumerate(zip(frames, chunks)):
-            assert f == ea[int(eo[i]):int(eo[i]) + int(es[i])].tobytes(), (name, i)
+        frames = B.compress_many(codec, chunks, level)
+        for i, (f, e) in enumerate(zip(frames, B.oracle_frames(chunks, level))):
+            assert f == e, (name, i)
         assert O.decompress(frames[0], len(chunks[0])) == chunks[0] and O.decompress(frames[-1], len(chunks[-1])) == chunks[-1]
-        got = _decompress_many(codec, frames, [len(c) for c in chunks])
+        got = B.decode_many(codec, frames, [len(c) for c in chunks])
         assert all(g == (len(c), c) for g, c in zip(got, chunks)), name
         if O.libzstd():
             worst[name] = round(sum(len(f) for f in frames) / sum(len(O.zstd_compress(c, level)) for c in chunks), 4)
@@ -343,43 +311,42 @@ def test_one_mib_of_zeros_level3(codec):
     if O.libzstd():
         assert O.zstd_decompress(f, len(data)) == data
     chunks = [data[i:i + 65536] for i in range(0, len(data), 65536)]
-    frames = _compress_many(codec, chunks, 3)
+    frames = B.compress_many(codec, chunks, 3)
     assert all(fr == O.compress(c, 3) for fr, c in zip(frames, chunks)) and len(frames[0]) == 11
-    assert all(g == (65536, c) for g, c in zip(_decompress_many(codec, frames, [65536] * 16), chunks))
+    assert all(g == (65536, c) for g, c in zip(B.decode_many(codec, frames, [65536] * 16), chunks))
 
 
 _CHILD = r'''
 import sys, os, numpy as np
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
-import _oracle as O, _data as D
+import _oracle as O, _data as D, _batch as B
 from zstandard_amd import BatchCodec
-ERR = 0xFFFFFF88
 bc = BatchCodec()
 data = D.zipf_log(24 << 20, seed_lo=4242)
 rng = np.random.default_rng(21)
 # 150 chunks of 0 .. 3 blocks: the compress sub-batch loop (> 64 blocks in flight) turns over several times and meets chunks of
 # every block count at the boundaries; 150 frames, then 700 small frames: the decode launch loop (> 64 items in flight)
 sizes = np.concatenate([rng.integers(0, 190000, 150), [65536] * 70, [131072] * 10]).astype(np.uint32)
-offs = np.zeros(len(sizes), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
+offs = B.layout(sizes)
 assert int(offs[-1]) + int(sizes[-1]) <= len(data)
 for level in (3, 1):
     arena, do, dsz = bc.compress_host(data, offs, sizes, level)
-    assert (dsz < ERR).all()
+    assert (dsz < B.ERR).all()
     ea, eo, es = O.compress_batch(data, offs, sizes, level, 8)
     assert (dsz == es).all(), np.nonzero(dsz != es)[0][:5]
     for i in range(len(sizes)):
         assert (arena[int(do[i]):int(do[i]) + int(dsz[i])] == ea[int(eo[i]):int(eo[i]) + int(es[i])]).all(), i
 frames = np.concatenate([arena[int(do[i]):int(do[i]) + int(dsz[i])] for i in range(len(sizes))])
-fo = np.zeros(len(sizes), dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
+fo = B.layout(dsz)
 out, oo, osz = bc.decompress_host(frames, fo, dsz, np.maximum(sizes, 1))
 assert (osz == sizes).all()
 for i in range(len(sizes)):
     assert (out[int(oo[i]):int(oo[i]) + int(sizes[i])] == data[int(offs[i]):int(offs[i]) + int(sizes[i])]).all(), i
 small = rng.integers(1, 5000, 700).astype(np.uint32)
-so = np.zeros(len(small), dtype=np.uint64); so[1:] = np.cumsum(small.astype(np.uint64))[:-1]
+so = B.layout(small)
 a2, d2, s2 = bc.compress_host(data, so, small, 3)
 fr = np.concatenate([a2[int(d2[i]):int(d2[i]) + int(s2[i])] for i in range(len(small))])
-f2 = np.zeros(len(small), dtype=np.uint64); f2[1:] = np.cumsum(s2.astype(np.uint64))[:-1]
+f2 = B.layout(s2)
 # every 7th frame damaged: its status must be the oracle's error code, its neighbours untouched
 frd = fr.copy()
 for i in range(0, len(small), 7):
@@ -400,10 +367,7 @@ print("CHILD-OK")
 def test_in_flight_limits_cross_both_ways():
     """ZSMI_BLOCKS_IN_FLIGHT=64 / ZSMI_ITEMS_IN_FLIGHT=64 in a child process: the compress sub-batch loop and the decode
     launch loop (zsmi_api.hip) run many turns on a small batch; every item compared with the oracle"""
-    import subprocess
-    env = dict(os.environ, ZSMI_BLOCKS_IN_FLIGHT="64", ZSMI_ITEMS_IN_FLIGHT="64")
-    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CHILD-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    B.run_child("-c", _CHILD, ROOT, env=dict(os.environ, ZSMI_BLOCKS_IN_FLIGHT="64", ZSMI_ITEMS_IN_FLIGHT="64"))
 
 
 def test_decode_two_block_frames_fast_path_and_its_fallbacks(codec):
@@ -421,7 +385,7 @@ def test_decode_two_block_frames_fast_path_and_its_fallbacks(codec):
     frames = [O.compress(c, 3) for c in chunks]
     bad = bytearray(frames[0]); bad[len(bad) - 200] ^= 0x41                              # inside the second block of a two-block frame
     frames.append(bytes(bad)); chunks.append(chunks[0])
-    res = _decompress_many(codec, frames, [len(c) for c in chunks])
+    res = B.decode_many(codec, frames, [len(c) for c in chunks])
     for i, (f, c, (sz, got)) in enumerate(zip(frames, chunks, res)):
         try:
             want = O.decompress(f, len(c))
@@ -432,7 +396,7 @@ def test_decode_two_block_frames_fast_path_and_its_fallbacks(codec):
     # libzstd's own two-block frames (tables may repeat in the second block: the general kernel takes those)
     if O.libzstd():
         zf = [O.zstd_compress(c, 3) for c in chunks[:4]]
-        for (sz, got), c in zip(_decompress_many(codec, zf, [len(c) for c in chunks[:4]]), chunks[:4]):
+        for (sz, got), c in zip(B.decode_many(codec, zf, [len(c) for c in chunks[:4]]), chunks[:4]):
             assert sz == len(c) and got == c
 
 
@@ -440,15 +404,15 @@ def test_kernel_timing_modes(codec):
     """zsmi_enableKernelTiming: 1 = events around every launch, 2 = only around the dominant kernel of each direction
     (what bench.py's timed region carries), 0 = none; the data path is the same in all three"""
     chunks = [D.zipf_log(65536, seed_lo=900 + i).tobytes() for i in range(40)] + [D.zipf_log(131072, seed_lo=990).tobytes()]
-    ref = _compress_many(codec, chunks)
+    ref = B.compress_many(codec, chunks)
     try:
         codec.enable_timing(2)
-        fr = _compress_many(codec, chunks)
+        fr = B.compress_many(codec, chunks)
         t2c = codec.kernel_times()
-        back = _decompress_many(codec, fr, [len(c) for c in chunks])
+        back = B.decode_many(codec, fr, [len(c) for c in chunks])
         t2d = codec.kernel_times()
         codec.enable_timing(True)
-        fr1 = _compress_many(codec, chunks)
+        fr1 = B.compress_many(codec, chunks)
         t1c = codec.kernel_times()
     finally:
         codec.enable_timing(False)
@@ -479,7 +443,7 @@ def test_decode_literal_spread_across_windows(codec):
     frames = [O.zstd_compress(c, 3) for c in chunks]
     try:
         codec.enable_timing(True)
-        res = _decompress_many(codec, frames, [len(c) for c in chunks])
+        res = B.decode_many(codec, frames, [len(c) for c in chunks])
         kt = codec.kernel_times()
     finally:
         codec.enable_timing(False)
@@ -512,7 +476,7 @@ def test_long_matches_are_joined_as_in_the_oracle(codec, level):
     sequence count small (a 64 KiB block of period-1000 data is a handful of sequences, not one per walk range)"""
     inputs = _long_match_inputs()
     names = sorted(inputs)
-    frames = _compress_many(codec, [inputs[k] for k in names], level)
+    frames = B.compress_many(codec, [inputs[k] for k in names], level)
     for k, f in zip(names, frames):
         data = inputs[k]
         assert f == O.compress(data, level), k
@@ -531,7 +495,7 @@ def test_units_of_one_repeated_byte_skip_the_parse(codec, level):
               b"\x00" * 65536 + b"\x01" + b"\x00" * 65535, text, b"k" * 200000, b"k" * 196608]
     for _ in range(8):                                                            # one differing byte at a random place
         c = bytearray(b"\x07" * 65536); c[int(rng.integers(0, 65536))] = 8; chunks.append(bytes(c))
-    frames = _compress_many(codec, chunks, level)
+    frames = B.compress_many(codec, chunks, level)
     for i, (c, f) in enumerate(zip(chunks, frames)):
         assert f == O.compress(c, level), i
         assert O.decompress(f, len(c)) == c, i
@@ -573,7 +537,7 @@ def test_matchless_units_skip_the_parse(codec, level):
     leaves the unit): the frames are oracle E's on both sides of the threshold and decode; pure noise becomes raw blocks"""
     inputs = _matchless_inputs()
     names = sorted(inputs)
-    frames = _compress_many(codec, [inputs[k] for k in names], level)
+    frames = B.compress_many(codec, [inputs[k] for k in names], level)
     for k, f in zip(names, frames):
         assert f == O.compress(inputs[k], level), k
         assert O.decompress(f, len(inputs[k])) == inputs[k], k
@@ -611,7 +575,7 @@ def test_runs_of_one_byte_are_parsed_as_in_the_oracle(codec, level):
     64 lanes on one address) and gives them the distance 1 the sequential loop of oracle E's findCandidates finds: the frames are oracle E's"""
     inputs = _byte_run_inputs()
     names = sorted(inputs)
-    frames = _compress_many(codec, [inputs[k] for k in names], level)
+    frames = B.compress_many(codec, [inputs[k] for k in names], level)
     for k, f in zip(names, frames):
         assert f == O.compress(inputs[k], level), k
         assert O.decompress(f, len(inputs[k])) == inputs[k], k
@@ -627,8 +591,8 @@ def test_decode_calls_on_both_sides_of_the_launch_shape_rules(codec):
         sizes = rng.integers(600, 1500, n)
         starts = rng.integers(0, len(log) - 1500, n)
         chunks = [log[int(a):int(a) + int(z)] for a, z in zip(starts, sizes)]
-        frames = _compress_many(codec, chunks, 3)
-        got = _decompress_many(codec, frames, [len(c) for c in chunks])
+        frames = B.compress_many(codec, chunks, 3)
+        got = B.decode_many(codec, frames, [len(c) for c in chunks])
         bad = [i for i, ((sz, data), c) in enumerate(zip(got, chunks)) if sz != len(c) or data != c]
         assert not bad, (n, bad[:5])
 
@@ -645,11 +609,11 @@ def test_decode_wide_alphabets_flat_huffman_table(codec):
         perm = r.permutation(256).astype(np.uint8)
         return perm[r.choice(256, size=n, p=p)].tobytes()
     chunks = [skewed(65536, 0.975, 1), skewed(131072, 0.98, 2), skewed(40000, 0.96, 3), skewed(3000, 0.985, 4), skewed(65536, 0.99, 5), skewed(20000, 0.97, 6)]
-    frames = _compress_many(codec, chunks, 3)
+    frames = B.compress_many(codec, chunks, 3)
     if O.libzstd():
         frames += [O.zstd_compress(c, 3) for c in chunks]
         chunks = chunks + chunks
-    got = _decompress_many(codec, frames, [len(c) for c in chunks])
+    got = B.decode_many(codec, frames, [len(c) for c in chunks])
     for i, (g, c, f) in enumerate(zip(got, chunks, frames)):
         assert g == (len(c), c), i
         assert O.decompress(f, len(c)) == c, i
@@ -664,15 +628,15 @@ def test_decode_large_frames_of_many_blocks(codec):
     noise = rng.integers(0, 256, 70000, dtype=np.uint8).tobytes()
     chunks = [text[:150000], text[100000:100000 + 262144], text[:1 << 20], text[5000:5000 + 1000000], text[:(1 << 20) + 1],
               text[:200000] + noise + text[200000:400000], text[:65536 * 3] + bytes(65536) + text[:70000], text[:40000], text[:65536 * 5 + 17]]
-    frames = _compress_many(codec, chunks, 3)
-    got = _decompress_many(codec, frames, [len(c) for c in chunks])
+    frames = B.compress_many(codec, chunks, 3)
+    got = B.decode_many(codec, frames, [len(c) for c in chunks])
     for i, (g, c, f) in enumerate(zip(got, chunks, frames)):
         assert g == (len(c), c), i
     assert O.decompress(frames[2], len(chunks[2])) == chunks[2] and O.decompress(frames[6], len(chunks[6])) == chunks[6]
     # the same frames one by one and among many small ones (the call then keeps its one or two slots: the general kernel takes the large frames)
     small = [text[i * 30000:(i + 1) * 30000] for i in range(40)]
-    frames2 = _compress_many(codec, small + chunks[:3], 3)
-    got2 = _decompress_many(codec, frames2, [len(c) for c in small + chunks[:3]])
+    frames2 = B.compress_many(codec, small + chunks[:3], 3)
+    got2 = B.decode_many(codec, frames2, [len(c) for c in small + chunks[:3]])
     assert all(g == (len(c), c) for g, c in zip(got2, small + chunks[:3]))
 
 
@@ -692,7 +656,7 @@ def test_decode_libzstd_frames_of_many_blocks_with_repeated_tables(codec):
                                         (binary, 400000, 3), (binary, 600000, 1), (text[:200000] + binary[:200000] + text[:150000], 550000, 3), (text, 131073, 3)]):
         a = int(rng.integers(0, len(data) - n + 1)); c = data[a:a + n]
         chunks.append(c); frames.append(O.zstd_compress(c, lvl))
-    got = _decompress_many(codec, frames, [len(c) for c in chunks])
+    got = B.decode_many(codec, frames, [len(c) for c in chunks])
     for i, (g, c, f) in enumerate(zip(got, chunks, frames)):
         assert g == (len(c), c), i
     assert O.decompress(frames[1], len(chunks[1])) == chunks[1] and O.decompress(frames[6], len(chunks[6])) == chunks[6]
@@ -701,11 +665,9 @@ def test_decode_libzstd_frames_of_many_blocks_with_repeated_tables(codec):
 def test_intended_shapes_stay_on_the_decode_fast_path():
     """tools/fastpath_check.py (its own process: the library with the debug hooks): every shape the fast path is meant to take is decoded
     THERE - a silent fall-back to the general kernel decodes correctly, 4 x slower, and no other test would notice."""
-    import json, subprocess
     # (the tool builds the debug-hook library itself when it is missing or stale: on a GPU run this test never skips)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fastpath_check.py")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    out = B.run_child(os.path.join(ROOT, "tools", "fastpath_check.py"), marker=None)
+    res = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert len(res) >= 5, res
     for label, (fast, n) in res.items():
         assert fast >= 0, (label, "wrong output")
@@ -721,9 +683,9 @@ def test_decode_scratch_follows_the_capacities_and_is_given_back():
     try:
         text = D.zipf_log(2048 * 32768, seed_lo=5).tobytes()
         chunks = [text[i * 32768:(i + 1) * 32768] for i in range(2048)]
-        frames = _compress_many(bc, chunks, 3)
+        frames = B.compress_many(bc, chunks, 3)
         def scratch_after(caps):
-            out = _decompress_many(bc, frames, caps)
+            out = B.decode_many(bc, frames, caps)
             assert all(sz == 32768 and data == c for (sz, data), c in zip(out, chunks))
             return int(bc.L.zsmi_decodeScratchBytes(bc.ctx))
         small = scratch_after([32768] * 2048)

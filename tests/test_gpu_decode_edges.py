@@ -1,16 +1,16 @@
 """The HIP decoder on the hand-built edge catalogue (tests/_edge_catalogue.py), in several placements.  In each, every item's status must
 equal oracle D's at the same capacity: the same bytes, or the same error code ((1 << 32) - code).  Plus output bounds on the device
 API: no byte outside an item's [dstOffset, dstOffset + dstCap) changes, for decode, and outside [dstOffset, + compressBound) for encode."""
-import json, os, subprocess, sys
-import numpy as np
+import json, os
 import pytest
 import _oracle as O
 import _edge_catalogue as C
 import _framewriter as W
 import _data as D
+import _batch as B
+from _batch import ROOT
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIB = 1 << 20
 
 
@@ -32,17 +32,7 @@ def bc():
 
 def _batch(bc, items):
     """items: [(frame, cap)] -> [bytes or status word] from one decompress_host call"""
-    blob = b"".join(f for f, _ in items)
-    fsz = np.array([len(f) for f, _ in items], dtype=np.uint32)
-    fo = np.zeros(len(items), dtype=np.uint64)
-    fo[1:] = np.cumsum(fsz.astype(np.uint64))[:-1]
-    caps = np.array([c for _, c in items], dtype=np.uint32)
-    out, oo, osz = bc.decompress_host(np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, np.uint8), fo, fsz, caps)
-    res = []
-    for i in range(len(items)):
-        s = int(osz[i])
-        res.append(s if s > 0xFFFFFF88 else out[int(oo[i]):int(oo[i]) + s].tobytes())
-    return res
+    return [sz if sz > B.ERR else got for sz, got in B.decode_many(bc, [f for f, _ in items], [c for _, c in items], min_cap=0)]
 
 
 def _check(names, items, got):
@@ -140,9 +130,7 @@ def test_edges_one_shot_apis_keep_outside_bytes():
 def test_device_api_stays_inside_each_item(capsys):
     """decompress_device / compress_device on torch buffers filled with a canary, items with gaps and tightly packed: no byte outside
     an item's region changes (tools/bounds_edges.py, a process of its own: torch has to be loaded before libzsmi.so)"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bounds_edges.py")], capture_output=True, text=True, cwd=ROOT, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    rep = json.loads(r.stdout.strip().splitlines()[-1])
+    rep = json.loads(B.run_child(os.path.join(ROOT, "tools", "bounds_edges.py"), cwd=ROOT, marker=None).strip().splitlines()[-1])
     assert rep["decode_items"] >= 7 * 200 and rep["compress_items"] >= 24
     with capsys.disabled():
         print(f"\n[device bounds] decoded items whose bytes between the produced size and dstCap were touched: {rep['tail_touched']}, "
@@ -168,10 +156,7 @@ FAST_EXPECTED = {
 def test_edge_shapes_stay_on_the_fast_path():
     """a child process with the debug library (tools/fastpath_edges.py) reads back each item's fast-path descriptor"""
     env = dict(os.environ, ZSMI_DEBUG_LIB="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fastpath_edges.py")], capture_output=True, text=True, env=env,
-                       cwd=ROOT, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = json.loads(B.run_child(os.path.join(ROOT, "tools", "fastpath_edges.py"), env=env, cwd=ROOT, marker=None).strip().splitlines()[-1])
     for placement, names in FAST_EXPECTED.items():
         slow = [n for n in names if res[placement].get(n) != 1]
         assert not slow, (placement, slow)

@@ -4,21 +4,17 @@ for byte: at levels 1 - 4 and above, for raw, tiny, trained, re-offset and re-nu
 and contents aimed at the prefix rules, across plan reuse, through device pointers and in sub-batches.  The frames must also decode to
 their input with the same dictionary under oracle D, under the library's own decoder and under upstream libzstd; the dictionary must
 really be used (ratio, dictID, recent offsets); corrupted dictionaries are refused as oracle D refuses them; no dictionary gives exactly
-the frames of the calls without one.  Dictionaries and chunks: tests/_dicts.py."""
-import ctypes, os, subprocess, sys
+the frames of the calls without one.  Dictionaries and chunks: tests/_dicts.py; batches and round trips: tests/_batch.py."""
+import ctypes, os
 import numpy as np
 import pytest
 import _oracle as O
 import _data as D
 import _corpus as C
 import _dicts as X
+import _batch as B
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR = 0xFFFFFF88
-FIX, FIXC, TRAINED8K, RECORD_CLASSES = X.FIX, X.FIXC, X.TRAINED8K, X.RECORD_CLASSES
-trained, content_of, class_data, with_reps, bad_dictionaries = X.trained, X.content_of, X.class_data, X.with_reps, X.bad_dictionaries
-_zstd, zstd_compress_dict, zstd_decompress_dict = X.zstd, X.zstd_compress_dict, X.zstd_decompress_dict
 
 
 @pytest.fixture(scope="module")
@@ -27,38 +23,10 @@ def codec():
     return BatchCodec(0)
 
 
-def compress_many(codec, chunks, level, dic=b""):
-    sizes = np.array([len(c) for c in chunks], dtype=np.uint32)
-    offs = np.zeros(len(chunks), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-    src = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
-    arena, do, dsz = codec.compress_host(src, offs, sizes, level, dic)
-    assert (dsz <= ERR).all()
-    return [arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes() for i in range(len(chunks))]
-
-
-def decode_many(codec, frames, caps, dic):
-    sizes = np.array([len(f) for f in frames], dtype=np.uint32)
-    offs = np.zeros(len(frames), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-    out, oo, osz = codec.decompress_host(np.frombuffer(b"".join(frames), dtype=np.uint8), offs, sizes, np.maximum(np.array(caps, dtype=np.uint32), 1), dic)
-    return [(int(osz[i]), out[int(oo[i]):int(oo[i]) + (int(osz[i]) if osz[i] <= ERR else 0)].tobytes()) for i in range(len(frames))]
-
-
-def assert_round_trip(codec, frames, chunks, dic):
-    bound = codec.L.zsmi_compressBound
-    for i, (f, c) in enumerate(zip(frames, chunks)):
-        assert len(f) <= bound(len(c)), i
-        assert O.decompress_using_dict(f, len(c), dic) == c, ("oracle D", i, len(c))
-    for i, ((sz, got), c) in enumerate(zip(decode_many(codec, frames, [len(c) for c in chunks], dic), chunks)):
-        assert sz == len(c) and got == c, ("zsmi_decompressBatchHost_usingDict", i, len(c), hex(sz))
-    if _zstd():
-        for i, (f, c) in enumerate(zip(frames, chunks)):
-            assert zstd_decompress_dict(f, len(c), dic) == c, ("libzstd", i, len(c))
-
-
 def dictionaries():
     raw = D.zipf_log(200000, seed_lo=0x515).tobytes()
     jraw = C.json_records(120000, seed=303)
-    return {"trained8k": TRAINED8K, "trained64k_json": trained("json_records"), "raw6000": raw[:6000], "raw65536": jraw[:65536],
+    return {"trained8k": X.TRAINED8K, "trained64k_json": X.trained("json_records"), "raw6000": raw[:6000], "raw65536": jraw[:65536],
             "raw100k": jraw[:100000], "raw5": raw[:5]}
 
 
@@ -70,23 +38,23 @@ def test_round_trip(codec, level):
     for name, dic in dictionaries().items():
         chunks = []
         for k, cls in enumerate(classes):
-            data = class_data(cls)
+            data = X.class_data(cls)
             for j, cs in enumerate((300, 1024, 4096, 16384, 65536)):
                 o = (k * 7919 + j * 40009) % (len(data) - cs)
                 chunks.append(data[o:o + cs])
-        big = class_data("json_records")
-        chunks += [big[1000:1000 + 65537], class_data("zipf")[5000:5000 + 200 * 1024], b"", b"x"]
-        frames = compress_many(codec, chunks, level, dic)
-        assert_round_trip(codec, frames, chunks, dic)
+        big = X.class_data("json_records")
+        chunks += [big[1000:1000 + 65537], X.class_data("zipf")[5000:5000 + 200 * 1024], b"", b"x"]
+        frames = B.compress_many(codec, chunks, level, dic)
+        B.assert_round_trip(codec, frames, chunks, dic)
 
 
 # ------------------------------------------------------------------ byte for byte: oracle E
 def assert_matches_oracle(codec, chunks, level, dic, what):
     """the HIP frames of one batch call (BatchCodec.compress_host) against oracle E's batch form, frame by frame"""
-    frames = compress_many(codec, chunks, level, dic)
-    expect = X.oracle_frames(chunks, level, dic)
+    frames = B.compress_many(codec, chunks, level, dic)
+    expect = B.oracle_frames(chunks, level, dic)
     for i, (f, e) in enumerate(zip(frames, expect)):
-        assert f == e, (what, level, i, len(chunks[i]), len(f), len(e), X.first_difference(f, e))
+        assert f == e, (what, level, i, len(chunks[i]), len(f), len(e), B.first_difference(f, e))
     return frames
 
 
@@ -122,27 +90,24 @@ def test_plan_reuse_matches_oracle(codec):
             if dic:
                 assert_matches_oracle(codec, chunks, level, dic, name)
             else:
-                frames = compress_many(codec, chunks, level)
-                src, offs, sizes = X.batch(chunks)
-                ea, eo, es = O.compress_batch(src, offs, sizes, level, 8)
-                assert frames == [ea[int(eo[i]):int(eo[i]) + int(es[i])].tobytes() for i in range(len(chunks))], (name, level)
+                assert B.compress_many(codec, chunks, level) == B.oracle_frames(chunks, level), (name, level)
 
 
 # ------------------------------------------------------------------ the dictionary is used
 def test_trained_dictionary_shrinks_small_chunks(codec):
     for cls in ("json_records", "xml_records", "zipf"):
-        data, dic = class_data(cls), trained(cls)
+        data, dic = X.class_data(cls), X.trained(cls)
         for cs in (1024, 4096):
             chunks = [data[i:i + cs] for i in range(0, 256 * 1024, cs)]
-            with_d = sum(len(f) for f in compress_many(codec, chunks, 3, dic))
-            without = sum(len(f) for f in compress_many(codec, chunks, 3))
+            with_d = sum(len(f) for f in B.compress_many(codec, chunks, 3, dic))
+            without = sum(len(f) for f in B.compress_many(codec, chunks, 3))
             assert with_d <= 0.9 * without, (cls, cs, with_d / without)
 
 
 def test_frames_need_their_dictionary(codec):
-    data, dic = class_data("json_records"), trained("json_records")
+    data, dic = X.class_data("json_records"), X.trained("json_records")
     chunks = [data[i:i + 4096] for i in range(0, 64 * 4096, 4096)]
-    frames = compress_many(codec, chunks, 3, dic)
+    frames = B.compress_many(codec, chunks, 3, dic)
     dict_id = int.from_bytes(dic[4:8], "little")
     for f in frames:                                                      # the ID in every header (FHD's dictionary-ID field)
         did = f[4] & 3
@@ -154,12 +119,12 @@ def test_frames_need_their_dictionary(codec):
         except O.OracleError:
             wrong += 1
         with pytest.raises(O.OracleError) as e:                           # another formatted dictionary: dictionary_wrong
-            O.decompress_using_dict(f, len(c), TRAINED8K)
+            O.decompress_using_dict(f, len(c), X.TRAINED8K)
         assert e.value.code == 32
     assert wrong > 0
     # raw content: no ID, but the frames reach into it
     raw = dictionaries()["raw65536"]
-    frames = compress_many(codec, chunks, 3, raw)
+    frames = B.compress_many(codec, chunks, 3, raw)
     assert all(f[4] & 3 == 0 for f in frames)
     bad = 0
     for f, c in zip(frames, chunks):
@@ -173,8 +138,8 @@ def test_frames_need_their_dictionary(codec):
 def test_first_block_starts_from_the_dictionarys_recent_offsets(codec):
     """a dictionary whose recent offsets are not {1, 4, 8}: chunks whose first sequences repeat at offsets 1, 4 and 8 decode right only if
     the encoder's repcodes start from the dictionary's offsets"""
-    base = trained("json_records")
-    assert base[-len(content_of(base)) - 12:-len(content_of(base))] == bytes([1, 0, 0, 0, 4, 0, 0, 0, 8, 0, 0, 0])   # ZDICT's defaults
+    base = X.trained("json_records")
+    assert base[-len(X.content_of(base)) - 12:-len(X.content_of(base))] == bytes([1, 0, 0, 0, 4, 0, 0, 0, 8, 0, 0, 0])   # ZDICT's defaults
     rng = np.random.default_rng(3)
     chunks = []
     for period in (1, 4, 8, 4, 8, 1):
@@ -184,17 +149,17 @@ def test_first_block_starts_from_the_dictionarys_recent_offsets(codec):
             tail = rng.integers(0, 256, 64, dtype=np.uint8).tobytes()
             chunks.append(head + unit * (200 // period) + tail + unit * 4 + tail[:8] + unit * 10)
     for reps in ((4, 8, 1), (8, 1, 4), (2, 3, 5), (1000, 40000, 7)):
-        dic = with_reps(base, reps)
+        dic = X.with_reps(base, reps)
         for level in (1, 3, 4):
-            frames = compress_many(codec, chunks, level, dic)
-            assert_round_trip(codec, frames, chunks, dic)
+            frames = B.compress_many(codec, chunks, level, dic)
+            B.assert_round_trip(codec, frames, chunks, dic)
 
 
 # ------------------------------------------------------------------ errors
 def test_corrupted_dictionaries_are_refused(codec):
     L = codec.L
-    data = class_data("json_records")[:4096]
-    for d in bad_dictionaries():
+    data = X.class_data("json_records")[:4096]
+    for d in X.bad_dictionaries():
         with pytest.raises(O.OracleError) as e:                           # what oracle D says of the same dictionary
             O.decompress_using_dict(O.compress(data, 3), len(data), d)
         assert e.value.code == 30
@@ -202,27 +167,25 @@ def test_corrupted_dictionaries_are_refused(codec):
         r = L.zsmi_compress_usingDict(out, len(out), data, len(data), d, len(d), 3)
         assert L.zsmi_getErrorCode(r) == 30
         with pytest.raises(RuntimeError, match="error 30"):
-            compress_many(codec, [data, data[:100]], 3, d)
+            B.compress_many(codec, [data, data[:100]], 3, d)
 
 
 # ------------------------------------------------------------------ equivalence
 def test_no_dictionary_is_the_plain_call(codec):
     from zstandard_amd import ZstdCompressor
     L = codec.L
-    data = class_data("zipf")
+    data = X.class_data("zipf")
     chunks = [data[0:300], data[1000:66536], data[70000:70000 + 65537], data[200000:200000 + 150000], b""]
     for level in (1, 3, 4):
-        plain = compress_many(codec, chunks, level)
-        so = np.zeros(len(chunks), dtype=np.uint64); ss = np.array([len(c) for c in chunks], dtype=np.uint32)
-        so[1:] = np.cumsum(ss.astype(np.uint64))[:-1]
-        src = np.frombuffer(b"".join(chunks), dtype=np.uint8)
+        plain = B.compress_many(codec, chunks, level)
+        src, so, ss = B.batch(chunks)
         bounds = [L.zsmi_compressBound(len(c)) for c in chunks]
-        do = np.zeros(len(chunks), dtype=np.uint64); do[1:] = np.cumsum(np.array(bounds, dtype=np.uint64))[:-1]
+        do = B.layout(bounds)
         arena = np.zeros(sum(bounds), dtype=np.uint8); dsz = np.zeros(len(chunks), dtype=np.uint32)
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
         for d, dn in ((None, 0), (b"abc", 0), (None, 100)):
             assert L.zsmi_compressBatchHost_usingDict(codec.ctx, p(src), p(so), p(ss), len(chunks), p(arena), p(do), p(dsz), level, d, dn) == 0
-            assert [arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes() for i in range(len(chunks))] == plain
+            assert B.cut(arena, do, dsz) == plain
         for c, f in zip(chunks, plain):
             out = ctypes.create_string_buffer(L.zsmi_compressBound(len(c)))
             r = L.zsmi_compress_usingDict(out, len(out), c, len(c), None, 0, level)
@@ -230,12 +193,12 @@ def test_no_dictionary_is_the_plain_call(codec):
             assert ZstdCompressor(level, dictionary=b"").compress(c) == f
         for c in chunks:                                                  # oracle E: the same holds for the scalar statement
             assert O.compress_using_dict(c, None, level) == O.compress_using_dict(c, b"", level) == O.compress(c, level)
-    dic = trained("json_records")
-    c = class_data("json_records")[:3000]
+    dic = X.trained("json_records")
+    c = X.class_data("json_records")[:3000]
     out = ctypes.create_string_buffer(L.zsmi_compressBound(len(c)))
     r = L.zsmi_compress_usingDict(out, len(out), c, len(c), dic, len(dic), 3)
     assert not L.zsmi_isError(r) and ZstdCompressor(3, dictionary=dic).compress(c) == out.raw[:r]
-    assert out.raw[:r] == compress_many(codec, [c], 3, dic)[0] == O.compress_using_dict(c, dic, 3)
+    assert out.raw[:r] == B.compress_many(codec, [c], 3, dic)[0] == O.compress_using_dict(c, dic, 3)
     assert O.decompress_using_dict(out.raw[:r], len(c), dic) == c
 
 
@@ -245,63 +208,46 @@ import sys, os, ctypes
 import torch
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import numpy as np
-import _oracle as O, _data as D, _corpus as C
+import _oracle as O, _corpus as C, _dicts as X, _batch as B
 from zstandard_amd import BatchCodec
-ERR = 0xFFFFFF88
-CANARY = 0xA5
-FIXC = np.load(os.path.join(D.GOLDEN, "libzstd_fixtures_dict_compress.npz"))
-FIX = np.load(os.path.join(D.GOLDEN, "libzstd_fixtures_dict.npz"))
 bc = BatchCodec(0)
 L = bc.L
 data = C.json_records(3 << 20, seed=99)
 rng = np.random.default_rng(4)
 sizes = np.concatenate([rng.integers(0, 70000, 40), [65536, 65537, 131072, 131073, 200000, 1, 0, 17]]).astype(np.uint32)
-so = np.zeros(len(sizes), dtype=np.uint64); so[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
 assert int(sizes.sum()) <= len(data)
 src_np = np.frombuffer(data[:int(sizes.sum())], dtype=np.uint8)
-bounds = np.array([L.zsmi_compressBound(int(s)) for s in sizes], dtype=np.uint64)
-gaps = rng.integers(0, 300, len(sizes)).astype(np.uint64) * (np.arange(len(sizes)) % 2)
-do = np.zeros(len(sizes), dtype=np.uint64)
-pos = 0
-for i in range(len(sizes)):
-    pos += int(gaps[i]); do[i] = pos; pos += int(bounds[i])
-total = pos + 4096
+so, do, bounds, total = B.ragged_device_layout(L, sizes, rng)
+chunks = B.cut(src_np, so, sizes)
 src = torch.from_numpy(src_np.copy()).cuda()
-for name, dic in (("trained", FIXC["trained_json_records"].tobytes()), ("raw", data[500000:600000])):
+for name, dic in (("trained", X.trained("json_records")), ("raw", data[500000:600000])):
     ddict = torch.from_numpy(np.frombuffer(dic, dtype=np.uint8).copy()).cuda()
     for level in (1, 3, 4):
-        dst = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda")
+        dst = torch.full((total,), B.CANARY, dtype=torch.uint8, device="cuda")
         dsz = torch.zeros(len(sizes), dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
         bc.compress_device(src.data_ptr(), so, sizes, dst.data_ptr(), do, dsz.data_ptr(), level, ddict.data_ptr(), len(dic))
         bc.sync()
         host = dst.cpu().numpy(); sz = dsz.cpu().numpy().view(np.uint32)
-        inside = np.zeros(total, dtype=bool)
-        for i in range(len(sizes)):
-            assert sz[i] <= bounds[i], (name, level, i)
-            inside[int(do[i]):int(do[i]) + int(sz[i])] = True
-        bad = np.flatnonzero(~inside & (host != CANARY))
-        assert bad.size == 0, (name, level, "written outside the frames", bad[:10].tolist())
-        ea, eo, es = O.compress_batch_using_dict(src_np, so, sizes, dic, level, 8)
-        for i in range(len(sizes)):
-            f = host[int(do[i]):int(do[i]) + int(sz[i])].tobytes(); c = src_np[int(so[i]):int(so[i]) + int(sizes[i])].tobytes()
+        B.assert_only_frames_written(host, do, sz, bounds, B.CANARY, (name, level))
+        frames = B.cut(host, do, sz)
+        for i, (f, c, e) in enumerate(zip(frames, chunks, B.oracle_frames(chunks, level, dic))):
             assert O.decompress_using_dict(f, len(c), dic) == c, (name, level, i)
-            assert f == ea[int(eo[i]):int(eo[i]) + int(es[i])].tobytes(), ("oracle E", name, level, i)
+            assert f == e, ("oracle E", name, level, i)
         # the host form gives the same frames
         arena, hdo, hsz = bc.compress_host(src_np, so, sizes, level, dic)
-        assert (hsz == sz).all() and all(arena[int(hdo[i]):int(hdo[i]) + int(hsz[i])].tobytes() == host[int(do[i]):int(do[i]) + int(sz[i])].tobytes() for i in range(len(sizes)))
+        assert (hsz == sz).all() and B.cut(arena, hdo, hsz) == frames
     # NULL / 0 bytes: the plain call
-    dst0 = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda"); dst1 = dst0.clone()
+    dst0 = torch.full((total,), B.CANARY, dtype=torch.uint8, device="cuda"); dst1 = dst0.clone()
     s0 = torch.zeros(len(sizes), dtype=torch.int32, device="cuda"); s1 = s0.clone()
     bc.compress_device(src.data_ptr(), so, sizes, dst0.data_ptr(), do, s0.data_ptr(), 3)
     bc.compress_device(src.data_ptr(), so, sizes, dst1.data_ptr(), do, s1.data_ptr(), 3, ddict.data_ptr(), 0)
     bc.sync()
     assert torch.equal(dst0, dst1) and torch.equal(s0, s1)
 # corrupted dictionaries: 30 before anything runs
-dic = FIX["trained_small_l3_dict"].tobytes()
 dst = torch.zeros(total, dtype=torch.uint8, device="cuda"); dsz = torch.zeros(len(sizes), dtype=torch.int32, device="cuda")
 p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-for d in [dic[:9], dic[:40], dic[:120]] + [bytes.fromhex(h) for h in sys.argv[2].split(",")]:
+for d in X.bad_dictionaries():
     dd = torch.from_numpy(np.frombuffer(d, dtype=np.uint8).copy()).cuda()
     rc = L.zsmi_compressBatchDevice_usingDict(bc.ctx, ctypes.c_void_p(src.data_ptr()), p(so), p(sizes), len(sizes), ctypes.c_void_p(dst.data_ptr()), p(do),
                                               ctypes.c_void_p(dsz.data_ptr()), 3, ctypes.c_void_p(dd.data_ptr()), len(d))
@@ -314,38 +260,30 @@ def test_device_calls_stay_in_bounds_and_refuse_bad_dictionaries():
     """zsmi_compressBatchDevice_usingDict: canary-filled output, ragged chunks around the 64 KiB limit; every frame within
     zsmi_compressBound and nothing written outside the frames; frames equal to the host form's and oracle E's and decode under oracle D; a NULL /
     0-byte dictionary is the plain call; corrupted dictionaries return 30"""
-    extra = ",".join(d.hex() for d in bad_dictionaries()[3:])
-    r = subprocess.run([sys.executable, "-c", _DEVICE_CHILD, ROOT, extra], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CHILD-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    B.run_child("-c", _DEVICE_CHILD, B.ROOT)
 
 
 _SUB_CHILD = r'''
 import sys, os
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import numpy as np
-import _oracle as O, _data as D
+import _oracle as O, _data as D, _dicts as X, _batch as B
 from zstandard_amd import BatchCodec
-ERR = 0xFFFFFF88
-FIXC = np.load(os.path.join(D.GOLDEN, "libzstd_fixtures_dict_compress.npz"))
-dic = FIXC["trained_zipf"].tobytes()
+dic = X.trained("zipf")
 bc = BatchCodec()
 data = D.zipf_log(16 << 20, seed_lo=4343)
 rng = np.random.default_rng(22)
 sizes = np.concatenate([rng.integers(0, 190000, 120), [65536] * 40, [1024] * 60, [131072] * 6]).astype(np.uint32)
 rng.shuffle(sizes)
-offs = np.zeros(len(sizes), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
+offs = B.layout(sizes)
+chunks = B.cut(data, offs, sizes)
 for level in (3, 1):
-    arena, do, dsz = bc.compress_host(data, offs, sizes, level, dic)
-    assert (dsz < ERR).all()
-    frames = [arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes() for i in range(len(sizes))]
-    ea, eo, es = O.compress_batch_using_dict(data, offs, sizes, dic, level, 8)
-    for i, f in enumerate(frames):
-        c = data[int(offs[i]):int(offs[i]) + int(sizes[i])].tobytes()
+    frames = B.frames_of(bc.compress_host(data, offs, sizes, level, dic))
+    expect = B.cut(*O.compress_batch_using_dict(data, offs, sizes, dic, level, 8))
+    for i, (f, c, e) in enumerate(zip(frames, chunks, expect)):
         assert O.decompress_using_dict(f, len(c), dic) == c, (level, i)
-        assert f == ea[int(eo[i]):int(eo[i]) + int(es[i])].tobytes(), ("oracle E", level, i)
-    fo = np.zeros(len(sizes), dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
-    out, oo, osz = bc.decompress_host(np.frombuffer(b"".join(frames), dtype=np.uint8), fo, dsz, np.maximum(sizes, 1), dic)
-    assert (osz == sizes).all()
+        assert f == e, ("oracle E", level, i)
+    assert [sz for sz, _ in B.decode_many(bc, frames, sizes, dic)] == sizes.tolist()
 print("CHILD-OK")
 '''
 
@@ -354,27 +292,26 @@ def test_sub_batches_with_a_dictionary():
     """ZSMI_BLOCKS_IN_FLIGHT=64 in a child process: a mixed batch (prefixed units, tails of long chunks, big units) is cut in many
     sub-batches; every frame equals oracle E's and round-trips"""
     env = dict(os.environ, ZSMI_BLOCKS_IN_FLIGHT="64")
-    r = subprocess.run([sys.executable, "-c", _SUB_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CHILD-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    B.run_child("-c", _SUB_CHILD, B.ROOT, env=env)
 
 
 # ------------------------------------------------------------------ ratio contract
 def test_ratio_against_libzstd_with_the_same_dictionary(codec):
     """level 3, chunks of 1 / 4 / 16 KiB: <= 1.03 x libzstd with the same raw-content dictionary (the trained dictionary's content);
     <= 1.10 x libzstd with the trained dictionary at >= 4 KiB, <= 1.25 x at 1 KiB (libzstd also uses its tables, this encoder does not)"""
-    if not _zstd():
+    if not X.zstd():
         pytest.skip("libzstd not available")
     table = {}
-    for cls in RECORD_CLASSES:
-        data, dic = class_data(cls), trained(cls)
-        raw = content_of(dic)
+    for cls in X.RECORD_CLASSES:
+        data, dic = X.class_data(cls), X.trained(cls)
+        raw = X.content_of(dic)
         assert len(raw) <= 65536
         for cs in (1024, 4096, 16384):
             chunks = [data[i:i + cs] for i in range(0, 256 * 1024, cs)]
-            ours_raw = sum(len(f) for f in compress_many(codec, chunks, 3, raw))
-            ours_tr = sum(len(f) for f in compress_many(codec, chunks, 3, dic))
-            z_raw = sum(len(zstd_compress_dict(c, raw, 3)) for c in chunks)
-            z_tr = sum(len(zstd_compress_dict(c, dic, 3)) for c in chunks)
+            ours_raw = sum(len(f) for f in B.compress_many(codec, chunks, 3, raw))
+            ours_tr = sum(len(f) for f in B.compress_many(codec, chunks, 3, dic))
+            z_raw = sum(len(X.zstd_compress_dict(c, raw, 3)) for c in chunks)
+            z_tr = sum(len(X.zstd_compress_dict(c, dic, 3)) for c in chunks)
             table[(cls, cs)] = (round(ours_raw / z_raw, 3), round(ours_tr / z_tr, 3))
     print(table)
     assert all(v[0] <= 1.03 for v in table.values()), table

@@ -4,16 +4,17 @@ parse, NCounts without a zero), compress held-out chunks within 1.03x of the com
 compressor, round-trip under oracle D, this library's decoder and libzstd (libzstd's own frames repeat our entropy tables); finalize alone
 must match libzstd's tables on libzstd's content within 1.01x; calls are deterministic across forms and sub-batches; errors write nothing.
 Samples and held-out chunks: tests/_train.py."""
-import ctypes, os, subprocess, sys
+import ctypes, os
 import numpy as np
 import pytest
 import _oracle as O
 import _dicts as X
 import _train as T
+import _batch as B
+import _framewriter as W
+from _hip import hip_of, Dev
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR = 0xFFFFFF88
 MAGIC = bytes([0x37, 0xA4, 0x30, 0xEC])
 
 
@@ -41,42 +42,8 @@ def train_fc(parts, cap, p):
 
 
 def compressed_total(codec, chunks, dic=b""):
-    sizes = np.array([len(c) for c in chunks], dtype=np.uint32)
-    offs = np.zeros(len(chunks), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-    arena, do, dsz = codec.compress_host(np.frombuffer(b"".join(chunks), dtype=np.uint8), offs, sizes, 3, dic)
-    assert (dsz <= ERR).all()
-    return int(dsz.astype(np.uint64).sum()), [arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes() for i in range(len(chunks))]
-
-
-def read_ncount(b, max_sym):
-    """FSE_readNCount: (normalized counts, table log, bytes read)"""
-    bits = int.from_bytes(b[:64] + bytes(8), "little")
-    pos = 0
-    def take(n):
-        nonlocal pos
-        v = (bits >> pos) & ((1 << n) - 1); return v
-    log = take(4) + 5; pos += 4
-    remaining, threshold, nb = (1 << log) + 1, 1 << log, log + 1
-    norm, prev0 = [], False
-    while remaining > 1 and len(norm) <= max_sym:
-        if prev0:
-            while take(16) == 0xFFFF: norm += [0] * 24; pos += 16
-            while take(2) == 3: norm += [0] * 3; pos += 2
-            norm += [0] * take(2); pos += 2
-        mx = (2 * threshold - 1) - remaining
-        low = take(nb - 1)
-        if low < mx:
-            count = low; pos += nb - 1
-        else:
-            count = take(nb)
-            if count >= threshold: count -= mx
-            pos += nb
-        count -= 1
-        remaining -= abs(count)
-        norm.append(count); prev0 = count == 0
-        while remaining < threshold: nb -= 1; threshold >>= 1
-    assert remaining == 1
-    return norm, log, (pos + 7) // 8
+    frames = B.compress_many(codec, chunks, 3, dic)
+    return sum(map(len, frames)), frames
 
 
 def check_format(dic, cap):
@@ -93,9 +60,8 @@ def check_format(dic, cap):
     assert h < 128, "256 weights only fit an FSE-compressed description"
     of_max = (len(content) + (128 << 10)).bit_length() - 1
     for max_sym, log in ((of_max, 8), (52, 9), (35, 9)):
-        norm, tl, used = read_ncount(dic[p:], max_sym)
+        norm, tl, p = W.read_ncount(dic, p, max_sym)
         assert tl == log and len(norm) == max_sym + 1 and all(v != 0 for v in norm), (max_sym, norm)
-        p += used
     assert p + 12 == off
     return content
 
@@ -161,23 +127,15 @@ def test_round_trips(codec, cls):
     _, frames = compressed_total(codec, held, dic)
     for c, fr in zip(held, frames):
         assert O.decompress_using_dict(fr, len(c), dic) == c
-    sizes = np.array([len(f) for f in frames], dtype=np.uint32)
-    offs = np.zeros(len(frames), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-    caps = np.array([len(c) for c in held], dtype=np.uint32)
-    arena, do, dsz = codec.decompress_host(np.frombuffer(b"".join(frames), dtype=np.uint8), offs, sizes, caps, dic)
-    for i, c in enumerate(held):
-        assert int(dsz[i]) == len(c) and arena[int(do[i]):int(do[i]) + len(c)].tobytes() == c
+    caps = [len(c) for c in held]
+    assert B.decode_many(codec, frames, caps, dic, min_cap=0) == [(len(c), c) for c in held]
     if X.zstd():
         for c, fr in zip(held, frames):
             assert X.zstd_decompress_dict(fr, len(c), dic) == c
         zf = [X.zstd_compress_dict(c, dic, 3) for c in held]         # libzstd's frames repeat the dictionary's entropy tables
         for c, fr in zip(held, zf):
             assert O.decompress_using_dict(fr, len(c), dic) == c
-        zs = np.array([len(f) for f in zf], dtype=np.uint32)
-        zo = np.zeros(len(zf), dtype=np.uint64); zo[1:] = np.cumsum(zs.astype(np.uint64))[:-1]
-        arena, do, dsz = codec.decompress_host(np.frombuffer(b"".join(zf), dtype=np.uint8), zo, zs, caps, dic)
-        for i, c in enumerate(held):
-            assert int(dsz[i]) == len(c) and arena[int(do[i]):int(do[i]) + len(c)].tobytes() == c
+        assert B.decode_many(codec, zf, caps, dic, min_cap=0) == [(len(c), c) for c in held]
 
 
 # finalize from this library's parse: libzstd's own parse of csv_records and binary_table takes more repeat-offset matches than this encoder's
@@ -203,16 +161,6 @@ def test_finalize_matches_libzstd_tables(cls):
 
 
 # ------------------------------------------------------------------ determinism, forms, write-back
-def hip_of():
-    """the HIP runtime libzsmi.so is linked against (the copy already loaded with it)"""
-    L()
-    H = ctypes.CDLL("libamdhip64.so.7")
-    H.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    H.hipFree.argtypes = [ctypes.c_void_p]
-    H.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return H
-
-
 def test_deterministic_and_forms(codec):
     from zstandard_amd import train_dictionary
     parts = T.samples("json_records", 1 << 20)
@@ -220,18 +168,15 @@ def test_deterministic_and_forms(codec):
     b, kb, db = train_dictionary(parts, 32768, k=0, d=8, steps=4, return_params=True)
     assert a == b and (ka, da) == (kb, db) and da == 8 and ka in range(50, 2001)
     # the device form: the samples in reverse order behind 4 KiB of other bytes, named by their offsets
-    H = hip_of()
     rev = b"".join(reversed(parts))
-    base = ctypes.c_void_p()
-    assert H.hipMalloc(ctypes.byref(base), len(rev) + 4096) == 0
+    dev = Dev(hip_of(), len(rev), rev)                                       # (.p: behind PAD = 4 KiB of canary bytes)
     try:
-        assert H.hipMemcpy(ctypes.c_void_p(base.value + 4096), rev, len(rev), 1) == 0
         sizes = np.array([len(x) for x in parts], dtype=np.uint32)
         ends = np.cumsum(sizes[::-1].astype(np.uint64))[::-1]
         offs = (ends - sizes).astype(np.uint64)                              # sample i: behind the samples after it
-        c, kc, dc = codec.train_device(base.value + 4096, offs, sizes, 32768, k=0, d=8, steps=4)
+        c, kc, dc = codec.train_device(dev.p, offs, sizes, 32768, k=0, d=8, steps=4)
     finally:
-        H.hipFree(base)
+        dev.free()
     assert c == a and (kc, dc) == (ka, da)
     g, kg, dg = train_dictionary(parts, 32768, k=0, d=0, steps=2, return_params=True)      # d searched too
     assert dg in (6, 8) and check_format(g, 32768)
@@ -251,9 +196,7 @@ def test_sub_batches_give_the_same_dictionary():
     from zstandard_amd import train_dictionary
     want = train_dictionary(T.samples("zipf", 1 << 20), 32768, k=0, d=8, steps=4)
     env = dict(os.environ, ZSMI_BLOCKS_IN_FLIGHT="64")
-    r = subprocess.run([sys.executable, "-c", _SUB_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    got = bytes.fromhex(r.stdout.split("DICT ")[1].strip())
+    got = bytes.fromhex(B.run_child("-c", _SUB_CHILD, B.ROOT, env=env, marker="DICT ").split("DICT ")[1].strip())
     assert got == want
 
 

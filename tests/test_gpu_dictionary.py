@@ -6,11 +6,12 @@ import numpy as np
 import pytest
 import _oracle as O
 import _data as D
+import _batch as B
+from _batch import ERR
 
 pytestmark = pytest.mark.gpu
 FIX = np.load(os.path.join(D.GOLDEN, "libzstd_fixtures_dict.npz"))
 NAMES = sorted(k[:-6] for k in FIX.files if k.endswith("_frame"))
-ERR = 0xFFFFFF88
 
 
 @pytest.fixture(scope="module")
@@ -19,20 +20,12 @@ def codec():
     return BatchCodec(0)
 
 
-def _decode(codec, frames, caps, dictionary):
-    sizes = np.array([len(f) for f in frames], dtype=np.uint32)
-    offs = np.zeros(len(frames), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-    blob = np.frombuffer(b"".join(frames), dtype=np.uint8)
-    out, oo, osz = codec.decompress_host(blob, offs, sizes, np.array(caps, dtype=np.uint32), dictionary)
-    return [(int(osz[i]), out[int(oo[i]):int(oo[i]) + (int(osz[i]) if osz[i] <= ERR else 0)].tobytes()) for i in range(len(frames))]
-
-
 @pytest.mark.parametrize("kind", ["raw", "trained"])
 def test_dictionary_frames_decode_in_one_batch(codec, kind):
     names = [n for n in NAMES if n.startswith(kind)]
     dic = FIX[names[0] + "_dict"].tobytes()
     frames = [FIX[n + "_frame"].tobytes() for n in names]; wants = [FIX[n + "_want"].tobytes() for n in names]
-    for (sz, got), want in zip(_decode(codec, frames, [len(w) for w in wants], dic), wants):
+    for (sz, got), want in zip(B.decode_many(codec, frames, [len(w) for w in wants], dic, min_cap=0), wants):
         assert sz == len(want) and got == want
 
 
@@ -52,14 +45,14 @@ def test_dictionary_errors_are_the_references(codec):
     cases = [(b"", 32), (FIX["raw_small_l3_dict"].tobytes(), 32), (dic[:9], 30), (dic[:40], 30), (dic[:120], 30)]
     other = bytearray(dic); other[4] ^= 1; cases.append((bytes(other), 32))
     for d, code in cases:
-        (sz, _), = _decode(codec, [frame], [len(want)], d)
+        (sz, _), = B.decode_many(codec, [frame], [len(want)], d, min_cap=0)
         assert sz > ERR and (0x100000000 - sz) == code
         with pytest.raises(O.OracleError) as e:
             O.decompress_using_dict(frame, len(want), d) if d else O.decompress(frame, len(want))
         assert e.value.code == code
     # raw-content frames without their dictionary: an offset reaches in front of the output (or the bytes differ)
     rname = "raw_text_l19"
-    (sz, got), = _decode(codec, [FIX[rname + "_frame"].tobytes()], [len(FIX[rname + "_want"])], b"")
+    (sz, got), = B.decode_many(codec, [FIX[rname + "_frame"].tobytes()], [len(FIX[rname + "_want"])], b"", min_cap=0)
     assert sz > ERR or got != FIX[rname + "_want"].tobytes()
 
 
@@ -68,5 +61,5 @@ def test_own_frames_still_decode_when_a_dictionary_is_given(codec):
     data = D.zipf_log(1 << 18, seed_lo=3)
     chunks = [data[i * 40000:(i + 1) * 40000].tobytes() for i in range(4)]
     frames = [O.compress(c, 3) for c in chunks]
-    for (sz, got), want in zip(_decode(codec, frames, [len(c) for c in chunks], FIX["raw_small_l3_dict"].tobytes()), chunks):
+    for (sz, got), want in zip(B.decode_many(codec, frames, [len(c) for c in chunks], FIX["raw_small_l3_dict"].tobytes(), min_cap=0), chunks):
         assert sz == len(want) and got == want

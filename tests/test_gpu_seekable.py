@@ -11,11 +11,10 @@ import _corpus as C
 import _data as D
 import _oracle as O
 import _seekable as S
+from _hip import hip_of, Dev, CANARY, PAD
 
 pytestmark = pytest.mark.gpu
 E_PREFIX, E_CORRUPT, E_CHECKSUM, E_OUT_OF_BOUND = 10, 20, 22, 42
-CANARY = 0xA5
-PAD = 4096
 
 
 @pytest.fixture(scope="module")
@@ -24,42 +23,9 @@ def L():
     return _lib.lib()
 
 
-def hip_of():
-    """the HIP runtime libzsmi.so is linked against (by its soname: the copy already loaded with it)"""
-    from zstandard_amd import _lib
-    _lib.lib()
-    H = ctypes.CDLL("libamdhip64.so.7")
-    H.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    H.hipFree.argtypes = [ctypes.c_void_p]
-    H.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    H.hipMemset.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]
-    return H
-
-
 @pytest.fixture(scope="module")
 def hip():
     return hip_of()
-
-
-class Dev:
-    """device buffer of n bytes + PAD canary bytes on each side; .p is the first byte after the front canary"""
-
-    def __init__(self, H, n, fill=b""):
-        self.H, self.n = H, n
-        self.base = ctypes.c_void_p()
-        assert H.hipMalloc(ctypes.byref(self.base), n + 2 * PAD) == 0
-        assert H.hipMemset(self.base, CANARY, n + 2 * PAD) == 0
-        self.p = self.base.value + PAD
-        if fill:
-            assert H.hipMemcpy(ctypes.c_void_p(self.p), fill, len(fill), 1) == 0
-
-    def all(self) -> bytes:
-        out = ctypes.create_string_buffer(self.n + 2 * PAD)
-        assert self.H.hipMemcpy(out, self.base, self.n + 2 * PAD, 2) == 0
-        return out.raw
-
-    def free(self):
-        self.H.hipFree(self.base)
 
 
 @pytest.fixture(scope="module")

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import _oracle as O
 import _dicts as X
+import _batch as B
 
 SIZES = (0, 1, 7, 8, 16, 17, 255, 256, 1024, 4096, 65535, 65536, 65537, 65792, 131073)
 
@@ -23,20 +24,18 @@ def test_round_trip(level):
     """every dictionary kind x chunk sizes around every limit, every corpus class, contents aimed at the prefix rules"""
     for name, dic in X.identity_dictionaries().items():
         chunks = X.prefix_chunks(dic, SIZES)
-        frames = X.oracle_frames(chunks, level, dic)
+        frames = B.oracle_frames(chunks, level, dic)
         assert_decodes(frames, chunks, dic, name)
         assert frames[3] == O.compress_using_dict(chunks[3], dic, level)           # the one-shot form is the batch form
 
 
 def test_no_dictionary_is_the_plain_call():
     chunks = X.prefix_chunks(X.TRAINED8K, SIZES)
-    src, offs, sizes = X.batch(chunks)
+    src, offs, sizes = B.batch(chunks)
     for level in (1, 3):
-        a, o, s = O.compress_batch(src, offs, sizes, level, 4)
-        plain = [a[int(o[i]):int(o[i]) + int(s[i])].tobytes() for i in range(len(chunks))]
+        plain = B.cut(*O.compress_batch(src, offs, sizes, level, 4))
         for d in (None, b""):
-            a, o, s = O.compress_batch_using_dict(src, offs, sizes, d, level, 4)
-            assert [a[int(o[i]):int(o[i]) + int(s[i])].tobytes() for i in range(len(chunks))] == plain
+            assert B.cut(*O.compress_batch_using_dict(src, offs, sizes, d, level, 4)) == plain
             assert all(O.compress_using_dict(c, d, level) == f for c, f in zip(chunks, plain))
 
 
@@ -44,7 +43,7 @@ def test_dictionary_id_at_every_field_size():
     chunks = [X.STREAM[:300], X.STREAM[1000:1000 + 70000], b"", X.STREAM[:65536]]
     for did, dic in X.id_dictionaries().items():
         size = 0 if did == 0 else (1 if did < 256 else (2 if did < 65536 else 4))
-        for f, c in zip(X.oracle_frames(chunks, 3, dic), chunks):
+        for f, c in zip(B.oracle_frames(chunks, 3, dic), chunks):
             assert f[4] & 3 == (3 if size == 4 else size)
             assert int.from_bytes(f[5:5 + size], "little") == did
             assert O.decompress_using_dict(f, len(c), dic) == c
@@ -56,7 +55,7 @@ def test_dictionary_id_at_every_field_size():
 
 def test_refused_dictionaries():
     data = X.STREAM[:4096]
-    src, offs, sizes = X.batch([data, data[:100]])
+    src, offs, sizes = B.batch([data, data[:100]])
     for d in X.bad_dictionaries():
         with pytest.raises(O.OracleError) as e:
             O.compress_using_dict(data, d, 3)
@@ -74,10 +73,10 @@ def test_only_the_last_64k_of_the_content_is_referenced():
         other = dic[:off] + bytes(len(dic) - off - 65536) + dic[-65536:]
         chunks = X.prefix_chunks(dic, SIZES)
         for level in (1, 3):
-            for f, c in zip(X.oracle_frames(chunks, level, dic), chunks):
+            for f, c in zip(B.oracle_frames(chunks, level, dic), chunks):
                 assert O.decompress_using_dict(f, len(c), other) == c
         cut = [c for c in chunks if len(c) > 65536]
-        for f, c in zip(X.oracle_frames(cut, 3, dic), cut):
+        for f, c in zip(B.oracle_frames(cut, 3, dic), cut):
             assert O.decompress_using_dict(f, len(c), dic[:off] + bytes(len(dic) - off)) == c
 
 
@@ -95,7 +94,7 @@ def test_first_block_starts_from_the_dictionarys_recent_offsets():
     for reps in ((4, 8, 1), (8, 1, 4), (2, 3, 5), (1000, 40000, 7)):
         dic = X.with_reps(X.trained("json_records"), reps)
         for level in (1, 3, 4):
-            assert_decodes(X.oracle_frames(chunks, level, dic), chunks, dic, reps)
+            assert_decodes(B.oracle_frames(chunks, level, dic), chunks, dic, reps)
 
 
 @pytest.mark.skipif(not X.zstd(), reason="libzstd not present")
@@ -108,8 +107,8 @@ def test_ratio_against_libzstd_with_the_same_dictionary():
         raw = X.content_of(dic)
         for cs in (1024, 4096, 16384):
             chunks = [data[i:i + cs] for i in range(0, 256 * 1024, cs)]
-            ours_raw = sum(len(f) for f in X.oracle_frames(chunks, 3, raw))
-            ours_tr = sum(len(f) for f in X.oracle_frames(chunks, 3, dic))
+            ours_raw = sum(len(f) for f in B.oracle_frames(chunks, 3, raw))
+            ours_tr = sum(len(f) for f in B.oracle_frames(chunks, 3, dic))
             z_raw = sum(len(X.zstd_compress_dict(c, raw, 3)) for c in chunks)
             z_tr = sum(len(X.zstd_compress_dict(c, dic, 3)) for c in chunks)
             table[(cls, cs)] = (round(ours_raw / z_raw, 3), round(ours_tr / z_tr, 3))

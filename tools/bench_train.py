@@ -12,6 +12,8 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import _corpus as C
 import _train as T
+import _batch as B
+from _hip import hip_of
 
 SEEDS = {"json_records": 1011, "binary_table": 1014}
 
@@ -36,15 +38,11 @@ def main():
     L = _lib.lib()
     Z = T.zdict()
     bc = BatchCodec(0)
-    H = ctypes.CDLL("libamdhip64.so.7")
-    H.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]; H.hipFree.argtypes = [ctypes.c_void_p]
-    H.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    H = hip_of()
     cap = a.capacity
     for cls in a.classes.split(","):
         held = T.held_out(cls)
-        hs = np.array([len(c) for c in held], dtype=np.uint32)
-        ho = np.zeros(len(held), dtype=np.uint64); ho[1:] = np.cumsum(hs.astype(np.uint64))[:-1]
-        src = np.frombuffer(b"".join(held), dtype=np.uint8)
+        src, ho, hs = B.batch(held)
 
         def held_total(dic):
             _, _, dsz = bc.compress_host(src, ho, hs, 3, dic)
@@ -66,7 +64,7 @@ def main():
             dptr = ctypes.c_void_p()
             assert H.hipMalloc(ctypes.byref(dptr), len(buf) + 64) == 0 and H.hipMemcpy(dptr, buf, len(buf), 1) == 0
             ss = np.array([len(x) for x in parts], dtype=np.uint32)
-            so = np.zeros(len(parts), dtype=np.uint64); so[1:] = np.cumsum(ss.astype(np.uint64))[:-1]
+            so = B.layout(ss)
             bc.enable_timing(True)
             t0 = time.perf_counter()
             dev, kk, dd = bc.train_device(dptr.value, so, ss, cap, d=8, steps=4, split_point=0.75, level=3)

@@ -12,7 +12,7 @@ import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
-import _oracle as O, _edge_catalogue as C, _framewriter as W, _data as D
+import _oracle as O, _edge_catalogue as C, _framewriter as W, _data as D, _batch as B
 from zstandard_amd import BatchCodec, _lib
 
 MIB = 1 << 20
@@ -28,11 +28,8 @@ def want(frame, cap):
 
 
 def place(caps, gaps):
-    do = np.zeros(len(caps), dtype=np.uint64)
-    pos = 0
-    for i, c in enumerate(caps):
-        pos += int(gaps[i]); do[i] = pos; pos += int(c)
-    return do, pos + 4096
+    do = B.layout(caps, gaps)
+    return do, int(do[-1]) + int(caps[-1]) + 4096
 
 
 def outside(host, do, caps):
@@ -45,9 +42,8 @@ def outside(host, do, caps):
 def decode_case(bc, frames, caps, gaps):
     caps = np.array(caps, dtype=np.uint32)
     do, total = place(caps, gaps)
-    fsz = np.array([len(f) for f in frames], dtype=np.uint32)
-    fo = np.zeros(len(frames), dtype=np.uint64); fo[1:] = np.cumsum(fsz.astype(np.uint64))[:-1]
-    src = torch.from_numpy(np.frombuffer(b"".join(frames), dtype=np.uint8).copy()).cuda()
+    blob, fo, fsz = B.batch(frames)
+    src = torch.from_numpy(blob.copy()).cuda()
     dst = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda")
     sizes = torch.zeros(len(frames), dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -90,12 +86,11 @@ def main():
     noise = rng.integers(0, 256, 2 << 20, dtype=np.uint8).tobytes()
     chunks = [(noise if i % 3 == 1 else text)[i * 50000:i * 50000 + k]
               for i, k in enumerate([0, 1, 17, 4095, 65535, 65536, 65537, 131072, 300000, 0, MIB, 7])]
-    csz = np.array([len(c) for c in chunks], dtype=np.uint32)
-    so = np.zeros(len(chunks), dtype=np.uint64); so[1:] = np.cumsum(csz.astype(np.uint64))[:-1]
+    blob, so, csz = B.batch(chunks)
     bounds = np.array([L.zsmi_compressBound(int(s)) for s in csz], dtype=np.uint64)
     for gaps in (np.zeros(len(chunks), dtype=np.int64), rng.integers(1, 200, len(chunks))):
         do, total = place(bounds, gaps)
-        src = torch.from_numpy(np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()).cuda()
+        src = torch.from_numpy(blob.copy()).cuda()
         dst = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda")
         dsz = torch.zeros(len(chunks), dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
@@ -104,8 +99,7 @@ def main():
         host = dst.cpu().numpy(); zs = dsz.cpu().numpy().view(np.uint32)
         bad = outside(host, do, bounds)
         assert bad.size == 0, f"compress wrote outside the compressBound regions at {bad[:10].tolist()}"
-        for i, c in enumerate(chunks):
-            f = host[int(do[i]):int(do[i]) + int(zs[i])].tobytes()
+        for i, (f, c) in enumerate(zip(B.cut(host, do, zs), chunks)):
             assert int(zs[i]) <= int(bounds[i]) and O.decompress(f, len(c)) == c, i
         REPORT["compress_items"] += len(chunks)
     bc.close()

@@ -8,7 +8,7 @@ import sys, ctypes, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
-import _data as D, _oracle as O, _corpus as C
+import _data as D, _oracle as O, _corpus as C, _batch as B
 from zstandard_amd import BatchCodec, _lib
 
 
@@ -35,16 +35,10 @@ def main():
 
     def run(label, chunks, own=True, lvl=3):
         if own:
-            src = np.frombuffer(b"".join(chunks), dtype=np.uint8); sizes = np.array([len(c) for c in chunks], dtype=np.uint32)
-            offs = np.zeros(len(chunks), dtype=np.uint64); offs[1:] = np.cumsum(sizes.astype(np.uint64))[:-1]
-            arena, do, dsz = bc.compress_host(src, offs, sizes, lvl)
-            frames = [arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes() for i in range(len(chunks))]
+            frames = B.cut(*bc.compress_host(*B.batch(chunks), lvl))
         else:
             frames = [O.zstd_compress(c, lvl) for c in chunks]
-        sizes = np.array([len(c) for c in chunks], dtype=np.uint32); fsz = np.array([len(f) for f in frames], dtype=np.uint32)
-        blob = np.frombuffer(b"".join(frames), dtype=np.uint8); fo = np.zeros(len(frames), dtype=np.uint64); fo[1:] = np.cumsum(fsz.astype(np.uint64))[:-1]
-        out, oo, osz = bc.decompress_host(blob, fo, fsz, sizes)
-        ok = all(int(osz[i]) == len(c) and out[int(oo[i]):int(oo[i]) + len(c)].tobytes() == c for i, c in enumerate(chunks))
+        ok = B.decode_many(bc, frames, [len(c) for c in chunks], min_cap=0) == [(len(c), c) for c in chunks]
         n = len(chunks)
         buf = np.zeros(n * DESC_WORDS, dtype=np.uint32)
         rc = Z.zsmi_dbg_copyScratch(bc.ctx, 10, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc

@@ -8,7 +8,7 @@ import sys, ctypes, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
-import _oracle as O, _edge_catalogue as C
+import _oracle as O, _edge_catalogue as C, _batch as B
 from zstandard_amd import BatchCodec, _lib
 from fastpath_check import desc_layout
 
@@ -21,10 +21,7 @@ def main():
     cat = C.catalogue()
     res = {}
     for placement, caps in (("a", [e.cap for e in cat]), ("b", [1 << 20] * len(cat))):
-        frames = [e.frame for e in cat]
-        fsz = np.array([len(f) for f in frames], dtype=np.uint32)
-        fo = np.zeros(len(frames), dtype=np.uint64); fo[1:] = np.cumsum(fsz.astype(np.uint64))[:-1]
-        out, oo, osz = bc.decompress_host(np.frombuffer(b"".join(frames), dtype=np.uint8), fo, fsz, np.array(caps, dtype=np.uint32))
+        out, oo, osz = bc.decompress_host(*B.batch([e.frame for e in cat]), np.array(caps, dtype=np.uint32))
         buf = np.zeros(len(cat) * DESC_WORDS, dtype=np.uint32)
         rc = Z.zsmi_dbg_copyScratch(bc.ctx, 10, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
         fast = buf.reshape(-1, DESC_WORDS)[:len(cat), FAST_AT]

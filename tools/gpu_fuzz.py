@@ -6,7 +6,7 @@ import sys, os
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import _data as D, _oracle as O
+import _data as D, _oracle as O, _batch as B
 from zstandard_amd import BatchCodec
 
 def content(rng, total):
@@ -46,17 +46,13 @@ def main():
         level = 1 if rd % 3 == 2 else 3
         arena, do, dsz = bc.compress_host(data, starts, sizes, level)
         ea, eo, esz = O.compress_batch(data, starts, sizes, level, threads=8)
-        frames = []
-        for i in range(n):
-            g = arena[int(do[i]):int(do[i]) + int(dsz[i])].tobytes(); e = ea[int(eo[i]):int(eo[i]) + int(esz[i])].tobytes()
+        frames = B.cut(arena, do, dsz)
+        for i, (g, e) in enumerate(zip(frames, B.cut(ea, eo, esz))):
             if g != e:
                 bad += 1; print(f"round {rd} chunk {i} size {sizes[i]} level {level}: frames differ ({len(g)} vs {len(e)})")
             elif rd < 2 and i % 7 == 0 and O.decompress(g, int(sizes[i])) != data[int(starts[i]):int(starts[i]) + int(sizes[i])].tobytes():
                 bad += 1; print(f"round {rd} chunk {i}: oracle D does not restore the chunk")
-            frames.append(g)
-        blob = np.frombuffer(b"".join(frames), dtype=np.uint8)
-        fo = np.zeros(n, dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
-        out, oo, osz = bc.decompress_host(blob, fo, dsz, sizes)
+        out, oo, osz = bc.decompress_host(*B.batch(frames), sizes)
         for i in range(n):
             if int(osz[i]) != int(sizes[i]) or out[int(oo[i]):int(oo[i]) + int(sizes[i])].tobytes() != data[int(starts[i]):int(starts[i]) + int(sizes[i])].tobytes():
                 bad += 1; print(f"round {rd} chunk {i} size {sizes[i]}: HIP decoder result differs (size {osz[i]})")

@@ -7,7 +7,7 @@ import sys, os
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import _data as D, _oracle as O
+import _data as D, _oracle as O, _batch as B
 from zstandard_amd import BatchCodec
 
 def pieces(rng, total):
@@ -60,10 +60,7 @@ def dictionary_rounds(bc, rounds):
             c = base[a:a + n]
             chunks.append(c); frames.append(comp(c, dic, int(rng.integers(1, 20))))
         sizes = np.array([len(c) for c in chunks], dtype=np.uint32)
-        fsz = np.array([len(f) for f in frames], dtype=np.uint32)
-        blob = np.frombuffer(b"".join(frames), dtype=np.uint8)
-        fo = np.zeros(len(frames), dtype=np.uint64); fo[1:] = np.cumsum(fsz.astype(np.uint64))[:-1]
-        out, oo, osz = bc.decompress_host(blob, fo, fsz, sizes, dic)
+        out, oo, osz = bc.decompress_host(*B.batch(frames), sizes, dic)
         for i, c in enumerate(chunks):
             if int(osz[i]) != len(c) or out[int(oo[i]):int(oo[i]) + len(c)].tobytes() != c:
                 bad += 1; print(f"dictionary round {rd} frame {i} ({len(c)} B, dictionary {len(dic)} B): wrong output, size/status {osz[i]:#x}")
@@ -111,10 +108,7 @@ def main():
             f = zstd_compress_checked(c, int(rng.integers(1, 20))) if i % 3 == 0 else O.zstd_compress(c, int(rng.integers(1, 20)))
             chunks.append(c); frames.append(f)
         sizes = np.array([len(c) for c in chunks], dtype=np.uint32)
-        fsz = np.array([len(f) for f in frames], dtype=np.uint32)
-        blob = np.frombuffer(b"".join(frames), dtype=np.uint8)
-        fo = np.zeros(len(frames), dtype=np.uint64); fo[1:] = np.cumsum(fsz.astype(np.uint64))[:-1]
-        out, oo, osz = bc.decompress_host(blob, fo, fsz, sizes)
+        out, oo, osz = bc.decompress_host(*B.batch(frames), sizes)
         for i, c in enumerate(chunks):
             if int(osz[i]) != len(c) or out[int(oo[i]):int(oo[i]) + len(c)].tobytes() != c:
                 bad += 1; print(f"round {rd} frame {i} ({len(c)} B): wrong output, size/status {osz[i]:#x}")
@@ -122,11 +116,8 @@ def main():
         dmg = []
         for i, f in enumerate(frames[:40]):
             b = bytearray(f); p = int(rng.integers(0, len(b))); b[p] ^= 1 << int(rng.integers(0, 8)); dmg.append(bytes(b))
-        dsz = np.array([len(f) for f in dmg], dtype=np.uint32)
-        dblob = np.frombuffer(b"".join(dmg), dtype=np.uint8)
-        dfo = np.zeros(len(dmg), dtype=np.uint64); dfo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
         caps = sizes[:len(dmg)]
-        out2, oo2, osz2 = bc.decompress_host(dblob, dfo, dsz, caps)
+        out2, oo2, osz2 = bc.decompress_host(*B.batch(dmg), caps)
         for i, f in enumerate(dmg):
             try:
                 want = O.decompress(f, int(caps[i])); werr = None
@@ -134,7 +125,7 @@ def main():
                 want = None; werr = e.code
             got = int(osz2[i])
             if want is None:
-                if got <= 0xFFFFFF88:
+                if got <= B.ERR:
                     bad += 1; print(f"round {rd} damaged {i}: oracle error {werr}, HIP {got:#x}")
             elif got != len(want) or out2[int(oo2[i]):int(oo2[i]) + got].tobytes() != want:
                 bad += 1; print(f"round {rd} damaged {i}: oracle decodes {len(want)} B, HIP {got:#x}")

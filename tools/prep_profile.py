@@ -5,7 +5,7 @@ import sys, os, ctypes
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import _data as D
+import _data as D, _batch as B
 from zstandard_amd import BatchCodec, _lib
 n, cs = 8192, 32768
 host = D.zipf_log(n * cs)
@@ -13,7 +13,7 @@ bc = BatchCodec(0); Z = _lib.lib()
 offs = np.arange(n, dtype=np.uint64) * cs; sizes = np.full(n, cs, dtype=np.uint32)
 arena, do, dsz = bc.compress_host(host, offs, sizes, 3)
 frames = np.concatenate([arena[int(do[i]):int(do[i]) + int(dsz[i])] for i in range(n)])
-fo = np.zeros(n, dtype=np.uint64); fo[1:] = np.cumsum(dsz.astype(np.uint64))[:-1]
+fo = B.layout(dsz)
 out, oo, osz = bc.decompress_host(frames, fo, dsz, sizes)
 assert (osz == cs).all()
 buf = np.zeros(n * 4096, dtype=np.uint8)
