@@ -17,6 +17,13 @@ namespace EPAM.Deltix.ZStd
         static extern int zsmi_compressBatchDevice_usingDict(IntPtr ctx, void* dSrc, ulong* srcOffsets, uint* srcSizes, uint n, void* dDst, ulong* dstOffsets, uint* dDstSizes, int level, void* dDict, UIntPtr dictSize);
         [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
         static extern int zsmi_decompressBatchHost(IntPtr ctx, void* src, ulong* srcOffsets, uint* srcSizes, uint n, void* dst, ulong* dstOffsets, uint* dstCaps, uint* dstSizes);
+        // digested decode dictionaries (include/zsmi.h: zsmi_createDDict ... zsmi_decompressBatchHost_usingDDict); declarations only
+        [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
+        static extern IntPtr zsmi_createDDict(IntPtr ctx, void* dict, UIntPtr dictSize, int* err);
+        [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
+        static extern void zsmi_freeDDict(IntPtr ddict);
+        [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
+        static extern int zsmi_decompressBatchHost_usingDDict(IntPtr ctx, void* src, ulong* srcOffsets, uint* srcSizes, uint n, void* dst, ulong* dstOffsets, uint* dstCaps, uint* dstSizes, IntPtr ddict);
 
         IntPtr ctx;
         public ZstdBatch(int device = -1)

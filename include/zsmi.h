@@ -140,10 +140,37 @@ int zsmi_decompressBatchDevice(zsmi_ctx *ctx, const void *dSrc, const uint64_t *
                                uint32_t *dDstSizes);
 
 /* The same with one dictionary for every frame of the call (dDict: device memory).  Frames decoded with a dictionary take the
- * general kernel. */
+ * general kernel (a digested dictionary, zsmi_createDDict below, puts them on the fast path). */
 int zsmi_decompressBatchDevice_usingDict(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                          uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps,
                                          uint32_t *dDstSizes, const void *dDict, size_t dictSize);
+
+/* ------------------------------------------------------------------------------------------
+ * Digested decode dictionaries (ZSTD_createDDict / ZSTD_decompress_usingDDict): a dictionary parsed, checked and laid out in device memory
+ * once - its bytes, and for a formatted dictionary its entropy tables in the form the fast decode kernels read - then used by many calls.
+ * Results per item (bytes, sizes, error codes) are those of the _usingDict calls with the same dictionary; frames that name the dictionary
+ * (or none) decode on the fast path instead of the general kernel.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zsmi_ddict zsmi_ddict;
+/* dict: raw content or a formatted dictionary (host memory), parsed and checked as zsmi_createCDict does (dictionary_corrupted in *err before
+ * anything runs on the device; memory_allocation when memory runs out).  NULL / 0: an empty DDict, whose calls are the plain calls.  Builds
+ * the device image on ctx's device and stream and waits for it, once.  NULL on failure, with the code in *err if err != NULL.  A DDict is
+ * read-only after creation: any context of the same device may use it (a context of another device: parameter_unsupported).  It must outlive
+ * the work queued with it: free it after zsmi_sync. */
+zsmi_ddict *zsmi_createDDict(zsmi_ctx *ctx, const void *dict, size_t dictSize, int *err);
+void zsmi_freeDDict(zsmi_ddict *dd);                   /* NULL: nothing */
+unsigned zsmi_getDictID_fromDDict(const zsmi_ddict *dd);   /* 0: raw content, or NULL */
+size_t zsmi_sizeofDDict(const zsmi_ddict *dd);         /* device bytes held */
+/* zsmi_decompressBatchDevice with a digested dictionary for every frame.  Queues its work and returns: no device-to-host copy, no wait for
+ * the stream.  dd == NULL: zsmi_decompressBatchDevice. */
+int zsmi_decompressBatchDevice_usingDDict(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                          uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps,
+                                          uint32_t *dDstSizes, const zsmi_ddict *dd);
+/* the host-buffer form, and the one-shot form (which runs on the current device; replaces ZSTD_decompress_usingDDict) */
+int zsmi_decompressBatchHost_usingDDict(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                        uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps,
+                                        uint32_t *dstSizes, const zsmi_ddict *dd);
+size_t zsmi_decompress_usingDDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_ddict *dd);
 
 /* Host-buffer forms: stage through device memory, run the device form, copy back, synchronise. */
 int zsmi_compressBatchHost(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,

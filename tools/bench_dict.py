@@ -6,13 +6,18 @@ alone (the first 64 chunks; absent without libzstd).  The same call with the dic
 zsmi_compressBatchDevice_usingCDict) is measured next to it in the same process: gib_s_cdict, ratio_cdict, vs_libzstd_trained_cdict, and
 gap_closed = the share of the _usingDict call's excess over libzstd that the CDict call removes.  Every rate is the median of --repeats
 timings of --steps calls; spread_* is (max - min) / median of those timings.  --kernels: per-kernel times of one call of each dictionary
-form (zsmi_enableKernelTiming)."""
+form (zsmi_enableKernelTiming).
+The decode leg runs on the frames the record has just made: dec_gib_s_dict (the _usingDict frames through zsmi_decompressBatchDevice_usingDict:
+the general kernel), dec_gib_s_ddict (the CDict frames through a DecompressionDict: the fast path) and dec_gib_s_plain (the no-dictionary
+frames of the same chunks, plain decode), GiB/s of decoded bytes; dec_min_* / dec_max_* are the slowest and fastest of the --repeats timings
+as rates, dec_spread_* their spread; ddict_over_dict and ddict_over_plain the ratios of the medians; dec_ranges_apart says that the DDict's
+slowest repeat beat the _usingDict call's fastest.  --kernels adds dec_kernels_ms_*."""
 import argparse, ctypes, json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _data as D, _oracle as O, _corpus as C
-from zstandard_amd import BatchCodec, CompressionDict, _lib
+from zstandard_amd import BatchCodec, CompressionDict, DecompressionDict, _lib
 
 FIXC = os.path.join(ROOT, "tests", "golden", "libzstd_fixtures_dict_compress.npz")
 
@@ -66,6 +71,7 @@ def main():
             for lvl in [int(x) for x in a.levels.split(",")]:
                 rec = {"class": cls, "chunk": cs, "level": lvl, "chunks": n}
                 cdict = CompressionDict(bc, dic, lvl)
+                made = {}                                             # tag -> (frames on the device, their sizes): the decode leg's input
                 for tag, dp, dn, cd in (("plain", 0, 0, None), ("dict", ddict.data_ptr(), len(dic), None), ("cdict", 0, len(dic), cdict)):
                     run = lambda: bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), lvl, dp, dn if dp else 0, cdict=cd)
                     for _ in range(2):
@@ -80,6 +86,7 @@ def main():
                     rec["spread_" + tag] = round((max(times) - min(times)) / dt, 3)
                     sizes = dsz.cpu().numpy().view(np.uint32)
                     assert (sizes < 0xFFFFFF88).all()
+                    made[tag] = (ddst.clone(), sizes.copy())
                     host = ddst[:min(n, 64) * bound].cpu().numpy()
                     for i in (0, min(n, 64) - 1):                     # spot check under oracle D
                         f = host[int(doff[i]):int(doff[i]) + int(sizes[i])].tobytes()
@@ -103,6 +110,44 @@ def main():
                             rec["kernels_ms" + ("_cdict" if cd else "")] = {k2: round(v[0] * 1e3, 3) for k2, v in bc.kernel_times().items()}
                             bc.enable_timing(False)
                 bc.sync(); cdict.close()
+                # ---- the decode leg: the frames above, back into chunk-sized slots
+                dd = DecompressionDict(bc, dic)
+                dout = torch.empty(n * cs, dtype=torch.uint8, device=dev); dosz = torch.empty(n, dtype=torch.int32, device=dev)
+                want = dsrc[:n * cs]
+                caps = np.full(n, cs, dtype=np.uint32)
+                vp = ctypes.c_void_p
+                pa = lambda x: x.ctypes.data_as(vp)
+                for tag, frames_tag in (("plain", "plain"), ("dict", "dict"), ("ddict", "cdict")):
+                    dfr, fsz = made[frames_tag]
+                    if tag == "dict":
+                        run = lambda: Z.zsmi_decompressBatchDevice_usingDict(bc.ctx, vp(dfr.data_ptr()), pa(doff), pa(fsz), n, vp(dout.data_ptr()), pa(off), pa(caps),
+                                                                             vp(dosz.data_ptr()), vp(ddict.data_ptr()), len(dic))
+                    else:
+                        run = lambda: bc.decompress_device(dfr.data_ptr(), doff, fsz, dout.data_ptr(), off, caps, dosz.data_ptr(), ddict=dd if tag == "ddict" else None)
+                    dout.zero_()
+                    for _ in range(2):
+                        run()
+                    bc.sync()
+                    assert torch.equal(dout, want) and bool((dosz == cs).all()), ("decode leg", tag)
+                    times = []
+                    for _ in range(a.repeats):
+                        bc.sync(); t0 = time.perf_counter()
+                        for _ in range(a.steps):
+                            run()
+                        bc.sync(); times.append((time.perf_counter() - t0) / a.steps)
+                    dt = float(np.median(times)); gib = n * cs / 2**30
+                    rec["dec_gib_s_" + tag] = round(gib / dt, 2)
+                    rec["dec_min_" + tag] = round(gib / max(times), 2); rec["dec_max_" + tag] = round(gib / min(times), 2)
+                    rec["dec_spread_" + tag] = round((max(times) - min(times)) / dt, 3)
+                    if a.kernels:
+                        bc.enable_timing(True); run(); bc.sync()
+                        rec["dec_kernels_ms_" + tag] = {k2: round(v[0] * 1e3, 3) for k2, v in bc.kernel_times().items()}
+                        bc.enable_timing(False)
+                bc.sync(); dd.close()
+                rec["ddict_over_dict"] = round(rec["dec_gib_s_ddict"] / rec["dec_gib_s_dict"], 3)
+                rec["ddict_over_plain"] = round(rec["dec_gib_s_ddict"] / rec["dec_gib_s_plain"], 3)
+                rec["dec_ranges_apart"] = rec["dec_min_ddict"] > rec["dec_max_dict"]
+                del made, dout, dosz
                 rec["dict_over_plain"] = round(rec["gib_s_dict"] / rec["gib_s_plain"], 3)
                 rec["cdict_over_dict"] = round(rec["gib_s_cdict"] / rec["gib_s_dict"], 3)
                 print(json.dumps(rec), flush=True)

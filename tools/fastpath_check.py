@@ -2,14 +2,16 @@
 """GPU check (run by tests/test_gpu_codec.py::test_intended_shapes_stay_on_the_decode_fast_path, in a process of its own because it loads
 the library built with the debug hooks): frames of the shapes the decoder's fast path is meant to take are decoded, and the per-item
 descriptors (ZsFastDesc.fast) are read back.  A shape that silently falls back to the general kernel decodes correctly and 4 x slower -
-only this count shows it (ELF-class frames did so for two rounds).  Prints one JSON object: shape -> [items on the fast path, items]."""
+only this count shows it (ELF-class frames did so for two rounds).  Rows "ddict ..." are dictionary frames decoded with a DecompressionDict
+(zsmi_createDDict): own CDict frames with a trained dictionary, own frames with a raw-content one, libzstd's with the trained one.
+Prints one JSON object: shape -> [items on the fast path, items]."""
 import os; os.environ["ZSMI_DEBUG_LIB"] = "1"
 import sys, ctypes, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
-import _data as D, _oracle as O, _corpus as C, _batch as B
-from zstandard_amd import BatchCodec, _lib
+import _data as D, _oracle as O, _corpus as C, _batch as B, _dicts as X, _ddict as DD
+from zstandard_amd import BatchCodec, CompressionDict, DecompressionDict, _lib
 
 
 def desc_layout(Z):
@@ -33,12 +35,20 @@ def main():
     elf = dict(C.corpus(1 << 20)).get("elf", None)
     res = {}
 
-    def run(label, chunks, own=True, lvl=3):
-        if own:
+    def run(label, chunks, own=True, lvl=3, frames=None, dic=None):
+        """frames: made by the caller (dictionary frames); dic: decoded with a DecompressionDict of it"""
+        if frames is not None:
+            pass
+        elif own:
             frames = B.cut(*bc.compress_host(*B.batch(chunks), lvl))
         else:
             frames = [O.zstd_compress(c, lvl) for c in chunks]
-        ok = B.decode_many(bc, frames, [len(c) for c in chunks], min_cap=0) == [(len(c), c) for c in chunks]
+        if dic is not None:
+            dd = DecompressionDict(bc, dic)
+            ok = DD.decode_many(bc, frames, [len(c) for c in chunks], dd) == [(len(c), c) for c in chunks]
+            dd.close()
+        else:
+            ok = B.decode_many(bc, frames, [len(c) for c in chunks], min_cap=0) == [(len(c), c) for c in chunks]
         n = len(chunks)
         buf = np.zeros(n * DESC_WORDS, dtype=np.uint32)
         rc = Z.zsmi_dbg_copyScratch(bc.ctx, 10, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
@@ -60,6 +70,20 @@ def main():
         run("libzstd 300 KB level 1", [text[i * 70000:i * 70000 + 300000] for i in range(16)], own=False, lvl=1)
         run("libzstd 1 MiB level 3 (repeated tables)", [text[i * 70000:i * 70000 + (1 << 20)] for i in range(16)], own=False)
         run("libzstd 400 KB level 9", [text[i * 70000:i * 70000 + 400000] for i in range(16)], own=False, lvl=9)
+    # dictionary frames through a digested decode dictionary
+    cls = "json_records"
+    trained, records = X.trained(cls), X.class_data(cls)
+    cd = CompressionDict(bc, trained, 3)
+    for cs, n in ((1024, 256), (4096, 64), (65536, 8)):
+        chunks = [records[i * cs:(i + 1) * cs] for i in range(n)]
+        run("ddict, own CDict frames of %d KiB, trained dictionary" % (cs >> 10), chunks, frames=B.compress_many(bc, chunks, cdict=cd), dic=trained)
+    cd.close()
+    rawdic = X.STREAM[:6000]
+    chunks = [X.STREAM[6000 + i * 4096:6000 + (i + 1) * 4096] for i in range(64)]
+    run("ddict, own frames of 4 KiB, raw-content dictionary", chunks, frames=B.compress_many(bc, chunks, 3, rawdic), dic=rawdic)
+    if X.zstd():
+        chunks = [records[i * 4096:(i + 1) * 4096] for i in range(64)]
+        run("ddict, libzstd frames of 4 KiB, trained dictionary", chunks, frames=[X.zstd_compress_dict(c, trained, 3) for c in chunks], dic=trained)
     print(json.dumps(res))
     return 0
 

@@ -106,6 +106,13 @@ def lib():
     L.zsmi_compressBatchDevice_usingCDict.restype = i32; L.zsmi_compressBatchDevice_usingCDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_compressBatchHost_usingCDict.restype = i32; L.zsmi_compressBatchHost_usingCDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_compress_usingCDict.restype = sz; L.zsmi_compress_usingCDict.argtypes = [vp, sz, vp, sz, vp]
+    L.zsmi_createDDict.restype = vp; L.zsmi_createDDict.argtypes = [vp, vp, sz, ctypes.POINTER(i32)]
+    L.zsmi_freeDDict.restype = None; L.zsmi_freeDDict.argtypes = [vp]
+    L.zsmi_getDictID_fromDDict.restype = ctypes.c_uint; L.zsmi_getDictID_fromDDict.argtypes = [vp]
+    L.zsmi_sizeofDDict.restype = sz; L.zsmi_sizeofDDict.argtypes = [vp]
+    L.zsmi_decompressBatchDevice_usingDDict.restype = i32; L.zsmi_decompressBatchDevice_usingDDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.zsmi_decompressBatchHost_usingDDict.restype = i32; L.zsmi_decompressBatchHost_usingDDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.zsmi_decompress_usingDDict.restype = sz; L.zsmi_decompress_usingDDict.argtypes = [vp, sz, vp, sz, vp]
     L.zsmi_decompressBatchHost.restype = i32; L.zsmi_decompressBatchHost.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_decompressBatchHost_usingDict.restype = i32; L.zsmi_decompressBatchHost_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
     L.zsmi_decompressBatchDevice_usingDict.restype = i32; L.zsmi_decompressBatchDevice_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
@@ -142,6 +149,8 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_compress_usingDict", "zsmi_compressBatchDevice_usingDict", "zsmi_compressBatchHost_usingDict",
            "zsmi_createCDict", "zsmi_freeCDict", "zsmi_getDictID_fromCDict", "zsmi_sizeofCDict",
            "zsmi_compressBatchDevice_usingCDict", "zsmi_compressBatchHost_usingCDict", "zsmi_compress_usingCDict",
+           "zsmi_createDDict", "zsmi_freeDDict", "zsmi_getDictID_fromDDict", "zsmi_sizeofDDict",
+           "zsmi_decompressBatchDevice_usingDDict", "zsmi_decompressBatchHost_usingDDict", "zsmi_decompress_usingDDict",
            "zsmi_packFramesDevice", "zsmi_enableKernelTiming", "zsmi_getKernelTimes", "zsmi_versionString", "zsmi_decodeScratchBytes", "zsmi_shutdown",
            "zsmi_seekableBound", "zsmi_compressSeekable", "zsmi_compressSeekableDevice", "zsmi_decompressSeekable", "zsmi_decompressSeekableDevice",
            "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo",

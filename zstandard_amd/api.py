@@ -10,6 +10,8 @@
   BatchCodec          the batch hot path on device memory (torch tensors are only a handle to device memory here).
   CompressionDict     a digested dictionary (zsmi_createCDict): parsed and laid out on the device once, used by many calls; with a
                       formatted dictionary its entropy tables code the first block of a frame where that is smaller.
+  DecompressionDict   a digested decode dictionary (zsmi_createDDict): the dictionary's bytes and, for a formatted one, its entropy tables in
+                      the fast decode kernels' form, on the device once; its calls decode dictionary frames on the fast path.
   train_dictionary, finalize_dictionary, get_dict_id
                       zstd dictionaries made on the GPU (fastCover and ZDICT_finalizeDictionary; zdict.h's parameters).
 
@@ -123,6 +125,40 @@ class CompressionDict:
     def close(self):
         if self.handle:
             self.L.zsmi_freeCDict(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecompressionDict:
+    """A digested decode dictionary (ZSTD_createDDict): `dictionary` (raw content or a formatted dictionary) parsed, checked and laid out in
+    the device memory of `codec`'s device once.  Any BatchCodec of that device may use it (ddict=): results are those of the call with the
+    dictionary's bytes, and frames that name it decode on the fast path.  It must stay open until the work queued with it is done
+    (BatchCodec.sync).  An empty dictionary makes a DecompressionDict whose calls are the plain calls."""
+
+    def __init__(self, codec, dictionary):
+        self.L = codec.L
+        err = ctypes.c_int(0)
+        dic = bytes(dictionary or b"")
+        self.handle = self.L.zsmi_createDDict(codec.ctx, dic if dic else None, len(dic), ctypes.byref(err))
+        if not self.handle:
+            raise RuntimeError(f"zsmi_createDDict: error {err.value} ({_error_name(self.L, err.value)})")
+
+    @property
+    def dict_id(self) -> int:
+        return int(self.L.zsmi_getDictID_fromDDict(self.handle))
+
+    @property
+    def device_bytes(self) -> int:
+        return int(self.L.zsmi_sizeofDDict(self.handle))
+
+    def close(self):
+        if self.handle:
+            self.L.zsmi_freeDDict(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -299,11 +335,15 @@ class BatchCodec:
         _check(getattr(self.L, name)(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss), ctypes.c_void_p(d_dst_ptr), self._p(do),
                                      ctypes.c_void_p(d_dst_sizes_ptr), *tail), name)
 
-    def decompress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, dst_caps, d_dst_sizes_ptr):
+    def decompress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, dst_caps, d_dst_sizes_ptr, ddict=None):
+        """ddict: a DecompressionDict for every frame of the call (zsmi_decompressBatchDevice_usingDDict: queued without a wait)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64); dc = np.ascontiguousarray(dst_caps, dtype=np.uint32)
-        _check(self.L.zsmi_decompressBatchDevice(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss),
-                                                 ctypes.c_void_p(d_dst_ptr), self._p(do), self._p(dc), ctypes.c_void_p(d_dst_sizes_ptr)), "zsmi_decompressBatchDevice")
+        args = (self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss), ctypes.c_void_p(d_dst_ptr), self._p(do), self._p(dc), ctypes.c_void_p(d_dst_sizes_ptr))
+        if ddict is not None:
+            _check(self.L.zsmi_decompressBatchDevice_usingDDict(*args, ddict.handle), "zsmi_decompressBatchDevice_usingDDict")
+        else:
+            _check(self.L.zsmi_decompressBatchDevice(*args), "zsmi_decompressBatchDevice")
 
     def pack_device(self, d_frames_ptr, dst_offsets, d_sizes_ptr, n, d_packed_ptr, d_packed_offsets_ptr):
         """frames sitting at dst_offsets (sizes on the device) -> one contiguous run at d_packed; d_packed_offsets[n + 1] (device, uint64)"""
@@ -350,9 +390,9 @@ class BatchCodec:
         _check(getattr(self.L, name)(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), *tail), name)
         return arena, do, dsz
 
-    def decompress_host(self, src: np.ndarray, src_offsets, src_sizes, dst_caps, dictionary: bytes = b""):
+    def decompress_host(self, src: np.ndarray, src_offsets, src_sizes, dst_caps, dictionary: bytes = b"", ddict=None):
         """dictionary: every frame is decoded with it (raw content or a formatted dictionary; ZSTD_decompress_usingDict,
-        ZStdDecompress.cs:2162)"""
+        ZStdDecompress.cs:2162).  ddict: a DecompressionDict instead (zsmi_decompressBatchHost_usingDDict)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         dc = np.ascontiguousarray(dst_caps, dtype=np.uint32)
         n = len(ss)
@@ -361,7 +401,10 @@ class BatchCodec:
             do[1:] = np.cumsum(dc.astype(np.uint64))[:-1]
         arena = np.zeros(max(int(dc.astype(np.uint64).sum()), 1), dtype=np.uint8)
         dsz = np.zeros(n, dtype=np.uint32)
-        if dictionary:
+        if ddict is not None:
+            rc = self.L.zsmi_decompressBatchHost_usingDDict(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dc), self._p(dsz),
+                                                            ddict.handle)
+        elif dictionary:
             dbuf = np.frombuffer(dictionary, dtype=np.uint8)
             rc = self.L.zsmi_decompressBatchHost_usingDict(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dc), self._p(dsz),
                                                            self._p(dbuf), len(dbuf))

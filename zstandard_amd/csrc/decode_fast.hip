@@ -53,11 +53,29 @@ struct ZsFastDesc {                               // per item, global memory, wr
     uint32_t llLog, ofLog, mlLog;
     uint32_t contentSize, hasContentSize;
     uint32_t hasChecksum, checksum;               // content checksum (low 32 bits of XXH64, ZStdDecompress.cs:2078-2082): checked by k_dec_checksum
-    uint32_t hufFlat;                             // 1: the item's Huffman table is the flat one of 2^11 entries (more long-code prefixes than the two-level table has sub-tables)
+    uint32_t hufFlat;                             // bit 0: the item's Huffman table is the flat one of 2^11 entries (more long-code prefixes than the two-level table has sub-tables);
+                                                  // bit 1 (calls with a digested dictionary only): the table is the dictionary's, staged from its image, not from the slot
     uint32_t why;                                 // which fast kernel handed the item to the general one (1 Huffman stream, 2 sequence stream, 3.. execute: tools/dec_why.py)
 };
 #define ZS_FAST_HUFTAB_BYTES (2u << ZS_FAST_HUFLOG)                       // uint16 entries
 #define ZS_FAST_SEQTAB_BYTES ((512u + 256u + 512u) * 2u)                  // LL, OF, ML cells, 2 bytes each
+// A digested decode dictionary's device image (zsmi_createDDict; filled by k_ddict_tables, read-only afterwards): what a frame decoded with
+// the dictionary starts from (ZSTD_decompress_insertDictionary :2452-2475) - the content in front of the frame, the recent offsets, and for a
+// formatted dictionary its entropy tables in exactly the form the fast kernels read: the Huffman table as k_dec_prep leaves one in a slot
+// (two-level or flat), the LL / OF / ML cells in a slot's layout.  The DD instantiations of the fast kernels take it; the others never look at it.
+struct ZsDDictImage {
+    const uint8_t *contentEnd;                    // one past the content's last byte (the dictionary's bytes stay in device memory beside the image)
+    uint32_t contentSize, dictID;                 // dictID 0: raw content
+    uint32_t rep[3];                              // {1, 4, 8} for raw content
+    uint32_t tables;                              // 1: a formatted dictionary, the sequence tables below are valid (a frame starts with fseEntropy and litEntropy set)
+    uint32_t hufLog, hufFlat, hufWide;            // hufWide: the Huffman log is above ZS_FAST_HUFLOG, no table is held - a Treeless first block goes to the general kernel
+    uint32_t seqLog[3];                           // LL, OF, ML
+    uint32_t pad[2];
+    __attribute__((aligned(16))) uint8_t hufTab[ZS_FAST_HUFTAB_BYTES];
+    __attribute__((aligned(16))) uint8_t seqTab[ZS_FAST_SEQTAB_BYTES];
+};
+#define ZS_DD_SLOT 0xFFFFFFFFu                    // k_dec_prep's "block + 1 of the slot that holds the current table": the dictionary's image
+
 // what the sequences kernel leaves per sequence, 8 bytes: where its extra bits start in the bitstream (bit position, 20 bits)
 // and its three codes (LL 6 bits at 20, ML 6 bits at 26, OF 5 bits at 32).  The execute kernel turns that into lengths and
 // offsets, 64 sequences at a time on 64 lanes; only the FSE state chain stays serial.
@@ -71,11 +89,15 @@ __device__ __forceinline__ ZsFastSeq zs_fastseq(uint32_t bitPos, uint32_t symLL,
 #ifndef ZS_PREP_MINWG
 #define ZS_PREP_MINWG 4                 // wavefronts per SIMD the prep kernel is compiled for (128 VGPRs; per 57344 frames: 2: 0.96 ms, 3: 0.97, 4: 0.97, 5: 1.02, 6: 1.04, 8: 1.10 with ~450 spilled registers; the kernel is bound by the instructions it issues)
 #endif
-template <int F>
+// DD: the call decodes with a digested dictionary (dd, its image).  A frame may name no dictionary, ID 0 or the dictionary's ID (any other: the
+// general kernel answers dictionary_wrong); with a formatted dictionary it starts with the dictionary's tables current (misc[11], misc[12] =
+// ZS_DD_SLOT): a Treeless literals section is flagged to be decoded from the image's Huffman table (no copy into the slot), a Repeat_Mode
+// sequence table is copied from the image's cells as it would be from an earlier block's slot.
+template <int F, bool DD>
 __global__ void __launch_bounds__(64 * F, ZS_PREP_MINWG)
 k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems,
            ZsFastDesc *__restrict__ descs, uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ seqTabs, uint32_t cap, uint32_t maxBlocks, uint32_t *__restrict__ seqLists,
-           uint32_t litCap, uint32_t seqCap)
+           uint32_t litCap, uint32_t seqCap, const ZsDDictImage *__restrict__ dd)
 {
     // (litCap, seqCap: literal bytes / sequences a block slot of this call holds - sized by the call's largest capacity, zsmi_api.hip; a block that
     //  wants more cannot fit its item's capacity and is left to the general kernel, which says why)
@@ -104,17 +126,23 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
 #endif
     bool ok = false; uint32_t nBlocks = 0;
     do {
-        // ---- frame header (:389-499): one frame, no dictionary ----
+        // ---- frame header (:389-499): one frame, no dictionary (DD: none, or the call's) ----
         if (srcSize < 5 + 1 + 3 || rd32(src) != 0xFD2FB528u) { ZS_PREP_WHY(__LINE__); break; }
         const uint32_t fhd = src[4];
         const uint32_t dictIDCode = fhd & 3, checksumFlag = (fhd >> 2) & 1, singleSegment = (fhd >> 5) & 1, fcsID = fhd >> 6;
-        if (dictIDCode || (fhd & 0x08)) { ZS_PREP_WHY(__LINE__); break; }
+        if ((!DD && dictIDCode) || (fhd & 0x08)) { ZS_PREP_WHY(__LINE__); break; }
+        const uint32_t didSize = DD ? (dictIDCode == 3 ? 4u : dictIDCode) : 0u;
         const uint32_t tail = checksumFlag ? 4u : 0u;              // the checksum behind the last block
         const uint32_t fcsSize = fcsID == 0 ? 0 : (fcsID == 1 ? 2 : (fcsID == 2 ? 4 : 8));
-        const uint32_t fhs = 5 + !singleSegment + fcsSize + (singleSegment && !fcsID);
+        const uint32_t fhs = 5 + !singleSegment + didSize + fcsSize + (singleSegment && !fcsID);
         if (srcSize < fhs + 3 + tail) { ZS_PREP_WHY(__LINE__); break; }
         uint32_t pos = 5;
         if (!singleSegment) { const uint32_t wl = src[pos++]; if ((wl >> 3) + 10 > 30) { ZS_PREP_WHY(__LINE__); break; } }
+        if (DD && dictIDCode) {                                     // (:632-634: a frame that names another dictionary is dictionary_wrong, the general kernel's to say)
+            const uint32_t id = dictIDCode == 1 ? (uint32_t)src[pos] : (dictIDCode == 2 ? rd16(src + pos) : rd32(src + pos));
+            pos += didSize;
+            if (id != 0 && id != dd->dictID) { ZS_PREP_WHY(__LINE__); break; }
+        }
         uint64_t fcs = ~0ull;
         if (fcsID == 0) { if (singleSegment) fcs = src[pos]; } else if (fcsID == 1) fcs = rd16(src + pos) + 256; else if (fcsID == 2) fcs = rd32(src + pos); else fcs = zs_load64(src + pos);
         if (fcs != ~0ull && fcs > 0xFFFFFFFFull) { ZS_PREP_WHY(__LINE__); break; }
@@ -128,6 +156,10 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
         //  misc[11]: block + 1 of the Huffman table's slot; misc[12]: block + 1 of the last block with sequences; misc[13]: Huffman log | flat << 8;
         //  misc[14]: raw / RLE blocks so far; misc[8..10]: the sequence tables' logs, left alone by a block without sequences)
         if (lane < 8) L.misc[8 + lane] = 0;
+        if (DD && dd->tables && lane == 0) {                        // the frame starts from the dictionary's tables (LoadEntropy :2378-2450)
+            L.misc[8] = dd->seqLog[0]; L.misc[9] = dd->seqLog[1]; L.misc[10] = dd->seqLog[2];
+            L.misc[11] = ZS_DD_SLOT; L.misc[12] = ZS_DD_SLOT; L.misc[13] = dd->hufLog | (dd->hufFlat << 8) | (dd->hufWide << 16);
+        }
         wave_sync();
         #pragma unroll 1
         for (uint32_t blk = 0; blk < maxBlocks && !fail; blk++) {
@@ -169,6 +201,8 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
             {
                 const uint32_t type = bs[0] & 3, lhl = (bs[0] >> 2) & 3;
                 if (type == 3 && L.misc[11] == 0) { ZS_PREP_WHY(__LINE__); break; }            // a repeated Huffman table without one before it: the general kernel says what is wrong
+                const bool hufOfDict = DD && type == 3 && L.misc[11] == ZS_DD_SLOT;             // the dictionary's table is still the current one
+                if (hufOfDict && (L.misc[13] >> 16)) { ZS_PREP_WHY(__LINE__); break; }           // ... and the image does not hold it (log above ZS_FAST_HUFLOG)
                 if (type >= 2) {
                     if (cSize < 5) { ZS_PREP_WHY(__LINE__); break; }
                     const uint32_t lhc = rd32(bs);
@@ -186,7 +220,7 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
                         const uint32_t flat = h >> 30; h &= 0x3FFFFFFFu;       // (readHufTableT<true> marks a flat table in bit 30)
                         if (h >= litCSize || L.hufLog > ZS_FAST_HUFLOG) { ZS_PREP_WHY(__LINE__); break; }
                         if (lane == 0) L.misc[13] = L.hufLog | (flat << 8);
-                    } else {
+                    } else if (!hufOfDict) {                               // (the dictionary's table: k_dec_huffman stages the image, nothing is copied)
                         // the table of the block that built it, into this block's slot (the whole 4 KiB: 16 bytes a lane, 4 rounds)
                         const uint4 *from = reinterpret_cast<const uint4 *>(hufTabs + ((size_t)(L.misc[11] - 1u) * cap + item) * ZS_FAST_HUFTAB_BYTES);
                         uint4 *to = reinterpret_cast<uint4 *>(ht);
@@ -198,9 +232,9 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
                         for (uint32_t u = 0; u < ZS_FAST_HUFTAB_BYTES / 16 / 64; u++) to[lane + 64 * u] = v[u];
                     }
                     wave_sync();
-                    if (lane == 0) L.misc[11] = blk + 1;
+                    if (lane == 0 && !hufOfDict) L.misc[11] = blk + 1;
                     wave_sync();
-                    DSET(hufFlat, L.misc[13] >> 8);
+                    DSET(hufFlat, DD ? (((L.misc[13] >> 8) & 1u) | (hufOfDict ? 2u : 0u)) : L.misc[13] >> 8);
                     const uint32_t cs0 = b0 + lhSize + h, csz = litCSize - h;
                     DSET(litType, 2u); DSET(litSize, litSize); DSET(hufLog, L.misc[13] & 0xFFu);
                     if (single) { DSET(nStreams, 1u); DSET(sOff[0], cs0); DSET(sLen[0], csz); DSET(sCnt[0], litSize); DSET(sOut[0], 0u); }
@@ -237,6 +271,7 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
             DState st; st.rep[0] = 1; st.rep[1] = 4; st.rep[2] = 8; st.litEntropy = 0; st.fseEntropy = seqPrev != 0; st.llRepeatOk = 0; st.hufX4 = 0;
             uint16_t *stab = reinterpret_cast<uint16_t *>(seqTabs + slot * ZS_FAST_SEQTAB_BYTES);
             const uint16_t *stabPrev = seqPrev ? reinterpret_cast<const uint16_t *>(seqTabs + ((size_t)(seqPrev - 1u) * cap + item) * ZS_FAST_SEQTAB_BYTES) : nullptr;
+            if (DD && seqPrev == ZS_DD_SLOT) stabPrev = reinterpret_cast<const uint16_t *>(dd->seqTab);
             if (seqHeadersT<true>(L, st, ip, remaining, nbSeq, stab, &L.misc[8], stabPrev)) { ZS_PREP_WHY(__LINE__); break; }      // (misc[8..10]: a repeated table keeps the log it had)
             if (nbSeq > seqCap) { ZS_PREP_WHY(__LINE__); break; }
             if (nbSeq == 0 && remaining != 0) { ZS_PREP_WHY(__LINE__); break; }
@@ -343,9 +378,9 @@ __device__ __forceinline__ void stageOwnWindow(uint32_t *win, const uint8_t *src
 template <bool FLAT, uint32_t G>
 struct HufLds { uint16_t huf[G][FLAT ? (1u << ZS_FAST_HUFLOG) : ZS_HUF2_ENTRIES]; uint32_t win[4 * G][(ZS_FAST_HUFWIN + 8) / 4 + 2]; };
 
-template <bool FLAT, uint32_t G>
+template <bool FLAT, uint32_t G, bool DD>
 __device__ __forceinline__ void zs_dec_huffman_body(HufLds<FLAT, G> &H, const uint32_t bid, const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
-              const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, uint32_t nBlk, uint32_t cap, uint32_t litStride)
+              const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, uint32_t nBlk, uint32_t cap, uint32_t litStride, const ZsDDictImage *__restrict__ dd)
 {
     const uint32_t lane = (uint32_t)zs_lane();
     const uint32_t g = lane >> 2, k = lane & 3u;
@@ -355,13 +390,14 @@ __device__ __forceinline__ void zs_dec_huffman_body(HufLds<FLAT, G> &H, const ui
     const uint32_t blk = bid / groupsPerBlk, bx = bid - blk * groupsPerBlk;
     (void)nBlk;
     const uint32_t item = bx * G + g;
-    bool mine = false; uint32_t dtLog = 1, n = 0, size = 0;
+    bool mine = false; uint32_t dtLog = 1, n = 0, size = 0, ofDict = 0;       // ofDict (DD): the item's table is the dictionary's
     const uint8_t *src = srcAll; uint8_t *out = litScratchAll;
     const size_t slot0 = (size_t)blk * cap;                          // this block index's descriptors, tables, literal scratch
     if (g < G && item < nItems) {
         const ZsFastDesc *d = descs + slot0 + item;
-        if (descs[item].fast && d->fast && d->litType == 2 && k < d->nStreams && (d->hufFlat != 0) == FLAT) {
+        if (descs[item].fast && d->fast && d->litType == 2 && k < d->nStreams && ((DD ? d->hufFlat & 1u : d->hufFlat) != 0) == FLAT) {
             mine = true; dtLog = d->hufLog; n = d->sCnt[k]; size = d->sLen[k];
+            if (DD) ofDict = d->hufFlat >> 1;
             src = srcAll + items[item].srcOff + d->sOff[k];
             out = litScratchAll + (slot0 + item) * litStride + d->sOut[k];
         }
@@ -373,6 +409,7 @@ __device__ __forceinline__ void zs_dec_huffman_body(HufLds<FLAT, G> &H, const ui
         const uint32_t log2 = wave_get(mine ? dtLog : 0u, (int)(gg * 4));        // stream 0 of the item exists whenever any does
         if (!log2) continue;
         const uint32_t *ht = reinterpret_cast<const uint32_t *>(hufTabs + (slot0 + it2) * ZS_FAST_HUFTAB_BYTES);
+        if (DD && wave_get(ofDict, (int)(gg * 4))) ht = reinterpret_cast<const uint32_t *>(dd->hufTab);     // one image for every item: hot in L2
         uint32_t *dstw = reinterpret_cast<uint32_t *>(H.huf[gg]);
         {   // 5 (flat: 16) dwords per lane, the loads issued together
             constexpr uint32_t words = (FLAT ? (1u << ZS_FAST_HUFLOG) : ZS_HUF2_ENTRIES) / 2, per = (words + 63) / 64;
@@ -590,13 +627,49 @@ __device__ __forceinline__ void zs_dec_sequences_body(SeqDecLds<LOG9, G> &S, con
 #ifndef ZS_EXEC_ROUNDS
 #define ZS_EXEC_ROUNDS 3                // rounds of pointer jumping a tile's matches get (what is left after them stays a dependent match)
 #endif
-__device__ __forceinline__ void execTileMatchesFast(uint32_t mdst, uint32_t ml, uint32_t off, uint8_t *dstBase, uint32_t tileStart, uint32_t safeEnd, uint32_t *lds3)
+// DD: a source in front of the output's first byte lies in the dictionary's content, which ends at dictEnd (the ext-dict case of ExecSequence
+// :1290-1315, execTileT<true>): those bytes are copied first - they depend on no other match, so every such match goes at once - and what is
+// left of a match that runs over the content's end continues at the output's first byte: an ordinary match with source 0, which takes the
+// passes below (it overlaps its destination when it is longer than its distance from the output's start).
+template <bool DD>
+__device__ __forceinline__ void execTileMatchesFast(uint32_t mdst, uint32_t ml, uint32_t off, uint8_t *dstBase, uint32_t tileStart, uint32_t safeEnd, uint32_t *lds3, const uint8_t *dictEnd)
 {
     // Every piece below is an instruction only if some lane needs it, and short matches share the first load (a vector-memory instruction
     // costs a CU ~7 ns with a few lanes active, ~19 ns with all 64: tools/probe/vmem_rate.hip; the rounds themselves are latency).
     const uint32_t lane = (uint32_t)zs_lane();
+    const bool has = ml != 0;                                            // (DD: a match wholly from the dictionary keeps its place among the destinations)
+    if (DD) {
+        const bool inDict = ml && off > mdst;
+        if (__ballot(inDict)) {
+            const uint32_t beyond = off - mdst;                          // bytes of the source in front of the output's first byte (<= the content's size: pass A)
+            const uint32_t n = inDict ? min(ml, beyond) : 0u;
+            const uint8_t *s = dictEnd - (inDict ? beyond : 0u);
+            uint8_t *d = dstBase + mdst;
+            if (n && n <= 32) {                                          // a lane each: 8-byte pieces at min(8 k, n - 8), as copyShort below
+                if (n >= 8) {
+                    const uint32_t lastAt = n - 8;
+                    uint64_t v[4];
+                    #pragma unroll
+                    for (uint32_t k = 0; k < 4; k++) v[k] = (8 * k < n) ? zs_load64(s + min(8 * k, lastAt)) : 0ull;
+                    #pragma unroll
+                    for (uint32_t k = 0; k < 4; k++) if (8 * k < n) __builtin_memcpy(d + min(8 * k, lastAt), &v[k], 8);
+                } else if (n >= 4) {
+                    const uint32_t x0 = zs_load32(s), x1 = zs_load32(s + n - 4);
+                    __builtin_memcpy(d, &x0, 4); __builtin_memcpy(d + n - 4, &x1, 4);
+                } else for (uint32_t j = 0; j < n; j++) d[j] = s[j];
+            }
+            for (uint64_t lm = __ballot(n > 32); lm; lm &= lm - 1) {     // a long one by the whole wavefront
+                const int t = __builtin_ctzll(lm);
+                const uint32_t n2 = wave_get(n, t), d2 = wave_get(mdst, t);
+                const uint8_t *s2 = dictEnd - wave_get(beyond, t);
+                for (uint32_t j = lane * 8u; j < n2; j += 512u) { const uint32_t jj = min(j, n2 - 8u); const uint64_t v = zs_load64(s2 + jj); __builtin_memcpy(dstBase + d2 + jj, &v, 8); }
+            }
+            if (inDict) { mdst += n; ml -= n; off = mdst; }              // the rest: from the output's first byte
+            wave_mem_sync();
+        }
+    }
     uint32_t msrc = mdst - off;
-    lds3[lane] = ml ? mdst : 0xFFFFFFFFu;                                // the tile's match destinations, ascending over the lanes; lanes without a sequence behind every position
+    lds3[lane] = (DD ? has : ml != 0) ? mdst : 0xFFFFFFFFu;                                // the tile's match destinations, ascending over the lanes; lanes without a sequence behind every position
     // A match that reads this tile's own output waits for the matches that write it: a memory round trip per level of that dependence
     // (measured on the bench frames: 24 such matches a tile, 8.7 rounds).  Most of those sources lie INSIDE the destination of one earlier
     // match of the tile, whose bytes are a copy themselves: the reader takes them from that match's source instead (and so on: every lane
@@ -721,13 +794,13 @@ __device__ __forceinline__ void execTileMatchesFast(uint32_t mdst, uint32_t ml, 
 }
 
 // the kernels over the two bodies: each class of the Huffman and of the sequences decoding as a launch of its own ...
-template <bool FLAT, uint32_t G>
+template <bool FLAT, uint32_t G, bool DD>
 __global__ void __launch_bounds__(64)
 k_dec_huffman(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
-              const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, uint32_t nBlk, uint32_t cap, uint32_t litStride)
+              const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, uint32_t nBlk, uint32_t cap, uint32_t litStride, const ZsDDictImage *__restrict__ dd)
 {
     __shared__ __attribute__((aligned(16))) HufLds<FLAT, G> H;
-    zs_dec_huffman_body<FLAT, G>(H, blockIdx.x, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride);
+    zs_dec_huffman_body<FLAT, G, DD>(H, blockIdx.x, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, dd);
 }
 template <bool LOG9, uint32_t G>
 __global__ void __launch_bounds__(64)
@@ -743,15 +816,16 @@ k_dec_sequences(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict_
 // streams do not depend on each other - side by side they take the longer chain's time.  (Two streams for the same: 0.4 ms SLOWER, the
 // cross-stream waits cost more than the overlap brought.)  The grid is the four grids one behind the other; the LDS is the largest of the four
 // images (37376 B: fewer workgroups a CU than the Huffman kernel's 30 KiB allows, which is why large calls keep the separate launches).
+template <bool DD>
 __global__ void __launch_bounds__(64)
 k_dec_entropy(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
               const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, const uint8_t *__restrict__ seqTabs, ZsFastSeq *__restrict__ seqOutAll,
-              uint32_t nBlk, uint32_t cap, const uint32_t *__restrict__ seqLists, uint32_t litStride, uint32_t seqCap, uint32_t gridH0, uint32_t gridH1, uint32_t gridS0)
+              uint32_t nBlk, uint32_t cap, const uint32_t *__restrict__ seqLists, uint32_t litStride, uint32_t seqCap, uint32_t gridH0, uint32_t gridH1, uint32_t gridS0, const ZsDDictImage *__restrict__ dd)
 {
     __shared__ __attribute__((aligned(16))) union U_ { HufLds<false, ZS_FAST_GROUP> h0; HufLds<true, 8u> h1; SeqDecLds<false, ZS_FAST_SEQGROUP_SMALL> s0; SeqDecLds<true, 4u> s1; } U;
     const uint32_t b = blockIdx.x;
-    if (b < gridH0) zs_dec_huffman_body<false, ZS_FAST_GROUP>(U.h0, b, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride);
-    else if (b < gridH0 + gridH1) zs_dec_huffman_body<true, 8u>(U.h1, b - gridH0, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride);
+    if (b < gridH0) zs_dec_huffman_body<false, ZS_FAST_GROUP, DD>(U.h0, b, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, dd);
+    else if (b < gridH0 + gridH1) zs_dec_huffman_body<true, 8u, DD>(U.h1, b - gridH0, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, dd);
     else if (b < gridH0 + gridH1 + gridS0) zs_dec_sequences_body<false, ZS_FAST_SEQGROUP_SMALL>(U.s0, b - gridH0 - gridH1, srcAll, items, nItems, descs, seqTabs, seqOutAll, nBlk, cap, seqLists, seqCap);
     else zs_dec_sequences_body<true, 4u>(U.s1, b - gridH0 - gridH1 - gridS0, srcAll, items, nItems, descs, seqTabs, seqOutAll, nBlk, cap, seqLists, seqCap);
 }
@@ -764,11 +838,13 @@ k_dec_entropy(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ 
 // wavefronts per SIMD the kernel is compiled for: 6 = 80 VGPRs (9 spilled), 7 = 72 (more spills).  Per 57344 frames of 32 KiB: 5: 3.79 ms, 6: 3.57,
 // 7: 3.41, 8: 3.65; per 16384 frames of 128 KiB: 6: 5.42, 7: 5.57 - so a call of one-block items takes the 7 form, any other the 6 form (MW); the 8 form (64 VGPRs) only
 // where it turns two rounds of wavefronts into one (zsmi_api.hip)
-template <int F, int MW>
+// DD (a call with a digested dictionary): the recent offsets start from the dictionary's, an offset may reach its content's size beyond the output's
+// first byte (:1290), and the match pass reads such sources from the content's end (execTileMatchesFast<true>).
+template <int F, int MW, bool DD>
 __global__ void __launch_bounds__(64 * F, MW)
 k_dec_execute(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
               ZsFastSeq *seqAll, uint8_t *__restrict__ litScratchAll, uint8_t *dstAll, uint32_t *__restrict__ dstSizes, uint32_t cap, uint32_t slots,
-              uint32_t litStride, uint32_t seqCap)
+              uint32_t litStride, uint32_t seqCap, const ZsDDictImage *__restrict__ dd)
 {
     __shared__ uint32_t tiles[F][3][64];
     __shared__ uint32_t codeTabs[36 + 53];                                      // base | extra bits << 24 of the LL / ML codes
@@ -795,6 +871,9 @@ k_dec_execute(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ 
     const uint64_t oend = it.dstCap;
     uint64_t op = 0; bool bad = false; uint32_t why = 0;
     uint32_t rep0 = 1, rep1 = 4, rep2 = 8;                                      // the list carried from tile to tile and block to block (lane 0 holds it)
+    if (DD) { rep0 = dd->rep[0]; rep1 = dd->rep[1]; rep2 = dd->rep[2]; }
+    const uint32_t dictSize = DD ? dd->contentSize : 0u;
+    const uint8_t *dictEnd = DD ? dd->contentEnd : nullptr;
     #pragma unroll 1
     for (uint32_t blk = 0; blk < slots && !bad; blk++) {
     const size_t slot = (size_t)blk * cap + itemU;
@@ -913,7 +992,7 @@ k_dec_execute(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ 
             if (lane < T) {
                 if ((uint64_t)ll + ml > oend - outStart64 || outStart64 > oend) e = true;
                 else if (ll > d.litSize - litStart || litStart > d.litSize) e = true;
-                else if (off > outStart64 + ll || off >= (1u << 29) || ml >= (1u << 17) || ll + ml >= (1u << 18)) e = true;
+                else if (off > outStart64 + ll + dictSize || off >= (1u << 29) || ml >= (1u << 17) || ll + ml >= (1u << 18)) e = true;
                 else {
                     seqs[t0 + lane] = (uint64_t)(ll + ml) | ((uint64_t)ml << 18) | ((uint64_t)off << 35);
                     const uint32_t ms = (uint32_t)outStart64 + ll - blockStart32, me = ms + ml;            // the match, relative to the block's output
@@ -1021,7 +1100,7 @@ k_dec_execute(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ 
                 const uint64_t r = (t0 + lane < d.nbSeq) ? seqs[t0 + lane] : 0ull;
                 const uint32_t tot = (uint32_t)r & 0x3FFFFu, ml = (uint32_t)(r >> 18) & 0x1FFFFu, off = (uint32_t)(r >> 35);
                 const uint32_t incl = wave_incl_scan(tot);
-                execTileMatchesFast(pos + incl - ml, ml, off, dstBase, pos, (uint32_t)oend, &tiles[w][0][0]);
+                execTileMatchesFast<DD>(pos + incl - ml, ml, off, dstBase, pos, (uint32_t)oend, &tiles[w][0][0], dictEnd);
                 pos += wave_last(incl);
             }
             op = blockEnd;
@@ -1052,4 +1131,58 @@ k_dec_checksum(const ZsDecItem *__restrict__ items, uint32_t nItems, const ZsFas
     if (!__ballot(work)) return;
     const uint64_t h = xxh64_quad(dstAll + items[item].dstOff, work ? size : 0u);     // (whole quads take part: a quad without work hashes nothing)
     if (work && (threadIdx.x & 3u) == 0 && (uint32_t)h != d->checksum) dstSizes[item] = ZE(E_checksum_wrong);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_ddict_tables : one wavefront, once per digested decode dictionary (zsmi_createDDict).  The host has parsed and checked the dictionary
+// (parseCompressDict: what LoadEntropy :2378-2450 refuses is refused there) and hands over where the content starts, the ID and the recent
+// offsets; a formatted dictionary's tables are built here with the routines k_dec_prep builds a block's with, from the dictionary's own
+// bytes: the form is the slots' by construction.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64)
+k_ddict_tables(const uint8_t *__restrict__ dict, uint32_t dictBytes, uint32_t contentOff, uint32_t dictID, uint32_t rep0, uint32_t rep1, uint32_t rep2,
+               ZsDDictImage *__restrict__ img)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char LSraw[(ZS_DLDS_PREP + 15) & ~15u];
+    DLds &L = *reinterpret_cast<DLds *>(LSraw);
+    const uint32_t lane = (uint32_t)zs_lane();
+    uint32_t tables = 0, hufLog = 0, hufFlat = 0, hufWide = 0;
+    if (contentOff >= 8 + 12 && contentOff <= dictBytes) {
+        const uint8_t *p = dict + 8, *const pend = dict + contentOff - 12;      // the entropy section: Huffman description, then the OF, ML, LL counts
+        const uint32_t first = p[0], hs = first >= 128 ? (first - 127 + 1) / 2 + 1 : first + 1;      // (EntropyCommon.cs:215-225: the description's size)
+        const uint32_t h = readHufTableT<true>(L, p, (uint32_t)(pend - p), reinterpret_cast<uint16_t *>(img->hufTab), ZS_FAST_HUFLOG);
+        if (isErr(h)) hufWide = 1;                                               // a table of 2^12: not held
+        else { hufFlat = h >> 30; hufLog = L.hufLog; }
+        wave_sync();
+        p += hs;
+        tables = 1;
+        uint16_t *stab = reinterpret_cast<uint16_t *>(img->seqTab);
+        for (int t = 0; t < 3 && tables; t++) {
+            const uint32_t maxS = t == 0 ? 31 : (t == 1 ? 52 : 35), maxLog = t == 0 ? 8 : 9;
+            const uint32_t at = t == 0 ? 512u : (t == 1 ? 768u : 0u), slot = t == 0 ? 1u : (t == 1 ? 2u : 0u);
+            const uint32_t left = p < pend ? (uint32_t)(pend - p) : 0u;
+            hw_stage(L.u.tb.hdrWin, p, left);
+            if (lane == 0) {
+                uint32_t tableLog = 0, max = maxS;
+                const uint32_t nc = readNCount(L.u.tb.norm, &max, &tableLog, L.u.tb.hdrWin, left, 0);
+                L.misc[0] = (isErr(nc) || max > maxS || tableLog > maxLog) ? 1u : 0u; L.misc[1] = nc; L.misc[3] = max; L.misc[4] = tableLog;
+            }
+            wave_sync();
+            if (L.misc[0]) { tables = 0; break; }                               // (the host's parse refuses these: no table, every such frame to the general kernel)
+            const uint32_t adv = L.misc[1], bmax = L.misc[3], blog = L.misc[4];
+            buildSeqTableWave(L, L.LL.cells, &L.LL.tableLog, bmax, blog);
+            wave_sync();
+            const uint32_t log = L.LL.tableLog;
+            for (uint32_t i = lane; i < (1u << log); i += 64) { const SeqSym c = L.LL.cells[i]; stab[at + i] = (uint16_t)zs_fastcell(c.nextState, c.nbBits, c.sym); }
+            if (lane == 0) img->seqLog[slot] = log;
+            wave_sync();
+            p += adv;
+        }
+    }
+    if (lane == 0) {
+        img->contentEnd = dict + dictBytes; img->contentSize = dictBytes - contentOff; img->dictID = dictID;
+        img->rep[0] = rep0; img->rep[1] = rep1; img->rep[2] = rep2;
+        img->tables = tables; img->hufLog = hufLog; img->hufFlat = hufFlat; img->hufWide = hufWide || !tables;
+        if (!tables) { img->seqLog[0] = 0; img->seqLog[1] = 0; img->seqLog[2] = 0; }
+    }
 }

@@ -20,6 +20,7 @@
 #include <condition_variable>
 #include <map>
 #include <mutex>
+#include <new>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -672,7 +673,8 @@ extern "C" int zsmi_compressBatchDevice_usingCDict(zsmi_ctx *c, const void *dSrc
 //   + Huffman table 4 KiB + sequence tables 2.5 KiB + a descriptor                     -> 32 KiB items: ~125 KiB an item (round 3: 263 KiB whatever the capacity)
 // A block that wants more than its slot holds cannot fit its item's capacity: k_dec_prep leaves it to the general kernel, which reports it.
 struct DecodePlan {
-    bool fast;                                        // the fast path runs: not under ZSMI_DEC_FAST=0, not for a dictionary call (frames that name one go to the general kernel)
+    bool fast;                                        // the fast path runs: not under ZSMI_DEC_FAST=0, not for a _usingDict call (frames that name a dictionary go to the general
+                                                      // kernel; a digested dictionary, zsmi_ddict, brings the image the fast kernels' dictionary forms need)
     uint32_t maxBlocks, descSlots;                    // block slots an item; descriptors an item (>= 2)
     uint32_t blockCap, litStride, litCap, seqCap;     // a slot: the bytes its block may regenerate, its literal stride and bytes, its sequences
     uint32_t pool, cap;                               // wavefronts of the general kernel's pool (whole workgroups); items in flight
@@ -716,10 +718,10 @@ bool zsmi_ctx::DecodeScratch::reserve(const DecodePlan &p)
 // The budget: a call whose buffers all fit asks the runtime nothing (the one-shot path).  When any buffer must grow, the scratch gets half of the
 // free device memory and of what the context holds: first the slots per item go back to 2 and 1, then the items in flight are cut down (never
 // below one sub-batch of 64, never above n).
-static DecodePlan planDecode(zsmi_ctx *c, const uint32_t *dstCaps, uint32_t n, bool useDict)
+static DecodePlan planDecode(zsmi_ctx *c, const uint32_t *dstCaps, uint32_t n, bool generalOnly)
 {
     DecodePlan p;
-    p.fast = c->decodeFast && !useDict; p.maxBlocks = 1;
+    p.fast = c->decodeFast && !generalOnly; p.maxBlocks = 1;
     uint32_t bigItems = 0, needBlocks = 1, maxCapBytes = 0;
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t nb = (uint32_t)(((uint64_t)dstCaps[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX);
@@ -788,16 +790,59 @@ static int uploadDecodeItems(zsmi_ctx *c, const uint64_t *srcOffsets, const uint
     return 0;
 }
 
+// The fast path's launches for a sub-batch of cnt items (dI) in the context's scratch: k_dec_prep, the entropy stage, k_dec_execute,
+// k_dec_checksum.  DD: the call has a digested dictionary - the dictionary forms of the kernels that need it, with its image img.
+template <bool DD>
+static void launchFastDecode(zsmi_ctx *c, const DecodePlan &p, const DecodeShape &shape, const uint8_t *src, const ZsDecItem *dI, uint32_t cnt, void *dDst,
+                             uint32_t *dDstSizes, uint32_t *classes, const ZsDDictImage *img)
+{
+    zsmi_ctx::DecodeScratch &S = c->dec;
+    const uint32_t mb = p.maxBlocks;
+    ZsFastDesc *dD = (ZsFastDesc *)S.dFastDesc.p;
+    LAUNCH(c, "k_dec_prep", (k_dec_prep<ZS_DEC_GROUP, DD>), dim3((cnt + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, dD,
+           (uint8_t *)S.dHufTabs.p, (uint8_t *)S.dSeqTabs.p, p.cap, mb, classes, p.litCap, p.seqCap, img);
+    // every block index of the items in one launch per kernel class (the grid: mb runs of the items' groups; a wavefront whose items have no such
+    // block leaves at once)
+    const uint32_t gH0 = ((cnt + ZS_FAST_GROUP - 1) / ZS_FAST_GROUP) * mb, gH1 = ((cnt + 7) / 8) * mb;
+    const uint32_t gS0 = ((cnt + ZS_FAST_SEQGROUP_SMALL - 1) / ZS_FAST_SEQGROUP_SMALL) * mb, gS1 = ((cnt + 3) / 4) * mb;
+    if (shape.fused) {
+        // the four entropy launches as one (k_dec_entropy), the 2.5 KiB sequence class at 4 items a wavefront as below
+        LAUNCH(c, "k_dec_entropy", k_dec_entropy<DD>, dim3(gH0 + gH1 + gS0 + gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p,
+               (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.litStride, p.seqCap, gH0, gH1, gS0, img);
+    } else {
+        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<false, ZS_FAST_GROUP, DD>), dim3(gH0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride, img);
+        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<true, 8u, DD>), dim3(gH1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride, img);
+        LAUNCH(c, "k_dec_sequences", (k_dec_sequences<false, ZS_FAST_SEQGROUP_SMALL>), dim3(gS0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
+               mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, 0xFFFFFFFFu);
+        // the 2.5 KiB table class (blocks of > 2048 sequences: sources, tables, binaries at 32 KiB; the 64 KiB blocks of 128 KiB frames).  How many blocks of a call
+        // are in it only the device knows (k_dec_prep's list), and it decides the shape: 16 items a wavefront when the class holds most of a large call (the
+        // wavefront's instructions are what the kernel costs: 57344 frames of Python sources 4.00 -> 3.78 ms, of a binary table 4.99 -> 4.00), 4 a wavefront
+        // when it is a fraction of it (libzstd's 32 KiB frames: 9 % of the blocks; fewer, emptier wavefronts finish sooner: 3.8 vs 5.2 ms) or the call is small.
+        // Both shapes are launched; each looks at the list's length and leaves at once when the other one serves it.
+        LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, ZS_FAST_SEQGROUP>), dim3(((cnt + ZS_FAST_SEQGROUP - 1) / ZS_FAST_SEQGROUP) * mb), dim3(64), 0, src, dI, cnt, dD,
+               (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.seqCap, ZS_FAST_SEQGROUP_MANY, 0xFFFFFFFFu);
+        LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, 4u>), dim3(gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
+               mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, ZS_FAST_SEQGROUP_MANY);
+    }
+    const auto execute = shape.executeWaves == 6 ? k_dec_execute<4, 6, DD> : (shape.executeWaves == 8 ? k_dec_execute<4, 8, DD> : k_dec_execute<4, 7, DD>);
+    LAUNCH(c, "k_dec_execute", execute, dim3((cnt + 3) / 4), dim3(256), 0, src, dI, cnt, dD, (ZsFastSeq *)S.dSeqOut.p,
+           (uint8_t *)S.dLitScratch.p, (uint8_t *)dDst, dDstSizes, p.cap, p.descSlots, p.litStride, p.seqCap, img);
+    LAUNCH(c, "k_dec_checksum", k_dec_checksum, dim3((cnt + 15) / 16), dim3(64), 0, dI, cnt, (const ZsFastDesc *)dD, (const uint8_t *)dDst, dDstSizes);
+}
+
+// dDict / dictSize: the call's dictionary in device memory (nullptr: none).  img: a digested dictionary's image of those bytes (zsmi_ddict) - with it the
+// call takes the fast path; without it a dictionary call is the general kernel's alone.
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
-                                     const void *dDict, uint32_t dictSize)
+                                     const void *dDict, uint32_t dictSize, const ZsDDictImage *img)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
     if (const int e = uploadDecodeItems(c, srcOffsets, srcSizes, n, dstOffsets, dstCaps)) return e;
     const bool useDict = dDict != nullptr && dictSize != 0;
-    const DecodePlan p = planDecode(c, dstCaps, n, useDict);
+    if (!useDict) img = nullptr;
+    const DecodePlan p = planDecode(c, dstCaps, n, useDict && !img);
     zsmi_ctx::DecodeScratch &S = c->dec;
     if (!S.reserve(p)) return ZSMI_error_memory_allocation;
     const uint8_t *src = (const uint8_t *)dSrc;
@@ -813,35 +858,8 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
             // items that are one frame of up to mb blocks: entropy decoding lane-parallel across 16 items per wavefront (decode_fast.hip); whatever
             // those kernels do not take or reject is left to the general kernel below
             if (hipMemsetAsync(lists, 0, DecLists::kClassLists * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-            LAUNCH(c, "k_dec_prep", (k_dec_prep<ZS_DEC_GROUP>), dim3((cnt + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, dD,
-                   (uint8_t *)S.dHufTabs.p, (uint8_t *)S.dSeqTabs.p, p.cap, mb, classes, p.litCap, p.seqCap);
-            // every block index of the items in one launch per kernel class (the grid: mb runs of the items' groups; a wavefront whose items have no such
-            // block leaves at once)
-            const uint32_t gH0 = ((cnt + ZS_FAST_GROUP - 1) / ZS_FAST_GROUP) * mb, gH1 = ((cnt + 7) / 8) * mb;
-            const uint32_t gS0 = ((cnt + ZS_FAST_SEQGROUP_SMALL - 1) / ZS_FAST_SEQGROUP_SMALL) * mb, gS1 = ((cnt + 3) / 4) * mb;
-            if (shape.fused) {
-                // the four entropy launches as one (k_dec_entropy), the 2.5 KiB sequence class at 4 items a wavefront as below
-                LAUNCH(c, "k_dec_entropy", k_dec_entropy, dim3(gH0 + gH1 + gS0 + gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p,
-                       (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.litStride, p.seqCap, gH0, gH1, gS0);
-            } else {
-                LAUNCH(c, "k_dec_huffman", (k_dec_huffman<false, ZS_FAST_GROUP>), dim3(gH0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride);
-                LAUNCH(c, "k_dec_huffman", (k_dec_huffman<true, 8u>), dim3(gH1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride);
-                LAUNCH(c, "k_dec_sequences", (k_dec_sequences<false, ZS_FAST_SEQGROUP_SMALL>), dim3(gS0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
-                       mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, 0xFFFFFFFFu);
-                // the 2.5 KiB table class (blocks of > 2048 sequences: sources, tables, binaries at 32 KiB; the 64 KiB blocks of 128 KiB frames).  How many blocks of a call
-                // are in it only the device knows (k_dec_prep's list), and it decides the shape: 16 items a wavefront when the class holds most of a large call (the
-                // wavefront's instructions are what the kernel costs: 57344 frames of Python sources 4.00 -> 3.78 ms, of a binary table 4.99 -> 4.00), 4 a wavefront
-                // when it is a fraction of it (libzstd's 32 KiB frames: 9 % of the blocks; fewer, emptier wavefronts finish sooner: 3.8 vs 5.2 ms) or the call is small.
-                // Both shapes are launched; each looks at the list's length and leaves at once when the other one serves it.
-                LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, ZS_FAST_SEQGROUP>), dim3(((cnt + ZS_FAST_SEQGROUP - 1) / ZS_FAST_SEQGROUP) * mb), dim3(64), 0, src, dI, cnt, dD,
-                       (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.seqCap, ZS_FAST_SEQGROUP_MANY, 0xFFFFFFFFu);
-                LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, 4u>), dim3(gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
-                       mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, ZS_FAST_SEQGROUP_MANY);
-            }
-            const auto execute = shape.executeWaves == 6 ? k_dec_execute<4, 6> : (shape.executeWaves == 8 ? k_dec_execute<4, 8> : k_dec_execute<4, 7>);
-            LAUNCH(c, "k_dec_execute", execute, dim3((cnt + 3) / 4), dim3(256), 0, src, dI, cnt, dD, (ZsFastSeq *)S.dSeqOut.p,
-                   (uint8_t *)S.dLitScratch.p, (uint8_t *)dDst, dDstSizes + i0, p.cap, p.descSlots, p.litStride, p.seqCap);
-            LAUNCH(c, "k_dec_checksum", k_dec_checksum, dim3((cnt + 15) / 16), dim3(64), 0, dI, cnt, (const ZsFastDesc *)dD, (const uint8_t *)dDst, dDstSizes + i0);
+            if (img) launchFastDecode<true>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, img);
+            else launchFastDecode<false>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, nullptr);
             // the items the fast path did not finish, listed for the general kernel
             left = lists + DecLists::leftList((size_t)p.cap * mb);
             LAUNCH(c, "k_dec_collect", k_dec_collect, dim3((cnt + 255) / 256), dim3(256), 0, &dD->fast, (uint32_t)(sizeof(ZsFastDesc) / sizeof(uint32_t)), cnt, left, leftCount);
@@ -867,6 +885,64 @@ extern "C" int zsmi_decompressBatchDevice_usingDict(zsmi_ctx *c, const void *dSr
 {
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
     return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, dDict, (uint32_t)dictSize);
+}
+
+// ---- digested decode dictionaries (ZSTD_createDDict / ZSTD_decompress_usingDDict): parsed and checked once on the host, the bytes and the image
+// the fast kernels' dictionary forms read (ZsDDictImage, k_ddict_tables) kept in device memory.  Read-only after creation: any context of the
+// same device may use it, from any thread.  A call with one queues its work and returns - nothing is read back, nothing waited for - and its
+// dictionary frames take the fast path; what the fast kernels give up goes to k_decode_frames_dict with the same bytes, as in a _usingDict call. ----
+struct zsmi_ddict {
+    int device = 0;
+    bool empty = false;                  // no bytes: its calls are the plain calls
+    uint32_t dictID = 0, dictSize = 0;
+    DevBuf dBytes, dImg;
+};
+extern "C" zsmi_ddict *zsmi_createDDict(zsmi_ctx *c, const void *dict, size_t dictSize, int *err)
+{
+    int code = 0;
+    zsmi_ddict *dd = nullptr;
+    do {
+        if (!c) { code = ZSMI_error_init_missing; break; }
+        if (dictSize > 0xFFFFFFFFull) { code = ZSMI_error_dictionary_corrupted; break; }
+        dd = new (std::nothrow) zsmi_ddict();
+        if (!dd) { code = ZSMI_error_memory_allocation; break; }
+        dd->device = c->device;
+        if (!dict || dictSize == 0) { dd->empty = true; break; }
+        ZsCompressDict d;
+        if ((code = parseCompressDict((const uint8_t *)dict, dictSize, d))) break;
+        dd->dictID = d.dictID; dd->dictSize = (uint32_t)dictSize;
+        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        if (!dd->dBytes.reserve(dictSize + 64) || !dd->dImg.reserve(sizeof(ZsDDictImage))) { code = ZSMI_error_memory_allocation; break; }
+        if (hipMemcpyAsync(dd->dBytes.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        LAUNCH(c, "k_ddict_tables", k_ddict_tables, dim3(1), dim3(64), 0, (const uint8_t *)dd->dBytes.p, (uint32_t)dictSize, d.contentOff, d.dictID,
+               d.rep[0], d.rep[1], d.rep[2], (ZsDDictImage *)dd->dImg.p);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
+    } while (0);
+    if (code) { delete dd; dd = nullptr; }
+    if (err) *err = code;
+    return dd;
+}
+extern "C" void zsmi_freeDDict(zsmi_ddict *dd) { delete dd; }
+extern "C" unsigned zsmi_getDictID_fromDDict(const zsmi_ddict *dd) { return dd ? dd->dictID : 0; }
+extern "C" size_t zsmi_sizeofDDict(const zsmi_ddict *dd) { return dd ? dd->dBytes.cap + dd->dImg.cap : 0; }
+// What a zsmi_ddict * argument asks of a call on context c - 0, with bytes / size / img set (all null: the plain call, for a null ddict or one
+// without bytes); or the error (a dictionary digested on another device: parameter_unsupported)
+static int resolveDDict(const zsmi_ctx *c, const zsmi_ddict *dd, const void *&bytes, uint32_t &size, const ZsDDictImage *&img)
+{
+    bytes = nullptr; size = 0; img = nullptr;
+    if (!dd) return 0;
+    if (!c) return ZSMI_error_init_missing;
+    if (dd->device != c->device) return ZSMI_error_parameter_unsupported;
+    if (!dd->empty) { bytes = dd->dBytes.p; size = dd->dictSize; img = (const ZsDDictImage *)dd->dImg.p; }
+    return 0;
+}
+extern "C" int zsmi_decompressBatchDevice_usingDDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                     uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
+                                                     const zsmi_ddict *dd)
+{
+    const void *bytes; uint32_t size; const ZsDDictImage *img;
+    if (const int e = resolveDDict(c, dd, bytes, size, img)) return e;
+    return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, bytes, size, img);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -997,16 +1073,20 @@ extern "C" int zsmi_compressBatchHost_usingCDict(zsmi_ctx *c, const void *src, c
     if (const int e = resolveCDict(c, cd, level, dict)) return e;
     return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict);
 }
+// dict / dictSize: the call's dictionary in host memory, which this call stages; or dd: a digested one, whose bytes are on the device already
 static int decompressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
-                                   const void *dict, size_t dictSize)
+                                   const void *dict, size_t dictSize, const zsmi_ddict *dd = nullptr)
 {
+    const void *ddBytes; uint32_t ddSize; const ZsDDictImage *img;
+    if (const int e = resolveDDict(c, dd, ddBytes, ddSize, img)) return e;
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    const bool useDict = dict != nullptr && dictSize != 0;
+    const bool useDict = !img && dict != nullptr && dictSize != 0;
     return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, useDict ? dict : nullptr, dictSize,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
+                      if (img) return decompressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dstCaps, dSizes, ddBytes, ddSize, img);
                       return decompressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dstCaps, dSizes, useDict ? c->sDict.p : nullptr,
                                                        useDict ? (uint32_t)dictSize : 0u);
                   });
@@ -1022,6 +1102,12 @@ extern "C" int zsmi_decompressBatchHost_usingDict(zsmi_ctx *c, const void *src, 
                                                   const void *dict, size_t dictSize)
 {
     return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, dict, dictSize);
+}
+extern "C" int zsmi_decompressBatchHost_usingDDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                   uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
+                                                   const zsmi_ddict *dd)
+{
+    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, nullptr, 0, dd);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1118,17 +1204,27 @@ extern "C" size_t zsmi_decompress(void *dst, size_t dstCapacity, const void *src
     return zsmi_decompress_usingDict(dst, dstCapacity, src, srcSize, nullptr, 0);
 }
 
-extern "C" size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize)
+// one frame (or several concatenated) through a borrowed context: with the dictionary's bytes (or none), or with the digested dictionary dd
+static size_t decompressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, const zsmi_ddict *dd)
 {
     if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
     Borrowed b; zsmi_ctx *c = b.c;
     if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
     const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
     const uint32_t cap = (uint32_t)std::min<size_t>(dstCapacity, 0xFFFFFF00u);
-    const int rc = zsmi_decompressBatchHost_usingDict(c, src, &so, &ss, 1, dst, &dof, &cap, &ds, dict, dictSize);
+    const int rc = decompressBatchHostImpl(c, src, &so, &ss, 1, dst, &dof, &cap, &ds, dict, dictSize, dd);
     if (rc) return ZSMI_ERR(rc);
     if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
     return ds;
+}
+extern "C" size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize)
+{
+    return decompressOneShot(dst, dstCapacity, src, srcSize, dict, dictSize, nullptr);
+}
+// a null dd: zsmi_decompress.  (The borrowed context is one of the current device: a dictionary digested on another device is parameter_unsupported)
+extern "C" size_t zsmi_decompress_usingDDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_ddict *dd)
+{
+    return decompressOneShot(dst, dstCapacity, src, srcSize, nullptr, 0, dd);
 }
 
 #ifdef ZSMI_DEBUG_HOOKS
