@@ -103,8 +103,8 @@ int zsmi_compressBatchDevice(zsmi_ctx *ctx, const void *dSrc, const uint64_t *sr
                              uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level);
 
 /* The same with one dictionary for every chunk of the call (dDict: device memory; rules as zsmi_compress_usingDict: chunks of <= 64 KiB
- * may match into the last 64 KiB of its content).  The dictionary is read back and parsed on the host first: the call waits for the
- * context's stream once.  NULL / 0 = zsmi_compressBatchDevice. */
+ * may match into the last 64 KiB of its content).  The dictionary is loaded and checked on the device first and the few fields the host needs are
+ * read back: the call waits for the context's stream once.  NULL / 0 = zsmi_compressBatchDevice. */
 int zsmi_compressBatchDevice_usingDict(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                        uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
                                        const void *dDict, size_t dictSize);

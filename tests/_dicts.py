@@ -59,12 +59,49 @@ def class_data(cls, n=1 << 19):
     return _data_cache[(cls, n)]
 
 
+def entropy_layout(dic):
+    """where the parts of a formatted dictionary's entropy section start: [offset-code counts, match-length counts, literal-length
+    counts, recent offsets] (the Huffman description starts at 8)"""
+    import _framewriter as W
+    h = dic[8]
+    p = 8 + ((h - 127 + 1) // 2 + 1 if h >= 128 else h + 1)
+    marks = [p]
+    for max_symbol in (31, 52, 35):
+        p = W.read_ncount(dic, p, max_symbol)[2]
+        marks.append(p)
+    assert marks[3] == len(dic) - len(content_of(dic)) - 12
+    return marks
+
+
+def bad_entropy_sections():
+    """the 8 KiB trained dictionary with one part of its entropy section replaced or cut, by name: what LoadEntropy's own checks refuse
+    (the Huffman description's, the limits of each count header, the section's end) - every one is refused by oracle D with 30
+    (tests/test_oracle_dict_encoder.py::test_refused_dictionaries checks the list on the CPU)"""
+    import _framewriter as W
+    dic = TRAINED8K
+    of, ml, ll, reps = entropy_layout(dic)
+    huf = lambda weights: dic[:8] + W.huf_description(weights) + dic[of:]     # (weights: the last one is implied, not written)
+    return {
+        "magic and ID, nothing else": dic[:8],
+        "offset-code counts at accuracy log 9": dic[:of] + W.ncount([128] * 4, 9) + dic[ml:],
+        "match-length counts that declare symbol 53": dic[:ml] + W.ncount([2] * 10 + [1] * 44, 6) + dic[ll:],
+        "literal-length counts that declare symbol 36": dic[:ll] + W.ncount([2] * 27 + [1] * 10, 6) + dic[reps:],
+        "literal-length counts at accuracy log 10": dic[:ll] + W.ncount([256] * 4, 10) + dic[reps:],
+        "Huffman weights that do not complete to a power of two": huf([3, 1, 0]),          # 4 + 1 = 5 of 8: 3 are left
+        "Huffman table log 13": huf([11, 11, 11, 11, 0]),                                      # 4 * 1024: a total of 2^12 asks for 13 bits
+        "Huffman weights without a pair of weight 1": huf([2, 0]),                             # 2 of 4, the implied weight is 2 as well
+        "cut inside the third count header": dic[:ll + 2],
+        "cut inside the twelve offset bytes": dic[:reps + 6],
+    }
+
+
 def bad_dictionaries():
-    """dictionaries oracle D refuses (dictionary_corrupted): cut entropy sections, a recent offset of 0, one past the content"""
+    """dictionaries oracle D refuses (dictionary_corrupted): cut entropy sections, a recent offset of 0, one past the content, and the
+    hand-built entropy sections of bad_entropy_sections()"""
     dic = TRAINED8K
     rep0 = with_reps(dic, (0, 4, 8))
     past = with_reps(dic, (1, len(content_of(dic)), 8))
-    return [dic[:9], dic[:40], dic[:120], rep0, past]
+    return [dic[:9], dic[:40], dic[:120], rep0, past] + list(bad_entropy_sections().values())
 
 
 def identity_dictionaries():

@@ -205,6 +205,52 @@ def test_corrupted_dictionaries_give_null_with_code_30(codec):
             CompressionDict(codec, d)
 
 
+def test_every_entry_point_gives_a_dictionary_the_same_verdict(codec):
+    """one loader decides: for every dictionary of tests/_dicts.py (valid, with each ID field size, refused) zsmi_createCDict,
+    zsmi_createDDict, the device and the host _usingDict compress of one 100-byte chunk and the _usingDict decode of one plain 100-byte
+    frame (its per-item code) answer 30 together or succeed together, as oracle D does; on success the three IDs agree"""
+    from _hip import hip_of, Dev
+    L, H = codec.L, hip_of()
+    vp, p = ctypes.c_void_p, lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    chunk = X.class_data("json_records")[:100]
+    frame = O.compress(chunk, 3)
+    src, so, ss = B.batch([chunk])
+    bound = L.zsmi_compressBound(len(chunk))
+    dsrc, ddst, dsz = Dev(H, len(chunk), chunk), Dev(H, bound), Dev(H, 4)
+    do = np.zeros(1, dtype=np.uint64)
+    dicts = list(X.identity_dictionaries().values()) + list(X.id_dictionaries().values()) + X.bad_dictionaries()
+    refused = 0
+    for k, d in enumerate(dicts):
+        try:
+            want, want_id = 0, O.dict_params(d)[1]
+        except O.OracleError as e:
+            want, want_id = e.code, None
+        err = ctypes.c_int(-1)
+        cd = L.zsmi_createCDict(codec.ctx, d, len(d), 3, ctypes.byref(err))
+        verdicts = {"createCDict": err.value}
+        dd = L.zsmi_createDDict(codec.ctx, d, len(d), ctypes.byref(err))
+        verdicts["createDDict"] = err.value
+        ddic = Dev(H, len(d), d)
+        verdicts["device compress"] = L.zsmi_compressBatchDevice_usingDict(codec.ctx, vp(dsrc.p), p(so), p(ss), 1, vp(ddst.p), p(do), vp(dsz.p), 3, vp(ddic.p), len(d))
+        codec.sync(); ddic.free()
+        hsz, out = np.zeros(1, dtype=np.uint32), np.zeros(bound, dtype=np.uint8)
+        dbuf = np.frombuffer(d, dtype=np.uint8)
+        verdicts["host compress"] = L.zsmi_compressBatchHost_usingDict(codec.ctx, p(src), p(so), p(ss), 1, p(out), p(do), p(hsz), 3, p(dbuf), len(d))
+        (sz, got), = B.decode_many(codec, [frame], [len(chunk)], d)
+        verdicts["decode"] = 0x100000000 - sz if sz > B.ERR else 0
+        assert set(verdicts.values()) == {want} and want in (0, 30), (k, len(d), want, verdicts)
+        assert bool(cd) == bool(dd) == (want == 0), (k, len(d))
+        if want == 0:
+            assert got == chunk and hsz[0] < B.ERR and O.decompress_using_dict(out[:int(hsz[0])].tobytes(), len(chunk), d) == chunk, (k, len(d))
+            assert L.zsmi_getDictID_fromCDict(cd) == L.zsmi_getDictID_fromDDict(dd) == want_id, (k, len(d), want_id)
+        refused += want == 30
+        L.zsmi_freeCDict(cd); L.zsmi_freeDDict(dd)
+    assert refused == len(X.bad_dictionaries()) >= 9
+    for b in (dsrc, ddst, dsz):
+        assert b.all()[:4096] == bytes([B.CANARY]) * 4096 and b.all()[-4096:] == bytes([B.CANARY]) * 4096
+        b.free()
+
+
 def test_one_shot_null_and_compressor_forms(codec):
     from zstandard_amd import CompressionDict, ZstdCompressor
     L = codec.L

@@ -11,7 +11,12 @@ The decode leg runs on the frames the record has just made: dec_gib_s_dict (the 
 the general kernel), dec_gib_s_ddict (the CDict frames through a DecompressionDict: the fast path) and dec_gib_s_plain (the no-dictionary
 frames of the same chunks, plain decode), GiB/s of decoded bytes; dec_min_* / dec_max_* are the slowest and fastest of the --repeats timings
 as rates, dec_spread_* their spread; ddict_over_dict and ddict_over_plain the ratios of the medians; dec_ranges_apart says that the DDict's
-slowest repeat beat the _usingDict call's fastest.  --kernels adds dec_kernels_ms_*."""
+slowest repeat beat the _usingDict call's fastest.  --kernels adds dec_kernels_ms_*.
+--loader: instead of all that, what LOADING a dictionary costs at each entry point that reads its bytes (one JSON line; per call, in
+microseconds: median, min and max of --repeats timings of --steps calls): the device _usingDict compress of one 1 KiB chunk and of 4096
+chunks of 4 KiB, the host _usingDict compress of 64 chunks of 1 KiB, zsmi_createCDict, zsmi_createDDict (each with its free), and the
+_usingDict decode of 4096 frames of 4 KiB (k_decode_frames_dict loads the dictionary in front of every frame).  ZSMI_LIB_FILE names another
+build of the library to measure with the same tool."""
 import argparse, ctypes, json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,6 +48,55 @@ def zstd_sizes(chunks, dic, level):
     return total
 
 
+def loader_leg(a):
+    cls = a.classes.split(",")[0]
+    dic = np.load(FIXC)["trained_" + cls].tobytes()
+    data = class_bytes(cls, 4096 * 4096)
+    dev = torch.device("cuda:0")
+    bc = BatchCodec(device=0); Z = _lib.lib()
+    vp = ctypes.c_void_p
+    pa = lambda x: x.ctypes.data_as(vp)
+    dsrc = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).to(dev)
+    ddict = torch.from_numpy(np.frombuffer(dic, dtype=np.uint8).copy()).to(dev)
+    hsrc = np.frombuffer(data, dtype=np.uint8)
+
+    def layout(n, cs):
+        bound = int(Z.zsmi_compressBound(cs))
+        return np.arange(n, dtype=np.uint64) * cs, np.full(n, cs, dtype=np.uint32), np.arange(n, dtype=np.uint64) * bound, bound
+    off, sz, doff, bound = layout(4096, 4096)
+    ddst = torch.empty(4096 * bound, dtype=torch.uint8, device=dev); dsz = torch.empty(4096, dtype=torch.int32, device=dev)
+    dout = torch.empty(4096 * 4096, dtype=torch.uint8, device=dev); dosz = torch.empty(4096, dtype=torch.int32, device=dev)
+    o1, s1, d1, _ = layout(1, 1024)
+    o64, s64, _, _ = layout(64, 1024)
+    legs = {}
+    legs["device_usingDict_1x1KiB"] = lambda: bc.compress_device(dsrc.data_ptr(), o1, s1, ddst.data_ptr(), d1, dsz.data_ptr(), 3, ddict.data_ptr(), len(dic))
+    legs["device_usingDict_4096x4KiB"] = lambda: bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), 3, ddict.data_ptr(), len(dic))
+    legs["host_usingDict_64x1KiB"] = lambda: bc.compress_host(hsrc, o64, s64, 3, dic)
+    legs["createCDict"] = lambda: CompressionDict(bc, dic, 3).close()
+    legs["createDDict"] = lambda: DecompressionDict(bc, dic).close()
+    caps = np.full(4096, 4096, dtype=np.uint32)
+    rec = {"loader": True, "class": cls, "dict_bytes": len(dic), "library": Z.zsmi_versionString().decode(), "steps": a.steps, "repeats": a.repeats, "unit": "us per call"}
+    for name in list(legs) + ["usingDict_decode_4096x4KiB"]:
+        if name == "usingDict_decode_4096x4KiB":                       # the frames the second leg left in ddst
+            legs["device_usingDict_4096x4KiB"](); bc.sync()
+            fsz = dsz.cpu().numpy().view(np.uint32).copy()
+            run = lambda: Z.zsmi_decompressBatchDevice_usingDict(bc.ctx, vp(ddst.data_ptr()), pa(doff), pa(fsz), 4096, vp(dout.data_ptr()), pa(off), pa(caps),
+                                                                 vp(dosz.data_ptr()), vp(ddict.data_ptr()), len(dic))
+        else:
+            run = legs[name]
+        for _ in range(3):
+            run()
+        times = []
+        for _ in range(a.repeats):
+            bc.sync(); t0 = time.perf_counter()
+            for _ in range(a.steps):
+                run()
+            bc.sync(); times.append((time.perf_counter() - t0) / a.steps * 1e6)
+        rec[name] = {"median": round(float(np.median(times)), 1), "min": round(min(times), 1), "max": round(max(times), 1)}
+    assert torch.equal(dout, dsrc[:4096 * 4096]) and bool((dosz == 4096).all())
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bytes", type=int, default=64 << 20, help="input bytes per class")
@@ -52,7 +106,10 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--loader", action="store_true", help="only the cost of loading a dictionary at each entry point that reads its bytes")
     a = ap.parse_args()
+    if a.loader:
+        return loader_leg(a)
     fix = np.load(FIXC)
     dev = torch.device("cuda:0")
     bc = BatchCodec(device=0)

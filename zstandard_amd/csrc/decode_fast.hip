@@ -20,6 +20,10 @@
 //
 // Reference functions restated: see decode_kernels.hip, whose routines this path shares: the error codes and isErr, ZsDecItem, DLds and the
 // constant tables, readNCount, buildSeqTableWave, readHufTableT, BitC and its readers, hufDecodeStreams, seqHeadersT, execTileT.
+//
+// Dictionaries: k_dict_load, at the end of this file, is how the HOST learns what a dictionary holds - it runs decode_kernels.hip's
+// loadDictEntropy (the only place where a dictionary's entropy section is walked and checked; the host parses nothing) and leaves a
+// ZsDictRecord, and for a digested decode dictionary the ZsDDictImage the DD forms of the kernels above read.
 #include "zsmi_device.h"
 #include "zsmi_wave.h"
 #include "decode_kernels.hip"
@@ -59,7 +63,7 @@ struct ZsFastDesc {                               // per item, global memory, wr
 };
 #define ZS_FAST_HUFTAB_BYTES (2u << ZS_FAST_HUFLOG)                       // uint16 entries
 #define ZS_FAST_SEQTAB_BYTES ((512u + 256u + 512u) * 2u)                  // LL, OF, ML cells, 2 bytes each
-// A digested decode dictionary's device image (zsmi_createDDict; filled by k_ddict_tables, read-only afterwards): what a frame decoded with
+// A digested decode dictionary's device image (zsmi_createDDict; filled by k_dict_load, read-only afterwards): what a frame decoded with
 // the dictionary starts from (ZSTD_decompress_insertDictionary :2452-2475) - the content in front of the frame, the recent offsets, and for a
 // formatted dictionary its entropy tables in exactly the form the fast kernels read: the Huffman table as k_dec_prep leaves one in a slot
 // (two-level or flat), the LL / OF / ML cells in a slot's layout.  The DD instantiations of the fast kernels take it; the others never look at it.
@@ -1134,54 +1138,51 @@ k_dec_checksum(const ZsDecItem *__restrict__ items, uint32_t nItems, const ZsFas
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// k_ddict_tables : one wavefront, once per digested decode dictionary (zsmi_createDDict).  The host has parsed and checked the dictionary
-// (parseCompressDict: what LoadEntropy :2378-2450 refuses is refused there) and hands over where the content starts, the ID and the recent
-// offsets; a formatted dictionary's tables are built here with the routines k_dec_prep builds a block's with, from the dictionary's own
-// bytes: the form is the slots' by construction.
+// k_dict_load : one wavefront over a dictionary in device memory - the host's only reader of one (zsmi_api.hip: loadDict; the host parses
+// nothing).  It runs the dictionary loader of the general decoder (loadDictEntropy, decode_kernels.hip) and leaves in rec the verdict, the
+// ID, where the content starts, the recent offsets and the entropy section as read (what a digested compression dictionary is built from).
+// img (zsmi_createDDict; nullptr on every other path): besides, a digested decode dictionary's image - a formatted dictionary's tables built
+// with the routines k_dec_prep builds a block's with, from the dictionary's own bytes: the form is the slots' by construction.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
-k_ddict_tables(const uint8_t *__restrict__ dict, uint32_t dictBytes, uint32_t contentOff, uint32_t dictID, uint32_t rep0, uint32_t rep1, uint32_t rep2,
-               ZsDDictImage *__restrict__ img)
+k_dict_load(const uint8_t *__restrict__ dict, uint32_t dictBytes, ZsDictRecord *__restrict__ rec, ZsDDictImage *__restrict__ img)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char LSraw[(ZS_DLDS_PREP + 15) & ~15u];
-    DLds &L = *reinterpret_cast<DLds *>(LSraw);
+    __shared__ DLds L;
     const uint32_t lane = (uint32_t)zs_lane();
-    uint32_t tables = 0, hufLog = 0, hufFlat = 0, hufWide = 0;
-    if (contentOff >= 8 + 12 && contentOff <= dictBytes) {
-        const uint8_t *p = dict + 8, *const pend = dict + contentOff - 12;      // the entropy section: Huffman description, then the OF, ML, LL counts
-        const uint32_t first = p[0], hs = first >= 128 ? (first - 127 + 1) / 2 + 1 : first + 1;      // (EntropyCommon.cs:215-225: the description's size)
-        const uint32_t h = readHufTableT<true>(L, p, (uint32_t)(pend - p), reinterpret_cast<uint16_t *>(img->hufTab), ZS_FAST_HUFLOG);
-        if (isErr(h)) hufWide = 1;                                               // a table of 2^12: not held
-        else { hufFlat = h >> 30; hufLog = L.hufLog; }
-        wave_sync();
-        p += hs;
-        tables = 1;
-        uint16_t *stab = reinterpret_cast<uint16_t *>(img->seqTab);
-        for (int t = 0; t < 3 && tables; t++) {
-            const uint32_t maxS = t == 0 ? 31 : (t == 1 ? 52 : 35), maxLog = t == 0 ? 8 : 9;
-            const uint32_t at = t == 0 ? 512u : (t == 1 ? 768u : 0u), slot = t == 0 ? 1u : (t == 1 ? 2u : 0u);
-            const uint32_t left = p < pend ? (uint32_t)(pend - p) : 0u;
-            hw_stage(L.u.tb.hdrWin, p, left);
-            if (lane == 0) {
-                uint32_t tableLog = 0, max = maxS;
-                const uint32_t nc = readNCount(L.u.tb.norm, &max, &tableLog, L.u.tb.hdrWin, left, 0);
-                L.misc[0] = (isErr(nc) || max > maxS || tableLog > maxLog) ? 1u : 0u; L.misc[1] = nc; L.misc[3] = max; L.misc[4] = tableLog;
-            }
+    uint32_t dictID, rep[3], hufLog = 0, hufFlat = 0, hufWide = 0;
+    const uint32_t contentOff = loadDictEntropy(L, dict, dictBytes, dictID, rep,
+        [&](const uint8_t *p, uint32_t n) __attribute__((always_inline)) {
+            // the image holds a Huffman table of up to 2^ZS_FAST_HUFLOG entries in a slot's form; a description that form does not take (a
+            // table of 2^12: not held) and every description without an image goes to the full-size reader, the general decoder's, which decides
+            uint32_t h = img ? readHufTableT<true>(L, p, n, reinterpret_cast<uint16_t *>(img->hufTab), ZS_FAST_HUFLOG) : ZE(E_tableLog_tooLarge);
+            if (isErr(h)) { hufWide = 1; wave_sync(); h = readHufTable(L, p, n); }
+            else { hufFlat = h >> 30; h &= 0x3FFFFFFFu; hufLog = L.hufLog; }
+            if (isErr(h)) return h;
+            uint32_t nWeights = 0;                                               // (the weights, the implied last one included, are still in the workspace)
+            for (uint32_t i = lane; i < 256; i += 64) { const uint8_t w = L.u.tb.weights[i]; rec->ent.weights[i] = w; if (w) nWeights = i + 1; }
+            nWeights = wave_max(nWeights);
+            if (lane == 0) { rec->ent.nWeights = nWeights; rec->ent.hufLog = L.hufLog; }
+            return h;
+        },
+        [&](int t, uint32_t maxSym, uint32_t tableLog) __attribute__((always_inline)) {
+            const uint32_t k = t == 0 ? 1u : (t == 1 ? 2u : 0u);                 // the encoder's order, and a slot's: LL, OF, ML
+            rec->ent.norm[k][lane] = lane <= maxSym ? L.u.tb.norm[lane] : (int16_t)0;
+            if (lane == 0) { rec->ent.maxSym[k] = maxSym; rec->ent.tableLog[k] = tableLog; }
+            if (!img) return;
+            buildSeqTableWave(L, L.LL.cells, &L.LL.tableLog, maxSym, tableLog);
             wave_sync();
-            if (L.misc[0]) { tables = 0; break; }                               // (the host's parse refuses these: no table, every such frame to the general kernel)
-            const uint32_t adv = L.misc[1], bmax = L.misc[3], blog = L.misc[4];
-            buildSeqTableWave(L, L.LL.cells, &L.LL.tableLog, bmax, blog);
-            wave_sync();
-            const uint32_t log = L.LL.tableLog;
-            for (uint32_t i = lane; i < (1u << log); i += 64) { const SeqSym c = L.LL.cells[i]; stab[at + i] = (uint16_t)zs_fastcell(c.nextState, c.nbBits, c.sym); }
-            if (lane == 0) img->seqLog[slot] = log;
-            wave_sync();
-            p += adv;
-        }
-    }
-    if (lane == 0) {
+            uint16_t *stab = reinterpret_cast<uint16_t *>(img->seqTab) + (k == 1 ? 512u : (k == 2 ? 768u : 0u));
+            for (uint32_t i = lane; i < (1u << tableLog); i += 64) { const SeqSym c = L.LL.cells[i]; stab[i] = (uint16_t)zs_fastcell(c.nextState, c.nbBits, c.sym); }
+            if (lane == 0) img->seqLog[k] = tableLog;
+        });
+    if (lane != 0) return;
+    const bool bad = isErr(contentOff);
+    rec->status = bad ? (uint32_t)E_dictionary_corrupted : 0u; rec->dictID = dictID; rec->contentOff = bad ? 0u : contentOff;
+    rec->rep[0] = rep[0]; rec->rep[1] = rep[1]; rec->rep[2] = rep[2];
+    if (img && !bad) {
+        const uint32_t tables = contentOff != 0;
         img->contentEnd = dict + dictBytes; img->contentSize = dictBytes - contentOff; img->dictID = dictID;
-        img->rep[0] = rep0; img->rep[1] = rep1; img->rep[2] = rep2;
+        img->rep[0] = rep[0]; img->rep[1] = rep[1]; img->rep[2] = rep[2];
         img->tables = tables; img->hufLog = hufLog; img->hufFlat = hufFlat; img->hufWide = hufWide || !tables;
         if (!tables) { img->seqLog[0] = 0; img->seqLog[1] = 0; img->seqLog[2] = 0; }
     }

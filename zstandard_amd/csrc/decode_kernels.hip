@@ -1072,6 +1072,44 @@ __device__ __forceinline__ uint32_t decodeBlock(DLds &L, DState &st, uint8_t *ds
     return (uint32_t)(op - ostart);
 }
 
+// ---- THE reader of a dictionary's bytes (ZSTD_decompress_insertDictionary :2452-2475 with LoadEntropy :2378-2450): every path that
+// takes a dictionary - the general kernel in front of each frame, k_dict_load for the host (decode_fast.hip) - decides here, and only here,
+// what a dictionary holds and whether it is refused.  Returns the content's offset, or dictionary_corrupted.  Anything but the magic
+// 0xEC30A437 in front of >= 8 bytes is raw content: offset 0, ID 0, recent offsets {1, 4, 8}.  A formatted dictionary: the ID, the Huffman
+// description (huf(p, n): a readHufTableT form of the caller's choice - its size, or an error), the count headers of the offset codes,
+// match lengths and literal lengths (table(t, maxSym, tableLog), t in that order, called with the counts in L.u.tb.norm: the caller
+// builds or keeps what it needs), three recent offsets inside the content, the content.
+template <class Huf, class Table>
+__device__ __forceinline__ uint32_t loadDictEntropy(DLds &L, const uint8_t *dict, uint32_t dictBytes, uint32_t &dictID, uint32_t (&rep)[3], Huf huf, Table table)
+{
+    dictID = 0; rep[0] = 1; rep[1] = 4; rep[2] = 8;
+    if (dictBytes < 8 || rd32(dict) != 0xEC30A437u) return 0;
+    dictID = rd32(dict + 4);
+    const uint8_t *p = dict + 8; const uint8_t *const pend = dict + dictBytes;
+    if (dictBytes <= 8) return ZE(E_dictionary_corrupted);
+    { const uint32_t h = huf(p, (uint32_t)(pend - p)); if (isErr(h)) return ZE(E_dictionary_corrupted); p += h; }
+    for (int t = 0; t < 3; t++) {                                     // :2395-2435
+        const uint32_t maxS = t == 0 ? 31 : (t == 1 ? 52 : 35), maxLog = t == 0 ? 8 : 9;
+        const uint32_t left = (uint32_t)(pend - p);
+        hw_stage(L.u.tb.hdrWin, p, left);
+        if (zs_lane() == 0) {
+            uint32_t tableLog = 0, max = maxS;
+            const uint32_t h = readNCount(L.u.tb.norm, &max, &tableLog, L.u.tb.hdrWin, left, 0);
+            L.misc[0] = (isErr(h) || max > maxS || tableLog > maxLog) ? 1u : 0u; L.misc[1] = h; L.misc[3] = max; L.misc[4] = tableLog;
+        }
+        wave_sync();
+        if (L.misc[0]) return ZE(E_dictionary_corrupted);
+        const uint32_t adv = L.misc[1], bmax = L.misc[3], blog = L.misc[4];
+        table(t, bmax, blog);
+        wave_sync();
+        p += adv;
+    }
+    if (p + 12 > pend) return ZE(E_dictionary_corrupted);
+    const uint32_t contentSize = (uint32_t)(pend - (p + 12));
+    for (int i = 0; i < 3; i++) { const uint32_t r = rd32(p); p += 4; if (r == 0 || r >= contentSize) return ZE(E_dictionary_corrupted); rep[i] = r; }
+    return (uint32_t)(p - dict);
+}
+
 #ifndef ZS_DEC_GROUP
 #define ZS_DEC_GROUP 2             // items (= wavefronts) per workgroup
 #endif
@@ -1135,37 +1173,14 @@ __device__ __forceinline__ void zs_decode_item(DLds &L, const uint32_t item, con
         DState st; st.rep[0] = 1; st.rep[1] = 4; st.rep[2] = 8; st.litEntropy = 0; st.fseEntropy = 0; st.llRepeatOk = 0; st.hufX4 = 0;   // DecompressBegin :2478-2499
         const uint8_t *dictEnd = nullptr; uint32_t dictSize = 0, dictIDLoaded = 0;
         if (DICT && dict && dictBytes) {                             // ZSTD_decompress_insertDictionary :2452-2475
-            const uint8_t *content = dict; uint32_t contentSize = dictBytes;
-            if (dictBytes >= 8 && rd32(dict) == 0xEC30A437u) {
-                dictIDLoaded = rd32(dict + 4);
-                const uint8_t *p = dict + 8; const uint8_t *const pend = dict + dictBytes;
-                if (dictBytes <= 8) DONE(ZE(E_dictionary_corrupted));
-                { const uint32_t h = readHufTable(L, p, (uint32_t)(pend - p)); if (isErr(h)) DONE(ZE(E_dictionary_corrupted)); p += h; st.hufX4 = 1; }   // HUF_readDTableX4_wksp (:2391)
-                for (int t = 0; t < 3; t++) {                         // offset codes, match lengths, literal lengths (:2395-2435)
-                    const uint32_t maxS = t == 0 ? 31 : (t == 1 ? 52 : 35), maxLog = t == 0 ? 8 : 9;
-                    SeqSym *cells = t == 0 ? L.OF.cells : (t == 1 ? L.ML.cells : L.LL.cells);
-                    uint32_t *tl = t == 0 ? &L.OF.tableLog : (t == 1 ? &L.ML.tableLog : &L.LL.tableLog);
-                    const uint32_t left = (uint32_t)(pend - p);
-                    hw_stage(L.u.tb.hdrWin, p, left);
-                    if (lane == 0) {
-                        uint32_t tableLog = 0, max = maxS;
-                        const uint32_t h = readNCount(L.u.tb.norm, &max, &tableLog, L.u.tb.hdrWin, left, 0);
-                        L.misc[0] = (isErr(h) || max > maxS || tableLog > maxLog) ? 1u : 0u; L.misc[1] = h; L.misc[3] = max; L.misc[4] = tableLog;
-                    }
-                    wave_sync();
-                    if (L.misc[0]) DONE(ZE(E_dictionary_corrupted));
-                    const uint32_t adv = L.misc[1], bmax = L.misc[3], blog = L.misc[4];
-                    buildSeqTableWave(L, cells, tl, bmax, blog);
-                    wave_sync();
-                    p += adv;
-                }
-                if (p + 12 > pend) DONE(ZE(E_dictionary_corrupted));
-                contentSize = (uint32_t)(pend - (p + 12));
-                for (int i = 0; i < 3; i++) { const uint32_t rep = rd32(p); p += 4; if (rep == 0 || rep >= contentSize) DONE(ZE(E_dictionary_corrupted)); st.rep[i] = rep; }
-                st.litEntropy = 1; st.fseEntropy = 1;
-                content = p;
-            }
-            dictEnd = content + contentSize; dictSize = contentSize;
+            const uint32_t contentOff = loadDictEntropy(L, dict, dictBytes, dictIDLoaded, st.rep,
+                [&](const uint8_t *p, uint32_t n) __attribute__((always_inline)) { return readHufTable(L, p, n); },      // HUF_readDTableX4_wksp (:2391)
+                [&](int t, uint32_t maxSym, uint32_t tableLog) __attribute__((always_inline)) {
+                    buildSeqTableWave(L, t == 0 ? L.OF.cells : (t == 1 ? L.ML.cells : L.LL.cells), t == 0 ? &L.OF.tableLog : (t == 1 ? &L.ML.tableLog : &L.LL.tableLog), maxSym, tableLog);
+                });
+            if (isErr(contentOff)) DONE(contentOff);
+            if (contentOff) { st.hufX4 = 1; st.litEntropy = 1; st.fseEntropy = 1; }     // a formatted dictionary: its tables are the frame's first
+            dictSize = dictBytes - contentOff; dictEnd = dict + dictBytes;
         }
         if (dictID != 0 && dictID != dictIDLoaded) DONE(ZE(E_dictionary_wrong));      // :632-634
         const uint64_t frameStart = op;

@@ -107,13 +107,10 @@ struct FseCT {                       // encoding table of one symbol type
     uint32_t tableLog;
     uint32_t rle;
 };
-// A digested dictionary (zsmi_cdict): the entropy tables of a formatted dictionary as the decoder loads them (parsed on the host), and
-// their encoder form (k_cdict_tables), which the _cdict kernels read for a frame's first block: Repeat_Mode sequences, Treeless literals.
+// A digested dictionary (zsmi_cdict): the entropy tables of a formatted dictionary as the decoder loads them (ZsCDictEntropy, zsmi_device.h:
+// what the dictionary loader read), in their encoder form (k_cdict_tables), which the _cdict kernels read for a frame's first block:
+// Repeat_Mode sequences, Treeless literals.
 #define ZS_COST_NONE 0xFFFFu         // a symbol the table cannot code (probability 0)
-struct ZsCDictEntropy {              // kernel argument of k_cdict_tables
-    uint8_t weights[256]; uint32_t nWeights, hufLog;           // Huffman weights, the implied last one included
-    int16_t norm[3][64]; uint32_t maxSym[3], tableLog[3];      // normalised counts of LL, OF, ML (-1: low probability)
-};
 struct ZsCDictTables {
     FseCT ct[3];                     // LL, OF, ML
     uint16_t cost[3][64];            // bits to code symbol s under ct[t], in 1/256 bit (fseSymbolCost); ZS_COST_NONE
@@ -1670,8 +1667,9 @@ __global__ void __launch_bounds__(256) k_train_stats(const uint8_t *__restrict__
 // A digested dictionary's entropy tables in encoder form, once per dictionary, by the encoder's own routines: the Huffman codes in the decoder's
 // order from the weights (huffCodesAndWeights), the three encoding tables by the lane-0 buildCTable (a trained dictionary's counts hold -1
 // entries, which buildCTableWave does not take), and the cost of every symbol.  One workgroup of 256 threads; wavefront t < 3 makes table t.
-__global__ void __launch_bounds__(256) k_cdict_tables(const ZsCDictEntropy e, ZsCDictTables *__restrict__ out)
+__global__ void __launch_bounds__(256) k_cdict_tables(const ZsCDictEntropy *__restrict__ ent, ZsCDictTables *__restrict__ out)
 {
+    const ZsCDictEntropy &e = *ent;                  // (in the dictionary loader's record, device memory)
     __shared__ K3Lds L;
     __shared__ struct { FseCT ct; int16_t norm[64]; uint8_t tableSymbol[512]; uint32_t cumul[66]; } F[3];
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;

@@ -8,8 +8,8 @@
 #include "zsmi_wave.h"            // device primitives of more than one kernel file: wave_*, zs_block_copy, rd16/24/32, xxh64_quad
 #include "lz_kernels.hip"         // encoder, LZ stage: k_lz_candidates, k_lz_walk, k_lz_stitch, k_lz_dict_tables
 #include "entropy_kernels.hip"    // encoder, entropy stage: k_encode_sequences, k_encode_literals, k_assemble_frames; k_train_stats, k_pack_*
-#include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares
-#include "decode_fast.hip"        // fast decode path: k_dec_prep, k_dec_huffman, k_dec_sequences, k_dec_entropy, k_dec_execute, k_dec_checksum, k_dec_collect
+#include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares; loadDictEntropy, the one reader of a dictionary
+#include "decode_fast.hip"        // fast decode path: k_dec_prep, k_dec_huffman, k_dec_sequences, k_dec_entropy, k_dec_execute, k_dec_checksum, k_dec_collect; k_dict_load (a dictionary -> its record for the host, a DDict's image)
 #include "zsmi_ctx.h"             // host: zsmi_ctx and its buffers, LAUNCH, the batch entry points the features call
 #include "seekable.hip"           // feature: seekable archives (kernels and host)
 #include "dict_train.hip"         // feature: dictionary training and finalize (kernels and host)
@@ -192,183 +192,27 @@ extern "C" int zsmi_getKernelTimes(zsmi_ctx *c, zsmi_kernel_time *out, int maxEn
 }
 
 // ---------------------------------------------------------------------------------------------
-// dictionaries for the compressor: what a usingDict DECODE of the frames will load (ZSTD_decompress_insertDictionary :2452-2475).
-// A formatted dictionary (magic 0xEC30A437, >= 8 bytes) gives the frames its ID and their first blocks its recent offsets; its entropy
-// section is parsed only to find where the content starts and to refuse, with dictionary_corrupted, exactly what LoadEntropy
-// (:2378-2450) refuses (its checks restated on the host: readNCount, the Huffman weights and their FSE header, the recent offsets).
-// Any other bytes are raw content: offsets {1, 4, 8}, no ID.  The _usingDict calls use none of the dictionary's tables; a digested
-// dictionary (zsmi_createCDict) takes them from the same parse (ZsCDictEntropy).
+// dictionaries: what a usingDict DECODE of the frames will load (ZSTD_decompress_insertDictionary :2452-2475).
+// A formatted dictionary (magic 0xEC30A437, >= 8 bytes) gives the frames its ID and their first blocks its recent offsets; any other
+// bytes are raw content: offsets {1, 4, 8}, no ID.  The host parses nothing: the one reader of a dictionary's bytes is the device's
+// (loadDictEntropy in decode_kernels.hip, the general decoder's own, which refuses exactly what LoadEntropy :2378-2450 refuses), and
+// k_dict_load (decode_fast.hip) runs it for the host, so the compressor and the decoder cannot disagree about a dictionary.  The _usingDict
+// calls use none of the dictionary's tables; a digested dictionary takes them from the same run - zsmi_createCDict the entropy section as
+// read (ZsCDictEntropy, in the record), zsmi_createDDict the fast kernels' image (img).
 // ---------------------------------------------------------------------------------------------
-namespace hdict {
-static uint32_t hb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
-static const size_t kErr = ~(size_t)0;
-// EntropyCommon.cs:79-188 (FSE_readNCount): bytes read or kErr
-static size_t readNCount(int16_t *norm, uint32_t *maxSV, uint32_t *tableLog, const uint8_t *istart, size_t hbSize)
+// dDict[0 .. dictSize): device memory.  One launch on the context's stream, the record (a few hundred bytes) copied back, ONE wait.
+// 0 with `out` filled (dBytes = dDict), or ZSMI_error_dictionary_corrupted; the record stays in c->dDictRec until the context's next load.
+static int loadDict(zsmi_ctx *c, const void *dDict, size_t dictSize, ZsCompressDict &out, ZsDDictImage *img = nullptr)
 {
-    const uint8_t *const iend = istart + hbSize;
-    const uint8_t *ip = istart;
-    if (hbSize < 4) return kErr;
-    uint32_t bitStream = h_rd32(ip), charnum = 0;
-    int nbBits = (int)(bitStream & 0xF) + 5, remaining, threshold, bitCount, previous0 = 0;
-    if (nbBits > 15) return kErr;
-    bitStream >>= 4; bitCount = 4;
-    *tableLog = (uint32_t)nbBits;
-    remaining = (1 << nbBits) + 1; threshold = 1 << nbBits; nbBits++;
-    while ((remaining > 1) & (charnum <= *maxSV)) {
-        if (previous0) {
-            uint32_t n0 = charnum;
-            while ((bitStream & 0xFFFF) == 0xFFFF) {
-                n0 += 24;
-                if (ip < iend - 5) { ip += 2; bitStream = h_rd32(ip) >> bitCount; }
-                else { bitStream >>= 16; bitCount += 16; }
-            }
-            while ((bitStream & 3) == 3) { n0 += 3; bitStream >>= 2; bitCount += 2; }
-            n0 += bitStream & 3; bitCount += 2;
-            if (n0 > *maxSV) return kErr;
-            while (charnum < n0) norm[charnum++] = 0;
-            if ((ip <= iend - 7) || (ip + (bitCount >> 3) <= iend - 4)) { ip += bitCount >> 3; bitCount &= 7; bitStream = h_rd32(ip) >> bitCount; }
-            else bitStream >>= 2;
-        }
-        const int max = (2 * threshold - 1) - remaining;
-        int count;
-        if ((bitStream & (uint32_t)(threshold - 1)) < (uint32_t)max) { count = (int)(bitStream & (uint32_t)(threshold - 1)); bitCount += nbBits - 1; }
-        else { count = (int)(bitStream & (uint32_t)(2 * threshold - 1)); if (count >= threshold) count -= max; bitCount += nbBits; }
-        count--;
-        remaining -= count < 0 ? -count : count;
-        norm[charnum++] = (int16_t)count;
-        previous0 = !count;
-        while (remaining < threshold) { nbBits--; threshold >>= 1; }
-        if ((ip <= iend - 7) || (ip + (bitCount >> 3) <= iend - 4)) { ip += bitCount >> 3; bitCount &= 7; }
-        else { bitCount -= (int)(8 * (iend - 4 - ip)); ip = iend - 4; }
-        bitStream = h_rd32(ip) >> (bitCount & 31);
-    }
-    if (remaining != 1 || bitCount > 32) return kErr;
-    *maxSV = charnum - 1;
-    ip += (bitCount + 7) >> 3;
-    return (size_t)(ip - istart);
-}
-// BitStream.cs:322-494: the backward bit reader, 32-bit container
-struct Bits { uint32_t c = 0, used = 0; const uint8_t *ptr = nullptr, *start = nullptr, *limit = nullptr; };
-static bool bitInit(Bits &b, const uint8_t *src, size_t n)
-{
-    if (n < 1) return false;
-    b.start = src; b.limit = src + 4;
-    const uint8_t last = src[n - 1];
-    if (last == 0) return false;
-    b.used = 8 - hb(last);
-    if (n >= 4) { b.ptr = src + n - 4; b.c = h_rd32(b.ptr); }
-    else {
-        b.ptr = src; b.c = src[0];
-        if (n >= 3) b.c += (uint32_t)src[2] << 16;
-        if (n >= 2) b.c += (uint32_t)src[1] << 8;
-        b.used += (uint32_t)(4 - n) * 8;
-    }
-    return true;
-}
-static uint32_t bitRead(Bits &b, uint32_t n) { const uint32_t v = ((b.c << (b.used & 31)) >> 1) >> ((31 - n) & 31); b.used += n; return v; }
-enum { B_unfinished, B_end, B_completed, B_overflow };
-static int bitReload(Bits &b)
-{
-    if (b.used > 32) return B_overflow;
-    if (b.ptr >= b.limit) { b.ptr -= b.used >> 3; b.used &= 7; b.c = h_rd32(b.ptr); return B_unfinished; }
-    if (b.ptr == b.start) return b.used < 32 ? B_end : B_completed;
-    uint32_t nb = b.used >> 3; int r = B_unfinished;
-    if (b.ptr - nb < b.start) { nb = (uint32_t)(b.ptr - b.start); r = B_end; }
-    b.ptr -= nb; b.used -= nb * 8; b.c = h_rd32(b.ptr);
-    return r;
-}
-// FseDecompress.cs:111-332 for the Huffman weights (tableLog <= 6): the weights decoded, or kErr
-static size_t fseWeights(uint8_t *dst, size_t cap, const uint8_t *src, size_t n)
-{
-    int16_t norm[256]; uint32_t maxSV = 255, tableLog;
-    const size_t nc = readNCount(norm, &maxSV, &tableLog, src, n);
-    if (nc == kErr || tableLog > 6) return kErr;
-    src += nc; n -= nc;
-    struct Cell { uint16_t next; uint8_t sym, bits; } cells[64];
-    uint16_t symNext[256];
-    const uint32_t size = 1u << tableLog, mask = size - 1, step = (size >> 1) + (size >> 3) + 3;
-    uint32_t high = size - 1, pos = 0;
-    for (uint32_t s = 0; s <= maxSV; s++) { if (norm[s] == -1) { cells[high--].sym = (uint8_t)s; symNext[s] = 1; } else symNext[s] = (uint16_t)norm[s]; }
-    for (uint32_t s = 0; s <= maxSV; s++)
-        for (int i = 0; i < norm[s]; i++) { cells[pos].sym = (uint8_t)s; pos = (pos + step) & mask; while (pos > high) pos = (pos + step) & mask; }
-    if (pos != 0) return kErr;
-    for (uint32_t u = 0; u < size; u++) { const uint32_t ns = symNext[cells[u].sym]++; cells[u].bits = (uint8_t)(tableLog - hb(ns)); cells[u].next = (uint16_t)((ns << cells[u].bits) - size); }
-    Bits b;
-    if (!bitInit(b, src, n)) return kErr;
-    uint32_t s1 = bitRead(b, tableLog); bitReload(b);
-    uint32_t s2 = bitRead(b, tableLog); bitReload(b);
-    auto sym = [&](uint32_t &st) { const Cell c = cells[st]; st = c.next + bitRead(b, c.bits); return c.sym; };
-    uint8_t *op = dst, *const omax = dst + cap;
-    for (; (bitReload(b) == B_unfinished) & (op < omax - 3); op += 4) {
-        op[0] = sym(s1); op[1] = sym(s2);
-        if (bitReload(b) > B_unfinished) { op += 2; break; }
-        op[2] = sym(s1); op[3] = sym(s2);
-    }
-    for (;;) {
-        if (op > omax - 2) return kErr;
-        *op++ = sym(s1);
-        if (bitReload(b) == B_overflow) { *op++ = sym(s2); break; }
-        if (op > omax - 2) return kErr;
-        *op++ = sym(s2);
-        if (bitReload(b) == B_overflow) { *op++ = sym(s1); break; }
-    }
-    return (size_t)(op - dst);
-}
-// EntropyCommon.cs:198-269 (HUF_readStats) with the table-log limit of HUF_readDTableX4: bytes of the table description, or kErr.
-// ent: receives the weights (the implied last one included) and the table log
-static size_t hufTable(const uint8_t *ip, size_t n, ZsCDictEntropy *ent = nullptr)
-{
-    uint8_t w[256]; size_t iSize, oSize;
-    if (!n) return kErr;
-    iSize = ip[0];
-    if (iSize >= 128) {
-        oSize = iSize - 127; iSize = (oSize + 1) / 2;
-        if (iSize + 1 > n || oSize >= 256) return kErr;
-        for (uint32_t k = 0; k < oSize; k += 2) { w[k] = ip[1 + k / 2] >> 4; w[k + 1] = ip[1 + k / 2] & 15; }
-    } else {
-        if (iSize + 1 > n) return kErr;
-        oSize = fseWeights(w, 255, ip + 1, iSize);
-        if (oSize == kErr) return kErr;
-    }
-    uint32_t rank[13] = {}, total = 0;
-    for (size_t k = 0; k < oSize; k++) { if (w[k] >= 12) return kErr; rank[w[k]]++; total += (1u << w[k]) >> 1; }
-    if (total == 0) return kErr;
-    const uint32_t tableLog = hb(total) + 1;
-    if (tableLog > 12) return kErr;
-    const uint32_t rest = (1u << tableLog) - total;
-    if ((1u << hb(rest)) != rest) return kErr;
-    rank[hb(rest) + 1]++;
-    if (rank[1] < 2 || (rank[1] & 1)) return kErr;
-    if (ent) { memcpy(ent->weights, w, oSize); ent->weights[oSize] = (uint8_t)(hb(rest) + 1); ent->nWeights = (uint32_t)oSize + 1; ent->hufLog = tableLog; }
-    return iSize + 1;
-}
-}
-// 0, or ZSMI_error_dictionary_corrupted
-static int parseCompressDict(const uint8_t *d, size_t size, ZsCompressDict &out, ZsCDictEntropy *ent = nullptr)
-{
+    if (!c->dDictRec.reserve(sizeof(ZsDictRecord)) || !c->hDictRec.reserve(sizeof(ZsDictRecord))) return ZSMI_error_memory_allocation;
+    LAUNCH(c, "k_dict_load", k_dict_load, dim3(1), dim3(64), 0, (const uint8_t *)dDict, (uint32_t)dictSize, (ZsDictRecord *)c->dDictRec.p, img);
+    if (hipMemcpyAsync(c->hDictRec.p, c->dDictRec.p, sizeof(ZsDictRecord), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    const ZsDictRecord &r = *(const ZsDictRecord *)c->hDictRec.p;
+    if (r.status) return (int)r.status;
     out = ZsCompressDict();
-    if (size >= 8 && h_rd32(d) == 0xEC30A437u) {
-        out.dictID = h_rd32(d + 4);
-        if (size <= 8) return ZSMI_error_dictionary_corrupted;
-        const uint8_t *p = d + 8, *const end = d + size;
-        const size_t hs = hdict::hufTable(p, (size_t)(end - p), ent);
-        if (hs == hdict::kErr) return ZSMI_error_dictionary_corrupted;
-        p += hs;
-        const uint32_t maxes[3] = { 31, 52, 35 }, logs[3] = { 8, 9, 9 };     // offsets, match lengths, literal lengths
-        for (int t = 0; t < 3; t++) {
-            int16_t norm[256]; uint32_t mx = maxes[t], lg;
-            const size_t h = hdict::readNCount(norm, &mx, &lg, p, (size_t)(end - p));
-            if (h == hdict::kErr || mx > maxes[t] || lg > logs[t]) return ZSMI_error_dictionary_corrupted;
-            if (ent) { const int k = t == 0 ? 1 : (t == 1 ? 2 : 0); memcpy(ent->norm[k], norm, sizeof(int16_t) * (mx + 1)); ent->maxSym[k] = mx; ent->tableLog[k] = lg; }     // (the encoder's order: LL, OF, ML)
-            p += h;
-        }
-        if (p + 12 > end) return ZSMI_error_dictionary_corrupted;
-        const size_t contentSize = (size_t)(end - (p + 12));
-        for (int i = 0; i < 3; i++) { const uint32_t r = h_rd32(p + 4 * i); if (r == 0 || r >= contentSize) return ZSMI_error_dictionary_corrupted; out.rep[i] = r; }
-        p += 12;
-        out.contentOff = (uint32_t)(p - d);
-    }
-    out.contentSize = (uint32_t)(size - out.contentOff);
+    out.dBytes = (const uint8_t *)dDict; out.contentOff = r.contentOff; out.contentSize = (uint32_t)dictSize - r.contentOff; out.dictID = r.dictID;
+    for (int i = 0; i < 3; i++) out.rep[i] = r.rep[i];
     return 0;
 }
 
@@ -582,8 +426,8 @@ extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uin
 {
     return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr);
 }
-// dDict: device memory.  Its bytes are read back to the host to be parsed (a formatted dictionary's ID, recent offsets and content
-// offset): the call waits for the context's stream once.
+// dDict: device memory.  The dictionary loader runs over it and its record (a formatted dictionary's ID, recent offsets and content
+// offset, or the refusal) is read back: the call waits for the context's stream once.
 extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                   uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
                                                   const void *dDict, size_t dictSize)
@@ -592,17 +436,14 @@ extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc,
     if (!c) return ZSMI_error_init_missing;
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    std::vector<uint8_t> h(dictSize);
-    if (hipMemcpyAsync(h.data(), dDict, dictSize, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     ZsCompressDict d;
-    if (const int e = parseCompressDict(h.data(), dictSize, d)) return e;
-    d.dBytes = (const uint8_t *)dDict;
+    if (const int e = loadDict(c, dDict, dictSize, d)) return e;
     return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &d);
 }
 
-// ---- digested dictionaries (ZSTD_createCDict / ZSTD_compress_usingCDict): parsed once, everything a call needs kept in device memory - the
+// ---- digested dictionaries (ZSTD_createCDict / ZSTD_compress_usingCDict): loaded once, everything a call needs kept in device memory - the
 // bytes, the prefix's candidate-table images for the bound level's LZ shape, and for a formatted dictionary its entropy tables in encoder
-// form (k_cdict_tables).  Read-only after creation: any context of the same device may use it, from any thread. ----
+// form (k_cdict_tables, from the loader's record).  Read-only after creation: any context of the same device may use it, from any thread. ----
 struct zsmi_cdict {
     int device = 0, level = 3;
     bool empty = false;                  // no bytes: its calls are the plain calls at its level
@@ -619,17 +460,16 @@ extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t di
         cd = new zsmi_cdict();
         cd->device = c->device; cd->level = level;
         if (!dict || dictSize == 0) { cd->empty = true; break; }
-        ZsCDictEntropy ent; memset(&ent, 0, sizeof ent);
-        if ((code = parseCompressDict((const uint8_t *)dict, dictSize, cd->d, &ent))) break;
-        const bool formatted = cd->d.contentOff != 0;
         if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if (!cd->dBytes.reserve(dictSize + 64) || !cd->dImg.reserve(kDictImgBytes) || (formatted && !cd->dTables.reserve(sizeof(ZsCDictTables)))) { code = ZSMI_error_memory_allocation; break; }
+        if (!cd->dBytes.reserve(dictSize + 64) || !cd->dImg.reserve(kDictImgBytes)) { code = ZSMI_error_memory_allocation; break; }
         if (hipMemcpyAsync(cd->dBytes.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        cd->d.dBytes = (const uint8_t *)cd->dBytes.p;
+        if ((code = loadDict(c, cd->dBytes.p, dictSize, cd->d))) break;
+        const bool formatted = cd->d.contentOff != 0;
+        if (formatted && !cd->dTables.reserve(sizeof(ZsCDictTables))) { code = ZSMI_error_memory_allocation; break; }
         launchDictTables(c, cd->d, level, cd->dImg.p);
         cd->d.dImg = (const uint32_t *)cd->dImg.p;
         if (formatted) {
-            LAUNCH(c, "k_cdict_tables", k_cdict_tables, dim3(1), dim3(256), 0, ent, (ZsCDictTables *)cd->dTables.p);
+            LAUNCH(c, "k_cdict_tables", k_cdict_tables, dim3(1), dim3(256), 0, &((const ZsDictRecord *)c->dDictRec.p)->ent, (ZsCDictTables *)cd->dTables.p);
             cd->d.dTables = (const ZsCDictTables *)cd->dTables.p;
         }
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
@@ -887,8 +727,8 @@ extern "C" int zsmi_decompressBatchDevice_usingDict(zsmi_ctx *c, const void *dSr
     return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, dDict, (uint32_t)dictSize);
 }
 
-// ---- digested decode dictionaries (ZSTD_createDDict / ZSTD_decompress_usingDDict): parsed and checked once on the host, the bytes and the image
-// the fast kernels' dictionary forms read (ZsDDictImage, k_ddict_tables) kept in device memory.  Read-only after creation: any context of the
+// ---- digested decode dictionaries (ZSTD_createDDict / ZSTD_decompress_usingDDict): loaded and checked once (loadDict), the bytes and the image
+// the fast kernels' dictionary forms read (ZsDDictImage, filled by the same run of k_dict_load) kept in device memory.  Read-only after creation: any context of the
 // same device may use it, from any thread.  A call with one queues its work and returns - nothing is read back, nothing waited for - and its
 // dictionary frames take the fast path; what the fast kernels give up goes to k_decode_frames_dict with the same bytes, as in a _usingDict call. ----
 struct zsmi_ddict {
@@ -908,15 +748,13 @@ extern "C" zsmi_ddict *zsmi_createDDict(zsmi_ctx *c, const void *dict, size_t di
         if (!dd) { code = ZSMI_error_memory_allocation; break; }
         dd->device = c->device;
         if (!dict || dictSize == 0) { dd->empty = true; break; }
-        ZsCompressDict d;
-        if ((code = parseCompressDict((const uint8_t *)dict, dictSize, d))) break;
-        dd->dictID = d.dictID; dd->dictSize = (uint32_t)dictSize;
         if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
         if (!dd->dBytes.reserve(dictSize + 64) || !dd->dImg.reserve(sizeof(ZsDDictImage))) { code = ZSMI_error_memory_allocation; break; }
         if (hipMemcpyAsync(dd->dBytes.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        LAUNCH(c, "k_ddict_tables", k_ddict_tables, dim3(1), dim3(64), 0, (const uint8_t *)dd->dBytes.p, (uint32_t)dictSize, d.contentOff, d.dictID,
-               d.rep[0], d.rep[1], d.rep[2], (ZsDDictImage *)dd->dImg.p);
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
+        ZsCompressDict d;
+        if ((code = loadDict(c, dd->dBytes.p, dictSize, d, (ZsDDictImage *)dd->dImg.p))) break;
+        dd->dictID = d.dictID; dd->dictSize = (uint32_t)dictSize;
+        if (hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
     } while (0);
     if (code) { delete dd; dd = nullptr; }
     if (err) *err = code;
@@ -1035,19 +873,22 @@ static int staged(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, cons
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     return copyBack(c, (const uint8_t *)c->sDst.p, dof.data(), (uint8_t *)dst, dstOffsets, dstSizes, n);
 }
-// dict: the call's dictionary, or nullptr.  hostDict (the _usingDict form): its bytes, which this call stages; dict's other members come from their parse
+// the destination slots a compress call is staged with: every chunk's bound
+static std::vector<uint32_t> compressBounds(const uint32_t *srcSizes, uint32_t n)
+{
+    std::vector<uint32_t> bounds(n);
+    for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
+    return bounds;
+}
+// dict: the call's dictionary (a digested one's descriptor), or nullptr
 static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, void *dst, const uint64_t *dstOffsets,
-                                 uint32_t *dstSizes, int level, const ZsCompressDict *dict, const void *hostDict = nullptr, size_t hostDictSize = 0)
+                                 uint32_t *dstSizes, int level, const ZsCompressDict *dict)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
-    std::vector<uint32_t> bounds(n);
-    for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
-    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes, hostDict, hostDictSize,
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, compressBounds(srcSizes, n).data(), dstSizes, nullptr, 0,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      ZsCompressDict d = dict ? *dict : ZsCompressDict();
-                      if (hostDict) d.dBytes = (const uint8_t *)c->sDict.p;
-                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict ? &d : nullptr);
+                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict);
                   });
 }
 extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
@@ -1055,6 +896,8 @@ extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64
 {
     return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr);
 }
+// the dictionary is staged with the sources, and the run step is the device form on the staged bytes (which loads and checks them: its one
+// wait, then the staged call's own for the results)
 extern "C" int zsmi_compressBatchHost_usingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                 uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
                                                 const void *dict, size_t dictSize)
@@ -1062,9 +905,10 @@ extern "C" int zsmi_compressBatchHost_usingDict(zsmi_ctx *c, const void *src, co
     if (!dict || dictSize == 0) return zsmi_compressBatchHost(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level);
     if (!c) return ZSMI_error_init_missing;
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    ZsCompressDict d;
-    if (const int e = parseCompressDict((const uint8_t *)dict, dictSize, d)) return e;
-    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, &d, dict, dictSize);
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, compressBounds(srcSizes, n).data(), dstSizes, dict, dictSize,
+                  [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
+                      return zsmi_compressBatchDevice_usingDict(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, c->sDict.p, dictSize);
+                  });
 }
 extern "C" int zsmi_compressBatchHost_usingCDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                  uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, const zsmi_cdict *cd)

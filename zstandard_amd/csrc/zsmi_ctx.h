@@ -73,6 +73,7 @@ struct zsmi_ctx {
         bool reserve(uint32_t cap);            // cap: blocks of a sub-batch
     } scratch;
     DevBuf dDictImg;                       // a _usingDict call's candidate-table images of the prefix (a digested dictionary holds its own)
+    DevBuf dDictRec; PinBuf hDictRec;      // the dictionary loader's record (ZsDictRecord: k_dict_load writes it, loadDict in zsmi_api.hip reads it back)
     int stopAfterWalk = 0;                 // ZSMI_STOP_AFTER_WALK (debug-hooks build, tools/walk_check.py): the entropy kernels are not launched
     int stopLit = 0, stopSeq = 0;          // timing aids of a -DZSMI_DEBUG_HOOKS build (ZSMI_STOP_LIT / ZSMI_STOP_SEQ): end a kernel after a stage; always 0 in the product
     // decompress workspace: the item list (on the host: two pinned buffers taken in turn) and the scratch of a sub-batch, whose sizes for a
@@ -127,8 +128,9 @@ static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz
 #define LAUNCH(ctx, name, kernel, grid, block, lds, ...) LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, lds, __VA_ARGS__)
 
 // ---- the batch calls in device memory (zsmi_api.hip: the compress and the decompress section state their arguments) ----
-// A dictionary as the compress launch sequence takes it (nullptr: none).  dBytes: its bytes in device memory; contentOff .. rep: what
-// parseCompressDict found in them (raw content: all of it, no ID, offsets {1, 4, 8}).  dImg, dTables: a digested dictionary's (zsmi_cdict) - the
+// A dictionary as the compress launch sequence takes it (nullptr: none).  dBytes: its bytes in device memory; contentOff .. rep: what the
+// device's dictionary loader found in them (loadDict in zsmi_api.hip copies its record: the host parses no dictionary; raw content: all of
+// it, no ID, offsets {1, 4, 8}).  dImg, dTables: a digested dictionary's (zsmi_cdict) - the
 // prefix's candidate-table images, built once and not by the call, and a formatted one's entropy tables in encoder form.
 struct ZsCDictTables;
 struct ZsCompressDict {

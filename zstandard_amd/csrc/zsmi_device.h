@@ -59,6 +59,20 @@ struct ZsRangeHdr { uint32_t nseq, trailing, litSum, first; };
 // per-block result of the encode kernel
 struct ZsBlockResult { uint32_t payloadSize; uint32_t type; /* 0 raw, 1 rle, 2 compressed */ uint32_t rleByte; uint32_t pad; };
 
+// What the dictionary loader (loadDictEntropy, decode_kernels.hip) found in a dictionary's bytes, as k_dict_load (decode_fast.hip) leaves
+// it in device memory for the host: the verdict and the header fields, and a formatted dictionary's entropy section as the decoder reads it,
+// which k_cdict_tables (entropy_kernels.hip) turns into encoder tables.
+struct ZsCDictEntropy {
+    uint8_t weights[256]; uint32_t nWeights, hufLog;           // Huffman weights, the implied last one included
+    int16_t norm[3][64]; uint32_t maxSym[3], tableLog[3];      // normalised counts of LL, OF, ML (-1: low probability)
+};
+struct ZsDictRecord {
+    uint32_t status;                 // 0, or 30 (dictionary_corrupted): nothing else is valid then
+    uint32_t dictID, contentOff;     // raw content: 0, 0
+    uint32_t rep[3];
+    ZsCDictEntropy ent;              // contentOff != 0 only
+};
+
 // unaligned loads.  memcpy keeps the alignment-1 fact visible to the compiler: a cast to an over-aligned
 // pointer lets it turn a wave-uniform address into a scalar load, which drops the low address bits.
 __device__ __forceinline__ uint32_t zs_load32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
