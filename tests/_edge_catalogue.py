@@ -67,6 +67,18 @@ def catalogue():
     add("fcs_4gib", fam, W.frame([W.raw(txt[:300])], fcs=1 << 32, fcs_bytes=8), expect=COR, cap=400)
     add("fcs_4gib_minus1", fam, W.frame([W.raw(txt[:300])], fcs=(1 << 32) - 1, fcs_bytes=4), expect=COR, cap=400)
     add("bad_magic", fam, W.frame([W.raw(txt[:40])], magic=0xFD2FB527), expect=10, cap=40)
+    # the order of refusals inside a header - too few bytes for it and a block header, then the reserved bit, then the window log: three
+    # header shapes (and the windowed one with window log 31) over one 40-byte raw block, each cut to every length from 5 bytes up to the
+    # header and the block header, as written and with the reserved bit set (the windowed shape's 2-byte content size cannot say 40)
+    for shape, hs, kw in [("single_did4_fcs8", 17, dict(dict_id=0, dict_bytes=4, fcs_bytes=8)), ("window_fcs2", 8, dict(single=False, window=(0, 0), fcs=300)),
+                          ("single_fcs1", 6, {}), ("windowlog31_fcs2", 8, dict(single=False, window=(21, 0), fcs=300))]:
+        for res in (False, True):
+            f, c = W.frame([W.raw(txt[:40])], reserved=res, **kw)
+            assert W.frame_header(f).end == hs
+            whole = PAR if res else WIN if "log31" in shape else COR if "fcs" in kw else "ok"
+            add(f"{shape}{'_reserved' if res else ''}", fam, (f, c), expect=whole, cap=40)
+            for n in range(5, hs + 4):
+                add(f"{shape}{'_reserved' if res else ''}_cut{n}", fam, (f, c), expect=SRC if n < hs + 3 or whole in ("ok", COR) else whole, cap=40, frame=f[:n])
 
     # ---- checksum (XXH64 tails: 32-byte stripes, 8-, 4- and 1-byte rests)
     fam = "checksum"
@@ -147,6 +159,18 @@ def catalogue():
                                             W.comp(W.Lit("treeless", txt[1000:1400]), W.Seqs([(10, 20, 12)]))]))
     add("treeless_first", fam, W.frame([W.comp(W.Lit("treeless", txt[:500]))]), expect=DIC, cap=500)
     add("treeless_after_raw_only", fam, W.frame([W.comp(W.Lit("raw", txt[:500])), W.comp(W.Lit("treeless", txt[:500]))]), expect=DIC, cap=1000)
+
+    # a literals header the block is too short for: a compressed block of 3 and of 4 bytes that announces Huffman (a block below 5 bytes) or
+    # treeless literals (first in its frame: no table comes before that; behind a Huffman block: too short again) in each size format, and
+    # RLE literals with the 3-byte header in a block of 3 bytes (no room for the byte)
+    for n in (3, 4):
+        for sf in range(4):
+            for t, kind in ((2, "huf"), (3, "treeless")):
+                add(f"short{n}_{kind}_sf{sf}", fam, (_as_compressed(W.frame([W.raw(bytes([t | sf << 2]) + bytes(n - 1))])[0], 0), None),
+                    expect=COR if t == 2 else DIC, cap=200)
+            add(f"short{n}_treeless_after_huf_sf{sf}", fam,
+                (_as_compressed(W.frame([W.comp(W.Lit("huf", txt[:100])), W.raw(bytes([3 | sf << 2]) + bytes(n - 1))])[0], 1), None), expect=COR, cap=200)
+    add("rle_sf3_in_3_bytes", fam, (_as_compressed(W.frame([W.raw((1 | 3 << 2 | 5 << 4).to_bytes(3, "little"))])[0], 0), None), expect=COR, cap=200)
 
     # ---- sequences
     fam = "sequences"
@@ -240,6 +264,15 @@ def catalogue():
     add("only_skippable", fam, (W.skippable(b"abc"), b""))
     add("second_frame_bad", fam, (f1 + f2[:-3], c1), expect=SRC, cap=len(c1 + c2))
     return E
+
+
+def _as_compressed(frame, index):
+    """the frame with its raw block number `index` called a compressed block: the same bytes, read as a literals section"""
+    b = bytearray(frame)
+    blk = list(W.blocks(frame))[index]
+    assert blk.type == 0
+    b[blk.pos - 3] |= 2 << 1
+    return bytes(b)
 
 
 def _patch_mode_byte(frame, symbol):

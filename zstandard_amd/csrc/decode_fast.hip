@@ -121,37 +121,25 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
     #define DSET(field, value) do { if (lane == 0) dp->field = (value); } while (0)
     uint32_t prepWhy = 0;                                      // source line of the test that left the fast path (ZsFastDesc.why = 1000 + line: tools/dec_why.py)
     #define ZS_PREP_WHY(line) do { prepWhy = 1000u + (uint32_t)(line); } while (0)
-    if (lane < 36) L.llTab[lane] = d_LL_base[lane] | ((uint32_t)d_LL_bits[lane] << 24);
-    if (lane < 53) L.mlTab[lane] = d_ML_base[lane] | ((uint32_t)d_ML_bits[lane] << 24);
-    wave_sync();
+    zs_lds_length_tables(L);
 #ifdef ZS_PREP_PROFILE
     if (lane == 0) { for (int k = 0; k < 12; k++) L.pp[k] = 0; L.ppMark = __builtin_amdgcn_s_memtime(); }
     const unsigned long long ppStart = __builtin_amdgcn_s_memtime();
 #endif
     bool ok = false; uint32_t nBlocks = 0;
     do {
-        // ---- frame header (:389-499): one frame, no dictionary (DD: none, or the call's) ----
-        if (srcSize < 5 + 1 + 3 || rd32(src) != 0xFD2FB528u) { ZS_PREP_WHY(__LINE__); break; }
-        const uint32_t fhd = src[4];
-        const uint32_t dictIDCode = fhd & 3, checksumFlag = (fhd >> 2) & 1, singleSegment = (fhd >> 5) & 1, fcsID = fhd >> 6;
-        if ((!DD && dictIDCode) || (fhd & 0x08)) { ZS_PREP_WHY(__LINE__); break; }
-        const uint32_t didSize = DD ? (dictIDCode == 3 ? 4u : dictIDCode) : 0u;
-        const uint32_t tail = checksumFlag ? 4u : 0u;              // the checksum behind the last block
-        const uint32_t fcsSize = fcsID == 0 ? 0 : (fcsID == 1 ? 2 : (fcsID == 2 ? 4 : 8));
-        const uint32_t fhs = 5 + !singleSegment + didSize + fcsSize + (singleSegment && !fcsID);
-        if (srcSize < fhs + 3 + tail) { ZS_PREP_WHY(__LINE__); break; }
-        uint32_t pos = 5;
-        if (!singleSegment) { const uint32_t wl = src[pos++]; if ((wl >> 3) + 10 > 30) { ZS_PREP_WHY(__LINE__); break; } }
-        if (DD && dictIDCode) {                                     // (:632-634: a frame that names another dictionary is dictionary_wrong, the general kernel's to say)
-            const uint32_t id = dictIDCode == 1 ? (uint32_t)src[pos] : (dictIDCode == 2 ? rd16(src + pos) : rd32(src + pos));
-            pos += didSize;
-            if (id != 0 && id != dd->dictID) { ZS_PREP_WHY(__LINE__); break; }
+        // ---- frame header: one frame, no dictionary named (DD: none, or the call's); what the header reader refuses is the general kernel's to say ----
+        if (srcSize < 5 || rd32(src) != 0xFD2FB528u) { ZS_PREP_WHY(__LINE__); break; }
+        const ZsFrameHeader fh = zs_read_frame_header(src, srcSize, 3);
+        if (fh.status) { ZS_PREP_WHY(__LINE__); break; }
+        if (fh.dictID != 0 && (!DD || fh.dictID != dd->dictID)) { ZS_PREP_WHY(__LINE__); break; }     // (:632-634: a frame that names another dictionary is dictionary_wrong, the general kernel's to say)
+        const uint32_t tail = fh.checksumFlag ? 4u : 0u;            // the checksum behind the last block
+        if (srcSize < fh.headerSize + 3 + tail) { ZS_PREP_WHY(__LINE__); break; }
+        if (fh.contentSize != ~0ull && fh.contentSize > 0xFFFFFFFFull) { ZS_PREP_WHY(__LINE__); break; }
+        {   ZsFastDesc *dp = descs + item;                          // what the frame header says: in the descriptor of block 0
+            DSET(why, 0u); DSET(hasContentSize, fh.contentSize != ~0ull); DSET(contentSize, (uint32_t)fh.contentSize); DSET(hasChecksum, fh.checksumFlag); DSET(checksum, fh.checksumFlag ? rd32(src + srcSize - 4) : 0u);
         }
-        uint64_t fcs = ~0ull;
-        if (fcsID == 0) { if (singleSegment) fcs = src[pos]; } else if (fcsID == 1) fcs = rd16(src + pos) + 256; else if (fcsID == 2) fcs = rd32(src + pos); else fcs = zs_load64(src + pos);
-        if (fcs != ~0ull && fcs > 0xFFFFFFFFull) { ZS_PREP_WHY(__LINE__); break; }
-        const uint32_t hasContentSize = fcs != ~0ull, contentSize = (uint32_t)fcs;
-        uint32_t b0 = fhs;                                          // offset of the next block header in the item
+        uint32_t b0 = fh.headerSize;                                // offset of the next block header in the item
         bool fail = false;
         // tables a later block may repeat (literals type 3, sequence mode 3: ZStdDecompress.cs:696-697, 1062-1064): the slot that holds the frame's
         // current Huffman table, the slot of the last block that had sequences (it holds all three sequence tables, built or copied) and their logs.
@@ -170,51 +158,40 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
             fail = true;
             const size_t slot = (size_t)blk * cap + item;
             ZsFastDesc *dp = descs + slot;
-            if (blk == 0) { DSET(why, 0u); DSET(hasContentSize, hasContentSize); DSET(contentSize, contentSize); DSET(hasChecksum, checksumFlag); DSET(checksum, checksumFlag ? rd32(src + srcSize - 4) : 0u); }
             // ---- a block (:646-659): compressed; the last one fills the rest of the item ----
             if ((uint64_t)b0 + 3 + tail > srcSize) { ZS_PREP_WHY(__LINE__); break; }
-            const uint32_t bh = rd24(src + b0);
-            const uint32_t lastBlock = bh & 1, btype = (bh >> 1) & 3, cSize = bh >> 3;
+            const ZsBlockHeader bh = zs_read_block_header(src + b0);
+            const uint32_t lastBlock = bh.last, btype = bh.type, cSize = bh.size;
             if (btype == 3) { ZS_PREP_WHY(__LINE__); break; }
+            // its size (compressed: 3 .. 128 KiB - 1; RLE: what the slot's literal buffer holds, it is spread there), its end inside the item - the last block's AT the item's -, a slot for a block behind it
+            const uint64_t bend = (uint64_t)b0 + 3 + bh.payload + tail;
+            if ((btype == 2 ? (cSize >= (1u << 17) || cSize < 3) : (cSize > (1u << 17) || (btype == 1 && cSize > litCap)))
+                || bend > srcSize || (lastBlock && bend != srcSize) || (!lastBlock && blk + 1 == maxBlocks)) { ZS_PREP_WHY(__LINE__); break; }
+            b0 += 3;                                                // block payload offset in the item
             if (btype != 2) {
                 // a raw or RLE block among the compressed ones (:2043-2056): to the kernels behind this one a block of nothing but literals - raw
                 // literals at the block's bytes, or RLE literals of its byte - and no sequences; the entropy tables a later block may repeat stay
-                const uint32_t csz = btype == 1 ? 1u : cSize;
-                if (cSize > (1u << 17) || (btype == 1 && cSize > litCap)) { ZS_PREP_WHY(__LINE__); break; }       // (an RLE block is spread through the slot's literal buffer)
-                if ((uint64_t)b0 + 3 + csz + tail > srcSize) { ZS_PREP_WHY(__LINE__); break; }
-                if (lastBlock && (uint64_t)b0 + 3 + csz + tail != srcSize) { ZS_PREP_WHY(__LINE__); break; }
-                if (!lastBlock && blk + 1 == maxBlocks) { ZS_PREP_WHY(__LINE__); break; }
-                b0 += 3;
                 DSET(litType, btype == 0 ? 0u : 1u); DSET(litSrc, btype == 0 ? b0 : (uint32_t)src[b0]); DSET(litSize, cSize); DSET(nStreams, 0u);
                 DSET(nbSeq, 0u); DSET(seqOff, 0u); DSET(seqSize, 0u); DSET(llLog, 0u); DSET(ofLog, 0u); DSET(mlLog, 0u); DSET(hufFlat, 0u);
                 DSET(fast, 1u);
                 nBlocks = blk + 1; if (lane == 0) L.misc[14] = L.misc[14] + 1;
-                b0 += csz;
+                b0 += bh.payload;
                 fail = false;
                 if (lastBlock) break;
                 continue;
             }
-            if (cSize >= (1u << 17) || cSize < 3) { ZS_PREP_WHY(__LINE__); break; }
-            if ((uint64_t)b0 + 3 + cSize + tail > srcSize) { ZS_PREP_WHY(__LINE__); break; }
-            if (lastBlock && (uint64_t)b0 + 3 + cSize + tail != srcSize) { ZS_PREP_WHY(__LINE__); break; }
-            if (!lastBlock && blk + 1 == maxBlocks) { ZS_PREP_WHY(__LINE__); break; }           // more blocks than slots: general kernel
-            b0 += 3;                                                // block payload offset in the item
             const uint8_t *bs = src + b0;
-            // ---- literals section header (:683-821) ----
-            uint32_t litCSizeTot;
+            // ---- literals section (:683-821) ----
+            const ZsLiteralsHeader lh = zs_read_literals_header(bs, cSize);
+            if (lh.status || (lh.type != 0 && lh.regenSize > litCap)) { ZS_PREP_WHY(__LINE__); break; }      // (raw literals stay in the source: no slot bytes)
+            const uint32_t litCSizeTot = lh.headerSize + lh.compSize;
             {
-                const uint32_t type = bs[0] & 3, lhl = (bs[0] >> 2) & 3;
+                const uint32_t type = lh.type, lhSize = lh.headerSize, litSize = lh.regenSize;
                 if (type == 3 && L.misc[11] == 0) { ZS_PREP_WHY(__LINE__); break; }            // a repeated Huffman table without one before it: the general kernel says what is wrong
                 const bool hufOfDict = DD && type == 3 && L.misc[11] == ZS_DD_SLOT;             // the dictionary's table is still the current one
                 if (hufOfDict && (L.misc[13] >> 16)) { ZS_PREP_WHY(__LINE__); break; }           // ... and the image does not hold it (log above ZS_FAST_HUFLOG)
                 if (type >= 2) {
-                    if (cSize < 5) { ZS_PREP_WHY(__LINE__); break; }
-                    const uint32_t lhc = rd32(bs);
-                    uint32_t lhSize, litSize, litCSize; bool single = false;
-                    if (lhl < 2) { single = !lhl; lhSize = 3; litSize = (lhc >> 4) & 0x3FF; litCSize = (lhc >> 14) & 0x3FF; }
-                    else if (lhl == 2) { lhSize = 4; litSize = (lhc >> 4) & 0x3FFF; litCSize = lhc >> 18; }
-                    else { lhSize = 5; litSize = (lhc >> 4) & 0x3FFFF; litCSize = (lhc >> 22) + ((uint32_t)bs[4] << 10); }
-                    if (litSize > litCap || litCSize + lhSize > cSize) { ZS_PREP_WHY(__LINE__); break; }
+                    const uint32_t litCSize = lh.compSize; const bool single = lh.single;
                     if (!single && (litSize == 0 || litCSize == 0)) { ZS_PREP_WHY(__LINE__); break; }
                     uint16_t *ht = reinterpret_cast<uint16_t *>(hufTabs + slot * ZS_FAST_HUFTAB_BYTES);
                     uint32_t h = 0;
@@ -243,36 +220,23 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
                     DSET(litType, 2u); DSET(litSize, litSize); DSET(hufLog, L.misc[13] & 0xFFu);
                     if (single) { DSET(nStreams, 1u); DSET(sOff[0], cs0); DSET(sLen[0], csz); DSET(sCnt[0], litSize); DSET(sOut[0], 0u); }
                     else {
-                        if (csz < 10) { ZS_PREP_WHY(__LINE__); break; }
-                        const uint8_t *cs = src + cs0;
-                        const uint32_t l1 = rd16(cs), l2 = rd16(cs + 2), l3 = rd16(cs + 4);
-                        if (l1 + l2 + l3 + 6 > csz) { ZS_PREP_WHY(__LINE__); break; }
-                        const uint32_t seg = (litSize + 3) / 4;
-                        if (3 * seg > litSize) { ZS_PREP_WHY(__LINE__); break; }
+                        const ZsStreamSplit sp = zs_read_stream_split(src + cs0, csz, litSize); if (sp.status) { ZS_PREP_WHY(__LINE__); break; }
                         if (lane == 0) {
                             dp->nStreams = 4;
-                            dp->sOff[0] = cs0 + 6; dp->sOff[1] = cs0 + 6 + l1; dp->sOff[2] = cs0 + 6 + l1 + l2; dp->sOff[3] = cs0 + 6 + l1 + l2 + l3;
-                            dp->sLen[0] = l1; dp->sLen[1] = l2; dp->sLen[2] = l3; dp->sLen[3] = csz - (l1 + l2 + l3 + 6);
-                            for (uint32_t k = 0; k < 4; k++) { dp->sCnt[k] = k < 3 ? seg : litSize - 3 * seg; dp->sOut[k] = k * seg; }
+                            uint32_t at = cs0 + 6;
+                            for (uint32_t k = 0; k < 4; k++) { dp->sOff[k] = at; dp->sLen[k] = sp.len[k]; at += sp.len[k]; dp->sCnt[k] = k < 3 ? sp.seg : litSize - 3 * sp.seg; dp->sOut[k] = k * sp.seg; }
                         }
                     }
-                    litCSizeTot = litCSize + lhSize;
                 } else {
-                    uint32_t lhSize, litSize;
-                    if (lhl == 1) { lhSize = 2; litSize = rd16(bs) >> 4; }
-                    else if (lhl == 3) { lhSize = 3; litSize = rd24(bs) >> 4; }
-                    else { lhSize = 1; litSize = bs[0] >> 3; }
-                    if (type == 0) { if (litSize + lhSize > cSize) { ZS_PREP_WHY(__LINE__); break; } DSET(litType, 0u); DSET(litSrc, b0 + lhSize); litCSizeTot = lhSize + litSize; }
-                    else { if (lhSize + 1 > cSize || litSize > litCap) { ZS_PREP_WHY(__LINE__); break; } DSET(litType, 1u); DSET(litSrc, (uint32_t)bs[lhSize]); litCSizeTot = lhSize + 1; }
+                    DSET(litType, type); DSET(litSrc, type == 0 ? b0 + lhSize : (uint32_t)bs[lhSize]);       // raw: where the bytes lie; RLE: the byte
                     DSET(litSize, litSize); DSET(nStreams, 0u);
                 }
             }
-            if (litCSizeTot > cSize) { ZS_PREP_WHY(__LINE__); break; }
             // ---- sequence headers + tables (:1110-1180), then the tables leave for the sequences kernel.  st.fseEntropy stays 0: a
             //      table repeated from the block before (mode 3) is an error here and sends the item to the general kernel ----
             const uint8_t *ip = bs + litCSizeTot; uint32_t remaining = cSize - litCSizeTot, nbSeq = 0;
             const uint32_t seqPrev = L.misc[12];                    // block + 1 of the last block that had sequences (its slot holds all three tables)
-            DState st; st.rep[0] = 1; st.rep[1] = 4; st.rep[2] = 8; st.litEntropy = 0; st.fseEntropy = seqPrev != 0; st.llRepeatOk = 0; st.hufX4 = 0;
+            DState st = zs_dstate_begin(); st.fseEntropy = seqPrev != 0;
             uint16_t *stab = reinterpret_cast<uint16_t *>(seqTabs + slot * ZS_FAST_SEQTAB_BYTES);
             const uint16_t *stabPrev = seqPrev ? reinterpret_cast<const uint16_t *>(seqTabs + ((size_t)(seqPrev - 1u) * cap + item) * ZS_FAST_SEQTAB_BYTES) : nullptr;
             if (DD && seqPrev == ZS_DD_SLOT) stabPrev = reinterpret_cast<const uint16_t *>(dd->seqTab);

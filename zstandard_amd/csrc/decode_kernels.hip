@@ -17,6 +17,7 @@
 #define ZSMI_DECODE_KERNELS_HIP
 #include "zsmi_device.h"
 #include "zsmi_wave.h"
+#include "zsmi_frame.h"           // the one place a frame, block or literals-section header is read
 
 // -DZS_DEC_PROFILE: cycles per phase of each item, left in the 64 spare bytes behind its literal scratch
 // (0 literals incl. Huffman table, 1 sequence tables, 2 sequence decoding, 3 sequence execution, 4 checksum, 5 whole item)
@@ -96,6 +97,14 @@ struct DLds {
     uint16_t huf[4096];                 // byte | nbBits << 8   (HufDecompress.cs:109-113)
 };
 #define ZS_DLDS_PREP (offsetof(DLds, ML))
+// every lane of the wavefront calls, once per kernel, before its first sequence (LL_base / LL_bits, ML_base / ML_bits: ZStdInternal.cs:158-198)
+__device__ __forceinline__ void zs_lds_length_tables(DLds &L)
+{
+    const uint32_t lane = (uint32_t)zs_lane();
+    if (lane < 36) L.llTab[lane] = d_LL_base[lane] | ((uint32_t)d_LL_bits[lane] << 24);
+    if (lane < 53) L.mlTab[lane] = d_ML_base[lane] | ((uint32_t)d_ML_bits[lane] << 24);
+    wave_sync();
+}
 #ifdef ZS_PREP_PROFILE
 #define PPROF(L, k) do { if (zs_lane() == 0) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); (L).pp[k] += now_ - (L).ppMark; (L).ppMark = now_; } } while (0)
 #else
@@ -661,6 +670,7 @@ __device__ __forceinline__ bool hufDecodeStreams(DLds &L, uint32_t nStreams, uin
 }
 
 struct DState { uint32_t rep[3]; uint32_t litEntropy, fseEntropy; uint32_t llRepeatOk; uint32_t hufX4; };   // hufX4: the reference built the current Huffman table for its double-symbol decoder
+__device__ __forceinline__ DState zs_dstate_begin() { return DState{ { 1, 4, 8 }, 0, 0, 0, 0 }; }             // a frame's start (DecompressBegin :2478-2499)
 
 // ---- one tile of <= 64 decoded sequences (L.u.sq.tile*) -> output bytes.  Returns 0 or an error; advances op / litPos. ----
 // DICT: a dictionary's content is the segment in front of the frame (RefDictContent :2366, CheckContinuity :1911): offsets may reach
@@ -917,22 +927,17 @@ __device__ __forceinline__ uint32_t decodeBlock(DLds &L, DState &st, uint8_t *ds
     // ---- literals (DecodeLiteralsBlock :683-821) ----
     const uint8_t *litPtr; uint32_t litSize, litCSizeTot;
     {
-        const uint32_t type = src[0] & 3, lhl = (src[0] >> 2) & 3;
-        if (type >= 2) {
-            if (type == 3 && st.litEntropy == 0) return ZE(E_dictionary_corrupted);
-            if (srcSize < 5) return ZE(E_corruption_detected);
-            const uint32_t lhc = rd32(src);
-            uint32_t lhSize, litCSize; bool single = false;
-            if (lhl < 2) { single = !lhl; lhSize = 3; litSize = (lhc >> 4) & 0x3FF; litCSize = (lhc >> 14) & 0x3FF; }
-            else if (lhl == 2) { lhSize = 4; litSize = (lhc >> 4) & 0x3FFF; litCSize = lhc >> 18; }
-            else { lhSize = 5; litSize = (lhc >> 4) & 0x3FFFF; litCSize = (lhc >> 22) + ((uint32_t)src[4] << 10); }
-            if (litSize > (1u << 17)) return ZE(E_corruption_detected);
-            if (litCSize + lhSize > srcSize) return ZE(E_corruption_detected);
-            const uint8_t *cs = src + lhSize; uint32_t csz = litCSize;
-            if (type == 2) {
+        const ZsLiteralsHeader lh = zs_read_literals_header(src, srcSize);
+        if (lh.type == 3 && st.litEntropy == 0) return ZE(E_dictionary_corrupted);
+        if (lh.status) return ZE(lh.status);
+        litSize = lh.regenSize; litCSizeTot = lh.headerSize + lh.compSize;
+        if (litSize > (1u << 17)) return ZE(E_corruption_detected);    // (what the literal buffer holds; raw literals lie in the block, which is smaller)
+        if (lh.type >= 2) {
+            const bool single = lh.single; const uint8_t *cs = src + lh.headerSize; uint32_t csz = lh.compSize;
+            if (lh.type == 2) {
                 if (!single && litSize == 0) return ZE(E_corruption_detected);
-                if (!single && litCSize == 0) return ZE(E_corruption_detected);
-                st.hufX4 = single ? 0u : hufSelectDecoder(litSize, litCSize);      // ZStdDecompress.cs:737 (1 stream: X2) / HufDecompress.cs:1208-1220
+                if (!single && csz == 0) return ZE(E_corruption_detected);
+                st.hufX4 = single ? 0u : hufSelectDecoder(litSize, csz);           // ZStdDecompress.cs:737 (1 stream: X2) / HufDecompress.cs:1208-1220
                 const uint32_t h = readHufTable(L, cs, csz);
 #ifdef ZS_DEC_PROFILE
                 { const uint64_t now_ = __builtin_readcyclecounter(); if (g_prof) g_prof[6] += now_ - prof_t_; }
@@ -948,39 +953,22 @@ __device__ __forceinline__ uint32_t decodeBlock(DLds &L, DState &st, uint8_t *ds
             // every LDS read of the symbol loop would then wait for)
             uint32_t nStreams = 1, sOff = 0, sLen = csz, sCnt = litSize, sOut = 0;
             if (!single) {
-                if (csz < 10) return ZE(E_corruption_detected);
-                const uint32_t l1 = rd16(cs), l2 = rd16(cs + 2), l3 = rd16(cs + 4);
-                if (l1 + l2 + l3 + 6 > csz) return ZE(E_corruption_detected);
-                const uint32_t l4 = csz - (l1 + l2 + l3 + 6);
-                const uint32_t seg = (litSize + 3) / 4;
-                if (3 * seg > litSize) return ZE(E_corruption_detected);
-                const uint32_t sl = min(lane, 3u);
+                const ZsStreamSplit sp = zs_read_stream_split(cs, csz, litSize); if (sp.status) return ZE(sp.status);
+                const uint32_t sl = min(lane, 3u);                             // this lane's stream
                 nStreams = 4;
-                sOff = 6 + (sl > 0 ? l1 : 0) + (sl > 1 ? l2 : 0) + (sl > 2 ? l3 : 0);
-                sLen = sl == 0 ? l1 : (sl == 1 ? l2 : (sl == 2 ? l3 : l4));
-                sCnt = sl < 3 ? seg : litSize - 3 * seg;
-                sOut = sl * seg;
+                sOff = 6 + (sl > 0 ? sp.len[0] : 0) + (sl > 1 ? sp.len[1] : 0) + (sl > 2 ? sp.len[2] : 0);
+                sLen = sl == 0 ? sp.len[0] : (sl == 1 ? sp.len[1] : (sl == 2 ? sp.len[2] : sp.len[3]));
+                sCnt = sl < 3 ? sp.seg : litSize - 3 * sp.seg; sOut = sl * sp.seg;
             }
             const bool ok = hufDecodeStreams(L, nStreams, litBuf + sOut, sCnt, cs + sOff, sLen, st.hufX4 != 0, g_prof);
             if (__ballot(!ok)) return ZE(E_corruption_detected);
             wave_mem_sync();
-            litPtr = litBuf; st.litEntropy = 1; litCSizeTot = litCSize + lhSize;
-        } else {
-            uint32_t lhSize;
-            if (lhl == 1) { lhSize = 2; litSize = rd16(src) >> 4; }
-            else if (lhl == 3) { lhSize = 3; litSize = rd24(src) >> 4; }
-            else { lhSize = 1; litSize = src[0] >> 3; }
-            if (type == 0) {
-                if (litSize + lhSize > srcSize) return ZE(E_corruption_detected);
-                litPtr = src + lhSize; litCSizeTot = lhSize + litSize;
-            } else {
-                if (lhl == 3 && srcSize < 4) return ZE(E_corruption_detected);
-                if (litSize > (1u << 17)) return ZE(E_corruption_detected);
-                const uint8_t v = src[lhSize];
-                for (uint32_t j = lane; j < litSize; j += 64) litBuf[j] = v;
-                wave_mem_sync();
-                litPtr = litBuf; litCSizeTot = lhSize + 1;
-            }
+            litPtr = litBuf; st.litEntropy = 1;
+        } else if (lh.type == 0) litPtr = src + lh.headerSize;
+        else {
+            const uint8_t v = src[lh.headerSize];
+            for (uint32_t j = lane; j < litSize; j += 64) litBuf[j] = v;
+            wave_mem_sync(); litPtr = litBuf;
         }
     }
     PROF_ADD(0);
@@ -1152,25 +1140,12 @@ __device__ __forceinline__ void zs_decode_item(DLds &L, const uint32_t item, con
             }
             DONE(ZE(E_prefix_unknown));
         }
-        // ---- frame header (:389-499, :2008-2031) ----
-        if (rem < 6 + 3) DONE(ZE(E_srcSize_wrong));
-        const uint32_t fhd = ip[4];
-        const uint32_t dictIDCode = fhd & 3, checksumFlag = (fhd >> 2) & 1, singleSegment = (fhd >> 5) & 1, fcsID = fhd >> 6;
-        const uint32_t didSize = dictIDCode == 3 ? 4 : dictIDCode, fcsSize = fcsID == 0 ? 0 : (fcsID == 1 ? 2 : (fcsID == 2 ? 4 : 8));
-        const uint32_t fhs = 5 + !singleSegment + didSize + fcsSize + (singleSegment && !fcsID);
-        if (rem < fhs + 3) DONE(ZE(E_srcSize_wrong));
-        if (fhd & 0x08) DONE(ZE(E_frameParameter_unsupported));
-        uint32_t pos = 5; uint64_t windowSize = 0, fcs = ~0ull; uint32_t dictID = 0;
-        if (!singleSegment) {
-            const uint32_t wl = ip[pos++]; const uint32_t windowLog = (wl >> 3) + 10;
-            if (windowLog > 30) DONE(ZE(E_frameParameter_windowTooLarge));
-            windowSize = 1ull << windowLog; windowSize += (windowSize >> 3) * (wl & 7);
-        }
-        if (dictIDCode == 1) { dictID = ip[pos]; pos += 1; } else if (dictIDCode == 2) { dictID = rd16(ip + pos); pos += 2; } else if (dictIDCode == 3) { dictID = rd32(ip + pos); pos += 4; }
-        if (fcsID == 0) { if (singleSegment) fcs = ip[pos]; } else if (fcsID == 1) fcs = rd16(ip + pos) + 256; else if (fcsID == 2) fcs = rd32(ip + pos); else fcs = zs_load64(ip + pos);
-        if (singleSegment) windowSize = fcs;
-        ipos += fhs;
-        DState st; st.rep[0] = 1; st.rep[1] = 4; st.rep[2] = 8; st.litEntropy = 0; st.fseEntropy = 0; st.llRepeatOk = 0; st.hufX4 = 0;   // DecompressBegin :2478-2499
+        // ---- frame header (:2008-2031), a block header behind it (a header is >= 6 bytes: the reference's first test, for 6 + 3 bytes, is implied) ----
+        const ZsFrameHeader fh = zs_read_frame_header(ip, rem, 3);
+        if (fh.status) DONE(ZE(fh.status));
+        const uint64_t windowSize = fh.windowSize, fcs = fh.contentSize;
+        ipos += fh.headerSize;
+        DState st = zs_dstate_begin();
         const uint8_t *dictEnd = nullptr; uint32_t dictSize = 0, dictIDLoaded = 0;
         if (DICT && dict && dictBytes) {                             // ZSTD_decompress_insertDictionary :2452-2475
             const uint32_t contentOff = loadDictEntropy(L, dict, dictBytes, dictIDLoaded, st.rep,
@@ -1182,14 +1157,13 @@ __device__ __forceinline__ void zs_decode_item(DLds &L, const uint32_t item, con
             if (contentOff) { st.hufX4 = 1; st.litEntropy = 1; st.fseEntropy = 1; }     // a formatted dictionary: its tables are the frame's first
             dictSize = dictBytes - contentOff; dictEnd = dict + dictBytes;
         }
-        if (dictID != 0 && dictID != dictIDLoaded) DONE(ZE(E_dictionary_wrong));      // :632-634
+        if (fh.dictID != 0 && fh.dictID != dictIDLoaded) DONE(ZE(E_dictionary_wrong));      // :632-634
         const uint64_t frameStart = op;
         for (;;) {                                                   // block loop :2033-2067
             if (srcSize - ipos < 3) DONE(ZE(E_srcSize_wrong));
-            const uint32_t bh = rd24(src + ipos);
-            const uint32_t lastBlock = bh & 1, btype = (bh >> 1) & 3, cSize = bh >> 3;
+            const ZsBlockHeader bh = zs_read_block_header(src + ipos);
+            const uint32_t lastBlock = bh.last, btype = bh.type, cSize = bh.size, cBlockSize = bh.payload;
             if (btype == 3) DONE(ZE(E_corruption_detected));
-            const uint32_t cBlockSize = btype == 1 ? 1 : cSize;
             ipos += 3;
             if (cBlockSize > srcSize - ipos) DONE(ZE(E_srcSize_wrong));
             uint32_t decoded;
@@ -1211,7 +1185,7 @@ __device__ __forceinline__ void zs_decode_item(DLds &L, const uint32_t item, con
             if (lastBlock) break;
         }
         if (fcs != ~0ull && (op - frameStart) != fcs) DONE(ZE(E_corruption_detected));
-        if (checksumFlag) {
+        if (fh.checksumFlag) {
             if (srcSize - ipos < 4) DONE(ZE(E_checksum_wrong));
             { const uint64_t hq = xxh64_quad(dstBase + frameStart, op - frameStart); if (lane == 0) L.misc[2] = (uint32_t)hq; }     // (every lane calls: the quads hash the same bytes, lane 0's counts)
             wave_sync();
@@ -1257,9 +1231,7 @@ k_decode_frames(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict_
     DLds &L = LS[threadIdx.x >> 6];
     const uint32_t lane = (uint32_t)zs_lane();
     uint8_t *litBuf = litScratchAll + (size_t)(blockIdx.x * F + (threadIdx.x >> 6)) * ZS_DEC_LITBUF;
-    if (lane < 36) L.llTab[lane] = d_LL_base[lane] | ((uint32_t)d_LL_bits[lane] << 24);
-    if (lane < 53) L.mlTab[lane] = d_ML_base[lane] | ((uint32_t)d_ML_bits[lane] << 24);
-    wave_sync();
+    zs_lds_length_tables(L);
     for (;;) {
         uint32_t at = 0;
         if (lane == 0) at = atomicAdd(queue, 1u);

@@ -15,7 +15,7 @@
 //                                 LL / OF / ML codes; k_train_id hashes the content (XXH64) into the dictionary ID; k_train_tables builds the
 //                                 Huffman description and the three NCounts with the encoder's routines and assembles the dictionary.
 #include <hipcub/hipcub.hpp>      // the radix sort of the d-mer keys
-#include "zsmi_wave.h"            // zs_block_copy, xxh64_quad
+#include "zsmi_wave.h"            // zs_block_copy, xxh64_quad, rd32
 #include "entropy_kernels.hip"    // k_train_stats and kTrainStatWords; the encoder's routines k_train_tables builds with (K3Lds, huffLengths,
                                   // huffCodesAndWeights, writeHuffHeaderWave, normalizeCounts, writeNCount)
 #include "zsmi_ctx.h"
@@ -251,8 +251,8 @@ __global__ void k_train_gather(const uint8_t *__restrict__ src, const uint64_t *
 extern "C" unsigned zsmi_getDictID(const void *dict, size_t dictSize)
 {
     const uint8_t *d = (const uint8_t *)dict;
-    if (!d || dictSize < 8 || h_rd32(d) != 0xEC30A437u) return 0;
-    return h_rd32(d + 4);
+    if (!d || dictSize < 8 || rd32(d) != 0xEC30A437u) return 0;
+    return rd32(d + 4);
 }
 
 namespace {

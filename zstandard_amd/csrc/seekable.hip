@@ -11,7 +11,7 @@
 // Decompressed_Size as capacity - the ones wholly inside the range decode straight into dDst, a partial first / last one into context scratch
 // and is copied in slices - then k_seek_verify checks every decoded frame's size and checksum against its entry.
 
-#include "zsmi_wave.h"            // zs_block_copy, xxh64_quad
+#include "zsmi_wave.h"            // zs_block_copy, xxh64_quad, rd32
 #include "entropy_kernels.hip"    // k_pack_offsets
 #include "decode_kernels.hip"     // the decoder's error codes (E_*)
 #include "zsmi_ctx.h"
@@ -131,10 +131,10 @@ struct SeekTable {
 // the footer (the archive's last 9 bytes): the frame count and the table's size
 static int seekFooter(const uint8_t *footer, uint64_t srcSize, SeekTable &t)
 {
-    if (h_rd32(footer + 5) != kSeekableMagic) return ZSMI_error_prefix_unknown;
+    if (rd32(footer + 5) != kSeekableMagic) return ZSMI_error_prefix_unknown;
     const uint8_t desc = footer[4];
     if (desc & 0x7C) return ZSMI_error_corruption_detected;                 // reserved bits 6 - 2 (bits 1 - 0 are unused: ignored)
-    const uint32_t n = h_rd32(footer);
+    const uint32_t n = rd32(footer);
     if (n > kSeekMaxFrames) return ZSMI_error_frameIndex_tooLarge;
     t.n = n; t.checksum = (desc & 0x80) != 0; t.entry = t.checksum ? 12 : 8;
     t.tableSize = kSeekTableFixed + (uint64_t)n * t.entry;
@@ -143,14 +143,14 @@ static int seekFooter(const uint8_t *footer, uint64_t srcSize, SeekTable &t)
 // the table's bytes (t.tableSize of them, after seekFooter): entries, and their sums against the archive
 static int seekEntries(const uint8_t *tbl, uint64_t srcSize, SeekTable &t)
 {
-    if (h_rd32(tbl) != kSeekSkippableMagic) return ZSMI_error_prefix_unknown;
-    if (h_rd32(tbl + 4) != t.n * t.entry + 9u) return ZSMI_error_corruption_detected;
+    if (rd32(tbl) != kSeekSkippableMagic) return ZSMI_error_prefix_unknown;
+    if (rd32(tbl + 4) != t.n * t.entry + 9u) return ZSMI_error_corruption_detected;
     t.cOff.assign((size_t)t.n + 1, 0); t.dOff.assign((size_t)t.n + 1, 0);
     t.cSize.resize(t.n); t.dSize.resize(t.n); t.hash.assign(t.n, 0);
     const uint8_t *e = tbl + 8;
     for (uint32_t i = 0; i < t.n; i++, e += t.entry) {
-        t.cSize[i] = h_rd32(e); t.dSize[i] = h_rd32(e + 4);
-        if (t.checksum) t.hash[i] = h_rd32(e + 8);
+        t.cSize[i] = rd32(e); t.dSize[i] = rd32(e + 4);
+        if (t.checksum) t.hash[i] = rd32(e + 8);
         if (t.cSize[i] == 0 || t.dSize[i] > kSeekMaxFrameSize) return ZSMI_error_corruption_detected;
         t.cOff[i + 1] = t.cOff[i] + t.cSize[i]; t.dOff[i + 1] = t.dOff[i] + t.dSize[i];
     }

@@ -6,6 +6,7 @@
 // it uses; the list is the library's table of contents.
 #include "zsmi_device.h"          // format constants, block / unit / sequence records, unaligned loads and stores
 #include "zsmi_wave.h"            // device primitives of more than one kernel file: wave_*, zs_block_copy, rd16/24/32, xxh64_quad
+#include "zsmi_frame.h"           // the readers of the container headers (frame, block, literals section, stream split): device and host
 #include "lz_kernels.hip"         // encoder, LZ stage: k_lz_candidates, k_lz_walk, k_lz_stitch, k_lz_dict_tables
 #include "entropy_kernels.hip"    // encoder, entropy stage: k_encode_sequences, k_encode_literals, k_assemble_frames; k_train_stats, k_pack_*
 #include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares; loadDictEntropy, the one reader of a dictionary
@@ -68,30 +69,14 @@ extern "C" size_t zsmi_compressBound(size_t srcSize)
     return srcSize + (srcSize >> 8) + ((srcSize < (128u << 10)) ? (((128u << 10) - srcSize) >> 11) : 0) + 3 * (srcSize / ZS_BLOCK_MAX + 1) + 18;
 }
 
-// ---- host-only frame header parse: ZStdDecompress.cs:421-499, 518-532, 617-622 ----
+// ---- ZStdDecompress.cs:518-532, 617-622: the content size the first frame's header states; 0 where it states none, is no zstd frame
+//      (a skippable one too) or is refused ----
 extern "C" unsigned long long zsmi_getDecompressedSize(const void *srcv, size_t srcSize)
 {
     const uint8_t *src = (const uint8_t *)srcv;
-    if (srcSize < 5) return 0;
-    const uint32_t magic = h_rd32(src);
-    if (magic != 0xFD2FB528u) return 0;                    // skippable -> 0, unknown -> 0
-    const uint32_t fhd = src[4];
-    const uint32_t dictIDCode = fhd & 3, singleSegment = (fhd >> 5) & 1, fcsID = fhd >> 6;
-    const size_t didSize = dictIDCode == 3 ? 4 : dictIDCode, fcsSize = fcsID == 0 ? 0 : (fcsID == 1 ? 2 : (fcsID == 2 ? 4 : 8));
-    const size_t fhs = 5 + !singleSegment + didSize + fcsSize + (singleSegment && !fcsID);
-    if (srcSize < fhs) return 0;
-    if (fhd & 0x08) return 0;
-    size_t pos = 5;
-    if (!singleSegment) { const uint32_t wl = src[pos++]; if ((wl >> 3) + 10 > 30) return 0; }
-    pos += didSize;
-    unsigned long long fcs;
-    switch (fcsID) {
-    case 0: if (!singleSegment) return 0; fcs = src[pos]; break;
-    case 1: fcs = ((unsigned long long)src[pos] | ((unsigned long long)src[pos + 1] << 8)) + 256; break;
-    case 2: fcs = h_rd32(src + pos); break;
-    default: fcs = (unsigned long long)h_rd32(src + pos) | ((unsigned long long)h_rd32(src + pos + 4) << 32); break;
-    }
-    return (fcs >= 0xFFFFFFFFFFFFFFFEull) ? 0 : fcs;
+    if (srcSize < 5 || rd32(src) != 0xFD2FB528u) return 0;
+    const ZsFrameHeader fh = zs_read_frame_header(src, srcSize, 0);
+    return (fh.status || fh.contentSize >= 0xFFFFFFFFFFFFFFFEull) ? 0 : fh.contentSize;
 }
 
 // ---- the LZ kernels of a level: k_lz_candidates and k_lz_walk for small units (<= 64 KiB), big units and a dictionary call's prefixed units ----

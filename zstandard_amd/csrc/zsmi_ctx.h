@@ -10,8 +10,6 @@
 
 #define ZSMI_ERR(code) ((size_t)0 - (size_t)(code))
 
-static uint32_t h_rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------

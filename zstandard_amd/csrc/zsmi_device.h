@@ -73,10 +73,11 @@ struct ZsDictRecord {
     ZsCDictEntropy ent;              // contentOff != 0 only
 };
 
-// unaligned loads.  memcpy keeps the alignment-1 fact visible to the compiler: a cast to an over-aligned
-// pointer lets it turn a wave-uniform address into a scalar load, which drops the low address bits.
-__device__ __forceinline__ uint32_t zs_load32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint64_t zs_load64(const uint8_t *p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
+// unaligned little-endian loads.  memcpy keeps the alignment-1 fact visible to the compiler: a cast to an over-aligned
+// pointer lets it turn a wave-uniform address into a scalar load, which drops the low address bits.  (Host code reads
+// container headers with the same loads: the host is little-endian too.)
+__host__ __device__ __forceinline__ uint32_t zs_load32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+__host__ __device__ __forceinline__ uint64_t zs_load64(const uint8_t *p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
 // unaligned stores (global memory takes them at any byte address)
 __device__ __forceinline__ void zs_store16(uint8_t *p, uint16_t v) { __builtin_memcpy(p, &v, 2); }
 __device__ __forceinline__ void zs_store32(uint8_t *p, uint32_t v) { __builtin_memcpy(p, &v, 4); }

@@ -58,9 +58,9 @@ __device__ __forceinline__ void zs_block_copy(uint8_t *__restrict__ d, const uin
     for (uint32_t j = (n16 << 4) + tid; j < n; j += nthreads) d[j] = s[j];
 }
 
-__device__ __forceinline__ uint32_t rd16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t rd24(const uint8_t *p) { return rd16(p) | ((uint32_t)p[2] << 16); }
-__device__ __forceinline__ uint32_t rd32(const uint8_t *p) { return zs_load32(p); }
+__host__ __device__ __forceinline__ uint32_t rd16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+__host__ __device__ __forceinline__ uint32_t rd24(const uint8_t *p) { return rd16(p) | ((uint32_t)p[2] << 16); }
+__host__ __device__ __forceinline__ uint32_t rd32(const uint8_t *p) { return zs_load32(p); }
 
 __device__ static uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 
