@@ -614,3 +614,27 @@ def blocks(frame):
             b.tables_pos = q + (1 if b.nseq else 0)
         yield b
         pos = b.end
+
+
+def entropy_shapes(frame):
+    """per block of the frame, how its entropy tables are described: None for a raw or RLE block, else a namespace with nseq, tables
+    (None without sequences, else for LL, OF, ML in turn "pre", "rle", "repeat" or the accuracy log of an FSE description) and weights
+    (None unless the literals carry a Huffman description, else "4bit" or the accuracy log of its FSE form).  3.1.1.3.2.1, 4.2.1"""
+    out = []
+    for b in blocks(frame):
+        if b.type != 2:
+            out.append(None); continue
+        s = SimpleNamespace(nseq=b.nseq, tables=None, weights=None)
+        if b.lit_type == 2:
+            s.weights = "4bit" if frame[b.huf_pos] >= 128 else (frame[b.huf_pos + 1] & 15) + 5
+        if b.nseq:
+            p, s.tables = b.tables_pos, []
+            for shift, max_symbol in ((6, 35), (4, 31), (2, 52)):
+                mode = (b.modes >> shift) & 3
+                if mode == 2:
+                    _, al, p = read_ncount(frame, p, max_symbol)
+                    s.tables.append(al)
+                else:
+                    s.tables.append(("pre", "rle", None, "repeat")[mode]); p += mode == 1
+        out.append(s)
+    return out

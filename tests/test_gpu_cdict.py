@@ -126,22 +126,9 @@ def test_sizes_against_usingdict_and_libzstd(codec):
 
 
 # ------------------------------------------------------------------ 5. symbols the dictionary cannot code
-def narrow_dictionary():
-    """a formatted dictionary whose Huffman table covers only 'a'..'h' and whose FSE tables cover few codes: offsets codes 0 - 3, match
-    length codes 0 - 3, literal length codes 0 - 3"""
-    lengths = W.flat_lengths(range(ord("a"), ord("i")))
-    weights, _ = W.lengths_to_weights(lengths)
-    of = ([8, 8, 8, 8], 5)
-    ml = ([16, 16, 16, 16], 6)
-    ll = ([16, 16, 16, 16], 6)
-    content = (b"abcdefgh" * 40 + bytes(range(256)) * 4 + b"hgfedcba" * 40)
-    return (0xEC30A437).to_bytes(4, "little") + (77).to_bytes(4, "little") + W.huf_description(weights) + W.ncount(*of) + W.ncount(*ml) + W.ncount(*ll) + \
-        b"".join(r.to_bytes(4, "little") for r in (1, 4, 8)) + content
-
-
 def test_symbols_the_dictionary_cannot_code(codec):
     from zstandard_amd import CompressionDict
-    dic = narrow_dictionary()
+    dic = K.narrow_dictionary()
     assert O.dict_params(dic)[1] == 77                                    # oracle D accepts the dictionary
     probe = b"abcdefgh" * 8
     assert O.decompress_using_dict(O.compress_using_dict(probe, dic, 3), len(probe), dic) == probe
@@ -162,7 +149,29 @@ def test_symbols_the_dictionary_cannot_code(codec):
             assert b0[1] != 3, b0
 
 
-# ------------------------------------------------------------------ 6. lifecycle
+# ------------------------------------------------------------------ 6. the frames themselves
+def test_formatted_dictionary_frames_are_pinned(codec):
+    """no oracle writes Repeat_Mode or treeless blocks: the frames of a fixed set of records under formatted dictionaries (trained ones,
+    whose counts hold -1 entries, and the narrow one) are pinned by the digests of tests/golden/cdict_frame_digests.json (made by
+    gen_fixtures_cdict_frames.py before the encoder's table builders were unified); the frames' own bytes say that the pin covers a first
+    block with a Repeat_Mode and one with treeless literals"""
+    import json
+    from zstandard_amd import CompressionDict
+    want = json.load(open(os.path.join(D.GOLDEN, "cdict_frame_digests.json")))
+    got, repeat, treeless = {}, 0, 0
+    for name, (dic, records) in K.pin_cases().items():
+        for level in K.PIN_LEVELS:
+            cd = CompressionDict(codec, dic, level)
+            frames = B.compress_many(codec, records, cdict=cd)
+            cd.close()
+            first = [K.blocks_of(f)[0] for f in frames]
+            repeat += sum(K.uses_repeat_mode(b) for b in first); treeless += sum(b[1] == 3 for b in first)
+            got[f"{name}_l{level}"] = K.frames_digest(frames)
+    assert repeat > 0 and treeless > 0, (repeat, treeless)
+    assert got == want, sorted(k for k in want if got.get(k) != want[k])
+
+
+# ------------------------------------------------------------------ 7. lifecycle
 def test_one_cdict_many_calls_and_two_in_alternation(codec):
     from zstandard_amd import CompressionDict
     da, db = X.trained("json_records"), X.trained("zipf")

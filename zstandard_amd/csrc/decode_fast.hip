@@ -19,13 +19,14 @@
 // path only ever has to be right about VALID frames; the error behaviour stays that of decode_kernels.hip.
 //
 // Reference functions restated: see decode_kernels.hip, whose routines this path shares: the error codes and isErr, ZsDecItem, DLds and the
-// constant tables, readNCount, buildSeqTableWave, readHufTableT, BitC and its readers, hufDecodeStreams, seqHeadersT, execTileT.
+// length tables, readNCount, buildSeqTableWave, readHufTableT, BitC and its readers, hufDecodeStreams, seqHeadersT, execTileT.
 //
 // Dictionaries: k_dict_load, at the end of this file, is how the HOST learns what a dictionary holds - it runs decode_kernels.hip's
 // loadDictEntropy (the only place where a dictionary's entropy section is walked and checked; the host parses nothing) and leaves a
 // ZsDictRecord, and for a digested decode dictionary the ZsDDictImage the DD forms of the kernels above read.
 #include "zsmi_device.h"
 #include "zsmi_wave.h"
+#include "zsmi_fse.h"             // LL_base, LL_bits, ML_base, ML_bits
 #include "decode_kernels.hip"
 
 #define ZS_FAST_HUFLOG   11u                      // Huffman tables the fast kernel holds: 2^11 entries per item
@@ -820,8 +821,8 @@ k_dec_execute(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ 
     __shared__ uint32_t expSel[16];                                             // v_perm selectors that spread the next literals over a 4-bit mask's set bytes
     const uint32_t w = threadIdx.x >> 6, lane = (uint32_t)zs_lane();
     const uint32_t item = blockIdx.x * F + w;
-    if (threadIdx.x < 36) codeTabs[threadIdx.x] = d_LL_base[threadIdx.x] | ((uint32_t)d_LL_bits[threadIdx.x] << 24);
-    else if (threadIdx.x >= 64 && threadIdx.x < 64 + 53) codeTabs[36 + threadIdx.x - 64] = d_ML_base[threadIdx.x - 64] | ((uint32_t)d_ML_bits[threadIdx.x - 64] << 24);
+    if (threadIdx.x < 36) codeTabs[threadIdx.x] = LL_base[threadIdx.x] | ((uint32_t)LL_bits[threadIdx.x] << 24);
+    else if (threadIdx.x >= 64 && threadIdx.x < 64 + 53) codeTabs[36 + threadIdx.x - 64] = ML_base[threadIdx.x - 64] | ((uint32_t)ML_bits[threadIdx.x - 64] << 24);
     if (threadIdx.x >= 128 && threadIdx.x < 144) {
         const uint32_t m = threadIdx.x - 128; uint32_t sel = 0, k = 0;
         for (uint32_t j = 0; j < 4; j++) { if (m & (1u << j)) { sel |= k << (8 * j); k++; } else sel |= 0x0Cu << (8 * j); }

@@ -18,6 +18,7 @@
 #include "zsmi_device.h"
 #include "zsmi_wave.h"
 #include "zsmi_frame.h"           // the one place a frame, block or literals-section header is read
+#include "zsmi_fse.h"             // the alphabets' constants (default distributions, LL / ML base and bits), the table builder's two routines
 
 // -DZS_DEC_PROFILE: cycles per phase of each item, left in the 64 spare bytes behind its literal scratch
 // (0 literals incl. Huffman table, 1 sequence tables, 2 sequence decoding, 3 sequence execution, 4 checksum, 5 whole item)
@@ -51,19 +52,6 @@ __device__ __forceinline__ bool isErr(uint32_t v) { return v > ZE(120); }
 #endif
 
 struct ZsDecItem { uint64_t srcOff; uint64_t dstOff; uint32_t srcSize; uint32_t dstCap; };
-
-__constant__ uint8_t d_LL_bits[36] = { 0,0,0,0,0,0,0,0, 0,0,0,0,0,0,0,0, 1,1,1,1,2,2,3,3, 4,6,7,8,9,10,11,12, 13,14,15,16 };
-__constant__ uint8_t d_ML_bits[53] = { 0,0,0,0,0,0,0,0, 0,0,0,0,0,0,0,0, 0,0,0,0,0,0,0,0, 0,0,0,0,0,0,0,0,
-                                      1,1,1,1,2,2,3,3, 4,4,5,7,8,9,10,11, 12,13,14,15,16 };
-__constant__ uint32_t d_LL_base[36] = { 0,1,2,3,4,5,6,7, 8,9,10,11,12,13,14,15, 16,18,20,22,24,28,32,40,
-                                       48,64,0x80,0x100,0x200,0x400,0x800,0x1000, 0x2000,0x4000,0x8000,0x10000 };
-__constant__ uint32_t d_ML_base[53] = { 3,4,5,6,7,8,9,10, 11,12,13,14,15,16,17,18, 19,20,21,22,23,24,25,26,
-                                       27,28,29,30,31,32,33,34, 35,37,39,41,43,47,51,59, 67,83,99,0x83,0x103,0x203,0x403,0x803,
-                                       0x1003,0x2003,0x4003,0x8003,0x10003 };
-__constant__ int16_t d_LL_defaultNorm[36] = { 4,3,2,2,2,2,2,2, 2,2,2,2,2,1,1,1, 2,2,2,2,2,2,2,2, 2,3,2,1,1,1,1,1, -1,-1,-1,-1 };
-__constant__ int16_t d_ML_defaultNorm[53] = { 1,4,3,2,2,2,2,2, 2,1,1,1,1,1,1,1, 1,1,1,1,1,1,1,1, 1,1,1,1,1,1,1,1,
-                                             1,1,1,1,1,1,1,1, 1,1,1,1,1,1,-1,-1, -1,-1,-1,-1,-1 };
-__constant__ int16_t d_OF_defaultNorm[29] = { 1,1,1,1,1,1,2,2, 2,1,1,1,1,1,1,1, 1,1,1,1,1,1,1,1, -1,-1,-1,-1,-1 };
 
 // one cell of a sequence decoding table (ZStdDecompress.cs:132-146).  The reference keeps baseValue and nbAdditionalBits in
 // the cell; here the cell keeps the symbol (4 bytes instead of 8: the three tables take 5 KiB of LDS, not 10) and the
@@ -101,8 +89,8 @@ struct DLds {
 __device__ __forceinline__ void zs_lds_length_tables(DLds &L)
 {
     const uint32_t lane = (uint32_t)zs_lane();
-    if (lane < 36) L.llTab[lane] = d_LL_base[lane] | ((uint32_t)d_LL_bits[lane] << 24);
-    if (lane < 53) L.mlTab[lane] = d_ML_base[lane] | ((uint32_t)d_ML_bits[lane] << 24);
+    if (lane < 36) L.llTab[lane] = LL_base[lane] | ((uint32_t)LL_bits[lane] << 24);
+    if (lane < 53) L.mlTab[lane] = ML_base[lane] | ((uint32_t)ML_bits[lane] << 24);
     wave_sync();
 }
 #ifdef ZS_PREP_PROFILE
@@ -183,70 +171,22 @@ __device__ __forceinline__ uint32_t readNCount(int16_t *norm, uint32_t *maxSVPtr
     return (uint32_t)ip;
 }
 
-// ---- BuildFSETable (ZStdDecompress.cs:958-1034) by all 64 lanes; lane s owns symbol s (maxSym <= 52).
-// The reference walks the cells in the order p_k = (k * step) & mask, skipping the low-probability area at the top, and
-// hands them to the symbols in turn; step is odd, so p_k is a permutation: the k-th visit is valid iff p_k <= highThreshold
-// and takes the j-th entry of the expanded symbol list, j = valid visits before k.  Then nextState numbers go to the cells
-// of a symbol in ascending cell order. ----
+// ---- BuildFSETable (ZStdDecompress.cs:958-1034) by all 64 lanes; lane s owns symbol s (maxSym <= 52): the builder of zsmi_fse.h with
+// the decoder's cell (the spread stores a cell's symbol, the ranking its nextState and nbBits, :1017-1027) ----
 __device__ __forceinline__ void buildSeqTableWave(DLds &L, SeqSym *cells, uint32_t *tableLogOut, uint32_t maxSym, uint32_t tableLog)
 {
     const uint32_t lane = (uint32_t)zs_lane();
-    const uint32_t tableSize = 1u << tableLog, tableMask = tableSize - 1, step = (tableSize >> 1) + (tableSize >> 3) + 3;
-    const uint64_t below = (1ull << lane) - 1ull;
-    uint16_t *cumul = L.u.tb.symStart, *symbolNext = L.u.tb.symbolNext;              // scratch of this phase
+    const uint32_t tableSize = 1u << tableLog;
     const int n = (lane <= maxSym) ? (int)L.u.tb.norm[lane] : 0;
-    const bool low = n == -1;
-    const uint64_t lowMask = __ballot(low);
-    const uint32_t highThreshold = tableSize - 1 - (uint32_t)__popcll(lowMask);
-    if (low) cells[tableSize - 1 - (uint32_t)__popcll(lowMask & below)].sym = (uint8_t)lane;   // :975-978, symbols ascending take cells descending
-    const uint32_t cnt = n > 0 ? (uint32_t)n : 0u;
-    const uint32_t incl = wave_incl_scan(cnt);
-    cumul[lane] = (uint16_t)(incl - cnt);
-    symbolNext[lane] = (uint16_t)(low ? 1 : cnt);
+    L.u.tb.symbolNext[lane] = (uint16_t)(n == -1 ? 1 : (n > 0 ? n : 0));
     if (lane == 0) *tableLogOut = tableLog;
-    wave_sync();
-    uint32_t validBefore = 0;
-    for (uint32_t base = 0; base < tableSize; base += 64) {
-        const uint32_t k = base + lane, p = (k * step) & tableMask;
-        const bool valid = k < tableSize && p <= highThreshold;
-        const uint64_t vm = __ballot(valid);
-        if (valid) {
-            const uint32_t j = validBefore + (uint32_t)__popcll(vm & below);
-            uint32_t lo = 0, hi = maxSym + 1;                                        // last symbol whose first entry index is <= j
-            while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (cumul[mid] <= j) lo = mid; else hi = mid; }
-            cells[p].sym = (uint8_t)lo;
-        }
-        validBefore += (uint32_t)__popcll(vm);
-    }
-    wave_sync();
-    // nextState numbers in ascending cell order (:1017-1027), 64 cells at a time: every lane ors its bit into its symbol's 64-bit lane
-    // mask (LDS); the mask read back gives its rank among the chunk's cells of that symbol and the symbol's count in the chunk, which
-    // the symbol's first lane adds to symbolNext.  (A loop over the chunk's distinct symbols cost three LDS round trips per symbol.)
-    uint32_t *symMask = L.u.tb.symMask;
-    for (uint32_t base = 0; base < tableSize; base += 64) {
-        const uint32_t u = base + lane;
-        const bool in = u < tableSize;
-        const uint32_t sym = in ? cells[u].sym : 0u;
-        symMask[2 * lane] = 0; symMask[2 * lane + 1] = 0;
-        wave_sync();
-        if (in) atomicOr(&symMask[2 * sym + (lane >> 5)], 1u << (lane & 31u));
-        wave_sync();
-        uint32_t first = 0, rank = 1, cnt = 0;
-        if (in) {
-            const uint32_t lo = symMask[2 * sym], hi = symMask[2 * sym + 1];
-            rank = (uint32_t)__popc(lo & (uint32_t)below) + (uint32_t)__popc(hi & (uint32_t)(below >> 32));
-            cnt = (uint32_t)__popc(lo) + (uint32_t)__popc(hi);
-            first = symbolNext[sym];
-            const uint32_t nextState = first + rank;                                                       // :1021-1023
-            const uint32_t nb = tableLog - zs_highbit(nextState);
-            cells[u].nbBits = (uint8_t)nb;
-            cells[u].nextState = (uint16_t)((nextState << nb) - tableSize);
-        }
-        wave_sync();
-        if (in && rank == 0) symbolNext[sym] = (uint16_t)(first + cnt);
-        wave_sync();
-    }
-    wave_sync();
+    fseSpreadWave(L.u.tb.symStart, n, maxSym, tableLog, [&](uint32_t cell, uint32_t sym) __attribute__((always_inline)) { cells[cell].sym = (uint8_t)sym; });
+    fseRankWave(L.u.tb.symMask, L.u.tb.symbolNext, tableSize, [&](uint32_t u) __attribute__((always_inline)) { return (uint32_t)cells[u].sym; },
+                [&](uint32_t u, uint32_t, uint32_t nextState) __attribute__((always_inline)) {
+                    const uint32_t nb = tableLog - zs_highbit(nextState);                                          // :1021-1023
+                    cells[u].nbBits = (uint8_t)nb;
+                    cells[u].nextState = (uint16_t)((nextState << nb) - tableSize);
+                });
 }
 
 // ---- ReadStats + table fill (EntropyCommon.cs:198-269, HufDecompress.cs:117-180) ----
@@ -850,11 +790,11 @@ __device__ __forceinline__ uint32_t seqHeadersT(DLds &L, const DState &st, const
             uint32_t consumed = 0;
             for (int t = 0; t < 3; t++) {
                 const uint32_t type = (modes >> (6 - 2 * t)) & 3;
-                const uint32_t maxS = t == 0 ? 35 : (t == 1 ? 31 : 52), maxLog = t == 1 ? 8 : 9;
+                const uint32_t maxS = t == 0 ? MaxLL : (t == 1 ? MaxOff : MaxML), maxLog = t == 0 ? LLFSELog : (t == 1 ? OffFSELog : MLFSELog);
                 SeqSym *cells = (EMIT || t == 0) ? L.LL.cells : (t == 1 ? L.OF.cells : L.ML.cells);
                 uint32_t *tl = (EMIT || t == 0) ? &L.LL.tableLog : (t == 1 ? &L.OF.tableLog : &L.ML.tableLog);
-                const int16_t *dn = t == 0 ? d_LL_defaultNorm : (t == 1 ? d_OF_defaultNorm : d_ML_defaultNorm);
-                const uint32_t dmax = t == 0 ? 35 : (t == 1 ? 28 : 52);
+                const int16_t *dn = t == 0 ? LL_defaultNorm : (t == 1 ? OF_defaultNorm : ML_defaultNorm);
+                const uint32_t dmax = t == 0 ? MaxLL : (t == 1 ? DefaultMaxOff : MaxML);
                 PPROF(L, 7);
                 hw_stage(L.u.tb.hdrWin, ip + consumed, (uint32_t)(iend - (ip + consumed)));           // this table's description, staged
                 PPROF(L, 8);
@@ -869,7 +809,7 @@ __device__ __forceinline__ uint32_t seqHeadersT(DLds &L, const DState &st, const
                             if (symbol > maxS) err = ZE(E_corruption_detected);
                             else { *tl = 0; cells[0].nbBits = 0; cells[0].nextState = 0; cells[0].sym = (uint8_t)symbol; adv = 1; }
                         }
-                    } else if (type == 0) { bmax = dmax; blog = t == 1 ? 5 : 6; }
+                    } else if (type == 0) { bmax = dmax; blog = t == 0 ? LL_defaultNormLog : (t == 1 ? OF_defaultNormLog : ML_defaultNormLog); }
                     else if (type == 3) { if (!st.fseEntropy) err = ZE(E_corruption_detected); }
                     else {
                         uint32_t tableLog = 0, max = maxS;
@@ -1077,7 +1017,7 @@ __device__ __forceinline__ uint32_t loadDictEntropy(DLds &L, const uint8_t *dict
     if (dictBytes <= 8) return ZE(E_dictionary_corrupted);
     { const uint32_t h = huf(p, (uint32_t)(pend - p)); if (isErr(h)) return ZE(E_dictionary_corrupted); p += h; }
     for (int t = 0; t < 3; t++) {                                     // :2395-2435
-        const uint32_t maxS = t == 0 ? 31 : (t == 1 ? 52 : 35), maxLog = t == 0 ? 8 : 9;
+        const uint32_t maxS = t == 0 ? MaxOff : (t == 1 ? MaxML : MaxLL), maxLog = t == 0 ? OffFSELog : (t == 1 ? MLFSELog : LLFSELog);
         const uint32_t left = (uint32_t)(pend - p);
         hw_stage(L.u.tb.hdrWin, p, left);
         if (zs_lane() == 0) {

@@ -17,7 +17,8 @@
 #include <hipcub/hipcub.hpp>      // the radix sort of the d-mer keys
 #include "zsmi_wave.h"            // zs_block_copy, xxh64_quad, rd32
 #include "entropy_kernels.hip"    // k_train_stats and kTrainStatWords; the encoder's routines k_train_tables builds with (K3Lds, huffLengths,
-                                  // huffCodesAndWeights, writeHuffHeaderWave, normalizeCounts, writeNCount)
+                                  // huffCodesAndWeights, writeHuffHeaderWave, normalizeCountsWave, writeNCount)
+#include "zsmi_fse.h"             // MaxLL, MaxML, MaxOff, LLFSELog, MLFSELog, OffFSELog
 #include "zsmi_ctx.h"
 #include <algorithm>
 
@@ -195,7 +196,8 @@ __global__ void __launch_bounds__(256) k_train_tables(const uint32_t *__restrict
                                                       const uint32_t *__restrict__ dictID, uint8_t *__restrict__ hdr, uint8_t *__restrict__ out, uint32_t *__restrict__ result)
 {
     __shared__ K3Lds L;
-    __shared__ uint32_t cnt[64], misc[4];
+    __shared__ uint32_t cnt[64], misc[4];           // misc[0]: the Huffman description's size, misc[1]: the entropy section's size (0: no dictionary);
+                                                    // not K3Lds's L.misc, two slots of which carry values from lane 0 to wavefront 0 below
     __shared__ int16_t norm[64];
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t hcap = 1024;
@@ -212,23 +214,29 @@ __global__ void __launch_bounds__(256) k_train_tables(const uint32_t *__restrict
         if (misc[0]) break;
         __syncthreads();
     }
-    if (tid == 0 && misc[0]) {
+    if (wave == 0 && misc[0]) {                     // wavefront 0: counts scaled and written by lane 0, normalised by all lanes
         uint32_t pos = 8 + misc[0];
         const uint32_t ofMax = zs_highbit(contentSize + (128u << 10));
-        const uint32_t maxes[3] = { min(ofMax, (uint32_t)MaxOff), MaxML, MaxLL }, logs[3] = { 8, 9, 9 }, base[3] = { 320, 384, 256 };
+        const uint32_t maxes[3] = { min(ofMax, (uint32_t)MaxOff), MaxML, MaxLL }, logs[3] = { OffFSELog, MLFSELog, LLFSELog }, base[3] = { 320, 384, 256 };
         bool ok = true;
+        uint32_t &scaledTotal = L.misc[0], &ncountBytes = L.misc[1];       // lane 0 -> all lanes (the literals workspace is free by now)
         for (uint32_t t = 0; t < 3 && ok; t++) {
-            const uint32_t total = train_scaled(stats + base[t], maxes[t] + 1, cnt, 1u << 30);
-            normalizeCounts(norm, logs[t], cnt, total, maxes[t]);
-            const uint32_t w = writeNCount(hdr + pos, hcap - pos, norm, maxes[t], logs[t]);
+            if (lane == 0) scaledTotal = train_scaled(stats + base[t], maxes[t] + 1, cnt, 1u << 30);
+            wave_sync();
+            normalizeCountsWave(norm, logs[t], cnt, scaledTotal, maxes[t]);
+            if (lane == 0) ncountBytes = writeNCount(hdr + pos, hcap - pos, norm, maxes[t], logs[t]);
+            wave_sync();
+            const uint32_t w = ncountBytes;
             ok = w != 0; pos += w;
         }
         ok = ok && pos + 12 <= hcap;
-        const uint32_t id = *dictID, words[5] = { 0xEC30A437u, id, 1u, 4u, 8u };
-        for (uint32_t i = 0; i < 2; i++) zs_store32(hdr + 4 * i, words[i]);
-        if (ok) for (uint32_t i = 0; i < 3; i++) zs_store32(hdr + pos + 4 * i, words[2 + i]);
-        pos += 12;
-        misc[1] = (ok && pos <= hcap && pos < cap) ? pos : 0u;
+        if (lane == 0) {
+            const uint32_t id = *dictID, words[5] = { 0xEC30A437u, id, 1u, 4u, 8u };
+            for (uint32_t i = 0; i < 2; i++) zs_store32(hdr + 4 * i, words[i]);
+            if (ok) for (uint32_t i = 0; i < 3; i++) zs_store32(hdr + pos + 4 * i, words[2 + i]);
+            pos += 12;
+            misc[1] = (ok && pos <= hcap && pos < cap) ? pos : 0u;
+        }
     }
     __syncthreads();
     const uint32_t hs = misc[1];

@@ -6,7 +6,10 @@
 //   k_train_stats       (1 block per workgroup)                  -> the dictionary trainer's finalize: counts of what the sequences kernel coded
 //   k_cdict_tables      (one workgroup)                          -> a digested dictionary's entropy tables in encoder form (ZsCDictTables)
 //   k_pack_offsets, k_pack_copy                                  -> frames in bound-sized slots packed back to back
-// Scalar statement of the same algorithm: oracle/zso_encoder.c (compressBlock and below); the two
+// k_encode_sequences and k_encode_literals are templates on CD alone (a digested dictionary's tables are used); every form takes the
+// dictionary's recent offsets / ID as arguments ({1, 4, 8} / 0 without one).  Every FSE encoding table - a block's, a predefined one, the
+// Huffman weights', a digested dictionary's - is built by buildCTableWave over the shared builder of zsmi_fse.h, which also holds the
+// alphabets' constants.  Scalar statement of the same algorithm: oracle/zso_encoder.c (compressBlock and below); the two
 // must agree bit for bit.  Every piece is the format-inverse of a function of the reference decoder:
 //   literals section        <-> DecodeLiteralsBlock            csharp/src/ZStdDecompress.cs:683-821
 //   Huffman table / streams <-> ReadStats, HUF_readDTableX2,   EntropyCommon.cs:198-269, HufDecompress.cs:117-358
@@ -16,6 +19,7 @@
 #define ZSMI_ENTROPY_KERNELS_HIP
 #include "zsmi_device.h"
 #include "zsmi_wave.h"
+#include "zsmi_fse.h"            // the alphabets' constants, FseBuild, the table builder's two routines
 // timing aids of the development tools (tools/time_kernels.py): end a kernel after a stage.  Compiled in only with
 // -DZSMI_DEBUG_HOOKS (the library the product ships ignores the stopAt argument).
 #ifdef ZSMI_DEBUG_HOOKS
@@ -26,33 +30,9 @@
 #define ZS_STOPPED false
 #endif
 
-#define MaxLL 35
-#define MaxML 52
-#define MaxOff 31
-
-// ---- constant tables (ZStdInternal.cs:158-192, ZStdDecompress.cs:1081-1105) ----
-__constant__ uint8_t c_LL_bits[36] = { 0,0,0,0,0,0,0,0, 0,0,0,0,0,0,0,0, 1,1,1,1,2,2,3,3, 4,6,7,8,9,10,11,12, 13,14,15,16 };
-__constant__ uint8_t c_ML_bits[53] = { 0,0,0,0,0,0,0,0, 0,0,0,0,0,0,0,0, 0,0,0,0,0,0,0,0, 0,0,0,0,0,0,0,0,
-                                      1,1,1,1,2,2,3,3, 4,4,5,7,8,9,10,11, 12,13,14,15,16 };
-__constant__ uint32_t c_LL_base[36] = { 0,1,2,3,4,5,6,7, 8,9,10,11,12,13,14,15, 16,18,20,22,24,28,32,40,
-                                       48,64,0x80,0x100,0x200,0x400,0x800,0x1000, 0x2000,0x4000,0x8000,0x10000 };
-__constant__ uint32_t c_ML_base[53] = { 3,4,5,6,7,8,9,10, 11,12,13,14,15,16,17,18, 19,20,21,22,23,24,25,26,
-                                       27,28,29,30,31,32,33,34, 35,37,39,41,43,47,51,59, 67,83,99,0x83,0x103,0x203,0x403,0x803,
-                                       0x1003,0x2003,0x4003,0x8003,0x10003 };
-__constant__ int16_t c_LL_defaultNorm[36] = { 4,3,2,2,2,2,2,2, 2,2,2,2,2,1,1,1, 2,2,2,2,2,2,2,2, 2,3,2,1,1,1,1,1, -1,-1,-1,-1 };
-__constant__ int16_t c_ML_defaultNorm[53] = { 1,4,3,2,2,2,2,2, 2,1,1,1,1,1,1,1, 1,1,1,1,1,1,1,1, 1,1,1,1,1,1,1,1,
-                                             1,1,1,1,1,1,1,1, 1,1,1,1,1,1,-1,-1, -1,-1,-1,-1,-1 };
-__constant__ int16_t c_OF_defaultNorm[29] = { 1,1,1,1,1,1,2,2, 2,1,1,1,1,1,1,1, 1,1,1,1,1,1,1,1, -1,-1,-1,-1,-1 };
-__constant__ uint8_t c_LL_Code[64] = { 0,1,2,3,4,5,6,7, 8,9,10,11,12,13,14,15, 16,16,17,17,18,18,19,19, 20,20,20,20,21,21,21,21,
-                                      22,22,22,22,22,22,22,22, 23,23,23,23,23,23,23,23, 24,24,24,24,24,24,24,24, 24,24,24,24,24,24,24,24 };
-__constant__ uint8_t c_ML_Code[128] = { 0,1,2,3,4,5,6,7, 8,9,10,11,12,13,14,15, 16,17,18,19,20,21,22,23, 24,25,26,27,28,29,30,31,
-                                       32,32,33,33,34,34,35,35, 36,36,36,36,37,37,37,37, 38,38,38,38,38,38,38,38, 39,39,39,39,39,39,39,39,
-                                       40,40,40,40,40,40,40,40, 40,40,40,40,40,40,40,40, 41,41,41,41,41,41,41,41, 41,41,41,41,41,41,41,41,
-                                       42,42,42,42,42,42,42,42, 42,42,42,42,42,42,42,42, 42,42,42,42,42,42,42,42, 42,42,42,42,42,42,42,42 };
-
-// Codes and extra bits by arithmetic: the same values as the tables above (LL_Code / ML_Code, LL_base / LL_bits, ML_base /
-// ML_bits; checked value by value for every length up to 2^17), without a gather from constant memory in the middle of a
-// tile (a memory round trip each, and its wait takes the loop's prefetch along).
+// Codes and extra bits by arithmetic: the values of the format's tables (LL_Code / ML_Code of ZStdInternal.cs:158-192; LL_base / LL_bits,
+// ML_base / ML_bits of zsmi_fse.h; checked value by value for every length up to 2^17), without a gather from constant memory in the
+// middle of a tile (a memory round trip each, and its wait takes the loop's prefetch along).
 __device__ __forceinline__ uint32_t llCodeOf(uint32_t ll)
 {
     uint32_t c = zs_highbit(ll | 1u) + 19;                        // ll >= 64
@@ -140,7 +120,8 @@ struct K3Lds {                       // literals kernel
     uint8_t  weights[256];
     union {
         struct { uint32_t pkg[10][256]; uint32_t S[512]; uint32_t npk[12]; } pm;      // package-merge (levels 2..11)
-        struct { FseCT ct[1]; int16_t norm[64]; uint8_t tableSymbol[512]; uint32_t cumul[66]; uint16_t stepOut[256]; uint32_t bits[64]; } fse;   // weights table; per step: state bits out | count << 8; the description's bitstream
+        struct { FseCT ct; FseBuild build; uint16_t stepOut[256]; uint32_t bits[64]; } fse;   // weights table and its build scratch; per step: state bits out | count << 8; the description's bitstream
+        struct { FseCT ct; FseBuild build; } cd[3];      // k_cdict_tables: a digested dictionary's three tables (below pm.S, which its Huffman codes use)
         uint32_t tile[4][208];       // bit-packing tiles, one per wavefront (streams are written after the tables are done)
         uint32_t hist[8][257];       // literal gather: eight private histograms (lane & 7), rows one word apart in the banks
         struct { uint32_t T[2052]; uint32_t wpar[4], wcnt[4]; uint32_t sel[16]; } gm;   // literal gather: a bit per block byte (toggles at match ends -> inside a match -> literal), per-wavefront parities / literal counts, byte-compaction selectors
@@ -150,12 +131,15 @@ struct K3Lds {                       // literals kernel
     uint8_t  rngFirst[ZS_WALK_RANGES];   // index of a range's first record that counts (after the walk kernel's stitch)
     uint32_t wcount[16]; int16_t wnorm[16]; uint32_t rankStart[16], rankCount[16];   // small tables kept out of scratch memory
 };
+// cd[] lies below pm.S, which huffCodesAndWeights writes before k_cdict_tables builds its tables; fse (wave 0, the table description)
+// is done with behind a __syncthreads before the streams' tiles take its place
+static_assert(sizeof(((K3Lds *)nullptr)->u.cd) <= offsetof(decltype(((K3Lds *)nullptr)->u.pm), S), "the digested dictionary's tables overlap the Huffman scratch S");
 struct SeqLds {                      // sequences kernel.  Kept under 10 KiB: 16 workgroups per CU = one round for 4096 blocks
     uint32_t count[192];             // code counts: [0..63] LL, [64..127] OF, [128..191] ML
     FseCT ct[3];                     // LL, OF, ML
     int16_t norm[64];
     union {
-        struct { uint8_t tableSymbol[512]; uint32_t cumul[66]; uint32_t symCount[64]; uint32_t symMask[128]; } build;      // while a table is built
+        FseBuild build;                          // while a table is built
         struct { uint32_t op[3][64]; } chain;    // while the state chains run: per table and code, deltaNbBits | (deltaFindState + 1024) << 20 (one read a step)
     } u;
     uint32_t tile[208];              // bit-packing tile
@@ -221,32 +205,9 @@ __device__ __forceinline__ uint32_t sink_close(BitSink &b)
 }
 
 // ---------------------------------------------------------------------------------------------
-// lane-0 sequential pieces (small tables; scalar statement in oracle/zso_encoder.c)
+// FSE tables: the count description by one lane (serial by nature), normalisation and the encoding table by all lanes
+// (scalar statement in oracle/zso_encoder.c)
 // ---------------------------------------------------------------------------------------------
-__device__ static void normalizeCounts(int16_t *norm, uint32_t tableLog, const uint32_t *count, uint32_t total, uint32_t maxSym)
-{
-    const uint32_t tableSize = 1u << tableLog;
-    int still = (int)tableSize;
-    uint32_t largest = 0;
-    for (uint32_t s = 0; s <= maxSym; s++) {
-        if (!count[s]) { norm[s] = 0; continue; }
-        const uint64_t scaled = (uint64_t)count[s] * tableSize;
-        uint32_t p = (uint32_t)(scaled / total);
-        const uint32_t rem = (uint32_t)(scaled % total);
-        if (2 * (uint64_t)rem >= total) p++;
-        if (p == 0) p = 1;
-        norm[s] = (int16_t)p;
-        still -= (int)p;
-        if (norm[s] > norm[largest] || !count[largest]) largest = s;
-    }
-    if (still > 0) norm[largest] = (int16_t)(norm[largest] + still);
-    while (still < 0) {
-        uint32_t best = 0; int found = 0;
-        for (uint32_t s = 0; s <= maxSym; s++) if (norm[s] > 1 && (!found || norm[s] > norm[best])) { best = s; found = 1; }
-        norm[best]--; still++;
-    }
-}
-
 __device__ static uint32_t writeNCount(uint8_t *dst, uint32_t cap, const int16_t *norm, uint32_t maxSym, uint32_t tableLog)
 {
     uint8_t *out = dst; uint8_t *const oend = dst + cap;
@@ -293,37 +254,55 @@ __device__ static uint32_t writeNCount(uint8_t *dst, uint32_t cap, const int16_t
     return (uint32_t)(out - dst);
 }
 
-// cell order is the decoder's (ZStdDecompress.cs:993-1013): spread with the same step and low-probability area
-__device__ static void buildCTable(FseCT &ct, uint8_t *tableSymbol, uint32_t *cumul, const int16_t *norm, uint32_t maxSym, uint32_t tableLog)
+// normalise counts to 2^tableLog, all lanes (lane s owns symbol s); scalar statement: normalizeCounts in the oracle
+__device__ __forceinline__ void normalizeCountsWave(int16_t *norm, uint32_t tableLog, const uint32_t *count, uint32_t total, uint32_t maxSym)
 {
-    const uint32_t tableSize = 1u << tableLog, tableMask = tableSize - 1, step = (tableSize >> 1) + (tableSize >> 3) + 3;
-    uint32_t highThreshold = tableSize - 1, position = 0;
-    ct.tableLog = tableLog; ct.rle = 0;
-    cumul[0] = 0;
-    for (uint32_t s = 1; s <= maxSym + 1; s++) {
-        if (norm[s - 1] == -1) { cumul[s] = cumul[s - 1] + 1; tableSymbol[highThreshold--] = (uint8_t)(s - 1); }
-        else cumul[s] = cumul[s - 1] + (uint32_t)norm[s - 1];
+    const uint32_t lane = (uint32_t)zs_lane();
+    const uint32_t tableSize = 1u << tableLog;
+    const uint32_t c = (lane <= maxSym) ? count[lane] : 0u;
+    uint32_t p = 0;
+    if (c) {
+        const uint64_t scaled = (uint64_t)c * tableSize;
+        p = (uint32_t)(scaled / total);
+        const uint32_t rem = (uint32_t)(scaled % total);
+        if (2 * (uint64_t)rem >= total) p++;
+        if (p == 0) p = 1;
     }
-    for (uint32_t s = 0; s <= maxSym; s++)
-        for (int i = 0; i < norm[s]; i++) {
-            tableSymbol[position] = (uint8_t)s;
-            position = (position + step) & tableMask;
-            while (position > highThreshold) position = (position + step) & tableMask;
-        }
-    for (uint32_t u = 0; u < tableSize; u++) { const uint8_t sym = tableSymbol[u]; ct.stateTable[cumul[sym]++] = (uint16_t)(tableSize + u); }
-    uint32_t total = 0;
-    for (uint32_t s = 0; s <= maxSym; s++) {
-        const int nv = norm[s];
-        if (nv == 0) { ct.deltaNbBits[s] = ((tableLog + 1) << 16) - (1u << tableLog); ct.deltaFindState[s] = 0; }
-        else if (nv == 1 || nv == -1) { ct.deltaNbBits[s] = (tableLog << 16) - (1u << tableLog); ct.deltaFindState[s] = (int)total - 1; total++; }
-        else {
-            const uint32_t maxBitsOut = tableLog - zs_highbit((uint32_t)nv - 1);
-            const uint32_t minStatePlus = (uint32_t)nv << maxBitsOut;
-            ct.deltaNbBits[s] = (maxBitsOut << 16) - minStatePlus;
-            ct.deltaFindState[s] = (int)total - nv;
-            total += (uint32_t)nv;
-        }
+    int still = (int)tableSize - (int)wave_sum(p);
+    // largest: first symbol holding the maximum
+    { const uint32_t key = (p << 6) | (63u - lane); const uint32_t best = wave_max(key); const uint32_t li = 63u - (best & 63u);
+      if (still > 0 && lane == li) p += (uint32_t)still; }
+    while (still < 0) {
+        const uint32_t key = (p > 1) ? ((p << 6) | (63u - lane)) : 0u;
+        const uint32_t best = wave_max(key);
+        const uint32_t li = 63u - (best & 63u);
+        if (lane == li) p--;
+        still++;
     }
+    if (lane <= maxSym) norm[lane] = (int16_t)p;
+    wave_sync();
+}
+
+// THE encoding table, all lanes, from a distribution that may hold -1 entries (a predefined one, a trained dictionary's): the cells in
+// the decoder's order (fseSpreadWave), stateTable[cumul[sym] + (rank of cell u among the cells of sym)] = tableSize + u (fseRankWave);
+// a -1 counts as 1 in the cumulative counts and in deltaNbBits / deltaFindState.  Scalar statement: buildCTable in the oracle.
+__device__ __forceinline__ void buildCTableWave(FseBuild &B, FseCT &ct, const int16_t *norm, uint32_t maxSym, uint32_t tableLog)
+{
+    const uint32_t lane = (uint32_t)zs_lane();
+    const uint32_t tableSize = 1u << tableLog;
+    const int n = (lane <= maxSym) ? (int)norm[lane] : 0;
+    const uint32_t nv = n < 0 ? 1u : (uint32_t)n;
+    const uint32_t excl = wave_incl_scan(nv) - nv;
+    B.symCount[lane] = excl;
+    if (lane <= maxSym) {
+        if (nv == 0) { ct.deltaNbBits[lane] = ((tableLog + 1) << 16) - (1u << tableLog); ct.deltaFindState[lane] = 0; }
+        else if (nv == 1) { ct.deltaNbBits[lane] = (tableLog << 16) - (1u << tableLog); ct.deltaFindState[lane] = (int)excl - 1; }
+        else { const uint32_t maxBitsOut = tableLog - zs_highbit(nv - 1); ct.deltaNbBits[lane] = (maxBitsOut << 16) - (nv << maxBitsOut); ct.deltaFindState[lane] = (int)excl - (int)nv; }
+    }
+    if (lane == 0) { ct.tableLog = tableLog; ct.rle = 0; }
+    fseSpreadWave(B.cumul, n, maxSym, tableLog, [&](uint32_t cell, uint32_t sym) __attribute__((always_inline)) { B.tableSymbol[cell] = (uint8_t)sym; });
+    fseRankWave(B.symMask, B.symCount, tableSize, [&](uint32_t u) __attribute__((always_inline)) { return (uint32_t)B.tableSymbol[u]; },
+                [&](uint32_t u, uint32_t, uint32_t next) __attribute__((always_inline)) { ct.stateTable[next] = (uint16_t)(tableSize + u); });
 }
 __device__ __forceinline__ uint32_t cstate_init(const FseCT &ct, uint32_t symbol)
 {
@@ -334,7 +313,8 @@ __device__ __forceinline__ uint32_t cstate_init(const FseCT &ct, uint32_t symbol
 }
 
 // weights -> FSE (inverse of FSE_decompress_wksp as used by ReadStats, EntropyCommon.cs:226-231), by one wavefront; the weight
-// histogram L.wcount[] (all 16 entries) is already filled.  Lane 0 makes the table (<= 13 symbols, <= 64 cells).  The encoder's two
+// histogram L.wcount[] (all 16 entries) is already filled.  Lane 0 decides the table's shape (<= 13 symbols, <= 64 cells) and writes its
+// description; the counts are normalised and the table is built by all lanes, as every FSE table of the encoder.  The encoder's two
 // interleaved states run side by side on lanes 0 and 1 (state "first" takes the symbols nw-3, nw-5, ..., "second" nw-4, nw-6, ...;
 // per step: value | bit count << 8 into LDS), then all lanes place the steps' bits by a prefix sum of the counts - the scalar form
 // (one lane, a byte-wise bit writer, ~250 dependent steps) was a third of the kernel's time between the code lengths and the streams.
@@ -342,11 +322,13 @@ __device__ __forceinline__ uint32_t cstate_init(const FseCT &ct, uint32_t symbol
 __device__ __forceinline__ uint32_t fseCompressWeightsWave(K3Lds &L, uint8_t *dst, uint32_t cap, const uint8_t *weights, uint32_t nw)
 {
     const uint32_t lane = (uint32_t)zs_lane();
-    if (lane == 0) {
-        uint32_t hs = 0, tl = 0;
+    // (misc[12 .. 14] are borrowed: the block's per-wavefront code bits, which every thread has read before the workgroup barriers of
+    //  huffCodesAndWeights that lie between that read and this call)
+    if (lane == 0) {                                                      // what is scalar by nature: is there an FSE form, and its shape
+        uint32_t tl = 0, maxSym = 0;
         do {
-            uint32_t *count = L.wcount; int16_t *norm = L.wnorm;
-            uint32_t maxSym = 0, tableLog;
+            const uint32_t *count = L.wcount;
+            uint32_t tableLog;
             if (nw <= 1) break;
             for (uint32_t i = 0; i < 16; i++) if (count[i]) maxSym = i;
             bool one = false;
@@ -355,19 +337,21 @@ __device__ __forceinline__ uint32_t fseCompressWeightsWave(K3Lds &L, uint8_t *ds
             tableLog = 6;
             while (tableLog > 5 && (1u << (tableLog - 1)) >= nw) tableLog--;
             { uint32_t present = 0; for (uint32_t i = 0; i <= maxSym; i++) present += count[i] != 0; if (present > (1u << tableLog)) break; }
-            normalizeCounts(norm, tableLog, count, nw, maxSym);
-            hs = writeNCount(dst, cap, norm, maxSym, tableLog);
-            if (!hs) break;
-            buildCTable(L.u.fse.ct[0], L.u.fse.tableSymbol, L.u.fse.cumul, norm, maxSym, tableLog);
             tl = tableLog;
         } while (0);
-        L.misc[12] = hs; L.misc[13] = tl;
+        L.misc[13] = tl; L.misc[14] = maxSym;
     }
     L.u.fse.bits[lane] = 0;
     wave_sync();
-    const uint32_t hsize = L.misc[12], tableLog = L.misc[13];
+    const uint32_t tableLog = L.misc[13], maxSym = L.misc[14];
+    if (!tableLog) return 0;
+    normalizeCountsWave(L.wnorm, tableLog, L.wcount, nw, maxSym);
+    if (lane == 0) L.misc[12] = writeNCount(dst, cap, L.wnorm, maxSym, tableLog);
+    wave_sync();
+    const uint32_t hsize = L.misc[12];
     if (!hsize) return 0;
-    const FseCT &ct = L.u.fse.ct[0];
+    buildCTableWave(L.u.fse.build, L.u.fse.ct, L.wnorm, maxSym, tableLog);
+    const FseCT &ct = L.u.fse.ct;
     const uint32_t K = nw - 2;                                            // encode steps; step k takes symbol nw - 3 - k
     uint16_t *stepOut = L.u.fse.stepOut;
     uint32_t fin = 0;
@@ -658,9 +642,9 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
 // literal gather (a stream compaction of the block) + histogram, Huffman lengths by package-merge (256 threads),
 // table description (one lane), the 4 Huffman streams (one wavefront each)  -> litSec[], meta.{type, rleByte, litSecSize}
 // ---------------------------------------------------------------------------------------------
-// (k_encode_literals_dict: the same for a dictionary call, whose frame headers carry the dictionary's ID; k_encode_literals_cdict: with a
-//  digested dictionary's Huffman codes besides - CD: the first block of a frame is coded as Treeless literals (type 3) iff every literal byte
-//  has a code and that section is strictly smaller than the one the rules below produce)
+// (dictID: the dictionary ID the frame headers carry, 0 for none.  CD: with a digested dictionary's Huffman codes in cdt (else nullptr) - the
+//  first block of a frame is coded as Treeless literals (type 3) iff every literal byte has a code and that section is strictly smaller
+//  than the one the rules below produce)
 #define ZS_LIT_PARAMS const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, \
                       const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
                       uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, uint8_t *__restrict__ litSecAll, \
@@ -1042,99 +1026,14 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     FINISH(2, litSecSize, 0);
     #undef FINISH
 }
-extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS) { encode_literals_block<false>(ZS_LIT_ARGS, 0u, nullptr); }
-extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals_dict(ZS_LIT_PARAMS, uint32_t dictID) { encode_literals_block<false>(ZS_LIT_ARGS, dictID, nullptr); }
-extern "C" __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals_cdict(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictTables *__restrict__ cdt) { encode_literals_block<true>(ZS_LIT_ARGS, dictID, cdt); }
+template <bool CD>
+__global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictTables *__restrict__ cdt) { encode_literals_block<CD>(ZS_LIT_ARGS, dictID, cdt); }
 
 // ---------------------------------------------------------------------------------------------
 // k_encode_sequences : one wavefront per block.  Repcodes (parallel: two last-index scans), code
 // histograms, tables (normalisation and encoding tables built by all lanes), bitstream
 // -> seqSec[], meta.seqSecSize
 // ---------------------------------------------------------------------------------------------
-// normalise counts to 2^tableLog, all lanes (lane s owns symbol s); scalar statement: normalizeCounts in the oracle
-__device__ static void normalizeCountsWave(int16_t *norm, uint32_t tableLog, const uint32_t *count, uint32_t total, uint32_t maxSym)
-{
-    const uint32_t lane = (uint32_t)zs_lane();
-    const uint32_t tableSize = 1u << tableLog;
-    const uint32_t c = (lane <= maxSym) ? count[lane] : 0u;
-    uint32_t p = 0;
-    if (c) {
-        const uint64_t scaled = (uint64_t)c * tableSize;
-        p = (uint32_t)(scaled / total);
-        const uint32_t rem = (uint32_t)(scaled % total);
-        if (2 * (uint64_t)rem >= total) p++;
-        if (p == 0) p = 1;
-    }
-    int still = (int)tableSize - (int)wave_sum(p);
-    // largest: first symbol holding the maximum
-    { const uint32_t key = (p << 6) | (63u - lane); const uint32_t best = wave_max(key); const uint32_t li = 63u - (best & 63u);
-      if (still > 0 && lane == li) p += (uint32_t)still; }
-    while (still < 0) {
-        const uint32_t key = (p > 1) ? ((p << 6) | (63u - lane)) : 0u;
-        const uint32_t best = wave_max(key);
-        const uint32_t li = 63u - (best & 63u);
-        if (lane == li) p--;
-        still++;
-    }
-    if (lane <= maxSym) norm[lane] = (int16_t)p;
-    wave_sync();
-}
-
-// encoding table from a distribution without -1 entries, all lanes.  Cell order is the decoder's
-// (ZStdDecompress.cs:993-1013): with no low-probability area the j-th laid cell is (j * step) mod size.
-__device__ static void buildCTableWave(SeqLds &L, FseCT &ct, const int16_t *norm, uint32_t maxSym, uint32_t tableLog)
-{
-    const uint32_t lane = (uint32_t)zs_lane();
-    const uint32_t tableSize = 1u << tableLog, tableMask = tableSize - 1, step = (tableSize >> 1) + (tableSize >> 3) + 3;
-    const uint32_t nv = (lane <= maxSym) ? (uint32_t)norm[lane] : 0u;
-    const uint32_t incl = wave_incl_scan(nv);
-    const uint32_t excl = incl - nv;
-    L.u.build.cumul[lane] = excl; if (lane == 63) L.u.build.cumul[64] = incl;
-    L.u.build.symCount[lane] = excl;
-    if (lane <= maxSym) {
-        if (nv == 0) { ct.deltaNbBits[lane] = ((tableLog + 1) << 16) - (1u << tableLog); ct.deltaFindState[lane] = 0; }
-        else if (nv == 1) { ct.deltaNbBits[lane] = (tableLog << 16) - (1u << tableLog); ct.deltaFindState[lane] = (int)excl - 1; }
-        else { const uint32_t maxBitsOut = tableLog - zs_highbit(nv - 1); ct.deltaNbBits[lane] = (maxBitsOut << 16) - (nv << maxBitsOut); ct.deltaFindState[lane] = (int)excl - (int)nv; }
-    }
-    if (lane == 0) { ct.tableLog = tableLog; ct.rle = 0; }
-    wave_sync();
-    for (uint32_t j = lane; j < tableSize; j += 64) {
-        // symbol owning slot j : last s with cumul[s] <= j
-        uint32_t lo = 0, hi = maxSym + 1;
-        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (L.u.build.cumul[mid] <= j) lo = mid; else hi = mid; }
-        L.u.build.tableSymbol[(j * step) & tableMask] = (uint8_t)lo;
-    }
-    wave_sync();
-    // stateTable[cumul[sym] + (rank of cell u among the cells of sym)] = tableSize + u, cells taken in ascending u.
-    // 64 cells at a time: every lane ors its bit into its symbol's 64-bit lane mask (LDS); the mask read back gives the lane its rank
-    // among the chunk's cells of that symbol (bits below it) and the symbol's count in the chunk, which the symbol's first lane adds to
-    // the running count.  (A loop over the chunk's distinct symbols, a ballot each, was ~25 rounds of three LDS round trips per chunk:
-    // most of the kernel's table stage.)
-    uint32_t *symMask = L.u.build.symMask;
-    for (uint32_t base = 0; base < tableSize; base += 64) {
-        const uint32_t u = base + lane;
-        const bool in = u < tableSize;
-        const uint32_t sym = in ? L.u.build.tableSymbol[u] : 0u;
-        symMask[2 * lane] = 0; symMask[2 * lane + 1] = 0;
-        wave_sync();
-        if (in) atomicOr(&symMask[2 * sym + (lane >> 5)], 1u << (lane & 31u));
-        wave_sync();
-        uint32_t start = 0, rank = 1, cnt = 0;
-        if (in) {
-            const uint32_t lo = symMask[2 * sym], hi = symMask[2 * sym + 1];
-            const uint32_t belowLo = (lane < 32u) ? ((1u << lane) - 1u) : 0xFFFFFFFFu, belowHi = (lane < 32u) ? 0u : ((1u << (lane - 32u)) - 1u);
-            rank = (uint32_t)__popc(lo & belowLo) + (uint32_t)__popc(hi & belowHi);
-            cnt = (uint32_t)__popc(lo) + (uint32_t)__popc(hi);
-            start = L.u.build.symCount[sym];
-            ct.stateTable[start + rank] = (uint16_t)(tableSize + u);
-        }
-        wave_sync();
-        if (in && rank == 0) L.u.build.symCount[sym] = start + cnt;
-        wave_sync();
-    }
-    wave_sync();
-}
-
 #ifndef ZS_SEQ_GROUP
 #define ZS_SEQ_GROUP 4             // blocks (= wavefronts) per workgroup of the sequences kernel
 #endif
@@ -1152,12 +1051,12 @@ __device__ static void buildCTableWave(SeqLds &L, FseCT &ct, const int16_t *norm
 #define ZS_CHAIN_MINSEG 4u         // shortest segment, in blocks of 16 steps
 #endif
 static_assert(3u * ZS_CHAIN_CODES <= ZS_BLOCK_MAX + 64u && 3u * 2u * ZS_CHAIN_CODES <= 4u * ZS_STREAM_STRIDE && ZS_CHAIN_CODES == ZS_WALK_RANGES * ZS_SEQ_PER_RANGE, "the chain scratch fits the buffers it borrows");
-// reps: the recent offsets a chunk's first block starts from ({1, 4, 8}; a formatted dictionary's own in k_encode_sequences_dict)
+// reps: the recent offsets a chunk's first block starts from ({1, 4, 8}, or a formatted dictionary's own)
 #define ZS_SEQ_PARAMS const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
                       uint8_t *__restrict__ seqSecAll, ZsBlockMeta *__restrict__ metas, int stopAt, uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, \
                       uint2 *__restrict__ packRecAll
 #define ZS_SEQ_ARGS blocks, nBlocks, seqAll, hdrAll, seqSecAll, metas, stopAt, litsAll, streamAll, packRecAll
-// CD (k_encode_sequences_cdict: a digested dictionary's tables in cdt): for the first block of a frame each of LL / OF / ML is coded in
+// CD (a digested dictionary's tables in cdt, else nullptr): for the first block of a frame each of LL / OF / ML is coded in
 // Repeat_Mode (3) with the dictionary's table iff that table codes every code present and its estimate, the sum of count x cost, is strictly
 // below the estimate of what the rules below pick: RLE one byte, the predefined table its own sum of count x cost, a new table its
 // description's bytes plus that sum over its normalised counts (in 1/256 bit throughout)
@@ -1308,8 +1207,8 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
         for (uint32_t t = 0; t < 3; t++) {
             const uint32_t *count = L.count + 64 * t;
             const uint32_t maxCode = t == 0 ? MaxLL : (t == 1 ? MaxOff : MaxML);
-            const uint32_t maxLog = t == 1 ? 8 : 9;
-            const uint32_t defLog = t == 1 ? 5 : 6, defMax = t == 0 ? MaxLL : (t == 1 ? 28 : MaxML);
+            const uint32_t maxLog = t == 0 ? LLFSELog : (t == 1 ? OffFSELog : MLFSELog);
+            const uint32_t defLog = t == 0 ? LL_defaultNormLog : (t == 1 ? OF_defaultNormLog : ML_defaultNormLog), defMax = t == 0 ? MaxLL : (t == 1 ? DefaultMaxOff : MaxML);
             FseCT &ct = L.ct[t];
             const uint32_t c = (lane <= maxCode) ? count[lane] : 0u;
             const uint64_t present = __ballot(c != 0);
@@ -1328,16 +1227,12 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
                 mode = 0;
                 if constexpr (CD) {
                     if (bd.firstInChunk) {
-                        const int16_t *defNorm = t == 0 ? c_LL_defaultNorm : (t == 1 ? c_OF_defaultNorm : c_ML_defaultNorm);
+                        const int16_t *defNorm = t == 0 ? LL_defaultNorm : (t == 1 ? OF_defaultNorm : ML_defaultNorm);
                         const int nv = lane <= defMax ? defNorm[lane] : 1;
                         if (repeatBeats(t, c, wave_sum(c * fseSymbolCost((uint32_t)(nv < 0 ? 1 : nv), defLog)))) mode = 3;
                     }
                 }
-                if (mode == 0 && lane == 0) {
-                    const int16_t *defNorm = t == 0 ? c_LL_defaultNorm : (t == 1 ? c_OF_defaultNorm : c_ML_defaultNorm);
-                    for (uint32_t i = 0; i <= defMax; i++) L.norm[i] = defNorm[i];
-                    buildCTable(ct, L.u.build.tableSymbol, L.u.build.cumul, L.norm, defMax, defLog);
-                }
+                if (mode == 0) buildCTableWave(L.u.build, ct, t == 0 ? LL_defaultNorm : (t == 1 ? OF_defaultNorm : ML_defaultNorm), defMax, defLog);
             } else {
                 uint32_t tableLog = maxLog;
                 { const uint32_t hb = zs_highbit(nseq - 1); const uint32_t want = hb > 2 ? hb - 2 : 5; if (want < tableLog) tableLog = want; }
@@ -1356,7 +1251,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
                 }
                 if (mode == 2) {
                 pos += h;
-                buildCTableWave(L, ct, L.norm, maxSym, tableLog);
+                buildCTableWave(L.u.build, ct, L.norm, maxSym, tableLog);
                 }
             }
             modeByte |= mode << (6 - 2 * t);
@@ -1588,12 +1483,8 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
     }
     if (lane == 0 && exists) { metas[blk].seqSecSize = result; metas[blk].seqHdrSize = (secHdr == 0xFFFFFFFFu) ? result : secHdr; metas[blk].seqGap = secGap; }
 }
-template <int G>
-__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS) { encode_sequences_block<G, false>(ZS_SEQ_ARGS, 1u, 4u, 8u, nullptr); }
-template <int G>
-__global__ void __launch_bounds__(64 * G) k_encode_sequences_dict(ZS_SEQ_PARAMS, uint4 reps) { encode_sequences_block<G, false>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, nullptr); }
-template <int G>
-__global__ void __launch_bounds__(64 * G) k_encode_sequences_cdict(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictTables *__restrict__ cdt) { encode_sequences_block<G, true>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, cdt); }
+template <int G, bool CD>
+__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictTables *__restrict__ cdt) { encode_sequences_block<G, CD>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, cdt); }
 
 // ---------------------------------------------------------------------------------------------
 // k_assemble_frames : one workgroup per chunk.  frame = magic + FHD + FCS (single segment)
@@ -1604,8 +1495,8 @@ __global__ void __launch_bounds__(64 * G) k_encode_sequences_cdict(ZS_SEQ_PARAMS
 #define ZS_ASM_PARAMS const uint8_t *__restrict__ src, const ZsChunkDesc *__restrict__ chunks, const ZsBlockDesc *__restrict__ blocks, \
                       const ZsBlockMeta *__restrict__ metas, const uint8_t *__restrict__ litSecAll, const uint8_t *__restrict__ seqSecAll, \
                       uint32_t blockBase, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes, uint32_t chunkBase
-#define ZS_ASM_ARGS src, chunks, blocks, metas, litSecAll, seqSecAll, blockBase, dst, dstSizes, chunkBase
-__device__ __forceinline__ void assemble_frame(ZS_ASM_PARAMS, uint32_t dictID)
+// dictID: the dictionary ID the frame header carries, 0 for none
+extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAMS, uint32_t dictID)
 {
     const ZsChunkDesc cd = chunks[chunkBase + blockIdx.x];
     if (cd.nBlocks <= 1) return;                               // one-block chunks were assembled by the literals kernel
@@ -1621,8 +1512,6 @@ __device__ __forceinline__ void assemble_frame(ZS_ASM_PARAMS, uint32_t dictID)
     }
     if (tid == 0) dstSizes[chunkBase + blockIdx.x] = pos;
 }
-extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAMS) { assemble_frame(ZS_ASM_ARGS, 0u); }
-extern "C" __global__ void __launch_bounds__(256) k_assemble_frames_dict(ZS_ASM_PARAMS, uint32_t dictID) { assemble_frame(ZS_ASM_ARGS, dictID); }
 
 static const uint32_t kTrainStatWords = 448;                                // literal bytes [0, 256), LL codes [256, 320), OF [320, 384), ML [384, 448)
 // finalize statistics of one compressed sub-batch, between k_encode_sequences and k_encode_literals: the codes the sequences kernel left in the
@@ -1665,13 +1554,12 @@ __global__ void __launch_bounds__(256) k_train_stats(const uint8_t *__restrict__
 }
 
 // A digested dictionary's entropy tables in encoder form, once per dictionary, by the encoder's own routines: the Huffman codes in the decoder's
-// order from the weights (huffCodesAndWeights), the three encoding tables by the lane-0 buildCTable (a trained dictionary's counts hold -1
-// entries, which buildCTableWave does not take), and the cost of every symbol.  One workgroup of 256 threads; wavefront t < 3 makes table t.
+// order from the weights (huffCodesAndWeights), the three encoding tables (buildCTableWave: a trained dictionary's counts hold -1 entries),
+// and the cost of every symbol.  One workgroup of 256 threads; wavefront t < 3 makes table t.
 __global__ void __launch_bounds__(256) k_cdict_tables(const ZsCDictEntropy *__restrict__ ent, ZsCDictTables *__restrict__ out)
 {
     const ZsCDictEntropy &e = *ent;                  // (in the dictionary loader's record, device memory)
     __shared__ K3Lds L;
-    __shared__ struct { FseCT ct; int16_t norm[64]; uint8_t tableSymbol[512]; uint32_t cumul[66]; } F[3];
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const bool huf = e.hufLog != 0 && e.hufLog <= ZS_HUF_MAXBITS;
     const uint32_t w = (huf && tid < e.nWeights) ? e.weights[tid] : 0u;
@@ -1681,15 +1569,14 @@ __global__ void __launch_bounds__(256) k_cdict_tables(const ZsCDictEntropy *__re
     out->hufCodeNb[tid] = w ? L.codeNb[tid] : 0u;
     if (tid == 0) out->hufLog = huf ? e.hufLog : 0u;
     if (wave < 3) {
-        const uint32_t maxSym = e.maxSym[wave], tableLog = e.tableLog[wave];
-        const int nv = lane <= maxSym ? e.norm[wave][lane] : 0;
-        F[wave].norm[lane] = (int16_t)nv;
-        wave_sync();
-        if (lane == 0) buildCTable(F[wave].ct, F[wave].tableSymbol, F[wave].cumul, F[wave].norm, maxSym, tableLog);
-        wave_sync();
-        const uint32_t *from = reinterpret_cast<const uint32_t *>(&F[wave].ct); uint32_t *to = reinterpret_cast<uint32_t *>(&out->ct[wave]);
+        const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);      // (in a scalar register: so are the table's log and size)
+        const uint32_t maxSym = e.maxSym[t], tableLog = e.tableLog[t];
+        FseCT &ct = L.u.cd[wave].ct;
+        buildCTableWave(L.u.cd[wave].build, ct, e.norm[t], maxSym, tableLog);
+        const int nv = lane <= maxSym ? e.norm[t][lane] : 0;
+        const uint32_t *from = reinterpret_cast<const uint32_t *>(&ct); uint32_t *to = reinterpret_cast<uint32_t *>(&out->ct[t]);
         for (uint32_t i = lane; i < sizeof(FseCT) / 4; i += 64) to[i] = from[i];
-        out->cost[wave][lane] = (uint16_t)(nv == 0 ? ZS_COST_NONE : fseSymbolCost((uint32_t)(nv < 0 ? 1 : nv), tableLog));
+        out->cost[t][lane] = (uint16_t)(nv == 0 ? ZS_COST_NONE : fseSymbolCost((uint32_t)(nv < 0 ? 1 : nv), tableLog));
     }
 }
 

@@ -23,7 +23,6 @@
 #include <mutex>
 #include <new>
 #include <string>
-#include <tuple>
 #include <vector>
 
 extern "C" unsigned zsmi_isError(size_t code) { return code > ZSMI_ERR(ZSMI_error_maxCode); }     // ZStdErrors.cs:95-98
@@ -377,32 +376,26 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
         LAUNCH(c, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, (const uint2 *)S.dRecs.p, (const uint4 *)S.dRes.p, (ZsSeqRec *)S.dSeqs.p, (ZsRangeHdr *)S.dHdrs.p, shape.walkLog);
         if (c->stopAfterWalk) continue;
         // The entropy stage.  Sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and
-        // reads the sequence sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  A
-        // dictionary's kind chooses the kernels and what they take besides (tuples): its recent offsets, its ID, a digested one's tables.
-        auto entropy = [&](auto seqKernel, auto seqDict, auto litKernel, auto litDict, auto asmKernel, auto asmDict) {
-            std::apply([&](auto... a) {
-                LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)S.dSeqs.p,
-                       (const ZsRangeHdr *)S.dHdrs.p, (uint8_t *)S.dSeqSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopSeq, (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p,
-                       (uint2 *)S.dDist.p, a...); }, seqDict);
-            if (dStats)                                              // (the codes it reads are in the literal buffers until the literals kernel)
-                LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p,
-                       (const ZsRangeHdr *)S.dHdrs.p, (const uint8_t *)S.dLits.p, dStats);
-            std::apply([&](auto... a) {
-                LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p, (const ZsRangeHdr *)S.dHdrs.p,
-                       (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p, (uint8_t *)S.dLitSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopLit,
-                       dChunks, (const uint8_t *)S.dSeqSec.p, (uint8_t *)dDst, dDstSizes, a...); }, litDict);
-            if (P.maxChunkBlocks > 1)                                // chunks of several blocks
-                std::apply([&](auto... a) {
-                    LAUNCH(c, "k_assemble_frames", asmKernel, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, dChunks,
-                           (const ZsBlockDesc *)P.dBlocks.p, (const ZsBlockMeta *)S.dMetas.p, (const uint8_t *)S.dLitSec.p, (const uint8_t *)S.dSeqSec.p, block0,
-                           (uint8_t *)dDst, dDstSizes, chunk0, a...); }, asmDict);
-        };
-        using std::make_tuple;
-        const uint4 rep = dict ? make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u) : uint4();
-        if (dict && dict->dTables) entropy(k_encode_sequences_cdict<ZS_SEQ_GROUP>, make_tuple(rep, dict->dTables), k_encode_literals_cdict, make_tuple(dict->dictID, dict->dTables),
-                                           k_assemble_frames_dict, make_tuple(dict->dictID));
-        else if (dict) entropy(k_encode_sequences_dict<ZS_SEQ_GROUP>, make_tuple(rep), k_encode_literals_dict, make_tuple(dict->dictID), k_assemble_frames_dict, make_tuple(dict->dictID));
-        else entropy(k_encode_sequences<ZS_SEQ_GROUP>, make_tuple(), k_encode_literals, make_tuple(), k_assemble_frames, make_tuple());
+        // reads the sequence sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  Every
+        // kernel takes the dictionary's recent offsets or ID ({1, 4, 8} and 0 without one); a digested one's tables choose the CD forms.
+        const ZsCDictTables *cdt = dict ? dict->dTables : nullptr;
+        const auto seqKernel = cdt ? k_encode_sequences<ZS_SEQ_GROUP, true> : k_encode_sequences<ZS_SEQ_GROUP, false>;
+        const auto litKernel = cdt ? k_encode_literals<true> : k_encode_literals<false>;
+        const uint4 rep = dict ? make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u) : make_uint4(1u, 4u, 8u, 0u);
+        const uint32_t dictID = dict ? dict->dictID : 0u;
+        LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)S.dSeqs.p,
+               (const ZsRangeHdr *)S.dHdrs.p, (uint8_t *)S.dSeqSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopSeq, (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p,
+               (uint2 *)S.dDist.p, rep, cdt);
+        if (dStats)                                                  // (the codes it reads are in the literal buffers until the literals kernel)
+            LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p,
+                   (const ZsRangeHdr *)S.dHdrs.p, (const uint8_t *)S.dLits.p, dStats);
+        LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p, (const ZsRangeHdr *)S.dHdrs.p,
+               (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p, (uint8_t *)S.dLitSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopLit,
+               dChunks, (const uint8_t *)S.dSeqSec.p, (uint8_t *)dDst, dDstSizes, dictID, cdt);
+        if (P.maxChunkBlocks > 1)                                    // chunks of several blocks
+            LAUNCH(c, "k_assemble_frames", k_assemble_frames, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, dChunks,
+                   (const ZsBlockDesc *)P.dBlocks.p, (const ZsBlockMeta *)S.dMetas.p, (const uint8_t *)S.dLitSec.p, (const uint8_t *)S.dSeqSec.p, block0,
+                   (uint8_t *)dDst, dDstSizes, chunk0, dictID);
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
