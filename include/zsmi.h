@@ -172,6 +172,45 @@ int zsmi_decompressBatchHost_usingDDict(zsmi_ctx *ctx, const void *src, const ui
                                         uint32_t *dstSizes, const zsmi_ddict *dd);
 size_t zsmi_decompress_usingDDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_ddict *dd);
 
+/* ------------------------------------------------------------------------------------------
+ * DDict sets (ZSTD_d_refMultipleDDicts): a read-only device table of digested decode dictionaries.  A decode call that takes a set gives
+ * every frame the dictionary its dictID names - on the device, inside the kernels - so one call decodes a batch whose frames name different
+ * dictionaries, dictionary frames on the fast path.
+ *
+ * Which dictionary a frame gets:
+ *  - a frame that names dictID X != 0: the member whose ID is X; no member has that ID: the item's result is dictionary_wrong (32);
+ *  - a frame that names no dictionary (field absent or 0): `unnamed`; unnamed NULL or an empty DDict: no dictionary, as the plain call.
+ *  This holds per frame, not per item: an item of several concatenated frames may name a different dictionary in each (such items are the
+ *  general kernel's, as in every call).  Per item the results (bytes, sizes, error codes) are those of the _usingDDict call with the
+ *  dictionary this rule picks.
+ * What dds[] and unnamed may be:
+ *  - members of dds[] are formatted dictionaries (their ID is not 0): a raw-content or empty DDict in dds[] is parameter_unsupported, raw
+ *    content can only be `unnamed`;
+ *  - a formatted `unnamed` also counts as a member under its own ID; two members with one ID are parameter_unsupported, this case included.
+ *    So zsmi_decompress*_usingDDict(dd) is exactly the call with the set ({}, unnamed = dd);
+ *  - n may be 0; more than 4096 members: parameter_outOfBound; a member (or unnamed) of another device than ctx's, a NULL entry, or NULL dds
+ *    with n > 0: parameter_unsupported; a NULL ctx: init_missing.
+ * Creation and lifetime: every check runs on the host before anything touches the device - ctx, n against 4096, dds, then each entry of dds[]
+ * in turn (NULL, its device, formatted), unnamed's device, the IDs.  The set copies nothing from its members: it holds one device table of
+ * {dictID, image pointer, bytes pointer, size}, sorted by ID, uploaded on ctx's stream and waited for, once.  The members must outlive the
+ * set, and the set the work queued with it (free it after zsmi_sync).  Read-only after creation: any context of the same device may use it
+ * (a context of another device: parameter_unsupported).  NULL on failure, with the code in *err if err != NULL.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zsmi_ddictSet zsmi_ddictSet;
+zsmi_ddictSet *zsmi_createDDictSet(zsmi_ctx *ctx, const zsmi_ddict *const *dds, uint32_t n, const zsmi_ddict *unnamed, int *err);
+void zsmi_freeDDictSet(zsmi_ddictSet *set);            /* NULL: nothing */
+uint32_t zsmi_sizeofDDictSetMembers(const zsmi_ddictSet *set); /* members by ID: dds[] and a formatted unnamed (0 for NULL) */
+/* zsmi_decompressBatchDevice with the set's dictionaries.  Like _usingDDict it only queues work: no device-to-host copy, no wait for the
+ * stream.  set == NULL: zsmi_decompressBatchDevice. */
+int zsmi_decompressBatchDevice_usingDDictSet(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                             uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps,
+                                             uint32_t *dDstSizes, const zsmi_ddictSet *set);
+/* the host-buffer form, and the one-shot form (which runs on the current device) */
+int zsmi_decompressBatchHost_usingDDictSet(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                           uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps,
+                                           uint32_t *dstSizes, const zsmi_ddictSet *set);
+size_t zsmi_decompress_usingDDictSet(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_ddictSet *set);
+
 /* Host-buffer forms: stage through device memory, run the device form, copy back, synchronise. */
 int zsmi_compressBatchHost(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                            uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level);

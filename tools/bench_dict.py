@@ -16,13 +16,20 @@ slowest repeat beat the _usingDict call's fastest.  --kernels adds dec_kernels_m
 microseconds: median, min and max of --repeats timings of --steps calls): the device _usingDict compress of one 1 KiB chunk and of 4096
 chunks of 4 KiB, the host _usingDict compress of 64 chunks of 1 KiB, zsmi_createCDict, zsmi_createDDict (each with its free), and the
 _usingDict decode of 4096 frames of 4 KiB (k_decode_frames_dict loads the dictionary in front of every frame).  ZSMI_LIB_FILE names another
-build of the library to measure with the same tool."""
+build of the library to measure with the same tool.
+--dict-set K: instead of all that, a decode call whose frames name K dictionaries (one JSON line per chunk size of 1, 4 and 64 KiB): one
+32 MB call of CDict frames, item i of dictionary i % K, through a DecompressionDictSet (zsmi_decompressBatchDevice_usingDDictSet) against
+what a caller had to do without one - K zsmi_decompressBatchDevice_usingDDict calls one after the other, each over its dictionary's frames -
+in the same process, on the same frames.  set_gib_s / seq_gib_s: the median of --repeats timings of --steps calls (of K calls each), with the
+slowest and fastest as rates (*_min, *_max) and their spread; set_over_seq the ratio of the medians; slower_beyond_spreads says that the set
+call is slower by more than both spreads together.  The K dictionaries are the trained ones of --classes in turn, each under an ID of its own
+(the fixtures hold five: a dictionary met again is another DDict with its own device image and ID, over that class's next chunks)."""
 import argparse, ctypes, json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _data as D, _oracle as O, _corpus as C
-from zstandard_amd import BatchCodec, CompressionDict, DecompressionDict, _lib
+from zstandard_amd import BatchCodec, CompressionDict, DecompressionDict, DecompressionDictSet, _lib
 
 FIXC = os.path.join(ROOT, "tests", "golden", "libzstd_fixtures_dict_compress.npz")
 
@@ -97,6 +104,78 @@ def loader_leg(a):
     print(json.dumps(rec), flush=True)
 
 
+def dict_set_leg(a):
+    K = a.dict_set
+    fix = np.load(FIXC)
+    classes = a.classes.split(",")
+    dev = torch.device("cuda:0")
+    bc = BatchCodec(device=0); Z = _lib.lib()
+    dics = [fix["trained_" + classes[k % len(classes)]].tobytes() for k in range(K)]
+    dics = [d[:4] + (1000 + k).to_bytes(4, "little") + d[8:] for k, d in enumerate(dics)]
+    dds = [DecompressionDict(bc, d) for d in dics]
+    order = np.random.default_rng(1).permutation(K)                       # (the set sorts its members itself)
+    dset = DecompressionDictSet(bc, [dds[k] for k in order])
+    assert len(dset) == K
+    for cs in (1024, 4096, 65536):
+        per = (32 << 20) // cs // K; n = per * K
+        rounds = (K + len(classes) - 1) // len(classes)
+        data = {c: np.frombuffer(class_bytes(c, rounds * per * cs), dtype=np.uint8) for c in classes[:min(K, len(classes))]}
+        src = np.empty((n, cs), dtype=np.uint8)
+        for k in range(K):                                                # item i holds chunk i // K of dictionary i % K
+            at = (k // len(classes)) * per * cs
+            src[k::K] = data[classes[k % len(classes)]][at:at + per * cs].reshape(per, cs)
+        dsrc = torch.from_numpy(src.reshape(-1)).to(dev)
+        off = np.arange(n, dtype=np.uint64) * cs; sz = np.full(n, cs, dtype=np.uint32); caps = sz.copy()
+        bound = int(Z.zsmi_compressBound(cs)); doff = np.arange(n, dtype=np.uint64) * bound
+        dfr = torch.empty(n * bound, dtype=torch.uint8, device=dev)
+        fsz = np.zeros(n, dtype=np.uint32)
+        part = torch.empty(per, dtype=torch.int32, device=dev)
+        sub = [tuple(np.ascontiguousarray(x[k::K]) for x in (off, doff, caps)) for k in range(K)]
+        for k in range(K):
+            cd = CompressionDict(bc, dics[k], 3)
+            bc.compress_device(dsrc.data_ptr(), sub[k][0], np.ascontiguousarray(sz[k::K]), dfr.data_ptr(), sub[k][1], part.data_ptr(), cdict=cd)
+            bc.sync(); cd.close()
+            fsz[k::K] = part.cpu().numpy().view(np.uint32)
+        assert (fsz < 0xFFFFFF88).all()
+        subsz = [np.ascontiguousarray(fsz[k::K]) for k in range(K)]
+        dout = torch.empty(n * cs, dtype=torch.uint8, device=dev); dosz = torch.empty(n, dtype=torch.int32, device=dev)
+
+        def run_set():
+            bc.decompress_device(dfr.data_ptr(), doff, fsz, dout.data_ptr(), off, caps, dosz.data_ptr(), ddict_set=dset)
+
+        def run_seq():
+            for k in range(K):
+                bc.decompress_device(dfr.data_ptr(), sub[k][1], subsz[k], dout.data_ptr(), sub[k][0], sub[k][2], dosz.data_ptr() + 4 * k * per, ddict=dds[k])
+        rec = {"dict_set": K, "chunk": cs, "chunks": n, "library": Z.zsmi_versionString().decode(), "steps": a.steps, "repeats": a.repeats}
+        gib = n * cs / 2**30
+        for tag, run in (("set", run_set), ("seq", run_seq)):
+            dout.zero_(); dosz.zero_()
+            for _ in range(2):
+                run()
+            bc.sync()
+            assert torch.equal(dout, dsrc) and bool((dosz == cs).all()), ("dict-set leg", tag, cs)
+            times = []
+            for _ in range(a.repeats):
+                bc.sync(); t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    run()
+                bc.sync(); times.append((time.perf_counter() - t0) / a.steps)
+            dt = float(np.median(times))
+            rec[tag + "_gib_s"] = round(gib / dt, 2); rec[tag + "_min"] = round(gib / max(times), 2); rec[tag + "_max"] = round(gib / min(times), 2)
+            rec[tag + "_spread"] = round((max(times) - min(times)) / dt, 3)
+            if a.kernels:
+                bc.enable_timing(True); run(); bc.sync()
+                rec["dec_kernels_ms_" + tag] = {k2: round(v[0] * 1e3, 3) for k2, v in bc.kernel_times().items()}
+                bc.enable_timing(False)
+        rec["set_over_seq"] = round(rec["set_gib_s"] / rec["seq_gib_s"], 3)
+        rec["slower_beyond_spreads"] = bool(rec["set_over_seq"] < 1.0 - rec["set_spread"] - rec["seq_spread"])
+        print(json.dumps(rec), flush=True)
+        del dfr, dout, dosz, dsrc
+    bc.sync(); dset.close()
+    for d in dds:
+        d.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bytes", type=int, default=64 << 20, help="input bytes per class")
@@ -107,9 +186,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--loader", action="store_true", help="only the cost of loading a dictionary at each entry point that reads its bytes")
+    ap.add_argument("--dict-set", type=int, default=0, metavar="K", help="only the decode of one 32 MB call whose frames name K dictionaries: a DDict set against K _usingDDict calls")
     a = ap.parse_args()
     if a.loader:
         return loader_leg(a)
+    if a.dict_set:
+        return dict_set_leg(a)
     fix = np.load(FIXC)
     dev = torch.device("cuda:0")
     bc = BatchCodec(device=0)

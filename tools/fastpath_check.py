@@ -3,7 +3,9 @@
 the library built with the debug hooks): frames of the shapes the decoder's fast path is meant to take are decoded, and the per-item
 descriptors (ZsFastDesc.fast) are read back.  A shape that silently falls back to the general kernel decodes correctly and 4 x slower -
 only this count shows it (ELF-class frames did so for two rounds).  Rows "ddict ..." are dictionary frames decoded with a DecompressionDict
-(zsmi_createDDict): own CDict frames with a trained dictionary, own frames with a raw-content one, libzstd's with the trained one.
+(zsmi_createDDict): own CDict frames with a trained dictionary, own frames with a raw-content one, libzstd's with the trained one.  Rows
+"ddict set ..." are mixed batches through a DecompressionDictSet (zsmi_createDDictSet): own CDict frames of three trained dictionaries,
+interleaved, and a committed libzstd frame of a fourth - every frame decoded with the dictionary it names.
 Prints one JSON object: shape -> [items on the fast path, items]."""
 import os; os.environ["ZSMI_DEBUG_LIB"] = "1"
 import sys, ctypes, json
@@ -11,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import _data as D, _oracle as O, _corpus as C, _batch as B, _dicts as X, _ddict as DD
-from zstandard_amd import BatchCodec, CompressionDict, DecompressionDict, _lib
+from zstandard_amd import BatchCodec, CompressionDict, DecompressionDict, DecompressionDictSet, _lib
 
 
 def desc_layout(Z):
@@ -35,15 +37,18 @@ def main():
     elf = dict(C.corpus(1 << 20)).get("elf", None)
     res = {}
 
-    def run(label, chunks, own=True, lvl=3, frames=None, dic=None):
-        """frames: made by the caller (dictionary frames); dic: decoded with a DecompressionDict of it"""
+    def run(label, chunks, own=True, lvl=3, frames=None, dic=None, dset=None):
+        """frames: made by the caller (dictionary frames); dic: decoded with a DecompressionDict of it; dset: with this DecompressionDictSet"""
         if frames is not None:
             pass
         elif own:
             frames = B.cut(*bc.compress_host(*B.batch(chunks), lvl))
         else:
             frames = [O.zstd_compress(c, lvl) for c in chunks]
-        if dic is not None:
+        if dset is not None:
+            out, oo, osz = bc.decompress_host(*B.batch(frames), np.array([len(c) for c in chunks], dtype=np.uint32), ddict_set=dset)
+            ok = (osz < B.ERR).all() and B.cut(out, oo, osz) == chunks
+        elif dic is not None:
             dd = DecompressionDict(bc, dic)
             ok = DD.decode_many(bc, frames, [len(c) for c in chunks], dd) == [(len(c), c) for c in chunks]
             dd.close()
@@ -84,6 +89,24 @@ def main():
     if X.zstd():
         chunks = [records[i * 4096:(i + 1) * 4096] for i in range(64)]
         run("ddict, libzstd frames of 4 KiB, trained dictionary", chunks, frames=[X.zstd_compress_dict(c, trained, 3) for c in chunks], dic=trained)
+    # a mixed batch through a DDict set: item i names dictionary i % 3; the last one is libzstd's frame of the 8 KiB trained dictionary
+    classes = ("json_records", "zipf", "xml_records")
+    dics = [X.trained(c) for c in classes] + [X.TRAINED8K]
+    datas = [X.class_data(c, 1 << 20) for c in classes]
+    dds = [DecompressionDict(bc, d) for d in dics]
+    dset = DecompressionDictSet(bc, dds)
+    cds = [CompressionDict(bc, d, 3) for d in dics[:3]]
+    for cs, n in ((1024, 255), (4096, 63), (65536, 9)):
+        chunks = [datas[i % 3][(i // 3) * cs:(i // 3 + 1) * cs] for i in range(n)]
+        frames = [None] * n
+        for k in range(3):
+            for i, f in zip(range(k, n, 3), B.compress_many(bc, chunks[k::3], cdict=cds[k])):
+                frames[i] = f
+        chunks.append(X.FIX["trained_small_l3_want"].tobytes()); frames.append(X.FIX["trained_small_l3_frame"].tobytes())
+        run("ddict set, own CDict frames of %d KiB of 3 trained dictionaries interleaved, and a libzstd frame of a fourth" % (cs >> 10), chunks, frames=frames, dset=dset)
+    dset.close()
+    for x in cds + dds:
+        x.close()
     print(json.dumps(res))
     return 0
 

@@ -113,6 +113,12 @@ def lib():
     L.zsmi_decompressBatchDevice_usingDDict.restype = i32; L.zsmi_decompressBatchDevice_usingDDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     L.zsmi_decompressBatchHost_usingDDict.restype = i32; L.zsmi_decompressBatchHost_usingDDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     L.zsmi_decompress_usingDDict.restype = sz; L.zsmi_decompress_usingDDict.argtypes = [vp, sz, vp, sz, vp]
+    L.zsmi_createDDictSet.restype = vp; L.zsmi_createDDictSet.argtypes = [vp, vp, u32, vp, ctypes.POINTER(i32)]
+    L.zsmi_freeDDictSet.restype = None; L.zsmi_freeDDictSet.argtypes = [vp]
+    L.zsmi_sizeofDDictSetMembers.restype = u32; L.zsmi_sizeofDDictSetMembers.argtypes = [vp]
+    L.zsmi_decompressBatchDevice_usingDDictSet.restype = i32; L.zsmi_decompressBatchDevice_usingDDictSet.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.zsmi_decompressBatchHost_usingDDictSet.restype = i32; L.zsmi_decompressBatchHost_usingDDictSet.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.zsmi_decompress_usingDDictSet.restype = sz; L.zsmi_decompress_usingDDictSet.argtypes = [vp, sz, vp, sz, vp]
     L.zsmi_decompressBatchHost.restype = i32; L.zsmi_decompressBatchHost.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_decompressBatchHost_usingDict.restype = i32; L.zsmi_decompressBatchHost_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
     L.zsmi_decompressBatchDevice_usingDict.restype = i32; L.zsmi_decompressBatchDevice_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
@@ -151,6 +157,8 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_compressBatchDevice_usingCDict", "zsmi_compressBatchHost_usingCDict", "zsmi_compress_usingCDict",
            "zsmi_createDDict", "zsmi_freeDDict", "zsmi_getDictID_fromDDict", "zsmi_sizeofDDict",
            "zsmi_decompressBatchDevice_usingDDict", "zsmi_decompressBatchHost_usingDDict", "zsmi_decompress_usingDDict",
+           "zsmi_createDDictSet", "zsmi_freeDDictSet", "zsmi_sizeofDDictSetMembers",
+           "zsmi_decompressBatchDevice_usingDDictSet", "zsmi_decompressBatchHost_usingDDictSet", "zsmi_decompress_usingDDictSet",
            "zsmi_packFramesDevice", "zsmi_enableKernelTiming", "zsmi_getKernelTimes", "zsmi_versionString", "zsmi_decodeScratchBytes", "zsmi_shutdown",
            "zsmi_seekableBound", "zsmi_compressSeekable", "zsmi_compressSeekableDevice", "zsmi_decompressSeekable", "zsmi_decompressSeekableDevice",
            "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo",

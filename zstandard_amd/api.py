@@ -12,6 +12,9 @@
                       formatted dictionary its entropy tables code the first block of a frame where that is smaller.
   DecompressionDict   a digested decode dictionary (zsmi_createDDict): the dictionary's bytes and, for a formatted one, its entropy tables in
                       the fast decode kernels' form, on the device once; its calls decode dictionary frames on the fast path.
+  DecompressionDictSet
+                      a DDict set (zsmi_createDDictSet): a device table of DecompressionDicts; a decode call with it gives every frame
+                      the dictionary its dictID names, so one call decodes a batch whose frames name different dictionaries.
   train_dictionary, finalize_dictionary, get_dict_id
                       zstd dictionaries made on the GPU (fastCover and ZDICT_finalizeDictionary; zdict.h's parameters).
 
@@ -159,6 +162,37 @@ class DecompressionDict:
     def close(self):
         if self.handle:
             self.L.zsmi_freeDDict(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecompressionDictSet:
+    """A DDict set (ZSTD_d_refMultipleDDicts): a read-only device table of the formatted DecompressionDicts `ddicts`.  A decode call with it
+    (ddict_set=) decodes every frame with the member its dictID names (no such member: dictionary_wrong for that item) and a frame that names
+    no dictionary with `unnamed` (None: without one); a formatted `unnamed` is also a member under its own ID.  The set copies nothing: the
+    members must stay open as long as the set, and the set until the work queued with it is done (BatchCodec.sync).  len(): its members."""
+
+    def __init__(self, codec, ddicts, unnamed=None):
+        self.L = codec.L
+        self.members = list(ddicts)                  # (kept alive with the set)
+        self.unnamed = unnamed
+        arr = (ctypes.c_void_p * max(len(self.members), 1))(*[d.handle for d in self.members])
+        err = ctypes.c_int(0)
+        self.handle = self.L.zsmi_createDDictSet(codec.ctx, arr, len(self.members), unnamed.handle if unnamed is not None else None, ctypes.byref(err))
+        if not self.handle:
+            raise RuntimeError(f"zsmi_createDDictSet: error {err.value} ({_error_name(self.L, err.value)})")
+
+    def __len__(self) -> int:
+        return int(self.L.zsmi_sizeofDDictSetMembers(self.handle))
+
+    def close(self):
+        if self.handle:
+            self.L.zsmi_freeDDictSet(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -335,12 +369,17 @@ class BatchCodec:
         _check(getattr(self.L, name)(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss), ctypes.c_void_p(d_dst_ptr), self._p(do),
                                      ctypes.c_void_p(d_dst_sizes_ptr), *tail), name)
 
-    def decompress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, dst_caps, d_dst_sizes_ptr, ddict=None):
-        """ddict: a DecompressionDict for every frame of the call (zsmi_decompressBatchDevice_usingDDict: queued without a wait)"""
+    def decompress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, dst_caps, d_dst_sizes_ptr, ddict=None, ddict_set=None):
+        """ddict: a DecompressionDict for every frame of the call (zsmi_decompressBatchDevice_usingDDict: queued without a wait).
+        ddict_set: a DecompressionDictSet instead - each frame's dictID picks its dictionary (zsmi_decompressBatchDevice_usingDDictSet)"""
+        if ddict_set is not None and ddict is not None:
+            raise ValueError("ddict_set= and ddict= exclude each other")
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64); dc = np.ascontiguousarray(dst_caps, dtype=np.uint32)
         args = (self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss), ctypes.c_void_p(d_dst_ptr), self._p(do), self._p(dc), ctypes.c_void_p(d_dst_sizes_ptr))
-        if ddict is not None:
+        if ddict_set is not None:
+            _check(self.L.zsmi_decompressBatchDevice_usingDDictSet(*args, ddict_set.handle), "zsmi_decompressBatchDevice_usingDDictSet")
+        elif ddict is not None:
             _check(self.L.zsmi_decompressBatchDevice_usingDDict(*args, ddict.handle), "zsmi_decompressBatchDevice_usingDDict")
         else:
             _check(self.L.zsmi_decompressBatchDevice(*args), "zsmi_decompressBatchDevice")
@@ -390,9 +429,12 @@ class BatchCodec:
         _check(getattr(self.L, name)(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), *tail), name)
         return arena, do, dsz
 
-    def decompress_host(self, src: np.ndarray, src_offsets, src_sizes, dst_caps, dictionary: bytes = b"", ddict=None):
+    def decompress_host(self, src: np.ndarray, src_offsets, src_sizes, dst_caps, dictionary: bytes = b"", ddict=None, ddict_set=None):
         """dictionary: every frame is decoded with it (raw content or a formatted dictionary; ZSTD_decompress_usingDict,
-        ZStdDecompress.cs:2162).  ddict: a DecompressionDict instead (zsmi_decompressBatchHost_usingDDict)"""
+        ZStdDecompress.cs:2162).  ddict: a DecompressionDict instead (zsmi_decompressBatchHost_usingDDict).  ddict_set: a
+        DecompressionDictSet instead - each frame's dictID picks its dictionary (zsmi_decompressBatchHost_usingDDictSet)"""
+        if ddict_set is not None and (ddict is not None or dictionary):
+            raise ValueError("ddict_set= excludes ddict= and dictionary=")
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         dc = np.ascontiguousarray(dst_caps, dtype=np.uint32)
         n = len(ss)
@@ -401,7 +443,10 @@ class BatchCodec:
             do[1:] = np.cumsum(dc.astype(np.uint64))[:-1]
         arena = np.zeros(max(int(dc.astype(np.uint64).sum()), 1), dtype=np.uint8)
         dsz = np.zeros(n, dtype=np.uint32)
-        if ddict is not None:
+        if ddict_set is not None:
+            rc = self.L.zsmi_decompressBatchHost_usingDDictSet(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dc), self._p(dsz),
+                                                               ddict_set.handle)
+        elif ddict is not None:
             rc = self.L.zsmi_decompressBatchHost_usingDDict(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dc), self._p(dsz),
                                                             ddict.handle)
         elif dictionary:

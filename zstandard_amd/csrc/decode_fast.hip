@@ -61,13 +61,16 @@ struct ZsFastDesc {                               // per item, global memory, wr
     uint32_t hufFlat;                             // bit 0: the item's Huffman table is the flat one of 2^11 entries (more long-code prefixes than the two-level table has sub-tables);
                                                   // bit 1 (calls with a digested dictionary only): the table is the dictionary's, staged from its image, not from the slot
     uint32_t why;                                 // which fast kernel handed the item to the general one (1 Huffman stream, 2 sequence stream, 3.. execute: tools/dec_why.py)
+    uint32_t dict;                                // block 0's, calls with a dictionary only: which one the frame is decoded with (zs_dict_index: a member's index in the
+                                                  // call's table, ZS_DICT_UNNAMED, or ZS_DICT_NONE) - the kernels behind k_dec_prep take the item's image through it
 };
 #define ZS_FAST_HUFTAB_BYTES (2u << ZS_FAST_HUFLOG)                       // uint16 entries
 #define ZS_FAST_SEQTAB_BYTES ((512u + 256u + 512u) * 2u)                  // LL, OF, ML cells, 2 bytes each
 // A digested decode dictionary's device image (zsmi_createDDict; filled by k_dict_load, read-only afterwards): what a frame decoded with
 // the dictionary starts from (ZSTD_decompress_insertDictionary :2452-2475) - the content in front of the frame, the recent offsets, and for a
 // formatted dictionary its entropy tables in exactly the form the fast kernels read: the Huffman table as k_dec_prep leaves one in a slot
-// (two-level or flat), the LL / OF / ML cells in a slot's layout.  The DD instantiations of the fast kernels take it; the others never look at it.
+// (two-level or flat), the LL / OF / ML cells in a slot's layout.  The DD instantiations of the fast kernels take it, per item, through the
+// call's selector (ZsDictSel, decode_kernels.hip) and the index k_dec_prep leaves in the descriptor; the others never look at it.
 struct ZsDDictImage {
     const uint8_t *contentEnd;                    // one past the content's last byte (the dictionary's bytes stay in device memory beside the image)
     uint32_t contentSize, dictID;                 // dictID 0: raw content
@@ -94,15 +97,16 @@ __device__ __forceinline__ ZsFastSeq zs_fastseq(uint32_t bitPos, uint32_t symLL,
 #ifndef ZS_PREP_MINWG
 #define ZS_PREP_MINWG 4                 // wavefronts per SIMD the prep kernel is compiled for (128 VGPRs; per 57344 frames: 2: 0.96 ms, 3: 0.97, 4: 0.97, 5: 1.02, 6: 1.04, 8: 1.10 with ~450 spilled registers; the kernel is bound by the instructions it issues)
 #endif
-// DD: the call decodes with a digested dictionary (dd, its image).  A frame may name no dictionary, ID 0 or the dictionary's ID (any other: the
-// general kernel answers dictionary_wrong); with a formatted dictionary it starts with the dictionary's tables current (misc[11], misc[12] =
+// DD: the call decodes with digested dictionaries (sel: one, or a DDict set's table).  The frame's ID picks its dictionary (zs_dict_index; an ID
+// the selector does not hold: the general kernel answers dictionary_wrong), whose image dd is the frame's from here on - nullptr for a frame
+// that gets none, which is then prepared as in the DD = false form; with a formatted dictionary it starts with the dictionary's tables current (misc[11], misc[12] =
 // ZS_DD_SLOT): a Treeless literals section is flagged to be decoded from the image's Huffman table (no copy into the slot), a Repeat_Mode
 // sequence table is copied from the image's cells as it would be from an earlier block's slot.
 template <int F, bool DD>
 __global__ void __launch_bounds__(64 * F, ZS_PREP_MINWG)
 k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems,
            ZsFastDesc *__restrict__ descs, uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ seqTabs, uint32_t cap, uint32_t maxBlocks, uint32_t *__restrict__ seqLists,
-           uint32_t litCap, uint32_t seqCap, const ZsDDictImage *__restrict__ dd)
+           uint32_t litCap, uint32_t seqCap, const ZsDictSel sel)
 {
     // (litCap, seqCap: literal bytes / sequences a block slot of this call holds - sized by the call's largest capacity, zsmi_api.hip; a block that
     //  wants more cannot fit its item's capacity and is left to the general kernel, which says why)
@@ -133,12 +137,15 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
         if (srcSize < 5 || rd32(src) != 0xFD2FB528u) { ZS_PREP_WHY(__LINE__); break; }
         const ZsFrameHeader fh = zs_read_frame_header(src, srcSize, 3);
         if (fh.status) { ZS_PREP_WHY(__LINE__); break; }
-        if (fh.dictID != 0 && (!DD || fh.dictID != dd->dictID)) { ZS_PREP_WHY(__LINE__); break; }     // (:632-634: a frame that names another dictionary is dictionary_wrong, the general kernel's to say)
+        const uint32_t dictAt = DD ? (uint32_t)__builtin_amdgcn_readfirstlane((int)zs_dict_index(sel, fh.dictID)) : ZS_DICT_NONE;
+        if (fh.dictID != 0 && dictAt == ZS_DICT_NONE) { ZS_PREP_WHY(__LINE__); break; }              // (:632-634: a frame that names a dictionary the call does not have is dictionary_wrong, the general kernel's to say)
+        const ZsDDictImage *dd = DD ? zs_dict_entry(sel, dictAt).img : nullptr;
         const uint32_t tail = fh.checksumFlag ? 4u : 0u;            // the checksum behind the last block
         if (srcSize < fh.headerSize + 3 + tail) { ZS_PREP_WHY(__LINE__); break; }
         if (fh.contentSize != ~0ull && fh.contentSize > 0xFFFFFFFFull) { ZS_PREP_WHY(__LINE__); break; }
         {   ZsFastDesc *dp = descs + item;                          // what the frame header says: in the descriptor of block 0
             DSET(why, 0u); DSET(hasContentSize, fh.contentSize != ~0ull); DSET(contentSize, (uint32_t)fh.contentSize); DSET(hasChecksum, fh.checksumFlag); DSET(checksum, fh.checksumFlag ? rd32(src + srcSize - 4) : 0u);
+            if (DD) DSET(dict, dictAt);
         }
         uint32_t b0 = fh.headerSize;                                // offset of the next block header in the item
         bool fail = false;
@@ -149,7 +156,7 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
         //  misc[11]: block + 1 of the Huffman table's slot; misc[12]: block + 1 of the last block with sequences; misc[13]: Huffman log | flat << 8;
         //  misc[14]: raw / RLE blocks so far; misc[8..10]: the sequence tables' logs, left alone by a block without sequences)
         if (lane < 8) L.misc[8 + lane] = 0;
-        if (DD && dd->tables && lane == 0) {                        // the frame starts from the dictionary's tables (LoadEntropy :2378-2450)
+        if (DD && dd && dd->tables && lane == 0) {                  // the frame starts from the dictionary's tables (LoadEntropy :2378-2450)
             L.misc[8] = dd->seqLog[0]; L.misc[9] = dd->seqLog[1]; L.misc[10] = dd->seqLog[2];
             L.misc[11] = ZS_DD_SLOT; L.misc[12] = ZS_DD_SLOT; L.misc[13] = dd->hufLog | (dd->hufFlat << 8) | (dd->hufWide << 16);
         }
@@ -349,7 +356,7 @@ struct HufLds { uint16_t huf[G][FLAT ? (1u << ZS_FAST_HUFLOG) : ZS_HUF2_ENTRIES]
 
 template <bool FLAT, uint32_t G, bool DD>
 __device__ __forceinline__ void zs_dec_huffman_body(HufLds<FLAT, G> &H, const uint32_t bid, const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
-              const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, uint32_t nBlk, uint32_t cap, uint32_t litStride, const ZsDDictImage *__restrict__ dd)
+              const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, uint32_t nBlk, uint32_t cap, uint32_t litStride, const ZsDictSel &sel)
 {
     const uint32_t lane = (uint32_t)zs_lane();
     const uint32_t g = lane >> 2, k = lane & 3u;
@@ -359,14 +366,15 @@ __device__ __forceinline__ void zs_dec_huffman_body(HufLds<FLAT, G> &H, const ui
     const uint32_t blk = bid / groupsPerBlk, bx = bid - blk * groupsPerBlk;
     (void)nBlk;
     const uint32_t item = bx * G + g;
-    bool mine = false; uint32_t dtLog = 1, n = 0, size = 0, ofDict = 0;       // ofDict (DD): the item's table is the dictionary's
+    bool mine = false; uint32_t dtLog = 1, n = 0, size = 0;
+    uint64_t dictHuf = 0;                                            // (DD) the item's table is its dictionary's: where that image holds it
     const uint8_t *src = srcAll; uint8_t *out = litScratchAll;
     const size_t slot0 = (size_t)blk * cap;                          // this block index's descriptors, tables, literal scratch
     if (g < G && item < nItems) {
         const ZsFastDesc *d = descs + slot0 + item;
         if (descs[item].fast && d->fast && d->litType == 2 && k < d->nStreams && ((DD ? d->hufFlat & 1u : d->hufFlat) != 0) == FLAT) {
             mine = true; dtLog = d->hufLog; n = d->sCnt[k]; size = d->sLen[k];
-            if (DD) ofDict = d->hufFlat >> 1;
+            if (DD && (d->hufFlat >> 1)) dictHuf = (uint64_t)zs_dict_entry(sel, descs[item].dict).img->hufTab;
             src = srcAll + items[item].srcOff + d->sOff[k];
             out = litScratchAll + (slot0 + item) * litStride + d->sOut[k];
         }
@@ -378,7 +386,10 @@ __device__ __forceinline__ void zs_dec_huffman_body(HufLds<FLAT, G> &H, const ui
         const uint32_t log2 = wave_get(mine ? dtLog : 0u, (int)(gg * 4));        // stream 0 of the item exists whenever any does
         if (!log2) continue;
         const uint32_t *ht = reinterpret_cast<const uint32_t *>(hufTabs + (slot0 + it2) * ZS_FAST_HUFTAB_BYTES);
-        if (DD && wave_get(ofDict, (int)(gg * 4))) ht = reinterpret_cast<const uint32_t *>(dd->hufTab);     // one image for every item: hot in L2
+        if (DD) {                                                    // (few images for many items: hot in L2)
+            const uint64_t dh = ((uint64_t)wave_get((uint32_t)(dictHuf >> 32), (int)(gg * 4)) << 32) | wave_get((uint32_t)dictHuf, (int)(gg * 4));
+            if (dh) ht = reinterpret_cast<const uint32_t *>(dh);
+        }
         uint32_t *dstw = reinterpret_cast<uint32_t *>(H.huf[gg]);
         {   // 5 (flat: 16) dwords per lane, the loads issued together
             constexpr uint32_t words = (FLAT ? (1u << ZS_FAST_HUFLOG) : ZS_HUF2_ENTRIES) / 2, per = (words + 63) / 64;
@@ -766,10 +777,10 @@ __device__ __forceinline__ void execTileMatchesFast(uint32_t mdst, uint32_t ml, 
 template <bool FLAT, uint32_t G, bool DD>
 __global__ void __launch_bounds__(64)
 k_dec_huffman(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
-              const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, uint32_t nBlk, uint32_t cap, uint32_t litStride, const ZsDDictImage *__restrict__ dd)
+              const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, uint32_t nBlk, uint32_t cap, uint32_t litStride, const ZsDictSel sel)
 {
     __shared__ __attribute__((aligned(16))) HufLds<FLAT, G> H;
-    zs_dec_huffman_body<FLAT, G, DD>(H, blockIdx.x, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, dd);
+    zs_dec_huffman_body<FLAT, G, DD>(H, blockIdx.x, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, sel);
 }
 template <bool LOG9, uint32_t G>
 __global__ void __launch_bounds__(64)
@@ -789,12 +800,12 @@ template <bool DD>
 __global__ void __launch_bounds__(64)
 k_dec_entropy(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
               const uint8_t *__restrict__ hufTabs, uint8_t *__restrict__ litScratchAll, const uint8_t *__restrict__ seqTabs, ZsFastSeq *__restrict__ seqOutAll,
-              uint32_t nBlk, uint32_t cap, const uint32_t *__restrict__ seqLists, uint32_t litStride, uint32_t seqCap, uint32_t gridH0, uint32_t gridH1, uint32_t gridS0, const ZsDDictImage *__restrict__ dd)
+              uint32_t nBlk, uint32_t cap, const uint32_t *__restrict__ seqLists, uint32_t litStride, uint32_t seqCap, uint32_t gridH0, uint32_t gridH1, uint32_t gridS0, const ZsDictSel sel)
 {
     __shared__ __attribute__((aligned(16))) union U_ { HufLds<false, ZS_FAST_GROUP> h0; HufLds<true, 8u> h1; SeqDecLds<false, ZS_FAST_SEQGROUP_SMALL> s0; SeqDecLds<true, 4u> s1; } U;
     const uint32_t b = blockIdx.x;
-    if (b < gridH0) zs_dec_huffman_body<false, ZS_FAST_GROUP, DD>(U.h0, b, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, dd);
-    else if (b < gridH0 + gridH1) zs_dec_huffman_body<true, 8u, DD>(U.h1, b - gridH0, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, dd);
+    if (b < gridH0) zs_dec_huffman_body<false, ZS_FAST_GROUP, DD>(U.h0, b, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, sel);
+    else if (b < gridH0 + gridH1) zs_dec_huffman_body<true, 8u, DD>(U.h1, b - gridH0, srcAll, items, nItems, descs, hufTabs, litScratchAll, nBlk, cap, litStride, sel);
     else if (b < gridH0 + gridH1 + gridS0) zs_dec_sequences_body<false, ZS_FAST_SEQGROUP_SMALL>(U.s0, b - gridH0 - gridH1, srcAll, items, nItems, descs, seqTabs, seqOutAll, nBlk, cap, seqLists, seqCap);
     else zs_dec_sequences_body<true, 4u>(U.s1, b - gridH0 - gridH1 - gridS0, srcAll, items, nItems, descs, seqTabs, seqOutAll, nBlk, cap, seqLists, seqCap);
 }
@@ -807,13 +818,14 @@ k_dec_entropy(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ 
 // wavefronts per SIMD the kernel is compiled for: 6 = 80 VGPRs (9 spilled), 7 = 72 (more spills).  Per 57344 frames of 32 KiB: 5: 3.79 ms, 6: 3.57,
 // 7: 3.41, 8: 3.65; per 16384 frames of 128 KiB: 6: 5.42, 7: 5.57 - so a call of one-block items takes the 7 form, any other the 6 form (MW); the 8 form (64 VGPRs) only
 // where it turns two rounds of wavefronts into one (zsmi_api.hip)
-// DD (a call with a digested dictionary): the recent offsets start from the dictionary's, an offset may reach its content's size beyond the output's
-// first byte (:1290), and the match pass reads such sources from the content's end (execTileMatchesFast<true>).
+// DD (a call with digested dictionaries): the item's image comes through its descriptor (ZsFastDesc.dict).  The recent offsets start from the
+// dictionary's, an offset may reach its content's size beyond the output's first byte (:1290), and the match pass reads such sources from the
+// content's end (execTileMatchesFast<true>).  An item without a dictionary: offsets {1, 4, 8} and no reach in front of the output, as DD = false.
 template <int F, int MW, bool DD>
 __global__ void __launch_bounds__(64 * F, MW)
 k_dec_execute(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, ZsFastDesc *__restrict__ descs,
               ZsFastSeq *seqAll, uint8_t *__restrict__ litScratchAll, uint8_t *dstAll, uint32_t *__restrict__ dstSizes, uint32_t cap, uint32_t slots,
-              uint32_t litStride, uint32_t seqCap, const ZsDDictImage *__restrict__ dd)
+              uint32_t litStride, uint32_t seqCap, const ZsDictSel sel)
 {
     __shared__ uint32_t tiles[F][3][64];
     __shared__ uint32_t codeTabs[36 + 53];                                      // base | extra bits << 24 of the LL / ML codes
@@ -840,9 +852,10 @@ k_dec_execute(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ 
     const uint64_t oend = it.dstCap;
     uint64_t op = 0; bool bad = false; uint32_t why = 0;
     uint32_t rep0 = 1, rep1 = 4, rep2 = 8;                                      // the list carried from tile to tile and block to block (lane 0 holds it)
-    if (DD) { rep0 = dd->rep[0]; rep1 = dd->rep[1]; rep2 = dd->rep[2]; }
-    const uint32_t dictSize = DD ? dd->contentSize : 0u;
-    const uint8_t *dictEnd = DD ? dd->contentEnd : nullptr;
+    const ZsDDictImage *dd = DD ? zs_dict_entry(sel, descs[itemU].dict).img : nullptr;
+    if (DD && dd) { rep0 = dd->rep[0]; rep1 = dd->rep[1]; rep2 = dd->rep[2]; }
+    const uint32_t dictSize = (DD && dd) ? dd->contentSize : 0u;
+    const uint8_t *dictEnd = (DD && dd) ? dd->contentEnd : nullptr;
     #pragma unroll 1
     for (uint32_t blk = 0; blk < slots && !bad; blk++) {
     const size_t slot = (size_t)blk * cap + itemU;

@@ -1038,19 +1038,62 @@ __device__ __forceinline__ uint32_t loadDictEntropy(DLds &L, const uint8_t *dict
     return (uint32_t)(p - dict);
 }
 
+// ---- WHICH dictionary a frame gets (ZSTD_d_refMultipleDDicts: the frame's dictID picks it).  A call's selector, passed to the kernels by value:
+// `table`, n members sorted by ID (a DDict set's device table, zsmi_createDDictSet; none for a call with one dictionary), and `one`, the
+// dictionary of the frames that name none - which, formatted, is also the member of its own ID.  So a call with one dictionary is the selector
+// ({}, one): no device table.  anyID (the _usingDict calls, whose bytes the host has not read): every frame gets `one`, and the general kernel
+// compares the IDs once it has loaded it. ----
+struct ZsDDictImage;                              // a digested dictionary's tables for the fast kernels (decode_fast.hip)
+struct ZsDictEntry {
+    uint32_t dictID, size;                        // size 0: no dictionary
+    const ZsDDictImage *img;
+    const uint8_t *bytes;
+};
+struct ZsDictSel {
+    const ZsDictEntry *table; uint32_t n, anyID;
+    ZsDictEntry one;
+};
+#define ZS_DICT_NONE    0xFFFFFFFFu               // a frame's dictionary index: no dictionary (for a frame that names one: not in the set) ...
+#define ZS_DICT_UNNAMED 0xFFFFFFFEu               // ... the selector's `one`; any other value: table[index]
+// The index of the dictionary a frame that names `id` is decoded with.  Every lane of the wavefront calls with the same arguments.  The table
+// is searched 64 ways a round, a member a lane: lane l looks at every step-th member, the last one that is not above `id` starts the next
+// round's range (two rounds for 4096 members, one load each).
+__device__ __forceinline__ uint32_t zs_dict_index(const ZsDictSel &s, uint32_t id)
+{
+    if (s.anyID || id == 0 || id == s.one.dictID) return s.one.size ? ZS_DICT_UNNAMED : ZS_DICT_NONE;
+    const uint32_t lane = (uint32_t)zs_lane();
+    uint32_t lo = 0, len = s.n;
+    while (len > 64) {
+        const uint32_t step = (len + 63) / 64, at = lo + lane * step;
+        const uint64_t m = __ballot(at < lo + len && s.table[at].dictID <= id);          // (ascending IDs: a prefix of the lanes)
+        if (!m) return ZS_DICT_NONE;
+        const uint32_t from = lo + (63u - (uint32_t)__builtin_clzll(m)) * step;
+        len = min(step, lo + len - from); lo = from;
+    }
+    const uint64_t m = __ballot(lane < len && s.table[lo + lane].dictID == id);
+    return m ? lo + (uint32_t)__builtin_ctzll(m) : ZS_DICT_NONE;
+}
+__device__ __forceinline__ ZsDictEntry zs_dict_entry(const ZsDictSel &s, uint32_t index)
+{
+    if (index == ZS_DICT_UNNAMED) return s.one;
+    if (index == ZS_DICT_NONE) { ZsDictEntry e; e.dictID = 0; e.size = 0; e.img = nullptr; e.bytes = nullptr; return e; }
+    return s.table[index];
+}
+
 #ifndef ZS_DEC_GROUP
 #define ZS_DEC_GROUP 2             // items (= wavefronts) per workgroup
 #endif
 // every synchronisation inside an item is wavefront-local (wave_sync): the wavefronts of a workgroup run independently.
 // Every function that touches the LDS workspace is force-inlined: through a call the workspace reference becomes a generic
 // pointer and its accesses flat_* instructions, which complete out of order with the ds_* accesses of the inlined code.
-// DICT: every frame of every item is decoded with the dictionary dict[0 .. dictBytes) (ZSTD_decompress_usingDict :2162): raw
-// content, or a formatted dictionary (magic 0xEC30A437) whose entropy tables and recent offsets are loaded in front of each frame
-// (ZSTD_decompressBegin_usingDict :2501, LoadEntropy :2378-2450) -- by every wavefront for itself: a dictionary is a few KiB.
+// DICT: every frame of every item is decoded with the dictionary the call's selector gives it (zs_dict_index; ZSTD_decompress_usingDict :2162
+// for a call with one dictionary): raw content, or a formatted dictionary (magic 0xEC30A437) whose entropy tables and recent offsets are
+// loaded in front of each frame (ZSTD_decompressBegin_usingDict :2501, LoadEntropy :2378-2450) -- by every wavefront for itself: a dictionary
+// is a few KiB.  A frame that names an ID the selector does not hold gets none, and is dictionary_wrong by the test behind the load.
 #define ZS_DEC_LITBUF ((1u << 17) + 64u)                 // a wavefront's literal buffer: the largest block + slack
 template <bool DICT>
 __device__ __forceinline__ void zs_decode_item(DLds &L, const uint32_t item, const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint8_t *dstAll,
-                                               uint32_t *__restrict__ dstSizes, uint8_t *litBuf, const uint8_t *__restrict__ dict, uint32_t dictBytes)
+                                               uint32_t *__restrict__ dstSizes, uint8_t *litBuf, const ZsDictSel &sel)
 {
     const ZsDecItem it = items[item];
     const uint32_t lane = (uint32_t)zs_lane();
@@ -1087,6 +1130,8 @@ __device__ __forceinline__ void zs_decode_item(DLds &L, const uint32_t item, con
         ipos += fh.headerSize;
         DState st = zs_dstate_begin();
         const uint8_t *dictEnd = nullptr; uint32_t dictSize = 0, dictIDLoaded = 0;
+        const uint8_t *dict = nullptr; uint32_t dictBytes = 0;
+        if (DICT) { const ZsDictEntry e = zs_dict_entry(sel, zs_dict_index(sel, fh.dictID)); dict = e.bytes; dictBytes = e.size; }
         if (DICT && dict && dictBytes) {                             // ZSTD_decompress_insertDictionary :2452-2475
             const uint32_t contentOff = loadDictEntropy(L, dict, dictBytes, dictIDLoaded, st.rep,
                 [&](const uint8_t *p, uint32_t n) __attribute__((always_inline)) { return readHufTable(L, p, n); },      // HUF_readDTableX4_wksp (:2391)
@@ -1163,7 +1208,7 @@ template <int F, bool DICT>
 __global__ void __launch_bounds__(64 * F)
 k_decode_frames(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint32_t nItems, uint8_t *dstAll,
                 uint32_t *__restrict__ dstSizes, uint8_t *__restrict__ litScratchAll, const uint32_t *__restrict__ list, const uint32_t *__restrict__ listCount,
-                const uint8_t *__restrict__ dict, uint32_t dictBytes, uint32_t *__restrict__ queue)
+                const ZsDictSel sel, uint32_t *__restrict__ queue)
 {
     __shared__ DLds LS[F];
     const uint32_t total = list ? *listCount : nItems;                          // (list == nullptr: every item of the call)
@@ -1178,7 +1223,7 @@ k_decode_frames(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict_
         at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
         if (at >= total) break;                                                 // (every wavefront gets here: the queue only grows)
         const uint32_t item = list ? list[at] : at;
-        zs_decode_item<DICT>(L, item, srcAll, items, dstAll, dstSizes, litBuf, dict, dictBytes);
+        zs_decode_item<DICT>(L, item, srcAll, items, dstAll, dstSizes, litBuf, sel);
         wave_mem_sync();                                                        // the buffer and the LDS image are the next item's
     }
 }

@@ -282,7 +282,7 @@ static int seekReadQueue(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames
     };
     if (in1 > in0) {
         for (uint32_t k = in0; k < in1; k++) item(k, dDst, t.dOff[first + k] - a, k);
-        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), in1 - in0, dDst, dof.data(), caps.data(), dSt + in0, nullptr, 0)) return e;
+        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), in1 - in0, dDst, dof.data(), caps.data(), dSt + in0, nullptr)) return e;
     }
     if (partFirst || partLast) {
         uint32_t parts[2], np = 0;
@@ -301,7 +301,7 @@ static int seekReadQueue(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames
             sl.from[j] = pos + (lo - t.dOff[i]); sl.to[j] = lo - a; sl.len[j] = hi2 - lo;
             pos += t.dSize[i];
         }
-        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), np, dS, dof.data(), caps.data(), dSt + m, nullptr, 0)) return e;
+        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), np, dS, dof.data(), caps.data(), dSt + m, nullptr)) return e;
         LAUNCH(c, "k_seek_slice", k_seek_slice, dim3(np), dim3(256), 0, (const uint8_t *)dS, dDst, sl);
     }
     if (hipMemcpyAsync(dItems, hi, (size_t)m * sizeof(ZsSeekItem), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;

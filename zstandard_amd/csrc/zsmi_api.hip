@@ -22,6 +22,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -609,16 +610,16 @@ static int uploadDecodeItems(zsmi_ctx *c, const uint64_t *srcOffsets, const uint
 }
 
 // The fast path's launches for a sub-batch of cnt items (dI) in the context's scratch: k_dec_prep, the entropy stage, k_dec_execute,
-// k_dec_checksum.  DD: the call has a digested dictionary - the dictionary forms of the kernels that need it, with its image img.
+// k_dec_checksum.  DD: the call has digested dictionaries - the dictionary forms of the kernels that need them, with the call's selector.
 template <bool DD>
 static void launchFastDecode(zsmi_ctx *c, const DecodePlan &p, const DecodeShape &shape, const uint8_t *src, const ZsDecItem *dI, uint32_t cnt, void *dDst,
-                             uint32_t *dDstSizes, uint32_t *classes, const ZsDDictImage *img)
+                             uint32_t *dDstSizes, uint32_t *classes, const ZsDictSel &sel)
 {
     zsmi_ctx::DecodeScratch &S = c->dec;
     const uint32_t mb = p.maxBlocks;
     ZsFastDesc *dD = (ZsFastDesc *)S.dFastDesc.p;
     LAUNCH(c, "k_dec_prep", (k_dec_prep<ZS_DEC_GROUP, DD>), dim3((cnt + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, dD,
-           (uint8_t *)S.dHufTabs.p, (uint8_t *)S.dSeqTabs.p, p.cap, mb, classes, p.litCap, p.seqCap, img);
+           (uint8_t *)S.dHufTabs.p, (uint8_t *)S.dSeqTabs.p, p.cap, mb, classes, p.litCap, p.seqCap, sel);
     // every block index of the items in one launch per kernel class (the grid: mb runs of the items' groups; a wavefront whose items have no such
     // block leaves at once)
     const uint32_t gH0 = ((cnt + ZS_FAST_GROUP - 1) / ZS_FAST_GROUP) * mb, gH1 = ((cnt + 7) / 8) * mb;
@@ -626,10 +627,10 @@ static void launchFastDecode(zsmi_ctx *c, const DecodePlan &p, const DecodeShape
     if (shape.fused) {
         // the four entropy launches as one (k_dec_entropy), the 2.5 KiB sequence class at 4 items a wavefront as below
         LAUNCH(c, "k_dec_entropy", k_dec_entropy<DD>, dim3(gH0 + gH1 + gS0 + gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p,
-               (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.litStride, p.seqCap, gH0, gH1, gS0, img);
+               (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.litStride, p.seqCap, gH0, gH1, gS0, sel);
     } else {
-        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<false, ZS_FAST_GROUP, DD>), dim3(gH0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride, img);
-        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<true, 8u, DD>), dim3(gH1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride, img);
+        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<false, ZS_FAST_GROUP, DD>), dim3(gH0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride, sel);
+        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<true, 8u, DD>), dim3(gH1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride, sel);
         LAUNCH(c, "k_dec_sequences", (k_dec_sequences<false, ZS_FAST_SEQGROUP_SMALL>), dim3(gS0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
                mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, 0xFFFFFFFFu);
         // the 2.5 KiB table class (blocks of > 2048 sequences: sources, tables, binaries at 32 KiB; the 64 KiB blocks of 128 KiB frames).  How many blocks of a call
@@ -644,23 +645,31 @@ static void launchFastDecode(zsmi_ctx *c, const DecodePlan &p, const DecodeShape
     }
     const auto execute = shape.executeWaves == 6 ? k_dec_execute<4, 6, DD> : (shape.executeWaves == 8 ? k_dec_execute<4, 8, DD> : k_dec_execute<4, 7, DD>);
     LAUNCH(c, "k_dec_execute", execute, dim3((cnt + 3) / 4), dim3(256), 0, src, dI, cnt, dD, (ZsFastSeq *)S.dSeqOut.p,
-           (uint8_t *)S.dLitScratch.p, (uint8_t *)dDst, dDstSizes, p.cap, p.descSlots, p.litStride, p.seqCap, img);
+           (uint8_t *)S.dLitScratch.p, (uint8_t *)dDst, dDstSizes, p.cap, p.descSlots, p.litStride, p.seqCap, sel);
     LAUNCH(c, "k_dec_checksum", k_dec_checksum, dim3((cnt + 15) / 16), dim3(64), 0, dI, cnt, (const ZsFastDesc *)dD, (const uint8_t *)dDst, dDstSizes);
 }
 
-// dDict / dictSize: the call's dictionary in device memory (nullptr: none).  img: a digested dictionary's image of those bytes (zsmi_ddict) - with it the
-// call takes the fast path; without it a dictionary call is the general kernel's alone.
+// the selector of a call with one dictionary, its bytes in device memory (decode_kernels.hip: ZsDictSel).  img: a digested dictionary's image of
+// them, with its ID; none (the _usingDict calls): the device is the one to read the ID - anyID
+static ZsDictSel oneDictionary(const void *dBytes, uint32_t size, const ZsDDictImage *img = nullptr, uint32_t dictID = 0)
+{
+    ZsDictSel sel = ZsDictSel();
+    if (dBytes && size) { sel.one.bytes = (const uint8_t *)dBytes; sel.one.size = size; sel.one.img = img; sel.one.dictID = dictID; sel.anyID = img == nullptr; }
+    return sel;
+}
+// dict: which dictionary each frame of the call gets (nullptr, or a selector that holds none: the plain call).  Digested dictionaries bring the
+// images the fast kernels' dictionary forms need; a call with a dictionary's bare bytes (anyID) is the general kernel's alone.
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
-                                     const void *dDict, uint32_t dictSize, const ZsDDictImage *img)
+                                     const ZsDictSel *dict)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
     if (const int e = uploadDecodeItems(c, srcOffsets, srcSizes, n, dstOffsets, dstCaps)) return e;
-    const bool useDict = dDict != nullptr && dictSize != 0;
-    if (!useDict) img = nullptr;
-    const DecodePlan p = planDecode(c, dstCaps, n, useDict && !img);
+    const bool useDict = dict && (dict->one.size || dict->n);
+    const ZsDictSel sel = useDict ? *dict : ZsDictSel();
+    const DecodePlan p = planDecode(c, dstCaps, n, useDict && sel.anyID);
     zsmi_ctx::DecodeScratch &S = c->dec;
     if (!S.reserve(p)) return ZSMI_error_memory_allocation;
     const uint8_t *src = (const uint8_t *)dSrc;
@@ -676,8 +685,8 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
             // items that are one frame of up to mb blocks: entropy decoding lane-parallel across 16 items per wavefront (decode_fast.hip); whatever
             // those kernels do not take or reject is left to the general kernel below
             if (hipMemsetAsync(lists, 0, DecLists::kClassLists * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-            if (img) launchFastDecode<true>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, img);
-            else launchFastDecode<false>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, nullptr);
+            if (useDict) launchFastDecode<true>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, sel);
+            else launchFastDecode<false>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, sel);
             // the items the fast path did not finish, listed for the general kernel
             left = lists + DecLists::leftList((size_t)p.cap * mb);
             LAUNCH(c, "k_dec_collect", k_dec_collect, dim3((cnt + 255) / 256), dim3(256), 0, &dD->fast, (uint32_t)(sizeof(ZsFastDesc) / sizeof(uint32_t)), cnt, left, leftCount);
@@ -685,7 +694,7 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
         // the general kernel: a pool of wavefronts over a queue - of every item, or (behind the fast path) of the list of the items it left
         LAUNCH(c, useDict ? "k_decode_frames_dict" : "k_decode_frames", useDict ? (k_decode_frames<ZS_DEC_GROUP, true>) : (k_decode_frames<ZS_DEC_GROUP, false>),
                dim3(shape.poolWgs), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, (uint8_t *)dDst, dDstSizes + i0, (uint8_t *)S.dPoolLit.p, (const uint32_t *)left,
-               (const uint32_t *)leftCount, useDict ? (const uint8_t *)dDict : nullptr, useDict ? dictSize : 0u, lists + DecLists::kQueue);
+               (const uint32_t *)leftCount, sel, lists + DecLists::kQueue);
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
@@ -693,7 +702,7 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
 extern "C" int zsmi_decompressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                           uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes)
 {
-    return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, nullptr, 0);
+    return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, nullptr);
 }
 // every frame of every item is decoded with the dictionary dDict[0 .. dictSize) (device memory; ZSTD_decompress_usingDict,
 // ZStdDecompress.cs:2162): raw content or a formatted dictionary (magic 0xEC30A437)
@@ -702,7 +711,8 @@ extern "C" int zsmi_decompressBatchDevice_usingDict(zsmi_ctx *c, const void *dSr
                                                     const void *dDict, size_t dictSize)
 {
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, dDict, (uint32_t)dictSize);
+    const ZsDictSel sel = oneDictionary(dDict, (uint32_t)dictSize);
+    return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, &sel);
 }
 
 // ---- digested decode dictionaries (ZSTD_createDDict / ZSTD_decompress_usingDDict): loaded and checked once (loadDict), the bytes and the image
@@ -741,24 +751,93 @@ extern "C" zsmi_ddict *zsmi_createDDict(zsmi_ctx *c, const void *dict, size_t di
 extern "C" void zsmi_freeDDict(zsmi_ddict *dd) { delete dd; }
 extern "C" unsigned zsmi_getDictID_fromDDict(const zsmi_ddict *dd) { return dd ? dd->dictID : 0; }
 extern "C" size_t zsmi_sizeofDDict(const zsmi_ddict *dd) { return dd ? dd->dBytes.cap + dd->dImg.cap : 0; }
-// What a zsmi_ddict * argument asks of a call on context c - 0, with bytes / size / img set (all null: the plain call, for a null ddict or one
-// without bytes); or the error (a dictionary digested on another device: parameter_unsupported)
-static int resolveDDict(const zsmi_ctx *c, const zsmi_ddict *dd, const void *&bytes, uint32_t &size, const ZsDDictImage *&img)
+// What a zsmi_ddict * argument asks of a call on context c - 0, with the call's selector set: the set ({}, unnamed = dd) (one that holds no
+// dictionary: the plain call, for a null ddict or one without bytes); or the error (a dictionary digested on another device: parameter_unsupported)
+static int resolveDDict(const zsmi_ctx *c, const zsmi_ddict *dd, ZsDictSel &sel)
 {
-    bytes = nullptr; size = 0; img = nullptr;
+    sel = ZsDictSel();
     if (!dd) return 0;
     if (!c) return ZSMI_error_init_missing;
     if (dd->device != c->device) return ZSMI_error_parameter_unsupported;
-    if (!dd->empty) { bytes = dd->dBytes.p; size = dd->dictSize; img = (const ZsDDictImage *)dd->dImg.p; }
+    if (!dd->empty) sel = oneDictionary(dd->dBytes.p, dd->dictSize, (const ZsDDictImage *)dd->dImg.p, dd->dictID);
     return 0;
 }
 extern "C" int zsmi_decompressBatchDevice_usingDDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                                      const zsmi_ddict *dd)
 {
-    const void *bytes; uint32_t size; const ZsDDictImage *img;
-    if (const int e = resolveDDict(c, dd, bytes, size, img)) return e;
-    return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, bytes, size, img);
+    ZsDictSel sel;
+    if (const int e = resolveDDict(c, dd, sel)) return e;
+    return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, &sel);
+}
+
+// ---- DDict sets (ZSTD_d_refMultipleDDicts): a read-only device table of digested dictionaries, sorted by ID; a call with a set gives every
+// frame the member its dictID names, on the device (zs_dict_index, decode_kernels.hip).  The set copies nothing from its members: the table holds
+// {ID, size, image, bytes} of each, and `sel` is the selector its calls pass to the kernels - the table, and `unnamed` for the frames that name no
+// dictionary.  Every check is the host's, before anything touches the device; the one upload is waited for, once. ----
+struct zsmi_ddictSet {
+    int device = 0;
+    uint32_t members = 0;                // dictionaries a frame can name: dds[], and a formatted `unnamed`
+    ZsDictSel sel = ZsDictSel();
+    DevBuf dTable;
+};
+#define ZSMI_DDICTSET_MAX 4096u
+extern "C" zsmi_ddictSet *zsmi_createDDictSet(zsmi_ctx *c, const zsmi_ddict *const *dds, uint32_t n, const zsmi_ddict *unnamed, int *err)
+{
+    int code = 0;
+    zsmi_ddictSet *set = nullptr;
+    do {
+        if (!c) { code = ZSMI_error_init_missing; break; }
+        if (n > ZSMI_DDICTSET_MAX) { code = ZSMI_error_parameter_outOfBound; break; }
+        if (n && !dds) { code = ZSMI_error_parameter_unsupported; break; }
+        std::vector<ZsDictEntry> table(n);
+        for (uint32_t i = 0; i < n && !code; i++) {
+            const zsmi_ddict *dd = dds[i];
+            // a member: there, of this device, formatted (raw content has no ID a frame could name: it can only be `unnamed`)
+            if (!dd || dd->device != c->device || dd->empty || dd->dictID == 0) { code = ZSMI_error_parameter_unsupported; break; }
+            table[i].dictID = dd->dictID; table[i].size = dd->dictSize; table[i].img = (const ZsDDictImage *)dd->dImg.p; table[i].bytes = (const uint8_t *)dd->dBytes.p;
+        }
+        if (code) break;
+        if (unnamed && unnamed->device != c->device) { code = ZSMI_error_parameter_unsupported; break; }
+        std::sort(table.begin(), table.end(), [](const ZsDictEntry &a, const ZsDictEntry &b) { return a.dictID < b.dictID; });
+        const uint32_t unnamedID = (unnamed && !unnamed->empty) ? unnamed->dictID : 0;      // (formatted: a member under its own ID)
+        for (uint32_t i = 0; i < n && !code; i++)
+            if ((i && table[i].dictID == table[i - 1].dictID) || table[i].dictID == unnamedID) code = ZSMI_error_parameter_unsupported;
+        if (code) break;
+        set = new (std::nothrow) zsmi_ddictSet();
+        if (!set) { code = ZSMI_error_memory_allocation; break; }
+        set->device = c->device; set->members = n + (unnamedID != 0);
+        if (unnamed && !unnamed->empty) set->sel = oneDictionary(unnamed->dBytes.p, unnamed->dictSize, (const ZsDDictImage *)unnamed->dImg.p, unnamed->dictID);
+        if (n == 0) break;
+        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        if (!set->dTable.reserve(sizeof(ZsDictEntry) * n)) { code = ZSMI_error_memory_allocation; break; }
+        if (hipMemcpyAsync(set->dTable.p, table.data(), sizeof(ZsDictEntry) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        set->sel.table = (const ZsDictEntry *)set->dTable.p; set->sel.n = n;
+    } while (0);
+    if (code) { delete set; set = nullptr; }
+    if (err) *err = code;
+    return set;
+}
+extern "C" void zsmi_freeDDictSet(zsmi_ddictSet *set) { delete set; }
+extern "C" uint32_t zsmi_sizeofDDictSetMembers(const zsmi_ddictSet *set) { return set ? set->members : 0; }
+// resolveDDict's sibling: what a zsmi_ddictSet * argument asks of a call on context c (null, or a set that holds nothing: the plain call)
+static int resolveDDictSet(const zsmi_ctx *c, const zsmi_ddictSet *set, ZsDictSel &sel)
+{
+    sel = ZsDictSel();
+    if (!set) return 0;
+    if (!c) return ZSMI_error_init_missing;
+    if (set->device != c->device) return ZSMI_error_parameter_unsupported;
+    sel = set->sel;
+    return 0;
+}
+extern "C" int zsmi_decompressBatchDevice_usingDDictSet(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                        uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
+                                                        const zsmi_ddictSet *set)
+{
+    ZsDictSel sel;
+    if (const int e = resolveDDictSet(c, set, sel)) return e;
+    return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, &sel);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -895,22 +974,20 @@ extern "C" int zsmi_compressBatchHost_usingCDict(zsmi_ctx *c, const void *src, c
     if (const int e = resolveCDict(c, cd, level, dict)) return e;
     return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict);
 }
-// dict / dictSize: the call's dictionary in host memory, which this call stages; or dd: a digested one, whose bytes are on the device already
+// dict / dictSize: the call's dictionary in host memory, which this call stages; or digested: the selector of digested ones (a DDict's or a
+// set's), whose bytes are on the device already
 static int decompressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
-                                   const void *dict, size_t dictSize, const zsmi_ddict *dd = nullptr)
+                                   const void *dict, size_t dictSize, const ZsDictSel *digested = nullptr)
 {
-    const void *ddBytes; uint32_t ddSize; const ZsDDictImage *img;
-    if (const int e = resolveDDict(c, dd, ddBytes, ddSize, img)) return e;
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    const bool useDict = !img && dict != nullptr && dictSize != 0;
+    const bool useDict = !digested && dict != nullptr && dictSize != 0;
     return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, useDict ? dict : nullptr, dictSize,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      if (img) return decompressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dstCaps, dSizes, ddBytes, ddSize, img);
-                      return decompressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dstCaps, dSizes, useDict ? c->sDict.p : nullptr,
-                                                       useDict ? (uint32_t)dictSize : 0u);
+                      const ZsDictSel stagedDict = oneDictionary(useDict ? c->sDict.p : nullptr, (uint32_t)dictSize);
+                      return decompressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dstCaps, dSizes, digested ? digested : &stagedDict);
                   });
 }
 
@@ -929,7 +1006,17 @@ extern "C" int zsmi_decompressBatchHost_usingDDict(zsmi_ctx *c, const void *src,
                                                    uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
                                                    const zsmi_ddict *dd)
 {
-    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, nullptr, 0, dd);
+    ZsDictSel sel;
+    if (const int e = resolveDDict(c, dd, sel)) return e;
+    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, nullptr, 0, &sel);
+}
+extern "C" int zsmi_decompressBatchHost_usingDDictSet(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                      uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
+                                                      const zsmi_ddictSet *set)
+{
+    ZsDictSel sel;
+    if (const int e = resolveDDictSet(c, set, sel)) return e;
+    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, nullptr, 0, &sel);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1026,15 +1113,19 @@ extern "C" size_t zsmi_decompress(void *dst, size_t dstCapacity, const void *src
     return zsmi_decompress_usingDict(dst, dstCapacity, src, srcSize, nullptr, 0);
 }
 
-// one frame (or several concatenated) through a borrowed context: with the dictionary's bytes (or none), or with the digested dictionary dd
-static size_t decompressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, const zsmi_ddict *dd)
+// one frame (or several concatenated) through a borrowed context: with the dictionary's bytes (or none), with the digested dictionary dd, or
+// with the DDict set
+static size_t decompressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, const zsmi_ddict *dd,
+                                const zsmi_ddictSet *set = nullptr)
 {
     if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
     Borrowed b; zsmi_ctx *c = b.c;
     if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
     const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
     const uint32_t cap = (uint32_t)std::min<size_t>(dstCapacity, 0xFFFFFF00u);
-    const int rc = decompressBatchHostImpl(c, src, &so, &ss, 1, dst, &dof, &cap, &ds, dict, dictSize, dd);
+    ZsDictSel sel;
+    if (const int e = set ? resolveDDictSet(c, set, sel) : resolveDDict(c, dd, sel)) return ZSMI_ERR(e);
+    const int rc = decompressBatchHostImpl(c, src, &so, &ss, 1, dst, &dof, &cap, &ds, dict, dictSize, (dd || set) ? &sel : nullptr);
     if (rc) return ZSMI_ERR(rc);
     if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
     return ds;
@@ -1047,6 +1138,11 @@ extern "C" size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const
 extern "C" size_t zsmi_decompress_usingDDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_ddict *dd)
 {
     return decompressOneShot(dst, dstCapacity, src, srcSize, nullptr, 0, dd);
+}
+// a null set: zsmi_decompress
+extern "C" size_t zsmi_decompress_usingDDictSet(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_ddictSet *set)
+{
+    return decompressOneShot(dst, dstCapacity, src, srcSize, nullptr, 0, nullptr, set);
 }
 
 #ifdef ZSMI_DEBUG_HOOKS

@@ -141,6 +141,6 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
                                    const ZsCompressDict *dict, uint32_t *dStats = nullptr);
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
-                                     const void *dDict, uint32_t dictSize, const struct ZsDDictImage *img = nullptr);
+                                     const struct ZsDictSel *dict);
 // a context of the one-shot pool (zsmi_api.hip), given back when the handle goes
 namespace { struct Borrowed { zsmi_ctx *c; Borrowed(); ~Borrowed(); }; }
