@@ -258,9 +258,44 @@ size_t zsmi_decompressSeekable(void *dst, size_t dstCapacity, const void *src, s
 /* Device buffers.  Reads back the table (the call waits for the context's stream), checks it, then queues the decode of the frames that
  * overlap [offset, offset + length) (clipped at the content's end) and returns; *written (host) receives the bytes the range holds,
  * *dStatus (device) 0 or the first failing frame's code.  Frames wholly inside the range decode straight into dDst, a partial first or
- * last frame into context scratch.  Writes only inside [dDst, dDst + *written). */
+ * last frame into context scratch.  Writes only inside [dDst, dDst + *written).  (The one-range read of an archive opened for this call
+ * alone: many reads of one archive belong to zsmi_openSeekableDevice and zsmi_seekableReadRangesDevice below.) */
 int zsmi_decompressSeekableDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, uint64_t offset, uint64_t length,
                                   void *dDst, uint64_t *written, uint32_t *dStatus);
+/* An opened archive (ZSTD_seekable_init*): the table read and checked once, then many reads through the handle.  A read is a batch of ranges:
+ * every frame the batch touches is decoded once, however many ranges touch it.
+ * zsmi_openSeekable: a host archive.  archive == NULL or size < 9: prefix_unknown; then the table's own rejections (as above); a NULL ctx:
+ * init_missing, only after those - so a host archive's table can be judged without a device.  The frames' bytes (not the table) are copied to
+ * device memory the handle owns, on ctx's device and stream, and waited for, once.
+ * zsmi_openSeekableDevice: an archive in device memory, borrowed: it must outlive the handle.  A NULL ctx: init_missing, first (the table is in
+ * device memory); the table is read back and the stream waited for, once, here.
+ * NULL on failure, with the code in *err if err != NULL.  A handle is read-only after creation: any context of the same device may use it (a
+ * context of another device: parameter_unsupported).  It must outlive the work queued with it: close it after zsmi_sync. */
+typedef struct zsmi_seekable zsmi_seekable;
+zsmi_seekable *zsmi_openSeekable(zsmi_ctx *ctx, const void *archive, size_t size, int *err);
+zsmi_seekable *zsmi_openSeekableDevice(zsmi_ctx *ctx, const void *dArchive, uint64_t size, int *err);
+void zsmi_closeSeekable(zsmi_seekable *sk);                        /* NULL: nothing */
+size_t zsmi_getNumFrames_fromSeekable(const zsmi_seekable *sk);    /* 0 for NULL */
+unsigned long long zsmi_getContentSize_fromSeekable(const zsmi_seekable *sk);   /* 0 for NULL */
+size_t zsmi_sizeofSeekable(const zsmi_seekable *sk);               /* device bytes held: the frames' bytes of a host archive; 0 for a borrowed archive, or NULL */
+/* nRanges reads in one call: content bytes [offsets[r], offsets[r] + lengths[r]), clipped at the content's end, land at dDst + dstOffsets[r];
+ * written[r] (host) receives the clipped length, dStatus[r] (device) 0 or the code of the first failing frame, in content order, among the
+ * frames range r overlaps (an empty range overlaps none: 0).  offsets, lengths, dstOffsets and written are host arrays, as the batch calls'.
+ * Checked on the host first - on failure nothing is queued or written and the code is returned: a NULL ctx: init_missing; a NULL sk, or a NULL
+ * array with nRanges > 0: GENERIC; a handle of another device: parameter_unsupported; any offsets[r] past the content size:
+ * parameter_outOfBound (offsets[r] == content size reads 0 bytes).  nRanges == 0 is a valid call that does nothing.
+ * The call decodes the union of the frames its ranges overlap, each once (*framesDecoded, host, may be NULL: how many).  A frame wholly inside
+ * the one range that overlaps it decodes straight to its place in dDst; every other one decodes into context scratch - the sum of the
+ * Decompressed_Size of those frames, memory_allocation when that cannot be reserved - from where its pieces are copied out.  Queues its work
+ * and returns: no device-to-host copy, no wait for the stream.  Range r writes only inside [dDst + dstOffsets[r], + written[r]), also when it
+ * fails (its bytes are then unspecified); the ranges' places must not overlap. */
+int zsmi_seekableReadRangesDevice(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *offsets, const uint64_t *lengths, uint32_t nRanges,
+                                  void *dDst, const uint64_t *dstOffsets, uint64_t *written, uint32_t *dStatus, uint32_t *framesDecoded);
+/* The host-buffer form: the results land back to back in range order (range r starts at the sum of written[0 .. r)), statuses[r] (host) is
+ * range r's code.  The same checks, then dstSize_tooSmall - before anything is queued - when the clipped lengths sum to more than
+ * dstCapacity.  Staged through device memory, copied back, synchronised. */
+int zsmi_seekableReadRangesHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *offsets, const uint64_t *lengths, uint32_t nRanges,
+                                void *dst, size_t dstCapacity, uint64_t *written, uint32_t *statuses);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

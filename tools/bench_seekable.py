@@ -5,9 +5,12 @@
   decode:    zsmi_decompressSeekableDevice of the whole archive vs zsmi_decompressBatchDevice of the same frames
   kernels:   k_seek_hash (compress) and k_seek_verify (decode), HIP-event timing of one call each
   latency:   a 4 KiB zsmi_decompressSeekable (one-shot, host buffers) from the middle of the archive, and the frames it overlaps
+  ranges:    --ranges N reads of --range-bytes B at seeded uniform offsets through an opened archive (zsmi_openSeekableDevice): ONE
+             zsmi_seekableReadRangesDevice call, the same ranges as N zsmi_decompressSeekableDevice calls one after the other, and the whole
+             archive as one range through the handle; ms, GiB/s of content delivered, distinct frames decoded
 Every call is followed by a synchronisation (the seekable read waits for its stream anyway), rates are the median over --reps calls.
 The archive and the decoded content are checked once.  Prints one JSON line.
-  python tools/bench_seekable.py [--mib 1024] [--reps 10] [--frame 65536]"""
+  python tools/bench_seekable.py [--mib 1024] [--reps 10] [--frame 65536] [--ranges 4096] [--range-bytes 4096]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +34,8 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--frame", type=int, default=65536)
     ap.add_argument("--level", type=int, default=3)
+    ap.add_argument("--ranges", type=int, default=4096)
+    ap.add_argument("--range-bytes", type=int, default=4096)
     a = ap.parse_args()
     size, F, level = a.mib << 20, a.frame, a.level
     gib = size / float(1 << 30)
@@ -85,6 +90,33 @@ def main():
         t = time.perf_counter(); got = sa.read(mid, 4096); lat.append(time.perf_counter() - t)
     assert got == data[mid:mid + 4096].tobytes()
     frames_4k = sum(1 for i in info if i[1] < mid + 4096 and i[1] + i[3] > mid)
+    # N short reads through an opened archive: one call, N single calls, and the whole archive as one range
+    N, B = a.ranges, a.range_bytes
+    offs = np.random.default_rng(7).integers(0, size - B, N).astype(np.uint64)
+    lens = np.full(N, B, dtype=np.uint64)
+    place = np.arange(N, dtype=np.uint64) * B
+    out_r = torch.zeros(N * B, dtype=torch.uint8, device="cuda")
+    st_r = torch.ones(N, dtype=torch.int32, device="cuda")
+    want_r = src[(torch.from_numpy(offs.astype(np.int64)).cuda()[:, None] + torch.arange(B, device="cuda")[None, :]).reshape(-1)]
+    torch.cuda.synchronize()
+    h = bc.open_seekable_device(arc.data_ptr(), asize)
+    assert h.num_frames == n and h.content_size == size and h.device_bytes == 0
+    frames_r = [0]
+    def one_call():
+        frames_r[0] = h.read_ranges_device(offs, lens, out_r.data_ptr(), place, st_r.data_ptr())[1]
+    t_ranges = timed(one_call, bc.sync, a.reps)
+    assert not st_r.any().item() and torch.equal(out_r, want_r), "the batch of ranges differs from the content"
+    out_r.zero_()
+    def single_calls():
+        for i in range(N):
+            bc.decompress_seekable_device(arc.data_ptr(), asize, int(offs[i]), B, out_r.data_ptr() + i * B, status.data_ptr())
+    t_singles = timed(single_calls, bc.sync, min(a.reps, 3))
+    assert torch.equal(out_r, want_r), "the single reads differ from the content"
+    out_seek.zero_()
+    t_whole = timed(lambda: h.read_ranges_device([0], [size], out_seek.data_ptr(), [0], status.data_ptr()), bc.sync, a.reps)
+    assert int(status.item()) == 0 and torch.equal(out_seek, src), "the archive as one range differs from the content"
+    h.close()
+    rgib = N * B / float(1 << 30)
     ms = lambda kt, k: round(kt.get(k, (0.0, 0))[0] * 1e3, 4)
     rep = {"metric": "seekable", "gib": gib, "frame": F, "level": level, "frames": n, "archive_bytes": asize, "ratio": round(size / asize, 4),
            "compress_batch_gibs": round(gib / t_batch_c, 2), "compress_seekable_gibs": round(gib / t_seek_c, 2),
@@ -96,7 +128,12 @@ def main():
            "compress_kernels_ms": {k: round(v[0] * 1e3, 4) for k, v in kt_c.items()},
            "decode_kernels_ms": {k: round(v[0] * 1e3, 4) for k, v in kt_d.items()},
            "read_4k_ms_median": round(float(np.median(lat[3:])) * 1e3, 4), "read_4k_ms_min": round(float(np.min(lat[3:])) * 1e3, 4),
-           "read_4k_frames": frames_4k}
+           "read_4k_frames": frames_4k,
+           "ranges": N, "range_bytes": B, "ranges_frames_decoded": frames_r[0],
+           "ranges_one_call_ms": round(t_ranges * 1e3, 4), "ranges_one_call_gibs": round(rgib / t_ranges, 3),
+           "ranges_single_calls_ms": round(t_singles * 1e3, 3), "ranges_single_calls_gibs": round(rgib / t_singles, 4),
+           "ranges_one_call_speedup": round(t_singles / t_ranges, 1),
+           "whole_as_one_range_ms": round(t_whole * 1e3, 3), "whole_as_one_range_gibs": round(gib / t_whole, 2)}
     bc.close()
     print(json.dumps(rep))
 

@@ -136,6 +136,14 @@ def lib():
     L.zsmi_seekableNumFrames.restype = sz; L.zsmi_seekableNumFrames.argtypes = [vp, sz]
     L.zsmi_seekableContentSize.restype = sz; L.zsmi_seekableContentSize.argtypes = [vp, sz]
     L.zsmi_seekableFrameInfo.restype = i32; L.zsmi_seekableFrameInfo.argtypes = [vp, sz, u32, pu64, pu64, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.zsmi_openSeekable.restype = vp; L.zsmi_openSeekable.argtypes = [vp, vp, sz, ctypes.POINTER(i32)]
+    L.zsmi_openSeekableDevice.restype = vp; L.zsmi_openSeekableDevice.argtypes = [vp, vp, u64, ctypes.POINTER(i32)]
+    L.zsmi_closeSeekable.restype = None; L.zsmi_closeSeekable.argtypes = [vp]
+    L.zsmi_getNumFrames_fromSeekable.restype = sz; L.zsmi_getNumFrames_fromSeekable.argtypes = [vp]
+    L.zsmi_getContentSize_fromSeekable.restype = ull; L.zsmi_getContentSize_fromSeekable.argtypes = [vp]
+    L.zsmi_sizeofSeekable.restype = sz; L.zsmi_sizeofSeekable.argtypes = [vp]
+    L.zsmi_seekableReadRangesDevice.restype = i32; L.zsmi_seekableReadRangesDevice.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, ctypes.POINTER(u32)]
+    L.zsmi_seekableReadRangesHost.restype = i32; L.zsmi_seekableReadRangesHost.argtypes = [vp, vp, vp, vp, u32, vp, sz, vp, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -162,4 +170,6 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_packFramesDevice", "zsmi_enableKernelTiming", "zsmi_getKernelTimes", "zsmi_versionString", "zsmi_decodeScratchBytes", "zsmi_shutdown",
            "zsmi_seekableBound", "zsmi_compressSeekable", "zsmi_compressSeekableDevice", "zsmi_decompressSeekable", "zsmi_decompressSeekableDevice",
            "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo",
+           "zsmi_openSeekable", "zsmi_openSeekableDevice", "zsmi_closeSeekable", "zsmi_getNumFrames_fromSeekable", "zsmi_getContentSize_fromSeekable",
+           "zsmi_sizeofSeekable", "zsmi_seekableReadRangesDevice", "zsmi_seekableReadRangesHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID"]

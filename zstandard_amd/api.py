@@ -7,6 +7,7 @@
   ZstdCompressor      the compressor the reference lacks (north_star), same calling conventions.
   SeekableArchive     random access into a seekable archive (zstd's seekable format: independent frames + a seek table), made by
                       ZstdCompressor.compress_seekable or BatchCodec.compress_seekable_device.
+  SeekableHandle      an archive in device memory opened once (zsmi_openSeekableDevice): batches of range reads, every frame decoded once.
   BatchCodec          the batch hot path on device memory (torch tensors are only a handle to device memory here).
   CompressionDict     a digested dictionary (zsmi_createCDict): parsed and laid out on the device once, used by many calls; with a
                       formatted dictionary its entropy tables code the first block of a frame where that is smaller.
@@ -245,13 +246,62 @@ class ZstdCompressor:
 
 class SeekableArchive:
     """A seekable archive in host memory.  The table is checked when the object is made (RuntimeError with the error's name, as every
-    read); read() decodes on the GPU only the frames that overlap the range."""
+    read); read() decodes on the GPU only the frames that overlap the range.  read_many() reads a batch of ranges through an opened
+    archive (zsmi_openSeekable: the frames go to device memory once, at the first call; close() frees them), every frame the batch
+    touches decoded once."""
 
     def __init__(self, archive):
         self.L = _lib.lib()
+        self.codec = self.handle = None
         self.archive = bytes(archive)
         self.num_frames = _raise_if_error(self.L, self.L.zsmi_seekableNumFrames(self.archive, len(self.archive)))
         self.content_size = _raise_if_error(self.L, self.L.zsmi_seekableContentSize(self.archive, len(self.archive)))
+
+    def close(self):
+        if self.handle:
+            self.L.zsmi_closeSeekable(self.handle)
+            self.handle = None
+        if self.codec is not None:
+            self.codec.close()
+            self.codec = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def read_many(self, ranges, return_codes=False):
+        """ranges: (offset, length) pairs -> the list of their bytes (each clipped at the content's end), one call for all of them
+        (zsmi_seekableReadRangesHost).  A failing range raises RuntimeError with the error's name and the range's index; with
+        return_codes=True nothing raises for a range and the result is (list, codes): codes[r] is 0 or range r's error code, whose
+        bytes are then unspecified."""
+        if self.handle is None:
+            self.codec = self.codec or BatchCodec()
+            err = ctypes.c_int(0)
+            self.handle = self.L.zsmi_openSeekable(self.codec.ctx, self.archive, len(self.archive), ctypes.byref(err))
+            if not self.handle:
+                raise RuntimeError(_error_name(self.L, err.value))
+        ranges = list(ranges)
+        n = len(ranges)
+        off = np.array([r[0] for r in ranges], dtype=np.uint64); ln = np.array([r[1] for r in ranges], dtype=np.uint64)
+        if n and int(off.max()) > self.content_size:
+            raise RuntimeError(_error_name(self.L, 42))                    # parameter_outOfBound (before the capacity is worked out)
+        cap = int(sum(min(int(l), self.content_size - int(o)) for o, l in zip(off, ln)))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        written = np.zeros(max(n, 1), dtype=np.uint64); codes = np.zeros(max(n, 1), dtype=np.uint32)
+        p = BatchCodec._p
+        rc = self.L.zsmi_seekableReadRangesHost(self.codec.ctx, self.handle, p(off), p(ln), n, p(out), cap, p(written), p(codes))
+        if rc:
+            raise RuntimeError(_error_name(self.L, rc))
+        codes = [int(c) for c in codes[:n]]
+        if not return_codes:
+            for r, c in enumerate(codes):
+                if c:
+                    raise RuntimeError(f"{_error_name(self.L, c)} (range {r})")
+        ends = np.cumsum(written[:n]).astype(np.int64)
+        res = [out[int(e) - int(w):int(e)].tobytes() for e, w in zip(ends, written[:n])]
+        return (res, codes) if return_codes else res
 
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`"""
@@ -319,6 +369,57 @@ def get_dict_id(dic) -> int:
     """the ID of a formatted dictionary; 0 for raw content (host only)"""
     dic = bytes(dic)
     return int(_lib.lib().zsmi_getDictID(dic, len(dic)))
+
+
+class SeekableHandle:
+    """An opened seekable archive in device memory (zsmi_openSeekableDevice; BatchCodec.open_seekable_device makes it).  Read-only: any
+    BatchCodec of the same device may read through it.  It must stay open until the work queued with it is done (BatchCodec.sync)."""
+
+    def __init__(self, codec, d_ptr, size):
+        self.L, self.codec = codec.L, codec
+        err = ctypes.c_int(0)
+        self.handle = self.L.zsmi_openSeekableDevice(codec.ctx, ctypes.c_void_p(d_ptr), size, ctypes.byref(err))
+        if not self.handle:
+            raise RuntimeError(f"zsmi_openSeekableDevice: {_error_name(self.L, err.value)}")
+
+    @property
+    def num_frames(self) -> int:
+        return int(self.L.zsmi_getNumFrames_fromSeekable(self.handle))
+
+    @property
+    def content_size(self) -> int:
+        return int(self.L.zsmi_getContentSize_fromSeekable(self.handle))
+
+    @property
+    def device_bytes(self) -> int:
+        return int(self.L.zsmi_sizeofSeekable(self.handle))
+
+    def read_ranges_device(self, offsets, lengths, d_dst_ptr, dst_offsets, d_status_ptr, codec=None):
+        """content [offsets[r], offsets[r] + lengths[r]) to d_dst + dst_offsets[r], for every r in one call (asynchronous, on `codec`'s
+        stream: the one the handle was opened with unless given); d_status_ptr: device uint32[n], 0 or range r's error code.  Returns
+        (written: the lengths clipped at the content's end, frames_decoded: distinct frames the call decodes)."""
+        codec = codec or self.codec
+        off = np.ascontiguousarray(offsets, dtype=np.uint64); ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        do = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        written = np.zeros(len(off), dtype=np.uint64)
+        frames = ctypes.c_uint32(0)
+        p = BatchCodec._p
+        rc = self.L.zsmi_seekableReadRangesDevice(codec.ctx, self.handle, p(off), p(ln), len(off), ctypes.c_void_p(d_dst_ptr), p(do), p(written),
+                                                  ctypes.c_void_p(d_status_ptr), ctypes.byref(frames))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableReadRangesDevice: {_error_name(self.L, rc)}")
+        return written, frames.value
+
+    def close(self):
+        if self.handle:
+            self.L.zsmi_closeSeekable(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BatchCodec:
@@ -411,6 +512,11 @@ class BatchCodec:
         if rc:
             raise RuntimeError(f"zsmi_decompressSeekableDevice: {_error_name(self.L, rc)}")
         return written.value
+
+    def open_seekable_device(self, d_ptr, size):
+        """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The
+        table is read back and checked here, once (RuntimeError with the error's name)."""
+        return SeekableHandle(self, d_ptr, size)
 
     def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b"", cdict=None):
         """returns (arena uint8, dst_offsets uint64, dst_sizes uint32).  dictionary: one for every chunk (raw content or a formatted

@@ -7,15 +7,18 @@
 // Compress: the frames are the chunks of one zsmi_compressBatchDevice call (chunk i = src[i F, min((i + 1) F, size))) into context staging at
 // compressBound(F) spacing; k_seek_hash hashes the INPUT of each frame (checksum flag), the pack kernels close the gaps into dDst, k_seek_table
 // writes the table behind them and the archive's size (or the first failing frame's code).
-// Decompress: the table is read and checked on the host; the frames that overlap the range are items of the batch decoder with their exact
-// Decompressed_Size as capacity - the ones wholly inside the range decode straight into dDst, a partial first / last one into context scratch
-// and is copied in slices - then k_seek_verify checks every decoded frame's size and checksum against its entry.
+// Decompress: the table is read and checked on the host - once for an opened archive (zsmi_seekable), per call by the single-range calls.  A
+// read is a batch of ranges: the union of the frames they overlap are items of the batch decoder with their exact Decompressed_Size as
+// capacity, each decoded once - a frame wholly inside the one range that touches it straight into dDst, every other one into context scratch,
+// from where k_seek_gather copies its overlaps with the ranges - then k_seek_verify checks every decoded frame's size and checksum against
+// its entry and k_seek_range_status gives each range the code of its first failing frame.
 
 #include "zsmi_wave.h"            // zs_block_copy, xxh64_quad, rd32
 #include "entropy_kernels.hip"    // k_pack_offsets
 #include "decode_kernels.hip"     // the decoder's error codes (E_*)
 #include "zsmi_ctx.h"
 #include <algorithm>
+#include <new>
 
 static const uint32_t kSeekSkippableMagic = 0x184D2A5Eu, kSeekableMagic = 0x8F92EAB1u;
 static const uint64_t kSeekMaxFrames = 0x8000000ull, kSeekMaxFrameSize = 1ull << 30;
@@ -72,15 +75,34 @@ __global__ void k_seek_finish(const uint64_t *__restrict__ packedOffsets, uint32
 }
 
 struct ZsSeekItem { uint64_t out; uint32_t size, hash, slot, pad; };     // a decoded frame: where its bytes are, its entry, its status word
-struct ZsSeekSlices { uint64_t from[2], to[2], len[2]; };               // partial frames: scratch -> dDst
-__global__ void k_seek_slice(const uint8_t *__restrict__ scratch, uint8_t *__restrict__ dst, ZsSeekSlices s)
+struct ZsSeekPiece { uint64_t from, to; uint32_t len, pad; };            // one scratch frame's overlap with one range (a tile of it): scratch + from -> dDst + to
+struct ZsSeekSpan { uint32_t firstSlot, count; };                        // a range's frames: consecutive entries of the per-frame code array
+static const uint32_t kSeekTile = 64u << 10;         // the most a workgroup of k_seek_gather copies: longer pieces are cut into tiles in the list
+static const uint32_t kSeekWavePiece = 4u << 10;     // pieces up to this take one wavefront each (four to a workgroup): 64 lanes x 16 bytes x 4 in flight
+
+// The pieces of the frames that more than one range reads, or one range reads in part: scratch -> dDst.  pieces[0, nSmall) are the short ones
+// (records: up to kSeekWavePiece bytes), a wavefront each, four to a workgroup; pieces[nSmall, nPieces) are tiles of up to kSeekTile bytes, a
+// workgroup each.  Lane i moves the 16 bytes at 16 i of each 1 KiB (4 KiB a workgroup) step: whatever the two alignments are, a wavefront's
+// accesses are one contiguous run.
+__global__ void __launch_bounds__(256) k_seek_gather(const uint8_t *__restrict__ scratch, uint8_t *__restrict__ dst, const ZsSeekPiece *__restrict__ pieces,
+                                                     uint32_t nSmall, uint32_t nPieces)
 {
-    const uint32_t k = blockIdx.x;
-    zs_block_copy(dst + s.to[k], scratch + s.from[k], (uint32_t)s.len[k], threadIdx.x, blockDim.x);
+    const uint32_t gSmall = (nSmall + 3) / 4;
+    if (blockIdx.x < gSmall) {
+        const uint32_t k = blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (k >= nSmall) return;
+        const ZsSeekPiece p = pieces[k];
+        zs_block_copy(dst + p.to, scratch + p.from, p.len, threadIdx.x & 63u, 64u);
+    } else {
+        const uint32_t k = nSmall + (blockIdx.x - gSmall);
+        if (k >= nPieces) return;
+        const ZsSeekPiece p = pieces[k];
+        zs_block_copy(dst + p.to, scratch + p.from, p.len, threadIdx.x, 256u);
+    }
 }
 // one quad a decoded frame: its decoder status, its size against the entry (a frame the decoder found longer than its entry failed with
-// dstSize_tooSmall: that is the same disagreement), its checksum (flag set).  The first failing frame in content order wins (*err, set to ~0 before).
-__global__ void __launch_bounds__(64) k_seek_verify(const ZsSeekItem *__restrict__ items, uint32_t m, const uint32_t *__restrict__ status, int checksum, unsigned long long *err)
+// dstSize_tooSmall: that is the same disagreement), its checksum (flag set).  codes[q]: frame q's code (0: none), the frames in index order.
+__global__ void __launch_bounds__(64) k_seek_verify(const ZsSeekItem *__restrict__ items, uint32_t m, const uint32_t *__restrict__ status, int checksum, uint32_t *__restrict__ codes)
 {
     const uint32_t q = blockIdx.x * 16 + (threadIdx.x >> 2);
     const bool real = q < m;
@@ -94,12 +116,28 @@ __global__ void __launch_bounds__(64) k_seek_verify(const ZsSeekItem *__restrict
         const uint64_t h = xxh64_quad<kSeekHashAhead>((const uint8_t *)it.out, hash ? it.size : 0u);
         if (hash && (uint32_t)h != it.hash) code = E_checksum_wrong;
     }
-    if (real && code && (threadIdx.x & 3u) == 0) atomicMin(err, ((unsigned long long)q << 8) | code);
+    if (real && (threadIdx.x & 3u) == 0) codes[q] = code;
 }
-__global__ void k_seek_status(const unsigned long long *__restrict__ err, uint32_t *status)
+// one wavefront a range (four to a workgroup): the code of the first failing frame, in content order, among the range's frames - the lanes
+// stride over the span, each stops at its first failing entry k, the lowest k of the wavefront decides (k alone is reduced: an archive may
+// hold 2^27 frames, so k << 8 | code does not fit the 32 bits of the wave_* primitives).  An empty range: 0.
+__global__ void __launch_bounds__(256) k_seek_range_status(const ZsSeekSpan *__restrict__ spans, uint32_t nRanges, const uint32_t *__restrict__ codes, uint32_t *__restrict__ status)
 {
-    const unsigned long long e = *err;
-    *status = e == ~0ull ? 0u : (uint32_t)(e & 0xFFu);
+    const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (r >= nRanges) return;                                            // (the same for every lane of a wavefront)
+    const ZsSeekSpan s = spans[r];
+    uint32_t first = ~0u;
+    // (eight entries a lane and round.  The whole archive as one range is 16384 entries and takes 0.066 ms here: the compiler still waits for each
+    // of the eight guarded loads in turn; loads at a clamped index, none behind a branch, are the next step, not measured yet)
+    for (uint32_t k0 = lane; k0 < s.count && first == ~0u; k0 += 64 * 8) {
+        uint32_t v[8];
+        #pragma unroll
+        for (uint32_t j = 0; j < 8; j++) { const uint32_t k = k0 + 64 * j; v[j] = k < s.count ? codes[s.firstSlot + k] : 0u; }
+        #pragma unroll
+        for (uint32_t j = 0; j < 8; j++) if (v[j] && first == ~0u) first = k0 + 64 * j;
+    }
+    first = wave_min(first);
+    if (lane == 0) status[r] = first == ~0u ? 0u : codes[s.firstSlot + first];
 }
 
 // ---- host: parameters, bound, the table ----
@@ -255,61 +293,241 @@ static void seekSpan(const SeekTable &t, uint64_t a, uint64_t b, uint32_t &first
     first = (uint32_t)(std::upper_bound(t.dOff.begin(), t.dOff.end(), a) - t.dOff.begin()) - 1;
     last = (uint32_t)(std::lower_bound(t.dOff.begin(), t.dOff.end(), b) - t.dOff.begin()) - 1;
 }
-// Queue the decode of [a, b) on the context's stream.  Frame i's compressed bytes are at dFrames + t.cOff[i] - base.  The context must be idle
-// on the host side (seek.hItems is refilled): the callers have waited for its stream.
-static int seekReadQueue(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames, uint64_t base, uint64_t a, uint64_t b, uint8_t *dDst, uint32_t *dStatus)
+// the table of an archive in device memory: its tail is read back and the stream waited for
+static int seekParseDevice(zsmi_ctx *c, const uint8_t *src, uint64_t srcSize, SeekTable &t)
 {
-    if (hipMemsetAsync(dStatus, 0, sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (a == b) return 0;
-    uint32_t first, last;
-    seekSpan(t, a, b, first, last);
-    const uint32_t m = last - first + 1;
-    // frames wholly inside the range: items [in0, in1) of the span, straight into dDst; the first and the last may be partial (scratch)
-    const bool partFirst = t.dOff[first] < a || t.dOff[first + 1] > b, partLast = last != first && t.dOff[last + 1] > b;
-    const uint32_t in0 = partFirst ? 1 : 0, in1 = partLast ? m - 1 : m;
-    // status words: [m] for the span in content order, [2] behind them for the partial frames' decode call; (8-aligned) the error word; the verify list
-    const size_t words = (((size_t)m + 3) & ~(size_t)1) * sizeof(uint32_t);
-    if (!c->seek.dMeta.reserve(words + sizeof(uint64_t) + (size_t)m * sizeof(ZsSeekItem)) || !c->seek.hItems.reserve((size_t)m * sizeof(ZsSeekItem))) return ZSMI_error_memory_allocation;
-    uint32_t *dSt = (uint32_t *)c->seek.dMeta.p;
-    unsigned long long *dErr = (unsigned long long *)((uint8_t *)c->seek.dMeta.p + words);
-    ZsSeekItem *dItems = (ZsSeekItem *)(dErr + 1);
-    ZsSeekItem *hi = (ZsSeekItem *)c->seek.hItems.p;
-    std::vector<uint64_t> so, dof; std::vector<uint32_t> ss, caps;
-    auto item = [&](uint32_t k, uint8_t *dBase, uint64_t at, uint32_t slot) {
-        const uint32_t i = first + k;
-        so.push_back(t.cOff[i] - base); ss.push_back(t.cSize[i]); caps.push_back(t.dSize[i]); dof.push_back(at);
-        hi[k] = { (uint64_t)(uintptr_t)(dBase + at), t.dSize[i], t.hash[i], slot, 0 };
+    // the archive's tail, once: it holds the whole table up to 256 KiB (16384 entries with checksums: 1 GiB in 64 KiB frames); a larger
+    // table is read again at its size
+    std::vector<uint8_t> tail(std::min<uint64_t>(srcSize, 256u << 10));
+    if (hipMemcpyAsync(tail.data(), src + srcSize - tail.size(), tail.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = seekFooter(tail.data() + tail.size() - 9, srcSize, t)) return e;
+    if (t.tableSize > tail.size()) {
+        tail.resize(t.tableSize);
+        if (hipMemcpyAsync(tail.data(), src + srcSize - t.tableSize, t.tableSize, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    }
+    return seekEntries(tail.data() + tail.size() - t.tableSize, srcSize, t);
+}
+
+// A batch of range reads, queued on the context's stream: content [a, b) (b <= content size; a == b: nothing) lands at dDst + to.  Frame i's
+// compressed bytes are at dFrames + t.cOff[i] - base.
+//   The plan: every range's frames are seekSpan's first .. last; the union of those index sets, in index order, is what the call decodes -
+// each frame once, slot s of the union.  A frame that lies wholly inside the one range that overlaps it is OWNED: it decodes straight to its
+// place in dDst.  Every other frame of the union (read in part, or by several ranges) decodes into context scratch, those packed back to back,
+// and each of its overlaps with a range is a PIECE {scratch offset, dDst offset, length} for k_seek_gather, cut into tiles of kSeekTile.
+// That is one decode call for the owned frames and one for the scratch frames, whatever nRanges is.  k_seek_verify leaves a code per slot; a
+// range's frames are consecutive slots {firstSlot, count}, which k_seek_range_status reduces to dStatus[r].
+//   The call's lists (verify items, pieces, spans) travel through one of two pinned buffers taken in turn, each guarded by an event, as the
+// decoder's item list does (uploadDecodeItems): nothing here waits for the stream.
+struct SeekRange { uint64_t a, b, to; };
+static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames, uint64_t base, const SeekRange *rg, uint32_t nRanges,
+                          uint8_t *dDst, uint32_t *dStatus, uint32_t *framesDecoded)
+{
+    if (framesDecoded) *framesDecoded = 0;
+    if (nRanges == 0) return 0;
+    // the ranges' spans, and their union as runs of consecutive frames {lo, hi} with the slot of lo
+    struct Span { uint32_t first, count; };
+    struct Run { uint32_t lo, hi, slot0; };
+    std::vector<Span> sp(nRanges, Span{ 0, 0 });
+    std::vector<uint32_t> order;
+    for (uint32_t r = 0; r < nRanges; r++) {
+        if (rg[r].a == rg[r].b) continue;
+        uint32_t first, last;
+        seekSpan(t, rg[r].a, rg[r].b, first, last);
+        sp[r] = { first, last - first + 1 };
+        order.push_back(r);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return sp[x].first < sp[y].first; });
+    std::vector<Run> runs;
+    for (const uint32_t r : order) {
+        const uint32_t lo = sp[r].first, hi = lo + sp[r].count - 1;
+        if (runs.empty() || lo > runs.back().hi + 1) runs.push_back({ lo, hi, 0 });
+        else runs.back().hi = std::max(runs.back().hi, hi);
+    }
+    uint32_t m = 0;
+    for (Run &u : runs) { u.slot0 = m; m += u.hi - u.lo + 1; }
+    if (framesDecoded) *framesDecoded = m;
+    if (m == 0) return hipMemsetAsync(dStatus, 0, (size_t)nRanges * sizeof(uint32_t), c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    auto slotOf = [&](uint32_t i) {
+        const Run &u = *(std::upper_bound(runs.begin(), runs.end(), i, [](uint32_t v, const Run &x) { return v < x.lo; }) - 1);
+        return u.slot0 + (i - u.lo);
     };
-    if (in1 > in0) {
-        for (uint32_t k = in0; k < in1; k++) item(k, dDst, t.dOff[first + k] - a, k);
-        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), in1 - in0, dDst, dof.data(), caps.data(), dSt + in0, nullptr)) return e;
-    }
-    if (partFirst || partLast) {
-        uint32_t parts[2], np = 0;
-        if (partFirst) parts[np++] = 0;
-        if (partLast) parts[np++] = m - 1;
-        const uint64_t partBytes = (uint64_t)t.dSize[first + parts[0]] + (np > 1 ? t.dSize[first + parts[1]] : 0u);
-        if (!c->seek.dDec.reserve(partBytes + 64)) return ZSMI_error_memory_allocation;
-        uint8_t *dS = (uint8_t *)c->seek.dDec.p;
-        so.clear(); dof.clear(); ss.clear(); caps.clear();
-        ZsSeekSlices sl = {};
-        uint64_t pos = 0;
-        for (uint32_t j = 0; j < np; j++) {
-            const uint32_t i = first + parts[j];
-            item(parts[j], dS, pos, m + j);
-            const uint64_t lo = std::max(a, t.dOff[i]), hi2 = std::min(b, t.dOff[i + 1]);
-            sl.from[j] = pos + (lo - t.dOff[i]); sl.to[j] = lo - a; sl.len[j] = hi2 - lo;
-            pos += t.dSize[i];
+    // how many ranges overlap each slot; the owned slots and their places in dDst
+    std::vector<uint32_t> frameOf(m), firstSlot(nRanges, 0);
+    std::vector<int32_t> cover((size_t)m + 1, 0);
+    for (const Run &u : runs) for (uint32_t i = u.lo; i <= u.hi; i++) frameOf[u.slot0 + (i - u.lo)] = i;
+    for (const uint32_t r : order) { firstSlot[r] = slotOf(sp[r].first); cover[firstSlot[r]]++; cover[firstSlot[r] + sp[r].count]--; }
+    for (uint32_t s = 1; s < m; s++) cover[s] += cover[s - 1];
+    const uint64_t kScratch = ~0ull;
+    std::vector<uint64_t> place(m, kScratch);                 // owned: the offset in dDst; the others: then the offset in the scratch
+    uint32_t nOwned = 0;
+    for (const uint32_t r : order)
+        for (uint32_t k = 0; k < sp[r].count; k++) {
+            const uint32_t s = firstSlot[r] + k, i = sp[r].first + k;
+            if (cover[s] == 1 && t.dOff[i] >= rg[r].a && t.dOff[i + 1] <= rg[r].b) { place[s] = rg[r].to + (t.dOff[i] - rg[r].a); nOwned++; }
         }
-        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), np, dS, dof.data(), caps.data(), dSt + m, nullptr)) return e;
-        LAUNCH(c, "k_seek_slice", k_seek_slice, dim3(np), dim3(256), 0, (const uint8_t *)dS, dDst, sl);
+    std::vector<uint8_t> owned(m);
+    uint64_t scratchBytes = 0;
+    for (uint32_t s = 0; s < m; s++) {
+        owned[s] = place[s] != kScratch;
+        if (!owned[s]) { place[s] = scratchBytes; scratchBytes += t.dSize[frameOf[s]]; }
     }
-    if (hipMemcpyAsync(dItems, hi, (size_t)m * sizeof(ZsSeekItem), hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipMemsetAsync(dErr, 0xFF, sizeof(*dErr), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((m + 15) / 16), dim3(64), 0, (const ZsSeekItem *)dItems, m, (const uint32_t *)dSt, t.checksum ? 1 : 0, dErr);
-    LAUNCH(c, "k_seek_status", k_seek_status, dim3(1), dim3(1), 0, (const unsigned long long *)dErr, dStatus);
+    // the pieces: short ones first, then the tiles
+    std::vector<ZsSeekPiece> small, tiles;
+    for (const uint32_t r : order)
+        for (uint32_t k = 0; k < sp[r].count; k++) {
+            const uint32_t s = firstSlot[r] + k, i = sp[r].first + k;
+            if (owned[s]) continue;
+            const uint64_t lo = std::max(rg[r].a, t.dOff[i]), hi = std::min(rg[r].b, t.dOff[i + 1]);
+            if (hi <= lo) continue;
+            const uint64_t from = place[s] + (lo - t.dOff[i]), to = rg[r].to + (lo - rg[r].a), len = hi - lo;
+            if (len <= kSeekWavePiece) small.push_back({ from, to, (uint32_t)len, 0 });
+            else for (uint64_t at = 0; at < len; at += kSeekTile) tiles.push_back({ from + at, to + at, (uint32_t)std::min<uint64_t>(kSeekTile, len - at), 0 });
+        }
+    const size_t nPieces = small.size() + tiles.size();
+    if (nPieces > 0x7FFFFFFFull) return ZSMI_error_memory_allocation;
+    // device words: decoder status [m] (the owned frames' call, then the scratch frames'), codes [m]; (8-aligned) the lists: items, pieces, spans
+    const size_t words = (2 * (size_t)m * sizeof(uint32_t) + 7) & ~(size_t)7;
+    const size_t listBytes = (size_t)m * sizeof(ZsSeekItem) + nPieces * sizeof(ZsSeekPiece) + (size_t)nRanges * sizeof(ZsSeekSpan);
+    const int hb = (int)(c->seek.calls++ & 1u);
+    if (c->seek.hBusy[hb]) { if (hipEventSynchronize(c->seek.hEv[hb]) != hipSuccess) return ZSMI_error_GENERIC; c->seek.hBusy[hb] = false; }
+    if (!c->seek.dMeta.reserve(words + listBytes) || !c->seek.hLists[hb].reserve(listBytes)) return ZSMI_error_memory_allocation;
+    if (m > nOwned && !c->seek.dDec.reserve(scratchBytes + 64)) return ZSMI_error_memory_allocation;
+    uint32_t *dSt = (uint32_t *)c->seek.dMeta.p, *dCodes = dSt + m;
+    uint8_t *dLists = (uint8_t *)c->seek.dMeta.p + words, *dS = (uint8_t *)c->seek.dDec.p;
+    const ZsSeekItem *dItems = (const ZsSeekItem *)dLists;
+    const ZsSeekPiece *dPieces = (const ZsSeekPiece *)(dItems + m);
+    const ZsSeekSpan *dSpans = (const ZsSeekSpan *)(dPieces + nPieces);
+    ZsSeekItem *hi = (ZsSeekItem *)c->seek.hLists[hb].p;
+    ZsSeekPiece *hp = (ZsSeekPiece *)(hi + m);
+    ZsSeekSpan *hs = (ZsSeekSpan *)(hp + nPieces);
+    // the two decode calls' items: the owned frames (status words [0, nOwned)), then the scratch frames ([nOwned, m)), each in index order
+    std::vector<uint64_t> so(m), dof(m); std::vector<uint32_t> ss(m), caps(m);
+    uint32_t at[2] = { 0, nOwned };
+    for (uint32_t s = 0; s < m; s++) {
+        const uint32_t i = frameOf[s], j = at[owned[s] ? 0 : 1]++;
+        so[j] = t.cOff[i] - base; ss[j] = t.cSize[i]; caps[j] = t.dSize[i]; dof[j] = place[s];
+        hi[s] = { (uint64_t)(uintptr_t)((owned[s] ? dDst : dS) + place[s]), t.dSize[i], t.hash[i], j, 0 };
+    }
+    if (!small.empty()) memcpy(hp, small.data(), small.size() * sizeof(ZsSeekPiece));
+    if (!tiles.empty()) memcpy(hp + small.size(), tiles.data(), tiles.size() * sizeof(ZsSeekPiece));
+    for (uint32_t r = 0; r < nRanges; r++) hs[r] = { firstSlot[r], sp[r].count };
+    if (hipMemcpyAsync(dLists, hi, listBytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (hipEventRecord(c->seek.hEv[hb], c->stream) != hipSuccess) { (void)hipStreamSynchronize(c->stream); return ZSMI_error_GENERIC; }   // (the buffer is idle after that)
+    c->seek.hBusy[hb] = true;
+    if (nOwned)
+        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), nOwned, dDst, dof.data(), caps.data(), dSt, nullptr)) return e;
+    if (m > nOwned) {
+        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data() + nOwned, ss.data() + nOwned, m - nOwned, dS, dof.data() + nOwned, caps.data() + nOwned, dSt + nOwned, nullptr)) return e;
+        if (nPieces) LAUNCH(c, "k_seek_gather", k_seek_gather, dim3((uint32_t)((small.size() + 3) / 4 + tiles.size())), dim3(256), 0, (const uint8_t *)dS, dDst, dPieces,
+                            (uint32_t)small.size(), (uint32_t)nPieces);
+    }
+    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((m + 15) / 16), dim3(64), 0, dItems, m, (const uint32_t *)dSt, t.checksum ? 1 : 0, dCodes);
+    LAUNCH(c, "k_seek_range_status", k_seek_range_status, dim3((nRanges + 3) / 4), dim3(256), 0, dSpans, nRanges, (const uint32_t *)dCodes, dStatus);
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
+
+// ---- opened archives: the table parsed and checked once, the frames' bytes in device memory (the handle's own copy of a host archive, or the
+// caller's device archive).  Read-only after creation. ----
+struct zsmi_seekable {
+    int device = 0;
+    SeekTable t;
+    const uint8_t *dFrames = nullptr;    // frame i's compressed bytes: dFrames + t.cOff[i]
+    void *dOwned = nullptr;              // a host archive's frames (exactly their bytes + 64: no reserve slack on what may be GiBs)
+    ~zsmi_seekable() { if (dOwned) (void)hipFree(dOwned); }
+};
+extern "C" zsmi_seekable *zsmi_openSeekable(zsmi_ctx *c, const void *archive, size_t size, int *err)
+{
+    int code = 0;
+    zsmi_seekable *sk = new (std::nothrow) zsmi_seekable();
+    do {
+        if (!sk) { code = ZSMI_error_memory_allocation; break; }
+        if ((code = seekParseHost(archive, size, sk->t))) break;
+        if (!c) { code = ZSMI_error_init_missing; break; }
+        sk->device = c->device;
+        const uint64_t bytes = sk->t.cOff[sk->t.n];
+        if (bytes == 0) break;
+        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        if (hipMalloc(&sk->dOwned, bytes + 64) != hipSuccess) { (void)hipGetLastError(); sk->dOwned = nullptr; code = ZSMI_error_memory_allocation; break; }
+        sk->dFrames = (const uint8_t *)sk->dOwned;
+        if (hipMemcpyAsync(sk->dOwned, archive, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) code = ZSMI_error_GENERIC;
+    } while (0);
+    if (code) { delete sk; sk = nullptr; }
+    if (err) *err = code;
+    return sk;
+}
+extern "C" zsmi_seekable *zsmi_openSeekableDevice(zsmi_ctx *c, const void *dArchive, uint64_t size, int *err)
+{
+    int code = 0;
+    zsmi_seekable *sk = nullptr;
+    do {
+        if (!c) { code = ZSMI_error_init_missing; break; }
+        if (!dArchive || size < 9) { code = ZSMI_error_prefix_unknown; break; }
+        sk = new (std::nothrow) zsmi_seekable();
+        if (!sk) { code = ZSMI_error_memory_allocation; break; }
+        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        if ((code = seekParseDevice(c, (const uint8_t *)dArchive, size, sk->t))) break;
+        sk->device = c->device; sk->dFrames = (const uint8_t *)dArchive;
+    } while (0);
+    if (code) { delete sk; sk = nullptr; }
+    if (err) *err = code;
+    return sk;
+}
+extern "C" void zsmi_closeSeekable(zsmi_seekable *sk) { delete sk; }
+extern "C" size_t zsmi_getNumFrames_fromSeekable(const zsmi_seekable *sk) { return sk ? sk->t.n : 0; }
+extern "C" unsigned long long zsmi_getContentSize_fromSeekable(const zsmi_seekable *sk) { return sk ? sk->t.dOff[sk->t.n] : 0; }
+extern "C" size_t zsmi_sizeofSeekable(const zsmi_seekable *sk) { return sk && sk->dOwned ? sk->t.cOff[sk->t.n] : 0; }
+
+// the host checks of a batch read, in the header's order; rg[r]: the range clipped at the content's end (its place in dDst is the caller's to set)
+static int seekCheckRanges(const zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *offsets, const uint64_t *lengths, uint32_t nRanges, const void *a1, const void *a2,
+                           std::vector<SeekRange> &rg)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (!sk || (nRanges && (!offsets || !lengths || !a1 || !a2))) return ZSMI_error_GENERIC;
+    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
+    const uint64_t content = sk->t.dOff[sk->t.n];
+    rg.resize(nRanges);
+    for (uint32_t r = 0; r < nRanges; r++) {
+        if (offsets[r] > content) return ZSMI_error_parameter_outOfBound;
+        rg[r] = { offsets[r], offsets[r] + std::min(lengths[r], content - offsets[r]), 0 };
+    }
+    return 0;
+}
+extern "C" int zsmi_seekableReadRangesDevice(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *offsets, const uint64_t *lengths, uint32_t nRanges,
+                                             void *dDst, const uint64_t *dstOffsets, uint64_t *written, uint32_t *dStatus, uint32_t *framesDecoded)
+{
+    std::vector<SeekRange> rg;
+    if (const int e = seekCheckRanges(c, sk, offsets, lengths, nRanges, dstOffsets, written, rg)) return e;
+    if (nRanges && !dStatus) return ZSMI_error_GENERIC;
+    uint64_t bytes = 0;
+    for (uint32_t r = 0; r < nRanges; r++) { rg[r].to = dstOffsets[r]; bytes += rg[r].b - rg[r].a; }
+    if (bytes && !dDst) return ZSMI_error_GENERIC;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    for (uint32_t r = 0; r < nRanges; r++) written[r] = rg[r].b - rg[r].a;
+    return seekReadRanges(c, sk->t, sk->dFrames, 0, rg.data(), nRanges, (uint8_t *)dDst, dStatus, framesDecoded);
+}
+extern "C" int zsmi_seekableReadRangesHost(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *offsets, const uint64_t *lengths, uint32_t nRanges,
+                                           void *dst, size_t dstCapacity, uint64_t *written, uint32_t *statuses)
+{
+    std::vector<SeekRange> rg;
+    if (const int e = seekCheckRanges(c, sk, offsets, lengths, nRanges, written, statuses, rg)) return e;
+    uint64_t bytes = 0;
+    for (uint32_t r = 0; r < nRanges; r++) { rg[r].to = bytes; bytes += rg[r].b - rg[r].a; }
+    if (bytes > dstCapacity) return ZSMI_error_dstSize_tooSmall;
+    if (bytes && !dst) return ZSMI_error_GENERIC;
+    for (uint32_t r = 0; r < nRanges; r++) written[r] = rg[r].b - rg[r].a;
+    if (nRanges == 0) return 0;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (!c->sDst.reserve(bytes + 64) || !c->sSizes.reserve((size_t)nRanges * sizeof(uint32_t))) return ZSMI_error_memory_allocation;
+    int rc = seekReadRanges(c, sk->t, sk->dFrames, 0, rg.data(), nRanges, (uint8_t *)c->sDst.p, (uint32_t *)c->sSizes.p, nullptr);
+    if (!rc && hipMemcpyAsync(statuses, c->sSizes.p, (size_t)nRanges * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZSMI_error_GENERIC;
+    if (!rc && bytes && hipMemcpyAsync(dst, c->sDst.p, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZSMI_error_GENERIC;
+    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ZSMI_error_GENERIC;
+    return rc;
+}
+
+// ---- the single-range calls: the one-range case of seekReadRanges ----
 extern "C" int zsmi_decompressSeekableDevice(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, uint64_t offset, uint64_t length,
                                              void *dDst, uint64_t *written, uint32_t *dStatus)
 {
@@ -317,26 +535,14 @@ extern "C" int zsmi_decompressSeekableDevice(zsmi_ctx *c, const void *dSrc, uint
     if (!dSrc || srcSize < 9) return ZSMI_error_prefix_unknown;
     if (!dStatus || !written) return ZSMI_error_GENERIC;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    // the archive's tail, once: it holds the whole table up to 256 KiB (16384 entries with checksums: 1 GiB in 64 KiB frames); a larger
-    // table is read again at its size
-    std::vector<uint8_t> tail(std::min<uint64_t>(srcSize, 256u << 10));
-    const uint8_t *src = (const uint8_t *)dSrc;
-    if (hipMemcpyAsync(tail.data(), src + srcSize - tail.size(), tail.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    SeekTable t;
-    if (const int e = seekFooter(tail.data() + tail.size() - 9, srcSize, t)) return e;
-    if (t.tableSize > tail.size()) {
-        tail.resize(t.tableSize);
-        if (hipMemcpyAsync(tail.data(), src + srcSize - t.tableSize, t.tableSize, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    }
-    if (const int e = seekEntries(tail.data() + tail.size() - t.tableSize, srcSize, t)) return e;
+    SeekTable t;                                                        // (a table for this call alone: an opened archive keeps it)
+    if (const int e = seekParseDevice(c, (const uint8_t *)dSrc, srcSize, t)) return e;
     const uint64_t content = t.dOff[t.n];
     if (offset > content) return ZSMI_error_parameter_outOfBound;
-    const uint64_t b = offset + std::min(length, content - offset);
-    *written = b - offset;
-    if (b > offset && !dDst) return ZSMI_error_GENERIC;
-    return seekReadQueue(c, t, src, 0, offset, b, (uint8_t *)dDst, dStatus);
+    const SeekRange rg = { offset, offset + std::min(length, content - offset), 0 };
+    *written = rg.b - rg.a;
+    if (rg.b > rg.a && !dDst) return ZSMI_error_GENERIC;
+    return seekReadRanges(c, t, (const uint8_t *)dSrc, 0, &rg, 1, (uint8_t *)dDst, dStatus, nullptr);
 }
 extern "C" size_t zsmi_decompressSeekable(void *dst, size_t dstCapacity, const void *src, size_t srcSize, unsigned long long offset)
 {
@@ -344,24 +550,23 @@ extern "C" size_t zsmi_decompressSeekable(void *dst, size_t dstCapacity, const v
     if (const int e = seekParseHost(src, srcSize, t)) return ZSMI_ERR(e);
     const uint64_t content = t.dOff[t.n];
     if (offset > content) return ZSMI_ERR(ZSMI_error_parameter_outOfBound);
-    const uint64_t a = offset, b = a + std::min<uint64_t>(dstCapacity, content - a);
-    if (a == b) return 0;
+    const SeekRange rg = { offset, offset + std::min<uint64_t>(dstCapacity, content - offset), 0 };
+    if (rg.a == rg.b) return 0;
     uint32_t first, last;
-    seekSpan(t, a, b, first, last);
+    seekSpan(t, rg.a, rg.b, first, last);
     const uint64_t base = t.cOff[first], span = t.cOff[last + 1] - base;       // only the overlapping frames' bytes go to the device
     Borrowed bw; zsmi_ctx *c = bw.c;
     if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
-    if (!c->sSrc.reserve(span + 64) || !c->sDst.reserve(b - a + 64) || !c->sSizes.reserve(sizeof(uint32_t))) return ZSMI_ERR(ZSMI_error_memory_allocation);
-    // (a borrowed context is idle: its last user waited for its stream)
+    if (!c->sSrc.reserve(span + 64) || !c->sDst.reserve(rg.b - rg.a + 64) || !c->sSizes.reserve(sizeof(uint32_t))) return ZSMI_ERR(ZSMI_error_memory_allocation);
     if (hipMemcpyAsync(c->sSrc.p, (const uint8_t *)src + base, span, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
-    if (const int rc = seekReadQueue(c, t, (const uint8_t *)c->sSrc.p, base, a, b, (uint8_t *)c->sDst.p, (uint32_t *)c->sSizes.p)) {
+    if (const int rc = seekReadRanges(c, t, (const uint8_t *)c->sSrc.p, base, &rg, 1, (uint8_t *)c->sDst.p, (uint32_t *)c->sSizes.p, nullptr)) {
         (void)hipStreamSynchronize(c->stream);
         return ZSMI_ERR(rc);
     }
     uint32_t status = 0;
     if (hipMemcpyAsync(&status, c->sSizes.p, sizeof status, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
     if (status) return ZSMI_ERR(status);
-    if (hipMemcpyAsync(dst, c->sDst.p, b - a, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
-    return b - a;
+    if (hipMemcpyAsync(dst, c->sDst.p, rg.b - rg.a, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    return rg.b - rg.a;
 }

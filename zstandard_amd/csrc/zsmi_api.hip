@@ -123,6 +123,7 @@ extern "C" zsmi_ctx *zsmi_createCtx(int device, void *hipStream)
                   hipFuncGetAttributes(&fa, (const void *)s.walk[k].fn) == hipSuccess && fa.sharedSizeBytes == 0;
         }
     for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->hItemsEv[i], hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->seek.hEv[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); zsmi_freeCtx(c); return nullptr; }
     if (const char *e = getenv("ZSMI_BLOCKS_IN_FLIGHT")) { long v = atol(e); if (v >= 64) c->maxBlocksInFlight = (uint32_t)v; }
     if (const char *e = getenv("ZSMI_DEC_FAST")) c->decodeFast = atoi(e) != 0;
@@ -141,6 +142,7 @@ extern "C" void zsmi_freeCtx(zsmi_ctx *c)
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
     for (int i = 0; i < 2; i++) if (c->hItemsEv[i]) (void)hipEventDestroy(c->hItemsEv[i]);
+    for (int i = 0; i < 2; i++) if (c->seek.hEv[i]) (void)hipEventDestroy(c->seek.hEv[i]);
     for (auto &tl : c->launches) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->eventPool) (void)hipEventDestroy(e);
     if (c->ownStream) (void)hipStreamDestroy(c->stream);

@@ -95,9 +95,10 @@ struct zsmi_ctx {
     // staging for host-buffer calls
     DevBuf sSrc, sDst, sSizes, sDict, sPack, sPackOff;
     PinBuf hPack;
-    // seekable archives (seekable.hip): compressed frames at bound spacing before they are packed, per-frame words (sizes, hashes, offsets,
-    // the error word), a partial first / last frame's decoded bytes, the verify list
-    struct SeekScratch { DevBuf dStage, dMeta, dDec; PinBuf hItems; } seek;
+    // seekable archives (seekable.hip): compressed frames at bound spacing before they are packed, per-frame words (sizes, hashes, offsets, the
+    // error word; a read's status words, codes and lists), the decoded bytes of the frames a read does not decode in place, and a read's lists
+    // on the host: two pinned buffers taken in turn, each guarded by an event (created with the context), as hItems2
+    struct SeekScratch { DevBuf dStage, dMeta, dDec; PinBuf hLists[2]; hipEvent_t hEv[2] = { nullptr, nullptr }; bool hBusy[2] = { false, false }; uint32_t calls = 0; } seek;
     // dictionary training (dict_train.hip): the samples back to back, sort keys, per-position hash / links (d = 6, 8), base and per-candidate
     // frequency tables, candidate contents and list, compressed sizes and frames of the scoring / statistics calls, stats + header scratch, the result
     struct TrainScratch {

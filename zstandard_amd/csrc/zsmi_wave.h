@@ -34,6 +34,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v)
     v = max(v, ZS_DPP(0, v, 0x143, 0xC, false));
     return wave_last(v);
 }
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) { return ~wave_max(~v); }     // (the zero fill of the row shifts is max's identity, not min's)
 
 // ordering point between LDS accesses of different lanes of ONE wavefront: LDS instructions of a wave execute in issue
 // order, so only the compiler has to be kept from moving them across
