@@ -662,6 +662,14 @@ def test_decode_libzstd_frames_of_many_blocks_with_repeated_tables(codec):
     assert O.decompress(frames[1], len(chunks[1])) == chunks[1] and O.decompress(frames[6], len(chunks[6])) == chunks[6]
 
 
+@pytest.mark.parametrize("chunks,size,level", [(2, 131072, 1), (2, 131072, 3), (3, 65536, 3)])
+def test_walk_output_read_back_by_name(chunks, size, level):
+    """tools/walk_check.py (its own process: the library with the debug hooks, the entropy kernels not launched): the sequence records and
+    range headers of every block slot, read back through zsmi_dbg_copyScratch by the buffers' names, are oracle E's parse.  Two chunks of
+    128 KiB are four block slots in two LZ units (the slot stride, a unit's second block); three of 64 KiB are one-block units."""
+    B.run_child(os.path.join(ROOT, "tools", "walk_check.py"), str(chunks), str(size), str(level), timeout=300, marker="different parse: 0")
+
+
 def test_intended_shapes_stay_on_the_decode_fast_path():
     """tools/fastpath_check.py (its own process: the library with the debug hooks): every shape the fast path is meant to take is decoded
     THERE - a silent fall-back to the general kernel decodes correctly, 4 x slower, and no other test would notice."""

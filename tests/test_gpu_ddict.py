@@ -76,7 +76,7 @@ for dname, dic in sorted(DD.dictionaries().items()):
     bc.decompress_device(src.data_ptr(), so, ss, dst.data_ptr(), do, np.array(caps, dtype=np.uint32), dsz.data_ptr(), ddict=dd)
     bc.sync()
     buf = np.zeros(n * WORDS, dtype=np.uint32)
-    assert Z.zsmi_dbg_copyScratch(bc.ctx, 10, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
+    assert Z.zsmi_dbg_copyScratch(bc.ctx, b"fastDesc", buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
     desc = buf.reshape(-1, WORDS)
     host = dst.cpu().numpy(); sz = dsz.cpu().numpy().view(np.uint32)
     got = [(int(s), host[int(o):int(o) + (int(s) if s < B.ERR else 0)].tobytes()) for o, s in zip(do, sz)]

@@ -23,11 +23,9 @@ off = np.arange(n, dtype=np.uint64) * cs; sz = np.full(n, cs, dtype=np.uint32)
 bound = int(Z.zsmi_compressBound(cs)); doff = np.arange(n, dtype=np.uint64) * bound
 ddst = torch.empty(n * bound, dtype=torch.uint8, device="cuda"); dsz = torch.empty(n, dtype=torch.int32, device="cuda")
 bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), 3); bc.sync()
-buf = np.zeros(n * 32, dtype=np.uint8)
-rc = Z.zsmi_dbg_copyScratch(bc.ctx, 3, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(len(buf))); assert rc == 0, rc
-m = buf.view(np.uint32).reshape(n, 8)
-fails = m[:, 6] & 0xFFFF; rounds = m[:, 6] >> 16      # (fails: not counted by the kernel - lane 0's ballot; rounds of repair are)
-K = m[:, 7] & 0xFF; Sb = (m[:, 7] >> 8) & 0xFF; ns = m[:, 7] >> 16
+m = _lib.copy_scratch(bc.ctx, "metas", n).view(np.uint32).reshape(n, -1)      # a ZsBlockMeta a block: the counts are its last two words (pad)
+fails = m[:, -2] & 0xFFFF; rounds = m[:, -2] >> 16    # (fails: not counted by the kernel - lane 0's ballot; rounds of repair are)
+K = m[:, -1] & 0xFF; Sb = (m[:, -1] >> 8) & 0xFF; ns = m[:, -1] >> 16
 print(cls, "blocks", n, "K", np.bincount(K), "Sb mean", Sb.mean(), "nseq mean", ns.mean())
 print("repair rounds histogram:", np.bincount(rounds, minlength=22).tolist())
 print("nseq of blocks with >= 8 rounds:", np.sort(ns[rounds >= 8])[::max(1, int((rounds >= 8).sum()) // 12)].tolist())

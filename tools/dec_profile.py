@@ -20,11 +20,10 @@ frames = np.concatenate([arena[int(do[i]):int(do[i]) + int(dsz[i])] for i in ran
 fo = B.layout(dsz)
 out, oo, osz = bc.decompress_host(frames, fo, dsz, sizes)
 assert (osz == cs).all() and (out[:n * cs] == host).all()
-stride = (1 << 17) + 64
-buf = np.zeros(pool * stride, dtype=np.uint8)             # the pool's literal buffers: a wavefront's counts sit in the 64 spare bytes behind its own
-rc = Z.zsmi_dbg_copyScratch(bc.ctx, 5, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(pool * stride)); assert rc == 0, rc
-prof = np.stack([buf[i * stride + (1 << 17): i * stride + (1 << 17) + 64].view(np.uint64) for i in range(pool)])
 names = ["literals", "seq tables", "seq decode", "seq execute", "checksum", "whole item", "  huf table", "  huf symbol loops"]
+# the pool's literal buffers: a wavefront's counts, a word a name, are the last bytes of its own (zs_poollit_lend_dec_profile, csrc/zsmi_scratch.h)
+bufs = _lib.copy_scratch(bc.ctx, "poolLit", pool).reshape(pool, -1)
+prof = np.ascontiguousarray(bufs[:, -8 * len(names):]).view(np.uint64)
 m = prof.mean(axis=0)
 for k, nm in enumerate(names):
     print(f"{nm:12s} {m[k]:12.0f} ticks  {100 * m[k] / m[5]:5.1f} %")

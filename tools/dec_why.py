@@ -27,7 +27,7 @@ for name in (sys.argv[1:] or list(classes)):
     d_out = torch.empty(n * cs, dtype=torch.uint8, device="cuda"); d_osz = torch.zeros(n, dtype=torch.int32, device="cuda")
     bc.decompress_device(d_dst.data_ptr(), doffs, csz, d_out.data_ptr(), offs, sizes, d_osz.data_ptr()); torch.cuda.synchronize()
     buf = np.zeros(n * DESC_WORDS, dtype=np.uint32)
-    rc = Z.zsmi_dbg_copyScratch(bc.ctx, 10, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
+    rc = Z.zsmi_dbg_copyScratch(bc.ctx, b"fastDesc", buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
     d = buf.reshape(n, DESC_WORDS)
     fast, why = d[:, FAST_AT], d[:, WHY_AT]
     left = np.nonzero(fast == 0)[0]

@@ -56,7 +56,7 @@ def main():
             ok = B.decode_many(bc, frames, [len(c) for c in chunks], min_cap=0) == [(len(c), c) for c in chunks]
         n = len(chunks)
         buf = np.zeros(n * DESC_WORDS, dtype=np.uint32)
-        rc = Z.zsmi_dbg_copyScratch(bc.ctx, 10, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
+        rc = Z.zsmi_dbg_copyScratch(bc.ctx, b"fastDesc", buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
         res[label] = [int((buf.reshape(-1, DESC_WORDS)[:n, FAST_AT] == 1).sum()) if ok else -1, n]
 
     run("own 32 KiB", [text[i * 32768:(i + 1) * 32768] for i in range(64)])

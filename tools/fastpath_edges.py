@@ -23,7 +23,7 @@ def main():
     for placement, caps in (("a", [e.cap for e in cat]), ("b", [1 << 20] * len(cat))):
         out, oo, osz = bc.decompress_host(*B.batch([e.frame for e in cat]), np.array(caps, dtype=np.uint32))
         buf = np.zeros(len(cat) * DESC_WORDS, dtype=np.uint32)
-        rc = Z.zsmi_dbg_copyScratch(bc.ctx, 10, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
+        rc = Z.zsmi_dbg_copyScratch(bc.ctx, b"fastDesc", buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
         fast = buf.reshape(-1, DESC_WORDS)[:len(cat), FAST_AT]
         r = {}
         for i, e in enumerate(cat):

@@ -32,10 +32,11 @@ def main():
             n0 = min(len(data), 131072)          # first LZ unit
             blk = data[:n0]
             dist_e = np.zeros(n0, dtype=np.uint32); L.zso_debugCandidates(dist_e.ctypes.data_as(ctypes.c_void_p), blk, n0, 3)
-            dist_lo = np.zeros(131072, dtype=np.uint16); Z.zsmi_dbg_copyScratch(bc.ctx, 0, dist_lo.ctypes.data_as(ctypes.c_void_p), 131072 * 2)
+            nblk = (n0 + 65535) // 65536
+            dist_lo = _lib.copy_scratch(bc.ctx, "dist", nblk).view(np.uint16)   # the unit's block slots, sized by the library (csrc/zsmi_scratch.h)
             dist_g = dist_lo[:n0].astype(np.uint32)
             if n0 > 65536:
-                hi = np.zeros(16384, dtype=np.uint8); Z.zsmi_dbg_copyScratch(bc.ctx, 4, hi.ctypes.data_as(ctypes.c_void_p), 16384)
+                hi = _lib.copy_scratch(bc.ctx, "distHi", nblk)
                 dist_g |= np.unpackbits(hi, bitorder="little")[:n0].astype(np.uint32) << 16
                 dist_g[dist_lo[:n0] == 0] = 0
             if n0 <= 65536: dist_g = dist_lo[:n0].astype(np.uint32)
@@ -43,12 +44,10 @@ def main():
             bad = np.nonzero(dist_e[:hashable] != dist_g[:hashable])[0]
             print(f"   dist mismatches (unit 0): {len(bad)}", bad[:8], dist_e[bad[:8]], dist_g[bad[:8]])
             # the parse: sequences per block as the stitch kernel leaves them (64 output ranges x 256 records) against oracle E's
-            nblk = (n0 + 65535) // 65536
             seq_e = np.zeros(3 * 65536 * nblk, dtype=np.uint32); ns_e = np.zeros(2, dtype=np.uint32)
             L.zso_debugWalk(seq_e.ctypes.data_as(ctypes.c_void_p), ns_e.ctypes.data_as(ctypes.c_void_p), blk, n0, 3)
-            hdr_g = np.zeros(nblk * 64 * 4, dtype=np.uint32); Z.zsmi_dbg_copyScratch(bc.ctx, 2, hdr_g.ctypes.data_as(ctypes.c_void_p), hdr_g.nbytes)
-            seq_g = np.zeros(nblk * 64 * 256 * 2, dtype=np.uint32); Z.zsmi_dbg_copyScratch(bc.ctx, 1, seq_g.ctypes.data_as(ctypes.c_void_p), seq_g.nbytes)
-            hdr_g = hdr_g.reshape(nblk, 64, 4); seq_g = seq_g.reshape(nblk, 64, 256, 2); o = 0
+            hdr_g = _lib.copy_scratch(bc.ctx, "hdrs", nblk).view(np.uint32).reshape(nblk, 64, 4)
+            seq_g = _lib.copy_scratch(bc.ctx, "seqs", nblk).view(np.uint32).reshape(nblk, 64, -1, 2); o = 0
             for b in range(nblk):
                 want = seq_e[3 * o:3 * (o + int(ns_e[b]))].reshape(-1, 3); o += int(ns_e[b])
                 got = []

@@ -16,11 +16,13 @@ frames = np.concatenate([arena[int(do[i]):int(do[i]) + int(dsz[i])] for i in ran
 fo = B.layout(dsz)
 out, oo, osz = bc.decompress_host(frames, fo, dsz, sizes)
 assert (osz == cs).all()
-buf = np.zeros(n * 4096, dtype=np.uint8)
-rc = Z.zsmi_dbg_copyScratch(bc.ctx, 9, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n * 4096)); assert rc == 0, rc
-prof = np.stack([buf[i * 4096 + 2048: i * 4096 + 2048 + 104].view(np.uint64) for i in range(n)]).astype(np.float64)
 names = ["headers up to the Huffman description", "huf: stage the description", "huf: weight counts (readNCount)", "huf: weight FSE table", "huf: weights (two FSE states)",
          "huf: ranks, start cells", "huf: table fill", "seq: between tables", "seq: stage a description", "seq: parse (readNCount)", "seq: build", "seq: emit 16-bit cells", "whole wavefront"]
+# the items' block-0 Huffman table slots (one-block frames: slot = item); the stamps, a word a name, start at the middle of a slot
+# (zs_huftab_lend_prep_profile, csrc/zsmi_scratch.h)
+tabs = _lib.copy_scratch(bc.ctx, "hufTabs", n).reshape(n, -1)
+half = tabs.shape[1] // 2
+prof = np.ascontiguousarray(tabs[:, half:half + 8 * len(names)]).view(np.uint64).astype(np.float64)
 m = prof.mean(axis=0)
 for k, nm in enumerate(names):
     print(f"{nm:40s} {m[k]:10.0f} ticks  {100 * m[k] / m[12]:5.1f} %")

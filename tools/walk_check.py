@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Development aid (GPU box): the walk kernel's output (sequences per block, read back from the scratch) against oracle E's parse, for a batch of
 N chunks of the Zipf log -- the entropy kernels are NOT launched (ZSMI_STOP_AFTER_WALK, debug-hooks library), so a wrong parse cannot take
-anything else down.  usage: walk_check.py [chunks] [chunk_size] [level]"""
+anything else down.  The records and range headers are read back by name (zsmi_dbg_copyScratch "seqs", "hdrs"), every block slot of the batch.
+usage: walk_check.py [chunks] [chunk_size] [level] [calls]; exit 0: every block checked has oracle E's parse.  Run by
+tests/test_gpu_codec.py::test_walk_output_read_back_by_name."""
 import os, sys, ctypes
 os.environ["ZSMI_DEBUG_LIB"] = "1"; os.environ["ZSMI_STOP_AFTER_WALK"] = "1"
 import numpy as np
@@ -14,16 +16,18 @@ cs = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
 level = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 reps = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 data = D.zipf_log(n * cs)
-bc = BatchCodec(0); Z = _lib.lib(); L = O.lib()
+if _lib.built_fingerprint() != _lib.source_fingerprint():
+    _lib.build()                                         # (a stale debug build would check yesterday's kernels)
+bc = BatchCodec(0); L = O.lib()
 L.zso_debugWalk.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int]
 offs = np.arange(n, dtype=np.uint64) * cs; sizes = np.full(n, cs, dtype=np.uint32)
 for _ in range(reps):
     bc.compress_host(data, offs, sizes, level)           # (the frames are not written: sizes come back as they were)
 bpc = (cs + 65535) // 65536                              # blocks per chunk
 nb = n * bpc
-hdr = np.zeros(nb * 64 * 4, dtype=np.uint32); rc = Z.zsmi_dbg_copyScratch(bc.ctx, 2, hdr.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(hdr.nbytes)); assert rc == 0, rc
-seq = np.zeros(nb * 64 * 256 * 2, dtype=np.uint32); rc = Z.zsmi_dbg_copyScratch(bc.ctx, 1, seq.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(seq.nbytes)); assert rc == 0, rc
-hdr = hdr.reshape(nb, 64, 4); seq = seq.reshape(nb, 64, 256, 2)
+# a block's slot (sized by the library: csrc/zsmi_scratch.h): 64 output ranges - a header of 4 words each, and each range's record slots of 2 words
+hdr = _lib.copy_scratch(bc.ctx, "hdrs", nb).view(np.uint32).reshape(nb, 64, 4)
+seq = _lib.copy_scratch(bc.ctx, "seqs", nb).view(np.uint32).reshape(nb, 64, -1, 2)
 bad = 0
 step = max(1, n // 64)
 for ci in list(range(0, n, step)) + [n - 1]:
@@ -39,7 +43,7 @@ for ci in list(range(0, n, step)) + [n - 1]:
             got = []
             for g in range(64):
                 nsq, first = int(hdr[b, g, 0]), int(hdr[b, g, 3])
-                if nsq > 256 or first != 0: got = None; break
+                if nsq > seq.shape[2] or first != 0: got = None; break
                 x, y = seq[b, g, :nsq, 0], seq[b, g, :nsq, 1]
                 got.append(np.stack([y >> 16, (x >> 11) & 0x1FFFF, (y & 0xFFFF) | (((x >> 28) & 1) << 16)], axis=1))
             got = np.concatenate(got) if got is not None else None

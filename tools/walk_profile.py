@@ -18,12 +18,12 @@ off = np.arange(n, dtype=np.uint64) * cs; sz = np.full(n, cs, dtype=np.uint32)
 bound = int(Z.zsmi_compressBound(cs)); doff = np.arange(n, dtype=np.uint64) * bound
 ddst = torch.empty(n * bound, dtype=torch.uint8, device="cuda"); dsz = torch.empty(n, dtype=torch.int32, device="cuda")
 bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), 3); bc.sync()
-base = n * 256 * 16                                         # behind the blocks' range results
-buf = np.zeros(base + n * waves * 80, dtype=np.uint8)
-rc = Z.zsmi_dbg_copyScratch(bc.ctx, 8, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(len(buf))); assert rc == 0, rc
-prof = buf[base:].view(np.uint64).reshape(n, waves, 10).astype(np.float64)
-m = prof.mean(axis=(0, 1))
 names = ["staging", "grab / loop head / barrier wait", "recent offsets + window", "candidate picks + distance loads", "scoring", "whole length", "record + bookkeeping", "-", "steps per wavefront", "active lanes per step"]
+# the stamps, a word a name for every wavefront of every unit, lie behind ALL blocks' range results (zs_res_lend_walk_profile, csrc/zsmi_scratch.h)
+base = n * _lib.scratch_layout("res")[0]
+buf = _lib.copy_scratch(bc.ctx, "res", n, extra=n * waves * 8 * len(names))
+prof = buf[base:].view(np.uint64).reshape(n, waves, len(names)).astype(np.float64)
+m = prof.mean(axis=(0, 1))
 tot = m[:8].sum()
 for k in range(8):
     print(f"{names[k]:36s} {m[k]:10.0f} ticks {100 * m[k] / tot:5.1f} %")

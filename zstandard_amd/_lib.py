@@ -151,9 +151,30 @@ def lib():
     L.zsmi_finalizeDictionary.restype = sz; L.zsmi_finalizeDictionary.argtypes = [vp, sz, vp, sz, vp, psz, ctypes.c_uint, i32, ctypes.c_uint]
     L.zsmi_getDictID.restype = ctypes.c_uint; L.zsmi_getDictID.argtypes = [vp, sz]
     if DEBUG or hasattr(L, "zsmi_dbg_copyScratch"):            # (a variant build named by ZSMI_LIB_FILE may carry the hooks too)
-        L.zsmi_dbg_copyScratch.restype = i32; L.zsmi_dbg_copyScratch.argtypes = [vp, i32, vp, sz]
+        L.zsmi_dbg_copyScratch.restype = i32; L.zsmi_dbg_copyScratch.argtypes = [vp, ctypes.c_char_p, vp, sz]
+        L.zsmi_dbg_scratchLayout.restype = i32; L.zsmi_dbg_scratchLayout.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]
     _lib = L
     return L
+
+
+def scratch_layout(name):
+    """debug-hook library: (bytes a slot, fixed bytes behind the slots) of the scratch buffer `name` - the names and the numbers are
+    csrc/zsmi_scratch.h's; KeyError for a name that is no buffer's"""
+    out = (ctypes.c_uint64 * 2)()
+    if lib().zsmi_dbg_scratchLayout(name.encode(), out) != 0:
+        raise KeyError(name)
+    return int(out[0]), int(out[1])
+
+
+def copy_scratch(ctx, name, slots, extra=0):
+    """debug-hook library: the first `slots` slots of the scratch buffer `name` (+ `extra` bytes behind them) as the context's last call left
+    them: a uint8 array of slots * (bytes a slot) + extra"""
+    import numpy as np
+    buf = np.zeros(slots * scratch_layout(name)[0] + extra, dtype=np.uint8)
+    rc = lib().zsmi_dbg_copyScratch(ctx, name.encode(), buf.ctypes.data_as(ctypes.c_void_p), buf.nbytes)
+    if rc != 0:
+        raise RuntimeError("zsmi_dbg_copyScratch(%s): %d" % (name, rc))
+    return buf
 
 
 EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decompress", "zsmi_getDecompressedSize",

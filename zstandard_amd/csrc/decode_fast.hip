@@ -24,13 +24,18 @@
 // Dictionaries: k_dict_load, at the end of this file, is how the HOST learns what a dictionary holds - it runs decode_kernels.hip's
 // loadDictEntropy (the only place where a dictionary's entropy section is walked and checked; the host parses nothing) and leaves a
 // ZsDictRecord, and for a digested decode dictionary the ZsDDictImage the DD forms of the kernels above read.
+//
+// Scratch: what a slot of each buffer holds, its stride and the accessor the kernels reach it through are stated in zsmi_scratch.h - slot =
+// zs_dec_slot(block, cap, item); zs_slot_desc, zs_slot_huf_table, zs_slot_seq_tables, zs_slot_literals (the call's litStride), zs_slot_seq_out
+// (the call's seqCap); the class lists k_dec_prep fills for the sequences kernels are DecLists'.  The constants that size a slot
+// (ZS_FAST_HUFLOG, ZS_FAST_MAXSEQ, ZS_FAST_HUFTAB_BYTES, ZS_FAST_SEQTAB_BYTES) and ZsFastSeq live there too; the descriptor, ZsFastDesc, is
+// this file's.
 #include "zsmi_device.h"
+#include "zsmi_scratch.h"         // the fast path's block slots: descriptors (ZsFastDesc), tables, literal scratch, sequences (ZsFastSeq); the class lists (DecLists)
 #include "zsmi_wave.h"
 #include "zsmi_fse.h"             // LL_base, LL_bits, ML_base, ML_bits
 #include "decode_kernels.hip"
 
-#define ZS_FAST_HUFLOG   11u                      // Huffman tables the fast kernel holds: 2^11 entries per item
-#define ZS_FAST_MAXSEQ   16384u                   // sequences per block the fast path buffers (8 bytes each)
 #define ZS_FAST_MAXBLOCKS 16u                      // block slots per item a call may reserve (frames of up to 1 MiB; 1 or 2 unless the call is mostly large frames)
 #ifndef ZS_FAST_HUFWIN
 #define ZS_FAST_HUFWIN   128u                     // bytes of each Huffman stream staged in LDS at a time
@@ -64,8 +69,6 @@ struct ZsFastDesc {                               // per item, global memory, wr
     uint32_t dict;                                // block 0's, calls with a dictionary only: which one the frame is decoded with (zs_dict_index: a member's index in the
                                                   // call's table, ZS_DICT_UNNAMED, or ZS_DICT_NONE) - the kernels behind k_dec_prep take the item's image through it
 };
-#define ZS_FAST_HUFTAB_BYTES (2u << ZS_FAST_HUFLOG)                       // uint16 entries
-#define ZS_FAST_SEQTAB_BYTES ((512u + 256u + 512u) * 2u)                  // LL, OF, ML cells, 2 bytes each
 // A digested decode dictionary's device image (zsmi_createDDict; filled by k_dict_load, read-only afterwards): what a frame decoded with
 // the dictionary starts from (ZSTD_decompress_insertDictionary :2452-2475) - the content in front of the frame, the recent offsets, and for a
 // formatted dictionary its entropy tables in exactly the form the fast kernels read: the Huffman table as k_dec_prep leaves one in a slot
@@ -84,10 +87,7 @@ struct ZsDDictImage {
 };
 #define ZS_DD_SLOT 0xFFFFFFFFu                    // k_dec_prep's "block + 1 of the slot that holds the current table": the dictionary's image
 
-// what the sequences kernel leaves per sequence, 8 bytes: where its extra bits start in the bitstream (bit position, 20 bits)
-// and its three codes (LL 6 bits at 20, ML 6 bits at 26, OF 5 bits at 32).  The execute kernel turns that into lengths and
-// offsets, 64 sequences at a time on 64 lanes; only the FSE state chain stays serial.
-typedef uint64_t ZsFastSeq;
+// a ZsFastSeq (zsmi_scratch.h) from its parts
 __device__ __forceinline__ ZsFastSeq zs_fastseq(uint32_t bitPos, uint32_t symLL, uint32_t symML, uint32_t symOF)
 { return (uint64_t)(bitPos | (symLL << 20) | (symML << 26)) | ((uint64_t)symOF << 32); }
 
@@ -143,7 +143,7 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
         const uint32_t tail = fh.checksumFlag ? 4u : 0u;            // the checksum behind the last block
         if (srcSize < fh.headerSize + 3 + tail) { ZS_PREP_WHY(__LINE__); break; }
         if (fh.contentSize != ~0ull && fh.contentSize > 0xFFFFFFFFull) { ZS_PREP_WHY(__LINE__); break; }
-        {   ZsFastDesc *dp = descs + item;                          // what the frame header says: in the descriptor of block 0
+        {   ZsFastDesc *dp = zs_slot_desc(descs, item);                         // what the frame header says: in the descriptor of block 0
             DSET(why, 0u); DSET(hasContentSize, fh.contentSize != ~0ull); DSET(contentSize, (uint32_t)fh.contentSize); DSET(hasChecksum, fh.checksumFlag); DSET(checksum, fh.checksumFlag ? rd32(src + srcSize - 4) : 0u);
             if (DD) DSET(dict, dictAt);
         }
@@ -164,8 +164,8 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
         #pragma unroll 1
         for (uint32_t blk = 0; blk < maxBlocks && !fail; blk++) {
             fail = true;
-            const size_t slot = (size_t)blk * cap + item;
-            ZsFastDesc *dp = descs + slot;
+            const size_t slot = zs_dec_slot(blk, cap, item);
+            ZsFastDesc *dp = zs_slot_desc(descs, slot);
             // ---- a block (:646-659): compressed; the last one fills the rest of the item ----
             if ((uint64_t)b0 + 3 + tail > srcSize) { ZS_PREP_WHY(__LINE__); break; }
             const ZsBlockHeader bh = zs_read_block_header(src + b0);
@@ -201,7 +201,7 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
                 if (type >= 2) {
                     const uint32_t litCSize = lh.compSize; const bool single = lh.single;
                     if (!single && (litSize == 0 || litCSize == 0)) { ZS_PREP_WHY(__LINE__); break; }
-                    uint16_t *ht = reinterpret_cast<uint16_t *>(hufTabs + slot * ZS_FAST_HUFTAB_BYTES);
+                    uint16_t *ht = reinterpret_cast<uint16_t *>(zs_slot_huf_table(hufTabs, slot));
                     uint32_t h = 0;
                     if (type == 2) {
                         h = readHufTableT<true>(L, bs + lhSize, litCSize, ht, ZS_FAST_HUFLOG);
@@ -211,7 +211,7 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
                         if (lane == 0) L.misc[13] = L.hufLog | (flat << 8);
                     } else if (!hufOfDict) {                               // (the dictionary's table: k_dec_huffman stages the image, nothing is copied)
                         // the table of the block that built it, into this block's slot (the whole 4 KiB: 16 bytes a lane, 4 rounds)
-                        const uint4 *from = reinterpret_cast<const uint4 *>(hufTabs + ((size_t)(L.misc[11] - 1u) * cap + item) * ZS_FAST_HUFTAB_BYTES);
+                        const uint4 *from = reinterpret_cast<const uint4 *>(zs_slot_huf_table(hufTabs, zs_dec_slot(L.misc[11] - 1u, cap, item)));
                         uint4 *to = reinterpret_cast<uint4 *>(ht);
                         uint4 v[ZS_FAST_HUFTAB_BYTES / 16 / 64];
                         wave_mem_sync();                               // (stored by this wavefront, some blocks earlier)
@@ -245,8 +245,8 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
             const uint8_t *ip = bs + litCSizeTot; uint32_t remaining = cSize - litCSizeTot, nbSeq = 0;
             const uint32_t seqPrev = L.misc[12];                    // block + 1 of the last block that had sequences (its slot holds all three tables)
             DState st = zs_dstate_begin(); st.fseEntropy = seqPrev != 0;
-            uint16_t *stab = reinterpret_cast<uint16_t *>(seqTabs + slot * ZS_FAST_SEQTAB_BYTES);
-            const uint16_t *stabPrev = seqPrev ? reinterpret_cast<const uint16_t *>(seqTabs + ((size_t)(seqPrev - 1u) * cap + item) * ZS_FAST_SEQTAB_BYTES) : nullptr;
+            uint16_t *stab = reinterpret_cast<uint16_t *>(seqTabs + zs_slot_seq_tables_at(slot));
+            const uint16_t *stabPrev = seqPrev ? reinterpret_cast<const uint16_t *>(zs_slot_seq_tables(seqTabs, zs_dec_slot(seqPrev - 1u, cap, item))) : nullptr;
             if (DD && seqPrev == ZS_DD_SLOT) stabPrev = reinterpret_cast<const uint16_t *>(dd->seqTab);
             if (seqHeadersT<true>(L, st, ip, remaining, nbSeq, stab, &L.misc[8], stabPrev)) { ZS_PREP_WHY(__LINE__); break; }      // (misc[8..10]: a repeated table keeps the log it had)
             if (nbSeq > seqCap) { ZS_PREP_WHY(__LINE__); break; }
@@ -258,8 +258,8 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
                 // the block joins the list of its table class (k_dec_sequences takes its items from the lists: a launch over every slot with most lanes
                 // idle cost a whole chain's time for a class that holds a tenth of the blocks - libzstd's 32 KiB frames: 9 % have 2^9-cell tables)
                 const uint32_t cls = (L.misc[8] > 8u || L.misc[10] > 8u) ? 1u : 0u;
-                const uint32_t at = atomicAdd(&seqLists[cls], 1u);
-                seqLists[2 + (size_t)cls * cap * maxBlocks + at] = (uint32_t)slot;
+                const uint32_t at = atomicAdd(&seqLists[DecLists::kCountAt + cls], 1u);
+                seqLists[DecLists::kListAt + (size_t)cls * cap * maxBlocks + at] = (uint32_t)slot;
             }
             wave_sync();
             DSET(fast, 1u);
@@ -273,7 +273,7 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
     } while (0);
 #ifdef ZS_PREP_PROFILE
     if (lane == 0 && !descs[item].hufFlat) {          // phases 0-11, then the wavefront's whole time: behind the item's Huffman table (the two-level table ends at 1280 bytes; a flat one fills the slot)
-        unsigned long long *o = reinterpret_cast<unsigned long long *>(hufTabs + (size_t)item * ZS_FAST_HUFTAB_BYTES + 2048);
+        unsigned long long *o = zs_huftab_lend_prep_profile(hufTabs, item);
         for (int k = 0; k < 12; k++) o[k] = L.pp[k];
         o[12] = __builtin_amdgcn_s_memtime() - ppStart;
     }
@@ -281,7 +281,7 @@ k_dec_prep(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ ite
     // an item is fast only as a whole; a block index it does not use reads as absent
     if (lane == 0) {
         const uint32_t slots = max(2u, maxBlocks);                               // (a descriptor slot 1 exists even when the call reserved one block slot)
-        for (uint32_t b = ok ? nBlocks : 0u; b < slots; b++) descs[(size_t)b * cap + item].fast = 0;
+        for (uint32_t b = ok ? nBlocks : 0u; b < slots; b++) zs_slot_desc(descs, zs_dec_slot(b, cap, item))->fast = 0;
         if (!ok) descs[item].why = prepWhy;
     }
     #undef ZS_PREP_WHY
@@ -369,14 +369,14 @@ __device__ __forceinline__ void zs_dec_huffman_body(HufLds<FLAT, G> &H, const ui
     bool mine = false; uint32_t dtLog = 1, n = 0, size = 0;
     uint64_t dictHuf = 0;                                            // (DD) the item's table is its dictionary's: where that image holds it
     const uint8_t *src = srcAll; uint8_t *out = litScratchAll;
-    const size_t slot0 = (size_t)blk * cap;                          // this block index's descriptors, tables, literal scratch
+    const size_t slot0 = zs_dec_slot(blk, cap, 0);                        // this block index's descriptors, tables, literal scratch
     if (g < G && item < nItems) {
-        const ZsFastDesc *d = descs + slot0 + item;
+        const ZsFastDesc *d = zs_slot_desc(descs, slot0) + item;
         if (descs[item].fast && d->fast && d->litType == 2 && k < d->nStreams && ((DD ? d->hufFlat & 1u : d->hufFlat) != 0) == FLAT) {
             mine = true; dtLog = d->hufLog; n = d->sCnt[k]; size = d->sLen[k];
             if (DD && (d->hufFlat >> 1)) dictHuf = (uint64_t)zs_dict_entry(sel, descs[item].dict).img->hufTab;
             src = srcAll + items[item].srcOff + d->sOff[k];
-            out = litScratchAll + (slot0 + item) * litStride + d->sOut[k];
+            out = zs_slot_literals(litScratchAll, slot0 + item, litStride) + d->sOut[k];
         }
     }
     if (!__ballot(mine)) return;
@@ -385,7 +385,7 @@ __device__ __forceinline__ void zs_dec_huffman_body(HufLds<FLAT, G> &H, const ui
         const uint32_t it2 = bx * G + gg;
         const uint32_t log2 = wave_get(mine ? dtLog : 0u, (int)(gg * 4));        // stream 0 of the item exists whenever any does
         if (!log2) continue;
-        const uint32_t *ht = reinterpret_cast<const uint32_t *>(hufTabs + (slot0 + it2) * ZS_FAST_HUFTAB_BYTES);
+        const uint32_t *ht = reinterpret_cast<const uint32_t *>(zs_slot_huf_table(hufTabs, slot0 + it2));
         if (DD) {                                                    // (few images for many items: hot in L2)
             const uint64_t dh = ((uint64_t)wave_get((uint32_t)(dictHuf >> 32), (int)(gg * 4)) << 32) | wave_get((uint32_t)dictHuf, (int)(gg * 4));
             if (dh) ht = reinterpret_cast<const uint32_t *>(dh);
@@ -485,9 +485,9 @@ __device__ __forceinline__ void zs_dec_sequences_body(SeqDecLds<LOG9, G> &S, con
                   uint32_t listedMin = 0, uint32_t listedMax = 0xFFFFFFFFu)
 {
     // the blocks of this table class, listed by k_dec_prep (every block index of the call in one launch: blocks decode independently)
-    const uint32_t listed = seqLists[LOG9 ? 1 : 0];
+    const uint32_t listed = DecLists::classCount(seqLists, LOG9 ? 1 : 0);
     if (bid * G >= listed || listed < listedMin || listed >= listedMax) return;      // (listedMin / Max: the launch serves the class only when it holds that many blocks - the host cannot know)
-    const uint32_t *list = seqLists + 2 + (LOG9 ? (size_t)cap * nBlk : 0);
+    const uint32_t *list = DecLists::classList(seqLists, LOG9 ? 1 : 0, cap, nBlk);
     static_assert(G <= 16, "four lanes an item");
     constexpr uint32_t LLC = LOG9 ? 512 : 256, OFB = LLC, MLB = LLC + 256;        // cells of the LL table; where OF and ML start
     const uint32_t lane = (uint32_t)zs_lane();
@@ -498,13 +498,13 @@ __device__ __forceinline__ void zs_dec_sequences_body(SeqDecLds<LOG9, G> &S, con
     bool mine = false; uint32_t nbSeq = 0, size = 0, llLog = 0, ofLog = 0, mlLog = 0;
     const uint8_t *src = srcAll;
     if (g < G && v < listed && item < nItems) {
-        const ZsFastDesc *d = descs + slot;
+        const ZsFastDesc *d = zs_slot_desc(descs, slot);
         if (descs[item].fast && d->fast && d->nbSeq && ((d->llLog > 8 || d->mlLog > 8) == LOG9)) { mine = true; nbSeq = d->nbSeq; size = d->seqSize; llLog = d->llLog; ofLog = d->ofLog; mlLog = d->mlLog; src = srcAll + items[item].srcOff + d->seqOff; }
     }
     if (!__ballot(mine)) return;
     for (uint32_t gg = 0; gg < G; gg++) {
         if (!wave_get(mine ? 1u : 0u, (int)(4 * gg))) continue;
-        const uint32_t *st = reinterpret_cast<const uint32_t *>(seqTabs + (size_t)wave_get(slot, (int)(4 * gg)) * ZS_FAST_SEQTAB_BYTES);
+        const uint32_t *st = reinterpret_cast<const uint32_t *>(zs_slot_seq_tables(seqTabs, wave_get(slot, (int)(4 * gg))));
         const uint32_t a = 1u << wave_get(llLog, (int)(4 * gg)), o = 1u << wave_get(ofLog, (int)(4 * gg)), m = 1u << wave_get(mlLog, (int)(4 * gg));
         {   // the three tables, two cells a dword: every load issued before the first LDS store (up to 4 + 2 + 4 dwords per lane)
             uint32_t va[4], vo[2], vm[4];
@@ -528,7 +528,7 @@ __device__ __forceinline__ void zs_dec_sequences_body(SeqDecLds<LOG9, G> &S, con
     const uint32_t gi = min(g, G - 1u);
     uint32_t *winW = S.win[gi];
     const uint32_t *win = winW;
-    ZsFastSeq *outp = seqOutAll + (size_t)slot * seqCap;
+    ZsFastSeq *outp = zs_slot_seq_out(seqOutAll, slot, seqCap);
     // what a lane's role fixes: its table, the constants of its code's extra-bit count (see k_dec_sequences; an offset code IS its count),
     // where its state bits sit below the other states' (LL on top, then ML, then OF, :1547-1550)
     const uint16_t *cellsB = S.cells[gi] + (r == 1 ? MLB : (r == 2 ? OFB : 0u)) - 512;
@@ -858,16 +858,16 @@ k_dec_execute(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ 
     const uint8_t *dictEnd = (DD && dd) ? dd->contentEnd : nullptr;
     #pragma unroll 1
     for (uint32_t blk = 0; blk < slots && !bad; blk++) {
-    const size_t slot = (size_t)blk * cap + itemU;
-    const ZsFastDesc *dp = descs + slot;
+    const size_t slot = zs_dec_slot(blk, cap, itemU);
+    const ZsFastDesc *dp = zs_slot_desc(descs, slot);
     if (blk && !dp->fast) break;                                                // a one-block frame
     struct { uint32_t litType, litSize, litSrc, nbSeq, seqOff; } d;            // what this kernel needs of the block's descriptor (scalars)
     d.litType = dp->litType; d.litSize = dp->litSize; d.litSrc = dp->litSrc; d.nbSeq = dp->nbSeq; d.seqOff = dp->seqOff;
-    uint8_t *litBuf = litScratchAll + slot * litStride;
+    uint8_t *litBuf = zs_slot_literals(litScratchAll, slot, litStride);
     const uint8_t *litPtr = litBuf;
     if (d.litType == 0) litPtr = srcAll + it.srcOff + d.litSrc;
     else if (d.litType == 1 && d.nbSeq != 0) { for (uint32_t j = lane; j < d.litSize; j += 64) litBuf[j] = (uint8_t)d.litSrc; wave_mem_sync(); }
-    ZsFastSeq *seqs = seqAll + slot * seqCap;                           // (pass A writes each sequence back in place)
+    ZsFastSeq *seqs = zs_slot_seq_out(seqAll, slot, seqCap);                         // (pass A writes each sequence back in place)
     const uint8_t *bits = srcAll + it.srcOff + d.seqOff;                        // the sequence bitstream, d.seqSize bytes
     // the 64 stream bits below bit position p, top aligned (bit p - 1 at bit 63); bits below the stream start read as 0
     auto bitsBelow = [&](int32_t p) -> uint64_t {
@@ -1107,7 +1107,7 @@ k_dec_checksum(const ZsDecItem *__restrict__ items, uint32_t nItems, const ZsFas
     // four lanes an item (round 4): XXH64's four stripe accumulators side by side
     const uint32_t item = min(blockIdx.x * 16 + (threadIdx.x >> 2), nItems - 1u);
     const bool real = blockIdx.x * 16 + (threadIdx.x >> 2) < nItems;
-    const ZsFastDesc *d = descs + item;
+    const ZsFastDesc *d = zs_slot_desc(descs, item);
     uint32_t size = (real && d->fast && d->hasChecksum) ? dstSizes[item] : 0xFFFFFFFFu;
     const bool work = size <= 0xFFFFFF88u;
     if (!__ballot(work)) return;

@@ -16,11 +16,12 @@
 #ifndef ZSMI_DECODE_KERNELS_HIP         // (decode_fast.hip and seekable.hip include this file too)
 #define ZSMI_DECODE_KERNELS_HIP
 #include "zsmi_device.h"
+#include "zsmi_scratch.h"         // the pool's literal buffers, the general kernel's lists (DecLists)
 #include "zsmi_wave.h"
 #include "zsmi_frame.h"           // the one place a frame, block or literals-section header is read
 #include "zsmi_fse.h"             // the alphabets' constants (default distributions, LL / ML base and bits), the table builder's two routines
 
-// -DZS_DEC_PROFILE: cycles per phase of each item, left in the 64 spare bytes behind its literal scratch
+// -DZS_DEC_PROFILE: cycles per phase of each item, left in the 64 spare bytes behind its literal scratch (zs_poollit_lend_dec_profile)
 // (0 literals incl. Huffman table, 1 sequence tables, 2 sequence decoding, 3 sequence execution, 4 checksum, 5 whole item)
 #ifdef ZS_DEC_PROFILE
 #define PROF_T0() uint64_t prof_t_ = __builtin_readcyclecounter()
@@ -1090,7 +1091,6 @@ __device__ __forceinline__ ZsDictEntry zs_dict_entry(const ZsDictSel &s, uint32_
 // for a call with one dictionary): raw content, or a formatted dictionary (magic 0xEC30A437) whose entropy tables and recent offsets are
 // loaded in front of each frame (ZSTD_decompressBegin_usingDict :2501, LoadEntropy :2378-2450) -- by every wavefront for itself: a dictionary
 // is a few KiB.  A frame that names an ID the selector does not hold gets none, and is dictionary_wrong by the test behind the load.
-#define ZS_DEC_LITBUF ((1u << 17) + 64u)                 // a wavefront's literal buffer: the largest block + slack
 template <bool DICT>
 __device__ __forceinline__ void zs_decode_item(DLds &L, const uint32_t item, const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict__ items, uint8_t *dstAll,
                                                uint32_t *__restrict__ dstSizes, uint8_t *litBuf, const ZsDictSel &sel)
@@ -1101,7 +1101,7 @@ __device__ __forceinline__ void zs_decode_item(DLds &L, const uint32_t item, con
     uint8_t *dstBase = dstAll + it.dstOff;
     uint64_t *g_prof = nullptr;
 #ifdef ZS_DEC_PROFILE
-    if (lane == 0) { g_prof = reinterpret_cast<uint64_t *>(litBuf + (1u << 17)); for (int k = 0; k < 8; k++) g_prof[k] = 0; }
+    if (lane == 0) { g_prof = zs_poollit_lend_dec_profile(litBuf); for (int k = 0; k < 8; k++) g_prof[k] = 0; }
     const uint64_t prof_start_ = __builtin_readcyclecounter();
 #endif
     uint32_t srcSize = it.srcSize;
@@ -1192,6 +1192,7 @@ finish:
 // memory, zeroed before the launch): what the buffers cost is set by the wavefronts the chip holds, not by the items of a call (round 3 reserved
 // 128 KiB per ITEM: 7 GiB for 57344 frames of 32 KiB that the fast path had already decoded), and wavefronts that finish early take more.
 // After the fast path the queue runs over the LIST of the items it left (k_dec_collect), so an atomic is spent per item to decode, not per item of the call.
+// (list, listCount, queue: DecLists' left list, left count and queue, handed out by the host.)
 __global__ void __launch_bounds__(256)
 k_dec_collect(const uint32_t *__restrict__ doneFlags, uint32_t flagStride, uint32_t nItems, uint32_t *__restrict__ list, uint32_t *__restrict__ listCount)
 {
@@ -1211,18 +1212,18 @@ k_decode_frames(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict_
                 const ZsDictSel sel, uint32_t *__restrict__ queue)
 {
     __shared__ DLds LS[F];
-    const uint32_t total = list ? *listCount : nItems;                          // (list == nullptr: every item of the call)
+    const uint32_t total = DecLists::queued(list, listCount, nItems);                        // (list == nullptr: every item of the call)
     if (blockIdx.x * F >= total) return;                                        // nothing left for this workgroup (behind the fast path usually for all of them: the launch is then a few microseconds, not the 0.04 ms of 3072 wavefronts setting up)
     DLds &L = LS[threadIdx.x >> 6];
     const uint32_t lane = (uint32_t)zs_lane();
-    uint8_t *litBuf = litScratchAll + (size_t)(blockIdx.x * F + (threadIdx.x >> 6)) * ZS_DEC_LITBUF;
+    uint8_t *litBuf = zs_pool_lit_buffer(litScratchAll, blockIdx.x * F + (threadIdx.x >> 6));
     zs_lds_length_tables(L);
     for (;;) {
         uint32_t at = 0;
         if (lane == 0) at = atomicAdd(queue, 1u);
         at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
         if (at >= total) break;                                                 // (every wavefront gets here: the queue only grows)
-        const uint32_t item = list ? list[at] : at;
+        const uint32_t item = DecLists::queuedItem(list, at);
         zs_decode_item<DICT>(L, item, srcAll, items, dstAll, dstSizes, litBuf, sel);
         wave_mem_sync();                                                        // the buffer and the LDS image are the next item's
     }

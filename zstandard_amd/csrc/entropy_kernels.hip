@@ -18,6 +18,7 @@
 #ifndef ZSMI_ENTROPY_KERNELS_HIP        // (dict_train.hip and seekable.hip include this file too)
 #define ZSMI_ENTROPY_KERNELS_HIP
 #include "zsmi_device.h"
+#include "zsmi_scratch.h"         // the scratch slots of a block (records, range headers, literals, streams, sections, meta: ZsBlockMeta) and what the sequences kernel borrows
 #include "zsmi_wave.h"
 #include "zsmi_fse.h"            // the alphabets' constants, FseBuild, the table builder's two routines
 // timing aids of the development tools (tools/time_kernels.py): end a kernel after a stage.  Compiled in only with
@@ -550,17 +551,6 @@ __device__ __forceinline__ uint32_t huffEncodeStream(K3Lds &L, uint32_t *tile, u
     return sink_close(sink);
 }
 
-// ---------------------------------------------------------------------------------------------
-// per-block result of the two encode kernels, consumed by k_assemble_frames
-// ---------------------------------------------------------------------------------------------
-struct ZsBlockMeta { uint32_t type;       // 0 raw, 1 rle, 2 literal + sequence sections present
-                     uint32_t rleByte; uint32_t litSecSize; uint32_t seqSecSize;      // seqSecSize 0xFFFFFFFF: section failed / overflowed
-                     uint32_t seqHdrSize, seqGap;     // the sequence section lies in its buffer as seqHdrSize bytes, seqGap (0..3) unused bytes,
-                     uint32_t pad[2]; };              // then the bitstream (built 4-byte aligned); k_assemble_frames closes the gap as it copies
-#define ZS_LITSEC_STRIDE  (ZS_BLOCK_MAX + 1024u)
-#define ZS_SEQSEC_STRIDE  (ZS_BLOCK_MAX + 4096u)
-#define ZS_STREAM_STRIDE  (24u * 1024u)          // per Huffman stream scratch: 16384 symbols * 11 bits = 22528 B max
-
 // exclusive "last lane below me with flag" : returns lane index or -1
 __device__ __forceinline__ int lastFlagBelow(bool flag)
 {
@@ -660,28 +650,28 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     const ZsBlockDesc bd = blocks[blk];
     const uint8_t *s = src + bd.srcOff;
     const uint32_t n = bd.size;
-    const ZsSeqRec *seqBase = seqAll + (size_t)blk * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE;
-    const ZsRangeHdr *hdr = hdrAll + (size_t)blk * ZS_WALK_RANGES;
-    uint8_t *lits = litsAll + (size_t)blk * (ZS_BLOCK_MAX + 64);
-    uint8_t *streams = streamAll + (size_t)blk * 4 * ZS_STREAM_STRIDE;
+    const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
+    const ZsRangeHdr *hdr = zs_block_range_hdrs(hdrAll, blk);
+    uint8_t *lits = zs_block_lits(litsAll, blk);
+    uint8_t *streams = zs_block_streams(streamAll, blk);
     // the literal section of a one-block chunk is built where its frame wants it (behind the frame header and the 3-byte block header: the
     // slot holds zsmi_compressBound(n) >= n + 27 bytes, the section never more than n + 3), every other block's in the section buffer
     const bool solo = bd.firstInChunk && bd.lastInChunk && !ZS_STOPPED;
-    uint8_t *payload = litSecAll + (size_t)blk * ZS_LITSEC_STRIDE;
+    uint8_t *payload = zs_block_lit_section(litSecAll, blk);
     if (solo) { const ZsChunkDesc cd0 = chunks[bd.chunk]; payload = dst + cd0.dstOff + zs_frame_header(nullptr, cd0.size, false, dictID) + 3; }
     const uint32_t cap = n + 512;
 
     // The block's literal side is done: its meta goes out; a chunk of ONE block is assembled right here (the sequences kernel ran before this
     // one on the stream, its section and meta fields are there) - k_assemble_frames is launched only for batches with longer chunks
     #define FINISH(tp, lsz, rb) do { \
-        if (tid == 0) { metas[blk].type = (tp); metas[blk].rleByte = (rb); metas[blk].litSecSize = (lsz); } \
+        if (tid == 0) { ZsBlockMeta &mo_ = zs_block_meta(metas, blk); mo_.type = (tp); mo_.rleByte = (rb); mo_.litSecSize = (lsz); } \
         if (bd.firstInChunk && bd.lastInChunk && !ZS_STOPPED) { \
             __syncthreads();                         /* the literal section was written by all wavefronts */ \
-            ZsBlockMeta m_ = metas[blk]; m_.type = (tp); m_.rleByte = (rb); m_.litSecSize = (lsz); \
+            ZsBlockMeta m_ = zs_block_meta(metas, blk); m_.type = (tp); m_.rleByte = (rb); m_.litSecSize = (lsz); \
             const ZsChunkDesc cd_ = chunks[bd.chunk]; \
             uint8_t *out_ = dst + cd_.dstOff; \
             uint32_t pos_ = zs_frame_header(out_, cd_.size, tid == 0, dictID); \
-            pos_ += zs_emit_block(out_, pos_, s, n, 1u, m_, payload, seqSecAll + (size_t)blk * ZS_SEQSEC_STRIDE, tid, 256); \
+            pos_ += zs_emit_block(out_, pos_, s, n, 1u, m_, payload, zs_block_seq_section(seqSecAll, blk), tid, 256); \
             if (tid == 0) dstSizes[bd.chunk] = pos_; \
         } \
         return; } while (0)
@@ -733,7 +723,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
             for (uint32_t g = 0; g < 4; g++) {
                 const uint32_t r = r0 + 4 * g;
                 ns[g] = (r < ZS_WALK_RANGES) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)L.rngN[r]) : 0u;
-                const ZsSeqRec *rb = seqBase + (size_t)min(r, (uint32_t)ZS_WALK_RANGES - 1) * ZS_SEQ_PER_RANGE + L.rngFirst[min(r, (uint32_t)ZS_WALK_RANGES - 1)];
+                const ZsSeqRec *rb = zs_range_seqs(seqBase, min(r, (uint32_t)ZS_WALK_RANGES - 1)) + L.rngFirst[min(r, (uint32_t)ZS_WALK_RANGES - 1)];
                 #pragma unroll
                 for (uint32_t q = 0; q < 4; q++) {
                     rec[g][q] = make_uint2(0, 0);
@@ -942,7 +932,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
             if (single) { if (wave == 0) { const uint32_t z = huffEncodeStream(L, L.u.tile[0], streams, litp, 0, nlit); if (lane == 0) L.misc[8] = z; } }
             else {
                 const uint32_t len = (wave < 3) ? seg : nlit - 3 * seg;
-                const uint32_t z = huffEncodeStream(L, L.u.tile[wave], streams + wave * ZS_STREAM_STRIDE, litp, wave * seg, len);
+                const uint32_t z = huffEncodeStream(L, L.u.tile[wave], zs_stream(streams, wave), litp, wave * seg, len);
                 if (lane == 0) L.misc[8 + wave] = z;
             }
             __syncthreads();
@@ -957,7 +947,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
                 }
                 const uint32_t ssz[4] = { ssz0, ssz1, ssz2, ssz3 };
                 for (uint32_t k = 0; k < (single ? 1u : 4u); k++) {
-                    const uint8_t *from = streams + k * ZS_STREAM_STRIDE;
+                    const uint8_t *from = zs_stream(streams, k);
                     zs_block_copy(op, from, ssz[k], tid, 256);
                     op += ssz[k];
                 }
@@ -984,7 +974,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
             if (single) { if (wave == 0) { const uint32_t z = huffEncodeStream(L, L.u.tile[0], streams, litp, 0, nlit); if (lane == 0) L.misc[8] = z; } }
             else {
                 const uint32_t len = (wave < 3) ? seg : nlit - 3 * seg;
-                const uint32_t z = huffEncodeStream(L, L.u.tile[wave], streams + wave * ZS_STREAM_STRIDE, litp, wave * seg, len);
+                const uint32_t z = huffEncodeStream(L, L.u.tile[wave], zs_stream(streams, wave), litp, wave * seg, len);
                 if (lane == 0) L.misc[8 + wave] = z;
             }
             __syncthreads();
@@ -999,7 +989,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
                 }
                 const uint32_t ssz[4] = { ssz0, ssz1, ssz2, ssz3 };
                 for (uint32_t k = 0; k < (single ? 1u : 4u); k++) {
-                    const uint8_t *from = streams + k * ZS_STREAM_STRIDE;
+                    const uint8_t *from = zs_stream(streams, k);
                     zs_block_copy(op, from, ssz[k], tid, 256);
                     op += ssz[k];
                 }
@@ -1040,7 +1030,6 @@ __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PA
 #ifndef ZS_SEQ_TB
 #define ZS_SEQ_TB 4                // tiles of 64 sequences whose records are requested together (pass 1, packing)
 #endif
-#define ZS_CHAIN_CODES 16384u      // most sequences a block can hold (64 output ranges of 256 record slots): elements per table in the chain scratch
 #ifndef ZS_CHAIN_WARM
 #define ZS_CHAIN_WARM 512u         // steps a chain segment starts ahead of its first output (a multiple of 16)
 #endif
@@ -1050,7 +1039,6 @@ __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PA
 #ifndef ZS_CHAIN_MINSEG
 #define ZS_CHAIN_MINSEG 4u         // shortest segment, in blocks of 16 steps
 #endif
-static_assert(3u * ZS_CHAIN_CODES <= ZS_BLOCK_MAX + 64u && 3u * 2u * ZS_CHAIN_CODES <= 4u * ZS_STREAM_STRIDE && ZS_CHAIN_CODES == ZS_WALK_RANGES * ZS_SEQ_PER_RANGE, "the chain scratch fits the buffers it borrows");
 // reps: the recent offsets a chunk's first block starts from ({1, 4, 8}, or a formatted dictionary's own)
 #define ZS_SEQ_PARAMS const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
                       uint8_t *__restrict__ seqSecAll, ZsBlockMeta *__restrict__ metas, int stopAt, uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, \
@@ -1071,15 +1059,14 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
     const bool exists = blk < nBlocks;
     const ZsBlockDesc bd = blocks[exists ? blk : 0];
     const uint32_t n = bd.size;
-    const ZsSeqRec *seqBase = seqAll + (size_t)blk * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE;
-    const ZsRangeHdr *hdr = hdrAll + (size_t)blk * ZS_WALK_RANGES;
-    uint8_t *out = seqSecAll + (size_t)blk * ZS_SEQSEC_STRIDE;         // 4-byte aligned
+    const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
+    const ZsRangeHdr *hdr = zs_block_range_hdrs(hdrAll, blk);
+    uint8_t *out = zs_block_seq_section(seqSecAll, blk);
     const uint32_t cap = n + 512;
-    // scratch of part 2's state chains, borrowed from the literals kernel (which runs after this one and writes both before it reads them):
-    // a code byte a sequence and table in the block's literal buffer, 16 bits of chain output a sequence and table in its Huffman stream buffers
-    uint8_t *chainCodes = litsAll + (size_t)blk * (ZS_BLOCK_MAX + 64);
-    uint16_t *chainOuts = reinterpret_cast<uint16_t *>(streamAll + (size_t)blk * 4 * ZS_STREAM_STRIDE);
-    uint2 *packRec = packRecAll + (size_t)blk * ZS_CHAIN_CODES;       // 8 bytes a sequence: its extra bits; the block's slot of the stage-1 distances (128 KiB), dead since the walk
+    // scratch of part 2's state chains and of the packing, borrowed (zsmi_scratch.h says from whom and until when)
+    uint8_t *chainCodes = zs_lits_lend_chain_codes(litsAll, blk);
+    uint16_t *chainOuts = zs_streams_lend_chain_outs(streamAll, blk);
+    uint2 *packRec = zs_dist_lend_pack_records(packRecAll, blk);
 
     // ======== part 1, each wavefront on its own block (no workgroup barrier inside): header, recent-offset codes,
     //          histograms, tables.  result: section size so far / 0xFFFFFFFF = no compressed sequences section ========
@@ -1118,7 +1105,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
                 #pragma unroll
                 for (uint32_t stepb = ZS_WALK_RANGES / 2; stepb >= 1; stepb >>= 1) if (g >= L.rngStart[rr + stepb]) rr += stepb;
                 kOut = g - L.rngStart[rr]; rrOut = rr;
-                return seqBase + (size_t)rr * ZS_SEQ_PER_RANGE + L.rngFirst[rr] + kOut;
+                return zs_range_seqs(seqBase, rr) + L.rngFirst[rr] + kOut;
             };
             // (a record travels as its two raw words and is taken apart only where it is used: unpacked next to the load, the
             // compiler waits for the load on the spot).  ZS_SEQ_TB tiles of 64 are requested together and worked through one after the other:
@@ -1311,7 +1298,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
         // see, and waited for by count: vmcnt(2) leaves exactly those stores in flight (in-order return: DESIGN section 6).  For the count to
         // hold every lane stores every round - where it has nothing to store, into a junk slot of the section buffer (written by the packing later).
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        uint8_t *junk = out + 32768u + 32u * lane;
+        uint8_t *junk = zs_seqsec_lend_junk_store(out, lane);
         auto runBlocks = [&](uint32_t from, uint32_t to, uint32_t outFrom, uint32_t mark, uint32_t &state, uint32_t &entry, uint32_t rounds) {
             u32x4 cw;
             {
@@ -1372,7 +1359,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
         };
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");          // pass 1's code bytes (other lanes' stores) are read below
 #ifdef ZS_CHAIN_COUNT
-        if (lane == 0) { metas[blk].pad[0] = 0; metas[blk].pad[1] = K | (Sb << 8) | (nseq << 16); }
+        if (lane == 0) { zs_meta_lend_chain_counts(metas, blk).pad[0] = 0; zs_meta_lend_chain_counts(metas, blk).pad[1] = K | (Sb << 8) | (nseq << 16); }
 #endif
         uint32_t state = 0, entry = 0;
         const bool runs = chainLane && (firstOut < nFull || k == 0);
@@ -1398,7 +1385,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
             const bool bad = runs && k == kk && entry != prevExit;
             if (__any(bad)) {
 #ifdef ZS_CHAIN_COUNT
-                if (lane == 0) metas[blk].pad[0] += (uint32_t)__popcll(__ballot(bad)) | (1u << 16);      // development aid: seams that failed / rounds of repair
+                if (lane == 0) zs_meta_lend_chain_counts(metas, blk).pad[0] += (uint32_t)__popcll(__ballot(bad)) | (1u << 16);      // development aid: seams that failed / rounds of repair
 #endif
                 // (a repair is the chain run serially with one to three lanes: its wavefront issues ahead of the others on its SIMD, as the shared chain
                 //  wavefront of rounds 1 - 3 did)
@@ -1481,7 +1468,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
         const uint32_t total = bitstreamOff + bsSize;
         result = total > cap ? 0xFFFFFFFFu : total;
     }
-    if (lane == 0 && exists) { metas[blk].seqSecSize = result; metas[blk].seqHdrSize = (secHdr == 0xFFFFFFFFu) ? result : secHdr; metas[blk].seqGap = secGap; }
+    if (lane == 0 && exists) { ZsBlockMeta &mo = zs_block_meta(metas, blk); mo.seqSecSize = result; mo.seqHdrSize = (secHdr == 0xFFFFFFFFu) ? result : secHdr; mo.seqGap = secGap; }
 }
 template <int G, bool CD>
 __global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictTables *__restrict__ cdt) { encode_sequences_block<G, CD>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, cdt); }
@@ -1507,8 +1494,8 @@ extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAM
         const uint32_t gb = cd.firstBlock + b;             // global block index
         const uint32_t lb = gb - blockBase;                // index inside this sub-batch's scratch
         const ZsBlockDesc bd = blocks[gb];
-        pos += zs_emit_block(out, pos, src + bd.srcOff, bd.size, (b + 1 == cd.nBlocks) ? 1u : 0u, metas[lb],
-                             litSecAll + (size_t)lb * ZS_LITSEC_STRIDE, seqSecAll + (size_t)lb * ZS_SEQSEC_STRIDE, tid, blockDim.x);
+        pos += zs_emit_block(out, pos, src + bd.srcOff, bd.size, (b + 1 == cd.nBlocks) ? 1u : 0u, zs_block_meta(metas, lb),
+                             zs_block_lit_section(litSecAll, lb), zs_block_seq_section(seqSecAll, lb), tid, blockDim.x);
     }
     if (tid == 0) dstSizes[chunkBase + blockIdx.x] = pos;
 }
@@ -1526,16 +1513,16 @@ __global__ void __launch_bounds__(256) k_train_stats(const uint8_t *__restrict__
     const uint32_t n = bd.size;
     for (uint32_t i = tid; i < ZS_BLOCK_MAX / 32; i += 256) cov[i] = 0;
     for (uint32_t i = tid; i < kTrainStatWords; i += 256) hist[i] = 0;
-    const ZsRangeHdr *hdr = hdrAll + (size_t)blk * ZS_WALK_RANGES;
+    const ZsRangeHdr *hdr = zs_block_range_hdrs(hdrAll, blk);
     if (tid == 0) { uint32_t s = 0; for (uint32_t r = 0; r < ZS_WALK_RANGES; r++) { rstart[r] = s; s += n >= 16 ? hdr[r].nseq : 0u; } rstart[ZS_WALK_RANGES] = s; }
     __syncthreads();
     const uint32_t nseq = rstart[ZS_WALK_RANGES];
-    const ZsSeqRec *seqBase = seqAll + (size_t)blk * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE;
-    const uint8_t *codes = litsAll + (size_t)blk * (ZS_BLOCK_MAX + 64);
+    const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
+    const uint8_t *codes = zs_lits_lend_chain_codes_to_stats(litsAll, blk);
     for (uint32_t g = tid; g < nseq; g += 256) {
         uint32_t r = 0;
         for (uint32_t st = ZS_WALK_RANGES / 2; st >= 1; st >>= 1) if (g >= rstart[r + st]) r += st;
-        const ZsSeqRec rec = seqBase[(size_t)r * ZS_SEQ_PER_RANGE + hdr[r].first + (g - rstart[r])];
+        const ZsSeqRec rec = seqBase[zs_range_seq_slot(r) + hdr[r].first + (g - rstart[r])];
         const uint32_t pos = zs_rec_pos(rec.y), end = min(pos + zs_rec_ml(rec.x), n);
         for (uint32_t b = pos; b < end;) {                                  // the match's bytes in the coverage bitmap
             const uint32_t w = b >> 5, lo = b & 31u, cnt = min(32u - lo, end - b);

@@ -6,6 +6,7 @@
 // There is no reference code for this stage (the reference has no encoder);
 // what it emits is consumed by entropy_kernels.hip, whose output the reference decoder must accept.
 #include "zsmi_device.h"
+#include "zsmi_scratch.h"         // the scratch slots of a block: distances, candidate counts, walk records, range results, sequence records, range headers
 #include <type_traits>
 
 // ---------------------------------------------------------------------------------------------
@@ -96,13 +97,13 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
     const uint8_t *s = src + ud.srcOff;
     const uint32_t n = ud.size;
     const size_t slot = (size_t)(ud.firstBlock - block0);
-    uint16_t *dist = distAll + slot * ZS_BLOCK_MAX;
-    uint8_t *distHi = distHiAll + slot * (ZS_BLOCK_MAX / 8);
+    uint16_t *dist = zs_block_dist(distAll, slot);
+    uint8_t *distHi = zs_block_dist_hi(distHiAll, slot);
     const uint32_t hashable = (n >= 8) ? n - 7 : 0;                   // positions [0, hashable) have 8 bytes
     const uint32_t nGroups = (hashable + GP - 1) / GP;
-    // candidate positions of the unit, counted by the mergers (a word each: candCount[2 slot + table]): k_lz_walk leaves a unit with fewer than
+    // candidate positions of the unit, counted by the mergers (a word each: zs_block_cand): k_lz_walk leaves a unit with fewer than
     // n >> ZS_MATCHLESS_SHIFT of them alone (findCandidates in oracle/zso_encoder.c: matchless units)
-    if (threadIdx.x < 2) candCount[2 * slot + threadIdx.x] = 0;          // (written again by the mergers at their end: same wavefront order does not matter, they add nothing before)
+    if (threadIdx.x < 2) zs_block_cand(candCount, slot, threadIdx.x) = 0;          // (written again by the mergers at their end: same wavefront order does not matter, they add nothing before)
     if (nGroups == 0) return;
     // A unit of one repeated byte needs no candidates: the walk kernel tests for exactly this (same condition) and skips its walk, the
     // blocks become RLE blocks.  Ordinary data fails the test on its first 16 bytes.
@@ -173,7 +174,7 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
             mergeStore(i - 2, mS, mL);
             __syncthreads();
         }
-        if (lane == 0) candCount[2 * slot + tab] = found;
+        if (lane == 0) zs_block_cand(candCount, slot, tab) = found;
         return;
     }
 
@@ -485,7 +486,7 @@ __device__ __forceinline__ uint32_t zs_nonzero8(const uint4 d)
 
 #ifdef ZS_WALK_PROFILE
 // diagnostic build (tools/walk_profile.py): s_memtime stamps per wavefront and step part, every outstanding memory operation waited for at a stamp
-// (so the parts do not overlap as they do in the product); the sums go behind all blocks' range results (the output stays valid)
+// (so the parts do not overlap as they do in the product); the sums go behind all blocks' range results (zs_res_lend_walk_profile; the output stays valid)
 #define WPROF_STAMP(k) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); wprof[k] += t_ - wlast; wlast = t_; }
 #else
 #define WPROF_STAMP(k)
@@ -528,15 +529,15 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     const uint32_t slot = ud.firstBlock - block0;                                // scratch slot of the unit's first block
     const uint8_t *s = src + ud.srcOff;
     const uint32_t n = ud.size;
-    const uint16_t *dist = distAll + (size_t)slot * ZS_BLOCK_MAX;
-    const uint8_t *distHi = distHiAll + (size_t)slot * (ZS_BLOCK_MAX / 8);
+    const uint16_t *dist = zs_block_dist(distAll, slot);
+    const uint8_t *distHi = zs_block_dist_hi(distHiAll, slot);
     uint4 *xbuf = reinterpret_cast<uint4 *>(walkLds);                              // exchange buffer: wavefront w's region holds GPL x 64 slots of 8 distances: lane t's k-th group at [(64 w) GPL + 64 k + t]
     const uint32_t xw = (tid & ~63u) * GPL;                                      // my wavefront's first slot
     const uint32_t safeAddr = (xw + lane) * 16u;                                 // LDS address of my own first slot: where a lane with nothing to read reads (its own banks, no conflict)
     uint32_t *queue = reinterpret_cast<uint32_t *>(walkLds + SRC + ZS_WALK_SRCBYTES(CAP));
-    uint4 *res = resAll + (size_t)slot * ZS_RES_PER_BLOCK;                       // per walk range (R >= 256: at most 256 a block): records, last match end in its block, last offset
+    uint4 *res = zs_block_range_results(resAll, slot);                         // per walk range (R >= 256: at most 256 a block): records, last match end in its block, last offset
     uint8_t *xhi = reinterpret_cast<uint8_t *>(queue + 4);                        // BIG: lane t's byte of bit 16 of its 8 distances
-    uint2 *recs = recAll + (size_t)slot * (ZS_BLOCK_MAX / 4);                     // range at unit position p: slots from p / 4 (its matches start inside it, >= 4 bytes each)
+    uint2 *recs = zs_block_walk_records(recAll, slot);                        // range at unit position p: slots from p / 4 (its matches start inside it, >= 4 bytes each)
     const uint32_t sub = lane & (LPW - 1u);
 #ifdef ZS_WALK_PROFILE
     unsigned long long wprof[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, wlast;
@@ -545,9 +546,9 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
 
     // a MATCHLESS unit (fewer than n >> ZS_MATCHLESS_SHIFT candidate positions: incompressible input's chance candidates) is not walked: its ranges
     // report no records, its blocks go on without sequences (findCandidates / parseBlock in oracle/zso_encoder.c)
-    if (candCount[2 * slot] + candCount[2 * slot + 1] < (n >> ZS_MATCHLESS_SHIFT)) {
+    if (zs_block_cand(candCount, slot, 0) + zs_block_cand(candCount, slot, 1) < (n >> ZS_MATCHLESS_SHIFT)) {
         const uint32_t nRanges = (n + R - 1) >> rangeLog, perBlockLog = 16u - rangeLog;
-        for (uint32_t r = tid; r < nRanges; r += NT) res[(r >> perBlockLog) * ZS_RES_PER_BLOCK + (r & ((1u << perBlockLog) - 1u))] = make_uint4(0, 0, 0, 0);
+        for (uint32_t r = tid; r < nRanges; r += NT) res[zs_unit_range_result(r, perBlockLog)] = make_uint4(0, 0, 0, 0);
         return;
     }
     // ---- stage the unit ----
@@ -619,7 +620,7 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     __syncthreads();
     if (queue[1] == 0) {
         const uint32_t nRanges = (n + R - 1) >> rangeLog, perBlockLog = 16u - rangeLog;
-        for (uint32_t r = tid; r < nRanges; r += NT) res[(r >> perBlockLog) * ZS_RES_PER_BLOCK + (r & ((1u << perBlockLog) - 1u))] = make_uint4(0, 0, 0, 0);
+        for (uint32_t r = tid; r < nRanges; r += NT) res[zs_unit_range_result(r, perBlockLog)] = make_uint4(0, 0, 0, 0);
         return;
     }
     WPROF_STAMP(0)
@@ -631,7 +632,7 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
         uint32_t r = 0, ip = 0, anchor = 0, scanEnd = 0, limit = 0, rep0 = 0, rep1 = 0, nseq = 0, lastOff = 0, recBase = 0, blockBase = 0;
         uint2 heldRec = make_uint2(0, 0);                                        // the odd record waiting for its pair
         const uint32_t perBlockLog = 16u - rangeLog;                             // walk ranges per block
-        auto resIndex = [&](uint32_t rr) { return (rr >> perBlockLog) * ZS_RES_PER_BLOCK + (rr & ((1u << perBlockLog) - 1u)); };
+        auto resIndex = [&](uint32_t rr) { return zs_unit_range_result(rr, perBlockLog); };
         // distances of the group (ip >> 3) + sub, requested as soon as ip is known: 16 bytes a lane straight into the lane's slot of the
         // exchange buffer (LDS-DMA: no registers carried around the loop, no wait the compiler places for me; behind the hashable positions
         // whatever the scratch holds: those bits are cut off the window).  BIG: bit 16 of the distances, a byte per group, by an ordinary load.
@@ -846,7 +847,7 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     WPROF_STAMP(1)
 #ifdef ZS_WALK_PROFILE
     __syncthreads();
-    if (lane == 0) { unsigned long long *o = reinterpret_cast<unsigned long long *>(resAll + (size_t)(junkSlot / 64)) + ((size_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 10;   /* behind all blocks' results */ for (int k = 0; k < 10; k++) o[k] = wprof[k]; }
+    if (lane == 0) { unsigned long long *o = zs_res_lend_walk_profile(resAll, junkSlot) + ((size_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 10; for (int k = 0; k < 10; k++) o[k] = wprof[k]; }
 #endif
 }
 
@@ -868,8 +869,8 @@ k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ re
     const uint32_t slot = blockIdx.x;
     const uint32_t NRB = ZS_BLOCK_MAX >> rangeLog;                               // walk ranges per block
     const uint32_t gLog = ZS_OUT_LOG - rangeLog, G = 1u << gLog;                 // walk ranges per output range
-    const uint2 *recs = recAll + (size_t)slot * (ZS_BLOCK_MAX / 4);
-    const uint4 *res = resAll + (size_t)slot * ZS_RES_PER_BLOCK;
+    const uint2 *recs = zs_block_walk_records(recAll, slot);
+    const uint4 *res = zs_block_range_results(resAll, slot);
     {
         const uint32_t bStart = 0, bi = 0;
         const uint32_t bN = blocks[slot].size;
@@ -954,7 +955,7 @@ k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ re
             const uint32_t g = wave * (ZS_WALK_RANGES / (NT / 64)) + go, j0 = g << gLog;
             uint32_t c[4] = { 0, 0, 0, 0 }, total = 0;
             for (uint32_t i = 0; i < G; i++) { c[i] = sCnt[j0 + i]; total += c[i]; }
-            ZsSeqRec *out = seqAll + ((size_t)slot * ZS_WALK_RANGES + g) * ZS_SEQ_PER_RANGE;
+            ZsSeqRec *out = zs_out_range_seqs(seqAll, zs_out_range(slot, g));
             uint32_t lits = 0;
             for (uint32_t d0 = 0; d0 < total; d0 += 64) {
                 const uint32_t d = d0 + lane;
@@ -981,7 +982,7 @@ k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ re
             if (lane == 0) {
                 ZsRangeHdr h; h.nseq = total; h.litSum = lits; h.trailing = 0; h.first = 0;
                 for (uint32_t i = G; i > 0; i--) { h.trailing += sTrail[j0 + i - 1]; if (sCnt[j0 + i - 1]) break; }
-                hdrAll[(size_t)slot * ZS_WALK_RANGES + g] = h;
+                zs_out_range_hdr(hdrAll, zs_out_range(slot, g)) = h;
             }
         }
     }

@@ -5,6 +5,7 @@
 // Single translation unit: the kernel sources are included so that launches and kernels share one code object.  Every file includes what
 // it uses; the list is the library's table of contents.
 #include "zsmi_device.h"          // format constants, block / unit / sequence records, unaligned loads and stores
+#include "zsmi_scratch.h"         // the scratch layouts: the table of the compress buffers, the slot accessors and borrowings of both pipelines, DecLists
 #include "zsmi_wave.h"            // device primitives of more than one kernel file: wave_*, zs_block_copy, rd16/24/32, xxh64_quad
 #include "zsmi_frame.h"           // the readers of the container headers (frame, block, literals section, stream split): device and host
 #include "lz_kernels.hip"         // encoder, LZ stage: k_lz_candidates, k_lz_walk, k_lz_stitch, k_lz_dict_tables
@@ -206,14 +207,12 @@ static int loadDict(zsmi_ctx *c, const void *dDict, size_t dictSize, ZsCompressD
 // ---------------------------------------------------------------------------------------------
 // compress
 // ---------------------------------------------------------------------------------------------
-// the scratch of a sub-batch of cap blocks
+// the scratch of a sub-batch of cap blocks: every buffer of ZS_SCRATCH_TABLE (zsmi_scratch.h) at cap slots and its fixed tail
 bool zsmi_ctx::Scratch::reserve(uint32_t cap)
 {
-    return dDist.reserve((size_t)cap * ZS_BLOCK_MAX * 2 + 256) && dDistHi.reserve((size_t)cap * (ZS_BLOCK_MAX / 8) + 256) && dCand.reserve((size_t)cap * 2 * sizeof(uint32_t) + 64) &&
-           dRecs.reserve(((size_t)cap * (ZS_BLOCK_MAX / 4) + 64) * sizeof(uint2)) && dRes.reserve((size_t)cap * ZS_RES_PER_BLOCK * sizeof(uint4) + ((size_t)8 << 20)) &&
-           dSeqs.reserve((size_t)cap * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE * sizeof(ZsSeqRec)) && dHdrs.reserve((size_t)cap * ZS_WALK_RANGES * sizeof(ZsRangeHdr)) &&
-           dLits.reserve((size_t)cap * (ZS_BLOCK_MAX + 64)) && dStreams.reserve((size_t)cap * 4 * ZS_STREAM_STRIDE) && dLitSec.reserve((size_t)cap * ZS_LITSEC_STRIDE) &&
-           dSeqSec.reserve((size_t)cap * ZS_SEQSEC_STRIDE) && dMetas.reserve((size_t)cap * sizeof(ZsBlockMeta));
+    for (int i = 0; i < kZsScratchCount; i++)
+        if (!buf[i].reserve((size_t)cap * kZsScratchRows[i].slotBytes + kZsScratchRows[i].tailBytes)) return false;
+    return true;
 }
 // The plan of a call: chunks -> blocks (ZsChunkDesc, ZsBlockDesc) and LZ units, built on the host and copied to the device.  It is reused
 // while the chunk layout repeats (steady-state batches; compared in place: such a call allocates and copies nothing).  A dictionary call
@@ -365,18 +364,18 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
             const LzKernel<CandFn> &K = shape.cand[k];
             const bool p = k == kUnitsPfx;
             if (units[k].n)
-                LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, (uint16_t *)S.dDist.p,
-                       (uint8_t *)S.dDistHi.p, (uint32_t *)S.dCand.p, p ? dImg : nullptr, p ? pre.size : 0u);
+                LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, S.dist(),
+                       S.distHi(), S.cand(), p ? dImg : nullptr, p ? pre.size : 0u);
         }
         for (int k = 0; k < 3; k++) {
             const LzKernel<WalkFn> &K = shape.walk[k];
             const bool p = k == kUnitsPfx;
             if (units[k].n)
-                LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, (const uint16_t *)S.dDist.p,
-                       (const uint8_t *)S.dDistHi.p, (uint2 *)S.dRecs.p, cap * (ZS_BLOCK_MAX / 4), (uint4 *)S.dRes.p, shape.walkLog, (const uint32_t *)S.dCand.p,
+                LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, S.dist(),
+                       S.distHi(), S.recs(), zs_walk_records_end(cap), S.res(), shape.walkLog, S.cand(),
                        p ? pre.d : nullptr, p ? pre.size : 0u);
         }
-        LAUNCH(c, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, (const uint2 *)S.dRecs.p, (const uint4 *)S.dRes.p, (ZsSeqRec *)S.dSeqs.p, (ZsRangeHdr *)S.dHdrs.p, shape.walkLog);
+        LAUNCH(c, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, S.recs(), S.res(), S.seqs(), S.hdrs(), shape.walkLog);
         if (c->stopAfterWalk) continue;
         // The entropy stage.  Sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and
         // reads the sequence sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  Every
@@ -386,18 +385,18 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
         const auto litKernel = cdt ? k_encode_literals<true> : k_encode_literals<false>;
         const uint4 rep = dict ? make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u) : make_uint4(1u, 4u, 8u, 0u);
         const uint32_t dictID = dict ? dict->dictID : 0u;
-        LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, (const ZsSeqRec *)S.dSeqs.p,
-               (const ZsRangeHdr *)S.dHdrs.p, (uint8_t *)S.dSeqSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopSeq, (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p,
-               (uint2 *)S.dDist.p, rep, cdt);
+        LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, S.seqs(),
+               S.hdrs(), S.seqSec(), S.metas(), c->stopSeq, S.lits(), S.streams(),
+               S.distAsPackRecords(), rep, cdt);
         if (dStats)                                                  // (the codes it reads are in the literal buffers until the literals kernel)
-            LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p,
-                   (const ZsRangeHdr *)S.dHdrs.p, (const uint8_t *)S.dLits.p, dStats);
-        LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, (const ZsSeqRec *)S.dSeqs.p, (const ZsRangeHdr *)S.dHdrs.p,
-               (uint8_t *)S.dLits.p, (uint8_t *)S.dStreams.p, (uint8_t *)S.dLitSec.p, (ZsBlockMeta *)S.dMetas.p, c->stopLit,
-               dChunks, (const uint8_t *)S.dSeqSec.p, (uint8_t *)dDst, dDstSizes, dictID, cdt);
+            LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(),
+                   S.hdrs(), S.lits(), dStats);
+        LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(), S.hdrs(),
+               S.lits(), S.streams(), S.litSec(), S.metas(), c->stopLit,
+               dChunks, S.seqSec(), (uint8_t *)dDst, dDstSizes, dictID, cdt);
         if (P.maxChunkBlocks > 1)                                    // chunks of several blocks
             LAUNCH(c, "k_assemble_frames", k_assemble_frames, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, dChunks,
-                   (const ZsBlockDesc *)P.dBlocks.p, (const ZsBlockMeta *)S.dMetas.p, (const uint8_t *)S.dLitSec.p, (const uint8_t *)S.dSeqSec.p, block0,
+                   (const ZsBlockDesc *)P.dBlocks.p, S.metas(), S.litSec(), S.seqSec(), block0,
                    (uint8_t *)dDst, dDstSizes, chunk0, dictID);
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
@@ -500,29 +499,19 @@ struct DecodePlan {
     uint32_t blockCap, litStride, litCap, seqCap;     // a slot: the bytes its block may regenerate, its literal stride and bytes, its sequences
     uint32_t pool, cap;                               // wavefronts of the general kernel's pool (whole workgroups); items in flight
 };
-// dSeqLists, in 32-bit words (slots = cap * maxBlocks; "-": unused):
-//   [queue][left count][-][-][class count 0][class count 1][class list 0: slots][class list 1: slots][-][-][left list: cap]
-// k_dec_prep, k_dec_sequences and k_dec_entropy are handed the words from kClassCounts on and index them themselves (decode_fast.hip: k_dec_prep's
-// seqLists[cls] and seqLists[2 + cls * cap * maxBlocks + at]; zs_dec_sequences_body's seqLists[LOG9 ? 1 : 0] and seqLists + 2 + (LOG9 ? cap * nBlk : 0)).
-// k_dec_collect fills the left list and its count; k_decode_frames takes the queue, the count and the list (decode_kernels.hip).  Without the fast
-// path only the queue and the left count are used.
-struct DecLists {
-    static constexpr size_t kQueue = 0, kLeftCount = 1, kClassCounts = 4, kClassLists = kClassCounts + 2;   // (the fast path zeroes every word in front of kClassLists)
-    static size_t leftList(size_t slots) { return kClassLists + 2 * slots + 2; }
-};
 // Every decode scratch buffer and its bytes for a plan: the one statement of the sizes, which the budget (planDecode), the reservation and
 // zsmi_decodeScratchBytes go through.  0: a buffer the plan does not use (the fast path's, on a call without it), left as it is.
 template <class F>
 void zsmi_ctx::DecodeScratch::each(const DecodePlan &p, F f)
 {
     const size_t items = p.fast ? p.cap : 0, slots = items * p.maxBlocks;
-    f(dPoolLit, (size_t)p.pool * ZS_DEC_LITBUF);
+    f(dPoolLit, p.pool * ZsDecSlotBytes::poolLit);
     f(dLitScratch, slots * p.litStride);
     f(dFastDesc, items * p.descSlots * sizeof(ZsFastDesc));
-    f(dHufTabs, slots * ZS_FAST_HUFTAB_BYTES);
-    f(dSeqTabs, slots * ZS_FAST_SEQTAB_BYTES);
-    f(dSeqOut, slots * p.seqCap * sizeof(ZsFastSeq));
-    f(dSeqLists, (DecLists::leftList(slots) + items) * sizeof(uint32_t));
+    f(dHufTabs, slots * ZsDecSlotBytes::hufTabs);
+    f(dSeqTabs, slots * ZsDecSlotBytes::seqTabs);
+    f(dSeqOut, slots * p.seqCap * ZsDecSlotBytes::seqOut);
+    f(dSeqLists, DecLists::words(slots, items) * sizeof(uint32_t));
 }
 size_t zsmi_ctx::DecodeScratch::held() { size_t s = 0; each(DecodePlan(), [&](DevBuf &b, size_t) { s += b.cap; }); return s; }
 // give back what an earlier, larger call left behind: a buffer more than twice (and 256 MiB) beyond this call's need is released first
@@ -619,21 +608,21 @@ static void launchFastDecode(zsmi_ctx *c, const DecodePlan &p, const DecodeShape
 {
     zsmi_ctx::DecodeScratch &S = c->dec;
     const uint32_t mb = p.maxBlocks;
-    ZsFastDesc *dD = (ZsFastDesc *)S.dFastDesc.p;
+    ZsFastDesc *dD = S.fastDesc();
     LAUNCH(c, "k_dec_prep", (k_dec_prep<ZS_DEC_GROUP, DD>), dim3((cnt + ZS_DEC_GROUP - 1) / ZS_DEC_GROUP), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, dD,
-           (uint8_t *)S.dHufTabs.p, (uint8_t *)S.dSeqTabs.p, p.cap, mb, classes, p.litCap, p.seqCap, sel);
+           S.hufTabs(), S.seqTabs(), p.cap, mb, classes, p.litCap, p.seqCap, sel);
     // every block index of the items in one launch per kernel class (the grid: mb runs of the items' groups; a wavefront whose items have no such
     // block leaves at once)
     const uint32_t gH0 = ((cnt + ZS_FAST_GROUP - 1) / ZS_FAST_GROUP) * mb, gH1 = ((cnt + 7) / 8) * mb;
     const uint32_t gS0 = ((cnt + ZS_FAST_SEQGROUP_SMALL - 1) / ZS_FAST_SEQGROUP_SMALL) * mb, gS1 = ((cnt + 3) / 4) * mb;
     if (shape.fused) {
         // the four entropy launches as one (k_dec_entropy), the 2.5 KiB sequence class at 4 items a wavefront as below
-        LAUNCH(c, "k_dec_entropy", k_dec_entropy<DD>, dim3(gH0 + gH1 + gS0 + gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p,
-               (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.litStride, p.seqCap, gH0, gH1, gS0, sel);
+        LAUNCH(c, "k_dec_entropy", k_dec_entropy<DD>, dim3(gH0 + gH1 + gS0 + gS1), dim3(64), 0, src, dI, cnt, dD, S.hufTabs(), S.litScratch(),
+               S.seqTabs(), S.seqOut(), mb, p.cap, (const uint32_t *)classes, p.litStride, p.seqCap, gH0, gH1, gS0, sel);
     } else {
-        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<false, ZS_FAST_GROUP, DD>), dim3(gH0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride, sel);
-        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<true, 8u, DD>), dim3(gH1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dHufTabs.p, (uint8_t *)S.dLitScratch.p, mb, p.cap, p.litStride, sel);
-        LAUNCH(c, "k_dec_sequences", (k_dec_sequences<false, ZS_FAST_SEQGROUP_SMALL>), dim3(gS0), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
+        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<false, ZS_FAST_GROUP, DD>), dim3(gH0), dim3(64), 0, src, dI, cnt, dD, S.hufTabs(), S.litScratch(), mb, p.cap, p.litStride, sel);
+        LAUNCH(c, "k_dec_huffman", (k_dec_huffman<true, 8u, DD>), dim3(gH1), dim3(64), 0, src, dI, cnt, dD, S.hufTabs(), S.litScratch(), mb, p.cap, p.litStride, sel);
+        LAUNCH(c, "k_dec_sequences", (k_dec_sequences<false, ZS_FAST_SEQGROUP_SMALL>), dim3(gS0), dim3(64), 0, src, dI, cnt, dD, S.seqTabs(), S.seqOut(),
                mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, 0xFFFFFFFFu);
         // the 2.5 KiB table class (blocks of > 2048 sequences: sources, tables, binaries at 32 KiB; the 64 KiB blocks of 128 KiB frames).  How many blocks of a call
         // are in it only the device knows (k_dec_prep's list), and it decides the shape: 16 items a wavefront when the class holds most of a large call (the
@@ -641,13 +630,13 @@ static void launchFastDecode(zsmi_ctx *c, const DecodePlan &p, const DecodeShape
         // when it is a fraction of it (libzstd's 32 KiB frames: 9 % of the blocks; fewer, emptier wavefronts finish sooner: 3.8 vs 5.2 ms) or the call is small.
         // Both shapes are launched; each looks at the list's length and leaves at once when the other one serves it.
         LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, ZS_FAST_SEQGROUP>), dim3(((cnt + ZS_FAST_SEQGROUP - 1) / ZS_FAST_SEQGROUP) * mb), dim3(64), 0, src, dI, cnt, dD,
-               (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p, mb, p.cap, (const uint32_t *)classes, p.seqCap, ZS_FAST_SEQGROUP_MANY, 0xFFFFFFFFu);
-        LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, 4u>), dim3(gS1), dim3(64), 0, src, dI, cnt, dD, (const uint8_t *)S.dSeqTabs.p, (ZsFastSeq *)S.dSeqOut.p,
+               S.seqTabs(), S.seqOut(), mb, p.cap, (const uint32_t *)classes, p.seqCap, ZS_FAST_SEQGROUP_MANY, 0xFFFFFFFFu);
+        LAUNCH(c, "k_dec_sequences", (k_dec_sequences<true, 4u>), dim3(gS1), dim3(64), 0, src, dI, cnt, dD, S.seqTabs(), S.seqOut(),
                mb, p.cap, (const uint32_t *)classes, p.seqCap, 0u, ZS_FAST_SEQGROUP_MANY);
     }
     const auto execute = shape.executeWaves == 6 ? k_dec_execute<4, 6, DD> : (shape.executeWaves == 8 ? k_dec_execute<4, 8, DD> : k_dec_execute<4, 7, DD>);
-    LAUNCH(c, "k_dec_execute", execute, dim3((cnt + 3) / 4), dim3(256), 0, src, dI, cnt, dD, (ZsFastSeq *)S.dSeqOut.p,
-           (uint8_t *)S.dLitScratch.p, (uint8_t *)dDst, dDstSizes, p.cap, p.descSlots, p.litStride, p.seqCap, sel);
+    LAUNCH(c, "k_dec_execute", execute, dim3((cnt + 3) / 4), dim3(256), 0, src, dI, cnt, dD, S.seqOut(),
+           S.litScratch(), (uint8_t *)dDst, dDstSizes, p.cap, p.descSlots, p.litStride, p.seqCap, sel);
     LAUNCH(c, "k_dec_checksum", k_dec_checksum, dim3((cnt + 15) / 16), dim3(64), 0, dI, cnt, (const ZsFastDesc *)dD, (const uint8_t *)dDst, dDstSizes);
 }
 
@@ -676,8 +665,8 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
     if (!S.reserve(p)) return ZSMI_error_memory_allocation;
     const uint8_t *src = (const uint8_t *)dSrc;
     const uint32_t mb = p.maxBlocks;
-    ZsFastDesc *dD = (ZsFastDesc *)S.dFastDesc.p;
-    uint32_t *lists = (uint32_t *)S.dSeqLists.p, *classes = lists + DecLists::kClassCounts, *leftCount = lists + DecLists::kLeftCount;
+    ZsFastDesc *dD = S.fastDesc();
+    uint32_t *lists = S.seqLists(), *classes = DecLists::classes(lists), *leftCount = DecLists::leftCount(lists);
     for (uint32_t i0 = 0; i0 < n; i0 += p.cap) {
         const uint32_t cnt = std::min(p.cap, n - i0);
         const ZsDecItem *dI = (const ZsDecItem *)c->dItems.p + i0;
@@ -690,13 +679,13 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
             if (useDict) launchFastDecode<true>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, sel);
             else launchFastDecode<false>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, sel);
             // the items the fast path did not finish, listed for the general kernel
-            left = lists + DecLists::leftList((size_t)p.cap * mb);
+            left = DecLists::leftList(lists, (size_t)p.cap * mb);
             LAUNCH(c, "k_dec_collect", k_dec_collect, dim3((cnt + 255) / 256), dim3(256), 0, &dD->fast, (uint32_t)(sizeof(ZsFastDesc) / sizeof(uint32_t)), cnt, left, leftCount);
         } else if (hipMemsetAsync(lists, 0, (DecLists::kLeftCount + 1) * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
         // the general kernel: a pool of wavefronts over a queue - of every item, or (behind the fast path) of the list of the items it left
         LAUNCH(c, useDict ? "k_decode_frames_dict" : "k_decode_frames", useDict ? (k_decode_frames<ZS_DEC_GROUP, true>) : (k_decode_frames<ZS_DEC_GROUP, false>),
-               dim3(shape.poolWgs), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, (uint8_t *)dDst, dDstSizes + i0, (uint8_t *)S.dPoolLit.p, (const uint32_t *)left,
-               (const uint32_t *)leftCount, sel, lists + DecLists::kQueue);
+               dim3(shape.poolWgs), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, (uint8_t *)dDst, dDstSizes + i0, S.poolLit(), (const uint32_t *)left,
+               (const uint32_t *)leftCount, sel, DecLists::queue(lists));
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
@@ -1148,20 +1137,41 @@ extern "C" size_t zsmi_decompress_usingDDictSet(void *dst, size_t dstCapacity, c
 }
 
 #ifdef ZSMI_DEBUG_HOOKS
-// ---- test hook (not in include/zsmi.h): copy a scratch buffer of the last compress sub-batch to the host.
-//      which: 0 dist (u16 x 65536 per block), 1 sequences (ZsSeqRec x 8 x 2048 per block), 2 range headers, 3 block results ----
+// ---- test hooks (not in include/zsmi.h) ----
 // words of a ZsFastDesc, and the word index of its fields `fast`, `why`, `nbSeq`, `litType`, `hufLog` (tools/fastpath_check.py, tools/dec_why.py)
 extern "C" void zsmi_dbg_descLayout(uint32_t out[6])
 {
     out[0] = (uint32_t)(sizeof(ZsFastDesc) / 4); out[1] = (uint32_t)(offsetof(ZsFastDesc, fast) / 4); out[2] = (uint32_t)(offsetof(ZsFastDesc, why) / 4);
     out[3] = (uint32_t)(offsetof(ZsFastDesc, nbSeq) / 4); out[4] = (uint32_t)(offsetof(ZsFastDesc, litType) / 4); out[5] = (uint32_t)(offsetof(ZsFastDesc, hufLog) / 4);
 }
-extern "C" int zsmi_dbg_copyScratch(zsmi_ctx *c, int which, void *hostDst, size_t bytes)
+// The scratch buffers a tool can name: the twelve of the compress side by their names in ZS_SCRATCH_TABLE (zsmi_scratch.h), and the decode
+// side's whose stride no plan chooses.  c: nullptr to ask for the layout alone.
+static const ZsScratchRow *dbgScratch(zsmi_ctx *c, const char *name, DevBuf **buf)
 {
-    if (!c) return -1;
+    static const ZsScratchRow dec[] = { { "poolLit", ZsDecSlotBytes::poolLit, 0 }, { "hufTabs", ZsDecSlotBytes::hufTabs, 0 }, { "seqTabs", ZsDecSlotBytes::seqTabs, 0 },
+                                        { "fastDesc", sizeof(ZsFastDesc), 0 } };
+    if (!name) return nullptr;
+    for (int i = 0; i < kZsScratchCount; i++)
+        if (!strcmp(name, kZsScratchRows[i].name)) { if (c) *buf = &c->scratch.buf[i]; return &kZsScratchRows[i]; }
+    for (int i = 0; i < 4; i++)
+        if (!strcmp(name, dec[i].name)) { if (c) *buf = i == 0 ? &c->dec.dPoolLit : i == 1 ? &c->dec.dHufTabs : i == 2 ? &c->dec.dSeqTabs : &c->dec.dFastDesc; return &dec[i]; }
+    return nullptr;
+}
+// out[0]: bytes a slot of the buffer (compress: a block; poolLit: a wavefront; hufTabs, seqTabs: a block slot; fastDesc: a descriptor),
+// out[1]: the fixed bytes behind the slots.  Host only.  0, or -1 for a name that is no buffer's.
+extern "C" int zsmi_dbg_scratchLayout(const char *name, uint64_t out[2])
+{
+    const ZsScratchRow *row = dbgScratch(nullptr, name, nullptr);
+    if (!row) return -1;
+    out[0] = row->slotBytes; out[1] = row->tailBytes;
+    return 0;
+}
+// copies the first `bytes` of the named buffer, as the context's last call left it, to the host (-1: no context or no such buffer)
+extern "C" int zsmi_dbg_copyScratch(zsmi_ctx *c, const char *name, void *hostDst, size_t bytes)
+{
+    DevBuf *b = nullptr;
+    if (!c || !dbgScratch(c, name, &b)) return -1;
     (void)hipStreamSynchronize(c->stream);
-    zsmi_ctx::Scratch &S = c->scratch;
-    DevBuf *b = which == 0 ? &S.dDist : which == 1 ? &S.dSeqs : which == 2 ? &S.dHdrs : which == 4 ? &S.dDistHi : which == 7 ? &S.dRecs : which == 8 ? &S.dRes : which == 5 ? &c->dec.dPoolLit : which == 9 ? &c->dec.dHufTabs : which == 10 ? &c->dec.dFastDesc : &S.dMetas;
     if (bytes > b->cap) return -2;
     return hipMemcpy(hostDst, b->p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/zsmi.h"
 #include "zsmi_device.h"
+#include "zsmi_scratch.h"         // what the scratch buffers hold: the table Scratch is made of
 
 #include <cstring>
 #include <vector>
@@ -67,7 +68,11 @@ struct zsmi_ctx {
     // compress workspace: the plan of the call's layout and the scratch of a sub-batch (its sizes: the compress section of zsmi_api.hip)
     CompressPlan plan;
     struct Scratch {
-        DevBuf dDist, dDistHi, dCand, dRecs, dRes, dSeqs, dHdrs, dLits, dStreams, dLitSec, dSeqSec, dMetas;
+        DevBuf buf[kZsScratchCount];           // a buffer a row of ZS_SCRATCH_TABLE (zsmi_scratch.h), and a typed getter by the row's name
+        #define X(name, T, perSlot, tail) T *name() const { return (T *)buf[kZsScratch_##name].p; }
+        ZS_SCRATCH_TABLE(X)
+        #undef X
+        uint2 *distAsPackRecords() const { return (uint2 *)buf[kZsScratch_dist].p; }      // (lent to k_encode_sequences: zs_dist_lend_pack_records)
         bool reserve(uint32_t cap);            // cap: blocks of a sub-batch
     } scratch;
     DevBuf dDictImg;                       // a _usingDict call's candidate-table images of the prefix (a digested dictionary holds its own)
@@ -82,6 +87,13 @@ struct zsmi_ctx {
         DevBuf dPoolLit;                                                 // the general kernel's literal buffers: one per wavefront of its pool
         DevBuf dLitScratch, dFastDesc, dHufTabs, dSeqTabs, dSeqOut;      // the fast path's block slots: literals, descriptors, tables, sequences
         DevBuf dSeqLists;                                                // the general kernel's queue, the blocks of each table class, the items left (DecLists)
+        uint8_t *poolLit() const { return (uint8_t *)dPoolLit.p; }
+        uint8_t *litScratch() const { return (uint8_t *)dLitScratch.p; }
+        ZsFastDesc *fastDesc() const { return (ZsFastDesc *)dFastDesc.p; }
+        uint8_t *hufTabs() const { return (uint8_t *)dHufTabs.p; }
+        uint8_t *seqTabs() const { return (uint8_t *)dSeqTabs.p; }
+        ZsFastSeq *seqOut() const { return (ZsFastSeq *)dSeqOut.p; }
+        uint32_t *seqLists() const { return (uint32_t *)dSeqLists.p; }
         template <class F> void each(const DecodePlan &p, F f);
         size_t held();
         bool reserve(const DecodePlan &p);
