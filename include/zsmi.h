@@ -133,6 +133,41 @@ int zsmi_compressBatchHost_usingCDict(zsmi_ctx *ctx, const void *src, const uint
                                       uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, const zsmi_cdict *cd);
 size_t zsmi_compress_usingCDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd);
 
+/* ------------------------------------------------------------------------------------------
+ * CDict sets: a read-only device table of digested compression dictionaries.  A compress call that takes a set gives chunk i the member
+ * dictIndex[i] names - on the device, inside the kernels - so one call compresses a batch whose chunks use different dictionaries (the
+ * frames a DDict set, below, decodes in one call).
+ *
+ * The contract: frame i is, byte for byte, the frame zsmi_compressBatchDevice_usingCDict gives chunk i with member dictIndex[i]; for
+ * ZSMI_DICT_NONE or an empty member, the frame zsmi_compressBatchDevice gives at `level` - whatever the neighbouring chunks use.
+ * What cds[] may be: formatted dictionaries, raw content, empty CDicts (no dictionary for the chunks that pick them), every one digested on
+ * ctx's device for `level` (the images in a CDict are built for one level's parse).  Two members may carry one ID and one CDict may stand
+ * at two indices: the caller names the dictionary, not the ID.  n may be 0.
+ * Creation and lifetime: every check runs on the host before anything touches the device, in this order - a NULL ctx: init_missing; more
+ * than 4096 members: parameter_outOfBound; NULL cds with n > 0: parameter_unsupported; then each entry of cds[] in turn: a NULL entry, one
+ * of another device than ctx's, one of another level: parameter_unsupported.  The set copies nothing from its members: it holds one device
+ * table of {prefix pointer and size, candidate-table images, entropy tables, recent offsets, dictID} in the order of cds[], uploaded on
+ * ctx's stream and waited for, once.  The members must outlive the set, and the set the work queued with it (free it after zsmi_sync).
+ * Read-only after creation: any context of the same device may use it.  NULL on failure, with the code in *err if err != NULL.
+ * ------------------------------------------------------------------------------------------ */
+#define ZSMI_DICT_NONE 0xFFFFFFFFu
+typedef struct zsmi_cdictSet zsmi_cdictSet;
+zsmi_cdictSet *zsmi_createCDictSet(zsmi_ctx *ctx, const zsmi_cdict *const *cds, uint32_t n, int level, int *err);
+void zsmi_freeCDictSet(zsmi_cdictSet *set);                     /* NULL: nothing */
+uint32_t zsmi_sizeofCDictSetMembers(const zsmi_cdictSet *set);  /* n; 0 for NULL */
+/* zsmi_compressBatchDevice at the set's level; chunk i with member dictIndex[i] (a host array of n entries, as the offsets), or with no
+ * dictionary for ZSMI_DICT_NONE.  Checked on the host first - on failure nothing is queued or written and the code is returned: a NULL ctx:
+ * init_missing; a NULL dictIndex with n > 0: GENERIC; an index that is neither ZSMI_DICT_NONE nor below the number of members:
+ * parameter_outOfBound; a set of another device: parameter_unsupported.  set == NULL: zsmi_compressBatchDevice at level 3 (dictIndex is not
+ * read).  Like _usingCDict it only queues work: no device-to-host copy, no wait for the stream beyond the plan's own for a new layout. */
+int zsmi_compressBatchDevice_usingCDictSet(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                           uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes,
+                                           const zsmi_cdictSet *set, const uint32_t *dictIndex);
+/* the host-buffer form */
+int zsmi_compressBatchHost_usingCDictSet(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                         uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes,
+                                         const zsmi_cdictSet *set, const uint32_t *dictIndex);
+
 /* Asynchronous on the context's stream.  Each frame i = src[srcOffsets[i] .. +srcSizes[i]) may hold several
  * concatenated / skippable frames (same rules as zsmi_decompress); dstCaps[i] is the room at dstOffsets[i]. */
 int zsmi_decompressBatchDevice(zsmi_ctx *ctx, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,

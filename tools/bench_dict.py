@@ -23,13 +23,16 @@ what a caller had to do without one - K zsmi_decompressBatchDevice_usingDDict ca
 in the same process, on the same frames.  set_gib_s / seq_gib_s: the median of --repeats timings of --steps calls (of K calls each), with the
 slowest and fastest as rates (*_min, *_max) and their spread; set_over_seq the ratio of the medians; slower_beyond_spreads says that the set
 call is slower by more than both spreads together.  The K dictionaries are the trained ones of --classes in turn, each under an ID of its own
-(the fixtures hold five: a dictionary met again is another DDict with its own device image and ID, over that class's next chunks)."""
+(the fixtures hold five: a dictionary met again is another DDict with its own device image and ID, over that class's next chunks).
+--cdict-set K: the same for the compress side (one JSON line per chunk size of 1, 4 and 64 KiB): one 32 MB call of chunks, chunk i with
+dictionary i % K, through a CompressionDictSet (zsmi_compressBatchDevice_usingCDictSet) against K zsmi_compressBatchDevice_usingCDict calls
+one after the other, each over its dictionary's chunks, in the same process; both outputs are compared byte for byte.  Fields as --dict-set's."""
 import argparse, ctypes, json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _data as D, _oracle as O, _corpus as C
-from zstandard_amd import BatchCodec, CompressionDict, DecompressionDict, DecompressionDictSet, _lib
+from zstandard_amd import BatchCodec, CompressionDict, CompressionDictSet, DecompressionDict, DecompressionDictSet, _lib
 
 FIXC = os.path.join(ROOT, "tests", "golden", "libzstd_fixtures_dict_compress.npz")
 
@@ -104,6 +107,19 @@ def loader_leg(a):
     print(json.dumps(rec), flush=True)
 
 
+def interleaved_chunks(classes, K, cs):
+    """(n, per, an (n, cs) array): per chunks of cs bytes for each of K dictionaries - item i holds chunk i // K of dictionary i % K, cut from
+    its class's data (a class met again: its next chunks) - 32 MB in all"""
+    per = (32 << 20) // cs // K; n = per * K
+    rounds = (K + len(classes) - 1) // len(classes)
+    data = {c: np.frombuffer(class_bytes(c, rounds * per * cs), dtype=np.uint8) for c in classes[:min(K, len(classes))]}
+    src = np.empty((n, cs), dtype=np.uint8)
+    for k in range(K):
+        at = (k // len(classes)) * per * cs
+        src[k::K] = data[classes[k % len(classes)]][at:at + per * cs].reshape(per, cs)
+    return n, per, src
+
+
 def dict_set_leg(a):
     K = a.dict_set
     fix = np.load(FIXC)
@@ -117,13 +133,7 @@ def dict_set_leg(a):
     dset = DecompressionDictSet(bc, [dds[k] for k in order])
     assert len(dset) == K
     for cs in (1024, 4096, 65536):
-        per = (32 << 20) // cs // K; n = per * K
-        rounds = (K + len(classes) - 1) // len(classes)
-        data = {c: np.frombuffer(class_bytes(c, rounds * per * cs), dtype=np.uint8) for c in classes[:min(K, len(classes))]}
-        src = np.empty((n, cs), dtype=np.uint8)
-        for k in range(K):                                                # item i holds chunk i // K of dictionary i % K
-            at = (k // len(classes)) * per * cs
-            src[k::K] = data[classes[k % len(classes)]][at:at + per * cs].reshape(per, cs)
+        n, per, src = interleaved_chunks(classes, K, cs)                  # item i holds chunk i // K of dictionary i % K
         dsrc = torch.from_numpy(src.reshape(-1)).to(dev)
         off = np.arange(n, dtype=np.uint64) * cs; sz = np.full(n, cs, dtype=np.uint32); caps = sz.copy()
         bound = int(Z.zsmi_compressBound(cs)); doff = np.arange(n, dtype=np.uint64) * bound
@@ -176,6 +186,74 @@ def dict_set_leg(a):
         d.close()
 
 
+def cdict_set_leg(a):
+    K = a.cdict_set
+    fix = np.load(FIXC)
+    classes = a.classes.split(",")
+    dev = torch.device("cuda:0")
+    bc = BatchCodec(device=0); Z = _lib.lib()
+    dics = [fix["trained_" + classes[k % len(classes)]].tobytes() for k in range(K)]
+    dics = [d[:4] + (1000 + k).to_bytes(4, "little") + d[8:] for k, d in enumerate(dics)]
+    cds = [CompressionDict(bc, d, 3) for d in dics]
+    cset = CompressionDictSet(bc, cds, 3)
+    assert len(cset) == K
+    for cs in (1024, 4096, 65536):
+        n, per, src = interleaved_chunks(classes, K, cs)
+        dsrc = torch.from_numpy(src.reshape(-1)).to(dev)
+        off = np.arange(n, dtype=np.uint64) * cs; sz = np.full(n, cs, dtype=np.uint32)
+        index = (np.arange(n) % K).astype(np.uint32)
+        bound = int(Z.zsmi_compressBound(cs)); doff = np.arange(n, dtype=np.uint64) * bound
+        sub = [tuple(np.ascontiguousarray(x[k::K]) for x in (off, sz, doff)) for k in range(K)]
+        outs = {}
+
+        def run_set(ddst, dsz):
+            bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), cdict_set=cset, dict_index=index)
+
+        def run_seq(ddst, dsz):                                       # (chunk i's size lands at i % K * per + i // K)
+            for k in range(K):
+                bc.compress_device(dsrc.data_ptr(), sub[k][0], sub[k][1], ddst.data_ptr(), sub[k][2], dsz.data_ptr() + 4 * k * per, cdict=cds[k])
+        rec = {"cdict_set": K, "chunk": cs, "chunks": n, "library": Z.zsmi_versionString().decode(), "steps": a.steps, "repeats": a.repeats}
+        gib = n * cs / 2**30
+        for tag, run in (("set", run_set), ("seq", run_seq)):
+            ddst = torch.zeros(n * bound, dtype=torch.uint8, device=dev); dsz = torch.zeros(n, dtype=torch.int32, device=dev)
+            for _ in range(2):
+                run(ddst, dsz)
+            times = []
+            for _ in range(a.repeats):
+                bc.sync(); t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    run(ddst, dsz)
+                bc.sync(); times.append((time.perf_counter() - t0) / a.steps)
+            dt = float(np.median(times))
+            rec[tag + "_gib_s"] = round(gib / dt, 2); rec[tag + "_min"] = round(gib / max(times), 2); rec[tag + "_max"] = round(gib / min(times), 2)
+            rec[tag + "_spread"] = round((max(times) - min(times)) / dt, 3)
+            if a.kernels:
+                bc.enable_timing(True); run(ddst, dsz); bc.sync()
+                rec["kernels_ms_" + tag] = {k2: round(v[0] * 1e3, 3) for k2, v in bc.kernel_times().items()}
+                bc.enable_timing(False)
+            sizes = dsz.cpu().numpy().view(np.uint32)
+            if tag == "seq":
+                sizes = sizes.reshape(K, per).T.reshape(-1)
+            assert (sizes < 0xFFFFFF88).all()
+            outs[tag] = (ddst, sizes.copy())
+            del dsz
+        # byte for byte: the sizes, and every frame (the slots were zeroed, and a call writes a chunk's frame only)
+        assert (outs["set"][1] == outs["seq"][1]).all(), ("cdict-set leg: sizes differ", cs)
+        assert torch.equal(outs["set"][0], outs["seq"][0]), ("cdict-set leg: frames differ", cs)
+        host = outs["set"][0][:min(n, 64) * bound].cpu().numpy()
+        for i in (0, min(n, 64) - 1):                                 # spot check under oracle D
+            f = host[int(doff[i]):int(doff[i]) + int(outs["set"][1][i])].tobytes()
+            assert O.decompress_using_dict(f, cs, dics[i % K]) == src[i].tobytes()
+        rec["ratio"] = round(n * cs / float(outs["set"][1].sum()), 4)
+        rec["set_over_seq"] = round(rec["set_gib_s"] / rec["seq_gib_s"], 3)
+        rec["slower_beyond_spreads"] = bool(rec["set_over_seq"] < 1.0 - rec["set_spread"] - rec["seq_spread"])
+        print(json.dumps(rec), flush=True)
+        del outs, dsrc
+    bc.sync(); cset.close()
+    for cd in cds:
+        cd.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bytes", type=int, default=64 << 20, help="input bytes per class")
@@ -187,9 +265,12 @@ def main():
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--loader", action="store_true", help="only the cost of loading a dictionary at each entry point that reads its bytes")
     ap.add_argument("--dict-set", type=int, default=0, metavar="K", help="only the decode of one 32 MB call whose frames name K dictionaries: a DDict set against K _usingDDict calls")
+    ap.add_argument("--cdict-set", type=int, default=0, metavar="K", help="only the compress of one 32 MB call whose chunks use K dictionaries: a CDict set against K _usingCDict calls")
     a = ap.parse_args()
     if a.loader:
         return loader_leg(a)
+    if a.cdict_set:
+        return cdict_set_leg(a)
     if a.dict_set:
         return dict_set_leg(a)
     fix = np.load(FIXC)

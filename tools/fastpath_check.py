@@ -5,7 +5,8 @@ descriptors (ZsFastDesc.fast) are read back.  A shape that silently falls back t
 only this count shows it (ELF-class frames did so for two rounds).  Rows "ddict ..." are dictionary frames decoded with a DecompressionDict
 (zsmi_createDDict): own CDict frames with a trained dictionary, own frames with a raw-content one, libzstd's with the trained one.  Rows
 "ddict set ..." are mixed batches through a DecompressionDictSet (zsmi_createDDictSet): own CDict frames of three trained dictionaries,
-interleaved, and a committed libzstd frame of a fourth - every frame decoded with the dictionary it names.
+interleaved, and a committed libzstd frame of a fourth - every frame decoded with the dictionary it names.  Rows "cdict set -> ddict set ..."
+are such batches compressed in one call through a CompressionDictSet (zsmi_createCDictSet) first.
 Prints one JSON object: shape -> [items on the fast path, items]."""
 import os; os.environ["ZSMI_DEBUG_LIB"] = "1"
 import sys, ctypes, json
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import _data as D, _oracle as O, _corpus as C, _batch as B, _dicts as X, _ddict as DD
-from zstandard_amd import BatchCodec, CompressionDict, DecompressionDict, DecompressionDictSet, _lib
+from zstandard_amd import BatchCodec, CompressionDict, CompressionDictSet, NO_DICT, DecompressionDict, DecompressionDictSet, _lib
 
 
 def desc_layout(Z):
@@ -104,6 +105,17 @@ def main():
                 frames[i] = f
         chunks.append(X.FIX["trained_small_l3_want"].tobytes()); frames.append(X.FIX["trained_small_l3_frame"].tobytes())
         run("ddict set, own CDict frames of %d KiB of 3 trained dictionaries interleaved, and a libzstd frame of a fourth" % (cs >> 10), chunks, frames=frames, dset=dset)
+    # the same batches compressed in ONE call through a CDict set of the three dictionaries (chunk i: member i % 3, every fourth chunk without a
+    # dictionary) and decoded in one call through the DDict set of the same dictionaries
+    cset = CompressionDictSet(bc, cds, 3)
+    for cs, n in ((1024, 256), (4096, 64), (65536, 8)):
+        chunks = [datas[i % 3][(i // 3) * cs:(i // 3 + 1) * cs] for i in range(n)]
+        index = np.array([NO_DICT if i % 4 == 3 else i % 3 for i in range(n)], dtype=np.uint32)
+        frames = B.frames_of(bc.compress_host(*B.batch(chunks), cdict_set=cset, dict_index=index))
+        named = sum((f[4] & 3) != 0 for f in frames)
+        assert named == int((index != NO_DICT).sum()), (named, "frames name a dictionary")
+        run("cdict set -> ddict set, own frames of %d KiB: 3 trained dictionaries and no dictionary interleaved, one call each way" % (cs >> 10), chunks, frames=frames, dset=dset)
+    cset.close()
     dset.close()
     for x in cds + dds:
         x.close()

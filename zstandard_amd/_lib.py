@@ -106,6 +106,11 @@ def lib():
     L.zsmi_compressBatchDevice_usingCDict.restype = i32; L.zsmi_compressBatchDevice_usingCDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_compressBatchHost_usingCDict.restype = i32; L.zsmi_compressBatchHost_usingCDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_compress_usingCDict.restype = sz; L.zsmi_compress_usingCDict.argtypes = [vp, sz, vp, sz, vp]
+    L.zsmi_createCDictSet.restype = vp; L.zsmi_createCDictSet.argtypes = [vp, vp, u32, i32, ctypes.POINTER(i32)]
+    L.zsmi_freeCDictSet.restype = None; L.zsmi_freeCDictSet.argtypes = [vp]
+    L.zsmi_sizeofCDictSetMembers.restype = u32; L.zsmi_sizeofCDictSetMembers.argtypes = [vp]
+    L.zsmi_compressBatchDevice_usingCDictSet.restype = i32; L.zsmi_compressBatchDevice_usingCDictSet.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.zsmi_compressBatchHost_usingCDictSet.restype = i32; L.zsmi_compressBatchHost_usingCDictSet.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     L.zsmi_createDDict.restype = vp; L.zsmi_createDDict.argtypes = [vp, vp, sz, ctypes.POINTER(i32)]
     L.zsmi_freeDDict.restype = None; L.zsmi_freeDDict.argtypes = [vp]
     L.zsmi_getDictID_fromDDict.restype = ctypes.c_uint; L.zsmi_getDictID_fromDDict.argtypes = [vp]
@@ -184,6 +189,8 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_compress_usingDict", "zsmi_compressBatchDevice_usingDict", "zsmi_compressBatchHost_usingDict",
            "zsmi_createCDict", "zsmi_freeCDict", "zsmi_getDictID_fromCDict", "zsmi_sizeofCDict",
            "zsmi_compressBatchDevice_usingCDict", "zsmi_compressBatchHost_usingCDict", "zsmi_compress_usingCDict",
+           "zsmi_createCDictSet", "zsmi_freeCDictSet", "zsmi_sizeofCDictSetMembers",
+           "zsmi_compressBatchDevice_usingCDictSet", "zsmi_compressBatchHost_usingCDictSet",
            "zsmi_createDDict", "zsmi_freeDDict", "zsmi_getDictID_fromDDict", "zsmi_sizeofDDict",
            "zsmi_decompressBatchDevice_usingDDict", "zsmi_decompressBatchHost_usingDDict", "zsmi_decompress_usingDDict",
            "zsmi_createDDictSet", "zsmi_freeDDictSet", "zsmi_sizeofDDictSetMembers",

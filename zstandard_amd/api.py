@@ -138,6 +138,40 @@ class CompressionDict:
             pass
 
 
+NO_DICT = 0xFFFFFFFF            # ZSMI_DICT_NONE: a dict_index entry for a chunk that uses no dictionary
+
+
+class CompressionDictSet:
+    """A CDict set: a read-only device table of the CompressionDicts `cdicts` (formatted, raw content or empty; all of `level`), in their
+    order.  A compress call with it (cdict_set=, dict_index=) compresses chunk i with member dict_index[i], or without a dictionary for
+    NO_DICT or an empty member: each frame is the one the cdict= call with that member gives.  The set copies nothing: the members are
+    kept alive with it, and it must stay open until the work queued with it is done (BatchCodec.sync).  len(): its members."""
+
+    def __init__(self, codec, cdicts, level=3):
+        self.L = codec.L
+        self.level = level
+        self.members = list(cdicts)                  # (kept alive with the set)
+        arr = (ctypes.c_void_p * max(len(self.members), 1))(*[d.handle for d in self.members])
+        err = ctypes.c_int(0)
+        self.handle = self.L.zsmi_createCDictSet(codec.ctx, arr, len(self.members), level, ctypes.byref(err))
+        if not self.handle:
+            raise RuntimeError(f"zsmi_createCDictSet: error {err.value} ({_error_name(self.L, err.value)})")
+
+    def __len__(self) -> int:
+        return int(self.L.zsmi_sizeofCDictSetMembers(self.handle))
+
+    def close(self):
+        if self.handle:
+            self.L.zsmi_freeCDictSet(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DecompressionDict:
     """A digested decode dictionary (ZSTD_createDDict): `dictionary` (raw content or a formatted dictionary) parsed, checked and laid out in
     the device memory of `codec`'s device once.  Any BatchCodec of that device may use it (ddict=): results are those of the call with the
@@ -453,20 +487,42 @@ class BatchCodec:
         return a.ctypes.data_as(ctypes.c_void_p)
 
     @staticmethod
-    def _compress_form(name, level, dict_ptr, dict_size, cdict):
-        """the C function of a batch compress call and its arguments behind the common ones: a CompressionDict comes first, then a dictionary"""
+    def _compress_form(name, level, dict_ptr, dict_size, cdict, cdict_set=None, dict_index=None):
+        """the C function of a batch compress call and its arguments behind the common ones: a CompressionDictSet comes first, then a
+        CompressionDict, then a dictionary"""
+        if cdict_set is not None:
+            if cdict is not None or dict_size:
+                raise ValueError("cdict_set= excludes cdict= and a dictionary")
+            if dict_index is None:
+                raise ValueError("cdict_set= needs dict_index=")
+            return name + "_usingCDictSet", (cdict_set.handle, BatchCodec._p(dict_index))
+        if dict_index is not None:
+            raise ValueError("dict_index= needs cdict_set=")
         if cdict is not None:
             return name + "_usingCDict", (cdict.handle,)
         if dict_size:
             return name + "_usingDict", (level, dict_ptr, dict_size)
         return name, (level,)
 
-    def compress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, d_dst_sizes_ptr, level=3, d_dict_ptr=0, dict_size=0, cdict=None):
+    @staticmethod
+    def _dict_index(dict_index, n):
+        if dict_index is None:
+            return None
+        di = np.ascontiguousarray(dict_index, dtype=np.uint32)
+        if di.shape != (n,):
+            raise ValueError("dict_index= holds one entry a chunk")
+        return di
+
+    def compress_device(self, d_src_ptr, src_offsets, src_sizes, d_dst_ptr, dst_offsets, d_dst_sizes_ptr, level=3, d_dict_ptr=0, dict_size=0, cdict=None,
+                        cdict_set=None, dict_index=None):
         """d_dict_ptr / dict_size: one dictionary (device memory) for every chunk of the call (zsmi_compressBatchDevice_usingDict).
-        cdict: a CompressionDict instead (zsmi_compressBatchDevice_usingCDict: its level holds; queued without a wait)"""
+        cdict: a CompressionDict instead (zsmi_compressBatchDevice_usingCDict: its level holds; queued without a wait).
+        cdict_set, dict_index: a CompressionDictSet instead, chunk i with its member dict_index[i] or, for NO_DICT, with none
+        (zsmi_compressBatchDevice_usingCDictSet: the set's level holds; queued without a wait)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
-        name, tail = self._compress_form("zsmi_compressBatchDevice", level, ctypes.c_void_p(d_dict_ptr), d_dict_ptr and dict_size, cdict)
+        di = self._dict_index(dict_index, len(ss))
+        name, tail = self._compress_form("zsmi_compressBatchDevice", level, ctypes.c_void_p(d_dict_ptr), d_dict_ptr and dict_size, cdict, cdict_set, di)
         _check(getattr(self.L, name)(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(so), self._p(ss), len(ss), ctypes.c_void_p(d_dst_ptr), self._p(do),
                                      ctypes.c_void_p(d_dst_sizes_ptr), *tail), name)
 
@@ -518,9 +574,11 @@ class BatchCodec:
         table is read back and checked here, once (RuntimeError with the error's name)."""
         return SeekableHandle(self, d_ptr, size)
 
-    def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b"", cdict=None):
+    def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b"", cdict=None, cdict_set=None, dict_index=None):
         """returns (arena uint8, dst_offsets uint64, dst_sizes uint32).  dictionary: one for every chunk (raw content or a formatted
-        dictionary; zsmi_compressBatchHost_usingDict).  cdict: a CompressionDict instead (zsmi_compressBatchHost_usingCDict: its level holds)"""
+        dictionary; zsmi_compressBatchHost_usingDict).  cdict: a CompressionDict instead (zsmi_compressBatchHost_usingCDict: its level holds).
+        cdict_set, dict_index: a CompressionDictSet instead, chunk i with its member dict_index[i] or, for NO_DICT, with none
+        (zsmi_compressBatchHost_usingCDictSet: the set's level holds)"""
         so = np.ascontiguousarray(src_offsets, dtype=np.uint64); ss = np.ascontiguousarray(src_sizes, dtype=np.uint32)
         n = len(ss)
         bounds = np.array([self.L.zsmi_compressBound(int(s)) for s in ss], dtype=np.uint64) if n < 4096 else \
@@ -531,7 +589,7 @@ class BatchCodec:
         arena = np.zeros(int(bounds.sum()), dtype=np.uint8)
         dsz = np.zeros(n, dtype=np.uint32)
         dbuf = np.frombuffer(bytes(dictionary or b""), dtype=np.uint8)
-        name, tail = self._compress_form("zsmi_compressBatchHost", level, self._p(dbuf), len(dbuf), cdict)
+        name, tail = self._compress_form("zsmi_compressBatchHost", level, self._p(dbuf), len(dbuf), cdict, cdict_set, self._dict_index(dict_index, n))
         _check(getattr(self.L, name)(self.ctx, self._p(src), self._p(so), self._p(ss), n, self._p(arena), self._p(do), self._p(dsz), *tail), name)
         return arena, do, dsz
 

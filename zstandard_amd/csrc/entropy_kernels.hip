@@ -632,9 +632,10 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
 // literal gather (a stream compaction of the block) + histogram, Huffman lengths by package-merge (256 threads),
 // table description (one lane), the 4 Huffman streams (one wavefront each)  -> litSec[], meta.{type, rleByte, litSecSize}
 // ---------------------------------------------------------------------------------------------
-// (dictID: the dictionary ID the frame headers carry, 0 for none.  CD: with a digested dictionary's Huffman codes in cdt (else nullptr) - the
-//  first block of a frame is coded as Treeless literals (type 3) iff every literal byte has a code and that section is strictly smaller
-//  than the one the rules below produce)
+// (dictID: the dictionary ID the frame headers carry, 0 for none - the form without CD.  CD: the ID is the chunk's record's
+//  (dictTab[chunkDict[chunk]], ZsCDictEntry), and with a digested dictionary's Huffman codes in the record's tables the first block of a
+//  frame is coded as Treeless literals (type 3) iff every literal byte has a code and that section is strictly smaller than the one the
+//  rules below produce)
 #define ZS_LIT_PARAMS const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, \
                       const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
                       uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, uint8_t *__restrict__ litSecAll, \
@@ -642,12 +643,22 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
                       const ZsChunkDesc *__restrict__ chunks, const uint8_t *__restrict__ seqSecAll, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes
 #define ZS_LIT_ARGS src, blocks, seqAll, hdrAll, litsAll, streamAll, litSecAll, metas, stopAt, chunks, seqSecAll, dst, dstSizes
 template <bool CD>
-__device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictTables *__restrict__ cdt)
+__device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
 {
     __shared__ K3Lds L;
     const uint32_t blk = blockIdx.x;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const ZsBlockDesc bd = blocks[blk];
+    // CD: a frame's first block takes the ID and the tables of its chunk's record (the workgroup's one address); no record, or one without
+    // tables: cdt stays null and the block is coded as by the form without CD
+    const ZsCDictTables *__restrict__ cdt = nullptr;
+    if constexpr (CD) {
+        dictID = 0;
+        if (bd.firstInChunk) {
+            const uint32_t e = chunkDict ? chunkDict[bd.chunk] : 0u;
+            if (e != ZS_DICT_NONE) { dictID = dictTab[e].dictID; cdt = dictTab[e].tables; }
+        }
+    }
     const uint8_t *s = src + bd.srcOff;
     const uint32_t n = bd.size;
     const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
@@ -880,7 +891,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     if constexpr (CD) {
         const uint32_t lhSize = 3 + (nlit >= 1024) + (nlit >= 16384);
         const bool single = nlit < 256;
-        if (!done && bd.firstInChunk && nlit > 0 && !ZS_STOPPED && cdt->hufLog) {
+        if (!done && cdt && nlit > 0 && !ZS_STOPPED && cdt->hufLog) {
             const uint32_t cn = cdt->hufCodeNb[tid];
             L.nbBits[tid] = (uint8_t)(cn >> 16);                         // (free until the code lengths are made)
             if (__syncthreads_and(L.count[tid] == 0 || (cn >> 16) != 0)) {
@@ -1017,7 +1028,8 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     #undef FINISH
 }
 template <bool CD>
-__global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictTables *__restrict__ cdt) { encode_literals_block<CD>(ZS_LIT_ARGS, dictID, cdt); }
+__global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
+{ encode_literals_block<CD>(ZS_LIT_ARGS, dictID, dictTab, chunkDict); }
 
 // ---------------------------------------------------------------------------------------------
 // k_encode_sequences : one wavefront per block.  Repcodes (parallel: two last-index scans), code
@@ -1039,17 +1051,19 @@ __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PA
 #ifndef ZS_CHAIN_MINSEG
 #define ZS_CHAIN_MINSEG 4u         // shortest segment, in blocks of 16 steps
 #endif
-// reps: the recent offsets a chunk's first block starts from ({1, 4, 8}, or a formatted dictionary's own)
+// reps: the recent offsets a chunk's first block starts from ({1, 4, 8}, or a formatted dictionary's own) - the form without CD; with CD
+// they are the chunk's record's (dictTab[chunkDict[chunk]], ZsCDictEntry)
 #define ZS_SEQ_PARAMS const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
                       uint8_t *__restrict__ seqSecAll, ZsBlockMeta *__restrict__ metas, int stopAt, uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, \
                       uint2 *__restrict__ packRecAll
 #define ZS_SEQ_ARGS blocks, nBlocks, seqAll, hdrAll, seqSecAll, metas, stopAt, litsAll, streamAll, packRecAll
-// CD (a digested dictionary's tables in cdt, else nullptr): for the first block of a frame each of LL / OF / ML is coded in
+// CD (a digested dictionary's tables in cdt, the record's; none: nullptr): for the first block of a frame each of LL / OF / ML is coded in
 // Repeat_Mode (3) with the dictionary's table iff that table codes every code present and its estimate, the sum of count x cost, is strictly
 // below the estimate of what the rules below pick: RLE one byte, the predefined table its own sum of count x cost, a new table its
 // description's bytes plus that sum over its normalised counts (in 1/256 bit throughout)
 template <int G, bool CD>
-__device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint32_t rep0, const uint32_t rep1, const uint32_t rep2, const ZsCDictTables *__restrict__ cdt)
+__device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t rep0, uint32_t rep1, uint32_t rep2, const ZsCDictEntry *__restrict__ dictTab,
+                                                       const uint32_t *__restrict__ chunkDict)
 {
     __shared__ SeqLds LS[G];
     const uint32_t wave = threadIdx.x >> 6;
@@ -1058,6 +1072,19 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
     const uint32_t lane = (uint32_t)zs_lane();
     const bool exists = blk < nBlocks;
     const ZsBlockDesc bd = blocks[exists ? blk : 0];
+    // CD: a frame's first block takes the recent offsets and the tables of its chunk's record (the wavefront's one address); no record:
+    // {1, 4, 8}; no tables: cdt stays null and the block is coded as by the form without CD
+    const ZsCDictTables *__restrict__ cdt = nullptr;
+    if constexpr (CD) {
+        rep0 = 1u; rep1 = 4u; rep2 = 8u;
+        if (bd.firstInChunk) {
+            const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)(chunkDict ? chunkDict[bd.chunk] : 0u));
+            if (e != ZS_DICT_NONE) {
+                const ZsCDictEntry &de = dictTab[e];
+                rep0 = de.rep[0]; rep1 = de.rep[1]; rep2 = de.rep[2]; cdt = de.tables;
+            }
+        }
+    }
     const uint32_t n = bd.size;
     const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
     const ZsRangeHdr *hdr = zs_block_range_hdrs(hdrAll, blk);
@@ -1205,7 +1232,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
             if (largest == nseq) {
                 mode = 1;
                 if (pos >= cap) { fail = true; break; }
-                if constexpr (CD) { if (bd.firstInChunk && repeatBeats(t, c, 8u * 256u)) mode = 3; }
+                if constexpr (CD) { if (cdt && repeatBeats(t, c, 8u * 256u)) mode = 3; }
                 if (mode == 1) {
                 if (lane == 0) { out[pos] = (uint8_t)maxSym; ct.rle = 1; ct.tableLog = 0; }
                 pos += 1;
@@ -1213,7 +1240,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
             } else if (nseq < 64 && maxSym <= defMax) {
                 mode = 0;
                 if constexpr (CD) {
-                    if (bd.firstInChunk) {
+                    if (cdt) {
                         const int16_t *defNorm = t == 0 ? LL_defaultNorm : (t == 1 ? OF_defaultNorm : ML_defaultNorm);
                         const int nv = lane <= defMax ? defNorm[lane] : 1;
                         if (repeatBeats(t, c, wave_sum(c * fseSymbolCost((uint32_t)(nv < 0 ? 1 : nv), defLog)))) mode = 3;
@@ -1234,7 +1261,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
                 if (!h) { fail = true; break; }
                 mode = 2;
                 if constexpr (CD) {
-                    if (bd.firstInChunk && repeatBeats(t, c, h * 8u * 256u + wave_sum(c ? c * fseSymbolCost((uint32_t)L.norm[lane], tableLog) : 0u))) mode = 3;
+                    if (cdt && repeatBeats(t, c, h * 8u * 256u + wave_sum(c ? c * fseSymbolCost((uint32_t)L.norm[lane], tableLog) : 0u))) mode = 3;
                 }
                 if (mode == 2) {
                 pos += h;
@@ -1471,7 +1498,8 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const uint
     if (lane == 0 && exists) { ZsBlockMeta &mo = zs_block_meta(metas, blk); mo.seqSecSize = result; mo.seqHdrSize = (secHdr == 0xFFFFFFFFu) ? result : secHdr; mo.seqGap = secGap; }
 }
 template <int G, bool CD>
-__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictTables *__restrict__ cdt) { encode_sequences_block<G, CD>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, cdt); }
+__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
+{ encode_sequences_block<G, CD>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, dictTab, chunkDict); }
 
 // ---------------------------------------------------------------------------------------------
 // k_assemble_frames : one workgroup per chunk.  frame = magic + FHD + FCS (single segment)
@@ -1482,11 +1510,17 @@ __global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint
 #define ZS_ASM_PARAMS const uint8_t *__restrict__ src, const ZsChunkDesc *__restrict__ chunks, const ZsBlockDesc *__restrict__ blocks, \
                       const ZsBlockMeta *__restrict__ metas, const uint8_t *__restrict__ litSecAll, const uint8_t *__restrict__ seqSecAll, \
                       uint32_t blockBase, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes, uint32_t chunkBase
-// dictID: the dictionary ID the frame header carries, 0 for none
-extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAMS, uint32_t dictID)
+// dictID: the dictionary ID the frame header carries, 0 for none; with a table (the launches that take the CD forms of the entropy kernels)
+// it is the chunk's record's, dictTab[chunkDict[chunk]]
+extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAMS, uint32_t dictID, const ZsCDictEntry *__restrict__ dictTab,
+                                                                    const uint32_t *__restrict__ chunkDict)
 {
     const ZsChunkDesc cd = chunks[chunkBase + blockIdx.x];
     if (cd.nBlocks <= 1) return;                               // one-block chunks were assembled by the literals kernel
+    if (dictTab) {
+        const uint32_t e = chunkDict ? chunkDict[chunkBase + blockIdx.x] : 0u;
+        dictID = e != ZS_DICT_NONE ? dictTab[e].dictID : 0u;
+    }
     uint8_t *out = dst + cd.dstOff;
     const uint32_t tid = threadIdx.x;
     uint32_t pos = zs_frame_header(out, cd.size, tid == 0, dictID);

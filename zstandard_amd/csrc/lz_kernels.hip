@@ -75,9 +75,15 @@ template <int TLOG, int NT, bool PFX = false>
 __global__ void __launch_bounds__(64 * ZS_CAND_WAVES(NT))
 k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units, uint32_t block0,
                 uint16_t *__restrict__ distAll, uint8_t *__restrict__ distHiAll, uint32_t *__restrict__ candCount,
-                const uint32_t *__restrict__ dictImg = nullptr, uint32_t pfx = 0)
+                const ZsCDictEntry *__restrict__ dictTab = nullptr, const uint32_t *__restrict__ unitDict = nullptr)
 {
     static_assert(!PFX || TLOG == ZS_TABLE_LOG_BIG, "a prefixed unit spans up to 128 KiB of positions");
+    // PFX: the unit's dictionary, record unitDict[unit] of the table (null: record 0), read by the workgroup's one address: scalar registers
+    const uint32_t *dictImg = nullptr; uint32_t pfx = 0;
+    if constexpr (PFX) {
+        const ZsCDictEntry &de = dictTab[unitDict ? unitDict[blockIdx.x] : 0u];
+        dictImg = de.img; pfx = (uint32_t)__builtin_amdgcn_readfirstlane((int)de.pfx);
+    }
     extern __shared__ __attribute__((aligned(16))) uint32_t candLds[];
     constexpr bool BIG = TLOG > ZS_TABLE_LOG_SMALL;
     constexpr uint32_t G = ZS_CAND_GOF(TLOG), GP = G * 64u, H = G / NT;  // H: steps of a group a hasher merges and stores
@@ -325,14 +331,17 @@ k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ 
 // what its owner wavefront would hold after inserting them one after the other - every slot the LAST position that hashed to it (an LDS
 // atomicMax of (position + 1) << 15 | tag), then written out as tag << 17 | position.  Every prefixed unit of the call loads the image
 // instead of hashing the same pfx bytes again ("Dictionary prefix").  (The last 7 positions of the prefix would hash bytes of
-// the chunk: they are left out, as the unit's own last 7 positions are.)
+// the chunk: they are left out, as the unit's own last 7 positions are.)  entry: the dictionary's record, complete (pre, pfx and img are
+// read from it); it goes to entryOut next to the images, so that a dictionary's table is in device memory when its images are.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(1024)
-k_lz_dict_tables(const uint8_t *__restrict__ pre, uint32_t pfx, uint32_t *__restrict__ img)
+k_lz_dict_tables(const ZsCDictEntry entry, ZsCDictEntry *__restrict__ entryOut)
 {
     constexpr int TLOG = ZS_TABLE_LOG_BIG;
     __shared__ uint32_t T[1u << TLOG];
     const uint32_t tab = blockIdx.x, tid = threadIdx.x;
+    const uint8_t *__restrict__ pre = entry.pre; const uint32_t pfx = entry.pfx; uint32_t *__restrict__ img = const_cast<uint32_t *>(entry.img);
+    if (tab == 0 && tid == 0) *entryOut = entry;                            // the dictionary's record: the one-entry table its calls pass
     for (uint32_t i = tid; i < (1u << TLOG); i += 1024) T[i] = 0;
     __syncthreads();
     const uint32_t hashable = pfx >= 8 ? pfx - 7 : 0;
@@ -501,9 +510,15 @@ __global__ void __launch_bounds__(NT, BIG ? 1 : ZS_WALK_MINW)
 k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units, uint32_t block0,
           const uint16_t *__restrict__ distAll, const uint8_t *__restrict__ distHiAll,
           uint2 *__restrict__ recAll, uint32_t junkSlot, uint4 *__restrict__ resAll, int rangeLogArg, const uint32_t *__restrict__ candCount,
-          const uint8_t *__restrict__ pre = nullptr, uint32_t pfx = 0)
+          const ZsCDictEntry *__restrict__ dictTab = nullptr, const uint32_t *__restrict__ unitDict = nullptr)
 {
     static_assert(!PFX || BIG, "a prefixed unit is staged in the 128 KiB layout");
+    // PFX: the unit's dictionary (as k_lz_candidates reads it); pfx stays in a scalar register: it feeds the staging loop and vb
+    const uint8_t *pre = nullptr; uint32_t pfx = 0;
+    if constexpr (PFX) {
+        const ZsCDictEntry &de = dictTab[unitDict ? unitDict[blockIdx.x] : 0u];
+        pre = de.pre; pfx = (uint32_t)__builtin_amdgcn_readfirstlane((int)de.pfx);
+    }
     constexpr uint32_t CAP = BIG ? ZS_UNIT_MAX : ZS_BLOCK_MAX;                  // unit capacity in bytes
     constexpr uint32_t CPL = LOOK / LPW, RPL = REPWIN / LPW, GPL = WGRP / LPW;   // candidates / recent-offset positions / groups of distances per lane and step
     static_assert((LPW == 1 || LPW == 2 || LPW == 4) && WGRP % LPW == 0 && LOOK % LPW == 0 && REPWIN % LPW == 0 && CPL >= 1 && RPL >= 1 && LOOK <= 8 && REPWIN <= 8, "a walker's lanes share the groups and candidates evenly");

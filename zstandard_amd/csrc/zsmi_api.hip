@@ -83,9 +83,9 @@ extern "C" unsigned long long zsmi_getDecompressedSize(const void *srcv, size_t 
 // ---- the LZ kernels of a level: k_lz_candidates and k_lz_walk for small units (<= 64 KiB), big units and a dictionary call's prefixed units ----
 // level <= 2: short table only ("fast"), walk ranges of 512 bytes; level >= 3: short + long table ("double"), ranges of 256 bytes;
 // level >= 4 scores 8 candidates a step instead of 4 (paramsForLevel in oracle/zso_encoder.c)
-typedef void (*CandFn)(const uint8_t *, const ZsUnitDesc *, uint32_t, uint16_t *, uint8_t *, uint32_t *, const uint32_t *, uint32_t);
+typedef void (*CandFn)(const uint8_t *, const ZsUnitDesc *, uint32_t, uint16_t *, uint8_t *, uint32_t *, const ZsCDictEntry *, const uint32_t *);
 typedef void (*WalkFn)(const uint8_t *, const ZsUnitDesc *, uint32_t, const uint16_t *, const uint8_t *, uint2 *, uint32_t, uint4 *, int,
-                       const uint32_t *, const uint8_t *, uint32_t);
+                       const uint32_t *, const ZsCDictEntry *, const uint32_t *);
 template <class Fn> struct LzKernel { const char *name; Fn fn; uint32_t threads; size_t lds; };
 enum { kUnitsPfx, kUnitsSmall, kUnitsBig };       // (the order the kernels are launched in)
 struct LzShape { LzKernel<CandFn> cand[3]; LzKernel<WalkFn> walk[3]; int walkLog; bool useLong; };
@@ -125,6 +125,7 @@ extern "C" zsmi_ctx *zsmi_createCtx(int device, void *hipStream)
         }
     for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->hItemsEv[i], hipEventDisableTiming) == hipSuccess;
     for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->seek.hEv[i], hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->plan.hDictEv[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); zsmi_freeCtx(c); return nullptr; }
     if (const char *e = getenv("ZSMI_BLOCKS_IN_FLIGHT")) { long v = atol(e); if (v >= 64) c->maxBlocksInFlight = (uint32_t)v; }
     if (const char *e = getenv("ZSMI_DEC_FAST")) c->decodeFast = atoi(e) != 0;
@@ -144,6 +145,7 @@ extern "C" void zsmi_freeCtx(zsmi_ctx *c)
     (void)hipStreamSynchronize(c->stream);
     for (int i = 0; i < 2; i++) if (c->hItemsEv[i]) (void)hipEventDestroy(c->hItemsEv[i]);
     for (int i = 0; i < 2; i++) if (c->seek.hEv[i]) (void)hipEventDestroy(c->seek.hEv[i]);
+    for (int i = 0; i < 2; i++) if (c->plan.hDictEv[i]) (void)hipEventDestroy(c->plan.hDictEv[i]);
     for (auto &tl : c->launches) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->eventPool) (void)hipEventDestroy(e);
     if (c->ownStream) (void)hipStreamDestroy(c->stream);
@@ -216,8 +218,9 @@ bool zsmi_ctx::Scratch::reserve(uint32_t cap)
 }
 // The plan of a call: chunks -> blocks (ZsChunkDesc, ZsBlockDesc) and LZ units, built on the host and copied to the device.  It is reused
 // while the chunk layout repeats (steady-state batches; compared in place: such a call allocates and copies nothing).  A dictionary call
-// adds a unit list of its own, once per plan.
-int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict)
+// adds a unit list of its own, kept while the layout and the chunks' choice of dictionary repeat.
+int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict,
+                        const uint32_t *dictIndex, const uint8_t *memberHasDict)
 {
     bool same = key.size() == (size_t)n * 3 + 1 && key[0] == n;
     for (uint32_t i = 0; same && i < n; i++) same = key[1 + i] == srcOffsets[i] && key[1 + n + i] == dstOffsets[i] && key[1 + 2 * (size_t)n + i] == srcSizes[i];
@@ -267,29 +270,55 @@ int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const ui
         if (hipMemcpyAsync(dChunks.p, hc0, sizeof(ZsChunkDesc) * n, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
         if (hipMemcpyAsync(dBlocks.p, hb, sizeof(ZsBlockDesc) * nBlocks, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
         key.swap(newKey); blocks = nBlocks; maxChunkBlocks = maxNb;
-        hasDictList = false;
+        dictKind = kDictNone;
     }
-    // dictionary calls: the small units again, in a list of their own - [chunks of <= 64 KiB, one unit each (prefixed)][the other small
-    // units: tails of longer chunks]
-    if (dict && !hasDictList) {
-        whole.before.assign((size_t)n + 1, 0); tail.before.assign((size_t)n + 1, 0);
-        uint32_t nWhole = 0, nTail = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            whole.before[i] = nWhole; tail.before[i] = nTail;
-            if (srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX) nWhole++;
-            else if (srcSizes[i] > ZS_BLOCK_MAX && ((srcSizes[i] - 1) % ZS_UNIT_MAX) < ZS_BLOCK_MAX) nTail++;      // its last unit is one block
-        }
-        whole.before[n] = nWhole; tail.before[n] = nTail;
-        if (!hUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1)) || !dUnitsDict.reserve(sizeof(ZsUnitDesc) * (nWhole + nTail + 1))) return ZSMI_error_memory_allocation;
-        if (hipStreamSynchronize(stream) != hipSuccess) return ZSMI_error_GENERIC;         // (the pinned list may still feed a previous copy)
-        ZsUnitDesc *hu = (ZsUnitDesc *)hUnitsDict.p;
-        const ZsUnitDesc *all = (const ZsUnitDesc *)hUnits.p;
-        uint32_t iw = 0, it = nWhole;
-        for (uint32_t i = 0; i < n; i++)                                     // the small units are in chunk order: a chunk's is its whole or its tail
-            for (uint32_t k = small.before[i]; k < small.before[i + 1]; k++) hu[srcSizes[i] <= ZS_BLOCK_MAX ? iw++ : it++] = all[k];
-        if (nWhole + nTail && hipMemcpyAsync(dUnitsDict.p, hu, sizeof(ZsUnitDesc) * (nWhole + nTail), hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
-        whole.base = 0; tail.base = nWhole; hasDictList = true;
+    // dictionary calls: the small units again, in a list of their own - [chunks of <= 64 KiB that have a dictionary, one unit each
+    // (prefixed)][the other small units: tails of longer chunks, chunks without a dictionary]
+    if (!dict) return 0;
+    const int kind = dictIndex ? kDictPerChunk : kDictAll;
+    // the record chunk i uses (ZS_DICT_NONE: no dictionary; an empty member is none)
+    auto choice = [&](uint32_t i) -> uint32_t {
+        if (!dictIndex) return 0u;
+        const uint32_t e = dictIndex[i];
+        return (e == ZS_DICT_NONE || !memberHasDict[e]) ? ZS_DICT_NONE : e;
+    };
+    bool have = dictKind == kind && (kind == kDictAll || dictKey.size() == (size_t)n);
+    if (kind == kDictPerChunk) for (uint32_t i = 0; have && i < n; i++) have = dictKey[i] == choice(i);
+    if (have) return 0;
+    dictKind = kDictNone;
+    whole.before.assign((size_t)n + 1, 0); tail.before.assign((size_t)n + 1, 0);
+    if (kind == kDictPerChunk) dictKey.resize(n); else dictKey.clear();
+    uint32_t nWhole = 0, nTail = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        whole.before[i] = nWhole; tail.before[i] = nTail;
+        const uint32_t e = choice(i);
+        if (kind == kDictPerChunk) dictKey[i] = e;
+        if (srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX && e != ZS_DICT_NONE) nWhole++;
+        else nTail += small.before[i + 1] - small.before[i];                 // (a chunk has at most one small unit: itself, or its last unit when that is one block)
     }
+    whole.before[n] = nWhole; tail.before[n] = nTail;
+    const size_t unitBytes = sizeof(ZsUnitDesc) * ((size_t)nWhole + nTail);
+    const size_t bytes = unitBytes + (kind == kDictPerChunk ? sizeof(uint32_t) * ((size_t)n + nWhole) : 0);
+    const int hb = (int)(dictBuilds++ & 1u);
+    if (hDictBusy[hb]) { if (hipEventSynchronize(hDictEv[hb]) != hipSuccess) return ZSMI_error_GENERIC; hDictBusy[hb] = false; }
+    if (!hDictList[hb].reserve(bytes + 16) || !dDictList.reserve(bytes + 16)) return ZSMI_error_memory_allocation;
+    ZsUnitDesc *hu = (ZsUnitDesc *)hDictList[hb].p;
+    uint32_t *hChunkDict = (uint32_t *)((uint8_t *)hDictList[hb].p + unitBytes), *hUnitDict = hChunkDict + n;
+    const ZsUnitDesc *all = (const ZsUnitDesc *)hUnits.p;
+    uint32_t iw = 0, it = nWhole;
+    for (uint32_t i = 0; i < n; i++) {                                       // the small units are in chunk order
+        const uint32_t e = choice(i);
+        const bool prefixed = srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX && e != ZS_DICT_NONE;
+        if (kind == kDictPerChunk) { hChunkDict[i] = e; if (prefixed) hUnitDict[iw] = e; }
+        for (uint32_t k = small.before[i]; k < small.before[i + 1]; k++) hu[prefixed ? iw++ : it++] = all[k];
+    }
+    if (bytes) {
+        if (hipMemcpyAsync(dDictList.p, hu, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
+        if (hipEventRecord(hDictEv[hb], stream) != hipSuccess) { (void)hipStreamSynchronize(stream); return ZSMI_error_GENERIC; }   // (the buffer is idle after that)
+        hDictBusy[hb] = true;
+    }
+    whole.base = 0; tail.base = nWhole; chunkDictOff = unitBytes; unitDictOff = unitBytes + sizeof(uint32_t) * (size_t)n;
+    dictKind = kind;
     return 0;
 }
 CompressPlan::Cut CompressPlan::cut(uint32_t chunk0, uint32_t cap) const
@@ -305,7 +334,7 @@ CompressPlan::Units CompressPlan::units(int kind, bool dict, uint32_t chunk0, ui
     if (kind == kUnitsPfx && !dict) return { nullptr, 0 };
     const bool ownList = dict && kind != kUnitsBig;
     const Run &r = kind == kUnitsBig ? big : (!dict ? small : (kind == kUnitsPfx ? whole : tail));
-    return { (const ZsUnitDesc *)(ownList ? dUnitsDict : dUnits).p + r.base + r.before[chunk0], r.before[chunk1] - r.before[chunk0] };
+    return { (const ZsUnitDesc *)(ownList ? dDictList : dUnits).p + r.base + r.before[chunk0], r.before[chunk1] - r.before[chunk0] };
 }
 
 // the prefix: the dictionary content's last <= 64 KiB, where a prefixed unit's matches may reach
@@ -315,12 +344,21 @@ static DictPrefix dictPrefix(const ZsCompressDict &d)
     const uint32_t size = std::min<uint32_t>(d.contentSize, ZS_BLOCK_MAX);
     return { d.dBytes + d.contentOff + d.contentSize - size, size };
 }
-// the prefix's candidate-table images for a level's LZ shape (the short table's and the long table's), into dImg
-static const size_t kDictImgBytes = (size_t)2 << (ZS_TABLE_LOG_BIG + 2);
-static void launchDictTables(zsmi_ctx *c, const ZsCompressDict &d, int level, void *dImg)
+// a dictionary's record as the kernels read it (its images at dImg)
+static ZsCDictEntry dictEntry(const ZsCompressDict &d, const uint32_t *dImg)
 {
     const DictPrefix pre = dictPrefix(d);
-    LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(lzShape(level).useLong ? 2 : 1), dim3(1024), 0, pre.d, pre.size, (uint32_t *)dImg);
+    ZsCDictEntry e;
+    e.pre = pre.d; e.img = dImg; e.tables = d.dTables; e.pfx = pre.size; e.dictID = d.dictID; e.pad = 0;
+    for (int i = 0; i < 3; i++) e.rep[i] = d.rep[i];
+    return e;
+}
+// the prefix's candidate-table images for a level's LZ shape (the short table's and the long table's), into dImg, and the dictionary's
+// record into dEntry: its one-entry table
+static const size_t kDictImgBytes = (size_t)2 << (ZS_TABLE_LOG_BIG + 2);
+static void launchDictTables(zsmi_ctx *c, const ZsCompressDict &d, int level, void *dImg, void *dEntry)
+{
+    LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(lzShape(level).useLong ? 2 : 1), dim3(1024), 0, dictEntry(d, (const uint32_t *)dImg), (ZsCDictEntry *)dEntry);
 }
 // The launch sequence of a call, over the plan's sub-batches.  dict: nullptr, or the call's dictionary, in one of three kinds -
 //   content only, or parsed from a formatted dictionary (the _usingDict calls, the trainer): the table images are built here, every call;
@@ -328,25 +366,33 @@ static void launchDictTables(zsmi_ctx *c, const ZsCompressDict &d, int level, vo
 //   digested, formatted (dImg and dTables): besides, its entropy tables may code a frame's first block.
 // Chunks of <= 64 KiB are PREFIXED units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the prefix); the units of longer
 // chunks are parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
-// A call without a dictionary is one with no prefixed units.  dStats (the dictionary trainer's finalize; nullptr on every other path): device
+// set (instead of dict): the dictionaries of a zsmi_cdictSet and the call's choice - every chunk its own of the three kinds above, or none.
+// The kernels take the dictionary as a table of records (ZsCDictEntry) and an index a chunk; a single dictionary is the one-entry table
+// with no index.  A call without a dictionary is one with no prefixed units.  dStats (the dictionary trainer's finalize; nullptr on every other path): device
 // counters of the literal bytes and LL / OF / ML codes, added to by k_train_stats after each sub-batch's sequences kernel.
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const ZsCompressDict *dict, uint32_t *dStats)
+                                   const ZsCompressDict *dict, uint32_t *dStats, const ZsCompressDictSet *set)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
     const LzShape &shape = lzShape(level);
     CompressPlan &P = c->plan;
-    if (const int e = P.build(c->stream, srcOffsets, srcSizes, n, dstOffsets, dict != nullptr)) return e;
-    const DictPrefix pre = dict ? dictPrefix(*dict) : DictPrefix{ nullptr, 0u };
-    const uint32_t *dImg = dict ? dict->dImg : nullptr;
-    if (dict && !dImg) {
-        if (!c->dDictImg.reserve(kDictImgBytes)) return ZSMI_error_memory_allocation;
-        launchDictTables(c, *dict, level, c->dDictImg.p);
-        dImg = (const uint32_t *)c->dDictImg.p;
+    if (set) {                                                       // (a choice that gives no chunk a dictionary: the plain call)
+        bool any = false;
+        for (uint32_t i = 0; i < n && !any; i++) any = set->dictIndex[i] != ZS_DICT_NONE && set->memberHasDict[set->dictIndex[i]];
+        if (!any) set = nullptr;
     }
+    const bool useDict = dict || set;
+    if (const int e = P.build(c->stream, srcOffsets, srcSizes, n, dstOffsets, useDict, set ? set->dictIndex : nullptr, set ? set->memberHasDict : nullptr)) return e;
+    const ZsCDictEntry *dTable = set ? set->dTable : (dict ? dict->dEntry : nullptr);
+    if (dict && !dTable) {
+        if (!c->dDictImg.reserve(kDictImgBytes + sizeof(ZsCDictEntry))) return ZSMI_error_memory_allocation;
+        launchDictTables(c, *dict, level, c->dDictImg.p, (uint8_t *)c->dDictImg.p + kDictImgBytes);
+        dTable = (const ZsCDictEntry *)((const uint8_t *)c->dDictImg.p + kDictImgBytes);
+    }
+    const uint32_t *dChunkDict = set ? P.chunkDict() : nullptr;          // (null: every chunk uses record 0)
     // sub-batches of whole chunks, one after the other through one scratch set.  Every kernel goes to the caller's stream: a stream of
     // the context's own costs two queue crossings a call (~0.01 - 0.09 ms each: a bench line of 126 GiB/s where the kernels added up to 137).
     const uint32_t cap = std::max<uint32_t>((uint32_t)std::min<uint64_t>(P.blocks, std::max<uint32_t>(64, c->maxBlocksInFlight)), P.maxChunkBlocks);
@@ -359,13 +405,13 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
         chunk1 = sub.chunk1;
         const ZsBlockDesc *dB = (const ZsBlockDesc *)P.dBlocks.p + block0;
         CompressPlan::Units units[3];
-        for (int k = 0; k < 3; k++) units[k] = P.units(k, dict != nullptr, chunk0, chunk1);
+        for (int k = 0; k < 3; k++) units[k] = P.units(k, useDict, chunk0, chunk1);
         for (int k = 0; k < 3; k++) {
             const LzKernel<CandFn> &K = shape.cand[k];
             const bool p = k == kUnitsPfx;
             if (units[k].n)
                 LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, S.dist(),
-                       S.distHi(), S.cand(), p ? dImg : nullptr, p ? pre.size : 0u);
+                       S.distHi(), S.cand(), p ? dTable : nullptr, p ? P.unitDict(chunk0) : nullptr);
         }
         for (int k = 0; k < 3; k++) {
             const LzKernel<WalkFn> &K = shape.walk[k];
@@ -373,31 +419,33 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
             if (units[k].n)
                 LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, S.dist(),
                        S.distHi(), S.recs(), zs_walk_records_end(cap), S.res(), shape.walkLog, S.cand(),
-                       p ? pre.d : nullptr, p ? pre.size : 0u);
+                       p ? dTable : nullptr, p ? P.unitDict(chunk0) : nullptr);
         }
         LAUNCH(c, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, S.recs(), S.res(), S.seqs(), S.hdrs(), shape.walkLog);
         if (c->stopAfterWalk) continue;
         // The entropy stage.  Sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and
         // reads the sequence sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  Every
-        // kernel takes the dictionary's recent offsets or ID ({1, 4, 8} and 0 without one); a digested one's tables choose the CD forms.
-        const ZsCDictTables *cdt = dict ? dict->dTables : nullptr;
+        // kernel takes the dictionary's recent offsets or ID ({1, 4, 8} and 0 without one).  Digested tables - the one dictionary's, any
+        // member's of a set - choose the CD forms, which take offsets, ID and tables from each chunk's record instead.
+        const bool cdForms = set ? set->tables : (dict && dict->dTables);
+        const ZsCDictEntry *cdt = cdForms ? dTable : nullptr;
         const auto seqKernel = cdt ? k_encode_sequences<ZS_SEQ_GROUP, true> : k_encode_sequences<ZS_SEQ_GROUP, false>;
         const auto litKernel = cdt ? k_encode_literals<true> : k_encode_literals<false>;
         const uint4 rep = dict ? make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u) : make_uint4(1u, 4u, 8u, 0u);
         const uint32_t dictID = dict ? dict->dictID : 0u;
         LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, S.seqs(),
                S.hdrs(), S.seqSec(), S.metas(), c->stopSeq, S.lits(), S.streams(),
-               S.distAsPackRecords(), rep, cdt);
+               S.distAsPackRecords(), rep, cdt, dChunkDict);
         if (dStats)                                                  // (the codes it reads are in the literal buffers until the literals kernel)
             LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(),
                    S.hdrs(), S.lits(), dStats);
         LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(), S.hdrs(),
                S.lits(), S.streams(), S.litSec(), S.metas(), c->stopLit,
-               dChunks, S.seqSec(), (uint8_t *)dDst, dDstSizes, dictID, cdt);
+               dChunks, S.seqSec(), (uint8_t *)dDst, dDstSizes, dictID, cdt, dChunkDict);
         if (P.maxChunkBlocks > 1)                                    // chunks of several blocks
             LAUNCH(c, "k_assemble_frames", k_assemble_frames, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, dChunks,
                    (const ZsBlockDesc *)P.dBlocks.p, S.metas(), S.litSec(), S.seqSec(), block0,
-                   (uint8_t *)dDst, dDstSizes, chunk0, dictID);
+                   (uint8_t *)dDst, dDstSizes, chunk0, dictID, cdt, dChunkDict);
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
@@ -427,8 +475,8 @@ extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc,
 struct zsmi_cdict {
     int device = 0, level = 3;
     bool empty = false;                  // no bytes: its calls are the plain calls at its level
-    ZsCompressDict d;                    // (dBytes, dImg, dTables: into the buffers below)
-    DevBuf dBytes, dImg, dTables;
+    ZsCompressDict d;                    // (dBytes, dImg, dTables, dEntry: into the buffers below)
+    DevBuf dBytes, dImg, dTables, dEntry;
 };
 extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t dictSize, int level, int *err)
 {
@@ -441,17 +489,18 @@ extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t di
         cd->device = c->device; cd->level = level;
         if (!dict || dictSize == 0) { cd->empty = true; break; }
         if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if (!cd->dBytes.reserve(dictSize + 64) || !cd->dImg.reserve(kDictImgBytes)) { code = ZSMI_error_memory_allocation; break; }
+        if (!cd->dBytes.reserve(dictSize + 64) || !cd->dImg.reserve(kDictImgBytes) || !cd->dEntry.reserve(sizeof(ZsCDictEntry))) { code = ZSMI_error_memory_allocation; break; }
         if (hipMemcpyAsync(cd->dBytes.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
         if ((code = loadDict(c, cd->dBytes.p, dictSize, cd->d))) break;
         const bool formatted = cd->d.contentOff != 0;
         if (formatted && !cd->dTables.reserve(sizeof(ZsCDictTables))) { code = ZSMI_error_memory_allocation; break; }
-        launchDictTables(c, cd->d, level, cd->dImg.p);
         cd->d.dImg = (const uint32_t *)cd->dImg.p;
         if (formatted) {
             LAUNCH(c, "k_cdict_tables", k_cdict_tables, dim3(1), dim3(256), 0, &((const ZsDictRecord *)c->dDictRec.p)->ent, (ZsCDictTables *)cd->dTables.p);
             cd->d.dTables = (const ZsCDictTables *)cd->dTables.p;
         }
+        launchDictTables(c, cd->d, level, cd->dImg.p, cd->dEntry.p);         // (and the one-entry table its calls pass)
+        cd->d.dEntry = (const ZsCDictEntry *)cd->dEntry.p;
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
     } while (0);
     if (code) { delete cd; cd = nullptr; }
@@ -460,7 +509,7 @@ extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t di
 }
 extern "C" void zsmi_freeCDict(zsmi_cdict *cd) { delete cd; }
 extern "C" unsigned zsmi_getDictID_fromCDict(const zsmi_cdict *cd) { return cd ? cd->d.dictID : 0; }
-extern "C" size_t zsmi_sizeofCDict(const zsmi_cdict *cd) { return cd ? cd->dBytes.cap + cd->dImg.cap + cd->dTables.cap : 0; }
+extern "C" size_t zsmi_sizeofCDict(const zsmi_cdict *cd) { return cd ? cd->dBytes.cap + cd->dImg.cap + cd->dTables.cap + cd->dEntry.cap : 0; }
 // What a zsmi_cdict * argument asks of a call on context c - 0, with level and dict set: compress at `level`, plainly (dict nullptr: a null
 // cdict at level 3, one without bytes at its own) or with the descriptor; or the error (a dictionary digested on another device: parameter_unsupported)
 static int resolveCDict(const zsmi_ctx *c, const zsmi_cdict *cd, int &level, const ZsCompressDict *&dict)
@@ -477,6 +526,77 @@ extern "C" int zsmi_compressBatchDevice_usingCDict(zsmi_ctx *c, const void *dSrc
     int level; const ZsCompressDict *dict;
     if (const int e = resolveCDict(c, cd, level, dict)) return e;
     return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, dict);
+}
+
+// ---- CDict sets: a read-only device table with one record (ZsCDictEntry) per member, in the caller's order; a call with a set gives chunk i
+// the member dictIndex[i] names, on the device, inside the kernels.  The set copies nothing from its members: a record points into its
+// member's buffers.  Every check is the host's, before anything touches the device; the one upload is waited for, once. ----
+struct zsmi_cdictSet {
+    int device = 0, level = 3;
+    uint32_t members = 0;
+    bool tables = false;                 // some member is formatted: its calls take the CD forms of the entropy kernels
+    std::vector<uint8_t> hasDict;        // per member: 0 for an empty CDict (its chunks have no dictionary)
+    DevBuf dTable;
+};
+#define ZSMI_CDICTSET_MAX 4096u
+extern "C" zsmi_cdictSet *zsmi_createCDictSet(zsmi_ctx *c, const zsmi_cdict *const *cds, uint32_t n, int level, int *err)
+{
+    int code = 0;
+    zsmi_cdictSet *set = nullptr;
+    do {
+        if (!c) { code = ZSMI_error_init_missing; break; }
+        if (n > ZSMI_CDICTSET_MAX) { code = ZSMI_error_parameter_outOfBound; break; }
+        if (n && !cds) { code = ZSMI_error_parameter_unsupported; break; }
+        std::vector<ZsCDictEntry> table(n);
+        std::vector<uint8_t> hasDict(n);
+        bool tables = false;
+        for (uint32_t i = 0; i < n && !code; i++) {
+            const zsmi_cdict *cd = cds[i];
+            // a member: there, of this device, digested for this level (its images are built for one LZ shape)
+            if (!cd || cd->device != c->device || cd->level != level) { code = ZSMI_error_parameter_unsupported; break; }
+            hasDict[i] = !cd->empty;
+            table[i] = cd->empty ? ZsCDictEntry() : dictEntry(cd->d, cd->d.dImg);
+            tables |= !cd->empty && cd->d.dTables != nullptr;
+        }
+        if (code) break;
+        set = new (std::nothrow) zsmi_cdictSet();
+        if (!set) { code = ZSMI_error_memory_allocation; break; }
+        set->device = c->device; set->level = level; set->members = n; set->tables = tables; set->hasDict.swap(hasDict);
+        if (n == 0) break;
+        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+        if (!set->dTable.reserve(sizeof(ZsCDictEntry) * n)) { code = ZSMI_error_memory_allocation; break; }
+        if (hipMemcpyAsync(set->dTable.p, table.data(), sizeof(ZsCDictEntry) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+    } while (0);
+    if (code) { delete set; set = nullptr; }
+    if (err) *err = code;
+    return set;
+}
+extern "C" void zsmi_freeCDictSet(zsmi_cdictSet *set) { delete set; }
+extern "C" uint32_t zsmi_sizeofCDictSetMembers(const zsmi_cdictSet *set) { return set ? set->members : 0; }
+// resolveCDict's sibling: what a zsmi_cdictSet * argument and the call's choice ask of a call on context c - 0, with level and `sel` set
+// (use: false for a null set, the plain call at level 3); or the error, before anything is queued or written
+struct CDictSetCall { bool use; ZsCompressDictSet sel; };
+static int resolveCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dictIndex, uint32_t n, int &level, CDictSetCall &call)
+{
+    level = set ? set->level : 3; call.use = false;
+    if (!c) return ZSMI_error_init_missing;
+    if (!set) return 0;
+    if (n && !dictIndex) return ZSMI_error_GENERIC;
+    for (uint32_t i = 0; i < n; i++) if (dictIndex[i] != ZS_DICT_NONE && dictIndex[i] >= set->members) return ZSMI_error_parameter_outOfBound;
+    if (set->device != c->device) return ZSMI_error_parameter_unsupported;
+    call.use = true;
+    call.sel.dTable = (const ZsCDictEntry *)set->dTable.p; call.sel.memberHasDict = set->hasDict.data(); call.sel.tables = set->tables; call.sel.dictIndex = dictIndex;
+    return 0;
+}
+// queues the work and returns, as the _usingCDict call: the choice goes up with the plan's dictionary list, through pinned buffers taken in turn
+extern "C" int zsmi_compressBatchDevice_usingCDictSet(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes,
+                                                      const zsmi_cdictSet *set, const uint32_t *dictIndex)
+{
+    int level; CDictSetCall call;
+    if (const int e = resolveCDictSet(c, set, dictIndex, n, level, call)) return e;
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, nullptr, call.use ? &call.sel : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -930,13 +1050,13 @@ static std::vector<uint32_t> compressBounds(const uint32_t *srcSizes, uint32_t n
 }
 // dict: the call's dictionary (a digested one's descriptor), or nullptr
 static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, void *dst, const uint64_t *dstOffsets,
-                                 uint32_t *dstSizes, int level, const ZsCompressDict *dict)
+                                 uint32_t *dstSizes, int level, const ZsCompressDict *dict, const ZsCompressDictSet *set = nullptr)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, compressBounds(srcSizes, n).data(), dstSizes, nullptr, 0,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict);
+                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict, nullptr, set);
                   });
 }
 extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
@@ -964,6 +1084,14 @@ extern "C" int zsmi_compressBatchHost_usingCDict(zsmi_ctx *c, const void *src, c
     int level; const ZsCompressDict *dict;
     if (const int e = resolveCDict(c, cd, level, dict)) return e;
     return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict);
+}
+extern "C" int zsmi_compressBatchHost_usingCDictSet(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                    uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes,
+                                                    const zsmi_cdictSet *set, const uint32_t *dictIndex)
+{
+    int level; CDictSetCall call;
+    if (const int e = resolveCDictSet(c, set, dictIndex, n, level, call)) return e;
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, call.use ? &call.sel : nullptr);
 }
 // dict / dictSize: the call's dictionary in host memory, which this call stages; or digested: the selector of digested ones (a DDict's or a
 // set's), whose bytes are on the device already

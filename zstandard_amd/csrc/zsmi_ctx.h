@@ -40,22 +40,36 @@ struct TimedLaunch { const char *name; hipEvent_t a, b; };
 struct DecodePlan;
 
 // The plan of a compress call (built in the compress section of zsmi_api.hip): chunks -> blocks and LZ units, on the host and in device
-// memory.  Everything here is valid together, for the layout `key` states; the dictionary list only while hasDictList.
+// memory.  Everything here is valid together, for the layout `key` states; the dictionary list for the choice dictKind / dictKey state.
 struct CompressPlan {
     std::vector<uint64_t> key;           // n, then the srcOffsets, dstOffsets and srcSizes the plan was built from
     uint64_t blocks = 0; uint32_t maxChunkBlocks = 1;
-    PinBuf hBlocks, hChunks, hUnits, hUnitsDict;
-    DevBuf dBlocks, dChunks, dUnits, dUnitsDict;
+    PinBuf hBlocks, hChunks, hUnits;
+    DevBuf dBlocks, dChunks, dUnits, dDictList;
     // A run of units in chunk order inside one of the two device lists: before[i] (n + 1 entries) units of the run belong to chunks in
     // front of chunk i; the run starts at unit `base` of its list.
-    //   dUnits:     [small: units of <= 64 KiB][big]
-    //   dUnitsDict: [whole: chunks of <= 64 KiB, one prefixed unit each][tail: the other small units] - dictionary calls; built on the first of a plan
+    //   dUnits:    [small: units of <= 64 KiB][big]
+    //   dDictList: [whole: chunks of <= 64 KiB that have a dictionary, one prefixed unit each][tail: the other small units - tails of longer
+    //              chunks, and a set call's chunks without a dictionary] - dictionary calls.  A set call's list is followed by the record
+    //              index of every chunk (ZS_DICT_NONE: no dictionary) and of every unit of `whole`: chunkDict(), unitDict()
     struct Run { std::vector<uint32_t> before; uint32_t base = 0; } small, big, whole, tail;
-    bool hasDictList = false;
+    // Which dictionary list the plan holds: kDictNone; kDictAll, one dictionary for every chunk; kDictPerChunk, the choice dictKey states
+    // (a chunk's record, ZS_DICT_NONE for none).  The list depends on the choice: the same layout with another choice builds it again, through
+    // two pinned buffers taken in turn behind events, as the decoder's item list - no wait for the stream
+    enum { kDictNone, kDictAll, kDictPerChunk };
+    int dictKind = kDictNone;
+    std::vector<uint32_t> dictKey;
+    PinBuf hDictList[2]; hipEvent_t hDictEv[2] = { nullptr, nullptr }; bool hDictBusy[2] = { false, false }; uint32_t dictBuilds = 0;
+    size_t chunkDictOff = 0, unitDictOff = 0;      // (bytes into dDictList; kDictPerChunk only)
+    const uint32_t *chunkDict() const { return dictKind == kDictPerChunk ? (const uint32_t *)((const uint8_t *)dDictList.p + chunkDictOff) : nullptr; }
+    const uint32_t *unitDict(uint32_t chunk0) const { return dictKind == kDictPerChunk ? (const uint32_t *)((const uint8_t *)dDictList.p + unitDictOff) + whole.before[chunk0] : nullptr; }
     struct Units { const ZsUnitDesc *d; uint32_t n; };
     struct Cut { uint32_t chunk1, nb, block0; };
 
-    int build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict);
+    // dict: a dictionary call; dictIndex (host, n entries; null: one dictionary for every chunk) and memberHasDict: chunk i uses record
+    // dictIndex[i], and none for ZS_DICT_NONE or a record that memberHasDict says stands for no dictionary
+    int build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict,
+              const uint32_t *dictIndex = nullptr, const uint8_t *memberHasDict = nullptr);
     Cut cut(uint32_t chunk0, uint32_t cap) const;                                      // the sub-batch of whole chunks from chunk0: at most cap blocks (one chunk at least)
     Units units(int kind, bool dict, uint32_t chunk0, uint32_t chunk1) const;          // kind: kUnitsPfx, kUnitsSmall, kUnitsBig
 };
@@ -75,7 +89,7 @@ struct zsmi_ctx {
         uint2 *distAsPackRecords() const { return (uint2 *)buf[kZsScratch_dist].p; }      // (lent to k_encode_sequences: zs_dist_lend_pack_records)
         bool reserve(uint32_t cap);            // cap: blocks of a sub-batch
     } scratch;
-    DevBuf dDictImg;                       // a _usingDict call's candidate-table images of the prefix (a digested dictionary holds its own)
+    DevBuf dDictImg;                       // a _usingDict call's candidate-table images of the prefix and, behind them, its one-entry table (a digested dictionary holds its own)
     DevBuf dDictRec; PinBuf hDictRec;      // the dictionary loader's record (ZsDictRecord: k_dict_load writes it, loadDict in zsmi_api.hip reads it back)
     int stopAfterWalk = 0;                 // ZSMI_STOP_AFTER_WALK (debug-hooks build, tools/walk_check.py): the entropy kernels are not launched
     int stopLit = 0, stopSeq = 0;          // timing aids of a -DZSMI_DEBUG_HOOKS build (ZSMI_STOP_LIT / ZSMI_STOP_SEQ): end a kernel after a stage; always 0 in the product
@@ -141,17 +155,24 @@ static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz
 // ---- the batch calls in device memory (zsmi_api.hip: the compress and the decompress section state their arguments) ----
 // A dictionary as the compress launch sequence takes it (nullptr: none).  dBytes: its bytes in device memory; contentOff .. rep: what the
 // device's dictionary loader found in them (loadDict in zsmi_api.hip copies its record: the host parses no dictionary; raw content: all of
-// it, no ID, offsets {1, 4, 8}).  dImg, dTables: a digested dictionary's (zsmi_cdict) - the
-// prefix's candidate-table images, built once and not by the call, and a formatted one's entropy tables in encoder form.
+// it, no ID, offsets {1, 4, 8}).  dImg, dTables, dEntry: a digested dictionary's (zsmi_cdict) - the
+// prefix's candidate-table images, built once and not by the call, a formatted one's entropy tables in encoder form, and its one-entry
+// table (ZsCDictEntry, zsmi_device.h: what the kernels read).
 struct ZsCDictTables;
 struct ZsCompressDict {
     const uint8_t *dBytes = nullptr;
     uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 };
-    const uint32_t *dImg = nullptr; const ZsCDictTables *dTables = nullptr;
+    const uint32_t *dImg = nullptr; const ZsCDictTables *dTables = nullptr; const ZsCDictEntry *dEntry = nullptr;
+};
+// The dictionaries of a set call (zsmi_cdictSet): the device table, which of its records stand for a dictionary (an empty member's does
+// not), whether any has entropy tables, and the call's choice - chunk i uses record dictIndex[i] (host), ZS_DICT_NONE: none.
+struct ZsCompressDictSet {
+    const ZsCDictEntry *dTable; const uint8_t *memberHasDict; bool tables;
+    const uint32_t *dictIndex;
 };
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const ZsCompressDict *dict, uint32_t *dStats = nullptr);
+                                   const ZsCompressDict *dict, uint32_t *dStats = nullptr, const ZsCompressDictSet *set = nullptr);
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                      const struct ZsDictSel *dict);

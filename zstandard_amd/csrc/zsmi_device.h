@@ -73,6 +73,19 @@ struct ZsDictRecord {
     ZsCDictEntropy ent;              // contentOff != 0 only
 };
 
+// One compression dictionary as the encoder kernels take it: a record of a read-only device table (a zsmi_cdict's own one-entry table, a
+// _usingDict call's, a zsmi_cdictSet's with one record a member).  A kernel gets the table and an index array (null: every chunk uses
+// record 0; an entry of ZS_DICT_NONE: that chunk has no dictionary) and reads its record once, by a wave-uniform address.
+//   pre, pfx: the content's last <= 64 KiB, where a prefixed unit's matches may reach; img: k_lz_dict_tables' candidate-table images of it
+//   tables:   a formatted digested dictionary's entropy tables in encoder form, else null
+//   rep, dictID: the recent offsets a frame's first block starts from and the ID its header carries ({1, 4, 8} and 0 for raw content)
+#define ZS_DICT_NONE 0xFFFFFFFFu
+struct ZsCDictTables;
+struct ZsCDictEntry {
+    const uint8_t *pre; const uint32_t *img; const ZsCDictTables *tables;
+    uint32_t pfx, dictID, rep[3], pad;
+};
+
 // unaligned little-endian loads.  memcpy keeps the alignment-1 fact visible to the compiler: a cast to an over-aligned
 // pointer lets it turn a wave-uniform address into a scalar load, which drops the low address bits.  (Host code reads
 // container headers with the same loads: the host is little-endian too.)
