@@ -14,6 +14,8 @@ namespace EPAM.Deltix.ZStd
         [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
         static extern UIntPtr zsmi_compress_usingDict(void* dst, UIntPtr dstCapacity, void* src, UIntPtr srcSize, void* dict, UIntPtr dictSize, int level);
         [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
+        static extern UIntPtr zsmi_compress_advanced(void* dst, UIntPtr dstCapacity, void* src, UIntPtr srcSize, void* dict, UIntPtr dictSize, int level, int checksumFlag);
+        [DllImport(ZStdDecompress.Lib, CallingConvention = CallingConvention.Cdecl)]
         static extern IntPtr zsmi_getErrorName(UIntPtr code);
 
         public const int DefaultLevel = 3;
@@ -35,6 +37,16 @@ namespace EPAM.Deltix.ZStd
             if (dstCapacity > (uint)dst.Length || srcSize > (uint)src.Length) throw new ArgumentOutOfRangeException();
             fixed (byte* d = dst, s = src, dc = dict)
                 return unchecked((uint)(ulong)zsmi_compress_usingDict(d, (UIntPtr)dstCapacity, s, (UIntPtr)srcSize, dc, (UIntPtr)(uint)(dict?.Length ?? 0), compressionLevel));
+        }
+        // the same with a content checksum (ZSTD_c_checksumFlag): the frame of Compress / CompressUsingDict with bit 2 of byte 4 set and the low 32 bits
+        // of the content's XXH64 behind the last block; a decoder answers checksum_wrong (22) for a frame whose content it cannot restore.
+        // dict: null / empty = none; checksum false: Compress / CompressUsingDict byte for byte
+        public static uint Compress(byte[] dst, uint dstCapacity, byte[] src, uint srcSize, byte[] dict, int compressionLevel, bool checksum)
+        {
+            if (dst == null || src == null) throw new ArgumentNullException(dst == null ? nameof(dst) : nameof(src));
+            if (dstCapacity > (uint)dst.Length || srcSize > (uint)src.Length) throw new ArgumentOutOfRangeException();
+            fixed (byte* d = dst, s = src, dc = dict)
+                return unchecked((uint)(ulong)zsmi_compress_advanced(d, (UIntPtr)dstCapacity, s, (UIntPtr)srcSize, dc, (UIntPtr)(uint)(dict?.Length ?? 0), compressionLevel, checksum ? 1 : 0));
         }
         public static uint Compress(byte[] dst, byte[] src, int compressionLevel = DefaultLevel) => Compress(dst, (uint)dst.Length, src, (uint)src.Length, compressionLevel);
 

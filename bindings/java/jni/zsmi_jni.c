@@ -1,4 +1,4 @@
-/* UNVERIFIED (no JDK / jni.h in the build image).  JNI shim for bindings/java/.../ZstdDecompressor.java over libzsmi.so.
+/* UNVERIFIED (no JDK / jni.h in the build image).  JNI shim for bindings/java/.../ZstdDecompressor.java and ZstdCompressor.java over libzsmi.so.
  * gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I include zsmi_jni.c -L zstandard_amd/lib -lzsmi -o libzsmi_jni.so */
 #include <jni.h>
 #include <stdint.h>
@@ -21,6 +21,28 @@ JNIEXPORT jlong JNICALL Java_com_epam_deltix_zstd_ZstdDecompressor_nDecompress(J
         /* the Java decoder takes exactly one frame per call and needs no trailing bytes (ZstdFrameDecompressor.java:157-225) */
         size_t const r = zsmi_decompress(dst, (size_t)maxLen, src, (size_t)inLen);
         if (zsmi_isError(r)) res = -(jlong)zsmi_getErrorCode(r);
+        else { (*env)->SetByteArrayRegion(env, out, outOff, (jsize)r, dst); res = (jlong)r; }
+    }
+    free(src); free(dst);
+    return res;
+}
+
+/* one frame for the whole input (zsmi_compress_advanced, no dictionary); checksum: the frame carries a Content_Checksum.  The frame is made in a
+ * buffer of zsmi_compressBound bytes and copied back when it fits maxLen */
+JNIEXPORT jlong JNICALL Java_com_epam_deltix_zstd_ZstdCompressor_nCompress(JNIEnv *env, jclass cls, jbyteArray in, jint inOff, jint inLen,
+                                                                           jbyteArray out, jint outOff, jint maxLen, jint level, jboolean checksum)
+{
+    (void)cls;
+    size_t const bound = zsmi_compressBound(inLen > 0 ? (size_t)inLen : 0);
+    jbyte *src = (jbyte *)malloc(inLen > 0 ? (size_t)inLen : 1), *dst = (jbyte *)malloc(bound);
+    jlong res;
+    if (!src || !dst) { free(src); free(dst); return -(jlong)ZSMI_error_memory_allocation; }
+    (*env)->GetByteArrayRegion(env, in, inOff, inLen, src);
+    if ((*env)->ExceptionCheck(env)) { free(src); free(dst); return -(jlong)ZSMI_error_GENERIC; }
+    {
+        size_t const r = zsmi_compress_advanced(dst, bound, src, (size_t)inLen, NULL, 0, (int)level, checksum ? 1 : 0);
+        if (zsmi_isError(r)) res = -(jlong)zsmi_getErrorCode(r);
+        else if (r > (size_t)(maxLen > 0 ? maxLen : 0)) res = -(jlong)ZSMI_error_dstSize_tooSmall;
         else { (*env)->SetByteArrayRegion(env, out, outOff, (jsize)r, dst); res = (jlong)r; }
     }
     free(src); free(dst);

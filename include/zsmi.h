@@ -78,8 +78,17 @@ size_t zsmi_compress(void *dst, size_t dstCapacity, const void *src, size_t srcS
  * for byte.  Errors: dictionary_corrupted (30) for a formatted dictionary the decoder would refuse, before anything runs on the device. */
 size_t zsmi_compress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level);
 
-/* replaces: commented macro ZSTD_COMPRESSBOUND  csharp/src/ZStd.cs:144-145 (plus this codec's per-64 KiB block headers) */
+/* replaces: commented macro ZSTD_COMPRESSBOUND  csharp/src/ZStd.cs:144-145 (plus this codec's per-64 KiB block headers).  Holds the
+ * largest frame this library writes for srcSize bytes, the 4 bytes of a content checksum included. */
 size_t zsmi_compressBound(size_t srcSize);
+
+/* The one-shot calls with a checksumFlag (ZSTD_c_checksumFlag).  checksumFlag != 0: the frame is the frame the call writes with 0, byte
+ * for byte, but for bit 2 of the Frame_Header_Descriptor (byte 4), set, and 4 more bytes behind the last block: the low 32 bits of XXH64
+ * (seed 0) of the content, little-endian.  A decoder (this one, libzstd) then answers checksum_wrong (22) for a frame whose content it cannot
+ * restore.  zsmi_compress_advanced with NULL / 0 and checksumFlag 0 is zsmi_compress; with a dictionary, zsmi_compress_usingDict.
+ * (zsmi_compress_usingCDict_advanced: declared with the digested dictionaries, below.) */
+size_t zsmi_compress_advanced(void *dst, size_t dstCapacity, const void *src, size_t srcSize,
+                              const void *dict, size_t dictSize, int level, int checksumFlag);
 
 /* ------------------------------------------------------------------------------------------
  * Batch calls: n independent chunks <-> n frames, the data-parallel hot path (no analogue in the
@@ -96,6 +105,20 @@ zsmi_ctx *zsmi_createCtx(int device, void *hipStream);
 void zsmi_freeCtx(zsmi_ctx *ctx);
 /* block until everything queued on the context's stream has finished; returns 0 or an error code value */
 int zsmi_sync(zsmi_ctx *ctx);
+
+/* Sticky compression parameters of a context (ZSTD_CCtx_setParameter).  A value is read on the host when a compress call is made and governs
+ * the work that call queues; calls queued before keep theirs.
+ *   ZSMI_c_checksumFlag (0 or 1; default 0): every frame of the compress calls on this context - zsmi_compressBatchDevice / Host, their
+ *   _usingDict, _usingCDict and _usingCDictSet forms, the frames of zsmi_compressSeekableDevice - carries a Content_Checksum: the frame the call
+ *   writes with 0, byte for byte, but for bit 2 of byte 4, set, and the low 32 bits of XXH64 (seed 0) of the chunk behind its last block;
+ *   dstSizes[i] grows by exactly 4 (zsmi_compressBound holds them).  A chunk whose dstSizes[i] is an error code is left as it is; an empty
+ *   chunk gets its checksum too.  One more kernel a call (k_frame_checksum), whose time is that of hashing the call's largest chunk; with 0 the
+ *   calls launch and write exactly what they did without the parameter.  Dictionary training never uses it.
+ * Checked in this order - a NULL ctx: init_missing; a param that is none of the above: parameter_unsupported; a value outside the
+ * parameter's range: parameter_outOfBound; zsmi_getParameter with a NULL value: GENERIC.  Return 0 or an error code value. */
+enum { ZSMI_c_checksumFlag = 201 };                         /* ZSTD_c_checksumFlag's number */
+int zsmi_setParameter(zsmi_ctx *ctx, int param, int value);
+int zsmi_getParameter(const zsmi_ctx *ctx, int param, int *value);
 
 /* Asynchronous on the context's stream.  dstOffsets[i] must leave zsmi_compressBound(srcSizes[i]) bytes.
  * Chunks may be any size >= 0; the codec cuts them in 64 KiB blocks inside one frame. */
@@ -132,6 +155,9 @@ int zsmi_compressBatchDevice_usingCDict(zsmi_ctx *ctx, const void *dSrc, const u
 int zsmi_compressBatchHost_usingCDict(zsmi_ctx *ctx, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                       uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, const zsmi_cdict *cd);
 size_t zsmi_compress_usingCDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd);
+/* the one-shot form with a checksumFlag, as zsmi_compress_advanced; 0: zsmi_compress_usingCDict */
+size_t zsmi_compress_usingCDict_advanced(void *dst, size_t dstCapacity, const void *src, size_t srcSize,
+                                         const zsmi_cdict *cd, int checksumFlag);
 
 /* ------------------------------------------------------------------------------------------
  * CDict sets: a read-only device table of digested compression dictionaries.  A compress call that takes a set gives chunk i the member
@@ -270,7 +296,9 @@ int zsmi_packFramesDevice(zsmi_ctx *ctx, const void *dFrames, const uint64_t *ds
  * Any zstd decoder reads an archive as concatenated frames (zsmi_decompress included).  Frame i holds src[i F, min((i + 1) F, srcSize)),
  * compressed exactly as chunk i of zsmi_compressBatchDevice at the same level.  frameSize F: 0 = 64 KiB, else 1 .. 1 GiB
  * (parameter_outOfBound otherwise); more than 0x8000000 frames: frameIndex_tooLarge.  checksumFlag: each entry carries the low 32 bits of
- * XXH64 (seed 0) of the frame's content.  An empty input is an archive of 0 frames (the 17-byte table alone).
+ * XXH64 (seed 0) of the frame's content; it is the table's flag alone.  The frames themselves carry a Content_Checksum when the context's
+ * ZSMI_c_checksumFlag is set (zsmi_compressSeekableDevice; the one-shot zsmi_compressSeekable writes none): Compressed_Size then includes the
+ * 4 bytes, and zsmi_seekableBound holds them either way.  An empty input is an archive of 0 frames (the 17-byte table alone).
  * Reading checks the table before anything runs on the device: prefix_unknown (a magic is wrong), corruption_detected (reserved descriptor
  * bits, Frame_Size against n, compressed sizes that do not add up to the bytes in front of the table, a Compressed_Size of 0, a
  * Decompressed_Size over 1 GiB), frameIndex_tooLarge (more than 0x8000000 frames), parameter_outOfBound (offset past the content).

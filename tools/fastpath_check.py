@@ -6,7 +6,8 @@ only this count shows it (ELF-class frames did so for two rounds).  Rows "ddict 
 (zsmi_createDDict): own CDict frames with a trained dictionary, own frames with a raw-content one, libzstd's with the trained one.  Rows
 "ddict set ..." are mixed batches through a DecompressionDictSet (zsmi_createDDictSet): own CDict frames of three trained dictionaries,
 interleaved, and a committed libzstd frame of a fourth - every frame decoded with the dictionary it names.  Rows "cdict set -> ddict set ..."
-are such batches compressed in one call through a CompressionDictSet (zsmi_createCDictSet) first.
+are such batches compressed in one call through a CompressionDictSet (zsmi_createCDictSet) first.  Row "checksum ..." is own frames written
+with the context's checksum parameter on (zsmi_setParameter): the fast path verifies their Content_Checksum itself.
 Prints one JSON object: shape -> [items on the fast path, items]."""
 import os; os.environ["ZSMI_DEBUG_LIB"] = "1"
 import sys, ctypes, json
@@ -61,6 +62,12 @@ def main():
         res[label] = [int((buf.reshape(-1, DESC_WORDS)[:n, FAST_AT] == 1).sum()) if ok else -1, n]
 
     run("own 32 KiB", [text[i * 32768:(i + 1) * 32768] for i in range(64)])
+    chunks = [text[i * 32768:(i + 1) * 32768] for i in range(64)]
+    bc.set_parameter("checksum", 1)
+    frames = B.frames_of(bc.compress_host(*B.batch(chunks), 3))
+    bc.set_parameter("checksum", 0)
+    assert all(f[4] & 4 for f in frames), "frames carry a Content_Checksum"
+    run("checksum: own 32 KiB frames that carry a Content_Checksum", chunks, frames=frames)
     run("own 128 KiB", [text[i * 40000:i * 40000 + 131072] for i in range(32)])
     run("own 1 MiB", [text[i * 70000:i * 70000 + (1 << 20)] for i in range(16)])
     run("own, raw and RLE blocks among compressed ones", [text[i * 50000:i * 50000 + 200000] + noise[i * 1000:i * 1000 + 70000] + bytes(70000) + text[:100000] for i in range(16)])

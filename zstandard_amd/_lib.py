@@ -94,6 +94,10 @@ def lib():
     L.zsmi_createCtx.restype = vp; L.zsmi_createCtx.argtypes = [i32, vp]
     L.zsmi_freeCtx.restype = None; L.zsmi_freeCtx.argtypes = [vp]
     L.zsmi_sync.restype = i32; L.zsmi_sync.argtypes = [vp]
+    L.zsmi_setParameter.restype = i32; L.zsmi_setParameter.argtypes = [vp, i32, i32]
+    L.zsmi_getParameter.restype = i32; L.zsmi_getParameter.argtypes = [vp, i32, ctypes.POINTER(i32)]
+    L.zsmi_compress_advanced.restype = sz; L.zsmi_compress_advanced.argtypes = [vp, sz, vp, sz, vp, sz, i32, i32]
+    L.zsmi_compress_usingCDict_advanced.restype = sz; L.zsmi_compress_usingCDict_advanced.argtypes = [vp, sz, vp, sz, vp, i32]
     L.zsmi_compressBatchDevice.restype = i32; L.zsmi_compressBatchDevice.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32]
     L.zsmi_decompressBatchDevice.restype = i32; L.zsmi_decompressBatchDevice.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zsmi_compressBatchHost.restype = i32; L.zsmi_compressBatchHost.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, i32]
@@ -200,4 +204,5 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo",
            "zsmi_openSeekable", "zsmi_openSeekableDevice", "zsmi_closeSeekable", "zsmi_getNumFrames_fromSeekable", "zsmi_getContentSize_fromSeekable",
            "zsmi_sizeofSeekable", "zsmi_seekableReadRangesDevice", "zsmi_seekableReadRangesHost",
-           "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID"]
+           "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
+           "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced"]

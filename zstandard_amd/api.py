@@ -240,10 +240,12 @@ class DecompressionDictSet:
 class ZstdCompressor:
     """One frame per call; level <= 2 fast parameters, level >= 3 default parameters.  dictionary: raw content or a formatted
     dictionary (ZSTD_compress_usingDict), or a CompressionDict (ZSTD_compress_usingCDict: its level holds); the frames decode with the
-    same dictionary (zsmi_decompress_usingDict)."""
+    same dictionary (zsmi_decompress_usingDict).  checksum: the frames of compress() carry a Content_Checksum (ZSTD_c_checksumFlag: the
+    low 32 bits of the content's XXH64 behind the last block, which every zstd decoder verifies); nothing else about them changes."""
 
-    def __init__(self, level=3, dictionary=None):
+    def __init__(self, level=3, dictionary=None, checksum=False):
         self.level = level
+        self.checksum = bool(checksum)
         self.cdict = dictionary if isinstance(dictionary, CompressionDict) else None
         self.dictionary = bytes(dictionary) if dictionary and not self.cdict else b""
 
@@ -256,7 +258,9 @@ class ZstdCompressor:
         s, sn = _buf(src)
         cap = L.zsmi_compressBound(sn)
         out = ctypes.create_string_buffer(cap)
-        call = (L.zsmi_compress_usingCDict, self.cdict.handle) if self.cdict else \
+        call = (L.zsmi_compress_usingCDict_advanced, self.cdict.handle, 1) if self.cdict and self.checksum else \
+               (L.zsmi_compress_advanced, self.dictionary or None, len(self.dictionary), self.level, 1) if self.checksum else \
+               (L.zsmi_compress_usingCDict, self.cdict.handle) if self.cdict else \
                (L.zsmi_compress_usingDict, self.dictionary, len(self.dictionary), self.level) if self.dictionary else \
                (L.zsmi_compress, self.level)
         r = call[0](out, cap, s, sn, *call[1:])
@@ -482,6 +486,31 @@ class BatchCodec:
         if rc:
             raise RuntimeError(f"device error {rc}")
 
+    PARAMETERS = {"checksum": 201}      # ZSMI_c_checksumFlag
+
+    def _parameter(self, name_or_id):
+        if isinstance(name_or_id, str):
+            if name_or_id not in self.PARAMETERS:
+                raise ValueError(f"no such parameter: {name_or_id!r} (known: {sorted(self.PARAMETERS)})")
+            return self.PARAMETERS[name_or_id]
+        return int(name_or_id)
+
+    def set_parameter(self, name_or_id, value):
+        """a sticky compression parameter of this codec (zsmi_setParameter), by name or by its number.  "checksum" (0 / 1): every frame
+        of the compress calls made after it carries a Content_Checksum - the same frames otherwise, 4 bytes longer - and a decoder
+        answers checksum_wrong (22) for a frame whose content it cannot restore.  RuntimeError with the error's name for a number or a
+        value the library refuses."""
+        rc = self.L.zsmi_setParameter(self.ctx, self._parameter(name_or_id), int(value))
+        if rc:
+            raise RuntimeError(f"zsmi_setParameter: {_error_name(self.L, rc)}")
+
+    def get_parameter(self, name_or_id) -> int:
+        v = ctypes.c_int(0)
+        rc = self.L.zsmi_getParameter(self.ctx, self._parameter(name_or_id), ctypes.byref(v))
+        if rc:
+            raise RuntimeError(f"zsmi_getParameter: {_error_name(self.L, rc)}")
+        return v.value
+
     @staticmethod
     def _p(a):
         return a.ctypes.data_as(ctypes.c_void_p)
@@ -552,7 +581,8 @@ class BatchCodec:
 
     def compress_seekable_device(self, d_src_ptr, src_size, d_dst_ptr, dst_capacity, d_archive_size_ptr, level=3, frame_size=0, checksum=True):
         """a seekable archive of d_src[0, src_size) at d_dst (asynchronous); *d_archive_size_ptr (device uint64) receives its size, or
-        (uint64)-code if a frame failed.  dst_capacity must be at least seekable_bound(src_size, frame_size, checksum)."""
+        (uint64)-code if a frame failed.  dst_capacity must be at least seekable_bound(src_size, frame_size, checksum).  checksum is the
+        table's; the frames carry their own Content_Checksum when the codec's "checksum" parameter is set."""
         rc = self.L.zsmi_compressSeekableDevice(self.ctx, ctypes.c_void_p(d_src_ptr), src_size, ctypes.c_void_p(d_dst_ptr), dst_capacity,
                                                 ctypes.c_void_p(d_archive_size_ptr), level, frame_size, int(bool(checksum)))
         if rc:

@@ -327,7 +327,7 @@ static int finalizeQueue(zsmi_ctx *c, const uint8_t *dSamples, const std::vector
     uint8_t *dHdr = (uint8_t *)(dId + 8);
     if (hipMemsetAsync(dStats, 0, sizeof(uint32_t) * kTrainStatWords, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     ZsCompressDict dict; dict.dBytes = dContent; dict.contentSize = contentSize;
-    if (const int e = compressBatchDeviceImpl(c, dSamples, offs.data(), sizes.data(), n, c->train.dArena.p, dof.data(), (uint32_t *)c->train.dSizes.p, level, &dict, dStats)) return e;
+    if (const int e = compressBatchDeviceImpl(c, dSamples, offs.data(), sizes.data(), n, c->train.dArena.p, dof.data(), (uint32_t *)c->train.dSizes.p, level, &dict, 0, dStats)) return e;
     LAUNCH(c, "k_train_id", k_train_id, dim3(1), dim3(64), 0, dContent, contentSize, dictID, dId);
     LAUNCH(c, "k_train_tables", k_train_tables, dim3(1), dim3(256), 0, (const uint32_t *)dStats, dContent, contentSize, cap, (const uint32_t *)dId, dHdr, dOut, dResult);
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
@@ -404,7 +404,7 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
         for (uint32_t i = 0; i < nc; i++) {
             ZsCompressDict dict; dict.dBytes = hc[i].content + hTails[i]; dict.contentSize = cap32 - hTails[i];
             uint32_t *dSizes = (uint32_t *)c->train.dSizes.p + (size_t)nt * i;
-            if (const int e = compressBatchDeviceImpl(c, dSamples, so.data(), ss.data(), nt, c->train.dArena.p, dof.data(), dSizes, t.level, dict.contentSize ? &dict : nullptr)) return e;
+            if (const int e = compressBatchDeviceImpl(c, dSamples, so.data(), ss.data(), nt, c->train.dArena.p, dof.data(), dSizes, t.level, dict.contentSize ? &dict : nullptr, 0)) return e;
         }
         std::vector<uint32_t> hs((size_t)nt * nc);
         if (hipMemcpyAsync(hs.data(), c->train.dSizes.p, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;

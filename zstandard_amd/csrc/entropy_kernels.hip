@@ -3,6 +3,7 @@
 //   k_encode_literals   (1 block, 4 wavefronts per workgroup)    -> literals section: gather, Huffman lengths / codes / description / streams;
 //                                                                    writes the frame of a one-block chunk as its workgroup finishes
 //   k_assemble_frames   (1 chunk per workgroup)                  -> frames of chunks of several blocks
+//   k_frame_checksum    (1 chunk per quad, 16 per workgroup)     -> checksumFlag: the Content_Checksum behind every frame of a call, once they are final
 //   k_train_stats       (1 block per workgroup)                  -> the dictionary trainer's finalize: counts of what the sequences kernel coded
 //   k_cdict_tables      (one workgroup)                          -> a digested dictionary's entropy tables in encoder form (ZsCDictTables)
 //   k_pack_offsets, k_pack_copy                                  -> frames in bound-sized slots packed back to back
@@ -1532,6 +1533,31 @@ extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAM
                              zs_block_lit_section(litSecAll, lb), zs_block_seq_section(seqSecAll, lb), tid, blockDim.x);
     }
     if (tid == 0) dstSizes[chunkBase + blockIdx.x] = pos;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_frame_checksum : the Content_Checksum of a call's frames (checksumFlag), a post-pass over frames that are already final: the low 32 bits
+// of XXH64 (seed 0) of the chunk's content go behind the last block, bit 2 of the Frame_Header_Descriptor is set and the size grows by 4 -
+// no other byte of the frame changes, so a checksummed frame is the plain frame plus these two edits whatever kernel assembled it.
+// One quad a chunk (16 a wavefront, as k_seek_hash); a chunk whose size is an error code is left as it is.  A chunk's hash is one serial
+// chain: the launch takes as long as the call's largest chunk, whatever the batch.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_frame_checksum(const uint8_t *__restrict__ src, const ZsChunkDesc *__restrict__ chunks, uint32_t n,
+                                                       uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes)
+{
+    const uint32_t q = blockIdx.x * 16 + (threadIdx.x >> 2);
+    const bool real = q < n;
+    ZsChunkDesc cd = {};
+    if (real) cd = chunks[q];
+    const uint32_t written = real ? dstSizes[q] : 0xFFFFFFFFu;
+    // a frame to close: not an error code, and - always, the bound holds the 4 bytes - one that leaves them room in its slot
+    const bool work = written <= 0xFFFFFF88u && (uint64_t)written + 4 <= zs_compress_bound(cd.size);
+    const uint64_t h = xxh64_quad<16>(src + cd.srcOff, work ? cd.size : 0u);           // (every lane of a quad calls; a quad without work hashes nothing)
+    if (!work || (threadIdx.x & 3u) != 0) return;
+    uint8_t *out = dst + cd.dstOff, *t = out + written;
+    t[0] = (uint8_t)h; t[1] = (uint8_t)(h >> 8); t[2] = (uint8_t)(h >> 16); t[3] = (uint8_t)(h >> 24);
+    out[4] |= 0x04;
+    dstSizes[q] = written + 4;
 }
 
 static const uint32_t kTrainStatWords = 448;                                // literal bytes [0, 256), LL codes [256, 320), OF [320, 384), ML [384, 448)

@@ -226,8 +226,10 @@ extern "C" int zsmi_seekableFrameInfo(const void *src, size_t srcSize, uint32_t 
 }
 
 // ---- compress ----
+// checksumFlag: the table's (each entry carries its frame's hash); frameChecksum: the frames' own Content_Checksum (the context's
+// ZSMI_c_checksumFlag) - the two are independent
 static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize,
-                                int level, uint32_t frameSize, int checksumFlag)
+                                int level, uint32_t frameSize, int checksumFlag, int frameChecksum)
 {
     if (!c) return ZSMI_error_init_missing;
     uint64_t F, n64;
@@ -248,7 +250,7 @@ static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize,
         std::vector<uint64_t> so(n), dof(n);
         std::vector<uint32_t> ss(n);
         for (uint32_t i = 0; i < n; i++) { so[i] = (uint64_t)i * F; ss[i] = (uint32_t)std::min<uint64_t>(F, srcSize - so[i]); dof[i] = (uint64_t)i * stride; }
-        if (const int e = compressBatchDeviceImpl(c, dSrc, so.data(), ss.data(), n, c->seek.dStage.p, dof.data(), dSizes, level, nullptr)) return e;
+        if (const int e = compressBatchDeviceImpl(c, dSrc, so.data(), ss.data(), n, c->seek.dStage.p, dof.data(), dSizes, level, nullptr, frameChecksum)) return e;
         if (checksumFlag) LAUNCH(c, "k_seek_hash", k_seek_hash, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, srcSize, F, n, dHash);
     }
     LAUNCH(c, "k_pack_offsets", k_pack_offsets, dim3(1), dim3(1024), 0, (const uint32_t *)dSizes, n, dPacked);
@@ -262,7 +264,7 @@ static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize,
 extern "C" int zsmi_compressSeekableDevice(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, void *dDst, uint64_t dstCapacity,
                                            uint64_t *dArchiveSize, int level, uint32_t frameSize, int checksumFlag)
 {
-    return compressSeekableImpl(c, dSrc, srcSize, dDst, dstCapacity, dArchiveSize, level, frameSize, checksumFlag);
+    return compressSeekableImpl(c, dSrc, srcSize, dDst, dstCapacity, dArchiveSize, level, frameSize, checksumFlag, c ? c->checksumFlag : 0);
 }
 extern "C" size_t zsmi_compressSeekable(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level, uint32_t frameSize, int checksumFlag)
 {
@@ -274,7 +276,7 @@ extern "C" size_t zsmi_compressSeekable(void *dst, size_t dstCapacity, const voi
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
     if (!c->sSrc.reserve(srcSize + 64) || !c->sDst.reserve(bound + 64) || !c->sSizes.reserve(sizeof(uint64_t))) return ZSMI_ERR(ZSMI_error_memory_allocation);
     if (srcSize && hipMemcpyAsync(c->sSrc.p, src, srcSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
-    if (const int rc = compressSeekableImpl(c, c->sSrc.p, srcSize, c->sDst.p, bound, (uint64_t *)c->sSizes.p, level, frameSize, checksumFlag)) {
+    if (const int rc = compressSeekableImpl(c, c->sSrc.p, srcSize, c->sDst.p, bound, (uint64_t *)c->sSizes.p, level, frameSize, checksumFlag, 0)) {
         (void)hipStreamSynchronize(c->stream);
         return ZSMI_ERR(rc);
     }

@@ -9,7 +9,7 @@
 #include "zsmi_wave.h"            // device primitives of more than one kernel file: wave_*, zs_block_copy, rd16/24/32, xxh64_quad
 #include "zsmi_frame.h"           // the readers of the container headers (frame, block, literals section, stream split): device and host
 #include "lz_kernels.hip"         // encoder, LZ stage: k_lz_candidates, k_lz_walk, k_lz_stitch, k_lz_dict_tables
-#include "entropy_kernels.hip"    // encoder, entropy stage: k_encode_sequences, k_encode_literals, k_assemble_frames; k_train_stats, k_pack_*
+#include "entropy_kernels.hip"    // encoder, entropy stage: k_encode_sequences, k_encode_literals, k_assemble_frames, k_frame_checksum; k_train_stats, k_pack_*
 #include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares; loadDictEntropy, the one reader of a dictionary
 #include "decode_fast.hip"        // fast decode path: k_dec_prep, k_dec_huffman, k_dec_sequences, k_dec_entropy, k_dec_execute, k_dec_checksum, k_dec_collect; k_dict_load (a dictionary -> its record for the host, a DDict's image)
 #include "zsmi_ctx.h"             // host: zsmi_ctx and its buffers, LAUNCH, the batch entry points the features call
@@ -67,7 +67,7 @@ extern "C" const char *zsmi_versionString(void) { return "zsmi 0.3 (gfx950 HIP k
 
 extern "C" size_t zsmi_compressBound(size_t srcSize)
 {
-    return srcSize + (srcSize >> 8) + ((srcSize < (128u << 10)) ? (((128u << 10) - srcSize) >> 11) : 0) + 3 * (srcSize / ZS_BLOCK_MAX + 1) + 18;
+    return (size_t)zs_compress_bound(srcSize);
 }
 
 // ---- ZStdDecompress.cs:518-532, 617-622: the content size the first frame's header states; 0 where it states none, is no zstd frame
@@ -155,6 +155,23 @@ extern "C" int zsmi_sync(zsmi_ctx *c)
 {
     if (!c) return ZSMI_error_init_missing;
     return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+// ---- sticky compression parameters (ZSTD_CCtx_setParameter): read on the host when a compress call is made, they govern what is queued after ----
+extern "C" int zsmi_setParameter(zsmi_ctx *c, int param, int value)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (param != ZSMI_c_checksumFlag) return ZSMI_error_parameter_unsupported;
+    if (value != 0 && value != 1) return ZSMI_error_parameter_outOfBound;
+    c->checksumFlag = value;
+    return 0;
+}
+extern "C" int zsmi_getParameter(const zsmi_ctx *c, int param, int *value)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (param != ZSMI_c_checksumFlag) return ZSMI_error_parameter_unsupported;
+    if (!value) return ZSMI_error_GENERIC;
+    *value = c->checksumFlag;
+    return 0;
 }
 extern "C" int zsmi_enableKernelTiming(zsmi_ctx *c, int on)
 {
@@ -370,9 +387,11 @@ static void launchDictTables(zsmi_ctx *c, const ZsCompressDict &d, int level, vo
 // The kernels take the dictionary as a table of records (ZsCDictEntry) and an index a chunk; a single dictionary is the one-entry table
 // with no index.  A call without a dictionary is one with no prefixed units.  dStats (the dictionary trainer's finalize; nullptr on every other path): device
 // counters of the literal bytes and LL / OF / ML codes, added to by k_train_stats after each sub-batch's sequences kernel.
+// checksum: behind the last sub-batch, when every frame and size of the call is final on the stream, k_frame_checksum closes the frames
+// with their Content_Checksum - one launch over all n chunks.  Without it the call launches nothing more and writes nothing else.
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const ZsCompressDict *dict, uint32_t *dStats, const ZsCompressDictSet *set)
+                                   const ZsCompressDict *dict, int checksum, uint32_t *dStats, const ZsCompressDictSet *set)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
@@ -447,26 +466,34 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
                    (const ZsBlockDesc *)P.dBlocks.p, S.metas(), S.litSec(), S.seqSec(), block0,
                    (uint8_t *)dDst, dDstSizes, chunk0, dictID, cdt, dChunkDict);
     }
+    if (checksum && !c->stopAfterWalk && !c->stopLit && !c->stopSeq)     // (a stopped stage leaves no frames to close)
+        LAUNCH(c, "k_frame_checksum", k_frame_checksum, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, dChunks, n, (uint8_t *)dDst, dDstSizes);
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
 extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                         uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level)
 {
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr);
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, c ? c->checksumFlag : 0);
 }
 // dDict: device memory.  The dictionary loader runs over it and its record (a formatted dictionary's ID, recent offsets and content
 // offset, or the refusal) is read back: the call waits for the context's stream once.
-extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                                  uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                                  const void *dDict, size_t dictSize)
+static int compressBatchDeviceUsingDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                        uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
+                                        const void *dDict, size_t dictSize, int checksum)
 {
-    if (!dDict || dictSize == 0) return zsmi_compressBatchDevice(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level);
+    if (!dDict || dictSize == 0) return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, checksum);
     if (!c) return ZSMI_error_init_missing;
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
     ZsCompressDict d;
     if (const int e = loadDict(c, dDict, dictSize, d)) return e;
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &d);
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &d, checksum);
+}
+extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                  uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
+                                                  const void *dDict, size_t dictSize)
+{
+    return compressBatchDeviceUsingDict(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, dDict, dictSize, c ? c->checksumFlag : 0);
 }
 
 // ---- digested dictionaries (ZSTD_createCDict / ZSTD_compress_usingCDict): loaded once, everything a call needs kept in device memory - the
@@ -525,7 +552,7 @@ extern "C" int zsmi_compressBatchDevice_usingCDict(zsmi_ctx *c, const void *dSrc
 {
     int level; const ZsCompressDict *dict;
     if (const int e = resolveCDict(c, cd, level, dict)) return e;
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, dict);
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, dict, c ? c->checksumFlag : 0);
 }
 
 // ---- CDict sets: a read-only device table with one record (ZsCDictEntry) per member, in the caller's order; a call with a set gives chunk i
@@ -596,7 +623,7 @@ extern "C" int zsmi_compressBatchDevice_usingCDictSet(zsmi_ctx *c, const void *d
 {
     int level; CDictSetCall call;
     if (const int e = resolveCDictSet(c, set, dictIndex, n, level, call)) return e;
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, nullptr, call.use ? &call.sel : nullptr);
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, c->checksumFlag, nullptr, call.use ? &call.sel : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1048,42 +1075,48 @@ static std::vector<uint32_t> compressBounds(const uint32_t *srcSizes, uint32_t n
     for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
     return bounds;
 }
-// dict: the call's dictionary (a digested one's descriptor), or nullptr
+// dict: the call's dictionary (a digested one's descriptor), or nullptr; checksum: as compressBatchDeviceImpl's
 static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, void *dst, const uint64_t *dstOffsets,
-                                 uint32_t *dstSizes, int level, const ZsCompressDict *dict, const ZsCompressDictSet *set = nullptr)
+                                 uint32_t *dstSizes, int level, const ZsCompressDict *dict, int checksum, const ZsCompressDictSet *set = nullptr)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, compressBounds(srcSizes, n).data(), dstSizes, nullptr, 0,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict, nullptr, set);
+                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict, checksum, nullptr, set);
                   });
 }
 extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                       uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level)
 {
-    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr);
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, c ? c->checksumFlag : 0);
 }
 // the dictionary is staged with the sources, and the run step is the device form on the staged bytes (which loads and checks them: its one
 // wait, then the staged call's own for the results)
-extern "C" int zsmi_compressBatchHost_usingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                                uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
-                                                const void *dict, size_t dictSize)
+static int compressBatchHostUsingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                      uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
+                                      const void *dict, size_t dictSize, int checksum)
 {
-    if (!dict || dictSize == 0) return zsmi_compressBatchHost(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level);
+    if (!dict || dictSize == 0) return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, checksum);
     if (!c) return ZSMI_error_init_missing;
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
     return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, compressBounds(srcSizes, n).data(), dstSizes, dict, dictSize,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      return zsmi_compressBatchDevice_usingDict(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, c->sDict.p, dictSize);
+                      return compressBatchDeviceUsingDict(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, c->sDict.p, dictSize, checksum);
                   });
+}
+extern "C" int zsmi_compressBatchHost_usingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                                uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
+                                                const void *dict, size_t dictSize)
+{
+    return compressBatchHostUsingDict(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict, dictSize, c ? c->checksumFlag : 0);
 }
 extern "C" int zsmi_compressBatchHost_usingCDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                  uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, const zsmi_cdict *cd)
 {
     int level; const ZsCompressDict *dict;
     if (const int e = resolveCDict(c, cd, level, dict)) return e;
-    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict);
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict, c ? c->checksumFlag : 0);
 }
 extern "C" int zsmi_compressBatchHost_usingCDictSet(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                     uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes,
@@ -1091,7 +1124,7 @@ extern "C" int zsmi_compressBatchHost_usingCDictSet(zsmi_ctx *c, const void *src
 {
     int level; CDictSetCall call;
     if (const int e = resolveCDictSet(c, set, dictIndex, n, level, call)) return e;
-    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, call.use ? &call.sel : nullptr);
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, c->checksumFlag, call.use ? &call.sel : nullptr);
 }
 // dict / dictSize: the call's dictionary in host memory, which this call stages; or digested: the selector of digested ones (a DDict's or a
 // set's), whose bytes are on the device already
@@ -1195,8 +1228,10 @@ extern "C" size_t zsmi_decodeScratchBytes(zsmi_ctx *c)
     return c->dec.held();
 }
 
-// one frame through a borrowed context: with the digested dictionary cd, or at `level` with the dictionary's bytes (or with none)
-static size_t compressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level, const void *dict, size_t dictSize, const zsmi_cdict *cd)
+// one frame through a borrowed context: with the digested dictionary cd, or at `level` with the dictionary's bytes (or with none).
+// checksum: the call's own - the borrowed context's sticky state is neither read nor changed
+static size_t compressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level, const void *dict, size_t dictSize, const zsmi_cdict *cd,
+                              int checksum = 0)
 {
     if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
     Borrowed b; zsmi_ctx *c = b.c;
@@ -1206,8 +1241,10 @@ static size_t compressOneShot(void *dst, size_t dstCapacity, const void *src, si
     uint8_t *out = (uint8_t *)dst;
     if (dstCapacity < bound) { tmp.resize(bound); out = tmp.data(); }     // compress into a bound-sized buffer, then check the fit
     const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
-    const int rc = cd ? zsmi_compressBatchHost_usingCDict(c, src, &so, &ss, 1, out, &dof, &ds, cd)
-                      : zsmi_compressBatchHost_usingDict(c, src, &so, &ss, 1, out, &dof, &ds, level, dict, dictSize);
+    const ZsCompressDict *digested = nullptr;
+    int rc = cd ? resolveCDict(c, cd, level, digested) : 0;
+    if (!rc) rc = cd ? compressBatchHostImpl(c, src, &so, &ss, 1, out, &dof, &ds, level, digested, checksum)
+                     : compressBatchHostUsingDict(c, src, &so, &ss, 1, out, &dof, &ds, level, dict, dictSize, checksum);
     if (rc) return ZSMI_ERR(rc);
     if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
     if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
@@ -1226,6 +1263,15 @@ extern "C" size_t zsmi_compress_usingDict(void *dst, size_t dstCapacity, const v
 extern "C" size_t zsmi_compress_usingCDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd)
 {
     return compressOneShot(dst, dstCapacity, src, srcSize, 3, nullptr, 0, cd);
+}
+// the one-shot forms with a checksumFlag (0: the frames of the calls above, byte for byte; any other value: 1)
+extern "C" size_t zsmi_compress_advanced(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level, int checksumFlag)
+{
+    return compressOneShot(dst, dstCapacity, src, srcSize, level, dict, dictSize, nullptr, checksumFlag != 0);
+}
+extern "C" size_t zsmi_compress_usingCDict_advanced(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd, int checksumFlag)
+{
+    return compressOneShot(dst, dstCapacity, src, srcSize, 3, nullptr, 0, cd, checksumFlag != 0);
 }
 extern "C" size_t zsmi_decompress(void *dst, size_t dstCapacity, const void *src, size_t srcSize)
 {

@@ -78,6 +78,7 @@ struct zsmi_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool ownStream = false;
+    int checksumFlag = 0;                 // ZSMI_c_checksumFlag (zsmi_setParameter): the compress calls made on this context close their frames with a Content_Checksum
     uint32_t maxBlocksInFlight = 16384;   // ZSMI_BLOCKS_IN_FLIGHT: 64 KiB blocks per sub-batch (scratch ~0.6 MiB a block, reserved for what a call needs); 2 GiB of 128 KiB chunks: 8192: 86.5, 16384: 88.2, 32768: 89.4 GiB/s
     // compress workspace: the plan of the call's layout and the scratch of a sub-batch (its sizes: the compress section of zsmi_api.hip)
     CompressPlan plan;
@@ -170,9 +171,11 @@ struct ZsCompressDictSet {
     const ZsCDictEntry *dTable; const uint8_t *memberHasDict; bool tables;
     const uint32_t *dictIndex;
 };
+// checksum: the frames carry a Content_Checksum (k_frame_checksum).  An argument, not the context's flag: the public calls pass c->checksumFlag,
+// the one-shot _advanced calls their own, the dictionary trainer 0 - what it trains must not depend on the context's state
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const ZsCompressDict *dict, uint32_t *dStats = nullptr, const ZsCompressDictSet *set = nullptr);
+                                   const ZsCompressDict *dict, int checksum, uint32_t *dStats = nullptr, const ZsCompressDictSet *set = nullptr);
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                      const struct ZsDictSel *dict);

@@ -86,6 +86,13 @@ struct ZsCDictEntry {
     uint32_t pfx, dictID, rep[3], pad;
 };
 
+// zsmi_compressBound: the most a frame of srcSize content bytes takes, header, every block raw and the content checksum included.  Stated
+// here because k_frame_checksum holds a frame's size against it before it writes behind the frame
+__host__ __device__ __forceinline__ uint64_t zs_compress_bound(uint64_t srcSize)
+{
+    return srcSize + (srcSize >> 8) + ((srcSize < (128u << 10)) ? (((128u << 10) - srcSize) >> 11) : 0) + 3 * (srcSize / ZS_BLOCK_MAX + 1) + 18;
+}
+
 // unaligned little-endian loads.  memcpy keeps the alignment-1 fact visible to the compiler: a cast to an over-aligned
 // pointer lets it turn a wave-uniform address into a scalar load, which drops the low address bits.  (Host code reads
 // container headers with the same loads: the host is little-endian too.)
