@@ -43,18 +43,15 @@ def main():
             hashable = max(n0 - 7, 0)                                         # (behind the hashable positions the scratch holds whatever: the walk cuts them off)
             bad = np.nonzero(dist_e[:hashable] != dist_g[:hashable])[0]
             print(f"   dist mismatches (unit 0): {len(bad)}", bad[:8], dist_e[bad[:8]], dist_g[bad[:8]])
-            # the parse: sequences per block as the stitch kernel leaves them (64 output ranges x 256 records) against oracle E's
+            # the parse: sequences per block as the stitch kernel leaves them (a list a block, its count in the block's header) against oracle E's
             seq_e = np.zeros(3 * 65536 * nblk, dtype=np.uint32); ns_e = np.zeros(2, dtype=np.uint32)
             L.zso_debugWalk(seq_e.ctypes.data_as(ctypes.c_void_p), ns_e.ctypes.data_as(ctypes.c_void_p), blk, n0, 3)
-            hdr_g = _lib.copy_scratch(bc.ctx, "hdrs", nblk).view(np.uint32).reshape(nblk, 64, 4)
-            seq_g = _lib.copy_scratch(bc.ctx, "seqs", nblk).view(np.uint32).reshape(nblk, 64, -1, 2); o = 0
+            hdr_g = _lib.copy_scratch(bc.ctx, "hdrs", nblk).view(np.uint32).reshape(nblk, -1)
+            seq_g = _lib.copy_scratch(bc.ctx, "seqs", nblk).view(np.uint32).reshape(nblk, -1, 2); o = 0
             for b in range(nblk):
                 want = seq_e[3 * o:3 * (o + int(ns_e[b]))].reshape(-1, 3); o += int(ns_e[b])
-                got = []
-                for g in range(64):
-                    x, y = seq_g[b, g, :int(hdr_g[b, g, 0]), 0], seq_g[b, g, :int(hdr_g[b, g, 0]), 1]
-                    got.append(np.stack([y >> 16, (x >> 11) & 0x1FFFF, (y & 0xFFFF) | (((x >> 28) & 1) << 16)], axis=1))
-                got = np.concatenate(got)
+                x, y = seq_g[b, :int(hdr_g[b, 0]), 0], seq_g[b, :int(hdr_g[b, 0]), 1]
+                got = np.stack([y >> 16, (x >> 11) & 0x1FFFF, (y & 0xFFFF) | (((x >> 28) & 1) << 16)], axis=1)
                 mlen = min(len(got), len(want)); d = np.nonzero((got[:mlen] != want[:mlen]).any(axis=1))[0]
                 if len(got) != len(want) or len(d):
                     k = int(d[0]) if len(d) else mlen

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Development aid (GPU box): the walk kernel's output (sequences per block, read back from the scratch) against oracle E's parse, for a batch of
 N chunks of the Zipf log -- the entropy kernels are NOT launched (ZSMI_STOP_AFTER_WALK, debug-hooks library), so a wrong parse cannot take
-anything else down.  The records and range headers are read back by name (zsmi_dbg_copyScratch "seqs", "hdrs"), every block slot of the batch.
+anything else down.  The records and block headers are read back by name (zsmi_dbg_copyScratch "seqs", "hdrs"), every block slot of the batch.
 usage: walk_check.py [chunks] [chunk_size] [level] [calls]; exit 0: every block checked has oracle E's parse.  Run by
 tests/test_gpu_codec.py::test_walk_output_read_back_by_name."""
 import os, sys, ctypes
@@ -25,9 +25,10 @@ for _ in range(reps):
     bc.compress_host(data, offs, sizes, level)           # (the frames are not written: sizes come back as they were)
 bpc = (cs + 65535) // 65536                              # blocks per chunk
 nb = n * bpc
-# a block's slot (sized by the library: csrc/zsmi_scratch.h): 64 output ranges - a header of 4 words each, and each range's record slots of 2 words
-hdr = _lib.copy_scratch(bc.ctx, "hdrs", nb).view(np.uint32).reshape(nb, 64, 4)
-seq = _lib.copy_scratch(bc.ctx, "seqs", nb).view(np.uint32).reshape(nb, 64, -1, 2)
+# a block's slot (sized by the library: csrc/zsmi_scratch.h): its header in the slot's first words (sequences, trailing literals, all literals),
+# and its list of records of 2 words, in block order
+hdr = _lib.copy_scratch(bc.ctx, "hdrs", nb).view(np.uint32).reshape(nb, -1)
+seq = _lib.copy_scratch(bc.ctx, "seqs", nb).view(np.uint32).reshape(nb, -1, 2)
 bad = 0
 step = max(1, n // 64)
 for ci in list(range(0, n, step)) + [n - 1]:
@@ -40,13 +41,14 @@ for ci in list(range(0, n, step)) + [n - 1]:
         for bi in range((len(unit) + 65535) // 65536):
             b = ci * bpc + u0 // 65536 + bi
             want = se[3 * o:3 * (o + int(ne[bi]))].reshape(-1, 3); o += int(ne[bi])
-            got = []
-            for g in range(64):
-                nsq, first = int(hdr[b, g, 0]), int(hdr[b, g, 3])
-                if nsq > seq.shape[2] or first != 0: got = None; break
-                x, y = seq[b, g, :nsq, 0], seq[b, g, :nsq, 1]
-                got.append(np.stack([y >> 16, (x >> 11) & 0x1FFFF, (y & 0xFFFF) | (((x >> 28) & 1) << 16)], axis=1))
-            got = np.concatenate(got) if got is not None else None
+            nsq, trailing, nlit = (int(v) for v in hdr[b, :3])
+            got = None
+            if nsq <= seq.shape[1]:
+                x, y = seq[b, :nsq, 0], seq[b, :nsq, 1]
+                got = np.stack([y >> 16, (x >> 11) & 0x1FFFF, (y & 0xFFFF) | (((x >> 28) & 1) << 16)], axis=1)
+                size = min(65536, len(unit) - 65536 * bi)
+                covered = int(want[:, 1].sum())                      # the header's literal counts against the parse's
+                if size >= 16 and (nlit != size - covered or trailing != size - (int(want[-1, 0] + want[-1, 1]) if len(want) else 0)): got = None
             if got is None or got.shape != want.shape or (got != want).any():
                 bad += 1
                 if bad <= 5:

@@ -19,7 +19,7 @@
 #ifndef ZSMI_ENTROPY_KERNELS_HIP        // (dict_train.hip and seekable.hip include this file too)
 #define ZSMI_ENTROPY_KERNELS_HIP
 #include "zsmi_device.h"
-#include "zsmi_scratch.h"         // the scratch slots of a block (records, range headers, literals, streams, sections, meta: ZsBlockMeta) and what the sequences kernel borrows
+#include "zsmi_scratch.h"         // the scratch slots of a block (its list of records, its header, literals, streams, sections, meta: ZsBlockMeta) and what the sequences kernel borrows
 #include "zsmi_wave.h"
 #include "zsmi_fse.h"            // the alphabets' constants, FseBuild, the table builder's two routines
 // timing aids of the development tools (tools/time_kernels.py): end a kernel after a stage.  Compiled in only with
@@ -129,8 +129,6 @@ struct K3Lds {                       // literals kernel
         struct { uint32_t T[2052]; uint32_t wpar[4], wcnt[4]; uint32_t sel[16]; } gm;   // literal gather: a bit per block byte (toggles at match ends -> inside a match -> literal), per-wavefront parities / literal counts, byte-compaction selectors
     } u;
     uint32_t misc[16];
-    uint32_t rngN[ZS_WALK_RANGES], rngCarry[ZS_WALK_RANGES], litBase[ZS_WALK_RANGES];
-    uint8_t  rngFirst[ZS_WALK_RANGES];   // index of a range's first record that counts (after the walk kernel's stitch)
     uint32_t wcount[16]; int16_t wnorm[16]; uint32_t rankStart[16], rankCount[16];   // small tables kept out of scratch memory
 };
 // cd[] lies below pm.S, which huffCodesAndWeights writes before k_cdict_tables builds its tables; fse (wave 0, the table description)
@@ -146,8 +144,6 @@ struct SeqLds {                      // sequences kernel.  Kept under 10 KiB: 16
     } u;
     uint32_t tile[208];              // bit-packing tile
     uint32_t misc[16];
-    uint32_t rngN[ZS_WALK_RANGES], rngCarry[ZS_WALK_RANGES], rngStart[ZS_WALK_RANGES + 1];
-    uint8_t  rngFirst[ZS_WALK_RANGES];   // index of a range's first record that counts (after the walk kernel's stitch)
 };
 
 // Wave-cooperative forward bit writer.  Each put() appends, lane 0 first, up to 96 bits per lane.
@@ -561,28 +557,6 @@ __device__ __forceinline__ int lastFlagBelow(bool flag)
     return below ? 63 - __builtin_clzll(below) : -1;
 }
 
-// Range bookkeeping by one wavefront, lane r = walk range r (64 ranges):
-//   rngN[r] sequences, rngStart[r] index of its first sequence in block order, rngCarry[r] literals carried into its first
-//   sequence (trailing literals of the ranges since the last one that had a sequence), litBase[r] (optional) index of its
-//   first own literal; returns the literals left after the last sequence of the block and the total literal count.
-__device__ __forceinline__ void loadRangesWave(const ZsRangeHdr *hdr, uint32_t *rngN, uint32_t *rngCarry, uint32_t *rngStart, uint32_t *litBase, uint8_t *rngFirst,
-                                               uint32_t *lastLits, uint32_t *allLits)
-{
-    const uint32_t lane = (uint32_t)zs_lane();
-    const ZsRangeHdr h = hdr[lane];
-    const uint32_t ns = h.nseq, tr = h.trailing, lsum = h.litSum + h.trailing;
-    const uint32_t nsIncl = wave_incl_scan(ns), trIncl = wave_incl_scan(tr), lsIncl = wave_incl_scan(lsum);
-    const uint32_t P = trIncl - tr;                                     // trailing literals of the ranges before me
-    const int j = lastFlagBelow(ns != 0);
-    const uint32_t Pj = (uint32_t)__shfl((int)P, max(j, 0));
-    rngN[lane] = ns; rngFirst[lane] = (uint8_t)h.first; if (rngStart) rngStart[lane] = nsIncl - ns; rngCarry[lane] = (j >= 0) ? P - Pj : P;
-    if (litBase) litBase[lane] = lsIncl - lsum;
-    const uint64_t has = __ballot(ns != 0);
-    const uint32_t total = wave_last(trIncl);
-    const uint32_t Plast = has ? wave_get(P, 63 - __builtin_clzll(has)) : 0u;
-    if (lane == 63) { if (rngStart) rngStart[ZS_WALK_RANGES] = nsIncl; *lastLits = has ? total - Plast : total; *allLits = lsIncl; }
-}
-
 struct ZsChunkDesc { uint64_t srcOff; uint64_t dstOff; uint32_t size; uint32_t firstBlock; uint32_t nBlocks; uint32_t pad; };
 
 // frame header of a chunk (magic + FHD + FCS, single segment); returns its size.  One thread writes it.
@@ -638,7 +612,7 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
 //  frame is coded as Treeless literals (type 3) iff every literal byte has a code and that section is strictly smaller than the one the
 //  rules below produce)
 #define ZS_LIT_PARAMS const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, \
-                      const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
+                      const ZsSeqRec *__restrict__ seqAll, const uint32_t *__restrict__ hdrAll, \
                       uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, uint8_t *__restrict__ litSecAll, \
                       ZsBlockMeta *__restrict__ metas, int stopAt, \
                       const ZsChunkDesc *__restrict__ chunks, const uint8_t *__restrict__ seqSecAll, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes
@@ -663,7 +637,6 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     const uint8_t *s = src + bd.srcOff;
     const uint32_t n = bd.size;
     const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
-    const ZsRangeHdr *hdr = zs_block_range_hdrs(hdrAll, blk);
     uint8_t *lits = zs_block_lits(litsAll, blk);
     uint8_t *streams = zs_block_streams(streamAll, blk);
     // the literal section of a one-block chunk is built where its frame wants it (behind the frame header and the 3-byte block header: the
@@ -704,9 +677,8 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     }
     if (n < 16) FINISH(0, 0, 0);
 
-    if (wave == 0) loadRangesWave(hdr, L.rngN, L.rngCarry, nullptr, L.litBase, L.rngFirst, &L.misc[1], &L.misc[2]);
-    __syncthreads();
-    const uint32_t nlit = L.misc[2];
+    const ZsBlockHdr bh = zs_block_hdr(hdrAll, blk);                       // (the workgroup's one address)
+    const uint32_t nseq = bh.nseq, nlit = bh.lits;
 
     // ---- literals: gather into lits[], histogram ----
     uint32_t *hist = L.u.hist[lane & 7u];                                  // this lane's private histogram
@@ -716,8 +688,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     // The literals of a block are its bytes outside every match, in order.  So: a bit per byte, toggled at every match start and
     // end (LDS atomics, lane = sequence); a prefix xor turns the toggles into "inside a match"; the rest is a stream compaction of
     // the source, 16 bytes a lane and round, every lane busy with contiguous, coalesced bytes.  (Taking the literal runs sequence by
-    // sequence - a run of ~3 bytes per lane, its own load and store pieces - was ~300 instructions per 64 sequences, issue-bound; that
-    // form is gone, and with it the only reader of rngCarry, litBase and misc[1], which loadRangesWave still fills.)
+    // sequence - a run of ~3 bytes per lane, its own load and store pieces - was ~300 instructions per 64 sequences, issue-bound.)
     if (!ungathered) {
         uint32_t *T = L.u.gm.T;
         for (uint32_t i = tid; i < 2052; i += 256) T[i] = 0;
@@ -728,29 +699,22 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
             L.u.gm.sel[tid] = sel;
         }
         __syncthreads();
-        // 1. toggles.  Wavefront w takes ranges w, w + 4, ...; four ranges at a time, their record loads (<= 4 per lane and range) issued together
-        for (uint32_t r0 = wave; r0 < ZS_WALK_RANGES; r0 += 16) {
-            uint2 rec[4][4]; uint32_t ns[4];
+        // 1. toggles, a lane a record of the block's list: tile 4 q + w of a sweep of 64 tiles is wavefront w's; its 16 record loads are issued together
+        for (uint32_t g0 = 0; g0 < nseq; g0 += 64u * 64u) {
+            uint2 rec[16];
             #pragma unroll
-            for (uint32_t g = 0; g < 4; g++) {
-                const uint32_t r = r0 + 4 * g;
-                ns[g] = (r < ZS_WALK_RANGES) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)L.rngN[r]) : 0u;
-                const ZsSeqRec *rb = zs_range_seqs(seqBase, min(r, (uint32_t)ZS_WALK_RANGES - 1)) + L.rngFirst[min(r, (uint32_t)ZS_WALK_RANGES - 1)];
-                #pragma unroll
-                for (uint32_t q = 0; q < 4; q++) {
-                    rec[g][q] = make_uint2(0, 0);
-                    if (64 * q < ns[g] && lane + 64 * q < ns[g]) rec[g][q] = *reinterpret_cast<const uint2 *>(rb + lane + 64 * q);
-                }
+            for (uint32_t q = 0; q < 16; q++) {
+                const uint32_t t0 = g0 + 64u * (4u * q + wave);
+                rec[q] = make_uint2(0, 0);
+                if (t0 < nseq && t0 + lane < nseq) rec[q] = *reinterpret_cast<const uint2 *>(seqBase + t0 + lane);
             }
             #pragma unroll
-            for (uint32_t g = 0; g < 4; g++) {
-                #pragma unroll
-                for (uint32_t q = 0; q < 4; q++) {
-                    if (64 * q < ns[g] && lane + 64 * q < ns[g]) {
-                        const uint32_t p0 = zs_rec_pos(rec[g][q].y), p1 = p0 + zs_rec_ml(rec[g][q].x);
-                        atomicXor(&T[p0 >> 5], 1u << (p0 & 31u));
-                        atomicXor(&T[p1 >> 5], 1u << (p1 & 31u));
-                    }
+            for (uint32_t q = 0; q < 16; q++) {
+                const uint32_t t0 = g0 + 64u * (4u * q + wave);
+                if (t0 < nseq && t0 + lane < nseq) {
+                    const uint32_t p0 = zs_rec_pos(rec[q].y), p1 = p0 + zs_rec_ml(rec[q].x);
+                    atomicXor(&T[p0 >> 5], 1u << (p0 & 31u));
+                    atomicXor(&T[p1 >> 5], 1u << (p1 & 31u));
                 }
             }
         }
@@ -1054,7 +1018,7 @@ __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PA
 #endif
 // reps: the recent offsets a chunk's first block starts from ({1, 4, 8}, or a formatted dictionary's own) - the form without CD; with CD
 // they are the chunk's record's (dictTab[chunkDict[chunk]], ZsCDictEntry)
-#define ZS_SEQ_PARAMS const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, const ZsSeqRec *__restrict__ seqAll, const ZsRangeHdr *__restrict__ hdrAll, \
+#define ZS_SEQ_PARAMS const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, const ZsSeqRec *__restrict__ seqAll, const uint32_t *__restrict__ hdrAll, \
                       uint8_t *__restrict__ seqSecAll, ZsBlockMeta *__restrict__ metas, int stopAt, uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, \
                       uint2 *__restrict__ packRecAll
 #define ZS_SEQ_ARGS blocks, nBlocks, seqAll, hdrAll, seqSecAll, metas, stopAt, litsAll, streamAll, packRecAll
@@ -1088,7 +1052,6 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
     }
     const uint32_t n = bd.size;
     const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
-    const ZsRangeHdr *hdr = zs_block_range_hdrs(hdrAll, blk);
     uint8_t *out = zs_block_seq_section(seqSecAll, blk);
     const uint32_t cap = n + 512;
     // scratch of part 2's state chains and of the packing, borrowed (zsmi_scratch.h says from whom and until when)
@@ -1103,11 +1066,9 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
     bool live = false;                                  // this wavefront has a bitstream to write in part 2
     do {
         if (!exists || n < 16) break;
-        loadRangesWave(hdr, L.rngN, L.rngCarry, L.rngStart, nullptr, L.rngFirst, &L.misc[1], &L.misc[2]);
+        nseq = (uint32_t)__builtin_amdgcn_readfirstlane((int)zs_block_hdr(hdrAll, blk).nseq);
         for (uint32_t i = lane; i < 192; i += 64) L.count[i] = 0;
         wave_sync();
-        nseq = L.rngStart[ZS_WALK_RANGES];
-        const uint32_t *rngN = L.rngN, *rngCarry = L.rngCarry;
 
         // ---- sequences section header (inverse of DecodeSeqHeaders, ZStdDecompress.cs:1110-1180) ----
         uint32_t hdrBytes = (nseq < 128) ? 1 : (nseq < 0x7F00 ? 2 : 3);
@@ -1126,35 +1087,28 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
         {
             uint32_t cPrev, cA, cB;                       // carried: previous offset (= rep0), rep1, rep2
             if (bd.firstInChunk) { cPrev = rep0; cA = rep1; cB = rep2; } else { cPrev = 0xFFFFFFF1u; cA = 0xFFFFFFF2u; cB = 0xFFFFFFF3u; }
-            // sequences are taken 64 at a time in block order, whatever walk range they belong to; the records of the next 64 are
-            // loaded while these are worked on (their addresses depend on nothing that is carried)
-            auto locate = [&](uint32_t g, uint32_t &kOut, uint32_t &rrOut) -> const ZsSeqRec * {
-                uint32_t rr = 0;
-                #pragma unroll
-                for (uint32_t stepb = ZS_WALK_RANGES / 2; stepb >= 1; stepb >>= 1) if (g >= L.rngStart[rr + stepb]) rr += stepb;
-                kOut = g - L.rngStart[rr]; rrOut = rr;
-                return zs_range_seqs(seqBase, rr) + L.rngFirst[rr] + kOut;
-            };
+            uint32_t cEnd = 0;                            // carried: where the sequence before ends in the block (its literals start there)
+            // tile t is the records [64 t, 64 t + 64) of the block's list; the records of the next tiles are loaded while these are worked on
             // (a record travels as its two raw words and is taken apart only where it is used: unpacked next to the load, the
             // compiler waits for the load on the spot).  ZS_SEQ_TB tiles of 64 are requested together and worked through one after the other:
             // a request a tile was a memory round trip a tile (the kernel's wavefronts spent half their time in s_waitcnt).
             constexpr uint32_t TB = ZS_SEQ_TB;
-            uint2 rawN[TB]; uint32_t kN[TB], rrN[TB];
+            uint2 rawN[TB];
             auto request = [&](uint32_t base) {
                 #pragma unroll
                 for (uint32_t t = 0; t < TB; t++) {
                     const uint32_t g = base + 64u * t + lane;
-                    rawN[t] = make_uint2(0, 0); kN[t] = 1; rrN[t] = 0;
-                    if (g < nseq) { const ZsSeqRec *rp = locate(g, kN[t], rrN[t]); rawN[t] = *reinterpret_cast<const uint2 *>(rp); }
+                    rawN[t] = make_uint2(0, 0);
+                    if (g < nseq) rawN[t] = *reinterpret_cast<const uint2 *>(seqBase + g);
                 }
             };
             request(0);
             #pragma unroll
             for (uint32_t t = 0; t < TB; t++) asm volatile("" : "+v"(rawN[t].x), "+v"(rawN[t].y));     // the first records are waited for here, not inside the loop
             for (uint32_t base0 = 0; base0 < nseq; base0 += 64u * TB) {
-                uint2 rawC[TB]; uint32_t kC[TB], rrC[TB];
+                uint2 rawC[TB];
                 #pragma unroll
-                for (uint32_t t = 0; t < TB; t++) { rawC[t] = rawN[t]; kC[t] = kN[t]; rrC[t] = rrN[t]; }
+                for (uint32_t t = 0; t < TB; t++) rawC[t] = rawN[t];
                 if (base0 + 64u * TB < nseq) request(base0 + 64u * TB);
                 #pragma unroll
                 for (uint32_t t = 0; t < TB; t++) {
@@ -1162,9 +1116,12 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
                 if (base >= nseq) break;
                 const uint32_t g = base + lane;
                 const bool in = g < nseq;
-                const uint2 raw = rawC[t]; const uint32_t k = kC[t], rr = rrC[t];
-                uint32_t off = 0, ll = 0, ml = 0;
-                if (in) { off = zs_rec_off(raw.x, raw.y); ll = zs_rec_ll(raw.x); ml = zs_rec_ml(raw.x); if (k == 0) ll += rngCarry[rr]; }
+                const uint2 raw = rawC[t];
+                uint32_t off = 0, ll = 0, ml = 0, st = 0;
+                if (in) { off = zs_rec_off(raw.x, raw.y); ml = zs_rec_ml(raw.x); st = zs_rec_pos(raw.y); }
+                const uint32_t end = st + ml;
+                uint32_t prevEnd = ZS_DPP(0, end, 0x138, 0xF, true); if (lane == 0) prevEnd = cEnd;  // wave_shr:1        // where the sequence before me ends
+                if (in) ll = st - prevEnd;                                                            // the literals in front of me, however many
                 uint32_t prev = ZS_DPP(0, off, 0x138, 0xF, true); if (lane == 0) prev = cPrev;      // wave_shr:1        // rep0 before me
                 const bool change = in && !(ll > 0 && off == prev);
                 const int j = lastFlagBelow(change);                                                  // last changing sequence before me
@@ -1198,7 +1155,7 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
                 const uint32_t lastOff = wave_get(off, (int)(cnt - 1));
                 if (chm) { const int jl = 63 - __builtin_clzll(chm); cA = wave_get(prev, jl); }
                 if (rsm) { const int kl = 63 - __builtin_clzll(rsm); cB = wave_get(a, kl); }
-                cPrev = lastOff;
+                cPrev = lastOff; cEnd = wave_get(end, (int)(cnt - 1));
                 }
             }
         }
@@ -1565,24 +1522,20 @@ static const uint32_t kTrainStatWords = 448;                                // l
 // block's literal buffer (LL, OF with the recent-offset codes applied, ML; ZS_CHAIN_CODES apart), and the literal bytes - every block byte no match
 // of the block's records covers.  One workgroup a block, counts added to stats[kTrainStatWords].
 __global__ void __launch_bounds__(256) k_train_stats(const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, const ZsSeqRec *__restrict__ seqAll,
-                                                     const ZsRangeHdr *__restrict__ hdrAll, const uint8_t *__restrict__ litsAll, uint32_t *__restrict__ stats)
+                                                     const uint32_t *__restrict__ hdrAll, const uint8_t *__restrict__ litsAll, uint32_t *__restrict__ stats)
 {
-    __shared__ uint32_t cov[ZS_BLOCK_MAX / 32], hist[kTrainStatWords], rstart[ZS_WALK_RANGES + 1];
+    __shared__ uint32_t cov[ZS_BLOCK_MAX / 32], hist[kTrainStatWords];
     const uint32_t blk = blockIdx.x, tid = threadIdx.x;
     const ZsBlockDesc bd = blocks[blk];
     const uint32_t n = bd.size;
     for (uint32_t i = tid; i < ZS_BLOCK_MAX / 32; i += 256) cov[i] = 0;
     for (uint32_t i = tid; i < kTrainStatWords; i += 256) hist[i] = 0;
-    const ZsRangeHdr *hdr = zs_block_range_hdrs(hdrAll, blk);
-    if (tid == 0) { uint32_t s = 0; for (uint32_t r = 0; r < ZS_WALK_RANGES; r++) { rstart[r] = s; s += n >= 16 ? hdr[r].nseq : 0u; } rstart[ZS_WALK_RANGES] = s; }
     __syncthreads();
-    const uint32_t nseq = rstart[ZS_WALK_RANGES];
+    const uint32_t nseq = n >= 16 ? zs_block_hdr(hdrAll, blk).nseq : 0u;
     const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
     const uint8_t *codes = zs_lits_lend_chain_codes_to_stats(litsAll, blk);
     for (uint32_t g = tid; g < nseq; g += 256) {
-        uint32_t r = 0;
-        for (uint32_t st = ZS_WALK_RANGES / 2; st >= 1; st >>= 1) if (g >= rstart[r + st]) r += st;
-        const ZsSeqRec rec = seqBase[zs_range_seq_slot(r) + hdr[r].first + (g - rstart[r])];
+        const ZsSeqRec rec = seqBase[g];
         const uint32_t pos = zs_rec_pos(rec.y), end = min(pos + zs_rec_ml(rec.x), n);
         for (uint32_t b = pos; b < end;) {                                  // the match's bytes in the coverage bitmap
             const uint32_t w = b >> 5, lo = b & 31u, cnt = min(32u - lo, end - b);

@@ -380,8 +380,8 @@ k_lz_dict_tables(const ZsCDictEntry entry, ZsCDictEntry *__restrict__ entryOut)
 // ends (a scan); a range drops the records that end at or below the reach before it and cuts the front of one that straddles; its first
 // record left is JOINED to the match that defines the reach if it starts there with the same offset (long matches are found piecewise:
 // the walkers cannot see each other); a second, backward scan gives every range's last record the end of what was joined to it.
-// Last, the records that count are packed, 1 KiB of source (an OUTPUT RANGE = 1024 / R walk ranges) at a time, into the layout the
-// entropy kernels read: seqAll[block][64 output ranges][256 records] + hdrAll (nseq, trailing, litSum, first = 0).
+// Last, the records that count are packed into the layout the entropy kernels read: one list a block, in block order, without holes
+// (zs_block_seqs), and the block's header (ZsBlockHdr: nseq, trailing, lits).
 // ---------------------------------------------------------------------------------------------
 #ifndef ZS_WALK_MINW
 #define ZS_WALK_MINW 1             // waves per SIMD the small-unit kernel is compiled for (register budget)
@@ -874,16 +874,18 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ recAll, const uint4 *__restrict__ resAll,
-            ZsSeqRec *__restrict__ seqAll, ZsRangeHdr *__restrict__ hdrAll, int rangeLogArg)
+            ZsSeqRec *__restrict__ seqAll, uint32_t *__restrict__ hdrAll, int rangeLogArg)
 {
     constexpr int NT = 256;
-    __shared__ uint32_t sa[9 * 256 + 16];
-    uint32_t *sKept = sa, *sCnt = sa + 256, *sTrail = sa + 512, *sFOut = sa + 768, *sNs = sa + 1024, *sOwn = sa + 1280, *sEs = sa + 1536, *sPend = sa + 1792, *sChain = sa + 2048, *sWave = sa + 2304;
+    // a word a walk range: sKept its first verdict and its last offset; sStart the place of its first kept record in the block's list; sInfo
+    // what the packing needs of it (two words: own | first kept record << 17, chain end | records << 17); sWave, sTot, sMl a word a wavefront; sEnd where the list's last record ends
+    __shared__ __attribute__((aligned(16))) uint32_t sa[4 * 256 + 16];
+    uint32_t *sKept = sa, *sStart = sa + 256, *sWave = sa + 1024, *sTot = sa + 1028, *sMl = sa + 1032, *sEnd = sa + 1036;
+    uint2 *sInfo = reinterpret_cast<uint2 *>(sa + 512);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t rangeLog = (uint32_t)rangeLogArg, R = 1u << rangeLog;
+    const uint32_t rangeLog = (uint32_t)rangeLogArg;
     const uint32_t slot = blockIdx.x;
     const uint32_t NRB = ZS_BLOCK_MAX >> rangeLog;                               // walk ranges per block
-    const uint32_t gLog = ZS_OUT_LOG - rangeLog, G = 1u << gLog;                 // walk ranges per output range
     const uint2 *recs = zs_block_walk_records(recAll, slot);
     const uint4 *res = zs_block_range_results(resAll, slot);
     {
@@ -895,7 +897,7 @@ k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ re
         const bool walked = mine && bN >= 16 && (t << rangeLog) < bN;            // (ranges of a block too small to compress, or behind its end, leave no result)
         const uint4 rr = walked ? res[t] : make_uint4(0, 0, 0, 0);
         const uint32_t ns = rr.x, le = rr.y;
-        const uint32_t rs = min(bStart + (t << rangeLog), bEnd), re = min(bStart + (t << rangeLog) + R, bEnd);   // the range, cut at the block end
+        const uint32_t rs = min(bStart + (t << rangeLog), bEnd);                 // the range's start, cut at the block end
         const uint2 *rp = recs + ((bStart + (t << rangeLog)) >> 2);
         // reach before me / with me: maximum of the ranges' last match ends; the low bits name the range that holds it (the earliest of equals)
         uint32_t total;
@@ -903,7 +905,7 @@ k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ re
         const uint32_t incl = block_scan_max<NT, 1>(key, sWave, tid, &total);
         uint32_t excl = (uint32_t)__shfl_up((int)incl, 1);
         if (lane == 0) { excl = 0; for (uint32_t k = 0; k < (tid >> 6); k++) excl = max(excl, sWave[k]); }
-        const uint32_t own = max(excl >> 9, bStart), reach = max(incl >> 9, bStart), reachAll = max(total >> 9, bStart);
+        const uint32_t own = max(excl >> 9, bStart), reachAll = max(total >> 9, bStart);
         const uint32_t definer = 511u - (excl & 511u);                           // valid if excl != 0
 #if defined(ZS_STITCH_STOP) && ZS_STITCH_STOP == 2
         if (bN) return;                                                          // timing aid: the first scan only
@@ -935,12 +937,12 @@ k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ re
             }
         }
         const bool keptAny = f < ns;
-        if (mine) sKept[t] = keptAny;
+        sKept[t] = (keptAny ? 1u : 0u) | (rr.z << 1);                            // (with the range's last offset: the joined test of the ranges behind reads both)
         __syncthreads();
         // joined to the match that defines the reach: starts there, same offset, and that match (its range's last record) counts itself
-        const bool joined = keptAny && excl != 0 && own >= rs && fStart == own && fOff == res[definer].z && sKept[definer] != 0;
+        const uint32_t defWord = sKept[excl != 0 ? definer : 0u];
+        const bool joined = keptAny && excl != 0 && own >= rs && fStart == own && fOff == (defWord >> 1) && (defWord & 1u) != 0;
         const uint32_t fOut = f + (joined ? 1u : 0u), cnt = ns - fOut;
-        const uint32_t es = joined ? fEnd : max(rs, own), te = max(re, reach), lastEnd = cnt ? le : es;
         // what was joined to my last record: the nearest range behind me that ends a chain says where (one that only passes a chain on does not)
         const bool stopper = ns && le > own && !(joined && cnt == 0);
         uint32_t total2;
@@ -949,56 +951,83 @@ k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ re
         uint32_t sfxEx = (uint32_t)__shfl_down((int)sfx, 1);
         if (lane == 63) { sfxEx = 0; for (uint32_t k = (tid >> 6) + 1; k < NT / 64; k++) sfxEx = max(sfxEx, sWave[k]); }
         const uint32_t chainEnd = sfxEx ? (sfxEx & 0x3FFFFu) : reachAll;
-        if (mine) { sCnt[t] = cnt; sTrail[t] = te - lastEnd; sFOut[t] = fOut; sNs[t] = ns; sOwn[t] = own; sEs[t] = es; sChain[t] = chainEnd; }
+        // the place of my first kept record in the block's list: an exclusive sum of the counts (a thread without a range counts 0)
+        const uint32_t wave = tid >> 6;
+        const uint32_t cntIncl = wave_incl_scan(cnt);
+        if (lane == 63) sTot[wave] = cntIncl;
+        sInfo[t] = make_uint2(own | (fOut << 17), chainEnd | (ns << 17));
         __syncthreads();
-        const uint32_t gi = t & (G - 1u);
-        if (mine) {                                                              // literals left over in front of my territory, inside my output range
-            uint32_t pend = 0;
-            for (uint32_t i = gi; i > 0; i--) { pend += sTrail[t - gi + i - 1]; if (sCnt[t - gi + i - 1]) break; }
-            sPend[t] = pend;
-        }
+        uint32_t start = cntIncl - cnt, nseq = 0;
+        #pragma unroll
+        for (uint32_t k = 0; k < NT / 64; k++) { const uint32_t x = sTot[k]; nseq += x; if (k < wave) start += x; }
+        sStart[t] = start;
         __syncthreads();
 #if defined(ZS_STITCH_STOP) && ZS_STITCH_STOP == 1
         if (bN) return;                                                          // timing aid: no packing
 #endif
-        // pack, a lane a record: wavefront w takes the output ranges 16 w .. 16 w + 15 in turn; lane d of a round the d-th record of the output
-        // range = record fOut + (d - records of the walk ranges before) of its walk range: loads of consecutive lanes run along a walk range's
-        // slots, stores along the output range's.  (A thread packing its own range's records one by one - 8 scattered bytes a lane and
-        // store - took 0.26 ms of this kernel's 0.32: the stores queued at issue.)
-        const uint32_t wave = tid >> 6;
-        for (uint32_t go = 0; go < ZS_WALK_RANGES / (NT / 64); go++) {
-            const uint32_t g = wave * (ZS_WALK_RANGES / (NT / 64)) + go, j0 = g << gLog;
-            uint32_t c[4] = { 0, 0, 0, 0 }, total = 0;
-            for (uint32_t i = 0; i < G; i++) { c[i] = sCnt[j0 + i]; total += c[i]; }
-            ZsSeqRec *out = zs_out_range_seqs(seqAll, zs_out_range(slot, g));
-            uint32_t lits = 0;
-            for (uint32_t d0 = 0; d0 < total; d0 += 64) {
-                const uint32_t d = d0 + lane;
-                if (d < total) {
-                    uint32_t j = 0, pre = 0;
-                    if (d >= c[0]) { j = 1; pre = c[0]; if (G > 2) { if (d >= pre + c[1]) { j = 2; pre += c[1]; if (d >= pre + c[2]) { j = 3; pre += c[2]; } } } }
-                    const uint32_t jr = j0 + j, k = sFOut[jr] + (d - pre);
-                    const uint2 rec = recs[(jr << (rangeLog - 2)) + k];
-                    uint32_t st = rec.x & 0x1FFFFu, ml = rec.x >> 17, ll = rec.y >> 17;
-                    const uint32_t off = rec.y & 0x1FFFFu, en = st + ml;
-                    if (d == pre) {                                              // the walk range's first record that counts: a straddling one is cut; its literals start at the territory
-                        const uint32_t ownj = sOwn[jr];
-                        if (st < ownj) { st = ownj; ml = en - st; }
-                        ll = st - sEs[jr] + sPend[jr];
-                    }
-                    if (k + 1 == sNs[jr]) ml = sChain[jr] - st;                  // its last: with what was joined to it
-                    ZsSeqRec w; w.x = zs_rec_x(ll, ml, off); w.y = zs_rec_y(off, st);
-                    out[d] = w;
-                    lits += ll;
+        // pack, a lane a record: record d of the list is record fOut + (d - start) of the walk range that holds it (the last whose start is
+        // <= d: the empty ones before it share its start) - loads of consecutive lanes run along a walk range's slots, stores along the list.
+        // A record carries no literal length: the consumer takes it from the end of the record before.  PB rounds of 256 records are
+        // requested together, a whole step ahead of their use, so that nothing in the loop waits for a load but its own use.  (A wavefront
+        // packing 16 output ranges in turn - load, wait, store, reduce, header - was 16 serial round trips; a thread packing its own range's
+        // records one by one - 8 scattered bytes a lane and store - took 0.26 ms of this kernel's 0.32: the stores queued at issue.)
+        constexpr uint32_t PB = 4;
+        ZsSeqRec *out = zs_block_seqs(seqAll, slot);
+        uint2 recN[PB]; uint32_t ownN[PB], endN[PB];                             // own | first of its range << 31, chain end | last of its range << 31
+        auto request = [&](uint32_t base) {
+            #pragma unroll
+            for (uint32_t q = 0; q < PB; q++) {
+                const uint32_t d = base + NT * q + tid;
+                recN[q] = make_uint2(0, 0); ownN[q] = 0; endN[q] = 0;
+                if (d < nseq) {
+                    uint32_t jr = 0;
+                    #pragma unroll
+                    for (uint32_t stepb = NT / 2; stepb >= 1; stepb >>= 1) if (d >= sStart[jr + stepb]) jr += stepb;
+                    const uint2 info = sInfo[jr];
+                    const uint32_t at = d - sStart[jr], k = (info.x >> 17) + at;
+                    ownN[q] = (info.x & 0x1FFFFu) | (at == 0 ? 0x80000000u : 0u);
+                    endN[q] = (info.y & 0x1FFFFu) | (k + 1 == (info.y >> 17) ? 0x80000000u : 0u);
+                    recN[q] = recs[(jr << (rangeLog - 2)) + k];
                 }
             }
+        };
+        request(0);
+        #pragma unroll
+        for (uint32_t q = 0; q < PB; q++) asm volatile("" : "+v"(recN[q].x), "+v"(recN[q].y));    // the first records are waited for here, not inside the loop
+        uint32_t mlSum = 0;
+        for (uint32_t base = 0; base < nseq; base += NT * PB) {
+            uint2 recC[PB]; uint32_t ownC[PB], endC[PB];
             #pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) lits += (uint32_t)__shfl_xor((int)lits, o);
-            if (lane == 0) {
-                ZsRangeHdr h; h.nseq = total; h.litSum = lits; h.trailing = 0; h.first = 0;
-                for (uint32_t i = G; i > 0; i--) { h.trailing += sTrail[j0 + i - 1]; if (sCnt[j0 + i - 1]) break; }
-                zs_out_range_hdr(hdrAll, zs_out_range(slot, g)) = h;
+            for (uint32_t q = 0; q < PB; q++) { recC[q] = recN[q]; ownC[q] = ownN[q]; endC[q] = endN[q]; }
+            if (base + NT * PB < nseq) request(base + NT * PB);
+            #pragma unroll
+            for (uint32_t q = 0; q < PB; q++) {
+                const uint32_t d = base + NT * q + tid;
+                if (d < nseq) {
+                    const uint2 rec = recC[q];
+                    uint32_t st = rec.x & 0x1FFFFu, ml = rec.x >> 17;
+                    const uint32_t off = rec.y & 0x1FFFFu, en = st + ml;
+                    if (ownC[q] >> 31) {                                         // the walk range's first record that counts: a straddling one is cut at the territory
+                        const uint32_t ownj = ownC[q] & 0x1FFFFu;
+                        if (st < ownj) { st = ownj; ml = en - st; }
+                    }
+                    if (endC[q] >> 31) ml = (endC[q] & 0x1FFFFu) - st;           // its last: with what was joined to it
+                    ZsSeqRec w; w.x = zs_rec_x(ml, off); w.y = zs_rec_y(off, st);
+                    out[d] = w;
+                    mlSum += ml;
+                    if (d + 1 == nseq) sEnd[0] = st + ml;
+                }
             }
+        }
+        // the block's header: its sequences, the literals behind the last match, all its literals (the bytes no match covers)
+        const uint32_t mlWave = wave_sum(mlSum);
+        if (lane == 0) sMl[wave] = mlWave;
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t covered = 0;
+            for (uint32_t k = 0; k < NT / 64; k++) covered += sMl[k];
+            ZsBlockHdr h; h.nseq = nseq; h.trailing = bN - (nseq ? sEnd[0] : 0u); h.lits = bN - covered; h.pad = 0;
+            zs_block_hdr(hdrAll, slot) = h;
         }
     }
 }

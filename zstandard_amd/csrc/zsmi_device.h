@@ -9,8 +9,6 @@
 #define ZS_TABLE_LOG_SMALL 13     // slots of each candidate table, units <= 64 KiB
 #define ZS_TABLE_LOG_BIG   14     // units <= 128 KiB
 #define ZS_WALK_LOG_MIN 8         // the walk cuts a block in ranges of 256 bytes (512 at levels <= 2: the launch says which)
-#define ZS_OUT_LOG     10         // the walk kernel hands the sequences on in output ranges of 1 KiB
-#define ZS_WALK_RANGES 64u        // output ranges per block
 #define ZS_RES_PER_BLOCK 256u     // walk-range results per block (ranges of >= 256 bytes)
 #ifndef ZS_CROSS_MAX
 #define ZS_CROSS_MAX   1024u      // a match may pass its walk range's end by this much (never the block's end)
@@ -21,7 +19,7 @@
 #define ZS_WINDOW      32u        // positions looked at per walk step
 #define ZS_FCAP        8u         // forward bytes compared when scoring a candidate (the match taken is measured to its end)
 #define ZS_BCAP        4u         // backward bytes compared when scoring a candidate
-#define ZS_SEQ_PER_RANGE 256u     // record slots per output range: its matches start inside it and are >= 4 bytes long
+#define ZS_SEQ_MAX     (ZS_BLOCK_MAX / 4u)    // most sequences a block can hold: its matches do not overlap and are >= 4 bytes long
 #define ZS_HUF_MAXBITS 11u
 
 // one 64 KiB block of one chunk
@@ -40,21 +38,21 @@ struct ZsUnitDesc {
     uint32_t firstBlock;  // index of its first block in the call's block list
 };
 
-// one sequence as the walk kernel leaves it (per range) / as the entropy kernels consume it: two 32-bit words
-//   x: bits 0-10 literals in front of it inside its output range's territory (<= 1024), bits 11-27 match length (<= 65536: matches found
-//      piecewise are joined), bit 28 bit 16 of the offset, bits 29-30 recent-offset code (written by the sequences kernel)
+// one sequence as the stitch leaves it in a block's list / as the entropy kernels consume it: two 32-bit words
+//   x: bits 0-10 unused (zero), bits 11-27 match length (<= 65536: matches found piecewise are joined), bit 28 bit 16 of the offset
 //   y: bits 0-15 low 16 bits of the offset, bits 16-31 block position of the match start
+// A record carries no literal length: the literals in front of a match run from the end of the record before it (start + match length;
+// 0 for a block's first record) to its start, however long that run is.
 struct ZsSeqRec { uint32_t x, y; };
-__device__ __forceinline__ uint32_t zs_rec_ll(uint32_t x) { return x & 0x7FFu; }
 __device__ __forceinline__ uint32_t zs_rec_ml(uint32_t x) { return (x >> 11) & 0x1FFFFu; }
 __device__ __forceinline__ uint32_t zs_rec_off(uint32_t x, uint32_t y) { return (y & 0xFFFFu) | (((x >> 28) & 1u) << 16); }
 __device__ __forceinline__ uint32_t zs_rec_pos(uint32_t y) { return y >> 16; }
-__device__ __forceinline__ uint32_t zs_rec_x(uint32_t ll, uint32_t ml, uint32_t off) { return ll | (ml << 11) | ((off >> 16) << 28); }
+__device__ __forceinline__ uint32_t zs_rec_x(uint32_t ml, uint32_t off) { return (ml << 11) | ((off >> 16) << 28); }
 __device__ __forceinline__ uint32_t zs_rec_y(uint32_t off, uint32_t pos) { return (off & 0xFFFFu) | (pos << 16); }
 
-// a walk range after the stitch: its records [first, first + nseq) count; litSum: literal bytes in front of those matches inside the
-// range's territory; trailing: literal bytes behind the last of them (the whole territory if there is none)
-struct ZsRangeHdr { uint32_t nseq, trailing, litSum, first; };
+// a block after the stitch: records [0, nseq) of its list count, in block order; trailing: literal bytes behind the last match (the whole
+// block if there is none); lits: all its literal bytes (the bytes no match covers)
+struct ZsBlockHdr { uint32_t nseq, trailing, lits, pad; };
 
 // per-block result of the encode kernel
 struct ZsBlockResult { uint32_t payloadSize; uint32_t type; /* 0 raw, 1 rle, 2 compressed */ uint32_t rleByte; uint32_t pad; };

@@ -14,8 +14,11 @@
 #define ZS_LITSEC_STRIDE  (ZS_BLOCK_MAX + 1024u)
 #define ZS_SEQSEC_STRIDE  (ZS_BLOCK_MAX + 4096u)
 #define ZS_STREAM_STRIDE  (24u * 1024u)          // per Huffman stream scratch: 16384 symbols * 11 bits = 22528 B max
-#define ZS_CHAIN_CODES 16384u      // most sequences a block can hold (64 output ranges of 256 record slots): elements per table in the chain scratch
-static_assert(ZS_CHAIN_CODES == ZS_WALK_RANGES * ZS_SEQ_PER_RANGE, "a chain table holds an element for every record slot of a block");
+#define ZS_CHAIN_CODES 16384u      // most sequences a block can hold (ZS_SEQ_MAX): elements per table in the chain scratch
+static_assert(ZS_CHAIN_CODES == ZS_SEQ_MAX, "a chain table holds an element for every record a block's list can hold");
+#define ZS_HDR_SLOT_WORDS 256u     // words a block's slot of hdrs takes: its ZsBlockHdr in front, the rest unused (the slot keeps the 1 KiB it
+                                   // had as 64 range headers: tests/test_scratch_layout.py states every buffer's sizes)
+static_assert(sizeof(ZsBlockHdr) <= ZS_HDR_SLOT_WORDS * sizeof(uint32_t), "a block's header fits its slot");
 
 // per-block result of the two encode kernels, consumed by k_assemble_frames
 struct ZsBlockMeta { uint32_t type;       // 0 raw, 1 rle, 2 literal + sequence sections present
@@ -32,8 +35,8 @@ struct ZsBlockMeta { uint32_t type;       // 0 raw, 1 rle, 2 literal + sequence 
 //   cand     candidate positions of a unit, a word a table          k_lz_candidates -> k_lz_walk
 //   recs     the walkers' records: a walk range at block position p owns the slots from p / 4       k_lz_walk -> k_lz_stitch
 //   res      a result a walk range: records, last match end, last offset                            k_lz_walk -> k_lz_stitch
-//   seqs     the records that count, 64 output ranges of 256 slots  k_lz_stitch -> entropy kernels, k_train_stats
-//   hdrs     a header an output range                                k_lz_stitch -> entropy kernels, k_train_stats
+//   seqs     a block's records that count: one list, in block order, no holes                      k_lz_stitch -> entropy kernels, k_train_stats
+//   hdrs     a block's ZsBlockHdr (sequences, trailing literals, all literals) in front of its slot  k_lz_stitch -> entropy kernels, k_train_stats
 //   lits     the block's literals, gathered                          k_encode_literals (lends: chain codes)
 //   streams  its four Huffman streams before they are joined        k_encode_literals (lends: chain outputs)
 //   litSec   its literal section                                     k_encode_literals -> k_assemble_frames
@@ -45,8 +48,8 @@ struct ZsBlockMeta { uint32_t type;       // 0 raw, 1 rle, 2 literal + sequence 
     X(cand,    uint32_t,    2u,                                64u) \
     X(recs,    uint2,       ZS_BLOCK_MAX / 4,                  512u) \
     X(res,     uint4,       ZS_RES_PER_BLOCK,                  8u << 20) \
-    X(seqs,    ZsSeqRec,    ZS_WALK_RANGES * ZS_SEQ_PER_RANGE, 0u) \
-    X(hdrs,    ZsRangeHdr,  ZS_WALK_RANGES,                    0u) \
+    X(seqs,    ZsSeqRec,    ZS_SEQ_MAX,                        0u) \
+    X(hdrs,    uint32_t,    ZS_HDR_SLOT_WORDS,                 0u) \
     X(lits,    uint8_t,     ZS_BLOCK_MAX + 64u,                0u) \
     X(streams, uint8_t,     4u * ZS_STREAM_STRIDE,             0u) \
     X(litSec,  uint8_t,     ZS_LITSEC_STRIDE,                  0u) \
@@ -86,14 +89,10 @@ static_assert((ZS_BLOCK_MAX / 4) / 64 == ZS_RES_PER_BLOCK && 4096u * 16u * 10u *
 __device__ __forceinline__ unsigned long long *zs_res_lend_walk_profile(uint4 *resAll, uint32_t recordsEnd) { return reinterpret_cast<unsigned long long *>(resAll + (size_t)(recordsEnd / 64)); }
 
 // ---- seqs, hdrs ----
-template <class P> __device__ __forceinline__ P *zs_block_seqs(P *seqAll, size_t slot) { ZS_SLOT_OF(ZsSeqRec, P); return seqAll + slot * ZS_WALK_RANGES * ZS_SEQ_PER_RANGE; }
-__device__ __forceinline__ size_t zs_range_seq_slot(size_t range) { return range * ZS_SEQ_PER_RANGE; }                                                                        // an output range's first record slot among its block's
-template <class P> __device__ __forceinline__ P *zs_range_seqs(P *blockSeqs, size_t range) { ZS_SLOT_OF(ZsSeqRec, P); return blockSeqs + zs_range_seq_slot(range); }            // of a block's (zs_block_seqs)
-// output range `range` of the block in `slot`, counted over the whole sub-batch; its records and its header
-__device__ __forceinline__ size_t zs_out_range(size_t slot, uint32_t range) { return slot * ZS_WALK_RANGES + range; }
-template <class P> __device__ __forceinline__ P *zs_out_range_seqs(P *seqAll, size_t outRange) { ZS_SLOT_OF(ZsSeqRec, P); return seqAll + outRange * ZS_SEQ_PER_RANGE; }
-template <class P> __device__ __forceinline__ P &zs_out_range_hdr(P *hdrAll, size_t outRange) { ZS_SLOT_OF(ZsRangeHdr, P); return hdrAll[outRange]; }
-template <class P> __device__ __forceinline__ P *zs_block_range_hdrs(P *hdrAll, size_t slot) { ZS_SLOT_OF(ZsRangeHdr, P); return hdrAll + slot * ZS_WALK_RANGES; }               // [output range]
+// a block's list: records [0, ZsBlockHdr::nseq), in block order (a record's literals: from the end of the record before it, zsmi_device.h)
+template <class P> __device__ __forceinline__ P *zs_block_seqs(P *seqAll, size_t slot) { ZS_SLOT_OF(ZsSeqRec, P); return seqAll + slot * ZS_SEQ_MAX; }
+__device__ __forceinline__ ZsBlockHdr &zs_block_hdr(uint32_t *hdrAll, size_t slot) { return *reinterpret_cast<ZsBlockHdr *>(hdrAll + slot * ZS_HDR_SLOT_WORDS); }
+__device__ __forceinline__ const ZsBlockHdr &zs_block_hdr(const uint32_t *hdrAll, size_t slot) { return *reinterpret_cast<const ZsBlockHdr *>(hdrAll + slot * ZS_HDR_SLOT_WORDS); }
 
 // ---- lits, streams ----
 template <class P> __device__ __forceinline__ P *zs_block_lits(P *litsAll, size_t slot) { ZS_SLOT_OF(uint8_t, P); return litsAll + slot * (ZS_BLOCK_MAX + 64); }
