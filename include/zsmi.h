@@ -66,6 +66,31 @@ size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const void *src,
  * Content size of the first frame; 0 if unknown, on error, or for a skippable frame. Host-only header parse. */
 unsigned long long zsmi_getDecompressedSize(const void *src, size_t srcSize);
 
+/* The size queries of a buffer of frames.  Host-only: they read the container's headers - frame headers, block headers, skippable
+ * frames - and decode nothing; no device is needed.  They read only inside src[0 .. srcSize); srcSize may pass 4 GiB.
+ * Every one is the answer of one container walker, the decoder's own frame / block loop without the decoding, so a frame is refused here
+ * with the code the decoder would give it where the headers alone decide: prefix_unknown (10) for a magic that is neither a zstd frame's
+ * nor a skippable frame's, frameParameter_unsupported (14) for the reserved header bit, frameParameter_windowTooLarge (16) for a window
+ * log above 30, corruption_detected (20) for a block of the reserved type 3, srcSize_wrong (72) for a header, a block, a skippable frame
+ * or a checksum that ends behind srcSize (the decoder says checksum_wrong for the last of these) and for bytes left over behind the last frame.
+ *   ZSMI_CONTENTSIZE_UNKNOWN: a frame states no content size.   ZSMI_CONTENTSIZE_ERROR: any of the refusals above, or a sum beyond 64 bits. */
+#define ZSMI_CONTENTSIZE_UNKNOWN (0ULL - 1)
+#define ZSMI_CONTENTSIZE_ERROR   (0ULL - 2)
+/* replaces: ZStdDecompress.GetFrameContentSize  csharp/src/ZStdDecompress.cs:518-531 (internal there).  What the header of the first frame
+ * states: its Frame_Content_Size, or UNKNOWN; 0 for a skippable frame; ERROR for fewer than 5 bytes or a header that is refused or cut
+ * short.  Only the header is read: the frame's blocks need not be there. */
+unsigned long long zsmi_getFrameContentSize(const void *src, size_t srcSize);
+/* replaces: commented upstream FindFrameCompressedSize  csharp/src/ZStdDecompress.cs:1957-2004.  The bytes the first frame of src takes -
+ * header, blocks up to the last-block bit, checksum; a skippable frame: its 8 + Frame_Size bytes - or an error code (zsmi_isError).  What
+ * follows the frame is not looked at, so the first frame of a concatenation gives its own length. */
+size_t zsmi_findFrameCompressedSize(const void *src, size_t srcSize);
+/* replaces: commented upstream FindDecompressedSize  csharp/src/ZStdDecompress.cs:538-580.  src must be exactly some number of frames, as
+ * for zsmi_decompress: the sum of their stated content sizes (a skippable frame adds 0; no byte at all: 0), UNKNOWN, or ERROR. */
+unsigned long long zsmi_findDecompressedSize(const void *src, size_t srcSize);
+/* ZSTD_decompressBound (no counterpart in the reference): room that holds the content of every frame of src whether it states a size or
+ * not - a frame's stated size, else its number of blocks x min(window size, 128 KiB) - summed; ZSMI_CONTENTSIZE_ERROR on error. */
+unsigned long long zsmi_decompressBound(const void *src, size_t srcSize);
+
 /* replaces: commented upstream declaration  size_t Compress(void* dst, size_t dstCapacity, void* src, size_t srcSize,
  *           int compressionLevel)  csharp/src/ZStd.cs:89-96   (the reference has no live compressor)
  * One frame for the whole input.  level <= 2: fast parameters, level >= 3: default parameters. */
@@ -94,7 +119,7 @@ size_t zsmi_compress_advanced(void *dst, size_t dstCapacity, const void *src, si
  * Batch calls: n independent chunks <-> n frames, the data-parallel hot path (no analogue in the
  * reference).  Chunk i is src[srcOffsets[i] .. +srcSizes[i]); its result goes to
  * dst[dstOffsets[i] ..).  Offsets/sizes arrays are HOST memory; src/dst/dstSizes are DEVICE memory
- * in the *Device calls and host memory in the *Host calls.
+ * in the *Device calls and host memory in the *Host calls (the device-resident calls, further down, take every array from device memory).
  * Per-chunk status: dstSizes[i] = bytes produced, or (uint32_t)-code on error (same codes as above).
  * ------------------------------------------------------------------------------------------ */
 typedef struct zsmi_ctx zsmi_ctx;
@@ -289,6 +314,39 @@ int zsmi_decompressBatchHost_usingDict(zsmi_ctx *ctx, const void *src, const uin
  * dPackedOffsets[n+1] (device, uint64) receives the running offsets.  Asynchronous. */
 int zsmi_packFramesDevice(zsmi_ctx *ctx, const void *dFrames, const uint64_t *dstOffsets, const uint32_t *dSizes,
                           uint32_t n, void *dPacked, uint64_t *dPackedOffsets);
+
+/* ------------------------------------------------------------------------------------------
+ * Device-resident decode: a batch whose descriptors - offsets, sizes, capacities - are DEVICE memory, as an earlier GPU step left them
+ * (dDstSizes of a compress call, dPackedOffsets of zsmi_packFramesDevice, the frames some kernel of the caller's located).  The three
+ * calls below only queue work on the context's stream: no device-to-host copy, no wait, and nothing of the host-array calls' pinned
+ * staging is touched.  Chained - sizes, layout, decode - they decode frames nobody has looked at on the host.
+ * ------------------------------------------------------------------------------------------ */
+/* The size queries above for n items at once, on the device: item i is dSrc[dSrcOffsets[i] .. + dSrcSizes[i]), some number of frames.
+ * dContentSizes[i]: zsmi_findDecompressedSize of the item; dBounds[i]: its zsmi_decompressBound (either array may be NULL);
+ * dStatus[i]: 0 or the code that made them ZSMI_CONTENTSIZE_ERROR.  Every array is device memory; entries [0, n) are written and nothing
+ * else; an item is read only inside its own bytes.  Checked on the host before anything is queued - a NULL ctx: init_missing; NULL dSrc,
+ * dSrcOffsets, dSrcSizes or dStatus with n > 0: GENERIC.  n == 0 does nothing.  One kernel (k_frame_sizes), a lane an item. */
+int zsmi_getFrameSizesBatchDevice(zsmi_ctx *ctx, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                  uint64_t *dContentSizes, uint64_t *dBounds, uint32_t *dStatus);
+/* Places for n outputs from their sizes (dContentSizes or dBounds of the call above), on the device.
+ * dDstCaps[i] = dSizes[i] if dStatus[i] == 0 (a NULL dStatus: every one 0) and dSizes[i] <= 0xFFFFFF88, the largest size that is no error
+ * code; 0 otherwise - an unknown size, a refused item, one too large for a batch item: the decode then reports the item's own error, or
+ * dstSize_tooSmall (70).  dDstOffsets[0 .. n]: the exclusive running sum of the capacities, each rounded up to `align`; dDstOffsets[n] is
+ * the room the outputs take.  align: a power of two in 1 .. 4096 (anything else: parameter_outOfBound); a NULL ctx: init_missing; a NULL
+ * dDstOffsets, or NULL dSizes or dDstCaps with n > 0: GENERIC. */
+int zsmi_layoutOutputsDevice(zsmi_ctx *ctx, const uint64_t *dSizes, const uint32_t *dStatus, uint32_t n, uint32_t align,
+                             uint32_t *dDstCaps, uint64_t *dDstOffsets /* n + 1 */);
+/* zsmi_decompressBatchDevice with its four descriptor arrays in device memory.  maxDstCap is the one thing the host is told: no item
+ * gets more room than that, and the call's scratch is planned as for n items of maxDstCap bytes each (give the largest
+ * capacity the batch can hold, not a loose ceiling).
+ * The contract: item i's bytes, dDstSizes[i] and error code are those of zsmi_decompressBatchDevice - with a set,
+ * zsmi_decompressBatchDevice_usingDDictSet - called with the same four arrays from the host and the capacities min(dDstCaps[i], maxDstCap).
+ * set: NULL for the plain call; one DDict dd is the set ({}, unnamed = dd), so this entry point serves every dictionary form.
+ * Checked on the host, in this order, before anything is queued - a NULL ctx: init_missing; a NULL dSrc, dDst, descriptor array or
+ * dDstSizes with n > 0: GENERIC; a set of another device: parameter_unsupported.  n == 0 does nothing. */
+int zsmi_decompressBatchResident(zsmi_ctx *ctx, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                 void *dDst, const uint64_t *dDstOffsets, const uint32_t *dDstCaps, uint32_t maxDstCap,
+                                 uint32_t *dDstSizes, const zsmi_ddictSet *set);
 
 /* ------------------------------------------------------------------------------------------
  * Seekable archives (zstd's seekable format): independent frames, then a seek table in a skippable frame

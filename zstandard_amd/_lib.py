@@ -132,6 +132,14 @@ def lib():
     L.zsmi_decompressBatchHost_usingDict.restype = i32; L.zsmi_decompressBatchHost_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
     L.zsmi_decompressBatchDevice_usingDict.restype = i32; L.zsmi_decompressBatchDevice_usingDict.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, sz]
     L.zsmi_packFramesDevice.restype = i32; L.zsmi_packFramesDevice.argtypes = [vp, vp, vp, vp, u32, vp, vp]
+    ull_ = ctypes.c_ulonglong
+    L.zsmi_getFrameContentSize.restype = ull_; L.zsmi_getFrameContentSize.argtypes = [vp, sz]
+    L.zsmi_findFrameCompressedSize.restype = sz; L.zsmi_findFrameCompressedSize.argtypes = [vp, sz]
+    L.zsmi_findDecompressedSize.restype = ull_; L.zsmi_findDecompressedSize.argtypes = [vp, sz]
+    L.zsmi_decompressBound.restype = ull_; L.zsmi_decompressBound.argtypes = [vp, sz]
+    L.zsmi_getFrameSizesBatchDevice.restype = i32; L.zsmi_getFrameSizesBatchDevice.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
+    L.zsmi_layoutOutputsDevice.restype = i32; L.zsmi_layoutOutputsDevice.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    L.zsmi_decompressBatchResident.restype = i32; L.zsmi_decompressBatchResident.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp]
     L.zsmi_enableKernelTiming.restype = i32; L.zsmi_enableKernelTiming.argtypes = [vp, i32]
     L.zsmi_getKernelTimes.restype = i32; L.zsmi_getKernelTimes.argtypes = [vp, ctypes.POINTER(KernelTime), i32]
     L.zsmi_decodeScratchBytes.restype = sz; L.zsmi_decodeScratchBytes.argtypes = [vp]
@@ -205,4 +213,6 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_openSeekable", "zsmi_openSeekableDevice", "zsmi_closeSeekable", "zsmi_getNumFrames_fromSeekable", "zsmi_getContentSize_fromSeekable",
            "zsmi_sizeofSeekable", "zsmi_seekableReadRangesDevice", "zsmi_seekableReadRangesHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
-           "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced"]
+           "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
+           "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",
+           "zsmi_getFrameSizesBatchDevice", "zsmi_layoutOutputsDevice", "zsmi_decompressBatchResident"]

@@ -16,6 +16,10 @@
   DecompressionDictSet
                       a DDict set (zsmi_createDDictSet): a device table of DecompressionDicts; a decode call with it gives every frame
                       the dictionary its dictID names, so one call decodes a batch whose frames name different dictionaries.
+  frame_content_size, find_frame_compressed_size, find_decompressed_size, decompress_bound
+                      the size queries of a buffer of frames (zsmi_getFrameContentSize ...): host only, the container's headers alone.
+                      On the device, for a batch: BatchCodec.frame_sizes_device, and with layout_outputs_device and decompress_resident
+                      a decode whose descriptors never leave device memory.
   train_dictionary, finalize_dictionary, get_dict_id
                       zstd dictionaries made on the GPU (fastCover and ZDICT_finalizeDictionary; zdict.h's parameters).
 
@@ -55,6 +59,37 @@ def _buf(b):
             return ctypes.c_char_p(b), len(b)
         return (ctypes.c_char * len(mv)).from_buffer(b), len(mv)
     raise TypeError(type(b))
+
+
+CONTENTSIZE_UNKNOWN = (1 << 64) - 1      # ZSMI_CONTENTSIZE_UNKNOWN: a frame states no content size
+CONTENTSIZE_ERROR = (1 << 64) - 2        # ZSMI_CONTENTSIZE_ERROR: the frames are refused (or their sizes sum beyond 64 bits)
+
+
+def frame_content_size(src) -> int:
+    """what the header of the first frame of src states (zsmi_getFrameContentSize; GetFrameContentSize, ZStdDecompress.cs:518): its content
+    size, CONTENTSIZE_UNKNOWN, 0 for a skippable frame, or CONTENTSIZE_ERROR.  Host only, like the three below: no device is needed."""
+    s, n = _buf(src)
+    return int(_lib.lib().zsmi_getFrameContentSize(s, n))
+
+
+def find_frame_compressed_size(src) -> int:
+    """the bytes the first frame of src takes, a skippable one included (zsmi_findFrameCompressedSize); RuntimeError with the error's name
+    for a frame the container walker refuses"""
+    L = _lib.lib()
+    s, n = _buf(src)
+    return _raise_if_error(L, L.zsmi_findFrameCompressedSize(s, n))
+
+
+def find_decompressed_size(src) -> int:
+    """the sum of the content sizes the frames of src state (zsmi_findDecompressedSize), CONTENTSIZE_UNKNOWN or CONTENTSIZE_ERROR"""
+    s, n = _buf(src)
+    return int(_lib.lib().zsmi_findDecompressedSize(s, n))
+
+
+def decompress_bound(src) -> int:
+    """room that holds the content of every frame of src, stated or not (zsmi_decompressBound), or CONTENTSIZE_ERROR"""
+    s, n = _buf(src)
+    return int(_lib.lib().zsmi_decompressBound(s, n))
 
 
 class ZStdDecompress:
@@ -575,6 +610,36 @@ class BatchCodec:
         do = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
         _check(self.L.zsmi_packFramesDevice(self.ctx, ctypes.c_void_p(d_frames_ptr), self._p(do), ctypes.c_void_p(d_sizes_ptr), n,
                                             ctypes.c_void_p(d_packed_ptr), ctypes.c_void_p(d_packed_offsets_ptr)), "zsmi_packFramesDevice")
+
+    # ---- device-resident decode: every array is device memory (pointers), the calls only queue work.  Chained - pack_device's offsets and
+    # compress_device's sizes -> frame_sizes_device -> layout_outputs_device -> decompress_resident - nothing comes to the host in between
+    def frame_sizes_device(self, d_src_ptr, d_src_offsets_ptr, d_src_sizes_ptr, n, d_content_sizes_ptr, d_bounds_ptr, d_status_ptr):
+        """per item: find_decompressed_size -> d_content_sizes (uint64), decompress_bound -> d_bounds (uint64; either may be 0: not
+        wanted), 0 or the refusal's code -> d_status (uint32).  zsmi_getFrameSizesBatchDevice"""
+        rc = self.L.zsmi_getFrameSizesBatchDevice(self.ctx, ctypes.c_void_p(d_src_ptr), ctypes.c_void_p(d_src_offsets_ptr), ctypes.c_void_p(d_src_sizes_ptr), n,
+                                                  ctypes.c_void_p(d_content_sizes_ptr), ctypes.c_void_p(d_bounds_ptr), ctypes.c_void_p(d_status_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_getFrameSizesBatchDevice: {_error_name(self.L, rc)}")
+
+    def layout_outputs_device(self, d_sizes_ptr, d_status_ptr, n, d_dst_caps_ptr, d_dst_offsets_ptr, align=1):
+        """sizes (uint64) and statuses (uint32; 0: none) -> d_dst_caps (uint32: the size, or 0 for an item with a status or a size that is
+        unknown or no batch item's) and d_dst_offsets (uint64, n + 1: the running sum of the caps rounded up to align; the last is the
+        room they take).  zsmi_layoutOutputsDevice"""
+        rc = self.L.zsmi_layoutOutputsDevice(self.ctx, ctypes.c_void_p(d_sizes_ptr), ctypes.c_void_p(d_status_ptr), n, align,
+                                             ctypes.c_void_p(d_dst_caps_ptr), ctypes.c_void_p(d_dst_offsets_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_layoutOutputsDevice: {_error_name(self.L, rc)}")
+
+    def decompress_resident(self, d_src_ptr, d_src_offsets_ptr, d_src_sizes_ptr, n, d_dst_ptr, d_dst_offsets_ptr, d_dst_caps_ptr, max_dst_cap,
+                            d_dst_sizes_ptr, ddict_set=None):
+        """decompress_device with its four descriptor arrays in device memory; max_dst_cap: no item gets more room, and the scratch is
+        planned for n items of it.  ddict_set: a DecompressionDictSet (one dictionary: DecompressionDictSet(codec, [], unnamed=ddict)).
+        zsmi_decompressBatchResident"""
+        rc = self.L.zsmi_decompressBatchResident(self.ctx, ctypes.c_void_p(d_src_ptr), ctypes.c_void_p(d_src_offsets_ptr), ctypes.c_void_p(d_src_sizes_ptr), n,
+                                                 ctypes.c_void_p(d_dst_ptr), ctypes.c_void_p(d_dst_offsets_ptr), ctypes.c_void_p(d_dst_caps_ptr), max_dst_cap,
+                                                 ctypes.c_void_p(d_dst_sizes_ptr), ddict_set.handle if ddict_set is not None else None)
+        if rc:
+            raise RuntimeError(f"zsmi_decompressBatchResident: {_error_name(self.L, rc)}")
 
     def seekable_bound(self, src_size, frame_size=0, checksum=True) -> int:
         return _raise_if_error(self.L, self.L.zsmi_seekableBound(src_size, frame_size, int(bool(checksum))))

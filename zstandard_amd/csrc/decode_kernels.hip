@@ -13,6 +13,9 @@
 // Work split inside the wavefront: headers and FSE/Huffman table parsing on lane 0 (small, serial),
 // Huffman streams on lanes 0..3 (one stream each), sequence decoding on lane 0 in tiles of 64,
 // literal and match copies by all 64 lanes.
+//
+// Behind it, the two small kernels of device-resident decode: k_frame_sizes (the container loop without decoding: sizes and status an
+// item, a lane an item) and k_dec_items (the item list from descriptor arrays in device memory).
 #ifndef ZSMI_DECODE_KERNELS_HIP         // (decode_fast.hip and seekable.hip include this file too)
 #define ZSMI_DECODE_KERNELS_HIP
 #include "zsmi_device.h"
@@ -1227,6 +1230,36 @@ k_decode_frames(const uint8_t *__restrict__ srcAll, const ZsDecItem *__restrict_
         zs_decode_item<DICT>(L, item, srcAll, items, dstAll, dstSizes, litBuf, sel);
         wave_mem_sync();                                                        // the buffer and the LDS image are the next item's
     }
+}
+
+// ---- device-resident decode: what the decoder's container loop above would find in each item, without decoding it, and the item list
+//      built from descriptors that never left the device ----
+// k_frame_sizes: zs_walk_item (zsmi_frame.h) over every item, ONE LANE an item.  The walk is a chain of dependent loads - a frame header, then a
+// 3-byte block header per block, each placed by the one before - with nothing for a second lane to do: a wavefront an item would idle 63 lanes
+// on the one-block frames large batches are made of.  Lanes of a wavefront diverge in the block loop (a wavefront takes as long as its item of
+// the most blocks); the loads are bytes at any address (rd24 / rd32 are byte-wise or memcpy: no alignment is asked of an item's place).
+// contentSizes, bounds: either may be null.  Writes entries [0, n) only.
+__global__ void __launch_bounds__(256)
+k_frame_sizes(const uint8_t *__restrict__ srcAll, const uint64_t *__restrict__ srcOffsets, const uint32_t *__restrict__ srcSizes, uint32_t n,
+              uint64_t *__restrict__ contentSizes, uint64_t *__restrict__ bounds, uint32_t *__restrict__ status)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const ZsWalk w = zs_walk_item(srcAll + srcOffsets[i], srcSizes[i]);
+    if (contentSizes) contentSizes[i] = w.contentSize;
+    if (bounds) bounds[i] = w.bound;
+    status[i] = w.status;
+}
+// k_dec_items: the item list (ZsDecItem) of a call whose four descriptor arrays are device memory; no capacity above maxDstCap, which is what
+// the host planned the call's scratch for
+__global__ void __launch_bounds__(256)
+k_dec_items(const uint64_t *__restrict__ srcOffsets, const uint32_t *__restrict__ srcSizes, const uint64_t *__restrict__ dstOffsets,
+            const uint32_t *__restrict__ dstCaps, uint32_t maxDstCap, uint32_t n, ZsDecItem *__restrict__ items)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    ZsDecItem it; it.srcOff = srcOffsets[i]; it.dstOff = dstOffsets[i]; it.srcSize = srcSizes[i]; it.dstCap = min(dstCaps[i], maxDstCap);
+    items[i] = it;
 }
 
 #endif

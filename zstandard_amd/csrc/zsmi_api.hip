@@ -7,10 +7,10 @@
 #include "zsmi_device.h"          // format constants, block / unit / sequence records, unaligned loads and stores
 #include "zsmi_scratch.h"         // the scratch layouts: the table of the compress buffers, the slot accessors and borrowings of both pipelines, DecLists
 #include "zsmi_wave.h"            // device primitives of more than one kernel file: wave_*, zs_block_copy, rd16/24/32, xxh64_quad
-#include "zsmi_frame.h"           // the readers of the container headers (frame, block, literals section, stream split): device and host
+#include "zsmi_frame.h"           // the readers of the container headers (frame, block, literals section, stream split) and the container walker: device and host
 #include "lz_kernels.hip"         // encoder, LZ stage: k_lz_candidates, k_lz_walk, k_lz_stitch, k_lz_dict_tables
 #include "entropy_kernels.hip"    // encoder, entropy stage: k_encode_sequences, k_encode_literals, k_assemble_frames, k_frame_checksum; k_train_stats, k_pack_*
-#include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares; loadDictEntropy, the one reader of a dictionary
+#include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares; loadDictEntropy, the one reader of a dictionary; k_frame_sizes, k_dec_items
 #include "decode_fast.hip"        // fast decode path: k_dec_prep, k_dec_huffman, k_dec_sequences, k_dec_entropy, k_dec_execute, k_dec_checksum, k_dec_collect; k_dict_load (a dictionary -> its record for the host, a DDict's image)
 #include "zsmi_ctx.h"             // host: zsmi_ctx and its buffers, LAUNCH, the batch entry points the features call
 #include "seekable.hip"           // feature: seekable archives (kernels and host)
@@ -78,6 +78,30 @@ extern "C" unsigned long long zsmi_getDecompressedSize(const void *srcv, size_t 
     if (srcSize < 5 || rd32(src) != 0xFD2FB528u) return 0;
     const ZsFrameHeader fh = zs_read_frame_header(src, srcSize, 0);
     return (fh.status || fh.contentSize >= 0xFFFFFFFFFFFFFFFEull) ? 0 : fh.contentSize;
+}
+
+// ---- the size queries of a host buffer, every one the container walker's answer (zs_walk, zsmi_frame.h) - no device is touched.
+//      zsmi_getFrameContentSize  GetFrameContentSize :518-531: what the first frame's header states (no block is looked at)
+//      zsmi_findFrameCompressedSize  FindFrameCompressedSize :1957-2004: the bytes the first frame takes, a skippable one included
+//      zsmi_findDecompressedSize  FindDecompressedSize :538-580, and zsmi_decompressBound (ZSTD_decompressBound): over every frame of src ----
+extern "C" unsigned long long zsmi_getFrameContentSize(const void *src, size_t srcSize)
+{
+    const ZsWalk w = zs_walk<uint64_t>((const uint8_t *)src, srcSize, ZS_WALK_FIRST_HEADER);
+    return w.nFrames ? w.contentSize : ZSMI_CONTENTSIZE_ERROR;              // (fewer than 5 bytes: no header)
+}
+extern "C" size_t zsmi_findFrameCompressedSize(const void *src, size_t srcSize)
+{
+    const ZsWalk w = zs_walk<uint64_t>((const uint8_t *)src, srcSize, ZS_WALK_FIRST_FRAME);
+    if (w.status) return ZSMI_ERR(w.status);
+    return w.nFrames ? (size_t)w.consumed : ZSMI_ERR(ZSMI_error_srcSize_wrong);
+}
+extern "C" unsigned long long zsmi_findDecompressedSize(const void *src, size_t srcSize)
+{
+    return zs_walk<uint64_t>((const uint8_t *)src, srcSize, ZS_WALK_ITEM).contentSize;
+}
+extern "C" unsigned long long zsmi_decompressBound(const void *src, size_t srcSize)
+{
+    return zs_walk<uint64_t>((const uint8_t *)src, srcSize, ZS_WALK_ITEM).bound;
 }
 
 // ---- the LZ kernels of a level: k_lz_candidates and k_lz_walk for small units (<= 64 KiB), big units and a dictionary call's prefixed units ----
@@ -669,24 +693,32 @@ bool zsmi_ctx::DecodeScratch::reserve(const DecodePlan &p)
     return ok;
 }
 
+// What a plan takes of a call's capacities: the largest, and how many items can hold more than one and more than two 64 KiB blocks.
+struct CapStats {
+    uint32_t maxCap = 0, over1 = 0, over2 = 0;
+    void add(uint32_t cap, uint32_t items = 1)
+    {
+        const uint32_t nb = (uint32_t)(((uint64_t)cap + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX);
+        maxCap = std::max(maxCap, cap);
+        if (nb > 1) over1 += items;
+        if (nb > 2) over2 += items;
+    }
+};
+
 // The plan of a call.  Block slots per item: 1; 2 when some item can hold more than one 64 KiB block; up to ZS_FAST_MAXBLOCKS when at least a
 // quarter of the call's items can hold more than two (a call of large frames; a few large frames among many small ones go to the general kernel,
 // so the small ones do not pay for slots and launches they do not use).
 // The budget: a call whose buffers all fit asks the runtime nothing (the one-shot path).  When any buffer must grow, the scratch gets half of the
 // free device memory and of what the context holds: first the slots per item go back to 2 and 1, then the items in flight are cut down (never
 // below one sub-batch of 64, never above n).
-static DecodePlan planDecode(zsmi_ctx *c, const uint32_t *dstCaps, uint32_t n, bool generalOnly)
+static DecodePlan planDecode(zsmi_ctx *c, const CapStats &caps, uint32_t n, bool generalOnly)
 {
     DecodePlan p;
-    p.fast = c->decodeFast && !generalOnly; p.maxBlocks = 1;
-    uint32_t bigItems = 0, needBlocks = 1, maxCapBytes = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t nb = (uint32_t)(((uint64_t)dstCaps[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX);
-        maxCapBytes = std::max(maxCapBytes, dstCaps[i]);
-        if (nb > 1) p.maxBlocks = 2;
-        if (nb > 2) { bigItems++; needBlocks = std::max(needBlocks, std::min<uint32_t>(nb, ZS_FAST_MAXBLOCKS)); }
-    }
-    if (bigItems && (uint64_t)bigItems * 4 >= n) p.maxBlocks = needBlocks;
+    p.fast = c->decodeFast && !generalOnly; p.maxBlocks = caps.over1 ? 2 : 1;
+    const uint32_t maxCapBytes = caps.maxCap;
+    // (the largest item is one of those that hold more than two blocks, when there are any: it states the slots they need)
+    const uint32_t needBlocks = std::min<uint32_t>((uint32_t)(((uint64_t)maxCapBytes + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX), ZS_FAST_MAXBLOCKS);
+    if (caps.over2 && (uint64_t)caps.over2 * 4 >= n) p.maxBlocks = needBlocks;
     p.descSlots = std::max(2u, p.maxBlocks);
     p.blockCap = std::min<uint32_t>(std::max<uint32_t>(maxCapBytes, 64u), 1u << 17);
     p.litStride = ((p.blockCap + 63u) & ~63u) + 64u; p.litCap = p.litStride - 64u;
@@ -797,17 +829,12 @@ static ZsDictSel oneDictionary(const void *dBytes, uint32_t size, const ZsDDictI
 }
 // dict: which dictionary each frame of the call gets (nullptr, or a selector that holds none: the plain call).  Digested dictionaries bring the
 // images the fast kernels' dictionary forms need; a call with a dictionary's bare bytes (anyID) is the general kernel's alone.
-static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                     uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
-                                     const ZsDictSel *dict)
+// The item list is in c->dItems, queued or copied there on the stream by the caller; caps: what the plan takes of the items' capacities.
+static int decodeItems(zsmi_ctx *c, const void *dSrc, uint32_t n, void *dDst, const CapStats &caps, uint32_t *dDstSizes, const ZsDictSel *dict)
 {
-    if (!c) return ZSMI_error_init_missing;
-    if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    if (const int e = uploadDecodeItems(c, srcOffsets, srcSizes, n, dstOffsets, dstCaps)) return e;
     const bool useDict = dict && (dict->one.size || dict->n);
     const ZsDictSel sel = useDict ? *dict : ZsDictSel();
-    const DecodePlan p = planDecode(c, dstCaps, n, useDict && sel.anyID);
+    const DecodePlan p = planDecode(c, caps, n, useDict && sel.anyID);
     zsmi_ctx::DecodeScratch &S = c->dec;
     if (!S.reserve(p)) return ZSMI_error_memory_allocation;
     const uint8_t *src = (const uint8_t *)dSrc;
@@ -835,6 +862,19 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
                (const uint32_t *)leftCount, sel, DecLists::queue(lists));
     }
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+
+static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
+                                     uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
+                                     const ZsDictSel *dict)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (n == 0) return 0;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = uploadDecodeItems(c, srcOffsets, srcSizes, n, dstOffsets, dstCaps)) return e;
+    CapStats caps;
+    for (uint32_t i = 0; i < n; i++) caps.add(dstCaps[i]);
+    return decodeItems(c, dSrc, n, dDst, caps, dDstSizes, dict);
 }
 
 extern "C" int zsmi_decompressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
@@ -981,6 +1021,19 @@ extern "C" int zsmi_decompressBatchDevice_usingDDictSet(zsmi_ctx *c, const void 
 // ---------------------------------------------------------------------------------------------
 // pack frames
 // ---------------------------------------------------------------------------------------------
+// offsets[0 .. n]: the exclusive scan of the bytes the items get (zs_layout_cap: a size, or 0 for an error word or a status), each rounded up
+// to align; caps (may be null): those bytes.  Three launches under one name (entropy_kernels.hip), the tile sums in context scratch.
+template <class Size>
+static int scanOffsets(zsmi_ctx *c, const char *name, const Size *dSizes, const uint32_t *dStatus, uint32_t n, uint32_t align, uint32_t *dCaps, uint64_t *dOffsets)
+{
+    const uint32_t tiles = (uint32_t)(((uint64_t)n + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE);
+    if (!c->dScan.reserve(sizeof(uint64_t) * std::max(tiles, 1u))) return ZSMI_error_memory_allocation;
+    uint64_t *dTiles = (uint64_t *)c->dScan.p;
+    if (tiles) LAUNCH(c, name, k_pack_tile_sums<Size>, dim3(tiles), dim3(256), 0, dSizes, dStatus, n, align, dTiles);
+    LAUNCH(c, name, k_pack_scan_tiles, dim3(1), dim3(1024), 0, dTiles, tiles, dOffsets + n);
+    if (tiles) LAUNCH(c, name, k_pack_offsets<Size>, dim3(tiles), dim3(256), 0, dSizes, dStatus, n, align, (const uint64_t *)dTiles, dCaps, dOffsets);
+    return 0;
+}
 extern "C" int zsmi_packFramesDevice(zsmi_ctx *c, const void *dFrames, const uint64_t *dstOffsets, const uint32_t *dSizes,
                                      uint32_t n, void *dPacked, uint64_t *dPackedOffsets)
 {
@@ -988,9 +1041,54 @@ extern "C" int zsmi_packFramesDevice(zsmi_ctx *c, const void *dFrames, const uin
     if (n == 0) return 0;
     if (!c->sSizes.reserve(sizeof(uint64_t) * n)) return ZSMI_error_memory_allocation;
     if (hipMemcpyAsync(c->sSizes.p, dstOffsets, sizeof(uint64_t) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    LAUNCH(c, "k_pack_offsets", k_pack_offsets, dim3(1), dim3(1024), 0, dSizes, n, dPackedOffsets);
+    if (const int e = scanOffsets(c, "k_pack_offsets", dSizes, nullptr, n, 1u, nullptr, dPackedOffsets)) return e;
     LAUNCH(c, "k_pack_copy", k_pack_copy, dim3(n), dim3(256), 0, (const uint8_t *)dFrames, (const uint64_t *)c->sSizes.p, dSizes, (const uint64_t *)dPackedOffsets, (uint8_t *)dPacked);
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+
+// ---------------------------------------------------------------------------------------------
+// device-resident decode: sizes, output layout and the decode itself from descriptors that stay in device memory.  The three calls queue
+// their kernels and return: nothing is copied to the host, nothing waited for, and the pinned item buffers of the host-array calls (and
+// their events) are not touched.
+// ---------------------------------------------------------------------------------------------
+extern "C" int zsmi_getFrameSizesBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                             uint64_t *dContentSizes, uint64_t *dBounds, uint32_t *dStatus)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (n == 0) return 0;
+    if (!dSrc || !dSrcOffsets || !dSrcSizes || !dStatus) return ZSMI_error_GENERIC;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    LAUNCH(c, "k_frame_sizes", k_frame_sizes, dim3((n + 255) / 256), dim3(256), 0, (const uint8_t *)dSrc, dSrcOffsets, dSrcSizes, n, dContentSizes, dBounds, dStatus);
+    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+// the packer's scan in its general form (the packer's: align 1, no status, no caps)
+extern "C" int zsmi_layoutOutputsDevice(zsmi_ctx *c, const uint64_t *dSizes, const uint32_t *dStatus, uint32_t n, uint32_t align,
+                                        uint32_t *dDstCaps, uint64_t *dDstOffsets)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (align == 0 || align > 4096 || (align & (align - 1))) return ZSMI_error_parameter_outOfBound;
+    if (!dDstOffsets || (n && (!dSizes || !dDstCaps))) return ZSMI_error_GENERIC;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = scanOffsets(c, "k_layout_outputs", dSizes, dStatus, n, align, dDstCaps, dDstOffsets)) return e;
+    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+// The plan is the plan of n items of maxDstCap bytes: the one thing the host knows of the capacities.  Item i's result is that of the
+// host-array call with capacity min(dDstCaps[i], maxDstCap) - which kernels take an item never shows in its result.
+extern "C" int zsmi_decompressBatchResident(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                            void *dDst, const uint64_t *dDstOffsets, const uint32_t *dDstCaps, uint32_t maxDstCap,
+                                            uint32_t *dDstSizes, const zsmi_ddictSet *set)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (n && (!dSrc || !dSrcOffsets || !dSrcSizes || !dDst || !dDstOffsets || !dDstCaps || !dDstSizes)) return ZSMI_error_GENERIC;
+    ZsDictSel sel;
+    if (const int e = resolveDDictSet(c, set, sel)) return e;
+    if (n == 0) return 0;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (!c->dItems.reserve(sizeof(ZsDecItem) * n)) return ZSMI_error_memory_allocation;
+    LAUNCH(c, "k_dec_items", k_dec_items, dim3((n + 255) / 256), dim3(256), 0, dSrcOffsets, dSrcSizes, dDstOffsets, dDstCaps, maxDstCap, n, (ZsDecItem *)c->dItems.p);
+    CapStats caps;
+    caps.add(maxDstCap, n);
+    return decodeItems(c, dSrc, n, dDst, caps, dDstSizes, &sel);
 }
 
 // ---------------------------------------------------------------------------------------------

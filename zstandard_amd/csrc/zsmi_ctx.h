@@ -121,6 +121,7 @@ struct zsmi_ctx {
     uint32_t decodePool = 3072;              // wavefronts of the general decode kernel's pool (ZSMI_DEC_POOL): the chip holds 10 a CU x 256
     // staging for host-buffer calls
     DevBuf sSrc, sDst, sSizes, sDict, sPack, sPackOff;
+    DevBuf dScan;                        // the tile sums of an offset scan (scanOffsets: zsmi_packFramesDevice, zsmi_layoutOutputsDevice, the seekable packer)
     PinBuf hPack;
     // seekable archives (seekable.hip): compressed frames at bound spacing before they are packed, per-frame words (sizes, hashes, offsets, the
     // error word; a read's status words, codes and lists), the decoded bytes of the frames a read does not decode in place, and a read's lists
@@ -179,5 +180,7 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                      const struct ZsDictSel *dict);
+template <class Size>
+static int scanOffsets(zsmi_ctx *c, const char *name, const Size *dSizes, const uint32_t *dStatus, uint32_t n, uint32_t align, uint32_t *dCaps, uint64_t *dOffsets);
 // a context of the one-shot pool (zsmi_api.hip), given back when the handle goes
 namespace { struct Borrowed { zsmi_ctx *c; Borrowed(); ~Borrowed(); }; }

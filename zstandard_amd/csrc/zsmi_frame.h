@@ -38,6 +38,69 @@ __host__ __device__ __forceinline__ ZsBlockHeader zs_read_block_header(const uin
 {
     const uint32_t bh = rd24(p); ZsBlockHeader b; b.last = bh & 1; b.type = (bh >> 1) & 3; b.size = bh >> 3; b.payload = b.type == 1 ? 1u : b.size; return b;
 }
+// ---- the container walker: the loop of zs_decode_item (decode_kernels.hip; DecompressMultiFrame :2111-2160, DecompressFrame :2008-2067)
+//      without decoding - what an item's headers alone say about it.  It reads only p[0 .. size).  Refusals are the decoder's, in its order,
+//      with one difference: a checksum cut short is srcSize_wrong here (FindFrameCompressedSize :1996-1999), checksum_wrong there.
+//      mode: the whole item (bytes left over are srcSize_wrong; 0 bytes: 0 frames, sizes 0); its first frame, a skippable one included
+//      (consumed: its length); or the first frame's header alone (GetFrameContentSize :518-531: no block is looked at).
+//      status: 0 or the code.  nFrames: zstd and skippable frames walked.  consumed: the bytes they take.
+//      contentSize: the sum of the stated Frame_Content_Size values (a skippable frame adds 0); ZSMI_CONTENTSIZE_UNKNOWN when a frame states
+//      none; ZSMI_CONTENTSIZE_ERROR on any refusal or when a sum passes 64 bits (FindDecompressedSize :538-580).
+//      bound: ZSTD_decompressBound - a frame's stated size, else its blocks x min(window size, 128 KiB); ZSMI_CONTENTSIZE_ERROR as above. ----
+struct ZsWalk { uint32_t status, nFrames; uint64_t contentSize, bound, consumed; };
+enum { ZS_WALK_ITEM = 0, ZS_WALK_FIRST_FRAME = 1, ZS_WALK_FIRST_HEADER = 2 };
+template <class Size>        // uint32_t: a batch item (the device); uint64_t: a host buffer, which may pass 4 GiB
+__host__ __device__ __forceinline__ ZsWalk zs_walk(const uint8_t *p, Size size, int mode)
+{
+    ZsWalk w = {}; Size pos = 0; bool unknown = false, overflow = false;
+    uint64_t content = 0, bound = 0;
+    while (size - pos >= 5) {
+        const uint8_t *ip = p + pos; const Size rem = size - pos;
+        const uint32_t magic = rd32(ip);
+        if (magic != 0xFD2FB528u) {
+            if ((magic & 0xFFFFFFF0u) != 0x184D2A50u) { w.status = ZSMI_error_prefix_unknown; break; }
+            if (rem < 8) { w.status = ZSMI_error_srcSize_wrong; break; }
+            if (mode == ZS_WALK_FIRST_HEADER) { w.nFrames++; break; }
+            const uint64_t skip = (uint64_t)rd32(ip + 4) + 8;
+            if (rem < skip) { w.status = ZSMI_error_srcSize_wrong; break; }
+            pos += (Size)skip; w.nFrames++;
+            if (mode != ZS_WALK_ITEM) break;
+            continue;
+        }
+        const ZsFrameHeader fh = zs_read_frame_header(ip, rem, mode == ZS_WALK_FIRST_HEADER ? 0u : 3u);
+        if (fh.status) { w.status = fh.status; break; }
+        pos += fh.headerSize;
+        uint64_t blocks = 0;
+        if (mode != ZS_WALK_FIRST_HEADER) {
+            for (;;) {                                               // block loop :2033-2067
+                if (size - pos < 3) { w.status = ZSMI_error_srcSize_wrong; break; }
+                const ZsBlockHeader bh = zs_read_block_header(p + pos);
+                if (bh.type == 3) { w.status = ZSMI_error_corruption_detected; break; }
+                pos += 3;
+                if (bh.payload > size - pos) { w.status = ZSMI_error_srcSize_wrong; break; }
+                pos += bh.payload; blocks++;
+                if (bh.last) break;
+            }
+            if (w.status) break;
+            if (fh.checksumFlag) { if (size - pos < 4) { w.status = ZSMI_error_srcSize_wrong; break; } pos += 4; }
+        }
+        const bool stated = fh.contentSize != ~0ull;
+        const uint64_t block = fh.windowSize < (1u << 17) ? fh.windowSize : (uint64_t)(1u << 17);
+        const uint64_t fb = stated ? fh.contentSize : blocks * block;
+        if (stated) { overflow |= content + fh.contentSize < content; content += fh.contentSize; } else unknown = true;
+        overflow |= bound + fb < bound; bound += fb;
+        w.nFrames++;
+        if (mode != ZS_WALK_ITEM) break;
+    }
+    if (!w.status && mode == ZS_WALK_ITEM && pos != size) w.status = ZSMI_error_srcSize_wrong;
+    w.consumed = pos;
+    const bool bad = w.status || overflow;
+    w.contentSize = bad ? ZSMI_CONTENTSIZE_ERROR : (unknown ? ZSMI_CONTENTSIZE_UNKNOWN : content);
+    w.bound = bad ? ZSMI_CONTENTSIZE_ERROR : bound;
+    return w;
+}
+__host__ __device__ __forceinline__ ZsWalk zs_walk_item(const uint8_t *p, uint32_t size) { return zs_walk<uint32_t>(p, size, ZS_WALK_ITEM); }
+
 // ---- literals section header (DecodeLiteralsBlock :683-821) of a compressed block p[0 .. blockSize), blockSize >= 3 (MIN_CBLOCK_SIZE).
 //      type: 0 raw, 1 RLE, 2 Huffman, 3 treeless.  compSize: the bytes behind the header (raw: regenSize, RLE: 1); single: one Huffman stream.
 //      Refused here (corruption_detected) is what the header and blockSize alone decide: a Huffman section in a block below 5 bytes (:699), a section
