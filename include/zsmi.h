@@ -349,6 +349,37 @@ int zsmi_decompressBatchResident(zsmi_ctx *ctx, const void *dSrc, const uint64_t
                                  uint32_t *dDstSizes, const zsmi_ddictSet *set);
 
 /* ------------------------------------------------------------------------------------------
+ * Device-resident compress: the head of the same chain.  Chunk boundaries that a GPU step produced - records a kernel located, the rows
+ * of a tensor, the dDstSizes / dPackedOffsets of this library - go into a compress call without a trip to the host: bounds, the layout
+ * of the destinations (zsmi_layoutOutputsDevice above, over the bounds) and the compress call itself only queue work on the context's
+ * stream.  The dictionary forms (_usingDict, _usingCDict, _usingCDictSet), seekable compress and the dictionary trainer still plan on
+ * the host, from host arrays.
+ * ------------------------------------------------------------------------------------------ */
+/* dBounds[i] = zsmi_compressBound(dSrcSizes[i]) for n sizes, on the device (both arrays device memory; entries [0, n) are written).
+ * zsmi_layoutOutputsDevice(ctx, dBounds, NULL, n, align, dCaps, dDstOffsets) then places the frames.  A NULL ctx: init_missing; a NULL
+ * array with n > 0: GENERIC; n == 0 does nothing. */
+int zsmi_compressBoundsDevice(zsmi_ctx *ctx, const uint32_t *dSrcSizes, uint32_t n, uint64_t *dBounds);
+/* zsmi_compressBatchDevice with its three descriptor arrays in device memory.  maxSrcSize is the one thing the host is told: the call's
+ * sub-batches, grids and scratch are planned as for n chunks of maxSrcSize bytes each, and the chunk, block and unit lists are written by
+ * kernels on the stream (give the largest size the batch can hold - a loose one costs sub-batches and idle workgroups,
+ * never a wrong result or more scratch than the context's blocks in flight).
+ * The contract:
+ *  - frames: for every chunk with dSrcSizes[i] <= maxSrcSize, frame i and dDstSizes[i] are byte for byte those of zsmi_compressBatchDevice
+ *    called with the same three arrays from the host at the same level, with the context's ZSMI_c_checksumFlag.  A chunk's frame does not
+ *    depend on its neighbours, on maxSrcSize or on how the call was cut into sub-batches;
+ *  - a chunk with dSrcSizes[i] > maxSrcSize: dDstSizes[i] = (uint32_t)-ZSMI_error_srcSize_wrong, at most zsmi_compressBound(0) bytes are
+ *    written at its place, its neighbours are not affected;
+ *  - no host traffic: the call only queues work - no device-to-host copy, no wait.  It keeps a plan of its own in device memory: the
+ *    host-array calls' plan, pinned buffers and events are not touched, and a host-array call with a repeated layout still reuses its
+ *    plan after a resident call;
+ *  - writes: entries [0, n) of dDstSizes; bytes only inside [dDstOffsets[i], + zsmi_compressBound(dSrcSizes[i])).
+ * Checked on the host, in this order, before anything is queued - a NULL ctx: init_missing; a NULL dSrc, dDst, descriptor array or
+ * dDstSizes with n > 0: GENERIC.  n == 0 does nothing.  No dictionary form exists (they need a third, prefixed unit list and a dictionary
+ * index in device memory). */
+int zsmi_compressBatchResident(zsmi_ctx *ctx, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                               uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level);
+
+/* ------------------------------------------------------------------------------------------
  * Seekable archives (zstd's seekable format): independent frames, then a seek table in a skippable frame
  *   Skippable magic 0x184D2A5E | Frame_Size | n entries {Compressed_Size, Decompressed_Size[, Checksum]} | n | descriptor | 0x8F92EAB1
  * Any zstd decoder reads an archive as concatenated frames (zsmi_decompress included).  Frame i holds src[i F, min((i + 1) F, srcSize)),

@@ -641,6 +641,23 @@ class BatchCodec:
         if rc:
             raise RuntimeError(f"zsmi_decompressBatchResident: {_error_name(self.L, rc)}")
 
+    # ---- device-resident compress: the head of the chain.  compress_bounds_device -> layout_outputs_device (over the bounds) ->
+    # compress_resident; its d_dst_offsets / d_dst_sizes are what frame_sizes_device and decompress_resident take
+    def compress_bounds_device(self, d_src_sizes_ptr, n, d_bounds_ptr):
+        """compress_bound of n sizes (uint32, device) -> d_bounds (uint64, device).  zsmi_compressBoundsDevice"""
+        rc = self.L.zsmi_compressBoundsDevice(self.ctx, ctypes.c_void_p(d_src_sizes_ptr), n, ctypes.c_void_p(d_bounds_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_compressBoundsDevice: {_error_name(self.L, rc)}")
+
+    def compress_resident(self, d_src_ptr, d_src_offsets_ptr, d_src_sizes_ptr, n, max_src_size, d_dst_ptr, d_dst_offsets_ptr, d_dst_sizes_ptr, level=3):
+        """compress_device with its three descriptor arrays in device memory; max_src_size: the call is planned for n chunks of it, and a
+        chunk above it gets the size word of srcSize_wrong (72) instead of a frame.  The frames are compress_device's, byte for byte; the
+        codec's "checksum" parameter holds.  No dictionary form.  zsmi_compressBatchResident"""
+        rc = self.L.zsmi_compressBatchResident(self.ctx, ctypes.c_void_p(d_src_ptr), ctypes.c_void_p(d_src_offsets_ptr), ctypes.c_void_p(d_src_sizes_ptr), n,
+                                               max_src_size, ctypes.c_void_p(d_dst_ptr), ctypes.c_void_p(d_dst_offsets_ptr), ctypes.c_void_p(d_dst_sizes_ptr), level)
+        if rc:
+            raise RuntimeError(f"zsmi_compressBatchResident: {_error_name(self.L, rc)}")
+
     def seekable_bound(self, src_size, frame_size=0, checksum=True) -> int:
         return _raise_if_error(self.L, self.L.zsmi_seekableBound(src_size, frame_size, int(bool(checksum))))
 

@@ -992,9 +992,15 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     FINISH(2, litSecSize, 0);
     #undef FINISH
 }
+// liveBlocks (a plan built on the device, plan_kernels.hip: the grid is the host's upper bound): the blocks the list holds - a workgroup at
+// or beyond them leaves.  Null: the grid is the list
 template <bool CD>
-__global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
-{ encode_literals_block<CD>(ZS_LIT_ARGS, dictID, dictTab, chunkDict); }
+__global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict,
+                                                                       const uint32_t *__restrict__ liveBlocks)
+{
+    if (liveBlocks && blockIdx.x >= *liveBlocks) return;
+    encode_literals_block<CD>(ZS_LIT_ARGS, dictID, dictTab, chunkDict);
+}
 
 // ---------------------------------------------------------------------------------------------
 // k_encode_sequences : one wavefront per block.  Repcodes (parallel: two last-index scans), code
@@ -1455,9 +1461,14 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
     }
     if (lane == 0 && exists) { ZsBlockMeta &mo = zs_block_meta(metas, blk); mo.seqSecSize = result; mo.seqHdrSize = (secHdr == 0xFFFFFFFFu) ? result : secHdr; mo.seqGap = secGap; }
 }
+// liveBlocks: as k_encode_literals' - it stands in for nBlocks, and a workgroup none of whose G blocks is live leaves
 template <int G, bool CD>
-__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
-{ encode_sequences_block<G, CD>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, dictTab, chunkDict); }
+__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict,
+                                                             const uint32_t *__restrict__ liveBlocks)
+{
+    if (liveBlocks) { nBlocks = *liveBlocks; if (blockIdx.x * G >= nBlocks) return; }
+    encode_sequences_block<G, CD>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, dictTab, chunkDict);
+}
 
 // ---------------------------------------------------------------------------------------------
 // k_assemble_frames : one workgroup per chunk.  frame = magic + FHD + FCS (single segment)

@@ -75,9 +75,13 @@ template <int TLOG, int NT, bool PFX = false>
 __global__ void __launch_bounds__(64 * ZS_CAND_WAVES(NT))
 k_lz_candidates(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units, uint32_t block0,
                 uint16_t *__restrict__ distAll, uint8_t *__restrict__ distHiAll, uint32_t *__restrict__ candCount,
-                const ZsCDictEntry *__restrict__ dictTab = nullptr, const uint32_t *__restrict__ unitDict = nullptr)
+                const ZsCDictEntry *__restrict__ dictTab = nullptr, const uint32_t *__restrict__ unitDict = nullptr,
+                const uint32_t *__restrict__ liveUnits = nullptr)
 {
     static_assert(!PFX || TLOG == ZS_TABLE_LOG_BIG, "a prefixed unit spans up to 128 KiB of positions");
+    // liveUnits (a plan built on the device, plan_kernels.hip: the grid is the host's upper bound): the units the list holds - a workgroup
+    // at or beyond them has none and leaves.  Null: the grid is the list (one address a workgroup either way: a scalar load)
+    if (liveUnits && blockIdx.x >= *liveUnits) return;
     // PFX: the unit's dictionary, record unitDict[unit] of the table (null: record 0), read by the workgroup's one address: scalar registers
     const uint32_t *dictImg = nullptr; uint32_t pfx = 0;
     if constexpr (PFX) {
@@ -510,9 +514,11 @@ __global__ void __launch_bounds__(NT, BIG ? 1 : ZS_WALK_MINW)
 k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units, uint32_t block0,
           const uint16_t *__restrict__ distAll, const uint8_t *__restrict__ distHiAll,
           uint2 *__restrict__ recAll, uint32_t junkSlot, uint4 *__restrict__ resAll, int rangeLogArg, const uint32_t *__restrict__ candCount,
-          const ZsCDictEntry *__restrict__ dictTab = nullptr, const uint32_t *__restrict__ unitDict = nullptr)
+          const ZsCDictEntry *__restrict__ dictTab = nullptr, const uint32_t *__restrict__ unitDict = nullptr,
+          const uint32_t *__restrict__ liveUnits = nullptr)
 {
     static_assert(!PFX || BIG, "a prefixed unit is staged in the 128 KiB layout");
+    if (liveUnits && blockIdx.x >= *liveUnits) return;                           // (as k_lz_candidates: a device-built list shorter than the grid)
     // PFX: the unit's dictionary (as k_lz_candidates reads it); pfx stays in a scalar register: it feeds the staging loop and vb
     const uint8_t *pre = nullptr; uint32_t pfx = 0;
     if constexpr (PFX) {
@@ -874,9 +880,10 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 k_lz_stitch(const ZsBlockDesc *__restrict__ blocks, const uint2 *__restrict__ recAll, const uint4 *__restrict__ resAll,
-            ZsSeqRec *__restrict__ seqAll, uint32_t *__restrict__ hdrAll, int rangeLogArg)
+            ZsSeqRec *__restrict__ seqAll, uint32_t *__restrict__ hdrAll, int rangeLogArg, const uint32_t *__restrict__ liveBlocks = nullptr)
 {
     constexpr int NT = 256;
+    if (liveBlocks && blockIdx.x >= *liveBlocks) return;                         // (a device-built block list shorter than the grid: plan_kernels.hip)
     // a word a walk range: sKept its first verdict and its last offset; sStart the place of its first kept record in the block's list; sInfo
     // what the packing needs of it (two words: own | first kept record << 17, chain end | records << 17); sWave, sTot, sMl a word a wavefront; sEnd where the list's last record ends
     __shared__ __attribute__((aligned(16))) uint32_t sa[4 * 256 + 16];

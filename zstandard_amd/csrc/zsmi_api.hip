@@ -7,9 +7,11 @@
 #include "zsmi_device.h"          // format constants, block / unit / sequence records, unaligned loads and stores
 #include "zsmi_scratch.h"         // the scratch layouts: the table of the compress buffers, the slot accessors and borrowings of both pipelines, DecLists
 #include "zsmi_wave.h"            // device primitives of more than one kernel file: wave_*, zs_block_copy, rd16/24/32, xxh64_quad
+#include "zsmi_plan.h"            // the compress plan's rule for one chunk: blocks and units of a size, host and device
 #include "zsmi_frame.h"           // the readers of the container headers (frame, block, literals section, stream split) and the container walker: device and host
 #include "lz_kernels.hip"         // encoder, LZ stage: k_lz_candidates, k_lz_walk, k_lz_stitch, k_lz_dict_tables
 #include "entropy_kernels.hip"    // encoder, entropy stage: k_encode_sequences, k_encode_literals, k_assemble_frames, k_frame_checksum; k_train_stats, k_pack_*
+#include "plan_kernels.hip"       // encoder, the plan built on the device (the resident call): k_plan_chunks, k_plan_blocks, k_plan_refuse; k_compress_bounds
 #include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares; loadDictEntropy, the one reader of a dictionary; k_frame_sizes, k_dec_items
 #include "decode_fast.hip"        // fast decode path: k_dec_prep, k_dec_huffman, k_dec_sequences, k_dec_entropy, k_dec_execute, k_dec_checksum, k_dec_collect; k_dict_load (a dictionary -> its record for the host, a DDict's image)
 #include "zsmi_ctx.h"             // host: zsmi_ctx and its buffers, LAUNCH, the batch entry points the features call
@@ -107,9 +109,9 @@ extern "C" unsigned long long zsmi_decompressBound(const void *src, size_t srcSi
 // ---- the LZ kernels of a level: k_lz_candidates and k_lz_walk for small units (<= 64 KiB), big units and a dictionary call's prefixed units ----
 // level <= 2: short table only ("fast"), walk ranges of 512 bytes; level >= 3: short + long table ("double"), ranges of 256 bytes;
 // level >= 4 scores 8 candidates a step instead of 4 (paramsForLevel in oracle/zso_encoder.c)
-typedef void (*CandFn)(const uint8_t *, const ZsUnitDesc *, uint32_t, uint16_t *, uint8_t *, uint32_t *, const ZsCDictEntry *, const uint32_t *);
+typedef void (*CandFn)(const uint8_t *, const ZsUnitDesc *, uint32_t, uint16_t *, uint8_t *, uint32_t *, const ZsCDictEntry *, const uint32_t *, const uint32_t *);
 typedef void (*WalkFn)(const uint8_t *, const ZsUnitDesc *, uint32_t, const uint16_t *, const uint8_t *, uint2 *, uint32_t, uint4 *, int,
-                       const uint32_t *, const ZsCDictEntry *, const uint32_t *);
+                       const uint32_t *, const ZsCDictEntry *, const uint32_t *, const uint32_t *);
 template <class Fn> struct LzKernel { const char *name; Fn fn; uint32_t threads; size_t lds; };
 enum { kUnitsPfx, kUnitsSmall, kUnitsBig };       // (the order the kernels are launched in)
 struct LzShape { LzKernel<CandFn> cand[3]; LzKernel<WalkFn> walk[3]; int walkLog; bool useLong; };
@@ -270,42 +272,42 @@ int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const ui
         newKey[0] = n;
         for (uint32_t i = 0; i < n; i++) { newKey[1 + i] = srcOffsets[i]; newKey[1 + n + i] = dstOffsets[i]; newKey[1 + 2 * (size_t)n + i] = srcSizes[i]; }
         uint64_t nBlocks = 0;
-        for (uint32_t i = 0; i < n; i++) nBlocks += srcSizes[i] ? (srcSizes[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX : 1;
+        for (uint32_t i = 0; i < n; i++) nBlocks += zs_chunk_counts(srcSizes[i]).blocks;
         if (nBlocks > 0x7FFFFFFFull) return ZSMI_error_srcSize_wrong;
         if (!hChunks.reserve(sizeof(ZsChunkDesc) * n) || !hBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
         if (!dChunks.reserve(sizeof(ZsChunkDesc) * n) || !dBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
         if (!hUnits.reserve(sizeof(ZsUnitDesc) * nBlocks) || !dUnits.reserve(sizeof(ZsUnitDesc) * nBlocks)) return ZSMI_error_memory_allocation;
         // the pinned plan buffers may still feed a previous asynchronous copy
         if (hipStreamSynchronize(stream) != hipSuccess) return ZSMI_error_GENERIC;
+        // a chunk's blocks and units: the rule of zsmi_plan.h, which the resident call's plan kernels apply too
         ZsChunkDesc *hc0 = (ZsChunkDesc *)hChunks.p; ZsBlockDesc *hb = (ZsBlockDesc *)hBlocks.p;
         uint32_t b = 0, maxNb = 1;
-        for (uint32_t i = 0; i < n; i++) {
-            const uint32_t nb = srcSizes[i] ? (srcSizes[i] + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX : 1;
-            hc0[i].srcOff = srcOffsets[i]; hc0[i].dstOff = dstOffsets[i]; hc0[i].size = srcSizes[i]; hc0[i].firstBlock = b; hc0[i].nBlocks = nb; hc0[i].pad = 0;
-            for (uint32_t k = 0; k < nb; k++, b++) {
-                hb[b].srcOff = srcOffsets[i] + (uint64_t)k * ZS_BLOCK_MAX;
-                const uint64_t left = (uint64_t)srcSizes[i] - (uint64_t)k * ZS_BLOCK_MAX;
-                hb[b].size = (uint32_t)(left < ZS_BLOCK_MAX ? left : ZS_BLOCK_MAX);
-                hb[b].chunk = i; hb[b].firstInChunk = (k == 0); hb[b].lastInChunk = (k + 1 == nb);
-            }
-            if (nb > maxNb) maxNb = nb;
-        }
-        // LZ units: every 128 KiB of a chunk (two blocks); a unit of <= 64 KiB goes to the small-unit kernels
         small.before.assign((size_t)n + 1, 0); big.before.assign((size_t)n + 1, 0);
         uint32_t nSmall = 0, nBig = 0;
         for (uint32_t i = 0; i < n; i++) {
+            const ZsChunkCounts cc = zs_chunk_counts(srcSizes[i]);
+            const uint32_t nb = cc.blocks;
+            hc0[i].srcOff = srcOffsets[i]; hc0[i].dstOff = dstOffsets[i]; hc0[i].size = srcSizes[i]; hc0[i].firstBlock = b; hc0[i].nBlocks = nb; hc0[i].pad = 0;
+            for (uint32_t k = 0; k < nb; k++, b++) {
+                const ZsChunkBlock cb = zs_chunk_block(srcSizes[i], k, nb);
+                hb[b].srcOff = srcOffsets[i] + cb.off; hb[b].size = cb.size;
+                hb[b].chunk = i; hb[b].firstInChunk = cb.first; hb[b].lastInChunk = cb.last;
+            }
+            if (nb > maxNb) maxNb = nb;
             small.before[i] = nSmall; big.before[i] = nBig;
-            for (uint64_t o = 0; o < srcSizes[i]; o += ZS_UNIT_MAX) { if ((uint64_t)srcSizes[i] - o > ZS_BLOCK_MAX) nBig++; else nSmall++; }
+            nSmall += cc.smallUnits; nBig += cc.bigUnits;
         }
         small.before[n] = nSmall; big.before[n] = nBig;
+        // the units in two runs, [small][big], each in chunk order
         ZsUnitDesc *hu = (ZsUnitDesc *)hUnits.p;
-        uint32_t is = 0, ib = nSmall;
-        for (uint32_t i = 0; i < n; i++)
-            for (uint64_t o = 0; o < srcSizes[i]; o += ZS_UNIT_MAX) {
-                const uint64_t left = (uint64_t)srcSizes[i] - o;
-                ZsUnitDesc &u = hu[left > ZS_BLOCK_MAX ? ib++ : is++];
-                u.srcOff = srcOffsets[i] + o; u.size = (uint32_t)(left < ZS_UNIT_MAX ? left : ZS_UNIT_MAX); u.firstBlock = hc0[i].firstBlock + (uint32_t)(o / ZS_BLOCK_MAX);
+        for (uint32_t i = 0; i < n; i++) {
+            const ZsChunkCounts cc = zs_chunk_counts(srcSizes[i]);
+            for (uint32_t k = 0; k < cc.smallUnits + cc.bigUnits; k++) {
+                const ZsChunkUnit cu = zs_chunk_unit(srcSizes[i], k);
+                ZsUnitDesc &u = hu[cu.big ? nSmall + big.before[i] + cu.at : small.before[i] + cu.at];
+                u.srcOff = srcOffsets[i] + cu.off; u.size = cu.size; u.firstBlock = hc0[i].firstBlock + cu.block;
             }
+        }
         if (nSmall + nBig && hipMemcpyAsync(dUnits.p, hu, sizeof(ZsUnitDesc) * (nSmall + nBig), hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
         small.base = 0; big.base = nSmall;
         if (hipMemcpyAsync(dChunks.p, hc0, sizeof(ZsChunkDesc) * n, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
@@ -401,6 +403,65 @@ static void launchDictTables(zsmi_ctx *c, const ZsCompressDict &d, int level, vo
 {
     LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(lzShape(level).useLong ? 2 : 1), dim3(1024), 0, dictEntry(d, (const uint32_t *)dImg), (ZsCDictEntry *)dEntry);
 }
+// One sub-batch of a compress call as its kernels take it, whoever planned it - the host (CompressPlan) or the device (plan_kernels.hip).
+//   dChunks: the call's chunk list; dBlocks: the block list a chunk's firstBlock counts in; block0: the sub-batch's first block there
+//   (scratch slot = block - block0); nb, units[k].n: its blocks and units - or, with `live`, the host's upper bounds of them: the grids
+//   live: null, or the device's counts of what the lists really hold (a ZsPlanCounts: blocks, small units, big units); the kernels whose
+//   index is a block or a unit leave at or beyond their count.  k_assemble_frames is indexed by chunks, which the host knows
+struct SubBatch {
+    const ZsChunkDesc *dChunks; const ZsBlockDesc *dBlocks;
+    uint32_t chunk0, nChunks, block0, nb, cap;
+    CompressPlan::Units units[3]; const uint32_t *dUnitDict = nullptr;
+    const uint32_t *live = nullptr;
+    bool assemble;                                   // chunks of several blocks may be among them
+    const ZsCDictEntry *dTable = nullptr, *cdt = nullptr; const uint32_t *dChunkDict = nullptr;
+    uint4 rep; uint32_t dictID = 0;
+};
+static void launchSubBatch(zsmi_ctx *c, const LzShape &shape, const SubBatch &sb, const void *dSrc, void *dDst, uint32_t *dDstSizes, uint32_t *dStats)
+{
+    zsmi_ctx::Scratch &S = c->scratch;
+    const uint32_t nb = sb.nb, block0 = sb.block0;
+    const ZsBlockDesc *dB = sb.dBlocks + block0;
+    const CompressPlan::Units *units = sb.units;
+    const uint32_t *liveBlocks = sb.live, *liveUnits[3] = { nullptr, sb.live ? sb.live + 1 : nullptr, sb.live ? sb.live + 2 : nullptr };
+    for (int k = 0; k < 3; k++) {
+        const LzKernel<CandFn> &K = shape.cand[k];
+        const bool p = k == kUnitsPfx;
+        if (units[k].n)
+            LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, S.dist(),
+                   S.distHi(), S.cand(), p ? sb.dTable : nullptr, p ? sb.dUnitDict : nullptr, liveUnits[k]);
+    }
+    for (int k = 0; k < 3; k++) {
+        const LzKernel<WalkFn> &K = shape.walk[k];
+        const bool p = k == kUnitsPfx;
+        if (units[k].n)
+            LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, S.dist(),
+                   S.distHi(), S.recs(), zs_walk_records_end(sb.cap), S.res(), shape.walkLog, S.cand(),
+                   p ? sb.dTable : nullptr, p ? sb.dUnitDict : nullptr, liveUnits[k]);
+    }
+    LAUNCH(c, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, S.recs(), S.res(), S.seqs(), S.hdrs(), shape.walkLog, liveBlocks);
+    if (c->stopAfterWalk) return;
+    // The entropy stage.  Sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and
+    // reads the sequence sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  Every
+    // kernel takes the dictionary's recent offsets or ID ({1, 4, 8} and 0 without one).  The CD forms (cdt) take offsets, ID and
+    // tables from each chunk's record instead.
+    const ZsCDictEntry *cdt = sb.cdt;
+    const auto seqKernel = cdt ? k_encode_sequences<ZS_SEQ_GROUP, true> : k_encode_sequences<ZS_SEQ_GROUP, false>;
+    const auto litKernel = cdt ? k_encode_literals<true> : k_encode_literals<false>;
+    LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, S.seqs(),
+           S.hdrs(), S.seqSec(), S.metas(), c->stopSeq, S.lits(), S.streams(),
+           S.distAsPackRecords(), sb.rep, cdt, sb.dChunkDict, liveBlocks);
+    if (dStats)                                                  // (the codes it reads are in the literal buffers until the literals kernel)
+        LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(),
+               S.hdrs(), S.lits(), dStats);
+    LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(), S.hdrs(),
+           S.lits(), S.streams(), S.litSec(), S.metas(), c->stopLit,
+           sb.dChunks, S.seqSec(), (uint8_t *)dDst, dDstSizes, sb.dictID, cdt, sb.dChunkDict, liveBlocks);
+    if (sb.assemble)                                             // chunks of several blocks
+        LAUNCH(c, "k_assemble_frames", k_assemble_frames, dim3(sb.nChunks), dim3(256), 0, (const uint8_t *)dSrc, sb.dChunks,
+               sb.dBlocks, S.metas(), S.litSec(), S.seqSec(), block0,
+               (uint8_t *)dDst, dDstSizes, sb.chunk0, sb.dictID, cdt, sb.dChunkDict);
+}
 // The launch sequence of a call, over the plan's sub-batches.  dict: nullptr, or the call's dictionary, in one of three kinds -
 //   content only, or parsed from a formatted dictionary (the _usingDict calls, the trainer): the table images are built here, every call;
 //   digested, raw content (dImg): it brings its images along;
@@ -435,69 +496,94 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
         launchDictTables(c, *dict, level, c->dDictImg.p, (uint8_t *)c->dDictImg.p + kDictImgBytes);
         dTable = (const ZsCDictEntry *)((const uint8_t *)c->dDictImg.p + kDictImgBytes);
     }
-    const uint32_t *dChunkDict = set ? P.chunkDict() : nullptr;          // (null: every chunk uses record 0)
     // sub-batches of whole chunks, one after the other through one scratch set.  Every kernel goes to the caller's stream: a stream of
     // the context's own costs two queue crossings a call (~0.01 - 0.09 ms each: a bench line of 126 GiB/s where the kernels added up to 137).
     const uint32_t cap = std::max<uint32_t>((uint32_t)std::min<uint64_t>(P.blocks, std::max<uint32_t>(64, c->maxBlocksInFlight)), P.maxChunkBlocks);
     zsmi_ctx::Scratch &S = c->scratch;
     if (!S.reserve(cap)) return ZSMI_error_memory_allocation;
-    const ZsChunkDesc *dChunks = (const ZsChunkDesc *)P.dChunks.p;
+    SubBatch sb;
+    sb.dChunks = (const ZsChunkDesc *)P.dChunks.p; sb.dBlocks = (const ZsBlockDesc *)P.dBlocks.p; sb.cap = cap; sb.assemble = P.maxChunkBlocks > 1;
+    sb.dTable = dTable; sb.dChunkDict = set ? P.chunkDict() : nullptr;          // (null: every chunk uses record 0)
+    // Digested tables - the one dictionary's, any member's of a set - choose the CD forms of the entropy kernels
+    sb.cdt = (set ? set->tables : (dict && dict->dTables)) ? dTable : nullptr;
+    sb.rep = dict ? make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u) : make_uint4(1u, 4u, 8u, 0u);
+    sb.dictID = dict ? dict->dictID : 0u;
     for (uint32_t chunk0 = 0, chunk1; chunk0 < n; chunk0 = chunk1) {
         const CompressPlan::Cut sub = P.cut(chunk0, cap);
-        const uint32_t nb = sub.nb, block0 = sub.block0;
         chunk1 = sub.chunk1;
-        const ZsBlockDesc *dB = (const ZsBlockDesc *)P.dBlocks.p + block0;
-        CompressPlan::Units units[3];
-        for (int k = 0; k < 3; k++) units[k] = P.units(k, useDict, chunk0, chunk1);
-        for (int k = 0; k < 3; k++) {
-            const LzKernel<CandFn> &K = shape.cand[k];
-            const bool p = k == kUnitsPfx;
-            if (units[k].n)
-                LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, S.dist(),
-                       S.distHi(), S.cand(), p ? dTable : nullptr, p ? P.unitDict(chunk0) : nullptr);
-        }
-        for (int k = 0; k < 3; k++) {
-            const LzKernel<WalkFn> &K = shape.walk[k];
-            const bool p = k == kUnitsPfx;
-            if (units[k].n)
-                LAUNCH(c, K.name, K.fn, dim3(units[k].n), dim3(K.threads), K.lds, (const uint8_t *)dSrc, units[k].d, block0, S.dist(),
-                       S.distHi(), S.recs(), zs_walk_records_end(cap), S.res(), shape.walkLog, S.cand(),
-                       p ? dTable : nullptr, p ? P.unitDict(chunk0) : nullptr);
-        }
-        LAUNCH(c, "k_lz_stitch", k_lz_stitch, dim3(nb), dim3(256), 0, dB, S.recs(), S.res(), S.seqs(), S.hdrs(), shape.walkLog);
-        if (c->stopAfterWalk) continue;
-        // The entropy stage.  Sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and
-        // reads the sequence sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  Every
-        // kernel takes the dictionary's recent offsets or ID ({1, 4, 8} and 0 without one).  Digested tables - the one dictionary's, any
-        // member's of a set - choose the CD forms, which take offsets, ID and tables from each chunk's record instead.
-        const bool cdForms = set ? set->tables : (dict && dict->dTables);
-        const ZsCDictEntry *cdt = cdForms ? dTable : nullptr;
-        const auto seqKernel = cdt ? k_encode_sequences<ZS_SEQ_GROUP, true> : k_encode_sequences<ZS_SEQ_GROUP, false>;
-        const auto litKernel = cdt ? k_encode_literals<true> : k_encode_literals<false>;
-        const uint4 rep = dict ? make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u) : make_uint4(1u, 4u, 8u, 0u);
-        const uint32_t dictID = dict ? dict->dictID : 0u;
-        LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, S.seqs(),
-               S.hdrs(), S.seqSec(), S.metas(), c->stopSeq, S.lits(), S.streams(),
-               S.distAsPackRecords(), rep, cdt, dChunkDict);
-        if (dStats)                                                  // (the codes it reads are in the literal buffers until the literals kernel)
-            LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(),
-                   S.hdrs(), S.lits(), dStats);
-        LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(), S.hdrs(),
-               S.lits(), S.streams(), S.litSec(), S.metas(), c->stopLit,
-               dChunks, S.seqSec(), (uint8_t *)dDst, dDstSizes, dictID, cdt, dChunkDict);
-        if (P.maxChunkBlocks > 1)                                    // chunks of several blocks
-            LAUNCH(c, "k_assemble_frames", k_assemble_frames, dim3(chunk1 - chunk0), dim3(256), 0, (const uint8_t *)dSrc, dChunks,
-                   (const ZsBlockDesc *)P.dBlocks.p, S.metas(), S.litSec(), S.seqSec(), block0,
-                   (uint8_t *)dDst, dDstSizes, chunk0, dictID, cdt, dChunkDict);
+        sb.chunk0 = chunk0; sb.nChunks = chunk1 - chunk0; sb.block0 = sub.block0; sb.nb = sub.nb;
+        for (int k = 0; k < 3; k++) sb.units[k] = P.units(k, useDict, chunk0, chunk1);
+        sb.dUnitDict = P.unitDict(chunk0);
+        launchSubBatch(c, shape, sb, dSrc, dDst, dDstSizes, dStats);
     }
     if (checksum && !c->stopAfterWalk && !c->stopLit && !c->stopSeq)     // (a stopped stage leaves no frames to close)
-        LAUNCH(c, "k_frame_checksum", k_frame_checksum, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, dChunks, n, (uint8_t *)dDst, dDstSizes);
+        LAUNCH(c, "k_frame_checksum", k_frame_checksum, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, sb.dChunks, n, (uint8_t *)dDst, dDstSizes);
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
 extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                         uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level)
 {
     return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, c ? c->checksumFlag : 0);
+}
+
+// ---- device-resident compress: the call above with its three descriptor arrays in device memory.  The plan is built by kernels
+// (plan_kernels.hip) into buffers of its own (zsmi_ctx::ResidentPlan): the host-array calls' plan, its key, pinned buffers and events are
+// not touched, nothing is copied to the host, nothing waited for.  The host knows maxSrcSize alone:
+//   nbMax = blocks of a chunk of maxSrcSize; cap = the blocks in flight, as above, with n * nbMax for the call's blocks;
+//   sub-batches are fixed runs of K = cap / nbMax chunks - never more than cap blocks, whatever the sizes are;
+//   grids are upper bounds (K * nbMax blocks, K small units, K * ceil(nbMax / 2) big units: none when nbMax is 1), the live counts reach
+//   the kernels through SubBatch::live.  With every chunk maxSrcSize long the bounds are the counts: no workgroup is launched in vain. ----
+extern "C" int zsmi_compressBoundsDevice(zsmi_ctx *c, const uint32_t *dSrcSizes, uint32_t n, uint64_t *dBounds)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (n && (!dSrcSizes || !dBounds)) return ZSMI_error_GENERIC;
+    if (n == 0) return 0;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    LAUNCH(c, "k_compress_bounds", k_compress_bounds, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, dBounds);
+    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+}
+extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                          uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (n && (!dSrc || !dSrcOffsets || !dSrcSizes || !dDst || !dDstOffsets || !dDstSizes)) return ZSMI_error_GENERIC;
+    if (n == 0) return 0;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    const LzShape &shape = lzShape(level);
+    const uint32_t nbMax = zs_chunk_counts(maxSrcSize).blocks, bigMax = (nbMax + 1) / 2;
+    const uint32_t cap = std::max<uint32_t>((uint32_t)std::min<uint64_t>((uint64_t)n * nbMax, std::max<uint32_t>(64, c->maxBlocksInFlight)), nbMax);
+    const uint32_t K = std::min(n, cap / nbMax), subs = (n + K - 1) / K;
+    zsmi_ctx::Scratch &S = c->scratch;
+    if (!S.reserve(cap)) return ZSMI_error_memory_allocation;
+    zsmi_ctx::ResidentPlan &R = c->resident;
+    const size_t nUnitSlots = (size_t)K + (nbMax > 1 ? (size_t)K * bigMax : 0);
+    if (!R.dChunks.reserve(sizeof(ZsChunkDesc) * n) || !R.dBefore.reserve(sizeof(ZsPlanBefore) * n) || !R.dCounts.reserve(sizeof(ZsPlanCounts) * subs) ||
+        !R.dBlocks.reserve(sizeof(ZsBlockDesc) * (size_t)K * nbMax) || !R.dUnits.reserve(sizeof(ZsUnitDesc) * nUnitSlots)) return ZSMI_error_memory_allocation;
+    ZsChunkDesc *dChunks = (ZsChunkDesc *)R.dChunks.p;
+    const ZsPlanBefore *dBefore = (const ZsPlanBefore *)R.dBefore.p;
+    const ZsPlanCounts *dCounts = (const ZsPlanCounts *)R.dCounts.p;
+    ZsPlanLists lists = { (ZsBlockDesc *)R.dBlocks.p, (ZsUnitDesc *)R.dUnits.p, 0u, K };
+    LAUNCH(c, "k_plan_chunks", k_plan_chunks, dim3(subs), dim3(ZS_PLAN_THREADS), 0, dSrcOffsets, dSrcSizes, dDstOffsets, n, K, maxSrcSize,
+           dChunks, (ZsPlanBefore *)R.dBefore.p, (ZsPlanCounts *)R.dCounts.p);
+    SubBatch sb;
+    sb.dChunks = dChunks; sb.dBlocks = lists.blocks; sb.block0 = 0; sb.cap = cap; sb.assemble = nbMax > 1;
+    sb.rep = make_uint4(1u, 4u, 8u, 0u);
+    for (uint32_t s = 0; s < subs; s++) {
+        const uint32_t chunk0 = s * K, nChunks = std::min(K, n - chunk0);
+        // the lists are the sub-batch's alone: every sub-batch writes them again, behind the kernels that read the one before's
+        LAUNCH(c, "k_plan_blocks", k_plan_blocks, dim3((nChunks * nbMax + 255) / 256), dim3(256), 0, (const ZsChunkDesc *)dChunks + chunk0, dBefore + chunk0,
+               dCounts + s, nChunks, chunk0, lists);
+        sb.chunk0 = chunk0; sb.nChunks = nChunks; sb.nb = nChunks * nbMax; sb.live = &dCounts[s].blocks;
+        sb.units[kUnitsPfx] = { nullptr, 0 };
+        sb.units[kUnitsSmall] = { lists.units + lists.smallBase, nChunks };
+        sb.units[kUnitsBig] = { lists.units + lists.bigBase, nbMax > 1 ? nChunks * bigMax : 0u };
+        launchSubBatch(c, shape, sb, dSrc, dDst, dDstSizes, nullptr);
+    }
+    if (c->checksumFlag && !c->stopAfterWalk && !c->stopLit && !c->stopSeq)
+        LAUNCH(c, "k_frame_checksum", k_frame_checksum, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, (const ZsChunkDesc *)dChunks, n, (uint8_t *)dDst, dDstSizes);
+    // last: a chunk above maxSrcSize was planned as an empty one, and its size word says so only now
+    LAUNCH(c, "k_plan_refuse", k_plan_refuse, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, maxSrcSize, 0u - (uint32_t)ZSMI_error_srcSize_wrong, dDstSizes);
+    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
 // dDict: device memory.  The dictionary loader runs over it and its record (a formatted dictionary's ID, recent offsets and content
 // offset, or the refusal) is read back: the call waits for the context's stream once.
