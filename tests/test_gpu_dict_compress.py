@@ -155,6 +155,31 @@ def test_first_block_starts_from_the_dictionarys_recent_offsets(codec):
             B.assert_round_trip(codec, frames, chunks, dic)
 
 
+@pytest.mark.parametrize("level", [1, 3])
+def test_every_frame_kind_takes_offsets_and_id_from_the_dictionary_record(codec, level):
+    """one call over an empty chunk, a one-block chunk (the literals kernel writes its frame) and chunks of two and three blocks
+    (k_assemble_frames), with a formatted dictionary whose recent offsets are not {1, 4, 8} and whose ID is not 0: oracle E's frames.  The
+    same chunks through a CompressionDict and through a set of it and a raw-content one, chosen 0, 1, NO_DICT, 0: every chunk gets the frame
+    of the call with its dictionary alone"""
+    from zstandard_amd import CompressionDict, CompressionDictSet, NO_DICT
+    dic = X.with_reps(X.trained("json_records"), (2, 3, 5))
+    assert int.from_bytes(dic[4:8], "little") != 0
+    raw = dictionaries()["raw6000"]
+    data = X.class_data("json_records")
+    chunks = [b"", data[5000:6000], data[70000:70000 + 65537], data[200000:200000 + 140000]]
+    frames = assert_matches_oracle(codec, chunks, level, dic, "by bytes")
+    B.assert_round_trip(codec, frames, chunks, dic)
+    cd, cd_raw = CompressionDict(codec, dic, level), CompressionDict(codec, raw, level)
+    digested = B.compress_many(codec, chunks, cdict=cd)
+    B.assert_round_trip(codec, digested, chunks, dic)
+    with_raw, plain = B.compress_many(codec, chunks, cdict=cd_raw), B.compress_many(codec, chunks, level)
+    assert with_raw == B.oracle_frames(chunks, level, raw) and plain == B.oracle_frames(chunks, level)
+    src, offs, sizes = B.batch(chunks)
+    index = np.array([0, 1, NO_DICT, 0], dtype=np.uint32)
+    mixed = B.frames_of(codec.compress_host(src, offs, sizes, cdict_set=CompressionDictSet(codec, [cd, cd_raw], level), dict_index=index), len(chunks))
+    assert mixed == [digested[0], with_raw[1], plain[2], digested[3]]
+
+
 # ------------------------------------------------------------------ errors
 def test_corrupted_dictionaries_are_refused(codec):
     L = codec.L

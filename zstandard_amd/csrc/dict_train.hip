@@ -326,7 +326,8 @@ static int finalizeQueue(zsmi_ctx *c, const uint8_t *dSamples, const std::vector
     uint32_t *dStats = (uint32_t *)c->train.dMisc.p, *dId = dStats + kTrainStatWords;
     uint8_t *dHdr = (uint8_t *)(dId + 8);
     if (hipMemsetAsync(dStats, 0, sizeof(uint32_t) * kTrainStatWords, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    ZsCompressDict dict; dict.dBytes = dContent; dict.contentSize = contentSize;
+    ZsCDictSel dict;
+    if (const int e = dictFromBytes(c, dContent, contentSize, kDictContent, level, n, dict)) return e;
     if (const int e = compressBatchDeviceImpl(c, dSamples, offs.data(), sizes.data(), n, c->train.dArena.p, dof.data(), (uint32_t *)c->train.dSizes.p, level, &dict, 0, dStats)) return e;
     LAUNCH(c, "k_train_id", k_train_id, dim3(1), dim3(64), 0, dContent, contentSize, dictID, dId);
     LAUNCH(c, "k_train_tables", k_train_tables, dim3(1), dim3(256), 0, (const uint32_t *)dStats, dContent, contentSize, cap, (const uint32_t *)dId, dHdr, dOut, dResult);
@@ -402,9 +403,10 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
         for (uint32_t i = 0; i < nt; i++) { dof[i] = at; at += zsmi_compressBound(ss[i]); }
         if (!c->train.dArena.reserve(at + 64) || !c->train.dSizes.reserve(sizeof(uint32_t) * (size_t)nt * nc + 64)) return ZSMI_error_memory_allocation;
         for (uint32_t i = 0; i < nc; i++) {
-            ZsCompressDict dict; dict.dBytes = hc[i].content + hTails[i]; dict.contentSize = cap32 - hTails[i];
+            ZsCDictSel dict;                                                    // (no content: the plain call)
+            if (const int e = dictFromBytes(c, hc[i].content + hTails[i], cap32 - hTails[i], kDictContent, t.level, nt, dict)) return e;
             uint32_t *dSizes = (uint32_t *)c->train.dSizes.p + (size_t)nt * i;
-            if (const int e = compressBatchDeviceImpl(c, dSamples, so.data(), ss.data(), nt, c->train.dArena.p, dof.data(), dSizes, t.level, dict.contentSize ? &dict : nullptr, 0)) return e;
+            if (const int e = compressBatchDeviceImpl(c, dSamples, so.data(), ss.data(), nt, c->train.dArena.p, dof.data(), dSizes, t.level, &dict, 0)) return e;
         }
         std::vector<uint32_t> hs((size_t)nt * nc);
         if (hipMemcpyAsync(hs.data(), c->train.dSizes.p, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;

@@ -7,8 +7,8 @@
 //   k_train_stats       (1 block per workgroup)                  -> the dictionary trainer's finalize: counts of what the sequences kernel coded
 //   k_cdict_tables      (one workgroup)                          -> a digested dictionary's entropy tables in encoder form (ZsCDictTables)
 //   k_pack_tile_sums, k_pack_scan_tiles, k_pack_offsets, k_pack_copy                                  -> frames in bound-sized slots packed back to back
-// k_encode_sequences and k_encode_literals are templates on CD alone (a digested dictionary's tables are used); every form takes the
-// dictionary's recent offsets / ID as arguments ({1, 4, 8} / 0 without one).  Every FSE encoding table - a block's, a predefined one, the
+// k_encode_sequences and k_encode_literals are templates on CD alone (a record's entropy tables may code a frame's first block); every
+// form takes a frame's recent offsets / ID from its chunk's dictionary record ({1, 4, 8} / 0 without one).  Every FSE encoding table - a block's, a predefined one, the
 // Huffman weights', a digested dictionary's - is built by buildCTableWave over the shared builder of zsmi_fse.h, which also holds the
 // alphabets' constants.  Scalar statement of the same algorithm: oracle/zso_encoder.c (compressBlock and below); the two
 // must agree bit for bit.  Every piece is the format-inverse of a function of the reference decoder:
@@ -129,6 +129,7 @@ struct K3Lds {                       // literals kernel
         struct { uint32_t T[2052]; uint32_t wpar[4], wcnt[4]; uint32_t sel[16]; } gm;   // literal gather: a bit per block byte (toggles at match ends -> inside a match -> literal), per-wavefront parities / literal counts, byte-compaction selectors
     } u;
     uint32_t misc[16];
+    uint32_t dictID;                 // a one-block chunk's dictionary ID, from where its header is sized to where it is written: the kernel has no register to hold it (63 VGPRs, SGPRs spilled)
     uint32_t wcount[16]; int16_t wnorm[16]; uint32_t rankStart[16], rankCount[16];   // small tables kept out of scratch memory
 };
 // cd[] lies below pm.S, which huffCodesAndWeights writes before k_cdict_tables builds its tables; fse (wave 0, the table description)
@@ -561,6 +562,12 @@ struct ZsChunkDesc { uint64_t srcOff; uint64_t dstOff; uint32_t size; uint32_t f
 
 // frame header of a chunk (magic + FHD + FCS, single segment); returns its size.  One thread writes it.
 // dictID != 0 (dictionary calls): the dictionary ID field between FHD and FCS, in 1, 2 or 4 bytes (the fewest that hold it, as libzstd)
+// the dictionary ID of a chunk's frame: its record's (dictTab[chunkDict[chunk]], one address a workgroup), 0 without a table or a record
+__device__ __forceinline__ uint32_t zs_chunk_dict_id(const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict, uint32_t chunk)
+{
+    const uint32_t e = dictTab ? (chunkDict ? chunkDict[chunk] : 0u) : ZS_DICT_NONE;
+    return e != ZS_DICT_NONE ? dictTab[e].dictID : 0u;
+}
 __device__ __forceinline__ uint32_t zs_frame_header(uint8_t *out, uint32_t size, bool writer, uint32_t dictID = 0)
 {
     const uint32_t didCode = (dictID != 0) + (dictID >= 256) + (dictID >= 65536), didSize = didCode == 3 ? 4 : didCode;
@@ -607,10 +614,9 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
 // literal gather (a stream compaction of the block) + histogram, Huffman lengths by package-merge (256 threads),
 // table description (one lane), the 4 Huffman streams (one wavefront each)  -> litSec[], meta.{type, rleByte, litSecSize}
 // ---------------------------------------------------------------------------------------------
-// (dictID: the dictionary ID the frame headers carry, 0 for none - the form without CD.  CD: the ID is the chunk's record's
-//  (dictTab[chunkDict[chunk]], ZsCDictEntry), and with a digested dictionary's Huffman codes in the record's tables the first block of a
-//  frame is coded as Treeless literals (type 3) iff every literal byte has a code and that section is strictly smaller than the one the
-//  rules below produce)
+// (dictTab, chunkDict: the call's dictionary records (ZsCDictEntry; null: none) and the record index a chunk (null: record 0; ZS_DICT_NONE:
+//  none).  The frame header carries the ID of the chunk's record, 0 without one.  CD: with a digested dictionary's Huffman codes in the record's tables the
+//  first block of a frame is coded as Treeless literals (type 3) iff every literal byte has a code and that section is strictly smaller than the rules' below)
 #define ZS_LIT_PARAMS const uint8_t *__restrict__ src, const ZsBlockDesc *__restrict__ blocks, \
                       const ZsSeqRec *__restrict__ seqAll, const uint32_t *__restrict__ hdrAll, \
                       uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, uint8_t *__restrict__ litSecAll, \
@@ -618,20 +624,19 @@ __device__ __forceinline__ uint32_t zs_emit_block(uint8_t *out, uint32_t pos, co
                       const ZsChunkDesc *__restrict__ chunks, const uint8_t *__restrict__ seqSecAll, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes
 #define ZS_LIT_ARGS src, blocks, seqAll, hdrAll, litsAll, streamAll, litSecAll, metas, stopAt, chunks, seqSecAll, dst, dstSizes
 template <bool CD>
-__device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
+__device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
 {
     __shared__ K3Lds L;
     const uint32_t blk = blockIdx.x;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const ZsBlockDesc bd = blocks[blk];
-    // CD: a frame's first block takes the ID and the tables of its chunk's record (the workgroup's one address); no record, or one without
-    // tables: cdt stays null and the block is coded as by the form without CD
+    // CD: a frame's first block takes the tables of its chunk's record (the workgroup's one address); no record, or one without tables:
+    // cdt stays null and the block is coded as by the form without CD
     const ZsCDictTables *__restrict__ cdt = nullptr;
     if constexpr (CD) {
-        dictID = 0;
-        if (bd.firstInChunk) {
+        if (dictTab && bd.firstInChunk) {
             const uint32_t e = chunkDict ? chunkDict[bd.chunk] : 0u;
-            if (e != ZS_DICT_NONE) { dictID = dictTab[e].dictID; cdt = dictTab[e].tables; }
+            if (e != ZS_DICT_NONE) cdt = dictTab[e].tables;
         }
     }
     const uint8_t *s = src + bd.srcOff;
@@ -643,7 +648,11 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
     // slot holds zsmi_compressBound(n) >= n + 27 bytes, the section never more than n + 3), every other block's in the section buffer
     const bool solo = bd.firstInChunk && bd.lastInChunk && !ZS_STOPPED;
     uint8_t *payload = zs_block_lit_section(litSecAll, blk);
-    if (solo) { const ZsChunkDesc cd0 = chunks[bd.chunk]; payload = dst + cd0.dstOff + zs_frame_header(nullptr, cd0.size, false, dictID) + 3; }
+    if (solo) {                                      // (the ID waits in LDS for FINISH, which reads it behind its barrier)
+        const uint32_t id0 = zs_chunk_dict_id(dictTab, chunkDict, bd.chunk);
+        if (tid == 0) L.dictID = id0;
+        const ZsChunkDesc cd0 = chunks[bd.chunk]; payload = dst + cd0.dstOff + zs_frame_header(nullptr, cd0.size, false, id0) + 3;
+    }
     const uint32_t cap = n + 512;
 
     // The block's literal side is done: its meta goes out; a chunk of ONE block is assembled right here (the sequences kernel ran before this
@@ -655,7 +664,7 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
             ZsBlockMeta m_ = zs_block_meta(metas, blk); m_.type = (tp); m_.rleByte = (rb); m_.litSecSize = (lsz); \
             const ZsChunkDesc cd_ = chunks[bd.chunk]; \
             uint8_t *out_ = dst + cd_.dstOff; \
-            uint32_t pos_ = zs_frame_header(out_, cd_.size, tid == 0, dictID); \
+            uint32_t pos_ = zs_frame_header(out_, cd_.size, tid == 0, L.dictID); \
             pos_ += zs_emit_block(out_, pos_, s, n, 1u, m_, payload, zs_block_seq_section(seqSecAll, blk), tid, 256); \
             if (tid == 0) dstSizes[bd.chunk] = pos_; \
         } \
@@ -995,11 +1004,11 @@ __device__ __forceinline__ void encode_literals_block(ZS_LIT_PARAMS, uint32_t di
 // liveBlocks (a plan built on the device, plan_kernels.hip: the grid is the host's upper bound): the blocks the list holds - a workgroup at
 // or beyond them leaves.  Null: the grid is the list
 template <bool CD>
-__global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS, uint32_t dictID, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict,
+__global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PARAMS, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict,
                                                                        const uint32_t *__restrict__ liveBlocks)
 {
     if (liveBlocks && blockIdx.x >= *liveBlocks) return;
-    encode_literals_block<CD>(ZS_LIT_ARGS, dictID, dictTab, chunkDict);
+    encode_literals_block<CD>(ZS_LIT_ARGS, dictTab, chunkDict);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1022,8 +1031,7 @@ __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PA
 #ifndef ZS_CHAIN_MINSEG
 #define ZS_CHAIN_MINSEG 4u         // shortest segment, in blocks of 16 steps
 #endif
-// reps: the recent offsets a chunk's first block starts from ({1, 4, 8}, or a formatted dictionary's own) - the form without CD; with CD
-// they are the chunk's record's (dictTab[chunkDict[chunk]], ZsCDictEntry)
+// (dictTab, chunkDict: as k_encode_literals'.  A chunk's first block starts from its record's recent offsets, {1, 4, 8} without one)
 #define ZS_SEQ_PARAMS const ZsBlockDesc *__restrict__ blocks, uint32_t nBlocks, const ZsSeqRec *__restrict__ seqAll, const uint32_t *__restrict__ hdrAll, \
                       uint8_t *__restrict__ seqSecAll, ZsBlockMeta *__restrict__ metas, int stopAt, uint8_t *__restrict__ litsAll, uint8_t *__restrict__ streamAll, \
                       uint2 *__restrict__ packRecAll
@@ -1033,8 +1041,7 @@ __global__ void __launch_bounds__(256, ZS_LIT_MINWG) k_encode_literals(ZS_LIT_PA
 // below the estimate of what the rules below pick: RLE one byte, the predefined table its own sum of count x cost, a new table its
 // description's bytes plus that sum over its normalised counts (in 1/256 bit throughout)
 template <int G, bool CD>
-__device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t rep0, uint32_t rep1, uint32_t rep2, const ZsCDictEntry *__restrict__ dictTab,
-                                                       const uint32_t *__restrict__ chunkDict)
+__device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
 {
     __shared__ SeqLds LS[G];
     const uint32_t wave = threadIdx.x >> 6;
@@ -1043,19 +1050,11 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
     const uint32_t lane = (uint32_t)zs_lane();
     const bool exists = blk < nBlocks;
     const ZsBlockDesc bd = blocks[exists ? blk : 0];
-    // CD: a frame's first block takes the recent offsets and the tables of its chunk's record (the wavefront's one address); no record:
-    // {1, 4, 8}; no tables: cdt stays null and the block is coded as by the form without CD
+    // A frame's first block reads its chunk's record (the wavefront's one address; none: ZS_DICT_NONE): its recent offsets where pass 1 starts from
+    // them ({1, 4, 8} without a record), and, CD, its tables - no tables: cdt stays null and the block is coded as by the form without CD
+    const uint32_t dictEntry = (dictTab && bd.firstInChunk) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(chunkDict ? chunkDict[bd.chunk] : 0u)) : ZS_DICT_NONE;
     const ZsCDictTables *__restrict__ cdt = nullptr;
-    if constexpr (CD) {
-        rep0 = 1u; rep1 = 4u; rep2 = 8u;
-        if (bd.firstInChunk) {
-            const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)(chunkDict ? chunkDict[bd.chunk] : 0u));
-            if (e != ZS_DICT_NONE) {
-                const ZsCDictEntry &de = dictTab[e];
-                rep0 = de.rep[0]; rep1 = de.rep[1]; rep2 = de.rep[2]; cdt = de.tables;
-            }
-        }
-    }
+    if constexpr (CD) { if (dictEntry != ZS_DICT_NONE) cdt = dictTab[dictEntry].tables; }
     const uint32_t n = bd.size;
     const ZsSeqRec *seqBase = zs_block_seqs(seqAll, blk);
     uint8_t *out = zs_block_seq_section(seqSecAll, blk);
@@ -1092,7 +1091,9 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
         //   whose offset differed from its rep1: two "last index below me" scans per 64 sequences. ----
         {
             uint32_t cPrev, cA, cB;                       // carried: previous offset (= rep0), rep1, rep2
-            if (bd.firstInChunk) { cPrev = rep0; cA = rep1; cB = rep2; } else { cPrev = 0xFFFFFFF1u; cA = 0xFFFFFFF2u; cB = 0xFFFFFFF3u; }
+            if (!bd.firstInChunk) { cPrev = 0xFFFFFFF1u; cA = 0xFFFFFFF2u; cB = 0xFFFFFFF3u; }
+            else if (dictEntry == ZS_DICT_NONE) { cPrev = 1u; cA = 4u; cB = 8u; }
+            else { const ZsCDictEntry &de = dictTab[dictEntry]; cPrev = de.rep[0]; cA = de.rep[1]; cB = de.rep[2]; }
             uint32_t cEnd = 0;                            // carried: where the sequence before ends in the block (its literals start there)
             // tile t is the records [64 t, 64 t + 64) of the block's list; the records of the next tiles are loaded while these are worked on
             // (a record travels as its two raw words and is taken apart only where it is used: unpacked next to the load, the
@@ -1463,11 +1464,11 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, uint32_t r
 }
 // liveBlocks: as k_encode_literals' - it stands in for nBlocks, and a workgroup none of whose G blocks is live leaves
 template <int G, bool CD>
-__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint4 reps, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict,
+__global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict,
                                                              const uint32_t *__restrict__ liveBlocks)
 {
     if (liveBlocks) { nBlocks = *liveBlocks; if (blockIdx.x * G >= nBlocks) return; }
-    encode_sequences_block<G, CD>(ZS_SEQ_ARGS, reps.x, reps.y, reps.z, dictTab, chunkDict);
+    encode_sequences_block<G, CD>(ZS_SEQ_ARGS, dictTab, chunkDict);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1479,20 +1480,14 @@ __global__ void __launch_bounds__(64 * G) k_encode_sequences(ZS_SEQ_PARAMS, uint
 #define ZS_ASM_PARAMS const uint8_t *__restrict__ src, const ZsChunkDesc *__restrict__ chunks, const ZsBlockDesc *__restrict__ blocks, \
                       const ZsBlockMeta *__restrict__ metas, const uint8_t *__restrict__ litSecAll, const uint8_t *__restrict__ seqSecAll, \
                       uint32_t blockBase, uint8_t *__restrict__ dst, uint32_t *__restrict__ dstSizes, uint32_t chunkBase
-// dictID: the dictionary ID the frame header carries, 0 for none; with a table (the launches that take the CD forms of the entropy kernels)
-// it is the chunk's record's, dictTab[chunkDict[chunk]]
-extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAMS, uint32_t dictID, const ZsCDictEntry *__restrict__ dictTab,
-                                                                    const uint32_t *__restrict__ chunkDict)
+// (dictTab, chunkDict: as k_encode_literals' - the dictionary ID the frame header carries is the chunk's record's, 0 without one)
+extern "C" __global__ void __launch_bounds__(256) k_assemble_frames(ZS_ASM_PARAMS, const ZsCDictEntry *__restrict__ dictTab, const uint32_t *__restrict__ chunkDict)
 {
     const ZsChunkDesc cd = chunks[chunkBase + blockIdx.x];
     if (cd.nBlocks <= 1) return;                               // one-block chunks were assembled by the literals kernel
-    if (dictTab) {
-        const uint32_t e = chunkDict ? chunkDict[chunkBase + blockIdx.x] : 0u;
-        dictID = e != ZS_DICT_NONE ? dictTab[e].dictID : 0u;
-    }
     uint8_t *out = dst + cd.dstOff;
     const uint32_t tid = threadIdx.x;
-    uint32_t pos = zs_frame_header(out, cd.size, tid == 0, dictID);
+    uint32_t pos = zs_frame_header(out, cd.size, tid == 0, zs_chunk_dict_id(dictTab, chunkDict, chunkBase + blockIdx.x));
     for (uint32_t b = 0; b < cd.nBlocks; b++) {
         const uint32_t gb = cd.firstBlock + b;             // global block index
         const uint32_t lb = gb - blockBase;                // index inside this sub-batch's scratch

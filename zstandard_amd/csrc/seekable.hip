@@ -320,8 +320,8 @@ static int seekParseDevice(zsmi_ctx *c, const uint8_t *src, uint64_t srcSize, Se
 // and each of its overlaps with a range is a PIECE {scratch offset, dDst offset, length} for k_seek_gather, cut into tiles of kSeekTile.
 // That is one decode call for the owned frames and one for the scratch frames, whatever nRanges is.  k_seek_verify leaves a code per slot; a
 // range's frames are consecutive slots {firstSlot, count}, which k_seek_range_status reduces to dStatus[r].
-//   The call's lists (verify items, pieces, spans) travel through one of two pinned buffers taken in turn, each guarded by an event, as the
-// decoder's item list does (uploadDecodeItems): nothing here waits for the stream.
+//   The call's lists (verify items, pieces, spans) travel through pinned buffers taken in turn (TurnBufs, zsmi_ctx.h), as the decoder's
+// item list does (uploadDecodeItems): nothing here waits for the stream.
 struct SeekRange { uint64_t a, b, to; };
 static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames, uint64_t base, const SeekRange *rg, uint32_t nRanges,
                           uint8_t *dDst, uint32_t *dStatus, uint32_t *framesDecoded)
@@ -392,16 +392,15 @@ static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrame
     // device words: decoder status [m] (the owned frames' call, then the scratch frames'), codes [m]; (8-aligned) the lists: items, pieces, spans
     const size_t words = (2 * (size_t)m * sizeof(uint32_t) + 7) & ~(size_t)7;
     const size_t listBytes = (size_t)m * sizeof(ZsSeekItem) + nPieces * sizeof(ZsSeekPiece) + (size_t)nRanges * sizeof(ZsSeekSpan);
-    const int hb = (int)(c->seek.calls++ & 1u);
-    if (c->seek.hBusy[hb]) { if (hipEventSynchronize(c->seek.hEv[hb]) != hipSuccess) return ZSMI_error_GENERIC; c->seek.hBusy[hb] = false; }
-    if (!c->seek.dMeta.reserve(words + listBytes) || !c->seek.hLists[hb].reserve(listBytes)) return ZSMI_error_memory_allocation;
+    ZsSeekItem *hi;
+    if (const int e = c->seek.hLists.take(listBytes, hi)) return e;
+    if (!c->seek.dMeta.reserve(words + listBytes)) return ZSMI_error_memory_allocation;
     if (m > nOwned && !c->seek.dDec.reserve(scratchBytes + 64)) return ZSMI_error_memory_allocation;
     uint32_t *dSt = (uint32_t *)c->seek.dMeta.p, *dCodes = dSt + m;
     uint8_t *dLists = (uint8_t *)c->seek.dMeta.p + words, *dS = (uint8_t *)c->seek.dDec.p;
     const ZsSeekItem *dItems = (const ZsSeekItem *)dLists;
     const ZsSeekPiece *dPieces = (const ZsSeekPiece *)(dItems + m);
     const ZsSeekSpan *dSpans = (const ZsSeekSpan *)(dPieces + nPieces);
-    ZsSeekItem *hi = (ZsSeekItem *)c->seek.hLists[hb].p;
     ZsSeekPiece *hp = (ZsSeekPiece *)(hi + m);
     ZsSeekSpan *hs = (ZsSeekSpan *)(hp + nPieces);
     // the two decode calls' items: the owned frames (status words [0, nOwned)), then the scratch frames ([nOwned, m)), each in index order
@@ -416,8 +415,7 @@ static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrame
     if (!tiles.empty()) memcpy(hp + small.size(), tiles.data(), tiles.size() * sizeof(ZsSeekPiece));
     for (uint32_t r = 0; r < nRanges; r++) hs[r] = { firstSlot[r], sp[r].count };
     if (hipMemcpyAsync(dLists, hi, listBytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipEventRecord(c->seek.hEv[hb], c->stream) != hipSuccess) { (void)hipStreamSynchronize(c->stream); return ZSMI_error_GENERIC; }   // (the buffer is idle after that)
-    c->seek.hBusy[hb] = true;
+    if (const int e = c->seek.hLists.sent(c->stream)) return e;
     if (nOwned)
         if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), nOwned, dDst, dof.data(), caps.data(), dSt, nullptr)) return e;
     if (m > nOwned) {

@@ -149,9 +149,7 @@ extern "C" zsmi_ctx *zsmi_createCtx(int device, void *hipStream)
             ok &= hipFuncSetAttribute((const void *)s.walk[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.walk[k].lds) == hipSuccess &&
                   hipFuncGetAttributes(&fa, (const void *)s.walk[k].fn) == hipSuccess && fa.sharedSizeBytes == 0;
         }
-    for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->hItemsEv[i], hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->seek.hEv[i], hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 2; i++) ok &= hipEventCreateWithFlags(&c->plan.hDictEv[i], hipEventDisableTiming) == hipSuccess;
+    for (TurnBufs *t : { &c->hItems, &c->seek.hLists, &c->plan.hDictList }) ok &= t->create();
     if (!ok) { (void)hipGetLastError(); zsmi_freeCtx(c); return nullptr; }
     if (const char *e = getenv("ZSMI_BLOCKS_IN_FLIGHT")) { long v = atol(e); if (v >= 64) c->maxBlocksInFlight = (uint32_t)v; }
     if (const char *e = getenv("ZSMI_DEC_FAST")) c->decodeFast = atoi(e) != 0;
@@ -169,13 +167,10 @@ extern "C" void zsmi_freeCtx(zsmi_ctx *c)
 {
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 2; i++) if (c->hItemsEv[i]) (void)hipEventDestroy(c->hItemsEv[i]);
-    for (int i = 0; i < 2; i++) if (c->seek.hEv[i]) (void)hipEventDestroy(c->seek.hEv[i]);
-    for (int i = 0; i < 2; i++) if (c->plan.hDictEv[i]) (void)hipEventDestroy(c->plan.hDictEv[i]);
     for (auto &tl : c->launches) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->eventPool) (void)hipEventDestroy(e);
     if (c->ownStream) (void)hipStreamDestroy(c->stream);
-    delete c;                                    // (and with it every buffer the context holds)
+    delete c;                                    // (and with it every buffer the context holds, and the turn buffers' events)
 }
 extern "C" int zsmi_sync(zsmi_ctx *c)
 {
@@ -323,7 +318,7 @@ int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const ui
     auto choice = [&](uint32_t i) -> uint32_t {
         if (!dictIndex) return 0u;
         const uint32_t e = dictIndex[i];
-        return (e == ZS_DICT_NONE || !memberHasDict[e]) ? ZS_DICT_NONE : e;
+        return (e == ZS_DICT_NONE || (memberHasDict && !memberHasDict[e])) ? ZS_DICT_NONE : e;
     };
     bool have = dictKind == kind && (kind == kDictAll || dictKey.size() == (size_t)n);
     if (kind == kDictPerChunk) for (uint32_t i = 0; have && i < n; i++) have = dictKey[i] == choice(i);
@@ -342,11 +337,10 @@ int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const ui
     whole.before[n] = nWhole; tail.before[n] = nTail;
     const size_t unitBytes = sizeof(ZsUnitDesc) * ((size_t)nWhole + nTail);
     const size_t bytes = unitBytes + (kind == kDictPerChunk ? sizeof(uint32_t) * ((size_t)n + nWhole) : 0);
-    const int hb = (int)(dictBuilds++ & 1u);
-    if (hDictBusy[hb]) { if (hipEventSynchronize(hDictEv[hb]) != hipSuccess) return ZSMI_error_GENERIC; hDictBusy[hb] = false; }
-    if (!hDictList[hb].reserve(bytes + 16) || !dDictList.reserve(bytes + 16)) return ZSMI_error_memory_allocation;
-    ZsUnitDesc *hu = (ZsUnitDesc *)hDictList[hb].p;
-    uint32_t *hChunkDict = (uint32_t *)((uint8_t *)hDictList[hb].p + unitBytes), *hUnitDict = hChunkDict + n;
+    ZsUnitDesc *hu;
+    if (const int e = hDictList.take(bytes + 16, hu)) return e;
+    if (!dDictList.reserve(bytes + 16)) return ZSMI_error_memory_allocation;
+    uint32_t *hChunkDict = (uint32_t *)((uint8_t *)hu + unitBytes), *hUnitDict = hChunkDict + n;
     const ZsUnitDesc *all = (const ZsUnitDesc *)hUnits.p;
     uint32_t iw = 0, it = nWhole;
     for (uint32_t i = 0; i < n; i++) {                                       // the small units are in chunk order
@@ -357,8 +351,7 @@ int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const ui
     }
     if (bytes) {
         if (hipMemcpyAsync(dDictList.p, hu, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
-        if (hipEventRecord(hDictEv[hb], stream) != hipSuccess) { (void)hipStreamSynchronize(stream); return ZSMI_error_GENERIC; }   // (the buffer is idle after that)
-        hDictBusy[hb] = true;
+        if (const int e = hDictList.sent(stream)) return e;
     }
     whole.base = 0; tail.base = nWhole; chunkDictOff = unitBytes; unitDictOff = unitBytes + sizeof(uint32_t) * (size_t)n;
     dictKind = kind;
@@ -380,19 +373,13 @@ CompressPlan::Units CompressPlan::units(int kind, bool dict, uint32_t chunk0, ui
     return { (const ZsUnitDesc *)(ownList ? dDictList : dUnits).p + r.base + r.before[chunk0], r.before[chunk1] - r.before[chunk0] };
 }
 
-// the prefix: the dictionary content's last <= 64 KiB, where a prefixed unit's matches may reach
-struct DictPrefix { const uint8_t *d; uint32_t size; };
-static DictPrefix dictPrefix(const ZsCompressDict &d)
-{
-    const uint32_t size = std::min<uint32_t>(d.contentSize, ZS_BLOCK_MAX);
-    return { d.dBytes + d.contentOff + d.contentSize - size, size };
-}
-// a dictionary's record as the kernels read it (its images at dImg)
+// a dictionary's record as the kernels read it, its images at dImg.  The prefix: the content's last <= 64 KiB, where a prefixed unit's
+// matches may reach
 static ZsCDictEntry dictEntry(const ZsCompressDict &d, const uint32_t *dImg)
 {
-    const DictPrefix pre = dictPrefix(d);
     ZsCDictEntry e;
-    e.pre = pre.d; e.img = dImg; e.tables = d.dTables; e.pfx = pre.size; e.dictID = d.dictID; e.pad = 0;
+    e.pfx = std::min<uint32_t>(d.contentSize, ZS_BLOCK_MAX); e.pre = d.dBytes + d.contentOff + d.contentSize - e.pfx;
+    e.img = dImg; e.tables = d.dTables; e.dictID = d.dictID; e.pad = 0;
     for (int i = 0; i < 3; i++) e.rep[i] = d.rep[i];
     return e;
 }
@@ -402,6 +389,26 @@ static const size_t kDictImgBytes = (size_t)2 << (ZS_TABLE_LOG_BIG + 2);
 static void launchDictTables(zsmi_ctx *c, const ZsCompressDict &d, int level, void *dImg, void *dEntry)
 {
     LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(lzShape(level).useLong ? 2 : 1), dim3(1024), 0, dictEntry(d, (const uint32_t *)dImg), (ZsCDictEntry *)dEntry);
+}
+static int dictFromBytes(zsmi_ctx *c, const void *dict, size_t dictSize, DictBytes kind, int level, uint32_t n, ZsCDictSel &sel)
+{
+    if (!dict || dictSize == 0) return 0;
+    if (!c) return ZSMI_error_init_missing;
+    if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
+    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (kind == kDictOnHost) {                                       // (through the context's staging buffer)
+        if (!c->sDict.reserve(dictSize + 64)) return ZSMI_error_memory_allocation;
+        if (hipMemcpyAsync(c->sDict.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        dict = c->sDict.p;
+    }
+    ZsCompressDict d;
+    d.dBytes = (const uint8_t *)dict; d.contentSize = (uint32_t)dictSize;
+    if (kind != kDictContent) if (const int e = loadDict(c, dict, dictSize, d)) return e;
+    if (n == 0) return 0;                                            // (an empty call gives the dictionary its verdict and builds nothing)
+    if (!c->dDictImg.reserve(kDictImgBytes + sizeof(ZsCDictEntry))) return ZSMI_error_memory_allocation;
+    sel.dTable = (const ZsCDictEntry *)((const uint8_t *)c->dDictImg.p + kDictImgBytes);
+    launchDictTables(c, d, level, c->dDictImg.p, const_cast<ZsCDictEntry *>(sel.dTable));
+    return 0;
 }
 // One sub-batch of a compress call as its kernels take it, whoever planned it - the host (CompressPlan) or the device (plan_kernels.hip).
 //   dChunks: the call's chunk list; dBlocks: the block list a chunk's firstBlock counts in; block0: the sub-batch's first block there
@@ -414,8 +421,8 @@ struct SubBatch {
     CompressPlan::Units units[3]; const uint32_t *dUnitDict = nullptr;
     const uint32_t *live = nullptr;
     bool assemble;                                   // chunks of several blocks may be among them
-    const ZsCDictEntry *dTable = nullptr, *cdt = nullptr; const uint32_t *dChunkDict = nullptr;
-    uint4 rep; uint32_t dictID = 0;
+    const ZsCDictEntry *dTable = nullptr; const uint32_t *dChunkDict = nullptr;      // the dictionary records (null: none) and the record index a chunk (null: record 0)
+    bool cdt = false;                                // some record has entropy tables: the CD forms of the entropy kernels
 };
 static void launchSubBatch(zsmi_ctx *c, const LzShape &shape, const SubBatch &sb, const void *dSrc, void *dDst, uint32_t *dDstSizes, uint32_t *dStats)
 {
@@ -443,71 +450,64 @@ static void launchSubBatch(zsmi_ctx *c, const LzShape &shape, const SubBatch &sb
     if (c->stopAfterWalk) return;
     // The entropy stage.  Sequences first: the literals kernel assembles the frames of one-block chunks as its workgroups finish, and
     // reads the sequence sections then.  (The two side by side on two streams was measured slower: both want the whole LDS.)  Every
-    // kernel takes the dictionary's recent offsets or ID ({1, 4, 8} and 0 without one).  The CD forms (cdt) take offsets, ID and
-    // tables from each chunk's record instead.
-    const ZsCDictEntry *cdt = sb.cdt;
-    const auto seqKernel = cdt ? k_encode_sequences<ZS_SEQ_GROUP, true> : k_encode_sequences<ZS_SEQ_GROUP, false>;
-    const auto litKernel = cdt ? k_encode_literals<true> : k_encode_literals<false>;
+    // kernel takes a frame's recent offsets and ID from its chunk's record ({1, 4, 8} and 0 without one); in the CD forms the record's
+    // entropy tables may code the frame's first block besides.
+    const auto seqKernel = sb.cdt ? k_encode_sequences<ZS_SEQ_GROUP, true> : k_encode_sequences<ZS_SEQ_GROUP, false>;
+    const auto litKernel = sb.cdt ? k_encode_literals<true> : k_encode_literals<false>;
     LAUNCH(c, "k_encode_sequences", seqKernel, dim3((nb + ZS_SEQ_GROUP - 1) / ZS_SEQ_GROUP), dim3(64 * ZS_SEQ_GROUP), 0, dB, nb, S.seqs(),
            S.hdrs(), S.seqSec(), S.metas(), c->stopSeq, S.lits(), S.streams(),
-           S.distAsPackRecords(), sb.rep, cdt, sb.dChunkDict, liveBlocks);
+           S.distAsPackRecords(), sb.dTable, sb.dChunkDict, liveBlocks);
     if (dStats)                                                  // (the codes it reads are in the literal buffers until the literals kernel)
         LAUNCH(c, "k_train_stats", k_train_stats, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(),
                S.hdrs(), S.lits(), dStats);
     LAUNCH(c, "k_encode_literals", litKernel, dim3(nb), dim3(256), 0, (const uint8_t *)dSrc, dB, S.seqs(), S.hdrs(),
            S.lits(), S.streams(), S.litSec(), S.metas(), c->stopLit,
-           sb.dChunks, S.seqSec(), (uint8_t *)dDst, dDstSizes, sb.dictID, cdt, sb.dChunkDict, liveBlocks);
+           sb.dChunks, S.seqSec(), (uint8_t *)dDst, dDstSizes, sb.dTable, sb.dChunkDict, liveBlocks);
     if (sb.assemble)                                             // chunks of several blocks
         LAUNCH(c, "k_assemble_frames", k_assemble_frames, dim3(sb.nChunks), dim3(256), 0, (const uint8_t *)dSrc, sb.dChunks,
                sb.dBlocks, S.metas(), S.litSec(), S.seqSec(), block0,
-               (uint8_t *)dDst, dDstSizes, sb.chunk0, sb.dictID, cdt, sb.dChunkDict);
+               (uint8_t *)dDst, dDstSizes, sb.chunk0, sb.dTable, sb.dChunkDict);
 }
-// The launch sequence of a call, over the plan's sub-batches.  dict: nullptr, or the call's dictionary, in one of three kinds -
-//   content only, or parsed from a formatted dictionary (the _usingDict calls, the trainer): the table images are built here, every call;
-//   digested, raw content (dImg): it brings its images along;
-//   digested, formatted (dImg and dTables): besides, its entropy tables may code a frame's first block.
-// Chunks of <= 64 KiB are PREFIXED units (k_lz_candidates / k_lz_walk with PFX: matches may reach into the prefix); the units of longer
-// chunks are parsed as without a dictionary.  Every frame carries the ID and its first block starts from the dictionary's recent offsets.
-// set (instead of dict): the dictionaries of a zsmi_cdictSet and the call's choice - every chunk its own of the three kinds above, or none.
-// The kernels take the dictionary as a table of records (ZsCDictEntry) and an index a chunk; a single dictionary is the one-entry table
-// with no index.  A call without a dictionary is one with no prefixed units.  dStats (the dictionary trainer's finalize; nullptr on every other path): device
-// counters of the literal bytes and LL / OF / ML codes, added to by k_train_stats after each sub-batch's sequences kernel.
-// checksum: behind the last sub-batch, when every frame and size of the call is final on the stream, k_frame_checksum closes the frames
-// with their Content_Checksum - one launch over all n chunks.  Without it the call launches nothing more and writes nothing else.
+// What both planners share.  The blocks of a sub-batch (its scratch slots): the blocks in flight - never below 64, never more than the call
+// has - and at least the largest chunk's, which goes whole
+static uint32_t subBatchCap(const zsmi_ctx *c, uint64_t blocks, uint32_t maxChunkBlocks)
+{
+    const uint64_t inFlight = std::min<uint64_t>(blocks, std::max<uint32_t>(64, c->maxBlocksInFlight));
+    return std::max<uint32_t>((uint32_t)inFlight, maxChunkBlocks);
+}
+// behind the last sub-batch, when every frame and size is final on the stream: with checksum, ONE k_frame_checksum launch over all n chunks; without it, none
+static void closeFrames(zsmi_ctx *c, const void *dSrc, const ZsChunkDesc *dChunks, uint32_t n, void *dDst, uint32_t *dDstSizes, int checksum)
+{
+    if (checksum && !c->stopAfterWalk && !c->stopLit && !c->stopSeq)     // (a stopped stage leaves no frames to close)
+        LAUNCH(c, "k_frame_checksum", k_frame_checksum, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, dChunks, n, (uint8_t *)dDst, dDstSizes);
+}
+// The launch sequence of a call, over the plan's sub-batches.  dict: the call's selector (ZsCDictSel, zsmi_ctx.h) - nullptr or without a
+// table: the plain call, which is a dictionary call with no prefixed units.  A chunk with a dictionary carries its record's ID and its
+// first block starts from the record's recent offsets; one of <= 64 KiB is a PREFIXED unit (k_lz_candidates / k_lz_walk with PFX: matches
+// may reach into the record's prefix, through the table images that came with the record), the units of longer chunks are parsed as
+// without a dictionary; and a record's entropy tables (a digested, formatted dictionary's) may code the first block.  The kernels take the
+// table and an index a chunk; a single dictionary is the one-entry table with no index.  dStats (the dictionary trainer's finalize; nullptr on every
+// other path): device counters of the literal bytes and LL / OF / ML codes, added to by k_train_stats after each sub-batch's sequences kernel.
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const ZsCompressDict *dict, int checksum, uint32_t *dStats, const ZsCompressDictSet *set)
+                                   const ZsCDictSel *dict, int checksum, uint32_t *dStats)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
     const LzShape &shape = lzShape(level);
     CompressPlan &P = c->plan;
-    if (set) {                                                       // (a choice that gives no chunk a dictionary: the plain call)
-        bool any = false;
-        for (uint32_t i = 0; i < n && !any; i++) any = set->dictIndex[i] != ZS_DICT_NONE && set->memberHasDict[set->dictIndex[i]];
-        if (!any) set = nullptr;
-    }
-    const bool useDict = dict || set;
-    if (const int e = P.build(c->stream, srcOffsets, srcSizes, n, dstOffsets, useDict, set ? set->dictIndex : nullptr, set ? set->memberHasDict : nullptr)) return e;
-    const ZsCDictEntry *dTable = set ? set->dTable : (dict ? dict->dEntry : nullptr);
-    if (dict && !dTable) {
-        if (!c->dDictImg.reserve(kDictImgBytes + sizeof(ZsCDictEntry))) return ZSMI_error_memory_allocation;
-        launchDictTables(c, *dict, level, c->dDictImg.p, (uint8_t *)c->dDictImg.p + kDictImgBytes);
-        dTable = (const ZsCDictEntry *)((const uint8_t *)c->dDictImg.p + kDictImgBytes);
-    }
+    const ZsCDictSel sel = dict && dict->dTable ? *dict : ZsCDictSel();
+    const bool useDict = sel.dTable != nullptr;
+    if (const int e = P.build(c->stream, srcOffsets, srcSizes, n, dstOffsets, useDict, sel.dictIndex, sel.memberHasDict)) return e;
     // sub-batches of whole chunks, one after the other through one scratch set.  Every kernel goes to the caller's stream: a stream of
     // the context's own costs two queue crossings a call (~0.01 - 0.09 ms each: a bench line of 126 GiB/s where the kernels added up to 137).
-    const uint32_t cap = std::max<uint32_t>((uint32_t)std::min<uint64_t>(P.blocks, std::max<uint32_t>(64, c->maxBlocksInFlight)), P.maxChunkBlocks);
+    const uint32_t cap = subBatchCap(c, P.blocks, P.maxChunkBlocks);
     zsmi_ctx::Scratch &S = c->scratch;
     if (!S.reserve(cap)) return ZSMI_error_memory_allocation;
     SubBatch sb;
     sb.dChunks = (const ZsChunkDesc *)P.dChunks.p; sb.dBlocks = (const ZsBlockDesc *)P.dBlocks.p; sb.cap = cap; sb.assemble = P.maxChunkBlocks > 1;
-    sb.dTable = dTable; sb.dChunkDict = set ? P.chunkDict() : nullptr;          // (null: every chunk uses record 0)
-    // Digested tables - the one dictionary's, any member's of a set - choose the CD forms of the entropy kernels
-    sb.cdt = (set ? set->tables : (dict && dict->dTables)) ? dTable : nullptr;
-    sb.rep = dict ? make_uint4(dict->rep[0], dict->rep[1], dict->rep[2], 0u) : make_uint4(1u, 4u, 8u, 0u);
-    sb.dictID = dict ? dict->dictID : 0u;
+    sb.dTable = sel.dTable; sb.dChunkDict = sel.dictIndex ? P.chunkDict() : nullptr; sb.cdt = sel.tables;
     for (uint32_t chunk0 = 0, chunk1; chunk0 < n; chunk0 = chunk1) {
         const CompressPlan::Cut sub = P.cut(chunk0, cap);
         chunk1 = sub.chunk1;
@@ -516,8 +516,7 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
         sb.dUnitDict = P.unitDict(chunk0);
         launchSubBatch(c, shape, sb, dSrc, dDst, dDstSizes, dStats);
     }
-    if (checksum && !c->stopAfterWalk && !c->stopLit && !c->stopSeq)     // (a stopped stage leaves no frames to close)
-        LAUNCH(c, "k_frame_checksum", k_frame_checksum, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, sb.dChunks, n, (uint8_t *)dDst, dDstSizes);
+    closeFrames(c, dSrc, sb.dChunks, n, dDst, dDstSizes, checksum);
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
 extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
@@ -551,7 +550,7 @@ extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const u
     if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
     const LzShape &shape = lzShape(level);
     const uint32_t nbMax = zs_chunk_counts(maxSrcSize).blocks, bigMax = (nbMax + 1) / 2;
-    const uint32_t cap = std::max<uint32_t>((uint32_t)std::min<uint64_t>((uint64_t)n * nbMax, std::max<uint32_t>(64, c->maxBlocksInFlight)), nbMax);
+    const uint32_t cap = subBatchCap(c, (uint64_t)n * nbMax, nbMax);
     const uint32_t K = std::min(n, cap / nbMax), subs = (n + K - 1) / K;
     zsmi_ctx::Scratch &S = c->scratch;
     if (!S.reserve(cap)) return ZSMI_error_memory_allocation;
@@ -567,7 +566,6 @@ extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const u
            dChunks, (ZsPlanBefore *)R.dBefore.p, (ZsPlanCounts *)R.dCounts.p);
     SubBatch sb;
     sb.dChunks = dChunks; sb.dBlocks = lists.blocks; sb.block0 = 0; sb.cap = cap; sb.assemble = nbMax > 1;
-    sb.rep = make_uint4(1u, 4u, 8u, 0u);
     for (uint32_t s = 0; s < subs; s++) {
         const uint32_t chunk0 = s * K, nChunks = std::min(K, n - chunk0);
         // the lists are the sub-batch's alone: every sub-batch writes them again, behind the kernels that read the one before's
@@ -579,31 +577,20 @@ extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const u
         sb.units[kUnitsBig] = { lists.units + lists.bigBase, nbMax > 1 ? nChunks * bigMax : 0u };
         launchSubBatch(c, shape, sb, dSrc, dDst, dDstSizes, nullptr);
     }
-    if (c->checksumFlag && !c->stopAfterWalk && !c->stopLit && !c->stopSeq)
-        LAUNCH(c, "k_frame_checksum", k_frame_checksum, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, (const ZsChunkDesc *)dChunks, n, (uint8_t *)dDst, dDstSizes);
+    closeFrames(c, dSrc, dChunks, n, dDst, dDstSizes, c->checksumFlag);
     // last: a chunk above maxSrcSize was planned as an empty one, and its size word says so only now
     LAUNCH(c, "k_plan_refuse", k_plan_refuse, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, maxSrcSize, 0u - (uint32_t)ZSMI_error_srcSize_wrong, dDstSizes);
     return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
 // dDict: device memory.  The dictionary loader runs over it and its record (a formatted dictionary's ID, recent offsets and content
-// offset, or the refusal) is read back: the call waits for the context's stream once.
-static int compressBatchDeviceUsingDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                        uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                        const void *dDict, size_t dictSize, int checksum)
-{
-    if (!dDict || dictSize == 0) return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, checksum);
-    if (!c) return ZSMI_error_init_missing;
-    if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    ZsCompressDict d;
-    if (const int e = loadDict(c, dDict, dictSize, d)) return e;
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &d, checksum);
-}
+// offset, or the refusal) is read back: the call waits for the context's stream once.  (Its tables are queued before the plan: a new layout's wait in build covers them)
 extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                   uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
                                                   const void *dDict, size_t dictSize)
 {
-    return compressBatchDeviceUsingDict(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, dDict, dictSize, c ? c->checksumFlag : 0);
+    ZsCDictSel sel;
+    if (const int e = dictFromBytes(c, dDict, dictSize, kDictOnDevice, level, n, sel)) return e;
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &sel, c ? c->checksumFlag : 0);
 }
 
 // ---- digested dictionaries (ZSTD_createCDict / ZSTD_compress_usingCDict): loaded once, everything a call needs kept in device memory - the
@@ -612,7 +599,7 @@ extern "C" int zsmi_compressBatchDevice_usingDict(zsmi_ctx *c, const void *dSrc,
 struct zsmi_cdict {
     int device = 0, level = 3;
     bool empty = false;                  // no bytes: its calls are the plain calls at its level
-    ZsCompressDict d;                    // (dBytes, dImg, dTables, dEntry: into the buffers below)
+    ZsCompressDict d;                    // (dBytes, dTables: into the buffers below)
     DevBuf dBytes, dImg, dTables, dEntry;
 };
 extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t dictSize, int level, int *err)
@@ -631,13 +618,11 @@ extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t di
         if ((code = loadDict(c, cd->dBytes.p, dictSize, cd->d))) break;
         const bool formatted = cd->d.contentOff != 0;
         if (formatted && !cd->dTables.reserve(sizeof(ZsCDictTables))) { code = ZSMI_error_memory_allocation; break; }
-        cd->d.dImg = (const uint32_t *)cd->dImg.p;
         if (formatted) {
             LAUNCH(c, "k_cdict_tables", k_cdict_tables, dim3(1), dim3(256), 0, &((const ZsDictRecord *)c->dDictRec.p)->ent, (ZsCDictTables *)cd->dTables.p);
             cd->d.dTables = (const ZsCDictTables *)cd->dTables.p;
         }
         launchDictTables(c, cd->d, level, cd->dImg.p, cd->dEntry.p);         // (and the one-entry table its calls pass)
-        cd->d.dEntry = (const ZsCDictEntry *)cd->dEntry.p;
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
     } while (0);
     if (code) { delete cd; cd = nullptr; }
@@ -647,11 +632,12 @@ extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t di
 extern "C" void zsmi_freeCDict(zsmi_cdict *cd) { delete cd; }
 extern "C" unsigned zsmi_getDictID_fromCDict(const zsmi_cdict *cd) { return cd ? cd->d.dictID : 0; }
 extern "C" size_t zsmi_sizeofCDict(const zsmi_cdict *cd) { return cd ? cd->dBytes.cap + cd->dImg.cap + cd->dTables.cap + cd->dEntry.cap : 0; }
-// What a zsmi_cdict * argument asks of a call on context c - 0, with level and dict set: compress at `level`, plainly (dict nullptr: a null
-// cdict at level 3, one without bytes at its own) or with the descriptor; or the error (a dictionary digested on another device: parameter_unsupported)
-static int resolveCDict(const zsmi_ctx *c, const zsmi_cdict *cd, int &level, const ZsCompressDict *&dict)
+// What a zsmi_cdict * argument asks of a call on context c - 0, with level and sel set: compress at `level`, plainly (no table: a null cdict at
+// level 3, one without bytes at its own) or with the dictionary's one-entry table; or the error (digested on another device: parameter_unsupported)
+static int resolveCDict(const zsmi_ctx *c, const zsmi_cdict *cd, int &level, ZsCDictSel &sel)
 {
-    level = cd ? cd->level : 3; dict = cd && !cd->empty ? &cd->d : nullptr;
+    level = cd ? cd->level : 3; sel = ZsCDictSel();
+    if (cd && !cd->empty) { sel.dTable = (const ZsCDictEntry *)cd->dEntry.p; sel.tables = cd->d.dTables != nullptr; }
     if (!cd) return 0;
     if (!c) return ZSMI_error_init_missing;
     return cd->device == c->device ? 0 : ZSMI_error_parameter_unsupported;
@@ -660,9 +646,9 @@ static int resolveCDict(const zsmi_ctx *c, const zsmi_cdict *cd, int &level, con
 extern "C" int zsmi_compressBatchDevice_usingCDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, const zsmi_cdict *cd)
 {
-    int level; const ZsCompressDict *dict;
-    if (const int e = resolveCDict(c, cd, level, dict)) return e;
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, dict, c ? c->checksumFlag : 0);
+    int level; ZsCDictSel sel;
+    if (const int e = resolveCDict(c, cd, level, sel)) return e;
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &sel, c ? c->checksumFlag : 0);
 }
 
 // ---- CDict sets: a read-only device table with one record (ZsCDictEntry) per member, in the caller's order; a call with a set gives chunk i
@@ -692,7 +678,7 @@ extern "C" zsmi_cdictSet *zsmi_createCDictSet(zsmi_ctx *c, const zsmi_cdict *con
             // a member: there, of this device, digested for this level (its images are built for one LZ shape)
             if (!cd || cd->device != c->device || cd->level != level) { code = ZSMI_error_parameter_unsupported; break; }
             hasDict[i] = !cd->empty;
-            table[i] = cd->empty ? ZsCDictEntry() : dictEntry(cd->d, cd->d.dImg);
+            table[i] = cd->empty ? ZsCDictEntry() : dictEntry(cd->d, (const uint32_t *)cd->dImg.p);
             tables |= !cd->empty && cd->d.dTables != nullptr;
         }
         if (code) break;
@@ -711,19 +697,22 @@ extern "C" zsmi_cdictSet *zsmi_createCDictSet(zsmi_ctx *c, const zsmi_cdict *con
 }
 extern "C" void zsmi_freeCDictSet(zsmi_cdictSet *set) { delete set; }
 extern "C" uint32_t zsmi_sizeofCDictSetMembers(const zsmi_cdictSet *set) { return set ? set->members : 0; }
-// resolveCDict's sibling: what a zsmi_cdictSet * argument and the call's choice ask of a call on context c - 0, with level and `sel` set
-// (use: false for a null set, the plain call at level 3); or the error, before anything is queued or written
-struct CDictSetCall { bool use; ZsCompressDictSet sel; };
-static int resolveCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dictIndex, uint32_t n, int &level, CDictSetCall &call)
+// resolveCDict's sibling: what a zsmi_cdictSet * argument and the call's choice ask of a call on context c - 0, with level and sel set
+// (without a table for a null set, the plain call at level 3); or the error, before anything is queued or written
+static int resolveCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dictIndex, uint32_t n, int &level, ZsCDictSel &sel)
 {
-    level = set ? set->level : 3; call.use = false;
+    level = set ? set->level : 3; sel = ZsCDictSel();
     if (!c) return ZSMI_error_init_missing;
     if (!set) return 0;
     if (n && !dictIndex) return ZSMI_error_GENERIC;
-    for (uint32_t i = 0; i < n; i++) if (dictIndex[i] != ZS_DICT_NONE && dictIndex[i] >= set->members) return ZSMI_error_parameter_outOfBound;
+    bool any = false;                                                // (a choice that gives no chunk a dictionary: the plain call)
+    for (uint32_t i = 0; i < n; i++) if (dictIndex[i] != ZS_DICT_NONE) {
+        if (dictIndex[i] >= set->members) return ZSMI_error_parameter_outOfBound;
+        any |= set->hasDict[dictIndex[i]] != 0;
+    }
     if (set->device != c->device) return ZSMI_error_parameter_unsupported;
-    call.use = true;
-    call.sel.dTable = (const ZsCDictEntry *)set->dTable.p; call.sel.memberHasDict = set->hasDict.data(); call.sel.tables = set->tables; call.sel.dictIndex = dictIndex;
+    if (!any) return 0;
+    sel.dTable = (const ZsCDictEntry *)set->dTable.p; sel.dictIndex = dictIndex; sel.memberHasDict = set->hasDict.data(); sel.tables = set->tables;
     return 0;
 }
 // queues the work and returns, as the _usingCDict call: the choice goes up with the plan's dictionary list, through pinned buffers taken in turn
@@ -731,9 +720,9 @@ extern "C" int zsmi_compressBatchDevice_usingCDictSet(zsmi_ctx *c, const void *d
                                                       uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes,
                                                       const zsmi_cdictSet *set, const uint32_t *dictIndex)
 {
-    int level; CDictSetCall call;
-    if (const int e = resolveCDictSet(c, set, dictIndex, n, level, call)) return e;
-    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, nullptr, c->checksumFlag, nullptr, call.use ? &call.sel : nullptr);
+    int level; ZsCDictSel sel;
+    if (const int e = resolveCDictSet(c, set, dictIndex, n, level, sel)) return e;
+    return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &sel, c->checksumFlag);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -849,20 +838,16 @@ static DecodeShape decodeShape(const DecodePlan &p, uint32_t cnt, uint32_t cus)
     return s;
 }
 
-// the item list travels through one of two pinned buffers: a call waits only for the copy that last read the buffer it is about to fill
-// (two calls back), not for the device to finish the call before it (round 3 began every call with hipStreamSynchronize)
+// the item list travels through pinned buffers taken in turn (TurnBufs): a call waits only for the copy that last read the buffer it is
+// about to fill (two calls back), not for the device to finish the call before it
 static int uploadDecodeItems(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, const uint32_t *dstCaps)
 {
-    const int hb = (int)(c->decodeCalls++ & 1u);
-    PinBuf &hItems = c->hItems2[hb];
-    if (c->hItemsBusy[hb]) { if (hipEventSynchronize(c->hItemsEv[hb]) != hipSuccess) return ZSMI_error_GENERIC; c->hItemsBusy[hb] = false; }
-    if (!hItems.reserve(sizeof(ZsDecItem) * n) || !c->dItems.reserve(sizeof(ZsDecItem) * n)) return ZSMI_error_memory_allocation;
-    ZsDecItem *hi = (ZsDecItem *)hItems.p;
+    ZsDecItem *hi;
+    if (const int e = c->hItems.take(sizeof(ZsDecItem) * n, hi)) return e;
+    if (!c->dItems.reserve(sizeof(ZsDecItem) * n)) return ZSMI_error_memory_allocation;
     for (uint32_t i = 0; i < n; i++) { hi[i].srcOff = srcOffsets[i]; hi[i].dstOff = dstOffsets[i]; hi[i].srcSize = srcSizes[i]; hi[i].dstCap = dstCaps[i]; }
     if (hipMemcpyAsync(c->dItems.p, hi, sizeof(ZsDecItem) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipEventRecord(c->hItemsEv[hb], c->stream) != hipSuccess) { (void)hipStreamSynchronize(c->stream); return ZSMI_error_GENERIC; }   // (the buffer is idle after that)
-    c->hItemsBusy[hb] = true;
-    return 0;
+    return c->hItems.sent(c->stream);
 }
 
 // The fast path's launches for a sub-batch of cnt items (dI) in the context's scratch: k_dec_prep, the entropy stage, k_dec_execute,
@@ -1252,22 +1237,17 @@ static int staged(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, cons
     if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     return copyBack(c, (const uint8_t *)c->sDst.p, dof.data(), (uint8_t *)dst, dstOffsets, dstSizes, n);
 }
-// the destination slots a compress call is staged with: every chunk's bound
-static std::vector<uint32_t> compressBounds(const uint32_t *srcSizes, uint32_t n)
-{
-    std::vector<uint32_t> bounds(n);
-    for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
-    return bounds;
-}
-// dict: the call's dictionary (a digested one's descriptor), or nullptr; checksum: as compressBatchDeviceImpl's
+// dict: the call's selector, of dictionaries that are on the device already; checksum: as compressBatchDeviceImpl's
 static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, void *dst, const uint64_t *dstOffsets,
-                                 uint32_t *dstSizes, int level, const ZsCompressDict *dict, int checksum, const ZsCompressDictSet *set = nullptr)
+                                 uint32_t *dstSizes, int level, const ZsCDictSel *dict, int checksum)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
-    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, compressBounds(srcSizes, n).data(), dstSizes, nullptr, 0,
+    std::vector<uint32_t> bounds(n);                                 // the destination slots the call is staged with: every chunk's bound
+    for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes, nullptr, 0,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict, checksum, nullptr, set);
+                      return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict, checksum);
                   });
 }
 extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
@@ -1275,40 +1255,30 @@ extern "C" int zsmi_compressBatchHost(zsmi_ctx *c, const void *src, const uint64
 {
     return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, c ? c->checksumFlag : 0);
 }
-// the dictionary is staged with the sources, and the run step is the device form on the staged bytes (which loads and checks them: its one
-// wait, then the staged call's own for the results)
-static int compressBatchHostUsingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                      uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
-                                      const void *dict, size_t dictSize, int checksum)
-{
-    if (!dict || dictSize == 0) return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, checksum);
-    if (!c) return ZSMI_error_init_missing;
-    if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, compressBounds(srcSizes, n).data(), dstSizes, dict, dictSize,
-                  [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      return compressBatchDeviceUsingDict(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, c->sDict.p, dictSize, checksum);
-                  });
-}
+// The dictionary is staged and loaded first (dictFromBytes: its copy, the loader, the one wait - a refusal comes before anything of the
+// sources is allocated or copied), then the sources are staged and the call runs as the _usingCDict form's does
 extern "C" int zsmi_compressBatchHost_usingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                 uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, int level,
                                                 const void *dict, size_t dictSize)
 {
-    return compressBatchHostUsingDict(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict, dictSize, c ? c->checksumFlag : 0);
+    ZsCDictSel sel;
+    if (const int e = dictFromBytes(c, dict, dictSize, kDictOnHost, level, n, sel)) return e;
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, &sel, c ? c->checksumFlag : 0);
 }
 extern "C" int zsmi_compressBatchHost_usingCDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                  uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes, const zsmi_cdict *cd)
 {
-    int level; const ZsCompressDict *dict;
-    if (const int e = resolveCDict(c, cd, level, dict)) return e;
-    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, dict, c ? c->checksumFlag : 0);
+    int level; ZsCDictSel sel;
+    if (const int e = resolveCDict(c, cd, level, sel)) return e;
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, &sel, c ? c->checksumFlag : 0);
 }
 extern "C" int zsmi_compressBatchHost_usingCDictSet(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                     uint32_t n, void *dst, const uint64_t *dstOffsets, uint32_t *dstSizes,
                                                     const zsmi_cdictSet *set, const uint32_t *dictIndex)
 {
-    int level; CDictSetCall call;
-    if (const int e = resolveCDictSet(c, set, dictIndex, n, level, call)) return e;
-    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, nullptr, c->checksumFlag, call.use ? &call.sel : nullptr);
+    int level; ZsCDictSel sel;
+    if (const int e = resolveCDictSet(c, set, dictIndex, n, level, sel)) return e;
+    return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, &sel, c->checksumFlag);
 }
 // dict / dictSize: the call's dictionary in host memory, which this call stages; or digested: the selector of digested ones (a DDict's or a
 // set's), whose bytes are on the device already
@@ -1412,10 +1382,10 @@ extern "C" size_t zsmi_decodeScratchBytes(zsmi_ctx *c)
     return c->dec.held();
 }
 
-// one frame through a borrowed context: with the digested dictionary cd, or at `level` with the dictionary's bytes (or with none).
-// checksum: the call's own - the borrowed context's sticky state is neither read nor changed
-static size_t compressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level, const void *dict, size_t dictSize, const zsmi_cdict *cd,
-                              int checksum = 0)
+// one frame through a borrowed context.  resolve(c, level, sel): the call's dictionary, resolved on that context as the batch forms resolve
+// theirs.  checksum: the call's own - the borrowed context's sticky state is neither read nor changed
+template <class Resolve>
+static size_t compressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level, int checksum, Resolve resolve)
 {
     if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
     Borrowed b; zsmi_ctx *c = b.c;
@@ -1425,37 +1395,45 @@ static size_t compressOneShot(void *dst, size_t dstCapacity, const void *src, si
     uint8_t *out = (uint8_t *)dst;
     if (dstCapacity < bound) { tmp.resize(bound); out = tmp.data(); }     // compress into a bound-sized buffer, then check the fit
     const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
-    const ZsCompressDict *digested = nullptr;
-    int rc = cd ? resolveCDict(c, cd, level, digested) : 0;
-    if (!rc) rc = cd ? compressBatchHostImpl(c, src, &so, &ss, 1, out, &dof, &ds, level, digested, checksum)
-                     : compressBatchHostUsingDict(c, src, &so, &ss, 1, out, &dof, &ds, level, dict, dictSize, checksum);
+    ZsCDictSel sel;
+    int rc = resolve(c, level, sel);
+    if (!rc) rc = compressBatchHostImpl(c, src, &so, &ss, 1, out, &dof, &ds, level, &sel, checksum);
     if (rc) return ZSMI_ERR(rc);
     if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
     if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
     if (out != dst) memcpy(dst, out, ds);
     return ds;
 }
+// at `level` with the dictionary's bytes (or with none)
+static size_t compressOneShotUsingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level, int checksum)
+{
+    return compressOneShot(dst, dstCapacity, src, srcSize, level, checksum, [&](zsmi_ctx *c, int &lv, ZsCDictSel &sel) { return dictFromBytes(c, dict, dictSize, kDictOnHost, lv, 1, sel); });
+}
+// with the digested dictionary cd; a null cd: the plain call at level 3.  (The borrowed context is the current device's: a dictionary of another is parameter_unsupported)
+static size_t compressOneShotUsingCDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd, int checksum)
+{
+    return compressOneShot(dst, dstCapacity, src, srcSize, 3, checksum, [&](zsmi_ctx *c, int &lv, ZsCDictSel &sel) { return resolveCDict(c, cd, lv, sel); });
+}
 extern "C" size_t zsmi_compress(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level)
 {
-    return compressOneShot(dst, dstCapacity, src, srcSize, level, nullptr, 0, nullptr);
+    return compressOneShotUsingDict(dst, dstCapacity, src, srcSize, nullptr, 0, level, 0);
 }
 extern "C" size_t zsmi_compress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level)
 {
-    return compressOneShot(dst, dstCapacity, src, srcSize, level, dict, dictSize, nullptr);
+    return compressOneShotUsingDict(dst, dstCapacity, src, srcSize, dict, dictSize, level, 0);
 }
-// a null cd: the plain call at level 3.  (The borrowed context is one of the current device: a dictionary digested on another device is parameter_unsupported)
 extern "C" size_t zsmi_compress_usingCDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd)
 {
-    return compressOneShot(dst, dstCapacity, src, srcSize, 3, nullptr, 0, cd);
+    return compressOneShotUsingCDict(dst, dstCapacity, src, srcSize, cd, 0);
 }
 // the one-shot forms with a checksumFlag (0: the frames of the calls above, byte for byte; any other value: 1)
 extern "C" size_t zsmi_compress_advanced(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level, int checksumFlag)
 {
-    return compressOneShot(dst, dstCapacity, src, srcSize, level, dict, dictSize, nullptr, checksumFlag != 0);
+    return compressOneShotUsingDict(dst, dstCapacity, src, srcSize, dict, dictSize, level, checksumFlag != 0);
 }
 extern "C" size_t zsmi_compress_usingCDict_advanced(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_cdict *cd, int checksumFlag)
 {
-    return compressOneShot(dst, dstCapacity, src, srcSize, 3, nullptr, 0, cd, checksumFlag != 0);
+    return compressOneShotUsingCDict(dst, dstCapacity, src, srcSize, cd, checksumFlag != 0);
 }
 extern "C" size_t zsmi_decompress(void *dst, size_t dstCapacity, const void *src, size_t srcSize)
 {

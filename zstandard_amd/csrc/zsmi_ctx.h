@@ -1,5 +1,6 @@
-// Host side that zsmi_api.hip and the feature files (seekable.hip, dict_train.hip) share: the context with its buffers, the timed launch,
-// and the batch entry points the features are built on (defined in zsmi_api.hip).
+// Host side that zsmi_api.hip and the feature files (seekable.hip, dict_train.hip) share: the context with its buffers (Buf; TurnBufs, the
+// pinned buffers a per-call list goes up through), the timed launch, and the batch entry points the features are built on (defined in
+// zsmi_api.hip) with the one thing they take about dictionaries - the compress calls a ZsCDictSel, the decompress calls a ZsDictSel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/zsmi.h"
@@ -35,6 +36,27 @@ struct Buf {
 };
 typedef Buf<devAlloc, hipFree> DevBuf;
 typedef Buf<pinAlloc, hipHostFree> PinBuf;
+// Two pinned buffers taken in turn, each behind an event (made with the context: create): a list that goes up with every call travels through
+// them, and a call waits only for the copy that last read the buffer it is about to fill (two calls back), never for the stream.  take: the next buffer, idle, of
+// >= n bytes, in p.  sent: the copy that reads it is queued on the stream; a record that fails is the call's error and leaves it known idle - the stream is waited for
+struct TurnBufs {
+    PinBuf buf[2]; hipEvent_t ev[2] = { nullptr, nullptr }; bool busy[2] = { false, false }; uint32_t turns = 0;
+    ~TurnBufs() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    bool create() { return hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) == hipSuccess; }
+    template <class T> int take(size_t n, T *&p)
+    {
+        const int t = (int)(turns++ & 1u);
+        if (busy[t]) { if (hipEventSynchronize(ev[t]) != hipSuccess) return ZSMI_error_GENERIC; busy[t] = false; }
+        if (!buf[t].reserve(n)) return ZSMI_error_memory_allocation;
+        p = (T *)buf[t].p; return 0;
+    }
+    int sent(hipStream_t stream)
+    {
+        const int t = (int)((turns - 1u) & 1u);
+        if (hipEventRecord(ev[t], stream) != hipSuccess) { (void)hipStreamSynchronize(stream); return ZSMI_error_GENERIC; }
+        busy[t] = true; return 0;
+    }
+};
 
 struct TimedLaunch { const char *name; hipEvent_t a, b; };
 struct DecodePlan;
@@ -55,19 +77,19 @@ struct CompressPlan {
     struct Run { std::vector<uint32_t> before; uint32_t base = 0; } small, big, whole, tail;
     // Which dictionary list the plan holds: kDictNone; kDictAll, one dictionary for every chunk; kDictPerChunk, the choice dictKey states
     // (a chunk's record, ZS_DICT_NONE for none).  The list depends on the choice: the same layout with another choice builds it again, through
-    // two pinned buffers taken in turn behind events, as the decoder's item list - no wait for the stream
+    // pinned buffers taken in turn (hDictList) - no wait for the stream
     enum { kDictNone, kDictAll, kDictPerChunk };
     int dictKind = kDictNone;
     std::vector<uint32_t> dictKey;
-    PinBuf hDictList[2]; hipEvent_t hDictEv[2] = { nullptr, nullptr }; bool hDictBusy[2] = { false, false }; uint32_t dictBuilds = 0;
+    TurnBufs hDictList;
     size_t chunkDictOff = 0, unitDictOff = 0;      // (bytes into dDictList; kDictPerChunk only)
     const uint32_t *chunkDict() const { return dictKind == kDictPerChunk ? (const uint32_t *)((const uint8_t *)dDictList.p + chunkDictOff) : nullptr; }
     const uint32_t *unitDict(uint32_t chunk0) const { return dictKind == kDictPerChunk ? (const uint32_t *)((const uint8_t *)dDictList.p + unitDictOff) + whole.before[chunk0] : nullptr; }
     struct Units { const ZsUnitDesc *d; uint32_t n; };
     struct Cut { uint32_t chunk1, nb, block0; };
 
-    // dict: a dictionary call; dictIndex (host, n entries; null: one dictionary for every chunk) and memberHasDict: chunk i uses record
-    // dictIndex[i], and none for ZS_DICT_NONE or a record that memberHasDict says stands for no dictionary
+    // dict: a dictionary call; dictIndex and memberHasDict: the call's selector's (ZsCDictSel below) - chunk i uses record dictIndex[i], and
+    // none for ZS_DICT_NONE or a record that memberHasDict says stands for no dictionary
     int build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict,
               const uint32_t *dictIndex = nullptr, const uint8_t *memberHasDict = nullptr);
     Cut cut(uint32_t chunk0, uint32_t cap) const;                                      // the sub-batch of whole chunks from chunk0: at most cap blocks (one chunk at least)
@@ -93,14 +115,14 @@ struct zsmi_ctx {
     // the resident compress call's plan (zsmi_compressBatchResident; plan_kernels.hip writes it): per chunk of the call its ZsChunkDesc and
     // the unit sums in front of it, per sub-batch the live counts; the block and unit lists of ONE sub-batch, which every sub-batch reuses
     struct ResidentPlan { DevBuf dChunks, dBefore, dCounts, dBlocks, dUnits; } resident;
-    DevBuf dDictImg;                       // a _usingDict call's candidate-table images of the prefix and, behind them, its one-entry table (a digested dictionary holds its own)
+    DevBuf dDictImg;                       // a dictionary given as bytes (dictFromBytes): the candidate-table images of its prefix and, behind them, its one-entry table (a digested dictionary holds its own)
     DevBuf dDictRec; PinBuf hDictRec;      // the dictionary loader's record (ZsDictRecord: k_dict_load writes it, loadDict in zsmi_api.hip reads it back)
     int stopAfterWalk = 0;                 // ZSMI_STOP_AFTER_WALK (debug-hooks build, tools/walk_check.py): the entropy kernels are not launched
     int stopLit = 0, stopSeq = 0;          // timing aids of a -DZSMI_DEBUG_HOOKS build (ZSMI_STOP_LIT / ZSMI_STOP_SEQ): end a kernel after a stage; always 0 in the product
-    // decompress workspace: the item list (on the host: two pinned buffers taken in turn) and the scratch of a sub-batch, whose sizes for a
+    // decompress workspace: the item list (on the host: pinned buffers taken in turn) and the scratch of a sub-batch, whose sizes for a
     // call's plan are stated once, in the decompress section (DecodeScratch::each)
     DevBuf dItems;
-    PinBuf hItems2[2]; hipEvent_t hItemsEv[2] = { nullptr, nullptr }; bool hItemsBusy[2] = { false, false }; uint32_t decodeCalls = 0;
+    TurnBufs hItems;
     struct DecodeScratch {
         DevBuf dPoolLit;                                                 // the general kernel's literal buffers: one per wavefront of its pool
         DevBuf dLitScratch, dFastDesc, dHufTabs, dSeqTabs, dSeqOut;      // the fast path's block slots: literals, descriptors, tables, sequences
@@ -128,8 +150,8 @@ struct zsmi_ctx {
     PinBuf hPack;
     // seekable archives (seekable.hip): compressed frames at bound spacing before they are packed, per-frame words (sizes, hashes, offsets, the
     // error word; a read's status words, codes and lists), the decoded bytes of the frames a read does not decode in place, and a read's lists
-    // on the host: two pinned buffers taken in turn, each guarded by an event (created with the context), as hItems2
-    struct SeekScratch { DevBuf dStage, dMeta, dDec; PinBuf hLists[2]; hipEvent_t hEv[2] = { nullptr, nullptr }; bool hBusy[2] = { false, false }; uint32_t calls = 0; } seek;
+    // on the host: pinned buffers taken in turn, as hItems
+    struct SeekScratch { DevBuf dStage, dMeta, dDec; TurnBufs hLists; } seek;
     // dictionary training (dict_train.hip): the samples back to back, sort keys, per-position hash / links (d = 6, 8), base and per-candidate
     // frequency tables, candidate contents and list, compressed sizes and frames of the scoring / statistics calls, stats + header scratch, the result
     struct TrainScratch {
@@ -158,28 +180,32 @@ static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz
 #define LAUNCH(ctx, name, kernel, grid, block, lds, ...) LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, lds, __VA_ARGS__)
 
 // ---- the batch calls in device memory (zsmi_api.hip: the compress and the decompress section state their arguments) ----
-// A dictionary as the compress launch sequence takes it (nullptr: none).  dBytes: its bytes in device memory; contentOff .. rep: what the
-// device's dictionary loader found in them (loadDict in zsmi_api.hip copies its record: the host parses no dictionary; raw content: all of
-// it, no ID, offsets {1, 4, 8}).  dImg, dTables, dEntry: a digested dictionary's (zsmi_cdict) - the
-// prefix's candidate-table images, built once and not by the call, a formatted one's entropy tables in encoder form, and its one-entry
-// table (ZsCDictEntry, zsmi_device.h: what the kernels read).
+// A dictionary as its loader leaves it (the launch sequence sees none of this: a record says it all).  dBytes: its bytes in device memory;
+// contentOff .. rep: what the device's dictionary loader found in them (loadDict in zsmi_api.hip copies its record: the host parses no
+// dictionary; raw content: all of it, no ID, offsets {1, 4, 8}); dTables: a digested, formatted dictionary's entropy tables in encoder form
 struct ZsCDictTables;
 struct ZsCompressDict {
     const uint8_t *dBytes = nullptr;
     uint32_t contentOff = 0, contentSize = 0, dictID = 0, rep[3] = { 1, 4, 8 };
-    const uint32_t *dImg = nullptr; const ZsCDictTables *dTables = nullptr; const ZsCDictEntry *dEntry = nullptr;
+    const ZsCDictTables *dTables = nullptr;
 };
-// The dictionaries of a set call (zsmi_cdictSet): the device table, which of its records stand for a dictionary (an empty member's does
-// not), whether any has entropy tables, and the call's choice - chunk i uses record dictIndex[i] (host), ZS_DICT_NONE: none.
-struct ZsCompressDictSet {
-    const ZsCDictEntry *dTable; const uint8_t *memberHasDict; bool tables;
-    const uint32_t *dictIndex;
+// Which dictionary each chunk of a compress call gets: what every form of the call resolves to, and all the launch sequence knows of
+// dictionaries (the decoder's ZsDictSel, for the encoder).  nullptr, or a selector without a table: the plain call.
+struct ZsCDictSel {
+    const ZsCDictEntry *dTable = nullptr;      // the records, in device memory: a digested dictionary's one-entry table, a set's, or the one dictFromBytes builds
+    const uint32_t *dictIndex = nullptr;       // the call's choice (host, n entries): chunk i uses record dictIndex[i], ZS_DICT_NONE: none.  Null: every chunk uses record 0
+    const uint8_t *memberHasDict = nullptr;    // which records stand for a dictionary (a set's empty member's does not).  Null: every one
+    bool tables = false;                       // some record has entropy tables: the CD forms of the entropy kernels
 };
+// a dictionary given as bytes (none: the plain call) - content alone in device memory (the trainer), or a dictionary the loader reads, the call waiting for its
+// record once (the _usingDict calls: in device memory, or in host memory and staged first) -> the selector of its one-entry table, built on the stream in c->dDictImg
+enum DictBytes { kDictContent, kDictOnDevice, kDictOnHost };
+static int dictFromBytes(zsmi_ctx *c, const void *dict, size_t dictSize, DictBytes kind, int level, uint32_t n, ZsCDictSel &sel);
 // checksum: the frames carry a Content_Checksum (k_frame_checksum).  An argument, not the context's flag: the public calls pass c->checksumFlag,
 // the one-shot _advanced calls their own, the dictionary trainer 0 - what it trains must not depend on the context's state
 static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                    uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level,
-                                   const ZsCompressDict *dict, int checksum, uint32_t *dStats = nullptr, const ZsCompressDictSet *set = nullptr);
+                                   const ZsCDictSel *dict, int checksum, uint32_t *dStats = nullptr);
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                      const struct ZsDictSel *dict);
