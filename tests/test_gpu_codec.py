@@ -211,6 +211,54 @@ def test_encode_128k_chunks_and_ragged(codec):
         assert f == O.compress(c, 3)
 
 
+_GROWING = {}
+
+
+def _growing_reference():
+    """the three calls of test_growing_layouts_back_to_back - 16, 600 and 5000 chunks of 512 bytes, one behind the other in one source - and
+    every chunk's frame by the oracle, computed once"""
+    if not _GROWING:
+        cs, counts = 512, (16, 600, 5000)
+        total = sum(counts)
+        data = D.zipf_log(total * cs, seed_lo=0x6A0)
+        offs = np.arange(total, dtype=np.uint64) * cs
+        sizes = np.full(total, cs, dtype=np.uint32)
+        ea, eo, es = O.compress_batch(data, offs, sizes, 3, 8)
+        first = dict(zip(counts, (0, 16, 616)))
+        _GROWING.update(cs=cs, total=total, data=data, offs=offs, sizes=sizes, first=first, want=B.cut(ea, eo, es))
+    return _GROWING
+
+
+@pytest.mark.parametrize("order", [(16, 600, 5000), (5000, 16, 600)])
+def test_growing_layouts_back_to_back(order):
+    """three compress_device calls on one codec with no sync between them, each with another layout - so each builds its plan in the pinned
+    buffers the call before copied from, and in the first order regrows them each time - into three disjoint destination regions; then one
+    sync: every frame of all three equals the oracle's, byte for byte"""
+    from zstandard_amd import BatchCodec
+    from _hip import hip_of, Dev, PAD
+    R = _growing_reference()
+    cs, total, first = R["cs"], R["total"], R["first"]
+    H = hip_of()
+    bc = BatchCodec()                       # (its own: the plan buffers start empty, whatever ran before)
+    bound = int(bc.L.zsmi_compressBound(cs))
+    src, dst, dsz = Dev(H, total * cs, R["data"].tobytes()), Dev(H, total * bound), Dev(H, 4 * total)
+    try:
+        for n in order:
+            i0 = first[n]
+            do = (np.arange(n, dtype=np.uint64) + np.uint64(i0)) * np.uint64(bound)
+            bc.compress_device(src.p, R["offs"][i0:i0 + n], R["sizes"][i0:i0 + n], dst.p, do, dsz.p + 4 * i0, 3)
+        bc.sync()
+        host = dst.all()[PAD:PAD + total * bound]
+        sz = np.frombuffer(dsz.all()[PAD:PAD + 4 * total], dtype=np.uint32)
+    finally:
+        for b in (src, dst, dsz):
+            b.free()
+        bc.close()
+    assert (sz < ERR).all()
+    bad = [i for i in range(total) if host[i * bound:i * bound + int(sz[i])] != R["want"][i]]
+    assert not bad, (order, len(bad), bad[:5])
+
+
 def test_many_tiny_and_odd_chunks(codec):
     """ragged batch: 3000 chunks of 0..3000 bytes, plus sizes around the block / frame-header boundaries"""
     data = D.zipf_log(6 << 20, seed_lo=99)

@@ -29,7 +29,10 @@ import ctypes
 import numpy as np
 from . import _lib
 
-ERROR_MAX = 0xFFFFFF88          # ZStdErrors.cs:95-98 : IsError(c) = c > (uint)-120
+ERROR_MAX_CODE = 120            # ZSMI_error_maxCode (include/zsmi.h)
+ERROR_MAX = (1 << 32) - ERROR_MAX_CODE      # ZStdErrors.cs:95-98 : IsError(c) = c > (uint)-120; csrc/zsmi_status.h states it for the library
+ERROR_PARAMETER_UNSUPPORTED = 40            # ZSMI_error_parameter_unsupported
+ERROR_PARAMETER_OUT_OF_BOUND = 42           # ZSMI_error_parameter_outOfBound
 
 
 def _raise_if_error(L, r):
@@ -309,7 +312,7 @@ class ZstdCompressor:
         Any zstd decoder reads it as concatenated frames; SeekableArchive reads ranges of it."""
         L = _lib.lib()
         if self.dictionary or self.cdict:
-            raise RuntimeError(_error_name(L, 40))                     # parameter_unsupported: no dictionaries in seekable archives
+            raise RuntimeError(_error_name(L, ERROR_PARAMETER_UNSUPPORTED))                     # parameter_unsupported: no dictionaries in seekable archives
         s, sn = _buf(src)
         cap = _raise_if_error(L, L.zsmi_seekableBound(sn, frame_size, int(bool(checksum))))
         out = ctypes.create_string_buffer(cap)
@@ -359,7 +362,7 @@ class SeekableArchive:
         n = len(ranges)
         off = np.array([r[0] for r in ranges], dtype=np.uint64); ln = np.array([r[1] for r in ranges], dtype=np.uint64)
         if n and int(off.max()) > self.content_size:
-            raise RuntimeError(_error_name(self.L, 42))                    # parameter_outOfBound (before the capacity is worked out)
+            raise RuntimeError(_error_name(self.L, ERROR_PARAMETER_OUT_OF_BOUND))                    # parameter_outOfBound (before the capacity is worked out)
         cap = int(sum(min(int(l), self.content_size - int(o)) for o, l in zip(off, ln)))
         out = np.empty(max(cap, 1), dtype=np.uint8)
         written = np.zeros(max(n, 1), dtype=np.uint64); codes = np.zeros(max(n, 1), dtype=np.uint32)

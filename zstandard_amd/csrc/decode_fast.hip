@@ -1109,7 +1109,7 @@ k_dec_checksum(const ZsDecItem *__restrict__ items, uint32_t nItems, const ZsFas
     const bool real = blockIdx.x * 16 + (threadIdx.x >> 2) < nItems;
     const ZsFastDesc *d = zs_slot_desc(descs, item);
     uint32_t size = (real && d->fast && d->hasChecksum) ? dstSizes[item] : 0xFFFFFFFFu;
-    const bool work = size <= 0xFFFFFF88u;
+    const bool work = !zs_word_is_error(size);
     if (!__ballot(work)) return;
     const uint64_t h = xxh64_quad(dstAll + items[item].dstOff, work ? size : 0u);     // (whole quads take part: a quad without work hashes nothing)
     if (work && (threadIdx.x & 3u) == 0 && (uint32_t)h != d->checksum) dstSizes[item] = ZE(E_checksum_wrong);

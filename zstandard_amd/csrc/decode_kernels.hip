@@ -19,6 +19,7 @@
 #ifndef ZSMI_DECODE_KERNELS_HIP         // (decode_fast.hip and seekable.hip include this file too)
 #define ZSMI_DECODE_KERNELS_HIP
 #include "zsmi_device.h"
+#include "zsmi_status.h"          // the size word: zs_error_word, zs_word_is_error; the codes of include/zsmi.h
 #include "zsmi_scratch.h"         // the pool's literal buffers, the general kernel's lists (DecLists)
 #include "zsmi_wave.h"
 #include "zsmi_frame.h"           // the one place a frame, block or literals-section header is read
@@ -36,23 +37,24 @@
 #ifdef ZS_DEC_ERRLINE                     // debugging aid: an error result carries the source line that raised it
 #define ZE(code) (0xFF000000u | (uint32_t)__LINE__)
 #else
-#define ZE(code) (0u - (uint32_t)(code))
+#define ZE(code) ZS_ERROR_WORD(code)
 #endif
-#define E_GENERIC 1
-#define E_prefix_unknown 10
-#define E_frameParameter_unsupported 14
-#define E_frameParameter_windowTooLarge 16
-#define E_corruption_detected 20
-#define E_checksum_wrong 22
-#define E_dictionary_corrupted 30
-#define E_dictionary_wrong 32
-#define E_tableLog_tooLarge 44
-#define E_dstSize_tooSmall 70
-#define E_srcSize_wrong 72
+// the decoder's short names of the codes it raises (include/zsmi.h)
+#define E_GENERIC ZSMI_error_GENERIC
+#define E_prefix_unknown ZSMI_error_prefix_unknown
+#define E_frameParameter_unsupported ZSMI_error_frameParameter_unsupported
+#define E_frameParameter_windowTooLarge ZSMI_error_frameParameter_windowTooLarge
+#define E_corruption_detected ZSMI_error_corruption_detected
+#define E_checksum_wrong ZSMI_error_checksum_wrong
+#define E_dictionary_corrupted ZSMI_error_dictionary_corrupted
+#define E_dictionary_wrong ZSMI_error_dictionary_wrong
+#define E_tableLog_tooLarge ZSMI_error_tableLog_tooLarge
+#define E_dstSize_tooSmall ZSMI_error_dstSize_tooSmall
+#define E_srcSize_wrong ZSMI_error_srcSize_wrong
 #ifdef ZS_DEC_ERRLINE
 __device__ __forceinline__ bool isErr(uint32_t v) { return v >= 0xFF000000u; }
 #else
-__device__ __forceinline__ bool isErr(uint32_t v) { return v > ZE(120); }
+__device__ __forceinline__ bool isErr(uint32_t v) { return zs_word_is_error(v); }
 #endif
 
 struct ZsDecItem { uint64_t srcOff; uint64_t dstOff; uint32_t srcSize; uint32_t dstCap; };

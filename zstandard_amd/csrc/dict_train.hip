@@ -19,6 +19,7 @@
 #include "entropy_kernels.hip"    // k_train_stats and kTrainStatWords; the encoder's routines k_train_tables builds with (K3Lds, huffLengths,
                                   // huffCodesAndWeights, writeHuffHeaderWave, normalizeCountsWave, writeNCount)
 #include "zsmi_fse.h"             // MaxLL, MaxML, MaxOff, LLFSELog, MLFSELog, OffFSELog
+#include "zsmi_status.h"          // the size word of the scoring calls' frames
 #include "zsmi_ctx.h"
 #include <algorithm>
 
@@ -306,11 +307,8 @@ static int trainLaunchSort(zsmi_ctx *c, uint32_t n, uint32_t f)
     size_t tmp = 0;
     if (hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n, 0, 32 + (int)f, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
     if (!c->train.dSortTmp.reserve(tmp)) return ZSMI_error_memory_allocation;
-    TimedLaunch tl{ "radix_sort", nullptr, nullptr };
-    if (c->timing == 1) { tl.a = getEvent(c); tl.b = getEvent(c); (void)hipEventRecord(tl.a, c->stream); }
-    if (hipcub::DeviceRadixSort::SortKeys(c->train.dSortTmp.p, tmp, (const uint64_t *)c->train.dKeys.p, (uint64_t *)c->train.dKeysOut.p, (int)n, 0, 32 + (int)f, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (c->timing == 1) { (void)hipEventRecord(tl.b, c->stream); c->launches.push_back(tl); }
-    return 0;
+    Timed timed(c, "radix_sort");
+    return hipcub::DeviceRadixSort::SortKeys(c->train.dSortTmp.p, tmp, (const uint64_t *)c->train.dKeys.p, (uint64_t *)c->train.dKeysOut.p, (int)n, 0, 32 + (int)f, c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
 }
 
 // content (device, contentSize bytes) + the samples (device, back to back at offs / sizes) -> a formatted dictionary at dOut (device, cap bytes);
@@ -325,15 +323,24 @@ static int finalizeQueue(zsmi_ctx *c, const uint8_t *dSamples, const std::vector
     if (!c->train.dArena.reserve(at + 64) || !c->train.dMisc.reserve(sizeof(uint32_t) * (kTrainStatWords + 8) + 1024) || !c->train.dSizes.reserve(sizeof(uint32_t) * n + 64)) return ZSMI_error_memory_allocation;
     uint32_t *dStats = (uint32_t *)c->train.dMisc.p, *dId = dStats + kTrainStatWords;
     uint8_t *dHdr = (uint8_t *)(dId + 8);
-    if (hipMemsetAsync(dStats, 0, sizeof(uint32_t) * kTrainStatWords, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->fill(dStats, 0, sizeof(uint32_t) * kTrainStatWords)) return e;
     ZsCDictSel dict;
     if (const int e = dictFromBytes(c, dContent, contentSize, kDictContent, level, n, dict)) return e;
     if (const int e = compressBatchDeviceImpl(c, dSamples, offs.data(), sizes.data(), n, c->train.dArena.p, dof.data(), (uint32_t *)c->train.dSizes.p, level, &dict, 0, dStats)) return e;
     LAUNCH(c, "k_train_id", k_train_id, dim3(1), dim3(64), 0, dContent, contentSize, dictID, dId);
     LAUNCH(c, "k_train_tables", k_train_tables, dim3(1), dim3(256), 0, (const uint32_t *)dStats, dContent, contentSize, cap, (const uint32_t *)dId, dHdr, dOut, dResult);
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 
+// what finalizeQueue left: *dResult, the dictionary's size (0: it could not be made), then the dictionary from c->train.dOut -> hostDict
+static int finalizeFetch(zsmi_ctx *c, const uint32_t *dResult, void *hostDict, size_t *dictSize)
+{
+    uint32_t size = 0;
+    if (c->toHost(&size, dResult, sizeof size) || c->wait()) return ZSMI_error_GENERIC;
+    if (!size) return ZSMI_error_dstSize_tooSmall;
+    if (hipMemcpy(hostDict, c->train.dOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_error_GENERIC;
+    *dictSize = size; return 0;
+}
 // samples back to back in device memory (sizes on the host) -> the dictionary in hostDict; the chosen k, d go back into *params
 static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uint32_t> &sizes, void *hostDict, size_t cap, zsmi_fastCoverParams *params, size_t *dictSize)
 {
@@ -343,7 +350,7 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
     TrainPlan t;
     if (const int e = trainParams(params, cap, total, n, t)) return e;
     if (!hostDict) return ZSMI_error_GENERIC;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     const uint32_t cap32 = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu - 4096);
     // training share: the first split of the samples while searching (at least one, and at least 8 bytes), all of them otherwise
     uint32_t nTrain = n;
@@ -360,8 +367,8 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
     for (auto &kd : t.cands) needD[kd.second == 8] = true;
     if (!c->train.dKeys.reserve((size_t)8 * nbDmers) || !c->train.dKeysOut.reserve((size_t)8 * nbDmers) || !c->train.dEnds.reserve(8 * (size_t)nTrain) || !c->train.dFreqBase.reserve(2 * table)) return ZSMI_error_memory_allocation;
     for (int w = 0; w < 2; w++) if (needD[w] && !c->train.dInfo[w].reserve((size_t)8 * nbDmers)) return ZSMI_error_memory_allocation;
-    if (hipMemcpyAsync(c->train.dEnds.p, ends.data(), 8 * (size_t)nTrain, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipMemsetAsync(c->train.dFreqBase.p, 0, 2 * table, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->toDevice(c->train.dEnds.p, ends.data(), 8 * (size_t)nTrain)) return e;
+    if (const int e = c->fill(c->train.dFreqBase.p, 0, 2 * table)) return e;
     for (int w = 0; w < 2; w++) {
         if (!needD[w]) continue;
         uint32_t *freqBase = (uint32_t *)((uint8_t *)c->train.dFreqBase.p + w * table);
@@ -373,9 +380,8 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
     // the candidates, in groups whose frequency tables fit 2 GiB
     const uint32_t nc = (uint32_t)t.cands.size();
     const uint32_t group = (uint32_t)std::max<size_t>(1, std::min<size_t>(nc, ((size_t)2 << 30) / table));
-    if (!c->train.dFreq.reserve(table * group) || !c->train.dContent.reserve((size_t)cap32 * nc) || !c->train.dCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc) ||
-        !c->train.hCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc)) return ZSMI_error_memory_allocation;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;          // (the pinned candidate list may feed an earlier copy)
+    if (!c->train.dFreq.reserve(table * group) || !c->train.dContent.reserve((size_t)cap32 * nc) || !c->train.dCand.reserve(sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc)) return ZSMI_error_memory_allocation;
+    if (const int e = c->idleReserve({ { &c->train.hCand, sizeof(ZsTrainCand) * nc + sizeof(uint32_t) * nc } })) return e;      // (the pinned candidate list may feed an earlier copy)
     ZsTrainCand *hc = (ZsTrainCand *)c->train.hCand.p;
     uint32_t *dTails = (uint32_t *)((ZsTrainCand *)c->train.dCand.p + nc);
     for (uint32_t i = 0; i < nc; i++) {
@@ -383,16 +389,16 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
         hc[i].freq = (uint32_t *)((uint8_t *)c->train.dFreq.p + table * (i % group));
         hc[i].content = (uint8_t *)c->train.dContent.p + (size_t)cap32 * i;
     }
-    if (hipMemcpyAsync(c->train.dCand.p, hc, sizeof(ZsTrainCand) * nc, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->toDevice(c->train.dCand.p, hc, sizeof(ZsTrainCand) * nc)) return e;
     for (uint32_t g0 = 0; g0 < nc; g0 += group) {
         const uint32_t g1 = std::min(nc, g0 + group);
         for (uint32_t i = g0; i < g1; i++)
-            if (hipMemcpyAsync(hc[i].freq, (uint8_t *)c->train.dFreqBase.p + (hc[i].d == 8) * table, table, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+            if (const int e = c->onDevice(hc[i].freq, (uint8_t *)c->train.dFreqBase.p + (hc[i].d == 8) * table, table)) return e;
         LAUNCH(c, "k_train_select", k_train_select, dim3(g1 - g0), dim3(kTrainThreads), 0, (const uint2 *)c->train.dInfo[0].p, (const uint2 *)c->train.dInfo[1].p, dSamples, nbDmers, cap32,
                (const ZsTrainCand *)c->train.dCand.p + g0, dTails + g0);
     }
     uint32_t *hTails = (uint32_t *)(hc + nc);
-    if (hipMemcpyAsync(hTails, dTails, sizeof(uint32_t) * nc, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (c->toHost(hTails, dTails, sizeof(uint32_t) * nc) || c->wait()) return ZSMI_error_GENERIC;
     uint32_t win = 0;
     if (nc > 1) {
         // each candidate as raw content for the held-out samples (the samples behind the training share; all of them if there are none)
@@ -409,11 +415,11 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
             if (const int e = compressBatchDeviceImpl(c, dSamples, so.data(), ss.data(), nt, c->train.dArena.p, dof.data(), dSizes, t.level, &dict, 0)) return e;
         }
         std::vector<uint32_t> hs((size_t)nt * nc);
-        if (hipMemcpyAsync(hs.data(), c->train.dSizes.p, sizeof(uint32_t) * hs.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        if (c->toHost(hs.data(), c->train.dSizes.p, sizeof(uint32_t) * hs.size()) || c->wait()) return ZSMI_error_GENERIC;
         uint64_t bestTotal = ~0ull;
         for (uint32_t i = 0; i < nc; i++) {
             uint64_t sum = 0;
-            for (uint32_t j = 0; j < nt; j++) { const uint32_t v = hs[(size_t)nt * i + j]; if (v > 0xFFFFFF88u) return 0u - v; sum += v; }
+            for (uint32_t j = 0; j < nt; j++) { const uint32_t v = hs[(size_t)nt * i + j]; if (zs_word_is_error(v)) return (int)zs_word_code(v); sum += v; }
             const bool better = sum < bestTotal || (sum == bestTotal && (hc[i].k < hc[win].k || (hc[i].k == hc[win].k && hc[i].d < hc[win].d)));
             if (better) { bestTotal = sum; win = i; }
         }
@@ -424,14 +430,17 @@ static int trainImpl(zsmi_ctx *c, const uint8_t *dSamples, const std::vector<uin
     if (!c->train.dOut.reserve(cap32 + 64)) return ZSMI_error_memory_allocation;
     uint32_t *dResult = dTails + win;                                       // (its tail is read already)
     if (const int e = finalizeQueue(c, dSamples, offs, sizes, hc[win].content + hTails[win], contentSize, cap32, t.level, params->dictID, (uint8_t *)c->train.dOut.p, dResult)) return e;
-    uint32_t size = 0;
-    if (hipMemcpyAsync(&size, dResult, sizeof size, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (!size) return ZSMI_error_dstSize_tooSmall;
-    if (hipMemcpy(hostDict, c->train.dOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_error_GENERIC;
-    *dictSize = size;
-    return 0;
+    return finalizeFetch(c, dResult, hostDict, dictSize);
 }
 
+// trainImpl over the context's samples, into a buffer of its own: nothing reaches the caller's buffer or params unless the call succeeds
+static int trainGuarded(zsmi_ctx *c, const std::vector<uint32_t> &sizes, void *dictBuffer, size_t cap, zsmi_fastCoverParams *params, size_t *dictSize)
+{
+    std::vector<uint8_t> tmp(cap); zsmi_fastCoverParams p = *params;
+    if (const int e = trainImpl(c, (const uint8_t *)c->train.dSamples.p, sizes, tmp.data(), cap, &p, dictSize)) return e;
+    memcpy(dictBuffer, tmp.data(), *dictSize); params->k = p.k; params->d = p.d;
+    return 0;
+}
 // host samples -> the context's device copy
 static int trainStageHost(zsmi_ctx *c, const void *samples, const size_t *samplesSizes, unsigned nb, std::vector<uint32_t> &sizes)
 {
@@ -439,10 +448,10 @@ static int trainStageHost(zsmi_ctx *c, const void *samples, const size_t *sample
     sizes.resize(nb);
     for (unsigned i = 0; i < nb; i++) { if (samplesSizes[i] > 0xFFFFFFFFull) return ZSMI_error_srcSize_wrong; sizes[i] = (uint32_t)samplesSizes[i]; total += samplesSizes[i]; }
     if (total >= (1ull << 32)) return ZSMI_error_srcSize_wrong;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     if (!c->train.dSamples.reserve(total + 64)) return ZSMI_error_memory_allocation;
-    if (hipMemsetAsync((uint8_t *)c->train.dSamples.p + total, 0, 64, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    return hipMemcpyAsync(c->train.dSamples.p, samples, total, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    if (const int e = c->fill((uint8_t *)c->train.dSamples.p + total, 0, 64)) return e;
+    return c->toDevice(c->train.dSamples.p, samples, total);
 }
 
 extern "C" size_t zsmi_trainFromBuffer_fastCover(void *dictBuffer, size_t dictCapacity, const void *samplesBuffer, const size_t *samplesSizes,
@@ -455,12 +464,8 @@ extern "C" size_t zsmi_trainFromBuffer_fastCover(void *dictBuffer, size_t dictCa
     if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
     std::vector<uint32_t> sizes;
     if (const int e = trainStageHost(c, samplesBuffer, samplesSizes, nbSamples, sizes)) return ZSMI_ERR(e);
-    std::vector<uint8_t> tmp(dictCapacity);                                  // nothing reaches the caller's buffer unless the call succeeds
-    zsmi_fastCoverParams p = *params;
     size_t size = 0;
-    if (const int e = trainImpl(c, (const uint8_t *)c->train.dSamples.p, sizes, tmp.data(), dictCapacity, &p, &size)) return ZSMI_ERR(e);
-    memcpy(dictBuffer, tmp.data(), size);
-    params->k = p.k; params->d = p.d;
+    if (const int e = trainGuarded(c, sizes, dictBuffer, dictCapacity, params, &size)) return ZSMI_ERR(e);
     return size;
 }
 
@@ -480,29 +485,22 @@ extern "C" int zsmi_trainFromDevice(zsmi_ctx *c, const void *dSamples, const uin
     for (uint32_t i = 0; i < nbSamples; i++) total += sampleSizes[i];
     { TrainPlan t; if (const int e = trainParams(params, dictCapacity, total, nbSamples, t)) return e; }
     if (!dictSize || !dSamples) return ZSMI_error_GENERIC;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     // the samples back to back in the context's buffer (one gather launch)
-    if (!c->train.dSamples.reserve(total + 64) || !c->train.dGather.reserve(sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples) ||
-        !c->train.hCand.reserve(sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples)) return ZSMI_error_memory_allocation;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    const size_t gatherBytes = sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples;
+    if (!c->train.dSamples.reserve(total + 64) || !c->train.dGather.reserve(gatherBytes)) return ZSMI_error_memory_allocation;
+    if (const int e = c->idleReserve({ { &c->train.hCand, gatherBytes } })) return e;      // (the pinned offsets may feed an earlier copy)
     uint64_t *ho = (uint64_t *)c->train.hCand.p;
     uint32_t *hs = (uint32_t *)(ho + 2 * (size_t)nbSamples);
     std::vector<uint32_t> sizes(sampleSizes, sampleSizes + nbSamples);
     uint64_t at = 0;
     for (uint32_t i = 0; i < nbSamples; i++) { ho[i] = sampleOffsets[i]; ho[nbSamples + i] = at; hs[i] = sampleSizes[i]; at += sampleSizes[i]; }
-    if (hipMemcpyAsync(c->train.dGather.p, ho, sizeof(uint64_t) * 2 * nbSamples + sizeof(uint32_t) * nbSamples, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipMemsetAsync((uint8_t *)c->train.dSamples.p + total, 0, 64, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->toDevice(c->train.dGather.p, ho, gatherBytes)) return e;
+    if (const int e = c->fill((uint8_t *)c->train.dSamples.p + total, 0, 64)) return e;
     LAUNCH(c, "k_train_gather", k_train_gather, dim3(nbSamples), dim3(256), 0, (const uint8_t *)dSamples, (const uint64_t *)c->train.dGather.p,
            (const uint32_t *)((const uint64_t *)c->train.dGather.p + 2 * (size_t)nbSamples), nbSamples, (uint8_t *)c->train.dSamples.p);
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;      // (the pinned offsets are reused below)
-    std::vector<uint8_t> tmp(dictCapacity);
-    zsmi_fastCoverParams p = *params;
-    size_t size = 0;
-    if (const int e = trainImpl(c, (const uint8_t *)c->train.dSamples.p, sizes, tmp.data(), dictCapacity, &p, &size)) return e;
-    memcpy(dictBuffer, tmp.data(), size);
-    params->k = p.k; params->d = p.d;
-    *dictSize = size;
-    return 0;
+    if (const int e = c->wait()) return e;                                              // (the pinned offsets are reused below)
+    return trainGuarded(c, sizes, dictBuffer, dictCapacity, params, dictSize);
 }
 
 extern "C" size_t zsmi_finalizeDictionary(void *dst, size_t dstCapacity, const void *content, size_t contentSize, const void *samplesBuffer,
@@ -519,15 +517,13 @@ extern "C" size_t zsmi_finalizeDictionary(void *dst, size_t dstCapacity, const v
     if (const int e = trainStageHost(c, samplesBuffer, samplesSizes, nbSamples, sizes)) return ZSMI_ERR(e);
     const uint32_t cap32 = (uint32_t)std::min<size_t>(dstCapacity, 0xFFFFFFFFu - 4096);
     if (!c->train.dContent.reserve(contentSize) || !c->train.dOut.reserve((size_t)cap32 + 64) || !c->train.dCand.reserve(64)) return ZSMI_ERR(ZSMI_error_memory_allocation);
-    if (hipMemcpyAsync(c->train.dContent.p, content, contentSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (const int e = c->toDevice(c->train.dContent.p, content, contentSize)) return ZSMI_ERR(e);
     std::vector<uint64_t> offs(nbSamples);
     { uint64_t at = 0; for (unsigned i = 0; i < nbSamples; i++) { offs[i] = at; at += sizes[i]; } }
     uint32_t *dResult = (uint32_t *)c->train.dCand.p;
     if (const int e = finalizeQueue(c, (const uint8_t *)c->train.dSamples.p, offs, sizes, (const uint8_t *)c->train.dContent.p, (uint32_t)contentSize, cap32, level ? level : 3, dictID,
                                     (uint8_t *)c->train.dOut.p, dResult)) return ZSMI_ERR(e);
-    uint32_t size = 0;
-    if (hipMemcpyAsync(&size, dResult, sizeof size, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
-    if (!size) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
-    if (hipMemcpy(dst, c->train.dOut.p, size, hipMemcpyDeviceToHost) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    size_t size = 0;
+    if (const int e = finalizeFetch(c, dResult, dst, &size)) return ZSMI_ERR(e);
     return size;
 }

@@ -19,6 +19,7 @@
 #ifndef ZSMI_ENTROPY_KERNELS_HIP        // (dict_train.hip and seekable.hip include this file too)
 #define ZSMI_ENTROPY_KERNELS_HIP
 #include "zsmi_device.h"
+#include "zsmi_status.h"          // the size word a frame leaves: zs_word_is_error, zs_word_bytes
 #include "zsmi_scratch.h"         // the scratch slots of a block (its list of records, its header, literals, streams, sections, meta: ZsBlockMeta) and what the sequences kernel borrows
 #include "zsmi_wave.h"
 #include "zsmi_fse.h"            // the alphabets' constants, FseBuild, the table builder's two routines
@@ -1514,7 +1515,7 @@ __global__ void __launch_bounds__(64) k_frame_checksum(const uint8_t *__restrict
     if (real) cd = chunks[q];
     const uint32_t written = real ? dstSizes[q] : 0xFFFFFFFFu;
     // a frame to close: not an error code, and - always, the bound holds the 4 bytes - one that leaves them room in its slot
-    const bool work = written <= 0xFFFFFF88u && (uint64_t)written + 4 <= zs_compress_bound(cd.size);
+    const bool work = !zs_word_is_error(written) && (uint64_t)written + 4 <= zs_compress_bound(cd.size);
     const uint64_t h = xxh64_quad<16>(src + cd.srcOff, work ? cd.size : 0u);           // (every lane of a quad calls; a quad without work hashes nothing)
     if (!work || (threadIdx.x & 3u) != 0) return;
     uint8_t *out = dst + cd.dstOff, *t = out + written;
@@ -1589,14 +1590,14 @@ __global__ void __launch_bounds__(256) k_cdict_tables(const ZsCDictEntropy *__re
 // ---------------------------------------------------------------------------------------------
 // pack frames: compressed frames in bound-sized slots -> back to back
 // ---------------------------------------------------------------------------------------------
-// The bytes item i gets: its size, or 0 for an error word (a size above 0xFFFFFF88) or an item whose status (may be null) is not 0.
+// The bytes item i gets: its size, or 0 for an error word (zsmi_status.h) or an item whose status (may be null) is not 0.
 // Size: uint32_t, the sizes a compress call leaves (zsmi_packFramesDevice: align 1, no status, no caps); uint64_t, the sizes k_frame_sizes
 // leaves (zsmi_layoutOutputsDevice), which also wants the items' bytes themselves: caps (may be null).
 template <class Size>
 __device__ __forceinline__ uint32_t zs_layout_cap(const Size *sizes, const uint32_t *status, uint32_t i)
 {
     const Size v = sizes[i];
-    return (v > (Size)0xFFFFFF88u || (status && status[i])) ? 0u : (uint32_t)v;
+    return (v > (Size)zs_word_max_size() || (status && status[i])) ? 0u : (uint32_t)v;
 }
 // The exclusive scan of n such sizes, each rounded up to `align` (a power of two); offsets[n]: the total.  Three launches (scanOffsets in
 // zsmi_api.hip): k_pack_tile_sums, a workgroup a tile of ZS_SCAN_TILE items - its sum; k_pack_scan_tiles, ONE workgroup - the exclusive
@@ -1668,7 +1669,7 @@ k_pack_offsets(const Size *sizes, const uint32_t *status, uint32_t n, uint32_t a
 __global__ void k_pack_copy(const uint8_t *frames, const uint64_t *srcOffsets, const uint32_t *sizes, const uint64_t *packedOffsets, uint8_t *packed)
 {
     const uint32_t i = blockIdx.x;
-    const uint32_t sz = sizes[i] > 0xFFFFFF88u ? 0 : sizes[i];
+    const uint32_t sz = zs_word_bytes(sizes[i]);
     const uint8_t *s = frames + srcOffsets[i]; uint8_t *d = packed + packedOffsets[i];
     zs_block_copy(d, s, sz, threadIdx.x, blockDim.x);
 }

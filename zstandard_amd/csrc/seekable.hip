@@ -13,6 +13,7 @@
 // from where k_seek_gather copies its overlaps with the ranges - then k_seek_verify checks every decoded frame's size and checksum against
 // its entry and k_seek_range_status gives each range the code of its first failing frame.
 
+#include "zsmi_status.h"          // the size word a compressed or decoded frame leaves
 #include "zsmi_wave.h"            // zs_block_copy, xxh64_quad, rd32
 #include "entropy_kernels.hip"    // k_pack_offsets
 #include "decode_kernels.hip"     // the decoder's error codes (E_*)
@@ -27,7 +28,6 @@ static const uint32_t kSeekHashAhead = 16;           // stripes a lane has in fl
 
 // ---- kernels ----
 __device__ __forceinline__ void seek_st32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-__device__ __forceinline__ bool seek_isErr(uint32_t s) { return s > 0xFFFFFF88u; }
 
 // XXH64 of each frame's input: one quad a frame (16 a wavefront), kSeekHashAhead stripes a lane in flight.  At 64 KiB frames 1 GiB is 16384
 // quads - one wavefront a SIMD - so the loads of one lane, not the number of wavefronts, are what hides the memory latency.
@@ -45,7 +45,7 @@ __global__ void __launch_bounds__(64) k_seek_hash(const uint8_t *__restrict__ sr
 __global__ void k_seek_pack(const uint8_t *__restrict__ stage, uint64_t stride, const uint32_t *__restrict__ sizes, const uint64_t *__restrict__ packedOffsets, uint8_t *__restrict__ dst)
 {
     const uint32_t i = blockIdx.x;
-    const uint32_t sz = seek_isErr(sizes[i]) ? 0u : sizes[i];
+    const uint32_t sz = zs_word_bytes(sizes[i]);
     zs_block_copy(dst + packedOffsets[i], stage + (uint64_t)i * stride, sz, threadIdx.x, blockDim.x);
 }
 // the table behind the packed frames: one entry a thread, the header and the footer from the first; a failed frame's (index << 8 | code) goes to
@@ -62,10 +62,10 @@ __global__ void k_seek_table(const uint32_t *__restrict__ sizes, const uint64_t 
     }
     if (i >= n) return;
     const uint32_t s = sizes[i];
-    if (seek_isErr(s)) atomicMin(err, ((unsigned long long)i << 8) | (0u - s));
+    if (zs_word_is_error(s)) atomicMin(err, ((unsigned long long)i << 8) | zs_word_code(s));
     uint8_t *e = t + 8 + (uint64_t)i * E;
     const uint64_t off = (uint64_t)i * frameSize;
-    seek_st32(e, seek_isErr(s) ? 0u : s); seek_st32(e + 4, (uint32_t)min(frameSize, srcSize - off));
+    seek_st32(e, zs_word_bytes(s)); seek_st32(e + 4, (uint32_t)min(frameSize, srcSize - off));
     if (checksum) seek_st32(e + 8, hashes[i]);
 }
 __global__ void k_seek_finish(const uint64_t *__restrict__ packedOffsets, uint32_t n, uint32_t entryBytes, const unsigned long long *__restrict__ err, uint64_t *archiveSize)
@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(64) k_seek_verify(const ZsSeekItem *__restrict
     const ZsSeekItem it = items[real ? q : m - 1u];
     const uint32_t s = real ? status[it.slot] : 0u;
     uint32_t code = 0;
-    if (seek_isErr(s)) code = (0u - s) == E_dstSize_tooSmall ? (uint32_t)E_corruption_detected : 0u - s;
+    if (zs_word_is_error(s)) code = zs_word_code(s) == E_dstSize_tooSmall ? (uint32_t)E_corruption_detected : zs_word_code(s);
     else if (s != it.size) code = E_corruption_detected;
     const bool hash = real && checksum && code == 0;
     if (__ballot(hash)) {
@@ -236,7 +236,7 @@ static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize,
     if (const int e = seekParams(srcSize, frameSize, F, n64)) return e;
     if (dstCapacity < seekBound(srcSize, F, n64, checksumFlag)) return ZSMI_error_dstSize_tooSmall;
     if (!dArchiveSize || !dDst || (srcSize && !dSrc)) return ZSMI_error_GENERIC;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     const uint32_t n = (uint32_t)n64, E = checksumFlag ? 12u : 8u;
     const uint64_t stride = zsmi_compressBound(F);
     // per-frame words: sizes [n], hashes [n], then (8-aligned) packed offsets [n + 1] and the error word
@@ -255,11 +255,11 @@ static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize,
     }
     if (const int e = scanOffsets(c, "k_pack_offsets", (const uint32_t *)dSizes, nullptr, n, 1u, nullptr, dPacked)) return e;
     if (n) LAUNCH(c, "k_seek_pack", k_seek_pack, dim3(n), dim3(256), 0, (const uint8_t *)c->seek.dStage.p, stride, (const uint32_t *)dSizes, (const uint64_t *)dPacked, (uint8_t *)dDst);
-    if (hipMemsetAsync(dErr, 0xFF, sizeof(*dErr), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->fill(dErr, 0xFF, sizeof(*dErr))) return e;
     LAUNCH(c, "k_seek_table", k_seek_table, dim3(std::max<uint32_t>(1, (n + 255) / 256)), dim3(256), 0, (const uint32_t *)dSizes, (const uint64_t *)dPacked,
            (const uint32_t *)dHash, srcSize, F, n, checksumFlag ? 1 : 0, (uint8_t *)dDst, dErr);
     LAUNCH(c, "k_seek_finish", k_seek_finish, dim3(1), dim3(1), 0, (const uint64_t *)dPacked, n, E, (const unsigned long long *)dErr, dArchiveSize);
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 extern "C" int zsmi_compressSeekableDevice(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, void *dDst, uint64_t dstCapacity,
                                            uint64_t *dArchiveSize, int level, uint32_t frameSize, int checksumFlag)
@@ -273,18 +273,15 @@ extern "C" size_t zsmi_compressSeekable(void *dst, size_t dstCapacity, const voi
     const uint64_t bound = seekBound(srcSize, F, n, checksumFlag);
     Borrowed b; zsmi_ctx *c = b.c;
     if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (const int e = c->bind()) return ZSMI_ERR(e);
     if (!c->sSrc.reserve(srcSize + 64) || !c->sDst.reserve(bound + 64) || !c->sSizes.reserve(sizeof(uint64_t))) return ZSMI_ERR(ZSMI_error_memory_allocation);
-    if (srcSize && hipMemcpyAsync(c->sSrc.p, src, srcSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
-    if (const int rc = compressSeekableImpl(c, c->sSrc.p, srcSize, c->sDst.p, bound, (uint64_t *)c->sSizes.p, level, frameSize, checksumFlag, 0)) {
-        (void)hipStreamSynchronize(c->stream);
-        return ZSMI_ERR(rc);
-    }
+    if (srcSize) if (const int e = c->toDevice(c->sSrc.p, src, srcSize)) return ZSMI_ERR(e);
+    if (const int rc = compressSeekableImpl(c, c->sSrc.p, srcSize, c->sDst.p, bound, (uint64_t *)c->sSizes.p, level, frameSize, checksumFlag, 0)) { (void)c->wait(); return ZSMI_ERR(rc); }
     uint64_t size = 0;
-    if (hipMemcpyAsync(&size, c->sSizes.p, sizeof size, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (c->toHost(&size, c->sSizes.p, sizeof size) || c->wait()) return ZSMI_ERR(ZSMI_error_GENERIC);
     if (zsmi_isError(size)) return size;
     if (size > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
-    if (hipMemcpyAsync(dst, c->sDst.p, size, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (c->toHost(dst, c->sDst.p, size) || c->wait()) return ZSMI_ERR(ZSMI_error_GENERIC);
     return size;
 }
 
@@ -301,13 +298,11 @@ static int seekParseDevice(zsmi_ctx *c, const uint8_t *src, uint64_t srcSize, Se
     // the archive's tail, once: it holds the whole table up to 256 KiB (16384 entries with checksums: 1 GiB in 64 KiB frames); a larger
     // table is read again at its size
     std::vector<uint8_t> tail(std::min<uint64_t>(srcSize, 256u << 10));
-    if (hipMemcpyAsync(tail.data(), src + srcSize - tail.size(), tail.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (c->toHost(tail.data(), src + srcSize - tail.size(), tail.size()) || c->wait()) return ZSMI_error_GENERIC;
     if (const int e = seekFooter(tail.data() + tail.size() - 9, srcSize, t)) return e;
     if (t.tableSize > tail.size()) {
         tail.resize(t.tableSize);
-        if (hipMemcpyAsync(tail.data(), src + srcSize - t.tableSize, t.tableSize, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        if (c->toHost(tail.data(), src + srcSize - t.tableSize, t.tableSize) || c->wait()) return ZSMI_error_GENERIC;
     }
     return seekEntries(tail.data() + tail.size() - t.tableSize, srcSize, t);
 }
@@ -350,7 +345,7 @@ static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrame
     uint32_t m = 0;
     for (Run &u : runs) { u.slot0 = m; m += u.hi - u.lo + 1; }
     if (framesDecoded) *framesDecoded = m;
-    if (m == 0) return hipMemsetAsync(dStatus, 0, (size_t)nRanges * sizeof(uint32_t), c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    if (m == 0) return c->fill(dStatus, 0, (size_t)nRanges * sizeof(uint32_t));
     auto slotOf = [&](uint32_t i) {
         const Run &u = *(std::upper_bound(runs.begin(), runs.end(), i, [](uint32_t v, const Run &x) { return v < x.lo; }) - 1);
         return u.slot0 + (i - u.lo);
@@ -414,7 +409,7 @@ static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrame
     if (!small.empty()) memcpy(hp, small.data(), small.size() * sizeof(ZsSeekPiece));
     if (!tiles.empty()) memcpy(hp + small.size(), tiles.data(), tiles.size() * sizeof(ZsSeekPiece));
     for (uint32_t r = 0; r < nRanges; r++) hs[r] = { firstSlot[r], sp[r].count };
-    if (hipMemcpyAsync(dLists, hi, listBytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->toDevice(dLists, hi, listBytes)) return e;
     if (const int e = c->seek.hLists.sent(c->stream)) return e;
     if (nOwned)
         if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), nOwned, dDst, dof.data(), caps.data(), dSt, nullptr)) return e;
@@ -425,7 +420,7 @@ static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrame
     }
     LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((m + 15) / 16), dim3(64), 0, dItems, m, (const uint32_t *)dSt, t.checksum ? 1 : 0, dCodes);
     LAUNCH(c, "k_seek_range_status", k_seek_range_status, dim3((nRanges + 3) / 4), dim3(256), 0, dSpans, nRanges, (const uint32_t *)dCodes, dStatus);
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 
 // ---- opened archives: the table parsed and checked once, the frames' bytes in device memory (the handle's own copy of a host archive, or the
@@ -439,40 +434,28 @@ struct zsmi_seekable {
 };
 extern "C" zsmi_seekable *zsmi_openSeekable(zsmi_ctx *c, const void *archive, size_t size, int *err)
 {
-    int code = 0;
-    zsmi_seekable *sk = new (std::nothrow) zsmi_seekable();
-    do {
-        if (!sk) { code = ZSMI_error_memory_allocation; break; }
-        if ((code = seekParseHost(archive, size, sk->t))) break;
-        if (!c) { code = ZSMI_error_init_missing; break; }
-        sk->device = c->device;
-        const uint64_t bytes = sk->t.cOff[sk->t.n];
-        if (bytes == 0) break;
-        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if (hipMalloc(&sk->dOwned, bytes + 64) != hipSuccess) { (void)hipGetLastError(); sk->dOwned = nullptr; code = ZSMI_error_memory_allocation; break; }
-        sk->dFrames = (const uint8_t *)sk->dOwned;
-        if (hipMemcpyAsync(sk->dOwned, archive, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) code = ZSMI_error_GENERIC;
-    } while (0);
-    if (code) { delete sk; sk = nullptr; }
-    if (err) *err = code;
-    return sk;
+    return makeHandle<zsmi_seekable>(err, [&](zsmi_seekable &sk) -> int {
+        if (const int e = seekParseHost(archive, size, sk.t)) return e;
+        if (!c) return ZSMI_error_init_missing;
+        sk.device = c->device;
+        const uint64_t bytes = sk.t.cOff[sk.t.n];
+        if (bytes == 0) return 0;
+        if (const int e = c->bind()) return e;
+        if (hipMalloc(&sk.dOwned, bytes + 64) != hipSuccess) { (void)hipGetLastError(); sk.dOwned = nullptr; return ZSMI_error_memory_allocation; }
+        sk.dFrames = (const uint8_t *)sk.dOwned;
+        return c->toDevice(sk.dOwned, archive, bytes) || c->wait() ? ZSMI_error_GENERIC : 0;
+    });
 }
 extern "C" zsmi_seekable *zsmi_openSeekableDevice(zsmi_ctx *c, const void *dArchive, uint64_t size, int *err)
 {
-    int code = 0;
-    zsmi_seekable *sk = nullptr;
-    do {
-        if (!c) { code = ZSMI_error_init_missing; break; }
-        if (!dArchive || size < 9) { code = ZSMI_error_prefix_unknown; break; }
-        sk = new (std::nothrow) zsmi_seekable();
-        if (!sk) { code = ZSMI_error_memory_allocation; break; }
-        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if ((code = seekParseDevice(c, (const uint8_t *)dArchive, size, sk->t))) break;
-        sk->device = c->device; sk->dFrames = (const uint8_t *)dArchive;
-    } while (0);
-    if (code) { delete sk; sk = nullptr; }
-    if (err) *err = code;
-    return sk;
+    return makeHandle<zsmi_seekable>(err, [&](zsmi_seekable &sk) -> int {
+        if (!c) return ZSMI_error_init_missing;
+        if (!dArchive || size < 9) return ZSMI_error_prefix_unknown;
+        if (const int e = c->bind()) return e;
+        if (const int e = seekParseDevice(c, (const uint8_t *)dArchive, size, sk.t)) return e;
+        sk.device = c->device; sk.dFrames = (const uint8_t *)dArchive;
+        return 0;
+    });
 }
 extern "C" void zsmi_closeSeekable(zsmi_seekable *sk) { delete sk; }
 extern "C" size_t zsmi_getNumFrames_fromSeekable(const zsmi_seekable *sk) { return sk ? sk->t.n : 0; }
@@ -503,7 +486,7 @@ extern "C" int zsmi_seekableReadRangesDevice(zsmi_ctx *c, const zsmi_seekable *s
     uint64_t bytes = 0;
     for (uint32_t r = 0; r < nRanges; r++) { rg[r].to = dstOffsets[r]; bytes += rg[r].b - rg[r].a; }
     if (bytes && !dDst) return ZSMI_error_GENERIC;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     for (uint32_t r = 0; r < nRanges; r++) written[r] = rg[r].b - rg[r].a;
     return seekReadRanges(c, sk->t, sk->dFrames, 0, rg.data(), nRanges, (uint8_t *)dDst, dStatus, framesDecoded);
 }
@@ -518,13 +501,12 @@ extern "C" int zsmi_seekableReadRangesHost(zsmi_ctx *c, const zsmi_seekable *sk,
     if (bytes && !dst) return ZSMI_error_GENERIC;
     for (uint32_t r = 0; r < nRanges; r++) written[r] = rg[r].b - rg[r].a;
     if (nRanges == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     if (!c->sDst.reserve(bytes + 64) || !c->sSizes.reserve((size_t)nRanges * sizeof(uint32_t))) return ZSMI_error_memory_allocation;
     int rc = seekReadRanges(c, sk->t, sk->dFrames, 0, rg.data(), nRanges, (uint8_t *)c->sDst.p, (uint32_t *)c->sSizes.p, nullptr);
-    if (!rc && hipMemcpyAsync(statuses, c->sSizes.p, (size_t)nRanges * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZSMI_error_GENERIC;
-    if (!rc && bytes && hipMemcpyAsync(dst, c->sDst.p, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZSMI_error_GENERIC;
-    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ZSMI_error_GENERIC;
-    return rc;
+    if (!rc) rc = c->toHost(statuses, c->sSizes.p, (size_t)nRanges * sizeof(uint32_t));
+    if (!rc && bytes) rc = c->toHost(dst, c->sDst.p, bytes);
+    const int waited = c->wait(); return rc ? rc : waited;              // (the wait: whatever was queued, a failed call included)
 }
 
 // ---- the single-range calls: the one-range case of seekReadRanges ----
@@ -534,7 +516,7 @@ extern "C" int zsmi_decompressSeekableDevice(zsmi_ctx *c, const void *dSrc, uint
     if (!c) return ZSMI_error_init_missing;
     if (!dSrc || srcSize < 9) return ZSMI_error_prefix_unknown;
     if (!dStatus || !written) return ZSMI_error_GENERIC;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     SeekTable t;                                                        // (a table for this call alone: an opened archive keeps it)
     if (const int e = seekParseDevice(c, (const uint8_t *)dSrc, srcSize, t)) return e;
     const uint64_t content = t.dOff[t.n];
@@ -557,16 +539,13 @@ extern "C" size_t zsmi_decompressSeekable(void *dst, size_t dstCapacity, const v
     const uint64_t base = t.cOff[first], span = t.cOff[last + 1] - base;       // only the overlapping frames' bytes go to the device
     Borrowed bw; zsmi_ctx *c = bw.c;
     if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (const int e = c->bind()) return ZSMI_ERR(e);
     if (!c->sSrc.reserve(span + 64) || !c->sDst.reserve(rg.b - rg.a + 64) || !c->sSizes.reserve(sizeof(uint32_t))) return ZSMI_ERR(ZSMI_error_memory_allocation);
-    if (hipMemcpyAsync(c->sSrc.p, (const uint8_t *)src + base, span, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
-    if (const int rc = seekReadRanges(c, t, (const uint8_t *)c->sSrc.p, base, &rg, 1, (uint8_t *)c->sDst.p, (uint32_t *)c->sSizes.p, nullptr)) {
-        (void)hipStreamSynchronize(c->stream);
-        return ZSMI_ERR(rc);
-    }
+    if (const int e = c->toDevice(c->sSrc.p, (const uint8_t *)src + base, span)) return ZSMI_ERR(e);
+    if (const int rc = seekReadRanges(c, t, (const uint8_t *)c->sSrc.p, base, &rg, 1, (uint8_t *)c->sDst.p, (uint32_t *)c->sSizes.p, nullptr)) { (void)c->wait(); return ZSMI_ERR(rc); }
     uint32_t status = 0;
-    if (hipMemcpyAsync(&status, c->sSizes.p, sizeof status, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (c->toHost(&status, c->sSizes.p, sizeof status) || c->wait()) return ZSMI_ERR(ZSMI_error_GENERIC);
     if (status) return ZSMI_ERR(status);
-    if (hipMemcpyAsync(dst, c->sDst.p, rg.b - rg.a, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (c->toHost(dst, c->sDst.p, rg.b - rg.a) || c->wait()) return ZSMI_ERR(ZSMI_error_GENERIC);
     return rg.b - rg.a;
 }

@@ -4,6 +4,7 @@
 //
 // Single translation unit: the kernel sources are included so that launches and kernels share one code object.  Every file includes what
 // it uses; the list is the library's table of contents.
+#include "zsmi_status.h"          // the size word: a byte count or an error code, host and device
 #include "zsmi_device.h"          // format constants, block / unit / sequence records, unaligned loads and stores
 #include "zsmi_scratch.h"         // the scratch layouts: the table of the compress buffers, the slot accessors and borrowings of both pipelines, DecLists
 #include "zsmi_wave.h"            // device primitives of more than one kernel file: wave_*, zs_block_copy, rd16/24/32, xxh64_quad
@@ -14,7 +15,7 @@
 #include "plan_kernels.hip"       // encoder, the plan built on the device (the resident call): k_plan_chunks, k_plan_blocks, k_plan_refuse; k_compress_bounds
 #include "decode_kernels.hip"     // general decoder: k_decode_frames, and the decoder routines the fast path shares; loadDictEntropy, the one reader of a dictionary; k_frame_sizes, k_dec_items
 #include "decode_fast.hip"        // fast decode path: k_dec_prep, k_dec_huffman, k_dec_sequences, k_dec_entropy, k_dec_execute, k_dec_checksum, k_dec_collect; k_dict_load (a dictionary -> its record for the host, a DDict's image)
-#include "zsmi_ctx.h"             // host: zsmi_ctx and its buffers, LAUNCH, the batch entry points the features call
+#include "zsmi_ctx.h"             // host: zsmi_ctx with its buffers and stream verbs, LAUNCH, makeHandle, the batch entry points the features call
 #include "seekable.hip"           // feature: seekable archives (kernels and host)
 #include "dict_train.hip"         // feature: dictionary training and finalize (kernels and host)
 
@@ -175,7 +176,7 @@ extern "C" void zsmi_freeCtx(zsmi_ctx *c)
 extern "C" int zsmi_sync(zsmi_ctx *c)
 {
     if (!c) return ZSMI_error_init_missing;
-    return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->wait();
 }
 // ---- sticky compression parameters (ZSTD_CCtx_setParameter): read on the host when a compress call is made, they govern what is queued after ----
 extern "C" int zsmi_setParameter(zsmi_ctx *c, int param, int value)
@@ -234,8 +235,7 @@ static int loadDict(zsmi_ctx *c, const void *dDict, size_t dictSize, ZsCompressD
 {
     if (!c->dDictRec.reserve(sizeof(ZsDictRecord)) || !c->hDictRec.reserve(sizeof(ZsDictRecord))) return ZSMI_error_memory_allocation;
     LAUNCH(c, "k_dict_load", k_dict_load, dim3(1), dim3(64), 0, (const uint8_t *)dDict, (uint32_t)dictSize, (ZsDictRecord *)c->dDictRec.p, img);
-    if (hipMemcpyAsync(c->hDictRec.p, c->dDictRec.p, sizeof(ZsDictRecord), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (c->toHost(c->hDictRec.p, c->dDictRec.p, sizeof(ZsDictRecord)) || c->wait()) return ZSMI_error_GENERIC;
     const ZsDictRecord &r = *(const ZsDictRecord *)c->hDictRec.p;
     if (r.status) return (int)r.status;
     out = ZsCompressDict();
@@ -257,7 +257,7 @@ bool zsmi_ctx::Scratch::reserve(uint32_t cap)
 // The plan of a call: chunks -> blocks (ZsChunkDesc, ZsBlockDesc) and LZ units, built on the host and copied to the device.  It is reused
 // while the chunk layout repeats (steady-state batches; compared in place: such a call allocates and copies nothing).  A dictionary call
 // adds a unit list of its own, kept while the layout and the chunks' choice of dictionary repeat.
-int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict,
+int CompressPlan::build(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict,
                         const uint32_t *dictIndex, const uint8_t *memberHasDict)
 {
     bool same = key.size() == (size_t)n * 3 + 1 && key[0] == n;
@@ -269,11 +269,8 @@ int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const ui
         uint64_t nBlocks = 0;
         for (uint32_t i = 0; i < n; i++) nBlocks += zs_chunk_counts(srcSizes[i]).blocks;
         if (nBlocks > 0x7FFFFFFFull) return ZSMI_error_srcSize_wrong;
-        if (!hChunks.reserve(sizeof(ZsChunkDesc) * n) || !hBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
-        if (!dChunks.reserve(sizeof(ZsChunkDesc) * n) || !dBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks)) return ZSMI_error_memory_allocation;
-        if (!hUnits.reserve(sizeof(ZsUnitDesc) * nBlocks) || !dUnits.reserve(sizeof(ZsUnitDesc) * nBlocks)) return ZSMI_error_memory_allocation;
-        // the pinned plan buffers may still feed a previous asynchronous copy
-        if (hipStreamSynchronize(stream) != hipSuccess) return ZSMI_error_GENERIC;
+        if (!dChunks.reserve(sizeof(ZsChunkDesc) * n) || !dBlocks.reserve(sizeof(ZsBlockDesc) * nBlocks) || !dUnits.reserve(sizeof(ZsUnitDesc) * nBlocks)) return ZSMI_error_memory_allocation;
+        if (const int e = c->idleReserve({ { &hChunks, sizeof(ZsChunkDesc) * n }, { &hBlocks, sizeof(ZsBlockDesc) * nBlocks }, { &hUnits, sizeof(ZsUnitDesc) * nBlocks } })) return e;      // (they may still feed the previous layout's copies)
         // a chunk's blocks and units: the rule of zsmi_plan.h, which the resident call's plan kernels apply too
         ZsChunkDesc *hc0 = (ZsChunkDesc *)hChunks.p; ZsBlockDesc *hb = (ZsBlockDesc *)hBlocks.p;
         uint32_t b = 0, maxNb = 1;
@@ -303,10 +300,10 @@ int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const ui
                 u.srcOff = srcOffsets[i] + cu.off; u.size = cu.size; u.firstBlock = hc0[i].firstBlock + cu.block;
             }
         }
-        if (nSmall + nBig && hipMemcpyAsync(dUnits.p, hu, sizeof(ZsUnitDesc) * (nSmall + nBig), hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
+        if (nSmall + nBig) if (const int e = c->toDevice(dUnits.p, hu, sizeof(ZsUnitDesc) * (nSmall + nBig))) return e;
         small.base = 0; big.base = nSmall;
-        if (hipMemcpyAsync(dChunks.p, hc0, sizeof(ZsChunkDesc) * n, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
-        if (hipMemcpyAsync(dBlocks.p, hb, sizeof(ZsBlockDesc) * nBlocks, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
+        if (const int e = c->toDevice(dChunks.p, hc0, sizeof(ZsChunkDesc) * n)) return e;
+        if (const int e = c->toDevice(dBlocks.p, hb, sizeof(ZsBlockDesc) * nBlocks)) return e;
         key.swap(newKey); blocks = nBlocks; maxChunkBlocks = maxNb;
         dictKind = kDictNone;
     }
@@ -350,8 +347,8 @@ int CompressPlan::build(hipStream_t stream, const uint64_t *srcOffsets, const ui
         for (uint32_t k = small.before[i]; k < small.before[i + 1]; k++) hu[prefixed ? iw++ : it++] = all[k];
     }
     if (bytes) {
-        if (hipMemcpyAsync(dDictList.p, hu, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return ZSMI_error_GENERIC;
-        if (const int e = hDictList.sent(stream)) return e;
+        if (const int e = c->toDevice(dDictList.p, hu, bytes)) return e;
+        if (const int e = hDictList.sent(c->stream)) return e;
     }
     whole.base = 0; tail.base = nWhole; chunkDictOff = unitBytes; unitDictOff = unitBytes + sizeof(uint32_t) * (size_t)n;
     dictKind = kind;
@@ -390,17 +387,20 @@ static void launchDictTables(zsmi_ctx *c, const ZsCompressDict &d, int level, vo
 {
     LAUNCH(c, "k_lz_dict_tables", k_lz_dict_tables, dim3(lzShape(level).useLong ? 2 : 1), dim3(1024), 0, dictEntry(d, (const uint32_t *)dImg), (ZsCDictEntry *)dEntry);
 }
+// a dictionary in host memory -> the context's staging buffer; dict: then its device copy
+static int stageDict(zsmi_ctx *c, const void *&dict, size_t dictSize)
+{
+    if (!c->sDict.reserve(dictSize + 64)) return ZSMI_error_memory_allocation;
+    if (const int e = c->toDevice(c->sDict.p, dict, dictSize)) return e;
+    dict = c->sDict.p; return 0;
+}
 static int dictFromBytes(zsmi_ctx *c, const void *dict, size_t dictSize, DictBytes kind, int level, uint32_t n, ZsCDictSel &sel)
 {
     if (!dict || dictSize == 0) return 0;
     if (!c) return ZSMI_error_init_missing;
     if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    if (kind == kDictOnHost) {                                       // (through the context's staging buffer)
-        if (!c->sDict.reserve(dictSize + 64)) return ZSMI_error_memory_allocation;
-        if (hipMemcpyAsync(c->sDict.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        dict = c->sDict.p;
-    }
+    if (const int e = c->bind()) return e;
+    if (kind == kDictOnHost) if (const int e = stageDict(c, dict, dictSize)) return e;
     ZsCompressDict d;
     d.dBytes = (const uint8_t *)dict; d.contentSize = (uint32_t)dictSize;
     if (kind != kDictContent) if (const int e = loadDict(c, dict, dictSize, d)) return e;
@@ -494,12 +494,12 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     const LzShape &shape = lzShape(level);
     CompressPlan &P = c->plan;
     const ZsCDictSel sel = dict && dict->dTable ? *dict : ZsCDictSel();
     const bool useDict = sel.dTable != nullptr;
-    if (const int e = P.build(c->stream, srcOffsets, srcSizes, n, dstOffsets, useDict, sel.dictIndex, sel.memberHasDict)) return e;
+    if (const int e = P.build(c, srcOffsets, srcSizes, n, dstOffsets, useDict, sel.dictIndex, sel.memberHasDict)) return e;
     // sub-batches of whole chunks, one after the other through one scratch set.  Every kernel goes to the caller's stream: a stream of
     // the context's own costs two queue crossings a call (~0.01 - 0.09 ms each: a bench line of 126 GiB/s where the kernels added up to 137).
     const uint32_t cap = subBatchCap(c, P.blocks, P.maxChunkBlocks);
@@ -517,7 +517,7 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
         launchSubBatch(c, shape, sb, dSrc, dDst, dDstSizes, dStats);
     }
     closeFrames(c, dSrc, sb.dChunks, n, dDst, dDstSizes, checksum);
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                         uint32_t n, void *dDst, const uint64_t *dstOffsets, uint32_t *dDstSizes, int level)
@@ -537,9 +537,9 @@ extern "C" int zsmi_compressBoundsDevice(zsmi_ctx *c, const uint32_t *dSrcSizes,
     if (!c) return ZSMI_error_init_missing;
     if (n && (!dSrcSizes || !dBounds)) return ZSMI_error_GENERIC;
     if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     LAUNCH(c, "k_compress_bounds", k_compress_bounds, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, dBounds);
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
                                           uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level)
@@ -547,7 +547,7 @@ extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const u
     if (!c) return ZSMI_error_init_missing;
     if (n && (!dSrc || !dSrcOffsets || !dSrcSizes || !dDst || !dDstOffsets || !dDstSizes)) return ZSMI_error_GENERIC;
     if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     const LzShape &shape = lzShape(level);
     const uint32_t nbMax = zs_chunk_counts(maxSrcSize).blocks, bigMax = (nbMax + 1) / 2;
     const uint32_t cap = subBatchCap(c, (uint64_t)n * nbMax, nbMax);
@@ -579,8 +579,8 @@ extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const u
     }
     closeFrames(c, dSrc, dChunks, n, dDst, dDstSizes, c->checksumFlag);
     // last: a chunk above maxSrcSize was planned as an empty one, and its size word says so only now
-    LAUNCH(c, "k_plan_refuse", k_plan_refuse, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, maxSrcSize, 0u - (uint32_t)ZSMI_error_srcSize_wrong, dDstSizes);
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    LAUNCH(c, "k_plan_refuse", k_plan_refuse, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, maxSrcSize, zs_error_word(ZSMI_error_srcSize_wrong), dDstSizes);
+    return c->launched();
 }
 // dDict: device memory.  The dictionary loader runs over it and its record (a formatted dictionary's ID, recent offsets and content
 // offset, or the refusal) is read back: the call waits for the context's stream once.  (Its tables are queued before the plan: a new layout's wait in build covers them)
@@ -604,30 +604,24 @@ struct zsmi_cdict {
 };
 extern "C" zsmi_cdict *zsmi_createCDict(zsmi_ctx *c, const void *dict, size_t dictSize, int level, int *err)
 {
-    int code = 0;
-    zsmi_cdict *cd = nullptr;
-    do {
-        if (!c) { code = ZSMI_error_init_missing; break; }
-        if (dictSize > 0xFFFFFFFFull) { code = ZSMI_error_dictionary_corrupted; break; }
-        cd = new zsmi_cdict();
-        cd->device = c->device; cd->level = level;
-        if (!dict || dictSize == 0) { cd->empty = true; break; }
-        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if (!cd->dBytes.reserve(dictSize + 64) || !cd->dImg.reserve(kDictImgBytes) || !cd->dEntry.reserve(sizeof(ZsCDictEntry))) { code = ZSMI_error_memory_allocation; break; }
-        if (hipMemcpyAsync(cd->dBytes.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if ((code = loadDict(c, cd->dBytes.p, dictSize, cd->d))) break;
-        const bool formatted = cd->d.contentOff != 0;
-        if (formatted && !cd->dTables.reserve(sizeof(ZsCDictTables))) { code = ZSMI_error_memory_allocation; break; }
+    return makeHandle<zsmi_cdict>(err, [&](zsmi_cdict &cd) -> int {
+        if (!c) return ZSMI_error_init_missing;
+        if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
+        cd.device = c->device; cd.level = level;
+        if (!dict || dictSize == 0) { cd.empty = true; return 0; }
+        if (const int e = c->bind()) return e;
+        if (!cd.dBytes.reserve(dictSize + 64) || !cd.dImg.reserve(kDictImgBytes) || !cd.dEntry.reserve(sizeof(ZsCDictEntry))) return ZSMI_error_memory_allocation;
+        if (const int e = c->toDevice(cd.dBytes.p, dict, dictSize)) return e;
+        if (const int e = loadDict(c, cd.dBytes.p, dictSize, cd.d)) return e;
+        const bool formatted = cd.d.contentOff != 0;
+        if (formatted && !cd.dTables.reserve(sizeof(ZsCDictTables))) return ZSMI_error_memory_allocation;
         if (formatted) {
-            LAUNCH(c, "k_cdict_tables", k_cdict_tables, dim3(1), dim3(256), 0, &((const ZsDictRecord *)c->dDictRec.p)->ent, (ZsCDictTables *)cd->dTables.p);
-            cd->d.dTables = (const ZsCDictTables *)cd->dTables.p;
+            LAUNCH(c, "k_cdict_tables", k_cdict_tables, dim3(1), dim3(256), 0, &((const ZsDictRecord *)c->dDictRec.p)->ent, (ZsCDictTables *)cd.dTables.p);
+            cd.d.dTables = (const ZsCDictTables *)cd.dTables.p;
         }
-        launchDictTables(c, cd->d, level, cd->dImg.p, cd->dEntry.p);         // (and the one-entry table its calls pass)
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
-    } while (0);
-    if (code) { delete cd; cd = nullptr; }
-    if (err) *err = code;
-    return cd;
+        launchDictTables(c, cd.d, level, cd.dImg.p, cd.dEntry.p);            // (and the one-entry table its calls pass)
+        return c->wait() || c->launched() ? ZSMI_error_GENERIC : 0;
+    });
 }
 extern "C" void zsmi_freeCDict(zsmi_cdict *cd) { delete cd; }
 extern "C" unsigned zsmi_getDictID_fromCDict(const zsmi_cdict *cd) { return cd ? cd->d.dictID : 0; }
@@ -664,36 +658,25 @@ struct zsmi_cdictSet {
 #define ZSMI_CDICTSET_MAX 4096u
 extern "C" zsmi_cdictSet *zsmi_createCDictSet(zsmi_ctx *c, const zsmi_cdict *const *cds, uint32_t n, int level, int *err)
 {
-    int code = 0;
-    zsmi_cdictSet *set = nullptr;
-    do {
-        if (!c) { code = ZSMI_error_init_missing; break; }
-        if (n > ZSMI_CDICTSET_MAX) { code = ZSMI_error_parameter_outOfBound; break; }
-        if (n && !cds) { code = ZSMI_error_parameter_unsupported; break; }
+    return makeHandle<zsmi_cdictSet>(err, [&](zsmi_cdictSet &set) -> int {
+        if (!c) return ZSMI_error_init_missing;
+        if (n > ZSMI_CDICTSET_MAX) return ZSMI_error_parameter_outOfBound;
+        if (n && !cds) return ZSMI_error_parameter_unsupported;
         std::vector<ZsCDictEntry> table(n);
-        std::vector<uint8_t> hasDict(n);
-        bool tables = false;
-        for (uint32_t i = 0; i < n && !code; i++) {
+        set.device = c->device; set.level = level; set.members = n; set.hasDict.resize(n);
+        for (uint32_t i = 0; i < n; i++) {
             const zsmi_cdict *cd = cds[i];
             // a member: there, of this device, digested for this level (its images are built for one LZ shape)
-            if (!cd || cd->device != c->device || cd->level != level) { code = ZSMI_error_parameter_unsupported; break; }
-            hasDict[i] = !cd->empty;
+            if (!cd || cd->device != c->device || cd->level != level) return ZSMI_error_parameter_unsupported;
+            set.hasDict[i] = !cd->empty;
             table[i] = cd->empty ? ZsCDictEntry() : dictEntry(cd->d, (const uint32_t *)cd->dImg.p);
-            tables |= !cd->empty && cd->d.dTables != nullptr;
+            set.tables |= !cd->empty && cd->d.dTables != nullptr;
         }
-        if (code) break;
-        set = new (std::nothrow) zsmi_cdictSet();
-        if (!set) { code = ZSMI_error_memory_allocation; break; }
-        set->device = c->device; set->level = level; set->members = n; set->tables = tables; set->hasDict.swap(hasDict);
-        if (n == 0) break;
-        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if (!set->dTable.reserve(sizeof(ZsCDictEntry) * n)) { code = ZSMI_error_memory_allocation; break; }
-        if (hipMemcpyAsync(set->dTable.p, table.data(), sizeof(ZsCDictEntry) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-    } while (0);
-    if (code) { delete set; set = nullptr; }
-    if (err) *err = code;
-    return set;
+        if (n == 0) return 0;
+        if (const int e = c->bind()) return e;
+        if (!set.dTable.reserve(sizeof(ZsCDictEntry) * n)) return ZSMI_error_memory_allocation;
+        return c->toDevice(set.dTable.p, table.data(), sizeof(ZsCDictEntry) * n) || c->wait() ? ZSMI_error_GENERIC : 0;
+    });
 }
 extern "C" void zsmi_freeCDictSet(zsmi_cdictSet *set) { delete set; }
 extern "C" uint32_t zsmi_sizeofCDictSetMembers(const zsmi_cdictSet *set) { return set ? set->members : 0; }
@@ -846,7 +829,7 @@ static int uploadDecodeItems(zsmi_ctx *c, const uint64_t *srcOffsets, const uint
     if (const int e = c->hItems.take(sizeof(ZsDecItem) * n, hi)) return e;
     if (!c->dItems.reserve(sizeof(ZsDecItem) * n)) return ZSMI_error_memory_allocation;
     for (uint32_t i = 0; i < n; i++) { hi[i].srcOff = srcOffsets[i]; hi[i].dstOff = dstOffsets[i]; hi[i].srcSize = srcSizes[i]; hi[i].dstCap = dstCaps[i]; }
-    if (hipMemcpyAsync(c->dItems.p, hi, sizeof(ZsDecItem) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->toDevice(c->dItems.p, hi, sizeof(ZsDecItem) * n)) return e;
     return c->hItems.sent(c->stream);
 }
 
@@ -898,6 +881,19 @@ static ZsDictSel oneDictionary(const void *dBytes, uint32_t size, const ZsDDictI
     if (dBytes && size) { sel.one.bytes = (const uint8_t *)dBytes; sel.one.size = size; sel.one.img = img; sel.one.dictID = dictID; sel.anyID = img == nullptr; }
     return sel;
 }
+// dictFromBytes for decode: a dictionary given as bytes (none: the plain call) -> the selector of a call with it, anyID: not digested, the
+// general kernel's alone.  In host memory: staged first, behind the checks a host-buffer call makes in front of it (its context, an empty call)
+static int dictBytesForDecode(zsmi_ctx *c, const void *dict, size_t dictSize, DictBytes kind, uint32_t n, ZsDictSel &sel)
+{
+    sel = ZsDictSel();
+    if (kind == kDictOnHost) { if (!c) return ZSMI_error_init_missing; if (n == 0) return 0; }
+    if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
+    if (kind == kDictOnHost && dict && dictSize) {
+        if (const int e = c->bind()) return e;
+        if (const int e = stageDict(c, dict, dictSize)) return e;
+    }
+    sel = oneDictionary(dict, (uint32_t)dictSize); return 0;
+}
 // dict: which dictionary each frame of the call gets (nullptr, or a selector that holds none: the plain call).  Digested dictionaries bring the
 // images the fast kernels' dictionary forms need; a call with a dictionary's bare bytes (anyID) is the general kernel's alone.
 // The item list is in c->dItems, queued or copied there on the stream by the caller; caps: what the plan takes of the items' capacities.
@@ -920,19 +916,19 @@ static int decodeItems(zsmi_ctx *c, const void *dSrc, uint32_t n, void *dDst, co
         if (p.fast) {
             // items that are one frame of up to mb blocks: entropy decoding lane-parallel across 16 items per wavefront (decode_fast.hip); whatever
             // those kernels do not take or reject is left to the general kernel below
-            if (hipMemsetAsync(lists, 0, DecLists::kClassLists * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+            if (const int e = c->fill(lists, 0, DecLists::kClassLists * sizeof(uint32_t))) return e;
             if (useDict) launchFastDecode<true>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, sel);
             else launchFastDecode<false>(c, p, shape, src, dI, cnt, dDst, dDstSizes + i0, classes, sel);
             // the items the fast path did not finish, listed for the general kernel
             left = DecLists::leftList(lists, (size_t)p.cap * mb);
             LAUNCH(c, "k_dec_collect", k_dec_collect, dim3((cnt + 255) / 256), dim3(256), 0, &dD->fast, (uint32_t)(sizeof(ZsFastDesc) / sizeof(uint32_t)), cnt, left, leftCount);
-        } else if (hipMemsetAsync(lists, 0, (DecLists::kLeftCount + 1) * sizeof(uint32_t), c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+        } else if (const int e = c->fill(lists, 0, (DecLists::kLeftCount + 1) * sizeof(uint32_t))) return e;
         // the general kernel: a pool of wavefronts over a queue - of every item, or (behind the fast path) of the list of the items it left
         LAUNCH(c, useDict ? "k_decode_frames_dict" : "k_decode_frames", useDict ? (k_decode_frames<ZS_DEC_GROUP, true>) : (k_decode_frames<ZS_DEC_GROUP, false>),
                dim3(shape.poolWgs), dim3(64 * ZS_DEC_GROUP), 0, src, dI, cnt, (uint8_t *)dDst, dDstSizes + i0, S.poolLit(), (const uint32_t *)left,
                (const uint32_t *)leftCount, sel, DecLists::queue(lists));
     }
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
@@ -941,7 +937,7 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     if (const int e = uploadDecodeItems(c, srcOffsets, srcSizes, n, dstOffsets, dstCaps)) return e;
     CapStats caps;
     for (uint32_t i = 0; i < n; i++) caps.add(dstCaps[i]);
@@ -959,8 +955,8 @@ extern "C" int zsmi_decompressBatchDevice_usingDict(zsmi_ctx *c, const void *dSr
                                                     uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                                     const void *dDict, size_t dictSize)
 {
-    if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    const ZsDictSel sel = oneDictionary(dDict, (uint32_t)dictSize);
+    ZsDictSel sel;
+    if (const int e = dictBytesForDecode(c, dDict, dictSize, kDictOnDevice, n, sel)) return e;
     return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, &sel);
 }
 
@@ -972,44 +968,37 @@ struct zsmi_ddict {
     int device = 0;
     bool empty = false;                  // no bytes: its calls are the plain calls
     uint32_t dictID = 0, dictSize = 0;
+    ZsDictSel sel = ZsDictSel();         // what its calls pass to the kernels (none for one without bytes)
     DevBuf dBytes, dImg;
 };
 extern "C" zsmi_ddict *zsmi_createDDict(zsmi_ctx *c, const void *dict, size_t dictSize, int *err)
 {
-    int code = 0;
-    zsmi_ddict *dd = nullptr;
-    do {
-        if (!c) { code = ZSMI_error_init_missing; break; }
-        if (dictSize > 0xFFFFFFFFull) { code = ZSMI_error_dictionary_corrupted; break; }
-        dd = new (std::nothrow) zsmi_ddict();
-        if (!dd) { code = ZSMI_error_memory_allocation; break; }
-        dd->device = c->device;
-        if (!dict || dictSize == 0) { dd->empty = true; break; }
-        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if (!dd->dBytes.reserve(dictSize + 64) || !dd->dImg.reserve(sizeof(ZsDDictImage))) { code = ZSMI_error_memory_allocation; break; }
-        if (hipMemcpyAsync(dd->dBytes.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
+    return makeHandle<zsmi_ddict>(err, [&](zsmi_ddict &dd) -> int {
+        if (!c) return ZSMI_error_init_missing;
+        if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
+        dd.device = c->device;
+        if (!dict || dictSize == 0) { dd.empty = true; return 0; }
+        if (const int e = c->bind()) return e;
+        if (!dd.dBytes.reserve(dictSize + 64) || !dd.dImg.reserve(sizeof(ZsDDictImage))) return ZSMI_error_memory_allocation;
+        if (const int e = c->toDevice(dd.dBytes.p, dict, dictSize)) return e;
         ZsCompressDict d;
-        if ((code = loadDict(c, dd->dBytes.p, dictSize, d, (ZsDDictImage *)dd->dImg.p))) break;
-        dd->dictID = d.dictID; dd->dictSize = (uint32_t)dictSize;
-        if (hipGetLastError() != hipSuccess) code = ZSMI_error_GENERIC;
-    } while (0);
-    if (code) { delete dd; dd = nullptr; }
-    if (err) *err = code;
-    return dd;
+        if (const int e = loadDict(c, dd.dBytes.p, dictSize, d, (ZsDDictImage *)dd.dImg.p)) return e;
+        dd.dictID = d.dictID; dd.dictSize = (uint32_t)dictSize; dd.sel = oneDictionary(dd.dBytes.p, dd.dictSize, (const ZsDDictImage *)dd.dImg.p, dd.dictID);
+        return c->launched();
+    });
 }
 extern "C" void zsmi_freeDDict(zsmi_ddict *dd) { delete dd; }
 extern "C" unsigned zsmi_getDictID_fromDDict(const zsmi_ddict *dd) { return dd ? dd->dictID : 0; }
 extern "C" size_t zsmi_sizeofDDict(const zsmi_ddict *dd) { return dd ? dd->dBytes.cap + dd->dImg.cap : 0; }
-// What a zsmi_ddict * argument asks of a call on context c - 0, with the call's selector set: the set ({}, unnamed = dd) (one that holds no
-// dictionary: the plain call, for a null ddict or one without bytes); or the error (a dictionary digested on another device: parameter_unsupported)
-static int resolveDDict(const zsmi_ctx *c, const zsmi_ddict *dd, ZsDictSel &sel)
+// What a zsmi_ddict * or zsmi_ddictSet * argument asks of a call on context c - 0, with the call's selector set: the handle's (one that holds no
+// dictionary: the plain call, for a null handle, a ddict without bytes, an empty set); or the error (digested on another device: parameter_unsupported)
+template <class Handle> static int resolveDDict(const zsmi_ctx *c, const Handle *h, ZsDictSel &sel)
 {
     sel = ZsDictSel();
-    if (!dd) return 0;
+    if (!h) return 0;
     if (!c) return ZSMI_error_init_missing;
-    if (dd->device != c->device) return ZSMI_error_parameter_unsupported;
-    if (!dd->empty) sel = oneDictionary(dd->dBytes.p, dd->dictSize, (const ZsDDictImage *)dd->dImg.p, dd->dictID);
-    return 0;
+    if (h->device != c->device) return ZSMI_error_parameter_unsupported;
+    sel = h->sel; return 0;
 }
 extern "C" int zsmi_decompressBatchDevice_usingDDict(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
@@ -1033,59 +1022,40 @@ struct zsmi_ddictSet {
 #define ZSMI_DDICTSET_MAX 4096u
 extern "C" zsmi_ddictSet *zsmi_createDDictSet(zsmi_ctx *c, const zsmi_ddict *const *dds, uint32_t n, const zsmi_ddict *unnamed, int *err)
 {
-    int code = 0;
-    zsmi_ddictSet *set = nullptr;
-    do {
-        if (!c) { code = ZSMI_error_init_missing; break; }
-        if (n > ZSMI_DDICTSET_MAX) { code = ZSMI_error_parameter_outOfBound; break; }
-        if (n && !dds) { code = ZSMI_error_parameter_unsupported; break; }
+    return makeHandle<zsmi_ddictSet>(err, [&](zsmi_ddictSet &set) -> int {
+        if (!c) return ZSMI_error_init_missing;
+        if (n > ZSMI_DDICTSET_MAX) return ZSMI_error_parameter_outOfBound;
+        if (n && !dds) return ZSMI_error_parameter_unsupported;
         std::vector<ZsDictEntry> table(n);
-        for (uint32_t i = 0; i < n && !code; i++) {
+        for (uint32_t i = 0; i < n; i++) {
             const zsmi_ddict *dd = dds[i];
             // a member: there, of this device, formatted (raw content has no ID a frame could name: it can only be `unnamed`)
-            if (!dd || dd->device != c->device || dd->empty || dd->dictID == 0) { code = ZSMI_error_parameter_unsupported; break; }
+            if (!dd || dd->device != c->device || dd->empty || dd->dictID == 0) return ZSMI_error_parameter_unsupported;
             table[i].dictID = dd->dictID; table[i].size = dd->dictSize; table[i].img = (const ZsDDictImage *)dd->dImg.p; table[i].bytes = (const uint8_t *)dd->dBytes.p;
         }
-        if (code) break;
-        if (unnamed && unnamed->device != c->device) { code = ZSMI_error_parameter_unsupported; break; }
+        if (unnamed && unnamed->device != c->device) return ZSMI_error_parameter_unsupported;
         std::sort(table.begin(), table.end(), [](const ZsDictEntry &a, const ZsDictEntry &b) { return a.dictID < b.dictID; });
         const uint32_t unnamedID = (unnamed && !unnamed->empty) ? unnamed->dictID : 0;      // (formatted: a member under its own ID)
-        for (uint32_t i = 0; i < n && !code; i++)
-            if ((i && table[i].dictID == table[i - 1].dictID) || table[i].dictID == unnamedID) code = ZSMI_error_parameter_unsupported;
-        if (code) break;
-        set = new (std::nothrow) zsmi_ddictSet();
-        if (!set) { code = ZSMI_error_memory_allocation; break; }
-        set->device = c->device; set->members = n + (unnamedID != 0);
-        if (unnamed && !unnamed->empty) set->sel = oneDictionary(unnamed->dBytes.p, unnamed->dictSize, (const ZsDDictImage *)unnamed->dImg.p, unnamed->dictID);
-        if (n == 0) break;
-        if (hipSetDevice(c->device) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        if (!set->dTable.reserve(sizeof(ZsDictEntry) * n)) { code = ZSMI_error_memory_allocation; break; }
-        if (hipMemcpyAsync(set->dTable.p, table.data(), sizeof(ZsDictEntry) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) { code = ZSMI_error_GENERIC; break; }
-        set->sel.table = (const ZsDictEntry *)set->dTable.p; set->sel.n = n;
-    } while (0);
-    if (code) { delete set; set = nullptr; }
-    if (err) *err = code;
-    return set;
+        for (uint32_t i = 0; i < n; i++)
+            if ((i && table[i].dictID == table[i - 1].dictID) || table[i].dictID == unnamedID) return ZSMI_error_parameter_unsupported;
+        set.device = c->device; set.members = n + (unnamedID != 0);
+        if (unnamed) set.sel = unnamed->sel;
+        if (n == 0) return 0;
+        if (const int e = c->bind()) return e;
+        if (!set.dTable.reserve(sizeof(ZsDictEntry) * n)) return ZSMI_error_memory_allocation;
+        if (c->toDevice(set.dTable.p, table.data(), sizeof(ZsDictEntry) * n) || c->wait()) return ZSMI_error_GENERIC;
+        set.sel.table = (const ZsDictEntry *)set.dTable.p; set.sel.n = n;
+        return 0;
+    });
 }
 extern "C" void zsmi_freeDDictSet(zsmi_ddictSet *set) { delete set; }
 extern "C" uint32_t zsmi_sizeofDDictSetMembers(const zsmi_ddictSet *set) { return set ? set->members : 0; }
-// resolveDDict's sibling: what a zsmi_ddictSet * argument asks of a call on context c (null, or a set that holds nothing: the plain call)
-static int resolveDDictSet(const zsmi_ctx *c, const zsmi_ddictSet *set, ZsDictSel &sel)
-{
-    sel = ZsDictSel();
-    if (!set) return 0;
-    if (!c) return ZSMI_error_init_missing;
-    if (set->device != c->device) return ZSMI_error_parameter_unsupported;
-    sel = set->sel;
-    return 0;
-}
 extern "C" int zsmi_decompressBatchDevice_usingDDictSet(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                         uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                                         const zsmi_ddictSet *set)
 {
     ZsDictSel sel;
-    if (const int e = resolveDDictSet(c, set, sel)) return e;
+    if (const int e = resolveDDict(c, set, sel)) return e;
     return decompressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dstCaps, dDstSizes, &sel);
 }
 
@@ -1111,10 +1081,10 @@ extern "C" int zsmi_packFramesDevice(zsmi_ctx *c, const void *dFrames, const uin
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (!c->sSizes.reserve(sizeof(uint64_t) * n)) return ZSMI_error_memory_allocation;
-    if (hipMemcpyAsync(c->sSizes.p, dstOffsets, sizeof(uint64_t) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->toDevice(c->sSizes.p, dstOffsets, sizeof(uint64_t) * n)) return e;
     if (const int e = scanOffsets(c, "k_pack_offsets", dSizes, nullptr, n, 1u, nullptr, dPackedOffsets)) return e;
     LAUNCH(c, "k_pack_copy", k_pack_copy, dim3(n), dim3(256), 0, (const uint8_t *)dFrames, (const uint64_t *)c->sSizes.p, dSizes, (const uint64_t *)dPackedOffsets, (uint8_t *)dPacked);
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1128,9 +1098,9 @@ extern "C" int zsmi_getFrameSizesBatchDevice(zsmi_ctx *c, const void *dSrc, cons
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
     if (!dSrc || !dSrcOffsets || !dSrcSizes || !dStatus) return ZSMI_error_GENERIC;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     LAUNCH(c, "k_frame_sizes", k_frame_sizes, dim3((n + 255) / 256), dim3(256), 0, (const uint8_t *)dSrc, dSrcOffsets, dSrcSizes, n, dContentSizes, dBounds, dStatus);
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 // the packer's scan in its general form (the packer's: align 1, no status, no caps)
 extern "C" int zsmi_layoutOutputsDevice(zsmi_ctx *c, const uint64_t *dSizes, const uint32_t *dStatus, uint32_t n, uint32_t align,
@@ -1139,9 +1109,9 @@ extern "C" int zsmi_layoutOutputsDevice(zsmi_ctx *c, const uint64_t *dSizes, con
     if (!c) return ZSMI_error_init_missing;
     if (align == 0 || align > 4096 || (align & (align - 1))) return ZSMI_error_parameter_outOfBound;
     if (!dDstOffsets || (n && (!dSizes || !dDstCaps))) return ZSMI_error_GENERIC;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     if (const int e = scanOffsets(c, "k_layout_outputs", dSizes, dStatus, n, align, dDstCaps, dDstOffsets)) return e;
-    return hipGetLastError() == hipSuccess ? 0 : ZSMI_error_GENERIC;
+    return c->launched();
 }
 // The plan is the plan of n items of maxDstCap bytes: the one thing the host knows of the capacities.  Item i's result is that of the
 // host-array call with capacity min(dDstCaps[i], maxDstCap) - which kernels take an item never shows in its result.
@@ -1152,9 +1122,9 @@ extern "C" int zsmi_decompressBatchResident(zsmi_ctx *c, const void *dSrc, const
     if (!c) return ZSMI_error_init_missing;
     if (n && (!dSrc || !dSrcOffsets || !dSrcSizes || !dDst || !dDstOffsets || !dDstCaps || !dDstSizes)) return ZSMI_error_GENERIC;
     ZsDictSel sel;
-    if (const int e = resolveDDictSet(c, set, sel)) return e;
+    if (const int e = resolveDDict(c, set, sel)) return e;
     if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
     if (!c->dItems.reserve(sizeof(ZsDecItem) * n)) return ZSMI_error_memory_allocation;
     LAUNCH(c, "k_dec_items", k_dec_items, dim3((n + 255) / 256), dim3(256), 0, dSrcOffsets, dSrcSizes, dDstOffsets, dDstCaps, maxDstCap, n, (ZsDecItem *)c->dItems.p);
     CapStats caps;
@@ -1178,63 +1148,58 @@ static void spanOf(const uint64_t *off, const uint32_t *len, uint32_t n, uint64_
 __global__ void k_pack_items(const uint8_t *base, const uint64_t *offs /* [0..n): where, [n..2n): packed position */, const uint32_t *sizes, uint32_t n, uint8_t *packed)
 {
     const uint32_t i = blockIdx.x;
-    const uint32_t sz = sizes[i] > 0xFFFFFF88u ? 0 : sizes[i];
+    const uint32_t sz = zs_word_bytes(sizes[i]);
     zs_block_copy(packed + offs[n + i], base + offs[i], sz, threadIdx.x, blockDim.x);
 }
-static int copyBack(zsmi_ctx *c, const uint8_t *dBase, const uint64_t *dof, uint8_t *dst, const uint64_t *dstOffsets, const uint32_t *sizes /* host, synchronised */, uint32_t n)
+static int copyBack(zsmi_ctx *c, const uint8_t *dBase, const uint64_t *dof, uint8_t *dst, const uint64_t *dstOffsets, const uint32_t *sizes, uint32_t n)
 {
+    if (const int e = c->wait()) return e;                           // (for the sizes, whose copy the caller queued)
     struct Run { uint64_t host, dev, len; };
     std::vector<Run> runs;
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; i++) {
-        if (sizes[i] > 0xFFFFFF88u || sizes[i] == 0) continue;
+        if (zs_word_bytes(sizes[i]) == 0) continue;
         total += sizes[i];
         if (!runs.empty() && runs.back().host + runs.back().len == dstOffsets[i] && runs.back().dev + runs.back().len == dof[i]) runs.back().len += sizes[i];
         else runs.push_back({ dstOffsets[i], dof[i], sizes[i] });
     }
     if (runs.size() <= 16) {
         for (const Run &r : runs)
-            if (hipMemcpyAsync(dst + r.host, dBase + r.dev, r.len, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-        return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : ZSMI_error_GENERIC;
+            if (const int e = c->toHost(dst + r.host, dBase + r.dev, r.len)) return e;
+        return c->wait();
     }
-    if (!c->sPack.reserve(total + 64) || !c->sPackOff.reserve(sizeof(uint64_t) * 2 * n + sizeof(uint32_t) * n) || !c->hPack.reserve(std::max<uint64_t>(total, sizeof(uint64_t) * 2 * n + sizeof(uint32_t) * n))) return ZSMI_error_memory_allocation;
+    const size_t listBytes = sizeof(uint64_t) * 2 * n + sizeof(uint32_t) * n;      // (hPack may be resized: nothing is queued since the wait above)
+    if (!c->sPack.reserve(total + 64) || !c->sPackOff.reserve(listBytes) || !c->hPack.reserve(std::max<uint64_t>(total, listBytes))) return ZSMI_error_memory_allocation;
     uint64_t *ho = (uint64_t *)c->hPack.p; uint32_t *hs = (uint32_t *)(ho + 2 * n);
     uint64_t run = 0;
-    for (uint32_t i = 0; i < n; i++) { ho[i] = dof[i]; ho[n + i] = run; hs[i] = sizes[i]; run += (sizes[i] > 0xFFFFFF88u) ? 0 : sizes[i]; }
-    if (hipMemcpyAsync(c->sPackOff.p, ho, sizeof(uint64_t) * 2 * n + sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;      // hPack is reused for the payload below
+    for (uint32_t i = 0; i < n; i++) { ho[i] = dof[i]; ho[n + i] = run; hs[i] = sizes[i]; run += zs_word_bytes(sizes[i]); }
+    if (c->toDevice(c->sPackOff.p, ho, listBytes) || c->wait()) return ZSMI_error_GENERIC;      // hPack is reused for the payload below
     LAUNCH(c, "k_pack_items", k_pack_items, dim3(n), dim3(256), 0, dBase, (const uint64_t *)c->sPackOff.p, (const uint32_t *)((const uint64_t *)c->sPackOff.p + 2 * n), n, (uint8_t *)c->sPack.p);
-    if (hipMemcpyAsync(c->hPack.p, c->sPack.p, total, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (c->toHost(c->hPack.p, c->sPack.p, total) || c->wait()) return ZSMI_error_GENERIC;
     const uint8_t *hp = (const uint8_t *)c->hPack.p;
     run = 0;
     for (uint32_t i = 0; i < n; i++) {
-        if (sizes[i] > 0xFFFFFF88u) continue;
-        memcpy(dst + dstOffsets[i], hp + run, sizes[i]); run += sizes[i];
+        const uint32_t bytes = zs_word_bytes(sizes[i]);
+        memcpy(dst + dstOffsets[i], hp + run, bytes); run += bytes;
     }
     return 0;
 }
-// A host-buffer call through the context's staging buffers: the dictionary (if any) and the span of the sources go to the device, run() is
+// A host-buffer call through the context's staging buffers: the span of the sources goes to the device (a dictionary given as bytes is there already), run() is
 // the device form with the offsets rebased to the spans (dstLen[i]: the bytes item i may write), then the sizes and the results come back.
 template <class Run>
 static int staged(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, void *dst, const uint64_t *dstOffsets,
-                  const uint32_t *dstLen, uint32_t *dstSizes, const void *dict, size_t dictSize, Run run)
+                  const uint32_t *dstLen, uint32_t *dstSizes, Run run)
 {
-    if (hipSetDevice(c->device) != hipSuccess) return ZSMI_error_GENERIC;
-    if (dict) {
-        if (!c->sDict.reserve(dictSize + 64)) return ZSMI_error_memory_allocation;
-        if (hipMemcpyAsync(c->sDict.p, dict, dictSize, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    }
+    if (const int e = c->bind()) return e;
     uint64_t slo, shi, dlo, dhi;
     spanOf(srcOffsets, srcSizes, n, slo, shi);
     spanOf(dstOffsets, dstLen, n, dlo, dhi);
     if (!c->sSrc.reserve(shi - slo + 64) || !c->sDst.reserve(dhi - dlo + 64) || !c->sSizes.reserve(sizeof(uint32_t) * n)) return ZSMI_error_memory_allocation;
     std::vector<uint64_t> so(n), dof(n);
     for (uint32_t i = 0; i < n; i++) { so[i] = srcOffsets[i] - slo; dof[i] = dstOffsets[i] - dlo; }
-    if (shi > slo && hipMemcpyAsync(c->sSrc.p, (const uint8_t *)src + slo, shi - slo, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (shi > slo) if (const int e = c->toDevice(c->sSrc.p, (const uint8_t *)src + slo, shi - slo)) return e;
     if (const int rc = run(so.data(), dof.data(), (uint32_t *)c->sSizes.p)) return rc;
-    if (hipMemcpyAsync(dstSizes, c->sSizes.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return ZSMI_error_GENERIC;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return ZSMI_error_GENERIC;
+    if (const int e = c->toHost(dstSizes, c->sSizes.p, sizeof(uint32_t) * n)) return e;
     return copyBack(c, (const uint8_t *)c->sDst.p, dof.data(), (uint8_t *)dst, dstOffsets, dstSizes, n);
 }
 // dict: the call's selector, of dictionaries that are on the device already; checksum: as compressBatchDeviceImpl's
@@ -1245,7 +1210,7 @@ static int compressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *s
     if (n == 0) return 0;
     std::vector<uint32_t> bounds(n);                                 // the destination slots the call is staged with: every chunk's bound
     for (uint32_t i = 0; i < n; i++) bounds[i] = (uint32_t)zsmi_compressBound(srcSizes[i]);
-    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes, nullptr, 0,
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, bounds.data(), dstSizes,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
                       return compressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dSizes, level, dict, checksum);
                   });
@@ -1280,33 +1245,30 @@ extern "C" int zsmi_compressBatchHost_usingCDictSet(zsmi_ctx *c, const void *src
     if (const int e = resolveCDictSet(c, set, dictIndex, n, level, sel)) return e;
     return compressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstSizes, level, &sel, c->checksumFlag);
 }
-// dict / dictSize: the call's dictionary in host memory, which this call stages; or digested: the selector of digested ones (a DDict's or a
-// set's), whose bytes are on the device already
+// dict: the call's selector, of dictionaries that are on the device already (digested ones, or bytes dictBytesForDecode staged)
 static int decompressBatchHostImpl(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
-                                   uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
-                                   const void *dict, size_t dictSize, const ZsDictSel *digested = nullptr)
+                                   uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes, const ZsDictSel *dict)
 {
     if (!c) return ZSMI_error_init_missing;
     if (n == 0) return 0;
-    if (dictSize > 0xFFFFFFFFull) return ZSMI_error_dictionary_corrupted;
-    const bool useDict = !digested && dict != nullptr && dictSize != 0;
-    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, useDict ? dict : nullptr, dictSize,
+    return staged(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes,
                   [&](const uint64_t *so, const uint64_t *dof, uint32_t *dSizes) {
-                      const ZsDictSel stagedDict = oneDictionary(useDict ? c->sDict.p : nullptr, (uint32_t)dictSize);
-                      return decompressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dstCaps, dSizes, digested ? digested : &stagedDict);
+                      return decompressBatchDeviceImpl(c, c->sSrc.p, so, srcSizes, n, c->sDst.p, dof, dstCaps, dSizes, dict);
                   });
 }
 
 extern "C" int zsmi_decompressBatchHost(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                         uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes)
 {
-    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, nullptr, 0);
+    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, nullptr);
 }
 extern "C" int zsmi_decompressBatchHost_usingDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                   uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
                                                   const void *dict, size_t dictSize)
 {
-    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, dict, dictSize);
+    ZsDictSel sel;
+    if (const int e = dictBytesForDecode(c, dict, dictSize, kDictOnHost, n, sel)) return e;
+    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, &sel);
 }
 extern "C" int zsmi_decompressBatchHost_usingDDict(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                    uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
@@ -1314,15 +1276,15 @@ extern "C" int zsmi_decompressBatchHost_usingDDict(zsmi_ctx *c, const void *src,
 {
     ZsDictSel sel;
     if (const int e = resolveDDict(c, dd, sel)) return e;
-    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, nullptr, 0, &sel);
+    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, &sel);
 }
 extern "C" int zsmi_decompressBatchHost_usingDDictSet(zsmi_ctx *c, const void *src, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                                       uint32_t n, void *dst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dstSizes,
                                                       const zsmi_ddictSet *set)
 {
     ZsDictSel sel;
-    if (const int e = resolveDDictSet(c, set, sel)) return e;
-    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, nullptr, 0, &sel);
+    if (const int e = resolveDDict(c, set, sel)) return e;
+    return decompressBatchHostImpl(c, src, srcOffsets, srcSizes, n, dst, dstOffsets, dstCaps, dstSizes, &sel);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1399,7 +1361,7 @@ static size_t compressOneShot(void *dst, size_t dstCapacity, const void *src, si
     int rc = resolve(c, level, sel);
     if (!rc) rc = compressBatchHostImpl(c, src, &so, &ss, 1, out, &dof, &ds, level, &sel, checksum);
     if (rc) return ZSMI_ERR(rc);
-    if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
+    if (zs_word_is_error(ds)) return ZSMI_ERR(zs_word_code(ds));
     if (ds > dstCapacity) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
     if (out != dst) memcpy(dst, out, ds);
     return ds;
@@ -1440,36 +1402,36 @@ extern "C" size_t zsmi_decompress(void *dst, size_t dstCapacity, const void *src
     return zsmi_decompress_usingDict(dst, dstCapacity, src, srcSize, nullptr, 0);
 }
 
-// one frame (or several concatenated) through a borrowed context: with the dictionary's bytes (or none), with the digested dictionary dd, or
-// with the DDict set
-static size_t decompressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, const zsmi_ddict *dd,
-                                const zsmi_ddictSet *set = nullptr)
+// one frame (or several concatenated) through a borrowed context.  resolve(c, sel): the call's dictionary, resolved on that context as the
+// batch forms resolve theirs - its bytes (or none), a digested dictionary, a DDict set
+template <class Resolve>
+static size_t decompressOneShot(void *dst, size_t dstCapacity, const void *src, size_t srcSize, Resolve resolve)
 {
     if (srcSize > 0xFFFFFFFFull) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
     Borrowed b; zsmi_ctx *c = b.c;
     if (!c) return ZSMI_ERR(ZSMI_error_GENERIC);
     const uint64_t so = 0, dof = 0; const uint32_t ss = (uint32_t)srcSize; uint32_t ds = 0;
-    const uint32_t cap = (uint32_t)std::min<size_t>(dstCapacity, 0xFFFFFF00u);
+    const uint32_t cap = (uint32_t)std::min<size_t>(dstCapacity, ZS_ONESHOT_CAP_MAX);
     ZsDictSel sel;
-    if (const int e = set ? resolveDDictSet(c, set, sel) : resolveDDict(c, dd, sel)) return ZSMI_ERR(e);
-    const int rc = decompressBatchHostImpl(c, src, &so, &ss, 1, dst, &dof, &cap, &ds, dict, dictSize, (dd || set) ? &sel : nullptr);
+    int rc = resolve(c, sel);
+    if (!rc) rc = decompressBatchHostImpl(c, src, &so, &ss, 1, dst, &dof, &cap, &ds, &sel);
     if (rc) return ZSMI_ERR(rc);
-    if (ds > 0xFFFFFF88u) return ZSMI_ERR(0u - ds);
+    if (zs_word_is_error(ds)) return ZSMI_ERR(zs_word_code(ds));
     return ds;
 }
 extern "C" size_t zsmi_decompress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize)
 {
-    return decompressOneShot(dst, dstCapacity, src, srcSize, dict, dictSize, nullptr);
+    return decompressOneShot(dst, dstCapacity, src, srcSize, [&](zsmi_ctx *c, ZsDictSel &sel) { return dictBytesForDecode(c, dict, dictSize, kDictOnHost, 1, sel); });
 }
 // a null dd: zsmi_decompress.  (The borrowed context is one of the current device: a dictionary digested on another device is parameter_unsupported)
 extern "C" size_t zsmi_decompress_usingDDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_ddict *dd)
 {
-    return decompressOneShot(dst, dstCapacity, src, srcSize, nullptr, 0, dd);
+    return decompressOneShot(dst, dstCapacity, src, srcSize, [&](zsmi_ctx *c, ZsDictSel &sel) { return resolveDDict(c, dd, sel); });
 }
 // a null set: zsmi_decompress
 extern "C" size_t zsmi_decompress_usingDDictSet(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const zsmi_ddictSet *set)
 {
-    return decompressOneShot(dst, dstCapacity, src, srcSize, nullptr, 0, nullptr, set);
+    return decompressOneShot(dst, dstCapacity, src, srcSize, [&](zsmi_ctx *c, ZsDictSel &sel) { return resolveDDict(c, set, sel); });
 }
 
 #ifdef ZSMI_DEBUG_HOOKS

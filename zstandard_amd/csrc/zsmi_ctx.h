@@ -1,13 +1,15 @@
 // Host side that zsmi_api.hip and the feature files (seekable.hip, dict_train.hip) share: the context with its buffers (Buf; TurnBufs, the
-// pinned buffers a per-call list goes up through), the timed launch, and the batch entry points the features are built on (defined in
+// pinned buffers a per-call list goes up through) and stream verbs, the handle maker, the timed launch, and the batch entry points the features are built on (defined in
 // zsmi_api.hip) with the one thing they take about dictionaries - the compress calls a ZsCDictSel, the decompress calls a ZsDictSel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/zsmi.h"
+#include "zsmi_status.h"          // the size word the kernels leave and the host reads
 #include "zsmi_device.h"
 #include "zsmi_scratch.h"         // what the scratch buffers hold: the table Scratch is made of
 
 #include <cstring>
+#include <new>
 #include <vector>
 
 #define ZSMI_ERR(code) ((size_t)0 - (size_t)(code))
@@ -16,6 +18,8 @@
 // context
 // ---------------------------------------------------------------------------------------------
 // A buffer that grows by 1/8 + 4 KiB beyond the request; device or pinned host memory.  The context owns its buffers: they go with it.
+// Growing frees the old block first: a DEVICE buffer relies on the runtime's free waiting for the device.  Nothing else assumes it: a PINNED
+// buffer that a queued copy may still read grows only behind a wait for the stream (zsmi_ctx::idleReserve) or that copy's event (TurnBufs).
 static hipError_t devAlloc(void **p, size_t n) { return hipMalloc(p, n); }
 static hipError_t pinAlloc(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
 template <hipError_t (*Alloc)(void **, size_t), hipError_t (*Free)(void *)>
@@ -90,7 +94,7 @@ struct CompressPlan {
 
     // dict: a dictionary call; dictIndex and memberHasDict: the call's selector's (ZsCDictSel below) - chunk i uses record dictIndex[i], and
     // none for ZS_DICT_NONE or a record that memberHasDict says stands for no dictionary
-    int build(hipStream_t stream, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict,
+    int build(struct zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t *srcSizes, uint32_t n, const uint64_t *dstOffsets, bool dict,
               const uint32_t *dictIndex = nullptr, const uint8_t *memberHasDict = nullptr);
     Cut cut(uint32_t chunk0, uint32_t cap) const;                                      // the sub-batch of whole chunks from chunk0: at most cap blocks (one chunk at least)
     Units units(int kind, bool dict, uint32_t chunk0, uint32_t chunk1) const;          // kind: kUnitsPfx, kUnitsSmall, kUnitsBig
@@ -162,22 +166,59 @@ struct zsmi_ctx {
     int timing = 0;                      // 1: events around every launch; 2: only around the dominant kernels (k_lz_walk*, k_dec_execute)
     std::vector<TimedLaunch> launches;
     std::vector<hipEvent_t> eventPool;
+
+    // ---- the stream verbs: what host code says to the context's device and stream, each 0 or ZSMI_error_GENERIC (what every site returns
+    // for a runtime call that fails).  Outside them hipSetDevice, hipMemcpyAsync, hipMemsetAsync, hipStreamSynchronize and hipGetLastError
+    // stand in host code only in this file's TurnBufs::sent, zsmi_createCtx and zsmi_freeCtx, zsmi_getKernelTimes, the debug hooks,
+    // destructors, and where zsmi_openSeekable clears a failed hipMalloc ----
+    static int code(hipError_t e) { return e == hipSuccess ? 0 : ZSMI_error_GENERIC; }
+    int bind() const { return code(hipSetDevice(device)); }
+    int toDevice(void *d, const void *h, size_t n) const { return code(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, stream)); }
+    int toHost(void *h, const void *d, size_t n) const { return code(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, stream)); }
+    int onDevice(void *d, const void *s, size_t n) const { return code(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream)); }
+    int fill(void *p, int byte, size_t n) const { return code(hipMemsetAsync(p, byte, n, stream)); }
+    int wait() const { return code(hipStreamSynchronize(stream)); }
+    int launched() const { return code(hipGetLastError()); }        // the tail of a call that queued kernels: a launch that failed
+    // Idle before resize: pinned buffers that an earlier call's copy may still read are reserved (growing frees the block that copy reads)
+    // and written only behind a wait for the stream.  One wait, then every {buffer, bytes} of the list
+    int idleReserve(std::initializer_list<std::pair<PinBuf *, size_t>> wants) const
+    {
+        if (const int e = wait()) return e;
+        for (const auto &w : wants) if (!w.first->reserve(w.second)) return ZSMI_error_memory_allocation;
+        return 0;
+    }
 };
 
+// A handle: a T allocated, then filled by build(T &) -> code, which makes the creator's checks in the creator's order; on a code it is
+// deleted and null returned; the code goes to *err (may be null)
+template <class T, class Build> static T *makeHandle(int *err, Build build)
+{
+    T *h = new (std::nothrow) T();
+    const int code = h ? build(*h) : ZSMI_error_memory_allocation;
+    if (code) { delete h; h = nullptr; }
+    if (err) *err = code; return h;
+}
+
+// ---- the timed launch: events around what is queued while a Timed lives, when the context's timing asks for them.  An event that cannot
+// be made is not handed out: the launch runs untimed ----
 static hipEvent_t getEvent(zsmi_ctx *c)
 {
     if (!c->eventPool.empty()) { hipEvent_t e = c->eventPool.back(); c->eventPool.pop_back(); return e; }
-    hipEvent_t e; (void)hipEventCreate(&e); return e;
+    hipEvent_t e = nullptr;
+    return hipEventCreate(&e) == hipSuccess ? e : nullptr;
 }
 static inline bool dominantKernel(const char *name) { return strncmp(name, "k_lz_walk", 9) == 0 || strncmp(name, "k_dec_execute", 13) == 0; }
-#define LAUNCH_ON(ctx, strm, name, kernel, grid, block, lds, ...) do { \
-        TimedLaunch tl_{name, nullptr, nullptr}; \
-        const bool timed_ = (ctx)->timing == 1 || ((ctx)->timing == 2 && dominantKernel(name)); \
-        if (timed_) { tl_.a = getEvent(ctx); tl_.b = getEvent(ctx); (void)hipEventRecord(tl_.a, (strm)); } \
-        hipLaunchKernelGGL(kernel, grid, block, lds, (strm), __VA_ARGS__); \
-        if (timed_) { (void)hipEventRecord(tl_.b, (strm)); (ctx)->launches.push_back(tl_); } \
-    } while (0)
-#define LAUNCH(ctx, name, kernel, grid, block, lds, ...) LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, lds, __VA_ARGS__)
+struct Timed {
+    zsmi_ctx *c; TimedLaunch tl;
+    Timed(zsmi_ctx *c, const char *name) : c(c), tl{ name, nullptr, nullptr }
+    {
+        if (!(c->timing == 1 || (c->timing == 2 && dominantKernel(name)))) return;
+        hipEvent_t a = getEvent(c), b = getEvent(c);
+        if (a && b) { tl.a = a; tl.b = b; (void)hipEventRecord(a, c->stream); } else for (hipEvent_t e : { a, b }) if (e) c->eventPool.push_back(e);
+    }
+    ~Timed() { if (tl.b) { (void)hipEventRecord(tl.b, c->stream); c->launches.push_back(tl); } }
+};
+#define LAUNCH(ctx, name, kernel, grid, block, lds, ...) do { Timed timed_(ctx, name); hipLaunchKernelGGL(kernel, grid, block, lds, (ctx)->stream, __VA_ARGS__); } while (0)
 
 // ---- the batch calls in device memory (zsmi_api.hip: the compress and the decompress section state their arguments) ----
 // A dictionary as its loader leaves it (the launch sequence sees none of this: a record says it all).  dBytes: its bytes in device memory;
