@@ -352,8 +352,9 @@ int zsmi_decompressBatchResident(zsmi_ctx *ctx, const void *dSrc, const uint64_t
  * Device-resident compress: the head of the same chain.  Chunk boundaries that a GPU step produced - records a kernel located, the rows
  * of a tensor, the dDstSizes / dPackedOffsets of this library - go into a compress call without a trip to the host: bounds, the layout
  * of the destinations (zsmi_layoutOutputsDevice above, over the bounds) and the compress call itself only queue work on the context's
- * stream.  The dictionary forms (_usingDict, _usingCDict, _usingCDictSet), seekable compress and the dictionary trainer still plan on
- * the host, from host arrays.
+ * stream.  Dictionaries come through zsmi_compressBatchResident_usingCDictSet: a CDict set and an index a chunk in device memory (one
+ * digested dictionary: the set of one member).  What still plans on the host, from host arrays: the _usingDict forms with dictionary BYTES
+ * (their loader reads a record back and waits), seekable compress and the dictionary trainer.
  * ------------------------------------------------------------------------------------------ */
 /* dBounds[i] = zsmi_compressBound(dSrcSizes[i]) for n sizes, on the device (both arrays device memory; entries [0, n) are written).
  * zsmi_layoutOutputsDevice(ctx, dBounds, NULL, n, align, dCaps, dDstOffsets) then places the frames.  A NULL ctx: init_missing; a NULL
@@ -374,10 +375,35 @@ int zsmi_compressBoundsDevice(zsmi_ctx *ctx, const uint32_t *dSrcSizes, uint32_t
  *    plan after a resident call;
  *  - writes: entries [0, n) of dDstSizes; bytes only inside [dDstOffsets[i], + zsmi_compressBound(dSrcSizes[i])).
  * Checked on the host, in this order, before anything is queued - a NULL ctx: init_missing; a NULL dSrc, dDst, descriptor array or
- * dDstSizes with n > 0: GENERIC.  n == 0 does nothing.  No dictionary form exists (they need a third, prefixed unit list and a dictionary
- * index in device memory). */
+ * dDstSizes with n > 0: GENERIC.  n == 0 does nothing.  The dictionary form follows. */
 int zsmi_compressBatchResident(zsmi_ctx *ctx, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
                                uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level);
+/* zsmi_compressBatchResident at the set's level, chunk i with member dDictIndex[i] of `set` (DEVICE memory, n entries, as the other
+ * descriptors), or with no dictionary for ZSMI_DICT_NONE: the pipeline step that located the records picks each record's dictionary too,
+ * and nothing of it comes to the host.  The plan kernels read the choice: a third, prefixed unit list and the record index of every chunk
+ * and prefixed unit are written in device memory.
+ * The contract:
+ *  - frames: for every chunk with dSrcSizes[i] <= maxSrcSize and an index that is ZSMI_DICT_NONE or below the set's member count, frame i
+ *    and dDstSizes[i] are byte for byte those of zsmi_compressBatchDevice_usingCDictSet called with the same arrays from the host, the same
+ *    set and the context's ZSMI_c_checksumFlag (hence the _usingCDict call's frame with that member).  A chunk's frame does not depend on
+ *    its neighbours, on maxSrcSize or on how the call was cut into sub-batches;
+ *  - refusals the host cannot make: dSrcSizes[i] > maxSrcSize gives dDstSizes[i] = (uint32_t)-ZSMI_error_srcSize_wrong, as above; an index
+ *    that is neither ZSMI_DICT_NONE nor below the member count gives (uint32_t)-ZSMI_error_parameter_outOfBound; both at once:
+ *    srcSize_wrong.  Such a chunk is planned as an empty one without a dictionary: at most zsmi_compressBound(0) bytes are written at its
+ *    place, its neighbours are not affected, and no list, grid, scratch or record lookup sees its size or its index;
+ *  - dDictIndex == NULL with a set of exactly one member: every chunk uses member 0.  One CDict cd is the set {cd}, so this entry point
+ *    serves the single digested dictionary too, as zsmi_decompressBatchResident does with a DDict.  NULL with any other member count and
+ *    n > 0: GENERIC;
+ *  - set == NULL: zsmi_compressBatchResident at level 3; dDictIndex is not read;
+ *  - no host traffic: the call only queues work - no device-to-host copy, no wait, no pinned staging; the host-array calls' plan is not
+ *    touched.  The host does not know whether any chunk picks a dictionary: the prefixed-unit kernels are always launched, over a unit a
+ *    chunk, and leave on the device's live count;
+ *  - writes: entries [0, n) of dDstSizes; bytes only inside [dDstOffsets[i], + zsmi_compressBound(dSrcSizes[i])).
+ * Checked on the host, in this order, before anything is queued - a NULL ctx: init_missing; a NULL dSrc, dDst, descriptor array or
+ * dDstSizes with n > 0: GENERIC; the dDictIndex rule above; a set of another device: parameter_unsupported.  n == 0 does nothing. */
+int zsmi_compressBatchResident_usingCDictSet(zsmi_ctx *ctx, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes,
+                                             uint32_t n, uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes,
+                                             const zsmi_cdictSet *set, const uint32_t *dDictIndex);
 
 /* ------------------------------------------------------------------------------------------
  * Seekable archives (zstd's seekable format): independent frames, then a seek table in a skippable frame

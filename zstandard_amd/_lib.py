@@ -142,6 +142,7 @@ def lib():
     L.zsmi_decompressBatchResident.restype = i32; L.zsmi_decompressBatchResident.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp]
     L.zsmi_compressBoundsDevice.restype = i32; L.zsmi_compressBoundsDevice.argtypes = [vp, vp, u32, vp]
     L.zsmi_compressBatchResident.restype = i32; L.zsmi_compressBatchResident.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, i32]
+    L.zsmi_compressBatchResident_usingCDictSet.restype = i32; L.zsmi_compressBatchResident_usingCDictSet.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]
     L.zsmi_enableKernelTiming.restype = i32; L.zsmi_enableKernelTiming.argtypes = [vp, i32]
     L.zsmi_getKernelTimes.restype = i32; L.zsmi_getKernelTimes.argtypes = [vp, ctypes.POINTER(KernelTime), i32]
     L.zsmi_decodeScratchBytes.restype = sz; L.zsmi_decodeScratchBytes.argtypes = [vp]
@@ -218,4 +219,4 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",
            "zsmi_getFrameSizesBatchDevice", "zsmi_layoutOutputsDevice", "zsmi_decompressBatchResident",
-           "zsmi_compressBoundsDevice", "zsmi_compressBatchResident"]
+           "zsmi_compressBoundsDevice", "zsmi_compressBatchResident", "zsmi_compressBatchResident_usingCDictSet"]

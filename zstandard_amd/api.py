@@ -652,14 +652,28 @@ class BatchCodec:
         if rc:
             raise RuntimeError(f"zsmi_compressBoundsDevice: {_error_name(self.L, rc)}")
 
-    def compress_resident(self, d_src_ptr, d_src_offsets_ptr, d_src_sizes_ptr, n, max_src_size, d_dst_ptr, d_dst_offsets_ptr, d_dst_sizes_ptr, level=3):
+    def compress_resident(self, d_src_ptr, d_src_offsets_ptr, d_src_sizes_ptr, n, max_src_size, d_dst_ptr, d_dst_offsets_ptr, d_dst_sizes_ptr, level=3,
+                          cdict_set=None, d_dict_index_ptr=0):
         """compress_device with its three descriptor arrays in device memory; max_src_size: the call is planned for n chunks of it, and a
         chunk above it gets the size word of srcSize_wrong (72) instead of a frame.  The frames are compress_device's, byte for byte; the
-        codec's "checksum" parameter holds.  No dictionary form.  zsmi_compressBatchResident"""
-        rc = self.L.zsmi_compressBatchResident(self.ctx, ctypes.c_void_p(d_src_ptr), ctypes.c_void_p(d_src_offsets_ptr), ctypes.c_void_p(d_src_sizes_ptr), n,
-                                               max_src_size, ctypes.c_void_p(d_dst_ptr), ctypes.c_void_p(d_dst_offsets_ptr), ctypes.c_void_p(d_dst_sizes_ptr), level)
+        codec's "checksum" parameter holds.  zsmi_compressBatchResident.
+        cdict_set, d_dict_index_ptr: a CompressionDictSet, chunk i with its member d_dict_index[i] (uint32, DEVICE memory, n entries) or,
+        for NO_DICT, with none; any other index gives the chunk the size word of parameter_outOfBound (42).  The set's level holds (a
+        `level` that disagrees raises).  d_dict_index_ptr = 0 with a set of one member: every chunk uses it - one CompressionDict cd is
+        CompressionDictSet(codec, [cd], level).  zsmi_compressBatchResident_usingCDictSet"""
+        common = (self.ctx, ctypes.c_void_p(d_src_ptr), ctypes.c_void_p(d_src_offsets_ptr), ctypes.c_void_p(d_src_sizes_ptr), n,
+                  max_src_size, ctypes.c_void_p(d_dst_ptr), ctypes.c_void_p(d_dst_offsets_ptr), ctypes.c_void_p(d_dst_sizes_ptr))
+        if cdict_set is None:
+            if d_dict_index_ptr:
+                raise ValueError("d_dict_index_ptr= needs cdict_set=")
+            name, rc = "zsmi_compressBatchResident", self.L.zsmi_compressBatchResident(*common, level)
+        else:
+            if level != 3 and level != cdict_set.level:
+                raise ValueError("cdict_set= compresses at the set's level")
+            name = "zsmi_compressBatchResident_usingCDictSet"
+            rc = self.L.zsmi_compressBatchResident_usingCDictSet(*common, cdict_set.handle, ctypes.c_void_p(d_dict_index_ptr))
         if rc:
-            raise RuntimeError(f"zsmi_compressBatchResident: {_error_name(self.L, rc)}")
+            raise RuntimeError(f"{name}: {_error_name(self.L, rc)}")
 
     def seekable_bound(self, src_size, frame_size=0, checksum=True) -> int:
         return _raise_if_error(self.L, self.L.zsmi_seekableBound(src_size, frame_size, int(bool(checksum))))

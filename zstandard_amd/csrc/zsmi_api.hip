@@ -328,8 +328,8 @@ int CompressPlan::build(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t 
         whole.before[i] = nWhole; tail.before[i] = nTail;
         const uint32_t e = choice(i);
         if (kind == kDictPerChunk) dictKey[i] = e;
-        if (srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX && e != ZS_DICT_NONE) nWhole++;
-        else nTail += small.before[i + 1] - small.before[i];                 // (a chunk has at most one small unit: itself, or its last unit when that is one block)
+        const ZsChunkDictCounts dc = zs_chunk_counts_dict(srcSizes[i], e != ZS_DICT_NONE);      // the dictionary rule of zsmi_plan.h, the plan kernels' too
+        nWhole += dc.pfxUnits; nTail += dc.tailUnits;                        // (a chunk has at most one small unit: itself, or its last unit when that is one block)
     }
     whole.before[n] = nWhole; tail.before[n] = nTail;
     const size_t unitBytes = sizeof(ZsUnitDesc) * ((size_t)nWhole + nTail);
@@ -342,7 +342,7 @@ int CompressPlan::build(zsmi_ctx *c, const uint64_t *srcOffsets, const uint32_t 
     uint32_t iw = 0, it = nWhole;
     for (uint32_t i = 0; i < n; i++) {                                       // the small units are in chunk order
         const uint32_t e = choice(i);
-        const bool prefixed = srcSizes[i] && srcSizes[i] <= ZS_BLOCK_MAX && e != ZS_DICT_NONE;
+        const bool prefixed = zs_chunk_prefixed(srcSizes[i], e != ZS_DICT_NONE);
         if (kind == kDictPerChunk) { hChunkDict[i] = e; if (prefixed) hUnitDict[iw] = e; }
         for (uint32_t k = small.before[i]; k < small.before[i + 1]; k++) hu[prefixed ? iw++ : it++] = all[k];
     }
@@ -376,7 +376,7 @@ static ZsCDictEntry dictEntry(const ZsCompressDict &d, const uint32_t *dImg)
 {
     ZsCDictEntry e;
     e.pfx = std::min<uint32_t>(d.contentSize, ZS_BLOCK_MAX); e.pre = d.dBytes + d.contentOff + d.contentSize - e.pfx;
-    e.img = dImg; e.tables = d.dTables; e.dictID = d.dictID; e.pad = 0;
+    e.img = dImg; e.tables = d.dTables; e.dictID = d.dictID; e.hasDict = 1;
     for (int i = 0; i < 3; i++) e.rep[i] = d.rep[i];
     return e;
 }
@@ -413,7 +413,7 @@ static int dictFromBytes(zsmi_ctx *c, const void *dict, size_t dictSize, DictByt
 // One sub-batch of a compress call as its kernels take it, whoever planned it - the host (CompressPlan) or the device (plan_kernels.hip).
 //   dChunks: the call's chunk list; dBlocks: the block list a chunk's firstBlock counts in; block0: the sub-batch's first block there
 //   (scratch slot = block - block0); nb, units[k].n: its blocks and units - or, with `live`, the host's upper bounds of them: the grids
-//   live: null, or the device's counts of what the lists really hold (a ZsPlanCounts: blocks, small units, big units); the kernels whose
+//   live: null, or the device's counts of what the lists really hold (a ZsPlanCounts: blocks, small units, big units, prefixed units); the kernels whose
 //   index is a block or a unit leave at or beyond their count.  k_assemble_frames is indexed by chunks, which the host knows
 struct SubBatch {
     const ZsChunkDesc *dChunks; const ZsBlockDesc *dBlocks;
@@ -430,7 +430,7 @@ static void launchSubBatch(zsmi_ctx *c, const LzShape &shape, const SubBatch &sb
     const uint32_t nb = sb.nb, block0 = sb.block0;
     const ZsBlockDesc *dB = sb.dBlocks + block0;
     const CompressPlan::Units *units = sb.units;
-    const uint32_t *liveBlocks = sb.live, *liveUnits[3] = { nullptr, sb.live ? sb.live + 1 : nullptr, sb.live ? sb.live + 2 : nullptr };
+    const uint32_t *liveBlocks = sb.live, *liveUnits[3] = { sb.live ? sb.live + 3 : nullptr, sb.live ? sb.live + 1 : nullptr, sb.live ? sb.live + 2 : nullptr };
     for (int k = 0; k < 3; k++) {
         const LzKernel<CandFn> &K = shape.cand[k];
         const bool p = k == kUnitsPfx;
@@ -531,7 +531,9 @@ extern "C" int zsmi_compressBatchDevice(zsmi_ctx *c, const void *dSrc, const uin
 //   nbMax = blocks of a chunk of maxSrcSize; cap = the blocks in flight, as above, with n * nbMax for the call's blocks;
 //   sub-batches are fixed runs of K = cap / nbMax chunks - never more than cap blocks, whatever the sizes are;
 //   grids are upper bounds (K * nbMax blocks, K small units, K * ceil(nbMax / 2) big units: none when nbMax is 1), the live counts reach
-//   the kernels through SubBatch::live.  With every chunk maxSrcSize long the bounds are the counts: no workgroup is launched in vain. ----
+//   the kernels through SubBatch::live.  With every chunk maxSrcSize long the bounds are the counts: no workgroup is launched in vain.
+//   The set form (zsmi_compressBatchResident_usingCDictSet, behind the CDict sets below) takes the chunks' choice of dictionary from device
+//   memory too: the same body with a prefixed unit list of K slots in front. ----
 extern "C" int zsmi_compressBoundsDevice(zsmi_ctx *c, const uint32_t *dSrcSizes, uint32_t n, uint64_t *dBounds)
 {
     if (!c) return ZSMI_error_init_missing;
@@ -541,11 +543,21 @@ extern "C" int zsmi_compressBoundsDevice(zsmi_ctx *c, const uint32_t *dSrcSizes,
     LAUNCH(c, "k_compress_bounds", k_compress_bounds, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, dBounds);
     return c->launched();
 }
-extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
-                                          uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level)
+// What the two resident compress calls check first, in this order, before anything is queued
+static int residentCompressArgs(const zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                const void *dDst, const uint64_t *dDstOffsets, const uint32_t *dDstSizes)
 {
     if (!c) return ZSMI_error_init_missing;
-    if (n && (!dSrc || !dSrcOffsets || !dSrcSizes || !dDst || !dDstOffsets || !dDstSizes)) return ZSMI_error_GENERIC;
+    return n && (!dSrc || !dSrcOffsets || !dSrcSizes || !dDst || !dDstOffsets || !dDstSizes) ? ZSMI_error_GENERIC : 0;
+}
+// The body of both (the arguments checked).  dict: null for the plain call; a set call's records and its choice in DEVICE memory - the
+// host knows neither which chunks pick a dictionary nor whether any does, so there is no "no chunk has one: plain call" shortcut: the unit
+// slots are [prefixed: K][small: K][big: K * bigMax], the prefixed-unit kernels go over their upper bound (a unit a chunk) and leave on a
+// live count that may be 0.  Everything a sub-batch's kernels take about dictionaries is device memory the plan kernels wrote.
+struct ResidentDict { const ZsCDictEntry *dTable; uint32_t members; bool tables; const uint32_t *dDictIndex; };
+static int compressBatchResidentImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                     uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level, const ResidentDict *dict)
+{
     if (n == 0) return 0;
     if (const int e = c->bind()) return e;
     const LzShape &shape = lzShape(level);
@@ -555,32 +567,47 @@ extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const u
     zsmi_ctx::Scratch &S = c->scratch;
     if (!S.reserve(cap)) return ZSMI_error_memory_allocation;
     zsmi_ctx::ResidentPlan &R = c->resident;
-    const size_t nUnitSlots = (size_t)K + (nbMax > 1 ? (size_t)K * bigMax : 0);
+    const uint32_t pfxSlots = dict ? K : 0u;
+    const size_t nUnitSlots = (size_t)pfxSlots + K + (nbMax > 1 ? (size_t)K * bigMax : 0);
     if (!R.dChunks.reserve(sizeof(ZsChunkDesc) * n) || !R.dBefore.reserve(sizeof(ZsPlanBefore) * n) || !R.dCounts.reserve(sizeof(ZsPlanCounts) * subs) ||
         !R.dBlocks.reserve(sizeof(ZsBlockDesc) * (size_t)K * nbMax) || !R.dUnits.reserve(sizeof(ZsUnitDesc) * nUnitSlots)) return ZSMI_error_memory_allocation;
+    if (dict && (!R.dChunkDict.reserve(sizeof(uint32_t) * n) || !R.dUnitDict.reserve(sizeof(uint32_t) * K))) return ZSMI_error_memory_allocation;
     ZsChunkDesc *dChunks = (ZsChunkDesc *)R.dChunks.p;
     const ZsPlanBefore *dBefore = (const ZsPlanBefore *)R.dBefore.p;
     const ZsPlanCounts *dCounts = (const ZsPlanCounts *)R.dCounts.p;
-    ZsPlanLists lists = { (ZsBlockDesc *)R.dBlocks.p, (ZsUnitDesc *)R.dUnits.p, 0u, K };
-    LAUNCH(c, "k_plan_chunks", k_plan_chunks, dim3(subs), dim3(ZS_PLAN_THREADS), 0, dSrcOffsets, dSrcSizes, dDstOffsets, n, K, maxSrcSize,
-           dChunks, (ZsPlanBefore *)R.dBefore.p, (ZsPlanCounts *)R.dCounts.p);
+    uint32_t *dChunkDict = dict ? (uint32_t *)R.dChunkDict.p : nullptr;
+    ZsPlanLists lists = { (ZsBlockDesc *)R.dBlocks.p, (ZsUnitDesc *)R.dUnits.p, 0u, pfxSlots, pfxSlots + K, dict ? (uint32_t *)R.dUnitDict.p : nullptr };
+    if (dict)
+        LAUNCH(c, "k_plan_chunks", k_plan_chunks<true>, dim3(subs), dim3(ZS_PLAN_THREADS), 0, dSrcOffsets, dSrcSizes, dDstOffsets, n, K, maxSrcSize,
+               dChunks, (ZsPlanBefore *)R.dBefore.p, (ZsPlanCounts *)R.dCounts.p, dict->dDictIndex, dict->dTable, dict->members, dChunkDict);
+    else
+        LAUNCH(c, "k_plan_chunks", k_plan_chunks<false>, dim3(subs), dim3(ZS_PLAN_THREADS), 0, dSrcOffsets, dSrcSizes, dDstOffsets, n, K, maxSrcSize,
+               dChunks, (ZsPlanBefore *)R.dBefore.p, (ZsPlanCounts *)R.dCounts.p, (const uint32_t *)nullptr, (const ZsCDictEntry *)nullptr, 0u, (uint32_t *)nullptr);
     SubBatch sb;
     sb.dChunks = dChunks; sb.dBlocks = lists.blocks; sb.block0 = 0; sb.cap = cap; sb.assemble = nbMax > 1;
+    if (dict) { sb.dTable = dict->dTable; sb.dChunkDict = dChunkDict; sb.dUnitDict = lists.unitDict; sb.cdt = dict->tables; }
     for (uint32_t s = 0; s < subs; s++) {
         const uint32_t chunk0 = s * K, nChunks = std::min(K, n - chunk0);
         // the lists are the sub-batch's alone: every sub-batch writes them again, behind the kernels that read the one before's
         LAUNCH(c, "k_plan_blocks", k_plan_blocks, dim3((nChunks * nbMax + 255) / 256), dim3(256), 0, (const ZsChunkDesc *)dChunks + chunk0, dBefore + chunk0,
-               dCounts + s, nChunks, chunk0, lists);
+               dCounts + s, nChunks, chunk0, lists, dict ? (const uint32_t *)dChunkDict + chunk0 : nullptr);
         sb.chunk0 = chunk0; sb.nChunks = nChunks; sb.nb = nChunks * nbMax; sb.live = &dCounts[s].blocks;
-        sb.units[kUnitsPfx] = { nullptr, 0 };
+        sb.units[kUnitsPfx] = { dict ? lists.units + lists.pfxBase : nullptr, dict ? nChunks : 0u };
         sb.units[kUnitsSmall] = { lists.units + lists.smallBase, nChunks };
         sb.units[kUnitsBig] = { lists.units + lists.bigBase, nbMax > 1 ? nChunks * bigMax : 0u };
         launchSubBatch(c, shape, sb, dSrc, dDst, dDstSizes, nullptr);
     }
     closeFrames(c, dSrc, dChunks, n, dDst, dDstSizes, c->checksumFlag);
-    // last: a chunk above maxSrcSize was planned as an empty one, and its size word says so only now
-    LAUNCH(c, "k_plan_refuse", k_plan_refuse, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, maxSrcSize, zs_error_word(ZSMI_error_srcSize_wrong), dDstSizes);
+    // last: a chunk above maxSrcSize, or one whose index names no member, was planned as an empty one, and its size word says so only now
+    LAUNCH(c, "k_plan_refuse", k_plan_refuse, dim3((n + 255) / 256), dim3(256), 0, dSrcSizes, n, maxSrcSize, zs_error_word(ZSMI_error_srcSize_wrong), dDstSizes,
+           dict ? dict->dDictIndex : nullptr, dict ? dict->members : 0u, zs_error_word(ZSMI_error_parameter_outOfBound));
     return c->launched();
+}
+extern "C" int zsmi_compressBatchResident(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                          uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level)
+{
+    if (const int e = residentCompressArgs(c, dSrc, dSrcOffsets, dSrcSizes, n, dDst, dDstOffsets, dDstSizes)) return e;
+    return compressBatchResidentImpl(c, dSrc, dSrcOffsets, dSrcSizes, n, maxSrcSize, dDst, dDstOffsets, dDstSizes, level, nullptr);
 }
 // dDict: device memory.  The dictionary loader runs over it and its record (a formatted dictionary's ID, recent offsets and content
 // offset, or the refusal) is read back: the call waits for the context's stream once.  (Its tables are queued before the plan: a new layout's wait in build covers them)
@@ -706,6 +733,19 @@ extern "C" int zsmi_compressBatchDevice_usingCDictSet(zsmi_ctx *c, const void *d
     int level; ZsCDictSel sel;
     if (const int e = resolveCDictSet(c, set, dictIndex, n, level, sel)) return e;
     return compressBatchDeviceImpl(c, dSrc, srcOffsets, srcSizes, n, dDst, dstOffsets, dDstSizes, level, &sel, c->checksumFlag);
+}
+// the resident form: the choice is device memory, so what resolveCDictSet judges on the host - an index out of range, a choice that gives
+// no chunk a dictionary - is the plan kernels' to find (plan_kernels.hip).  A NULL index: every chunk uses the one member
+extern "C" int zsmi_compressBatchResident_usingCDictSet(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes,
+                                                        uint32_t n, uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes,
+                                                        const zsmi_cdictSet *set, const uint32_t *dDictIndex)
+{
+    if (const int e = residentCompressArgs(c, dSrc, dSrcOffsets, dSrcSizes, n, dDst, dDstOffsets, dDstSizes)) return e;
+    if (!set) return compressBatchResidentImpl(c, dSrc, dSrcOffsets, dSrcSizes, n, maxSrcSize, dDst, dDstOffsets, dDstSizes, 3, nullptr);
+    if (n && !dDictIndex && set->members != 1) return ZSMI_error_GENERIC;
+    if (set->device != c->device) return ZSMI_error_parameter_unsupported;
+    const ResidentDict dict = { (const ZsCDictEntry *)set->dTable.p, set->members, set->tables, dDictIndex };
+    return compressBatchResidentImpl(c, dSrc, dSrcOffsets, dSrcSizes, n, maxSrcSize, dDst, dDstOffsets, dDstSizes, set->level, &dict);
 }
 
 // ---------------------------------------------------------------------------------------------

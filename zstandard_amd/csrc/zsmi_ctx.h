@@ -116,9 +116,10 @@ struct zsmi_ctx {
         uint2 *distAsPackRecords() const { return (uint2 *)buf[kZsScratch_dist].p; }      // (lent to k_encode_sequences: zs_dist_lend_pack_records)
         bool reserve(uint32_t cap);            // cap: blocks of a sub-batch
     } scratch;
-    // the resident compress call's plan (zsmi_compressBatchResident; plan_kernels.hip writes it): per chunk of the call its ZsChunkDesc and
+    // the resident compress calls' plan (zsmi_compressBatchResident[_usingCDictSet]; plan_kernels.hip writes it): per chunk of the call its ZsChunkDesc and
     // the unit sums in front of it, per sub-batch the live counts; the block and unit lists of ONE sub-batch, which every sub-batch reuses
-    struct ResidentPlan { DevBuf dChunks, dBefore, dCounts, dBlocks, dUnits; } resident;
+    // (a set call - _usingCDictSet - besides: the record index of every chunk of the call and of every prefixed unit of the sub-batch)
+    struct ResidentPlan { DevBuf dChunks, dBefore, dCounts, dBlocks, dUnits, dChunkDict, dUnitDict; } resident;
     DevBuf dDictImg;                       // a dictionary given as bytes (dictFromBytes): the candidate-table images of its prefix and, behind them, its one-entry table (a digested dictionary holds its own)
     DevBuf dDictRec; PinBuf hDictRec;      // the dictionary loader's record (ZsDictRecord: k_dict_load writes it, loadDict in zsmi_api.hip reads it back)
     int stopAfterWalk = 0;                 // ZSMI_STOP_AFTER_WALK (debug-hooks build, tools/walk_check.py): the entropy kernels are not launched

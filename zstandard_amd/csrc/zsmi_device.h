@@ -77,11 +77,13 @@ struct ZsDictRecord {
 //   pre, pfx: the content's last <= 64 KiB, where a prefixed unit's matches may reach; img: k_lz_dict_tables' candidate-table images of it
 //   tables:   a formatted digested dictionary's entropy tables in encoder form, else null
 //   rep, dictID: the recent offsets a frame's first block starts from and the ID its header carries ({1, 4, 8} and 0 for raw content)
+//   hasDict:  1: the record stands for a dictionary; 0: an empty member of a set (all zeros) - its chunks have none.  The plan reads it
+//             (zs_chunk_prefixed, zsmi_plan.h): on the host as zsmi_cdictSet::hasDict says the same, on the device from here
 #define ZS_DICT_NONE 0xFFFFFFFFu
 struct ZsCDictTables;
 struct ZsCDictEntry {
     const uint8_t *pre; const uint32_t *img; const ZsCDictTables *tables;
-    uint32_t pfx, dictID, rep[3], pad;
+    uint32_t pfx, dictID, rep[3], hasDict;
 };
 
 // zsmi_compressBound: the most a frame of srcSize content bytes takes, header, every block raw and the content checksum included.  Stated
