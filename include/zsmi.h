@@ -134,7 +134,7 @@ int zsmi_sync(zsmi_ctx *ctx);
 /* Sticky compression parameters of a context (ZSTD_CCtx_setParameter).  A value is read on the host when a compress call is made and governs
  * the work that call queues; calls queued before keep theirs.
  *   ZSMI_c_checksumFlag (0 or 1; default 0): every frame of the compress calls on this context - zsmi_compressBatchDevice / Host, their
- *   _usingDict, _usingCDict and _usingCDictSet forms, the frames of zsmi_compressSeekableDevice - carries a Content_Checksum: the frame the call
+ *   _usingDict, _usingCDict and _usingCDictSet forms, the frames of zsmi_compressSeekableDevice and zsmi_compressSeekableFrames* - carries a Content_Checksum: the frame the call
  *   writes with 0, byte for byte, but for bit 2 of byte 4, set, and the low 32 bits of XXH64 (seed 0) of the chunk behind its last block;
  *   dstSizes[i] grows by exactly 4 (zsmi_compressBound holds them).  A chunk whose dstSizes[i] is an error code is left as it is; an empty
  *   chunk gets its checksum too.  One more kernel a call (k_frame_checksum), whose time is that of hashing the call's largest chunk; with 0 the
@@ -473,6 +473,55 @@ int zsmi_seekableReadRangesDevice(zsmi_ctx *ctx, const zsmi_seekable *sk, const 
  * range r's code.  The same checks, then dstSize_tooSmall - before anything is queued - when the clipped lengths sum to more than
  * dstCapacity.  Staged through device memory, copied back, synchronised. */
 int zsmi_seekableReadRangesHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *offsets, const uint64_t *lengths, uint32_t nRanges,
+                                void *dst, size_t dstCapacity, uint64_t *written, uint32_t *statuses);
+/* Record archives: the caller's frame boundaries, a dictionary per frame.  One frame per record (or per group the caller chooses), each
+ * compressed with the member of a CDict set the caller picks; any zstd decoder that holds the dictionaries reads the archive as concatenated
+ * frames, and a handle opened with a DDict set reads it here, decoding exactly the frames asked for.
+ * frameSizes and dictIndex are host arrays of n entries, as the batch calls'.  Frame i holds src[o_i, o_i + frameSizes[i]), o_i the running sum
+ * of the sizes; the content is their concatenation and may pass 4 GiB.  A size of 0 makes a frame of an empty chunk that no read ever decodes.
+ * Frame i and its size are byte for byte those that zsmi_compressBatchDevice (at `level`) or zsmi_compressBatchDevice_usingCDictSet (same set,
+ * same choice) gives chunk i on this context, its ZSMI_c_checksumFlag included.  Entry i of the table is {Compressed_Size, frameSizes[i]
+ * [, low 32 bits of XXH64 of chunk i]}; checksumFlag is the table's flag alone.  With frameSizes = F, F, .., rest the archive is byte for byte
+ * what zsmi_compressSeekableDevice(frameSize = F) writes: that call is the fixed-size case of this path.
+ * Dictionaries: set == NULL: the plain form at level 3 (as every _using call).  dictIndex[i]: a member's index, or ZSMI_DICT_NONE.  dictIndex ==
+ * NULL with a set of exactly one member: every frame uses member 0 - one CDict cd is the set {cd}; with any other member count and n > 0: GENERIC.
+ * Checked on the host, in this order, before anything is queued or written: a NULL ctx: init_missing; n > 0x8000000: frameIndex_tooLarge
+ * (frameSizes is not read); a NULL frameSizes with n > 0: GENERIC; any frameSizes[i] > 1 GiB: parameter_outOfBound; the dictIndex rule above;
+ * an index that is neither ZSMI_DICT_NONE nor below the member count: parameter_outOfBound; a set of another device: parameter_unsupported;
+ * dstCapacity < zsmi_seekableFramesBound(...): dstSize_tooSmall; a NULL dArchiveSize or dDst (dst), or a NULL dSrc (src) with content: GENERIC. */
+/* room the calls below need: the sum of zsmi_compressBound(frameSizes[i]) + 17 + n * (checksumFlag ? 12 : 8).  Host only, no device.  Its three
+ * checks, in the order above.  Returns the size or an error code (zsmi_isError). */
+size_t zsmi_seekableFramesBound(const uint32_t *frameSizes, uint32_t n, int checksumFlag);
+/* Device buffers.  The calls only queue work: the per-frame lists go up through pinned buffers, nothing is copied back, nothing waited for.
+ * *dArchiveSize (device memory) receives the archive's size, or (uint64_t)-code of the lowest failing frame.  The frames are compressed into
+ * context staging of the sum of their bounds, then packed into dDst.  Writes only inside [dDst, dDst + dstCapacity).  n == 0 writes the
+ * 17-byte table. */
+int zsmi_compressSeekableFramesDevice(zsmi_ctx *ctx, const void *dSrc, const uint32_t *frameSizes, uint32_t n,
+                                      void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize, int level, int checksumFlag);
+int zsmi_compressSeekableFramesDevice_usingCDictSet(zsmi_ctx *ctx, const void *dSrc, const uint32_t *frameSizes, uint32_t n,
+                                      void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize, int checksumFlag,
+                                      const zsmi_cdictSet *set, const uint32_t *dictIndex);
+/* host buffers: staged, run, copied back, synchronised; returns the archive's size or an error code */
+size_t zsmi_compressSeekableFramesHost(zsmi_ctx *ctx, void *dst, size_t dstCapacity, const void *src, const uint32_t *frameSizes, uint32_t n,
+                                       int level, int checksumFlag);
+size_t zsmi_compressSeekableFramesHost_usingCDictSet(zsmi_ctx *ctx, void *dst, size_t dstCapacity, const void *src, const uint32_t *frameSizes,
+                                       uint32_t n, int checksumFlag, const zsmi_cdictSet *set, const uint32_t *dictIndex);
+/* zsmi_openSeekable / zsmi_openSeekableDevice whose reads decode with the set's dictionaries: every frame gets the dictionary its dictID names,
+ * a frame that names none gets `unnamed` (the rule of zsmi_decompressBatchDevice_usingDDictSet); a frame that names an ID the set does not
+ * hold makes its ranges dictionary_wrong.  set == NULL: the calls without a set.  The set is borrowed: it must outlive the handle, which must
+ * outlive the work queued with it.  One DDict dd is the set ({}, unnamed = dd).
+ * Checks as the calls without a set, then a set of another device than ctx's: parameter_unsupported.  The range reads above work unchanged on
+ * such a handle; the one-shot and one-range calls (zsmi_decompressSeekable, zsmi_decompressSeekableDevice) have no dictionary form. */
+zsmi_seekable *zsmi_openSeekable_usingDDictSet(zsmi_ctx *ctx, const void *archive, size_t size, const zsmi_ddictSet *set, int *err);
+zsmi_seekable *zsmi_openSeekableDevice_usingDDictSet(zsmi_ctx *ctx, const void *dArchive, uint64_t size, const zsmi_ddictSet *set, int *err);
+/* zsmi_seekableFrameInfo from the handle's parsed table (no re-parse); index >= frames: frameIndex_tooLarge; NULL sk: GENERIC */
+int zsmi_getFrameInfo_fromSeekable(const zsmi_seekable *sk, uint32_t index, uint64_t *cOffset, uint64_t *dOffset, uint32_t *cSize, uint32_t *dSize);
+/* records by number: exactly zsmi_seekableReadRangesDevice / Host with offsets[k] = content offset of frame frameIndex[k] and lengths[k] = its
+ * Decompressed_Size - the same bytes, written[], statuses and framesDecoded.  Host checks as that call, with any frameIndex[k] >= frames:
+ * frameIndex_tooLarge (nothing queued or written) in the place of parameter_outOfBound. */
+int zsmi_seekableReadFramesDevice(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint32_t *frameIndex, uint32_t nFrames,
+                                  void *dDst, const uint64_t *dstOffsets, uint64_t *written, uint32_t *dStatus, uint32_t *framesDecoded);
+int zsmi_seekableReadFramesHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint32_t *frameIndex, uint32_t nFrames,
                                 void *dst, size_t dstCapacity, uint64_t *written, uint32_t *statuses);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);

@@ -10,7 +10,17 @@
              archive as one range through the handle; ms, GiB/s of content delivered, distinct frames decoded
 Every call is followed by a synchronisation (the seekable read waits for its stream anyway), rates are the median over --reps calls.
 The archive and the decoded content are checked once.  Prints one JSON line.
-  python tools/bench_seekable.py [--mib 1024] [--reps 10] [--frame 65536] [--ranges 4096] [--range-bytes 4096]"""
+  python tools/bench_seekable.py [--mib 1024] [--reps 10] [--frame 65536] [--ranges 4096] [--range-bytes 4096]
+--records: record archives instead (zsmi_compressSeekableFrames*, zsmi_seekableReadFramesDevice).  --mib (256) of records of --record-bytes
+(1024 and 4096: a JSON line each), json_records and binary_table interleaved, one 64 KiB dictionary per class trained (zsmi_trainFromBuffer) on
+a disjoint part, both through a CDict set of two.  One process, the legs of a comparison in turn, three rounds:
+  size:   archive bytes over content for (a) 64 KiB fixed frames without a dictionary, (b) a frame per record without one, (c) a frame per
+          record with the dictionaries
+  write:  (c) against zsmi_compressBatchDevice_usingCDictSet + zsmi_packFramesDevice on the same chunks; the difference is the hash, table
+          and packing work, reported in ms beside the rates, with the kernels' own times of one call
+  fetch:  --ranges seeded random records in ONE zsmi_seekableReadFramesDevice call on (c) against the same records' byte ranges in one
+          zsmi_seekableReadRangesDevice call on (a): ms, frames decoded x frame bytes, content bytes delivered
+  python tools/bench_seekable.py --records [--mib 256] [--record-bytes 1024 4096] [--ranges 4096]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,15 +38,140 @@ def timed(fn, sync, reps):
     return float(np.median(ts))
 
 
+def _json_segment(job):
+    import _corpus as C
+    return C.json_records(job[1], seed=job[0])
+
+
+def records_content(size, workers=16, seg=1 << 20):
+    """size bytes of each of the two record classes, and 8 MiB of each from other seeds to train on.  The JSON generator is Python: it
+    runs as independent segments on a pool of processes, started by fork - before the GPU is touched"""
+    import multiprocessing as mp
+    import _corpus as C
+    nseg, ntrain = (size + seg - 1) // seg, 8
+    with mp.get_context("fork").Pool(workers) as pool:
+        parts = pool.map(_json_segment, [(11 + 1000 * k, seg) for k in range(nseg + ntrain)], chunksize=1)
+    js, js_train = b"".join(parts[:nseg])[:size], b"".join(parts[nseg:])
+    return {"json_records": (js, js_train), "binary_table": (C.binary_table(size, seed=14), C.binary_table(ntrain * seg, seed=15))}
+
+
+def alternating(legs, sync, reps):
+    """legs: name -> fn.  One warm-up each, then `reps` rounds, the legs in turn in every round -> name -> the sorted times"""
+    for fn in legs.values():
+        fn(); sync()
+    ts = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t = time.perf_counter(); fn(); sync(); ts[k].append(time.perf_counter() - t)
+    return {k: sorted(v) for k, v in ts.items()}
+
+
+def records(a):
+    """--records: one frame per record against 64 KiB fixed frames, on records of two classes interleaved (see the module's docstring)"""
+    from zstandard_amd import CompressionDict, CompressionDictSet, DecompressionDict, DecompressionDictSet, train_dictionary
+    size, level, reps, N = (a.mib or 256) << 20, a.level, 3, a.ranges
+    classes = ("json_records", "binary_table")
+    corp = records_content(size // 2)
+    bc = BatchCodec(0)
+    L = bc.L
+    med = lambda v: float(np.median(v))
+    for R in a.record_bytes:
+        n = size // R // 2 * 2
+        rows = [np.frombuffer(corp[c][0], dtype=np.uint8)[:n // 2 * R].reshape(-1, R) for c in classes]
+        data = np.stack(rows, axis=1).reshape(-1)                              # record i: class i % 2
+        total = data.size
+        dics = [train_dictionary((corp[c][1], np.full(len(corp[c][1]) // R, R)), capacity=65536, level=level) for c in classes]
+        cds = [CompressionDict(bc, d, level) for d in dics]
+        cset = CompressionDictSet(bc, cds, level)
+        dds = [DecompressionDict(bc, d) for d in dics]
+        dset = DecompressionDictSet(bc, dds)
+        src = torch.from_numpy(data).cuda()
+        fs = np.full(n, R, dtype=np.uint32)
+        index = (np.arange(n) % 2).astype(np.uint32)
+        bound_c = bc.seekable_frames_bound(fs, True)
+        bound_a = bc.seekable_bound(total, 65536, True)
+        arcs = {k: torch.empty(b, dtype=torch.uint8, device="cuda") for k, b in (("a", bound_a), ("b", bound_c), ("c", bound_c))}
+        asz = torch.zeros(1, dtype=torch.int64, device="cuda")
+        # the batch call and the packer on the same chunks, at the layout the archive's staging has
+        so = np.arange(n, dtype=np.uint64) * R
+        do = np.arange(n, dtype=np.uint64) * int(L.zsmi_compressBound(R))
+        stage = torch.empty(n * int(L.zsmi_compressBound(R)), dtype=torch.uint8, device="cuda")
+        bsz = torch.zeros(n, dtype=torch.int32, device="cuda")
+        packed = torch.empty(bound_c, dtype=torch.uint8, device="cuda")
+        poff = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+
+        def size_of(fn):
+            fn(); bc.sync()
+            v = int(asz.item())
+            assert 0 < v < (1 << 62), "a frame failed"
+            return v
+        size_a = size_of(lambda: bc.compress_seekable_device(src.data_ptr(), total, arcs["a"].data_ptr(), bound_a, asz.data_ptr(), level, 65536, True))
+        size_b = size_of(lambda: bc.compress_seekable_frames_device(src.data_ptr(), fs, arcs["b"].data_ptr(), bound_c, asz.data_ptr(), level, True))
+        write_c = lambda: bc.compress_seekable_frames_device(src.data_ptr(), fs, arcs["c"].data_ptr(), bound_c, asz.data_ptr(), checksum=True, cdict_set=cset, dict_index=index)
+        size_c = size_of(write_c)
+
+        def batch_pack():
+            bc.compress_device(src.data_ptr(), so, fs, stage.data_ptr(), do, bsz.data_ptr(), cdict_set=cset, dict_index=index)
+            bc.pack_device(stage.data_ptr(), do, bsz.data_ptr(), n, packed.data_ptr(), poff.data_ptr())
+        tw = alternating({"archive": write_c, "batch_pack": batch_pack}, bc.sync, reps)
+        frames_bytes = int(poff[n].item())
+        assert frames_bytes == size_c - 17 - 12 * n and torch.equal(packed[:frames_bytes], arcs["c"][:frames_bytes]), "the archive's frames differ from the batch call's"
+        bc.enable_timing(True); write_c(); kt = bc.kernel_times(); bc.enable_timing(False)
+        # fetch: N seeded random records - by number from (c), as byte ranges from (a)
+        pick = np.random.default_rng(7).integers(0, n, N).astype(np.uint32)
+        place = np.arange(N, dtype=np.uint64) * R
+        out = torch.zeros(N * R, dtype=torch.uint8, device="cuda")
+        st = torch.ones(N, dtype=torch.int32, device="cuda")
+        want = src.reshape(n, R)[torch.from_numpy(pick.astype(np.int64)).cuda()].reshape(-1)
+        ha = bc.open_seekable_device(arcs["a"].data_ptr(), size_a)
+        hc = bc.open_seekable_device(arcs["c"].data_ptr(), size_c, ddict_set=dset)
+        decoded = {}
+
+        def fetch_c():
+            decoded["c"] = hc.read_frames_device(pick, out.data_ptr(), place, st.data_ptr())[1]
+
+        def fetch_a():
+            decoded["a"] = ha.read_ranges_device(pick.astype(np.uint64) * R, np.full(N, R, dtype=np.uint64), out.data_ptr(), place, st.data_ptr())[1]
+        for f in (fetch_a, fetch_c):
+            out.zero_(); st.fill_(1); f(); bc.sync()
+            assert not st.any().item() and torch.equal(out, want), "fetched records differ from the content"
+        tf = alternating({"records_c": fetch_c, "ranges_a": fetch_a}, bc.sync, reps)
+        gib = total / float(1 << 30)
+        ms = lambda k: round(kt.get(k, (0.0, 0))[0] * 1e3, 4)
+        print(json.dumps({
+            "metric": "seekable_records", "mib": total >> 20, "record_bytes": R, "records": n, "level": level, "classes": classes,
+            "size_over_content": {"a_64k_frames_no_dict": round(size_a / total, 4), "b_frame_per_record_no_dict": round(size_b / total, 4),
+                                  "c_frame_per_record_dicts": round(size_c / total, 4)},
+            "write_c_gibs": round(gib / med(tw["archive"]), 2), "write_c_ms": [round(t * 1e3, 3) for t in tw["archive"]],
+            "batch_pack_gibs": round(gib / med(tw["batch_pack"]), 2), "batch_pack_ms": [round(t * 1e3, 3) for t in tw["batch_pack"]],
+            "write_c_minus_batch_pack_ms": round((med(tw["archive"]) - med(tw["batch_pack"])) * 1e3, 3),
+            "k_seek_hash_ms": ms("k_seek_hash"), "k_seek_table_ms": ms("k_seek_table"), "k_pack_copy_ms": ms("k_pack_copy"), "k_pack_offsets_ms": ms("k_pack_offsets"),
+            "fetch_records": N, "fetch_delivered_bytes": N * R,
+            "fetch_c_ms": [round(t * 1e3, 4) for t in tf["records_c"]], "fetch_c_frames_decoded": decoded["c"], "fetch_c_decoded_bytes": decoded["c"] * R,
+            "fetch_a_ms": [round(t * 1e3, 4) for t in tf["ranges_a"]], "fetch_a_frames_decoded": decoded["a"], "fetch_a_decoded_bytes": decoded["a"] * 65536,
+            "small_frame_packer_leg": "not tried"}), flush=True)
+        ha.close(); hc.close(); cset.close(); dset.close()
+        for x in cds + dds:
+            x.close()
+        del src, arcs, stage, packed, out
+    bc.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mib", type=int, default=1024)
+    ap.add_argument("--mib", type=int, default=0, help="content: 1024 MiB, or 256 MiB with --records")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--frame", type=int, default=65536)
     ap.add_argument("--level", type=int, default=3)
     ap.add_argument("--ranges", type=int, default=4096)
     ap.add_argument("--range-bytes", type=int, default=4096)
+    ap.add_argument("--records", action="store_true", help="record archives: one frame per record with dictionaries against 64 KiB fixed frames")
+    ap.add_argument("--record-bytes", type=int, nargs="+", default=[1024, 4096])
     a = ap.parse_args()
+    if a.records:
+        return records(a)
+    a.mib = a.mib or 1024
     size, F, level = a.mib << 20, a.frame, a.level
     gib = size / float(1 << 30)
     data = D.zipf_log(size)

@@ -6,7 +6,9 @@ only this count shows it (ELF-class frames did so for two rounds).  Rows "ddict 
 (zsmi_createDDict): own CDict frames with a trained dictionary, own frames with a raw-content one, libzstd's with the trained one.  Rows
 "ddict set ..." are mixed batches through a DecompressionDictSet (zsmi_createDDictSet): own CDict frames of three trained dictionaries,
 interleaved, and a committed libzstd frame of a fourth - every frame decoded with the dictionary it names.  Rows "cdict set -> ddict set ..."
-are such batches compressed in one call through a CompressionDictSet (zsmi_createCDictSet) first.  Row "checksum ..." is own frames written
+are such batches compressed in one call through a CompressionDictSet (zsmi_createCDictSet) first.  Rows "record archive -> ddict set ..." are such
+batches written as a record archive (zsmi_compressSeekableFrames*) and read by frame number through a handle opened with the DDict set: the
+dictionary frames of a read take the fast kernels.  Row "checksum ..." is own frames written
 with the context's checksum parameter on (zsmi_setParameter): the fast path verifies their Content_Checksum itself.
 Prints one JSON object: shape -> [items on the fast path, items]."""
 import os; os.environ["ZSMI_DEBUG_LIB"] = "1"
@@ -122,6 +124,24 @@ def main():
         named = sum((f[4] & 3) != 0 for f in frames)
         assert named == int((index != NO_DICT).sum()), (named, "frames name a dictionary")
         run("cdict set -> ddict set, own frames of %d KiB: 3 trained dictionaries and no dictionary interleaved, one call each way" % (cs >> 10), chunks, frames=frames, dset=dset)
+    # a record archive: one frame a record, the dictionaries chosen as above, written in one call (zsmi_compressSeekableFramesHost_usingCDictSet)
+    # and read by frame number through a handle opened with the DDict set - every frame its own range, so one decode call holds them all
+    for cs, n in ((1024, 256), (4096, 64)):
+        chunks = [datas[i % 3][(i // 3) * cs:(i // 3 + 1) * cs] for i in range(n)]
+        index = np.array([NO_DICT if i % 4 == 3 else i % 3 for i in range(n)], dtype=np.uint32)
+        arc = bc.compress_seekable_frames_host(b"".join(chunks), [cs] * n, cdict_set=cset, dict_index=index)
+        err = ctypes.c_int(0)
+        sk = Z.zsmi_openSeekable_usingDDictSet(bc.ctx, arc, len(arc), dset.handle, ctypes.byref(err)); assert sk, err.value
+        idx = np.arange(n, dtype=np.uint32)
+        out = np.zeros(n * cs, dtype=np.uint8); written = np.zeros(n, dtype=np.uint64); codes = np.ones(n, dtype=np.uint32)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = Z.zsmi_seekableReadFramesHost(bc.ctx, sk, p(idx), n, p(out), out.nbytes, p(written), p(codes)); assert rc == 0, rc
+        Z.zsmi_closeSeekable(sk)
+        ok = not codes.any() and out.tobytes() == b"".join(chunks)
+        buf = np.zeros(n * DESC_WORDS, dtype=np.uint32)
+        rc = Z.zsmi_dbg_copyScratch(bc.ctx, b"fastDesc", p(buf), ctypes.c_size_t(buf.nbytes)); assert rc == 0, rc
+        res["record archive -> ddict set, records of %d KiB: 3 trained dictionaries and no dictionary interleaved, read by frame number" % (cs >> 10)] = \
+            [int((buf.reshape(-1, DESC_WORDS)[:n, FAST_AT] == 1).sum()) if ok else -1, n]
     cset.close()
     dset.close()
     for x in cds + dds:

@@ -164,6 +164,19 @@ def lib():
     L.zsmi_sizeofSeekable.restype = sz; L.zsmi_sizeofSeekable.argtypes = [vp]
     L.zsmi_seekableReadRangesDevice.restype = i32; L.zsmi_seekableReadRangesDevice.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, ctypes.POINTER(u32)]
     L.zsmi_seekableReadRangesHost.restype = i32; L.zsmi_seekableReadRangesHost.argtypes = [vp, vp, vp, vp, u32, vp, sz, vp, vp]
+    L.zsmi_seekableFramesBound.restype = sz; L.zsmi_seekableFramesBound.argtypes = [vp, u32, i32]
+    L.zsmi_compressSeekableFramesDevice.restype = i32; L.zsmi_compressSeekableFramesDevice.argtypes = [vp, vp, vp, u32, vp, u64, vp, i32, i32]
+    L.zsmi_compressSeekableFramesDevice_usingCDictSet.restype = i32
+    L.zsmi_compressSeekableFramesDevice_usingCDictSet.argtypes = [vp, vp, vp, u32, vp, u64, vp, i32, vp, vp]
+    L.zsmi_compressSeekableFramesHost.restype = sz; L.zsmi_compressSeekableFramesHost.argtypes = [vp, vp, sz, vp, vp, u32, i32, i32]
+    L.zsmi_compressSeekableFramesHost_usingCDictSet.restype = sz
+    L.zsmi_compressSeekableFramesHost_usingCDictSet.argtypes = [vp, vp, sz, vp, vp, u32, i32, vp, vp]
+    L.zsmi_openSeekable_usingDDictSet.restype = vp; L.zsmi_openSeekable_usingDDictSet.argtypes = [vp, vp, sz, vp, ctypes.POINTER(i32)]
+    L.zsmi_openSeekableDevice_usingDDictSet.restype = vp; L.zsmi_openSeekableDevice_usingDDictSet.argtypes = [vp, vp, u64, vp, ctypes.POINTER(i32)]
+    L.zsmi_getFrameInfo_fromSeekable.restype = i32
+    L.zsmi_getFrameInfo_fromSeekable.argtypes = [vp, u32, pu64, pu64, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.zsmi_seekableReadFramesDevice.restype = i32; L.zsmi_seekableReadFramesDevice.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, ctypes.POINTER(u32)]
+    L.zsmi_seekableReadFramesHost.restype = i32; L.zsmi_seekableReadFramesHost.argtypes = [vp, vp, vp, u32, vp, sz, vp, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -215,6 +228,10 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_seekableNumFrames", "zsmi_seekableContentSize", "zsmi_seekableFrameInfo",
            "zsmi_openSeekable", "zsmi_openSeekableDevice", "zsmi_closeSeekable", "zsmi_getNumFrames_fromSeekable", "zsmi_getContentSize_fromSeekable",
            "zsmi_sizeofSeekable", "zsmi_seekableReadRangesDevice", "zsmi_seekableReadRangesHost",
+           "zsmi_seekableFramesBound", "zsmi_compressSeekableFramesDevice", "zsmi_compressSeekableFramesDevice_usingCDictSet",
+           "zsmi_compressSeekableFramesHost", "zsmi_compressSeekableFramesHost_usingCDictSet",
+           "zsmi_openSeekable_usingDDictSet", "zsmi_openSeekableDevice_usingDDictSet", "zsmi_getFrameInfo_fromSeekable",
+           "zsmi_seekableReadFramesDevice", "zsmi_seekableReadFramesHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

@@ -6,8 +6,10 @@
                       like Util.java:32-40.
   ZstdCompressor      the compressor the reference lacks (north_star), same calling conventions.
   SeekableArchive     random access into a seekable archive (zstd's seekable format: independent frames + a seek table), made by
-                      ZstdCompressor.compress_seekable or BatchCodec.compress_seekable_device.
-  SeekableHandle      an archive in device memory opened once (zsmi_openSeekableDevice): batches of range reads, every frame decoded once.
+                      ZstdCompressor.compress_seekable or BatchCodec.compress_seekable_device - or a record archive (the caller's frame
+                      sizes, a dictionary per frame: BatchCodec.compress_seekable_frames_*), read with ddict_set= / ddict= by frame number.
+  SeekableHandle      an archive in device memory opened once (zsmi_openSeekableDevice): batches of range reads, every frame decoded once;
+                      with a DecompressionDictSet a record archive's reader (read_frames_device).
   BatchCodec          the batch hot path on device memory (torch tensors are only a handle to device memory here).
   CompressionDict     a digested dictionary (zsmi_createCDict): parsed and laid out on the device once, used by many calls; with a
                       formatted dictionary its entropy tables code the first block of a frame where that is smaller.
@@ -33,6 +35,7 @@ ERROR_MAX_CODE = 120            # ZSMI_error_maxCode (include/zsmi.h)
 ERROR_MAX = (1 << 32) - ERROR_MAX_CODE      # ZStdErrors.cs:95-98 : IsError(c) = c > (uint)-120; csrc/zsmi_status.h states it for the library
 ERROR_PARAMETER_UNSUPPORTED = 40            # ZSMI_error_parameter_unsupported
 ERROR_PARAMETER_OUT_OF_BOUND = 42           # ZSMI_error_parameter_outOfBound
+ERROR_FRAME_INDEX_TOO_LARGE = 100           # ZSMI_error_frameIndex_tooLarge
 
 
 def _raise_if_error(L, r):
@@ -164,7 +167,16 @@ class CompressionDict:
     def device_bytes(self) -> int:
         return int(self.L.zsmi_sizeofCDict(self.handle))
 
+    def as_set(self, codec):
+        """the set {self} (made once, kept and closed with the dictionary): what a call that takes sets alone is given for cdict="""
+        if getattr(self, "_set", None) is None:
+            self._set = CompressionDictSet(codec, [self], level=self.level)
+        return self._set
+
     def close(self):
+        if getattr(self, "_set", None) is not None:
+            self._set.close()
+            self._set = None
         if self.handle:
             self.L.zsmi_freeCDict(self.handle)
             self.handle = None
@@ -326,9 +338,14 @@ class SeekableArchive:
     archive (zsmi_openSeekable: the frames go to device memory once, at the first call; close() frees them), every frame the batch
     touches decoded once."""
 
-    def __init__(self, archive):
+    def __init__(self, archive, ddict=None, ddict_set=None):
+        """ddict_set: a DecompressionDictSet the batch reads (read_many, read_frames) decode with - a record archive's dictionaries; ddict:
+        one DecompressionDict instead, the set ({}, unnamed=ddict).  Either must stay open as long as this object; read() takes none."""
+        if ddict is not None and ddict_set is not None:
+            raise ValueError("ddict_set= excludes ddict=")
         self.L = _lib.lib()
-        self.codec = self.handle = None
+        self.codec = self.handle = self._own_set = None
+        self.ddict, self.ddict_set = ddict, ddict_set
         self.archive = bytes(archive)
         self.num_frames = _raise_if_error(self.L, self.L.zsmi_seekableNumFrames(self.archive, len(self.archive)))
         self.content_size = _raise_if_error(self.L, self.L.zsmi_seekableContentSize(self.archive, len(self.archive)))
@@ -337,6 +354,9 @@ class SeekableArchive:
         if self.handle:
             self.L.zsmi_closeSeekable(self.handle)
             self.handle = None
+        if self._own_set is not None:
+            self._own_set.close()
+            self._own_set = None
         if self.codec is not None:
             self.codec.close()
             self.codec = None
@@ -347,17 +367,57 @@ class SeekableArchive:
         except Exception:
             pass
 
+    def _open(self):
+        if self.handle is not None:
+            return
+        self.codec = self.codec or BatchCodec()
+        dset = self.ddict_set
+        if self.ddict is not None:
+            if self._own_set is None:
+                self._own_set = DecompressionDictSet(self.codec, [], unnamed=self.ddict)
+            dset = self._own_set
+        err = ctypes.c_int(0)
+        self.handle = self.L.zsmi_openSeekable_usingDDictSet(self.codec.ctx, self.archive, len(self.archive), dset.handle if dset is not None else None,
+                                                             ctypes.byref(err))
+        if not self.handle:
+            self.handle = None
+            raise RuntimeError(_error_name(self.L, err.value))
+
+    def _results(self, out, written, codes, n, what, return_codes):
+        codes = [int(c) for c in codes[:n]]
+        if not return_codes:
+            for r, c in enumerate(codes):
+                if c:
+                    raise RuntimeError(f"{_error_name(self.L, c)} ({what} {r})")
+        ends = np.cumsum(written[:n]).astype(np.int64)
+        res = [out[int(e) - int(w):int(e)].tobytes() for e, w in zip(ends, written[:n])]
+        return (res, codes) if return_codes else res
+
+    def read_frames(self, indices, return_codes=False):
+        """records by number: the list of the contents of the frames `indices` name, one call for all of them (zsmi_seekableReadFramesHost);
+        every frame is decoded once, however often it is named.  Errors and return_codes as read_many; an index that is no frame's raises
+        RuntimeError (frameIndex_tooLarge) before anything is read."""
+        self._open()
+        idx = [int(i) + self.num_frames if int(i) < 0 else int(i) for i in indices]
+        idx = np.array([i if 0 <= i <= 0xFFFFFFFF else 0xFFFFFFFF for i in idx], dtype=np.uint32)
+        n = len(idx)
+        if n and int(idx.max()) >= self.num_frames:
+            raise RuntimeError(_error_name(self.L, ERROR_FRAME_INDEX_TOO_LARGE))                     # frameIndex_tooLarge (before the capacity is worked out)
+        cap = int(sum(self.frame_info(int(i))[3] for i in idx))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        written = np.zeros(max(n, 1), dtype=np.uint64); codes = np.zeros(max(n, 1), dtype=np.uint32)
+        p = BatchCodec._p
+        rc = self.L.zsmi_seekableReadFramesHost(self.codec.ctx, self.handle, p(idx), n, p(out), cap, p(written), p(codes))
+        if rc:
+            raise RuntimeError(_error_name(self.L, rc))
+        return self._results(out, written, codes, n, "frame", return_codes)
+
     def read_many(self, ranges, return_codes=False):
         """ranges: (offset, length) pairs -> the list of their bytes (each clipped at the content's end), one call for all of them
         (zsmi_seekableReadRangesHost).  A failing range raises RuntimeError with the error's name and the range's index; with
         return_codes=True nothing raises for a range and the result is (list, codes): codes[r] is 0 or range r's error code, whose
         bytes are then unspecified."""
-        if self.handle is None:
-            self.codec = self.codec or BatchCodec()
-            err = ctypes.c_int(0)
-            self.handle = self.L.zsmi_openSeekable(self.codec.ctx, self.archive, len(self.archive), ctypes.byref(err))
-            if not self.handle:
-                raise RuntimeError(_error_name(self.L, err.value))
+        self._open()
         ranges = list(ranges)
         n = len(ranges)
         off = np.array([r[0] for r in ranges], dtype=np.uint64); ln = np.array([r[1] for r in ranges], dtype=np.uint64)
@@ -370,14 +430,7 @@ class SeekableArchive:
         rc = self.L.zsmi_seekableReadRangesHost(self.codec.ctx, self.handle, p(off), p(ln), n, p(out), cap, p(written), p(codes))
         if rc:
             raise RuntimeError(_error_name(self.L, rc))
-        codes = [int(c) for c in codes[:n]]
-        if not return_codes:
-            for r, c in enumerate(codes):
-                if c:
-                    raise RuntimeError(f"{_error_name(self.L, c)} (range {r})")
-        ends = np.cumsum(written[:n]).astype(np.int64)
-        res = [out[int(e) - int(w):int(e)].tobytes() for e, w in zip(ends, written[:n])]
-        return (res, codes) if return_codes else res
+        return self._results(out, written, codes, n, "range", return_codes)
 
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`"""
@@ -385,8 +438,11 @@ class SeekableArchive:
         if index < 0:
             index += self.num_frames
         index = index if 0 <= index <= 0xFFFFFFFF else 0xFFFFFFFF          # (out of range either way: frameIndex_tooLarge)
-        rc = self.L.zsmi_seekableFrameInfo(self.archive, len(self.archive), index, ctypes.byref(co),
-                                           ctypes.byref(do), ctypes.byref(cs), ctypes.byref(ds))
+        if self.handle is not None:                                          # (an opened archive: its parsed table, no re-parse)
+            rc = self.L.zsmi_getFrameInfo_fromSeekable(self.handle, index, ctypes.byref(co), ctypes.byref(do), ctypes.byref(cs), ctypes.byref(ds))
+        else:
+            rc = self.L.zsmi_seekableFrameInfo(self.archive, len(self.archive), index, ctypes.byref(co),
+                                               ctypes.byref(do), ctypes.byref(cs), ctypes.byref(ds))
         if rc:
             raise RuntimeError(_error_name(self.L, rc))
         return co.value, do.value, cs.value, ds.value
@@ -451,10 +507,16 @@ class SeekableHandle:
     """An opened seekable archive in device memory (zsmi_openSeekableDevice; BatchCodec.open_seekable_device makes it).  Read-only: any
     BatchCodec of the same device may read through it.  It must stay open until the work queued with it is done (BatchCodec.sync)."""
 
-    def __init__(self, codec, d_ptr, size):
+    def __init__(self, codec, d_ptr, size, ddict=None, ddict_set=None):
+        if ddict is not None and ddict_set is not None:
+            raise ValueError("ddict_set= excludes ddict=")
         self.L, self.codec = codec.L, codec
+        self.ddict, self.ddict_set = ddict, ddict_set                       # (kept alive with the handle)
+        self._own_set = DecompressionDictSet(codec, [], unnamed=ddict) if ddict is not None else None
+        dset = self._own_set if ddict is not None else ddict_set
         err = ctypes.c_int(0)
-        self.handle = self.L.zsmi_openSeekableDevice(codec.ctx, ctypes.c_void_p(d_ptr), size, ctypes.byref(err))
+        self.handle = self.L.zsmi_openSeekableDevice_usingDDictSet(codec.ctx, ctypes.c_void_p(d_ptr), size, dset.handle if dset is not None else None,
+                                                                   ctypes.byref(err))
         if not self.handle:
             raise RuntimeError(f"zsmi_openSeekableDevice: {_error_name(self.L, err.value)}")
 
@@ -486,10 +548,39 @@ class SeekableHandle:
             raise RuntimeError(f"zsmi_seekableReadRangesDevice: {_error_name(self.L, rc)}")
         return written, frames.value
 
+    def read_frames_device(self, indices, d_dst_ptr, dst_offsets, d_status_ptr, codec=None):
+        """records by number: the content of frame indices[k] to d_dst + dst_offsets[k], for every k in one call (asynchronous, as
+        read_ranges_device: zsmi_seekableReadFramesDevice); d_status_ptr: device uint32[n].  Returns (written: the frames' content
+        sizes, frames_decoded)."""
+        codec = codec or self.codec
+        idx = np.ascontiguousarray(indices, dtype=np.uint32); do = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        written = np.zeros(len(idx), dtype=np.uint64)
+        frames = ctypes.c_uint32(0)
+        p = BatchCodec._p
+        rc = self.L.zsmi_seekableReadFramesDevice(codec.ctx, self.handle, p(idx), len(idx), ctypes.c_void_p(d_dst_ptr), p(do), p(written),
+                                                  ctypes.c_void_p(d_status_ptr), ctypes.byref(frames))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableReadFramesDevice: {_error_name(self.L, rc)}")
+        return written, frames.value
+
+    def frame_info(self, index):
+        """(compressed offset, content offset, compressed size, content size) of frame `index`, from the handle's table"""
+        co, do, cs, ds = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+        if index < 0:
+            index += self.num_frames
+        index = index if 0 <= index <= 0xFFFFFFFF else 0xFFFFFFFF          # (out of range either way: frameIndex_tooLarge)
+        rc = self.L.zsmi_getFrameInfo_fromSeekable(self.handle, index, ctypes.byref(co), ctypes.byref(do), ctypes.byref(cs), ctypes.byref(ds))
+        if rc:
+            raise RuntimeError(_error_name(self.L, rc))
+        return co.value, do.value, cs.value, ds.value
+
     def close(self):
         if self.handle:
             self.L.zsmi_closeSeekable(self.handle)
             self.handle = None
+        if getattr(self, "_own_set", None) is not None:
+            self._own_set.close()
+            self._own_set = None
 
     def __del__(self):
         try:
@@ -698,10 +789,58 @@ class BatchCodec:
             raise RuntimeError(f"zsmi_decompressSeekableDevice: {_error_name(self.L, rc)}")
         return written.value
 
-    def open_seekable_device(self, d_ptr, size):
+    def _frames_form(self, name, level, cdict, cdict_set, dict_index, n):
+        """the C function of a record-archive compress call and its arguments behind checksumFlag: a CompressionDictSet with the frames'
+        choice, or a CompressionDict as the set of one (a null choice: every frame uses it); else the plain form at `level`"""
+        if cdict is not None and cdict_set is not None:
+            raise ValueError("cdict_set= excludes cdict=")
+        if cdict is not None:
+            if dict_index is not None:
+                raise ValueError("dict_index= needs cdict_set=")
+            return name + "_usingCDictSet", (), (cdict.as_set(self).handle, None)
+        if cdict_set is not None:
+            di = self._dict_index(dict_index, n)
+            return name + "_usingCDictSet", (), (cdict_set.handle, self._p(di) if di is not None else None)
+        if dict_index is not None:
+            raise ValueError("dict_index= needs cdict_set=")
+        return name, (level,), ()
+
+    def seekable_frames_bound(self, frame_sizes, checksum=True) -> int:
+        """room a record archive of these frame sizes needs (zsmi_seekableFramesBound)"""
+        fs = np.ascontiguousarray(frame_sizes, dtype=np.uint32)
+        return _raise_if_error(self.L, self.L.zsmi_seekableFramesBound(self._p(fs) if len(fs) else None, len(fs), int(bool(checksum))))
+
+    def compress_seekable_frames_device(self, d_src_ptr, frame_sizes, d_dst_ptr, dst_capacity, d_archive_size_ptr, level=3, checksum=True, cdict=None,
+                                        cdict_set=None, dict_index=None):
+        """a record archive at d_dst (asynchronous): frame i holds the next frame_sizes[i] bytes of d_src, compressed with member
+        dict_index[i] of cdict_set (NO_DICT: none), with cdict, or plainly at `level`; *d_archive_size_ptr (device uint64) receives
+        its size, or (uint64)-code of the lowest failing frame.  dst_capacity must be at least seekable_frames_bound(frame_sizes, checksum).
+        checksum is the table's flag; the frames carry a Content_Checksum when the codec's "checksum" parameter is set."""
+        fs = np.ascontiguousarray(frame_sizes, dtype=np.uint32)
+        name, head, tail = self._frames_form("zsmi_compressSeekableFramesDevice", level, cdict, cdict_set, dict_index, len(fs))
+        rc = getattr(self.L, name)(self.ctx, ctypes.c_void_p(d_src_ptr), self._p(fs) if len(fs) else None, len(fs), ctypes.c_void_p(d_dst_ptr), dst_capacity,
+                                   ctypes.c_void_p(d_archive_size_ptr), *head, int(bool(checksum)), *tail)
+        if rc:
+            raise RuntimeError(f"{name}: {_error_name(self.L, rc)}")
+
+    def compress_seekable_frames_host(self, src, frame_sizes, level=3, checksum=True, cdict=None, cdict_set=None, dict_index=None) -> bytes:
+        """the record archive of `src` (host bytes) cut at frame_sizes, as compress_seekable_frames_device makes it: staged, run, copied back"""
+        s, sn = _buf(src)
+        fs = np.ascontiguousarray(frame_sizes, dtype=np.uint32)
+        if int(fs.sum(dtype=np.uint64)) != sn:
+            raise ValueError("frame_sizes must add up to len(src)")
+        cap = self.seekable_frames_bound(fs, checksum)
+        out = np.empty(cap, dtype=np.uint8)
+        name, head, tail = self._frames_form("zsmi_compressSeekableFramesHost", level, cdict, cdict_set, dict_index, len(fs))
+        r = _raise_if_error(self.L, getattr(self.L, name)(self.ctx, self._p(out), cap, s, self._p(fs) if len(fs) else None, len(fs), *head,
+                                                          int(bool(checksum)), *tail))
+        return out[:r].tobytes()
+
+    def open_seekable_device(self, d_ptr, size, ddict=None, ddict_set=None):
         """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The
-        table is read back and checked here, once (RuntimeError with the error's name)."""
-        return SeekableHandle(self, d_ptr, size)
+        table is read back and checked here, once (RuntimeError with the error's name).  ddict_set: a DecompressionDictSet its reads
+        decode with (a record archive's dictionaries); ddict: one DecompressionDict instead.  Either must outlive the handle."""
+        return SeekableHandle(self, d_ptr, size, ddict=ddict, ddict_set=ddict_set)
 
     def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b"", cdict=None, cdict_set=None, dict_index=None):
         """returns (arena uint8, dst_offsets uint64, dst_sizes uint32).  dictionary: one for every chunk (raw content or a formatted

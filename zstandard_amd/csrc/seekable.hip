@@ -4,18 +4,21 @@
 //   seek table = 0x184D2A5E | Frame_Size | entry_0 .. entry_{n-1} | Number_Of_Frames | Seek_Table_Descriptor | 0x8F92EAB1   (little-endian)
 //   entry      = Compressed_Size | Decompressed_Size [| Checksum: low 32 bits of XXH64 (seed 0) of the frame's content, when descriptor bit 7]
 //
-// Compress: the frames are the chunks of one zsmi_compressBatchDevice call (chunk i = src[i F, min((i + 1) F, size))) into context staging at
-// compressBound(F) spacing; k_seek_hash hashes the INPUT of each frame (checksum flag), the pack kernels close the gaps into dDst, k_seek_table
-// writes the table behind them and the archive's size (or the first failing frame's code).
+// Compress: the frames are the chunks of one batch compress call - chunk i = src[o_i, o_i + frameSizes[i]), o the running sum of the caller's
+// sizes (a record archive: zsmi_compressSeekableFrames*, each frame with the dictionary the caller picks from a CDict set) or of F, F, .., rest
+// (zsmi_compressSeekable*: the fixed-size case of the same path) - into context staging at the running sum of compressBound(frameSizes[i]);
+// k_seek_hash hashes the INPUT of each frame (checksum flag), the pack kernels close the gaps into dDst, k_seek_table writes the table behind
+// them and the archive's size (or the first failing frame's code).
 // Decompress: the table is read and checked on the host - once for an opened archive (zsmi_seekable), per call by the single-range calls.  A
 // read is a batch of ranges: the union of the frames they overlap are items of the batch decoder with their exact Decompressed_Size as
 // capacity, each decoded once - a frame wholly inside the one range that touches it straight into dDst, every other one into context scratch,
 // from where k_seek_gather copies its overlaps with the ranges - then k_seek_verify checks every decoded frame's size and checksum against
-// its entry and k_seek_range_status gives each range the code of its first failing frame.
+// its entry and k_seek_range_status gives each range the code of its first failing frame.  A handle opened with a DDict set decodes every
+// frame with the dictionary its dictID names (a record archive's reader); a read by frame index is the read of those frames' extents.
 
 #include "zsmi_status.h"          // the size word a compressed or decoded frame leaves
 #include "zsmi_wave.h"            // zs_block_copy, xxh64_quad, rd32
-#include "entropy_kernels.hip"    // k_pack_offsets
+#include "entropy_kernels.hip"    // k_pack_offsets, k_pack_copy
 #include "decode_kernels.hip"     // the decoder's error codes (E_*)
 #include "zsmi_ctx.h"
 #include <algorithm>
@@ -29,29 +32,23 @@ static const uint32_t kSeekHashAhead = 16;           // stripes a lane has in fl
 // ---- kernels ----
 __device__ __forceinline__ void seek_st32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 
-// XXH64 of each frame's input: one quad a frame (16 a wavefront), kSeekHashAhead stripes a lane in flight.  At 64 KiB frames 1 GiB is 16384
-// quads - one wavefront a SIMD - so the loads of one lane, not the number of wavefronts, are what hides the memory latency.
-__global__ void __launch_bounds__(64) k_seek_hash(const uint8_t *__restrict__ src, uint64_t srcSize, uint64_t frameSize, uint32_t n, uint32_t *__restrict__ hashes)
+// XXH64 of each frame's input (frame f: src[contentOff[f], + frameSizes[f])): one quad a frame (16 a wavefront), kSeekHashAhead stripes a lane
+// in flight.  At 64 KiB frames 1 GiB is 16384 quads - one wavefront a SIMD - so the loads of one lane, not the number of wavefronts, are what
+// hides the memory latency.
+__global__ void __launch_bounds__(64) k_seek_hash(const uint8_t *__restrict__ src, const uint64_t *__restrict__ contentOff, const uint32_t *__restrict__ frameSizes, uint32_t n,
+                                                  uint32_t *__restrict__ hashes)
 {
     const uint32_t q = blockIdx.x * 16 + (threadIdx.x >> 2);
     const bool real = q < n;
     const uint32_t f = real ? q : n - 1u;
-    const uint64_t off = (uint64_t)f * frameSize;
-    const uint64_t len = real ? min(frameSize, srcSize - off) : 0ull;
-    const uint64_t h = xxh64_quad<kSeekHashAhead>(src + off, len);      // (every lane of a quad calls: its four accumulators)
+    const uint64_t len = real ? frameSizes[f] : 0ull;
+    const uint64_t h = xxh64_quad<kSeekHashAhead>(src + contentOff[f], len);      // (every lane of a quad calls: its four accumulators)
     if (real && (threadIdx.x & 3u) == 0) hashes[f] = (uint32_t)h;
-}
-// frame i from staging (at i * stride) to its packed place; a failed frame (an error code for its size) moves nothing
-__global__ void k_seek_pack(const uint8_t *__restrict__ stage, uint64_t stride, const uint32_t *__restrict__ sizes, const uint64_t *__restrict__ packedOffsets, uint8_t *__restrict__ dst)
-{
-    const uint32_t i = blockIdx.x;
-    const uint32_t sz = zs_word_bytes(sizes[i]);
-    zs_block_copy(dst + packedOffsets[i], stage + (uint64_t)i * stride, sz, threadIdx.x, blockDim.x);
 }
 // the table behind the packed frames: one entry a thread, the header and the footer from the first; a failed frame's (index << 8 | code) goes to
 // *err (set to ~0 before), the lowest wins
-__global__ void k_seek_table(const uint32_t *__restrict__ sizes, const uint64_t *__restrict__ packedOffsets, const uint32_t *__restrict__ hashes, uint64_t srcSize,
-                             uint64_t frameSize, uint32_t n, int checksum, uint8_t *__restrict__ dst, unsigned long long *err)
+__global__ void k_seek_table(const uint32_t *__restrict__ sizes, const uint64_t *__restrict__ packedOffsets, const uint32_t *__restrict__ hashes,
+                             const uint32_t *__restrict__ frameSizes, uint32_t n, int checksum, uint8_t *__restrict__ dst, unsigned long long *err)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, E = checksum ? 12u : 8u;
     uint8_t *t = dst + packedOffsets[n];
@@ -64,8 +61,7 @@ __global__ void k_seek_table(const uint32_t *__restrict__ sizes, const uint64_t 
     const uint32_t s = sizes[i];
     if (zs_word_is_error(s)) atomicMin(err, ((unsigned long long)i << 8) | zs_word_code(s));
     uint8_t *e = t + 8 + (uint64_t)i * E;
-    const uint64_t off = (uint64_t)i * frameSize;
-    seek_st32(e, zs_word_bytes(s)); seek_st32(e + 4, (uint32_t)min(frameSize, srcSize - off));
+    seek_st32(e, zs_word_bytes(s)); seek_st32(e + 4, frameSizes[i]);
     if (checksum) seek_st32(e + 8, hashes[i]);
 }
 __global__ void k_seek_finish(const uint64_t *__restrict__ packedOffsets, uint32_t n, uint32_t entryBytes, const unsigned long long *__restrict__ err, uint64_t *archiveSize)
@@ -159,6 +155,24 @@ extern "C" size_t zsmi_seekableBound(unsigned long long srcSize, uint32_t frameS
     if (const int e = seekParams(srcSize, frameSize, F, n)) return ZSMI_ERR(e);
     return seekBound(srcSize, F, n, checksumFlag);
 }
+// the caller's frame sizes (a record archive): the three checks in the header's order, and the room the frames and the table need
+static int seekFramesBound(const uint32_t *frameSizes, uint32_t n, int checksum, uint64_t &bound)
+{
+    if (n > kSeekMaxFrames) return ZSMI_error_frameIndex_tooLarge;
+    if (n && !frameSizes) return ZSMI_error_GENERIC;
+    bound = kSeekTableFixed + (uint64_t)n * (checksum ? 12 : 8);
+    for (uint32_t i = 0; i < n; i++) {
+        if (frameSizes[i] > kSeekMaxFrameSize) return ZSMI_error_parameter_outOfBound;
+        bound += zsmi_compressBound(frameSizes[i]);
+    }
+    return 0;
+}
+extern "C" size_t zsmi_seekableFramesBound(const uint32_t *frameSizes, uint32_t n, int checksumFlag)
+{
+    uint64_t bound;
+    if (const int e = seekFramesBound(frameSizes, n, checksumFlag, bound)) return ZSMI_ERR(e);
+    return bound;
+}
 
 struct SeekTable {
     uint32_t n = 0, entry = 8; bool checksum = false;
@@ -228,6 +242,50 @@ extern "C" int zsmi_seekableFrameInfo(const void *src, size_t srcSize, uint32_t 
 // ---- compress ----
 // checksumFlag: the table's (each entry carries its frame's hash); frameChecksum: the frames' own Content_Checksum (the context's
 // ZSMI_c_checksumFlag) - the two are independent
+// The one path of every compress call here, its arguments checked by the caller: frame i is chunk i of one batch compress call with the
+// selector `dict` (null: plain, at `level`), chunk i = dSrc[o_i, o_i + frameSizes[i]) with o the running sum of frameSizes (host, n entries).
+//   The per-frame lists the device needs - the frames' staging offsets (the running sum of their bounds) and their sizes - go up through
+// pinned buffers taken in turn (TurnBufs), as a read's lists do: nothing is copied back, nothing waited for.  The frames' content offsets,
+// which only k_seek_hash reads, are scanOffsets over the uploaded sizes.
+static int seekCompressFrames(zsmi_ctx *c, const void *dSrc, const uint32_t *frameSizes, uint32_t n, void *dDst, uint64_t *dArchiveSize,
+                              int level, const ZsCDictSel *dict, int checksumFlag, int frameChecksum)
+{
+    if (const int e = c->bind()) return e;
+    const uint32_t E = checksumFlag ? 12u : 8u;
+    // device words: the uploaded lists - staging offsets [n] (64 bits), frame sizes [n]; (8-aligned) packed offsets [n + 1], content offsets
+    // [n + 1], the error word; compressed sizes [n], hashes [n]
+    const size_t listBytes = (size_t)n * (sizeof(uint64_t) + sizeof(uint32_t)), lists = (listBytes + 7) & ~(size_t)7;
+    if (!c->seek.dMeta.reserve(lists + (2 * (size_t)n + 3) * sizeof(uint64_t) + 2 * (size_t)n * sizeof(uint32_t))) return ZSMI_error_memory_allocation;
+    const uint64_t *dStageOff = (const uint64_t *)c->seek.dMeta.p;
+    const uint32_t *dFrameSizes = (const uint32_t *)(dStageOff + n);
+    uint64_t *dPacked = (uint64_t *)((uint8_t *)c->seek.dMeta.p + lists), *dContent = dPacked + n + 1;
+    unsigned long long *dErr = (unsigned long long *)(dContent + n + 1);
+    uint32_t *dSizes = (uint32_t *)(dErr + 1), *dHash = dSizes + n;
+    if (n) {
+        uint64_t *hStageOff;
+        if (const int e = c->seek.hLists.take(listBytes, hStageOff)) return e;
+        std::vector<uint64_t> so(n);
+        uint64_t content = 0, stage = 0;
+        for (uint32_t i = 0; i < n; i++) { so[i] = content; content += frameSizes[i]; hStageOff[i] = stage; stage += zsmi_compressBound(frameSizes[i]); }
+        memcpy(hStageOff + n, frameSizes, (size_t)n * sizeof(uint32_t));
+        if (!c->seek.dStage.reserve(stage)) return ZSMI_error_memory_allocation;
+        if (const int e = c->toDevice(c->seek.dMeta.p, hStageOff, listBytes)) return e;
+        if (const int e = c->seek.hLists.sent(c->stream)) return e;
+        if (const int e = compressBatchDeviceImpl(c, dSrc, so.data(), frameSizes, n, c->seek.dStage.p, hStageOff, dSizes, level, dict, frameChecksum)) return e;
+        if (checksumFlag) {
+            if (const int e = scanOffsets(c, "k_pack_offsets", dFrameSizes, nullptr, n, 1u, nullptr, dContent)) return e;
+            LAUNCH(c, "k_seek_hash", k_seek_hash, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, (const uint64_t *)dContent, dFrameSizes, n, dHash);
+        }
+    }
+    if (const int e = scanOffsets(c, "k_pack_offsets", (const uint32_t *)dSizes, nullptr, n, 1u, nullptr, dPacked)) return e;
+    if (n) LAUNCH(c, "k_pack_copy", k_pack_copy, dim3(n), dim3(256), 0, (const uint8_t *)c->seek.dStage.p, dStageOff, (const uint32_t *)dSizes, (const uint64_t *)dPacked, (uint8_t *)dDst);
+    if (const int e = c->fill(dErr, 0xFF, sizeof(*dErr))) return e;
+    LAUNCH(c, "k_seek_table", k_seek_table, dim3(std::max<uint32_t>(1, (n + 255) / 256)), dim3(256), 0, (const uint32_t *)dSizes, (const uint64_t *)dPacked,
+           (const uint32_t *)dHash, dFrameSizes, n, checksumFlag ? 1 : 0, (uint8_t *)dDst, dErr);
+    LAUNCH(c, "k_seek_finish", k_seek_finish, dim3(1), dim3(1), 0, (const uint64_t *)dPacked, n, E, (const unsigned long long *)dErr, dArchiveSize);
+    return c->launched();
+}
+// fixed-size frames: the sizes F, F, .., rest - the fixed-size case of the path above
 static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize,
                                 int level, uint32_t frameSize, int checksumFlag, int frameChecksum)
 {
@@ -236,30 +294,67 @@ static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize,
     if (const int e = seekParams(srcSize, frameSize, F, n64)) return e;
     if (dstCapacity < seekBound(srcSize, F, n64, checksumFlag)) return ZSMI_error_dstSize_tooSmall;
     if (!dArchiveSize || !dDst || (srcSize && !dSrc)) return ZSMI_error_GENERIC;
-    if (const int e = c->bind()) return e;
-    const uint32_t n = (uint32_t)n64, E = checksumFlag ? 12u : 8u;
-    const uint64_t stride = zsmi_compressBound(F);
-    // per-frame words: sizes [n], hashes [n], then (8-aligned) packed offsets [n + 1] and the error word
-    const size_t words = 2 * (size_t)n * sizeof(uint32_t);
-    if (!c->seek.dMeta.reserve(words + ((size_t)n + 2) * sizeof(uint64_t))) return ZSMI_error_memory_allocation;
-    uint32_t *dSizes = (uint32_t *)c->seek.dMeta.p, *dHash = dSizes + n;
-    uint64_t *dPacked = (uint64_t *)((uint8_t *)c->seek.dMeta.p + words);
-    unsigned long long *dErr = (unsigned long long *)(dPacked + n + 1);
-    if (n) {
-        if (!c->seek.dStage.reserve((n - 1) * stride + zsmi_compressBound(srcSize - (n64 - 1) * F))) return ZSMI_error_memory_allocation;
-        std::vector<uint64_t> so(n), dof(n);
-        std::vector<uint32_t> ss(n);
-        for (uint32_t i = 0; i < n; i++) { so[i] = (uint64_t)i * F; ss[i] = (uint32_t)std::min<uint64_t>(F, srcSize - so[i]); dof[i] = (uint64_t)i * stride; }
-        if (const int e = compressBatchDeviceImpl(c, dSrc, so.data(), ss.data(), n, c->seek.dStage.p, dof.data(), dSizes, level, nullptr, frameChecksum)) return e;
-        if (checksumFlag) LAUNCH(c, "k_seek_hash", k_seek_hash, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, srcSize, F, n, dHash);
-    }
-    if (const int e = scanOffsets(c, "k_pack_offsets", (const uint32_t *)dSizes, nullptr, n, 1u, nullptr, dPacked)) return e;
-    if (n) LAUNCH(c, "k_seek_pack", k_seek_pack, dim3(n), dim3(256), 0, (const uint8_t *)c->seek.dStage.p, stride, (const uint32_t *)dSizes, (const uint64_t *)dPacked, (uint8_t *)dDst);
-    if (const int e = c->fill(dErr, 0xFF, sizeof(*dErr))) return e;
-    LAUNCH(c, "k_seek_table", k_seek_table, dim3(std::max<uint32_t>(1, (n + 255) / 256)), dim3(256), 0, (const uint32_t *)dSizes, (const uint64_t *)dPacked,
-           (const uint32_t *)dHash, srcSize, F, n, checksumFlag ? 1 : 0, (uint8_t *)dDst, dErr);
-    LAUNCH(c, "k_seek_finish", k_seek_finish, dim3(1), dim3(1), 0, (const uint64_t *)dPacked, n, E, (const unsigned long long *)dErr, dArchiveSize);
-    return c->launched();
+    std::vector<uint32_t> sizes((size_t)n64, (uint32_t)F);
+    if (n64) sizes.back() = (uint32_t)(srcSize - (n64 - 1) * F);
+    return seekCompressFrames(c, dSrc, sizes.data(), (uint32_t)n64, dDst, dArchiveSize, level, nullptr, checksumFlag, frameChecksum);
+}
+// the caller's frames: the header's checks in its order, then the path above.  set: null for the plain form (sel without a table)
+static int compressSeekableFramesImpl(zsmi_ctx *c, const void *dSrc, const uint32_t *frameSizes, uint32_t n, void *dDst, uint64_t dstCapacity,
+                                      uint64_t *dArchiveSize, int level, int checksumFlag, const zsmi_cdictSet *set, const uint32_t *dictIndex)
+{
+    if (!c) return ZSMI_error_init_missing;
+    uint64_t bound;
+    if (const int e = seekFramesBound(frameSizes, n, checksumFlag, bound)) return e;
+    ZsCDictSel sel;
+    if (set) { if (const int e = resolveCDictSet(c, set, dictIndex, n, level, sel, true)) return e; }
+    if (dstCapacity < bound) return ZSMI_error_dstSize_tooSmall;
+    bool content = false;
+    for (uint32_t i = 0; i < n && !content; i++) content = frameSizes[i] != 0;
+    if (!dArchiveSize || !dDst || (content && !dSrc)) return ZSMI_error_GENERIC;
+    return seekCompressFrames(c, dSrc, frameSizes, n, dDst, dArchiveSize, level, &sel, checksumFlag, c->checksumFlag);
+}
+extern "C" int zsmi_compressSeekableFramesDevice(zsmi_ctx *c, const void *dSrc, const uint32_t *frameSizes, uint32_t n, void *dDst, uint64_t dstCapacity,
+                                                 uint64_t *dArchiveSize, int level, int checksumFlag)
+{
+    return compressSeekableFramesImpl(c, dSrc, frameSizes, n, dDst, dstCapacity, dArchiveSize, level, checksumFlag, nullptr, nullptr);
+}
+extern "C" int zsmi_compressSeekableFramesDevice_usingCDictSet(zsmi_ctx *c, const void *dSrc, const uint32_t *frameSizes, uint32_t n, void *dDst, uint64_t dstCapacity,
+                                                               uint64_t *dArchiveSize, int checksumFlag, const zsmi_cdictSet *set, const uint32_t *dictIndex)
+{
+    return compressSeekableFramesImpl(c, dSrc, frameSizes, n, dDst, dstCapacity, dArchiveSize, 3, checksumFlag, set, dictIndex);
+}
+// host buffers: the device call's checks on the host's arguments, then staged, run, copied back and waited for
+static size_t compressSeekableFramesHost(zsmi_ctx *c, void *dst, size_t dstCapacity, const void *src, const uint32_t *frameSizes, uint32_t n,
+                                         int level, int checksumFlag, const zsmi_cdictSet *set, const uint32_t *dictIndex)
+{
+    if (!c) return ZSMI_ERR(ZSMI_error_init_missing);
+    uint64_t bound;
+    if (const int e = seekFramesBound(frameSizes, n, checksumFlag, bound)) return ZSMI_ERR(e);
+    ZsCDictSel sel;
+    if (set) { if (const int e = resolveCDictSet(c, set, dictIndex, n, level, sel, true)) return ZSMI_ERR(e); }
+    if (dstCapacity < bound) return ZSMI_ERR(ZSMI_error_dstSize_tooSmall);
+    uint64_t srcSize = 0;
+    for (uint32_t i = 0; i < n; i++) srcSize += frameSizes[i];
+    if (!dst || (srcSize && !src)) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (const int e = c->bind()) return ZSMI_ERR(e);
+    if (!c->sSrc.reserve(srcSize + 64) || !c->sDst.reserve(bound + 64) || !c->sSizes.reserve(sizeof(uint64_t))) return ZSMI_ERR(ZSMI_error_memory_allocation);
+    if (srcSize) if (const int e = c->toDevice(c->sSrc.p, src, srcSize)) return ZSMI_ERR(e);
+    if (const int rc = seekCompressFrames(c, c->sSrc.p, frameSizes, n, c->sDst.p, (uint64_t *)c->sSizes.p, level, &sel, checksumFlag, c->checksumFlag)) { (void)c->wait(); return ZSMI_ERR(rc); }
+    uint64_t size = 0;
+    if (c->toHost(&size, c->sSizes.p, sizeof size) || c->wait()) return ZSMI_ERR(ZSMI_error_GENERIC);
+    if (zsmi_isError(size)) return size;
+    if (c->toHost(dst, c->sDst.p, size) || c->wait()) return ZSMI_ERR(ZSMI_error_GENERIC);
+    return size;
+}
+extern "C" size_t zsmi_compressSeekableFramesHost(zsmi_ctx *c, void *dst, size_t dstCapacity, const void *src, const uint32_t *frameSizes, uint32_t n,
+                                                  int level, int checksumFlag)
+{
+    return compressSeekableFramesHost(c, dst, dstCapacity, src, frameSizes, n, level, checksumFlag, nullptr, nullptr);
+}
+extern "C" size_t zsmi_compressSeekableFramesHost_usingCDictSet(zsmi_ctx *c, void *dst, size_t dstCapacity, const void *src, const uint32_t *frameSizes,
+                                                                uint32_t n, int checksumFlag, const zsmi_cdictSet *set, const uint32_t *dictIndex)
+{
+    return compressSeekableFramesHost(c, dst, dstCapacity, src, frameSizes, n, 3, checksumFlag, set, dictIndex);
 }
 extern "C" int zsmi_compressSeekableDevice(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, void *dDst, uint64_t dstCapacity,
                                            uint64_t *dArchiveSize, int level, uint32_t frameSize, int checksumFlag)
@@ -319,7 +414,7 @@ static int seekParseDevice(zsmi_ctx *c, const uint8_t *src, uint64_t srcSize, Se
 // item list does (uploadDecodeItems): nothing here waits for the stream.
 struct SeekRange { uint64_t a, b, to; };
 static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrames, uint64_t base, const SeekRange *rg, uint32_t nRanges,
-                          uint8_t *dDst, uint32_t *dStatus, uint32_t *framesDecoded)
+                          uint8_t *dDst, uint32_t *dStatus, uint32_t *framesDecoded, const ZsDictSel *dict = nullptr)
 {
     if (framesDecoded) *framesDecoded = 0;
     if (nRanges == 0) return 0;
@@ -412,9 +507,9 @@ static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrame
     if (const int e = c->toDevice(dLists, hi, listBytes)) return e;
     if (const int e = c->seek.hLists.sent(c->stream)) return e;
     if (nOwned)
-        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), nOwned, dDst, dof.data(), caps.data(), dSt, nullptr)) return e;
+        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data(), ss.data(), nOwned, dDst, dof.data(), caps.data(), dSt, dict)) return e;
     if (m > nOwned) {
-        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data() + nOwned, ss.data() + nOwned, m - nOwned, dS, dof.data() + nOwned, caps.data() + nOwned, dSt + nOwned, nullptr)) return e;
+        if (const int e = decompressBatchDeviceImpl(c, dFrames, so.data() + nOwned, ss.data() + nOwned, m - nOwned, dS, dof.data() + nOwned, caps.data() + nOwned, dSt + nOwned, dict)) return e;
         if (nPieces) LAUNCH(c, "k_seek_gather", k_seek_gather, dim3((uint32_t)((small.size() + 3) / 4 + tiles.size())), dim3(256), 0, (const uint8_t *)dS, dDst, dPieces,
                             (uint32_t)small.size(), (uint32_t)nPieces);
     }
@@ -430,6 +525,7 @@ struct zsmi_seekable {
     SeekTable t;
     const uint8_t *dFrames = nullptr;    // frame i's compressed bytes: dFrames + t.cOff[i]
     void *dOwned = nullptr;              // a host archive's frames (exactly their bytes + 64: no reserve slack on what may be GiBs)
+    ZsDictSel sel = ZsDictSel();         // a handle opened with a DDict set: the set's selector (borrowed: the set outlives the handle); else none
     ~zsmi_seekable() { if (dOwned) (void)hipFree(dOwned); }
 };
 extern "C" zsmi_seekable *zsmi_openSeekable(zsmi_ctx *c, const void *archive, size_t size, int *err)
@@ -457,7 +553,35 @@ extern "C" zsmi_seekable *zsmi_openSeekableDevice(zsmi_ctx *c, const void *dArch
         return 0;
     });
 }
+// the open calls with a DDict set: the call without one - its checks, in its order - then the set's own check; the handle keeps the set's selector
+static zsmi_seekable *seekWithSet(zsmi_ctx *c, zsmi_seekable *sk, const zsmi_ddictSet *set, int *err)
+{
+    if (!sk || !set) return sk;
+    const int e = ddictSetSel(c, set, sk->sel);
+    if (!e) return sk;
+    delete sk;
+    if (err) *err = e;
+    return nullptr;
+}
+extern "C" zsmi_seekable *zsmi_openSeekable_usingDDictSet(zsmi_ctx *c, const void *archive, size_t size, const zsmi_ddictSet *set, int *err)
+{
+    return seekWithSet(c, zsmi_openSeekable(c, archive, size, err), set, err);
+}
+extern "C" zsmi_seekable *zsmi_openSeekableDevice_usingDDictSet(zsmi_ctx *c, const void *dArchive, uint64_t size, const zsmi_ddictSet *set, int *err)
+{
+    return seekWithSet(c, zsmi_openSeekableDevice(c, dArchive, size, err), set, err);
+}
 extern "C" void zsmi_closeSeekable(zsmi_seekable *sk) { delete sk; }
+extern "C" int zsmi_getFrameInfo_fromSeekable(const zsmi_seekable *sk, uint32_t index, uint64_t *cOffset, uint64_t *dOffset, uint32_t *cSize, uint32_t *dSize)
+{
+    if (!sk) return ZSMI_error_GENERIC;
+    if (index >= sk->t.n) return ZSMI_error_frameIndex_tooLarge;
+    if (cOffset) *cOffset = sk->t.cOff[index];
+    if (dOffset) *dOffset = sk->t.dOff[index];
+    if (cSize) *cSize = sk->t.cSize[index];
+    if (dSize) *dSize = sk->t.dSize[index];
+    return 0;
+}
 extern "C" size_t zsmi_getNumFrames_fromSeekable(const zsmi_seekable *sk) { return sk ? sk->t.n : 0; }
 extern "C" unsigned long long zsmi_getContentSize_fromSeekable(const zsmi_seekable *sk) { return sk ? sk->t.dOff[sk->t.n] : 0; }
 extern "C" size_t zsmi_sizeofSeekable(const zsmi_seekable *sk) { return sk && sk->dOwned ? sk->t.cOff[sk->t.n] : 0; }
@@ -488,7 +612,7 @@ extern "C" int zsmi_seekableReadRangesDevice(zsmi_ctx *c, const zsmi_seekable *s
     if (bytes && !dDst) return ZSMI_error_GENERIC;
     if (const int e = c->bind()) return e;
     for (uint32_t r = 0; r < nRanges; r++) written[r] = rg[r].b - rg[r].a;
-    return seekReadRanges(c, sk->t, sk->dFrames, 0, rg.data(), nRanges, (uint8_t *)dDst, dStatus, framesDecoded);
+    return seekReadRanges(c, sk->t, sk->dFrames, 0, rg.data(), nRanges, (uint8_t *)dDst, dStatus, framesDecoded, &sk->sel);
 }
 extern "C" int zsmi_seekableReadRangesHost(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *offsets, const uint64_t *lengths, uint32_t nRanges,
                                            void *dst, size_t dstCapacity, uint64_t *written, uint32_t *statuses)
@@ -503,10 +627,39 @@ extern "C" int zsmi_seekableReadRangesHost(zsmi_ctx *c, const zsmi_seekable *sk,
     if (nRanges == 0) return 0;
     if (const int e = c->bind()) return e;
     if (!c->sDst.reserve(bytes + 64) || !c->sSizes.reserve((size_t)nRanges * sizeof(uint32_t))) return ZSMI_error_memory_allocation;
-    int rc = seekReadRanges(c, sk->t, sk->dFrames, 0, rg.data(), nRanges, (uint8_t *)c->sDst.p, (uint32_t *)c->sSizes.p, nullptr);
+    int rc = seekReadRanges(c, sk->t, sk->dFrames, 0, rg.data(), nRanges, (uint8_t *)c->sDst.p, (uint32_t *)c->sSizes.p, nullptr, &sk->sel);
     if (!rc) rc = c->toHost(statuses, c->sSizes.p, (size_t)nRanges * sizeof(uint32_t));
     if (!rc && bytes) rc = c->toHost(dst, c->sDst.p, bytes);
     const int waited = c->wait(); return rc ? rc : waited;              // (the wait: whatever was queued, a failed call included)
+}
+// records by number: the read of the frames' extents {content offset, Decompressed_Size}.  The checks the range calls make in front of their
+// offsets' check, then the indices; a1, a2: the arrays the range call would refuse as null
+static int seekFrameExtents(const zsmi_ctx *c, const zsmi_seekable *sk, const uint32_t *frameIndex, uint32_t nFrames, const void *a1, const void *a2,
+                            std::vector<uint64_t> &offsets, std::vector<uint64_t> &lengths)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (!sk || (nFrames && (!frameIndex || !a1 || !a2))) return ZSMI_error_GENERIC;
+    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
+    offsets.resize(nFrames); lengths.resize(nFrames);
+    for (uint32_t k = 0; k < nFrames; k++) {
+        if (frameIndex[k] >= sk->t.n) return ZSMI_error_frameIndex_tooLarge;
+        offsets[k] = sk->t.dOff[frameIndex[k]]; lengths[k] = sk->t.dSize[frameIndex[k]];
+    }
+    return 0;
+}
+extern "C" int zsmi_seekableReadFramesDevice(zsmi_ctx *c, const zsmi_seekable *sk, const uint32_t *frameIndex, uint32_t nFrames,
+                                             void *dDst, const uint64_t *dstOffsets, uint64_t *written, uint32_t *dStatus, uint32_t *framesDecoded)
+{
+    std::vector<uint64_t> offsets, lengths;
+    if (const int e = seekFrameExtents(c, sk, frameIndex, nFrames, dstOffsets, written, offsets, lengths)) return e;
+    return zsmi_seekableReadRangesDevice(c, sk, offsets.data(), lengths.data(), nFrames, dDst, dstOffsets, written, dStatus, framesDecoded);
+}
+extern "C" int zsmi_seekableReadFramesHost(zsmi_ctx *c, const zsmi_seekable *sk, const uint32_t *frameIndex, uint32_t nFrames,
+                                           void *dst, size_t dstCapacity, uint64_t *written, uint32_t *statuses)
+{
+    std::vector<uint64_t> offsets, lengths;
+    if (const int e = seekFrameExtents(c, sk, frameIndex, nFrames, written, statuses, offsets, lengths)) return e;
+    return zsmi_seekableReadRangesHost(c, sk, offsets.data(), lengths.data(), nFrames, dst, dstCapacity, written, statuses);
 }
 
 // ---- the single-range calls: the one-range case of seekReadRanges ----

@@ -709,14 +709,15 @@ extern "C" void zsmi_freeCDictSet(zsmi_cdictSet *set) { delete set; }
 extern "C" uint32_t zsmi_sizeofCDictSetMembers(const zsmi_cdictSet *set) { return set ? set->members : 0; }
 // resolveCDict's sibling: what a zsmi_cdictSet * argument and the call's choice ask of a call on context c - 0, with level and sel set
 // (without a table for a null set, the plain call at level 3); or the error, before anything is queued or written
-static int resolveCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dictIndex, uint32_t n, int &level, ZsCDictSel &sel)
+static int resolveCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dictIndex, uint32_t n, int &level, ZsCDictSel &sel, bool nullIsTheOneMember)
 {
     level = set ? set->level : 3; sel = ZsCDictSel();
     if (!c) return ZSMI_error_init_missing;
     if (!set) return 0;
-    if (n && !dictIndex) return ZSMI_error_GENERIC;
-    bool any = false;                                                // (a choice that gives no chunk a dictionary: the plain call)
-    for (uint32_t i = 0; i < n; i++) if (dictIndex[i] != ZS_DICT_NONE) {
+    const bool oneMember = !dictIndex && nullIsTheOneMember && set->members == 1;      // (the selector's null dictIndex: every chunk uses record 0)
+    if (n && !dictIndex && !oneMember) return ZSMI_error_GENERIC;
+    bool any = oneMember && n && set->hasDict[0] != 0;               // (a choice that gives no chunk a dictionary: the plain call)
+    for (uint32_t i = 0; dictIndex && i < n; i++) if (dictIndex[i] != ZS_DICT_NONE) {
         if (dictIndex[i] >= set->members) return ZSMI_error_parameter_outOfBound;
         any |= set->hasDict[dictIndex[i]] != 0;
     }
@@ -1088,6 +1089,7 @@ extern "C" zsmi_ddictSet *zsmi_createDDictSet(zsmi_ctx *c, const zsmi_ddict *con
         return 0;
     });
 }
+static int ddictSetSel(const zsmi_ctx *c, const zsmi_ddictSet *set, ZsDictSel &sel) { return resolveDDict(c, set, sel); }      // (zsmi_ctx.h: what seekable.hip takes of a set)
 extern "C" void zsmi_freeDDictSet(zsmi_ddictSet *set) { delete set; }
 extern "C" uint32_t zsmi_sizeofDDictSetMembers(const zsmi_ddictSet *set) { return set ? set->members : 0; }
 extern "C" int zsmi_decompressBatchDevice_usingDDictSet(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,

@@ -153,9 +153,10 @@ struct zsmi_ctx {
     DevBuf sSrc, sDst, sSizes, sDict, sPack, sPackOff;
     DevBuf dScan;                        // the tile sums of an offset scan (scanOffsets: zsmi_packFramesDevice, zsmi_layoutOutputsDevice, the seekable packer)
     PinBuf hPack;
-    // seekable archives (seekable.hip): compressed frames at bound spacing before they are packed, per-frame words (sizes, hashes, offsets, the
-    // error word; a read's status words, codes and lists), the decoded bytes of the frames a read does not decode in place, and a read's lists
-    // on the host: pinned buffers taken in turn, as hItems
+    // seekable archives (seekable.hip): compressed frames at the running sum of their bounds before they are packed, per-frame words (frame
+    // sizes, staging, packed and content offsets, compressed sizes, hashes, the error word; a read's status words, codes and lists), the decoded
+    // bytes of the frames a read does not decode in place, and a call's lists (a read's; a compress call's sizes and staging offsets) on the
+    // host: pinned buffers taken in turn, as hItems
     struct SeekScratch { DevBuf dStage, dMeta, dDec; TurnBufs hLists; } seek;
     // dictionary training (dict_train.hip): the samples back to back, sort keys, per-position hash / links (d = 6, 8), base and per-candidate
     // frequency tables, candidate contents and list, compressed sizes and frames of the scoring / statistics calls, stats + header scratch, the result
@@ -251,6 +252,12 @@ static int compressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t
 static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *srcOffsets, const uint32_t *srcSizes,
                                      uint32_t n, void *dDst, const uint64_t *dstOffsets, const uint32_t *dstCaps, uint32_t *dDstSizes,
                                      const struct ZsDictSel *dict);
+// what the features take of the two kinds of dictionary set (the structs: zsmi_api.hip).  resolveCDictSet: the checks of a set call's choice and
+// its selector; nullIsTheOneMember: a null dictIndex with a set of exactly one member gives every chunk that member (the resident set call's
+// rule) instead of GENERIC.  ddictSetSel: a DDict set's selector for a context of its device (a null set: none)
+static int resolveCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dictIndex, uint32_t n, int &level, ZsCDictSel &sel,
+                           bool nullIsTheOneMember = false);
+static int ddictSetSel(const zsmi_ctx *c, const zsmi_ddictSet *set, struct ZsDictSel &sel);
 template <class Size>
 static int scanOffsets(zsmi_ctx *c, const char *name, const Size *dSizes, const uint32_t *dStatus, uint32_t n, uint32_t align, uint32_t *dCaps, uint64_t *dOffsets);
 // a context of the one-shot pool (zsmi_api.hip), given back when the handle goes
