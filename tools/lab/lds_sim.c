@@ -81,7 +81,39 @@ static void priceSpan(int site, const Span *s, U32 bytes, const U32 *pairBase /*
     }
 }
 
-typedef struct { U32 ip, anchor, rep0, rep1, scanEnd, limit, start; int active; } Walker;
+typedef struct { U32 ip, anchor, rep0, rep1, scanEnd, limit, start, steps; int active; } Walker;
+
+/* Park and re-pack, the ideal policy: a wavefront runs until at most T of its walkers are still walking, parks those (one step charged for
+   the hand-over), and the unit's parked walkers are packed WPW to a wavefront, the longest together, each such wavefront running as long as its longest.
+   Counted in wave steps against the lock-step walk as it is (waveSteps); moving the state is free here, so this bounds what re-packing can win. */
+#define NPARK 6
+static const U32 parkT[NPARK] = { 2, 4, 6, 8, 12, 16 };
+static unsigned long long parkSteps[NPARK], rangeSteps, rangesWalked;
+static int cmpDesc(const void *a, const void *b) { U32 const x = *(const U32 *)a, y = *(const U32 *)b; return (x < y) - (x > y); }
+static void parkUnit(const U32 *steps, U32 nRanges, U32 WPW)
+{
+    static U32 rest[NPARK][1024];
+    U32 nRest[NPARK] = { 0 };
+    for (U32 r0 = 0; r0 < nRanges; r0 += WPW) {
+        U32 s[64], nw = (nRanges - r0 < WPW) ? nRanges - r0 : WPW;
+        memcpy(s, steps + r0, nw * sizeof(U32));
+        qsort(s, nw, sizeof(U32), cmpDesc);
+        for (int t = 0; t < NPARK; t++) {
+            U32 const T = parkT[t], own = (nw > T) ? s[T] : 0;        /* the step after which at most T walk on */
+            int parked = 0;
+            for (U32 k = 0; k < T && k < nw; k++) if (s[k] > own) { rest[t][nRest[t]++] = s[k] - own; parked = 1; }
+            parkSteps[t] += own + (parked ? 1u : 0u);
+        }
+    }
+    for (int t = 0; t < NPARK; t++) {
+        qsort(rest[t], nRest[t], sizeof(U32), cmpDesc);          /* the longest together: the packing that costs the fewest steps */
+        for (U32 k = 0; k < nRest[t]; k += WPW) {
+            U32 longest = 0;
+            for (U32 j = k; j < k + WPW && j < nRest[t]; j++) if (rest[t][j] > longest) longest = rest[t][j];
+            parkSteps[t] += longest;
+        }
+    }
+}
 
 static void simUnit(Work *w, const BYTE *src, U32 n, const EParams *prm)
 {
@@ -89,6 +121,7 @@ static void simUnit(Work *w, const BYTE *src, U32 n, const EParams *prm)
     U32 const WPW = 64u / (U32)LPW;                       /* walkers per wavefront */
     U32 const look = (U32)prm->look, repWin = (U32)prm->repWin, CPL = look / (U32)LPW, RPL = repWin / (U32)LPW;
     U32 const hashable = (n >= 8) ? n - 7 : 0;
+    U32 stepsOf[1024];                                    /* walker steps of every range of the unit (a walker's steps do not depend on its neighbours) */
     findCandidates(w, src, n, prm, 0);
     for (U32 r0 = 0; r0 < nRanges; r0 += WPW) {
         Walker wk[32];
@@ -114,7 +147,7 @@ static void simUnit(Work *w, const BYTE *src, U32 n, const EParams *prm)
                 Walker *W = &wk[k < nw ? k : 0];
                 int const live = k < nw && W->active;
                 U32 const ip = W->ip;
-                laneStepsAll += (U32)LPW; if (live) laneStepsActive += (U32)LPW;
+                laneStepsAll += (U32)LPW; if (live) { laneStepsActive += (U32)LPW; W->steps++; }
                 int const t0 = live && W->rep0 && ip >= W->rep0, t1 = live && W->rep1 && ip >= W->rep1;
                 for (U32 sub = 0; sub < (U32)LPW; sub++) {
                     U32 const l = k * (U32)LPW + sub, p0 = ip + sub * RPL;
@@ -189,7 +222,9 @@ static void simUnit(Work *w, const BYTE *src, U32 n, const EParams *prm)
                 }
             }
         }
+        for (k = 0; k < nw; k++) { stepsOf[r0 + k] = wk[k].steps; rangeSteps += wk[k].steps; rangesWalked++; }
     }
+    parkUnit(stepsOf, nRanges, WPW);
 }
 
 int sim_run(const BYTE *data, size_t n, U32 unit, int level, int pad)
@@ -197,11 +232,14 @@ int sim_run(const BYTE *data, size_t n, U32 unit, int level, int pad)
     EParams const prm = paramsForLevel(level);
     Work *w = (Work *)calloc(1, sizeof(Work));
     PAD = pad; LPW = prm.windowGroups;
-    memset(cyc, 0, sizeof cyc); memset(ins, 0, sizeof ins); waveSteps = laneStepsActive = laneStepsAll = extRounds = 0;
+    memset(cyc, 0, sizeof cyc); memset(ins, 0, sizeof ins); waveSteps = laneStepsActive = laneStepsAll = extRounds = rangeSteps = rangesWalked = 0; memset(parkSteps, 0, sizeof parkSteps);
     size_t units = 0;
     for (size_t o = 0; o + unit <= n; o += unit, units++) simUnit(w, data + o, unit, &prm);
     printf("units %zu of %u bytes, level %d, PAD %d: wave steps / unit %.1f, active lane-steps %.1f %%, extension rounds / wave step %.2f\n", units, unit, level, pad,
            (double)waveSteps / units, 100.0 * laneStepsActive / laneStepsAll, (double)extRounds / waveSteps);
+    printf("walker steps / range %.1f; park the last <= T walkers of a wavefront and re-pack them, wave steps against today's:", (double)rangeSteps / rangesWalked);
+    for (int t = 0; t < NPARK; t++) printf("  T=%u %.1f %%", parkT[t], 100.0 * parkSteps[t] / waveSteps);
+    printf("\n");
     printf("%-22s", "LDS cycles / wave step");
     for (int s = 0; s < NSITE; s++) printf("%10s", siteName[s]);
     printf("%10s %8s\n", "total", "instr");

@@ -18,7 +18,7 @@ off = np.arange(n, dtype=np.uint64) * cs; sz = np.full(n, cs, dtype=np.uint32)
 bound = int(Z.zsmi_compressBound(cs)); doff = np.arange(n, dtype=np.uint64) * bound
 ddst = torch.empty(n * bound, dtype=torch.uint8, device="cuda"); dsz = torch.empty(n, dtype=torch.int32, device="cuda")
 bc.compress_device(dsrc.data_ptr(), off, sz, ddst.data_ptr(), doff, dsz.data_ptr(), 3); bc.sync()
-names = ["staging", "grab / loop head / barrier wait", "recent offsets + window", "candidate picks + distance loads", "scoring", "whole length", "record + bookkeeping", "-", "steps per wavefront", "active lanes per step"]
+names = ["staging", "loop head / barrier wait", "recent offsets + window", "candidate picks + distance loads", "scoring", "whole length", "record + bookkeeping", "-", "steps per wavefront", "active lanes per step"]
 # the stamps, a word a name for every wavefront of every unit, lie behind ALL blocks' range results (zs_res_lend_walk_profile, csrc/zsmi_scratch.h)
 base = n * _lib.scratch_layout("res")[0]
 buf = _lib.copy_scratch(bc.ctx, "res", n, extra=n * waves * 8 * len(names))

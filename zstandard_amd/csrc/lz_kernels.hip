@@ -367,8 +367,8 @@ k_lz_dict_tables(const ZsCDictEntry entry, ZsCDictEntry *__restrict__ entryOut)
 // ---------------------------------------------------------------------------------------------
 // k_lz_walk<LPW, LOOK, REPWIN, BIG, NT> : one workgroup of NT threads per LZ unit (BIG: 64 KiB < unit <= 128 KiB).
 // The unit's source bytes are staged in LDS once (+ pads): every compare of the walk is an LDS read and the unit is fetched from HBM
-// once.  The unit is cut in walk ranges of R = 1 << rangeLog bytes (256; 512 at levels <= 2); a WALKER = 4 adjacent lanes takes ranges
-// from a queue (an LDS counter) and walks each on its own (walkRange in oracle/zso_encoder.c).  A step looks at the positions from ip to
+// once.  The unit is cut in walk ranges of R = 1 << rangeLog bytes (256; 512 at levels <= 2); a WALKER = 2 or 4 adjacent lanes (LPW) takes the
+// range of its own number - a workgroup has a walker per range of a full unit - and walks it on its own (walkRange in oracle/zso_encoder.c).  A step looks at the positions from ip to
 // the end of the fourth aligned group of 8: lane j of the walker has group j's stage-1 distances brought into its slot of the wavefront's
 // exchange buffer in LDS (16 coalesced bytes by LDS-DMA: the walker's 64 bytes are one cache line; requested a step ahead, right after ip
 // is known) and turns them into 8 candidate bits; plus, for the first REPWIN positions, the positions where one of the walker's two recent offsets
@@ -401,6 +401,10 @@ k_lz_dict_tables(const ZsCDictEntry entry, ZsCDictEntry *__restrict__ entryOut)
 #endif
 #define ZS_WALK_LPW(WLOG) ((WLOG) >= 9 ? ZS_WALK_LPW_512 : ZS_WALK_LPW_256)
 #define ZS_WALK_THREADS(BIG, WLOG) ((((BIG) ? ZS_UNIT_MAX : ZS_BLOCK_MAX) >> (WLOG)) * ZS_WALK_LPW(WLOG))
+// (k_lz_walk has no queue of ranges: walker w walks range w, so a workgroup must never hold fewer walkers than its unit can have ranges)
+static_assert(ZS_WALK_THREADS(false, 8) / ZS_WALK_LPW(8) == (ZS_BLOCK_MAX >> 8) && ZS_WALK_THREADS(false, 9) / ZS_WALK_LPW(9) == (ZS_BLOCK_MAX >> 9) &&
+              ZS_WALK_THREADS(true, 8) / ZS_WALK_LPW(8) == (ZS_UNIT_MAX >> 8) && ZS_WALK_THREADS(true, 9) / ZS_WALK_LPW(9) == (ZS_UNIT_MAX >> 9),
+              "a walker per walk range of a unit of full capacity");
 #define ZS_WALK_KERNEL(LOOK, REPW, BIG, WLOG) k_lz_walk<ZS_WALK_LPW(WLOG), ZS_WALK_WGRP(WLOG), LOOK, REPW, BIG, ZS_WALK_THREADS(BIG, WLOG)>
 // The unit's source in LDS is SKEWED: rows of 256 source bytes lie 256 + ZS_WALK_SKEW bytes apart, and the ZS_WALK_SKEW bytes behind a row
 // repeat the head of the next row, so a read of up to 24 bytes that STARTS in a row is contiguous in that row's storage:
@@ -414,7 +418,7 @@ k_lz_dict_tables(const ZsCDictEntry entry, ZsCDictEntry *__restrict__ entryOut)
 #define ZS_WALK_FRONT 48u          // row -1 of the staged source: 24 zero bytes (positions -24 .. -1: backward reads near position 0) + the copy of row 0's head
 #define ZS_WALK_TAIL  144u         // zero bytes behind the unit (forward reads near the end)
 #define ZS_WALK_SRCBYTES(CAPB) ((((CAPB) + ZS_WALK_TAIL + ZS_WALK_SKEW * (((CAPB) + ZS_WALK_TAIL) / 256u + 1u)) + 15u) & ~15u)
-// exchange buffer (16 bytes a lane) + front + skewed source + queue head + a byte a lane (BIG: bit 16 of the distances)
+// exchange buffer (16 bytes a lane) + front + skewed source + the "mixed" word's 16 bytes + a byte a lane (BIG: bit 16 of the distances)
 #define ZS_WALK_LDS(CAPB) ((CAPB) / 8 + 16 + ZS_WALK_FRONT + ZS_WALK_SRCBYTES(CAPB) + 16 + 1024)
 
 // K dwords of the LDS copy starting at any byte offset, fetched as K + 1 aligned dwords and shifted into place
@@ -530,7 +534,7 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     static_assert((LPW == 1 || LPW == 2 || LPW == 4) && WGRP % LPW == 0 && LOOK % LPW == 0 && REPWIN % LPW == 0 && CPL >= 1 && RPL >= 1 && LOOK <= 8 && REPWIN <= 8, "a walker's lanes share the groups and candidates evenly");
     static_assert(NT >= 64 && NT % 64 == 0 && NT * GPL * 16 <= CAP / 8, "the exchange buffer holds 16 bytes a lane and group");
     extern __shared__ __attribute__((aligned(16))) uint8_t walkLds[];
-    // LDS: exchange buffer (the low addresses: the LDS-DMA's base register is not known to reach beyond 64 KiB), front pad, source, tail pad, results, queue, xhi
+    // LDS: exchange buffer (the low addresses: the LDS-DMA's base register is not known to reach beyond 64 KiB), front pad, source, tail pad, the mixed word, xhi
     constexpr uint32_t SRC = CAP / 8 + 16 + ZS_WALK_FRONT;                       // LDS address of source byte 0
     // LDS address of staged position v (v may be a little negative: row -1 = the front pad); of source position p (a prefixed unit: v = p + pfx)
     auto lposv = [](uint32_t v) { return SRC + v + (uint32_t)__mul24((int)v >> 8, (int)ZS_WALK_SKEW); };
@@ -555,9 +559,9 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     uint4 *xbuf = reinterpret_cast<uint4 *>(walkLds);                              // exchange buffer: wavefront w's region holds GPL x 64 slots of 8 distances: lane t's k-th group at [(64 w) GPL + 64 k + t]
     const uint32_t xw = (tid & ~63u) * GPL;                                      // my wavefront's first slot
     const uint32_t safeAddr = (xw + lane) * 16u;                                 // LDS address of my own first slot: where a lane with nothing to read reads (its own banks, no conflict)
-    uint32_t *queue = reinterpret_cast<uint32_t *>(walkLds + SRC + ZS_WALK_SRCBYTES(CAP));
+    uint32_t *mixedWord = reinterpret_cast<uint32_t *>(walkLds + SRC + ZS_WALK_SRCBYTES(CAP)) + 1;   // some byte of the unit differs from its first (16 bytes are kept here: xhi stays aligned)
     uint4 *res = zs_block_range_results(resAll, slot);                         // per walk range (R >= 256: at most 256 a block): records, last match end in its block, last offset
-    uint8_t *xhi = reinterpret_cast<uint8_t *>(queue + 4);                        // BIG: lane t's byte of bit 16 of its 8 distances
+    uint8_t *xhi = reinterpret_cast<uint8_t *>(mixedWord + 3);                        // BIG: lane t's byte of bit 16 of its 8 distances
     uint2 *recs = zs_block_walk_records(recAll, slot);                        // range at unit position p: slots from p / 4 (its matches start inside it, >= 4 bytes each)
     const uint32_t sub = lane & (LPW - 1u);
 #ifdef ZS_WALK_PROFILE
@@ -575,7 +579,7 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     // ---- stage the unit ----
     uint32_t mixed = 0;                                                          // some byte of the unit differs from its first byte
     if (tid < (ZS_WALK_FRONT - ZS_WALK_SKEW) / 4) reinterpret_cast<uint32_t *>(walkLds + SRC - ZS_WALK_FRONT)[tid] = 0;
-    if (tid == 0) { queue[0] = 0; queue[1] = 0; }
+    if (tid == 0) *mixedWord = 0;
     __syncthreads();
     if constexpr (PFX) {
         // the dictionary's tail and the chunk, 16 staged bytes a thread and round: a piece wholly in one of them is one load, the (at most two)
@@ -637,9 +641,9 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     const uint32_t hashable = (n >= 8) ? n - 7 : 0;
     // A unit of one repeated byte becomes RLE blocks whatever the parse says (the literals kernel decides that from the bytes, as
     // zso_encoder.c:833-836 does before parsing): its walk -- the slowest there is, every match running to the crossing limit -- is skipped.
-    if (mixed) queue[1] = 1u;                                                    // (no __syncthreads_or: hipcc gives it static LDS of its own, which moves the dynamic part this kernel addresses by hand)
+    if (mixed) *mixedWord = 1u;                                                   // (no __syncthreads_or: hipcc gives it static LDS of its own, which moves the dynamic part this kernel addresses by hand)
     __syncthreads();
-    if (queue[1] == 0) {
+    if (*mixedWord == 0) {
         const uint32_t nRanges = (n + R - 1) >> rangeLog, perBlockLog = 16u - rangeLog;
         for (uint32_t r = tid; r < nRanges; r += NT) res[zs_unit_range_result(r, perBlockLog)] = make_uint4(0, 0, 0, 0);
         return;
@@ -649,56 +653,52 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     // ---- the walk ----
     {
         const uint32_t nRanges = (n + R - 1) >> rangeLog;
-        bool active = false, more = true;                                        // walking a range / the queue may hold more
-        uint32_t r = 0, ip = 0, anchor = 0, scanEnd = 0, limit = 0, rep0 = 0, rep1 = 0, nseq = 0, lastOff = 0, recBase = 0, blockBase = 0;
+        bool active = false;                                                     // walking my range
+        uint32_t ip = 0, anchor = 0, scanEnd = 0, limit = 0, rep0 = 0, rep1 = 0, nseq = 0, lastOff = 0, blockBase = 0;
         uint2 heldRec = make_uint2(0, 0);                                        // the odd record waiting for its pair
         const uint32_t perBlockLog = 16u - rangeLog;                             // walk ranges per block
-        auto resIndex = [&](uint32_t rr) { return zs_unit_range_result(rr, perBlockLog); };
         // distances of the group (ip >> 3) + sub, requested as soon as ip is known: 16 bytes a lane straight into the lane's slot of the
         // exchange buffer (LDS-DMA: no registers carried around the loop, no wait the compiler places for me; behind the hashable positions
         // whatever the scratch holds: those bits are cut off the window).  BIG: bit 16 of the distances, a byte per group, by an ordinary load.
         // (The load is an asm statement: hipcc counts a __builtin_amdgcn_global_load_lds and then waits vmcnt(0) in front of every LDS access it
-        // cannot tell apart from the destination; this one is waited for by hand: "s_waitcnt vmcnt(0)" at the top of the step and where a
-        // walker takes a new range.  M0 = LDS destination of lane 0, set inside the statement that uses it.)
+        // cannot tell apart from the destination; this one is waited for by hand: "s_waitcnt vmcnt(0)" at the top of the step and behind the
+        // walkers' first request.  M0 = LDS destination of lane 0.  A group a lane (GPL == 1: every shape the library is built with): the
+        // same value for every request of the wavefront, set ONCE, in front of the loop - nothing hipcc generates for this kernel from
+        // there on writes M0 (no movrel, no sendmsg, no LDS-DMA of its own: DESIGN.md section 4 says how that was checked), and the
+        // statements that need it come last in the kernel.  More groups a lane (an experiment's -DZS_WALK_LPW_*): set in front of each request.)
         typedef __attribute__((address_space(3))) uint4 *ZsLdsU4;
         const uint32_t xwaveLds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(ZsLdsU4)(xbuf + xw));
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" :: "s"(xwaveLds) : "memory");
         uint32_t gh[GPL] = {};
         auto loadGroup = [&](uint32_t p) {
             #pragma unroll
             for (uint32_t k = 0; k < GPL; k++) {                                 // the lane's groups: sub, sub + LPW, ..
                 const uint32_t g = (p >> 3) + sub + LPW * k;
                 const uint16_t *gsrc = dist + (size_t)g * 8u;
-                uint32_t keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(xwaveLds + k * 1024u) : "memory");
+                if constexpr (GPL == 1) asm volatile("global_load_lds_dwordx4 %0, off" :: "v"(gsrc) : "memory");
+                else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(gsrc), "s"(xwaveLds + k * 1024u) : "memory");
                 if (BIG) gh[k] = (uint32_t)distHi[g];
             }
         };
-        for (;;) {
-            if (__any(!active && more)) {
-                // idle walkers take the next ranges of the queue: one LDS atomic per wavefront
-                const uint64_t idle = __ballot(!active && more && sub == 0);
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(queue, (uint32_t)__popcll(idle));
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                if (!active && more) {
-                    const uint32_t leader = lane & ~(LPW - 1u);
-                    r = base + (uint32_t)__popcll(idle & ((1ull << leader) - 1ull));
-                    if (r >= nRanges) more = false;
-                    else {
-                        const uint32_t start = r << rangeLog;
-                        const uint32_t blockStart = start & ~(ZS_BLOCK_MAX - 1);     // the range's block inside the unit
-                        const uint32_t blockEnd = blockStart + min(n - blockStart, ZS_BLOCK_MAX);
-                        const uint32_t end = min(start + R, blockEnd);
-                        limit = min(end + ZS_CROSS_MAX, blockEnd);               // matches end at or before this
-                        scanEnd = (blockEnd - blockStart >= 16) ? min(end, hashable) : 0;
-                        ip = start; anchor = start; rep0 = 0; rep1 = 0; nseq = 0; lastOff = 0; recBase = start >> 2; blockBase = blockStart;
-                        active = ip < scanEnd;
-                        if (!active && sub == 0) res[resIndex(r)] = make_uint4(0, 0, 0, 0);    // nothing to scan
-                        if (active) { loadGroup(ip); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }    // (its first group: nothing to overlap it with)
-                    }
-                }
-            }
-            if (!__any(active)) { if (!__any(more)) break; continue; }
+        // Walker w = tid / LPW walks range w and no other: there are never more ranges than walkers (ZS_WALK_THREADS: a walker per range of
+        // the capacity the chunk's positions can fill - a prefixed unit's chunk is <= ZS_BLOCK_MAX), so nothing is left to hand out once
+        // the loop runs.  Its state is set here, its first group requested and waited for (nothing to overlap it with).
+        const uint32_t r = tid / LPW;
+        const uint32_t recBase = r << (rangeLog - 2u), resAt = zs_unit_range_result(r, perBlockLog);
+        if (r < nRanges) {
+            const uint32_t start = r << rangeLog;
+            const uint32_t blockStart = start & ~(ZS_BLOCK_MAX - 1);             // the range's block inside the unit
+            const uint32_t blockEnd = blockStart + min(n - blockStart, ZS_BLOCK_MAX);
+            const uint32_t end = min(start + R, blockEnd);
+            limit = min(end + ZS_CROSS_MAX, blockEnd);                           // matches end at or before this
+            scanEnd = (blockEnd - blockStart >= 16) ? min(end, hashable) : 0;
+            ip = start; anchor = start; blockBase = blockStart;
+            active = ip < scanEnd;
+            if (!active && sub == 0) res[resAt] = make_uint4(0, 0, 0, 0);        // nothing to scan
+            if (active) loadGroup(ip);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        while (__any(active)) {
             WPROF_STAMP(1)
 #ifdef ZS_WALK_PROFILE
             wprof[8] += 1; wprof[9] += (unsigned long long)__popcll(__ballot(active));
@@ -837,30 +837,27 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
             }
             if (extend) bfwd = pos - bq;
             WPROF_STAMP(5)
-            uint32_t recLl = 0;
-            if (took) {
-                recLl = bq - bback - anchor;                                     // literals in front of the match, inside the range (< R <= 512)
-                nseq++; lastOff = boff;
-                ip = bq + bfwd; anchor = ip;
-                if (boff == rep1) { rep1 = rep0; rep0 = boff; }
-                else if (boff != rep0) { rep1 = rep0; rep0 = boff; }
-            } else if (active) ip = wend;
+            // ---- the step's outcome, for every lane by selects (a lane that took nothing, or is at rest, keeps what it had): what stays
+            // conditional are the stores and the request, each under one flat predicate.  (Written as nested if / else the tail compiled to
+            // nine exec-mask regions with the loop-carried values copied from side to side of each: DESIGN.md section 4.)
+            const uint32_t recStart = bq - bback, recLl = recStart - anchor;      // literals in front of the match, inside the range (< R <= 512)
+            const uint2 rec = make_uint2((recStart - blockBase) | ((bback + bfwd) << 17), boff | (recLl << 17));    // start: position in its block; offset, literals
+            const bool rot = took && boff != rep0;                               // (boff == rep1 swaps the two, any other offset pushes rep0 down: the same two moves)
+            rep1 = rot ? rep0 : rep1; rep0 = rot ? boff : rep0;
+            nseq += took ? 1u : 0u;
+            lastOff = took ? boff : lastOff;
+            ip = took ? bq + bfwd : (active ? wend : ip);
+            anchor = took ? ip : anchor;
+            const bool odd = (nseq & 1u) != 0, done = active && ip >= scanEnd, first = sub == 0;
             // the record leaves (the walker's first lane, a step that took a match); the next step's distances are requested (walkers with a
             // step to come): the memory system takes a wavefront's small requests one by one, and the kernel's time follows their number
             // (every lane loading and storing every step, walkers at rest included: 4 requests a walker step, 0.95 ms; profiles/r3_walk_*)
             // (records leave in pairs, 16 aligned bytes: half the write requests; a range's odd last one alone)
-            if (took) {
-                const uint2 rec = make_uint2((bq - bback - blockBase) | ((bback + bfwd) << 17), boff | (recLl << 17));    // start: position in its block; offset, literals
-                if (nseq & 1u) heldRec = rec;
-                else if (sub == 0) *reinterpret_cast<uint4 *>(recs + recBase + nseq - 2) = make_uint4(heldRec.x, heldRec.y, rec.x, rec.y);
-            }
-            if (active && ip >= scanEnd) {
-                if (sub == 0) {
-                    if (nseq & 1u) recs[recBase + nseq - 1] = heldRec;
-                    res[resIndex(r)] = make_uint4(nseq, nseq ? anchor - blockBase : 0u, lastOff, 0u);
-                }
-                active = false;
-            }
+            if (took && !odd && first) *reinterpret_cast<uint4 *>(recs + recBase + nseq - 2) = make_uint4(heldRec.x, heldRec.y, rec.x, rec.y);
+            heldRec.x = (took && odd) ? rec.x : heldRec.x; heldRec.y = (took && odd) ? rec.y : heldRec.y;
+            if (done && odd && first) recs[recBase + nseq - 1] = heldRec;
+            if (done && first) res[resAt] = make_uint4(nseq, nseq ? anchor - blockBase : 0u, lastOff, 0u);
+            active = active && !done;
             if (active) loadGroup(ip);
             WPROF_STAMP(6)
         }
