@@ -354,7 +354,8 @@ int zsmi_decompressBatchResident(zsmi_ctx *ctx, const void *dSrc, const uint64_t
  * of the destinations (zsmi_layoutOutputsDevice above, over the bounds) and the compress call itself only queue work on the context's
  * stream.  Dictionaries come through zsmi_compressBatchResident_usingCDictSet: a CDict set and an index a chunk in device memory (one
  * digested dictionary: the set of one member).  What still plans on the host, from host arrays: the _usingDict forms with dictionary BYTES
- * (their loader reads a record back and waits), seekable compress and the dictionary trainer.
+ * (their loader reads a record back and waits), the fixed-size and host-array seekable compress calls and the dictionary trainer.  (Record
+ * archives have a resident form of their own: zsmi_compressSeekableFramesResident*, zsmi_seekableReadFramesResident.)
  * ------------------------------------------------------------------------------------------ */
 /* dBounds[i] = zsmi_compressBound(dSrcSizes[i]) for n sizes, on the device (both arrays device memory; entries [0, n) are written).
  * zsmi_layoutOutputsDevice(ctx, dBounds, NULL, n, align, dCaps, dDstOffsets) then places the frames.  A NULL ctx: init_missing; a NULL
@@ -447,6 +448,9 @@ int zsmi_decompressSeekableDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcS
  * device memory the handle owns, on ctx's device and stream, and waited for, once.
  * zsmi_openSeekableDevice: an archive in device memory, borrowed: it must outlive the handle.  A NULL ctx: init_missing, first (the table is in
  * device memory); the table is read back and the stream waited for, once, here.
+ * Both keep a copy of the table in device memory for zsmi_seekableReadFramesResident (24 bytes a frame; for a borrowed archive the handle's one
+ * allocation), uploaded on ctx's stream: by zsmi_openSeekable ahead of its one wait; by zsmi_openSeekableDevice, which knows the table only
+ * behind its parse's wait, with a wait of its own, so that a read on any context finds the table whole.
  * NULL on failure, with the code in *err if err != NULL.  A handle is read-only after creation: any context of the same device may use it (a
  * context of another device: parameter_unsupported).  It must outlive the work queued with it: close it after zsmi_sync. */
 typedef struct zsmi_seekable zsmi_seekable;
@@ -455,7 +459,9 @@ zsmi_seekable *zsmi_openSeekableDevice(zsmi_ctx *ctx, const void *dArchive, uint
 void zsmi_closeSeekable(zsmi_seekable *sk);                        /* NULL: nothing */
 size_t zsmi_getNumFrames_fromSeekable(const zsmi_seekable *sk);    /* 0 for NULL */
 unsigned long long zsmi_getContentSize_fromSeekable(const zsmi_seekable *sk);   /* 0 for NULL */
-size_t zsmi_sizeofSeekable(const zsmi_seekable *sk);               /* device bytes held: the frames' bytes of a host archive; 0 for a borrowed archive, or NULL */
+/* device bytes held for the ARCHIVE: the frames' bytes of a host archive; 0 for a borrowed archive, or NULL.  The handle's device copy of the
+ * table (above) is not counted. */
+size_t zsmi_sizeofSeekable(const zsmi_seekable *sk);
 /* nRanges reads in one call: content bytes [offsets[r], offsets[r] + lengths[r]), clipped at the content's end, land at dDst + dstOffsets[r];
  * written[r] (host) receives the clipped length, dStatus[r] (device) 0 or the code of the first failing frame, in content order, among the
  * frames range r overlaps (an empty range overlaps none: 0).  offsets, lengths, dstOffsets and written are host arrays, as the batch calls'.
@@ -523,6 +529,50 @@ int zsmi_seekableReadFramesDevice(zsmi_ctx *ctx, const zsmi_seekable *sk, const 
                                   void *dDst, const uint64_t *dstOffsets, uint64_t *written, uint32_t *dStatus, uint32_t *framesDecoded);
 int zsmi_seekableReadFramesHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint32_t *frameIndex, uint32_t nFrames,
                                 void *dst, size_t dstCapacity, uint64_t *written, uint32_t *statuses);
+/* Record archives, device-resident: the frame sizes and dictionary indices of a write, the frame numbers of a read are DEVICE memory - what a
+ * GPU step produced goes in without a trip to the host.  The three calls only queue work on the context's stream: no device-to-host copy, no
+ * wait, no pinned staging (a context buffer may grow).
+ * The host is told n, srcSize (the content bytes at dSrc) and maxFrameSize (no dFrameSizes[i] is above it: what the call's scratch is planned
+ * for, as maxSrcSize of zsmi_compressBatchResident; a loose value changes no byte).
+ * When every dFrameSizes[i] <= maxFrameSize and the sizes sum to srcSize, the archive and *dArchiveSize are byte for byte those of
+ * zsmi_compressSeekableFramesDevice / _usingCDictSet with the same sizes and indices given from the host, on this context, with either table
+ * flag.  Dictionaries: the NULL rules of zsmi_compressBatchResident_usingCDictSet - set == NULL: the plain form at level 3; dDictIndex == NULL
+ * with a set of exactly one member: every frame uses member 0; with any other member count and n > 0: GENERIC.
+ * What the host cannot judge goes to *dArchiveSize as (uint64_t)-code, the code of the lowest failing frame: a size above maxFrameSize, or a
+ * frame whose content would end behind srcSize: srcSize_wrong (such a frame is planned as an empty one: nothing of dSrc outside
+ * [0, srcSize) is read, nothing outside [dDst, dDst + dstCapacity) written, whatever the sizes say); an index that is neither ZSMI_DICT_NONE
+ * nor below the member count: parameter_outOfBound (the size's refusal first); sizes that sum to less than srcSize, when no frame failed:
+ * srcSize_wrong.
+ * Checked on the host, in this order, before anything is queued: a NULL ctx: init_missing; n > 0x8000000: frameIndex_tooLarge; a NULL
+ * dFrameSizes with n > 0: GENERIC; maxFrameSize > 1 GiB: parameter_outOfBound; the dDictIndex rule; a set of another device:
+ * parameter_unsupported; what zsmi_seekableFramesResidentBound refuses, with its code; dstCapacity below that bound: dstSize_tooSmall; a NULL
+ * dArchiveSize or dDst, or a NULL dSrc with srcSize > 0: GENERIC.  n == 0 with srcSize == 0 writes the 17-byte table. */
+/* room for the archive of EVERY split of srcSize content bytes into n frames (the host never sees the sizes):
+ *   srcSize + (srcSize >> 8) + 3 * (srcSize >> 16) + n * (64 + 3 + 18)  >=  the sum of zsmi_compressBound(s_i) over any sizes that sum to srcSize
+ * plus the table's 17 + n * (checksumFlag ? 12 : 8); never below zsmi_seekableFramesBound of such sizes.  Host only, no device.
+ * n > 0x8000000: frameIndex_tooLarge; srcSize > n * 1 GiB (no legal split; n == 0 with content): parameter_outOfBound. */
+size_t zsmi_seekableFramesResidentBound(unsigned long long srcSize, uint32_t n, int checksumFlag);
+int zsmi_compressSeekableFramesResident(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, const uint32_t *dFrameSizes, uint32_t n,
+                                        uint32_t maxFrameSize, void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize, int level, int checksumFlag);
+int zsmi_compressSeekableFramesResident_usingCDictSet(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, const uint32_t *dFrameSizes, uint32_t n,
+                                        uint32_t maxFrameSize, void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize, int checksumFlag,
+                                        const zsmi_cdictSet *set, const uint32_t *dDictIndex);
+/* records by numbers in device memory.  dFrameIndex (nFrames entries), dDstOffsets (nFrames + 1), dWritten and dStatus (nFrames) are device
+ * memory.  The call lays the outputs out itself: dDstOffsets[0 .. nFrames] is the exclusive running sum of the requested frames'
+ * Decompressed_Size, each rounded up to align (the rule of zsmi_layoutOutputsDevice); request k's bytes land at dDst + dDstOffsets[k],
+ * dWritten[k] is its frame's Decompressed_Size, dStatus[k] 0, the decoder's code, corruption_detected for a size that is not the entry's or
+ * checksum_wrong for a checksum that is not the entry's.  Every request decodes straight to its place, with the handle's dictionaries; a frame
+ * number named twice is decoded twice (zsmi_seekableReadFramesDevice decodes it once and copies).
+ * Per request, where the host-array call refuses the whole call: a number at or above the frame count: dStatus[k] = frameIndex_tooLarge,
+ * dWritten[k] = 0, no room taken; a place that would end behind dstCapacity: dStatus[k] = dstSize_tooSmall, nothing written for it (dWritten[k]
+ * still states what it needs).  The other requests are untouched by either.  For numbers below the frame count and enough room, the bytes at
+ * place k, dWritten[k] and dStatus[k] are those of zsmi_seekableReadFramesDevice with the same numbers and dstOffsets = the offsets this call
+ * computes.  Writes only inside [dDst, dDst + dstCapacity).
+ * Checked on the host, in this order: a NULL ctx: init_missing; a NULL sk or dDstOffsets, or another NULL array with nFrames > 0: GENERIC; a
+ * handle of another device: parameter_unsupported; align not a power of two in 1 .. 4096: parameter_outOfBound; a NULL dDst with
+ * dstCapacity > 0 and nFrames > 0: GENERIC.  nFrames == 0 writes dDstOffsets[0] = 0 and nothing else. */
+int zsmi_seekableReadFramesResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint32_t *dFrameIndex, uint32_t nFrames, uint32_t align,
+                                    void *dDst, uint64_t dstCapacity, uint64_t *dDstOffsets, uint32_t *dWritten, uint32_t *dStatus);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

@@ -20,7 +20,13 @@ a disjoint part, both through a CDict set of two.  One process, the legs of a co
           and packing work, reported in ms beside the rates, with the kernels' own times of one call
   fetch:  --ranges seeded random records in ONE zsmi_seekableReadFramesDevice call on (c) against the same records' byte ranges in one
           zsmi_seekableReadRangesDevice call on (a): ms, frames decoded x frame bytes, content bytes delivered
-  python tools/bench_seekable.py --records [--mib 256] [--record-bytes 1024 4096] [--ranges 4096]"""
+  python tools/bench_seekable.py --records [--mib 256] [--record-bytes 1024 4096] [--ranges 4096]
+--records --resident: a second JSON line a record size, the device-resident calls against the host-array calls above on the same records
+in the same process, the legs in turn, three rounds:
+  write:  zsmi_compressSeekableFramesResident_usingCDictSet (sizes and indices in device memory) against (c)'s call; the archives must be
+          equal; the kernels of one resident call, those that plan on the device summed
+  fetch:  the same --ranges records through zsmi_seekableReadFramesResident (numbers in device memory, a frame named twice decoded twice)
+          against zsmi_seekableReadFramesDevice"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -139,6 +145,7 @@ def records(a):
         tf = alternating({"records_c": fetch_c, "ranges_a": fetch_a}, bc.sync, reps)
         gib = total / float(1 << 30)
         ms = lambda k: round(kt.get(k, (0.0, 0))[0] * 1e3, 4)
+        resident = resident_legs(a, bc, locals()) if a.resident else None
         print(json.dumps({
             "metric": "seekable_records", "mib": total >> 20, "record_bytes": R, "records": n, "level": level, "classes": classes,
             "size_over_content": {"a_64k_frames_no_dict": round(size_a / total, 4), "b_frame_per_record_no_dict": round(size_b / total, 4),
@@ -151,11 +158,50 @@ def records(a):
             "fetch_c_ms": [round(t * 1e3, 4) for t in tf["records_c"]], "fetch_c_frames_decoded": decoded["c"], "fetch_c_decoded_bytes": decoded["c"] * R,
             "fetch_a_ms": [round(t * 1e3, 4) for t in tf["ranges_a"]], "fetch_a_frames_decoded": decoded["a"], "fetch_a_decoded_bytes": decoded["a"] * 65536,
             "small_frame_packer_leg": "not tried"}), flush=True)
+        if resident:
+            print(json.dumps(resident), flush=True)
         ha.close(); hc.close(); cset.close(); dset.close()
         for x in cds + dds:
             x.close()
         del src, arcs, stage, packed, out
     bc.close()
+
+
+PLAN_KERNELS = ("k_pack_offsets", "k_seek_guard", "k_compress_bounds", "k_plan_chunks", "k_plan_blocks", "k_plan_refuse", "k_seek_refuse")
+
+
+def resident_legs(a, bc, v):
+    """--resident: the device-resident write and fetch against the host-array calls of records(), whose locals are v"""
+    src, total, n, R, N, reps, cset, hc = v["src"], v["total"], v["n"], v["R"], v["N"], v["reps"], v["cset"], v["hc"]
+    med = lambda t: float(np.median(t))
+    d_fs = torch.from_numpy(v["fs"].astype(np.int32)).cuda()
+    d_ix = torch.from_numpy(v["index"].astype(np.int32)).cuda()
+    bound = bc.seekable_frames_resident_bound(total, n, True)
+    arc = torch.empty(bound, dtype=torch.uint8, device="cuda")
+    asz = v["asz"]
+    write_r = lambda: bc.compress_seekable_frames_resident(src.data_ptr(), total, d_fs.data_ptr(), n, R, arc.data_ptr(), bound, asz.data_ptr(), checksum=True,
+                                                           cdict_set=cset, d_dict_index_ptr=d_ix.data_ptr())
+    size_r = v["size_of"](write_r)
+    assert size_r == v["size_c"] and torch.equal(arc[:size_r], v["arcs"]["c"][:size_r]), "the resident archive differs from the host-array call's"
+    tw = alternating({"resident": write_r, "host_arrays": v["write_c"]}, bc.sync, reps)
+    bc.enable_timing(True); write_r(); kt = bc.kernel_times(); bc.enable_timing(False)
+    d_pick = torch.from_numpy(v["pick"].astype(np.int32)).cuda()
+    out, st, want = v["out"], v["st"], v["want"]
+    off = torch.zeros(N + 1, dtype=torch.int64, device="cuda")
+    wr = torch.zeros(N, dtype=torch.int32, device="cuda")
+    fetch_r = lambda: hc.read_frames_resident(d_pick.data_ptr(), N, out.data_ptr(), N * R, off.data_ptr(), wr.data_ptr(), st.data_ptr())
+    out.zero_(); st.fill_(1); fetch_r(); bc.sync()
+    assert not st.any().item() and torch.equal(out, want) and int(off[N].item()) == N * R, "the resident fetch differs from the content"
+    tf = alternating({"resident": fetch_r, "host_arrays": v["fetch_c"]}, bc.sync, reps)
+    gib = total / float(1 << 30)
+    return {"metric": "seekable_records_resident", "mib": total >> 20, "record_bytes": R, "records": n, "level": v["level"],
+            "write_resident_gibs": round(gib / med(tw["resident"]), 2), "write_resident_ms": [round(t * 1e3, 3) for t in tw["resident"]],
+            "write_host_arrays_gibs": round(gib / med(tw["host_arrays"]), 2), "write_host_arrays_ms": [round(t * 1e3, 3) for t in tw["host_arrays"]],
+            "write_resident_minus_host_arrays_ms": round((med(tw["resident"]) - med(tw["host_arrays"])) * 1e3, 3),
+            "device_plan_kernels_ms": round(sum(kt.get(k, (0.0, 0))[0] for k in PLAN_KERNELS) * 1e3, 4),
+            "write_resident_kernels_ms": {k: round(t[0] * 1e3, 4) for k, t in kt.items()},
+            "fetch_records": N, "fetch_distinct_records": int(len(set(v["pick"].tolist()))),
+            "fetch_resident_ms": [round(t * 1e3, 4) for t in tf["resident"]], "fetch_host_arrays_ms": [round(t * 1e3, 4) for t in tf["host_arrays"]]}
 
 
 def main():
@@ -168,6 +214,7 @@ def main():
     ap.add_argument("--range-bytes", type=int, default=4096)
     ap.add_argument("--records", action="store_true", help="record archives: one frame per record with dictionaries against 64 KiB fixed frames")
     ap.add_argument("--record-bytes", type=int, nargs="+", default=[1024, 4096])
+    ap.add_argument("--resident", action="store_true", help="with --records: the device-resident write and fetch against the host-array calls")
     a = ap.parse_args()
     if a.records:
         return records(a)

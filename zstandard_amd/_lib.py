@@ -177,6 +177,11 @@ def lib():
     L.zsmi_getFrameInfo_fromSeekable.argtypes = [vp, u32, pu64, pu64, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.zsmi_seekableReadFramesDevice.restype = i32; L.zsmi_seekableReadFramesDevice.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, ctypes.POINTER(u32)]
     L.zsmi_seekableReadFramesHost.restype = i32; L.zsmi_seekableReadFramesHost.argtypes = [vp, vp, vp, u32, vp, sz, vp, vp]
+    L.zsmi_seekableFramesResidentBound.restype = sz; L.zsmi_seekableFramesResidentBound.argtypes = [ull, u32, i32]
+    L.zsmi_compressSeekableFramesResident.restype = i32; L.zsmi_compressSeekableFramesResident.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, i32, i32]
+    L.zsmi_compressSeekableFramesResident_usingCDictSet.restype = i32
+    L.zsmi_compressSeekableFramesResident_usingCDictSet.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, i32, vp, vp]
+    L.zsmi_seekableReadFramesResident.restype = i32; L.zsmi_seekableReadFramesResident.argtypes = [vp, vp, vp, u32, u32, vp, u64, vp, vp, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -232,6 +237,8 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_compressSeekableFramesHost", "zsmi_compressSeekableFramesHost_usingCDictSet",
            "zsmi_openSeekable_usingDDictSet", "zsmi_openSeekableDevice_usingDDictSet", "zsmi_getFrameInfo_fromSeekable",
            "zsmi_seekableReadFramesDevice", "zsmi_seekableReadFramesHost",
+           "zsmi_seekableFramesResidentBound", "zsmi_compressSeekableFramesResident", "zsmi_compressSeekableFramesResident_usingCDictSet",
+           "zsmi_seekableReadFramesResident",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

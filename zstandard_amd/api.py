@@ -563,6 +563,19 @@ class SeekableHandle:
             raise RuntimeError(f"zsmi_seekableReadFramesDevice: {_error_name(self.L, rc)}")
         return written, frames.value
 
+    def read_frames_resident(self, d_frame_index_ptr, n, d_dst_ptr, dst_capacity, d_dst_offsets_ptr, d_written_ptr, d_status_ptr, align=1, codec=None):
+        """records by numbers that are DEVICE memory (uint32, n entries): nothing goes to the host.  The call lays the outputs out itself:
+        d_dst_offsets (device uint64[n + 1]) receives the running sum of the frames' content sizes, each rounded up to `align`; request
+        k's content lands at d_dst + d_dst_offsets[k], d_written (device uint32[n]) receives its size, d_status (device uint32[n]) 0 or
+        its code - frameIndex_tooLarge (100) for a number that names no frame, dstSize_tooSmall (70) for a place that ends behind
+        dst_capacity; neither touches its neighbours.  A number named twice is decoded twice.  zsmi_seekableReadFramesResident"""
+        codec = codec or self.codec
+        rc = self.L.zsmi_seekableReadFramesResident(codec.ctx, self.handle, ctypes.c_void_p(d_frame_index_ptr), n, align, ctypes.c_void_p(d_dst_ptr),
+                                                    dst_capacity, ctypes.c_void_p(d_dst_offsets_ptr), ctypes.c_void_p(d_written_ptr),
+                                                    ctypes.c_void_p(d_status_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableReadFramesResident: {_error_name(self.L, rc)}")
+
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`, from the handle's table"""
         co, do, cs, ds = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
@@ -835,6 +848,36 @@ class BatchCodec:
         r = _raise_if_error(self.L, getattr(self.L, name)(self.ctx, self._p(out), cap, s, self._p(fs) if len(fs) else None, len(fs), *head,
                                                           int(bool(checksum)), *tail))
         return out[:r].tobytes()
+
+    def seekable_frames_resident_bound(self, src_size, n, checksum=True) -> int:
+        """room the record archive of ANY split of src_size content bytes into n frames needs (zsmi_seekableFramesResidentBound): what
+        compress_seekable_frames_resident asks of dst_capacity, since the host never sees the sizes"""
+        return _raise_if_error(self.L, self.L.zsmi_seekableFramesResidentBound(src_size, n, int(bool(checksum))))
+
+    def compress_seekable_frames_resident(self, d_src_ptr, src_size, d_frame_sizes_ptr, n, max_frame_size, d_dst_ptr, dst_capacity, d_archive_size_ptr,
+                                          level=3, checksum=True, cdict=None, cdict_set=None, d_dict_index_ptr=0):
+        """compress_seekable_frames_device with its frame sizes (uint32, n entries) and dictionary indices in DEVICE memory: nothing goes
+        to the host.  src_size: the content bytes at d_src, which the sizes must add up to; max_frame_size: no size is above it (the call
+        is planned for it).  The archive is compress_seekable_frames_device's, byte for byte.  What the sizes or indices make impossible
+        goes to *d_archive_size_ptr as (uint64)-code: srcSize_wrong (72) for a size above max_frame_size, a frame that ends behind
+        src_size or sizes that sum to less; parameter_outOfBound (42) for an index that names no member.  dst_capacity must be at least
+        seekable_frames_resident_bound(src_size, n, checksum).
+        cdict_set, d_dict_index_ptr: frame i with member d_dict_index[i] (uint32, device, n entries; NO_DICT: none); d_dict_index_ptr = 0
+        with a set of one member, or cdict=: every frame uses it.  zsmi_compressSeekableFramesResident[_usingCDictSet]"""
+        if cdict is not None and cdict_set is not None:
+            raise ValueError("cdict_set= excludes cdict=")
+        if d_dict_index_ptr and cdict_set is None:
+            raise ValueError("d_dict_index_ptr= needs cdict_set=")
+        common = (self.ctx, ctypes.c_void_p(d_src_ptr), src_size, ctypes.c_void_p(d_frame_sizes_ptr), n, max_frame_size, ctypes.c_void_p(d_dst_ptr),
+                  dst_capacity, ctypes.c_void_p(d_archive_size_ptr))
+        if cdict is None and cdict_set is None:
+            name, rc = "zsmi_compressSeekableFramesResident", self.L.zsmi_compressSeekableFramesResident(*common, level, int(bool(checksum)))
+        else:
+            dset = cdict.as_set(self) if cdict is not None else cdict_set
+            name = "zsmi_compressSeekableFramesResident_usingCDictSet"
+            rc = self.L.zsmi_compressSeekableFramesResident_usingCDictSet(*common, int(bool(checksum)), dset.handle, ctypes.c_void_p(d_dict_index_ptr))
+        if rc:
+            raise RuntimeError(f"{name}: {_error_name(self.L, rc)}")
 
     def open_seekable_device(self, d_ptr, size, ddict=None, ddict_set=None):
         """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The

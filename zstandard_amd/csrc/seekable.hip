@@ -15,6 +15,11 @@
 // from where k_seek_gather copies its overlaps with the ranges - then k_seek_verify checks every decoded frame's size and checksum against
 // its entry and k_seek_range_status gives each range the code of its first failing frame.  A handle opened with a DDict set decodes every
 // frame with the dictionary its dictID names (a record archive's reader); a read by frame index is the read of those frames' extents.
+// Device-resident record archives: the same two paths planned from device memory.  A write whose sizes and dictionary indices are device
+// arrays (zsmi_compressSeekableFramesResident*) cleans the sizes with k_seek_guard, compresses through the body of the resident batch call
+// into staging sized for every split of the content, and shares the packing tail (seekPackArchive); a read whose frame numbers are a
+// device array (zsmi_seekableReadFramesResident) looks them up in the handle's device copy of the table, lays the outputs out with the
+// layout scan and decodes every request straight to its place - no union, no scratch: a frame named twice is decoded twice.
 
 #include "zsmi_status.h"          // the size word a compressed or decoded frame leaves
 #include "zsmi_wave.h"            // zs_block_copy, xxh64_quad, rd32
@@ -70,6 +75,36 @@ __global__ void k_seek_finish(const uint64_t *__restrict__ packedOffsets, uint32
     *archiveSize = e == ~0ull ? packedOffsets[n] + kSeekTableFixed + (uint64_t)n * entryBytes : 0ull - (e & 0xFFu);
 }
 
+// ---- the resident compress call's own kernels (zsmi_compressSeekableFramesResident*): the caller's sizes are device memory, so what
+// seekFramesBound judges on the host is judged here, a lane a frame.  rawOff: the running sum of the caller's sizes (n + 1 entries) ----
+// a frame the archive can hold: no longer than the host was told, and its content inside [0, srcSize)
+__device__ __forceinline__ bool zs_seek_frame_ok(uint32_t size, uint64_t off, uint32_t maxFrameSize, uint64_t srcSize)
+{
+    return size <= maxFrameSize && off <= srcSize && size <= srcSize - off;
+}
+// the CLEANED size list, which every later kernel reads in place of the caller's: a refused frame is an empty one at content offset 0, so no
+// kernel reads dSrc outside [0, srcSize) and the kept frames' bounds add up to no more than zs_compress_bound_split(srcSize, n)
+__global__ void __launch_bounds__(256)
+k_seek_guard(const uint32_t *__restrict__ frameSizes, const uint64_t *__restrict__ rawOff, uint32_t n, uint32_t maxFrameSize, uint64_t srcSize,
+             uint32_t *__restrict__ cleanSizes, uint64_t *__restrict__ cleanOff)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t size = frameSizes[i]; const uint64_t off = rawOff[i];
+    const bool ok = zs_seek_frame_ok(size, off, maxFrameSize, srcSize);
+    cleanSizes[i] = ok ? size : 0u; cleanOff[i] = ok ? off : 0ull;
+}
+// behind the compress call, in front of k_seek_table: a refused frame's size word says so (srcSize_wrong: over the dictionary index's
+// refusal, as in k_plan_refuse); sizes that end in front of srcSize fail the archive as frame n would - any failing frame's code comes first
+__global__ void __launch_bounds__(256)
+k_seek_refuse(const uint32_t *__restrict__ frameSizes, const uint64_t *__restrict__ rawOff, uint32_t n, uint32_t maxFrameSize, uint64_t srcSize,
+              uint32_t refusal, uint32_t *__restrict__ sizes, unsigned long long *err)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0 && rawOff[n] < srcSize) atomicMin(err, ((unsigned long long)n << 8) | zs_word_code(refusal));
+    if (i < n && !zs_seek_frame_ok(frameSizes[i], rawOff[i], maxFrameSize, srcSize)) sizes[i] = refusal;
+}
+
 struct ZsSeekItem { uint64_t out; uint32_t size, hash, slot, pad; };     // a decoded frame: where its bytes are, its entry, its status word
 struct ZsSeekPiece { uint64_t from, to; uint32_t len, pad; };            // one scratch frame's overlap with one range (a tile of it): scratch + from -> dDst + to
 struct ZsSeekSpan { uint32_t firstSlot, count; };                        // a range's frames: consecutive entries of the per-frame code array
@@ -98,14 +133,18 @@ __global__ void __launch_bounds__(256) k_seek_gather(const uint8_t *__restrict__
 }
 // one quad a decoded frame: its decoder status, its size against the entry (a frame the decoder found longer than its entry failed with
 // dstSize_tooSmall: that is the same disagreement), its checksum (flag set).  codes[q]: frame q's code (0: none), the frames in index order.
-__global__ void __launch_bounds__(64) k_seek_verify(const ZsSeekItem *__restrict__ items, uint32_t m, const uint32_t *__restrict__ status, int checksum, uint32_t *__restrict__ codes)
+// refused (null: no item is): the code of an item its planner refused and planned empty (zsmi_seekableReadFramesResident) - that is its
+// code, whatever the decoder made of nothing
+__global__ void __launch_bounds__(64) k_seek_verify(const ZsSeekItem *__restrict__ items, uint32_t m, const uint32_t *__restrict__ status, int checksum, uint32_t *__restrict__ codes,
+                                                    const uint32_t *__restrict__ refused)
 {
     const uint32_t q = blockIdx.x * 16 + (threadIdx.x >> 2);
     const bool real = q < m;
     const ZsSeekItem it = items[real ? q : m - 1u];
     const uint32_t s = real ? status[it.slot] : 0u;
-    uint32_t code = 0;
-    if (zs_word_is_error(s)) code = zs_word_code(s) == E_dstSize_tooSmall ? (uint32_t)E_corruption_detected : zs_word_code(s);
+    uint32_t code = refused && real ? refused[q] : 0u;
+    if (code) { }
+    else if (zs_word_is_error(s)) code = zs_word_code(s) == E_dstSize_tooSmall ? (uint32_t)E_corruption_detected : zs_word_code(s);
     else if (s != it.size) code = E_corruption_detected;
     const bool hash = real && checksum && code == 0;
     if (__ballot(hash)) {
@@ -134,6 +173,43 @@ __global__ void __launch_bounds__(256) k_seek_range_status(const ZsSeekSpan *__r
     }
     first = wave_min(first);
     if (lane == 0) status[r] = first == ~0u ? 0u : codes[s.firstSlot + first];
+}
+
+// ---- records by numbers that are device memory (zsmi_seekableReadFramesResident): the handle's table in device memory, an entry a frame,
+// and the two kernels that plan the read from it, a lane a request ----
+struct ZsSeekEntry { uint64_t cOff; uint32_t cSize, dSize, hash, pad; };  // where a frame's compressed bytes start, the entry's two sizes, its checksum (0 without the flag)
+// the bytes request k gets - its frame's Decompressed_Size, none for a number at or above the frame count - for the layout scan
+__global__ void __launch_bounds__(256)
+k_seek_request_sizes(const ZsSeekEntry *__restrict__ table, uint32_t nTable, const uint32_t *__restrict__ frameIndex, uint32_t nFrames, uint64_t *__restrict__ sizes)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= nFrames) return;
+    const uint32_t f = frameIndex[k];
+    sizes[k] = f < nTable ? table[f].dSize : 0ull;
+}
+// behind the layout: request k's decode item (its frame's extent -> its place, the entry's Decompressed_Size as capacity), its verify record
+// (status word k) and dWritten[k].  A number that names no frame (frameIndex_tooLarge), or a place that ends behind dstCapacity
+// (dstSize_tooSmall): refused[k] says so and the item is an EMPTY one - no source, no capacity - so the decoder touches neither a frame nor dDst for it
+__global__ void __launch_bounds__(256)
+k_seek_request_items(const ZsSeekEntry *__restrict__ table, uint32_t nTable, const uint32_t *__restrict__ frameIndex, uint32_t nFrames,
+                     const uint64_t *__restrict__ dstOffsets, uint64_t dstCapacity, uint8_t *dst, ZsDecItem *__restrict__ items,
+                     ZsSeekItem *__restrict__ verify, uint32_t *__restrict__ refused, uint32_t *__restrict__ written)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= nFrames) return;
+    const uint32_t f = frameIndex[k];
+    const bool named = f < nTable;
+    ZsSeekEntry e; e.cOff = 0; e.cSize = 0; e.dSize = 0; e.hash = 0; e.pad = 0;
+    if (named) e = table[f];
+    const uint64_t at = dstOffsets[k];
+    const bool fits = at <= dstCapacity && e.dSize <= dstCapacity - at;
+    const bool take = named && fits;
+    ZsDecItem it; it.srcOff = take ? e.cOff : 0ull; it.dstOff = take ? at : 0ull; it.srcSize = take ? e.cSize : 0u; it.dstCap = take ? e.dSize : 0u;
+    items[k] = it;
+    ZsSeekItem v; v.out = (uint64_t)(uintptr_t)(dst + it.dstOff); v.size = e.dSize; v.hash = e.hash; v.slot = k; v.pad = 0;
+    verify[k] = v;
+    refused[k] = !named ? (uint32_t)ZSMI_error_frameIndex_tooLarge : (!fits ? (uint32_t)ZSMI_error_dstSize_tooSmall : 0u);
+    written[k] = e.dSize;
 }
 
 // ---- host: parameters, bound, the table ----
@@ -242,7 +318,21 @@ extern "C" int zsmi_seekableFrameInfo(const void *src, size_t srcSize, uint32_t 
 // ---- compress ----
 // checksumFlag: the table's (each entry carries its frame's hash); frameChecksum: the frames' own Content_Checksum (the context's
 // ZSMI_c_checksumFlag) - the two are independent
-// The one path of every compress call here, its arguments checked by the caller: frame i is chunk i of one batch compress call with the
+// The tail of both compress paths, all of it device memory: the frames lie in context staging at dStageOff with their size words in dSizes
+// (an error word: a failed frame), dFrameSizes are the content sizes the entries state, dHash the entries' checksums (flag set), *dErr is
+// ~0 or holds what the caller found wrong already.  The gaps are closed into dDst, the table written behind the frames, and
+// *dArchiveSize is the archive's size or the lowest failing frame's code.
+static int seekPackArchive(zsmi_ctx *c, const uint64_t *dStageOff, const uint32_t *dFrameSizes, uint32_t n, const uint32_t *dSizes, const uint32_t *dHash,
+                           uint64_t *dPacked, unsigned long long *dErr, void *dDst, uint64_t *dArchiveSize, int checksumFlag)
+{
+    if (const int e = scanOffsets(c, "k_pack_offsets", dSizes, nullptr, n, 1u, nullptr, dPacked)) return e;
+    if (n) LAUNCH(c, "k_pack_copy", k_pack_copy, dim3(n), dim3(256), 0, (const uint8_t *)c->seek.dStage.p, dStageOff, dSizes, (const uint64_t *)dPacked, (uint8_t *)dDst);
+    LAUNCH(c, "k_seek_table", k_seek_table, dim3(std::max<uint32_t>(1, (n + 255) / 256)), dim3(256), 0, dSizes, (const uint64_t *)dPacked,
+           dHash, dFrameSizes, n, checksumFlag ? 1 : 0, (uint8_t *)dDst, dErr);
+    LAUNCH(c, "k_seek_finish", k_seek_finish, dim3(1), dim3(1), 0, (const uint64_t *)dPacked, n, checksumFlag ? 12u : 8u, (const unsigned long long *)dErr, dArchiveSize);
+    return c->launched();
+}
+// The one path of every compress call with HOST sizes, its arguments checked by the caller: frame i is chunk i of one batch compress call with the
 // selector `dict` (null: plain, at `level`), chunk i = dSrc[o_i, o_i + frameSizes[i]) with o the running sum of frameSizes (host, n entries).
 //   The per-frame lists the device needs - the frames' staging offsets (the running sum of their bounds) and their sizes - go up through
 // pinned buffers taken in turn (TurnBufs), as a read's lists do: nothing is copied back, nothing waited for.  The frames' content offsets,
@@ -251,7 +341,6 @@ static int seekCompressFrames(zsmi_ctx *c, const void *dSrc, const uint32_t *fra
                               int level, const ZsCDictSel *dict, int checksumFlag, int frameChecksum)
 {
     if (const int e = c->bind()) return e;
-    const uint32_t E = checksumFlag ? 12u : 8u;
     // device words: the uploaded lists - staging offsets [n] (64 bits), frame sizes [n]; (8-aligned) packed offsets [n + 1], content offsets
     // [n + 1], the error word; compressed sizes [n], hashes [n]
     const size_t listBytes = (size_t)n * (sizeof(uint64_t) + sizeof(uint32_t)), lists = (listBytes + 7) & ~(size_t)7;
@@ -277,13 +366,8 @@ static int seekCompressFrames(zsmi_ctx *c, const void *dSrc, const uint32_t *fra
             LAUNCH(c, "k_seek_hash", k_seek_hash, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, (const uint64_t *)dContent, dFrameSizes, n, dHash);
         }
     }
-    if (const int e = scanOffsets(c, "k_pack_offsets", (const uint32_t *)dSizes, nullptr, n, 1u, nullptr, dPacked)) return e;
-    if (n) LAUNCH(c, "k_pack_copy", k_pack_copy, dim3(n), dim3(256), 0, (const uint8_t *)c->seek.dStage.p, dStageOff, (const uint32_t *)dSizes, (const uint64_t *)dPacked, (uint8_t *)dDst);
     if (const int e = c->fill(dErr, 0xFF, sizeof(*dErr))) return e;
-    LAUNCH(c, "k_seek_table", k_seek_table, dim3(std::max<uint32_t>(1, (n + 255) / 256)), dim3(256), 0, (const uint32_t *)dSizes, (const uint64_t *)dPacked,
-           (const uint32_t *)dHash, dFrameSizes, n, checksumFlag ? 1 : 0, (uint8_t *)dDst, dErr);
-    LAUNCH(c, "k_seek_finish", k_seek_finish, dim3(1), dim3(1), 0, (const uint64_t *)dPacked, n, E, (const unsigned long long *)dErr, dArchiveSize);
-    return c->launched();
+    return seekPackArchive(c, dStageOff, dFrameSizes, n, dSizes, dHash, dPacked, dErr, dDst, dArchiveSize, checksumFlag);
 }
 // fixed-size frames: the sizes F, F, .., rest - the fixed-size case of the path above
 static int compressSeekableImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize,
@@ -322,6 +406,78 @@ extern "C" int zsmi_compressSeekableFramesDevice_usingCDictSet(zsmi_ctx *c, cons
                                                                uint64_t *dArchiveSize, int checksumFlag, const zsmi_cdictSet *set, const uint32_t *dictIndex)
 {
     return compressSeekableFramesImpl(c, dSrc, frameSizes, n, dDst, dstCapacity, dArchiveSize, 3, checksumFlag, set, dictIndex);
+}
+// ---- the same archive from sizes (and dictionary indices) that are DEVICE memory: nothing is copied to the host, nothing waited for, no
+// pinned buffer touched.  The host knows n, srcSize and maxFrameSize; its room for any split is zs_compress_bound_split (zsmi_device.h) ----
+static int seekResidentBound(uint64_t srcSize, uint32_t n, int checksum, uint64_t &bound)
+{
+    if (n > kSeekMaxFrames) return ZSMI_error_frameIndex_tooLarge;
+    if (srcSize > (uint64_t)n * kSeekMaxFrameSize) return ZSMI_error_parameter_outOfBound;       // (no legal split: n == 0 with content too)
+    bound = zs_compress_bound_split(srcSize, n) + kSeekTableFixed + (uint64_t)n * (checksum ? 12 : 8);
+    return 0;
+}
+extern "C" size_t zsmi_seekableFramesResidentBound(unsigned long long srcSize, uint32_t n, int checksumFlag)
+{
+    uint64_t bound;
+    if (const int e = seekResidentBound(srcSize, n, checksumFlag, bound)) return ZSMI_ERR(e);
+    return bound;
+}
+// The launch sequence (arguments checked by the caller).  scanOffsets over the caller's sizes gives the content offsets; k_seek_guard the
+// cleaned sizes and offsets every later kernel reads; k_compress_bounds and a second scan the staging offsets; the body of
+// zsmi_compressBatchResident[_usingCDictSet] compresses into the staging; k_seek_hash (table flag); k_seek_refuse marks what the guard
+// refused; the tail is seekCompressFrames'.
+static int seekCompressFramesResident(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, const uint32_t *dFrameSizes, uint32_t n, uint32_t maxFrameSize,
+                                      void *dDst, uint64_t *dArchiveSize, int level, const ResidentDict *dict, int checksumFlag)
+{
+    if (const int e = c->bind()) return e;
+    // device words, 64 bits: raw content offsets [n + 1], cleaned content offsets [n], bounds [n], staging offsets [n + 1], packed offsets
+    // [n + 1], the error word; 32 bits: cleaned sizes [n], compressed sizes [n], hashes [n]
+    if (!c->seek.dMeta.reserve((5 * (size_t)n + 4) * sizeof(uint64_t) + 3 * (size_t)n * sizeof(uint32_t))) return ZSMI_error_memory_allocation;
+    if (!c->seek.dStage.reserve(zs_compress_bound_split(srcSize, n) + 64)) return ZSMI_error_memory_allocation;
+    uint64_t *dRawOff = (uint64_t *)c->seek.dMeta.p, *dCleanOff = dRawOff + n + 1, *dBounds = dCleanOff + n, *dStageOff = dBounds + n, *dPacked = dStageOff + n + 1;
+    unsigned long long *dErr = (unsigned long long *)(dPacked + n + 1);
+    uint32_t *dCleanSizes = (uint32_t *)(dErr + 1), *dSizes = dCleanSizes + n, *dHash = dSizes + n;
+    const uint32_t grid = std::max<uint32_t>(1, (n + 255) / 256);
+    if (const int e = scanOffsets(c, "k_pack_offsets", dFrameSizes, nullptr, n, 1u, nullptr, dRawOff)) return e;
+    if (n) {
+        LAUNCH(c, "k_seek_guard", k_seek_guard, dim3(grid), dim3(256), 0, dFrameSizes, (const uint64_t *)dRawOff, n, maxFrameSize, srcSize, dCleanSizes, dCleanOff);
+        LAUNCH(c, "k_compress_bounds", k_compress_bounds, dim3(grid), dim3(256), 0, (const uint32_t *)dCleanSizes, n, dBounds);
+        if (const int e = scanOffsets(c, "k_pack_offsets", (const uint64_t *)dBounds, nullptr, n, 1u, nullptr, dStageOff)) return e;
+        if (const int e = compressBatchResidentImpl(c, dSrc, dCleanOff, dCleanSizes, n, maxFrameSize, c->seek.dStage.p, dStageOff, dSizes, level, dict)) return e;
+        if (checksumFlag) LAUNCH(c, "k_seek_hash", k_seek_hash, dim3((n + 15) / 16), dim3(64), 0, (const uint8_t *)dSrc, (const uint64_t *)dCleanOff, (const uint32_t *)dCleanSizes, n, dHash);
+    }
+    if (const int e = c->fill(dErr, 0xFF, sizeof(*dErr))) return e;
+    LAUNCH(c, "k_seek_refuse", k_seek_refuse, dim3(grid), dim3(256), 0, dFrameSizes, (const uint64_t *)dRawOff, n, maxFrameSize, srcSize,
+           zs_error_word(ZSMI_error_srcSize_wrong), dSizes, dErr);
+    return seekPackArchive(c, dStageOff, dCleanSizes, n, dSizes, dHash, dPacked, dErr, dDst, dArchiveSize, checksumFlag);
+}
+// the header's checks in its order, then the sequence above.  set: null for the plain form
+static int compressSeekableFramesResidentImpl(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, const uint32_t *dFrameSizes, uint32_t n, uint32_t maxFrameSize,
+                                              void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize, int level, int checksumFlag,
+                                              const zsmi_cdictSet *set, const uint32_t *dDictIndex)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (n > kSeekMaxFrames) return ZSMI_error_frameIndex_tooLarge;
+    if (n && !dFrameSizes) return ZSMI_error_GENERIC;
+    if (maxFrameSize > kSeekMaxFrameSize) return ZSMI_error_parameter_outOfBound;
+    ResidentDict dict;
+    if (set) { if (const int e = residentCDictSet(c, set, dDictIndex, n, level, dict)) return e; }      // (the set's level; without one: the caller's)
+    uint64_t bound;
+    if (const int e = seekResidentBound(srcSize, n, checksumFlag, bound)) return e;
+    if (dstCapacity < bound) return ZSMI_error_dstSize_tooSmall;
+    if (!dArchiveSize || !dDst || (srcSize && !dSrc)) return ZSMI_error_GENERIC;
+    return seekCompressFramesResident(c, dSrc, srcSize, dFrameSizes, n, maxFrameSize, dDst, dArchiveSize, level, set ? &dict : nullptr, checksumFlag);
+}
+extern "C" int zsmi_compressSeekableFramesResident(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, const uint32_t *dFrameSizes, uint32_t n,
+                                                   uint32_t maxFrameSize, void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize, int level, int checksumFlag)
+{
+    return compressSeekableFramesResidentImpl(c, dSrc, srcSize, dFrameSizes, n, maxFrameSize, dDst, dstCapacity, dArchiveSize, level, checksumFlag, nullptr, nullptr);
+}
+extern "C" int zsmi_compressSeekableFramesResident_usingCDictSet(zsmi_ctx *c, const void *dSrc, uint64_t srcSize, const uint32_t *dFrameSizes, uint32_t n,
+                                                                 uint32_t maxFrameSize, void *dDst, uint64_t dstCapacity, uint64_t *dArchiveSize,
+                                                                 int checksumFlag, const zsmi_cdictSet *set, const uint32_t *dDictIndex)
+{
+    return compressSeekableFramesResidentImpl(c, dSrc, srcSize, dFrameSizes, n, maxFrameSize, dDst, dstCapacity, dArchiveSize, 3, checksumFlag, set, dDictIndex);
 }
 // host buffers: the device call's checks on the host's arguments, then staged, run, copied back and waited for
 static size_t compressSeekableFramesHost(zsmi_ctx *c, void *dst, size_t dstCapacity, const void *src, const uint32_t *frameSizes, uint32_t n,
@@ -513,7 +669,7 @@ static int seekReadRanges(zsmi_ctx *c, const SeekTable &t, const uint8_t *dFrame
         if (nPieces) LAUNCH(c, "k_seek_gather", k_seek_gather, dim3((uint32_t)((small.size() + 3) / 4 + tiles.size())), dim3(256), 0, (const uint8_t *)dS, dDst, dPieces,
                             (uint32_t)small.size(), (uint32_t)nPieces);
     }
-    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((m + 15) / 16), dim3(64), 0, dItems, m, (const uint32_t *)dSt, t.checksum ? 1 : 0, dCodes);
+    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((m + 15) / 16), dim3(64), 0, dItems, m, (const uint32_t *)dSt, t.checksum ? 1 : 0, dCodes, (const uint32_t *)nullptr);
     LAUNCH(c, "k_seek_range_status", k_seek_range_status, dim3((nRanges + 3) / 4), dim3(256), 0, dSpans, nRanges, (const uint32_t *)dCodes, dStatus);
     return c->launched();
 }
@@ -526,8 +682,20 @@ struct zsmi_seekable {
     const uint8_t *dFrames = nullptr;    // frame i's compressed bytes: dFrames + t.cOff[i]
     void *dOwned = nullptr;              // a host archive's frames (exactly their bytes + 64: no reserve slack on what may be GiBs)
     ZsDictSel sel = ZsDictSel();         // a handle opened with a DDict set: the set's selector (borrowed: the set outlives the handle); else none
+    DevBuf dTable;                       // the table in device memory, a ZsSeekEntry a frame (none for an archive without frames): what the reads by device numbers look up
+    uint32_t maxDSize = 0;               // the largest Decompressed_Size: the capacity those reads plan their decode for
     ~zsmi_seekable() { if (dOwned) (void)hipFree(dOwned); }
 };
+// queued on the context's stream, from a list that lives until the caller's wait
+static int seekUploadTable(zsmi_ctx *c, zsmi_seekable &sk, std::vector<ZsSeekEntry> &entries)
+{
+    const SeekTable &t = sk.t;
+    if (t.n == 0) return 0;
+    entries.resize(t.n);
+    for (uint32_t i = 0; i < t.n; i++) { entries[i] = { t.cOff[i], t.cSize[i], t.dSize[i], t.hash[i], 0 }; sk.maxDSize = std::max(sk.maxDSize, t.dSize[i]); }
+    if (!sk.dTable.reserve(sizeof(ZsSeekEntry) * t.n)) return ZSMI_error_memory_allocation;
+    return c->toDevice(sk.dTable.p, entries.data(), sizeof(ZsSeekEntry) * t.n);
+}
 extern "C" zsmi_seekable *zsmi_openSeekable(zsmi_ctx *c, const void *archive, size_t size, int *err)
 {
     return makeHandle<zsmi_seekable>(err, [&](zsmi_seekable &sk) -> int {
@@ -539,6 +707,8 @@ extern "C" zsmi_seekable *zsmi_openSeekable(zsmi_ctx *c, const void *archive, si
         if (const int e = c->bind()) return e;
         if (hipMalloc(&sk.dOwned, bytes + 64) != hipSuccess) { (void)hipGetLastError(); sk.dOwned = nullptr; return ZSMI_error_memory_allocation; }
         sk.dFrames = (const uint8_t *)sk.dOwned;
+        std::vector<ZsSeekEntry> entries;
+        if (const int e = seekUploadTable(c, sk, entries)) { (void)c->wait(); return e; }
         return c->toDevice(sk.dOwned, archive, bytes) || c->wait() ? ZSMI_error_GENERIC : 0;
     });
 }
@@ -550,7 +720,11 @@ extern "C" zsmi_seekable *zsmi_openSeekableDevice(zsmi_ctx *c, const void *dArch
         if (const int e = c->bind()) return e;
         if (const int e = seekParseDevice(c, (const uint8_t *)dArchive, size, sk.t)) return e;
         sk.device = c->device; sk.dFrames = (const uint8_t *)dArchive;
-        return 0;
+        // (the table is known only behind the parse's wait: its copy is waited for here, so a read on any context finds it whole)
+        std::vector<ZsSeekEntry> entries;
+        const int e = seekUploadTable(c, sk, entries);
+        const int waited = sk.t.n ? c->wait() : 0;
+        return e ? e : waited;
     });
 }
 // the open calls with a DDict set: the call without one - its checks, in its order - then the set's own check; the handle keeps the set's selector
@@ -660,6 +834,41 @@ extern "C" int zsmi_seekableReadFramesHost(zsmi_ctx *c, const zsmi_seekable *sk,
     std::vector<uint64_t> offsets, lengths;
     if (const int e = seekFrameExtents(c, sk, frameIndex, nFrames, written, statuses, offsets, lengths)) return e;
     return zsmi_seekableReadRangesHost(c, sk, offsets.data(), lengths.data(), nFrames, dst, dstCapacity, written, statuses);
+}
+
+// records by numbers that are DEVICE memory: nothing is copied to the host, nothing waited for, no pinned buffer touched.  The requests'
+// sizes come from the handle's device table (k_seek_request_sizes), their places are the layout scan of zsmi_layoutOutputsDevice over them,
+// k_seek_request_items writes the decode items into c->dItems and the verify records; every request decodes straight to its place through
+// the body of zsmi_decompressBatchResident, planned for the table's largest Decompressed_Size; k_seek_verify leaves dStatus.  A frame
+// named twice is two items: decoded twice.
+extern "C" int zsmi_seekableReadFramesResident(zsmi_ctx *c, const zsmi_seekable *sk, const uint32_t *dFrameIndex, uint32_t nFrames, uint32_t align,
+                                               void *dDst, uint64_t dstCapacity, uint64_t *dDstOffsets, uint32_t *dWritten, uint32_t *dStatus)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (!sk || !dDstOffsets || (nFrames && (!dFrameIndex || !dWritten || !dStatus))) return ZSMI_error_GENERIC;
+    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
+    if (align == 0 || align > 4096 || (align & (align - 1))) return ZSMI_error_parameter_outOfBound;
+    if (nFrames && dstCapacity && !dDst) return ZSMI_error_GENERIC;
+    if (const int e = c->bind()) return e;
+    // device words: the requests' sizes [nFrames] (64 bits), verify records [nFrames]; decoder status [nFrames], refusals [nFrames]
+    if (!c->seek.dMeta.reserve((size_t)nFrames * (sizeof(uint64_t) + sizeof(ZsSeekItem) + 2 * sizeof(uint32_t))) ||
+        !c->dItems.reserve(sizeof(ZsDecItem) * (size_t)nFrames)) return ZSMI_error_memory_allocation;
+    uint64_t *dSizes = (uint64_t *)c->seek.dMeta.p;
+    ZsSeekItem *dVerify = (ZsSeekItem *)(dSizes + nFrames);
+    uint32_t *dSt = (uint32_t *)(dVerify + nFrames), *dRefused = dSt + nFrames;
+    const ZsSeekEntry *dTable = (const ZsSeekEntry *)sk->dTable.p;
+    const uint32_t grid = (nFrames + 255) / 256;
+    if (nFrames) LAUNCH(c, "k_seek_request_sizes", k_seek_request_sizes, dim3(grid), dim3(256), 0, dTable, sk->t.n, dFrameIndex, nFrames, dSizes);
+    if (const int e = scanOffsets(c, "k_layout_outputs", (const uint64_t *)dSizes, nullptr, nFrames, align, nullptr, dDstOffsets)) return e;
+    if (nFrames == 0) return c->launched();
+    LAUNCH(c, "k_seek_request_items", k_seek_request_items, dim3(grid), dim3(256), 0, dTable, sk->t.n, dFrameIndex, nFrames, (const uint64_t *)dDstOffsets, dstCapacity,
+           (uint8_t *)dDst, (ZsDecItem *)c->dItems.p, dVerify, dRefused, dWritten);
+    CapStats caps;
+    caps.add(sk->maxDSize, nFrames);
+    if (const int e = decodeItems(c, sk->dFrames, nFrames, dDst, caps, dSt, &sk->sel)) return e;
+    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((nFrames + 15) / 16), dim3(64), 0, (const ZsSeekItem *)dVerify, nFrames, (const uint32_t *)dSt, sk->t.checksum ? 1 : 0,
+           dStatus, (const uint32_t *)dRefused);
+    return c->launched();
 }
 
 // ---- the single-range calls: the one-range case of seekReadRanges ----

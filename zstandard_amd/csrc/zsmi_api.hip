@@ -554,7 +554,7 @@ static int residentCompressArgs(const zsmi_ctx *c, const void *dSrc, const uint6
 // host knows neither which chunks pick a dictionary nor whether any does, so there is no "no chunk has one: plain call" shortcut: the unit
 // slots are [prefixed: K][small: K][big: K * bigMax], the prefixed-unit kernels go over their upper bound (a unit a chunk) and leave on a
 // live count that may be 0.  Everything a sub-batch's kernels take about dictionaries is device memory the plan kernels wrote.
-struct ResidentDict { const ZsCDictEntry *dTable; uint32_t members; bool tables; const uint32_t *dDictIndex; };
+// (ResidentDict: zsmi_ctx.h - the resident record archives of seekable.hip run this body too)
 static int compressBatchResidentImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
                                      uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level, const ResidentDict *dict)
 {
@@ -737,16 +737,23 @@ extern "C" int zsmi_compressBatchDevice_usingCDictSet(zsmi_ctx *c, const void *d
 }
 // the resident form: the choice is device memory, so what resolveCDictSet judges on the host - an index out of range, a choice that gives
 // no chunk a dictionary - is the plan kernels' to find (plan_kernels.hip).  A NULL index: every chunk uses the one member
+static int residentCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dDictIndex, uint32_t n, int &level, ResidentDict &dict)
+{
+    level = set ? set->level : 3; dict = ResidentDict{ nullptr, 0u, false, nullptr };
+    if (!set) return 0;
+    if (n && !dDictIndex && set->members != 1) return ZSMI_error_GENERIC;
+    if (set->device != c->device) return ZSMI_error_parameter_unsupported;
+    dict = ResidentDict{ (const ZsCDictEntry *)set->dTable.p, set->members, set->tables, dDictIndex };
+    return 0;
+}
 extern "C" int zsmi_compressBatchResident_usingCDictSet(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes,
                                                         uint32_t n, uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes,
                                                         const zsmi_cdictSet *set, const uint32_t *dDictIndex)
 {
     if (const int e = residentCompressArgs(c, dSrc, dSrcOffsets, dSrcSizes, n, dDst, dDstOffsets, dDstSizes)) return e;
-    if (!set) return compressBatchResidentImpl(c, dSrc, dSrcOffsets, dSrcSizes, n, maxSrcSize, dDst, dDstOffsets, dDstSizes, 3, nullptr);
-    if (n && !dDictIndex && set->members != 1) return ZSMI_error_GENERIC;
-    if (set->device != c->device) return ZSMI_error_parameter_unsupported;
-    const ResidentDict dict = { (const ZsCDictEntry *)set->dTable.p, set->members, set->tables, dDictIndex };
-    return compressBatchResidentImpl(c, dSrc, dSrcOffsets, dSrcSizes, n, maxSrcSize, dDst, dDstOffsets, dDstSizes, set->level, &dict);
+    int level; ResidentDict dict;
+    if (const int e = residentCDictSet(c, set, dDictIndex, n, level, dict)) return e;
+    return compressBatchResidentImpl(c, dSrc, dSrcOffsets, dSrcSizes, n, maxSrcSize, dDst, dDstOffsets, dDstSizes, level, set ? &dict : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -792,19 +799,7 @@ bool zsmi_ctx::DecodeScratch::reserve(const DecodePlan &p)
     return ok;
 }
 
-// What a plan takes of a call's capacities: the largest, and how many items can hold more than one and more than two 64 KiB blocks.
-struct CapStats {
-    uint32_t maxCap = 0, over1 = 0, over2 = 0;
-    void add(uint32_t cap, uint32_t items = 1)
-    {
-        const uint32_t nb = (uint32_t)(((uint64_t)cap + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX);
-        maxCap = std::max(maxCap, cap);
-        if (nb > 1) over1 += items;
-        if (nb > 2) over2 += items;
-    }
-};
-
-// The plan of a call.  Block slots per item: 1; 2 when some item can hold more than one 64 KiB block; up to ZS_FAST_MAXBLOCKS when at least a
+// The plan of a call, from what it takes of the call's capacities (CapStats, zsmi_ctx.h).  Block slots per item: 1; 2 when some item can hold more than one 64 KiB block; up to ZS_FAST_MAXBLOCKS when at least a
 // quarter of the call's items can hold more than two (a call of large frames; a few large frames among many small ones go to the general kernel,
 // so the small ones do not pay for slots and launches they do not use).
 // The budget: a call whose buffers all fit asks the runtime nothing (the one-shot path).  When any buffer must grow, the scratch gets half of the

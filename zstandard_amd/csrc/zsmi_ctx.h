@@ -258,6 +258,27 @@ static int decompressBatchDeviceImpl(zsmi_ctx *c, const void *dSrc, const uint64
 static int resolveCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dictIndex, uint32_t n, int &level, ZsCDictSel &sel,
                            bool nullIsTheOneMember = false);
 static int ddictSetSel(const zsmi_ctx *c, const zsmi_ddictSet *set, struct ZsDictSel &sel);
+// ---- the bodies of the device-resident batch calls (zsmi_api.hip), for a feature whose descriptors are device memory too ----
+// compress: the body of zsmi_compressBatchResident[_usingCDictSet], its arguments checked by the caller.  dict: null for the plain call; a set
+// call's records and its choice in DEVICE memory.  residentCDictSet: what a zsmi_cdictSet * argument and a device choice ask of such a call -
+// the NULL-index rule, then the set's device; 0 with level and dict set (a null set: the plain call at level 3, which takes no dict)
+struct ResidentDict { const ZsCDictEntry *dTable; uint32_t members; bool tables; const uint32_t *dDictIndex; };
+static int residentCDictSet(const zsmi_ctx *c, const zsmi_cdictSet *set, const uint32_t *dDictIndex, uint32_t n, int &level, ResidentDict &dict);
+static int compressBatchResidentImpl(zsmi_ctx *c, const void *dSrc, const uint64_t *dSrcOffsets, const uint32_t *dSrcSizes, uint32_t n,
+                                     uint32_t maxSrcSize, void *dDst, const uint64_t *dDstOffsets, uint32_t *dDstSizes, int level, const ResidentDict *dict);
+// decompress: what a decode plan takes of a call's capacities - the largest, and how many items can hold more than one and more than two
+// 64 KiB blocks - and the body of every decode call: the item list (ZsDecItem) is in c->dItems, queued or copied there on the stream by the caller
+struct CapStats {
+    uint32_t maxCap = 0, over1 = 0, over2 = 0;
+    void add(uint32_t cap, uint32_t items = 1)
+    {
+        const uint32_t nb = (uint32_t)(((uint64_t)cap + ZS_BLOCK_MAX - 1) / ZS_BLOCK_MAX);
+        maxCap = maxCap > cap ? maxCap : cap;
+        if (nb > 1) over1 += items;
+        if (nb > 2) over2 += items;
+    }
+};
+static int decodeItems(zsmi_ctx *c, const void *dSrc, uint32_t n, void *dDst, const CapStats &caps, uint32_t *dDstSizes, const struct ZsDictSel *dict);
 template <class Size>
 static int scanOffsets(zsmi_ctx *c, const char *name, const Size *dSizes, const uint32_t *dStatus, uint32_t n, uint32_t align, uint32_t *dCaps, uint64_t *dOffsets);
 // a context of the one-shot pool (zsmi_api.hip), given back when the handle goes

@@ -92,6 +92,16 @@ __host__ __device__ __forceinline__ uint64_t zs_compress_bound(uint64_t srcSize)
 {
     return srcSize + (srcSize >> 8) + ((srcSize < (128u << 10)) ? (((128u << 10) - srcSize) >> 11) : 0) + 3 * (srcSize / ZS_BLOCK_MAX + 1) + 18;
 }
+// Room for the frames of EVERY split of at most srcSize content bytes into n chunks s_0 .. s_{n-1}: an upper bound of sum_i zs_compress_bound(s_i),
+// for whoever knows the sum and the count but not the sizes (the resident record archives: zsmi_seekableFramesResidentBound and the staging
+// behind it).  Term by term over the function above, with S = sum_i s_i <= srcSize:
+//   sum s_i = S;  sum (s_i >> 8) <= S >> 8;  the small-chunk term is at most (128 KiB) >> 11 = 64 a chunk;
+//   sum 3 * (s_i / 64 KiB + 1) <= 3 * (S >> 16) + 3 n;  18 a chunk
+// and every term grows with S, so srcSize stands for any smaller sum
+__host__ __device__ __forceinline__ uint64_t zs_compress_bound_split(uint64_t srcSize, uint64_t n)
+{
+    return srcSize + (srcSize >> 8) + 3 * (srcSize / ZS_BLOCK_MAX) + n * (64 + 3 + 18);
+}
 
 // unaligned little-endian loads.  memcpy keeps the alignment-1 fact visible to the compiler: a cast to an over-aligned
 // pointer lets it turn a wave-uniform address into a scalar load, which drops the low address bits.  (Host code reads
