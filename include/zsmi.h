@@ -520,6 +520,37 @@ size_t zsmi_compressSeekableFramesHost_usingCDictSet(zsmi_ctx *ctx, void *dst, s
  * such a handle; the one-shot and one-range calls (zsmi_decompressSeekable, zsmi_decompressSeekableDevice) have no dictionary form. */
 zsmi_seekable *zsmi_openSeekable_usingDDictSet(zsmi_ctx *ctx, const void *archive, size_t size, const zsmi_ddictSet *set, int *err);
 zsmi_seekable *zsmi_openSeekableDevice_usingDDictSet(zsmi_ctx *ctx, const void *dArchive, uint64_t size, const zsmi_ddictSet *set, int *err);
+/* Streams of frames that carry NO table - the packed output of a batch compress call, a pzstd file, `cat a.zst b.zst`, a log of one frame a
+ * record - opened for the same reads: the FRAME INDEX.  A table holds nothing the frames do not state themselves: the index has one entry a
+ * frame in stream order, skippable frames included (Decompressed_Size 0, Compressed_Size 8 + the frame's length: entries without content), and is
+ * defined by the size queries above.  From pos = 0, while pos < srcSize: c = zsmi_findFrameCompressedSize(src + pos, srcSize - pos), an error
+ * code being the result; d = zsmi_getFrameContentSize(src + pos, ..); the entry is {pos, c, d}; pos += c.  Bytes left over behind the last
+ * frame are srcSize_wrong, as that query answers them.  Behind the walker's own code, at the same frame, the table's field limits are
+ * frameParameter_unsupported: a frame that states no content size, a content size above 1 GiB, a compressed size above 0xFFFFFFFF.  More
+ * than 0x8000000 frames: frameIndex_tooLarge.  The first failing frame in stream order decides.  An empty stream is 0 frames.  srcSize > 0
+ * behind a NULL src: srcSize_wrong.  Only headers are read: a damaged payload shows when its frame is read.  An archive that has a table
+ * opens this way too and shows the table as a last entry of size 0.
+ * zsmi_countFrames, zsmi_buildSeekTable: host only, no device - header parses like the size queries.  The table is the seekable format's
+ * without checksums, 17 + 8 n bytes: src followed by these bytes is a seekable archive.  Returns the frames / the table's size, or an error
+ * code; dstCapacity below the size (or a NULL dst): dstSize_tooSmall, behind the stream's own code. */
+size_t zsmi_countFrames(const void *src, size_t srcSize);
+size_t zsmi_buildSeekTable(void *dst, size_t dstCapacity, const void *src, size_t srcSize);
+/* The handle is an ordinary zsmi_seekable whose table carries no checksums: every read call, zsmi_getFrameInfo_fromSeekable and the size
+ * getters work on it unchanged, with the lifetime rules of the open calls above (zsmi_openSeekable* keep refusing a stream without a table).
+ * One range over the whole content is the frame-parallel decode of a multi-frame stream.
+ * zsmi_openFrames: a host stream, judged on the host before a context is asked for - the stream's code, then a NULL ctx: init_missing - then
+ * copied to device memory the handle owns (zsmi_sizeofSeekable: srcSize) and waited for, once.
+ * zsmi_openFramesDevice: a stream in device memory, borrowed.  A NULL ctx: init_missing, first.  The index is built on the device, with the
+ * same entries and code as the host form: every place a magic number stands at is a candidate, found at memory bandwidth; each candidate's
+ * frame is walked by a lane of its own; the frames are the candidates reachable from offset 0, found by pointer doubling - a magic number
+ * inside a payload is never reached, even where it opens a whole valid frame.  Reads nothing outside [dSrc, dSrc + size).  The call waits for
+ * the stream twice (the candidate count, which sizes its scratch - memory_allocation when that cannot be reserved; the result) and once more
+ * for the table's device copy.
+ * The _usingDDictSet forms: as zsmi_openSeekable_usingDDictSet. */
+zsmi_seekable *zsmi_openFrames(zsmi_ctx *ctx, const void *src, size_t size, int *err);
+zsmi_seekable *zsmi_openFramesDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t size, int *err);
+zsmi_seekable *zsmi_openFrames_usingDDictSet(zsmi_ctx *ctx, const void *src, size_t size, const zsmi_ddictSet *set, int *err);
+zsmi_seekable *zsmi_openFramesDevice_usingDDictSet(zsmi_ctx *ctx, const void *dSrc, uint64_t size, const zsmi_ddictSet *set, int *err);
 /* zsmi_seekableFrameInfo from the handle's parsed table (no re-parse); index >= frames: frameIndex_tooLarge; NULL sk: GENERIC */
 int zsmi_getFrameInfo_fromSeekable(const zsmi_seekable *sk, uint32_t index, uint64_t *cOffset, uint64_t *dOffset, uint32_t *cSize, uint32_t *dSize);
 /* records by number: exactly zsmi_seekableReadRangesDevice / Host with offsets[k] = content offset of frame frameIndex[k] and lengths[k] = its

@@ -26,7 +26,11 @@ in the same process, the legs in turn, three rounds:
   write:  zsmi_compressSeekableFramesResident_usingCDictSet (sizes and indices in device memory) against (c)'s call; the archives must be
           equal; the kernels of one resident call, those that plan on the device summed
   fetch:  the same --ranges records through zsmi_seekableReadFramesResident (numbers in device memory, a frame named twice decoded twice)
-          against zsmi_seekableReadFramesDevice"""
+          against zsmi_seekableReadFramesDevice
+--index: streams of frames WITHOUT a table (zsmi_openFramesDevice) - the default archive with its table cut off and --record-mib of 1 KiB
+record frames: the open call against zsmi_openSeekableDevice on the same frames with their table, the index kernels one by one, the whole
+content through both handles, and the stream as one item of zsmi_decompressBatchDevice (index_legs' docstring).  One JSON line.
+  python tools/bench_seekable.py --index [--mib 1024] [--record-mib 256] [--one-item-limit 240]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -204,8 +208,127 @@ def resident_legs(a, bc, v):
             "fetch_resident_ms": [round(t * 1e3, 4) for t in tf["resident"]], "fetch_host_arrays_ms": [round(t * 1e3, 4) for t in tf["host_arrays"]]}
 
 
+def magic_positions(t):
+    """how many positions of the device byte tensor t hold one of the two frame magic numbers (the index's candidates, offset 0 apart)"""
+    total, step = 0, 64 << 20
+    for at in range(0, t.numel() - 3, step):
+        x = t[at:min(t.numel(), at + step + 3)].to(torch.int64)
+        w = x[:-3] | (x[1:-2] << 8) | (x[2:-1] << 16) | (x[3:] << 24)
+        total += int(((w == 0xFD2FB528) | ((w & 0xFFFFFFF0) == 0x184D2A50)).sum().item())
+    return total
+
+
+def index_one_item(a):
+    """--index-one-item (a process of its own, started by --index under a time limit): the stream of 64 KiB frames as ONE item of
+    zsmi_decompressBatchDevice - frame after frame on one wavefront, the only way in without the index.  Prints the seconds of one call."""
+    size, F = (a.mib or 1024) << 20, a.frame
+    bc = BatchCodec(0)
+    src = torch.from_numpy(D.zipf_log(size)).cuda()
+    bound = bc.seekable_bound(size, F, False)
+    arc = torch.empty(bound, dtype=torch.uint8, device="cuda"); asz = torch.zeros(1, dtype=torch.int64, device="cuda")
+    bc.compress_seekable_device(src.data_ptr(), size, arc.data_ptr(), bound, asz.data_ptr(), a.level, F, False); bc.sync()
+    n = (size + F - 1) // F
+    stream = int(asz.item()) - 17 - 8 * n
+    out = torch.empty(size, dtype=torch.uint8, device="cuda"); dsz = torch.zeros(1, dtype=torch.int32, device="cuda")
+    z = np.zeros(1, dtype=np.uint64)
+    t = time.perf_counter()
+    bc.decompress_device(arc.data_ptr(), z, np.array([stream], dtype=np.uint32), out.data_ptr(), z, np.array([size], dtype=np.uint32), dsz.data_ptr()); bc.sync()
+    t = time.perf_counter() - t
+    assert int(dsz.item()) == size and torch.equal(out, src), "the one item decoded to something else"
+    print(json.dumps({"one_item_seconds": round(t, 3)}), flush=True)
+    bc.close()
+
+
+def index_legs(a):
+    """--index: what it costs to have no table, and what the index buys.  The 1 GiB / 64 KiB-frame archive with its table cut off, and
+    --record-mib of 1 KiB record frames packed by zsmi_packFramesDevice; the legs of a comparison in turn in one process, three rounds:
+      open:   zsmi_openFramesDevice on the frames against zsmi_openSeekableDevice on the same frames with their table; the index kernels'
+              own times of one call; the candidates (places that hold a magic number) against the frames
+      read:   the whole content as one range through the indexed handle against the table-opened handle (the same frames, the same path)
+      item:   the same 64 KiB-frame stream as ONE item of zsmi_decompressBatchDevice, once, in a process of its own under --one-item-limit
+              seconds (sized from the general kernel's ~53 GiB/s over its pool of 3072 wavefronts: ~17 MiB/s a wavefront, a minute a GiB);
+              not finished inside it: said so, not tried again.  It runs last."""
+    import subprocess
+    size, F, level, reps = (a.mib or 1024) << 20, a.frame, a.level, 3
+    gib = size / float(1 << 30)
+    bc = BatchCodec(0)
+    L = bc.L
+    data = D.zipf_log(size)
+    src = torch.from_numpy(data).cuda()
+    n = (size + F - 1) // F
+    bound = bc.seekable_bound(size, F, False)
+    arc = torch.empty(bound, dtype=torch.uint8, device="cuda"); asz = torch.zeros(1, dtype=torch.int64, device="cuda")
+    bc.compress_seekable_device(src.data_ptr(), size, arc.data_ptr(), bound, asz.data_ptr(), level, F, False); bc.sync()
+    asize = int(asz.item()); stream = asize - 17 - 8 * n
+    ms = lambda v: [round(t * 1e3, 4) for t in v]
+    rep = {"metric": "frames_index", "gib": gib, "frame": F, "level": level, "frames": n, "stream_bytes": stream}
+
+    def open_close(fn):
+        def run():
+            fn().close()
+        return run
+
+    def open_legs(p, with_table, without, frames, key):
+        t = alternating({"table": open_close(lambda: bc.open_seekable_device(p, with_table)), "index": open_close(lambda: bc.open_frames_device(p, without))}, bc.sync, reps)
+        bc.enable_timing(True); h = bc.open_frames_device(p, without); kt = bc.kernel_times(); bc.enable_timing(False)
+        assert h.num_frames == frames
+        rep[key] = {"open_with_table_ms": ms(t["table"]), "open_frames_ms": ms(t["index"]), "no_table_costs_ms": round((np.median(t["index"]) - np.median(t["table"])) * 1e3, 4),
+                    "index_kernels_ms": {k: round(v[0] * 1e3, 4) for k, v in kt.items() if k.startswith("k_index")},
+                    "index_kernel_launches": {k: v[1] for k, v in kt.items() if k.startswith("k_index")}}
+        return h
+    hi = open_legs(arc.data_ptr(), asize, stream, n, "frames_64k")
+    rep["frames_64k"]["candidates"] = magic_positions(arc[:stream]) + 1
+    ht = bc.open_seekable_device(arc.data_ptr(), asize)
+    out = torch.empty(size, dtype=torch.uint8, device="cuda"); status = torch.ones(1, dtype=torch.int32, device="cuda")
+    whole = lambda h: (lambda: h.read_ranges_device([0], [size], out.data_ptr(), [0], status.data_ptr()))
+    for h in (hi, ht):
+        out.zero_(); status.fill_(1); whole(h)(); bc.sync()
+        assert int(status.item()) == 0 and torch.equal(out, src), "the whole content as one range differs"
+    t = alternating({"index": whole(hi), "table": whole(ht)}, bc.sync, reps)
+    rep["whole_content_indexed_ms"], rep["whole_content_table_ms"] = ms(t["index"]), ms(t["table"])
+    rep["whole_content_indexed_gibs"] = round(gib / float(np.median(t["index"])), 2); rep["whole_content_table_gibs"] = round(gib / float(np.median(t["table"])), 2)
+    hi.close(); ht.close()
+    # the record stream: 1 KiB frames from the batch call, packed - and the same frames as an archive of records, for its table
+    R = 1024
+    rsize = a.record_mib << 20
+    rn = rsize // R
+    fs = np.full(rn, R, dtype=np.uint32)
+    rbound = bc.seekable_frames_bound(fs, False)
+    rarc = torch.empty(rbound, dtype=torch.uint8, device="cuda")
+    bc.compress_seekable_frames_device(src.data_ptr(), fs, rarc.data_ptr(), rbound, asz.data_ptr(), level, False); bc.sync()
+    rasize = int(asz.item()); rstream = rasize - 17 - 8 * rn
+    rep["records_1k"] = {}
+    open_legs(rarc.data_ptr(), rasize, rstream, rn, "records_1k").close()
+    rep["records_1k"].update({"frames": rn, "stream_bytes": rstream, "candidates": magic_positions(rarc[:rstream]) + 1})
+    del out, rarc, arc, src
+    bc.close()
+    torch.cuda.empty_cache()
+    # last: the one item, once, in its own process under its limit (--one-item-limit 0: not run)
+    if a.one_item_limit <= 0:
+        rep["one_item"] = "not run"
+        print(json.dumps(rep), flush=True)
+        return
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--index-one-item", "--mib", str(size >> 20), "--frame", str(F), "--level", str(level)],
+                           capture_output=True, text=True, timeout=a.one_item_limit)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        if r.returncode == 0 and line:
+            sec = json.loads(line[-1])["one_item_seconds"]
+            rep["one_item_seconds"] = sec; rep["one_item_gibs"] = round(gib / sec, 4)
+            rep["indexed_over_one_item"] = round(sec / float(np.median(t["index"])), 1)
+        else:
+            rep["one_item"] = "failed: exit %d: %s" % (r.returncode, r.stderr[-300:])
+    except subprocess.TimeoutExpired:
+        rep["one_item"] = "not finished inside %d s; not tried again" % a.one_item_limit
+    print(json.dumps(rep), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--index", action="store_true", help="streams without a table: zsmi_openFramesDevice against zsmi_openSeekableDevice, reads through both, the stream as one item")
+    ap.add_argument("--index-one-item", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--record-mib", type=int, default=256, help="with --index: MiB of 1 KiB record frames")
+    ap.add_argument("--one-item-limit", type=int, default=240, help="with --index: seconds the one-item leg may take")
     ap.add_argument("--mib", type=int, default=0, help="content: 1024 MiB, or 256 MiB with --records")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--frame", type=int, default=65536)
@@ -216,6 +339,10 @@ def main():
     ap.add_argument("--record-bytes", type=int, nargs="+", default=[1024, 4096])
     ap.add_argument("--resident", action="store_true", help="with --records: the device-resident write and fetch against the host-array calls")
     a = ap.parse_args()
+    if a.index_one_item:
+        return index_one_item(a)
+    if a.index:
+        return index_legs(a)
     if a.records:
         return records(a)
     a.mib = a.mib or 1024

@@ -173,6 +173,12 @@ def lib():
     L.zsmi_compressSeekableFramesHost_usingCDictSet.argtypes = [vp, vp, sz, vp, vp, u32, i32, vp, vp]
     L.zsmi_openSeekable_usingDDictSet.restype = vp; L.zsmi_openSeekable_usingDDictSet.argtypes = [vp, vp, sz, vp, ctypes.POINTER(i32)]
     L.zsmi_openSeekableDevice_usingDDictSet.restype = vp; L.zsmi_openSeekableDevice_usingDDictSet.argtypes = [vp, vp, u64, vp, ctypes.POINTER(i32)]
+    L.zsmi_countFrames.restype = sz; L.zsmi_countFrames.argtypes = [vp, sz]
+    L.zsmi_buildSeekTable.restype = sz; L.zsmi_buildSeekTable.argtypes = [vp, sz, vp, sz]
+    L.zsmi_openFrames.restype = vp; L.zsmi_openFrames.argtypes = [vp, vp, sz, ctypes.POINTER(i32)]
+    L.zsmi_openFramesDevice.restype = vp; L.zsmi_openFramesDevice.argtypes = [vp, vp, u64, ctypes.POINTER(i32)]
+    L.zsmi_openFrames_usingDDictSet.restype = vp; L.zsmi_openFrames_usingDDictSet.argtypes = [vp, vp, sz, vp, ctypes.POINTER(i32)]
+    L.zsmi_openFramesDevice_usingDDictSet.restype = vp; L.zsmi_openFramesDevice_usingDDictSet.argtypes = [vp, vp, u64, vp, ctypes.POINTER(i32)]
     L.zsmi_getFrameInfo_fromSeekable.restype = i32
     L.zsmi_getFrameInfo_fromSeekable.argtypes = [vp, u32, pu64, pu64, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.zsmi_seekableReadFramesDevice.restype = i32; L.zsmi_seekableReadFramesDevice.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, ctypes.POINTER(u32)]
@@ -236,6 +242,8 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_seekableFramesBound", "zsmi_compressSeekableFramesDevice", "zsmi_compressSeekableFramesDevice_usingCDictSet",
            "zsmi_compressSeekableFramesHost", "zsmi_compressSeekableFramesHost_usingCDictSet",
            "zsmi_openSeekable_usingDDictSet", "zsmi_openSeekableDevice_usingDDictSet", "zsmi_getFrameInfo_fromSeekable",
+           "zsmi_countFrames", "zsmi_buildSeekTable", "zsmi_openFrames", "zsmi_openFramesDevice",
+           "zsmi_openFrames_usingDDictSet", "zsmi_openFramesDevice_usingDDictSet",
            "zsmi_seekableReadFramesDevice", "zsmi_seekableReadFramesHost",
            "zsmi_seekableFramesResidentBound", "zsmi_compressSeekableFramesResident", "zsmi_compressSeekableFramesResident_usingCDictSet",
            "zsmi_seekableReadFramesResident",

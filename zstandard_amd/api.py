@@ -98,6 +98,24 @@ def decompress_bound(src) -> int:
     return int(_lib.lib().zsmi_decompressBound(s, n))
 
 
+def count_frames(stream) -> int:
+    """the frames of a stream of frames, zstd and skippable (zsmi_countFrames: the frame index, host only); RuntimeError with the error's
+    name for a stream the index refuses"""
+    L = _lib.lib()
+    s, n = _buf(stream)
+    return _raise_if_error(L, L.zsmi_countFrames(s, n))
+
+
+def build_seek_table(stream) -> bytes:
+    """the seek table of the stream's frames, without checksums (zsmi_buildSeekTable, host only): stream + these bytes is a seekable archive"""
+    L = _lib.lib()
+    s, n = _buf(stream)
+    cap = 17 + 8 * count_frames(stream)
+    out = ctypes.create_string_buffer(cap)
+    size = _raise_if_error(L, L.zsmi_buildSeekTable(out, cap, s, n))
+    return out.raw[:size]
+
+
 class ZStdDecompress:
     """EPAM.Deltix.ZStd.ZStdDecompress (static). Sizes are 32-bit in the reference (size_t = UInt32, ZStdDecompress.cs:14)."""
 
@@ -338,17 +356,30 @@ class SeekableArchive:
     archive (zsmi_openSeekable: the frames go to device memory once, at the first call; close() frees them), every frame the batch
     touches decoded once."""
 
-    def __init__(self, archive, ddict=None, ddict_set=None):
+    def __init__(self, archive, ddict=None, ddict_set=None, frames=False):
         """ddict_set: a DecompressionDictSet the batch reads (read_many, read_frames) decode with - a record archive's dictionaries; ddict:
-        one DecompressionDict instead, the set ({}, unnamed=ddict).  Either must stay open as long as this object; read() takes none."""
+        one DecompressionDict instead, the set ({}, unnamed=ddict).  Either must stay open as long as this object; read() takes none.
+        frames: `archive` is a stream of frames without a table, opened through its frame index (from_frames)."""
         if ddict is not None and ddict_set is not None:
             raise ValueError("ddict_set= excludes ddict=")
         self.L = _lib.lib()
-        self.codec = self.handle = self._own_set = None
+        self.codec = self.handle = self._own_set = self._index = None
         self.ddict, self.ddict_set = ddict, ddict_set
         self.archive = bytes(archive)
-        self.num_frames = _raise_if_error(self.L, self.L.zsmi_seekableNumFrames(self.archive, len(self.archive)))
-        self.content_size = _raise_if_error(self.L, self.L.zsmi_seekableContentSize(self.archive, len(self.archive)))
+        self.frames = bool(frames)
+        if self.frames:
+            self.num_frames = count_frames(self.archive)
+            self.content_size = find_decompressed_size(self.archive)         # (every frame states its size: the index refuses one that does not)
+        else:
+            self.num_frames = _raise_if_error(self.L, self.L.zsmi_seekableNumFrames(self.archive, len(self.archive)))
+            self.content_size = _raise_if_error(self.L, self.L.zsmi_seekableContentSize(self.archive, len(self.archive)))
+
+    @classmethod
+    def from_frames(cls, stream, ddict=None, ddict_set=None):
+        """any stream of frames - no seek table needed: the packed output of a batch compress call, concatenated .zst files, a log of one
+        frame a record.  The frames are found by the frame index (zsmi_openFrames), skippable frames are entries of size 0; read_many /
+        read_frames / frame_info as for an archive, and read() is read_many's one range.  The index is checked when the object is made."""
+        return cls(stream, ddict=ddict, ddict_set=ddict_set, frames=True)
 
     def close(self):
         if self.handle:
@@ -377,8 +408,8 @@ class SeekableArchive:
                 self._own_set = DecompressionDictSet(self.codec, [], unnamed=self.ddict)
             dset = self._own_set
         err = ctypes.c_int(0)
-        self.handle = self.L.zsmi_openSeekable_usingDDictSet(self.codec.ctx, self.archive, len(self.archive), dset.handle if dset is not None else None,
-                                                             ctypes.byref(err))
+        open_call = self.L.zsmi_openFrames_usingDDictSet if self.frames else self.L.zsmi_openSeekable_usingDDictSet
+        self.handle = open_call(self.codec.ctx, self.archive, len(self.archive), dset.handle if dset is not None else None, ctypes.byref(err))
         if not self.handle:
             self.handle = None
             raise RuntimeError(_error_name(self.L, err.value))
@@ -440,6 +471,13 @@ class SeekableArchive:
         index = index if 0 <= index <= 0xFFFFFFFF else 0xFFFFFFFF          # (out of range either way: frameIndex_tooLarge)
         if self.handle is not None:                                          # (an opened archive: its parsed table, no re-parse)
             rc = self.L.zsmi_getFrameInfo_fromSeekable(self.handle, index, ctypes.byref(co), ctypes.byref(do), ctypes.byref(cs), ctypes.byref(ds))
+        elif self.frames:                                                    # (a stream not opened yet: the table the index writes, once)
+            if self._index is None:
+                self._index = np.frombuffer(build_seek_table(self.archive), dtype="<u4", count=2 * self.num_frames, offset=8).reshape(-1, 2).astype(np.uint64)
+            if index >= self.num_frames:
+                raise RuntimeError(_error_name(self.L, ERROR_FRAME_INDEX_TOO_LARGE))
+            c, d = self._index[:index, 0].sum(), self._index[:index, 1].sum()
+            return int(c), int(d), int(self._index[index, 0]), int(self._index[index, 1])
         else:
             rc = self.L.zsmi_seekableFrameInfo(self.archive, len(self.archive), index, ctypes.byref(co),
                                                ctypes.byref(do), ctypes.byref(cs), ctypes.byref(ds))
@@ -451,6 +489,8 @@ class SeekableArchive:
         """content bytes [offset, offset + length), clipped at the content's end (length None: to the end)"""
         if length is None:
             length = max(self.content_size - offset, 0)
+        if self.frames:
+            return self.read_many([(offset, length)])[0]
         out = ctypes.create_string_buffer(max(length, 1))
         r = _raise_if_error(self.L, self.L.zsmi_decompressSeekable(out, length, self.archive, len(self.archive), offset))
         return out.raw[:r]
@@ -504,10 +544,11 @@ def get_dict_id(dic) -> int:
 
 
 class SeekableHandle:
-    """An opened seekable archive in device memory (zsmi_openSeekableDevice; BatchCodec.open_seekable_device makes it).  Read-only: any
-    BatchCodec of the same device may read through it.  It must stay open until the work queued with it is done (BatchCodec.sync)."""
+    """An opened seekable archive in device memory (zsmi_openSeekableDevice; BatchCodec.open_seekable_device makes it), or a stream of
+    frames without a table opened through its frame index (zsmi_openFramesDevice; BatchCodec.open_frames_device: frames=True).  Read-only:
+    any BatchCodec of the same device may read through it.  It must stay open until the work queued with it is done (BatchCodec.sync)."""
 
-    def __init__(self, codec, d_ptr, size, ddict=None, ddict_set=None):
+    def __init__(self, codec, d_ptr, size, ddict=None, ddict_set=None, frames=False):
         if ddict is not None and ddict_set is not None:
             raise ValueError("ddict_set= excludes ddict=")
         self.L, self.codec = codec.L, codec
@@ -515,10 +556,11 @@ class SeekableHandle:
         self._own_set = DecompressionDictSet(codec, [], unnamed=ddict) if ddict is not None else None
         dset = self._own_set if ddict is not None else ddict_set
         err = ctypes.c_int(0)
-        self.handle = self.L.zsmi_openSeekableDevice_usingDDictSet(codec.ctx, ctypes.c_void_p(d_ptr), size, dset.handle if dset is not None else None,
-                                                                   ctypes.byref(err))
+        name = "zsmi_openFramesDevice" if frames else "zsmi_openSeekableDevice"
+        self.handle = getattr(self.L, name + "_usingDDictSet")(codec.ctx, ctypes.c_void_p(d_ptr), size, dset.handle if dset is not None else None,
+                                                               ctypes.byref(err))
         if not self.handle:
-            raise RuntimeError(f"zsmi_openSeekableDevice: {_error_name(self.L, err.value)}")
+            raise RuntimeError(f"{name}: {_error_name(self.L, err.value)}")
 
     @property
     def num_frames(self) -> int:
@@ -884,6 +926,12 @@ class BatchCodec:
         table is read back and checked here, once (RuntimeError with the error's name).  ddict_set: a DecompressionDictSet its reads
         decode with (a record archive's dictionaries); ddict: one DecompressionDict instead.  Either must outlive the handle."""
         return SeekableHandle(self, d_ptr, size, ddict=ddict, ddict_set=ddict_set)
+
+    def open_frames_device(self, d_ptr, size, ddict=None, ddict_set=None):
+        """any stream of frames at d_ptr[0, size) (device memory, borrowed) opened for the same reads: a SeekableHandle over the frame
+        index, which is built on the device here (zsmi_openFramesDevice; RuntimeError with the error's name for a stream it refuses).  One
+        range over the whole content is the frame-parallel decode of a multi-frame stream.  ddict, ddict_set: as open_seekable_device."""
+        return SeekableHandle(self, d_ptr, size, ddict=ddict, ddict_set=ddict_set, frames=True)
 
     def compress_host(self, src: np.ndarray, src_offsets, src_sizes, level=3, dictionary: bytes = b"", cdict=None, cdict_set=None, dict_index=None):
         """returns (arena uint8, dst_offsets uint64, dst_sizes uint32).  dictionary: one for every chunk (raw content or a formatted

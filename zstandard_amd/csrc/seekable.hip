@@ -20,18 +20,21 @@
 // into staging sized for every split of the content, and shares the packing tail (seekPackArchive); a read whose frame numbers are a
 // device array (zsmi_seekableReadFramesResident) looks them up in the handle's device copy of the table, lays the outputs out with the
 // layout scan and decodes every request straight to its place - no union, no scratch: a frame named twice is decoded twice.
+// Streams without a table (zsmi_openFrames*): the frame index (zsmi_index.h) - one entry a frame, read from the frames' own headers, on the
+// host by the serial walk, on the device by the k_index_* kernels - fills the same SeekTable, and the handle is the one above.
 
 #include "zsmi_status.h"          // the size word a compressed or decoded frame leaves
 #include "zsmi_wave.h"            // zs_block_copy, xxh64_quad, rd32
 #include "entropy_kernels.hip"    // k_pack_offsets, k_pack_copy
 #include "decode_kernels.hip"     // the decoder's error codes (E_*)
 #include "zsmi_ctx.h"
+#include "zsmi_index.h"           // the frame index of a stream without a table; the format's limits
 #include <algorithm>
 #include <new>
 
 static const uint32_t kSeekSkippableMagic = 0x184D2A5Eu, kSeekableMagic = 0x8F92EAB1u;
-static const uint64_t kSeekMaxFrames = 0x8000000ull, kSeekMaxFrameSize = 1ull << 30;
-static const uint64_t kSeekTableFixed = 17;          // skippable header (8) + footer (9)
+static const uint64_t kSeekMaxFrames = ZS_SEEK_MAX_FRAMES, kSeekMaxFrameSize = ZS_SEEK_MAX_FRAME_SIZE;
+static const uint64_t kSeekTableFixed = ZS_SEEK_TABLE_FIXED;          // skippable header (8) + footer (9)
 static const uint32_t kSeekHashAhead = 16;           // stripes a lane has in flight in k_seek_hash
 
 // ---- kernels ----
@@ -210,6 +213,152 @@ k_seek_request_items(const ZsSeekEntry *__restrict__ table, uint32_t nTable, con
     verify[k] = v;
     refused[k] = !named ? (uint32_t)ZSMI_error_frameIndex_tooLarge : (!fits ? (uint32_t)ZSMI_error_dstSize_tooSmall : 0u);
     written[k] = e.dSize;
+}
+
+// ---- the frame index of a stream that carries no table (zsmi_openFramesDevice; zsmi_index.h states the index and judges a frame).  The
+// true frames are the chain from offset 0 - each frame starts where the one before it ends - and a chain is serial: two dependent loads
+// that miss to HBM a frame.  Every frame starts with a magic number though, so: find every position that holds one (the CANDIDATES, with
+// offset 0 whatever its bytes: the chain's head), in ascending order - k_index_count, scanOffsets over the tiles' counts, k_index_emit;
+// walk the frame each candidate would start, a lane a candidate, and look its end up among the candidates: its successor - k_index_walk;
+// mark what the head reaches by pointer doubling over the successors - k_index_jump, ceil(log2(m + 1)) rounds for m candidates; and
+// compact the marked candidates, in order, into the table's entries - scanOffsets over the marks, k_index_table.  A magic number inside
+// a block's payload is a candidate like any other; nothing reaches it, even where it opens a whole valid frame, so it is no entry. ----
+#define ZS_INDEX_TILE 16384u             // the bytes of the stream a workgroup scans: 4 steps x 256 threads x 16 bytes
+static const uint32_t kIndexEnd = 0xFFFFFFFFu, kIndexBad = 0xFFFFFFFEu;      // a successor that is none: the stream's end; no candidate where the frame ends (or no frame)
+struct ZsIndexHead { uint64_t marked, err, refused; };     // what k_index_table leaves in front of the entries: the marked candidates (the scan's total),
+                                                           // ~0 or (position << 8 | code) of the chain's failure, how many marked candidates are refused frames
+// bit k: the four bytes at 16-byte group g's byte k are a magic number.  d: the group's four words and the word behind it
+__device__ __forceinline__ uint32_t zs_index_group_mask(const uint32_t d[5])
+{
+    uint32_t m = 0;
+    #pragma unroll
+    for (uint32_t k = 0; k < 16; k++) {
+        const uint64_t pair = ((uint64_t)d[k / 4 + 1] << 32) | d[k / 4];
+        m |= (uint32_t)zs_index_magic((uint32_t)(pair >> (8 * (k % 4)))) << k;
+    }
+    return m;
+}
+// The candidates of tile `tile`: mask[s] bit k stands for position tile * ZS_INDEX_TILE + s * 4096 + 16 * threadIdx.x + k, so the positions
+// ascend with (s, thread, k).  Thread t reads its 16 bytes and the 4 behind them - lane i at base + 16 i, a wavefront's loads one
+// contiguous KiB, the four steps' loads issued together - so a magic number that straddles two threads' or two tiles' bytes belongs to the
+// one position it starts at: seen once, by that position's owner.  A tile that ends within 4 bytes of the stream's end takes the slow
+// form, byte by byte with zeros behind the end: no byte outside [src, src + size) is read, and a position whose four bytes are not all
+// inside is no candidate.
+struct ZsIndexBytes16 { uint32_t w[4]; };
+__device__ __forceinline__ void zs_index_tile_masks(const uint8_t *__restrict__ src, uint64_t size, uint64_t tile, uint32_t mask[4])
+{
+    const uint64_t base = tile * ZS_INDEX_TILE + 16u * threadIdx.x;
+    if (size - tile * ZS_INDEX_TILE >= ZS_INDEX_TILE + 4u) {
+        ZsIndexBytes16 own[4]; uint32_t behind[4];
+        #pragma unroll
+        for (uint32_t s = 0; s < 4; s++) { const uint8_t *p = src + base + s * 4096u; __builtin_memcpy(&own[s], p, 16); behind[s] = zs_load32(p + 16); }
+        #pragma unroll
+        for (uint32_t s = 0; s < 4; s++) { const uint32_t d[5] = { own[s].w[0], own[s].w[1], own[s].w[2], own[s].w[3], behind[s] }; mask[s] = zs_index_group_mask(d); }
+    } else {
+        for (uint32_t s = 0; s < 4; s++) {
+            const uint64_t b = base + s * 4096u;
+            uint32_t d[5] = { 0, 0, 0, 0, 0 };
+            for (uint32_t j = 0; j < 20; j++) if (b + j < size) d[j >> 2] |= (uint32_t)src[b + j] << (8 * (j & 3));
+            const uint64_t whole = b + 4 <= size ? size - 3 - b : 0;                   // positions from b on whose four bytes are inside
+            mask[s] = zs_index_group_mask(d) & (whole >= 16 ? 0xFFFFu : (1u << whole) - 1u);
+        }
+    }
+    if (tile == 0 && threadIdx.x == 0) mask[0] |= 1u;                                   // offset 0: the head, whatever its bytes
+}
+__global__ void __launch_bounds__(256) k_index_count(const uint8_t *__restrict__ src, uint64_t size, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t waves[4];
+    uint32_t mask[4];
+    zs_index_tile_masks(src, size, blockIdx.x, mask);
+    const uint32_t n = wave_sum(__popc(mask[0]) + __popc(mask[1]) + __popc(mask[2]) + __popc(mask[3]));
+    if ((threadIdx.x & 63u) == 0) waves[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = waves[0] + waves[1] + waves[2] + waves[3];
+}
+// the same masks again; tileBase[tile]: the candidates in front of the tile (scanOffsets over the counts).  A step's candidates follow the
+// steps before it, a wavefront's the wavefronts before it, a thread's the lanes before it
+__global__ void __launch_bounds__(256) k_index_emit(const uint8_t *__restrict__ src, uint64_t size, const uint64_t *__restrict__ tileBase, uint64_t *__restrict__ pos, uint64_t m)
+{
+    __shared__ uint32_t waves[4][4];
+    uint32_t mask[4], before[4];
+    zs_index_tile_masks(src, size, blockIdx.x, mask);
+    const uint32_t wave = threadIdx.x >> 6;
+    #pragma unroll
+    for (uint32_t s = 0; s < 4; s++) {
+        const uint32_t n = __popc(mask[s]), incl = wave_incl_scan(n);
+        before[s] = incl - n;
+        if ((threadIdx.x & 63u) == 63u) waves[s][wave] = incl;
+    }
+    __syncthreads();
+    uint64_t at = tileBase[blockIdx.x];
+    #pragma unroll
+    for (uint32_t s = 0; s < 4; s++) {
+        uint32_t front = 0, all = 0;
+        #pragma unroll
+        for (uint32_t w = 0; w < 4; w++) { front += w < wave ? waves[s][w] : 0u; all += waves[s][w]; }
+        uint64_t out = at + front + before[s];
+        const uint64_t b = (uint64_t)blockIdx.x * ZS_INDEX_TILE + s * 4096u + 16u * threadIdx.x;
+        for (uint32_t bits = mask[s]; bits; bits &= bits - 1u, out++) if (out < m) pos[out] = b + (uint32_t)__ffs((int)bits) - 1u;      // (m: the room the counts asked for)
+        at += all;
+    }
+}
+// a lane a candidate: the frame it would start (zs_index_frame reads only [src + p, src + size)), and its successor - the candidate at
+// p + cSize, by binary search over the ascending positions; kIndexEnd where the frame ends the stream; kIndexBad where no candidate sits
+// (the chain fails THERE, should it come this way) or the frame is refused (it fails HERE).  The head starts marked.
+__global__ void __launch_bounds__(256)
+k_index_walk(const uint8_t *__restrict__ src, uint64_t size, const uint64_t *__restrict__ pos, uint32_t m, uint32_t *__restrict__ status, uint32_t *__restrict__ cSize,
+             uint32_t *__restrict__ dSize, uint32_t *__restrict__ next, uint32_t *__restrict__ mark)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t p = pos[i];
+    ZsIndexFrame f = {}; f.status = ZSMI_error_GENERIC;                                   // (a position outside the stream: one its owner changed under the call)
+    if (p < size) f = zs_index_frame(src + p, size - p);
+    uint32_t succ = kIndexBad;
+    if (!f.status) {
+        const uint64_t end = p + f.cSize;
+        if (end == size) succ = kIndexEnd;
+        else {
+            uint32_t lo = i + 1, hi = m;                                                   // (end > p: the first candidate at or behind end)
+            while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (pos[mid] < end) lo = mid + 1; else hi = mid; }
+            if (lo < m && pos[lo] == end) succ = lo;
+        }
+    }
+    status[i] = f.status; cSize[i] = (uint32_t)f.cSize; dSize[i] = f.dSize; next[i] = succ; mark[i] = i == 0;
+}
+// one round of pointer doubling.  In front of round k jump[i] is the candidate 2^k frames behind i and every candidate fewer than 2^k
+// frames behind the head is marked; a marked candidate marks its jump, then the jumps are squared (into the other array: a round reads
+// only what the round before wrote).  A mark seen while another lane of the round sets it marks a candidate the head reaches too: marks only grow
+__global__ void __launch_bounds__(256) k_index_jump(const uint32_t *__restrict__ jump, uint32_t *__restrict__ squared, uint32_t *mark, uint32_t m)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t j = jump[i];
+    if (j >= m) { squared[i] = j; return; }
+    if (mark[i]) mark[j] = 1u;
+    squared[i] = jump[j];
+}
+// the marked candidates, at the places the scan over the marks gives them, as the handle's entries.  The chain is one path, so one marked
+// candidate at most ends it badly: a refused frame, with its code, or a frame that ends where no frame starts - prefix_unknown if the
+// walker would find a word to judge there (5 bytes), else srcSize_wrong, as zsmi_findFrameCompressedSize answers those bytes
+__global__ void __launch_bounds__(256)
+k_index_table(const uint64_t *__restrict__ pos, const uint32_t *__restrict__ status, const uint32_t *__restrict__ cSize, const uint32_t *__restrict__ dSize,
+              const uint32_t *__restrict__ next, const uint32_t *__restrict__ mark, const uint64_t *__restrict__ slot, uint32_t m, uint64_t size,
+              ZsIndexHead *head, ZsSeekEntry *__restrict__ entries)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0) head->marked = slot[m];
+    if (i >= m || !mark[i]) return;
+    const uint64_t p = pos[i];
+    ZsSeekEntry e; e.cOff = p; e.cSize = cSize[i]; e.dSize = dSize[i]; e.hash = 0; e.pad = 0;
+    entries[slot[i]] = e;
+    if (status[i]) {
+        atomicMin((unsigned long long *)&head->err, ((unsigned long long)p << 8) | status[i]);
+        atomicAdd((unsigned long long *)&head->refused, 1ull);
+    } else if (next[i] == kIndexBad) {
+        const uint64_t end = p + e.cSize;
+        atomicMin((unsigned long long *)&head->err, ((unsigned long long)end << 8) | (size - end >= 5 ? (uint32_t)ZSMI_error_prefix_unknown : (uint32_t)ZSMI_error_srcSize_wrong));
+    }
 }
 
 // ---- host: parameters, bound, the table ----
@@ -744,6 +893,118 @@ extern "C" zsmi_seekable *zsmi_openSeekable_usingDDictSet(zsmi_ctx *c, const voi
 extern "C" zsmi_seekable *zsmi_openSeekableDevice_usingDDictSet(zsmi_ctx *c, const void *dArchive, uint64_t size, const zsmi_ddictSet *set, int *err)
 {
     return seekWithSet(c, zsmi_openSeekableDevice(c, dArchive, size, err), set, err);
+}
+
+// ---- streams of frames that carry no table: the frame index (zsmi_index.h) in place of the table's parse, then the same handle - its
+// table without checksums, its device copy through seekUploadTable, its set through seekWithSet; every read above takes it as it is ----
+extern "C" size_t zsmi_countFrames(const void *src, size_t srcSize) { return zs_index_count(src, srcSize); }
+extern "C" size_t zsmi_buildSeekTable(void *dst, size_t dstCapacity, const void *src, size_t srcSize) { return zs_index_build_table(dst, dstCapacity, src, srcSize); }
+static void seekIndexAdd(SeekTable &t, uint32_t cSize, uint32_t dSize)
+{
+    t.cSize.push_back(cSize); t.dSize.push_back(dSize); t.hash.push_back(0);
+    t.cOff.push_back(t.cOff.back() + cSize); t.dOff.push_back(t.dOff.back() + dSize);
+    t.n++;
+}
+static int seekIndexHost(const void *src, size_t size, SeekTable &t)
+{
+    t.cOff.assign(1, 0); t.dOff.assign(1, 0);
+    uint64_t n;
+    return zs_index_walk_host((const uint8_t *)src, size, n, [&t](uint64_t, uint32_t c, uint32_t d) { seekIndexAdd(t, c, d); });
+}
+// The index of a stream in device memory: the launch sequence above the kernels, with the call's two waits - for the candidate count m,
+// which sizes everything behind it (exactly m records: no guessed capacity), and for the result.  The tiles' counts and bases lie in the
+// context's size staging, the candidates' words in the seekable scratch; the handle keeps neither.
+static int seekIndexDevice(zsmi_ctx *c, const uint8_t *src, uint64_t size, SeekTable &t)
+{
+    t.cOff.assign(1, 0); t.dOff.assign(1, 0);
+    if (size == 0) return 0;
+    if (!src) return ZSMI_error_srcSize_wrong;
+    const uint64_t tiles64 = (size + ZS_INDEX_TILE - 1) / ZS_INDEX_TILE;
+    if (tiles64 > 0x7FFFFFFFull) return ZSMI_error_memory_allocation;
+    const uint32_t tiles = (uint32_t)tiles64;
+    // device words: the tiles' counts [tiles]; (8-aligned) the candidates in front of each tile [tiles + 1]
+    const size_t countBytes = ((size_t)tiles * sizeof(uint32_t) + 7) & ~(size_t)7;
+    if (!c->sSizes.reserve(countBytes + ((size_t)tiles + 1) * sizeof(uint64_t))) return ZSMI_error_memory_allocation;
+    uint32_t *dCounts = (uint32_t *)c->sSizes.p;
+    uint64_t *dTileBase = (uint64_t *)((uint8_t *)c->sSizes.p + countBytes);
+    LAUNCH(c, "k_index_count", k_index_count, dim3(tiles), dim3(256), 0, src, size, dCounts);
+    if (const int e = scanOffsets(c, "k_index_scan", (const uint32_t *)dCounts, nullptr, tiles, 1u, nullptr, dTileBase)) return e;
+    uint64_t m64 = 0;
+    if (c->toHost(&m64, dTileBase + tiles, sizeof m64) || c->wait()) return ZSMI_error_GENERIC;
+    if (m64 == 0) return ZSMI_error_GENERIC;                                              // (offset 0 is always one)
+    if (m64 >= kIndexBad) return ZSMI_error_memory_allocation;
+    const uint32_t m = (uint32_t)m64, grid = (m + 255) / 256;
+    // device words, 64 bits: positions [m], the marked candidates in front of each [m + 1], the head, the entries [m]; 32 bits: status,
+    // the two sizes, successors, the two jump arrays, marks [m each]
+    if (!c->seek.dMeta.reserve((2 * (size_t)m + 1) * sizeof(uint64_t) + sizeof(ZsIndexHead) + (size_t)m * sizeof(ZsSeekEntry) + 8 * (size_t)m * sizeof(uint32_t)))
+        return ZSMI_error_memory_allocation;
+    uint64_t *dPos = (uint64_t *)c->seek.dMeta.p, *dSlot = dPos + m;
+    ZsIndexHead *dHead = (ZsIndexHead *)(dSlot + m + 1);
+    ZsSeekEntry *dEntries = (ZsSeekEntry *)(dHead + 1);
+    uint32_t *dStatus = (uint32_t *)(dEntries + m), *dCSize = dStatus + m, *dDSize = dCSize + m, *dNext = dDSize + m, *dJump[2] = { dNext + m, dNext + 2 * (size_t)m }, *dMark = dNext + 3 * (size_t)m;
+    LAUNCH(c, "k_index_emit", k_index_emit, dim3(tiles), dim3(256), 0, src, size, (const uint64_t *)dTileBase, dPos, m64);
+    LAUNCH(c, "k_index_walk", k_index_walk, dim3(grid), dim3(256), 0, src, size, (const uint64_t *)dPos, m, dStatus, dCSize, dDSize, dNext, dMark);
+    const uint32_t *jump = dNext;
+    for (uint32_t round = 0; (1ull << round) < m64 + 1; round++) {
+        LAUNCH(c, "k_index_jump", k_index_jump, dim3(grid), dim3(256), 0, jump, dJump[round & 1u], dMark, m);
+        jump = dJump[round & 1u];
+    }
+    if (const int e = scanOffsets(c, "k_index_scan", (const uint32_t *)dMark, nullptr, m, 1u, nullptr, dSlot)) return e;
+    if (c->fill(dHead, 0, sizeof(ZsIndexHead)) || c->fill(&dHead->err, 0xFF, sizeof(dHead->err))) return ZSMI_error_GENERIC;
+    LAUNCH(c, "k_index_table", k_index_table, dim3(grid), dim3(256), 0, (const uint64_t *)dPos, (const uint32_t *)dStatus, (const uint32_t *)dCSize, (const uint32_t *)dDSize,
+           (const uint32_t *)dNext, (const uint32_t *)dMark, (const uint64_t *)dSlot, m, size, dHead, dEntries);
+    std::vector<uint8_t> back(sizeof(ZsIndexHead) + (size_t)m * sizeof(ZsSeekEntry));
+    if (c->launched() || c->toHost(back.data(), dHead, back.size()) || c->wait()) return ZSMI_error_GENERIC;
+    ZsIndexHead head;
+    memcpy(&head, back.data(), sizeof head);
+    if (head.marked > m64 || head.refused > head.marked) return ZSMI_error_GENERIC;
+    if (head.marked - head.refused > kSeekMaxFrames) return ZSMI_error_frameIndex_tooLarge;      // (the frames in front of a failure count first: the serial order)
+    if (head.err != ~0ull) return (int)(head.err & 0xFFu);
+    for (uint64_t i = 0; i < head.marked; i++) {
+        ZsSeekEntry e;
+        memcpy(&e, back.data() + sizeof head + i * sizeof e, sizeof e);
+        if (e.cOff != t.cOff.back()) return ZSMI_error_GENERIC;                             // (a chain that is none: the stream changed under the call)
+        seekIndexAdd(t, e.cSize, e.dSize);
+    }
+    return t.cOff.back() == size ? 0 : ZSMI_error_GENERIC;
+}
+// zsmi_openFrames judges the stream on the host before it asks for a context, as zsmi_openSeekable its table; the frames' bytes - all of
+// the stream - go to device memory the handle owns
+extern "C" zsmi_seekable *zsmi_openFrames(zsmi_ctx *c, const void *src, size_t size, int *err)
+{
+    return makeHandle<zsmi_seekable>(err, [&](zsmi_seekable &sk) -> int {
+        if (const int e = seekIndexHost(src, size, sk.t)) return e;
+        if (!c) return ZSMI_error_init_missing;
+        sk.device = c->device;
+        if (size == 0) return 0;
+        if (const int e = c->bind()) return e;
+        if (hipMalloc(&sk.dOwned, size + 64) != hipSuccess) { (void)c->launched(); sk.dOwned = nullptr; return ZSMI_error_memory_allocation; }
+        sk.dFrames = (const uint8_t *)sk.dOwned;
+        std::vector<ZsSeekEntry> entries;
+        if (const int e = seekUploadTable(c, sk, entries)) { (void)c->wait(); return e; }
+        return c->toDevice(sk.dOwned, src, size) || c->wait() ? ZSMI_error_GENERIC : 0;
+    });
+}
+extern "C" zsmi_seekable *zsmi_openFramesDevice(zsmi_ctx *c, const void *dSrc, uint64_t size, int *err)
+{
+    return makeHandle<zsmi_seekable>(err, [&](zsmi_seekable &sk) -> int {
+        if (!c) return ZSMI_error_init_missing;
+        if (const int e = c->bind()) return e;
+        if (const int e = seekIndexDevice(c, (const uint8_t *)dSrc, size, sk.t)) return e;
+        sk.device = c->device; sk.dFrames = (const uint8_t *)dSrc;
+        std::vector<ZsSeekEntry> entries;
+        const int e = seekUploadTable(c, sk, entries);
+        const int waited = sk.t.n ? c->wait() : 0;
+        return e ? e : waited;
+    });
+}
+extern "C" zsmi_seekable *zsmi_openFrames_usingDDictSet(zsmi_ctx *c, const void *src, size_t size, const zsmi_ddictSet *set, int *err)
+{
+    return seekWithSet(c, zsmi_openFrames(c, src, size, err), set, err);
+}
+extern "C" zsmi_seekable *zsmi_openFramesDevice_usingDDictSet(zsmi_ctx *c, const void *dSrc, uint64_t size, const zsmi_ddictSet *set, int *err)
+{
+    return seekWithSet(c, zsmi_openFramesDevice(c, dSrc, size, err), set, err);
 }
 extern "C" void zsmi_closeSeekable(zsmi_seekable *sk) { delete sk; }
 extern "C" int zsmi_getFrameInfo_fromSeekable(const zsmi_seekable *sk, uint32_t index, uint64_t *cOffset, uint64_t *dOffset, uint32_t *cSize, uint32_t *dSize)
