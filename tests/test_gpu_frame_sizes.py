@@ -1,6 +1,7 @@
 """zsmi_getFrameSizesBatchDevice (k_frame_sizes: the container walker, a lane an item) against the host calls, which
 tests/test_frame_sizes_host.py pins to libzstd and oracle D; and zsmi_layoutOutputsDevice (the packer's tiled offset scan in its general
-form) against numpy, below, at and above one tile of 2048 items.  Items sit at odd offsets with gaps in a buffer of canary bytes: a walk
+form) against numpy, below, at and above one tile of 2048 items and on both sides of 1024 tiles, where the one workgroup that scans the
+tile sums gives a thread a second sum.  Items sit at odd offsets with gaps in a buffer of canary bytes: a walk
 that leaves its item reads something else than the host call, which sees the item alone."""
 import numpy as np
 import pytest
@@ -96,8 +97,21 @@ LIMIT = 0xFFFFFF88            # the largest size that is no error code
 @pytest.mark.parametrize("align", [1, 64, 4096])
 @pytest.mark.parametrize("n", [1, 1025, 2048, 2049, 3000])
 def test_layout_equals_numpy(codec, H, n, align):
+    layout_equals_numpy(codec, H, n, align, 300000)
+
+
+# the single workgroup of 1024 threads that scans the tile sums (k_pack_scan_tiles) gives a thread ceil(tiles / 1024) of them: one up to
+# 1024 tiles of 2048 items (tests/_borders.py SCAN_LEVEL, held against the source by tests/test_borders_host.py).  Exactly 1024 tiles, one
+# item more (a thread two sums, the last threads none), 1025 tiles and one item
+@pytest.mark.parametrize("align", [1, 64])
+@pytest.mark.parametrize("n", [2097152, 2097153, 2099201])
+def test_layout_equals_numpy_at_the_scans_second_level(codec, H, n, align):
+    layout_equals_numpy(codec, H, n, align, 5001)
+
+
+def layout_equals_numpy(codec, H, n, align, top):
     rng = np.random.default_rng(n * 8191 + align)
-    sizes = rng.integers(0, 300000, n).astype(np.uint64)
+    sizes = rng.integers(0, top, n).astype(np.uint64)
     status = np.zeros(n, dtype=np.uint32)
     special = [LIMIT, LIMIT + 1, S.UNKNOWN, S.ERROR, 1 << 32, 0, 1, align, align + 1, (1 << 40) + 5]
     at = rng.choice(n, min(n, len(special)), replace=False)
