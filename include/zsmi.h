@@ -604,6 +604,39 @@ int zsmi_compressSeekableFramesResident_usingCDictSet(zsmi_ctx *ctx, const void 
  * dstCapacity > 0 and nFrames > 0: GENERIC.  nFrames == 0 writes dDstOffsets[0] = 0 and nothing else. */
 int zsmi_seekableReadFramesResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint32_t *dFrameIndex, uint32_t nFrames, uint32_t align,
                                     void *dDst, uint64_t dstCapacity, uint64_t *dDstOffsets, uint32_t *dWritten, uint32_t *dStatus);
+/* The record splitter: the GPU step that locates the records.  A buffer of delimited records (lines, JSON lines, CSV rows) -> the frame
+ * sizes of a record archive and, a frame, the number of its first record.  The rule (zstandard_amd/csrc/zsmi_split.h states it in code),
+ * for src[0, srcSize), a delimiter byte delim, targetSize T (0: a frame a record) and maxFrameSize M:
+ *  1. A record ends behind each byte equal to delim; bytes behind the last delimiter are a last record without one.  records: the
+ *     delimiters, + 1 for such a tail.  (One byte: CRLF text splits at LF and the CR stays in the record.)
+ *  2. A record of L <= M bytes is one piece; a longer one is cut at multiples of M from its own start: ceil(L / M) pieces.
+ *     pieces <= records + srcSize / M.
+ *  3. From pos = 0, while pos < srcSize: T == 0: the frame ends at the first piece end behind pos; T > 0: at the last piece end in
+ *     (pos, pos + T], or, if there is none, at the first piece end behind pos (greedy: the whole pieces that fit in T, a longer piece
+ *     alone).  No frame is above M; the sizes sum to srcSize.
+ *  4. firstRecord[i] = the delimiters in src[0, start of frame i); firstRecord[n] = records.  THE LOOKUP: the frame record r starts in is
+ *     the first i with firstRecord[i] >= r when that entry equals r, else i - 1.  A cut record always starts a frame.
+ * Checked on the host, in this order: a NULL ctx (device calls): init_missing; delim outside 0..255: parameter_outOfBound; maxFrameSize 0
+ * or above 1 GiB: parameter_outOfBound; targetSize > maxFrameSize: parameter_outOfBound; maxPieces > 0x80000000: parameter_outOfBound;
+ * srcSize > 0 behind a NULL source: srcSize_wrong; a NULL dResult / dRecords, or a NULL dFrameSizes with maxPieces > 0: GENERIC.
+ * srcSize == 0: 0 frames, 0 records, firstRecord[0] = 0.
+ * zsmi_splitRecords: host only, no device - the rule's loop as written.  Returns the frame count or an error code.  frameSizes == NULL only
+ * counts; more frames than capacity: dstSize_tooSmall, nothing written behind capacity.  firstRecord (capacity + 1 entries) and records
+ * may be NULL.
+ * zsmi_countRecordsDevice: *dRecords (device memory) = records.  Queues a count kernel and a sum: no wait, no host copy.
+ * zsmi_splitRecordsDevice: only queues work on the context's stream - no device-to-host copy, no wait, no pinned staging (a context buffer
+ * may grow: 12 bytes a 16 KiB of source and 40 bytes a piece of maxPieces; memory_allocation, before anything is queued, when that cannot
+ * be reserved).  The host is told maxPieces (zsmi_countRecordsDevice's answer + srcSize / maxFrameSize always suffices): scratch, grids
+ * and the rounds of pointer doubling are planned for it.  dFrameSizes: maxPieces entries; dFirstRecord: maxPieces + 1, may be NULL;
+ * dResult: three device words - [0] the frame count n or (uint64_t)-code, [1] records, [2] pieces.  pieces > maxPieces: [0] =
+ * -dstSize_tooSmall, no list is written, [1] and [2] are valid (exact while pieces <= 0x80000000) so that a second call can be sized.
+ * Nothing is written outside the arrays as sized here, nothing read outside [dSrc, dSrc + srcSize).  When it fits, dFrameSizes[0, n),
+ * dFirstRecord[0, n] and n are zsmi_splitRecords' for the same bytes. */
+size_t zsmi_splitRecords(const void *src, size_t srcSize, int delim, uint32_t targetSize, uint32_t maxFrameSize,
+                         uint32_t *frameSizes, uint64_t *firstRecord, size_t capacity, uint64_t *records);
+int zsmi_countRecordsDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, int delim, uint64_t *dRecords);
+int zsmi_splitRecordsDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, int delim, uint32_t targetSize, uint32_t maxFrameSize,
+                            uint32_t maxPieces, uint32_t *dFrameSizes, uint64_t *dFirstRecord, uint64_t *dResult);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

@@ -30,7 +30,10 @@ in the same process, the legs in turn, three rounds:
 --index: streams of frames WITHOUT a table (zsmi_openFramesDevice) - the default archive with its table cut off and --record-mib of 1 KiB
 record frames: the open call against zsmi_openSeekableDevice on the same frames with their table, the index kernels one by one, the whole
 content through both handles, and the stream as one item of zsmi_decompressBatchDevice (index_legs' docstring).  One JSON line.
-  python tools/bench_seekable.py --index [--mib 1024] [--record-mib 256] [--one-item-limit 240]"""
+  python tools/bench_seekable.py --index [--mib 1024] [--record-mib 256] [--one-item-limit 240]
+--split: the record splitter (zsmi_splitRecordsDevice) on the same text stream, split at newlines: the call and its kernels one by one at
+targetSize 0 and --target, against k_index_count / k_index_emit on the same buffer (split_legs' docstring).  One JSON line.
+  python tools/bench_seekable.py --split [--mib 1024] [--frame 65536] [--target 4096]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -323,8 +326,58 @@ def index_legs(a):
     print(json.dumps(rep), flush=True)
 
 
+def split_legs(a):
+    """--split: the record splitter on the Zipf log stream (text lines, ~150 bytes each) in device memory.  For targetSize 0 and --target:
+    zsmi_splitRecordsDevice, three calls each followed by a synchronisation; its kernels one by one (HIP events, three calls: the sorted
+    times of each); and, on the same buffer in the same process, k_index_count / k_index_emit - zsmi_openFramesDevice refuses text, but
+    only after both have scanned it - three calls too.  The chain cost (rounds x nodes of k_index_jump, targetSize > 0 only) is listed apart."""
+    size, M, reps = (a.mib or 1024) << 20, a.frame, 3
+    gib = size / float(1 << 30)
+    bc = BatchCodec(0)
+    src = torch.from_numpy(D.zipf_log(size)).cuda()
+    words = torch.zeros(4, dtype=torch.int64, device="cuda")
+    bc.count_records_device(src.data_ptr(), size, words.data_ptr()); bc.sync()
+    records = int(words[0].item())
+    mp = BatchCodec.split_pieces_bound(records, size, M)
+    fs = torch.zeros(mp, dtype=torch.int32, device="cuda"); fr = torch.zeros(mp + 1, dtype=torch.int64, device="cuda")
+    ms = lambda v: [round(t * 1e3, 4) for t in v]
+
+    def kernels(fn, prefix):
+        runs = []
+        for _ in range(reps):
+            bc.enable_timing(True)
+            try:
+                fn()
+            except RuntimeError:
+                pass                                               # (the index refuses text - behind its scan)
+            runs.append(bc.kernel_times()); bc.enable_timing(False)
+        names = [k for k in runs[0] if k.startswith(prefix)]
+        return {k: sorted(round(r[k][0] * 1e3, 4) for r in runs) for k in names}, {k: runs[0][k][1] for k in names}
+    rep = {"metric": "split_records", "gib": gib, "max_frame_size": M, "records": records, "max_pieces": mp,
+           "count_records_ms": ms(alternating({"count": lambda: bc.count_records_device(src.data_ptr(), size, words.data_ptr())}, bc.sync, reps)["count"])}
+    rep["index_kernels_ms"], _ = kernels(lambda: bc.open_frames_device(src.data_ptr(), size), "k_index")
+    rep["index_kernels_ms"] = {k: v for k, v in rep["index_kernels_ms"].items() if k in ("k_index_count", "k_index_emit")}
+    for T in (0, a.target):
+        call = lambda: bc.split_records_device(src.data_ptr(), size, mp, fs.data_ptr(), fr.data_ptr(), words.data_ptr() + 8, target_size=T, max_frame_size=M)
+        t = alternating({"split": call}, bc.sync, reps)["split"]
+        n, recs, pieces = (int(v) for v in words[1:4].tolist())
+        assert recs == records and pieces <= mp and 0 < n <= pieces, (n, recs, pieces)
+        assert int(fs[:n].to(torch.int64).sum().item()) == size and int(fr[n].item()) == records, "the sizes do not sum to the source"
+        kt, launches = kernels(call, "k_")
+        rounds = launches.get("k_index_jump", 0)
+        rep["target_%d" % T] = {"frames": n, "pieces": pieces, "split_call_ms": ms(t), "split_call_gibs": round(gib / float(np.median(t)), 1), "kernels_ms": kt,
+                                "chain_rounds": rounds, "chain_nodes": mp, "chain_rounds_x_nodes": rounds * mp, "chain_ms": kt.get("k_index_jump", [0.0] * reps)}
+    c0 = rep["target_0"]["kernels_ms"]
+    rep["k_split_count_over_k_index_count"] = round(c0["k_split_count"][1] / rep["index_kernels_ms"]["k_index_count"][1], 3)
+    rep["k_split_emit_over_k_index_emit"] = round(c0["k_split_emit"][1] / rep["index_kernels_ms"]["k_index_emit"][1], 3)
+    bc.close()
+    print(json.dumps(rep), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--split", action="store_true", help="the record splitter on the text stream: the call, its kernels, k_index_count / k_index_emit on the same buffer")
+    ap.add_argument("--target", type=int, default=4096, help="with --split: the targetSize of the second leg")
     ap.add_argument("--index", action="store_true", help="streams without a table: zsmi_openFramesDevice against zsmi_openSeekableDevice, reads through both, the stream as one item")
     ap.add_argument("--index-one-item", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--record-mib", type=int, default=256, help="with --index: MiB of 1 KiB record frames")
@@ -343,6 +396,8 @@ def main():
         return index_one_item(a)
     if a.index:
         return index_legs(a)
+    if a.split:
+        return split_legs(a)
     if a.records:
         return records(a)
     a.mib = a.mib or 1024

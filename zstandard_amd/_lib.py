@@ -188,6 +188,9 @@ def lib():
     L.zsmi_compressSeekableFramesResident_usingCDictSet.restype = i32
     L.zsmi_compressSeekableFramesResident_usingCDictSet.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, i32, vp, vp]
     L.zsmi_seekableReadFramesResident.restype = i32; L.zsmi_seekableReadFramesResident.argtypes = [vp, vp, vp, u32, u32, vp, u64, vp, vp, vp]
+    L.zsmi_splitRecords.restype = sz; L.zsmi_splitRecords.argtypes = [vp, sz, i32, u32, u32, vp, vp, sz, pu64]
+    L.zsmi_countRecordsDevice.restype = i32; L.zsmi_countRecordsDevice.argtypes = [vp, vp, u64, i32, vp]
+    L.zsmi_splitRecordsDevice.restype = i32; L.zsmi_splitRecordsDevice.argtypes = [vp, vp, u64, i32, u32, u32, u32, vp, vp, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -247,6 +250,7 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_seekableReadFramesDevice", "zsmi_seekableReadFramesHost",
            "zsmi_seekableFramesResidentBound", "zsmi_compressSeekableFramesResident", "zsmi_compressSeekableFramesResident_usingCDictSet",
            "zsmi_seekableReadFramesResident",
+           "zsmi_splitRecords", "zsmi_countRecordsDevice", "zsmi_splitRecordsDevice",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

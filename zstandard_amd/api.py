@@ -116,6 +116,32 @@ def build_seek_table(stream) -> bytes:
     return out.raw[:size]
 
 
+def _delimiter(delimiter) -> int:
+    """a delimiter given as one byte (b"\\n") or as its value"""
+    if isinstance(delimiter, (bytes, bytearray)):
+        if len(delimiter) != 1:
+            raise ValueError("the delimiter is one byte")
+        return delimiter[0]
+    return int(delimiter)
+
+
+def split_records(data, delimiter=b"\n", target_size=0, max_frame_size=1 << 16):
+    """the frames of a record archive over delimited records (zsmi_splitRecords, host only): (sizes uint32[n], first_record uint64[n + 1]).
+    A record ends behind each delimiter byte; a frame holds the whole records that fit in target_size (0: a frame a record), a record above
+    max_frame_size is cut at multiples of it.  first_record[i]: the records in front of frame i, first_record[n]: all.  The frame record
+    r starts in: i = searchsorted(first_record, r), and i - 1 where first_record[i] != r."""
+    L = _lib.lib()
+    s, n = _buf(data)
+    d = _delimiter(delimiter)
+    records = ctypes.c_uint64(0)
+    frames = _raise_if_error(L, L.zsmi_splitRecords(s, n, d, target_size, max_frame_size, None, None, 0, ctypes.byref(records)))
+    sizes = np.zeros(frames, dtype=np.uint32); first = np.zeros(frames + 1, dtype=np.uint64)
+    if frames:                                                             # (no frame: no record either)
+        p = ctypes.c_void_p
+        _raise_if_error(L, L.zsmi_splitRecords(s, n, d, target_size, max_frame_size, p(sizes.ctypes.data), p(first.ctypes.data), frames, None))
+    return sizes, first
+
+
 class ZStdDecompress:
     """EPAM.Deltix.ZStd.ZStdDecompress (static). Sizes are 32-bit in the reference (size_t = UInt32, ZStdDecompress.cs:14)."""
 
@@ -920,6 +946,30 @@ class BatchCodec:
             rc = self.L.zsmi_compressSeekableFramesResident_usingCDictSet(*common, int(bool(checksum)), dset.handle, ctypes.c_void_p(d_dict_index_ptr))
         if rc:
             raise RuntimeError(f"{name}: {_error_name(self.L, rc)}")
+
+    @staticmethod
+    def split_pieces_bound(records, src_size, max_frame_size) -> int:
+        """a max_pieces that always suffices for split_records_device: the records (count_records_device) + a cut every max_frame_size bytes"""
+        return records + src_size // max_frame_size
+
+    def count_records_device(self, d_src_ptr, src_size, d_records_ptr, delimiter=b"\n"):
+        """*d_records_ptr (device uint64) = the records of d_src[0, src_size): its delimiters, + 1 for a tail without one (asynchronous:
+        a count kernel and a sum are queued, nothing waited for).  zsmi_countRecordsDevice"""
+        rc = self.L.zsmi_countRecordsDevice(self.ctx, ctypes.c_void_p(d_src_ptr), src_size, _delimiter(delimiter), ctypes.c_void_p(d_records_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_countRecordsDevice: {_error_name(self.L, rc)}")
+
+    def split_records_device(self, d_src_ptr, src_size, max_pieces, d_frame_sizes_ptr, d_first_record_ptr, d_result_ptr, delimiter=b"\n", target_size=0,
+                             max_frame_size=1 << 16):
+        """split_records on the device, everything in device memory (asynchronous: only queued): d_frame_sizes (uint32[max_pieces]) and
+        d_first_record (uint64[max_pieces + 1]; 0: not wanted) receive what split_records returns for the same bytes, d_result
+        (uint64[3]) the frame count or (uint64)-code, the records and the pieces.  More pieces than max_pieces (split_pieces_bound always
+        suffices): d_result[0] = -dstSize_tooSmall (70) and no list.  What it leaves is what compress_seekable_frames_resident takes:
+        n = d_result[0] read back is that call's host argument.  zsmi_splitRecordsDevice"""
+        rc = self.L.zsmi_splitRecordsDevice(self.ctx, ctypes.c_void_p(d_src_ptr), src_size, _delimiter(delimiter), target_size, max_frame_size, max_pieces,
+                                            ctypes.c_void_p(d_frame_sizes_ptr), ctypes.c_void_p(d_first_record_ptr), ctypes.c_void_p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_splitRecordsDevice: {_error_name(self.L, rc)}")
 
     def open_seekable_device(self, d_ptr, size, ddict=None, ddict_set=None):
         """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The

@@ -18,6 +18,7 @@
 #include "zsmi_ctx.h"             // host: zsmi_ctx with its buffers and stream verbs, LAUNCH, makeHandle, the batch entry points the features call
 #include "seekable.hip"           // feature: seekable archives (kernels and host)
 #include "dict_train.hip"         // feature: dictionary training and finalize (kernels and host)
+#include "split.hip"              // feature: the record splitter - delimited records -> frame sizes and line numbers (kernels and host; the rule: zsmi_split.h)
 
 #include <cstdio>
 #include <cstdlib>
