@@ -448,7 +448,8 @@ int zsmi_decompressSeekableDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcS
  * device memory the handle owns, on ctx's device and stream, and waited for, once.
  * zsmi_openSeekableDevice: an archive in device memory, borrowed: it must outlive the handle.  A NULL ctx: init_missing, first (the table is in
  * device memory); the table is read back and the stream waited for, once, here.
- * Both keep a copy of the table in device memory for zsmi_seekableReadFramesResident (24 bytes a frame; for a borrowed archive the handle's one
+ * Both keep a copy of the table in device memory for zsmi_seekableReadFramesResident and zsmi_seekableReadRecordsResident (24 bytes a frame,
+ * and the frames' content offsets, 8 more; for a borrowed archive the handle's one
  * allocation), uploaded on ctx's stream: by zsmi_openSeekable ahead of its one wait; by zsmi_openSeekableDevice, which knows the table only
  * behind its parse's wait, with a wait of its own, so that a read on any context finds the table whole.
  * NULL on failure, with the code in *err if err != NULL.  A handle is read-only after creation: any context of the same device may use it (a
@@ -637,6 +638,53 @@ size_t zsmi_splitRecords(const void *src, size_t srcSize, int delim, uint32_t ta
 int zsmi_countRecordsDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, int delim, uint64_t *dRecords);
 int zsmi_splitRecordsDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, int delim, uint32_t targetSize, uint32_t maxFrameSize,
                             uint32_t maxPieces, uint32_t *dFrameSizes, uint64_t *dFirstRecord, uint64_t *dResult);
+/* Records by number: the pipeline's last step.  A record archive's handle, the firstRecord array zsmi_splitRecordsDevice left in device
+ * memory and record numbers in device memory -> the records' bytes, packed, with offsets and a status a request.  The two rules
+ * (zstandard_amd/csrc/zsmi_records.h states them in code):
+ *   FRAMES of record r < firstRecord[nFrames]: g = the last frame with firstRecord[g] <= r, lb = the first with firstRecord[lb] >= r, f = lb
+ *     when firstRecord[lb] == r, else g (rule 4's lookup).  Frames f .. g hold the record - f < g only for a record that was cut - and
+ *     skip = r - firstRecord[f] delimiters lie in front of it inside frame f.
+ *   EXTENT, in the content of frames f .. g as one run: the record starts behind the skip-th delimiter (at 0 for skip 0) and ends behind
+ *     the first delimiter at or behind its start, or at the run's end (the stream's tail record).  Fewer than skip delimiters:
+ *     corruption_detected - the array or the delimiter does not belong to this archive.
+ * zsmi_seekableReadRecordsResident only queues work on ctx's stream: no device-to-host copy, no wait, no pinned staging (context buffers may
+ * grow: 80 bytes a request, 60 a frame read of maxFrameReads, the decoder's scratch for maxFrameReads items; memory_allocation, before
+ * anything is queued, when that cannot be reserved).  All arrays are device memory: dFirstRecord nFrames + 1 entries; dRecordIndex, dWritten,
+ * dStatus nRecords; dDstOffsets nRecords + 1; dResult four words.  The host is told nFrames (the handle's frame count), nRecords and
+ * maxFrameReads, which lists, grids and the decode are planned for (nRecords suffices when no record exceeds the split's maxFrameSize).
+ * Request k with dRecordIndex[k] < firstRecord[nFrames]: the record's bytes, its delimiter included, at dDst + dDstOffsets[k]; dWritten[k] its
+ * length; dStatus[k] 0.  dDstOffsets is the exclusive running sum of the lengths, each rounded up to align (zsmi_layoutOutputsDevice's
+ * rule).  The bytes are the text's, whatever targetSize and maxFrameSize the split had.
+ * Followers: request k is a follower of k - 1 when both name frames and have the same (f, g); it reads no frame and uses its leader's decoded
+ * bytes, so an ascending run of numbers decodes each frame once.  Any other repeat decodes again.  The leaders' frames are decoded into
+ * dWork, end to end, with the handle's dictionaries and checked against their entries as zsmi_seekableReadFramesResident checks them: the
+ * first failing frame of a request, in frame order, gives dStatus[k] of the leader and its followers (the decoder's code,
+ * corruption_detected, checksum_wrong); such a request has dWritten[k] 0 and takes no room.
+ * Per request, the others untouched: a number at or above firstRecord[nFrames]: frameIndex_tooLarge, dWritten 0, no room; a leader whose
+ * list would end behind maxFrameReads or whose frames would end behind workCapacity: dstSize_tooSmall, dWritten 0, no room, its followers the
+ * same (so is a request whose frames hold 0xFFFFFF00 bytes or more: no array of the splitter's asks for that); a place that would end
+ * behind dstCapacity: dstSize_tooSmall, nothing written, dWritten[k] still the length.
+ * dResult: [0] the requests with status 0, [1] the frame reads all leaders need, [2] the work bytes those reads need, [3]
+ * dDstOffsets[nRecords]; [1] and [2] are exact whatever the caps are, so that a second call can be sized.
+ * Whatever dFirstRecord holds, nothing is read outside the arrays as sized here and the handle's frames, nothing written outside
+ * [dWork, +workCapacity), [dDst, +dstCapacity) and the arrays.
+ * Checked on the host, in this order, before anything is queued: a NULL ctx: init_missing; a NULL sk, dDstOffsets or dResult, or another NULL
+ * array with nRecords > 0: GENERIC; a handle of another device: parameter_unsupported; delim outside 0..255, align not a power of two in
+ * 1 .. 4096, nFrames != the handle's frame count: parameter_outOfBound; maxFrameReads > 0x8000000: frameIndex_tooLarge; a NULL dDst or dWork
+ * with a non-zero capacity and nRecords > 0: GENERIC.  (nRecords above 0x7FFFFFFF: memory_allocation.)  nRecords == 0 writes
+ * dDstOffsets[0] = 0 and dResult = {0, 0, 0, 0}, and nothing else.
+ * zsmi_seekableRecordsWorkBound: host only - dWork bytes that always suffice for maxFrameReads frame reads of this handle: maxFrameReads * its
+ * largest Decompressed_Size (0 for a NULL handle).
+ * zsmi_seekableReadRecordsHost: host arrays in, a host buffer out - the same checks on the host's arguments (dstOffsets: nRecords + 1 entries;
+ * more than 0x8000000 frame reads: frameIndex_tooLarge), then uploads, the resident body with align 1 and a work buffer of the context's
+ * sized from firstRecord by the same rule, the results copied down and waited for.  A record's length is dstOffsets[k + 1] - dstOffsets[k]. */
+size_t zsmi_seekableRecordsWorkBound(const zsmi_seekable *sk, uint32_t maxFrameReads);
+int zsmi_seekableReadRecordsResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
+                                     const uint64_t *dRecordIndex, uint32_t nRecords, uint32_t maxFrameReads, uint32_t align,
+                                     void *dWork, uint64_t workCapacity, void *dDst, uint64_t dstCapacity,
+                                     uint64_t *dDstOffsets, uint64_t *dWritten, uint32_t *dStatus, uint64_t *dResult);
+int zsmi_seekableReadRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
+                                 const uint64_t *recordIndex, uint32_t nRecords, void *dst, size_t dstCapacity, uint64_t *dstOffsets, uint32_t *statuses);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

@@ -33,7 +33,11 @@ content through both handles, and the stream as one item of zsmi_decompressBatch
   python tools/bench_seekable.py --index [--mib 1024] [--record-mib 256] [--one-item-limit 240]
 --split: the record splitter (zsmi_splitRecordsDevice) on the same text stream, split at newlines: the call and its kernels one by one at
 targetSize 0 and --target, against k_index_count / k_index_emit on the same buffer (split_legs' docstring).  One JSON line.
-  python tools/bench_seekable.py --split [--mib 1024] [--frame 65536] [--target 4096]"""
+  python tools/bench_seekable.py --split [--mib 1024] [--frame 65536] [--target 4096]
+--split --lines: lines by number from the split text's archive - zsmi_seekableReadRecordsResident against a host lookup and
+zsmi_seekableReadFramesResident of the whole frames, for --ranges random lines and an ascending run (lines_legs' docstring).  A JSON line a
+targetSize.
+  python tools/bench_seekable.py --split --lines [--mib 1024] [--ranges 4096] [--line-targets 4096 65536 1048576]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -374,8 +378,94 @@ def split_legs(a):
     print(json.dumps(rep), flush=True)
 
 
+def lines_legs(a):
+    """--split --lines: lines by number from the record archive of the Zipf log stream, for each targetSize of --line-targets (4096 and
+    65536 with maxFrameSize --frame, and 1 MiB frames - the case in which every follower rescans a long frame).  The text is split and
+    compressed by the resident calls and opened; then, for --ranges seeded random lines and for one ascending run of as many, the legs in
+    turn, three rounds, every call followed by a synchronisation:
+      records:  zsmi_seekableReadRecordsResident, its numbers and firstRecord in device memory
+      today:    firstRecord read back, the lookup in numpy, the frame numbers uploaded, zsmi_seekableReadFramesResident of the WHOLE frames
+                (the lines are not cut out of them: that part of today's way is left out of its time); `today_read_only` is that call
+                alone, its numbers already in device memory
+    and the kernels of one records call one by one (three calls: the sorted times of each), with dResult.  A JSON line a targetSize."""
+    size, reps, k = (a.mib or 1024) << 20, 3, a.ranges
+    bc = BatchCodec(0)
+    src = torch.from_numpy(D.zipf_log(size)).cuda()
+    words = torch.zeros(4, dtype=torch.int64, device="cuda")
+    bc.count_records_device(src.data_ptr(), size, words.data_ptr()); bc.sync()
+    records = int(words[0].item())
+    ms = lambda v: [round(t * 1e3, 4) for t in v]
+    rng = np.random.default_rng(8)
+    sets = {"random": rng.integers(0, records, k).astype(np.uint64), "ascending": (np.arange(k, dtype=np.uint64) + np.uint64(records // 3))}
+    for T in a.line_targets:
+        M = max(T, a.frame)
+        mp = BatchCodec.split_pieces_bound(records, size, M)
+        fs = torch.zeros(mp, dtype=torch.int32, device="cuda"); fr = torch.zeros(mp + 1, dtype=torch.int64, device="cuda")
+        bc.split_records_device(src.data_ptr(), size, mp, fs.data_ptr(), fr.data_ptr(), words.data_ptr() + 8, target_size=T, max_frame_size=M); bc.sync()
+        n = int(words[1].item())
+        bound = bc.seekable_frames_resident_bound(size, n, True)
+        arc = torch.empty(bound, dtype=torch.uint8, device="cuda"); arc_size = torch.zeros(1, dtype=torch.int64, device="cuda")
+        bc.compress_seekable_frames_resident(src.data_ptr(), size, fs.data_ptr(), n, M, arc.data_ptr(), bound, arc_size.data_ptr(), level=a.level, checksum=True); bc.sync()
+        m = int(arc_size.item())
+        assert 0 < m <= bound, hex(m)
+        sk = bc.open_seekable_device(arc.data_ptr(), m)
+        rep = {"metric": "read_records", "gib": size / float(1 << 30), "target_size": T, "max_frame_size": M, "frames": n, "records": records, "lines": k,
+               "archive_over_content": round(m / size, 4)}
+        work_cap = sk.records_work_bound(k)
+        work = torch.empty(max(work_cap, 1), dtype=torch.uint8, device="cuda")
+        dst = torch.empty(max(work_cap, 1), dtype=torch.uint8, device="cuda")      # (today's way delivers whole frames: the same room)
+        off = torch.zeros(k + 1, dtype=torch.int64, device="cuda"); wr = torch.zeros(k, dtype=torch.int64, device="cuda")
+        st = torch.zeros(k, dtype=torch.int32, device="cuda"); res = torch.zeros(4, dtype=torch.int64, device="cuda")
+        wr32 = torch.zeros(k, dtype=torch.int32, device="cuda")
+        for name, picks in sets.items():
+            d_idx = torch.from_numpy(picks.view(np.int64)).cuda()
+            d_frames = torch.zeros(k, dtype=torch.int32, device="cuda")
+
+            def new():
+                sk.read_records_resident(fr.data_ptr(), n, d_idx.data_ptr(), k, k, work.data_ptr(), work_cap, dst.data_ptr(), work_cap, off.data_ptr(), wr.data_ptr(),
+                                         st.data_ptr(), res.data_ptr())
+
+            def lookup():
+                first = fr[:n + 1].cpu().numpy().view(np.uint64)
+                i = np.searchsorted(first, picks)
+                return np.where(first[np.minimum(i, n)] == picks, i, i - 1).astype(np.int32)
+
+            def today():
+                d_frames.copy_(torch.from_numpy(lookup()))
+                sk.read_frames_resident(d_frames.data_ptr(), k, dst.data_ptr(), work_cap, off.data_ptr(), wr32.data_ptr(), st.data_ptr())
+
+            def today_read_only():
+                sk.read_frames_resident(d_frames.data_ptr(), k, dst.data_ptr(), work_cap, off.data_ptr(), wr32.data_ptr(), st.data_ptr())
+            sync = lambda: (bc.sync(), torch.cuda.synchronize())
+            t = alternating({"records": new, "today": today, "today_read_only": today_read_only}, sync, reps)
+            today(); sync()
+            assert not st.any().item(), "a frame read failed"
+            frame_bytes = int(off[k].item())
+            new(); sync()
+            assert not st.any().item() and int(res[0].item()) == k, "a record read failed"
+            lens, offs = wr.cpu().numpy(), off.cpu().numpy()
+            runs = []
+            for _ in range(reps):
+                bc.enable_timing(True); new(); bc.sync()
+                runs.append(bc.kernel_times()); bc.enable_timing(False)
+            kt = {kn: sorted(round(r[kn][0] * 1e3, 4) for r in runs) for kn in runs[0]}
+            rep[name] = {"records_ms": ms(t["records"]), "today_ms": ms(t["today"]), "today_read_only_ms": ms(t["today_read_only"]),
+                         "records_over_today": round(float(np.median(t["records"]) / np.median(t["today"])), 3),
+                         "frame_reads": int(res[1].item()), "work_bytes": int(res[2].item()), "line_bytes": int(res[3].item()), "today_bytes": frame_bytes,
+                         "kernels_ms": kt}
+            for q in (0, k - 1):                                               # what was delivered is one line each
+                line = dst[int(offs[q]):int(offs[q]) + int(lens[q])].cpu().numpy().tobytes()
+                assert line.endswith(b"\n") and line.count(b"\n") == 1, "not one line"
+        bc.sync(); sk.close()
+        print(json.dumps(rep), flush=True)
+        del arc, work, dst
+    bc.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--lines", action="store_true", help="with --split: lines by number from the split text's archive, zsmi_seekableReadRecordsResident against today's way")
+    ap.add_argument("--line-targets", type=int, nargs="+", default=[4096, 65536, 1 << 20], help="with --split --lines: the targetSizes")
     ap.add_argument("--split", action="store_true", help="the record splitter on the text stream: the call, its kernels, k_index_count / k_index_emit on the same buffer")
     ap.add_argument("--target", type=int, default=4096, help="with --split: the targetSize of the second leg")
     ap.add_argument("--index", action="store_true", help="streams without a table: zsmi_openFramesDevice against zsmi_openSeekableDevice, reads through both, the stream as one item")
@@ -397,7 +487,7 @@ def main():
     if a.index:
         return index_legs(a)
     if a.split:
-        return split_legs(a)
+        return lines_legs(a) if a.lines else split_legs(a)
     if a.records:
         return records(a)
     a.mib = a.mib or 1024

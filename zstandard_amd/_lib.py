@@ -191,6 +191,10 @@ def lib():
     L.zsmi_splitRecords.restype = sz; L.zsmi_splitRecords.argtypes = [vp, sz, i32, u32, u32, vp, vp, sz, pu64]
     L.zsmi_countRecordsDevice.restype = i32; L.zsmi_countRecordsDevice.argtypes = [vp, vp, u64, i32, vp]
     L.zsmi_splitRecordsDevice.restype = i32; L.zsmi_splitRecordsDevice.argtypes = [vp, vp, u64, i32, u32, u32, u32, vp, vp, vp]
+    L.zsmi_seekableRecordsWorkBound.restype = sz; L.zsmi_seekableRecordsWorkBound.argtypes = [vp, u32]
+    L.zsmi_seekableReadRecordsResident.restype = i32
+    L.zsmi_seekableReadRecordsResident.argtypes = [vp, vp, vp, u32, i32, vp, u32, u32, u32, vp, u64, vp, u64, vp, vp, vp, vp]
+    L.zsmi_seekableReadRecordsHost.restype = i32; L.zsmi_seekableReadRecordsHost.argtypes = [vp, vp, vp, u32, i32, vp, u32, vp, sz, vp, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -251,6 +255,7 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_seekableFramesResidentBound", "zsmi_compressSeekableFramesResident", "zsmi_compressSeekableFramesResident_usingCDictSet",
            "zsmi_seekableReadFramesResident",
            "zsmi_splitRecords", "zsmi_countRecordsDevice", "zsmi_splitRecordsDevice",
+           "zsmi_seekableRecordsWorkBound", "zsmi_seekableReadRecordsResident", "zsmi_seekableReadRecordsHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

@@ -469,6 +469,27 @@ class SeekableArchive:
             raise RuntimeError(_error_name(self.L, rc))
         return self._results(out, written, codes, n, "frame", return_codes)
 
+    def read_records(self, first_record, indices, delimiter=b"\n", return_codes=False):
+        """records by number from a record archive: first_record is split_records' second array for the text the archive was made from
+        (num_frames + 1 entries), indices the record numbers -> the list of the records' bytes, each with its delimiter, one call for all
+        of them (zsmi_seekableReadRecordsHost).  Numbers in a row that lie in the same frames decode them once.  The records' lengths are
+        known only behind the decode, so a first call without a destination sizes the second.  Errors and return_codes as read_many
+        (frameIndex_tooLarge, 100, for a number that is no record's)."""
+        self._open()
+        first = np.ascontiguousarray(first_record, dtype=np.uint64)
+        idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64)
+        n, d = len(idx), _delimiter(delimiter)
+        off = np.zeros(n + 1, dtype=np.uint64); codes = np.zeros(max(n, 1), dtype=np.uint32)
+        p = BatchCodec._p
+        out = np.empty(1, dtype=np.uint8)
+        for cap in (0, None):
+            cap = int(off[n]) if cap is None else cap
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            rc = self.L.zsmi_seekableReadRecordsHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, p(idx), n, p(out), cap, p(off), p(codes))
+            if rc:
+                raise RuntimeError(_error_name(self.L, rc))
+        return self._results(out, np.diff(off), codes, n, "record", return_codes)
+
     def read_many(self, ranges, return_codes=False):
         """ranges: (offset, length) pairs -> the list of their bytes (each clipped at the content's end), one call for all of them
         (zsmi_seekableReadRangesHost).  A failing range raises RuntimeError with the error's name and the range's index; with
@@ -643,6 +664,27 @@ class SeekableHandle:
                                                     ctypes.c_void_p(d_status_ptr))
         if rc:
             raise RuntimeError(f"zsmi_seekableReadFramesResident: {_error_name(self.L, rc)}")
+
+    def records_work_bound(self, max_frame_reads) -> int:
+        """d_work bytes that always suffice for max_frame_reads frame reads of this handle (zsmi_seekableRecordsWorkBound)"""
+        return int(self.L.zsmi_seekableRecordsWorkBound(self.handle, max_frame_reads))
+
+    def read_records_resident(self, d_first_record_ptr, n_frames, d_record_index_ptr, n_records, max_frame_reads, d_work_ptr, work_capacity, d_dst_ptr,
+                              dst_capacity, d_dst_offsets_ptr, d_written_ptr, d_status_ptr, d_result_ptr, delimiter=b"\n", align=1, codec=None):
+        """records by numbers that are DEVICE memory (uint64, n_records entries) from a record archive and the first_record array
+        split_records_device left in device memory (uint64[n_frames + 1]): nothing goes to the host.  Request k's record, its delimiter
+        included, lands at d_dst + d_dst_offsets[k] (device uint64[n_records + 1]: the running sum of the lengths, each rounded up to
+        `align`), d_written (device uint64[n_records]) receives its length, d_status (device uint32[n_records]) 0 or its code, d_result
+        (device uint64[4]) the requests with status 0, the frame reads and work bytes the call needs whatever its caps are, and
+        d_dst_offsets[n_records].  The frames are decoded into d_work (records_work_bound(max_frame_reads) always suffices); requests
+        in a row that name the same frames decode them once.  zsmi_seekableReadRecordsResident"""
+        codec = codec or self.codec
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_seekableReadRecordsResident(codec.ctx, self.handle, p(d_first_record_ptr), n_frames, _delimiter(delimiter), p(d_record_index_ptr), n_records,
+                                                     max_frame_reads, align, p(d_work_ptr), work_capacity, p(d_dst_ptr), dst_capacity, p(d_dst_offsets_ptr),
+                                                     p(d_written_ptr), p(d_status_ptr), p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableReadRecordsResident: {_error_name(self.L, rc)}")
 
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`, from the handle's table"""

@@ -833,6 +833,7 @@ struct zsmi_seekable {
     ZsDictSel sel = ZsDictSel();         // a handle opened with a DDict set: the set's selector (borrowed: the set outlives the handle); else none
     DevBuf dTable;                       // the table in device memory, a ZsSeekEntry a frame (none for an archive without frames): what the reads by device numbers look up
     uint32_t maxDSize = 0;               // the largest Decompressed_Size: the capacity those reads plan their decode for
+    const uint64_t *dContent = nullptr;  // t.dOff behind the table's entries in dTable (frames + 1 words): where a run of frames starts and ends in the content (records.hip)
     ~zsmi_seekable() { if (dOwned) (void)hipFree(dOwned); }
 };
 // queued on the context's stream, from a list that lives until the caller's wait
@@ -840,10 +841,14 @@ static int seekUploadTable(zsmi_ctx *c, zsmi_seekable &sk, std::vector<ZsSeekEnt
 {
     const SeekTable &t = sk.t;
     if (t.n == 0) return 0;
-    entries.resize(t.n);
+    // (one list, one copy: the entries, then the content offsets in the words behind them - whole entries' room, the last in part)
+    const size_t table = sizeof(ZsSeekEntry) * t.n, offsets = sizeof(uint64_t) * ((size_t)t.n + 1);
+    entries.resize(t.n + (offsets + sizeof(ZsSeekEntry) - 1) / sizeof(ZsSeekEntry));
     for (uint32_t i = 0; i < t.n; i++) { entries[i] = { t.cOff[i], t.cSize[i], t.dSize[i], t.hash[i], 0 }; sk.maxDSize = std::max(sk.maxDSize, t.dSize[i]); }
-    if (!sk.dTable.reserve(sizeof(ZsSeekEntry) * t.n)) return ZSMI_error_memory_allocation;
-    return c->toDevice(sk.dTable.p, entries.data(), sizeof(ZsSeekEntry) * t.n);
+    memcpy(entries.data() + t.n, t.dOff.data(), offsets);
+    if (!sk.dTable.reserve(table + offsets)) return ZSMI_error_memory_allocation;
+    sk.dContent = (const uint64_t *)((const uint8_t *)sk.dTable.p + table);
+    return c->toDevice(sk.dTable.p, entries.data(), table + offsets);
 }
 extern "C" zsmi_seekable *zsmi_openSeekable(zsmi_ctx *c, const void *archive, size_t size, int *err)
 {

@@ -19,6 +19,7 @@
 #include "seekable.hip"           // feature: seekable archives (kernels and host)
 #include "dict_train.hip"         // feature: dictionary training and finalize (kernels and host)
 #include "split.hip"              // feature: the record splitter - delimited records -> frame sizes and line numbers (kernels and host; the rule: zsmi_split.h)
+#include "records.hip"            // feature: records by number from a record archive - firstRecord and record numbers -> the records' bytes (kernels and host; the rules: zsmi_records.h)
 
 #include <cstdio>
 #include <cstdlib>
