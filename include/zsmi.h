@@ -685,6 +685,50 @@ int zsmi_seekableReadRecordsResident(zsmi_ctx *ctx, const zsmi_seekable *sk, con
                                      uint64_t *dDstOffsets, uint64_t *dWritten, uint32_t *dStatus, uint64_t *dResult);
 int zsmi_seekableReadRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
                                  const uint64_t *recordIndex, uint32_t nRecords, void *dst, size_t dstCapacity, uint64_t *dstOffsets, uint32_t *statuses);
+/* Find records by content: the step that SELECTS records, in front of zsmi_seekableReadRecordsResident, which takes the answer as it
+ * stands (dRecordIndex: ascending numbers decode each frame once).  A literal byte-pattern search; the rule
+ * (zstandard_amd/csrc/zsmi_find.h states it in code), for text[0, len), a delimiter byte delim, a pattern of m bytes (1 <= m <= 256) none
+ * of which equals delim, and a base B:
+ *  1. An occurrence is a position p with p + m <= len and text[p, p + m) == pattern.  Overlapping occurrences all count.
+ *  2. The record of p is B + the delimiters in text[0, p) (the splitter's rule 4).  The whole occurrence lies in that record.
+ *  3. The answer is the distinct records that hold an occurrence, ascending; total: their count; matches: the occurrence count.
+ * On an archive, text is the content of frames [firstFrame, firstFrame + frameCount) as one run and B = firstRecord[firstFrame]; an
+ * occurrence that crosses the window's border is not found.  Frame f begins a record exactly when f == 0 or firstRecord[f] !=
+ * firstRecord[f - 1], so windows cut at such frames together find what one window over all of them finds.
+ * Not covered: several patterns a call, ignoring case, anchors, regular expressions, patterns that hold the delimiter.
+ * pattern is HOST memory in every form - a parameter like delim, handed to the kernels by value: no upload, no pinned staging, no wait.
+ * dResult / result: four words - [0] total or (uint64_t)-code, [1] the numbers written, min(total, capacity), [2] matches, [3] the bytes
+ * scanned; [0] and [2] are exact whatever capacity is, so that a second call can be sized.  capacity == 0 with NULL dRecords only counts.
+ * Nothing is written behind dRecords[capacity), nothing read outside [dSrc, dSrc + srcSize).
+ * zsmi_findRecords: host only, no device - the rule's loop as written.  Returns total or an error code; *matches may be NULL.
+ * zsmi_findRecordsDevice: only queues work on the context's stream - no device-to-host copy, no wait, no pinned staging (a context buffer
+ * may grow: 40 bytes a 16 KiB of source; memory_allocation, before anything is queued, when that cannot be reserved).  dBase: one device
+ * word, NULL: 0.  srcSize == 0: dResult = {0, 0, 0, 0}.  What it leaves is zsmi_findRecords' answer for the same bytes.
+ * zsmi_seekableFindRecordsResident: the same contract; the window's frames are decoded end to end into dWork with the handle's dictionaries
+ * and checked against their entries as zsmi_seekableReadFramesResident checks them (60 more bytes of context scratch a frame of the window,
+ * the decoder's scratch), then searched, with B read on the device from dFirstRecord[firstFrame] (nFrames + 1 entries).  A frame that fails
+ * (the decoder's code, corruption_detected, checksum_wrong): the first failing frame in frame order gives dResult = {(uint64_t)-code, 0, 0,
+ * bytes} and dRecords is not written.  frameCount == 0: dResult = {0, 0, 0, 0}.
+ * zsmi_seekableFindWorkBound: host only - the dWork bytes the window needs: its frames' content, from the handle's table; 0 for a NULL
+ * handle or a window outside the archive.
+ * zsmi_seekableFindRecordsHost: host arrays in and out - the same checks on the host's arguments, then firstRecord goes up, the resident
+ * body runs with a work buffer of the context's, and the results come down behind one wait.
+ * Checked on the host, in this order, before anything is queued: a NULL ctx (device calls): init_missing; a NULL sk, dResult, pattern or
+ * dFirstRecord, or a NULL dRecords with capacity > 0: GENERIC; a handle of another device: parameter_unsupported; delim outside 0..255,
+ * patternSize 0 or above 256, a pattern byte equal to delim, nFrames != the handle's frame count, firstFrame + frameCount > nFrames:
+ * parameter_outOfBound; srcSize > 0 behind a NULL source: srcSize_wrong; a NULL dWork with a window that holds bytes: GENERIC; workCapacity
+ * below the work bound: dstSize_tooSmall.  (A text of 2^31 tiles of 16 KiB or more: memory_allocation.) */
+size_t zsmi_findRecords(const void *src, size_t srcSize, int delim, const void *pattern, uint32_t patternSize, uint64_t base,
+                        uint64_t *records, size_t capacity, uint64_t *matches);
+int zsmi_findRecordsDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, int delim, const void *pattern, uint32_t patternSize,
+                           const uint64_t *dBase, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult);
+size_t zsmi_seekableFindWorkBound(const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount);
+int zsmi_seekableFindRecordsResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
+                                     const void *pattern, uint32_t patternSize, uint32_t firstFrame, uint32_t frameCount,
+                                     void *dWork, uint64_t workCapacity, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult);
+int zsmi_seekableFindRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
+                                 const void *pattern, uint32_t patternSize, uint32_t firstFrame, uint32_t frameCount,
+                                 uint64_t *records, size_t capacity, uint64_t *result);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

@@ -37,14 +37,20 @@ targetSize 0 and --target, against k_index_count / k_index_emit on the same buff
 --split --lines: lines by number from the split text's archive - zsmi_seekableReadRecordsResident against a host lookup and
 zsmi_seekableReadFramesResident of the whole frames, for --ranges random lines and an ascending run (lines_legs' docstring).  A JSON line a
 targetSize.
-  python tools/bench_seekable.py --split --lines [--mib 1024] [--ranges 4096] [--line-targets 4096 65536 1048576]"""
+  python tools/bench_seekable.py --split --lines [--mib 1024] [--ranges 4096] [--line-targets 4096 65536 1048576]
+--split --find PATTERN ...: find records by content on the same text stream and on its record archive (4 KiB and 64 KiB frames), for each
+pattern: zsmi_findRecordsDevice and its kernels one by one against k_split_count / k_split_emit on the same buffer,
+zsmi_seekableFindRecordsResident over the whole archive against the whole-content range read of the same handle, and today's way - that
+range read, the copy to the host and bytes.find there (find_legs' docstring).  A JSON line a pattern, also appended to
+profiles/find_records_bench.jsonl.
+  python tools/bench_seekable.py --split --find "ERROR ienwbvuzw" e [--mib 1024] [--find-targets 4096 65536]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import _data as D
-from zstandard_amd import BatchCodec, SeekableArchive
+from zstandard_amd import BatchCodec, SeekableArchive, _lib
 
 
 def timed(fn, sync, reps):
@@ -462,8 +468,132 @@ def lines_legs(a):
     bc.close()
 
 
+def host_grep(data, pattern):
+    """today's way on the host: the numbers of the lines that hold the pattern, by bytes.find - the next occurrence, the newlines in front
+    of it, then on from the line's end"""
+    out, at, seen, counted = [], 0, 0, 0
+    while True:
+        p = data.find(pattern, at)
+        if p < 0:
+            return out
+        seen += data.count(b"\n", counted, p); counted = p
+        out.append(seen)
+        at = data.find(b"\n", p) + 1
+        if at == 0:
+            return out
+
+
+def find_legs(a):
+    """--split --find: find records by content on the Zipf log stream (text lines, ~150 bytes each), 1 GiB in device memory, for every
+    pattern of --find.  Legs in turn in one process, three rounds, every call followed by a synchronisation.
+      text:     zsmi_findRecordsDevice; its kernels one by one (HIP events, three calls: the sorted times of each) next to k_split_count /
+                k_split_emit of a zsmi_splitRecordsDevice call (targetSize 0) on the same buffer in the same process - the yardsticks
+                of a tile scan here
+      archive:  for each targetSize of --find-targets the text is split, compressed and opened by the resident calls; then
+                find:       zsmi_seekableFindRecordsResident over all frames
+                range_read: the whole content as one range of the same handle (zsmi_seekableReadRangesDevice) - the decode a search of an
+                            archive cannot avoid
+                today:      that range read, the copy to the host, bytes.find there (host_grep)
+    The numbers are held against host_grep on the text."""
+    size, M, reps = (a.mib or 1024) << 20, a.frame, 3
+    gib = size / float(1 << 30)
+    bc = BatchCodec(0)
+    host = D.zipf_log(size)
+    text = host.tobytes()
+    src = torch.from_numpy(host).cuda()
+    words = torch.zeros(4, dtype=torch.int64, device="cuda")
+    bc.count_records_device(src.data_ptr(), size, words.data_ptr()); bc.sync()
+    records = int(words[0].item())
+    ms = lambda v: [round(t * 1e3, 4) for t in v]
+    sync = lambda: (bc.sync(), torch.cuda.synchronize())
+    found = torch.zeros(records, dtype=torch.int64, device="cuda"); res = torch.zeros(4, dtype=torch.int64, device="cuda")
+
+    def kernels(fn):
+        runs = []
+        for _ in range(reps):
+            bc.enable_timing(True); fn(); bc.sync()
+            runs.append(bc.kernel_times()); bc.enable_timing(False)
+        return {k: sorted(round(r[k][0] * 1e3, 4) for r in runs) for k in runs[0]}
+    reports = {}
+    for pattern in a.find:
+        pat = pattern.encode()
+        want = host_grep(text, pat)
+        call = lambda: bc.find_records_device(src.data_ptr(), size, pat, found.data_ptr(), records, res.data_ptr())
+        mp = BatchCodec.split_pieces_bound(records, size, M)
+        fs = torch.zeros(mp, dtype=torch.int32, device="cuda"); fr = torch.zeros(mp + 1, dtype=torch.int64, device="cuda")
+        split = lambda: bc.split_records_device(src.data_ptr(), size, mp, fs.data_ptr(), fr.data_ptr(), words.data_ptr() + 8, target_size=0, max_frame_size=M)
+        t = alternating({"find": call, "split": split}, sync, reps)
+        call(); sync()
+        total, written, matches, scanned = (int(v) for v in res.tolist())
+        assert (total, written, scanned) == (len(want), len(want), size) and found[:total].cpu().numpy().tolist() == want, "the device call and the host search differ"
+        kf, ks = kernels(call), kernels(split)
+        mid = lambda v: v[len(v) // 2]
+        rep = {"metric": "find_records", "gib": gib, "pattern": pattern, "records": records, "records_found": total, "matches": matches,
+               "find_call_ms": ms(t["find"]), "find_call_gibs": round(gib / float(np.median(t["find"])), 1), "split_call_ms": ms(t["split"]),
+               "find_kernels_ms": {k: v for k, v in kf.items() if k.startswith("k_find")},
+               "split_kernels_ms": {k: v for k, v in ks.items() if k in ("k_split_count", "k_split_emit")}}
+        rep["k_find_count_over_k_split_count"] = round(mid(kf["k_find_count"]) / mid(ks["k_split_count"]), 3)
+        rep["k_find_emit_over_k_split_emit"] = round(mid(kf["k_find_emit"]) / mid(ks["k_split_emit"]), 3)
+        del fs, fr
+        reports[pattern] = (rep, want)
+    for T in a.find_targets:
+        Mx = max(T, M)
+        mp = BatchCodec.split_pieces_bound(records, size, Mx)
+        fs = torch.zeros(mp, dtype=torch.int32, device="cuda"); fr = torch.zeros(mp + 1, dtype=torch.int64, device="cuda")
+        bc.split_records_device(src.data_ptr(), size, mp, fs.data_ptr(), fr.data_ptr(), words.data_ptr() + 8, target_size=T, max_frame_size=Mx); bc.sync()
+        n = int(words[1].item())
+        bound = bc.seekable_frames_resident_bound(size, n, True)
+        arc = torch.empty(bound, dtype=torch.uint8, device="cuda"); arc_size = torch.zeros(1, dtype=torch.int64, device="cuda")
+        bc.compress_seekable_frames_resident(src.data_ptr(), size, fs.data_ptr(), n, Mx, arc.data_ptr(), bound, arc_size.data_ptr(), level=a.level, checksum=True); bc.sync()
+        m = int(arc_size.item())
+        assert 0 < m <= bound, hex(m)
+        sk = bc.open_seekable_device(arc.data_ptr(), m)
+        work_cap = sk.find_work_bound(0, n)
+        assert work_cap == size
+        work = torch.empty(size, dtype=torch.uint8, device="cuda"); st = torch.zeros(1, dtype=torch.int32, device="cuda")
+        pinned = torch.empty(size, dtype=torch.uint8).pin_memory()
+        for pattern in a.find:
+            pat = pattern.encode()
+            rep, want = reports[pattern]
+            got = {}
+
+            def find():
+                sk.find_records_resident(fr.data_ptr(), n, pat, 0, n, work.data_ptr(), work_cap, found.data_ptr(), records, res.data_ptr())
+
+            def range_read():
+                sk.read_ranges_device([0], [size], work.data_ptr(), [0], st.data_ptr())
+
+            def today():
+                range_read(); sync()
+                pinned.copy_(work); torch.cuda.synchronize()
+                got["today"] = host_grep(pinned.numpy().tobytes(), pat)
+            t = alternating({"find": find, "range_read": range_read, "today": today}, sync, reps)
+            find(); sync()
+            total = int(res[0].item())
+            assert total == len(want) and found[:total].cpu().numpy().tolist() == want and got["today"] == want, "the archive call, today's way and the host search differ"
+            bc.enable_timing(True); find(); bc.sync()
+            out = (_lib.KernelTime * 64)()                                     # (more names than kernel_times() holds: the decoder's lie between)
+            kt = {out[i].name.decode(): round(out[i].seconds * 1e3, 4) for i in range(bc.L.zsmi_getKernelTimes(bc.ctx, out, 64))}
+            kt = {k: v for k, v in kt.items() if k.startswith("k_find") or k.startswith("k_seek")}
+            bc.enable_timing(False)
+            rep["target_%d" % T] = {"frames": n, "archive_over_content": round(m / size, 4), "find_ms": ms(t["find"]), "range_read_ms": ms(t["range_read"]),
+                                    "today_ms": ms(t["today"]), "find_over_range_read": round(float(np.median(t["find"]) / np.median(t["range_read"])), 3),
+                                    "today_over_find": round(float(np.median(t["today"]) / np.median(t["find"])), 1), "find_kernels_once_ms": kt}
+        bc.sync(); sk.close()
+        del arc, work, pinned, fs, fr
+    bc.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(a.out or os.path.join(ROOT, "profiles", "find_records_bench.jsonl"), "a") as f:
+        for pattern in a.find:
+            line = json.dumps(reports[pattern][0])
+            print(line, flush=True); f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--find", nargs="+", default=None, help="with --split: find records by content, a leg set a pattern (a rare one and one most lines hold)")
+    ap.add_argument("--find-targets", type=int, nargs="+", default=[4096, 65536], help="with --split --find: the archives' targetSizes")
+    ap.add_argument("--out", default=None, help="with --split --find: the file the JSON lines are appended to (default profiles/find_records_bench.jsonl)")
     ap.add_argument("--lines", action="store_true", help="with --split: lines by number from the split text's archive, zsmi_seekableReadRecordsResident against today's way")
     ap.add_argument("--line-targets", type=int, nargs="+", default=[4096, 65536, 1 << 20], help="with --split --lines: the targetSizes")
     ap.add_argument("--split", action="store_true", help="the record splitter on the text stream: the call, its kernels, k_index_count / k_index_emit on the same buffer")
@@ -487,7 +617,7 @@ def main():
     if a.index:
         return index_legs(a)
     if a.split:
-        return lines_legs(a) if a.lines else split_legs(a)
+        return find_legs(a) if a.find else (lines_legs(a) if a.lines else split_legs(a))
     if a.records:
         return records(a)
     a.mib = a.mib or 1024

@@ -195,6 +195,12 @@ def lib():
     L.zsmi_seekableReadRecordsResident.restype = i32
     L.zsmi_seekableReadRecordsResident.argtypes = [vp, vp, vp, u32, i32, vp, u32, u32, u32, vp, u64, vp, u64, vp, vp, vp, vp]
     L.zsmi_seekableReadRecordsHost.restype = i32; L.zsmi_seekableReadRecordsHost.argtypes = [vp, vp, vp, u32, i32, vp, u32, vp, sz, vp, vp]
+    L.zsmi_findRecords.restype = sz; L.zsmi_findRecords.argtypes = [vp, sz, i32, vp, u32, u64, vp, sz, pu64]
+    L.zsmi_findRecordsDevice.restype = i32; L.zsmi_findRecordsDevice.argtypes = [vp, vp, u64, i32, vp, u32, vp, vp, u64, vp]
+    L.zsmi_seekableFindWorkBound.restype = sz; L.zsmi_seekableFindWorkBound.argtypes = [vp, u32, u32]
+    L.zsmi_seekableFindRecordsResident.restype = i32
+    L.zsmi_seekableFindRecordsResident.argtypes = [vp, vp, vp, u32, i32, vp, u32, u32, u32, vp, u64, vp, u64, vp]
+    L.zsmi_seekableFindRecordsHost.restype = i32; L.zsmi_seekableFindRecordsHost.argtypes = [vp, vp, vp, u32, i32, vp, u32, u32, u32, vp, sz, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -256,6 +262,7 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_seekableReadFramesResident",
            "zsmi_splitRecords", "zsmi_countRecordsDevice", "zsmi_splitRecordsDevice",
            "zsmi_seekableRecordsWorkBound", "zsmi_seekableReadRecordsResident", "zsmi_seekableReadRecordsHost",
+           "zsmi_findRecords", "zsmi_findRecordsDevice", "zsmi_seekableFindWorkBound", "zsmi_seekableFindRecordsResident", "zsmi_seekableFindRecordsHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

@@ -142,6 +142,20 @@ def split_records(data, delimiter=b"\n", target_size=0, max_frame_size=1 << 16):
     return sizes, first
 
 
+def find_records(data, pattern, delimiter=b"\n", base=0):
+    """the records of delimited text that hold `pattern`, a literal byte string of 1 .. 256 bytes without the delimiter (zsmi_findRecords,
+    host only): the list of their numbers, ascending - base + the delimiters in front of an occurrence.  Overlapping occurrences all
+    count, a record with several is listed once."""
+    L = _lib.lib()
+    s, n = _buf(data)
+    pat = bytes(pattern)
+    d = _delimiter(delimiter)
+    total = _raise_if_error(L, L.zsmi_findRecords(s, n, d, pat, len(pat), base, None, 0, None))
+    out = np.zeros(max(total, 1), dtype=np.uint64)
+    _raise_if_error(L, L.zsmi_findRecords(s, n, d, pat, len(pat), base, ctypes.c_void_p(out.ctypes.data), total, None))
+    return [int(v) for v in out[:total]]
+
+
 class ZStdDecompress:
     """EPAM.Deltix.ZStd.ZStdDecompress (static). Sizes are 32-bit in the reference (size_t = UInt32, ZStdDecompress.cs:14)."""
 
@@ -490,6 +504,32 @@ class SeekableArchive:
                 raise RuntimeError(_error_name(self.L, rc))
         return self._results(out, np.diff(off), codes, n, "record", return_codes)
 
+    def find_records(self, first_record, pattern, delimiter=b"\n", first_frame=0, frame_count=None):
+        """the records of a record archive that hold `pattern` (a literal byte string of 1 .. 256 bytes without the delimiter): the list
+        of their numbers, ascending, as read_records takes them.  first_record is split_records' second array for the text the archive
+        was made from; first_frame and frame_count (None: to the archive's end) name a window of frames - an occurrence across its
+        border is not found, and windows that start where first_record changes cut none.  A first call counts, the second is sized by
+        it (zsmi_seekableFindRecordsHost); a frame that fails raises RuntimeError with the error's name."""
+        self._open()
+        first = np.ascontiguousarray(first_record, dtype=np.uint64)
+        pat, d = bytes(pattern), _delimiter(delimiter)
+        count = self.num_frames - first_frame if frame_count is None else frame_count
+        p = BatchCodec._p
+        result = np.zeros(4, dtype=np.uint64)
+        out = np.zeros(1, dtype=np.uint64)
+        for cap in (0, None):
+            cap = int(result[0]) if cap is None else cap
+            out = np.zeros(max(cap, 1), dtype=np.uint64)
+            rc = self.L.zsmi_seekableFindRecordsHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, pat, len(pat), first_frame, count,
+                                                     p(out) if cap else None, cap, p(result))
+            if rc:
+                raise RuntimeError(_error_name(self.L, rc))
+            if int(result[0]) > (1 << 64) - ERROR_MAX_CODE:
+                raise RuntimeError(_error_name(self.L, (1 << 64) - int(result[0])))
+            if int(result[0]) == 0:
+                return []
+        return [int(v) for v in out[:int(result[1])]]
+
     def read_many(self, ranges, return_codes=False):
         """ranges: (offset, length) pairs -> the list of their bytes (each clipped at the content's end), one call for all of them
         (zsmi_seekableReadRangesHost).  A failing range raises RuntimeError with the error's name and the range's index; with
@@ -685,6 +725,27 @@ class SeekableHandle:
                                                      p(d_written_ptr), p(d_status_ptr), p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_seekableReadRecordsResident: {_error_name(self.L, rc)}")
+
+    def find_work_bound(self, first_frame, frame_count) -> int:
+        """the d_work bytes find_records_resident needs for this window: its frames' content (zsmi_seekableFindWorkBound; 0 for a window
+        outside the archive)"""
+        return int(self.L.zsmi_seekableFindWorkBound(self.handle, first_frame, frame_count))
+
+    def find_records_resident(self, d_first_record_ptr, n_frames, pattern, first_frame, frame_count, d_work_ptr, work_capacity, d_records_ptr, capacity,
+                              d_result_ptr, delimiter=b"\n", codec=None):
+        """the records of frames [first_frame, first_frame + frame_count) of a record archive that hold `pattern` (HOST bytes, 1 .. 256 of
+        them, none the delimiter), everything else in device memory and nothing going to the host: d_records (uint64[capacity]; 0 with
+        capacity 0: only count) receives their numbers, ascending - what read_records_resident takes as d_record_index - and d_result
+        (uint64[4]) the total or (uint64)-code, the numbers written, the occurrences and the bytes searched.  The window's frames are
+        decoded into d_work (find_work_bound bytes) and the numbers count from d_first_record[first_frame] (uint64[n_frames + 1], as
+        split_records_device left it).  zsmi_seekableFindRecordsResident"""
+        codec = codec or self.codec
+        p = ctypes.c_void_p
+        pat = bytes(pattern)
+        rc = self.L.zsmi_seekableFindRecordsResident(codec.ctx, self.handle, p(d_first_record_ptr), n_frames, _delimiter(delimiter), pat, len(pat), first_frame,
+                                                     frame_count, p(d_work_ptr), work_capacity, p(d_records_ptr), capacity, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableFindRecordsResident: {_error_name(self.L, rc)}")
 
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`, from the handle's table"""
@@ -1012,6 +1073,18 @@ class BatchCodec:
                                             ctypes.c_void_p(d_frame_sizes_ptr), ctypes.c_void_p(d_first_record_ptr), ctypes.c_void_p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_splitRecordsDevice: {_error_name(self.L, rc)}")
+
+    def find_records_device(self, d_src_ptr, src_size, pattern, d_records_ptr, capacity, d_result_ptr, delimiter=b"\n", d_base_ptr=0):
+        """find_records on the device, the text in device memory (asynchronous: only queued): d_records (uint64[capacity]; 0 with capacity
+        0: only count) receives the ascending numbers of the records of d_src[0, src_size) that hold `pattern` (HOST bytes, 1 .. 256 of
+        them, none the delimiter), d_result (uint64[4]) the total, the numbers written, the occurrences and the bytes searched; total and
+        occurrences are exact whatever capacity is.  d_base_ptr: one device uint64 the numbers count from (0: from 0).
+        zsmi_findRecordsDevice"""
+        pat = bytes(pattern)
+        rc = self.L.zsmi_findRecordsDevice(self.ctx, ctypes.c_void_p(d_src_ptr), src_size, _delimiter(delimiter), pat, len(pat), ctypes.c_void_p(d_base_ptr),
+                                           ctypes.c_void_p(d_records_ptr), capacity, ctypes.c_void_p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_findRecordsDevice: {_error_name(self.L, rc)}")
 
     def open_seekable_device(self, d_ptr, size, ddict=None, ddict_set=None):
         """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The

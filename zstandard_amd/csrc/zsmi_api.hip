@@ -20,6 +20,7 @@
 #include "dict_train.hip"         // feature: dictionary training and finalize (kernels and host)
 #include "split.hip"              // feature: the record splitter - delimited records -> frame sizes and line numbers (kernels and host; the rule: zsmi_split.h)
 #include "records.hip"            // feature: records by number from a record archive - firstRecord and record numbers -> the records' bytes (kernels and host; the rules: zsmi_records.h)
+#include "find.hip"               // feature: find records by content - text or a window of a record archive and a literal pattern -> ascending record numbers (kernels and host; the rule: zsmi_find.h)
 
 #include <cstdio>
 #include <cstdlib>
