@@ -98,9 +98,19 @@ def assert_only_frames_written(host, dst_offs, sizes, bounds, canary=CANARY, wha
 
 
 # ------------------------------------------------------------------ child processes
+class ChildFailed(AssertionError):
+    """a child that did not end as it must; returncode: its exit status (negative: ended by that signal)"""
+
+    def __init__(self, returncode, detail):
+        super().__init__(returncode, *detail)
+        self.returncode = returncode
+
+
 def run_child(*argv, env=None, timeout=600, marker="CHILD-OK", cwd=None):
     """a fresh Python process with these arguments: a file's path and its arguments, or "-c", a script's text and its arguments.  It must
-    exit with 0 and, unless marker is None, print the marker.  Returns its stdout."""
+    exit with 0 and, unless marker is None, print the marker (else ChildFailed, an AssertionError; a child that outlives `timeout` is
+    killed and subprocess.TimeoutExpired raised).  Returns its stdout."""
     r = subprocess.run([sys.executable, *argv], env=env, cwd=cwd, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0 and (marker is None or marker in r.stdout), (r.stdout[-2000:], r.stderr[-3000:])
+    if not (r.returncode == 0 and (marker is None or marker in r.stdout)):
+        raise ChildFailed(r.returncode, (r.stdout[-2000:], r.stderr[-3000:]))
     return r.stdout

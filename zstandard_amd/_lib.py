@@ -210,8 +210,35 @@ def lib():
     if DEBUG or hasattr(L, "zsmi_dbg_copyScratch"):            # (a variant build named by ZSMI_LIB_FILE may carry the hooks too)
         L.zsmi_dbg_copyScratch.restype = i32; L.zsmi_dbg_copyScratch.argtypes = [vp, ctypes.c_char_p, vp, sz]
         L.zsmi_dbg_scratchLayout.restype = i32; L.zsmi_dbg_scratchLayout.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "zsmi_dbg_fillScratch"):
+        L.zsmi_dbg_fillScratch.restype = i32; L.zsmi_dbg_fillScratch.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_uint64)]
+        L.zsmi_dbg_scratchInventory.restype = sz; L.zsmi_dbg_scratchInventory.argtypes = [ctypes.c_char_p, sz]
     _lib = L
     return L
+
+
+FILL_GROUPS = ("compress", "resident", "decode", "staging", "seek", "train", "plan")      # zsmi_dbg_fillScratch's bytesFilled, in this order
+
+
+def fill_scratch(ctx, pattern):
+    """debug-hook library: every buffer the context keeps from call to call is overwritten (0 .. 255: that byte; any other value: a mix of
+    small and large words made from it) and the compress plan forgotten.  Returns {group: bytes filled}"""
+    out = (ctypes.c_uint64 * len(FILL_GROUPS))()
+    rc = lib().zsmi_dbg_fillScratch(ctx, pattern, out)
+    if rc != 0:
+        raise RuntimeError("zsmi_dbg_fillScratch: %d" % rc)
+    return dict(zip(FILL_GROUPS, (int(v) for v in out)))
+
+
+def scratch_inventory(so=None):
+    """debug-hook library (host code only): [(group, "filled" | "forgotten" | "state", member of zsmi_ctx.h)] - what fill_scratch covers and
+    what it leaves as state.  so: the library as a ctypes.CDLL (default: the one lib() loads)"""
+    so = so or lib()
+    so.zsmi_dbg_scratchInventory.restype = ctypes.c_size_t; so.zsmi_dbg_scratchInventory.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    n = so.zsmi_dbg_scratchInventory(None, 0)
+    buf = ctypes.create_string_buffer(n)
+    so.zsmi_dbg_scratchInventory(buf, n)
+    return [tuple(line.split()) for line in buf.value.decode().splitlines()]
 
 
 def scratch_layout(name):

@@ -1513,4 +1513,108 @@ extern "C" int zsmi_dbg_copyScratch(zsmi_ctx *c, const char *name, void *hostDst
     if (bytes > b->cap) return -2;
     return hipMemcpy(hostDst, b->p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }
+
+// ---- scratch poisoning (tests/test_gpu_scratch_independence.py): everything a context carries from call to call is overwritten, so that a
+// kernel which reads a word nobody wrote for THIS call reads poison and not the well-formed leftovers of the call before.  DESIGN.md, "What a
+// context's memory may carry from call to call", states for every buffer below why the next call does not depend on it.
+// The groups bytesFilled reports, and every buffer member of zsmi_ctx.h in one list: visit(group, name, buffer).  A TurnBufs is its two buffers.
+enum { kFillCompress, kFillResident, kFillDecode, kFillStaging, kFillSeek, kFillTrain, kFillPlan, kFillGroups };
+static const char *const kFillGroupNames[kFillGroups] = { "compress", "resident", "decode", "staging", "seek", "train", "plan" };
+template <class F> static void eachCtxBuffer(zsmi_ctx *c, F visit)
+{
+    auto turn = [&](int g, const char *name, TurnBufs &t) { visit(g, name, t.buf[0]); visit(g, name, t.buf[1]); };
+    for (int i = 0; i < kZsScratchCount; i++) visit(kFillCompress, "scratch.buf", c->scratch.buf[i]);
+    zsmi_ctx::ResidentPlan &R = c->resident;
+    visit(kFillResident, "resident.dChunks", R.dChunks); visit(kFillResident, "resident.dBefore", R.dBefore); visit(kFillResident, "resident.dCounts", R.dCounts);
+    visit(kFillResident, "resident.dBlocks", R.dBlocks); visit(kFillResident, "resident.dUnits", R.dUnits);
+    visit(kFillResident, "resident.dChunkDict", R.dChunkDict); visit(kFillResident, "resident.dUnitDict", R.dUnitDict);
+    zsmi_ctx::DecodeScratch &D = c->dec;
+    visit(kFillDecode, "dItems", c->dItems); turn(kFillDecode, "hItems", c->hItems);
+    visit(kFillDecode, "dec.dPoolLit", D.dPoolLit); visit(kFillDecode, "dec.dLitScratch", D.dLitScratch); visit(kFillDecode, "dec.dFastDesc", D.dFastDesc);
+    visit(kFillDecode, "dec.dHufTabs", D.dHufTabs); visit(kFillDecode, "dec.dSeqTabs", D.dSeqTabs); visit(kFillDecode, "dec.dSeqOut", D.dSeqOut);
+    visit(kFillDecode, "dec.dSeqLists", D.dSeqLists);
+    visit(kFillStaging, "dDictImg", c->dDictImg); visit(kFillStaging, "dDictRec", c->dDictRec); visit(kFillStaging, "hDictRec", c->hDictRec);
+    visit(kFillStaging, "sSrc", c->sSrc); visit(kFillStaging, "sDst", c->sDst); visit(kFillStaging, "sSizes", c->sSizes); visit(kFillStaging, "sDict", c->sDict);
+    visit(kFillStaging, "sPack", c->sPack); visit(kFillStaging, "sPackOff", c->sPackOff); visit(kFillStaging, "dScan", c->dScan); visit(kFillStaging, "hPack", c->hPack);
+    visit(kFillSeek, "seek.dStage", c->seek.dStage); visit(kFillSeek, "seek.dMeta", c->seek.dMeta); visit(kFillSeek, "seek.dDec", c->seek.dDec);
+    turn(kFillSeek, "seek.hLists", c->seek.hLists);
+    zsmi_ctx::TrainScratch &T = c->train;
+    visit(kFillTrain, "train.dSamples", T.dSamples); visit(kFillTrain, "train.dGather", T.dGather); visit(kFillTrain, "train.dEnds", T.dEnds);
+    visit(kFillTrain, "train.dKeys", T.dKeys); visit(kFillTrain, "train.dKeysOut", T.dKeysOut); visit(kFillTrain, "train.dSortTmp", T.dSortTmp);
+    visit(kFillTrain, "train.dInfo", T.dInfo[0]); visit(kFillTrain, "train.dInfo", T.dInfo[1]);
+    visit(kFillTrain, "train.dFreqBase", T.dFreqBase); visit(kFillTrain, "train.dFreq", T.dFreq); visit(kFillTrain, "train.dContent", T.dContent);
+    visit(kFillTrain, "train.dCand", T.dCand); visit(kFillTrain, "train.dArena", T.dArena); visit(kFillTrain, "train.dSizes", T.dSizes);
+    visit(kFillTrain, "train.dMisc", T.dMisc); visit(kFillTrain, "train.dOut", T.dOut); visit(kFillTrain, "train.hCand", T.hCand);
+    CompressPlan &P = c->plan;
+    visit(kFillPlan, "plan.hBlocks", P.hBlocks); visit(kFillPlan, "plan.hChunks", P.hChunks); visit(kFillPlan, "plan.hUnits", P.hUnits);
+    visit(kFillPlan, "plan.dBlocks", P.dBlocks); visit(kFillPlan, "plan.dChunks", P.dChunks); visit(kFillPlan, "plan.dUnits", P.dUnits);
+    visit(kFillPlan, "plan.dDictList", P.dDictList); turn(kFillPlan, "plan.hDictList", P.hDictList);
+}
+// The member names the fill covers, one a line as "<group> filled <member>", then the plan's words that are valid across calls by design and are
+// forgotten with it ("plan forgotten <member>"), then what is kept as state ("<group> state <member>": which of a TurnBufs' two buffers is next, and
+// the events behind them - no call reads anything through them).  Host only: c may be null.  Returns the bytes the text takes (with its 0), whatever cap is.
+extern "C" size_t zsmi_dbg_scratchInventory(char *out, size_t cap)
+{
+    std::string text, last;
+    zsmi_ctx blank;                                            // (a context as its constructor leaves it holds nothing and touches no device)
+    struct Names { std::string &text, &last; void operator()(int g, const char *name, const DevBuf &) { add(g, name); } void operator()(int g, const char *name, const PinBuf &) { add(g, name); }
+                   void add(int g, const char *name) { if (last != name) { text += kFillGroupNames[g]; text += " filled "; text += name; text += "\n"; last = name; } } };
+    Names names{ text, last };
+    eachCtxBuffer(&blank, names);
+    for (const char *m : { "plan.key", "plan.dictKey", "plan.dictKind" }) { text += "plan forgotten "; text += m; text += "\n"; }
+    for (const char *m : { "decode state hItems.turns", "seek state seek.hLists.turns", "plan state plan.hDictList.turns" }) { text += m; text += "\n"; }
+    if (out && cap) { const size_t n = std::min(cap - 1, text.size()); memcpy(out, text.data(), n); out[n] = 0; }
+    return text.size() + 1;
+}
+// a word of the mixed pattern: a hash of the word's offset and the pattern, a quarter of the words cut down to a byte and a quarter to 20 bits -
+// values that pass for small counts, slots and positions
+__host__ __device__ static inline uint32_t dbgPoisonWord(uint64_t word, uint32_t pattern)
+{
+    uint32_t h = ((uint32_t)word * 0x9E3779B1u) ^ (uint32_t)(word >> 32) ^ pattern;
+    h ^= h >> 15; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    const uint32_t kind = h >> 30;
+    return kind == 0 ? (h & 0xFFu) : kind == 1 ? (h & 0xFFFFFu) : h;
+}
+__global__ void k_dbg_poison(uint32_t *p, uint64_t words, uint32_t pattern)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (uint64_t)gridDim.x * blockDim.x) p[i] = dbgPoisonWord(i, pattern);
+}
+// Overwrites the whole capacity of every buffer of eachCtxBuffer - growth slack and fixed tails included - behind a wait for the context's stream, and
+// forgets the compress plan (its buffers are filled like the rest).  pattern 0 .. 255: that byte; any other value: dbgPoisonWord (the bytes behind a
+// buffer's last whole word get the pattern's low byte).  bytesFilled (may be null): kFillGroups sums, in the order of kFillGroupNames.  Handles
+// (dictionaries, their sets, open archives) are not the context's and are not touched.  0, or a negative code.
+extern "C" int zsmi_dbg_fillScratch(zsmi_ctx *c, uint32_t pattern, uint64_t *bytesFilled)
+{
+    if (!c) return -1;
+    if (c->bind() || c->wait()) return -2;
+    uint64_t sums[kFillGroups] = { 0 };
+    bool ok = true;
+    struct Fill {
+        zsmi_ctx *c; uint32_t pattern; uint64_t *sums; bool &ok;
+        void operator()(int g, const char *, DevBuf &b)
+        {
+            if (!b.p || !b.cap) return;
+            sums[g] += b.cap;
+            if (pattern < 256u) { ok &= c->fill(b.p, (int)pattern, b.cap) == 0; return; }
+            const uint64_t words = b.cap / 4;                  // (hipMalloc's blocks are aligned far beyond a word)
+            if (words) hipLaunchKernelGGL(k_dbg_poison, dim3((unsigned)std::min<uint64_t>((words + 255) / 256, 4096)), dim3(256), 0, c->stream, (uint32_t *)b.p, words, pattern);
+            if (b.cap & 3) ok &= c->fill((uint8_t *)b.p + words * 4, (int)(pattern & 0xFFu), b.cap & 3) == 0;
+        }
+        void operator()(int g, const char *, PinBuf &b)          // idle: the stream was waited for, and every copy that read it is behind us
+        {
+            if (!b.p || !b.cap) return;
+            sums[g] += b.cap;
+            if (pattern < 256u) { memset(b.p, (int)pattern, b.cap); return; }
+            uint32_t *w = (uint32_t *)b.p;
+            for (uint64_t i = 0; i < b.cap / 4; i++) w[i] = dbgPoisonWord(i, pattern);
+            memset((uint8_t *)b.p + (b.cap & ~(size_t)3), (int)(pattern & 0xFFu), b.cap & 3);
+        }
+    } fill{ c, pattern, sums, ok };
+    eachCtxBuffer(c, fill);
+    c->plan.key.clear(); c->plan.dictKey.clear(); c->plan.dictKind = CompressPlan::kDictNone;
+    ok &= c->launched() == 0;
+    ok &= c->wait() == 0;
+    if (bytesFilled) for (int g = 0; g < kFillGroups; g++) bytesFilled[g] = sums[g];
+    return ok ? 0 : -3;
+}
 #endif
