@@ -638,3 +638,79 @@ def entropy_shapes(frame):
                     s.tables.append(("pre", "rle", None, "repeat")[mode]); p += mode == 1
         out.append(s)
     return out
+
+
+def _read_backward(stream):
+    """a reader of the backward bit stream `stream` (§4.1): take(n) gives the next n bits, left() the bits still unread (negative once
+    the reader has run past the stream's start, where it reads zeros)"""
+    assert stream and stream[-1], "a backward bit stream ends in its marker bit"
+    v = int.from_bytes(stream, "little")
+    at = [v.bit_length() - 1]
+
+    def take(n):
+        at[0] -= n
+        return (v >> at[0]) & ((1 << n) - 1) if at[0] >= 0 else (v << -at[0]) & ((1 << n) - 1)
+    return take, lambda: at[0]
+
+
+def huf_weights(frame, pos):
+    """the Huffman weights of the tree description at frame[pos:] (§4.2.1.1), the implied last one included, and the position behind the
+    description.  Direct form: 4 bits a weight.  FSE form (§4.2.1.2): two interleaved states, read until the stream is exhausted."""
+    h = frame[pos]
+    if h >= 128:
+        n = h - 127
+        body = frame[pos + 1:pos + 1 + (n + 1) // 2]
+        w = [(body[i >> 1] >> (0 if i & 1 else 4)) & 15 for i in range(n)]
+        end = pos + 1 + (n + 1) // 2
+    else:
+        end = pos + 1 + h
+        norm, al, p = read_ncount(frame, pos + 1, 12)
+        t = FSE(norm, al)
+        take, left = _read_backward(frame[p:end])
+        st, w, j = [take(al), take(al)], [], 0
+        while True:
+            assert len(w) < 255
+            u = st[j]
+            w.append(t.sym[u]); st[j] = t.base[u] + take(t.nb[u])
+            if left() < 0:                                # the stream ran out inside this update: the other state's symbol is the last
+                w.append(t.sym[st[j ^ 1]]); break
+            j ^= 1
+    total = sum(1 << (x - 1) for x in w if x)
+    rest = (1 << total.bit_length()) - total
+    assert total and rest & (rest - 1) == 0, "the weights must leave a power of two for the last symbol"
+    return w + [_highbit(rest) + 1], end
+
+
+def section_shapes(frame):
+    """per block of the frame, what blocks() and entropy_shapes() give (the fields of blocks(); tables and weights as entropy_shapes()
+    names them) and the decisions behind a compressed block's two sections:
+    literals: streams (1 or 4 for Huffman-coded literals, else None); huf_weights (the decoded weights by symbol, the implied last one
+    included; None without a description), and from them coded (symbols with a code), max_symbol and max_bits (the longest code);
+    sequences: nseq_bytes (the width of Number_of_Sequences) and, where nseq > 0, ll / of / ml: namespaces with mode ("pre", "rle", "fse",
+    "repeat"), al and norm (an FSE description's accuracy log and normalised counts, padded with zeros to the table's last code) and
+    symbol (RLE mode).  No bit stream is decoded beyond the weights."""
+    out = []
+    for b, e in zip(blocks(frame), entropy_shapes(frame)):
+        if b.type == 2:
+            b.tables, b.weights = e.tables, e.weights
+            b.streams = (1 if b.size_format == 0 else 4) if b.lit_type >= 2 else None
+            b.huf_weights = b.coded = b.max_symbol = b.max_bits = None
+            if b.lit_type == 2:
+                b.huf_weights, _ = huf_weights(frame, b.huf_pos)
+                present = [s for s, w in enumerate(b.huf_weights) if w]
+                b.coded, b.max_symbol = len(present), present[-1]
+                b.max_bits = _highbit(sum(1 << (w - 1) for w in b.huf_weights if w)) + 1 - min(b.huf_weights[s] for s in present)
+            b.nseq_bytes = 1 if frame[b.seq_pos] < 128 else 2 if frame[b.seq_pos] < 255 else 3
+            b.ll = b.of = b.ml = None
+            p = b.tables_pos
+            for name, shift, max_symbol in (("ll", 6, 35), ("of", 4, 31), ("ml", 2, 52)) if b.nseq else ():
+                mode = (b.modes >> shift) & 3
+                t = SimpleNamespace(mode=("pre", "rle", "fse", "repeat")[mode], al=None, norm=None, symbol=None)
+                if mode == 1:
+                    t.symbol = frame[p]; p += 1
+                elif mode == 2:
+                    norm, t.al, p = read_ncount(frame, p, max_symbol)
+                    t.norm = norm + [0] * (max_symbol + 1 - len(norm))
+                setattr(b, name, t)
+        out.append(b)
+    return out
