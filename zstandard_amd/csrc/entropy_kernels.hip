@@ -531,19 +531,28 @@ __device__ __forceinline__ uint32_t huffEncodeStream(K3Lds &L, uint32_t *tile, u
     uint64_t next = remaining ? fetch(remaining) : 0ull;                   // the next tile's bytes travel while this one is packed
     while (remaining) {
         const uint32_t T = min(512u, remaining);
-        uint64_t lo = 0; uint32_t hi = 0, nb = 0;
         const uint64_t eight = next;
         if (remaining > T) next = fetch(remaining - T);
+        // the eight codes are looked up as one batch (one wait), a symbol beyond the tile counts as code 0 of length 0 by a select, and the
+        // codes are merged as a tree: pairs in 32 bits (<= 22), fours in 64 (<= 44), the two fours into lo / hi (<= 88).  (Appended one
+        // by one, each symbol was a divergent region with its own LDS round trip and a ladder of exec masks around a 64-bit shift.)
+        uint32_t cn[8];
         #pragma unroll
-        for (uint32_t j = 0; j < 8; j++) {
-            if (k0 + j < T) {
-                const uint32_t sym = (uint32_t)(eight >> (8 * (7 - j))) & 0xFFu;
-                const uint32_t cn = L.codeNb[sym], c = cn & 0xFFFFu, b = cn >> 16;
-                if (nb < 64) { lo |= (uint64_t)c << nb; if (nb + b > 64) hi |= c >> (64 - nb); }
-                else hi |= c << (nb - 64);
-                nb += b;
-            }
+        for (uint32_t j = 0; j < 8; j++) cn[j] = L.codeNb[(uint32_t)(eight >> (8 * (7 - j))) & 0xFFu];
+        #pragma unroll
+        for (uint32_t j = 0; j < 8; j++) cn[j] = (k0 + j < T) ? cn[j] : 0u;
+        uint32_t pv[4], pn[4];
+        #pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t b0 = cn[2 * j] >> 16;
+            pv[j] = (cn[2 * j] & 0xFFFFu) | ((cn[2 * j + 1] & 0xFFFFu) << b0);
+            pn[j] = b0 + (cn[2 * j + 1] >> 16);
         }
+        const uint64_t q0 = (uint64_t)pv[0] | ((uint64_t)pv[1] << pn[0]), q1 = (uint64_t)pv[2] | ((uint64_t)pv[3] << pn[2]);
+        const uint32_t n0 = pn[0] + pn[1];                                  // <= 44
+        const uint64_t lo = q0 | (q1 << n0);
+        const uint32_t hi = (uint32_t)((q1 >> 1) >> (63u - n0));            // q1's bits from 64 - n0 up (n0 = 0: none)
+        const uint32_t nb = n0 + pn[2] + pn[3];
         sink_put(sink, lo, hi, nb);
         remaining -= T;
     }
@@ -1426,12 +1435,14 @@ __device__ __forceinline__ void encode_sequences_block(ZS_SEQ_PARAMS, const ZsCD
                 uint64_t lo = 0; uint32_t hi = 0, nb = 0;
                 if (jt + lane < nseq) {
                     const uint32_t sLL = rle0 ? 0u : sC[t][0], sOF = rle1 ? 0u : sC[t][1], sML = rle2 ? 0u : sC[t][2];
-                    #define PUTB(v, b) { const uint32_t b_ = (b); if (b_) { const uint64_t v_ = (uint64_t)(v); if (nb < 64) { lo |= v_ << nb; if (nb + b_ > 64) hi |= (uint32_t)(v_ >> (64 - nb)); } else hi |= (uint32_t)(v_ << (nb - 64)); nb += b_; } }
-                    PUTB(sOF & 0xFFFu, sOF >> 12);
-                    PUTB(sML & 0xFFFu, sML >> 12);
-                    PUTB(sLL & 0xFFFu, sLL >> 12);
-                    PUTB((uint64_t)pr[t].x | ((uint64_t)(pr[t].y & 0xFFFFFFu) << 32), pr[t].y >> 24);
-                    #undef PUTB
+                    // the three state outputs (<= 9 bits each, nothing above their count) side by side in 32 bits, the extra bits (<= 49) behind
+                    // them: no branch (huffEncodeStream's merge)
+                    const uint32_t bOF = sOF >> 12, bML = sML >> 12, n3 = bOF + bML + (sLL >> 12);         // n3 <= 27
+                    const uint32_t st = (sOF & 0xFFFu) | ((sML & 0xFFFu) << bOF) | ((sLL & 0xFFFu) << (bOF + bML));
+                    const uint64_t x = (uint64_t)pr[t].x | ((uint64_t)(pr[t].y & 0xFFFFFFu) << 32);
+                    lo = (uint64_t)st | (x << n3);
+                    hi = (uint32_t)((x >> 1) >> (63u - n3));                                            // x's bits from 64 - n3 up (n3 = 0: none)
+                    nb = n3 + (pr[t].y >> 24);
                 }
                 if (sink.bitpos / 8 + 1024 > bsCap) overflow = true;
                 else sink_put(sink, lo, hi, nb);

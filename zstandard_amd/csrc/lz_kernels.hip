@@ -425,11 +425,13 @@ static_assert(ZS_WALK_THREADS(false, 8) / ZS_WALK_LPW(8) == (ZS_BLOCK_MAX >> 8) 
 // (an unaligned ds_read_b64 / b128 costs the LDS several passes: SQ_LDS_UNALIGNED_STALL was 80 % of its busy time)
 // (byteOff is an LDS address: the kernel's dynamic LDS starts at address 0 - there is no static LDS in it, which zsmi_createCtx checks
 // through hipFuncGetAttributes - so the compiler has no symbol to add to every address)
+// (OFF, a multiple of 4: a constant part of the address, added behind the alignment so that it lands in the reads' offset field and costs no instruction)
 typedef const __attribute__((address_space(3))) uint32_t *ZsLdsU32;
-template <int K>
+template <int K, uint32_t OFF = 0>
 __device__ __forceinline__ void lds_span(uint32_t byteOff, uint32_t (&out)[K])
 {
-    ZsLdsU32 d = (ZsLdsU32)(uintptr_t)(byteOff & ~3u);
+    static_assert(OFF % 4u == 0 && OFF + 4u * K < 65536u, "the constant part keeps the alignment and fits the offset field");
+    ZsLdsU32 d = (ZsLdsU32)(uintptr_t)((byteOff & ~3u) + OFF);
     uint32_t w[K + 1];
     #pragma unroll
     for (int k = 0; k <= K; k++) w[k] = d[k];
@@ -444,13 +446,21 @@ __device__ __forceinline__ uint32_t span_at(const uint32_t (&v)[K])
     if constexpr ((I & 3) == 0) return v[I >> 2];
     else return __builtin_amdgcn_alignbyte(v[(I >> 2) + 1], v[I >> 2], I & 3);
 }
+// lowest set bit of the 64 bits x0 (low), x1; 64 if there is none.  Written as a select straight on the count, it compiles without a compare:
+// v_ffbl_b32 of 0 is 0xFFFFFFFF, so the bit is min(ffbl(x0), ffbl(x1) + 32 saturated, 64)
+__device__ __forceinline__ uint32_t zs_ctz64(uint32_t x0, uint32_t x1)
+{
+    const uint64_t x = (uint64_t)x0 | ((uint64_t)x1 << 32);
+    return x ? (uint32_t)__builtin_ctzll(x) : 64u;
+}
+// any lane of the wavefront, as a test of the ballot: given a compare, that is the compare's own mask tested on the scalar unit (__any() turns
+// its argument into an integer first: a select and a second compare on the vector unit)
+__device__ __forceinline__ bool zs_wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
 // bytes two 16-byte pieces agree on from their start (16: all)
 __device__ __forceinline__ uint32_t zs_agree16(const uint32_t (&a)[4], const uint32_t (&b)[4])
 {
-    const uint64_t x0 = (uint64_t)(a[0] ^ b[0]) | ((uint64_t)(a[1] ^ b[1]) << 32), x1 = (uint64_t)(a[2] ^ b[2]) | ((uint64_t)(a[3] ^ b[3]) << 32);
-    const uint32_t n0 = x0 ? ((uint32_t)__builtin_ctzll(x0) >> 3) : 8u;
-    const uint32_t n1 = x1 ? ((uint32_t)__builtin_ctzll(x1) >> 3) : 8u;
-    return (n0 < 8u) ? n0 : 8u + n1;
+    const uint32_t n0 = zs_ctz64(a[0] ^ b[0], a[1] ^ b[1]), n1 = zs_ctz64(a[2] ^ b[2], a[3] ^ b[3]);
+    return (n0 < 64u ? n0 : 64u + n1) >> 3;
 }
 // or / max / min over the LPW (2 or 4) adjacent lanes of a walker (data-parallel-primitive moves inside a quad: no LDS round trip)
 template <int LPW> __device__ __forceinline__ uint32_t walker_or(uint32_t v)
@@ -539,7 +549,15 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     // LDS address of staged position v (v may be a little negative: row -1 = the front pad); of source position p (a prefixed unit: v = p + pfx)
     auto lposv = [](uint32_t v) { return SRC + v + (uint32_t)__mul24((int)v >> 8, (int)ZS_WALK_SKEW); };
     const uint32_t vb = PFX ? pfx : 0u;
-    auto lpos = [&](uint32_t p) { return lposv(p + vb); };
+    // The walk's reads (lds_span) take that address in two parts, lbase + the constant SRCB.  Rows are counted from position -256 SRCM, with
+    // SRCM the whole rows' storage that fits below SRC: with t = v + 256 SRCM (never negative),
+    // lposv(v) = SRC + (t - 256 SRCM) + SKEW * ((t >> 8) - SRCM) = t + SKEW * (t >> 8) + SRC - (256 + SKEW) SRCM.  So the base is one add (which
+    // takes in a "- 4" or the prefix), a shift and an unsigned multiply-add (v_mad_u32_u24), and what is left of SRC is less than a row's
+    // storage: it fits the offset fields of the reads, those of a two-dword read (8 bits, in dwords) included, and costs no instruction.
+    constexpr uint32_t SRCM = SRC / (256u + ZS_WALK_SKEW), SRCB = SRC - (256u + ZS_WALK_SKEW) * SRCM;
+    static_assert(SRCM >= 1 && SRCB % 4u == 0 && SRCB / 4u + 5u < 256u, "the constant part fits the offset field of ds_read2_b32");
+    auto lbasev = [](uint32_t v) { const uint32_t t = v + 256u * SRCM; return t + __umul24(t >> 8, ZS_WALK_SKEW); };
+    auto lbase = [&](uint32_t p) { return lbasev(p + vb); };
     // 16 source bytes at staged position i (a multiple of 16) into the skewed copy, and into the row before's tail where they are a row's head
     auto stage16 = [&](uint32_t i, const uint4 v) {
         uint8_t *d = walkLds + lposv(i);
@@ -558,12 +576,14 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
     const uint8_t *distHi = zs_block_dist_hi(distHiAll, slot);
     uint4 *xbuf = reinterpret_cast<uint4 *>(walkLds);                              // exchange buffer: wavefront w's region holds GPL x 64 slots of 8 distances: lane t's k-th group at [(64 w) GPL + 64 k + t]
     const uint32_t xw = (tid & ~63u) * GPL;                                      // my wavefront's first slot
-    const uint32_t safeAddr = (xw + lane) * 16u;                                 // LDS address of my own first slot: where a lane with nothing to read reads (its own banks, no conflict)
+    const uint32_t safeAddr = (xw + lane) * 16u;                                 // LDS address of my own first slot: the base a lane with nothing to read reads at (16 bytes a lane apart: its own banks, no conflict;
+                                                                                 // with the reads' constant SRCB that is SRCB bytes further up, inside the allocation, and nobody looks at what comes back)
     uint32_t *mixedWord = reinterpret_cast<uint32_t *>(walkLds + SRC + ZS_WALK_SRCBYTES(CAP)) + 1;   // some byte of the unit differs from its first (16 bytes are kept here: xhi stays aligned)
     uint4 *res = zs_block_range_results(resAll, slot);                         // per walk range (R >= 256: at most 256 a block): records, last match end in its block, last offset
     uint8_t *xhi = reinterpret_cast<uint8_t *>(mixedWord + 3);                        // BIG: lane t's byte of bit 16 of its 8 distances
     uint2 *recs = zs_block_walk_records(recAll, slot);                        // range at unit position p: slots from p / 4 (its matches start inside it, >= 4 bytes each)
     const uint32_t sub = lane & (LPW - 1u);
+    const uint32_t wslot = xw + (lane & ~(LPW - 1u));                            // my walker's first slot of the exchange buffer
 #ifdef ZS_WALK_PROFILE
     unsigned long long wprof[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, wlast;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wlast) :: "memory");
@@ -698,7 +718,8 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
             if (active) loadGroup(ip);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        while (__any(active)) {
+        while (zs_wave_any(ip < scanEnd)) {                                      // (= active, in every lane: a walker at rest keeps its ip >= scanEnd, a lane without a range has 0 < 0; asked of the integers, the test needs no copy of the flag.
+                                                                                 // The ZS_WALK_PROFILE count below still reads `active`: whoever changes one of the two keeps the other in step)
             WPROF_STAMP(1)
 #ifdef ZS_WALK_PROFILE
             wprof[8] += 1; wprof[9] += (unsigned long long)__popcll(__ballot(active));
@@ -717,9 +738,9 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
                 // their own: walk 0.567 -> 0.549 ms without the branches))
                 {
                     const bool tr = t0 || t1;
-                    lds_span<SP>(tr ? lpos(p0) : safeAddr, a);
-                    lds_span<SP>(tr ? lpos(t0 ? p0 - rep0 : p0) : safeAddr, b);
-                    lds_span<SP>(tr ? lpos(t1 ? p0 - rep1 : p0) : safeAddr, c);
+                    lds_span<SP, SRCB>(tr ? lbase(p0) : safeAddr, a);
+                    lds_span<SP, SRCB>(tr ? lbase(t0 ? p0 - rep0 : p0) : safeAddr, b);
+                    lds_span<SP, SRCB>(tr ? lbase(t1 ? p0 - rep1 : p0) : safeAddr, c);
                 }
                 auto tryAt = [&](auto iTag) {
                     constexpr int I = decltype(iTag)::value;
@@ -762,10 +783,18 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
                 m &= m - 1;
                 const uint32_t q = ip + idx[c];
                 // the distance: group (q >> 3) - (ip >> 3) of the walker, that lane's slot of the exchange buffer (same wavefront: in order behind the stores above)
-                const uint32_t j = (q >> 3) - (ip >> 3);                         // its group: lane j % LPW of the walker, that lane's group j / LPW
-                const uint32_t owner = xw + 64u * (j / LPW) + (lane & ~(LPW - 1u)) + (j % LPW);
-                dv[c] = reinterpret_cast<const uint16_t *>(xbuf + owner)[q & 7u];
-                if (BIG) dv[c] |= (((uint32_t)xhi[owner] >> (q & 7u)) & 1u) << 16;
+                if constexpr (GPL == 1) {
+                    // a group a lane: the walker's LPW slots are adjacent, its 8 WGRP distances one run of 16-bit words from its first lane's slot
+                    // (and its LPW bytes of bit 16 one run of bits): the distance of q is word q - (ip & ~7) of it (< 8 WGRP: q < wend)
+                    const uint32_t d = (ip & 7u) + idx[c];
+                    dv[c] = reinterpret_cast<const uint16_t *>(xbuf + wslot)[d];
+                    if (BIG) dv[c] |= (((uint32_t)xhi[wslot + (d >> 3)] >> (d & 7u)) & 1u) << 16;
+                } else {
+                    const uint32_t j = (q >> 3) - (ip >> 3);                     // its group: lane j % LPW of the walker, that lane's group j / LPW
+                    const uint32_t owner = xw + 64u * (j / LPW) + (lane & ~(LPW - 1u)) + (j % LPW);
+                    dv[c] = reinterpret_cast<const uint16_t *>(xbuf + owner)[q & 7u];
+                    if (BIG) dv[c] |= (((uint32_t)xhi[owner] >> (q & 7u)) & 1u) << 16;
+                }
             }
             #pragma unroll
             for (uint32_t c = 0; c < CPL; c++) asm volatile("" : "+v"(dv[c]));      // every candidate's distance is read before the first is used: one LDS round trip, not one a candidate
@@ -786,8 +815,8 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
                 #pragma unroll
                 for (int k = 0; k < 3; k++) { sa[c][k] = 0; sb[c][k] = 0; }
                 const bool tr = have[c];
-                lds_span<3>(tr ? lpos(q - 4) : safeAddr, sa[c]);
-                lds_span<3>(tr ? lpos(q - off[c] - 4) : safeAddr, sb[c]);
+                lds_span<3, SRCB>(tr ? lbase(q - 4) : safeAddr, sa[c]);
+                lds_span<3, SRCB>(tr ? lbase(q - off[c] - 4) : safeAddr, sb[c]);
             }
             #pragma unroll
             for (uint32_t c = 0; c < CPL; c++) asm volatile("" : "+v"(sa[c][0]), "+v"(sa[c][1]), "+v"(sa[c][2]), "+v"(sb[c][0]), "+v"(sb[c][1]), "+v"(sb[c][2]));
@@ -796,12 +825,11 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
                 const uint32_t q = ip + idx[c];
                 const uint32_t (&a)[3] = sa[c], (&b)[3] = sb[c];
                 const uint32_t xb = a[0] ^ b[0], x0 = a[1] ^ b[1], x1 = a[2] ^ b[2];
-                const uint32_t f0 = x0 ? (uint32_t)__builtin_ctz(x0) : 32u, f1 = x1 ? (uint32_t)__builtin_ctz(x1) : 32u;
-                const uint32_t fwd = min(((x0 ? f0 : 32u + f1)) >> 3, limit - q);
+                const uint32_t fwd = min(zs_ctz64(x0, x1) >> 3, limit - q);
                 const uint32_t maxBack = min(min(q - anchor, q + vb - off[c]), ZS_BCAP);
                 const uint32_t back = min(xb ? ((uint32_t)__builtin_clz(xb) >> 3) : 4u, maxBack);
                 if (have[c] && fwd >= (isRep[c] ? ZS_REPMIN : ZS_MINMATCH)) {
-                    const int gain = (int)(4u * fwd + 8u * back) - (isRep[c] ? 0 : (int)zs_highbit(off[c] + 1)) - 5 * (int)idx[c];
+                    const int gain = (int)(4u * (fwd - idx[c]) + 8u * back) - (isRep[c] ? 0 : (int)zs_highbit(off[c] + 1)) - (int)idx[c];   // 4 fwd + 8 back - cost - 5 idx (written as 5 * idx it is a v_mul_lo_u32: quarter rate)
                     const int key = ((gain + 2048) << 3) | (int)(7u - (sub * CPL + c));
                     if (key > bestKey) { bestKey = key; bestPack = idx[c] | (fwd << 8) | (back << 16); bestOff = off[c]; }
                 }
@@ -816,15 +844,15 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
             const bool extend = took && bfwd == ZS_FCAP && (limit - bq) > ZS_FCAP;
             bool need = extend;
             uint32_t pos = bq + ZS_FCAP;
-            while (__any(need)) {
+            while (zs_wave_any(need)) {
                 uint32_t e = 0xFFFFFFFFu;                                        // bytes gained if the match ends in this lane's piece
                 if (need) {
                     const uint32_t cap = limit - pos, fo = 16u * sub;            // cap >= 1 while need
                     uint32_t nb = 0;
                     if (fo < cap) {
                         uint32_t a[4], b[4];
-                        lds_span<4>(lpos(pos + fo), a);
-                        lds_span<4>(lpos(pos - boff + fo), b);
+                        lds_span<4, SRCB>(lbase(pos + fo), a);
+                        lds_span<4, SRCB>(lbase(pos - boff + fo), b);
                         nb = zs_agree16(a, b);
                     }
                     if (nb < 16u || fo + 16u >= cap) e = min(fo + nb, cap);
