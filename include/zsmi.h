@@ -695,7 +695,8 @@ int zsmi_seekableReadRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const u
  * On an archive, text is the content of frames [firstFrame, firstFrame + frameCount) as one run and B = firstRecord[firstFrame]; an
  * occurrence that crosses the window's border is not found.  Frame f begins a record exactly when f == 0 or firstRecord[f] !=
  * firstRecord[f - 1], so windows cut at such frames together find what one window over all of them finds.
- * Not covered: several patterns a call, ignoring case, anchors, regular expressions, patterns that hold the delimiter.
+ * Not covered: anchors, regular expressions, patterns that hold the delimiter (several patterns a call and ignoring case: the query
+ * calls below).
  * pattern is HOST memory in every form - a parameter like delim, handed to the kernels by value: no upload, no pinned staging, no wait.
  * dResult / result: four words - [0] total or (uint64_t)-code, [1] the numbers written, min(total, capacity), [2] matches, [3] the bytes
  * scanned; [0] and [2] are exact whatever capacity is, so that a second call can be sized.  capacity == 0 with NULL dRecords only counts.
@@ -729,6 +730,41 @@ int zsmi_seekableFindRecordsResident(zsmi_ctx *ctx, const zsmi_seekable *sk, con
 int zsmi_seekableFindRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
                                  const void *pattern, uint32_t patternSize, uint32_t firstFrame, uint32_t frameCount,
                                  uint64_t *records, size_t capacity, uint64_t *result);
+/* Find records by several patterns: any of them, all of them or none (grep -e .. -e .., grep -v), with or without ASCII case folding
+ * (grep -i) - one search and, on an archive, one decode of the window, beside the single-pattern calls above, which are unchanged.  A
+ * query is nPatterns patterns (1 .. 8; HOST memory, handed to the kernels by value like the single pattern) of 1 .. 256 bytes each and at
+ * most 256 together, a mode and flags.  The rule (zstandard_amd/csrc/zsmi_findquery.h states it in code):
+ *  1. fold(b) = b + 0x20 for b in 'A' .. 'Z' when ZSMI_FIND_IGNORE_CASE is set, b otherwise; bytes of 0x80 and above are never touched.
+ *  2. An occurrence of pattern j is a position p with p + m_j <= len and fold(text[p + i]) == fold(P_j[i]) for every i.  Overlapping
+ *     occurrences count, and so do occurrences of two patterns at one position.
+ *  3. No pattern byte may satisfy fold(P_j[i]) == fold(delim); a text byte is a delimiter exactly when it equals delim, unfolded.
+ *  4. The records are the splitter's: one ends behind each delimiter, bytes behind the last delimiter are a last record; numbered from B.
+ *  5. H(r): the set of j with an occurrence of P_j in record r, bit j of an 8-bit word.
+ *  6. The answer is the records whose H satisfies the mode, ascending - any: H != 0; all: every j < nPatterns; none: H == 0 (empty
+ *     records included).  total: their count; matches: the occurrences summed over the patterns; hits[k]: H of the k-th record written.
+ * With one pattern, `any` and no flag the answer is the single-pattern call's.  Not covered: anchors, regular expressions, patterns that
+ * hold the delimiter, Unicode case folding, more than 8 patterns, occurrence counts a pattern.
+ * The contract is that of the single-pattern calls, word for word: the four result words, capacity == 0 with NULL dRecords only counts,
+ * nothing is written behind dRecords[capacity) or dHits[capacity) (a NULL dHits / hits: not wanted), nothing is read outside the source,
+ * the device forms only queue work; on an archive the window, B, the failing-frame rule and zsmi_seekableFindWorkBound are as above.
+ * Checked on the host in the order above with q where pattern stood (a NULL q: GENERIC), and of the query, where the single pattern's
+ * checks stood: delim outside 0..255, nPatterns 0 or above 8, a mode above 2, unknown flag bits: parameter_outOfBound; then a pattern at
+ * a time a NULL patterns[j]: GENERIC, patternSizes[j] 0 or above 256 or a sum above 256: parameter_outOfBound; then a pattern byte whose
+ * fold is the delimiter's: parameter_outOfBound. */
+#define ZSMI_FIND_MAX_PATTERNS 8u
+#define ZSMI_FIND_IGNORE_CASE  1u                 /* flags */
+enum { ZSMI_find_any = 0, ZSMI_find_all = 1, ZSMI_find_none = 2 };   /* mode */
+typedef struct { uint32_t nPatterns, mode, flags; const void *patterns[8]; uint32_t patternSizes[8]; } zsmi_findQuery;
+size_t zsmi_findRecordsQuery(const void *src, size_t srcSize, int delim, const zsmi_findQuery *q, uint64_t base,
+                             uint64_t *records, uint8_t *hits, size_t capacity, uint64_t *matches);
+int zsmi_findRecordsQueryDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, int delim, const zsmi_findQuery *q,
+                                const uint64_t *dBase, uint64_t *dRecords, uint8_t *dHits, uint64_t capacity, uint64_t *dResult);
+int zsmi_seekableFindQueryResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
+                                   const zsmi_findQuery *q, uint32_t firstFrame, uint32_t frameCount, void *dWork, uint64_t workCapacity,
+                                   uint64_t *dRecords, uint8_t *dHits, uint64_t capacity, uint64_t *dResult);
+int zsmi_seekableFindQueryHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
+                               const zsmi_findQuery *q, uint32_t firstFrame, uint32_t frameCount,
+                               uint64_t *records, uint8_t *hits, size_t capacity, uint64_t *result);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

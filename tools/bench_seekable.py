@@ -43,7 +43,10 @@ pattern: zsmi_findRecordsDevice and its kernels one by one against k_split_count
 zsmi_seekableFindRecordsResident over the whole archive against the whole-content range read of the same handle, and today's way - that
 range read, the copy to the host and bytes.find there (find_legs' docstring).  A JSON line a pattern, also appended to
 profiles/find_records_bench.jsonl.
-  python tools/bench_seekable.py --split --find "ERROR ienwbvuzw" e [--mib 1024] [--find-targets 4096 65536]"""
+  python tools/bench_seekable.py --split --find "ERROR ienwbvuzw" e [--mib 1024] [--find-targets 4096 65536]
+--split --find-query: find records by several patterns on the same stream and on its 64 KiB-frame archive, against the single-pattern calls
+in the same process (find_query_legs' docstring).  One JSON line, also appended to profiles/find_query_bench.jsonl.
+  python tools/bench_seekable.py --split --find-query [--mib 1024]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -589,8 +592,121 @@ def find_legs(a):
             print(line, flush=True); f.write(line + "\n")
 
 
+def find_query_legs(a):
+    """--split --find-query: find records by several patterns (zsmi_findRecordsQueryDevice, zsmi_seekableFindQueryResident) on the Zipf
+    log stream, 1 GiB in device memory, against the single-pattern calls in the same process.  Legs in turn, three rounds, every call
+    followed by a synchronisation; the sorted times of each leg.
+      k1:       the query call with one pattern, `any`, against zsmi_findRecordsDevice on that pattern - a rare one and one most lines hold
+      k4, k8:   K patterns, `any`, against K single-pattern calls one after the other (their answers are NOT merged: the merge on the
+                host, and the K - 1 copies it needs, are not counted against them)
+      fold:     the K = 4 query with ZSMI_FIND_IGNORE_CASE against the same query without
+      none:     `none` of the rare pattern, which writes nearly every record number, against `any` of it
+      archive:  on the 64 KiB-frame archive, K = 4 `any` against 4 zsmi_seekableFindRecordsResident calls: one decode against four
+    Every answer is held against the single-pattern calls' - the union for `any`, the complement's count for `none` - and the folded
+    query against the unfolded one with both cases spelled out."""
+    size, M, reps = (a.mib or 1024) << 20, a.frame, 3
+    gib = size / float(1 << 30)
+    bc = BatchCodec(0)
+    host = D.zipf_log(size)
+    src = torch.from_numpy(host).cuda()
+    del host
+    words = torch.zeros(4, dtype=torch.int64, device="cuda")
+    bc.count_records_device(src.data_ptr(), size, words.data_ptr()); bc.sync()
+    records = int(words[0].item())
+    ms = lambda v: [round(t * 1e3, 4) for t in v]
+    mid = lambda v: float(np.median(v))
+    sync = lambda: (bc.sync(), torch.cuda.synchronize())
+    found = torch.zeros(records, dtype=torch.int64, device="cuda"); hits = torch.zeros(records, dtype=torch.uint8, device="cuda")
+    res = torch.zeros(4, dtype=torch.int64, device="cuda")
+    rare, common = b"ERROR ienwbvuzw", b"e"
+    eight = [b"ERROR", b"WARN", b"jzpvzxzz", b"dwon", b"DEBUG ienwbvuzw", b"qky", b"vhgovduu", b"INFO ang"]
+
+    def single(pat):
+        return lambda: bc.find_records_device(src.data_ptr(), size, pat, found.data_ptr(), records, res.data_ptr())
+
+    def query(pats, mode="any", fold=False):
+        return lambda: bc.find_records_query_device(src.data_ptr(), size, pats, found.data_ptr(), hits.data_ptr(), records, res.data_ptr(), mode=mode, ignore_case=fold)
+
+    def singles(pats):
+        calls = [single(p) for p in pats]
+        return lambda: [c() for c in calls]
+
+    def answer(fn):
+        fn(); sync()
+        total, written, matches, scanned = (int(v) for v in res.tolist())
+        assert written == total and scanned == size
+        return found[:total].clone(), matches
+
+    def union(pats):
+        rows, matches = [], 0
+        for p in pats:
+            r, m = answer(single(p))
+            rows.append(r); matches += m
+        return torch.unique(torch.cat(rows)), matches          # (sorted)
+    rep = {"metric": "find_query", "gib": gib, "records": records}
+    for name, pat in (("k1_rare", rare), ("k1_common", common)):
+        t = alternating({"query": query([pat]), "single": single(pat)}, sync, reps)
+        got, want = answer(query([pat])), answer(single(pat))
+        assert torch.equal(got[0], want[0]) and got[1] == want[1], "the query call with one pattern and the single-pattern call differ"
+        rep[name] = {"pattern": pat.decode(), "records_found": int(got[0].numel()), "query_ms": ms(t["query"]), "single_ms": ms(t["single"]),
+                     "query_over_single": round(mid(t["query"]) / mid(t["single"]), 3)}
+    for K in (4, 8):
+        pats = eight[:K]
+        t = alternating({"query": query(pats), "singles": singles(pats)}, sync, reps)
+        got, want = answer(query(pats)), union(pats)
+        assert torch.equal(got[0], want[0]) and got[1] == want[1], "the query's answer is not the union of the single-pattern answers"
+        rep["k%d_any" % K] = {"patterns": [p.decode() for p in pats], "records_found": int(got[0].numel()), "query_ms": ms(t["query"]), "singles_ms": ms(t["singles"]),
+                              "query_over_singles": round(mid(t["query"]) / mid(t["singles"]), 3)}
+    pats = eight[:4]
+    lower = [p.lower() for p in pats]
+    t = alternating({"fold": query(lower, fold=True), "plain": query(pats)}, sync, reps)
+    got, want = answer(query(lower, fold=True)), union(pats + lower)
+    assert torch.equal(got[0], want[0]), "the folded query's answer is not the union over both cases"
+    rep["k4_fold"] = {"records_found": int(got[0].numel()), "fold_ms": ms(t["fold"]), "plain_ms": ms(t["plain"]), "fold_over_plain": round(mid(t["fold"]) / mid(t["plain"]), 3)}
+    t = alternating({"none": query([rare], "none"), "any": query([rare]), "single": single(rare)}, sync, reps)
+    got, want = answer(query([rare], "none")), answer(single(rare))
+    assert int(got[0].numel()) == records - int(want[0].numel()) and not bool(torch.isin(want[0], got[0]).any()), "`none` is not the complement"
+    rep["none_rare"] = {"records_found": int(got[0].numel()), "none_ms": ms(t["none"]), "any_ms": ms(t["any"]), "single_ms": ms(t["single"]),
+                        "none_over_single": round(mid(t["none"]) / mid(t["single"]), 3)}
+    T = 65536
+    Mx = max(T, M)
+    mp = BatchCodec.split_pieces_bound(records, size, Mx)
+    fs = torch.zeros(mp, dtype=torch.int32, device="cuda"); fr = torch.zeros(mp + 1, dtype=torch.int64, device="cuda")
+    bc.split_records_device(src.data_ptr(), size, mp, fs.data_ptr(), fr.data_ptr(), words.data_ptr() + 8, target_size=T, max_frame_size=Mx); bc.sync()
+    n = int(words[1].item())
+    bound = bc.seekable_frames_resident_bound(size, n, True)
+    arc = torch.empty(bound, dtype=torch.uint8, device="cuda"); arc_size = torch.zeros(1, dtype=torch.int64, device="cuda")
+    bc.compress_seekable_frames_resident(src.data_ptr(), size, fs.data_ptr(), n, Mx, arc.data_ptr(), bound, arc_size.data_ptr(), level=a.level, checksum=True); bc.sync()
+    m = int(arc_size.item())
+    assert 0 < m <= bound, hex(m)
+    want = union(pats)
+    del src
+    sk = bc.open_seekable_device(arc.data_ptr(), m)
+    work_cap = sk.find_work_bound(0, n)
+    assert work_cap == size
+    work = torch.empty(size, dtype=torch.uint8, device="cuda")
+
+    def archive_query():
+        sk.find_query_resident(fr.data_ptr(), n, pats, 0, n, work.data_ptr(), work_cap, found.data_ptr(), hits.data_ptr(), records, res.data_ptr())
+
+    def archive_singles():
+        for p in pats:
+            sk.find_records_resident(fr.data_ptr(), n, p, 0, n, work.data_ptr(), work_cap, found.data_ptr(), records, res.data_ptr())
+    t = alternating({"query": archive_query, "singles": archive_singles}, sync, reps)
+    got = answer(archive_query)
+    assert torch.equal(got[0], want[0]) and got[1] == want[1], "the archive query's answer is not the union of the text's single-pattern answers"
+    rep["archive_k4_any"] = {"target": T, "frames": n, "query_ms": ms(t["query"]), "singles_ms": ms(t["singles"]), "query_over_singles": round(mid(t["query"]) / mid(t["singles"]), 3)}
+    bc.sync(); sk.close(); bc.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    line = json.dumps(rep)
+    print(line, flush=True)
+    with open(a.out or os.path.join(ROOT, "profiles", "find_query_bench.jsonl"), "a") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--find-query", action="store_true", help="with --split: find records by several patterns against the single-pattern calls (find_query_legs' docstring)")
     ap.add_argument("--find", nargs="+", default=None, help="with --split: find records by content, a leg set a pattern (a rare one and one most lines hold)")
     ap.add_argument("--find-targets", type=int, nargs="+", default=[4096, 65536], help="with --split --find: the archives' targetSizes")
     ap.add_argument("--out", default=None, help="with --split --find: the file the JSON lines are appended to (default profiles/find_records_bench.jsonl)")
@@ -617,6 +733,8 @@ def main():
     if a.index:
         return index_legs(a)
     if a.split:
+        if a.find_query:
+            return find_query_legs(a)
         return find_legs(a) if a.find else (lines_legs(a) if a.lines else split_legs(a))
     if a.records:
         return records(a)

@@ -69,6 +69,12 @@ class FastCoverParams(ctypes.Structure):
                 ("splitPoint", ctypes.c_double), ("level", ctypes.c_int), ("dictID", ctypes.c_uint)]
 
 
+class FindQuery(ctypes.Structure):
+    """zsmi_findQuery: up to 8 patterns (host bytes, kept alive by the caller), a mode (0 any, 1 all, 2 none) and flags (1: ignore ASCII case)"""
+    _fields_ = [("nPatterns", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("patterns", ctypes.c_void_p * 8),
+                ("patternSizes", ctypes.c_uint32 * 8)]
+
+
 class KernelTime(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("seconds", ctypes.c_double), ("launches", ctypes.c_uint32)]
 
@@ -201,6 +207,12 @@ def lib():
     L.zsmi_seekableFindRecordsResident.restype = i32
     L.zsmi_seekableFindRecordsResident.argtypes = [vp, vp, vp, u32, i32, vp, u32, u32, u32, vp, u64, vp, u64, vp]
     L.zsmi_seekableFindRecordsHost.restype = i32; L.zsmi_seekableFindRecordsHost.argtypes = [vp, vp, vp, u32, i32, vp, u32, u32, u32, vp, sz, vp]
+    pq = ctypes.POINTER(FindQuery)
+    L.zsmi_findRecordsQuery.restype = sz; L.zsmi_findRecordsQuery.argtypes = [vp, sz, i32, pq, u64, vp, vp, sz, pu64]
+    L.zsmi_findRecordsQueryDevice.restype = i32; L.zsmi_findRecordsQueryDevice.argtypes = [vp, vp, u64, i32, pq, vp, vp, vp, u64, vp]
+    L.zsmi_seekableFindQueryResident.restype = i32
+    L.zsmi_seekableFindQueryResident.argtypes = [vp, vp, vp, u32, i32, pq, u32, u32, vp, u64, vp, vp, u64, vp]
+    L.zsmi_seekableFindQueryHost.restype = i32; L.zsmi_seekableFindQueryHost.argtypes = [vp, vp, vp, u32, i32, pq, u32, u32, vp, vp, sz, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -290,6 +302,7 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_splitRecords", "zsmi_countRecordsDevice", "zsmi_splitRecordsDevice",
            "zsmi_seekableRecordsWorkBound", "zsmi_seekableReadRecordsResident", "zsmi_seekableReadRecordsHost",
            "zsmi_findRecords", "zsmi_findRecordsDevice", "zsmi_seekableFindWorkBound", "zsmi_seekableFindRecordsResident", "zsmi_seekableFindRecordsHost",
+           "zsmi_findRecordsQuery", "zsmi_findRecordsQueryDevice", "zsmi_seekableFindQueryResident", "zsmi_seekableFindQueryHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

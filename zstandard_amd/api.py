@@ -156,6 +156,39 @@ def find_records(data, pattern, delimiter=b"\n", base=0):
     return [int(v) for v in out[:total]]
 
 
+FIND_MODES = {"any": 0, "all": 1, "none": 2}
+
+
+def _find_query(patterns, mode, ignore_case):
+    """(zsmi_findQuery, the buffers its pointers name - keep them until the call returns): the patterns are HOST bytes, read during the call"""
+    if mode not in FIND_MODES:
+        raise ValueError("mode is one of 'any', 'all', 'none'")
+    pats = [bytes(p) for p in patterns]
+    q = _lib.FindQuery()
+    q.nPatterns, q.mode, q.flags = len(pats), FIND_MODES[mode], 1 if ignore_case else 0
+    keep = [ctypes.create_string_buffer(p, max(len(p), 1)) for p in pats[:8]]
+    for j, buf in enumerate(keep):
+        q.patterns[j] = ctypes.cast(buf, ctypes.c_void_p)
+        q.patternSizes[j] = len(pats[j])
+    return q, keep
+
+
+def find_records_query(data, patterns, mode="any", ignore_case=False, delimiter=b"\n", base=0, return_hits=False):
+    """the records of delimited text that hold any of `patterns`, all of them, or none (mode; 'none' is grep -v and lists empty records
+    too): 1 .. 8 literal byte strings of 256 bytes together, none with the delimiter; ignore_case folds 'A' .. 'Z' only (zsmi_findRecordsQuery,
+    host only).  The list of their numbers, ascending; with return_hits (numbers, hits): hits[k] has bit j set where pattern j occurs in
+    record numbers[k]."""
+    L = _lib.lib()
+    s, n = _buf(data)
+    d = _delimiter(delimiter)
+    q, keep = _find_query(patterns, mode, ignore_case)
+    total = _raise_if_error(L, L.zsmi_findRecordsQuery(s, n, d, ctypes.byref(q), base, None, None, 0, None))
+    out = np.zeros(max(total, 1), dtype=np.uint64); hits = np.zeros(max(total, 1), dtype=np.uint8)
+    _raise_if_error(L, L.zsmi_findRecordsQuery(s, n, d, ctypes.byref(q), base, ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(hits.ctypes.data), total, None))
+    records = [int(v) for v in out[:total]]
+    return (records, [int(v) for v in hits[:total]]) if return_hits else records
+
+
 class ZStdDecompress:
     """EPAM.Deltix.ZStd.ZStdDecompress (static). Sizes are 32-bit in the reference (size_t = UInt32, ZStdDecompress.cs:14)."""
 
@@ -530,6 +563,33 @@ class SeekableArchive:
                 return []
         return [int(v) for v in out[:int(result[1])]]
 
+    def find_records_query(self, first_record, patterns, mode="any", ignore_case=False, delimiter=b"\n", first_frame=0, frame_count=None, return_hits=False):
+        """find_records for a query of 1 .. 8 patterns: the records of the window that hold any of them, all of them or none (mode), with
+        or without ASCII case folding, after ONE decode of the window (find_records_query states the rule; the window as in find_records).
+        The list of their numbers, ascending; with return_hits (numbers, hits).  zsmi_seekableFindQueryHost"""
+        self._open()
+        first = np.ascontiguousarray(first_record, dtype=np.uint64)
+        q, keep = _find_query(patterns, mode, ignore_case)
+        d = _delimiter(delimiter)
+        count = self.num_frames - first_frame if frame_count is None else frame_count
+        p = BatchCodec._p
+        result = np.zeros(4, dtype=np.uint64)
+        out = np.zeros(1, dtype=np.uint64); hits = np.zeros(1, dtype=np.uint8)
+        for cap in (0, None):
+            cap = int(result[0]) if cap is None else cap
+            out = np.zeros(max(cap, 1), dtype=np.uint64); hits = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = self.L.zsmi_seekableFindQueryHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(q), first_frame, count,
+                                                   p(out) if cap else None, p(hits) if cap else None, cap, p(result))
+            if rc:
+                raise RuntimeError(_error_name(self.L, rc))
+            if int(result[0]) > (1 << 64) - ERROR_MAX_CODE:
+                raise RuntimeError(_error_name(self.L, (1 << 64) - int(result[0])))
+            if int(result[0]) == 0:
+                return ([], []) if return_hits else []
+        n = int(result[1])
+        records = [int(v) for v in out[:n]]
+        return (records, [int(v) for v in hits[:n]]) if return_hits else records
+
     def read_many(self, ranges, return_codes=False):
         """ranges: (offset, length) pairs -> the list of their bytes (each clipped at the content's end), one call for all of them
         (zsmi_seekableReadRangesHost).  A failing range raises RuntimeError with the error's name and the range's index; with
@@ -746,6 +806,20 @@ class SeekableHandle:
                                                      frame_count, p(d_work_ptr), work_capacity, p(d_records_ptr), capacity, p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_seekableFindRecordsResident: {_error_name(self.L, rc)}")
+
+    def find_query_resident(self, d_first_record_ptr, n_frames, patterns, first_frame, frame_count, d_work_ptr, work_capacity, d_records_ptr, d_hits_ptr,
+                            capacity, d_result_ptr, mode="any", ignore_case=False, delimiter=b"\n", codec=None):
+        """find_records_resident for a query of 1 .. 8 patterns (HOST bytes; mode 'any', 'all' or 'none', ignore_case folds 'A' .. 'Z'):
+        one decode of the window into d_work, then d_records (uint64[capacity]) receives the numbers of the records whose hit set
+        satisfies the mode, d_hits (uint8[capacity]; 0: not wanted) their hit sets, d_result (uint64[4]) the words of
+        find_records_resident.  Nothing goes to the host.  zsmi_seekableFindQueryResident"""
+        codec = codec or self.codec
+        p = ctypes.c_void_p
+        q, keep = _find_query(patterns, mode, ignore_case)
+        rc = self.L.zsmi_seekableFindQueryResident(codec.ctx, self.handle, p(d_first_record_ptr), n_frames, _delimiter(delimiter), ctypes.byref(q), first_frame,
+                                                   frame_count, p(d_work_ptr), work_capacity, p(d_records_ptr), p(d_hits_ptr), capacity, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableFindQueryResident: {_error_name(self.L, rc)}")
 
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`, from the handle's table"""
@@ -1085,6 +1159,19 @@ class BatchCodec:
                                            ctypes.c_void_p(d_records_ptr), capacity, ctypes.c_void_p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_findRecordsDevice: {_error_name(self.L, rc)}")
+
+    def find_records_query_device(self, d_src_ptr, src_size, patterns, d_records_ptr, d_hits_ptr, capacity, d_result_ptr, mode="any", ignore_case=False,
+                                  delimiter=b"\n", d_base_ptr=0):
+        """find_records_query on the device, the text in device memory (asynchronous: only queued): d_records (uint64[capacity]; 0 with
+        capacity 0: only count) receives the ascending numbers of the records of d_src[0, src_size) whose hit set satisfies the mode,
+        d_hits (uint8[capacity]; 0: not wanted) the hit sets, d_result (uint64[4]) the total, the numbers written, the occurrences summed
+        over the patterns and the bytes searched.  patterns: 1 .. 8 HOST byte strings.  zsmi_findRecordsQueryDevice"""
+        q, keep = _find_query(patterns, mode, ignore_case)
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_findRecordsQueryDevice(self.ctx, p(d_src_ptr), src_size, _delimiter(delimiter), ctypes.byref(q), p(d_base_ptr), p(d_records_ptr),
+                                                p(d_hits_ptr), capacity, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_findRecordsQueryDevice: {_error_name(self.L, rc)}")
 
     def open_seekable_device(self, d_ptr, size, ddict=None, ddict_set=None):
         """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The

@@ -365,18 +365,18 @@ static int findCheck(const zsmi_ctx *c, const zsmi_seekable *sk, const void *fir
     if (!ownWork && workCapacity < bound) return ZSMI_error_dstSize_tooSmall;
     return 0;
 }
-// the launch sequence on an archive, its arguments checked by the caller: the window's frames into dWork, end to end, then findText
-static int findWindow(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, int delim, const void *pattern, uint32_t patternSize, uint32_t firstFrame,
-                      uint32_t frameCount, void *dWork, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult)
+// The decode half of a search on an archive, shared by the single-pattern search below and the query search of findquery.hip (context
+// bound, frameCount > 0, arguments checked by the caller): the scratch of the whole call reserved, then the window's frames into dWork, end
+// to end, verified, and the first failing frame's code in a device word.  Leaves the text's size, its tiles and that word
+struct FindDecoded { uint64_t bytes; FindTiles t; const uint32_t *dCode; };
+static int findDecode(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount, void *dWork, FindDecoded &w)
 {
-    if (const int e = c->bind()) return e;
-    if (frameCount == 0) return c->fill(dResult, 0, 4 * sizeof(uint64_t));
     const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
     const size_t F = frameCount;
+    FindTiles &t = w.t;
     // device words, a frame of the window: 64 bits - sizes [F], places in dWork [F + 1]; verify records [F]; 32 bits - the list, decoder
     // status, refusals, written, codes [F each], the window's code [1, padded to 8 bytes]
     const size_t head = (2 * F + 1) * sizeof(uint64_t) + F * sizeof(ZsSeekItem) + ((5 * F + 1) * sizeof(uint32_t) + 7) / 8 * 8;
-    FindTiles t;
     if (const int e = findReserve(c, bytes, head, F, t)) return e;
     if (!c->dItems.reserve(sizeof(ZsDecItem) * F)) return ZSMI_error_memory_allocation;
     uint64_t *dSizes = (uint64_t *)c->seek.dMeta.p, *dListAt = dSizes + F;
@@ -395,7 +395,18 @@ static int findWindow(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFir
     LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((frameCount + 15) / 16), dim3(64), 0, (const ZsSeekItem *)dVerify, frameCount, (const uint32_t *)dSt,
            sk->t.checksum ? 1 : 0, dCodes, (const uint32_t *)dRefused);
     LAUNCH(c, "k_find_code", k_find_code, dim3(1), dim3(1024), 0, (const uint32_t *)dCodes, frameCount, dCode);
-    return findText(c, dWork, bytes, delim, findPattern(pattern, patternSize), dFirstRecord + firstFrame, dCode, dRecords, capacity, dResult, t);
+    w.bytes = bytes; w.dCode = dCode;
+    return 0;
+}
+// the launch sequence on an archive, its arguments checked by the caller: the decode half, then findText
+static int findWindow(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, int delim, const void *pattern, uint32_t patternSize, uint32_t firstFrame,
+                      uint32_t frameCount, void *dWork, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult)
+{
+    if (const int e = c->bind()) return e;
+    if (frameCount == 0) return c->fill(dResult, 0, 4 * sizeof(uint64_t));
+    FindDecoded w;
+    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, w)) return e;
+    return findText(c, dWork, w.bytes, delim, findPattern(pattern, patternSize), dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, w.t);
 }
 extern "C" int zsmi_seekableFindRecordsResident(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
                                                 const void *pattern, uint32_t patternSize, uint32_t firstFrame, uint32_t frameCount,

@@ -21,6 +21,7 @@
 #include "split.hip"              // feature: the record splitter - delimited records -> frame sizes and line numbers (kernels and host; the rule: zsmi_split.h)
 #include "records.hip"            // feature: records by number from a record archive - firstRecord and record numbers -> the records' bytes (kernels and host; the rules: zsmi_records.h)
 #include "find.hip"               // feature: find records by content - text or a window of a record archive and a literal pattern -> ascending record numbers (kernels and host; the rule: zsmi_find.h)
+#include "findquery.hip"          // feature: find records by several patterns - any, all, none of up to 8 patterns, ASCII case folding -> ascending record numbers and hit sets (kernels and host; the rule: zsmi_findquery.h)
 
 #include <cstdio>
 #include <cstdlib>
