@@ -695,8 +695,8 @@ int zsmi_seekableReadRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const u
  * On an archive, text is the content of frames [firstFrame, firstFrame + frameCount) as one run and B = firstRecord[firstFrame]; an
  * occurrence that crosses the window's border is not found.  Frame f begins a record exactly when f == 0 or firstRecord[f] !=
  * firstRecord[f - 1], so windows cut at such frames together find what one window over all of them finds.
- * Not covered: anchors, regular expressions, patterns that hold the delimiter (several patterns a call and ignoring case: the query
- * calls below).
+ * Not covered: patterns that hold the delimiter (several patterns a call and ignoring case: the query calls below; anchors and regular
+ * expressions: the regular-expression calls below them).
  * pattern is HOST memory in every form - a parameter like delim, handed to the kernels by value: no upload, no pinned staging, no wait.
  * dResult / result: four words - [0] total or (uint64_t)-code, [1] the numbers written, min(total, capacity), [2] matches, [3] the bytes
  * scanned; [0] and [2] are exact whatever capacity is, so that a second call can be sized.  capacity == 0 with NULL dRecords only counts.
@@ -742,8 +742,8 @@ int zsmi_seekableFindRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const u
  *  5. H(r): the set of j with an occurrence of P_j in record r, bit j of an 8-bit word.
  *  6. The answer is the records whose H satisfies the mode, ascending - any: H != 0; all: every j < nPatterns; none: H == 0 (empty
  *     records included).  total: their count; matches: the occurrences summed over the patterns; hits[k]: H of the k-th record written.
- * With one pattern, `any` and no flag the answer is the single-pattern call's.  Not covered: anchors, regular expressions, patterns that
- * hold the delimiter, Unicode case folding, more than 8 patterns, occurrence counts a pattern.
+ * With one pattern, `any` and no flag the answer is the single-pattern call's.  Not covered: patterns that hold the delimiter, Unicode
+ * case folding, more than 8 patterns, occurrence counts a pattern (anchors and regular expressions: the regular-expression calls below).
  * The contract is that of the single-pattern calls, word for word: the four result words, capacity == 0 with NULL dRecords only counts,
  * nothing is written behind dRecords[capacity) or dHits[capacity) (a NULL dHits / hits: not wanted), nothing is read outside the source,
  * the device forms only queue work; on an archive the window, B, the failing-frame rule and zsmi_seekableFindWorkBound are as above.
@@ -765,6 +765,50 @@ int zsmi_seekableFindQueryResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const
 int zsmi_seekableFindQueryHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
                                const zsmi_findQuery *q, uint32_t firstFrame, uint32_t frameCount,
                                uint64_t *records, uint8_t *hits, size_t capacity, uint64_t *result);
+/* Find records by regular expression (grep -E): a third search beside the two above, which are unchanged.  A pattern is compiled on the
+ * HOST into a small DFA, the program - a POD the caller holds and the calls take by pointer from HOST memory, like a query; it reaches the
+ * kernels by value.  The rule (zstandard_amd/csrc/zsmi_regex.h states it in code, with the syntax accepted and the refusals in full):
+ *  1. A record - the splitter's: one ends behind each delimiter, bytes behind the last delimiter are a last record, empty records exist;
+ *     numbered from B - is a byte string without its delimiter.  It MATCHES exactly when Python's
+ *     re.compile(pattern, re.DOTALL | (re.IGNORECASE if ZSMI_FIND_IGNORE_CASE else 0)).search(record) succeeds.  Only existence counts.
+ *  2. The delimiter is a parameter of the search, not of the program: a text byte equal to delim, unfolded, ends a record and is never
+ *     fed to the program, so a `.`, a negated class or \s never sees it.
+ *  3. The answer is the matching records, ascending; with ZSMI_REGEX_INVERT the others, empty records included.
+ * The program: next[s * nClasses + classOf[b]] is the state behind byte b from state s; a record starts in `start` and matches when it
+ * ends in a state s with bit s of `accept` set.  It is THE minimal complete DFA of the pattern, at most 64 states, 256 byte classes and
+ * 3072 table entries.  zsmi_compileRegex: host only; 0, or the code of a refusal with *errorAt (may be NULL) the pattern offset at which it
+ * was decided, and prog is not written - a NULL pattern or prog: GENERIC; patternSize 0 or unknown flag bits: parameter_outOfBound; a
+ * recognised construct that is left out (^ or $ inside, \b \B \A \Z, backreferences, (? but (?:, lazy and possessive suffixes):
+ * parameter_unsupported; malformed input: parameter_outOfBound; a program above the caps: parameter_outOfBound with errorAt = patternSize.
+ * Accepted: literals (bytes of 0x80 and above too), \ before a non-alphanumeric byte, \t \n \r \f \v \xHH, \d \D \w \W \s \S (ASCII), `.`,
+ * [...] and [^...] with ranges, ( ), (?: ), |, * + ?, {m} {m,} {m,n} with m <= n <= 255, ^ first and $ last in a top-level alternative.
+ * Not covered: patterns that hold the delimiter, Unicode, word boundaries, backreferences, more than 64 states.
+ * The calls: the contract of the query calls above, word for word, except the third result word - [0] total or (uint64_t)-code, [1]
+ * min(total, capacity), [2] the RECORDS of the text searched (the delimiters, plus one for bytes behind the last; there is no occurrence
+ * count for a regular expression), [3] the bytes scanned; [0] and [2] are exact whatever capacity is.  capacity == 0 with NULL dRecords
+ * only counts; nothing is written behind dRecords[capacity), nothing read outside the source; the device forms only queue work (72 more
+ * bytes of context scratch a 16 KiB of text than the other searches); srcSize == 0 and frameCount == 0: four zeros; on an archive the
+ * window, B, the failing-frame rule and zsmi_seekableFindWorkBound are the existing ones, and a record the window's border cuts is judged
+ * on the part inside the window.  Checked on the host in the order of the query calls with prog where q stood (a NULL prog: GENERIC) and,
+ * where the query's checks stood: delim outside 0..255, unknown flag bits, nStates outside 1..64, nClasses outside 1..256, nStates *
+ * nClasses above 3072, start >= nStates, a classOf[] >= nClasses, a used next[] >= nStates, an accept bit at or above nStates:
+ * parameter_outOfBound - every call makes this check, so a damaged program never indexes outside a table. */
+#define ZSMI_REGEX_MAX_STATES 64u
+#define ZSMI_REGEX_MAX_TABLE  3072u               /* nStates * nClasses */
+#define ZSMI_REGEX_INVERT     2u                  /* flags, beside ZSMI_FIND_IGNORE_CASE = 1 */
+typedef struct { uint32_t nStates, nClasses, start, flags; uint64_t accept;
+                 uint8_t classOf[256]; uint8_t next[ZSMI_REGEX_MAX_TABLE]; } zsmi_regexProgram;
+int zsmi_compileRegex(const void *pattern, size_t patternSize, uint32_t flags, zsmi_regexProgram *prog, size_t *errorAt);
+size_t zsmi_findRecordsRegex(const void *src, size_t srcSize, int delim, const zsmi_regexProgram *prog, uint64_t base,
+                             uint64_t *records, size_t capacity, uint64_t *textRecords);
+int zsmi_findRecordsRegexDevice(zsmi_ctx *ctx, const void *dSrc, uint64_t srcSize, int delim, const zsmi_regexProgram *prog,
+                                const uint64_t *dBase, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult);
+int zsmi_seekableFindRegexResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
+                                   const zsmi_regexProgram *prog, uint32_t firstFrame, uint32_t frameCount, void *dWork,
+                                   uint64_t workCapacity, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult);
+int zsmi_seekableFindRegexHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
+                               const zsmi_regexProgram *prog, uint32_t firstFrame, uint32_t frameCount,
+                               uint64_t *records, size_t capacity, uint64_t *result);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

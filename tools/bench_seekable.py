@@ -46,7 +46,11 @@ profiles/find_records_bench.jsonl.
   python tools/bench_seekable.py --split --find "ERROR ienwbvuzw" e [--mib 1024] [--find-targets 4096 65536]
 --split --find-query: find records by several patterns on the same stream and on its 64 KiB-frame archive, against the single-pattern calls
 in the same process (find_query_legs' docstring).  One JSON line, also appended to profiles/find_query_bench.jsonl.
-  python tools/bench_seekable.py --split --find-query [--mib 1024]"""
+  python tools/bench_seekable.py --split --find-query [--mib 1024]
+--split --find-regex: find records by regular expression on the same stream, on a copy with records of a MiB and on the 64 KiB-frame
+archive, against the literal searches and against re on the host (find_regex_legs' docstring).  One JSON line, also appended to
+profiles/find_regex_bench.jsonl.
+  python tools/bench_seekable.py --split --find-regex [--mib 1024]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -704,8 +708,152 @@ def find_query_legs(a):
         f.write(line + "\n")
 
 
+def find_regex_legs(a):
+    """--split --find-regex: find records by regular expression (zsmi_findRecordsRegexDevice, zsmi_seekableFindRegexResident) on the
+    Zipf log stream, 1 GiB in device memory.  Legs in turn in one process, three rounds, every call followed by a synchronisation; the
+    sorted times of each leg.  Every answer is held against `re` on the host (finditer over the whole text with [^\\n] where the pattern
+    says `.`, an occurrence's record by the newlines in front of it), the one-byte literal against the single-pattern call.
+      literal:  `ERROR ienwbvuzw` and `e` as regular expressions against zsmi_findRecordsDevice on the same bytes
+      states:   ERROR.*[0-9]{3} and literals of 7, 15, 31 and 63 bytes (8 .. 64 states): the cost against the number of states
+      fold:     ignore-case on against off
+      invert:   ZSMI_REGEX_INVERT of the rare literal against the `none` query
+      long:     the same bytes with every newline but one a MiB turned into a space: long records, the carry's hard case
+      archive:  on the 64 KiB-frame archive, against zsmi_seekableFindRecordsResident and against today's way - the window read down
+                to the host and `re` run there
+      kernels:  the kernels' times one by one, of the rare literal"""
+    import re
+    from zstandard_amd import compile_regex
+    size, M, reps = (a.mib or 1024) << 20, a.frame, 3
+    gib = size / float(1 << 30)
+    bc = BatchCodec(0)
+    host = D.zipf_log(size)
+    src = torch.from_numpy(host).cuda()
+    words = torch.zeros(4, dtype=torch.int64, device="cuda")
+    bc.count_records_device(src.data_ptr(), size, words.data_ptr()); bc.sync()
+    records = int(words[0].item())
+    ms = lambda v: [round(t * 1e3, 4) for t in v]
+    mid = lambda v: float(np.median(v))
+    sync = lambda: (bc.sync(), torch.cuda.synchronize())
+    found = torch.zeros(records, dtype=torch.int64, device="cuda"); hits = torch.zeros(records, dtype=torch.uint8, device="cuda")
+    res = torch.zeros(4, dtype=torch.int64, device="cuda")
+    rare, common = b"ERROR ienwbvuzw", b"e"
+
+    def single(pat, text=None):
+        text = src if text is None else text
+        return lambda: bc.find_records_device(text.data_ptr(), size, pat, found.data_ptr(), records, res.data_ptr())
+
+    def regex(pattern, text=None, **kw):
+        prog = compile_regex(pattern, **kw)
+        text = src if text is None else text
+        return lambda: bc.find_records_regex_device(text.data_ptr(), size, prog, found.data_ptr(), records, res.data_ptr())
+
+    def answer(fn):
+        fn(); sync()
+        total, written, third, scanned = (int(v) for v in res.tolist())
+        assert written == total and scanned == size
+        return found[:total].clone(), third
+
+    def by_re(pattern, data, flags=0):
+        """the records `re` finds an occurrence in, ascending: the newlines in front of each occurrence's start"""
+        newlines = np.flatnonzero(data == 10)
+        starts = np.fromiter((m.start() for m in re.finditer(pattern, memoryview(data), flags)), dtype=np.int64)
+        return np.unique(np.searchsorted(newlines, starts, side="left"))
+
+    def same(got, want):
+        return got.numel() == len(want) and bool((got.cpu().numpy() == want).all())
+    rep = {"metric": "find_regex", "gib": gib, "records": records}
+    for name, pat in (("literal_rare", rare), ("literal_common", common)):
+        t = alternating({"regex": regex(re.escape(pat)), "single": single(pat)}, sync, reps)
+        got, want = answer(regex(re.escape(pat))), answer(single(pat))
+        assert got[1] == records and torch.equal(got[0], want[0]), "a literal as a regular expression and the single-pattern call differ"
+        if pat is rare:
+            assert same(got[0], by_re(re.escape(pat), host)), "the rare literal: not what re finds"
+        rep[name] = {"pattern": pat.decode(), "states": compile_regex(re.escape(pat)).nStates, "records_found": int(got[0].numel()), "regex_ms": ms(t["regex"]),
+                     "single_ms": ms(t["single"]), "regex_over_single": round(mid(t["regex"]) / mid(t["single"]), 3)}
+    base = mid(alternating({"regex": regex(re.escape(rare))}, sync, reps)["regex"])
+    curve = {}
+    line = max(bytes(host[:4096]).split(b"\n")[:20], key=len)
+    for name, pattern, on_host in [("ERROR.*[0-9]{3}", b"ERROR.*[0-9]{3}", b"ERROR[^\\n]*[0-9]{3}")] + \
+                                  [("literal_%d" % k, re.escape((line * 8)[:k]), re.escape((line * 8)[:k])) for k in (7, 15, 31, 63)]:
+        prog = compile_regex(pattern)
+        t = alternating({"regex": regex(pattern)}, sync, reps)
+        got = answer(regex(pattern))
+        assert same(got[0], by_re(on_host, host)), (name, "not what re finds")
+        curve[name] = {"states": prog.nStates, "classes": prog.nClasses, "records_found": int(got[0].numel()), "regex_ms": ms(t["regex"]),
+                       "over_rare_literal": round(mid(t["regex"]) / base, 3)}
+    rep["states"] = curve
+    t = alternating({"fold": regex(b"error ienwbvuzw", ignore_case=True), "plain": regex(b"ERROR ienwbvuzw")}, sync, reps)
+    got = answer(regex(b"error ienwbvuzw", ignore_case=True))
+    assert same(got[0], by_re(b"error ienwbvuzw", host, re.IGNORECASE)), "ignore-case: not what re finds"
+    rep["fold"] = {"records_found": int(got[0].numel()), "fold_ms": ms(t["fold"]), "plain_ms": ms(t["plain"]), "fold_over_plain": round(mid(t["fold"]) / mid(t["plain"]), 3)}
+    none = lambda: bc.find_records_query_device(src.data_ptr(), size, [rare], found.data_ptr(), 0, records, res.data_ptr(), mode="none")
+    t = alternating({"invert": regex(re.escape(rare), invert=True), "none": none}, sync, reps)
+    got, want = answer(regex(re.escape(rare), invert=True)), answer(none)
+    assert torch.equal(got[0], want[0]) and int(got[0].numel()) == records - len(by_re(re.escape(rare), host)), "invert is not the `none` query's answer"
+    rep["invert_rare"] = {"records_found": int(got[0].numel()), "invert_ms": ms(t["invert"]), "none_ms": ms(t["none"]), "invert_over_none": round(mid(t["invert"]) / mid(t["none"]), 3)}
+    # long records: every newline but the last of each MiB becomes a space
+    flat = host.copy()
+    newlines = np.flatnonzero(flat == 10)
+    keep = np.unique(np.searchsorted(newlines, np.arange(1 << 20, size + 1, 1 << 20), side="left") - 1)
+    flat[newlines] = 32; flat[newlines[keep[keep >= 0]]] = 10
+    long_text = torch.from_numpy(flat).cuda()
+    t = alternating({"long": regex(b"ERROR.*[0-9]{3}", long_text), "lines": regex(b"ERROR.*[0-9]{3}")}, sync, reps)
+    got = answer(regex(b"ERROR.*[0-9]{3}", long_text))
+    assert same(got[0], by_re(b"ERROR[^\\n]*[0-9]{3}", flat)), "long records: not what re finds"
+    rep["long_records"] = {"records": got[1], "records_found": int(got[0].numel()), "long_ms": ms(t["long"]), "lines_ms": ms(t["lines"]),
+                           "long_over_lines": round(mid(t["long"]) / mid(t["lines"]), 3)}
+    del long_text, flat
+    bc.enable_timing(True); regex(re.escape(rare))(); kt = bc.kernel_times(); bc.enable_timing(False)
+    rep["kernels_ms"] = {k: round(v[0] * 1e3, 4) for k, v in kt.items()}
+    # the archive
+    T = 65536
+    Mx = max(T, M)
+    mp = BatchCodec.split_pieces_bound(records, size, Mx)
+    fs = torch.zeros(mp, dtype=torch.int32, device="cuda"); fr = torch.zeros(mp + 1, dtype=torch.int64, device="cuda")
+    bc.split_records_device(src.data_ptr(), size, mp, fs.data_ptr(), fr.data_ptr(), words.data_ptr() + 8, target_size=T, max_frame_size=Mx); bc.sync()
+    n = int(words[1].item())
+    bound = bc.seekable_frames_resident_bound(size, n, True)
+    arc = torch.empty(bound, dtype=torch.uint8, device="cuda"); arc_size = torch.zeros(1, dtype=torch.int64, device="cuda")
+    bc.compress_seekable_frames_resident(src.data_ptr(), size, fs.data_ptr(), n, Mx, arc.data_ptr(), bound, arc_size.data_ptr(), level=a.level, checksum=True); bc.sync()
+    m = int(arc_size.item())
+    assert 0 < m <= bound, hex(m)
+    want = by_re(b"ERROR[^\\n]*[0-9]{3}", host)
+    del src
+    sk = bc.open_seekable_device(arc.data_ptr(), m)
+    work_cap = sk.find_work_bound(0, n)
+    assert work_cap == size
+    work = torch.empty(size, dtype=torch.uint8, device="cuda")
+    prog = compile_regex(b"ERROR.*[0-9]{3}")
+    rx = re.compile(b"ERROR[^\\n]*[0-9]{3}")
+    down = torch.empty(size, dtype=torch.uint8).pin_memory()
+    status = torch.ones(1, dtype=torch.int32, device="cuda")
+
+    def archive_regex():
+        sk.find_regex_resident(fr.data_ptr(), n, prog, 0, n, work.data_ptr(), work_cap, found.data_ptr(), records, res.data_ptr())
+
+    def archive_single():
+        sk.find_records_resident(fr.data_ptr(), n, b"ERROR", 0, n, work.data_ptr(), work_cap, found.data_ptr(), records, res.data_ptr())
+
+    def today():                                                                  # range read, copy down, re in Python
+        sk.read_ranges_device([0], [size], work.data_ptr(), [0], status.data_ptr())
+        down.copy_(work); torch.cuda.synchronize()
+        return sum(1 for _ in rx.finditer(memoryview(down.numpy())))
+    t = alternating({"regex": archive_regex, "single": archive_single, "today": today}, sync, reps)
+    got = answer(archive_regex)
+    assert same(got[0], want), "the archive: not what re finds on the text"
+    rep["archive"] = {"target": T, "frames": n, "regex_ms": ms(t["regex"]), "single_ms": ms(t["single"]), "today_ms": ms(t["today"]),
+                      "regex_over_single": round(mid(t["regex"]) / mid(t["single"]), 3), "regex_over_today": round(mid(t["regex"]) / mid(t["today"]), 4)}
+    bc.sync(); sk.close(); bc.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    line = json.dumps(rep)
+    print(line, flush=True)
+    with open(a.out or os.path.join(ROOT, "profiles", "find_regex_bench.jsonl"), "a") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--find-regex", action="store_true", help="with --split: find records by regular expression against the literal searches and re on the host (find_regex_legs' docstring)")
     ap.add_argument("--find-query", action="store_true", help="with --split: find records by several patterns against the single-pattern calls (find_query_legs' docstring)")
     ap.add_argument("--find", nargs="+", default=None, help="with --split: find records by content, a leg set a pattern (a rare one and one most lines hold)")
     ap.add_argument("--find-targets", type=int, nargs="+", default=[4096, 65536], help="with --split --find: the archives' targetSizes")
@@ -735,6 +883,8 @@ def main():
     if a.split:
         if a.find_query:
             return find_query_legs(a)
+        if a.find_regex:
+            return find_regex_legs(a)
         return find_legs(a) if a.find else (lines_legs(a) if a.lines else split_legs(a))
     if a.records:
         return records(a)

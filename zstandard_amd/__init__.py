@@ -3,4 +3,4 @@ mirror of the reference's public API (api.py)."""
 from .api import ZStdDecompress, ZstdDecompressor, ZstdCompressor, SeekableArchive, SeekableHandle, BatchCodec, CompressionDict, CompressionDictSet, NO_DICT, DecompressionDict, DecompressionDictSet, train_dictionary, finalize_dictionary, get_dict_id   # noqa: F401
 from .api import frame_content_size, find_frame_compressed_size, find_decompressed_size, decompress_bound, CONTENTSIZE_UNKNOWN, CONTENTSIZE_ERROR   # noqa: F401
 from .api import count_frames, build_seek_table   # noqa: F401
-from .api import split_records, find_records, find_records_query   # noqa: F401
+from .api import split_records, find_records, find_records_query, compile_regex, find_records_regex   # noqa: F401

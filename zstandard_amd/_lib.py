@@ -75,6 +75,13 @@ class FindQuery(ctypes.Structure):
                 ("patternSizes", ctypes.c_uint32 * 8)]
 
 
+class RegexProgram(ctypes.Structure):
+    """zsmi_regexProgram: the minimal DFA of a pattern (zsmi_compileRegex) - next[s * nClasses + classOf[b]], a start state, the accepting
+    states as a 64-bit word, flags (1: compiled ignoring ASCII case, 2: list the records that do NOT match)"""
+    _fields_ = [("nStates", ctypes.c_uint32), ("nClasses", ctypes.c_uint32), ("start", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("accept", ctypes.c_uint64), ("classOf", ctypes.c_uint8 * 256), ("next", ctypes.c_uint8 * 3072)]
+
+
 class KernelTime(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("seconds", ctypes.c_double), ("launches", ctypes.c_uint32)]
 
@@ -213,6 +220,13 @@ def lib():
     L.zsmi_seekableFindQueryResident.restype = i32
     L.zsmi_seekableFindQueryResident.argtypes = [vp, vp, vp, u32, i32, pq, u32, u32, vp, u64, vp, vp, u64, vp]
     L.zsmi_seekableFindQueryHost.restype = i32; L.zsmi_seekableFindQueryHost.argtypes = [vp, vp, vp, u32, i32, pq, u32, u32, vp, vp, sz, vp]
+    pr = ctypes.POINTER(RegexProgram)
+    L.zsmi_compileRegex.restype = i32; L.zsmi_compileRegex.argtypes = [vp, sz, u32, pr, ctypes.POINTER(sz)]
+    L.zsmi_findRecordsRegex.restype = sz; L.zsmi_findRecordsRegex.argtypes = [vp, sz, i32, pr, u64, vp, sz, pu64]
+    L.zsmi_findRecordsRegexDevice.restype = i32; L.zsmi_findRecordsRegexDevice.argtypes = [vp, vp, u64, i32, pr, vp, vp, u64, vp]
+    L.zsmi_seekableFindRegexResident.restype = i32
+    L.zsmi_seekableFindRegexResident.argtypes = [vp, vp, vp, u32, i32, pr, u32, u32, vp, u64, vp, u64, vp]
+    L.zsmi_seekableFindRegexHost.restype = i32; L.zsmi_seekableFindRegexHost.argtypes = [vp, vp, vp, u32, i32, pr, u32, u32, vp, sz, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -303,6 +317,7 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_seekableRecordsWorkBound", "zsmi_seekableReadRecordsResident", "zsmi_seekableReadRecordsHost",
            "zsmi_findRecords", "zsmi_findRecordsDevice", "zsmi_seekableFindWorkBound", "zsmi_seekableFindRecordsResident", "zsmi_seekableFindRecordsHost",
            "zsmi_findRecordsQuery", "zsmi_findRecordsQueryDevice", "zsmi_seekableFindQueryResident", "zsmi_seekableFindQueryHost",
+           "zsmi_compileRegex", "zsmi_findRecordsRegex", "zsmi_findRecordsRegexDevice", "zsmi_seekableFindRegexResident", "zsmi_seekableFindRegexHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

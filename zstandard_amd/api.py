@@ -189,6 +189,40 @@ def find_records_query(data, patterns, mode="any", ignore_case=False, delimiter=
     return (records, [int(v) for v in hits[:total]]) if return_hits else records
 
 
+def compile_regex(pattern, ignore_case=False, invert=False):
+    """a regular expression (bytes: literals, escapes, \\d \\w \\s, `.`, classes, groups, |, * + ?, {m,n}, ^ first and $ last in a
+    top-level alternative) compiled into the program the regular-expression searches take - the minimal DFA, at most 64 states
+    (zsmi_compileRegex, host only): a _lib.RegexProgram.  ignore_case folds ASCII letters only; invert lists the records that do NOT
+    match.  A pattern the compiler refuses raises ValueError with the error's name and the offset at which it was decided."""
+    L = _lib.lib()
+    pat = bytes(pattern)
+    prog = _lib.RegexProgram()
+    at = ctypes.c_size_t(0)
+    rc = L.zsmi_compileRegex(pat, len(pat), (1 if ignore_case else 0) | (2 if invert else 0), ctypes.byref(prog), ctypes.byref(at))
+    if rc:
+        raise ValueError(f"zsmi_compileRegex: {_error_name(L, rc)} at offset {at.value}")
+    return prog
+
+
+def _regex(regex):
+    """a compiled program as it is, bytes compiled on the spot"""
+    return regex if isinstance(regex, _lib.RegexProgram) else compile_regex(regex)
+
+
+def find_records_regex(data, regex, delimiter=b"\n", base=0):
+    """the records of delimited text that `regex` matches - a compile_regex program, or bytes that are compiled on the spot - as
+    re.compile(pattern, re.DOTALL).search on each record without its delimiter would (zsmi_findRecordsRegex, host only): the list of
+    their numbers, ascending; an inverted program lists the others, empty records included."""
+    L = _lib.lib()
+    s, n = _buf(data)
+    d = _delimiter(delimiter)
+    prog = _regex(regex)
+    total = _raise_if_error(L, L.zsmi_findRecordsRegex(s, n, d, ctypes.byref(prog), base, None, 0, None))
+    out = np.zeros(max(total, 1), dtype=np.uint64)
+    _raise_if_error(L, L.zsmi_findRecordsRegex(s, n, d, ctypes.byref(prog), base, ctypes.c_void_p(out.ctypes.data), total, None))
+    return [int(v) for v in out[:total]]
+
+
 class ZStdDecompress:
     """EPAM.Deltix.ZStd.ZStdDecompress (static). Sizes are 32-bit in the reference (size_t = UInt32, ZStdDecompress.cs:14)."""
 
@@ -590,6 +624,31 @@ class SeekableArchive:
         records = [int(v) for v in out[:n]]
         return (records, [int(v) for v in hits[:n]]) if return_hits else records
 
+    def find_records_regex(self, first_record, regex, delimiter=b"\n", first_frame=0, frame_count=None):
+        """find_records for a regular expression: the records of the window that `regex` (a compile_regex program, or bytes compiled on
+        the spot) matches, after ONE decode of the window (find_records_regex states the rule; the window as in find_records - a record
+        its border cuts is judged on the part inside).  The list of their numbers, ascending.  zsmi_seekableFindRegexHost"""
+        self._open()
+        first = np.ascontiguousarray(first_record, dtype=np.uint64)
+        prog = _regex(regex)
+        d = _delimiter(delimiter)
+        count = self.num_frames - first_frame if frame_count is None else frame_count
+        p = BatchCodec._p
+        result = np.zeros(4, dtype=np.uint64)
+        out = np.zeros(1, dtype=np.uint64)
+        for cap in (0, None):
+            cap = int(result[0]) if cap is None else cap
+            out = np.zeros(max(cap, 1), dtype=np.uint64)
+            rc = self.L.zsmi_seekableFindRegexHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(prog), first_frame, count,
+                                                   p(out) if cap else None, cap, p(result))
+            if rc:
+                raise RuntimeError(_error_name(self.L, rc))
+            if int(result[0]) > (1 << 64) - ERROR_MAX_CODE:
+                raise RuntimeError(_error_name(self.L, (1 << 64) - int(result[0])))
+            if int(result[0]) == 0:
+                return []
+        return [int(v) for v in out[:int(result[1])]]
+
     def read_many(self, ranges, return_codes=False):
         """ranges: (offset, length) pairs -> the list of their bytes (each clipped at the content's end), one call for all of them
         (zsmi_seekableReadRangesHost).  A failing range raises RuntimeError with the error's name and the range's index; with
@@ -820,6 +879,20 @@ class SeekableHandle:
                                                    frame_count, p(d_work_ptr), work_capacity, p(d_records_ptr), p(d_hits_ptr), capacity, p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_seekableFindQueryResident: {_error_name(self.L, rc)}")
+
+    def find_regex_resident(self, d_first_record_ptr, n_frames, regex, first_frame, frame_count, d_work_ptr, work_capacity, d_records_ptr, capacity,
+                            d_result_ptr, delimiter=b"\n", codec=None):
+        """find_records_resident for a regular expression (a compile_regex program, or bytes compiled on the spot; HOST memory): one
+        decode of the window into d_work, then d_records (uint64[capacity]) receives the numbers of the records the program lists and
+        d_result (uint64[4]) the total or (uint64)-code, the numbers written, the RECORDS of the window and the bytes searched.  Nothing
+        goes to the host.  zsmi_seekableFindRegexResident"""
+        codec = codec or self.codec
+        p = ctypes.c_void_p
+        prog = _regex(regex)
+        rc = self.L.zsmi_seekableFindRegexResident(codec.ctx, self.handle, p(d_first_record_ptr), n_frames, _delimiter(delimiter), ctypes.byref(prog), first_frame,
+                                                   frame_count, p(d_work_ptr), work_capacity, p(d_records_ptr), capacity, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableFindRegexResident: {_error_name(self.L, rc)}")
 
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`, from the handle's table"""
@@ -1172,6 +1245,18 @@ class BatchCodec:
                                                 p(d_hits_ptr), capacity, p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_findRecordsQueryDevice: {_error_name(self.L, rc)}")
+
+    def find_records_regex_device(self, d_src_ptr, src_size, regex, d_records_ptr, capacity, d_result_ptr, delimiter=b"\n", d_base_ptr=0):
+        """find_records_regex on the device, the text in device memory (asynchronous: only queued): d_records (uint64[capacity]; 0 with
+        capacity 0: only count) receives the ascending numbers of the records of d_src[0, src_size) that the program lists, d_result
+        (uint64[4]) the total, the numbers written, the RECORDS of the text and the bytes searched.  regex: a compile_regex program, or
+        bytes compiled on the spot (HOST memory: it reaches the kernels by value).  zsmi_findRecordsRegexDevice"""
+        prog = _regex(regex)
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_findRecordsRegexDevice(self.ctx, p(d_src_ptr), src_size, _delimiter(delimiter), ctypes.byref(prog), p(d_base_ptr), p(d_records_ptr),
+                                                capacity, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_findRecordsRegexDevice: {_error_name(self.L, rc)}")
 
     def open_seekable_device(self, d_ptr, size, ddict=None, ddict_set=None):
         """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The

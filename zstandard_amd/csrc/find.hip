@@ -369,14 +369,16 @@ static int findCheck(const zsmi_ctx *c, const zsmi_seekable *sk, const void *fir
 // bound, frameCount > 0, arguments checked by the caller): the scratch of the whole call reserved, then the window's frames into dWork, end
 // to end, verified, and the first failing frame's code in a device word.  Leaves the text's size, its tiles and that word
 struct FindDecoded { uint64_t bytes; FindTiles t; const uint32_t *dCode; };
+// device words, a frame of the window, in front of the tiles' (findDecode lays them out; a caller that reserves more scratch behind the
+// tiles' words sizes it with this): 64 bits - sizes [F], places in dWork [F + 1]; verify records [F]; 32 bits - the list, decoder status,
+// refusals, written, codes [F each], the window's code [1, padded to 8 bytes]
+static size_t findDecodeHead(size_t F) { return (2 * F + 1) * sizeof(uint64_t) + F * sizeof(ZsSeekItem) + ((5 * F + 1) * sizeof(uint32_t) + 7) / 8 * 8; }
 static int findDecode(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount, void *dWork, FindDecoded &w)
 {
     const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
     const size_t F = frameCount;
     FindTiles &t = w.t;
-    // device words, a frame of the window: 64 bits - sizes [F], places in dWork [F + 1]; verify records [F]; 32 bits - the list, decoder
-    // status, refusals, written, codes [F each], the window's code [1, padded to 8 bytes]
-    const size_t head = (2 * F + 1) * sizeof(uint64_t) + F * sizeof(ZsSeekItem) + ((5 * F + 1) * sizeof(uint32_t) + 7) / 8 * 8;
+    const size_t head = findDecodeHead(F);
     if (const int e = findReserve(c, bytes, head, F, t)) return e;
     if (!c->dItems.reserve(sizeof(ZsDecItem) * F)) return ZSMI_error_memory_allocation;
     uint64_t *dSizes = (uint64_t *)c->seek.dMeta.p, *dListAt = dSizes + F;

@@ -22,6 +22,7 @@
 #include "records.hip"            // feature: records by number from a record archive - firstRecord and record numbers -> the records' bytes (kernels and host; the rules: zsmi_records.h)
 #include "find.hip"               // feature: find records by content - text or a window of a record archive and a literal pattern -> ascending record numbers (kernels and host; the rule: zsmi_find.h)
 #include "findquery.hip"          // feature: find records by several patterns - any, all, none of up to 8 patterns, ASCII case folding -> ascending record numbers and hit sets (kernels and host; the rule: zsmi_findquery.h)
+#include "findregex.hip"          // feature: find records by regular expression - a pattern compiled on the host into a minimal DFA, a state function carried across lanes, wavefronts and tiles -> ascending record numbers (kernels and host; the rule and the compiler: zsmi_regex.h)
 
 #include <cstdio>
 #include <cstdlib>

@@ -14,8 +14,8 @@
 // of them starts where a record starts.  Windows cut at such frames cut no record, hence no occurrence: together they find exactly what
 // one window over all of them finds.  A window cut anywhere else may lose the occurrences across its border, and the record it begins
 // inside is numbered as the one its first frame's entry names.
-// NOT COVERED: anchors, regular expressions, and patterns that hold the delimiter.  (Several patterns a call and ignoring case:
-// zsmi_findquery.h.)
+// NOT COVERED: patterns that hold the delimiter.  (Several patterns a call and ignoring case: zsmi_findquery.h; anchors and regular
+// expressions: zsmi_regex.h.)
 // Host and device; a host program may include this header alone, with any C++ compiler (tests/c/find_records.cpp does, under the
 // sanitizers).
 #pragma once

@@ -20,8 +20,8 @@
 // intersection of the K single-pattern answers (folded), `none` the complement of `any` within the text's records.
 // zs_findq_records is the serial statement, and zsmi_findRecordsQuery runs it as written here; the kernels of findquery.hip reach the same
 // answer a workgroup a 16 KiB tile.  On an archive the window, B and the record-beginning frames are those of zsmi_find.h.
-// NOT COVERED: anchors, regular expressions, patterns that hold the delimiter, Unicode case folding, more than 8 patterns, and occurrence
-// counts a pattern.
+// NOT COVERED: patterns that hold the delimiter, Unicode case folding, more than 8 patterns, and occurrence counts a pattern.  (Anchors
+// and regular expressions: zsmi_regex.h.)
 // Host and device; a host program may include this header alone, with any C++ compiler (tests/c/find_query.cpp does, under the
 // sanitizers).
 #pragma once
