@@ -809,6 +809,82 @@ int zsmi_seekableFindRegexResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const
 int zsmi_seekableFindRegexHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
                                const zsmi_regexProgram *prog, uint32_t firstFrame, uint32_t frameCount,
                                uint64_t *records, size_t capacity, uint64_t *result);
+/* The record index: firstRecord as part of the archive.  Every record call above takes firstRecord; these calls rebuild it from content and
+ * frame borders, store it in the archive as a skippable frame, and load it from there - so that an archive written by one process, or by
+ * another tool, can be read and searched by record.  The rule (zstandard_amd/csrc/zsmi_recindex.h states it in code): with content of
+ * `size` bytes and frames at content offsets dOff[0 .. N], P(x) = the delimiters in content[0, x), + 1 when x == size, size > 0 and the
+ * last byte is no delimiter; firstRecord[i] = P(dOff[i]).  For the splitter's frames that is its firstRecord; an empty frame at the
+ * content's end gets `records`.  A frame is MISALIGNED when it holds a delimiter, its last byte is none and it does not end at `size`: the
+ * lookup of the record calls is valid for an archive exactly when no frame is misaligned (fixed-size frames over text have many).
+ * The index frame stands between the last content frame and the seek table and is the table's last entry {40 + 4 n, 0 [, 0x51D8E999]}:
+ * every reader sees n + 1 frames whose last is empty.  Little-endian: u32 0x184D2A5D | u32 Frame_Size = 32 + 4 n | u32 0x58444952 | u8
+ * version 1, u8 delim, u16 0 | u32 n | u32 0 | u64 records | u64 check | n x u32 count[i] = firstRecord[i + 1] - firstRecord[i];
+ * check = sum of (count[i] + 1) (2 i + 1) 0x9E3779B185EBCA87, + records 0xC2B2AE3D27D4EB4F + delim, mod 2^64.
+ * Host only, no device:
+ * zsmi_recordIndexFrameSize: 40 + 4 n; n >= 0x8000000: frameIndex_tooLarge.
+ * zsmi_writeRecordIndexFrame: firstRecord[0 .. n] -> the frame; its size or a code, in this order: delim outside 0..255:
+ * parameter_outOfBound; n >= 0x8000000: frameIndex_tooLarge; a NULL dst or firstRecord: GENERIC; firstRecord[0] != 0, a descent or a
+ * count above 32 bits: corruption_detected; dstCapacity below the size: dstSize_tooSmall.  Nothing is written on failure.
+ * zsmi_readRecordIndexFrame: returns n with firstRecord[0 .. n] (firstRecord[n] = records; NULL: the frame is only judged) and *delim
+ * (may be NULL), or a code, in this order: fewer than 40 bytes: srcSize_wrong; either magic: prefix_unknown; the version:
+ * version_unsupported; reserved fields, Frame_Size against n: corruption_detected; fewer bytes than n asks for: srcSize_wrong; capacity
+ * below n + 1: dstSize_tooSmall; the check, or counts that do not sum to records: corruption_detected.  Reads only src[0, 40 + 4 n).
+ * zsmi_indexRecords: the rule over plain text, serially - the statement the device calls are held against.  Frame i holds
+ * frameSizes[i] bytes.  firstRecord[0 .. n]; result (may be NULL) = {0, records, misaligned frames, delimiters}.  0 or a code: delim:
+ * parameter_outOfBound; a NULL frameSizes with n > 0 or a NULL firstRecord: GENERIC; a NULL src with bytes, sizes that do not sum to
+ * srcSize: srcSize_wrong.
+ * zsmi_seekableAttachRecordIndex: a host archive in place - the table moves back, the index frame takes its place, its entry is added.
+ * Returns the new size (archiveSize + 40 + 4 n + one entry) or a code, in this order: the table's own rejections (as the readers');
+ * delim outside 0..255 or n not the table's frame count: parameter_outOfBound; a NULL firstRecord: GENERIC; firstRecord[0] != 0, a
+ * descent or a count above its entry's Decompressed_Size: corruption_detected; an archive that already ends in an index frame:
+ * parameter_unsupported; n + 1 > 0x8000000: frameIndex_tooLarge; capacity below the new size: dstSize_tooSmall.  A refused archive is
+ * untouched.  Writes only inside [archive + the table's old place, archive + the new size).
+ * Device, only queued - no copy to the host, no wait, no pinned staging; all scratch is the context's, reserved before anything is queued:
+ * zsmi_indexRecordsDevice: the body of the rebuild over text in device memory.  dPlaces: uint64[n + 1], ascending, 0 first, `size` last
+ * (the frames' borders in the text); atEnd: `size` is the content's end (the tail record counts, and a frame that ends there is not
+ * misaligned).  Writes dFirstRecord[j] = *dBase + P(dPlaces[j]) for j = 1 .. n, and for j = 0 when dBase is NULL (base 0): windows of one
+ * content taken in ascending order chain through the array with dBase = their entry 0.  dResult = {status, records in the text,
+ * misaligned frames, delimiters}; status: parameter_outOfBound when dPlaces[0] != 0 or dPlaces[n] != size.  Places that do not ascend
+ * leave their entries unspecified; nothing outside dFirstRecord[0 .. n] and dResult[0 .. 3] is written, nothing outside the text read.
+ * Checked on the host, in this order: a NULL ctx: init_missing; a NULL dResult, dPlaces or dFirstRecord: GENERIC; delim outside 0..255:
+ * parameter_outOfBound; n > 0x8000000: frameIndex_tooLarge; size > 0 behind a NULL dText: srcSize_wrong.
+ * zsmi_seekableIndexRecordsResident: the rebuild on a window of an opened archive: its frames decoded end to end into dWork
+ * (zsmi_seekableFindWorkBound sizes it), the body over the decoded places with dBase = dFirstRecord + firstFrame; the window at 0 writes
+ * entry 0.  dFirstRecord holds the handle's frame count + 1 entries; the window writes [firstFrame (+ 1), firstFrame + frameCount].
+ * dResult[0]: the window's first failing frame's code, as the find calls report it - when it is not 0 the window's entries and the other
+ * three words are NOT to be trusted (they are written all the same).  frameCount == 0: dResult = {0, 0, 0, 0}.  Checked on the host, in
+ * the find calls' order less the pattern: a NULL ctx: init_missing; a NULL sk, dResult or dFirstRecord: GENERIC; a handle of another
+ * device: parameter_unsupported; delim outside 0..255, firstFrame + frameCount above the handle's frame count: parameter_outOfBound; a NULL
+ * dWork with a window that holds bytes: GENERIC; workCapacity below the work bound: dstSize_tooSmall.
+ * zsmi_seekableLoadRecordIndexResident: the handle's last entry, read from the handle's frames on the device and judged as
+ * zsmi_readRecordIndexFrame judges it, every count held against the handle's table besides (a count above its entry's
+ * Decompressed_Size: corruption_detected).  dResult = {status, records, delim, n}.  Status 0: dFirstRecord[0 .. N], N = n + 1 =
+ * zsmi_getNumFrames_fromSeekable(sk), is the array the record calls take with nFrames = N; its last two entries are `records`.  A handle
+ * with no frames, or whose last entry is no such frame: status prefix_unknown; with any status but 0 the array is untouched.  Checked on
+ * the host: a NULL ctx: init_missing; a NULL sk, dFirstRecord or dResult: GENERIC; a handle of another device: parameter_unsupported.
+ * zsmi_seekableAttachRecordIndexResident: zsmi_seekableAttachRecordIndex on an archive in device memory whose size is a device word -
+ * the one zsmi_compressSeekableFramesResident left: it goes in as the archive's size and comes out as the new size or (uint64_t)-code; an
+ * error word that comes in stays as it is and nothing is touched.  The host knows only n: the device reads the table's footer and
+ * refuses, in the word and in the host form's order, what the host form refuses (a size above capacity: prefix_unknown).  The result is
+ * byte for byte the host form's.  Checked on the host: a NULL ctx: init_missing; a NULL dArchive, dArchiveSize or dFirstRecord: GENERIC;
+ * delim outside 0..255: parameter_outOfBound; n > 0x8000000: frameIndex_tooLarge.
+ * Host arrays - the resident bodies with context staging, one wait: zsmi_seekableLoadRecordIndexHost (firstRecord[N + 1], written only
+ * with status 0; result[4] as dResult) and zsmi_seekableIndexRecordsHost (the whole archive in windows of at most 256 MiB of content, cut
+ * wherever the table allows; firstRecord[N + 1]; result = {the first failing frame's code, records, misaligned frames, delimiters}). */
+size_t zsmi_recordIndexFrameSize(size_t n);
+size_t zsmi_writeRecordIndexFrame(void *dst, size_t dstCapacity, const uint64_t *firstRecord, size_t n, int delim);
+size_t zsmi_readRecordIndexFrame(const void *src, size_t srcSize, uint64_t *firstRecord, size_t capacity, int *delim);
+int zsmi_indexRecords(const void *src, size_t srcSize, const uint32_t *frameSizes, size_t n, int delim, uint64_t *firstRecord, uint64_t *result);
+size_t zsmi_seekableAttachRecordIndex(void *archive, size_t archiveSize, size_t capacity, const uint64_t *firstRecord, size_t n, int delim);
+int zsmi_indexRecordsDevice(zsmi_ctx *ctx, const void *dText, uint64_t size, const uint64_t *dPlaces, uint32_t n, int delim, int atEnd,
+                            const uint64_t *dBase, uint64_t *dFirstRecord, uint64_t *dResult);
+int zsmi_seekableIndexRecordsResident(zsmi_ctx *ctx, const zsmi_seekable *sk, int delim, uint32_t firstFrame, uint32_t frameCount,
+                                      void *dWork, uint64_t workCapacity, uint64_t *dFirstRecord, uint64_t *dResult);
+int zsmi_seekableLoadRecordIndexResident(zsmi_ctx *ctx, const zsmi_seekable *sk, uint64_t *dFirstRecord, uint64_t *dResult);
+int zsmi_seekableAttachRecordIndexResident(zsmi_ctx *ctx, void *dArchive, uint64_t capacity, uint64_t *dArchiveSize,
+                                           const uint64_t *dFirstRecord, uint32_t n, int delim);
+int zsmi_seekableLoadRecordIndexHost(zsmi_ctx *ctx, const zsmi_seekable *sk, uint64_t *firstRecord, uint64_t *result);
+int zsmi_seekableIndexRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, int delim, uint64_t *firstRecord, uint64_t *result);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

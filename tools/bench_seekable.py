@@ -50,7 +50,11 @@ in the same process (find_query_legs' docstring).  One JSON line, also appended 
 --split --find-regex: find records by regular expression on the same stream, on a copy with records of a MiB and on the 64 KiB-frame
 archive, against the literal searches and against re on the host (find_regex_legs' docstring).  One JSON line, also appended to
 profiles/find_regex_bench.jsonl.
-  python tools/bench_seekable.py --split --find-regex [--mib 1024]"""
+  python tools/bench_seekable.py --split --find-regex [--mib 1024]
+--split --record-index: the record index on the same stream's archives at targetSize 65536, 4096 and 0 - attach against the resident compress
+call it follows, load against zsmi_openSeekableDevice, rebuild against the whole-content range read, the body's kernels against the
+splitter's (record_index_legs' docstring).  One JSON line, also appended to profiles/record_index_bench.jsonl.
+  python tools/bench_seekable.py --split --record-index [--mib 1024]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -851,8 +855,93 @@ def find_regex_legs(a):
         f.write(line + "\n")
 
 
+def record_index_legs(a):
+    """--split --record-index: the record index on the Zipf log stream (text lines, ~150 bytes each) in device memory, for archives of
+    targetSize 65536, 4096 and 0 (a frame a record), three rounds of alternating legs each, all in one process:
+      attach    zsmi_compressSeekableFramesResident alone against the same call followed by zsmi_seekableAttachRecordIndexResident;
+      load      zsmi_seekableLoadRecordIndexResident against zsmi_openSeekableDevice (open + close) on the same archive;
+      rebuild   zsmi_seekableIndexRecordsResident over the whole archive against the whole-content range read of the same handle - the
+                decode it cannot avoid;
+      kernels   k_recidx_tiles and k_recidx_places (zsmi_indexRecordsDevice on the text and the frames' borders, HIP events, three
+                calls: the sorted times) beside k_split_count and k_split_emit on the same buffer.
+    The loaded and the rebuilt arrays are held against the splitter's.  One JSON line, also appended to profiles/record_index_bench.jsonl."""
+    size, M, reps = (a.mib or 1024) << 20, a.frame, 3
+    gib = size / float(1 << 30)
+    bc = BatchCodec(0)
+    src = torch.from_numpy(D.zipf_log(size)).cuda()
+    words = torch.zeros(8, dtype=torch.int64, device="cuda")
+    bc.count_records_device(src.data_ptr(), size, words.data_ptr()); bc.sync()
+    records = int(words[0].item())
+    mp = BatchCodec.split_pieces_bound(records, size, M)
+    fs = torch.zeros(mp, dtype=torch.int32, device="cuda"); fr = torch.zeros(mp + 1, dtype=torch.int64, device="cuda")
+    work = torch.empty(size, dtype=torch.uint8, device="cuda"); dst = torch.empty(size, dtype=torch.uint8, device="cuda")
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ms = lambda v: [round(t * 1e3, 4) for t in v]
+    med = lambda v: float(np.median(v))
+
+    def kernels(fn, names):
+        runs = []
+        for _ in range(reps):
+            bc.enable_timing(True); fn(); runs.append(bc.kernel_times()); bc.enable_timing(False)
+        return {k: sorted(round(r[k][0] * 1e3, 4) for r in runs) for k in names}
+    rep = {"metric": "record_index", "gib": gib, "max_frame_size": M, "records": records, "library": bc.L.zsmi_versionString().decode()}
+    for T in (65536, 4096, 0):
+        split = lambda: bc.split_records_device(src.data_ptr(), size, mp, fs.data_ptr(), fr.data_ptr(), words.data_ptr() + 8, target_size=T, max_frame_size=M)
+        split(); bc.sync()
+        n = int(words[1].item())
+        room = bc.seekable_frames_resident_bound(size, n, True) + 40 + 4 * n + 12
+        arc = torch.empty(room, dtype=torch.uint8, device="cuda"); arc_size = words.data_ptr() + 32
+        compress = lambda: bc.compress_seekable_frames_resident(src.data_ptr(), size, fs.data_ptr(), n, M, arc.data_ptr(), room, arc_size, a.level, True)
+
+        def compress_attach():
+            compress(); bc.attach_record_index_resident(arc.data_ptr(), room, arc_size, fr.data_ptr(), n)
+        t = alternating({"compress": compress, "compress_attach": compress_attach}, bc.sync, reps)
+        asize = int(words[4].item())
+        assert asize < (1 << 63), "a frame failed, or the attach was refused: %#x" % (asize & ((1 << 64) - 1))
+        N = n + 1
+        loaded = torch.zeros(N + 1, dtype=torch.int64, device="cuda"); rebuilt = torch.zeros(N + 1, dtype=torch.int64, device="cuda")
+        res = torch.zeros(8, dtype=torch.int64, device="cuda")
+        h = bc.open_seekable_device(arc.data_ptr(), asize)
+        assert h.num_frames == N and h.content_size == size
+
+        def open_close():
+            bc.open_seekable_device(arc.data_ptr(), asize).close()
+        load = lambda: h.load_record_index_resident(loaded.data_ptr(), res.data_ptr())
+        rebuild = lambda: h.index_records_resident(0, N, work.data_ptr(), size, rebuilt.data_ptr(), res.data_ptr() + 32)
+        read = lambda: h.read_ranges_device([0], [size], dst.data_ptr(), [0], status.data_ptr())
+        t.update(alternating({"open": open_close, "load": load}, bc.sync, reps))
+        t.update(alternating({"range_read": read, "rebuild": rebuild}, bc.sync, reps))
+        got = res.tolist()
+        assert got[0] == 0 and got[1] == records and got[3] == n, ("load", got[:4])
+        assert got[4] == 0 and got[5] == records and got[6] == 0, ("rebuild", got[4:])
+        want = torch.cat([fr[:n + 1], fr[n:n + 1]])
+        assert bool((loaded == want).all()) and bool((rebuilt == want).all()) and int(status.item()) == 0 and bool((dst == src).all())
+        places = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(fs[:n].to(torch.int64), 0)])
+        text = lambda: bc.index_records_device(src.data_ptr(), size, places.data_ptr(), n, rebuilt.data_ptr(), res.data_ptr() + 32)
+        kt = kernels(text, ("k_recidx_tiles", "k_recidx_places"))
+        kt.update(kernels(split, ("k_split_count", "k_split_emit")))
+        bc.sync()
+        assert bool((rebuilt[:n + 1] == fr[:n + 1]).all())
+        row = {"frames": n, "archive_bytes": asize, "index_frame_bytes": 40 + 4 * n, "ms": {k: ms(v) for k, v in t.items()}, "kernels_ms": kt,
+               "attach_ms": round((med(t["compress_attach"]) - med(t["compress"])) * 1e3, 4),
+               "attach_over_compress": round((med(t["compress_attach"]) - med(t["compress"])) / med(t["compress"]), 4),
+               "load_over_open": round(med(t["load"]) / med(t["open"]), 3), "rebuild_over_range_read": round(med(t["rebuild"]) / med(t["range_read"]), 3),
+               "rebuild_gibs": round(gib / med(t["rebuild"]), 1), "range_read_gibs": round(gib / med(t["range_read"]), 1),
+               "k_recidx_tiles_over_k_split_count": round(kt["k_recidx_tiles"][1] / kt["k_split_count"][1], 3),
+               "k_recidx_places_over_k_split_emit": round(kt["k_recidx_places"][1] / kt["k_split_emit"][1], 3)}
+        rep["target_%d" % T] = row
+        bc.sync(); h.close()
+        del arc, loaded, rebuilt
+    bc.close()
+    line = json.dumps(rep)
+    print(line, flush=True)
+    with open(a.out or os.path.join(ROOT, "profiles", "record_index_bench.jsonl"), "a") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--record-index", action="store_true", help="with --split: the record index - attach, load and rebuild against the calls they follow or replace (record_index_legs' docstring)")
     ap.add_argument("--find-regex", action="store_true", help="with --split: find records by regular expression against the literal searches and re on the host (find_regex_legs' docstring)")
     ap.add_argument("--find-query", action="store_true", help="with --split: find records by several patterns against the single-pattern calls (find_query_legs' docstring)")
     ap.add_argument("--find", nargs="+", default=None, help="with --split: find records by content, a leg set a pattern (a rare one and one most lines hold)")
@@ -881,6 +970,8 @@ def main():
     if a.index:
         return index_legs(a)
     if a.split:
+        if a.record_index:
+            return record_index_legs(a)
         if a.find_query:
             return find_query_legs(a)
         if a.find_regex:

@@ -4,3 +4,4 @@ from .api import ZStdDecompress, ZstdDecompressor, ZstdCompressor, SeekableArchi
 from .api import frame_content_size, find_frame_compressed_size, find_decompressed_size, decompress_bound, CONTENTSIZE_UNKNOWN, CONTENTSIZE_ERROR   # noqa: F401
 from .api import count_frames, build_seek_table   # noqa: F401
 from .api import split_records, find_records, find_records_query, compile_regex, find_records_regex   # noqa: F401
+from .api import index_records, write_record_index_frame, read_record_index_frame, attach_record_index   # noqa: F401

@@ -227,6 +227,17 @@ def lib():
     L.zsmi_seekableFindRegexResident.restype = i32
     L.zsmi_seekableFindRegexResident.argtypes = [vp, vp, vp, u32, i32, pr, u32, u32, vp, u64, vp, u64, vp]
     L.zsmi_seekableFindRegexHost.restype = i32; L.zsmi_seekableFindRegexHost.argtypes = [vp, vp, vp, u32, i32, pr, u32, u32, vp, sz, vp]
+    L.zsmi_recordIndexFrameSize.restype = sz; L.zsmi_recordIndexFrameSize.argtypes = [sz]
+    L.zsmi_writeRecordIndexFrame.restype = sz; L.zsmi_writeRecordIndexFrame.argtypes = [vp, sz, vp, sz, i32]
+    L.zsmi_readRecordIndexFrame.restype = sz; L.zsmi_readRecordIndexFrame.argtypes = [vp, sz, vp, sz, ctypes.POINTER(i32)]
+    L.zsmi_indexRecords.restype = i32; L.zsmi_indexRecords.argtypes = [vp, sz, vp, sz, i32, vp, vp]
+    L.zsmi_seekableAttachRecordIndex.restype = sz; L.zsmi_seekableAttachRecordIndex.argtypes = [vp, sz, sz, vp, sz, i32]
+    L.zsmi_indexRecordsDevice.restype = i32; L.zsmi_indexRecordsDevice.argtypes = [vp, vp, u64, vp, u32, i32, i32, vp, vp, vp]
+    L.zsmi_seekableIndexRecordsResident.restype = i32; L.zsmi_seekableIndexRecordsResident.argtypes = [vp, vp, i32, u32, u32, vp, u64, vp, vp]
+    L.zsmi_seekableLoadRecordIndexResident.restype = i32; L.zsmi_seekableLoadRecordIndexResident.argtypes = [vp, vp, vp, vp]
+    L.zsmi_seekableAttachRecordIndexResident.restype = i32; L.zsmi_seekableAttachRecordIndexResident.argtypes = [vp, vp, u64, vp, vp, u32, i32]
+    L.zsmi_seekableLoadRecordIndexHost.restype = i32; L.zsmi_seekableLoadRecordIndexHost.argtypes = [vp, vp, vp, vp]
+    L.zsmi_seekableIndexRecordsHost.restype = i32; L.zsmi_seekableIndexRecordsHost.argtypes = [vp, vp, i32, vp, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -318,6 +329,9 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_findRecords", "zsmi_findRecordsDevice", "zsmi_seekableFindWorkBound", "zsmi_seekableFindRecordsResident", "zsmi_seekableFindRecordsHost",
            "zsmi_findRecordsQuery", "zsmi_findRecordsQueryDevice", "zsmi_seekableFindQueryResident", "zsmi_seekableFindQueryHost",
            "zsmi_compileRegex", "zsmi_findRecordsRegex", "zsmi_findRecordsRegexDevice", "zsmi_seekableFindRegexResident", "zsmi_seekableFindRegexHost",
+           "zsmi_recordIndexFrameSize", "zsmi_writeRecordIndexFrame", "zsmi_readRecordIndexFrame", "zsmi_indexRecords", "zsmi_seekableAttachRecordIndex",
+           "zsmi_indexRecordsDevice", "zsmi_seekableIndexRecordsResident", "zsmi_seekableLoadRecordIndexResident", "zsmi_seekableAttachRecordIndexResident",
+           "zsmi_seekableLoadRecordIndexHost", "zsmi_seekableIndexRecordsHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

@@ -22,6 +22,10 @@
                       the size queries of a buffer of frames (zsmi_getFrameContentSize ...): host only, the container's headers alone.
                       On the device, for a batch: BatchCodec.frame_sizes_device, and with layout_outputs_device and decompress_resident
                       a decode whose descriptors never leave device memory.
+  index_records, write_record_index_frame, read_record_index_frame, attach_record_index
+                      the record index of a record archive (first_record, which every record call takes) as part of the archive: host
+                      only.  On the device: BatchCodec.index_records_device, attach_record_index_resident, SeekableHandle.
+                      load_record_index_resident, index_records_resident; SeekableArchive.first_record() loads or rebuilds it.
   train_dictionary, finalize_dictionary, get_dict_id
                       zstd dictionaries made on the GPU (fastCover and ZDICT_finalizeDictionary; zdict.h's parameters).
 
@@ -33,6 +37,7 @@ from . import _lib
 
 ERROR_MAX_CODE = 120            # ZSMI_error_maxCode (include/zsmi.h)
 ERROR_MAX = (1 << 32) - ERROR_MAX_CODE      # ZStdErrors.cs:95-98 : IsError(c) = c > (uint)-120; csrc/zsmi_status.h states it for the library
+ERROR_PREFIX_UNKNOWN = 10                   # ZSMI_error_prefix_unknown
 ERROR_PARAMETER_UNSUPPORTED = 40            # ZSMI_error_parameter_unsupported
 ERROR_PARAMETER_OUT_OF_BOUND = 42           # ZSMI_error_parameter_outOfBound
 ERROR_FRAME_INDEX_TOO_LARGE = 100           # ZSMI_error_frameIndex_tooLarge
@@ -140,6 +145,60 @@ def split_records(data, delimiter=b"\n", target_size=0, max_frame_size=1 << 16):
         p = ctypes.c_void_p
         _raise_if_error(L, L.zsmi_splitRecords(s, n, d, target_size, max_frame_size, p(sizes.ctypes.data), p(first.ctypes.data), frames, None))
     return sizes, first
+
+
+def index_records(data, frame_sizes, delimiter=b"\n"):
+    """the record index of delimited text cut into frames of frame_sizes bytes (zsmi_indexRecords, host only): (first_record uint64[n + 1],
+    {"records", "misaligned", "delimiters"}).  first_record[i]: the delimiters in front of frame i (+ 1 at the text's end for a tail
+    without one).  misaligned: the frames that hold a delimiter, do not end on one and do not end the text - with any, a record that
+    is cut need not start a frame, and the lookup of read_records / find_records does not hold."""
+    L = _lib.lib()
+    s, n = _buf(data)
+    sizes = np.ascontiguousarray(frame_sizes, dtype=np.uint32)
+    first = np.zeros(len(sizes) + 1, dtype=np.uint64); result = np.zeros(4, dtype=np.uint64)
+    p = ctypes.c_void_p
+    rc = L.zsmi_indexRecords(s, n, p(sizes.ctypes.data) if len(sizes) else None, len(sizes), _delimiter(delimiter), p(first.ctypes.data), p(result.ctypes.data))
+    if rc:
+        raise RuntimeError(_error_name(L, rc))
+    return first, {"records": int(result[1]), "misaligned": int(result[2]), "delimiters": int(result[3])}
+
+
+def write_record_index_frame(first_record, delimiter=b"\n") -> bytes:
+    """the index frame of first_record (n + 1 entries, from 0, ascending): the skippable frame an archive carries between its last frame
+    and its seek table (zsmi_writeRecordIndexFrame, host only)"""
+    L = _lib.lib()
+    first = np.ascontiguousarray(first_record, dtype=np.uint64)
+    n = max(len(first) - 1, 0)
+    cap = _raise_if_error(L, L.zsmi_recordIndexFrameSize(n))
+    out = ctypes.create_string_buffer(cap)
+    size = _raise_if_error(L, L.zsmi_writeRecordIndexFrame(out, cap, ctypes.c_void_p(first.ctypes.data) if len(first) else None, n, _delimiter(delimiter)))
+    return out.raw[:size]
+
+
+def read_record_index_frame(frame):
+    """(first_record uint64[n + 1], the delimiter as one byte) of an index frame (zsmi_readRecordIndexFrame, host only); RuntimeError with
+    the error's name for bytes that are no such frame, or a damaged one"""
+    L = _lib.lib()
+    s, size = _buf(frame)
+    n = _raise_if_error(L, L.zsmi_readRecordIndexFrame(s, size, None, 0, None))
+    first = np.zeros(n + 1, dtype=np.uint64)
+    d = ctypes.c_int(0)
+    _raise_if_error(L, L.zsmi_readRecordIndexFrame(s, size, ctypes.c_void_p(first.ctypes.data), n + 1, ctypes.byref(d)))
+    return first, bytes([d.value])
+
+
+def attach_record_index(archive, first_record, delimiter=b"\n") -> bytes:
+    """the seekable archive with its record index attached (zsmi_seekableAttachRecordIndex, host only): first_record has the archive's
+    frame count + 1 entries.  Every reader sees one more frame, an empty one; SeekableArchive.first_record() loads the index back."""
+    L = _lib.lib()
+    first = np.ascontiguousarray(first_record, dtype=np.uint64)
+    n = max(len(first) - 1, 0)
+    frame = _raise_if_error(L, L.zsmi_recordIndexFrameSize(n))
+    room = np.zeros(len(archive) + frame + 12, dtype=np.uint8)
+    room[:len(archive)] = np.frombuffer(bytes(archive), dtype=np.uint8)
+    size = _raise_if_error(L, L.zsmi_seekableAttachRecordIndex(ctypes.c_void_p(room.ctypes.data), len(archive), len(room),
+                                                               ctypes.c_void_p(first.ctypes.data) if len(first) else None, n, _delimiter(delimiter)))
+    return room[:size].tobytes()
 
 
 def find_records(data, pattern, delimiter=b"\n", base=0):
@@ -571,6 +630,33 @@ class SeekableArchive:
                 raise RuntimeError(_error_name(self.L, rc))
         return self._results(out, np.diff(off), codes, n, "record", return_codes)
 
+    def first_record(self, delimiter=b"\n", allow_misaligned=False):
+        """the array read_records and the find calls take (uint64[num_frames + 1]): loaded from the archive's index frame when it
+        carries one (zsmi_seekableLoadRecordIndexHost; written for another delimiter: ValueError), else rebuilt from the content
+        (zsmi_seekableIndexRecordsHost: one decode of the archive).  A rebuilt index with misaligned frames - frames that hold a
+        delimiter, do not end on one and do not end the content, as fixed-size frames over text do - does not support the lookup of
+        the record calls: ValueError, unless allow_misaligned.  A frame that fails raises RuntimeError with the error's name."""
+        self._open()
+        d = _delimiter(delimiter)
+        first = np.zeros(self.num_frames + 1, dtype=np.uint64)
+        result = np.zeros(4, dtype=np.uint64)
+        p = BatchCodec._p
+        rc = self.L.zsmi_seekableLoadRecordIndexHost(self.codec.ctx, self.handle, p(first), p(result))
+        if rc:
+            raise RuntimeError(_error_name(self.L, rc))
+        if int(result[0]) == 0:
+            if int(result[2]) != d:
+                raise ValueError("the archive's record index was written for delimiter %d" % int(result[2]))
+            return first
+        if int(result[0]) != ERROR_PREFIX_UNKNOWN:
+            raise RuntimeError(_error_name(self.L, int(result[0])))
+        rc = self.L.zsmi_seekableIndexRecordsHost(self.codec.ctx, self.handle, d, p(first), p(result))
+        if rc or int(result[0]):
+            raise RuntimeError(_error_name(self.L, rc or int(result[0])))
+        if int(result[2]) and not allow_misaligned:
+            raise ValueError("%d frames are misaligned: records that are cut need not start a frame (allow_misaligned=True returns the array all the same)" % int(result[2]))
+        return first
+
     def find_records(self, first_record, pattern, delimiter=b"\n", first_frame=0, frame_count=None):
         """the records of a record archive that hold `pattern` (a literal byte string of 1 .. 256 bytes without the delimiter): the list
         of their numbers, ascending, as read_records takes them.  first_record is split_records' second array for the text the archive
@@ -893,6 +979,30 @@ class SeekableHandle:
                                                    frame_count, p(d_work_ptr), work_capacity, p(d_records_ptr), capacity, p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_seekableFindRegexResident: {_error_name(self.L, rc)}")
+
+    def load_record_index_resident(self, d_first_record_ptr, d_result_ptr, codec=None):
+        """the record index the archive carries (its last entry, an index frame) into d_first_record (uint64[num_frames + 1]): the array
+        the record calls above take with n_frames = num_frames.  d_result (uint64[4]) = {status, records, delimiter, n}; a status other
+        than 0 - prefix_unknown for an archive without an index - leaves the array untouched.  Nothing goes to the host.
+        zsmi_seekableLoadRecordIndexResident"""
+        codec = codec or self.codec
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_seekableLoadRecordIndexResident(codec.ctx, self.handle, p(d_first_record_ptr), p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableLoadRecordIndexResident: {_error_name(self.L, rc)}")
+
+    def index_records_resident(self, first_frame, frame_count, d_work_ptr, work_capacity, d_first_record_ptr, d_result_ptr, delimiter=b"\n", codec=None):
+        """the record index rebuilt from the content of frames [first_frame, first_frame + frame_count): they are decoded into d_work
+        (find_work_bound bytes) and d_first_record (uint64[num_frames + 1]) receives the entries behind first_frame (entry 0 too for the
+        window at 0), counted from d_first_record[first_frame] - windows taken in ascending order chain.  d_result (uint64[4]) = {the
+        first failing frame's code, records, misaligned frames, delimiters}.  Nothing goes to the host.
+        zsmi_seekableIndexRecordsResident"""
+        codec = codec or self.codec
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_seekableIndexRecordsResident(codec.ctx, self.handle, _delimiter(delimiter), first_frame, frame_count, p(d_work_ptr), work_capacity,
+                                                      p(d_first_record_ptr), p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableIndexRecordsResident: {_error_name(self.L, rc)}")
 
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`, from the handle's table"""
@@ -1257,6 +1367,28 @@ class BatchCodec:
                                                 capacity, p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_findRecordsRegexDevice: {_error_name(self.L, rc)}")
+
+    def index_records_device(self, d_text_ptr, size, d_places_ptr, n, d_first_record_ptr, d_result_ptr, delimiter=b"\n", at_end=True, d_base_ptr=0):
+        """index_records on the device, text and frame borders in device memory (asynchronous: only queued): d_places (uint64[n + 1],
+        ascending, 0 first, size last) are the frames' borders in d_text[0, size); d_first_record (uint64[n + 1]) receives *d_base + the
+        delimiters in front of each border (+ 1 at `size` for a tail without a delimiter when at_end says that `size` ends the content) -
+        entry 0 only without a base -, d_result (uint64[4]) the status, the records, the misaligned frames and the delimiters.
+        zsmi_indexRecordsDevice"""
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_indexRecordsDevice(self.ctx, p(d_text_ptr), size, p(d_places_ptr), n, _delimiter(delimiter), 1 if at_end else 0, p(d_base_ptr),
+                                            p(d_first_record_ptr), p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_indexRecordsDevice: {_error_name(self.L, rc)}")
+
+    def attach_record_index_resident(self, d_archive_ptr, capacity, d_archive_size_ptr, d_first_record_ptr, n, delimiter=b"\n"):
+        """attach_record_index on an archive in device memory whose size is a device word, as compress_seekable_frames_resident left both
+        (asynchronous: only queued): the index frame of d_first_record (uint64[n + 1]) goes between the last frame and the table, and the
+        word becomes the new size or (uint64)-code; an error word that comes in stays.  capacity: the bytes at d_archive (the new size
+        is 40 + 4 n + one table entry above the old).  zsmi_seekableAttachRecordIndexResident"""
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_seekableAttachRecordIndexResident(self.ctx, p(d_archive_ptr), capacity, p(d_archive_size_ptr), p(d_first_record_ptr), n, _delimiter(delimiter))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableAttachRecordIndexResident: {_error_name(self.L, rc)}")
 
     def open_seekable_device(self, d_ptr, size, ddict=None, ddict_set=None):
         """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The

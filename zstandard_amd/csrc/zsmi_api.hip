@@ -23,6 +23,7 @@
 #include "find.hip"               // feature: find records by content - text or a window of a record archive and a literal pattern -> ascending record numbers (kernels and host; the rule: zsmi_find.h)
 #include "findquery.hip"          // feature: find records by several patterns - any, all, none of up to 8 patterns, ASCII case folding -> ascending record numbers and hit sets (kernels and host; the rule: zsmi_findquery.h)
 #include "findregex.hip"          // feature: find records by regular expression - a pattern compiled on the host into a minimal DFA, a state function carried across lanes, wavefronts and tiles -> ascending record numbers (kernels and host; the rule and the compiler: zsmi_regex.h)
+#include "recindex.hip"           // feature: the record index of an archive - firstRecord rebuilt from text and frame borders, stored in the archive as a skippable frame, loaded from it (kernels and host; the rule and the frame: zsmi_recindex.h)
 
 #include <cstdio>
 #include <cstdlib>
