@@ -885,6 +885,113 @@ int zsmi_seekableAttachRecordIndexResident(zsmi_ctx *ctx, void *dArchive, uint64
                                            const uint64_t *dFirstRecord, uint32_t n, int delim);
 int zsmi_seekableLoadRecordIndexHost(zsmi_ctx *ctx, const zsmi_seekable *sk, uint64_t *firstRecord, uint64_t *result);
 int zsmi_seekableIndexRecordsHost(zsmi_ctx *ctx, const zsmi_seekable *sk, int delim, uint64_t *firstRecord, uint64_t *result);
+/* Frame filters: ask which frames of a record archive can hold a query's records BEFORE any frame is decoded - a small n-gram Bloom
+ * filter a frame, all of them one skippable frame that the caller keeps BESIDE the archive, as a file or blob of its own.  The rule
+ * (zstandard_amd/csrc/zsmi_filter.h states it in code, with the reason for rule 11): content of `size` bytes, frames at content offsets
+ * dOff[0 .. N], a delimiter, a gram length g in {3, 4}, log2Bits L in 9 .. 16 - the bits a frame:
+ *  1. fold(b) = b + 0x20 for 'A' .. 'Z', b otherwise: the query calls' fold, here ALWAYS applied - one filter serves searches with and
+ *     without ZSMI_FIND_IGNORE_CASE.
+ *  2. A gram of frame i is g consecutive bytes wholly inside frame i, none of which equals delim, unfolded.
+ *  3. Its value v is the little-endian integer of its folded bytes;  4. its bits are h_k = (uint32_t)(v * C_k) >> (32 - L), C_0 = 0x9E3779B1,
+ *     C_1 = 0x85EBCA77; bit h is bit h & 7 of byte h >> 3 of the frame's slot of 2^(L-3) bytes.
+ *  5. A border x is clean when x == 0, x == size or content[x - 1] == delim.  6. A non-empty frame with a border that is not clean is
+ *     SATURATED, its slot all ones (cut records and fixed-size frames over text produce them).  7. An empty frame's slot is all zeros,
+ *     every other frame's the OR of its grams' bits.
+ *  8. A pattern of m >= g bytes passes frame i when every bit of each of its m - g + 1 folded grams is set in slot i.  9. A pattern with
+ *     m < g passes every frame.  10. A query passes a frame - any: some pattern passes; all: every pattern passes; none: every frame.  (The
+ *     frame records no frame sizes and a frame without a gram has an empty frame's slot, so "every frame" includes the empty ones.)
+ * 11. No false negatives: a record lies inside one clean frame or inside a run of saturated frames, so a frame that holds any part of a
+ *     record satisfying an `any` or `all` query always passes.
+ * The frame, little-endian: u32 0x184D2A5C | u32 Frame_Size = 32 + N 2^(L-3) | u32 0x52544C46 | u8 version 1, u8 delim, u8 g, u8 L | u32 N |
+ * u32 0 | u64 size | u64 check | N slots;  check = sum over the slots' 64-bit words w_k of (w_k + 1) (2 k + 1) 0x9E3779B185EBCA87, + size
+ * 0xC2B2AE3D27D4EB4F + delim + (g << 8) + (L << 16), mod 2^64.
+ * Not covered: the single-pattern and regular-expression forms of the list search below; filters for regular expressions; `none` mode
+ * (every frame passes the filter, and the list search refuses it);
+ * the filter inside the archive (the record index frame is defined as the table's last entry); Bloom parameters other than two hashes.
+ * Host only, no device - the serial statements the device forms are held against:
+ * zsmi_frameFilterSize: 40 + n 2^(L-3); log2Bits outside 9..16: parameter_outOfBound; a Frame_Size beyond 32 bits: frameIndex_tooLarge.
+ * zsmi_buildFrameFilter: text whose frame i holds frameSizes[i] bytes -> the frame; its size or a code, in this order: delim outside
+ * 0..255, gram not 3 or 4, log2Bits outside 9..16: parameter_outOfBound; a Frame_Size beyond 32 bits: frameIndex_tooLarge; a NULL dst, a
+ * NULL frameSizes with n > 0: GENERIC; a NULL src with bytes, sizes that do not sum to srcSize: srcSize_wrong; dstCapacity below the size:
+ * dstSize_tooSmall.  Nothing is written on failure, nothing behind dst[size), nothing outside src[0, srcSize) is read.
+ * zsmi_readFrameFilter: judges the frame and fills *info; 0 or a code, in this order: a NULL info: GENERIC; fewer than 40 bytes:
+ * srcSize_wrong; either magic: prefix_unknown; the version: version_unsupported; delim / g / L out of range, the reserved field, a
+ * Frame_Size that is not N's: corruption_detected; fewer bytes than N asks for: srcSize_wrong; the check: corruption_detected.
+ * info.saturated counts the slots that are all ones.  Reads only src[0, 40 + N 2^(L-3)).
+ * zsmi_filterFrames: the ascending numbers of the frames of [firstFrame, firstFrame + frameCount) that pass q -> frames[0, capacity);
+ * result = {total, written = min(total, capacity), frames tested, all-ones slots among the total}; [0] and [3] are exact whatever
+ * capacity is (capacity == 0 with NULL frames only counts).  0 or a code, in this order: a NULL q or result, a NULL frames with capacity:
+ * GENERIC; the header's judgement as above, without the check (a caller that wants it calls zsmi_readFrameFilter once); the query's
+ * checks against the FILTER's delimiter (zsmi_findRecordsQuery's); a window beyond N: parameter_outOfBound.  A list it writes never
+ * separates a record's frames by a frame that holds bytes: window searches over the runs of the list - listed frames that follow one
+ * another, or have only EMPTY frames between them - find each record of the window once.
+ * Device, only queued - no copy to the host, no wait, no pinned staging; all scratch is the context's, reserved before anything is queued;
+ * dFilter is 8-byte aligned (otherwise parameter_outOfBound, behind the other argument checks):
+ * zsmi_buildFrameFilterDevice: the whole content in device memory, dPlaces as zsmi_indexRecordsDevice takes them (uint64[n + 1],
+ * ascending, 0 first, `size` last).  Writes the complete frame, header and check included, byte for byte the host call's.  dResult =
+ * {status, bytes written, all-ones slots, grams hashed}; status: parameter_outOfBound when dPlaces[0] != 0 or dPlaces[n] != size.  Places
+ * that do not ascend leave their slots unspecified; nothing outside dFilter[0, 40 + n 2^(L-3)) and dResult[0 .. 3] is written, nothing
+ * outside the text read.  Checked on the host, in this order: a NULL ctx: init_missing; a NULL dResult, dPlaces or dFilter: GENERIC;
+ * delim, gram, log2Bits: parameter_outOfBound; Frame_Size: frameIndex_tooLarge; size > 0 behind a NULL dText: srcSize_wrong; capacity
+ * below the frame: dstSize_tooSmall.
+ * zsmi_seekableBuildFrameFilterResident: the archive's frames decoded end to end into dWork - the whole archive one window,
+ * zsmi_seekableFindWorkBound(sk, 0, N) sizes it - then the body above with the handle's content offsets as places.  dResult[0]: the first
+ * failing frame's code, as zsmi_seekableIndexRecordsResident reports it - when it is not 0 the frame is NOT to be trusted (it is written
+ * all the same).  Checked on the host, in the rebuild's order: a NULL ctx: init_missing; a NULL sk, dResult or dFilter: GENERIC; a handle
+ * of another device: parameter_unsupported; delim, gram, log2Bits: parameter_outOfBound; Frame_Size: frameIndex_tooLarge; a NULL dWork
+ * with an archive that holds bytes: GENERIC; workCapacity below the bound, then capacity below the frame: dstSize_tooSmall.
+ * zsmi_seekableBuildFrameFilterHost: the same into a host buffer behind one wait, a work buffer of the context's, in windows of at most
+ * 256 MiB of content cut wherever the table allows; byte for byte the one-window result.  result[4] as dResult.
+ * zsmi_checkFrameFilterDevice: zsmi_readFrameFilter's judgement on the device, check word included, one pass over the slots.  dResult
+ * [8] = {status, N, delim, g, L, size, all-ones slots, 0}, the fields 0 with any status but 0.  Reads only inside dFilter[0, filterSize).
+ * Checked on the host: a NULL ctx: init_missing; a NULL dFilter or dResult: GENERIC.
+ * zsmi_filterFramesDevice: zsmi_filterFrames on a filter in device memory: dFrames uint32[capacity], dResult[4] as result - the host
+ * call's answers for the same bytes.  g, L and the delimiter lie in the header the host never reads, so the patterns travel by value and
+ * each workgroup hashes their grams once; the header's fields are judged on the device against filterSize, and what the host form
+ * refuses of these bytes and this query puts (uint64_t)-code in dResult[0] and zeros behind it; nothing is written to dFrames then.
+ * dResult[0] is a device word a later call can take as its frame count.  Checked on the host: a NULL ctx: init_missing; a NULL dFilter, q
+ * or dResult, a NULL dFrames with capacity: GENERIC; the query's shape (nPatterns, mode, flags, pointers, sizes): as zsmi_findRecordsQuery.
+ * zsmi_seekableFindQueryFramesResident: the query search over a LIST of frames in device memory - dFrames ascending, *dFrameCount a device
+ * word, so dResult[0] of zsmi_filterFramesDevice can be passed straight in; the host is told only maxFrames (the entries dFrames holds).
+ * The rule: a run is a maximal stretch of the list whose frames follow one another in the archive; the text searched is the runs'
+ * content; an occurrence lies inside one run; its record is firstRecord[f] + the delimiters in front of it inside the frame f it starts
+ * in; the answer is the satisfying records, ascending, each once a run.  A list the filter call wrote never separates a record's frames
+ * by a frame that holds bytes, so there each record appears once, and dRecords, dHits, dResult[0] and [1] are what
+ * zsmi_seekableFindQueryResident gives over the window the filter was asked about ([2], the occurrences, too for `any`; an `all` query
+ * counts only the occurrences inside the listed frames).  dResult = {total, written, occurrences, content bytes decoded}.  Refused in
+ * dResult[0] as (uint64_t)-code with nothing written to dRecords, in this order: *dFrameCount > maxFrames: dstSize_tooSmall, the work
+ * bound of that many frames in dResult[3]; a list that does not ascend or names a frame >= nFrames: frameIndex_tooLarge; content (one
+ * byte more a run that another follows) above workCapacity: dstSize_tooSmall, the bytes needed in dResult[3]; a frame that fails: its
+ * code, as the window searches report it.  zsmi_seekableFindFramesWorkBound(sk, maxFrames) = maxFrames x (the handle's largest
+ * Decompressed_Size + 1) always holds the list.  The text searched is min(workCapacity, that bound) bytes, filled with delimiters behind
+ * the content.  Checked on the host, in the query calls' order: a NULL ctx: init_missing; a NULL sk, dResult, q, dFirstRecord,
+ * dFrameCount, dFrames with maxFrames, dRecords with capacity: GENERIC; a handle of another device: parameter_unsupported; the query's
+ * checks; mode `none`: parameter_unsupported; nFrames not the handle's: parameter_outOfBound; a NULL dWork with workCapacity: GENERIC.
+ * zsmi_seekableFindQueryFramesHost: host arrays, one wait, a work buffer of the context's of the bound of frameCount frames. */
+typedef struct { uint32_t nFrames, delim, gram, log2Bits; uint64_t size, saturated; } zsmi_frameFilterInfo;
+size_t zsmi_seekableFindFramesWorkBound(const zsmi_seekable *sk, uint32_t maxFrames);
+int zsmi_seekableFindQueryFramesResident(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
+                                         const zsmi_findQuery *q, const uint32_t *dFrames, const uint64_t *dFrameCount, uint32_t maxFrames,
+                                         void *dWork, uint64_t workCapacity, uint64_t *dRecords, uint8_t *dHits, uint64_t capacity,
+                                         uint64_t *dResult);
+int zsmi_seekableFindQueryFramesHost(zsmi_ctx *ctx, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
+                                     const zsmi_findQuery *q, const uint32_t *frames, uint32_t frameCount,
+                                     uint64_t *records, uint8_t *hits, size_t capacity, uint64_t *result);
+size_t zsmi_frameFilterSize(size_t n, unsigned log2Bits);
+size_t zsmi_buildFrameFilter(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const uint32_t *frameSizes, size_t n,
+                             int delim, unsigned gram, unsigned log2Bits);
+int zsmi_readFrameFilter(const void *src, size_t srcSize, zsmi_frameFilterInfo *info);
+int zsmi_filterFrames(const void *filter, size_t filterSize, const zsmi_findQuery *q, uint32_t firstFrame, uint32_t frameCount,
+                      uint32_t *frames, size_t capacity, uint64_t *result);
+int zsmi_buildFrameFilterDevice(zsmi_ctx *ctx, const void *dText, uint64_t size, const uint64_t *dPlaces, uint32_t n, int delim,
+                                unsigned gram, unsigned log2Bits, void *dFilter, uint64_t capacity, uint64_t *dResult);
+int zsmi_seekableBuildFrameFilterResident(zsmi_ctx *ctx, const zsmi_seekable *sk, int delim, unsigned gram, unsigned log2Bits,
+                                          void *dWork, uint64_t workCapacity, void *dFilter, uint64_t capacity, uint64_t *dResult);
+int zsmi_seekableBuildFrameFilterHost(zsmi_ctx *ctx, const zsmi_seekable *sk, int delim, unsigned gram, unsigned log2Bits,
+                                      void *filter, size_t capacity, uint64_t *result);
+int zsmi_checkFrameFilterDevice(zsmi_ctx *ctx, const void *dFilter, uint64_t filterSize, uint64_t *dResult);
+int zsmi_filterFramesDevice(zsmi_ctx *ctx, const void *dFilter, uint64_t filterSize, const zsmi_findQuery *q, uint32_t firstFrame,
+                            uint32_t frameCount, uint32_t *dFrames, uint64_t capacity, uint64_t *dResult);
 /* host only: the table at the archive's end (errors as above) */
 size_t zsmi_seekableNumFrames(const void *src, size_t srcSize);
 size_t zsmi_seekableContentSize(const void *src, size_t srcSize);

@@ -54,14 +54,18 @@ profiles/find_regex_bench.jsonl.
 --split --record-index: the record index on the same stream's archives at targetSize 65536, 4096 and 0 - attach against the resident compress
 call it follows, load against zsmi_openSeekableDevice, rebuild against the whole-content range read, the body's kernels against the
 splitter's (record_index_legs' docstring).  One JSON line, also appended to profiles/record_index_bench.jsonl.
-  python tools/bench_seekable.py --split --record-index [--mib 1024]"""
+  python tools/bench_seekable.py --split --record-index [--mib 1024]
+--split --filter: frame filters on the same stream's archives at targetSize 65536 (g = 4, L = 13) and 4096 (g = 4, L = 10) - the filter's bytes
+over the archive's, the build against the index rebuild, its kernels beside k_split_count, candidates against true frames, and filter ->
+list search (zsmi_seekableFindQueryFramesResident, fed in device memory) against the whole-archive query search (filter_legs' docstring).
+  python tools/bench_seekable.py --split --filter [--mib 1024] [--filter-patterns "ERROR ienwbvuzw"]"""
 import argparse, json, os, sys, time
 import torch                                               # before libzsmi.so
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import _data as D
-from zstandard_amd import BatchCodec, SeekableArchive, _lib
+from zstandard_amd import BatchCodec, SeekableArchive, _lib, frame_filter_size
 
 
 def timed(fn, sync, reps):
@@ -939,8 +943,113 @@ def record_index_legs(a):
         f.write(line + "\n")
 
 
+def filter_legs(a):
+    """--split --filter: frame filters on the Zipf log stream (text lines, ~150 bytes each) in device memory, for the archives of targetSize
+    65536 (g = 4, L = 13; then L = 16) and 4096 (g = 4, L = 10; then L = 13), three rounds of alternating legs each, all in one process:
+      bytes      the filter frame's bytes over the archive's;
+      build      zsmi_seekableBuildFrameFilterResident against zsmi_seekableIndexRecordsResident on the same handle - both decode the archive;
+      kernels    k_filter_tiles and k_filter_check (zsmi_buildFrameFilterDevice on the text and the frames' borders, HIP events, three
+                 calls: the sorted times) beside k_split_count on the same buffer; k_filter_test and k_filter_list of one filter call;
+      candidates the frames zsmi_filterFramesDevice passes against the frames that truly hold a record of the answer, for a needle (the
+                 first 24 bytes of one line), a rare pattern (one line in 2000), `e` and a pattern shorter than g;
+      search     zsmi_filterFramesDevice and, fed by its dFrames and dResult[0] as they lie in device memory,
+                 zsmi_seekableFindQueryFramesResident (maxFrames = all frames, the work bound of that many) - against
+                 zsmi_seekableFindQueryResident over the whole archive for the same query; the answers are held against each other; the
+                 k_findsel_* kernels of one call.
+    One JSON line, also appended to profiles/frame_filter_bench.jsonl."""
+    size, M, reps = (a.mib or 1024) << 20, a.frame, 3
+    gib = size / float(1 << 30)
+    bc = BatchCodec(0)
+    src = torch.from_numpy(D.zipf_log(size)).cuda()
+    words = torch.zeros(8, dtype=torch.int64, device="cuda")
+    bc.count_records_device(src.data_ptr(), size, words.data_ptr()); bc.sync()
+    records = int(words[0].item())
+    mp = BatchCodec.split_pieces_bound(records, size, M)
+    fs = torch.zeros(mp, dtype=torch.int32, device="cuda"); fr = torch.zeros(mp + 1, dtype=torch.int64, device="cuda")
+    work = torch.empty(size, dtype=torch.uint8, device="cuda")
+    ms = lambda v: [round(t * 1e3, 4) for t in v]
+    med = lambda v: float(np.median(v))
+    mid = bytes(src[size // 2:size // 2 + 4096].cpu().numpy())
+    needle = mid[mid.index(b"\n") + 1:][:24].split(b"\n")[0]                # the start of one line in the middle of the stream: in a frame or two
+    patterns = {"needle": needle, "rare": a.filter_patterns[0].encode(), "e": b"e", "short": a.filter_patterns[0].encode()[:3]}
+
+    def kernels(fn, names):
+        runs = []
+        for _ in range(reps):
+            bc.enable_timing(True); fn(); runs.append(bc.kernel_times()); bc.enable_timing(False)
+        return {k: sorted(round(r[k][0] * 1e3, 4) for r in runs) for k in names}
+    rep = {"metric": "frame_filter", "gib": gib, "max_frame_size": M, "records": records, "patterns": {k: v.decode("latin-1") for k, v in patterns.items()},
+           "library": bc.L.zsmi_versionString().decode()}
+    for T, g, Lg in ((65536, 4, 13), (4096, 4, 10), (65536, 4, 16), (4096, 4, 13)):      # the two sets the archives were planned with; then the most bits a 64 KiB frame can have, and 2 bits a byte at 4 KiB
+        split = lambda: bc.split_records_device(src.data_ptr(), size, mp, fs.data_ptr(), fr.data_ptr(), words.data_ptr() + 8, target_size=T, max_frame_size=M)
+        split(); bc.sync()
+        n = int(words[1].item())
+        room = bc.seekable_frames_resident_bound(size, n, True)
+        arc = torch.empty(room, dtype=torch.uint8, device="cuda"); arc_size = words.data_ptr() + 32
+        bc.compress_seekable_frames_resident(src.data_ptr(), size, fs.data_ptr(), n, M, arc.data_ptr(), room, arc_size, a.level, True); bc.sync()
+        asize = int(words[4].item())
+        assert asize < (1 << 63), "a frame failed: %#x" % (asize & ((1 << 64) - 1))
+        h = bc.open_seekable_device(arc.data_ptr(), asize)
+        fbytes = frame_filter_size(n, Lg)
+        flt = torch.zeros(fbytes, dtype=torch.uint8, device="cuda"); flt_text = torch.zeros(fbytes, dtype=torch.uint8, device="cuda")
+        rebuilt = torch.zeros(n + 1, dtype=torch.int64, device="cuda"); res = torch.zeros(16, dtype=torch.int64, device="cuda")
+        build = lambda: h.build_frame_filter_resident(work.data_ptr(), size, flt.data_ptr(), fbytes, res.data_ptr(), gram=g, log2_bits=Lg)
+        rebuild = lambda: h.index_records_resident(0, n, work.data_ptr(), size, rebuilt.data_ptr(), res.data_ptr() + 32)
+        t = alternating({"index_rebuild": rebuild, "filter_build": build}, bc.sync, reps)
+        got = res.tolist()
+        assert got[0] == 0 and got[1] == fbytes and got[4] == 0 and got[5] == records, got[:8]
+        saturated, grams = got[2], got[3]
+        places = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(fs[:n].to(torch.int64), 0)])
+        text = lambda: bc.build_frame_filter_device(src.data_ptr(), size, places.data_ptr(), n, flt_text.data_ptr(), fbytes, res.data_ptr() + 64, gram=g, log2_bits=Lg)
+        kt = kernels(text, ("k_filter_tiles", "k_filter_check"))
+        kt.update(kernels(split, ("k_split_count",)))
+        bc.sync()
+        assert bool((flt == flt_text).all()), "the archive's filter is not the text's"
+        bc.check_frame_filter_device(flt.data_ptr(), fbytes, res.data_ptr() + 64); bc.sync()
+        assert res.tolist()[8:15] == [0, n, 10, g, Lg, size, saturated]
+        # the searches: the whole archive against filter -> list search, nothing read back between the two calls
+        cap = records
+        out_whole = torch.zeros(cap, dtype=torch.int64, device="cuda"); out_runs = torch.zeros(cap, dtype=torch.int64, device="cuda")
+        frames = torch.zeros(n, dtype=torch.int32, device="cuda")
+        lbound = h.find_frames_work_bound(n)
+        lwork = torch.empty(lbound, dtype=torch.uint8, device="cuda")
+        row_q = {}
+        for name, pat in patterns.items():
+            def whole():
+                h.find_query_resident(fr.data_ptr(), n, [pat], 0, n, work.data_ptr(), size, out_whole.data_ptr(), 0, cap, res.data_ptr())
+
+            def filtered():                                               # nothing comes to the host between the two calls
+                bc.filter_frames_device(flt.data_ptr(), fbytes, [pat], 0, n, frames.data_ptr(), n, res.data_ptr() + 32)
+                h.find_query_frames_resident(fr.data_ptr(), n, [pat], frames.data_ptr(), res.data_ptr() + 32, n, lwork.data_ptr(), lbound, out_runs.data_ptr(), 0, cap,
+                                             res.data_ptr() + 64)
+            tq = alternating({"whole": whole, "filtered": filtered}, bc.sync, reps)
+            got = res.tolist()
+            total, candidates, decoded = got[0], got[4], got[11]
+            assert got[8] == total and got[9] == got[1] and bool((out_whole[:total] == out_runs[:total]).all()), (name, got[:12])
+            hits = out_whole[:total]
+            true_frames = int(torch.unique(torch.searchsorted(fr[:n + 1], hits, right=True) - 1).numel()) if total else 0
+            kq = kernels(lambda: bc.filter_frames_device(flt.data_ptr(), fbytes, [pat], 0, n, frames.data_ptr(), n, res.data_ptr() + 32), ("k_filter_test", "k_filter_list"))
+            kq.update(kernels(filtered, ("k_findsel_list", "k_findsel_code", "k_findsel_fill", "k_findsel_prefix", "k_findsel_renumber", "k_findq_count", "k_findq_emit")))
+            row_q[name] = {"records_found": total, "frames_with_a_record": true_frames, "candidates": candidates, "bytes_decoded": decoded,
+                           "ms": {k: ms(v) for k, v in tq.items()}, "kernels_ms": kq, "filtered_over_whole": round(med(tq["filtered"]) / med(tq["whole"]), 3)}
+        rep["target_%d_L%d" % (T, Lg)] = {"frames": n, "gram": g, "log2_bits": Lg, "archive_bytes": asize, "filter_bytes": fbytes, "filter_over_archive": round(fbytes / asize, 5),
+                                "saturated_frames": saturated, "grams_hashed": grams, "ms": {k: ms(v) for k, v in t.items()}, "kernels_ms": kt,
+                                "build_over_index_rebuild": round(med(t["filter_build"]) / med(t["index_rebuild"]), 3),
+                                "k_filter_tiles_over_k_split_count": round(kt["k_filter_tiles"][1] / kt["k_split_count"][1], 3),
+                                "k_filter_tiles_gibs": round(gib / (kt["k_filter_tiles"][1] * 1e-3), 1), "queries": row_q}
+        bc.sync(); h.close()
+        del arc, flt, flt_text, out_whole, out_runs, lwork
+    bc.close()
+    line = json.dumps(rep)
+    print(line, flush=True)
+    with open(a.out or os.path.join(ROOT, "profiles", "frame_filter_bench.jsonl"), "a") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--filter", action="store_true", help="with --split: frame filters - build, kernels, candidates and the filtered search against the whole one (filter_legs' docstring)")
+    ap.add_argument("--filter-patterns", nargs="+", default=["ERROR ienwbvuzw"], help="with --split --filter: the rare pattern (its first three bytes are the short one)")
     ap.add_argument("--record-index", action="store_true", help="with --split: the record index - attach, load and rebuild against the calls they follow or replace (record_index_legs' docstring)")
     ap.add_argument("--find-regex", action="store_true", help="with --split: find records by regular expression against the literal searches and re on the host (find_regex_legs' docstring)")
     ap.add_argument("--find-query", action="store_true", help="with --split: find records by several patterns against the single-pattern calls (find_query_legs' docstring)")
@@ -970,6 +1079,8 @@ def main():
     if a.index:
         return index_legs(a)
     if a.split:
+        if a.filter:
+            return filter_legs(a)
         if a.record_index:
             return record_index_legs(a)
         if a.find_query:

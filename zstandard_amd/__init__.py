@@ -5,3 +5,4 @@ from .api import frame_content_size, find_frame_compressed_size, find_decompress
 from .api import count_frames, build_seek_table   # noqa: F401
 from .api import split_records, find_records, find_records_query, compile_regex, find_records_regex   # noqa: F401
 from .api import index_records, write_record_index_frame, read_record_index_frame, attach_record_index   # noqa: F401
+from .api import frame_filter_size, build_frame_filter, read_frame_filter, filter_frames   # noqa: F401

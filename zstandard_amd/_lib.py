@@ -75,6 +75,13 @@ class FindQuery(ctypes.Structure):
                 ("patternSizes", ctypes.c_uint32 * 8)]
 
 
+class FrameFilterInfo(ctypes.Structure):
+    """zsmi_frameFilterInfo: what zsmi_readFrameFilter finds in a filter frame that holds - its frames, delimiter, gram length, log2 of the
+    bits a frame, the content's size and the slots that are all ones"""
+    _fields_ = [("nFrames", ctypes.c_uint32), ("delim", ctypes.c_uint32), ("gram", ctypes.c_uint32), ("log2Bits", ctypes.c_uint32),
+                ("size", ctypes.c_uint64), ("saturated", ctypes.c_uint64)]
+
+
 class RegexProgram(ctypes.Structure):
     """zsmi_regexProgram: the minimal DFA of a pattern (zsmi_compileRegex) - next[s * nClasses + classOf[b]], a start state, the accepting
     states as a 64-bit word, flags (1: compiled ignoring ASCII case, 2: list the records that do NOT match)"""
@@ -238,6 +245,20 @@ def lib():
     L.zsmi_seekableAttachRecordIndexResident.restype = i32; L.zsmi_seekableAttachRecordIndexResident.argtypes = [vp, vp, u64, vp, vp, u32, i32]
     L.zsmi_seekableLoadRecordIndexHost.restype = i32; L.zsmi_seekableLoadRecordIndexHost.argtypes = [vp, vp, vp, vp]
     L.zsmi_seekableIndexRecordsHost.restype = i32; L.zsmi_seekableIndexRecordsHost.argtypes = [vp, vp, i32, vp, vp]
+    L.zsmi_frameFilterSize.restype = sz; L.zsmi_frameFilterSize.argtypes = [sz, ctypes.c_uint]
+    L.zsmi_buildFrameFilter.restype = sz; L.zsmi_buildFrameFilter.argtypes = [vp, sz, vp, sz, vp, sz, i32, ctypes.c_uint, ctypes.c_uint]
+    L.zsmi_readFrameFilter.restype = i32; L.zsmi_readFrameFilter.argtypes = [vp, sz, ctypes.POINTER(FrameFilterInfo)]
+    L.zsmi_filterFrames.restype = i32; L.zsmi_filterFrames.argtypes = [vp, sz, pq, u32, u32, vp, sz, vp]
+    L.zsmi_buildFrameFilterDevice.restype = i32; L.zsmi_buildFrameFilterDevice.argtypes = [vp, vp, u64, vp, u32, i32, ctypes.c_uint, ctypes.c_uint, vp, u64, vp]
+    L.zsmi_seekableBuildFrameFilterResident.restype = i32
+    L.zsmi_seekableBuildFrameFilterResident.argtypes = [vp, vp, i32, ctypes.c_uint, ctypes.c_uint, vp, u64, vp, u64, vp]
+    L.zsmi_seekableBuildFrameFilterHost.restype = i32; L.zsmi_seekableBuildFrameFilterHost.argtypes = [vp, vp, i32, ctypes.c_uint, ctypes.c_uint, vp, sz, vp]
+    L.zsmi_checkFrameFilterDevice.restype = i32; L.zsmi_checkFrameFilterDevice.argtypes = [vp, vp, u64, vp]
+    L.zsmi_filterFramesDevice.restype = i32; L.zsmi_filterFramesDevice.argtypes = [vp, vp, u64, pq, u32, u32, vp, u64, vp]
+    L.zsmi_seekableFindFramesWorkBound.restype = sz; L.zsmi_seekableFindFramesWorkBound.argtypes = [vp, u32]
+    L.zsmi_seekableFindQueryFramesResident.restype = i32
+    L.zsmi_seekableFindQueryFramesResident.argtypes = [vp, vp, vp, u32, i32, pq, vp, vp, u32, vp, u64, vp, vp, u64, vp]
+    L.zsmi_seekableFindQueryFramesHost.restype = i32; L.zsmi_seekableFindQueryFramesHost.argtypes = [vp, vp, vp, u32, i32, pq, vp, u32, vp, vp, sz, vp]
     pfc, psz = ctypes.POINTER(FastCoverParams), ctypes.POINTER(sz)
     L.zsmi_trainFromBuffer.restype = sz; L.zsmi_trainFromBuffer.argtypes = [vp, sz, vp, psz, ctypes.c_uint]
     L.zsmi_trainFromBuffer_fastCover.restype = sz; L.zsmi_trainFromBuffer_fastCover.argtypes = [vp, sz, vp, psz, ctypes.c_uint, pfc]
@@ -332,6 +353,9 @@ EXPORTS = ["zsmi_isError", "zsmi_getErrorName", "zsmi_getErrorCode", "zsmi_decom
            "zsmi_recordIndexFrameSize", "zsmi_writeRecordIndexFrame", "zsmi_readRecordIndexFrame", "zsmi_indexRecords", "zsmi_seekableAttachRecordIndex",
            "zsmi_indexRecordsDevice", "zsmi_seekableIndexRecordsResident", "zsmi_seekableLoadRecordIndexResident", "zsmi_seekableAttachRecordIndexResident",
            "zsmi_seekableLoadRecordIndexHost", "zsmi_seekableIndexRecordsHost",
+           "zsmi_frameFilterSize", "zsmi_buildFrameFilter", "zsmi_readFrameFilter", "zsmi_filterFrames", "zsmi_buildFrameFilterDevice",
+           "zsmi_seekableBuildFrameFilterResident", "zsmi_seekableBuildFrameFilterHost", "zsmi_checkFrameFilterDevice", "zsmi_filterFramesDevice",
+           "zsmi_seekableFindFramesWorkBound", "zsmi_seekableFindQueryFramesResident", "zsmi_seekableFindQueryFramesHost",
            "zsmi_trainFromBuffer", "zsmi_trainFromBuffer_fastCover", "zsmi_trainFromDevice", "zsmi_finalizeDictionary", "zsmi_getDictID",
            "zsmi_setParameter", "zsmi_getParameter", "zsmi_compress_advanced", "zsmi_compress_usingCDict_advanced",
            "zsmi_getFrameContentSize", "zsmi_findFrameCompressedSize", "zsmi_findDecompressedSize", "zsmi_decompressBound",

@@ -201,6 +201,59 @@ def attach_record_index(archive, first_record, delimiter=b"\n") -> bytes:
     return room[:size].tobytes()
 
 
+def frame_filter_size(n, log2_bits=13) -> int:
+    """the bytes of a filter frame of n frames with 2^log2_bits bits each (zsmi_frameFilterSize, host only): 40 + n * 2^(log2_bits - 3)"""
+    L = _lib.lib()
+    return _raise_if_error(L, L.zsmi_frameFilterSize(n, log2_bits))
+
+
+def build_frame_filter(data, frame_sizes, delimiter=b"\n", gram=4, log2_bits=13) -> bytes:
+    """the filter frame of delimited text cut into frames of frame_sizes bytes (zsmi_buildFrameFilter, host only): a Bloom filter of
+    2^log2_bits bits (9 .. 16) a frame over the frame's folded grams of `gram` bytes (3 or 4); a frame that shares a record with another is
+    saturated - all ones.  filter_frames asks it which frames can hold a query's records; keep it beside the archive."""
+    L = _lib.lib()
+    s, n = _buf(data)
+    sizes = np.ascontiguousarray(frame_sizes, dtype=np.uint32)
+    cap = _raise_if_error(L, L.zsmi_frameFilterSize(len(sizes), log2_bits))
+    out = ctypes.create_string_buffer(cap)
+    size = _raise_if_error(L, L.zsmi_buildFrameFilter(out, cap, s, n, ctypes.c_void_p(sizes.ctypes.data) if len(sizes) else None, len(sizes), _delimiter(delimiter),
+                                                      gram, log2_bits))
+    return out.raw[:size]
+
+
+def read_frame_filter(frame):
+    """what a filter frame says of itself (zsmi_readFrameFilter, host only; magic, version, fields, size and check are judged):
+    {"frames", "delimiter" (one byte), "gram", "log2_bits", "size" (the content's), "saturated" (the slots that are all ones)};
+    RuntimeError with the error's name for bytes that are no such frame, or a damaged one"""
+    L = _lib.lib()
+    s, size = _buf(frame)
+    info = _lib.FrameFilterInfo()
+    rc = L.zsmi_readFrameFilter(s, size, ctypes.byref(info))
+    if rc:
+        raise RuntimeError(_error_name(L, rc))
+    return {"frames": int(info.nFrames), "delimiter": bytes([info.delim]), "gram": int(info.gram), "log2_bits": int(info.log2Bits), "size": int(info.size),
+            "saturated": int(info.saturated)}
+
+
+def filter_frames(frame_filter, patterns, mode="any", ignore_case=False, first_frame=0, frame_count=None, return_info=False):
+    """the frames of [first_frame, first_frame + frame_count) (None: to the filter's end) that can hold a record satisfying the query
+    (find_records_query's patterns, mode, ignore_case), by the filter alone: the ascending list of their numbers - never a frame too few;
+    a pattern shorter than the filter's gram, and mode 'none', pass every frame (zsmi_filterFrames, host only).  With return_info (list,
+    {"tested", "saturated"}): the frames tested and the saturated ones among the list."""
+    L = _lib.lib()
+    s, size = _buf(frame_filter)
+    q, keep = _find_query(patterns, mode, ignore_case)
+    if frame_count is None:
+        frame_count = max(read_frame_filter(frame_filter)["frames"] - first_frame, 0)
+    result = np.zeros(4, dtype=np.uint64)
+    out = np.zeros(max(frame_count, 1), dtype=np.uint32)
+    rc = L.zsmi_filterFrames(s, size, ctypes.byref(q), first_frame, frame_count, ctypes.c_void_p(out.ctypes.data), frame_count, ctypes.c_void_p(result.ctypes.data))
+    if rc:
+        raise RuntimeError(_error_name(L, rc))
+    frames = [int(v) for v in out[:int(result[1])]]
+    return (frames, {"tested": int(result[2]), "saturated": int(result[3])}) if return_info else frames
+
+
 def find_records(data, pattern, delimiter=b"\n", base=0):
     """the records of delimited text that hold `pattern`, a literal byte string of 1 .. 256 bytes without the delimiter (zsmi_findRecords,
     host only): the list of their numbers, ascending - base + the delimiters in front of an occurrence.  Overlapping occurrences all
@@ -529,7 +582,7 @@ class SeekableArchive:
         if ddict is not None and ddict_set is not None:
             raise ValueError("ddict_set= excludes ddict=")
         self.L = _lib.lib()
-        self.codec = self.handle = self._own_set = self._index = None
+        self.codec = self.handle = self._own_set = self._index = self._filter_key = self._filter_ref = None
         self.ddict, self.ddict_set = ddict, ddict_set
         self.archive = bytes(archive)
         self.frames = bool(frames)
@@ -683,23 +736,59 @@ class SeekableArchive:
                 return []
         return [int(v) for v in out[:int(result[1])]]
 
-    def find_records_query(self, first_record, patterns, mode="any", ignore_case=False, delimiter=b"\n", first_frame=0, frame_count=None, return_hits=False):
+    def build_frame_filter(self, delimiter=b"\n", gram=4, log2_bits=13) -> bytes:
+        """the archive's filter frame (build_frame_filter states it), built on the GPU from one decode of the archive in windows of at
+        most 256 MiB of content (zsmi_seekableBuildFrameFilterHost): bytes to keep beside the archive and hand to
+        find_records_query(frame_filter=...).  A frame that fails raises RuntimeError with the error's name."""
+        self._open()
+        cap = frame_filter_size(self.num_frames, log2_bits)
+        out = np.zeros(cap, dtype=np.uint8)
+        result = np.zeros(4, dtype=np.uint64)
+        p = BatchCodec._p
+        rc = self.L.zsmi_seekableBuildFrameFilterHost(self.codec.ctx, self.handle, _delimiter(delimiter), gram, log2_bits, p(out), cap, p(result))
+        if rc or int(result[0]):
+            raise RuntimeError(_error_name(self.L, rc or int(result[0])))
+        return out[:int(result[1])].tobytes()
+
+    def _filter_frames(self, frame_filter, patterns, mode, ignore_case, delimiter, first_frame, count):
+        """the window's frames that pass the filter (uint32, ascending).  The filter is judged - check word included - once an object and
+        filter, not once a search"""
+        key = (id(frame_filter), len(frame_filter))
+        if self._filter_key != key:
+            info = read_frame_filter(frame_filter)
+            if (info["frames"], info["size"], info["delimiter"][0]) != (self.num_frames, self.content_size, _delimiter(delimiter)):
+                raise ValueError("the frame filter was built for another archive or delimiter")
+            self._filter_key, self._filter_ref = key, frame_filter         # (the reference keeps the id the filter's)
+        return np.asarray(filter_frames(frame_filter, patterns, mode, ignore_case, first_frame, count), dtype=np.uint32)
+
+    def find_records_query(self, first_record, patterns, mode="any", ignore_case=False, delimiter=b"\n", first_frame=0, frame_count=None, return_hits=False,
+                           frame_filter=None):
         """find_records for a query of 1 .. 8 patterns: the records of the window that hold any of them, all of them or none (mode), with
         or without ASCII case folding, after ONE decode of the window (find_records_query states the rule; the window as in find_records).
-        The list of their numbers, ascending; with return_hits (numbers, hits).  zsmi_seekableFindQueryHost"""
+        The list of their numbers, ascending; with return_hits (numbers, hits).  zsmi_seekableFindQueryHost
+        frame_filter: the archive's filter frame (build_frame_filter) - the filter is asked first and only the frames that pass are
+        decoded and searched, in one call (zsmi_seekableFindQueryFramesHost); the answer is exactly the one without it (a list the
+        filter writes never separates a record's frames).  Mode 'none', which no filter can help, takes the window search."""
         self._open()
         first = np.ascontiguousarray(first_record, dtype=np.uint64)
         q, keep = _find_query(patterns, mode, ignore_case)
         d = _delimiter(delimiter)
         count = self.num_frames - first_frame if frame_count is None else frame_count
         p = BatchCodec._p
+        frames = None
+        if frame_filter is not None and mode != "none":
+            frames = self._filter_frames(frame_filter, patterns, mode, ignore_case, delimiter, first_frame, count)
         result = np.zeros(4, dtype=np.uint64)
         out = np.zeros(1, dtype=np.uint64); hits = np.zeros(1, dtype=np.uint8)
         for cap in (0, None):
             cap = int(result[0]) if cap is None else cap
             out = np.zeros(max(cap, 1), dtype=np.uint64); hits = np.zeros(max(cap, 1), dtype=np.uint8)
-            rc = self.L.zsmi_seekableFindQueryHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(q), first_frame, count,
-                                                   p(out) if cap else None, p(hits) if cap else None, cap, p(result))
+            if frames is not None:
+                rc = self.L.zsmi_seekableFindQueryFramesHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(q),
+                                                             p(frames) if len(frames) else None, len(frames), p(out) if cap else None, p(hits) if cap else None, cap, p(result))
+            else:
+                rc = self.L.zsmi_seekableFindQueryHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(q), first_frame, count,
+                                                       p(out) if cap else None, p(hits) if cap else None, cap, p(result))
             if rc:
                 raise RuntimeError(_error_name(self.L, rc))
             if int(result[0]) > (1 << 64) - ERROR_MAX_CODE:
@@ -1003,6 +1092,38 @@ class SeekableHandle:
                                                       p(d_first_record_ptr), p(d_result_ptr))
         if rc:
             raise RuntimeError(f"zsmi_seekableIndexRecordsResident: {_error_name(self.L, rc)}")
+
+    def find_frames_work_bound(self, max_frames) -> int:
+        """the d_work bytes that hold any list of max_frames frames for find_query_frames_resident: max_frames x (the largest frame's
+        content + 1) (zsmi_seekableFindFramesWorkBound)"""
+        return int(self.L.zsmi_seekableFindFramesWorkBound(self.handle, max_frames))
+
+    def find_query_frames_resident(self, d_first_record_ptr, n_frames, patterns, d_frames_ptr, d_frame_count_ptr, max_frames, d_work_ptr, work_capacity,
+                                   d_records_ptr, d_hits_ptr, capacity, d_result_ptr, mode="any", ignore_case=False, delimiter=b"\n", codec=None):
+        """find_query_resident over a LIST of frames in device memory: d_frames (uint32[max_frames], ascending) and d_frame_count (one
+        uint64: d_result of filter_frames_device can be passed as it is) - only those frames are decoded into d_work
+        (find_frames_work_bound(max_frames) bytes always suffice) and searched; d_records, d_hits as find_query_resident, d_result
+        (uint64[4]) = {total or (uint64)-code, written, occurrences, content bytes decoded}; a refusal leaves the bytes needed in
+        d_result[3].  Mode 'none' is refused.  Nothing goes to the host.  zsmi_seekableFindQueryFramesResident"""
+        codec = codec or self.codec
+        p = ctypes.c_void_p
+        q, keep = _find_query(patterns, mode, ignore_case)
+        rc = self.L.zsmi_seekableFindQueryFramesResident(codec.ctx, self.handle, p(d_first_record_ptr), n_frames, _delimiter(delimiter), ctypes.byref(q), p(d_frames_ptr),
+                                                         p(d_frame_count_ptr), max_frames, p(d_work_ptr), work_capacity, p(d_records_ptr), p(d_hits_ptr), capacity, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableFindQueryFramesResident: {_error_name(self.L, rc)}")
+
+    def build_frame_filter_resident(self, d_work_ptr, work_capacity, d_filter_ptr, capacity, d_result_ptr, delimiter=b"\n", gram=4, log2_bits=13, codec=None):
+        """the archive's filter frame (build_frame_filter states it) into d_filter (8-byte aligned, frame_filter_size(num_frames,
+        log2_bits) bytes): the frames are decoded end to end into d_work (find_work_bound(0, num_frames) bytes) and hashed there.
+        d_result (uint64[4]) = {the first failing frame's code, bytes written, saturated frames, grams hashed}.  Nothing goes to the
+        host.  zsmi_seekableBuildFrameFilterResident"""
+        codec = codec or self.codec
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_seekableBuildFrameFilterResident(codec.ctx, self.handle, _delimiter(delimiter), gram, log2_bits, p(d_work_ptr), work_capacity,
+                                                          p(d_filter_ptr), capacity, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_seekableBuildFrameFilterResident: {_error_name(self.L, rc)}")
 
     def frame_info(self, index):
         """(compressed offset, content offset, compressed size, content size) of frame `index`, from the handle's table"""
@@ -1390,6 +1511,35 @@ class BatchCodec:
         if rc:
             raise RuntimeError(f"zsmi_seekableAttachRecordIndexResident: {_error_name(self.L, rc)}")
 
+    def build_frame_filter_device(self, d_text_ptr, size, d_places_ptr, n, d_filter_ptr, capacity, d_result_ptr, delimiter=b"\n", gram=4, log2_bits=13):
+        """build_frame_filter on the device, text and frame borders in device memory (asynchronous: only queued): d_places (uint64[n + 1],
+        ascending, 0 first, size last) are the frames' borders in d_text[0, size); d_filter (8-byte aligned, frame_filter_size(n,
+        log2_bits) bytes) receives the complete frame, byte for byte the host call's; d_result (uint64[4]) the status, the bytes written,
+        the saturated frames and the grams hashed.  zsmi_buildFrameFilterDevice"""
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_buildFrameFilterDevice(self.ctx, p(d_text_ptr), size, p(d_places_ptr), n, _delimiter(delimiter), gram, log2_bits, p(d_filter_ptr), capacity,
+                                                p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_buildFrameFilterDevice: {_error_name(self.L, rc)}")
+
+    def check_frame_filter_device(self, d_filter_ptr, filter_size, d_result_ptr):
+        """read_frame_filter's judgement of a filter frame in device memory, check word included (asynchronous: only queued): d_result
+        (uint64[8]) = {status, frames, delimiter, gram, log2_bits, the content's size, saturated frames, 0}.  zsmi_checkFrameFilterDevice"""
+        p = ctypes.c_void_p
+        rc = self.L.zsmi_checkFrameFilterDevice(self.ctx, p(d_filter_ptr), filter_size, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_checkFrameFilterDevice: {_error_name(self.L, rc)}")
+
+    def filter_frames_device(self, d_filter_ptr, filter_size, patterns, first_frame, frame_count, d_frames_ptr, capacity, d_result_ptr, mode="any", ignore_case=False):
+        """filter_frames on a filter frame in device memory (asynchronous: only queued): d_frames (uint32[capacity]) receives the ascending
+        numbers of the frames of the window that pass the query, d_result (uint64[4]) = {total or (uint64)-code, written, frames tested,
+        saturated frames among the total}.  zsmi_filterFramesDevice"""
+        p = ctypes.c_void_p
+        q, keep = _find_query(patterns, mode, ignore_case)
+        rc = self.L.zsmi_filterFramesDevice(self.ctx, p(d_filter_ptr), filter_size, ctypes.byref(q), first_frame, frame_count, p(d_frames_ptr), capacity, p(d_result_ptr))
+        if rc:
+            raise RuntimeError(f"zsmi_filterFramesDevice: {_error_name(self.L, rc)}")
+
     def open_seekable_device(self, d_ptr, size, ddict=None, ddict_set=None):
         """the archive at d_ptr[0, size) (device memory, borrowed: it must outlive the handle) opened for reads: a SeekableHandle.  The
         table is read back and checked here, once (RuntimeError with the error's name).  ddict_set: a DecompressionDictSet its reads
@@ -1462,8 +1612,8 @@ class BatchCodec:
         return out.raw[:size.value], p.k, p.d
 
     def kernel_times(self):
-        out = (_lib.KernelTime * 16)()
-        k = self.L.zsmi_getKernelTimes(self.ctx, out, 16)
+        out = (_lib.KernelTime * 64)()                                     # (a list search names more than 16 kernels)
+        k = self.L.zsmi_getKernelTimes(self.ctx, out, 64)
         return {out[i].name.decode(): (out[i].seconds, out[i].launches) for i in range(k)}
 
     def enable_timing(self, on=True):

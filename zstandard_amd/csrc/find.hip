@@ -368,7 +368,7 @@ static int findCheck(const zsmi_ctx *c, const zsmi_seekable *sk, const void *fir
 // The decode half of a search on an archive, shared by the single-pattern search below and the query search of findquery.hip (context
 // bound, frameCount > 0, arguments checked by the caller): the scratch of the whole call reserved, then the window's frames into dWork, end
 // to end, verified, and the first failing frame's code in a device word.  Leaves the text's size, its tiles and that word
-struct FindDecoded { uint64_t bytes; FindTiles t; const uint32_t *dCode; };
+struct FindDecoded { uint64_t bytes; FindTiles t; const uint32_t *dCode; const uint64_t *dListAt; };      // dListAt: the frames' places in dWork [frameCount + 1]
 // device words, a frame of the window, in front of the tiles' (findDecode lays them out; a caller that reserves more scratch behind the
 // tiles' words sizes it with this): 64 bits - sizes [F], places in dWork [F + 1]; verify records [F]; 32 bits - the list, decoder status,
 // refusals, written, codes [F each], the window's code [1, padded to 8 bytes]
@@ -397,7 +397,7 @@ static int findDecode(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame,
     LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((frameCount + 15) / 16), dim3(64), 0, (const ZsSeekItem *)dVerify, frameCount, (const uint32_t *)dSt,
            sk->t.checksum ? 1 : 0, dCodes, (const uint32_t *)dRefused);
     LAUNCH(c, "k_find_code", k_find_code, dim3(1), dim3(1024), 0, (const uint32_t *)dCodes, frameCount, dCode);
-    w.bytes = bytes; w.dCode = dCode;
+    w.bytes = bytes; w.dCode = dCode; w.dListAt = dListAt;
     return 0;
 }
 // the launch sequence on an archive, its arguments checked by the caller: the decode half, then findText

@@ -408,7 +408,7 @@ static int recidxWindow(zsmi_ctx *c, const zsmi_seekable *sk, int delim, uint32_
     RecidxTiles t;
     if (const int e = recidxLay(w.bytes, (uint8_t *)c->seek.dMeta.p + head, t)) return e;
     static_assert(3 * sizeof(uint64_t) >= 2 * sizeof(uint64_t) + 2 * sizeof(uint32_t), "what findReserve lays behind the head for a text of no tiles holds the body's one tile");
-    const uint64_t *dPlaces = (const uint64_t *)c->seek.dMeta.p + frameCount;          // findDecode's dListAt: [frameCount + 1] behind the sizes
+    const uint64_t *dPlaces = w.dListAt;
     const int atEnd = sk->t.dOff[(size_t)firstFrame + frameCount] == sk->t.dOff[sk->t.n];
     return recidxText(c, dWork, w.bytes, dPlaces, frameCount, delim, atEnd, firstFrame ? dFirstRecord + firstFrame : nullptr, w.dCode, dFirstRecord + firstFrame, dResult, t);
 }

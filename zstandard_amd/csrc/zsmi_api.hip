@@ -24,6 +24,8 @@
 #include "findquery.hip"          // feature: find records by several patterns - any, all, none of up to 8 patterns, ASCII case folding -> ascending record numbers and hit sets (kernels and host; the rule: zsmi_findquery.h)
 #include "findregex.hip"          // feature: find records by regular expression - a pattern compiled on the host into a minimal DFA, a state function carried across lanes, wavefronts and tiles -> ascending record numbers (kernels and host; the rule and the compiler: zsmi_regex.h)
 #include "recindex.hip"           // feature: the record index of an archive - firstRecord rebuilt from text and frame borders, stored in the archive as a skippable frame, loaded from it (kernels and host; the rule and the frame: zsmi_recindex.h)
+#include "filter.hip"             // feature: frame filters - an n-gram Bloom filter a frame of a record archive, built from text, judged, and asked which frames can hold a query's records before any is decoded (kernels and host; the rule and the frame: zsmi_filter.h)
+#include "findframes.hip"         // feature: the query search over a list of frames in device memory - what the filter call leaves goes straight into a search that decodes those frames and no others (kernels and host; the rule: its head)
 
 #include <cstdio>
 #include <cstdlib>
