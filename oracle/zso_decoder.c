@@ -41,6 +41,15 @@ static uint32_t g_stats[40];   /* [30] sequences [31] literals [32] literal-sect
 void zso_statsReset(void) { memset(g_stats, 0, sizeof g_stats); }
 void zso_statsGet(uint32_t *out) { memcpy(out, g_stats, 32 * sizeof(uint32_t)); }
 void zso_statsGet40(uint32_t *out) { memcpy(out, g_stats, sizeof g_stats); }
+/* the dictionary trainer's 448 counters (zso_trainStats in zso_encoder.c counts the same on the encoder's side) of every compressed block
+ * THIS THREAD decodes between zso_trainStatsReset, which arms them, and zso_trainStatsGet, which reads them and disarms: regenerated
+ * literal bytes [0, 256), LL codes [256, 320), OF codes [320, 384), ML codes [384, 448).  Unarmed - every other thread, the batch drivers'
+ * workers among them, and this one outside such a pair - a decode reads the thread-local pointer once a block and tests its copy once a
+ * sequence. */
+static __thread uint32_t t_trainStatsBuf[448];
+static __thread uint32_t *t_trainStats;
+void zso_trainStatsReset(void) { memset(t_trainStatsBuf, 0, sizeof t_trainStatsBuf); t_trainStats = t_trainStatsBuf; }
+void zso_trainStatsGet(uint32_t *out448) { memcpy(out448, t_trainStatsBuf, sizeof t_trainStatsBuf); t_trainStats = NULL; }
 #define STAT(i) (g_stats[i]++)
 
 /* ---- error ABI : ZStdErrors.cs:61-100 ---------------------------------- */
@@ -799,6 +808,7 @@ typedef struct {
     const BYTE *dictContent; size_t dictContentSize; U32 dictIDLoaded;   /* what decompress_insertDictionary left for the frame */
     /* frame params */
     U64 frameContentSize, windowSize; U32 checksumFlag, dictID, headerSize;
+    U32 *trainStats;                /* the trainer's counters if this thread armed them (read once a block), else NULL */
 } DCtx;
 
 /* ZStdDecompress.cs:1040-1079 */
@@ -973,7 +983,7 @@ static size_t decodeLiteralsBlock(DCtx *d, const void *src, size_t srcSize)
  *  ZStdDecompress.cs:1443-1553 : sequence decode (regular offsets, 32-bit mode)
  * ======================================================================= */
 typedef struct { U32 state; const SeqSymbol *table; } FseState;
-typedef struct { BIT_D DStream; FseState stateLL, stateOffb, stateML; U32 prevOffset[3]; } SeqState;
+typedef struct { BIT_D DStream; FseState stateLL, stateOffb, stateML; U32 prevOffset[3]; U32 *trainStats; } SeqState;
 typedef struct { U32 litLength, matchLength, offset; } Seq;
 
 static void initFseState(FseState *s, BIT_D *b, const SeqTable *dt)              /* :1443-1452 */
@@ -991,6 +1001,14 @@ static Seq decodeSequence(SeqState *st, int longOffsets)
     U32 const llBase = st->stateLL.table[st->stateLL.state].baseValue;
     U32 const mlBase = st->stateML.table[st->stateML.state].baseValue;
     U32 const ofBase = st->stateOffb.table[st->stateOffb.state].baseValue;
+    if (st->trainStats) {   /* the codes behind the cells: base values are distinct within LL and within ML; an offset code is its number of extra bits */
+        U32 c;
+        for (c = 0; c < MaxLL && LL_base[c] != llBase; c++) {}
+        st->trainStats[256 + c]++;
+        for (c = 0; c < MaxML && ML_base[c] != mlBase; c++) {}
+        st->trainStats[384 + c]++;
+        st->trainStats[320 + ofBits]++;
+    }
     {
         U32 offset;
         if (!ofBits) offset = 0;
@@ -1070,6 +1088,7 @@ static size_t decompressSequences(DCtx *d, void *dst, size_t maxDstSize, const v
     if (nbSeq) {
         SeqState st;
         U32 i;
+        st.trainStats = d->trainStats;
         d->fseEntropy = 1;
         for (i = 0; i < 3; i++) st.prevOffset[i] = d->rep[i];
         { size_t const e = BIT_init(&st.DStream, ip, seqSize); if (zso_isError(e)) return ERR(ZSO_corruption_detected); }
@@ -1102,9 +1121,11 @@ static size_t decompressSequences(DCtx *d, void *dst, size_t maxDstSize, const v
 static size_t decompressBlock_internal(DCtx *d, void *dst, size_t dstCapacity, const void *src, size_t srcSize)
 {
     const BYTE *ip = (const BYTE *)src;
+    d->trainStats = t_trainStats;
     if (srcSize >= ZSTD_BLOCKSIZE_MAX) return ERR(ZSO_srcSize_wrong);
     { size_t const litCSize = decodeLiteralsBlock(d, src, srcSize); if (zso_isError(litCSize)) return litCSize; ip += litCSize; srcSize -= litCSize;
-      g_stats[32] += (U32)litCSize; g_stats[31] += (U32)d->litSize; }
+      g_stats[32] += (U32)litCSize; g_stats[31] += (U32)d->litSize;
+      if (d->trainStats) { size_t i; for (i = 0; i < d->litSize; i++) d->trainStats[d->litPtr[i]]++; } }
     {
         int nbSeq = 0;
         size_t const seqHSize = decodeSeqHeaders(d, &nbSeq, ip, srcSize);

@@ -701,13 +701,13 @@ static size_t compressBlock(Work *w, BYTE *dst, size_t cap, const BYTE *src, U32
 
 /* stages 3b-6 for one block whose sequences (w->seqs) and literals (w->lits) are in place */
 U32 g_lastNseq;   /* development aid (tools/lab): sequences of the last block encoded */
-static size_t encodeParsed(Work *w, BYTE *dst, size_t cap, U32 nseq, U32 nlit, const U32 *firstRep)
+/* stage 3b: offsets -> offset field values through the 3-entry recent-offset list
+ * (inverse of ZStdDecompress.cs:1509-1530).  A chunk's first block starts from {1, 4, 8}, or from a dictionary's
+ * recent offsets; blocks after the first start from an unknown history: sentinels that never equal a real offset (< 131072).
+ * Leaves w->ofValue and the LL / OF / ML codes of the block's sequences: what the entropy stage (and the trainer's statistics) take. */
+static void codeSequences(Work *w, U32 nseq, const U32 *firstRep)
 {
-    g_lastNseq = nseq;
     {
-        /* stage 3b: offsets -> offset field values through the 3-entry recent-offset list
-         * (inverse of ZStdDecompress.cs:1509-1530).  A chunk's first block starts from {1, 4, 8}, or from a dictionary's
-         * recent offsets; blocks after the first start from an unknown history: sentinels that never equal a real offset (< 131072). */
         U32 rep[3];
         U32 i;
         if (firstRep) { rep[0] = firstRep[0]; rep[1] = firstRep[1]; rep[2] = firstRep[2]; } else { rep[0] = 0xFFFFFFF1u; rep[1] = 0xFFFFFFF2u; rep[2] = 0xFFFFFFF3u; }
@@ -730,6 +730,11 @@ static size_t encodeParsed(Work *w, BYTE *dst, size_t cap, U32 nseq, U32 nlit, c
             w->mlCode[i] = (BYTE)mlCodeOf(w->seqs[i].matchLength - 3);
         }
     }
+}
+static size_t encodeParsed(Work *w, BYTE *dst, size_t cap, U32 nseq, U32 nlit, const U32 *firstRep)
+{
+    g_lastNseq = nseq;
+    codeSequences(w, nseq, firstRep);
     {
         BYTE *op = dst;
         BYTE *const oend = dst + cap;
@@ -829,6 +834,27 @@ size_t zso_compressBound(size_t srcSize)
  * A dictionary gives the frame (zso_compress_usingDict, zso_batch.c): pre[0 .. pfx), the content's last pfx <= 64 KiB bytes, as the prefix of
  * a chunk of <= 64 KiB; the ID for the header (none if 0); the first block's recent offsets.  Without one: pfx 0, ID 0, rep NULL ({1, 4, 8}). */
 static const U32 kRepStart[3] = { 1, 4, 8 };
+
+/* The dictionary trainer's statistics (zso_trainStats below; the rule of k_train_stats): 448 counters - literal bytes [0, 256), LL codes
+ * [256, 320), OF codes [320, 384), ML codes [384, 448) - of what a block's parse hands to the entropy stage, whatever type the block ends
+ * as (raw, RLE or compressed).  Every block of >= 16 bytes is parsed, one of all one byte too (the frame writer below would not), with
+ * what the GPU's LZ stage leaves unparsed left out: a matchless unit's blocks have no sequences; nor has a UNIT (not a block) that is one
+ * repeated byte and a multiple of 16 bytes long, which k_lz_candidates and k_lz_walk skip - all its bytes are literals; a ragged unit of one
+ * byte is walked as any other.  A block under 16 bytes is all literals. */
+#define TRAIN_STATS 448
+static __thread U32 *t_trainStats;            /* where zso_compressFrame counts; NULL outside zso_trainStats */
+static void trainCount(Work *w, U32 *stats, const BYTE *src, U32 unitN, U32 blockOff, U32 n, const EParams *prm, U32 pfx, const U32 *firstRep)
+{
+    U32 i, nseq, nlit = 0;
+    int uniform = unitN >= 16 && (unitN & 15u) == 0;
+    for (i = 1; i < unitN && uniform; i++) uniform = src[i] == src[0];
+    if (n < 16 || uniform) { for (i = 0; i < n; i++) stats[src[blockOff + i]]++; return; }
+    nseq = parseBlock(w, src, unitN, blockOff, n, prm, pfx, &nlit);
+    codeSequences(w, nseq, firstRep);
+    for (i = 0; i < nlit; i++) stats[w->lits[i]]++;
+    for (i = 0; i < nseq; i++) { stats[256 + w->llCode[i]]++; stats[320 + w->ofCode[i]]++; stats[384 + w->mlCode[i]]++; }
+}
+
 size_t zso_compressFrame(void *dstv, size_t dstCapacity, const void *srcv, size_t srcSize, int level,
                          const void *pre, uint32_t pfxSize, uint32_t dictID, const uint32_t *rep)
 {
@@ -867,6 +893,7 @@ size_t zso_compressFrame(void *dstv, size_t dstCapacity, const void *srcv, size_
         size_t const unitPos = pos & ~(size_t)(UNIT_MAX - 1);             /* units are cut every 128 KiB of the chunk */
         U32 const unitN = (U32)((srcSize - unitPos < UNIT_MAX) ? srcSize - unitPos : UNIT_MAX);
         if (pos == unitPos && n) findCandidates(w, src + unitPos, unitN, &prm, pfx);
+        if (t_trainStats) trainCount(w, t_trainStats, src + unitPos, unitN, (U32)(pos - unitPos), n, &prm, pfx, pos == 0 ? (rep ? rep : kRepStart) : NULL);
         size_t csize = 0;
         U32 i, same = n > 0;
         if ((size_t)(oend - op) < 3 + 1) return ERR(ZSO_dstSize_tooSmall);
@@ -892,6 +919,102 @@ size_t zso_compressFrame(void *dstv, size_t dstCapacity, const void *srcv, size_
 size_t zso_compress(void *dst, size_t dstCapacity, const void *src, size_t srcSize, int level)
 {
     return zso_compressFrame(dst, dstCapacity, src, srcSize, level, NULL, 0, 0, NULL);
+}
+
+/* ======================================================================= *
+ *  dictionary finalize (the scalar statement of zsmi_finalizeDictionary: k_train_stats, k_train_id, k_train_tables)
+ * ======================================================================= */
+/* the 448 counters over the samples, each compressed as one frame with the content as a raw dictionary (its last <= 64 KiB the prefix of
+ * samples of <= 64 KiB, recent offsets {1, 4, 8}) */
+size_t zso_trainStats(uint32_t *stats, const void *content, size_t contentSize, const void *samples, const size_t *sizes, unsigned n, int level)
+{
+    const BYTE *sp = (const BYTE *)samples;
+    U32 const pfx = (U32)(contentSize < BLOCK_MAX ? contentSize : BLOCK_MAX);
+    const BYTE *const pre = (const BYTE *)content + contentSize - pfx;
+    size_t maxSize = 0, r = 0;
+    unsigned i;
+    BYTE *tmp;
+    memset(stats, 0, TRAIN_STATS * sizeof(U32));
+    for (i = 0; i < n; i++) if (sizes[i] > maxSize) maxSize = sizes[i];
+    tmp = (BYTE *)malloc(zso_compressBound(maxSize));
+    if (!tmp) return ERR(ZSO_memory_allocation);
+    t_trainStats = stats;
+    for (i = 0; i < n && !zso_isError(r); i++) {
+        r = zso_compressFrame(tmp, zso_compressBound(maxSize), sp, sizes[i], level, pre, pfx, 0, NULL);
+        sp += sizes[i];
+    }
+    t_trainStats = NULL;
+    free(tmp);
+    return zso_isError(r) ? r : 0;
+}
+
+/* counts + 1 (every symbol representable), halved until their sum is below `limit`, never below 1; returns the sum */
+static U32 trainScaled(const U32 *raw, U32 n, U32 *out, U64 limit)
+{
+    U64 total = 0;
+    U32 s, shift = 0, sum = 0;
+    for (s = 0; s < n; s++) total += (U64)raw[s] + 1;
+    while ((total >> shift) >= limit) shift++;
+    for (s = 0; s < n; s++) { U32 const v = (U32)(((U64)raw[s] + 1) >> shift); out[s] = v ? v : 1; sum += out[s]; }
+    return sum;
+}
+/* the Huffman description of the counters' literals at one maxBits, into dst[0, 256): its size, 0 if it takes more than 127 bytes.
+ * (Exported for the tests: which maxBits the finalize below settles on.) */
+size_t zso_trainHuffDescription(void *dst, const uint32_t *stats, unsigned maxBits)
+{
+    U32 count[256];
+    BYTE nbBits[256];
+    U32 tableLog;
+    trainScaled(stats, 256, count, 1u << 23);          /* (the GPU's package-merge keys are count << 8 | symbol) */
+    tableLog = huffLengths(nbBits, count, 255, maxBits);
+    return writeHuffHeader((BYTE *)dst, 256, nbBits, 255, tableLog);
+}
+
+/* magic, ID, entropy section (Huffman description of <= HUF_MAXBITS bits, flatter down to 8 until it fits; NCounts OF at log 8 over
+ * min(highbit(contentSize + 128 KiB), MaxOff) + 1 symbols, ML at log 9, LL at log 9), recent offsets {1, 4, 8}, then the content, cut at its
+ * front to fit cap.  Returns the dictionary's size; 0 if it cannot be made (the section needs more than 1 KiB or leaves no room for content);
+ * an error for arguments zsmi_finalizeDictionary refuses.  Nothing is written unless a size is returned. */
+size_t zso_finalizeDictionary(void *dst, size_t cap, const void *content, size_t contentSize, const void *samples, const size_t *sizes,
+                              unsigned n, int level, unsigned dictID)
+{
+    enum { HCAP = 1024 };
+    BYTE hdr[HCAP];
+    U32 stats[TRAIN_STATS], cnt[64];
+    S16 norm[64];
+    U64 total = 0;
+    U32 pos, t, maxBits, cap32;
+    size_t hs = 0, keep;
+    unsigned i;
+    if (cap < 256) return ERR(ZSO_dstSize_tooSmall);
+    if (!content || contentSize < 128 || contentSize > 0xFFFFFFFFull - (128u << 10) || n == 0) return ERR(ZSO_srcSize_wrong);
+    for (i = 0; i < n; i++) total += sizes[i];
+    if (total >= (1ull << 32)) return ERR(ZSO_srcSize_wrong);
+    cap32 = (U32)(cap < 0xFFFFFFFFu - 4096 ? cap : 0xFFFFFFFFu - 4096);
+    { size_t const e = zso_trainStats(stats, content, contentSize, samples, sizes, n, level ? level : 3); if (zso_isError(e)) return e; }
+    memset(hdr, 0, sizeof hdr);
+    for (maxBits = HUF_MAXBITS; maxBits >= 8 && !hs; maxBits--) hs = zso_trainHuffDescription(hdr + 8, stats, maxBits);
+    if (!hs) return 0;
+    pos = 8 + (U32)hs;
+    for (t = 0; t < 3; t++) {
+        U32 const ofMax = highbit32((U32)contentSize + (128u << 10));
+        U32 const maxSym = t == 0 ? (ofMax < MaxOff ? ofMax : MaxOff) : (t == 1 ? MaxML : MaxLL);
+        U32 const log = t == 0 ? OffFSELog : (t == 1 ? MLFSELog : LLFSELog), base = t == 0 ? 320 : (t == 1 ? 384 : 256);
+        U32 const sum = trainScaled(stats + base, maxSym + 1, cnt, 1u << 30);
+        size_t w;
+        normalizeCounts(norm, log, cnt, sum, maxSym);
+        w = writeNCount(hdr + pos, HCAP - pos, norm, maxSym, log);
+        if (!w) return 0;
+        pos += (U32)w;
+    }
+    if (pos + 12 > HCAP || pos + 12 >= cap32) return 0;
+    wr32(hdr, 0xEC30A437u);
+    wr32(hdr + 4, dictID ? dictID : (U32)(zso_xxh64(content, contentSize, 0) % 2147450880ull) + 32768u);
+    wr32(hdr + pos, 1); wr32(hdr + pos + 4, 4); wr32(hdr + pos + 8, 8);
+    pos += 12;
+    keep = contentSize < cap32 - pos ? contentSize : cap32 - pos;
+    memcpy(dst, hdr, pos);
+    memcpy((BYTE *)dst + pos, (const BYTE *)content + (contentSize - keep), keep);
+    return pos + keep;
 }
 
 /* ---- test hooks: intermediate results of stages 1 and 2 for one LZ unit (n <= 131072), so the HIP

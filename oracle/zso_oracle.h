@@ -32,6 +32,10 @@ unsigned zso_errorCode(size_t code);
 uint64_t zso_xxh64(const void *input, size_t len, uint64_t seed);
 void zso_statsReset(void);
 void zso_statsGet(uint32_t *out32);   /* 32 counters, see zso_decoder.c */
+/* the dictionary trainer's 448 counters of the compressed blocks the calling thread decodes between the reset (which arms them) and the get
+ * (which disarms them): literal bytes, LL, OF, ML codes (64 slots each).  Other threads' decodes, the batch drivers' among them, are not counted */
+void zso_trainStatsReset(void);
+void zso_trainStatsGet(uint32_t *out448);
 
 /* oracle E : scalar CPU statement of this repo's block encoder (the algorithm the HIP kernels run) */
 size_t zso_compressBound(size_t srcSize);
@@ -43,6 +47,12 @@ size_t zso_compressFrame(void *dst, size_t dstCapacity, const void *src, size_t 
 /* with a dictionary (what zsmi_compress_usingDict does): raw-content or formatted; NULL / 0 bytes = zso_compress.
  * A dictionary oracle D refuses gives dictionary_corrupted (30). */
 size_t zso_compress_usingDict(void *dst, size_t dstCapacity, const void *src, size_t srcSize, const void *dict, size_t dictSize, int level);
+/* dictionary finalize, the scalar statement of zsmi_finalizeDictionary (zso_encoder.c).  zso_trainStats: the 448 counters over the samples
+ * compressed with the content as a raw dictionary.  zso_finalizeDictionary: the dictionary's size, 0 if it cannot be made, or an error. */
+size_t zso_trainStats(uint32_t *stats448, const void *content, size_t contentSize, const void *samples, const size_t *sizes, unsigned n, int level);
+size_t zso_trainHuffDescription(void *dst256, const uint32_t *stats448, unsigned maxBits);
+size_t zso_finalizeDictionary(void *dst, size_t cap, const void *content, size_t contentSize, const void *samples, const size_t *sizes,
+                              unsigned n, int level, unsigned dictID);
 /* oracle D's dictionary parse (insertDictionary): content offset, ID (0 for raw content), first block's recent offsets */
 size_t zso_dictParams(const void *dict, size_t dictSize, size_t *contentOff, uint32_t *dictID, uint32_t rep[3]);
 /* multi-threaded drivers used by bench.py's cpu_baseline leg and tests: n independent chunks */

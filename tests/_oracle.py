@@ -113,6 +113,69 @@ def decode_stats(frame: bytes, capacity: int):
     return out, st
 
 
+# ---- dictionary finalize: the trainer's 448 counters on both sides, and the scalar zso_finalizeDictionary ----
+TRAIN_STATS = 448
+
+
+def _flat(parts):
+    return b"".join(parts), (ctypes.c_size_t * len(parts))(*[len(p) for p in parts])
+
+
+def train_stats(content: bytes, parts, level=3):
+    """oracle E's counters over the samples with the content as a raw dictionary: literal bytes, LL, OF, ML codes (64 slots each)"""
+    L = lib()
+    L.zso_trainStats.restype = ctypes.c_size_t
+    L.zso_trainStats.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint, ctypes.c_int]
+    buf, sizes = _flat(parts)
+    st = np.zeros(TRAIN_STATS, dtype=np.uint32)
+    r = L.zso_trainStats(st.ctypes.data_as(ctypes.c_void_p), content, len(content), buf, sizes, len(parts), level)
+    if L.zso_isError(r):
+        raise OracleError(L.zso_errorCode(r))
+    return st
+
+
+def decode_train_stats(frames, caps, dictionary=b""):
+    """oracle D's counters of the frames' compressed blocks, and what it decoded.  The counters are armed on this thread for these decodes
+    only (zso_trainStatsReset arms, zso_trainStatsGet disarms): every other decode leaves them alone"""
+    L = lib()
+    L.zso_trainStatsGet.argtypes = [ctypes.c_void_p]
+    st = np.zeros(TRAIN_STATS, dtype=np.uint32)
+    L.zso_trainStatsReset()
+    try:
+        out = [decompress_using_dict(f, c, dictionary) if dictionary else decompress(f, c) for f, c in zip(frames, caps)]
+    finally:
+        L.zso_trainStatsGet(st.ctypes.data_as(ctypes.c_void_p))
+    return st, out
+
+
+def huff_description(stats, max_bits):
+    """the Huffman description zso_finalizeDictionary would write from the counters at one maxBits; b"" if it takes more than 127 bytes"""
+    L = lib()
+    L.zso_trainHuffDescription.restype = ctypes.c_size_t
+    L.zso_trainHuffDescription.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    st = np.ascontiguousarray(stats, dtype=np.uint32)
+    out = ctypes.create_string_buffer(256)
+    return out.raw[:L.zso_trainHuffDescription(out, st.ctypes.data_as(ctypes.c_void_p), max_bits)]
+
+
+def finalize_dictionary(content, parts, cap, level=3, dict_id=0):
+    """zso_finalizeDictionary: the dictionary; None where it answers 0 (it cannot be made); OracleError for refused arguments.  The
+    destination is checked to be untouched unless a dictionary comes back."""
+    L = lib()
+    L.zso_finalizeDictionary.restype = ctypes.c_size_t
+    L.zso_finalizeDictionary.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t),
+                                         ctypes.c_uint, ctypes.c_int, ctypes.c_uint]
+    buf, sizes = _flat(parts)
+    out = ctypes.create_string_buffer(b"\xAA" * cap, cap)
+    r = L.zso_finalizeDictionary(out, cap, content, len(content), buf, sizes, len(parts), level, dict_id)
+    if L.zso_isError(r) or r == 0:
+        assert out.raw == b"\xAA" * cap
+        if r:
+            raise OracleError(L.zso_errorCode(r))
+        return None
+    return out.raw[:r]
+
+
 def compress_batch(src: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, level=3, threads=1, dictionary=None):
     """src uint8 array; returns (arena, dst_offsets, dst_sizes).  dictionary: one for every chunk (zso_compressBatch_usingDict)"""
     L = lib()

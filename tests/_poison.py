@@ -978,10 +978,10 @@ def family_seekable():
 # ================================================================================================ family: dictionary training
 def family_training():
     """zsmi_trainFromDevice on the context: the `short_samples` case of tests/test_gpu_dict_train.py::test_content_equals_model.  The
-    dictionary's CONTENT is held against the scalar model (tests/c/train_model.c) byte for byte in every run.  Its header - the entropy
-    tables the finalize step counts from the samples compressed with that content - has no independent model: it is held to
-    check_format (magic, ID, oracle D's parse of the tables, the recent offsets) and to equality with the fresh-scratch run's.  That part
-    is the weaker one: a dependence that showed on fresh scratch already would pass it."""
+    dictionary's CONTENT is held against the scalar model (tests/c/train_model.c) byte for byte in every run, and the whole DICTIONARY -
+    the header with the entropy tables the finalize step counts from the samples compressed with that content - against the reference of a
+    training call (tests/_train.py: reference_train, which finalizes with the oracle's scalar zso_finalizeDictionary), byte for byte in
+    every run: a dependence on scratch that showed on fresh scratch already would fail it too."""
     import _batch as B, _train as T
     import test_gpu_dict_train as TD
     from _hip import hip_of
@@ -992,7 +992,7 @@ def family_training():
     parts = make()
     want = T.model_content(parts, cap, k, d, f)
     other = T.samples("json_records", 1 << 18)
-    fresh = []
+    ref = T.reference_train(parts, cap, k, d, f, 0, 1.0, 3)[0]
 
     def train(samples, prefill, cap, k, d, f):
         src_np, so, ss = B.batch(samples)
@@ -1014,9 +1014,7 @@ def family_training():
         content = TD.check_format(dic, cap)
         assert len(want) >= len(content) and want.endswith(content), (what, "the content is the scalar model's", len(want), len(content))
         assert len(content) == min(len(want), cap - (len(dic) - len(content))), what
-        if not fresh:
-            fresh.append(dic)
-        assert dic == fresh[0], (what, "the header differs from the fresh-scratch run's at", B.first_difference(dic, fresh[0]))
+        assert dic == ref, (what, "the dictionary differs from the reference's at", B.first_difference(dic, ref))
 
     hold(bc, Case("trainFromDevice, short samples", lambda prefill: train(parts, prefill, cap, k, d, f), check,
                   hostile=[lambda: train(other, CANARY, 65536, 200, 8, 20), lambda: compress_host(bc, [c for _, c in chunks()], CANARY, 3)],

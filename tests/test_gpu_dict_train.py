@@ -141,7 +141,7 @@ def test_round_trips(codec, cls):
 # finalize from this library's parse: libzstd's own parse of csv_records and binary_table takes more repeat-offset matches than this encoder's
 # (binary_table: offset code 0 is 108 / 256 of libzstd's OF table, 32 / 256 of ours), and the OF and ML tables follow the parse they were
 # counted from (tables spliced one at a time: OF 1.022x, ML 1.012x, LL 1.008x, Huffman 1.005x on binary_table).  Measured 1.0137x and 1.0462x.
-FINALIZE_BOUND = {"csv_records": 1.02, "binary_table": 1.05}
+FINALIZE_BOUND = T.FINALIZE_BOUND
 
 
 @pytest.mark.parametrize("cls", X.RECORD_CLASSES)

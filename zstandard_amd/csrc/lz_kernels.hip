@@ -660,7 +660,8 @@ k_lz_walk(const uint8_t *__restrict__ src, const ZsUnitDesc *__restrict__ units,
 #endif
     const uint32_t hashable = (n >= 8) ? n - 7 : 0;
     // A unit of one repeated byte becomes RLE blocks whatever the parse says (the literals kernel decides that from the bytes, as
-    // zso_encoder.c:833-836 does before parsing): its walk -- the slowest there is, every match running to the crossing limit -- is skipped.
+    // zso_compressFrame in oracle/zso_encoder.c does before parsing, and as trainCount there counts for the dictionary trainer: every byte of
+    // such a unit a literal): its walk -- the slowest there is, every match running to the crossing limit -- is skipped.
     if (mixed) *mixedWord = 1u;                                                   // (no __syncthreads_or: hipcc gives it static LDS of its own, which moves the dynamic part this kernel addresses by hand)
     __syncthreads();
     if (*mixedWord == 0) {
