@@ -664,11 +664,11 @@ def family_seekable():
     the table), open + a batch of ranges (slices of the source), a record archive of the caller's frame sizes written with a CDict set -
     host arrays and resident - and read back by frame number with a dictionary - host arrays and resident -, zsmi_openFramesDevice on a
     stream with skippable frames and on streams with a junk magic (tests/_frames_index.py), records by number with followers and a refused
-    request (tests/test_gpu_read_records.py's yardstick), find in a text across tile borders and in windows of an archive
+    request (tests/test_gpu_read_records.py's yardstick), find - literal and by regular expression - in a text across tile borders and in windows of an archive
     (tests/_find.py), and zsmi_splitRecordsDevice at targetSize 0 and 4096 with one record above maxFrameSize (tests/_split.py).  The
     last six go through the builders of those modules' own tests, under prefilled()."""
     import _seekable as S, _split as SP
-    import _find as FD, _frames_index as FI, _seekable_ranges as SRG, _seekable_resident as SR
+    import _find as FD, _findre as FR, _frames_index as FI, _seekable_ranges as SRG, _seekable_resident as SR
     import test_gpu_find_archive as TFA, test_gpu_frames_index as TFI, test_gpu_read_records as TRR
     from _hip import hip_of
     from zstandard_amd import BatchCodec
@@ -916,6 +916,24 @@ def family_seekable():
     hold(bc, Case("find in a text across tile borders", find_text,
                   lambda got, what: same([(0, repr(got).encode())], [(0, repr(([len(frecords), len(frecords), fmatches, size], frecords)).encode())], what),
                   hostile=[lambda: write(_noise(50000, 9), CANARY, 3, 4096, False), other], predicted={"seek": 3 * (tiles + 1) * 8 + 16 * tiles}), log)
+
+    # the regular-expression search over the same text: an occurrence of 17 bytes across the border of the first two tiles, the last
+    # record - listed - without a delimiter; behind the tiles' words, 16-aligned, 72 bytes a tile more (OUT functions, HEADMASKs)
+    rx = b"![0-Z]{16}"                                                    # ('!' and 16 of the pattern's other bytes: 18 states)
+    rrecords, rtext = FR.find(ftext, rx, 0, 10, 1000)
+    assert len(rrecords) == 4 and rrecords[-1] == 1000 + rtext - 1 and ftext[-1] != 10 and ftext[FD.TILE - 5] == 0x21
+    rprog = FR.program(L, rx)
+
+    def find_regex_text(prefill):
+        with prefilled(H, prefill):
+            d = FR.device(L, H, bc, ftext, rprog, len(rrecords), base=1000, capacity=len(rrecords) + 3)
+        assert d.rc == 0, d.rc
+        assert all(v == int.from_bytes(bytes([prefill]) * 8, "little") for v in d.records[len(rrecords):]), "written behind the numbers"
+        return d.result, d.records[:len(rrecords)]
+    hold(bc, Case("find by regular expression in a text across tile borders", find_regex_text,
+                  lambda got, what: same([(0, repr(got).encode())], [(0, repr(([len(rrecords), len(rrecords), rtext, size], rrecords)).encode())], what),
+                  hostile=[lambda: write(_noise(50000, 9), CANARY, 3, 4096, False), other],
+                  predicted={"seek": (3 * (tiles + 1) * 8 + 16 * tiles + 15) // 16 * 16 + 72 * tiles}), log)
 
     wdata, wdelim, wT, wM = SP.cases()["cut_record_shares_its_last_piece"]
     wsplit = SP.Split(wdata, wdelim, wT, wM)

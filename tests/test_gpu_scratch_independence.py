@@ -107,10 +107,10 @@ def test_decode_general_kernel_only(capsys):
 def test_seekable_write_ranges_and_split(capsys):
     """the fixed-size archive write, open + a batch of ranges, a record archive written with a CDict set and read back by frame number
     with a dictionary (host arrays and resident), zsmi_openFramesDevice on a stream with skippable frames and on junk magics, records by
-    number with followers and a refused request, find in a text across tile borders and in windows of an archive,
+    number with followers and a refused request, find in a text across tile borders - literal and by regular expression - and in windows of an archive,
     zsmi_splitRecordsDevice at targetSize 0 and 4096 with a record above maxFrameSize - each against its Python statement"""
     rep = run_family("seekable", capsys)
-    assert len(rep["cases"]) == 2 + 1 + 2 + 2 + 6
+    assert len(rep["cases"]) == 2 + 1 + 2 + 2 + 7
 
 
 def test_dictionary_training(capsys):

@@ -721,20 +721,28 @@ class SeekableArchive:
         pat, d = bytes(pattern), _delimiter(delimiter)
         count = self.num_frames - first_frame if frame_count is None else frame_count
         p = BatchCodec._p
+        return self._find_sized(lambda out, hits, cap, result: self.L.zsmi_seekableFindRecordsHost(
+            self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, pat, len(pat), first_frame, count, out, cap, result))[0]
+
+    def _find_sized(self, call, sets=False):
+        """the host forms of the searches, whose answer's size only the search knows: a first call counts (capacity 0), the second is
+        sized by the count.  call(out, hits, cap, result) -> rc makes the C call with these four arguments (pointers; out and hits None
+        at capacity 0; hits a byte a number, asked for with sets).  (numbers, hit sets); a refusal or a frame that fails raises
+        RuntimeError with the error's name"""
+        p = BatchCodec._p
         result = np.zeros(4, dtype=np.uint64)
-        out = np.zeros(1, dtype=np.uint64)
         for cap in (0, None):
             cap = int(result[0]) if cap is None else cap
-            out = np.zeros(max(cap, 1), dtype=np.uint64)
-            rc = self.L.zsmi_seekableFindRecordsHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, pat, len(pat), first_frame, count,
-                                                     p(out) if cap else None, cap, p(result))
+            out = np.zeros(max(cap, 1), dtype=np.uint64); hits = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = call(p(out) if cap else None, p(hits) if cap and sets else None, cap, p(result))
             if rc:
                 raise RuntimeError(_error_name(self.L, rc))
             if int(result[0]) > (1 << 64) - ERROR_MAX_CODE:
                 raise RuntimeError(_error_name(self.L, (1 << 64) - int(result[0])))
             if int(result[0]) == 0:
-                return []
-        return [int(v) for v in out[:int(result[1])]]
+                return [], []
+        n = int(result[1])
+        return [int(v) for v in out[:n]], [int(v) for v in hits[:n]]
 
     def build_frame_filter(self, delimiter=b"\n", gram=4, log2_bits=13) -> bytes:
         """the archive's filter frame (build_frame_filter states it), built on the GPU from one decode of the archive in windows of at
@@ -778,26 +786,16 @@ class SeekableArchive:
         frames = None
         if frame_filter is not None and mode != "none":
             frames = self._filter_frames(frame_filter, patterns, mode, ignore_case, delimiter, first_frame, count)
-        result = np.zeros(4, dtype=np.uint64)
-        out = np.zeros(1, dtype=np.uint64); hits = np.zeros(1, dtype=np.uint8)
-        for cap in (0, None):
-            cap = int(result[0]) if cap is None else cap
-            out = np.zeros(max(cap, 1), dtype=np.uint64); hits = np.zeros(max(cap, 1), dtype=np.uint8)
-            if frames is not None:
-                rc = self.L.zsmi_seekableFindQueryFramesHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(q),
-                                                             p(frames) if len(frames) else None, len(frames), p(out) if cap else None, p(hits) if cap else None, cap, p(result))
-            else:
-                rc = self.L.zsmi_seekableFindQueryHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(q), first_frame, count,
-                                                       p(out) if cap else None, p(hits) if cap else None, cap, p(result))
-            if rc:
-                raise RuntimeError(_error_name(self.L, rc))
-            if int(result[0]) > (1 << 64) - ERROR_MAX_CODE:
-                raise RuntimeError(_error_name(self.L, (1 << 64) - int(result[0])))
-            if int(result[0]) == 0:
-                return ([], []) if return_hits else []
-        n = int(result[1])
-        records = [int(v) for v in out[:n]]
-        return (records, [int(v) for v in hits[:n]]) if return_hits else records
+        n = max(len(first) - 1, 0)
+        if frames is not None:
+            def call(out, hits, cap, result):
+                return self.L.zsmi_seekableFindQueryFramesHost(self.codec.ctx, self.handle, p(first), n, d, ctypes.byref(q), p(frames) if len(frames) else None, len(frames),
+                                                               out, hits, cap, result)
+        else:
+            def call(out, hits, cap, result):
+                return self.L.zsmi_seekableFindQueryHost(self.codec.ctx, self.handle, p(first), n, d, ctypes.byref(q), first_frame, count, out, hits, cap, result)
+        records, hits = self._find_sized(call, sets=True)
+        return (records, hits) if return_hits else records
 
     def find_records_regex(self, first_record, regex, delimiter=b"\n", first_frame=0, frame_count=None):
         """find_records for a regular expression: the records of the window that `regex` (a compile_regex program, or bytes compiled on
@@ -809,20 +807,8 @@ class SeekableArchive:
         d = _delimiter(delimiter)
         count = self.num_frames - first_frame if frame_count is None else frame_count
         p = BatchCodec._p
-        result = np.zeros(4, dtype=np.uint64)
-        out = np.zeros(1, dtype=np.uint64)
-        for cap in (0, None):
-            cap = int(result[0]) if cap is None else cap
-            out = np.zeros(max(cap, 1), dtype=np.uint64)
-            rc = self.L.zsmi_seekableFindRegexHost(self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(prog), first_frame, count,
-                                                   p(out) if cap else None, cap, p(result))
-            if rc:
-                raise RuntimeError(_error_name(self.L, rc))
-            if int(result[0]) > (1 << 64) - ERROR_MAX_CODE:
-                raise RuntimeError(_error_name(self.L, (1 << 64) - int(result[0])))
-            if int(result[0]) == 0:
-                return []
-        return [int(v) for v in out[:int(result[1])]]
+        return self._find_sized(lambda out, hits, cap, result: self.L.zsmi_seekableFindRegexHost(
+            self.codec.ctx, self.handle, p(first), max(len(first) - 1, 0), d, ctypes.byref(prog), first_frame, count, out, cap, result))[0]
 
     def read_many(self, ranges, return_codes=False):
         """ranges: (offset, length) pairs -> the list of their bytes (each clipped at the content's end), one call for all of them

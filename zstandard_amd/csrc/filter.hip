@@ -356,7 +356,7 @@ extern "C" int zsmi_seekableBuildFrameFilterResident(zsmi_ctx *c, const zsmi_see
     FltWords w;
     if (const int e = fltWords(c, 0, w)) return e;
     const size_t tiles = (size_t)(sk->t.dOff[N] / ZS_SPLIT_TILE + 2);      // findDecode's scratch, before the fills are queued
-    if (!c->dItems.reserve(sizeof(ZsDecItem) * (size_t)N) || !c->seek.dMeta.reserve(findDecodeHead(N) + 3 * (tiles + 1) * sizeof(uint64_t) + 4 * tiles * sizeof(uint32_t)) ||
+    if (!c->dItems.reserve(sizeof(ZsDecItem) * (size_t)N) || !c->seek.dMeta.reserve(findDecodeHead(N) + findTileBytes(tiles)) ||
         !c->dScan.reserve(sizeof(uint64_t) * ((std::max<size_t>(N, tiles) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
     if (const int e = c->fill(w.dSums, 0, sizeof(ZsFltSums))) return e;
     if (N) {
@@ -394,7 +394,7 @@ extern "C" int zsmi_seekableBuildFrameFilterHost(zsmi_ctx *c, const zsmi_seekabl
     FltWords w;
     if (const int e = fltWords(c, 4 * sizeof(uint64_t), w)) return e;
     if (!c->sDst.reserve(total + 64) || !c->seek.dDec.reserve(most + 64) || !c->dItems.reserve(sizeof(ZsDecItem) * (size_t)mostFrames) ||
-        !c->seek.dMeta.reserve(findDecodeHead(mostFrames) + 3 * (tilesMost + 1) * sizeof(uint64_t) + 4 * tilesMost * sizeof(uint32_t)) ||
+        !c->seek.dMeta.reserve(findDecodeHead(mostFrames) + findTileBytes(tilesMost)) ||
         !c->dScan.reserve(sizeof(uint64_t) * ((std::max<size_t>(mostFrames, tilesMost) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
     uint64_t *dResult = (uint64_t *)(w.dCarry + 8);
     std::vector<uint8_t> staged(total);

@@ -25,6 +25,12 @@
 // decodeItems, k_seek_verify; k_find_code brings the frames' codes down to the first failing frame's, which k_find_emit honours.
 // Scratch, all of it context buffers reserved before anything is queued: 16 bytes a tile and three scans of 8 bytes a tile in the seekable
 // scratch, 60 bytes a frame of the window there too, the decoder's item list and scratch.  Every store is a vector store from plain C++.
+// This file is the base of the search family (findquery.hip, findregex.hip, findframes.hip): what does not depend on the search rule is
+// defined here once and called there - on the device the tile's loads (zs_find_load), the emit kernels' head and tail (zs_find_emit_head,
+// zs_find_emit_tail, zs_find_emit_open) and zs_find_open; on the host the tiles' layout (FindTiles, findTileBytes, findReserve), the three
+// scans (findScans), the archive calls' checks (findCheck), the decode half (FindDecodeWords, findDecodeList, findDecode), the window
+// sequence (findWindow) and the host forms' staging (findStage).  The tile analyses, the count kernels and the carry kernels are each
+// search's own: what crosses a border there is a bit, a set, a state function.
 
 #include "zsmi_status.h"
 #include "zsmi_wave.h"            // wave_incl_scan, wave_sum, wave_min
@@ -68,19 +74,14 @@ __device__ __forceinline__ uint32_t zs_find_kept(uint32_t om, uint32_t dm, bool 
     }
     return kept;
 }
-// The masks of tile `tile`: bit k of dm[s] / om[s] / km[s] stands for the byte at tile * ZS_SPLIT_TILE + s * 4096 + 16 * threadIdx.x + k -
-// it is the delimiter / an occurrence starts there / that occurrence is the first of its record, given `carry` as the state in front of
-// the tile.  Lane i loads the 16 bytes at base + 16 i - a wavefront's loads one contiguous KiB, the four steps' issued together; the
-// stream's last tile, unless it is a whole one, and every halo go byte by byte: no byte at or behind src + size is read (LDS holds zeros
-// there, and an occurrence must END at or in front of size).  out: the state behind the tile; anyDelim: the tile holds a delimiter.
-struct ZsFindMasks { uint32_t dm[4], om[4], km[4]; bool out, anyDelim; };
-__device__ __forceinline__ void zs_find_tile(const uint8_t *__restrict__ src, uint64_t size, uint32_t delim, const ZsFindPattern &P, uint64_t tile, bool carry,
-                                             ZsFindShared &sh, ZsFindMasks &k)
+// A tile's loads, the same in the three searches (find.hip, findquery.hip, findregex.hip): lane i loads the 16 bytes at the tile's start +
+// s * 4096 + 16 i - a wavefront's loads one contiguous KiB, the four steps' issued together; the text's last tile, unless it is a whole
+// one, goes byte by byte: no byte at or behind src + size is read, own holds zeros there.  Returns `whole`
+__device__ __forceinline__ bool zs_find_load(const uint8_t *__restrict__ src, uint64_t size, uint64_t tile, ZsSplitBytes16 (&own)[4])
 {
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u, m = P.m;
-    const uint64_t tileAt = tile * ZS_SPLIT_TILE, base = tileAt + 16u * tid;
-    ZsSplitBytes16 own[4];
-    if (size - tileAt >= ZS_SPLIT_TILE) {
+    const uint64_t tileAt = tile * ZS_SPLIT_TILE, base = tileAt + 16u * threadIdx.x;
+    const bool whole = size - tileAt >= ZS_SPLIT_TILE;
+    if (whole) {
         #pragma unroll
         for (uint32_t s = 0; s < 4; s++) __builtin_memcpy(&own[s], src + base + s * 4096u, 16);
     } else {
@@ -93,6 +94,20 @@ __device__ __forceinline__ void zs_find_tile(const uint8_t *__restrict__ src, ui
             }
         }
     }
+    return whole;
+}
+// The masks of tile `tile`: bit k of dm[s] / om[s] / km[s] stands for the byte at tile * ZS_SPLIT_TILE + s * 4096 + 16 * threadIdx.x + k -
+// it is the delimiter / an occurrence starts there / that occurrence is the first of its record, given `carry` as the state in front of
+// the tile.  The loads are zs_find_load's; every halo goes byte by byte too: no byte at or behind src + size is read (LDS holds zeros
+// there, and an occurrence must END at or in front of size).  out: the state behind the tile; anyDelim: the tile holds a delimiter.
+struct ZsFindMasks { uint32_t dm[4], om[4], km[4]; bool out, anyDelim; };
+__device__ __forceinline__ void zs_find_tile(const uint8_t *__restrict__ src, uint64_t size, uint32_t delim, const ZsFindPattern &P, uint64_t tile, bool carry,
+                                             ZsFindShared &sh, ZsFindMasks &k)
+{
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u, m = P.m;
+    const uint64_t tileAt = tile * ZS_SPLIT_TILE;
+    ZsSplitBytes16 own[4];
+    zs_find_load(src, size, tile, own);
     #pragma unroll
     for (uint32_t s = 0; s < 4; s++) __builtin_memcpy(__builtin_assume_aligned(sh.text + s * 4096u + 16u * tid, 16), &own[s], 16);
     if (tid < m) sh.pat[tid] = P.b[tid];
@@ -233,40 +248,49 @@ k_find_frames(uint32_t firstFrame, uint32_t n, uint32_t *__restrict__ list)
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j < n) list[j] = firstFrame + j;
 }
-// The masks again, the tile's carry in front.  recBase[tile]: the delimiters in front of the tile; slotBase[tile]: the kept occurrences in
-// front of it (slotBase[tiles]: total); occBase[tiles]: matches.  A step's occurrences follow the steps before it, a wavefront's the
-// wavefronts before it, a lane's the lanes before it.  base: one device word, or null for 0.  code: null, or the window's code - not 0:
-// no number is written and dResult states it.  The grid is max(tiles, 1): the first lane writes dResult whatever `tiles` is.
-__global__ void __launch_bounds__(256)
-k_find_emit(const uint8_t *__restrict__ src, uint64_t size, uint32_t delim, const ZsFindPattern P, uint32_t tiles, const uint32_t *__restrict__ flags,
-            const uint64_t *__restrict__ recBase, const uint64_t *__restrict__ slotBase, const uint64_t *__restrict__ occBase, const uint64_t *__restrict__ base,
-            const uint32_t *__restrict__ code, uint64_t *__restrict__ records, uint64_t capacity, uint64_t *__restrict__ result)
+// ---- what the three emit kernels (k_find_emit, k_findq_emit, k_findre_emit) share ----
+// The head: the first lane of the first workgroup writes dResult - code: null, or the window's code; not 0: no number is written and
+// dResult states it; third(): dResult[2], the caller's, asked for by that one lane alone (every workgroup would else load its
+// words).  Returns whether this workgroup has anything to write, and slot0, its tile's first
+// slot: none when the window failed, behind the last tile, at or above capacity (the slots ascend with the tiles; capacity 0: nothing to
+// write) and, with skipEmpty, in a tile that lists nothing - most tiles of a rare pattern - which is then not read again.  (k_find_emit
+// passes false: DESIGN.md, "Find records".)  The same for the whole workgroup
+template <class Third>
+__device__ __forceinline__ bool zs_find_emit_head(const uint32_t *__restrict__ code, const uint64_t *__restrict__ slotBase, uint32_t tiles, uint64_t capacity, uint64_t size,
+                                                  Third third, bool skipEmpty, uint64_t *__restrict__ result, uint64_t &slot0)
 {
-    __shared__ ZsFindShared sh;
-    __shared__ uint32_t keptOf[4][4], delimsOf[4][4];
     const uint32_t failed = code ? *code : 0u;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const uint64_t total = slotBase[tiles];
         result[0] = failed ? 0ull - (uint64_t)failed : total;
         result[1] = failed ? 0ull : (total < capacity ? total : capacity);
-        result[2] = failed ? 0ull : occBase[tiles];
+        result[2] = failed ? 0ull : third();
         result[3] = size;
     }
-    if (failed || blockIdx.x >= tiles) return;                             // (the same for the whole workgroup)
-    const uint64_t slot0 = slotBase[blockIdx.x];
-    if (slot0 >= capacity) return;                                         // (the slots ascend with the tiles; capacity 0: nothing to write)
-    ZsFindMasks k;
-    zs_find_tile(src, size, delim, P, blockIdx.x, (flags[blockIdx.x] & kFindCarry) != 0u, sh, k);
+    if (failed || blockIdx.x >= tiles) return false;
+    slot0 = slotBase[blockIdx.x];
+    return slot0 < capacity && !(skipEmpty && slotBase[blockIdx.x + 1u] == slot0);
+}
+// The tail: bit k of km[s] is a number to write, bit k of dm[s] a delimiter, for the byte at the tile's start + s * 4096 + 16 *
+// threadIdx.x + k.  A step's numbers follow the steps before it, a wavefront's the wavefronts before it, a lane's the lanes before it:
+// ranks by wave_incl_scan, the wavefronts' totals through LDS.  The number is first - the tile's first record: the caller's base +
+// recBase[tile] - + the delimiters in front of the bit inside the tile; every one with a slot below capacity is written, and
+// each(slot, s, at) called for it.  Returns the tile's totals: its numbers and its delimiters
+struct ZsFindEmitted { uint32_t kept, delims; };
+template <class Each>
+__device__ __forceinline__ ZsFindEmitted zs_find_emit_tail(const uint32_t (&dm)[4], const uint32_t (&km)[4], uint64_t slot0, uint64_t first,
+                                                           uint64_t capacity, uint64_t *__restrict__ records, Each each)
+{
+    __shared__ uint32_t keptOf[4][4], delimsOf[4][4];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     uint32_t keptBefore[4], delimsBefore[4];
     #pragma unroll
     for (uint32_t s = 0; s < 4; s++) {
-        const uint32_t nk = (uint32_t)__popc(k.km[s]), nd = (uint32_t)__popc(k.dm[s]), inclK = wave_incl_scan(nk), inclD = wave_incl_scan(nd);
+        const uint32_t nk = (uint32_t)__popc(km[s]), nd = (uint32_t)__popc(dm[s]), inclK = wave_incl_scan(nk), inclD = wave_incl_scan(nd);
         keptBefore[s] = inclK - nk; delimsBefore[s] = inclD - nd;
         if (lane == 63u) { keptOf[s][wave] = inclK; delimsOf[s][wave] = inclD; }
     }
     __syncthreads();
-    const uint64_t first = (base ? *base : 0ull) + recBase[blockIdx.x];
     uint32_t keptAt = 0, delimsAt = 0;                                     // those of the steps in front
     #pragma unroll
     for (uint32_t s = 0; s < 4; s++) {
@@ -278,12 +302,36 @@ k_find_emit(const uint8_t *__restrict__ src, uint64_t size, uint32_t delim, cons
         }
         uint64_t slot = slot0 + keptAt + aheadK + keptBefore[s];
         const uint64_t rec = first + delimsAt + aheadD + delimsBefore[s];
-        for (uint32_t bits = k.km[s]; bits; bits &= bits - 1u, slot++) {
+        for (uint32_t bits = km[s]; bits; bits &= bits - 1u, slot++) {
             const uint32_t at = (uint32_t)__ffs((int)bits) - 1u;
-            if (slot < capacity) records[slot] = rec + (uint32_t)__popc(k.dm[s] & ((1u << at) - 1u));
+            if (slot < capacity) { records[slot] = rec + (uint32_t)__popc(dm[s] & ((1u << at) - 1u)); each(slot, s, at); }
         }
         keptAt += allK; delimsAt += allD;
     }
+    return { keptAt, delimsAt };
+}
+// the text's unterminated last record, where it is listed (the last tile's first lane decides): slot and rec lie behind every number
+// and every delimiter of the last tile
+template <class Each>
+__device__ __forceinline__ void zs_find_emit_open(uint64_t slot, uint64_t rec, uint64_t capacity, uint64_t *__restrict__ records, Each each)
+{
+    if (slot < capacity) { records[slot] = rec; each(slot); }
+}
+// The masks again, the tile's carry in front.  recBase[tile]: the delimiters in front of the tile; slotBase[tile]: the kept occurrences in
+// front of it (slotBase[tiles]: total); occBase[tiles]: matches.  A step's occurrences follow the steps before it, a wavefront's the
+// wavefronts before it, a lane's the lanes before it.  base: one device word, or null for 0.  code: null, or the window's code - not 0:
+// no number is written and dResult states it.  The grid is max(tiles, 1): the first lane writes dResult whatever `tiles` is.
+__global__ void __launch_bounds__(256)
+k_find_emit(const uint8_t *__restrict__ src, uint64_t size, uint32_t delim, const ZsFindPattern P, uint32_t tiles, const uint32_t *__restrict__ flags,
+            const uint64_t *__restrict__ recBase, const uint64_t *__restrict__ slotBase, const uint64_t *__restrict__ occBase, const uint64_t *__restrict__ base,
+            const uint32_t *__restrict__ code, uint64_t *__restrict__ records, uint64_t capacity, uint64_t *__restrict__ result)
+{
+    __shared__ ZsFindShared sh;
+    uint64_t slot0;
+    if (!zs_find_emit_head(code, slotBase, tiles, capacity, size, [&] { return occBase[tiles]; }, false, result, slot0)) return;
+    ZsFindMasks k;
+    zs_find_tile(src, size, delim, P, blockIdx.x, (flags[blockIdx.x] & kFindCarry) != 0u, sh, k);
+    zs_find_emit_tail(k.dm, k.km, slot0, (base ? *base : 0ull) + recBase[blockIdx.x], capacity, records, [](uint64_t, uint32_t, uint32_t) {});
 }
 
 // ---- host ----
@@ -295,20 +343,23 @@ extern "C" size_t zsmi_findRecords(const void *src, size_t srcSize, int delim, c
     if (srcSize && !src) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
     return (size_t)zs_find_records((const uint8_t *)src, srcSize, (uint8_t)delim, (const uint8_t *)pattern, patternSize, base, records, capacity, matches);
 }
-// the tiles of a text and what the calls lay over them in the seekable scratch, `head` bytes into it (8-aligned): delimiters, occurrences,
-// kept, flags [tiles each]; the three scans [tiles + 1 each].  findReserve: that, and the scans' tile sums for `scanned` items at least -
-// before anything is queued
-struct FindTiles { uint32_t tiles; uint32_t *dDelims, *dOccs, *dKept, *dFlags; uint64_t *dRecBase, *dSlotBase, *dOccBase; };
-static int findReserve(zsmi_ctx *c, uint64_t size, size_t head, uint64_t scanned, FindTiles &t)
+// the tiles of a text and what the calls lay over them in the seekable scratch, `head` bytes into it (8-aligned): the three scans
+// [tiles + 1 each]; delimiters, occurrences, kept, flags [tiles each] - findTileBytes; behind them, 16-aligned, extraPerTile bytes a tile
+// of the search's own (dExtra; findregex.hip's 72).  findReserve: that, and the scans' tile sums for `scanned` items at least - before
+// anything is queued
+struct FindTiles { uint32_t tiles; uint32_t *dDelims, *dOccs, *dKept, *dFlags; uint64_t *dRecBase, *dSlotBase, *dOccBase; uint8_t *dExtra; };
+static size_t findTileBytes(size_t tiles) { return 3 * (tiles + 1) * sizeof(uint64_t) + 4 * tiles * sizeof(uint32_t); }
+static int findReserve(zsmi_ctx *c, uint64_t size, size_t head, uint64_t scanned, FindTiles &t, size_t extraPerTile = 0)
 {
     const uint64_t tiles64 = (size + ZS_SPLIT_TILE - 1) / ZS_SPLIT_TILE;
     if (tiles64 > 0x7FFFFFFFull) return ZSMI_error_memory_allocation;
     t.tiles = (uint32_t)tiles64;
-    const size_t n = t.tiles;
-    if (!c->seek.dMeta.reserve(head + 3 * (n + 1) * sizeof(uint64_t) + 4 * n * sizeof(uint32_t))) return ZSMI_error_memory_allocation;
+    const size_t n = t.tiles, words = head + findTileBytes(n);
+    if (!c->seek.dMeta.reserve(words + (extraPerTile ? 16 + n * extraPerTile : 0))) return ZSMI_error_memory_allocation;
     if (!c->dScan.reserve(sizeof(uint64_t) * (size_t)((std::max<uint64_t>(scanned, n) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
     t.dRecBase = (uint64_t *)((uint8_t *)c->seek.dMeta.p + head); t.dSlotBase = t.dRecBase + n + 1; t.dOccBase = t.dSlotBase + n + 1;
     t.dDelims = (uint32_t *)(t.dOccBase + n + 1); t.dOccs = t.dDelims + n; t.dKept = t.dOccs + n; t.dFlags = t.dKept + n;
+    t.dExtra = extraPerTile ? (uint8_t *)c->seek.dMeta.p + (words + 15) / 16 * 16 : nullptr;
     return 0;
 }
 static ZsFindPattern findPattern(const void *pattern, uint32_t m)
@@ -318,6 +369,14 @@ static ZsFindPattern findPattern(const void *pattern, uint32_t m)
     P.m = m; memcpy(P.b, pattern, m);
     return P;
 }
+// the scans behind a search's count and carry kernels: over the delimiters (a tile's record base), over kept (a tile's output slot) and,
+// where the search counts them, over the occurrences (matches)
+static int findScans(zsmi_ctx *c, const FindTiles &t, bool occs)
+{
+    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dDelims, nullptr, t.tiles, 1u, nullptr, t.dRecBase)) return e;
+    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dKept, nullptr, t.tiles, 1u, nullptr, t.dSlotBase)) return e;
+    return occs ? scanOffsets(c, "k_find_scan", (const uint32_t *)t.dOccs, nullptr, t.tiles, 1u, nullptr, t.dOccBase) : 0;
+}
 // the launch sequence over dText[0, size), its arguments checked and its scratch reserved by the caller
 static int findText(zsmi_ctx *c, const void *dText, uint64_t size, int delim, const ZsFindPattern &P, const uint64_t *dBase, const uint32_t *dCode,
                     uint64_t *dRecords, uint64_t capacity, uint64_t *dResult, const FindTiles &t)
@@ -326,9 +385,7 @@ static int findText(zsmi_ctx *c, const void *dText, uint64_t size, int delim, co
         LAUNCH(c, "k_find_count", k_find_count, dim3(t.tiles), dim3(256), 0, (const uint8_t *)dText, size, (uint32_t)delim, P, t.dDelims, t.dOccs, t.dKept, t.dFlags);
         LAUNCH(c, "k_find_carry", k_find_carry, dim3(1), dim3(1024), 0, t.dFlags, t.dKept, t.tiles);
     }
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dDelims, nullptr, t.tiles, 1u, nullptr, t.dRecBase)) return e;
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dKept, nullptr, t.tiles, 1u, nullptr, t.dSlotBase)) return e;
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dOccs, nullptr, t.tiles, 1u, nullptr, t.dOccBase)) return e;
+    if (const int e = findScans(c, t, true)) return e;
     LAUNCH(c, "k_find_emit", k_find_emit, dim3(std::max(t.tiles, 1u)), dim3(256), 0, (const uint8_t *)dText, size, (uint32_t)delim, P, t.tiles, (const uint32_t *)t.dFlags,
            (const uint64_t *)t.dRecBase, (const uint64_t *)t.dSlotBase, (const uint64_t *)t.dOccBase, dBase, dCode, dRecords, capacity, dResult);
     return c->launched();
@@ -351,94 +408,136 @@ extern "C" size_t zsmi_seekableFindWorkBound(const zsmi_seekable *sk, uint32_t f
     if (!sk || (uint64_t)firstFrame + frameCount > sk->t.n) return 0;
     return (size_t)(sk->t.dOff[(size_t)firstFrame + frameCount] - sk->t.dOff[firstFrame]);
 }
-// the header's checks of the archive calls, in its order; work: null for the host form, which brings its own buffer
-static int findCheck(const zsmi_ctx *c, const zsmi_seekable *sk, const void *firstRecord, uint32_t nFrames, int delim, const void *pattern, uint32_t patternSize,
+// the header's checks of the archive calls, in its order; rule: the pattern, query or program, and ruleCheck its check (zs_find_check,
+// zs_findq_check, zs_regex_check) in the place the order gives it; work: null for the host form, which brings its own buffer
+template <class RuleCheck>
+static int findCheck(const zsmi_ctx *c, const zsmi_seekable *sk, const void *firstRecord, uint32_t nFrames, const void *rule, RuleCheck ruleCheck,
                      uint32_t firstFrame, uint32_t frameCount, bool ownWork, const void *work, uint64_t workCapacity, const void *records, uint64_t capacity, const void *result)
 {
     if (!c) return ZSMI_error_init_missing;
-    if (!sk || !result || !pattern || !firstRecord || (capacity && !records)) return ZSMI_error_GENERIC;
+    if (!sk || !result || !rule || !firstRecord || (capacity && !records)) return ZSMI_error_GENERIC;
     if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
-    if (const int e = zs_find_check(delim, pattern, patternSize)) return e;
+    if (const int e = ruleCheck()) return e;
     if (nFrames != sk->t.n || (uint64_t)firstFrame + frameCount > nFrames) return ZSMI_error_parameter_outOfBound;
     const uint64_t bound = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
     if (!ownWork && bound && !work) return ZSMI_error_GENERIC;
     if (!ownWork && workCapacity < bound) return ZSMI_error_dstSize_tooSmall;
     return 0;
 }
-// The decode half of a search on an archive, shared by the single-pattern search below and the query search of findquery.hip (context
-// bound, frameCount > 0, arguments checked by the caller): the scratch of the whole call reserved, then the window's frames into dWork, end
-// to end, verified, and the first failing frame's code in a device word.  Leaves the text's size, its tiles and that word
-struct FindDecoded { uint64_t bytes; FindTiles t; const uint32_t *dCode; const uint64_t *dListAt; };      // dListAt: the frames' places in dWork [frameCount + 1]
-// device words, a frame of the window, in front of the tiles' (findDecode lays them out; a caller that reserves more scratch behind the
-// tiles' words sizes it with this): 64 bits - sizes [F], places in dWork [F + 1]; verify records [F]; 32 bits - the list, decoder status,
-// refusals, written, codes [F each], the window's code [1, padded to 8 bytes]
+// The words of the decode half of a search on an archive, a frame of F, at the start of the seekable scratch, in front of the tiles'
+// (findDecodeHead: their bytes - the `head` of findReserve): 64 bits - sizes [F], places in dWork [F + 1]; verify records [F]; 32 bits -
+// the list, decoder status, refusals, written, codes [F each], the call's code [1, padded to 8 bytes]
+struct FindDecodeWords { uint64_t *dSizes, *dListAt; ZsSeekItem *dVerify; uint32_t *dList, *dSt, *dRefused, *dFrameWritten, *dCodes, *dCode; };
 static size_t findDecodeHead(size_t F) { return (2 * F + 1) * sizeof(uint64_t) + F * sizeof(ZsSeekItem) + ((5 * F + 1) * sizeof(uint32_t) + 7) / 8 * 8; }
-static int findDecode(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount, void *dWork, FindDecoded &w)
+static FindDecodeWords findDecodeWords(void *p, size_t F)
 {
-    const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
-    const size_t F = frameCount;
-    FindTiles &t = w.t;
-    const size_t head = findDecodeHead(F);
-    if (const int e = findReserve(c, bytes, head, F, t)) return e;
-    if (!c->dItems.reserve(sizeof(ZsDecItem) * F)) return ZSMI_error_memory_allocation;
-    uint64_t *dSizes = (uint64_t *)c->seek.dMeta.p, *dListAt = dSizes + F;
-    ZsSeekItem *dVerify = (ZsSeekItem *)(dListAt + F + 1);
-    uint32_t *dList = (uint32_t *)(dVerify + F), *dSt = dList + F, *dRefused = dSt + F, *dFrameWritten = dRefused + F, *dCodes = dFrameWritten + F, *dCode = dCodes + F;
+    FindDecodeWords d;
+    d.dSizes = (uint64_t *)p; d.dListAt = d.dSizes + F; d.dVerify = (ZsSeekItem *)(d.dListAt + F + 1);
+    d.dList = (uint32_t *)(d.dVerify + F); d.dSt = d.dList + F; d.dRefused = d.dSt + F; d.dFrameWritten = d.dRefused + F; d.dCodes = d.dFrameWritten + F; d.dCode = d.dCodes + F;
+    return d;
+}
+// the F frames of d.dList, of d.dSizes bytes each, into dWork[0, bytes), end to end and verified: d.dListAt their places, d.dCodes a code
+// a frame.  What makes the list and the sizes, and what becomes of the codes, is the caller's (k_find_frames and k_find_code here,
+// k_findsel_list and k_findsel_code in findframes.hip); the context's item list holds F items
+static int findDecodeList(zsmi_ctx *c, const zsmi_seekable *sk, const FindDecodeWords &d, uint32_t F, uint64_t bytes, void *dWork)
+{
     const ZsSeekEntry *dTable = (const ZsSeekEntry *)sk->dTable.p;
-    const uint32_t grid = (frameCount + 255) / 256;
-    LAUNCH(c, "k_find_frames", k_find_frames, dim3(grid), dim3(256), 0, firstFrame, frameCount, dList);
-    LAUNCH(c, "k_seek_request_sizes", k_seek_request_sizes, dim3(grid), dim3(256), 0, dTable, sk->t.n, (const uint32_t *)dList, frameCount, dSizes);
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint64_t *)dSizes, nullptr, frameCount, 1u, nullptr, dListAt)) return e;
-    LAUNCH(c, "k_seek_request_items", k_seek_request_items, dim3(grid), dim3(256), 0, dTable, sk->t.n, (const uint32_t *)dList, frameCount, (const uint64_t *)dListAt,
-           bytes, (uint8_t *)dWork, (ZsDecItem *)c->dItems.p, dVerify, dRefused, dFrameWritten);
+    if (const int e = scanOffsets(c, "k_find_scan", (const uint64_t *)d.dSizes, nullptr, F, 1u, nullptr, d.dListAt)) return e;
+    LAUNCH(c, "k_seek_request_items", k_seek_request_items, dim3((F + 255u) / 256u), dim3(256), 0, dTable, sk->t.n, (const uint32_t *)d.dList, F, (const uint64_t *)d.dListAt,
+           bytes, (uint8_t *)dWork, (ZsDecItem *)c->dItems.p, d.dVerify, d.dRefused, d.dFrameWritten);
     CapStats caps;
-    caps.add(sk->maxDSize, frameCount);
-    if (const int e = decodeItems(c, sk->dFrames, frameCount, dWork, caps, dSt, &sk->sel)) return e;
-    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((frameCount + 15) / 16), dim3(64), 0, (const ZsSeekItem *)dVerify, frameCount, (const uint32_t *)dSt,
-           sk->t.checksum ? 1 : 0, dCodes, (const uint32_t *)dRefused);
-    LAUNCH(c, "k_find_code", k_find_code, dim3(1), dim3(1024), 0, (const uint32_t *)dCodes, frameCount, dCode);
-    w.bytes = bytes; w.dCode = dCode; w.dListAt = dListAt;
+    caps.add(sk->maxDSize, F);
+    if (const int e = decodeItems(c, sk->dFrames, F, dWork, caps, d.dSt, &sk->sel)) return e;
+    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((F + 15) / 16), dim3(64), 0, (const ZsSeekItem *)d.dVerify, F, (const uint32_t *)d.dSt, sk->t.checksum ? 1 : 0, d.dCodes,
+           (const uint32_t *)d.dRefused);
     return 0;
 }
-// the launch sequence on an archive, its arguments checked by the caller: the decode half, then findText
-static int findWindow(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, int delim, const void *pattern, uint32_t patternSize, uint32_t firstFrame,
-                      uint32_t frameCount, void *dWork, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult)
+// The decode half of a search on a window of an archive, shared by the three searches, the record index and the frame filter (context
+// bound, frameCount > 0, arguments checked by the caller): the scratch of the whole call reserved - extraPerTile: findReserve's - then the
+// window's frames into dWork, end to end, verified, and the first failing frame's code in a device word.  Leaves the text's size, its
+// tiles and that word
+struct FindDecoded { uint64_t bytes; FindTiles t; const uint32_t *dCode; const uint64_t *dListAt; };      // dListAt: the frames' places in dWork [frameCount + 1]
+static int findDecode(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount, void *dWork, FindDecoded &w, size_t extraPerTile = 0)
+{
+    const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
+    if (const int e = findReserve(c, bytes, findDecodeHead(frameCount), frameCount, w.t, extraPerTile)) return e;
+    if (!c->dItems.reserve(sizeof(ZsDecItem) * (size_t)frameCount)) return ZSMI_error_memory_allocation;
+    const FindDecodeWords d = findDecodeWords(c->seek.dMeta.p, frameCount);
+    const uint32_t grid = (frameCount + 255) / 256;
+    LAUNCH(c, "k_find_frames", k_find_frames, dim3(grid), dim3(256), 0, firstFrame, frameCount, d.dList);
+    LAUNCH(c, "k_seek_request_sizes", k_seek_request_sizes, dim3(grid), dim3(256), 0, (const ZsSeekEntry *)sk->dTable.p, sk->t.n, (const uint32_t *)d.dList, frameCount, d.dSizes);
+    if (const int e = findDecodeList(c, sk, d, frameCount, bytes, dWork)) return e;
+    LAUNCH(c, "k_find_code", k_find_code, dim3(1), dim3(1024), 0, (const uint32_t *)d.dCodes, frameCount, d.dCode);
+    w.bytes = bytes; w.dCode = d.dCode; w.dListAt = d.dListAt;
+    return 0;
+}
+// the launch sequence on a window of an archive, its arguments checked by the caller: the decode half, then text(w) - the search's
+// sequence over the decoded text (findText, findqText, findreText)
+template <class Text>
+static int findWindow(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount, void *dWork, uint64_t *dResult, size_t extraPerTile, Text text)
 {
     if (const int e = c->bind()) return e;
     if (frameCount == 0) return c->fill(dResult, 0, 4 * sizeof(uint64_t));
     FindDecoded w;
-    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, w)) return e;
-    return findText(c, dWork, w.bytes, delim, findPattern(pattern, patternSize), dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, w.t);
+    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, w, extraPerTile)) return e;
+    return text(w);
+}
+// The host forms of the archive calls: host arrays in and out around a resident run, one wait.  Staged in device memory: firstRecord
+// [nFrames + 1], `front` 64-bit words and, behind the four result words, `back` bytes of the caller's own (the list search's count and
+// list), a work buffer of workBytes; the numbers [room] and, for a search with hit sets, a byte of set each behind them.  firstRecord goes
+// up, run(s) uploads what else it staged and queues the resident sequence, the result words and the staged numbers (and sets, where
+// hits is given) come down behind one wait, and what was written is handed over.  No exception leaves: this runs inside extern "C"
+struct FindStaged { uint64_t *dFirst, *dFront, *dResult; uint8_t *dBack; void *dWork; uint64_t *dRecords; uint8_t *dHits; };      // dRecords, dHits: null where nothing is wanted
+template <class Run>
+static int findStage(zsmi_ctx *c, const uint64_t *firstRecord, uint32_t nFrames, uint64_t workBytes, size_t room, bool sets, size_t front, size_t back,
+                     uint64_t *records, uint8_t *hits, uint64_t *result, Run run)
+{
+    if (const int e = c->bind()) return e;
+    const size_t words = (size_t)nFrames + 1 + front + 4;
+    if (!c->sSizes.reserve(words * sizeof(uint64_t) + back) || !c->sDst.reserve(room * (sizeof(uint64_t) + (sets ? 1 : 0)) + 64) || !c->seek.dDec.reserve(workBytes + 64))
+        return ZSMI_error_memory_allocation;
+    uint64_t *dRecords = (uint64_t *)c->sDst.p;
+    uint8_t *dHits = (uint8_t *)(dRecords + room);
+    FindStaged s;
+    s.dFirst = (uint64_t *)c->sSizes.p; s.dFront = s.dFirst + nFrames + 1; s.dResult = s.dFront + front; s.dBack = (uint8_t *)(s.dResult + 4); s.dWork = c->seek.dDec.p;
+    s.dRecords = room ? dRecords : nullptr; s.dHits = room && hits ? dHits : nullptr;
+    int rc = c->toDevice(s.dFirst, firstRecord, ((size_t)nFrames + 1) * sizeof(uint64_t));
+    if (!rc) rc = run(s);
+    std::vector<uint64_t> numbers;
+    std::vector<uint8_t> hitSets;
+    if (!rc) { try { numbers.resize(room); if (hits) hitSets.resize(room); } catch (const std::bad_alloc &) { rc = ZSMI_error_memory_allocation; } }
+    if (!rc) rc = c->toHost(result, s.dResult, 4 * sizeof(uint64_t));
+    if (!rc && room) rc = c->toHost(numbers.data(), dRecords, room * sizeof(uint64_t));
+    if (!rc && room && hits) rc = c->toHost(hitSets.data(), dHits, room);
+    const int waited = c->wait();                                                  // (whatever was queued, a failed call included)
+    if (rc || waited) return rc ? rc : waited;
+    if (result[1] && result[1] <= room) {
+        memcpy(records, numbers.data(), (size_t)result[1] * sizeof(uint64_t));
+        if (hits) memcpy(hits, hitSets.data(), (size_t)result[1]);
+    }
+    return 0;
 }
 extern "C" int zsmi_seekableFindRecordsResident(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
                                                 const void *pattern, uint32_t patternSize, uint32_t firstFrame, uint32_t frameCount,
                                                 void *dWork, uint64_t workCapacity, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult)
 {
-    if (const int e = findCheck(c, sk, dFirstRecord, nFrames, delim, pattern, patternSize, firstFrame, frameCount, false, dWork, workCapacity, dRecords, capacity, dResult)) return e;
-    return findWindow(c, sk, dFirstRecord, delim, pattern, patternSize, firstFrame, frameCount, dWork, dRecords, capacity, dResult);
+    if (const int e = findCheck(c, sk, dFirstRecord, nFrames, pattern, [&] { return zs_find_check(delim, pattern, patternSize); }, firstFrame, frameCount, false, dWork,
+                                workCapacity, dRecords, capacity, dResult)) return e;
+    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, 0, [&](const FindDecoded &w) {
+        return findText(c, dWork, w.bytes, delim, findPattern(pattern, patternSize), dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, w.t);
+    });
 }
-// host arrays in and out.  A record that holds an occurrence holds m bytes of its own, so the window's bytes / m numbers are all there can
-// be: the staging of the numbers is that, or capacity.  firstRecord goes up, the body above runs with a work buffer of the context's, the
-// result words and the staged numbers come down behind one wait, and the numbers written are handed over
+// host arrays in and out (findStage).  A record that holds an occurrence holds m bytes of its own, so the window's bytes / m numbers are
+// all there can be: the staging of the numbers is that, or capacity
 extern "C" int zsmi_seekableFindRecordsHost(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
                                             const void *pattern, uint32_t patternSize, uint32_t firstFrame, uint32_t frameCount,
                                             uint64_t *records, size_t capacity, uint64_t *result)
 {
-    if (const int e = findCheck(c, sk, firstRecord, nFrames, delim, pattern, patternSize, firstFrame, frameCount, true, nullptr, 0, records, capacity, result)) return e;
+    if (const int e = findCheck(c, sk, firstRecord, nFrames, pattern, [&] { return zs_find_check(delim, pattern, patternSize); }, firstFrame, frameCount, true, nullptr, 0,
+                                records, capacity, result)) return e;
     const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
     const size_t room = (size_t)std::min<uint64_t>(capacity, bytes / patternSize);
-    if (const int e = c->bind()) return e;
-    // staging: firstRecord [nFrames + 1], dResult [4]; the numbers [room]
-    const size_t words = (size_t)nFrames + 1 + 4;
-    if (!c->sSizes.reserve(words * sizeof(uint64_t)) || !c->sDst.reserve(room * sizeof(uint64_t) + 64) || !c->seek.dDec.reserve(bytes + 64)) return ZSMI_error_memory_allocation;
-    uint64_t *dFirst = (uint64_t *)c->sSizes.p, *dResult = dFirst + nFrames + 1, *dRecords = (uint64_t *)c->sDst.p;
-    int rc = c->toDevice(dFirst, firstRecord, ((size_t)nFrames + 1) * sizeof(uint64_t));
-    if (!rc) rc = findWindow(c, sk, dFirst, delim, pattern, patternSize, firstFrame, frameCount, c->seek.dDec.p, room ? dRecords : nullptr, room, dResult);
-    std::vector<uint64_t> numbers(room);
-    if (!rc) rc = c->toHost(result, dResult, 4 * sizeof(uint64_t));
-    if (!rc && room && frameCount) rc = c->toHost(numbers.data(), dRecords, room * sizeof(uint64_t));
-    const int waited = c->wait();                                                  // (whatever was queued, a failed call included)
-    if (rc || waited) return rc ? rc : waited;
-    if (result[1] && result[1] <= room) memcpy(records, numbers.data(), (size_t)result[1] * sizeof(uint64_t));
-    return 0;
+    return findStage(c, firstRecord, nFrames, bytes, room, false, 0, 0, records, nullptr, result, [&](const FindStaged &s) {
+        return zsmi_seekableFindRecordsResident(c, sk, s.dFirst, nFrames, delim, pattern, patternSize, firstFrame, frameCount, s.dWork, bytes, s.dRecords, room, s.dResult);
+    });
 }

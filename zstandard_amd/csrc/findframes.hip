@@ -9,7 +9,7 @@
 //   k_findsel_list     the list judged - a count above maxFrames, a frame number at or above nFrames, a list that does not ascend - and
 //                      laid out: an entry's bytes are its frame's Decompressed_Size, + 1 for the last frame of a run that another run
 //                      follows: ONE delimiter byte between runs.  A pattern holds no delimiter, so nothing straddles a run border
-//   scanOffsets        the frames' places in dWork; k_seek_request_items, decodeItems, k_seek_verify: find.hip's decode half on the list
+//   scanOffsets        the frames' places in dWork; k_seek_request_items, decodeItems, k_seek_verify: find.hip's findDecodeList on the list
 //   k_findsel_code     the call's code: the list's refusal, content above workCapacity, or the first failing frame's code
 //   k_findsel_fill     the delimiter between runs, and delimiters from the content's end to the end of the text searched: the text is
 //                      S = min(workCapacity, zsmi_seekableFindFramesWorkBound(sk, maxFrames)) bytes, a size the HOST knows; the records
@@ -31,8 +31,8 @@
 #include "zsmi_ctx.h"             // the context, LAUNCH, scanOffsets, decodeItems
 #include "zsmi_findquery.h"       // the query and its checks
 #include <algorithm>
-// From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE; seekable.hip - the handle, ZsSeekEntry,
-// ZsSeekItem, k_seek_request_items, k_seek_verify; find.hip - FindTiles, findReserve, findDecodeHead; findquery.hip - ZsFindQuery,
+// From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE; seekable.hip - the handle, ZsSeekEntry;
+// find.hip - FindTiles, findReserve, findDecodeHead, findDecodeWords, findDecodeList, FindStaged, findStage; findquery.hip -
 // findQuery, findqText, findQueryShortest; recindex.hip - zs_ridx_wave_sum64.
 
 struct ZsFselWords { unsigned long long needed, seps; uint32_t bad, tooMany, code, count; uint64_t tmp[4]; };      // zeroed on the stream in front of the kernels
@@ -165,31 +165,22 @@ static int findselRun(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFir
     FindTiles t;
     if (const int e = findReserve(c, S, head, F, t)) return e;
     if (!c->dItems.reserve(sizeof(ZsDecItem) * (size_t)F)) return ZSMI_error_memory_allocation;
-    uint64_t *dSizes = (uint64_t *)c->seek.dMeta.p, *dListAt = dSizes + F;
-    ZsSeekItem *dVerify = (ZsSeekItem *)(dListAt + F + 1);
-    uint32_t *dList = (uint32_t *)(dVerify + F), *dSt = dList + F, *dRefused = dSt + F, *dFrameWritten = dRefused + F, *dCodes = dFrameWritten + F;
+    const FindDecodeWords d = findDecodeWords(c->seek.dMeta.p, F);
     uint64_t *dPrefix = (uint64_t *)((uint8_t *)c->seek.dMeta.p + own);
     ZsFselWords *dWords = (ZsFselWords *)(dPrefix + F + 1);
     const ZsSeekEntry *dTable = (const ZsSeekEntry *)sk->dTable.p;
     const uint32_t grid = std::min((F + 255u) / 256u, 4096u);
     if (const int e = c->fill(dWords, 0, sizeof(ZsFselWords))) return e;
-    LAUNCH(c, "k_findsel_list", k_findsel_list, dim3(grid), dim3(256), 0, dTable, sk->t.n, dFrames, dFrameCount, maxFrames, F, dList, dSizes, dWords);
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint64_t *)dSizes, nullptr, F, 1u, nullptr, dListAt)) return e;
-    LAUNCH(c, "k_seek_request_items", k_seek_request_items, dim3((F + 255u) / 256u), dim3(256), 0, dTable, sk->t.n, (const uint32_t *)dList, F, (const uint64_t *)dListAt,
-           S, (uint8_t *)dWork, (ZsDecItem *)c->dItems.p, dVerify, dRefused, dFrameWritten);
-    CapStats caps;
-    caps.add(sk->maxDSize, F);
-    if (const int e = decodeItems(c, sk->dFrames, F, dWork, caps, dSt, &sk->sel)) return e;
-    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((F + 15) / 16), dim3(64), 0, (const ZsSeekItem *)dVerify, F, (const uint32_t *)dSt, sk->t.checksum ? 1 : 0, dCodes,
-           (const uint32_t *)dRefused);
-    LAUNCH(c, "k_findsel_code", k_findsel_code, dim3(1), dim3(256), 0, (const uint32_t *)dCodes, dFrameCount, sk->maxDSize, S, dWords);
+    LAUNCH(c, "k_findsel_list", k_findsel_list, dim3(grid), dim3(256), 0, dTable, sk->t.n, dFrames, dFrameCount, maxFrames, F, d.dList, d.dSizes, dWords);
+    if (const int e = findDecodeList(c, sk, d, F, S, dWork)) return e;
+    LAUNCH(c, "k_findsel_code", k_findsel_code, dim3(1), dim3(256), 0, (const uint32_t *)d.dCodes, dFrameCount, sk->maxDSize, S, dWords);
     LAUNCH(c, "k_findsel_fill", k_findsel_fill, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + 255) / 256, 8192))), dim3(256), 0, (uint8_t *)dWork, S, (uint32_t)delim,
-           dTable, (const uint32_t *)dList, (const uint64_t *)dSizes, (const uint64_t *)dListAt, F);
+           dTable, (const uint32_t *)d.dList, (const uint64_t *)d.dSizes, (const uint64_t *)d.dListAt, F);
     if (const int e = findqText(c, dWork, S, delim, findQuery(q), nullptr, &dWords->code, dRecords, dHits, capacity, dWords->tmp, t)) return e;
-    LAUNCH(c, "k_findsel_prefix", k_findsel_prefix, dim3(F), dim3(64), 0, (const uint8_t *)dWork, S, (uint32_t)delim, (const uint64_t *)dListAt, (const uint64_t *)t.dRecBase,
+    LAUNCH(c, "k_findsel_prefix", k_findsel_prefix, dim3(F), dim3(64), 0, (const uint8_t *)dWork, S, (uint32_t)delim, (const uint64_t *)d.dListAt, (const uint64_t *)t.dRecBase,
            (const ZsFselWords *)dWords, dPrefix);
     const uint32_t rgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((capacity + 255) / 256, 4096));
-    LAUNCH(c, "k_findsel_renumber", k_findsel_renumber, dim3(rgrid), dim3(256), 0, dRecords, (const ZsFselWords *)dWords, (const uint64_t *)dPrefix, (const uint32_t *)dList,
+    LAUNCH(c, "k_findsel_renumber", k_findsel_renumber, dim3(rgrid), dim3(256), 0, dRecords, (const ZsFselWords *)dWords, (const uint64_t *)dPrefix, (const uint32_t *)d.dList,
            dTable, dFirstRecord, dResult);
     return c->launched();
 }
@@ -201,38 +192,19 @@ extern "C" int zsmi_seekableFindQueryFramesResident(zsmi_ctx *c, const zsmi_seek
     if (const int e = c->bind()) return e;
     return findselRun(c, sk, dFirstRecord, delim, q, dFrames, dFrameCount, maxFrames, dWork, workCapacity, dRecords, dHits, capacity, dResult);
 }
-// host arrays in and out, one wait: firstRecord, the list and its count go up, the body above runs with a work buffer of the context's of
-// the work bound of frameCount frames, the result words and the staged numbers come down.  The staging of the numbers: capacity, or what
-// the listed content can hold at most - its bytes / the shortest pattern
+// host arrays in and out (find.hip's findStage): the count goes up in front of the result words and the list behind them, the body above
+// runs with a work buffer of the context's of the work bound of frameCount frames.  The staging of the numbers: capacity, or what the
+// listed content can hold at most - its bytes / the shortest pattern
 extern "C" int zsmi_seekableFindQueryFramesHost(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim, const zsmi_findQuery *q,
                                                 const uint32_t *frames, uint32_t frameCount, uint64_t *records, uint8_t *hits, size_t capacity, uint64_t *result)
 {
     const uint64_t count = frameCount;
     if (const int e = findselCheck(c, sk, firstRecord, nFrames, delim, q, frames, &count, frameCount, true, nullptr, 0, records, capacity, result)) return e;
-    if (const int e = c->bind()) return e;
     const uint64_t bound = zsmi_seekableFindFramesWorkBound(sk, frameCount);
     const size_t room = (size_t)std::min<uint64_t>(capacity, bound / findQueryShortest(q));
-    // staging: firstRecord [nFrames + 1], the count, dResult [4], the list [frameCount]; the numbers [room], the sets [room]
-    const size_t words = (size_t)nFrames + 1 + 1 + 4;
-    if (!c->sSizes.reserve(words * sizeof(uint64_t) + (size_t)frameCount * sizeof(uint32_t)) || !c->sDst.reserve(room * (sizeof(uint64_t) + 1) + 64) ||
-        !c->seek.dDec.reserve(bound + 64)) return ZSMI_error_memory_allocation;
-    uint64_t *dFirst = (uint64_t *)c->sSizes.p, *dCount = dFirst + nFrames + 1, *dResult = dCount + 1, *dRecords = (uint64_t *)c->sDst.p;
-    uint32_t *dFrames = (uint32_t *)(dResult + 4);
-    uint8_t *dHits = (uint8_t *)(dRecords + room);
-    int rc = c->toDevice(dFirst, firstRecord, ((size_t)nFrames + 1) * sizeof(uint64_t));
-    if (!rc) rc = c->toDevice(dCount, &count, sizeof count);
-    if (!rc && frameCount) rc = c->toDevice(dFrames, frames, (size_t)frameCount * sizeof(uint32_t));
-    if (!rc) rc = findselRun(c, sk, dFirst, delim, q, dFrames, dCount, frameCount, c->seek.dDec.p, bound, room ? dRecords : nullptr, room && hits ? dHits : nullptr, room, dResult);
-    std::vector<uint64_t> numbers(room);
-    std::vector<uint8_t> sets(room);
-    if (!rc) rc = c->toHost(result, dResult, 4 * sizeof(uint64_t));
-    if (!rc && room) rc = c->toHost(numbers.data(), dRecords, room * sizeof(uint64_t));
-    if (!rc && room && hits) rc = c->toHost(sets.data(), dHits, room);
-    const int waited = c->wait();                                                  // (whatever was queued, a failed call included)
-    if (rc || waited) return rc ? rc : waited;
-    if (result[0] <= 0ull - (uint64_t)ZSMI_error_maxCode && result[1] && result[1] <= room) {
-        memcpy(records, numbers.data(), (size_t)result[1] * sizeof(uint64_t));
-        if (hits) memcpy(hits, sets.data(), (size_t)result[1]);
-    }
-    return 0;
+    return findStage(c, firstRecord, nFrames, bound, room, true, 1, (size_t)frameCount * sizeof(uint32_t), records, hits, result, [&](const FindStaged &s) {
+        int rc = c->toDevice(s.dFront, &count, sizeof count);
+        if (!rc && frameCount) rc = c->toDevice(s.dBack, frames, (size_t)frameCount * sizeof(uint32_t));
+        return rc ? rc : findselRun(c, sk, s.dFirst, delim, q, (const uint32_t *)s.dBack, s.dFront, frameCount, s.dWork, bound, s.dRecords, s.dHits, room, s.dResult);
+    });
 }

@@ -1,9 +1,9 @@
 // findquery.hip -- find records by several patterns (zsmi_findquery.h states the rule; zsmi_findRecordsQuery runs it serially on the
 // host): text in device memory, or a window of frames of a record archive, and a query of up to 8 literal patterns, a mode (any, all, none)
 // and the ASCII case-folding flag -> the ascending numbers of the records whose hit set satisfies the mode, and the hit sets, in device
-// memory.  The device calls only queue work.  The single-pattern search of find.hip is left as it is; this file takes from it the tile
-// shape, the shared-memory layout (ZsFindShared), zs_find_open, the scratch layout (FindTiles, findReserve) and, on an archive, the decode
-// half (findDecode).
+// memory.  The device calls only queue work.  find.hip is the family's base: this file calls its tile loads, its emit head and tail,
+// zs_find_open, its shared-memory layout (ZsFindShared), its scratch layout and scans and, on an archive, its checks, window sequence and
+// staging; the tile analysis, the count kernel and the carry kernel are its own.
 //
 // What differs from find.hip is WHERE a record is decided: at its END, by the lane that owns its delimiter, not at its first occurrence -
 // `none` lists records without any occurrence, `all` needs the whole record's set.  The state that crosses a border is the 8-bit SET of
@@ -34,7 +34,8 @@
 #include "zsmi_findquery.h"       // the rule: zs_findq_check, zs_findq_records, zs_findq_listed
 #include <algorithm>
 // From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE, ZsSplitBytes16; records.hip -
-// zs_rec_mask16; find.hip - ZsFindShared, zs_find_open, zs_find_pop4, FindTiles, findReserve, findCheck's order, findDecode.
+// zs_rec_mask16; find.hip - ZsFindShared, zs_find_load, zs_find_open, zs_find_pop4, zs_find_emit_head, zs_find_emit_tail, zs_find_emit_open,
+// FindTiles, findReserve, findScans, findCheck, FindDecoded, findWindow, FindStaged, findStage, zsmi_seekableFindWorkBound.
 
 // the query, by value in the kernels' arguments: pattern j is b[at[j], at[j] + m[j]), folded where the flag is set
 struct ZsFindQuery { uint32_t K, mode, fold, longest; uint16_t m[ZSMI_FIND_MAX_PATTERNS], at[ZSMI_FIND_MAX_PATTERNS]; uint8_t b[ZS_FIND_MAX_PATTERN]; };
@@ -64,30 +65,17 @@ __device__ __forceinline__ uint32_t zs_findq_set(uint64_t lo, uint64_t hi, uint3
 }
 // The masks of tile `tile`: bit k of dm[s] / km[s] stands for the byte at tile * ZS_SPLIT_TILE + s * 4096 + 16 * threadIdx.x + k - it is
 // the delimiter / the record that ends there is listed, given `carry` as the set in front of the tile; byte k of lo[s], hi[s] (k - 8) is
-// the set of the patterns that occur at that byte; in[s]: the set in front of the lane's 16 bytes.  The loads are find.hip's: 16 bytes a
-// lane, the four steps' issued together; the text's last tile, unless it is a whole one, and every halo go byte by byte - no byte at or
-// behind src + size is read, is a delimiter or belongs to an occurrence.  out: the set behind the tile; occs: the lane's occurrences
+// the set of the patterns that occur at that byte; in[s]: the set in front of the lane's 16 bytes.  The loads are zs_find_load's; every
+// halo goes byte by byte too - no byte at or behind src + size is read, is a delimiter or belongs to an occurrence.  out: the set behind
+// the tile; occs: the lane's occurrences
 struct ZsFindqMasks { uint64_t lo[4], hi[4]; uint32_t dm[4], km[4], in[4], out, occs; bool anyDelim; };
 __device__ __forceinline__ void zs_findq_tile(const uint8_t *__restrict__ src, uint64_t size, uint32_t delim, const ZsFindQuery &Q, uint64_t tile, uint32_t carry,
                                               ZsFindShared &sh, ZsFindqMasks &k)
 {
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u, K = Q.K;
-    const uint64_t tileAt = tile * ZS_SPLIT_TILE, base = tileAt + 16u * tid;
-    const bool whole = size - tileAt >= ZS_SPLIT_TILE;
+    const uint64_t tileAt = tile * ZS_SPLIT_TILE;
     ZsSplitBytes16 own[4], low[4];
-    if (whole) {
-        #pragma unroll
-        for (uint32_t s = 0; s < 4; s++) __builtin_memcpy(&own[s], src + base + s * 4096u, 16);
-    } else {
-        for (uint32_t s = 0; s < 4; s++) {
-            const uint64_t b = base + s * 4096u;
-            for (uint32_t w = 0; w < 4; w++) {
-                uint32_t v = 0;
-                for (uint32_t j = 0; j < 4; j++) if (b + 4u * w + j < size) v |= (uint32_t)src[b + 4u * w + j] << (8u * j);
-                own[s].w[w] = v;
-            }
-        }
-    }
+    const bool whole = zs_find_load(src, size, tile, own);
     #pragma unroll
     for (uint32_t s = 0; s < 4; s++) {
         #pragma unroll
@@ -225,7 +213,7 @@ k_findq_carry(uint32_t *__restrict__ flags, uint32_t *__restrict__ kept, uint32_
         }
         const uint64_t delims = __ballot(segDelim);
         uint32_t front = 0, behind = 0;
-        for (uint32_t b = 0; b < K; b++) {
+        for (uint32_t b = 0; b < K; b++) {                                 // (zs_findq_tile's composition, without its skip of a pattern no lane holds: DESIGN.md, "Find records")
             const uint64_t tails = __ballot((segTail >> b) & 1u);
             front |= zs_find_open(tails, delims, below, false) ? 1u << b : 0u;
             behind |= zs_find_open(tails, delims, ~0ull, false) ? 1u << b : 0u;
@@ -265,57 +253,16 @@ k_findq_emit(const uint8_t *__restrict__ src, uint64_t size, uint32_t delim, con
              const uint32_t *__restrict__ code, uint64_t *__restrict__ records, uint8_t *__restrict__ hits, uint64_t capacity, uint64_t *__restrict__ result)
 {
     __shared__ ZsFindShared sh;
-    __shared__ uint32_t keptOf[4][4], delimsOf[4][4];
-    const uint32_t failed = code ? *code : 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint64_t total = slotBase[tiles];
-        result[0] = failed ? 0ull - (uint64_t)failed : total;
-        result[1] = failed ? 0ull : (total < capacity ? total : capacity);
-        result[2] = failed ? 0ull : occBase[tiles];
-        result[3] = size;
-    }
-    if (failed || blockIdx.x >= tiles) return;                             // (the same for the whole workgroup)
-    const uint64_t slot0 = slotBase[blockIdx.x];
-    if (slot0 >= capacity || slotBase[blockIdx.x + 1u] == slot0) return;   // (the slots ascend with the tiles; capacity 0: nothing to write.  A tile that lists no record - most tiles of a rare pattern - is not read again)
+    uint64_t slot0;
+    if (!zs_find_emit_head(code, slotBase, tiles, capacity, size, [&] { return occBase[tiles]; }, true, result, slot0)) return;
     ZsFindqMasks k;
     zs_findq_tile(src, size, delim, Q, blockIdx.x, flags[blockIdx.x] >> 24, sh, k);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    uint32_t keptBefore[4], delimsBefore[4];
-    #pragma unroll
-    for (uint32_t s = 0; s < 4; s++) {
-        const uint32_t nk = (uint32_t)__popc(k.km[s]), nd = (uint32_t)__popc(k.dm[s]), inclK = wave_incl_scan(nk), inclD = wave_incl_scan(nd);
-        keptBefore[s] = inclK - nk; delimsBefore[s] = inclD - nd;
-        if (lane == 63u) { keptOf[s][wave] = inclK; delimsOf[s][wave] = inclD; }
-    }
-    __syncthreads();
     const uint64_t first = (base ? *base : 0ull) + recBase[blockIdx.x];
-    uint32_t keptAt = 0, delimsAt = 0;                                     // those of the steps in front
-    #pragma unroll
-    for (uint32_t s = 0; s < 4; s++) {
-        uint32_t aheadK = 0, aheadD = 0, allK = 0, allD = 0;
-        #pragma unroll
-        for (uint32_t w = 0; w < 4; w++) {
-            aheadK += w < wave ? keptOf[s][w] : 0u; allK += keptOf[s][w];
-            aheadD += w < wave ? delimsOf[s][w] : 0u; allD += delimsOf[s][w];
-        }
-        uint64_t slot = slot0 + keptAt + aheadK + keptBefore[s];
-        const uint64_t rec = first + delimsAt + aheadD + delimsBefore[s];
-        for (uint32_t bits = k.km[s]; bits; bits &= bits - 1u, slot++) {
-            const uint32_t at = (uint32_t)__ffs((int)bits) - 1u;
-            if (slot < capacity) {
-                records[slot] = rec + (uint32_t)__popc(k.dm[s] & ((1u << at) - 1u));
-                if (hits) hits[slot] = (uint8_t)zs_findq_set(k.lo[s], k.hi[s], k.dm[s], at, k.in[s]);
-            }
-        }
-        keptAt += allK; delimsAt += allD;
-    }
-    if (blockIdx.x + 1u == tiles && threadIdx.x == 0 && src[size - 1u] != (uint8_t)delim && zs_findq_listed(k.out, Q.mode, Q.K)) {
-        const uint64_t slot = slot0 + keptAt;                              // the text's unterminated last record: behind every record end of the last tile
-        if (slot < capacity) {
-            records[slot] = first + delimsAt;
-            if (hits) hits[slot] = (uint8_t)k.out;
-        }
-    }
+    const ZsFindEmitted n = zs_find_emit_tail(k.dm, k.km, slot0, first, capacity, records, [&](uint64_t slot, uint32_t s, uint32_t at) {
+        if (hits) hits[slot] = (uint8_t)zs_findq_set(k.lo[s], k.hi[s], k.dm[s], at, k.in[s]);
+    });
+    if (blockIdx.x + 1u == tiles && threadIdx.x == 0 && src[size - 1u] != (uint8_t)delim && zs_findq_listed(k.out, Q.mode, Q.K))
+        zs_find_emit_open(slot0 + n.kept, first + n.delims, capacity, records, [&](uint64_t slot) { if (hits) hits[slot] = (uint8_t)k.out; });
 }
 
 // ---- host ----
@@ -356,9 +303,7 @@ static int findqText(zsmi_ctx *c, const void *dText, uint64_t size, int delim, c
         LAUNCH(c, "k_findq_count", k_findq_count, dim3(t.tiles), dim3(256), 0, (const uint8_t *)dText, size, (uint32_t)delim, Q, t.tiles, t.dDelims, t.dOccs, t.dKept, t.dFlags);
         LAUNCH(c, "k_findq_carry", k_findq_carry, dim3(1), dim3(1024), 0, t.dFlags, t.dKept, t.tiles, Q.K, Q.mode);
     }
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dDelims, nullptr, t.tiles, 1u, nullptr, t.dRecBase)) return e;
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dKept, nullptr, t.tiles, 1u, nullptr, t.dSlotBase)) return e;
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dOccs, nullptr, t.tiles, 1u, nullptr, t.dOccBase)) return e;
+    if (const int e = findScans(c, t, true)) return e;
     LAUNCH(c, "k_findq_emit", k_findq_emit, dim3(std::max(t.tiles, 1u)), dim3(256), 0, (const uint8_t *)dText, size, (uint32_t)delim, Q, t.tiles, (const uint32_t *)t.dFlags,
            (const uint64_t *)t.dRecBase, (const uint64_t *)t.dSlotBase, (const uint64_t *)t.dOccBase, dBase, dCode, dRecords, dHits, capacity, dResult);
     return c->launched();
@@ -376,65 +321,28 @@ extern "C" int zsmi_findRecordsQueryDevice(zsmi_ctx *c, const void *dSrc, uint64
     if (const int e = findReserve(c, srcSize, 0, 0, t)) return e;
     return findqText(c, dSrc, srcSize, delim, findQuery(q), dBase, nullptr, dRecords, dHits, capacity, dResult, t);
 }
-// the header's checks of the archive calls, in find.hip's order with the query where the pattern stood
-static int findqCheck(const zsmi_ctx *c, const zsmi_seekable *sk, const void *firstRecord, uint32_t nFrames, int delim, const zsmi_findQuery *q,
-                      uint32_t firstFrame, uint32_t frameCount, bool ownWork, const void *work, uint64_t workCapacity, const void *records, uint64_t capacity, const void *result)
-{
-    if (!c) return ZSMI_error_init_missing;
-    if (!sk || !result || !q || !firstRecord || (capacity && !records)) return ZSMI_error_GENERIC;
-    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
-    if (const int e = zs_findq_check(delim, q)) return e;
-    if (nFrames != sk->t.n || (uint64_t)firstFrame + frameCount > nFrames) return ZSMI_error_parameter_outOfBound;
-    const uint64_t bound = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
-    if (!ownWork && bound && !work) return ZSMI_error_GENERIC;
-    if (!ownWork && workCapacity < bound) return ZSMI_error_dstSize_tooSmall;
-    return 0;
-}
-// the launch sequence on an archive, its arguments checked by the caller: find.hip's decode half, then findqText
-static int findqWindow(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, int delim, const zsmi_findQuery *q, uint32_t firstFrame,
-                       uint32_t frameCount, void *dWork, uint64_t *dRecords, uint8_t *dHits, uint64_t capacity, uint64_t *dResult)
-{
-    if (const int e = c->bind()) return e;
-    if (frameCount == 0) return c->fill(dResult, 0, 4 * sizeof(uint64_t));
-    FindDecoded w;
-    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, w)) return e;
-    return findqText(c, dWork, w.bytes, delim, findQuery(q), dFirstRecord + firstFrame, w.dCode, dRecords, dHits, capacity, dResult, w.t);
-}
 extern "C" int zsmi_seekableFindQueryResident(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
                                               const zsmi_findQuery *q, uint32_t firstFrame, uint32_t frameCount, void *dWork, uint64_t workCapacity,
                                               uint64_t *dRecords, uint8_t *dHits, uint64_t capacity, uint64_t *dResult)
 {
-    if (const int e = findqCheck(c, sk, dFirstRecord, nFrames, delim, q, firstFrame, frameCount, false, dWork, workCapacity, dRecords, capacity, dResult)) return e;
-    return findqWindow(c, sk, dFirstRecord, delim, q, firstFrame, frameCount, dWork, dRecords, dHits, capacity, dResult);
+    if (const int e = findCheck(c, sk, dFirstRecord, nFrames, q, [&] { return zs_findq_check(delim, q); }, firstFrame, frameCount, false, dWork, workCapacity, dRecords,
+                                capacity, dResult)) return e;
+    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, 0, [&](const FindDecoded &w) {
+        return findqText(c, dWork, w.bytes, delim, findQuery(q), dFirstRecord + firstFrame, w.dCode, dRecords, dHits, capacity, dResult, w.t);
+    });
 }
-// host arrays in and out, as zsmi_seekableFindRecordsHost.  A record that holds an occurrence holds the shortest pattern's bytes of its own,
-// so any and all name at most bytes / that many records; a `none` query can name a record a byte.  The staged numbers are that, or
-// capacity, and a byte of set each behind them
+// host arrays in and out (find.hip's findStage).  A record that holds an occurrence holds the shortest pattern's bytes of its own, so any
+// and all name at most bytes / that many records; a `none` query can name a record a byte.  The staged numbers are that, or capacity,
+// and a byte of set each behind them
 extern "C" int zsmi_seekableFindQueryHost(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
                                           const zsmi_findQuery *q, uint32_t firstFrame, uint32_t frameCount,
                                           uint64_t *records, uint8_t *hits, size_t capacity, uint64_t *result)
 {
-    if (const int e = findqCheck(c, sk, firstRecord, nFrames, delim, q, firstFrame, frameCount, true, nullptr, 0, records, capacity, result)) return e;
+    if (const int e = findCheck(c, sk, firstRecord, nFrames, q, [&] { return zs_findq_check(delim, q); }, firstFrame, frameCount, true, nullptr, 0, records, capacity, result))
+        return e;
     const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
     const size_t room = (size_t)std::min<uint64_t>(capacity, q->mode == ZSMI_find_none ? bytes : bytes / findQueryShortest(q));
-    if (const int e = c->bind()) return e;
-    // staging: firstRecord [nFrames + 1], dResult [4]; the numbers [room], the sets [room]
-    const size_t words = (size_t)nFrames + 1 + 4;
-    if (!c->sSizes.reserve(words * sizeof(uint64_t)) || !c->sDst.reserve(room * (sizeof(uint64_t) + 1) + 64) || !c->seek.dDec.reserve(bytes + 64)) return ZSMI_error_memory_allocation;
-    uint64_t *dFirst = (uint64_t *)c->sSizes.p, *dResult = dFirst + nFrames + 1, *dRecords = (uint64_t *)c->sDst.p;
-    uint8_t *dHits = (uint8_t *)(dRecords + room);
-    int rc = c->toDevice(dFirst, firstRecord, ((size_t)nFrames + 1) * sizeof(uint64_t));
-    if (!rc) rc = findqWindow(c, sk, dFirst, delim, q, firstFrame, frameCount, c->seek.dDec.p, room ? dRecords : nullptr, room && hits ? dHits : nullptr, room, dResult);
-    std::vector<uint64_t> numbers(room);
-    std::vector<uint8_t> sets(room);
-    if (!rc) rc = c->toHost(result, dResult, 4 * sizeof(uint64_t));
-    if (!rc && room && frameCount) rc = c->toHost(numbers.data(), dRecords, room * sizeof(uint64_t));
-    if (!rc && room && frameCount && hits) rc = c->toHost(sets.data(), dHits, room);
-    const int waited = c->wait();                                                  // (whatever was queued, a failed call included)
-    if (rc || waited) return rc ? rc : waited;
-    if (result[1] && result[1] <= room) {
-        memcpy(records, numbers.data(), (size_t)result[1] * sizeof(uint64_t));
-        if (hits) memcpy(hits, sets.data(), (size_t)result[1]);
-    }
-    return 0;
+    return findStage(c, firstRecord, nFrames, bytes, room, true, 0, 0, records, hits, result, [&](const FindStaged &s) {
+        return zsmi_seekableFindQueryResident(c, sk, s.dFirst, nFrames, delim, q, firstFrame, frameCount, s.dWork, bytes, s.dRecords, s.dHits, room, s.dResult);
+    });
 }

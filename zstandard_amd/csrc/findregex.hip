@@ -1,8 +1,9 @@
 // findregex.hip -- find records by regular expression (zsmi_regex.h states the rule and holds the compiler; zsmi_findRecordsRegex runs the
 // rule serially on the host): text in device memory, or a window of frames of a record archive, and a program - the minimal DFA of a
 // pattern, compiled on the host - -> the ascending numbers of the records the program accepts (or, inverted, of the others), in device
-// memory.  The device calls only queue work.  The searches of find.hip and findquery.hip are left as they are; this file takes from them
-// the tile shape, the loads, the scratch layout (FindTiles, findReserve) and, on an archive, the decode half (findDecode).
+// memory.  The device calls only queue work.  find.hip is the family's base: this file calls its tile loads, its emit head and tail, its
+// scratch layout - with the extra region a tile this search needs - and scans and, on an archive, its checks, window sequence and staging;
+// the tile analysis, the count kernel and the carry kernel are its own.
 //
 // A record is decided at its END, by the lane that owns its delimiter, as in findquery.hip.  What crosses a border is a state FUNCTION
 // where the query search carries an 8-bit set: behind a stretch of text the state is hasDelimiter ? TAILSTATE : F(in) - F the stretch's
@@ -28,7 +29,8 @@
 //   scanOffsets x 2 over the delimiters (a tile's record base) and over kept (a tile's output slot)
 //   k_findre_emit   k_findq_emit's shape: tiles that list a record below capacity only; the masks again from the carried state; ranks by
 //                   wave_incl_scan; one lane writes dResult - [2] is the delimiter total plus the open end
-// Scratch: find.hip's 40 bytes a tile in the seekable scratch and, behind them, 72 more: OUT functions [64 a tile], HEADMASKs [8 a tile].
+// Scratch: find.hip's 40 bytes a tile in the seekable scratch and, behind them, 72 more - findReserve's extra region: OUT functions [64 a
+// tile], HEADMASKs [8 a tile].
 // Every store is a vector store from plain C++.
 
 #include "zsmi_status.h"
@@ -37,7 +39,8 @@
 #include "zsmi_regex.h"           // the rule: zs_regex_check, zs_regex_records, zs_regex_listed; the compiler
 #include <algorithm>
 // From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE, ZsSplitBytes16; records.hip -
-// zs_rec_mask16; seekable.hip - ZsSeekItem; find.hip - zs_find_pop4, FindTiles, findReserve, findCheck's order, findDecodeHead, findDecode.
+// zs_rec_mask16; find.hip - zs_find_load, zs_find_pop4, zs_find_emit_head, zs_find_emit_tail, zs_find_emit_open, FindTiles, findReserve,
+// findScans, findCheck, FindDecoded, findWindow, FindStaged, findStage, zsmi_seekableFindWorkBound.
 
 static const uint32_t kFindreHasDelim = 1u, kFindreOpenEnd = 2u;          // a tile's flags word; bits 8 .. 15: the state entering the tile (k_findre_carry)
 
@@ -57,9 +60,8 @@ struct ZsFindreShared {
     uint32_t sums[4][2];
 };
 // The masks of tile `tile`: bit k of dm[s] / km[s] stands for the byte at tile * ZS_SPLIT_TILE + s * 4096 + 16 * threadIdx.x + k - it is
-// the delimiter / the record that ends there is listed, given `entry` as the state in front of the tile.  The loads are find.hip's: 16
-// bytes a lane, the four steps' issued together; the text's last tile, unless it is a whole one, goes byte by byte - no byte at or behind
-// src + size is read, is a delimiter or is fed to the program.  out: the state behind the tile.  COUNT: besides, fnOut - the tile's
+// the delimiter / the record that ends there is listed, given `entry` as the state in front of the tile.  The loads are zs_find_load's:
+// no byte at or behind src + size is read, is a delimiter or is fed to the program.  out: the state behind the tile.  COUNT: besides, fnOut - the tile's
 // function of state min(threadIdx.x, nStates - 1), valid in the first wavefront - and headMask, valid there too
 struct ZsFindreMasks { uint32_t dm[4], km[4], out, fnOut; uint64_t headMask; bool anyDelim; };
 template <bool COUNT>
@@ -69,22 +71,9 @@ __device__ __forceinline__ void zs_findre_tile(const uint8_t *__restrict__ src, 
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t n = P.nStates, nc = P.nClasses, start = P.start, invert = P.flags & ZSMI_REGEX_INVERT;
     const uint64_t accept = P.accept;
-    const uint64_t tileAt = tile * ZS_SPLIT_TILE, base = tileAt + 16u * tid;
-    const bool whole = size - tileAt >= ZS_SPLIT_TILE;
+    const uint64_t tileAt = tile * ZS_SPLIT_TILE;
     ZsSplitBytes16 own[4];
-    if (whole) {
-        #pragma unroll
-        for (uint32_t s = 0; s < 4; s++) __builtin_memcpy(&own[s], src + base + s * 4096u, 16);
-    } else {
-        for (uint32_t s = 0; s < 4; s++) {
-            const uint64_t b = base + s * 4096u;
-            for (uint32_t w = 0; w < 4; w++) {
-                uint32_t v = 0;
-                for (uint32_t j = 0; j < 4; j++) if (b + 4u * w + j < size) v |= (uint32_t)src[b + 4u * w + j] << (8u * j);
-                own[s].w[w] = v;
-            }
-        }
-    }
+    zs_find_load(src, size, tile, own);
     sh.classOf[tid] = P.classOf[tid];
     for (uint32_t i = tid; i < n * nc; i += 256u) sh.next[i] = P.next[i];
     __syncthreads();
@@ -282,52 +271,15 @@ k_findre_emit(const uint8_t *__restrict__ src, uint64_t size, uint32_t delim, co
               uint64_t *__restrict__ records, uint64_t capacity, uint64_t *__restrict__ result)
 {
     __shared__ ZsFindreShared sh;
-    __shared__ uint32_t keptOf[4][4], delimsOf[4][4];
-    const uint32_t failed = code ? *code : 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint64_t total = slotBase[tiles];
-        result[0] = failed ? 0ull - (uint64_t)failed : total;
-        result[1] = failed ? 0ull : (total < capacity ? total : capacity);
-        result[2] = failed ? 0ull : recBase[tiles] + (tiles && (flags[tiles - 1u] & kFindreOpenEnd) ? 1ull : 0ull);
-        result[3] = size;
-    }
-    if (failed || blockIdx.x >= tiles) return;                             // (the same for the whole workgroup)
-    const uint64_t slot0 = slotBase[blockIdx.x];
-    if (slot0 >= capacity || slotBase[blockIdx.x + 1u] == slot0) return;   // (the slots ascend with the tiles; capacity 0: nothing to write.  A tile that lists no record is not read again)
+    uint64_t slot0;
+    if (!zs_find_emit_head(code, slotBase, tiles, capacity, size, [&] { return recBase[tiles] + (tiles && (flags[tiles - 1u] & kFindreOpenEnd) ? 1ull : 0ull); }, true, result, slot0)) return;
     ZsFindreMasks k;
     const uint32_t f = flags[blockIdx.x];
     zs_findre_tile<false>(src, size, delim, P, blockIdx.x, (f >> 8) & 0xFFu, sh, k);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    uint32_t keptBefore[4], delimsBefore[4];
-    #pragma unroll
-    for (uint32_t s = 0; s < 4; s++) {
-        const uint32_t nk = (uint32_t)__popc(k.km[s]), nd = (uint32_t)__popc(k.dm[s]), inclK = wave_incl_scan(nk), inclD = wave_incl_scan(nd);
-        keptBefore[s] = inclK - nk; delimsBefore[s] = inclD - nd;
-        if (lane == 63u) { keptOf[s][wave] = inclK; delimsOf[s][wave] = inclD; }
-    }
-    __syncthreads();
     const uint64_t first = (base ? *base : 0ull) + recBase[blockIdx.x];
-    uint32_t keptAt = 0, delimsAt = 0;                                     // those of the steps in front
-    #pragma unroll
-    for (uint32_t s = 0; s < 4; s++) {
-        uint32_t aheadK = 0, aheadD = 0, allK = 0, allD = 0;
-        #pragma unroll
-        for (uint32_t w = 0; w < 4; w++) {
-            aheadK += w < wave ? keptOf[s][w] : 0u; allK += keptOf[s][w];
-            aheadD += w < wave ? delimsOf[s][w] : 0u; allD += delimsOf[s][w];
-        }
-        uint64_t slot = slot0 + keptAt + aheadK + keptBefore[s];
-        const uint64_t rec = first + delimsAt + aheadD + delimsBefore[s];
-        for (uint32_t bits = k.km[s]; bits; bits &= bits - 1u, slot++) {
-            const uint32_t at = (uint32_t)__ffs((int)bits) - 1u;
-            if (slot < capacity) records[slot] = rec + (uint32_t)__popc(k.dm[s] & ((1u << at) - 1u));
-        }
-        keptAt += allK; delimsAt += allD;
-    }
-    if (threadIdx.x == 0 && (f & kFindreOpenEnd) && zs_regex_listed(P.accept, P.flags & ZSMI_REGEX_INVERT, k.out)) {
-        const uint64_t slot = slot0 + keptAt;                              // the text's unterminated last record: behind every record end of the last tile
-        if (slot < capacity) records[slot] = first + delimsAt;
-    }
+    const ZsFindEmitted n = zs_find_emit_tail(k.dm, k.km, slot0, first, capacity, records, [](uint64_t, uint32_t, uint32_t) {});
+    if (threadIdx.x == 0 && (f & kFindreOpenEnd) && zs_regex_listed(P.accept, P.flags & ZSMI_REGEX_INVERT, k.out))
+        zs_find_emit_open(slot0 + n.kept, first + n.delims, capacity, records, [](uint64_t) {});
 }
 
 // ---- host ----
@@ -344,34 +296,22 @@ extern "C" size_t zsmi_findRecordsRegex(const void *src, size_t srcSize, int del
     if (srcSize && !src) return ZSMI_ERR(ZSMI_error_srcSize_wrong);
     return (size_t)zs_regex_records((const uint8_t *)src, srcSize, (uint8_t)delim, prog, base, records, capacity, textRecords);
 }
-// what the search lays behind find.hip's words of a text's tiles in the seekable scratch (16-aligned): OUT functions [64 a tile],
-// HEADMASKs [8 a tile].  findreRoom: the bytes to reserve for a text of `size` bytes behind `head` bytes, BEFORE findReserve or findDecode
-// lay out theirs (a buffer that grows later would move); findrePlace: the places, checked against what the buffer holds
-struct FindreTiles { uint8_t *dOutFn; uint64_t *dHeadMask; };
-static size_t findreRoom(uint64_t size, size_t head)
-{
-    const size_t n = (size_t)((size + ZS_SPLIT_TILE - 1) / ZS_SPLIT_TILE);
-    return head + 3 * (n + 1) * sizeof(uint64_t) + 4 * n * sizeof(uint32_t) + 16 + n * (64 + sizeof(uint64_t));
-}
-static int findrePlace(const zsmi_ctx *c, const FindTiles &t, FindreTiles &r)
-{
-    const uintptr_t end = (uintptr_t)(t.dFlags + t.tiles), at = (end + 15u) & ~(uintptr_t)15u;
-    r.dOutFn = (uint8_t *)at; r.dHeadMask = (uint64_t *)(r.dOutFn + (size_t)t.tiles * 64u);
-    const uintptr_t last = (uintptr_t)(r.dHeadMask + t.tiles);
-    return last <= (uintptr_t)c->seek.dMeta.p + c->seek.dMeta.cap ? 0 : ZSMI_error_memory_allocation;
-}
+// what the search lays behind find.hip's words of a text's tiles in the seekable scratch, findReserve's extra region: OUT functions
+// [64 a tile], HEADMASKs [8 a tile]
+static const size_t kFindreExtraPerTile = 64 + sizeof(uint64_t);
 // the launch sequence over dText[0, size), its arguments checked and its scratch reserved by the caller
 static int findreText(zsmi_ctx *c, const void *dText, uint64_t size, int delim, const zsmi_regexProgram &P, const uint64_t *dBase, const uint32_t *dCode,
-                      uint64_t *dRecords, uint64_t capacity, uint64_t *dResult, const FindTiles &t, const FindreTiles &r)
+                      uint64_t *dRecords, uint64_t capacity, uint64_t *dResult, const FindTiles &t)
 {
+    uint8_t *dOutFn = t.dExtra;
+    uint64_t *dHeadMask = (uint64_t *)(dOutFn + (size_t)t.tiles * 64u);
     if (t.tiles) {
         LAUNCH(c, "k_findre_count", k_findre_count, dim3(t.tiles), dim3(256), 0, (const uint8_t *)dText, size, (uint32_t)delim, P, t.tiles, t.dDelims, t.dKept, t.dFlags,
-               r.dHeadMask, r.dOutFn);
-        LAUNCH(c, "k_findre_carry", k_findre_carry, dim3(1), dim3(1024), 0, (const uint8_t *)r.dOutFn, (const uint64_t *)r.dHeadMask, t.dFlags, t.dKept, t.tiles,
+               dHeadMask, dOutFn);
+        LAUNCH(c, "k_findre_carry", k_findre_carry, dim3(1), dim3(1024), 0, (const uint8_t *)dOutFn, (const uint64_t *)dHeadMask, t.dFlags, t.dKept, t.tiles,
                P.nStates, P.start, P.accept, P.flags & ZSMI_REGEX_INVERT);
     }
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dDelims, nullptr, t.tiles, 1u, nullptr, t.dRecBase)) return e;
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint32_t *)t.dKept, nullptr, t.tiles, 1u, nullptr, t.dSlotBase)) return e;
+    if (const int e = findScans(c, t, false)) return e;
     LAUNCH(c, "k_findre_emit", k_findre_emit, dim3(std::max(t.tiles, 1u)), dim3(256), 0, (const uint8_t *)dText, size, (uint32_t)delim, P, t.tiles, (const uint32_t *)t.dFlags,
            (const uint64_t *)t.dRecBase, (const uint64_t *)t.dSlotBase, dBase, dCode, dRecords, capacity, dResult);
     return c->launched();
@@ -386,70 +326,30 @@ extern "C" int zsmi_findRecordsRegexDevice(zsmi_ctx *c, const void *dSrc, uint64
     if (const int e = c->bind()) return e;
     if (srcSize == 0) return c->fill(dResult, 0, 4 * sizeof(uint64_t));
     FindTiles t;
-    FindreTiles r;
-    if (srcSize / ZS_SPLIT_TILE >= 0x7FFFFFFFull || !c->seek.dMeta.reserve(findreRoom(srcSize, 0))) return ZSMI_error_memory_allocation;
-    if (const int e = findReserve(c, srcSize, 0, 0, t)) return e;
-    if (const int e = findrePlace(c, t, r)) return e;
-    return findreText(c, dSrc, srcSize, delim, *prog, dBase, nullptr, dRecords, capacity, dResult, t, r);
-}
-// the header's checks of the archive calls, in find.hip's order with the program where the pattern stood
-static int findreCheck(const zsmi_ctx *c, const zsmi_seekable *sk, const void *firstRecord, uint32_t nFrames, int delim, const zsmi_regexProgram *prog,
-                       uint32_t firstFrame, uint32_t frameCount, bool ownWork, const void *work, uint64_t workCapacity, const void *records, uint64_t capacity, const void *result)
-{
-    if (!c) return ZSMI_error_init_missing;
-    if (!sk || !result || !prog || !firstRecord || (capacity && !records)) return ZSMI_error_GENERIC;
-    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
-    if (const int e = zs_regex_check(delim, prog)) return e;
-    if (nFrames != sk->t.n || (uint64_t)firstFrame + frameCount > nFrames) return ZSMI_error_parameter_outOfBound;
-    const uint64_t bound = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
-    if (!ownWork && bound && !work) return ZSMI_error_GENERIC;
-    if (!ownWork && workCapacity < bound) return ZSMI_error_dstSize_tooSmall;
-    return 0;
-}
-// the launch sequence on an archive, its arguments checked by the caller: find.hip's decode half, then findreText.  The scratch is
-// reserved here for both, in front of the decode half: findDecode's words a frame are findDecodeHead's, and findrePlace checks the outcome
-static int findreWindow(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, int delim, const zsmi_regexProgram *prog, uint32_t firstFrame,
-                        uint32_t frameCount, void *dWork, uint64_t *dRecords, uint64_t capacity, uint64_t *dResult)
-{
-    if (const int e = c->bind()) return e;
-    if (frameCount == 0) return c->fill(dResult, 0, 4 * sizeof(uint64_t));
-    const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
-    if (bytes / ZS_SPLIT_TILE >= 0x7FFFFFFFull || !c->seek.dMeta.reserve(findreRoom(bytes, findDecodeHead(frameCount)))) return ZSMI_error_memory_allocation;
-    FindDecoded w;
-    FindreTiles r;
-    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, w)) return e;
-    if (const int e = findrePlace(c, w.t, r)) return e;
-    return findreText(c, dWork, w.bytes, delim, *prog, dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, w.t, r);
+    if (const int e = findReserve(c, srcSize, 0, 0, t, kFindreExtraPerTile)) return e;
+    return findreText(c, dSrc, srcSize, delim, *prog, dBase, nullptr, dRecords, capacity, dResult, t);
 }
 extern "C" int zsmi_seekableFindRegexResident(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFirstRecord, uint32_t nFrames, int delim,
                                               const zsmi_regexProgram *prog, uint32_t firstFrame, uint32_t frameCount, void *dWork, uint64_t workCapacity,
                                               uint64_t *dRecords, uint64_t capacity, uint64_t *dResult)
 {
-    if (const int e = findreCheck(c, sk, dFirstRecord, nFrames, delim, prog, firstFrame, frameCount, false, dWork, workCapacity, dRecords, capacity, dResult)) return e;
-    return findreWindow(c, sk, dFirstRecord, delim, prog, firstFrame, frameCount, dWork, dRecords, capacity, dResult);
+    if (const int e = findCheck(c, sk, dFirstRecord, nFrames, prog, [&] { return zs_regex_check(delim, prog); }, firstFrame, frameCount, false, dWork, workCapacity, dRecords,
+                                capacity, dResult)) return e;
+    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, kFindreExtraPerTile, [&](const FindDecoded &w) {
+        return findreText(c, dWork, w.bytes, delim, *prog, dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, w.t);
+    });
 }
-// host arrays in and out, as zsmi_seekableFindQueryHost.  As with `none`, a program can list a record a byte: the staged numbers are the
-// window's bytes, or capacity
+// host arrays in and out (find.hip's findStage).  As with `none`, a program can list a record a byte: the staged numbers are the window's
+// bytes, or capacity
 extern "C" int zsmi_seekableFindRegexHost(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *firstRecord, uint32_t nFrames, int delim,
                                           const zsmi_regexProgram *prog, uint32_t firstFrame, uint32_t frameCount,
                                           uint64_t *records, size_t capacity, uint64_t *result)
 {
-    if (const int e = findreCheck(c, sk, firstRecord, nFrames, delim, prog, firstFrame, frameCount, true, nullptr, 0, records, capacity, result)) return e;
+    if (const int e = findCheck(c, sk, firstRecord, nFrames, prog, [&] { return zs_regex_check(delim, prog); }, firstFrame, frameCount, true, nullptr, 0, records, capacity,
+                                result)) return e;
     const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
     const size_t room = (size_t)std::min<uint64_t>(capacity, bytes);
-    if (const int e = c->bind()) return e;
-    // staging: firstRecord [nFrames + 1], dResult [4]; the numbers [room]
-    const size_t words = (size_t)nFrames + 1 + 4;
-    if (!c->sSizes.reserve(words * sizeof(uint64_t)) || !c->sDst.reserve(room * sizeof(uint64_t) + 64) || !c->seek.dDec.reserve(bytes + 64)) return ZSMI_error_memory_allocation;
-    uint64_t *dFirst = (uint64_t *)c->sSizes.p, *dResult = dFirst + nFrames + 1, *dRecords = (uint64_t *)c->sDst.p;
-    int rc = c->toDevice(dFirst, firstRecord, ((size_t)nFrames + 1) * sizeof(uint64_t));
-    if (!rc) rc = findreWindow(c, sk, dFirst, delim, prog, firstFrame, frameCount, c->seek.dDec.p, room ? dRecords : nullptr, room, dResult);
-    std::vector<uint64_t> numbers;
-    if (!rc) { try { numbers.resize(room); } catch (const std::bad_alloc &) { rc = ZSMI_error_memory_allocation; } }
-    if (!rc) rc = c->toHost(result, dResult, 4 * sizeof(uint64_t));
-    if (!rc && room && frameCount) rc = c->toHost(numbers.data(), dRecords, room * sizeof(uint64_t));
-    const int waited = c->wait();                                                  // (whatever was queued, a failed call included)
-    if (rc || waited) return rc ? rc : waited;
-    if (result[1] && result[1] <= room) memcpy(records, numbers.data(), (size_t)result[1] * sizeof(uint64_t));
-    return 0;
+    return findStage(c, firstRecord, nFrames, bytes, room, false, 0, 0, records, nullptr, result, [&](const FindStaged &s) {
+        return zsmi_seekableFindRegexResident(c, sk, s.dFirst, nFrames, delim, prog, firstFrame, frameCount, s.dWork, bytes, s.dRecords, room, s.dResult);
+    });
 }

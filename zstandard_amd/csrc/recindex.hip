@@ -517,7 +517,7 @@ extern "C" int zsmi_seekableIndexRecordsHost(zsmi_ctx *c, const zsmi_seekable *s
     const size_t W = windows.size(), words = (size_t)N + 1 + 4 * std::max<size_t>(W, 1);
     const size_t tilesMost = (size_t)(most / ZS_SPLIT_TILE + 2);
     if (!c->sSizes.reserve(words * sizeof(uint64_t)) || !c->seek.dDec.reserve(most + 64) || !c->dItems.reserve(sizeof(ZsDecItem) * (size_t)mostFrames) ||
-        !c->seek.dMeta.reserve(findDecodeHead(mostFrames) + 3 * (tilesMost + 1) * sizeof(uint64_t) + 4 * tilesMost * sizeof(uint32_t)) ||
+        !c->seek.dMeta.reserve(findDecodeHead(mostFrames) + findTileBytes(tilesMost)) ||
         !c->dScan.reserve(sizeof(uint64_t) * ((std::max<size_t>(mostFrames, tilesMost) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
     uint64_t *dFirst = (uint64_t *)c->sSizes.p, *dResults = dFirst + N + 1;
     std::vector<uint64_t> staged((size_t)N + 1), results(4 * std::max<size_t>(W, 1), 0);
