@@ -389,7 +389,7 @@ def poison_child():
             filled = _lib.fill_scratch(codec.ctx, pattern)
             assert filled["seek"] > 0 and filled["staging"] >= 40, ("the fill is vacuous", filled)
         once(poke, "scratch filled with %#x" % pattern)
-    # the host form in many windows over a small archive (the debug-hook library reads ZSMI_FILTER_WINDOW; the product's windows hold
+    # the host form in many windows over a small archive (the debug-hook library reads ZSMI_ARCHIVE_WINDOW; the product's windows hold
     # 256 MiB of content): a frame a window, a few frames a window, one window - byte for byte the statement's frame
     import os
     from zstandard_amd import SeekableArchive
@@ -397,7 +397,7 @@ def poison_child():
         archive = codec.compress_seekable_frames_host(np.frombuffer(text, dtype=np.uint8), sizes, 3, True)
         want = frame(text, sizes, 10, g, Lg)
         for window in ("1", "9000", "20000", "0"):
-            os.environ["ZSMI_FILTER_WINDOW"] = window
+            os.environ["ZSMI_ARCHIVE_WINDOW"] = window
             sa = SeekableArchive(archive)
             try:
                 sa._open()

@@ -237,8 +237,70 @@ def poison_child():
     print("poison ok")
 
 
+def windows_of(sizes, limit):
+    """the window plan restated: [(first frame, frames)] in ascending order - a window takes frames while its content stays at or below
+    `limit` bytes, and one frame at least (a longer frame is a window of its own)"""
+    at = [int(v) for v in offsets_of(sizes)]
+    n, out, f = len(sizes), [], 0
+    while f < n:
+        g = f + 1
+        while g < n and at[g + 1] - at[f] <= limit:
+            g += 1
+        out.append((f, g - f))
+        f = g
+    return out
+
+
+def windows_child():
+    """run in a process of its own on the debug-hook library (ZSMI_DEBUG_LIB=1), which reads ZSMI_ARCHIVE_WINDOW (the product's windows
+    hold 256 MiB of content): the host rebuild (zsmi_seekableIndexRecordsHost) of archives without an index frame in a frame a window, a
+    few frames a window and one window, on poisoned scratch - the status, the three counts and every entry of the array against the
+    rule; the windows chain through the array and add up the counts.  The launches of k_find_frames - one a window - say that the
+    windows were the plan's: the override cannot be vacuous"""
+    import ctypes, os
+    import _split as S
+    from zstandard_amd import BatchCodec, SeekableArchive, _lib
+    assert _lib.DEBUG
+    L, codec = _lib.lib(), BatchCodec(0)
+    p = ctypes.c_void_p
+    text = seeded_text(3 * TILE + 500, 41)
+    size = len(text)
+    shapes = [("split at 4096", S.Split(text, 10, 4096, 1 << 16).sizes), ("fixed 1000", [1000] * (size // 1000) + ([size % 1000] if size % 1000 else [])),
+              ("empty frames at the borders", [0, 0, 700, 0, 0, size - 700, 0])]
+    for what, sizes in shapes:
+        assert sum(sizes) == size
+        want = Index(text, 10, offsets_of(sizes), True)
+        assert (want.misaligned == 0) == (what == "split at 4096"), (what, want.misaligned)          # (the fixture: only frames that end on delimiters are aligned)
+        archive = codec.compress_seekable_frames_host(np.frombuffer(text, dtype=np.uint8), sizes, 3, True)
+        for window in ("1", "9000", "20000", "0"):
+            os.environ["ZSMI_ARCHIVE_WINDOW"] = window
+            plan = windows_of(sizes, int(window) or 256 << 20)
+            assert (len(plan) == 1) == (window == "0"), (what, window, plan)
+            sa = SeekableArchive(archive)
+            try:
+                sa._open()
+                assert sa.num_frames == len(sizes)
+                _lib.fill_scratch(sa.codec.ctx, 0x5EED0BAD)
+                sa.codec.enable_timing(True)
+                first, result = np.full(len(sizes) + 1, M64, dtype=np.uint64), np.full(4, M64, dtype=np.uint64)
+                rc = L.zsmi_seekableIndexRecordsHost(sa.codec.ctx, sa.handle, 10, p(first.ctypes.data), p(result.ctypes.data))
+                got = [int(v) for v in result]
+                print(what, "windows of", window, "->", len(plan), "rc", rc, "result", got, flush=True)
+                assert rc == 0, (what, window, rc)
+                assert got == [0, want.records, want.misaligned, want.delimiters], (what, window, got, [0, want.records, want.misaligned, want.delimiters])
+                bad = np.flatnonzero(first != want.first_record)
+                assert not len(bad), (what, window, "entries differ, first at", bad[:5].tolist(), first[bad[:5]].tolist(), want.first_record[bad[:5]].tolist())
+                assert sa.codec.kernel_times()["k_find_frames"][1] == len(plan), (what, window, "the windows are not the plan's")
+            finally:
+                sa.close()
+    codec.close()
+    print("windows ok")
+
+
 if __name__ == "__main__":
     import os, sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     if sys.argv[1:] == ["poison"]:
         poison_child()
+    if sys.argv[1:] == ["windows"]:
+        windows_child()

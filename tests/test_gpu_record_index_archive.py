@@ -4,8 +4,9 @@ behind the last); the attached archive byte for byte the host attach's; the inde
 window and in three chained ones; lines read and found through the loaded array, with the find window over ALL frames, the index
 frame's entry included; a handle with a DDict set; fixed-size frames, which are misaligned; 2 097 153 one-byte frames, where the
 counts' scan takes its second level; damage - a count, the inner magic, a content frame inside a rebuild window; an archive without an
-index.  Every device array is exactly as long as the header sizes it, between canaries."""
-import ctypes
+index; the host rebuild in many windows (a child process on the debug-hook library).  Every device array is exactly as long as the
+header sizes it, between canaries."""
+import ctypes, os, subprocess, sys
 import numpy as np
 import pytest
 import _recindex as R, _split as S, _find as FD, _borders as BD, _seekable_resident as SR, _resident_cdict_set as RS
@@ -14,6 +15,7 @@ from _resident import up, down
 
 pytestmark = pytest.mark.gpu
 p = ctypes.c_void_p
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -368,3 +370,11 @@ def test_host_checks(L, H, codec):
         assert L.zsmi_seekableLoadRecordIndexHost(ctx, sk, p(first.ctypes.data), p(result.ctypes.data)) == 0 and result.tolist() == [R.E_PREFIX, 0, 0, 0]
     finally:
         o.close(codec)
+
+
+def test_the_host_rebuild_in_many_windows():
+    """zsmi_seekableIndexRecordsHost with the window plan cut at one frame, 9000 and 20000 bytes and at its default, over frames that end
+    on delimiters, frames that cut records and empty frames on both sides of a window border (tests/_recindex.py, windows_child)"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_recindex.py"), "windows"], env=dict(os.environ, ZSMI_DEBUG_LIB="1"), cwd=ROOT,
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "windows ok" in out.stdout, (out.stdout[-2000:], out.stderr[-4000:])

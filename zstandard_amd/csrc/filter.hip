@@ -17,9 +17,9 @@
 //   k_filter_check   one pass over the slots' 64-bit words: the check's terms and the all-ones slots, added up by wavefront into two words
 //   k_filter_built   one lane: the header, its check, dResult
 // On an archive (zsmi_seekableBuildFrameFilterResident) the frames are decoded end to end into dWork by find.hip's findDecode as it
-// stands - the whole archive one window - and its layout scan is the body's places.  The host form works in windows of at most 256 MiB of
-// content, cut where the table allows (frames never cross a window); what the next window's first border needs is ONE byte, the text's
-// last, copied to a scratch word on the stream before dWork is written again.
+// stands - the whole archive one window - and its layout scan is the body's places.  The host form walks seekable.hip's window plan
+// (windows of at most 256 MiB of content; frames never cross a window); what the next window's first border needs is ONE byte, the
+// text's last, copied to a scratch word on the stream before dWork is written again.
 // Check (zsmi_checkFrameFilterDevice): the header judged on the device against filterSize, k_filter_check over the slots it names,
 // k_filter_judged - zsmi_readFrameFilter's verdict.
 // Filter (zsmi_filterFramesDevice): the patterns travel by value, folded as the query calls fold them (ZsFindQuery, findquery.hip); g, L
@@ -34,10 +34,10 @@
 #include "zsmi_ctx.h"             // the context, LAUNCH, scanOffsets
 #include "zsmi_filter.h"          // the rule, the frame, the host forms
 #include <algorithm>
-#include <cstdlib>
-// From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE, ZsSplitBytes16; seekable.hip - the handle;
-// find.hip - findDecode, FindDecoded, findDecodeHead, zsmi_seekableFindWorkBound; findquery.hip - ZsFindQuery, findQuery; recindex.hip -
-// zs_ridx_lower, zs_ridx_block_sum, zs_ridx_wave_sum64.
+// From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE, ZsSplitBytes16; seekable.hip - the handle,
+// seekWindowCheck, the window plan (SeekWindows, seekCutWindows, seekWindowLimit); find.hip - the decode half of a window
+// (findDecodeReserve, findDecode, FindDecoded); findquery.hip - ZsFindQuery, findQuery; recindex.hip - zs_ridx_lower, zs_ridx_block_sum,
+// zs_ridx_wave_sum64.
 
 struct ZsFltSums { unsigned long long check, saturated, grams, status; };  // zeroed on the stream in front of the kernels; status: the first window's that failed
 struct ZsFltShared { uint32_t text[ZS_SPLIT_TILE / 4u + 2u]; uint32_t bits[1u << (ZS_FLT_MAX_LOG - 5u)]; uint32_t slots[4]; };
@@ -321,28 +321,22 @@ extern "C" int zsmi_buildFrameFilterDevice(zsmi_ctx *c, const void *dText, uint6
     if (const int e = fltText(c, dText, size, dPlaces, n, 0, delim, gram, log2Bits, nullptr, true, nullptr, dFilter, w.dSums)) return e;
     return fltFinish(c, dFilter, n, delim, gram, log2Bits, size, w.dSums, dResult);
 }
-// one window of an archive: findDecode, whose layout scan - the places of the frames in dWork - is the body's places (recindex.hip's
-// recidxWindow); then the text's last byte to the carry word, for the window behind
+// one window of an archive: findDecode with nothing behind its words, whose layout scan - the places of the frames in dWork - is the
+// body's places (recindex.hip's recidxWindow); then the text's last byte to the carry word, for the window behind
 static int fltWindow(zsmi_ctx *c, const zsmi_seekable *sk, int delim, uint32_t g, uint32_t L, uint32_t firstFrame, uint32_t frameCount, void *dWork, void *dFilter, const FltWords &w)
 {
     FindDecoded d;
-    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, d)) return e;
-    const uint64_t *dPlaces = d.dListAt;
+    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, 0, 0, d)) return e;
     const bool atStart = sk->t.dOff[firstFrame] == 0, atEnd = sk->t.dOff[(size_t)firstFrame + frameCount] == sk->t.dOff[sk->t.n];
-    if (const int e = fltText(c, dWork, d.bytes, dPlaces, frameCount, firstFrame, delim, g, L, atStart ? nullptr : w.dCarry, atEnd, d.dCode, dFilter, w.dSums)) return e;
+    if (const int e = fltText(c, dWork, d.bytes, d.dListAt, frameCount, firstFrame, delim, g, L, atStart ? nullptr : w.dCarry, atEnd, d.dCode, dFilter, w.dSums)) return e;
     return d.bytes ? c->onDevice(w.dCarry, (const uint8_t *)dWork + d.bytes - 1, 1) : 0;
 }
-// the checks of the archive builds, in the rebuild's order (recidxCheck) with the filter where firstRecord stood
+// the checks of the archive builds, in the rebuild's order (seekable.hip's seekWindowCheck over the whole archive, the filter's shape as
+// the rule) with the filter where firstRecord stood, then the filter's place
 static int fltArchiveCheck(const zsmi_ctx *c, const zsmi_seekable *sk, int delim, unsigned g, unsigned L, bool ownWork, const void *work, uint64_t workCapacity,
                            const void *filter, uint64_t capacity, const void *result)
 {
-    if (!c) return ZSMI_error_init_missing;
-    if (!sk || !result || !filter) return ZSMI_error_GENERIC;
-    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
-    if (const int e = fltRoomCheck(sk->t.n, delim, g, L)) return e;
-    const uint64_t bound = zsmi_seekableFindWorkBound(sk, 0, sk->t.n);
-    if (!ownWork && bound && !work) return ZSMI_error_GENERIC;
-    if (!ownWork && workCapacity < bound) return ZSMI_error_dstSize_tooSmall;
+    if (const int e = seekWindowCheck(c, sk, !result || !filter, [&] { return fltRoomCheck(sk->t.n, delim, g, L); }, 0, sk ? sk->t.n : 0, ownWork, work, workCapacity)) return e;
     if (!ownWork && ((uintptr_t)filter & 7u)) return ZSMI_error_parameter_outOfBound;
     if (capacity < zs_flt_frame_size(sk->t.n, L)) return ZSMI_error_dstSize_tooSmall;
     return 0;
@@ -355,9 +349,7 @@ extern "C" int zsmi_seekableBuildFrameFilterResident(zsmi_ctx *c, const zsmi_see
     const uint32_t N = sk->t.n;
     FltWords w;
     if (const int e = fltWords(c, 0, w)) return e;
-    const size_t tiles = (size_t)(sk->t.dOff[N] / ZS_SPLIT_TILE + 2);      // findDecode's scratch, before the fills are queued
-    if (!c->dItems.reserve(sizeof(ZsDecItem) * (size_t)N) || !c->seek.dMeta.reserve(findDecodeHead(N) + findTileBytes(tiles)) ||
-        !c->dScan.reserve(sizeof(uint64_t) * ((std::max<size_t>(N, tiles) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
+    if (const int e = findDecodeReserve(c, N, 0, 0)) return e;              // the one window's scratch, before the fills are queued
     if (const int e = c->fill(w.dSums, 0, sizeof(ZsFltSums))) return e;
     if (N) {
         if (const int e = c->fill((uint8_t *)dFilter + ZS_FLT_FIXED, 0, (size_t)N * zs_flt_slot_bytes(log2Bits))) return e;
@@ -365,42 +357,25 @@ extern "C" int zsmi_seekableBuildFrameFilterResident(zsmi_ctx *c, const zsmi_see
     }
     return fltFinish(c, dFilter, N, delim, gram, log2Bits, sk->t.dOff[N], w.dSums, dResult);
 }
-// host buffers out, one wait: the archive in windows of at most 256 MiB of content, cut wherever the table allows (a longer frame is a
-// window of its own), in ascending order on the stream; the filter grows in context staging, the work buffer is the context's
-static uint64_t fltWindowBytes()
-{
-#ifdef ZSMI_DEBUG_HOOKS
-    if (const char *e = getenv("ZSMI_FILTER_WINDOW")) { const long long v = atoll(e); if (v > 0) return (uint64_t)v; }      // the tests' way to many windows over a small archive
-#endif
-    return 256ull << 20;
-}
+// host buffers out, one wait: seekable.hip's window plan, the windows in ascending order on the stream; the filter grows in context
+// staging, the work buffer is the context's
 extern "C" int zsmi_seekableBuildFrameFilterHost(zsmi_ctx *c, const zsmi_seekable *sk, int delim, unsigned gram, unsigned log2Bits, void *filter, size_t capacity, uint64_t *result)
 {
     if (const int e = fltArchiveCheck(c, sk, delim, gram, log2Bits, true, nullptr, 0, filter, capacity, result)) return e;
     if (const int e = c->bind()) return e;
     const uint32_t N = sk->t.n;
-    const uint64_t window = fltWindowBytes();
-    std::vector<std::pair<uint32_t, uint32_t>> windows;
-    uint64_t most = 0; uint32_t mostFrames = 0;
-    for (uint32_t f = 0; f < N;) {
-        uint32_t g = f + 1;
-        while (g < N && sk->t.dOff[g + 1] - sk->t.dOff[f] <= window) g++;
-        windows.push_back({ f, g - f });
-        most = std::max(most, sk->t.dOff[g] - sk->t.dOff[f]); mostFrames = std::max(mostFrames, g - f);
-        f = g;
-    }
+    const SeekWindows plan = seekCutWindows(sk, seekWindowLimit());
     // every window's scratch at once, before the first is queued: the largest text, the most frames
-    const size_t total = (size_t)zs_flt_frame_size(N, log2Bits), tilesMost = (size_t)(most / ZS_SPLIT_TILE + 2);
+    const size_t total = (size_t)zs_flt_frame_size(N, log2Bits);
     FltWords w;
     if (const int e = fltWords(c, 4 * sizeof(uint64_t), w)) return e;
-    if (!c->sDst.reserve(total + 64) || !c->seek.dDec.reserve(most + 64) || !c->dItems.reserve(sizeof(ZsDecItem) * (size_t)mostFrames) ||
-        !c->seek.dMeta.reserve(findDecodeHead(mostFrames) + findTileBytes(tilesMost)) ||
-        !c->dScan.reserve(sizeof(uint64_t) * ((std::max<size_t>(mostFrames, tilesMost) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
+    if (!c->sDst.reserve(total + 64) || !c->seek.dDec.reserve(plan.most + 64)) return ZSMI_error_memory_allocation;
+    if (const int e = findDecodeReserve(c, plan.mostFrames, 0, 0)) return e;
     uint64_t *dResult = (uint64_t *)(w.dCarry + 8);
     std::vector<uint8_t> staged(total);
     int rc = c->fill(w.dSums, 0, sizeof(ZsFltSums));
     if (!rc && N) rc = c->fill((uint8_t *)c->sDst.p + ZS_FLT_FIXED, 0, total - ZS_FLT_FIXED);
-    for (size_t k = 0; k < windows.size() && !rc; k++) rc = fltWindow(c, sk, delim, gram, log2Bits, windows[k].first, windows[k].second, c->seek.dDec.p, c->sDst.p, w);
+    for (size_t k = 0; k < plan.list.size() && !rc; k++) rc = fltWindow(c, sk, delim, gram, log2Bits, plan.list[k].first, plan.list[k].second, c->seek.dDec.p, c->sDst.p, w);
     if (!rc) rc = fltFinish(c, c->sDst.p, N, delim, gram, log2Bits, sk->t.dOff[N], w.dSums, dResult);
     if (!rc) rc = c->toHost(result, dResult, 4 * sizeof(uint64_t));
     if (!rc) rc = c->toHost(staged.data(), c->sDst.p, total);

@@ -20,15 +20,15 @@
 //                   B + the tile's base + the delimiters in front of it inside the tile.  One lane writes dResult.
 // The same three-level chain - lanes by ballots, (step, wavefront) pairs through LDS, tiles by k_find_carry - decides inside a tile which
 // occurrence is the first of its record (zs_find_open).
-// On an archive (zsmi_seekableFindRecordsResident) the window's frames are first decoded end to end into dWork by the frame read of
-// records.hip on the list firstFrame, firstFrame + 1 ..: k_find_frames, k_seek_request_sizes, scanOffsets, k_seek_request_items,
+// On an archive (zsmi_seekableFindRecordsResident) the window's frames are first decoded end to end into dWork by seekable.hip's
+// frame-list decode on the list firstFrame, firstFrame + 1 ..: k_find_frames, k_seek_request_sizes, then scanOffsets, k_seek_request_items,
 // decodeItems, k_seek_verify; k_find_code brings the frames' codes down to the first failing frame's, which k_find_emit honours.
 // Scratch, all of it context buffers reserved before anything is queued: 16 bytes a tile and three scans of 8 bytes a tile in the seekable
 // scratch, 60 bytes a frame of the window there too, the decoder's item list and scratch.  Every store is a vector store from plain C++.
 // This file is the base of the search family (findquery.hip, findregex.hip, findframes.hip): what does not depend on the search rule is
 // defined here once and called there - on the device the tile's loads (zs_find_load), the emit kernels' head and tail (zs_find_emit_head,
-// zs_find_emit_tail, zs_find_emit_open) and zs_find_open; on the host the tiles' layout (FindTiles, findTileBytes, findReserve), the three
-// scans (findScans), the archive calls' checks (findCheck), the decode half (FindDecodeWords, findDecodeList, findDecode), the window
+// zs_find_emit_tail, zs_find_emit_open) and zs_find_open; on the host the tiles' layout (FindTiles, findTileBytes, findLay, findReserve), the
+// three scans (findScans), the archive calls' checks (findCheck), the decode half of a window (findDecodeReserve, findDecode), the window
 // sequence (findWindow) and the host forms' staging (findStage).  The tile analyses, the count kernels and the carry kernels are each
 // search's own: what crosses a border there is a bit, a set, a state function.
 
@@ -38,8 +38,9 @@
 #include "zsmi_find.h"            // the rule: zs_find_check, zs_find_records
 #include <algorithm>
 // From the feature files zsmi_api.hip includes in front of this one (none can be included twice): split.hip - ZS_SPLIT_TILE, ZsSplitBytes16,
-// zs_split_word_mask; records.hip - zs_rec_mask16, the 16-bit mask of a lane's 16 bytes; seekable.hip - the handle, ZsSeekEntry, ZsSeekItem,
-// k_seek_request_sizes, k_seek_request_items, k_seek_verify.  (zs_split_tile_masks itself is not used: it marks the stream's last byte as
+// zs_split_word_mask; records.hip - zs_rec_mask16, the 16-bit mask of a lane's 16 bytes; seekable.hip - the handle, ZsSeekEntry,
+// k_seek_request_sizes, the frame-list decode (SeekListWords, seekListHead, seekListWords, seekDecodeList), seekWindowCheck,
+// zsmi_seekableFindWorkBound.  (zs_split_tile_masks itself is not used: it marks the stream's last byte as
 // a record end whatever it is, and here only delimiters count; and the bytes are wanted, not only their mask.)
 
 struct ZsFindPattern { uint32_t m; uint8_t b[ZS_FIND_MAX_PATTERN]; };    // the pattern, by value in the kernels' arguments
@@ -344,22 +345,31 @@ extern "C" size_t zsmi_findRecords(const void *src, size_t srcSize, int delim, c
     return (size_t)zs_find_records((const uint8_t *)src, srcSize, (uint8_t)delim, (const uint8_t *)pattern, patternSize, base, records, capacity, matches);
 }
 // the tiles of a text and what the calls lay over them in the seekable scratch, `head` bytes into it (8-aligned): the three scans
-// [tiles + 1 each]; delimiters, occurrences, kept, flags [tiles each] - findTileBytes; behind them, 16-aligned, extraPerTile bytes a tile
-// of the search's own (dExtra; findregex.hip's 72).  findReserve: that, and the scans' tile sums for `scanned` items at least - before
-// anything is queued
+// [tiles + 1 each]; delimiters, occurrences, kept, flags [tiles each]; behind them, 16-aligned, extraPerTile bytes a tile of the search's
+// own (dExtra; findregex.hip's 72) - findTileBytes: all of them.  findReserve: that, and the scans' tile sums for `scanned` items at
+// least - before anything is queued
 struct FindTiles { uint32_t tiles; uint32_t *dDelims, *dOccs, *dKept, *dFlags; uint64_t *dRecBase, *dSlotBase, *dOccBase; uint8_t *dExtra; };
-static size_t findTileBytes(size_t tiles) { return 3 * (tiles + 1) * sizeof(uint64_t) + 4 * tiles * sizeof(uint32_t); }
-static int findReserve(zsmi_ctx *c, uint64_t size, size_t head, uint64_t scanned, FindTiles &t, size_t extraPerTile = 0)
+static size_t findTileBytes(size_t tiles, size_t extraPerTile = 0) { return 3 * (tiles + 1) * sizeof(uint64_t) + 4 * tiles * sizeof(uint32_t) + (extraPerTile ? 16 + tiles * extraPerTile : 0); }
+static int findTilesOf(uint64_t size, FindTiles &t)
 {
     const uint64_t tiles64 = (size + ZS_SPLIT_TILE - 1) / ZS_SPLIT_TILE;
     if (tiles64 > 0x7FFFFFFFull) return ZSMI_error_memory_allocation;
     t.tiles = (uint32_t)tiles64;
+    return 0;
+}
+static void findLay(void *meta, size_t head, size_t extraPerTile, FindTiles &t)
+{
     const size_t n = t.tiles, words = head + findTileBytes(n);
-    if (!c->seek.dMeta.reserve(words + (extraPerTile ? 16 + n * extraPerTile : 0))) return ZSMI_error_memory_allocation;
-    if (!c->dScan.reserve(sizeof(uint64_t) * (size_t)((std::max<uint64_t>(scanned, n) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
-    t.dRecBase = (uint64_t *)((uint8_t *)c->seek.dMeta.p + head); t.dSlotBase = t.dRecBase + n + 1; t.dOccBase = t.dSlotBase + n + 1;
+    t.dRecBase = (uint64_t *)((uint8_t *)meta + head); t.dSlotBase = t.dRecBase + n + 1; t.dOccBase = t.dSlotBase + n + 1;
     t.dDelims = (uint32_t *)(t.dOccBase + n + 1); t.dOccs = t.dDelims + n; t.dKept = t.dOccs + n; t.dFlags = t.dKept + n;
-    t.dExtra = extraPerTile ? (uint8_t *)c->seek.dMeta.p + (words + 15) / 16 * 16 : nullptr;
+    t.dExtra = extraPerTile ? (uint8_t *)meta + (words + 15) / 16 * 16 : nullptr;
+}
+static int findReserve(zsmi_ctx *c, uint64_t size, size_t head, uint64_t scanned, FindTiles &t, size_t extraPerTile = 0)
+{
+    if (const int e = findTilesOf(size, t)) return e;
+    if (!c->seek.dMeta.reserve(head + findTileBytes(t.tiles, extraPerTile))) return ZSMI_error_memory_allocation;
+    if (!c->dScan.reserve(sizeof(uint64_t) * (size_t)((std::max<uint64_t>(scanned, t.tiles) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
+    findLay(c->seek.dMeta.p, head, extraPerTile, t);
     return 0;
 }
 static ZsFindPattern findPattern(const void *pattern, uint32_t m)
@@ -403,84 +413,56 @@ extern "C" int zsmi_findRecordsDevice(zsmi_ctx *c, const void *dSrc, uint64_t sr
     if (const int e = findReserve(c, srcSize, 0, 0, t)) return e;
     return findText(c, dSrc, srcSize, delim, findPattern(pattern, patternSize), dBase, nullptr, dRecords, capacity, dResult, t);
 }
-extern "C" size_t zsmi_seekableFindWorkBound(const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount)
-{
-    if (!sk || (uint64_t)firstFrame + frameCount > sk->t.n) return 0;
-    return (size_t)(sk->t.dOff[(size_t)firstFrame + frameCount] - sk->t.dOff[firstFrame]);
-}
-// the header's checks of the archive calls, in its order; rule: the pattern, query or program, and ruleCheck its check (zs_find_check,
-// zs_findq_check, zs_regex_check) in the place the order gives it; work: null for the host form, which brings its own buffer
+// the header's checks of the archive calls, in its order - seekable.hip's seekWindowCheck with the search's arrays; rule: the pattern,
+// query or program, and ruleCheck its check (zs_find_check, zs_findq_check, zs_regex_check), in front of the caller's frame count; work:
+// null for the host form, which brings its own buffer
 template <class RuleCheck>
 static int findCheck(const zsmi_ctx *c, const zsmi_seekable *sk, const void *firstRecord, uint32_t nFrames, const void *rule, RuleCheck ruleCheck,
                      uint32_t firstFrame, uint32_t frameCount, bool ownWork, const void *work, uint64_t workCapacity, const void *records, uint64_t capacity, const void *result)
 {
-    if (!c) return ZSMI_error_init_missing;
-    if (!sk || !result || !rule || !firstRecord || (capacity && !records)) return ZSMI_error_GENERIC;
-    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
-    if (const int e = ruleCheck()) return e;
-    if (nFrames != sk->t.n || (uint64_t)firstFrame + frameCount > nFrames) return ZSMI_error_parameter_outOfBound;
-    const uint64_t bound = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
-    if (!ownWork && bound && !work) return ZSMI_error_GENERIC;
-    if (!ownWork && workCapacity < bound) return ZSMI_error_dstSize_tooSmall;
-    return 0;
+    return seekWindowCheck(c, sk, !result || !rule || !firstRecord || (capacity && !records), [&] {
+        const int e = ruleCheck();
+        return e ? e : (nFrames != sk->t.n ? (int)ZSMI_error_parameter_outOfBound : 0);
+    }, firstFrame, frameCount, ownWork, work, workCapacity);
 }
-// The words of the decode half of a search on an archive, a frame of F, at the start of the seekable scratch, in front of the tiles'
-// (findDecodeHead: their bytes - the `head` of findReserve): 64 bits - sizes [F], places in dWork [F + 1]; verify records [F]; 32 bits -
-// the list, decoder status, refusals, written, codes [F each], the call's code [1, padded to 8 bytes]
-struct FindDecodeWords { uint64_t *dSizes, *dListAt; ZsSeekItem *dVerify; uint32_t *dList, *dSt, *dRefused, *dFrameWritten, *dCodes, *dCode; };
-static size_t findDecodeHead(size_t F) { return (2 * F + 1) * sizeof(uint64_t) + F * sizeof(ZsSeekItem) + ((5 * F + 1) * sizeof(uint32_t) + 7) / 8 * 8; }
-static FindDecodeWords findDecodeWords(void *p, size_t F)
+// The decode half of every call on a window of an archive - the three searches, the record index, the frame filter: the window's frames
+// into dWork, end to end, verified (seekable.hip's frame-list decode on the list firstFrame, firstFrame + 1 ..), and the first failing
+// frame's code in a device word.  In the seekable scratch the list's words (seekListHead) and, behind them, `behind` bytes of the
+// caller's own - a search's tiles, the index's; findDecodeReserve: that, the decoder's item list and the scans' tile sums for F items or
+// `scanned`, whichever is more.  A call of many windows reserves for the largest before it queues the first
+struct FindDecoded { uint64_t bytes; void *dBehind; const uint32_t *dCode; const uint64_t *dListAt; };      // dListAt: the frames' places in dWork [frameCount + 1]
+static int findDecodeReserve(zsmi_ctx *c, uint32_t F, size_t behind, uint64_t scanned)
 {
-    FindDecodeWords d;
-    d.dSizes = (uint64_t *)p; d.dListAt = d.dSizes + F; d.dVerify = (ZsSeekItem *)(d.dListAt + F + 1);
-    d.dList = (uint32_t *)(d.dVerify + F); d.dSt = d.dList + F; d.dRefused = d.dSt + F; d.dFrameWritten = d.dRefused + F; d.dCodes = d.dFrameWritten + F; d.dCode = d.dCodes + F;
-    return d;
+    return c->seek.dMeta.reserve(seekListHead(F) + behind) && c->dItems.reserve(sizeof(ZsDecItem) * (size_t)F) &&
+           c->dScan.reserve(sizeof(uint64_t) * (size_t)((std::max<uint64_t>(scanned, F) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1)) ? 0 : ZSMI_error_memory_allocation;
 }
-// the F frames of d.dList, of d.dSizes bytes each, into dWork[0, bytes), end to end and verified: d.dListAt their places, d.dCodes a code
-// a frame.  What makes the list and the sizes, and what becomes of the codes, is the caller's (k_find_frames and k_find_code here,
-// k_findsel_list and k_findsel_code in findframes.hip); the context's item list holds F items
-static int findDecodeList(zsmi_ctx *c, const zsmi_seekable *sk, const FindDecodeWords &d, uint32_t F, uint64_t bytes, void *dWork)
+// (context bound, frameCount > 0, arguments checked by the caller)
+static int findDecode(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount, void *dWork, size_t behind, uint64_t scanned, FindDecoded &w)
 {
-    const ZsSeekEntry *dTable = (const ZsSeekEntry *)sk->dTable.p;
-    if (const int e = scanOffsets(c, "k_find_scan", (const uint64_t *)d.dSizes, nullptr, F, 1u, nullptr, d.dListAt)) return e;
-    LAUNCH(c, "k_seek_request_items", k_seek_request_items, dim3((F + 255u) / 256u), dim3(256), 0, dTable, sk->t.n, (const uint32_t *)d.dList, F, (const uint64_t *)d.dListAt,
-           bytes, (uint8_t *)dWork, (ZsDecItem *)c->dItems.p, d.dVerify, d.dRefused, d.dFrameWritten);
-    CapStats caps;
-    caps.add(sk->maxDSize, F);
-    if (const int e = decodeItems(c, sk->dFrames, F, dWork, caps, d.dSt, &sk->sel)) return e;
-    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((F + 15) / 16), dim3(64), 0, (const ZsSeekItem *)d.dVerify, F, (const uint32_t *)d.dSt, sk->t.checksum ? 1 : 0, d.dCodes,
-           (const uint32_t *)d.dRefused);
-    return 0;
-}
-// The decode half of a search on a window of an archive, shared by the three searches, the record index and the frame filter (context
-// bound, frameCount > 0, arguments checked by the caller): the scratch of the whole call reserved - extraPerTile: findReserve's - then the
-// window's frames into dWork, end to end, verified, and the first failing frame's code in a device word.  Leaves the text's size, its
-// tiles and that word
-struct FindDecoded { uint64_t bytes; FindTiles t; const uint32_t *dCode; const uint64_t *dListAt; };      // dListAt: the frames' places in dWork [frameCount + 1]
-static int findDecode(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount, void *dWork, FindDecoded &w, size_t extraPerTile = 0)
-{
-    const uint64_t bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
-    if (const int e = findReserve(c, bytes, findDecodeHead(frameCount), frameCount, w.t, extraPerTile)) return e;
-    if (!c->dItems.reserve(sizeof(ZsDecItem) * (size_t)frameCount)) return ZSMI_error_memory_allocation;
-    const FindDecodeWords d = findDecodeWords(c->seek.dMeta.p, frameCount);
+    if (const int e = findDecodeReserve(c, frameCount, behind, scanned)) return e;
+    const SeekListWords d = seekListWords(c->seek.dMeta.p, frameCount);
     const uint32_t grid = (frameCount + 255) / 256;
+    w.bytes = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount); w.dBehind = (uint8_t *)c->seek.dMeta.p + seekListHead(frameCount); w.dCode = d.dCode; w.dListAt = d.dListAt;
     LAUNCH(c, "k_find_frames", k_find_frames, dim3(grid), dim3(256), 0, firstFrame, frameCount, d.dList);
     LAUNCH(c, "k_seek_request_sizes", k_seek_request_sizes, dim3(grid), dim3(256), 0, (const ZsSeekEntry *)sk->dTable.p, sk->t.n, (const uint32_t *)d.dList, frameCount, d.dSizes);
-    if (const int e = findDecodeList(c, sk, d, frameCount, bytes, dWork)) return e;
+    if (const int e = seekDecodeList(c, sk, d.dList, frameCount, d, "k_find_scan", 1u, dWork, w.bytes)) return e;
     LAUNCH(c, "k_find_code", k_find_code, dim3(1), dim3(1024), 0, (const uint32_t *)d.dCodes, frameCount, d.dCode);
-    w.bytes = bytes; w.dCode = d.dCode; w.dListAt = d.dListAt;
     return 0;
 }
-// the launch sequence on a window of an archive, its arguments checked by the caller: the decode half, then text(w) - the search's
-// sequence over the decoded text (findText, findqText, findreText)
+// the launch sequence of a search on a window of an archive, its arguments checked by the caller: the decode half with the search's tiles
+// behind its words - extraPerTile: findReserve's -, then text(w, t) - the search's sequence over the decoded text (findText, findqText,
+// findreText)
 template <class Text>
 static int findWindow(zsmi_ctx *c, const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount, void *dWork, uint64_t *dResult, size_t extraPerTile, Text text)
 {
     if (const int e = c->bind()) return e;
     if (frameCount == 0) return c->fill(dResult, 0, 4 * sizeof(uint64_t));
+    FindTiles t;
+    if (const int e = findTilesOf(zsmi_seekableFindWorkBound(sk, firstFrame, frameCount), t)) return e;
     FindDecoded w;
-    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, w, extraPerTile)) return e;
-    return text(w);
+    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, findTileBytes(t.tiles, extraPerTile), t.tiles, w)) return e;
+    findLay(c->seek.dMeta.p, seekListHead(frameCount), extraPerTile, t);
+    return text(w, t);
 }
 // The host forms of the archive calls: host arrays in and out around a resident run, one wait.  Staged in device memory: firstRecord
 // [nFrames + 1], `front` 64-bit words and, behind the four result words, `back` bytes of the caller's own (the list search's count and
@@ -523,8 +505,8 @@ extern "C" int zsmi_seekableFindRecordsResident(zsmi_ctx *c, const zsmi_seekable
 {
     if (const int e = findCheck(c, sk, dFirstRecord, nFrames, pattern, [&] { return zs_find_check(delim, pattern, patternSize); }, firstFrame, frameCount, false, dWork,
                                 workCapacity, dRecords, capacity, dResult)) return e;
-    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, 0, [&](const FindDecoded &w) {
-        return findText(c, dWork, w.bytes, delim, findPattern(pattern, patternSize), dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, w.t);
+    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, 0, [&](const FindDecoded &w, const FindTiles &t) {
+        return findText(c, dWork, w.bytes, delim, findPattern(pattern, patternSize), dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, t);
     });
 }
 // host arrays in and out (findStage).  A record that holds an occurrence holds m bytes of its own, so the window's bytes / m numbers are

@@ -9,7 +9,7 @@
 //   k_findsel_list     the list judged - a count above maxFrames, a frame number at or above nFrames, a list that does not ascend - and
 //                      laid out: an entry's bytes are its frame's Decompressed_Size, + 1 for the last frame of a run that another run
 //                      follows: ONE delimiter byte between runs.  A pattern holds no delimiter, so nothing straddles a run border
-//   scanOffsets        the frames' places in dWork; k_seek_request_items, decodeItems, k_seek_verify: find.hip's findDecodeList on the list
+//   scanOffsets        the frames' places in dWork; k_seek_request_items, decodeItems, k_seek_verify: seekable.hip's frame-list decode on the list
 //   k_findsel_code     the call's code: the list's refusal, content above workCapacity, or the first failing frame's code
 //   k_findsel_fill     the delimiter between runs, and delimiters from the content's end to the end of the text searched: the text is
 //                      S = min(workCapacity, zsmi_seekableFindFramesWorkBound(sk, maxFrames)) bytes, a size the HOST knows; the records
@@ -21,7 +21,7 @@
 //                      prefix.  An empty frame starts no record and is stepped over (at the content's end its firstRecord counts the
 //                      tail record already); a content tail without a delimiter is ended by the fill.  One lane writes dResult = {total, written, occurrences, content bytes decoded},
 //                      or {(uint64_t)-code, 0, 0, bytes needed}
-// Scratch, all of it context buffers reserved before anything is queued: find.hip's words for F frames and S bytes, 8 bytes a listed frame
+// Scratch, all of it context buffers reserved before anything is queued: the frame-list decode's words for F frames, find.hip's for S bytes, 8 bytes a listed frame
 // and 64 bytes of words.  Every store is a vector store from plain C++.
 // NOT COVERED: `none` mode (parameter_unsupported: the fill's empty records would be listed), the single-pattern and regular-expression
 // forms of the list search (the decode half is shared: they are small).
@@ -31,9 +31,9 @@
 #include "zsmi_ctx.h"             // the context, LAUNCH, scanOffsets, decodeItems
 #include "zsmi_findquery.h"       // the query and its checks
 #include <algorithm>
-// From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE; seekable.hip - the handle, ZsSeekEntry;
-// find.hip - FindTiles, findReserve, findDecodeHead, findDecodeWords, findDecodeList, FindStaged, findStage; findquery.hip -
-// findQuery, findqText, findQueryShortest; recindex.hip - zs_ridx_wave_sum64.
+// From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE; seekable.hip - the handle, ZsSeekEntry, the
+// frame-list decode (SeekListWords, seekListHead, seekListWords, seekDecodeList); find.hip - FindTiles, findReserve, FindStaged, findStage;
+// findquery.hip - findQuery, findqText, findQueryShortest; recindex.hip - zs_ridx_wave_sum64.
 
 struct ZsFselWords { unsigned long long needed, seps; uint32_t bad, tooMany, code, count; uint64_t tmp[4]; };      // zeroed on the stream in front of the kernels
 
@@ -160,19 +160,19 @@ static int findselRun(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFir
 {
     const uint32_t F = std::max(maxFrames, 1u);
     const uint64_t S = std::min<uint64_t>(workCapacity, zsmi_seekableFindFramesWorkBound(sk, maxFrames));
-    // scratch: find.hip's words of F frames, then the prefixes [F] and the words; the search's tiles behind them
-    const size_t own = findDecodeHead(F), head = own + ((size_t)F + 1) * sizeof(uint64_t) + sizeof(ZsFselWords);
+    // scratch: the frame-list decode's words of F frames, then the prefixes [F] and the words; the search's tiles behind them
+    const size_t own = seekListHead(F), head = own + ((size_t)F + 1) * sizeof(uint64_t) + sizeof(ZsFselWords);
     FindTiles t;
     if (const int e = findReserve(c, S, head, F, t)) return e;
     if (!c->dItems.reserve(sizeof(ZsDecItem) * (size_t)F)) return ZSMI_error_memory_allocation;
-    const FindDecodeWords d = findDecodeWords(c->seek.dMeta.p, F);
+    const SeekListWords d = seekListWords(c->seek.dMeta.p, F);
     uint64_t *dPrefix = (uint64_t *)((uint8_t *)c->seek.dMeta.p + own);
     ZsFselWords *dWords = (ZsFselWords *)(dPrefix + F + 1);
     const ZsSeekEntry *dTable = (const ZsSeekEntry *)sk->dTable.p;
     const uint32_t grid = std::min((F + 255u) / 256u, 4096u);
     if (const int e = c->fill(dWords, 0, sizeof(ZsFselWords))) return e;
     LAUNCH(c, "k_findsel_list", k_findsel_list, dim3(grid), dim3(256), 0, dTable, sk->t.n, dFrames, dFrameCount, maxFrames, F, d.dList, d.dSizes, dWords);
-    if (const int e = findDecodeList(c, sk, d, F, S, dWork)) return e;
+    if (const int e = seekDecodeList(c, sk, d.dList, F, d, "k_find_scan", 1u, dWork, S)) return e;
     LAUNCH(c, "k_findsel_code", k_findsel_code, dim3(1), dim3(256), 0, (const uint32_t *)d.dCodes, dFrameCount, sk->maxDSize, S, dWords);
     LAUNCH(c, "k_findsel_fill", k_findsel_fill, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + 255) / 256, 8192))), dim3(256), 0, (uint8_t *)dWork, S, (uint32_t)delim,
            dTable, (const uint32_t *)d.dList, (const uint64_t *)d.dSizes, (const uint64_t *)d.dListAt, F);

@@ -35,7 +35,7 @@
 #include <algorithm>
 // From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE, ZsSplitBytes16; records.hip -
 // zs_rec_mask16; find.hip - ZsFindShared, zs_find_load, zs_find_open, zs_find_pop4, zs_find_emit_head, zs_find_emit_tail, zs_find_emit_open,
-// FindTiles, findReserve, findScans, findCheck, FindDecoded, findWindow, FindStaged, findStage, zsmi_seekableFindWorkBound.
+// FindTiles, findReserve, findScans, findCheck, FindDecoded, findWindow, FindStaged, findStage; seekable.hip - zsmi_seekableFindWorkBound.
 
 // the query, by value in the kernels' arguments: pattern j is b[at[j], at[j] + m[j]), folded where the flag is set
 struct ZsFindQuery { uint32_t K, mode, fold, longest; uint16_t m[ZSMI_FIND_MAX_PATTERNS], at[ZSMI_FIND_MAX_PATTERNS]; uint8_t b[ZS_FIND_MAX_PATTERN]; };
@@ -327,8 +327,8 @@ extern "C" int zsmi_seekableFindQueryResident(zsmi_ctx *c, const zsmi_seekable *
 {
     if (const int e = findCheck(c, sk, dFirstRecord, nFrames, q, [&] { return zs_findq_check(delim, q); }, firstFrame, frameCount, false, dWork, workCapacity, dRecords,
                                 capacity, dResult)) return e;
-    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, 0, [&](const FindDecoded &w) {
-        return findqText(c, dWork, w.bytes, delim, findQuery(q), dFirstRecord + firstFrame, w.dCode, dRecords, dHits, capacity, dResult, w.t);
+    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, 0, [&](const FindDecoded &w, const FindTiles &t) {
+        return findqText(c, dWork, w.bytes, delim, findQuery(q), dFirstRecord + firstFrame, w.dCode, dRecords, dHits, capacity, dResult, t);
     });
 }
 // host arrays in and out (find.hip's findStage).  A record that holds an occurrence holds the shortest pattern's bytes of its own, so any

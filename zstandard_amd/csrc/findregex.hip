@@ -40,7 +40,7 @@
 #include <algorithm>
 // From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE, ZsSplitBytes16; records.hip -
 // zs_rec_mask16; find.hip - zs_find_load, zs_find_pop4, zs_find_emit_head, zs_find_emit_tail, zs_find_emit_open, FindTiles, findReserve,
-// findScans, findCheck, FindDecoded, findWindow, FindStaged, findStage, zsmi_seekableFindWorkBound.
+// findScans, findCheck, FindDecoded, findWindow, FindStaged, findStage; seekable.hip - zsmi_seekableFindWorkBound.
 
 static const uint32_t kFindreHasDelim = 1u, kFindreOpenEnd = 2u;          // a tile's flags word; bits 8 .. 15: the state entering the tile (k_findre_carry)
 
@@ -335,8 +335,8 @@ extern "C" int zsmi_seekableFindRegexResident(zsmi_ctx *c, const zsmi_seekable *
 {
     if (const int e = findCheck(c, sk, dFirstRecord, nFrames, prog, [&] { return zs_regex_check(delim, prog); }, firstFrame, frameCount, false, dWork, workCapacity, dRecords,
                                 capacity, dResult)) return e;
-    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, kFindreExtraPerTile, [&](const FindDecoded &w) {
-        return findreText(c, dWork, w.bytes, delim, *prog, dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, w.t);
+    return findWindow(c, sk, firstFrame, frameCount, dWork, dResult, kFindreExtraPerTile, [&](const FindDecoded &w, const FindTiles &t) {
+        return findreText(c, dWork, w.bytes, delim, *prog, dFirstRecord + firstFrame, w.dCode, dRecords, capacity, dResult, t);
     });
 }
 // host arrays in and out (find.hip's findStage).  As with `none`, a program can list a record a byte: the staged numbers are the window's

@@ -16,8 +16,8 @@
 //                    j - 1 is the last place of t', as the places ascend).  No lane reads a tile for a place's sake.
 //                    One lane of the first workgroup writes dResult, the tiles add their misaligned frames to its third word.
 // A tile's places are taken 256 at a time by one workgroup: millions of EMPTY frames at one place are one workgroup's loop.
-// On an archive (zsmi_seekableIndexRecordsResident) the window's frames are decoded end to end into dWork by find.hip's findDecode as it
-// stands; the places are its layout scan.  An index frame among them is an entry of no content: k_seek_request_items plans it with no
+// On an archive (zsmi_seekableIndexRecordsResident) the window's frames are decoded end to end into dWork by find.hip's findDecode, the
+// body's words behind its own; the places are its layout scan.  The host form walks seekable.hip's window plan.  An index frame among them is an entry of no content: k_seek_request_items plans it with no
 // capacity, the decoder steps over the skippable frame and k_seek_verify finds no bytes and the hash of none - it stays in the list.
 // Load (zsmi_seekableLoadRecordIndexResident): k_recidx_unpack - a lane a count, the check's terms and the counts' sum added up by
 // wavefront into four words, each count held against its entry of the handle's table -, scanOffsets over the counts, k_recidx_loaded -
@@ -36,7 +36,8 @@
 #include "zsmi_recindex.h"        // the rule, the frame, the host forms
 #include <algorithm>
 // From the feature files zsmi_api.hip includes in front of this one: split.hip - ZS_SPLIT_TILE, ZsSplitBytes16; records.hip -
-// zs_rec_mask16; seekable.hip - the handle, ZsSeekEntry; find.hip - findDecode, FindDecoded, zsmi_seekableFindWorkBound.
+// zs_rec_mask16; seekable.hip - the handle, ZsSeekEntry, seekWindowCheck, the window plan (SeekWindows, seekCutWindows, seekWindowLimit),
+// zsmi_seekableFindWorkBound; find.hip - the decode half of a window (findDecodeReserve, findDecode, FindDecoded).
 
 // ---- kernels: the body ----
 // mask[s] bit k: the byte at tile * ZS_SPLIT_TILE + s * 4096 + 16 * threadIdx.x + k is the delimiter.  Whole tiles by four 16-byte loads a
@@ -383,34 +384,25 @@ extern "C" int zsmi_indexRecordsDevice(zsmi_ctx *c, const void *dText, uint64_t 
     if (const int e = recidxReserve(c, size, 0, 0, t)) return e;
     return recidxText(c, dText, size, dPlaces, n, delim, atEnd, dBase, nullptr, dFirstRecord, dResult, t);
 }
-// the header's checks of the rebuild on an archive, in its order: findCheck's, less the pattern
+// the header's checks of the rebuild on an archive, in its order: seekable.hip's seekWindowCheck with the delimiter as the rule
 static int recidxCheck(const zsmi_ctx *c, const zsmi_seekable *sk, int delim, uint32_t firstFrame, uint32_t frameCount, bool ownWork, const void *work, uint64_t workCapacity,
                        const void *firstRecord, const void *result)
 {
-    if (!c) return ZSMI_error_init_missing;
-    if (!sk || !result || !firstRecord) return ZSMI_error_GENERIC;
-    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
-    if (delim < 0 || delim > 255) return ZSMI_error_parameter_outOfBound;
-    if ((uint64_t)firstFrame + frameCount > sk->t.n) return ZSMI_error_parameter_outOfBound;
-    const uint64_t bound = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
-    if (!ownWork && bound && !work) return ZSMI_error_GENERIC;
-    if (!ownWork && workCapacity < bound) return ZSMI_error_dstSize_tooSmall;
-    return 0;
+    return seekWindowCheck(c, sk, !result || !firstRecord, [&] { return delim < 0 || delim > 255 ? (int)ZSMI_error_parameter_outOfBound : 0; }, firstFrame, frameCount, ownWork, work,
+                           workCapacity);
 }
-// the launch sequence on a window, its arguments checked by the caller: findDecode, whose layout scan - the places of the frames in dWork -
-// is the body's places; the body's words take the place of the search's behind findDecode's (16 bytes a tile against 40)
+// the launch sequence on a window, its arguments checked by the caller: findDecode with the body's words behind its own; its layout scan -
+// the places of the frames in dWork - is the body's places
 static int recidxWindow(zsmi_ctx *c, const zsmi_seekable *sk, int delim, uint32_t firstFrame, uint32_t frameCount, void *dWork, uint64_t *dFirstRecord, uint64_t *dResult)
 {
     if (frameCount == 0) return c->fill(dResult, 0, 4 * sizeof(uint64_t));
-    FindDecoded w;
-    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, w)) return e;
-    const size_t head = findDecodeHead(frameCount);
     RecidxTiles t;
-    if (const int e = recidxLay(w.bytes, (uint8_t *)c->seek.dMeta.p + head, t)) return e;
-    static_assert(3 * sizeof(uint64_t) >= 2 * sizeof(uint64_t) + 2 * sizeof(uint32_t), "what findReserve lays behind the head for a text of no tiles holds the body's one tile");
-    const uint64_t *dPlaces = w.dListAt;
+    if (const int e = recidxLay(zsmi_seekableFindWorkBound(sk, firstFrame, frameCount), nullptr, t)) return e;
+    FindDecoded w;
+    if (const int e = findDecode(c, sk, firstFrame, frameCount, dWork, recidxTileBytes(t.tiles), t.tiles, w)) return e;
+    recidxLay(w.bytes, w.dBehind, t);
     const int atEnd = sk->t.dOff[(size_t)firstFrame + frameCount] == sk->t.dOff[sk->t.n];
-    return recidxText(c, dWork, w.bytes, dPlaces, frameCount, delim, atEnd, firstFrame ? dFirstRecord + firstFrame : nullptr, w.dCode, dFirstRecord + firstFrame, dResult, t);
+    return recidxText(c, dWork, w.bytes, w.dListAt, frameCount, delim, atEnd, firstFrame ? dFirstRecord + firstFrame : nullptr, w.dCode, dFirstRecord + firstFrame, dResult, t);
 }
 extern "C" int zsmi_seekableIndexRecordsResident(zsmi_ctx *c, const zsmi_seekable *sk, int delim, uint32_t firstFrame, uint32_t frameCount, void *dWork, uint64_t workCapacity,
                                                  uint64_t *dFirstRecord, uint64_t *dResult)
@@ -496,34 +488,25 @@ extern "C" int zsmi_seekableLoadRecordIndexHost(zsmi_ctx *c, const zsmi_seekable
     return 0;
 }
 // the rebuild over the whole archive -> firstRecord[0 .. N] (host) and result[4] = {the first failing frame's code, records, misaligned
-// frames, delimiters}: windows of at most 256 MiB of content, cut wherever the table allows (a longer frame is a window of its own), in
-// ascending order on the stream - they chain through the array in context staging -, a work buffer of the context's, one wait
-static const uint64_t kRecidxWindow = 256ull << 20;
+// frames, delimiters}: seekable.hip's window plan, the windows in ascending order on the stream - they chain through the array in context
+// staging -, a work buffer of the context's, one wait
 extern "C" int zsmi_seekableIndexRecordsHost(zsmi_ctx *c, const zsmi_seekable *sk, int delim, uint64_t *firstRecord, uint64_t *result)
 {
     if (const int e = recidxCheck(c, sk, delim, 0, 0, true, nullptr, 0, firstRecord, result)) return e;
     if (const int e = c->bind()) return e;
     const uint32_t N = sk->t.n;
-    std::vector<std::pair<uint32_t, uint32_t>> windows;
-    uint64_t most = 0; uint32_t mostFrames = 0;
-    for (uint32_t f = 0; f < N;) {
-        uint32_t g = f + 1;
-        while (g < N && sk->t.dOff[g + 1] - sk->t.dOff[f] <= kRecidxWindow) g++;
-        windows.push_back({ f, g - f });
-        most = std::max(most, sk->t.dOff[g] - sk->t.dOff[f]); mostFrames = std::max(mostFrames, g - f);
-        f = g;
-    }
+    const SeekWindows plan = seekCutWindows(sk, seekWindowLimit());
     // every window's scratch at once, before the first is queued: the largest text, the most frames
-    const size_t W = windows.size(), words = (size_t)N + 1 + 4 * std::max<size_t>(W, 1);
-    const size_t tilesMost = (size_t)(most / ZS_SPLIT_TILE + 2);
-    if (!c->sSizes.reserve(words * sizeof(uint64_t)) || !c->seek.dDec.reserve(most + 64) || !c->dItems.reserve(sizeof(ZsDecItem) * (size_t)mostFrames) ||
-        !c->seek.dMeta.reserve(findDecodeHead(mostFrames) + findTileBytes(tilesMost)) ||
-        !c->dScan.reserve(sizeof(uint64_t) * ((std::max<size_t>(mostFrames, tilesMost) + ZS_SCAN_TILE - 1) / ZS_SCAN_TILE + 1))) return ZSMI_error_memory_allocation;
+    const size_t W = plan.list.size(), words = (size_t)N + 1 + 4 * std::max<size_t>(W, 1);
+    RecidxTiles most;
+    if (const int e = recidxLay(plan.most, nullptr, most)) return e;
+    if (!c->sSizes.reserve(words * sizeof(uint64_t)) || !c->seek.dDec.reserve(plan.most + 64)) return ZSMI_error_memory_allocation;
+    if (const int e = findDecodeReserve(c, plan.mostFrames, recidxTileBytes(most.tiles), most.tiles)) return e;
     uint64_t *dFirst = (uint64_t *)c->sSizes.p, *dResults = dFirst + N + 1;
     std::vector<uint64_t> staged((size_t)N + 1), results(4 * std::max<size_t>(W, 1), 0);
     int rc = 0;
     if (N == 0) rc = c->fill(dFirst, 0, sizeof(uint64_t));
-    for (size_t k = 0; k < W && !rc; k++) rc = recidxWindow(c, sk, delim, windows[k].first, windows[k].second, c->seek.dDec.p, dFirst, dResults + 4 * k);
+    for (size_t k = 0; k < W && !rc; k++) rc = recidxWindow(c, sk, delim, plan.list[k].first, plan.list[k].second, c->seek.dDec.p, dFirst, dResults + 4 * k);
     if (!rc && W) rc = c->toHost(results.data(), dResults, 4 * W * sizeof(uint64_t));
     if (!rc) rc = c->toHost(staged.data(), dFirst, ((size_t)N + 1) * sizeof(uint64_t));
     const int waited = c->wait();

@@ -15,7 +15,7 @@
 //                     total and for a head whose list ends behind R or whose frames end behind workCapacity (from the first such head on
 //                     every head is one: both sums only grow)
 //   k_seek_request_sizes, scanOffsets, k_seek_request_items, decodeItems, k_seek_verify
-//                     the read of zsmi_seekableReadFramesResident on that list, with dWork as its destination and align 1: a slot
+//                     seekable.hip's frame-list decode (seekDecodeList) on that list, with dWork as its destination and align 1: a slot
 //                     that names no frame is an empty item, the frames of a head lie back to back in dWork, and every read gets a code
 //   k_rec_measure     a wavefront a request: its leader's first failing frame, in frame order, or the record's extent inside the
 //                     leader's run in dWork (EXTENT, 16 bytes a lane a step)
@@ -31,8 +31,8 @@
 #include "zsmi_records.h"         // the rules: zs_rec_frames, zs_rec_extent
 #include <algorithm>
 // From the two feature files zsmi_api.hip includes in front of this one (neither can be included twice): seekable.hip - the handle
-// (zsmi_seekable), its table (ZsSeekEntry), ZsSeekItem, ZsDecItem's writers k_seek_request_sizes and k_seek_request_items, k_seek_verify;
-// split.hip - zs_split_word_mask, the zero-byte test of a word XOR the delimiter, and ZsSplitBytes16, the 16 bytes a lane loads.
+// (zsmi_seekable), its table (ZsSeekEntry), k_seek_request_sizes and the frame-list decode (SeekListWords, seekListHead, seekListWords,
+// seekDecodeList); split.hip - zs_split_word_mask, the zero-byte test of a word XOR the delimiter, and ZsSplitBytes16, the 16 bytes a lane loads.
 
 static const uint32_t kRecNoFrame = 0xFFFFFFFFu;         // a slot of the planned read list that names no frame
 
@@ -250,40 +250,27 @@ static int recordsRead(zsmi_ctx *c, const zsmi_seekable *sk, const uint64_t *dFi
     }
     const size_t N = nRecords, R = maxFrameReads;
     // device words, a request: 64 bits - work bytes [N], the three scans [N + 1 each], starts [N], lengths [N]; the lookup's records [N];
-    // 32 bits - reads [N], head flags [N].  A frame read: 64 bits - sizes [R], places in dWork [R + 1]; verify records [R]; 32 bits - the
-    // list, decoder status, refusals, written, codes [R each]
-    const size_t words64 = 6 * N + 3 + 2 * R + 1;
-    if (!c->seek.dMeta.reserve(words64 * sizeof(uint64_t) + N * sizeof(ZsRecReq) + R * sizeof(ZsSeekItem) + (2 * N + 5 * R) * sizeof(uint32_t)) ||
-        !c->dItems.reserve(sizeof(ZsDecItem) * std::max<size_t>(R, 1))) return ZSMI_error_memory_allocation;
+    // 32 bits - reads [N], head flags [N] (8 N bytes: what follows is 8-aligned).  Behind them the frame-list decode's words of R frame reads
+    const size_t own = (6 * N + 3) * sizeof(uint64_t) + N * sizeof(ZsRecReq) + 2 * N * sizeof(uint32_t);
+    if (!c->seek.dMeta.reserve(own + seekListHead(R)) || !c->dItems.reserve(sizeof(ZsDecItem) * std::max<size_t>(R, 1))) return ZSMI_error_memory_allocation;
     uint64_t *dBytes = (uint64_t *)c->seek.dMeta.p, *dReadAt = dBytes + N, *dWorkAt = dReadAt + N + 1, *dHeadsBefore = dWorkAt + N + 1, *dStart = dHeadsBefore + N + 1,
-             *dLength = dStart + N, *dSizes = dLength + N, *dListAt = dSizes + R;
-    ZsRecReq *dReqs = (ZsRecReq *)(dListAt + R + 1);
-    ZsSeekItem *dVerify = (ZsSeekItem *)(dReqs + N);
-    uint32_t *dReads = (uint32_t *)(dVerify + R), *dHeads = dReads + N, *dList = dHeads + N, *dSt = dList + R, *dRefused = dSt + R, *dFrameWritten = dRefused + R, *dCodes = dFrameWritten + R;
-    const ZsSeekEntry *dTable = (const ZsSeekEntry *)sk->dTable.p;
-    const uint64_t *dContent = sk->dContent;
+             *dLength = dStart + N;
+    ZsRecReq *dReqs = (ZsRecReq *)(dLength + N);
+    uint32_t *dReads = (uint32_t *)(dReqs + N), *dHeads = dReads + N;
+    const SeekListWords d = seekListWords((uint8_t *)c->seek.dMeta.p + own, R);
     const uint32_t grid = (nRecords + 255) / 256, readGrid = (maxFrameReads + 255) / 256;
-    LAUNCH(c, "k_rec_lookup", k_rec_lookup, dim3(grid), dim3(256), 0, dFirstRecord, nFrames, dContent, dRecordIndex, nRecords, dReqs, dReads, dBytes, dHeads, dResult);
+    LAUNCH(c, "k_rec_lookup", k_rec_lookup, dim3(grid), dim3(256), 0, dFirstRecord, nFrames, sk->dContent, dRecordIndex, nRecords, dReqs, dReads, dBytes, dHeads, dResult);
     if (const int e = scanOffsets(c, "k_rec_scan", (const uint32_t *)dReads, nullptr, nRecords, 1u, nullptr, dReadAt)) return e;
     if (const int e = scanOffsets(c, "k_rec_scan", (const uint64_t *)dBytes, nullptr, nRecords, 1u, nullptr, dWorkAt)) return e;
     if (const int e = scanOffsets(c, "k_rec_scan", (const uint32_t *)dHeads, nullptr, nRecords, 1u, nullptr, dHeadsBefore)) return e;
     if (maxFrameReads) {
         LAUNCH(c, "k_rec_reads", k_rec_reads, dim3(readGrid), dim3(256), 0, (const ZsRecReq *)dReqs, (const uint64_t *)dReadAt, (const uint64_t *)dWorkAt, nRecords, maxFrameReads,
-               workCapacity, dList);
-        LAUNCH(c, "k_seek_request_sizes", k_seek_request_sizes, dim3(readGrid), dim3(256), 0, dTable, sk->t.n, (const uint32_t *)dList, maxFrameReads, dSizes);
+               workCapacity, d.dList);
+        LAUNCH(c, "k_seek_request_sizes", k_seek_request_sizes, dim3(readGrid), dim3(256), 0, (const ZsSeekEntry *)sk->dTable.p, sk->t.n, (const uint32_t *)d.dList, maxFrameReads, d.dSizes);
     }
-    if (const int e = scanOffsets(c, "k_rec_scan", (const uint64_t *)dSizes, nullptr, maxFrameReads, 1u, nullptr, dListAt)) return e;
-    if (maxFrameReads) {
-        LAUNCH(c, "k_seek_request_items", k_seek_request_items, dim3(readGrid), dim3(256), 0, dTable, sk->t.n, (const uint32_t *)dList, maxFrameReads, (const uint64_t *)dListAt,
-               workCapacity, (uint8_t *)dWork, (ZsDecItem *)c->dItems.p, dVerify, dRefused, dFrameWritten);
-        CapStats caps;
-        caps.add(sk->maxDSize, maxFrameReads);
-        if (const int e = decodeItems(c, sk->dFrames, maxFrameReads, dWork, caps, dSt, &sk->sel)) return e;
-        LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((maxFrameReads + 15) / 16), dim3(64), 0, (const ZsSeekItem *)dVerify, maxFrameReads, (const uint32_t *)dSt,
-               sk->t.checksum ? 1 : 0, dCodes, (const uint32_t *)dRefused);
-    }
+    if (const int e = seekDecodeList(c, sk, d.dList, maxFrameReads, d, "k_rec_scan", 1u, dWork, workCapacity)) return e;
     LAUNCH(c, "k_rec_measure", k_rec_measure, dim3((nRecords + 3) / 4), dim3(256), 0, (const ZsRecReq *)dReqs, (const uint64_t *)dReadAt, (const uint64_t *)dWorkAt,
-           (const uint64_t *)dHeadsBefore, nRecords, maxFrameReads, workCapacity, (const uint64_t *)dListAt, (const uint32_t *)dCodes, (const uint8_t *)dWork, (uint32_t)delim,
+           (const uint64_t *)dHeadsBefore, nRecords, maxFrameReads, workCapacity, (const uint64_t *)d.dListAt, (const uint32_t *)d.dCodes, (const uint8_t *)dWork, (uint32_t)delim,
            dStart, dLength, dStatus);
     if (const int e = scanOffsets(c, "k_layout_outputs", (const uint64_t *)dLength, nullptr, nRecords, align, nullptr, dDstOffsets)) return e;
     LAUNCH(c, "k_rec_copy", k_rec_copy, dim3(nRecords), dim3(256), 0, (const uint8_t *)dWork, (const uint64_t *)dStart, (const uint64_t *)dLength, (const uint64_t *)dDstOffsets,

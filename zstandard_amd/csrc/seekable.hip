@@ -19,7 +19,10 @@
 // arrays (zsmi_compressSeekableFramesResident*) cleans the sizes with k_seek_guard, compresses through the body of the resident batch call
 // into staging sized for every split of the content, and shares the packing tail (seekPackArchive); a read whose frame numbers are a
 // device array (zsmi_seekableReadFramesResident) looks them up in the handle's device copy of the table, lays the outputs out with the
-// layout scan and decodes every request straight to its place - no union, no scratch: a frame named twice is decoded twice.
+// layout scan and decodes every request straight to its place - no union, no scratch: a frame named twice is decoded twice.  That
+// sequence is the frame-list decode (seekDecodeList), which every call that decodes frames by device numbers runs - records by number, the
+// searches, the record index, the frame filter; their shared checks (seekWindowCheck) and the host builds' window plan (seekCutWindows)
+// stand beside it.
 // Streams without a table (zsmi_openFrames*): the frame index (zsmi_index.h) - one entry a frame, read from the frames' own headers, on the
 // host by the serial walk, on the device by the k_index_* kernels - fills the same SeekTable, and the handle is the one above.
 
@@ -30,6 +33,7 @@
 #include "zsmi_ctx.h"
 #include "zsmi_index.h"           // the frame index of a stream without a table; the format's limits
 #include <algorithm>
+#include <cstdlib>
 #include <new>
 
 static const uint32_t kSeekSkippableMagic = 0x184D2A5Eu, kSeekableMagic = 0x8F92EAB1u;
@@ -1102,11 +1106,93 @@ extern "C" int zsmi_seekableReadFramesHost(zsmi_ctx *c, const zsmi_seekable *sk,
     return zsmi_seekableReadRangesHost(c, sk, offsets.data(), lengths.data(), nFrames, dst, dstCapacity, written, statuses);
 }
 
+// ---- what every read of an opened archive by frame numbers in DEVICE memory is made of: the frame-list decode and the window plan.  Stated
+// here once, beside the kernels they drive; records.hip, find.hip and the files built on it (findframes.hip, recindex.hip, filter.hip) call them ----
+// The words of a frame-list decode, a frame of F, `p` 8-aligned in the seekable scratch (seekListHead: their bytes): 64 bits - sizes [F],
+// places [F + 1]; verify records [F]; 32 bits - the list, decoder status, refusals, written, codes [F each], the call's code [1, padded to
+// 8 bytes].  A caller that owns one of these arrays points the word at its own before the call
+struct SeekListWords { uint64_t *dSizes, *dListAt; ZsSeekItem *dVerify; uint32_t *dList, *dSt, *dRefused, *dFrameWritten, *dCodes, *dCode; };
+static size_t seekListHead(size_t F) { return (2 * F + 1) * sizeof(uint64_t) + F * sizeof(ZsSeekItem) + ((5 * F + 1) * sizeof(uint32_t) + 7) / 8 * 8; }
+static SeekListWords seekListWords(void *p, size_t F)
+{
+    SeekListWords d;
+    d.dSizes = (uint64_t *)p; d.dListAt = d.dSizes + F; d.dVerify = (ZsSeekItem *)(d.dListAt + F + 1);
+    d.dList = (uint32_t *)(d.dVerify + F); d.dSt = d.dList + F; d.dRefused = d.dSt + F; d.dFrameWritten = d.dRefused + F; d.dCodes = d.dFrameWritten + F; d.dCode = d.dCodes + F;
+    return d;
+}
+// THE FRAME-LIST DECODE.  The F frames dList names (the caller's list, or d.dList, which the caller's kernel wrote), of d.dSizes bytes
+// each (k_seek_request_sizes, or the caller's own), into dDst[0, capacity): the layout scan of the sizes under the caller's label and
+// alignment leaves their places in d.dListAt [F + 1], k_seek_request_items writes the decode items into the context's item list - which
+// holds F items: the caller reserved it, with everything else, before it queued anything - and the verify records, every frame decodes
+// straight to its place through the body of zsmi_decompressBatchResident, planned for the table's largest Decompressed_Size, and
+// k_seek_verify leaves a code a frame in d.dCodes; d.dFrameWritten: the bytes each frame holds.  A number that names no frame is an empty
+// item; a frame named twice is two items, decoded twice.  F == 0: the scan lays d.dListAt[0] and nothing else is queued
+static int seekDecodeList(zsmi_ctx *c, const zsmi_seekable *sk, const uint32_t *dList, uint32_t F, const SeekListWords &d, const char *scanName, uint32_t align,
+                          void *dDst, uint64_t capacity)
+{
+    const ZsSeekEntry *dTable = (const ZsSeekEntry *)sk->dTable.p;
+    if (const int e = scanOffsets(c, scanName, (const uint64_t *)d.dSizes, nullptr, F, align, nullptr, d.dListAt)) return e;
+    if (F == 0) return 0;
+    LAUNCH(c, "k_seek_request_items", k_seek_request_items, dim3((F + 255u) / 256u), dim3(256), 0, dTable, sk->t.n, dList, F, (const uint64_t *)d.dListAt, capacity, (uint8_t *)dDst,
+           (ZsDecItem *)c->dItems.p, d.dVerify, d.dRefused, d.dFrameWritten);
+    CapStats caps;
+    caps.add(sk->maxDSize, F);
+    if (const int e = decodeItems(c, sk->dFrames, F, dDst, caps, d.dSt, &sk->sel)) return e;
+    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((F + 15) / 16), dim3(64), 0, (const ZsSeekItem *)d.dVerify, F, (const uint32_t *)d.dSt, sk->t.checksum ? 1 : 0, d.dCodes,
+           (const uint32_t *)d.dRefused);
+    return 0;
+}
+// the content of frames [firstFrame, firstFrame + frameCount): what a window of them takes in a work buffer, end to end
+extern "C" size_t zsmi_seekableFindWorkBound(const zsmi_seekable *sk, uint32_t firstFrame, uint32_t frameCount)
+{
+    if (!sk || (uint64_t)firstFrame + frameCount > sk->t.n) return 0;
+    return (size_t)(sk->t.dOff[(size_t)firstFrame + frameCount] - sk->t.dOff[firstFrame]);
+}
+// The head of the checks of every call that decodes a window of an archive into a work buffer, in the headers' order: the context, the
+// handle and `nulls` - the call's own arrays, one of them null -, the device, ruleCheck() - the call's own rule, the handle known to be
+// there -, the window inside the archive, the work buffer (ownWork: a host form, which brings its own)
+template <class RuleCheck>
+static int seekWindowCheck(const zsmi_ctx *c, const zsmi_seekable *sk, bool nulls, RuleCheck ruleCheck, uint32_t firstFrame, uint32_t frameCount, bool ownWork, const void *work,
+                           uint64_t workCapacity)
+{
+    if (!c) return ZSMI_error_init_missing;
+    if (!sk || nulls) return ZSMI_error_GENERIC;
+    if (sk->device != c->device) return ZSMI_error_parameter_unsupported;
+    if (const int e = ruleCheck()) return e;
+    if ((uint64_t)firstFrame + frameCount > sk->t.n) return ZSMI_error_parameter_outOfBound;
+    const uint64_t bound = zsmi_seekableFindWorkBound(sk, firstFrame, frameCount);
+    if (!ownWork && bound && !work) return ZSMI_error_GENERIC;
+    if (!ownWork && workCapacity < bound) return ZSMI_error_dstSize_tooSmall;
+    return 0;
+}
+// THE WINDOW PLAN of the host forms that decode a whole archive through a work buffer of the context's: windows of consecutive frames, in
+// ascending order, of at most `limit` bytes of content each, cut wherever the table allows - a longer frame is a window of its own - with
+// the most bytes and the most frames a window holds: what the call reserves before the first window is queued
+struct SeekWindows { std::vector<std::pair<uint32_t, uint32_t>> list; uint64_t most = 0; uint32_t mostFrames = 0; };      // list: {firstFrame, frameCount}
+static SeekWindows seekCutWindows(const zsmi_seekable *sk, uint64_t limit)
+{
+    SeekWindows w;
+    const uint32_t N = sk->t.n;
+    for (uint32_t f = 0; f < N;) {
+        uint32_t g = f + 1;
+        while (g < N && sk->t.dOff[g + 1] - sk->t.dOff[f] <= limit) g++;
+        w.list.push_back({ f, g - f });
+        w.most = std::max(w.most, sk->t.dOff[g] - sk->t.dOff[f]); w.mostFrames = std::max(w.mostFrames, g - f);
+        f = g;
+    }
+    return w;
+}
+static uint64_t seekWindowLimit()
+{
+#ifdef ZSMI_DEBUG_HOOKS
+    if (const char *e = getenv("ZSMI_ARCHIVE_WINDOW")) { const long long v = atoll(e); if (v > 0) return (uint64_t)v; }      // the tests' way to many windows over a small archive
+#endif
+    return 256ull << 20;
+}
+
 // records by numbers that are DEVICE memory: nothing is copied to the host, nothing waited for, no pinned buffer touched.  The requests'
-// sizes come from the handle's device table (k_seek_request_sizes), their places are the layout scan of zsmi_layoutOutputsDevice over them,
-// k_seek_request_items writes the decode items into c->dItems and the verify records; every request decodes straight to its place through
-// the body of zsmi_decompressBatchResident, planned for the table's largest Decompressed_Size; k_seek_verify leaves dStatus.  A frame
-// named twice is two items: decoded twice.
+// sizes come from the handle's device table (k_seek_request_sizes); the rest is the frame-list decode on the caller's list, with the
+// caller's places - the layout scan of zsmi_layoutOutputsDevice - written and status arrays.
 extern "C" int zsmi_seekableReadFramesResident(zsmi_ctx *c, const zsmi_seekable *sk, const uint32_t *dFrameIndex, uint32_t nFrames, uint32_t align,
                                                void *dDst, uint64_t dstCapacity, uint64_t *dDstOffsets, uint32_t *dWritten, uint32_t *dStatus)
 {
@@ -1116,24 +1202,11 @@ extern "C" int zsmi_seekableReadFramesResident(zsmi_ctx *c, const zsmi_seekable 
     if (align == 0 || align > 4096 || (align & (align - 1))) return ZSMI_error_parameter_outOfBound;
     if (nFrames && dstCapacity && !dDst) return ZSMI_error_GENERIC;
     if (const int e = c->bind()) return e;
-    // device words: the requests' sizes [nFrames] (64 bits), verify records [nFrames]; decoder status [nFrames], refusals [nFrames]
-    if (!c->seek.dMeta.reserve((size_t)nFrames * (sizeof(uint64_t) + sizeof(ZsSeekItem) + 2 * sizeof(uint32_t))) ||
-        !c->dItems.reserve(sizeof(ZsDecItem) * (size_t)nFrames)) return ZSMI_error_memory_allocation;
-    uint64_t *dSizes = (uint64_t *)c->seek.dMeta.p;
-    ZsSeekItem *dVerify = (ZsSeekItem *)(dSizes + nFrames);
-    uint32_t *dSt = (uint32_t *)(dVerify + nFrames), *dRefused = dSt + nFrames;
-    const ZsSeekEntry *dTable = (const ZsSeekEntry *)sk->dTable.p;
-    const uint32_t grid = (nFrames + 255) / 256;
-    if (nFrames) LAUNCH(c, "k_seek_request_sizes", k_seek_request_sizes, dim3(grid), dim3(256), 0, dTable, sk->t.n, dFrameIndex, nFrames, dSizes);
-    if (const int e = scanOffsets(c, "k_layout_outputs", (const uint64_t *)dSizes, nullptr, nFrames, align, nullptr, dDstOffsets)) return e;
-    if (nFrames == 0) return c->launched();
-    LAUNCH(c, "k_seek_request_items", k_seek_request_items, dim3(grid), dim3(256), 0, dTable, sk->t.n, dFrameIndex, nFrames, (const uint64_t *)dDstOffsets, dstCapacity,
-           (uint8_t *)dDst, (ZsDecItem *)c->dItems.p, dVerify, dRefused, dWritten);
-    CapStats caps;
-    caps.add(sk->maxDSize, nFrames);
-    if (const int e = decodeItems(c, sk->dFrames, nFrames, dDst, caps, dSt, &sk->sel)) return e;
-    LAUNCH(c, "k_seek_verify", k_seek_verify, dim3((nFrames + 15) / 16), dim3(64), 0, (const ZsSeekItem *)dVerify, nFrames, (const uint32_t *)dSt, sk->t.checksum ? 1 : 0,
-           dStatus, (const uint32_t *)dRefused);
+    if (!c->seek.dMeta.reserve(seekListHead(nFrames)) || !c->dItems.reserve(sizeof(ZsDecItem) * (size_t)nFrames)) return ZSMI_error_memory_allocation;
+    SeekListWords d = seekListWords(c->seek.dMeta.p, nFrames);
+    d.dListAt = dDstOffsets; d.dFrameWritten = dWritten; d.dCodes = dStatus;
+    if (nFrames) LAUNCH(c, "k_seek_request_sizes", k_seek_request_sizes, dim3((nFrames + 255) / 256), dim3(256), 0, (const ZsSeekEntry *)sk->dTable.p, sk->t.n, dFrameIndex, nFrames, d.dSizes);
+    if (const int e = seekDecodeList(c, sk, dFrameIndex, nFrames, d, "k_layout_outputs", align, dDst, dstCapacity)) return e;
     return c->launched();
 }
 
